@@ -46,6 +46,11 @@ PEAK_VALU_LANE_OPS = 78.6e12      # 256 CU x 4 SIMD x 32 lanes x 2.4 GHz: what t
 PEAK_HBM_GBS = 8000.0             # MI355X_MICROARCH.md (spec)
 PROFILE_ROUND = "r04"   # the round whose committed counter profiles (profiles/pmc_<round>_cfg<c>.json) feed `roofline.executed`
 CENSUS_FILE = os.path.join(ROOT, "profiles", "census_r03.json")
+# --dump-outputs: an image larger than DUMP_MAX_BYTES is written as a fixed sample of DUMP_SAMPLE_PIXELS pixels (seed
+# DUMP_SAMPLE_SEED: the same pixels for the same frame size) beside their row-major indices, 48 MB in all
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21
+DUMP_SAMPLE_SEED = 0x5DF0D0
 
 
 def pcg_hash(x):
@@ -255,6 +260,26 @@ def cpu_baseline(config=HEADLINE, width=None, height=None, max_seconds=20.0):
     }
 
 
+def dump_image(directory, img):
+    """--dump-outputs: the H x W x 4 image the caller of the timed path received in its last step, as float32 .npy under
+    `directory` -- whole (image.npy) when it fits DUMP_MAX_BYTES, else a seeded sample of its pixels (image.npy, N x 4) and their
+    indices y * W + x (image_pixel_index.npy, float64).  Returns {file name: shape} for the result line."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    h, w, c = img.shape
+    arrays = {"image": img}
+    if img.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=DUMP_SAMPLE_PIXELS, replace=False))
+        arrays = {"image": img.reshape(h * w, c)[idx], "image_pixel_index": idx.astype(np.float64)}
+    written = {}
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        written[name + ".npy"] = list(arr.shape)
+    return written
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -291,6 +316,9 @@ def parse_args(argv=None):
                     help="N > 1: f16 = strips and image in the reference's RGBA16F target format (7 B/pixel on the links); f32 = lossless fp32 (13 B/pixel)")
     ap.add_argument("--frames-in-flight", type=int, default=3, help="N > 1: handles / streams the frames alternate between")
     ap.add_argument("--dry-launch", action="store_true", help="start the ranks, let each report its environment over gloo, touch no GPU (CPU test of the launcher)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the image of the last timed step to DIR/*.npy (float32; a fixed sample of its pixels "
+                         "when it is larger than 64 MB) for comparing two builds output for output")
     return ap.parse_args(argv)
 
 
@@ -386,6 +414,9 @@ def main(argv=None):
     if a.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         return 2
+    if a.steps < 1 or a.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return spawn_ranks(a, argv)      # BEFORE any GPU call (nothing below this line has run yet)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -414,8 +445,9 @@ def run_config1(a):
         ref, rst, tot = po.render(cfg["scene"], f, stats=True, nthreads=cores)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        po.render(cfg["scene"], f, nthreads=cores)
+        last = po.render(cfg["scene"], f, nthreads=cores)
     elapsed = time.perf_counter() - t0
+    dumped = dump_image(a.dump_outputs, last[0]) if a.dump_outputs else None
     t1 = time.perf_counter()
     po.render(cfg["scene"], f, nthreads=1)
     single = time.perf_counter() - t1
@@ -429,6 +461,8 @@ def run_config1(a):
                          "sample": "oracle (scalar C++ restatement, g++ -O2 -ffp-contract=off), the whole %dx%d frame, %d renders, %.2f s; one thread: %.3f Mrays/s"
                                    % (W, H, a.steps, elapsed, rays / single / 1e6)},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     try:
         import torch
 
@@ -709,6 +743,10 @@ def run(a, world):
     enqueue_ms = (time.perf_counter() - t0) / max(1, a.steps) * 1e3  # host time to enqueue a step
     fence()
     elapsed = time.perf_counter() - t0
+    # the image of the last timed step, before anything below renders into the same buffers (rank 0 holds the assembled frame)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_image(a.dump_outputs, images[(a.steps - 1) % depth].float().cpu().numpy())
 
     # rays are a property of the frames, independent of timing: counted outside the timed region, from
     # the kernels' own counters; N > 1: the duration of this rank's k_pixel launch alone comes from a
@@ -893,6 +931,8 @@ def run(a, world):
         out["host_enqueue_ms_per_step"] = enqueue_ms
         if verified is not None:
             out["verified"] = verified
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if not distributed and not a.no_second_pass:
             # Not the headline: the same sweep with TWO frames in flight inside the one handle (sdfr_set_frames_in_flight(2): two
             # internal streams and workspaces, frames rendered into two images in turn), measured after the timed region.  It shows

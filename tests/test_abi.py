@@ -1,6 +1,7 @@
 """CPU tier: the C-ABI library builds for gfx950, loads, exports every symbol that
 include/sdfr.h declares, and refuses to work without a GPU (no CPU fallback)."""
 import ctypes
+import json
 import os
 import re
 
@@ -33,11 +34,10 @@ def test_scene_list_matches_reference_stems(lib):
     assert sp.scene_names() == ["fast_sphere", "cube_sea", "labyrinth", "fractal", "lense", "gems", "light_shadows", "cube", "gyroid",
                                 "basic_transparency", "basic_clouds", "coordinate_material", "distortion", "table", "sierpinski", "neon",
                                 "fractal2", "shell", "spiral", "terrain", "tiling", "tree"]
-    # every name is a stem of the reference's scenes directory (SceneManager.cpp:142-158)
-    ref = "/root/reference/Engine/shader/scenes"
-    if os.path.isdir(ref):
-        stems = {f[len("sdf_scene_"):-5] for f in os.listdir(ref) if f.endswith(".hlsl")}
-        assert set(sp.scene_names()) == stems  # all 22 scenes of the reference
+    # every name is a stem of the reference's scenes directory (SceneManager.cpp:142-158), as recorded in the fixture read from it
+    with open(os.path.join(ROOT, "tests", "golden", "reference", "var_tags.json")) as fh:
+        stems = set(json.load(fh)["scenes"])
+    assert set(sp.scene_names()) == stems  # all 22 scenes of the reference
 
 
 def test_no_cpu_fallback_without_gpu(lib):

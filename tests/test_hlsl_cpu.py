@@ -1,34 +1,24 @@
 """CPU tier: scenes in the REFERENCE'S OWN DIALECT (sdfr_load_scene_hlsl; csrc/sdfr_hlsl.h, sdfr_hlsl.cpp).
 
 The plugin the reference exposes for the raymarch path is an .hlsl scene file (pshader_sdf.hlsl:79-84; Application.cpp:229,320).
-* every one of the 22 files under /root/reference/Engine/shader/scenes -- read here, in the build container, at test time; they
-  are never copied into this repository and the tests skip where the directory is absent -- translates, compiles for gfx950
-  (hiprtc, no device needed) and, built for the CPU around the product's per-pixel pipeline (tests/hostsim), renders the same
-  bits as the oracle's restatement of that scene: pixels and ray / step / hit counters, from two cameras, with the scene's
-  variables moved.  That is also a pin of the oracle's 22 scene restatements by the reference's own scene text;
+* every one of the 22 files under the reference's Engine/shader/scenes, translated from its dialect and rendered on the CPU around
+  the product's per-pixel pipeline (tests/hostsim), from two cameras, with the scene's variables moved: the pixels and ray / step /
+  hit counters it rendered are frozen by digest in tests/golden/reference/scene_renders.json (tools/make_reference_fixtures.py, which
+  reads the files and checks them against the oracle bit for bit).  The oracle's 22 scene restatements reproduce them: a pin of
+  the oracle by the reference's own scene text;
 * the textual pass, rule by rule, on builder-written snippets;
 * two builder-written scenes in the dialect (sdf_playground_amd/scenes/pendulum.hlsl, rounded.hlsl) against their C++ twins."""
-import glob
+import json
 import os
-from concurrent.futures import ThreadPoolExecutor
+import sys
 
 import numpy as np
 import pytest
 
-REF_SCENES = "/root/reference/Engine/shader/scenes"
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
 SCENES_DIR = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "scenes")
 FOVY = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="the reference tree is not here (GPU box): its scene files are read, never copied")
-
-
-def _ref_names():
-    return [os.path.basename(f)[len("sdf_scene_"):-len(".hlsl")] for f in sorted(glob.glob(os.path.join(REF_SCENES, "sdf_scene_*.hlsl")))]
-
-
-def _ref_text(name):
-    with open(os.path.join(REF_SCENES, "sdf_scene_%s.hlsl" % name)) as f:
-        return f.read()
 
 
 # ---- the textual pass -------------------------------------------------------------------------------------------
@@ -60,61 +50,20 @@ def test_a_scene_that_does_not_compile_reports_the_compiler_s_words():
 
 
 # ---- the reference's own scene files ---------------------------------------------------------------------------
-@needs_reference
-def test_all_22_reference_scene_files_are_there():
-    assert len(_ref_names()) == 22
+def test_reference_scene_files_render_the_oracle_s_bits(oracle):
+    from make_reference_fixtures import frame_from_dict, render_digests
 
-
-@needs_reference
-def test_reference_scene_files_compile_for_gfx950():
-    """sdfr_check_scene_hlsl on every file as it is (hiprtc; no device): ~1.5 s each"""
-    import sdf_playground_amd as sp
-
-    failed = {}
-    for name in _ref_names():
-        ok, log = sp.check_scene_hlsl(_ref_text(name))
-        if not ok:
-            failed[name] = [l for l in log.splitlines() if "error" in l][:4]
-    assert not failed, failed
-
-
-@pytest.fixture(scope="module")
-def reference_scene_libs():
-    import hostsim
-
-    names = _ref_names()
-    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        libs = list(ex.map(lambda n: hostsim.build_hlsl("ref_" + n, _ref_text(n)), names))
-    return dict(zip(names, libs))
-
-
-@needs_reference
-def test_reference_scene_files_render_the_oracle_s_bits(oracle, reference_scene_libs):
-    import hostsim
-
-    rng = np.random.default_rng(2026)
-    for name, (L, slots) in reference_scene_libs.items():
+    with open(os.path.join(HERE, "golden", "reference", "scene_renders.json")) as fh:
+        scenes = json.load(fh)["scenes"]
+    assert len(scenes) == 22 and set(scenes) <= set(oracle.scene_names())
+    for name, e in sorted(scenes.items()):
         table = oracle.var_table(name)
         # the variable slots the generated class reads (order of first appearance in the text) are the oracle's
-        assert slots == [r[0] for r in sorted(table, key=lambda r: r[6]) if r[6] >= 0], name
-        heavy = name in ("tree", "terrain", "distortion", "tiling")
-        w, h = (40, 28) if heavy else (72, 48)
-        for k in range(2):
-            if k == 0:
-                f = oracle.default_frame(name, w, h, stime=0.5)
-            else:
-                eye = (float(rng.uniform(-5, 5)), float(rng.uniform(0.4, 5)), float(rng.uniform(-6, -2)))
-                f = oracle.default_frame(name, w, h, basis=oracle.camera_lookat(eye, (0.0, 1.0, 0.0), FOVY, np.float32(w) / np.float32(h)), stime=1.7)
-                for vname, mn, mx, _start, _step, _v, slot in table:
-                    if slot >= 0:
-                        f.scene_var[slot] = float(np.float32(rng.uniform(mn, mx)))
-                f.max_cost_default = 9
-                f.debug_ny, f.debug_y = (1.0, 0.6) if name == "cube" else (0.0, 0.0)  # once through the debug-plane build
-            ref, rst, _ = oracle.render(name, f, stats=True)
-            img, st = hostsim.render_hlsl(L, hostsim.frame_from_oracle(f))
-            same = np.array_equal(img.view(np.uint32), ref.view(np.uint32)) or np.array_equal(img, ref, equal_nan=True)
-            assert same, (name, k, int((img.view(np.uint32) != ref.view(np.uint32)).any(axis=2).sum()))
-            assert np.array_equal(st, rst), (name, k)
+        assert e["slots"] == [r[0] for r in sorted(table, key=lambda r: r[6]) if r[6] >= 0], name
+        assert len(e["cases"]) == 2
+        for k, case in enumerate(e["cases"]):
+            ref, rst, _ = oracle.render(name, frame_from_dict(case["frame"]), stats=True)
+            assert render_digests(ref, rst) == {d: case[d] for d in ("rgba_sha256", "stats_sha256")}, (name, k)
 
 
 # ---- builder-written scenes in the dialect -----------------------------------------------------------------------

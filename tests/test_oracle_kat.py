@@ -2,6 +2,7 @@
 (UnitTest/UnitTest.cpp), the reference's Camera/Math3D compiled here (oracle/_ref), the
 camera golden of SURVEY.md 8(c), and analytic known answers for the restated library."""
 import math
+import os
 
 import numpy as np
 import pytest
@@ -87,21 +88,14 @@ def test_camera_startup_golden(oracle):
 
 
 def test_camera_matches_compiled_reference(oracle):
-    ref = oracle.ref_camera_lib()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    rng = np.random.default_rng(7)
-    for k in range(200):
-        eye = rng.uniform(-8, 8, 3).astype(np.float32)
-        tgt = rng.uniform(-8, 8, 3).astype(np.float32)
-        fovy = np.float32(rng.uniform(0.3, 2.0))
-        aspect = np.float32(rng.uniform(0.5, 2.5))
-        roll = np.float32(0.0 if k % 2 == 0 else rng.uniform(-1, 1))
+    """the reference's own Camera.cpp / Math3D.cpp (compiled as oracle/_ref) on 200 seeded cameras, frozen in
+    tests/golden/reference/camera.npz by tools/make_reference_fixtures.py: the oracle's basis equals it bit for bit"""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "camera.npz"))
+    assert g["basis"].shape == (200, 2, 12)
+    for k in range(len(g["eye"])):
         for is_dir in (0, 1):
-            out = np.zeros(12, np.float32)
-            ref.ref_camera_basis(eye.ctypes.data, tgt.ctypes.data, is_dir, fovy, aspect, roll, out.ctypes.data)
-            mine = (oracle.camera_direction if is_dir else oracle.camera_lookat)(eye, tgt, fovy, aspect, roll)
-            assert np.array_equal(mine.ravel().view(np.uint32), out.view(np.uint32))
+            mine = (oracle.camera_direction if is_dir else oracle.camera_lookat)(g["eye"][k], g["target"][k], g["fovy"][k], g["aspect"][k], g["roll"][k])
+            assert np.array_equal(mine.ravel().view(np.uint32), g["basis"][k, is_dir].view(np.uint32)), (k, is_dir)
 
 
 # ---- analytic known answers --------------------------------------------------------

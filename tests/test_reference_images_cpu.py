@@ -1,11 +1,12 @@
 """The oracle against the reference's OWN rendered frames (missing item 1).
 
-The reference holds screenshots of this very path: /root/reference/Images/*.png, 1200 x 800, taken from its window
+The reference holds screenshots of this very path: Images/*.png, 1200 x 800, taken from its window
 (README.md:30-104; window size, fovy 60 deg, aspect 1.5, roll 0: Engine/Application.cpp:39-40, 214-224).  Camera and time
 are not recorded, but they are seven numbers: tools/fit_reference_images.py found them by least squares on the oracle's
 frame pushed through the oracle's HDR::process (fp16 target, bloom, tone map, unorm8), and tests/golden/reference_images.json
 keeps them with the statistics of |oracle - screenshot|.  This test re-renders at the committed parameters and asserts the
-statistics -- with the screenshots read where they lie (never copied; skipped where the reference tree is absent).
+statistics on a fixed sample of each screenshot, every 16th row (tests/golden/reference/screenshots/: RGB and edge flag, made
+by tools/make_reference_fixtures.py; `sample_stats` beside the full-frame `stats`).
 
 What this pins that nothing else does: oracle/driver.h (ray generation, march, normal, shading, shadow / reflection /
 refraction rays, queue order), sdf_lib.h (primitives, operators, checker filter, sky), noise.h (the sky and the marble are
@@ -21,11 +22,10 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
-IMAGES = "/root/reference/Images"
-pytestmark = pytest.mark.skipif(not os.path.isdir(IMAGES), reason="the reference tree is not here (GPU box): its screenshots are read, never copied")
 
 with open(os.path.join(HERE, "golden", "reference_images.json")) as _f:
     FITS = json.load(_f)["images"]
+SAMPLES = os.path.join(HERE, "golden", "reference", "screenshots")
 
 
 def _params(e):
@@ -39,8 +39,12 @@ def test_oracle_reproduces_the_reference_s_screenshot(oracle, name):
     e = FITS[name]
     assert fr.TARGETS[name][0] == e["file"] and fr.TARGETS[name][1] == e["scene"] and fr.TARGETS[name][3] == e.get("variables", {})
     assert fr.ROWS_FROM.get(name, 0) == e.get("rows_from", 0)  # (spiral.png: from the horizon down, its sky is an older one)
-    stats, _ldr, _d = fr.compare(name, _params(e), variables=e.get("variables", {}))
-    want = e["stats"]
+    # the sample stands for the whole screenshot: its statistics (committed) are those of the full frame (committed by the fit).
+    # Both numbers are stored, so this runs no code: it attests that the fixture was representative when it was made
+    # (tools/make_reference_fixtures.py); what the oracle computes today is checked below.
+    full, want = e["stats"], e["sample_stats"]
+    assert abs(full["mean_abs_err"] - want["mean_abs_err"]) < 0.02 and abs(full["within_3"] - want["within_3"]) < 0.003, (full, want)
+    stats, _d = fr.compare_sample(name, _params(e), SAMPLES, variables=e.get("variables", {}))
     # the committed statistics are reproduced (same oracle, same screenshot) ...
     assert abs(stats["mean_abs_err"] - want["mean_abs_err"]) < 0.02 and abs(stats["within_3"] - want["within_3"]) < 0.003, (stats, want)
     # ... and they say "agrees": all pixels, edges included.  (lense1.png carries its own limits: four bounces of reflection and refraction
@@ -50,7 +54,7 @@ def test_oracle_reproduces_the_reference_s_screenshot(oracle, name):
     assert stats["mean_abs_err"] < lim["mean_abs_err"], stats
     assert stats["within_3"] > lim["within_3"] and stats["within_8"] > lim["within_8"], stats
     assert stats["flat_within_8"] > lim["flat_within_8"], stats
-    assert stats["rays"] == want["rays"]
+    assert stats["rays"] == full["rays"]
 
 
 def test_the_statistic_tells_a_wrong_scene_from_the_right_one(oracle):
@@ -62,7 +66,7 @@ def test_the_statistic_tells_a_wrong_scene_from_the_right_one(oracle):
     e = FITS["multi-lights"]
     p = _params(e)
     p[5] = 7.85  # today's file puts the lights where the screenshot has them at this time (fitted the same way)
-    stats, _ldr, _d = fr.compare("multi-lights-todays-file", p)
+    stats, _d = fr.compare_sample("multi-lights-todays-file", p, SAMPLES)
     assert stats["mean_abs_err"] > 10.0 and stats["within_3"] < 0.3, stats
 
 
@@ -71,9 +75,9 @@ def test_a_camera_a_hundredth_off_is_noticed(oracle):
 
     e = FITS["sphere"]
     p = _params(e)
-    good, _l, _d = fr.compare("sphere", p)
+    good, _d = fr.compare_sample("sphere", p, SAMPLES)
     p[0] += 0.01
-    off, _l, _d = fr.compare("sphere", p)
+    off, _d = fr.compare_sample("sphere", p, SAMPLES)
     assert good["within_3"] > 0.999 and off["within_3"] < 0.99 and off["mean_abs_err"] > 5 * good["mean_abs_err"]
 
 
@@ -90,5 +94,5 @@ def test_moved_sliders_sit_on_their_grid(oracle, name):
     for k, v in e["variables"].items():
         step = table[k][4]
         assert abs(v / step - round(v / step)) < 1e-3 and table[k][1] <= v <= table[k][2], (k, v)
-    defaults, _l, _d = fr.compare(name, _params(e), variables={})
+    defaults, _d = fr.compare_sample(name, _params(e), SAMPLES, variables={})
     assert defaults["mean_abs_err"] > 3.0 and defaults["within_3"] < 0.9, defaults

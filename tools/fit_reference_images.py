@@ -8,7 +8,8 @@ finds them by least squares on the oracle's frame pushed through the oracle's re
 (oracle/postprocess.h), and then reports how far apart the two images are.  The fitted parameters are committed in
 tests/golden/reference_images.json; tests/test_reference_images_cpu.py re-renders at them and asserts the statistics.
 
-The screenshots are read where they lie and never copied.  Nothing here is product code; the oracle is the renderer.
+The screenshots are read where they lie; the tests use the fixed sample of them stored as data in
+tests/golden/reference/screenshots/ (tools/make_reference_fixtures.py).  Nothing here is product code; the oracle is the renderer.
 
   python tools/fit_reference_images.py sphere --init ex ey ez yaw pitch stime [--spread ...] [--save /tmp/prefix]
 (global_search / refine / scan_time are the pieces the five committed fits were made with: a quasi-random search over the camera box
@@ -301,6 +302,74 @@ class FullObjective:
 ROWS_FROM = {"spiral": 256}
 
 
+def edges(ref8):
+    """An edge pixel is one whose 3 x 3 neighbourhood in the SCREENSHOT spans more than 24/255: a sub-pixel shift of a
+    silhouette or a checker line changes such a pixel by the whole contrast, whatever the renderer."""
+    from scipy.ndimage import maximum_filter, minimum_filter
+
+    g = ref8.max(axis=2)
+    return (maximum_filter(g, 3) - minimum_filter(g, 3)) > 24
+
+
+def statistics(ldr, ref8, edge, totals):
+    """|oracle - screenshot| over matching pixels (ldr, ref8: ... x 3 in 1/255; edge: ...), and the oracle frame's rays."""
+    diff = np.abs(ldr.astype(np.int32) - ref8.astype(np.int32))
+    d = diff.max(axis=-1)  # per pixel: largest channel difference, in 1/255
+    flat = ~edge
+    stats = {
+        "mean_abs_err": float(diff.mean()),
+        "within_3": float((d <= 3).mean()),
+        "within_8": float((d <= 8).mean()),
+        "flat_fraction": float(flat.mean()),
+        "flat_within_3": float((d[flat] <= 3).mean()),
+        "flat_within_8": float((d[flat] <= 8).mean()),
+        "flat_mean_abs_err": float(diff[flat].mean()),
+        "p99_flat": float(np.percentile(d[flat], 99)),
+        "rays": int(totals[1]),
+    }
+    return stats, d
+
+
+# The screenshots are data the tests need where the reference tree is absent: tests/golden/reference/screenshots/<file>.npz keeps a
+# fixed sample of each (tools/make_reference_fixtures.py) -- every SAMPLE_ROWS-th row of the compared rows, whole, with the screenshot's
+# RGB there (each pixel stored as its difference to the pixel on its left, mod 256: a row of a rendered frame is smooth, so it
+# compresses -- PNG's Sub filter) and the edge flag of each pixel (from the full screenshot).  compare_sample() is compare() on those
+# rows.  Every 16th row: 50 rows of 1200 pixels per screenshot, within 0.002 of the full frame's within_3 on every screenshot.
+SAMPLE_ROWS = 16
+
+
+def sample_rows(rows):
+    """The rows of the fixed sample among `rows` compared rows (the rows from ROWS_FROM down)."""
+    return slice(SAMPLE_ROWS // 2, rows, SAMPLE_ROWS)
+
+
+def sample_name(file):
+    return os.path.splitext(file)[0].replace(" ", "_") + ".npz"
+
+
+def encode_sample(rgb, edge):
+    """The stored form of a sample (rows x W x 3 uint8 RGB, rows x W edge flags)."""
+    rgb = rgb.astype(np.uint8)
+    return {"rgb_delta": np.diff(rgb, axis=1, prepend=np.zeros_like(rgb[:, :1])), "edge": edge.astype(bool)}
+
+
+def load_sample(directory, file):
+    """(rgb, edge) of the stored sample of screenshot `file` under `directory`."""
+    with np.load(os.path.join(directory, sample_name(file))) as z:
+        return np.cumsum(z["rgb_delta"], axis=1, dtype=np.uint8), z["edge"]
+
+
+def compare_sample(name, p, directory, variables=None):
+    """compare() on the stored sample of the screenshot: the oracle's full frame (bloom needs all of it), read at the sample rows."""
+    file, scene, _g, _v = TARGETS[name]
+    if variables is None:
+        variables = _v
+    r0 = ROWS_FROM.get(name, 0)
+    ldr, _hdr, totals = render_full(scene, p, variables)
+    rgb, edge = load_sample(directory, file)
+    return statistics(ldr[r0:][sample_rows(H - r0)], rgb, edge, totals)
+
+
 def compare(name, p, variables=None, save=None):
     """Statistics of |oracle through HDR::process - screenshot| at the fitted parameters, on the full 1200 x 800 frame (from row
     ROWS_FROM[name] down, for a screenshot listed there)."""
@@ -310,27 +379,8 @@ def compare(name, p, variables=None, save=None):
     r0 = ROWS_FROM.get(name, 0)
     ref8 = load_reference(name).astype(np.int32)[r0:]
     ldr, hdr, totals = render_full(scene, p, variables)
-    ldr, hdr = ldr[r0:], hdr[r0:]
-    d = np.abs(ldr.astype(np.int32) - ref8).max(axis=2)  # per pixel: largest channel difference, in 1/255
-    sky = hdr[..., 3] == 0  # misses write alpha 0 only when use_hdr is off; keep a geometric notion instead
-    # an edge pixel is one whose 3 x 3 neighbourhood in the SCREENSHOT spans more than 24/255: a sub-pixel shift of a
-    # silhouette or a checker line changes such a pixel by the whole contrast, whatever the renderer
-    from scipy.ndimage import maximum_filter, minimum_filter
-
-    g = ref8.max(axis=2)
-    edge = (maximum_filter(g, 3) - minimum_filter(g, 3)) > 24
-    flat = ~edge
-    stats = {
-        "mean_abs_err": float(np.abs(ldr.astype(np.int32) - ref8).mean()),
-        "within_3": float((d <= 3).mean()),
-        "within_8": float((d <= 8).mean()),
-        "flat_fraction": float(flat.mean()),
-        "flat_within_3": float((d[flat] <= 3).mean()),
-        "flat_within_8": float((d[flat] <= 8).mean()),
-        "flat_mean_abs_err": float(np.abs(ldr.astype(np.int32) - ref8)[flat].mean()),
-        "p99_flat": float(np.percentile(d[flat], 99)),
-        "rays": int(totals[1]),
-    }
+    ldr = ldr[r0:]
+    stats, d = statistics(ldr, ref8, edges(ref8), totals)
     if save:
         from PIL import Image
 
