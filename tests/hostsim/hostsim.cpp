@@ -683,3 +683,97 @@ extern "C" long long hostsim_check_escape_rule(const char *scene, FrameU *frame,
 	}
 	return -2;
 }
+
+// Which step-shortcut traits a built-in scene declares (sdfr_pixel.h): 1 = ray_escapes, 2 = escapes_from, 4 = inline_escaped_shadows in
+// effect (declared, and the scene has a ray_escapes for it to act on).  -2: no such scene.
+template <class Scene>
+static int scene_rules()
+{
+	return (RayEscapes<Scene>::available ? 1 : 0) | (EscapesFrom<Scene>::available ? 2 : 0) | (InlineEscapedShadows<Scene>::value ? 4 : 0);
+}
+extern "C" int hostsim_scene_rules(const char *scene)
+{
+	switch (scene_index(scene))
+	{
+#define SDFR_RULES(I, S) case I: return scene_rules<S>();
+		SDFR_FOR_EACH_SCENE(SDFR_RULES)
+#undef SDFR_RULES
+	}
+	return -2;
+}
+
+// Every built-in scene's escapes_from() against a dense walk: from the distance it returns on, up to the range the caller gives it (a shadow
+// ray towards a point light ends there), the scene is farther than 0.002 (twice the largest dist_eps the library accepts).  Rays towards
+// points anywhere about the scenes and along directions up to 6e-4 shorter than unit vectors (a shadow ray towards a directional light,
+// range 100), starts up to 45 away, the scene's variables as the caller set them in *frame.  Returns the number of violations (-1: the scene
+// has no such rule); *fired: how many rays were given a finite distance.
+template <class Scene>
+static long long check_escapes_from(const FrameU &U, long long n, unsigned seed, long long *fired, float *witness)
+{
+	if constexpr (!EscapesFrom<Scene>::available) return -1;
+	else
+	{
+		unsigned long long state = seed * 2654435761ull + 7373ull;
+		auto rnd = [&]() {
+			state = state * 6364136223846793005ull + 1442695040888963407ull;
+			return (float)((state >> 40) & 0xffffff) / 16777216.f;
+		};
+		long long bad = 0, spoke = 0;
+		for (long long i = 0; i < n; ++i)
+		{
+			const float span = (i % 3 == 0) ? 45.f : ((i % 3 == 1) ? 8.f : 2.5f);
+			const vec3 s = V3((rnd() * 2.f - 1.f) * span, (rnd() * 2.f - 1.f) * ((i % 5 == 0) ? 14.f : 7.f), (rnd() * 2.f - 1.f) * span);
+			vec3 d;
+			float range;
+			if (i % 2 == 0)
+			{
+				d = V3(rnd() * 2.f - 1.f, rnd() * 2.f - 0.7f, rnd() * 2.f - 1.f);
+				if (i % 8 == 0) d = V3(1.f, 1.f, -2.f) + V3(rnd() - 0.5f, rnd() - 0.5f, rnd() - 0.5f) * ((i % 16 == 0) ? 0.f : 3.f); // the sun of most scenes
+				if (!(length(d) > 1e-3f)) continue;
+				d = normalize(d) * (1.f - rnd() * 6e-4f);
+				range = 100.f;
+			}
+			else
+			{
+				const vec3 to = V3((rnd() * 2.f - 1.f) * 6.f, (rnd() * 2.f - 1.f) * 5.f + 1.f, (rnd() * 2.f - 1.f) * 6.f);
+				if (!(length(to - s) > 0.3f)) continue;
+				d = normalize(to - s);
+				range = length(to - s) - 0.25f;
+			}
+			const float t0 = Scene::escapes_from(U, s, d, range);
+			if (!(t0 < 1e30f)) continue;
+			++spoke;
+			RayFlags f;
+			f.has_transparent = false;
+			f.is_shadow = true;
+			f.last_transparent_pos = V3s(0.f);
+			const typename Scene::RayInv R = Scene::ray_setup(U, d, f);
+			const float end = min1(range, 70.f);
+			for (float t = t0; t <= end; t += (t < 8.f ? 0.004f : 0.02f) + rnd() * 0.01f)
+			{
+				const vec3 p = mad(d, t, s);
+				if (!(Scene::dist(U, R, p, d, true) >= 0.002f))
+				{
+					if (bad == 0 && witness) { witness[0] = s.x; witness[1] = s.y; witness[2] = s.z; witness[3] = d.x; witness[4] = d.y; witness[5] = d.z; witness[6] = t; witness[7] = t0; witness[8] = range; }
+					++bad;
+					break;
+				}
+			}
+		}
+		if (fired) *fired = spoke;
+		return bad;
+	}
+}
+extern "C" long long hostsim_check_escapes_from(const char *scene, FrameU *frame, long long n, unsigned seed, long long *fired, float *witness)
+{
+	const int si = scene_index(scene);
+	if (si < 0) return -2;
+	frame_derive(*frame, si);
+	switch (si)
+	{
+#define SDFR_CHK(I, S) case I: return check_escapes_from<S>(*frame, n, seed, fired, witness);
+		SDFR_FOR_EACH_SCENE(SDFR_CHK)
+#undef SDFR_CHK
+	}
+	return -2;
+}

@@ -4,6 +4,7 @@ oracle's.  The rest of the suite runs with the shortcuts off (tests/conftest.py)
 import numpy as np
 import pytest
 
+from shortcut_scenes import ALL_SCENES, INLINE_ESCAPED_SHADOWS
 from test_gpu_parity import _setup
 
 pytestmark = pytest.mark.gpu
@@ -64,17 +65,24 @@ def test_cube_sea_shortcuts_change_no_pixel(renderer, oracle, view):
         renderer.setStepShortcuts(False)
 
 
-@pytest.mark.parametrize("scene,limits", [("labyrinth", dict(iter_count=256)), ("labyrinth", dict(extension_marble_reflection=0.25)),
-                                          ("fractal", dict(iter_count=512)), ("gems", dict(max_cost_default=9, extension_lights=7)),
-                                          ("tree", None), ("terrain", None), ("distortion", None), ("fast_sphere", None), ("cube", None), ("sierpinski", None),
-                                          ("basic_transparency", None), ("coordinate_material", None), ("table", None),
-                                          ("light_shadows", None), ("tiling", None), ("gyroid", None), ("fractal2", None), ("neon", None), ("spiral", None), ("shell", None), ("basic_clouds", None),
-                                          ("cube_sea", dict(max_cost_default=6))])
+# every scene with its limits: the parity tests' for the scenes with ray_escapes (one more case with the labyrinth's marble reflective),
+# configuration 5's for lense, whose rule is escapes_from
+SEVEN_VIEW_CASES = [("labyrinth", dict(iter_count=256)), ("labyrinth", dict(extension_marble_reflection=0.25)),
+                    ("fractal", dict(iter_count=512)), ("gems", dict(max_cost_default=9, extension_lights=7)),
+                    ("tree", None), ("terrain", None), ("distortion", None), ("fast_sphere", None), ("cube", None), ("sierpinski", None),
+                    ("basic_transparency", None), ("coordinate_material", None), ("table", None),
+                    ("light_shadows", None), ("tiling", None), ("gyroid", None), ("fractal2", None), ("neon", None), ("spiral", None), ("shell", None), ("basic_clouds", None),
+                    ("cube_sea", dict(max_cost_default=6)), ("lense", dict(iter_count=100, max_cost_default=9, extension_lights=7))]
+
+
+@pytest.mark.parametrize("scene,limits", SEVEN_VIEW_CASES)
 def test_scenes_with_an_escape_rule(renderer, oracle, scene, limits):
-    """every scene that declares ray_escapes(), at the parity tests' camera and from six more (looking up from the
-    floor, down from above, along the horizon, from under / on / a hair above the floor): shortcuts on changes no pixel, ray or hit count and adds no step"""
+    """every scene (those that declare ray_escapes() or escapes_from() and the rest), at the parity tests' camera and from six more (looking
+    up from the floor, down from above, along the horizon, from under / on / a hair above the floor): shortcuts on changes no pixel, ray or
+    hit count and adds no step"""
     import sdf_playground_amd as sp
 
+    assert {c[0] for c in SEVEN_VIEW_CASES} == set(ALL_SCENES) == set(sp.scene_names())
     try:
         f = _setup(renderer, oracle, scene, 0.75, limits=limits)
         # ... and from under the floor, exactly on it and a hair above it (round-2 review: rules that take the floor to be
@@ -106,7 +114,9 @@ def test_scenes_with_an_escape_rule(renderer, oracle, scene, limits):
         renderer.setStepShortcuts(False)
 
 
-@pytest.mark.parametrize("config,scene,saves", [("2", "cube_sea", 0.7), ("3", "labyrinth", 0.9), ("4", "fractal", 0.9), ("5g", "gems", 0.7), ("3r", "labyrinth", 0.9)])
+# lense (configuration 5): shortcuts on marched 0.783 - 0.785 of the steps of sweep frames 0, 5 and 11 when its threshold was set
+@pytest.mark.parametrize("config,scene,saves", [("2", "cube_sea", 0.7), ("3", "labyrinth", 0.9), ("4", "fractal", 0.9), ("5", "lense", 0.85), ("5g", "gems", 0.7),
+                                                ("3r", "labyrinth", 0.9)])
 def test_configurations_at_full_size_with_shortcuts(renderer, oracle, config, scene, saves):
     """the BASELINE configurations whose scene has an escape rule, as bench.py runs them (shortcuts on): every 24th pixel
     against the oracle, rays and hits too; the whole frame equals the frame with every step marched; steps are saved"""
@@ -187,18 +197,24 @@ def test_run_time_scene_with_an_escape_rule(renderer, oracle):
         renderer.setStepShortcuts(False)
 
 
-@pytest.mark.parametrize("bounces,slots", [(16, 8), (9, 8), (5, 8), (3, 8), (2, 8), (1, 8), (16, 4), (16, 1), (6, 3)])
-def test_delivered_shadow_rays_keep_budget_and_queue_length(renderer, oracle, bounces, slots):
-    """gems declares inline_escaped_shadows: with eight lights, a ray budget that ends among a floor pixel's shadow rays and a queue
-    shorter than their number, the HIP path renders the oracle's pixels, ray and hit counts (the CPU tier runs the same cases on
-    the host build: tests/test_shortcuts_cpu.py)."""
-    renderer.initShader("gems")
+DELIVERY_VIEWS = [((2.5, 2.0, 0.5), (0.0, 1.0, 0.0)), ((0.3, 0.4, -4.0), (0.0, 0.8, 0.0)), ((5.0, 6.0, 5.0), (0.0, 0.0, 0.0))]
+GEMS_BUDGETS = [(16, 8), (9, 8), (5, 8), (3, 8), (2, 8), (1, 8), (16, 4), (16, 1), (6, 3)]
+
+
+@pytest.mark.parametrize("scene,bounces,slots", [pytest.param("gems", b, s, id="%d-%d" % (b, s)) for b, s in GEMS_BUDGETS] +
+                         [(scene, b, s) for scene in sorted(INLINE_ESCAPED_SHADOWS - {"gems"}) for b, s in [(9, 8), (1, 8), (16, 1), (6, 3)]])
+def test_delivered_shadow_rays_keep_budget_and_queue_length(renderer, oracle, scene, bounces, slots):
+    """every scene with inline_escaped_shadows in effect (tests/shortcut_scenes.py): with eight lights, a ray budget that ends among a
+    floor pixel's shadow rays and a queue shorter than their number, the HIP path renders the oracle's pixels, ray and hit counts (the
+    CPU tier runs the gems cases on the host build: tests/test_shortcuts_cpu.py).  gems from three views, the others from two."""
+    renderer.initShader(scene)
     limits = dict(max_cost_default=9, extension_lights=7, bounce_count=bounces, ray_count=slots)
+    views = DELIVERY_VIEWS if scene == "gems" else [DELIVERY_VIEWS[0], DELIVERY_VIEWS[2]]
     try:
-        for k, (eye, at) in enumerate([((2.5, 2.0, 0.5), (0.0, 1.0, 0.0)), ((0.3, 0.4, -4.0), (0.0, 0.8, 0.0)), ((5.0, 6.0, 5.0), (0.0, 0.0, 0.0))]):
-            f, img, st, _tot = _render(renderer, oracle, "gems", eye, at, 160, 96, 1.3 + k, limits, True)
-            ref, rst, _ = oracle.render("gems", f, stats=True)
-            assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), (eye, bounces, slots)
+        for k, (eye, at) in enumerate(views):
+            f, img, st, _tot = _render(renderer, oracle, scene, eye, at, 160, 96, 1.3 + k, limits, True)
+            ref, rst, _ = oracle.render(scene, f, stats=True)
+            assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), (scene, eye, bounces, slots)
             assert np.array_equal(st[..., 0], rst[..., 0]) and np.array_equal(st[..., 2], rst[..., 2])
             assert (st[..., 1] <= rst[..., 1]).all()
     finally:

@@ -7,6 +7,8 @@ import math
 
 import numpy as np
 
+from shortcut_scenes import ALL_SCENES, ESCAPES_FROM, INLINE_ESCAPED_SHADOWS, RAY_ESCAPES
+
 
 def test_labyrinth_bounds_hold_on_random_samples():
     import hostsim
@@ -358,4 +360,62 @@ def test_every_escape_rule_against_a_walk_along_the_ray(oracle):
         else:
             with_rule.append(scene)
             assert total > 300, (scene, total)
-    assert len(with_rule) >= 20, with_rule
+    # -1 means "no ray_escapes declared": the walk covered exactly the scenes that declare one
+    assert set(with_rule) == RAY_ESCAPES, sorted(set(with_rule) ^ RAY_ESCAPES)
+
+
+def _scene_rules():
+    import hostsim
+
+    L = hostsim.lib()
+    L.hostsim_scene_rules.restype = ctypes.c_int
+    L.hostsim_scene_rules.argtypes = [ctypes.c_char_p]
+    L.hostsim_scene_count.restype = ctypes.c_int
+    L.hostsim_scene_name.restype = ctypes.c_char_p
+    L.hostsim_scene_name.argtypes = [ctypes.c_int]
+    names = [L.hostsim_scene_name(k).decode() for k in range(L.hostsim_scene_count())]
+    return {name: L.hostsim_scene_rules(name.encode()) for name in names}
+
+
+def test_shared_scene_lists_match_the_rules_the_scenes_declare():
+    """tests/shortcut_scenes.py names the scenes whose rules the GPU tier covers one by one: it must be what the functors declare
+    (sdfr_pixel.h: RayEscapes, EscapesFrom, InlineEscapedShadows), so that a rule added or removed without the tests fails here"""
+    rules = _scene_rules()
+    assert tuple(rules) == ALL_SCENES and all(v >= 0 for v in rules.values()), rules
+    assert {s for s, v in rules.items() if v & 1} == RAY_ESCAPES
+    assert {s for s, v in rules.items() if v & 2} == ESCAPES_FROM
+    assert {s for s, v in rules.items() if v & 4} == INLINE_ESCAPED_SHADOWS
+    assert INLINE_ESCAPED_SHADOWS <= RAY_ESCAPES
+
+
+def test_every_escapes_from_rule_against_a_walk_along_the_ray(oracle):
+    """Every built-in scene's escapes_from(): from the distance it returns on, up to the ray's range, a dense walk finds the scene farther
+    than 0.002 -- rays towards points anywhere about the scene and towards the sun along directions up to 6e-4 shorter than unit
+    vectors, at random times and slider settings (the light ball of lense over its whole range).  -1 means "no escapes_from declared"."""
+    import hostsim
+
+    L = hostsim.lib()
+    L.hostsim_check_escapes_from.restype = ctypes.c_longlong
+    L.hostsim_check_escapes_from.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_uint, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_float)]
+    rng = np.random.default_rng(20261015)
+    with_rule = []
+    for scene in _scene_rules():
+        table = oracle.var_table(scene)
+        total = 0
+        for rep in range(6):
+            f = oracle.default_frame(scene, 64, 48, stime=float(rng.uniform(0, 40)))
+            for name, mn, mx, start, _st, _v, slot in table:
+                if slot >= 0 and rep:
+                    f.scene_var[slot] = float(np.float32(mn if rep == 1 else (mx if rep == 2 else rng.uniform(mn, mx))))
+            hf = hostsim.frame_from_oracle(f)
+            fired = ctypes.c_longlong(0)
+            witness = (ctypes.c_float * 9)()
+            bad = L.hostsim_check_escapes_from(scene.encode(), ctypes.byref(hf), 20000, 300 + rep, ctypes.byref(fired), witness)
+            if bad == -1:
+                break
+            assert bad == 0, (scene, list(witness), [f.scene_var[i] for i in range(8)], f.stime)
+            total += fired.value
+        else:
+            with_rule.append(scene)
+            assert total > 6 * 20000 // 20, (scene, total)
+    assert set(with_rule) == ESCAPES_FROM, with_rule
