@@ -293,7 +293,8 @@ int sdfr_sync(sdfr_renderer *r);
  *          sdfr_wait_frame(r, stream) -- `stream` waits (on the device, not the host) for the frame submitted last -- or sdfr_sync,
  *          which waits for both frames.  sdfr_get_stats / sdfr_get_timings report the frame submitted last (and wait for it).
  *        - two frames in flight write two buffers: a frame rendered into memory that overlaps the destination of the frame still in
- *          flight waits for that frame first (correct, but nothing overlaps) -- alternate between two images.
+ *          flight (its image or its pixel_stats) waits for that frame first (correct, but nothing overlaps) -- alternate between two images.
+ *        - a sdfr_render that fails leaves "the frame submitted last" unchanged: it is still the last frame that succeeded.
  *        - sdfr_render_strips / _gather / sdfr_postprocess run on the lane of the frame submitted last.
  *      n = 1 (the default) returns to one stream (the caller's) after waiting for both frames. ------------------------------------- */
 int sdfr_set_frames_in_flight(sdfr_renderer *r, int n);

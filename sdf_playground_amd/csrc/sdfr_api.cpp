@@ -78,7 +78,9 @@ static int ensure_workspace(sdfr_renderer *r, size_t pixels, bool wavefront)
 		if (e == hipSuccess && w.tile_cursors == nullptr)
 		{
 			alloc((void **)&w.tile_cursors, sizeof(uint32_t) * (size_t)pixel_tile_cursor_words());
-			if (e == hipSuccess) e = hipMemset(w.tile_cursors, 0, sizeof(uint32_t) * (size_t)pixel_tile_cursor_words());
+			// on the stream of the launch that uses them: hipMemset runs on the null stream, which the non-blocking streams of
+			// two frames in flight do not wait for -- a launch could take tiles from cursors not yet cleared
+			if (e == hipSuccess) e = hipMemsetAsync(w.tile_cursors, 0, sizeof(uint32_t) * (size_t)pixel_tile_cursor_words(), r->stream);
 		}
 		if (wavefront)
 		{
@@ -116,6 +118,8 @@ static void swap_lanes(sdfr_renderer *r)
 	std::swap(r->have_render, r->other.have_render);
 	std::swap(r->out_lo, r->other.out_lo);
 	std::swap(r->out_hi, r->other.out_hi);
+	std::swap(r->pst_lo, r->other.pst_lo);
+	std::swap(r->pst_hi, r->other.pst_hi);
 }
 static void release_second_lane(sdfr_renderer *r)
 {
@@ -174,6 +178,7 @@ int sdfr_set_frames_in_flight(sdfr_renderer *r, int n)
 		r->other = lane;
 		r->stream = r->lane_streams[0]; // the current lane keeps its workspace and the row order it has learned
 		r->out_lo = r->out_hi = nullptr;
+		r->pst_lo = r->pst_hi = nullptr;
 		r->frames_in_flight = 2;
 		return SDFR_OK;
 	});
@@ -679,12 +684,20 @@ int sdfr_set_strip_split(sdfr_renderer *r, int priv_count, int priv_period)
 	});
 }
 
+// a scene to render and a frame size it can have
+static int check_frame(sdfr_renderer *r, int width, int height)
+{
+	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
+	if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	return SDFR_OK;
+}
+
 // latch the variable values into the frame uniforms (the reference uploads them every frame,
 // SDFRenderer.cpp:75-78) and derive the per-frame constants
 static int latch_frame(sdfr_renderer *r, int width, int height)
 {
-	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
-	if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	const int rc = check_frame(r, width, height);
+	if (rc != SDFR_OK) return rc;
 	FrameU &U = r->U;
 	U.width = width;
 	U.height = height;
@@ -810,6 +823,7 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 		r->last_profiled = r->profiling;
 	}
 	if (e != hipSuccess) return hip_fail(r, e, "kernel launch");
+	++r->launches;
 	if (!r->caller_times)
 	{
 		SDFR_HIP(hipEventRecord(r->ev_end, r->stream));
@@ -831,19 +845,45 @@ extern "C" {
 int sdfr_render(sdfr_renderer *r, int width, int height, void *out, int format, int out_on_host, uint32_t *pixel_stats)
 {
 	return guarded(r, [&]() -> int {
-		if (r && r->frames_in_flight == 2 && out && width > 0 && height > 0)
+		if (r && r->frames_in_flight == 2)
 		{
+			// render_impl's own checks, before the lanes change: a call that fails leaves "the frame submitted last" (sdfr_get_stats,
+			// sdfr_wait_frame) and the ranges the two lanes write as they were
+			if (!out) return SDFR_ERR_INVALID_ARGUMENT;
+			if (format != SDFR_RGBA32F && format != SDFR_RGBA16F) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
+			int rc = check_frame(r, width, height);
+			if (rc != SDFR_OK) return rc;
 			// the lane of the frame before last takes this one; its stream orders it behind that frame (same workspace)
 			SDFR_HIP(hipSetDevice(r->device));
 			swap_lanes(r);
+			const char *const kept[4] = {r->out_lo, r->out_hi, r->pst_lo, r->pst_hi};
+			const size_t pixels = (size_t)width * height;
 			const char *lo = out_on_host ? nullptr : (const char *)out;
-			const char *hi = lo ? lo + image_bytes((size_t)width * height, format) : nullptr;
-			// the frame still in flight on the other lane writes [other.out_lo, other.out_hi): the same memory twice in a row is
-			// a hazard between the two streams
-			if (lo && r->other.out_lo && lo < r->other.out_hi && r->other.out_lo < hi && r->other.have_render)
-				SDFR_HIP(hipStreamWaitEvent(r->stream, r->other.ev_end, 0));
+			const char *hi = lo ? lo + image_bytes(pixels, format) : nullptr;
+			const char *plo = out_on_host ? nullptr : (const char *)pixel_stats;
+			const char *phi = plo ? plo + pixels * 12 : nullptr;
+			// the frame still in flight on the other lane writes [other.out_lo, other.out_hi) and [other.pst_lo, other.pst_hi): the same
+			// memory twice in a row is a hazard between the two streams
+			auto overlaps = [](const char *a, const char *b, const char *c, const char *d) { return a && c && a < d && c < b; };
+			const sdfr_renderer::Lane &o = r->other;
+			if (o.have_render && (overlaps(lo, hi, o.out_lo, o.out_hi) || overlaps(lo, hi, o.pst_lo, o.pst_hi) || overlaps(plo, phi, o.out_lo, o.out_hi) ||
+					overlaps(plo, phi, o.pst_lo, o.pst_hi)))
+				SDFR_HIP(hipStreamWaitEvent(r->stream, o.ev_end, 0));
 			r->out_lo = lo;
 			r->out_hi = hi;
+			r->pst_lo = plo;
+			r->pst_hi = phi;
+			const unsigned launches = r->launches;
+			rc = render_impl(r, width, height, 0, 1, out, format, out_on_host, pixel_stats, RENDER_FULL);
+			if (rc != SDFR_OK && r->launches == launches) // nothing launched: the lanes go back to where they were
+			{
+				r->out_lo = kept[0];
+				r->out_hi = kept[1];
+				r->pst_lo = kept[2];
+				r->pst_hi = kept[3];
+				swap_lanes(r);
+			}
+			return rc;
 		}
 		return render_impl(r, width, height, 0, 1, out, format, out_on_host, pixel_stats, RENDER_FULL);
 	});

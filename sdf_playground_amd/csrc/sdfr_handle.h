@@ -82,12 +82,15 @@ struct sdfr_renderer
 		hipEvent_t ev_begin = nullptr, ev_end = nullptr;
 		bool have_render = false;
 		const char *out_lo = nullptr, *out_hi = nullptr; // device range its last frame was rendered into
+		const char *pst_lo = nullptr, *pst_hi = nullptr; // ... and the device range of that frame's pixel_stats
 	};
 	int frames_in_flight = 1;
 	Lane other;
 	hipStream_t lane_streams[2] = {nullptr, nullptr}; // the library's own streams while frames_in_flight == 2
 	hipStream_t user_stream = nullptr;                // what sdfr_set_stream gave (in use while frames_in_flight == 1)
 	const char *out_lo = nullptr, *out_hi = nullptr;  // the current lane's
+	const char *pst_lo = nullptr, *pst_hi = nullptr;
+	unsigned launches = 0; // render launches so far: did a call that failed launch anything before it failed
 };
 
 static inline int fail(const sdfr_renderer *r, int code, const std::string &msg)
