@@ -226,11 +226,35 @@ struct SceneLabyrinth
 		if (wz > wx) { float t = wx; wx = wz; wz = t; }
 		return V3(wx, p.y, wz);
 	}
+	// min1(sd_box(p1, b1), sd_box(p2, b2)) with one square root instead of two, bit for bit.  Per box
+	// sd_box = s + m with a = dot(o, o), o = max(q, 0), s = sqrt1(a), m = min1(max1(q.x, q.y, q.z), 0):
+	//   * a >= +0, never -0 nor NaN: max1(x, 0) is a zero for x <= 0 and for NaN, and a zero of either sign squares to +0
+	//     (+0 + +0 = +0 in the fma); so s >= +0, never -0 -- which is why min1(m1, m2) needs no "+0 +" in front of it.
+	//   * m < 0 means every q < 0 (or NaN), so a = +0 and s = +0: sd_box = m.  Otherwise m is +-0 and sd_box = s + (+-0) = s.
+	//   * both m zero: min1(s1, s2) = sqrt1(min1(a1, a2)), sqrt1 being correctly rounded, hence monotone, on the domain
+	//     every sd_box relies on (+0 and [2^-96, FLT_MAX]; sdfr_math.h) and min1(a1, a2) one of a1, a2.  min1(m1, m2) is
+	//     +-0 and adds nothing.
+	//   * a box with m < 0: min1(a1, a2) = +0, the root is +0, and the result is min1(m1, m2) < 0 -- the other box's
+	//     sd_box is its own m if that is negative, and >= +0 otherwise.
+	//   * a = +inf (a |q| of about 2^64 or more): sqrt1 gives NaN there, which min1 drops; min1(a1, a2) drops the +inf box the same way,
+	//     whose m is +0; both +inf: NaN either way.
+	// min1(m1, m2) = min(max1 of the q of box 1, max1 of the q of box 2, 0): min1 over a set, NaN left out.  Host-checked
+	// against the two sd_box calls (tests/test_labyrinth_walls_cpu.py).  8 VALU fewer per evaluation: two roots, two min1 with 0,
+	// two additions and a min1 (17) become a min1, one root, a v_min3 and an addition (9).  The second box's a is written
+	// first: with the other order the allocator puts one more fma of the march loop in one register bank.
+	static SDF_HD float sd_box_pair_min(vec3 p1, vec3 b1, vec3 p2, vec3 b2)
+	{
+		const vec3 q1 = abs(p1) - b1, q2 = abs(p2) - b2;
+		const vec3 o1 = max(q1, 0.f), o2 = max(q2, 0.f);
+		const float in = min1(min1(max1(q1.x, max1(q1.y, q1.z)), max1(q2.x, max1(q2.y, q2.z))), 0.f);
+		return sqrt1(min1(dot(o2, o2), dot(o1, o1))) + in;
+	}
+	// For the walls every a lies in sqrt1's domain: a component q = |w - c| - h (h >= 1) that is not 0 and below h / 2 is
+	// an exact difference of two floats >= 1/2, so |q| >= 2^-24 and a nonzero a is >= 2^-48 (w.x and w.z are folded to
+	// about [0, 10]: only a |w.y| >= 2^64 overflows, to +inf, above).
 	static SDF_HD float walls(vec3 wp)
 	{
-		float wall1 = sd_box(wp - V3(3.5f, 2.f, 3.f), V3(1.5f, 2.f, 1.f));
-		float wall2 = sd_box(wp - V3(7.f, 2.f, 5.f), V3(3.f, 2.f, 1.f));
-		return min1(wall1, wall2);
+		return sd_box_pair_min(wp - V3(3.5f, 2.f, 3.f), V3(1.5f, 2.f, 1.f), wp - V3(7.f, 2.f, 5.f), V3(3.f, 2.f, 1.f));
 	}
 	// position in the vase's frame (the vase is mirrored about x = 8)
 	static SDF_HD vec3 vase_local(vec3 wp) { return V3(abs1(wp.x - 8.f), wp.y, wp.z) - V3(1.f, 0.f, 3.f); }
