@@ -38,9 +38,9 @@ bool is_wire_format(int format)
 }
 } // namespace sdfr
 
-static void free_workspace(sdfr_renderer *r)
+static void free_workspace(sdfr_renderer::Lane &l)
 {
-	WavefrontWorkspace &w = r->ws;
+	WavefrontWorkspace &w = l.ws;
 	(void)hipFree(w.ray_cur);
 	(void)hipFree(w.ray_queue);
 	(void)hipFree(w.qdepth_lo);
@@ -53,21 +53,21 @@ static void free_workspace(sdfr_renderer *r)
 	(void)hipFree(w.partials);
 	(void)hipFree(w.tile_cursors);
 	w = WavefrontWorkspace{};
-	r->wavefront_capacity = 0;
+	l.wavefront_capacity = 0;
 }
 
-// Per-pixel scratch sized for `pixels` work items.  Both schedules use the pending-ray queue and
+// Per-pixel scratch of lane `l` sized for `pixels` work items.  Both schedules use the pending-ray queue and
 // the counter partials; the per-round state of the wavefront schedule (another 116 B per pixel)
 // is allocated only once that schedule is used.  On failure everything is released (hipFree
 // waits for the device, so buffers of frames still in flight are safe to drop).
-static int ensure_workspace(sdfr_renderer *r, size_t pixels, bool wavefront)
+static int ensure_workspace(sdfr_renderer *r, sdfr_renderer::Lane &l, size_t pixels, bool wavefront)
 {
-	WavefrontWorkspace &w = r->ws;
+	WavefrontWorkspace &w = l.ws;
 	// the pixel kernel indexes the pending-ray records with 32 bits (GlobalRayStore::record)
 	if (pixels * (size_t)SDFR_MAX_RAYS >= ((size_t)1 << 32)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "frame too large: more than 2^32 / 8 pixels per launch");
-	if (w.capacity < pixels || (wavefront && r->wavefront_capacity < pixels))
+	if (w.capacity < pixels || (wavefront && l.wavefront_capacity < pixels))
 	{
-		if (w.capacity < pixels) free_workspace(r);
+		if (w.capacity < pixels) free_workspace(l);
 		const size_t n = w.capacity < pixels ? pixels : w.capacity;
 		hipError_t e = hipSuccess;
 		auto alloc = [&](void **p, size_t bytes) {
@@ -80,7 +80,7 @@ static int ensure_workspace(sdfr_renderer *r, size_t pixels, bool wavefront)
 			alloc((void **)&w.tile_cursors, sizeof(uint32_t) * (size_t)pixel_tile_cursor_words());
 			// on the stream of the launch that uses them: hipMemset runs on the null stream, which the non-blocking streams of
 			// two frames in flight do not wait for -- a launch could take tiles from cursors not yet cleared
-			if (e == hipSuccess) e = hipMemsetAsync(w.tile_cursors, 0, sizeof(uint32_t) * (size_t)pixel_tile_cursor_words(), r->stream);
+			if (e == hipSuccess) e = hipMemsetAsync(w.tile_cursors, 0, sizeof(uint32_t) * (size_t)pixel_tile_cursor_words(), l.stream);
 		}
 		if (wavefront)
 		{
@@ -95,50 +95,43 @@ static int ensure_workspace(sdfr_renderer *r, size_t pixels, bool wavefront)
 		}
 		if (e != hipSuccess)
 		{
-			free_workspace(r);
+			free_workspace(l);
 			return hip_fail(r, e, "workspace allocation");
 		}
 		w.capacity = n;
-		if (wavefront) r->wavefront_capacity = n;
+		if (wavefront) l.wavefront_capacity = n;
 		w.pstat = nullptr;
 	}
 	return SDFR_OK;
 }
 
-// ---- two frames in flight (sdfr_set_frames_in_flight): see sdfr_renderer::Lane -----------------------------------
-static void swap_lanes(sdfr_renderer *r)
+// the counters and events of a lane; its stream is the caller's to set
+static hipError_t create_lane(sdfr_renderer::Lane &l)
 {
-	std::swap(r->stream, r->other.stream);
-	std::swap(r->ws, r->other.ws);
-	std::swap(r->wavefront_capacity, r->other.wavefront_capacity);
-	std::swap(r->d_totals, r->other.d_totals);
-	std::swap(r->totals_parts, r->other.totals_parts);
-	std::swap(r->ev_begin, r->other.ev_begin);
-	std::swap(r->ev_end, r->other.ev_end);
-	std::swap(r->have_render, r->other.have_render);
-	std::swap(r->out_lo, r->other.out_lo);
-	std::swap(r->out_hi, r->other.out_hi);
-	std::swap(r->pst_lo, r->other.pst_lo);
-	std::swap(r->pst_hi, r->other.pst_hi);
+	hipError_t e = hipMalloc((void **)&l.d_totals, 2 * sizeof(RenderTotals));
+	if (e == hipSuccess) e = hipEventCreate(&l.ev_begin);
+	if (e == hipSuccess) e = hipEventCreate(&l.ev_end);
+	return e;
 }
+// frees what create_lane and ensure_workspace gave the lane (its stream is the caller's) and empties it
+static void release_lane(sdfr_renderer::Lane &l)
+{
+	free_workspace(l);
+	(void)hipFree(l.d_totals);
+	if (l.ev_begin) (void)hipEventDestroy(l.ev_begin);
+	if (l.ev_end) (void)hipEventDestroy(l.ev_end);
+	l = sdfr_renderer::Lane();
+}
+// back to one frame in flight: the current lane keeps its workspace and runs on the caller's stream again
 static void release_second_lane(sdfr_renderer *r)
 {
 	if (r->frames_in_flight != 2) return;
-	(void)hipStreamSynchronize(r->stream);
+	(void)hipStreamSynchronize(r->lane.stream);
 	(void)hipStreamSynchronize(r->other.stream);
-	swap_lanes(r); // free_workspace works on the current lane
-	free_workspace(r);
-	swap_lanes(r);
-	(void)hipFree(r->other.d_totals);
-	if (r->other.ev_begin) (void)hipEventDestroy(r->other.ev_begin);
-	if (r->other.ev_end) (void)hipEventDestroy(r->other.ev_end);
-	r->other = sdfr_renderer::Lane();
-	for (hipStream_t &s : r->lane_streams)
-	{
-		if (s) (void)hipStreamDestroy(s);
-		s = nullptr;
-	}
-	r->stream = r->user_stream;
+	(void)hipStreamDestroy(r->lane.stream);
+	(void)hipStreamDestroy(r->other.stream);
+	release_lane(r->other);
+	r->lane.stream = r->user_stream;
 	r->frames_in_flight = 1;
 }
 
@@ -155,30 +148,23 @@ int sdfr_set_frames_in_flight(sdfr_renderer *r, int n)
 			release_second_lane(r);
 			return SDFR_OK;
 		}
-		SDFR_HIP(hipStreamSynchronize(r->stream));
-		sdfr_renderer::Lane lane;
-		hipError_t e = hipStreamCreateWithFlags(&r->lane_streams[0], hipStreamNonBlocking);
-		if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->lane_streams[1], hipStreamNonBlocking);
-		if (e == hipSuccess) e = hipMalloc((void **)&lane.d_totals, 2 * sizeof(RenderTotals));
-		if (e == hipSuccess) e = hipEventCreate(&lane.ev_begin);
-		if (e == hipSuccess) e = hipEventCreate(&lane.ev_end);
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
+		hipStream_t stream = nullptr; // the current lane's from now on: it keeps its workspace and the row order it has learned
+		sdfr_renderer::Lane second;
+		hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+		if (e == hipSuccess) e = hipStreamCreateWithFlags(&second.stream, hipStreamNonBlocking);
+		if (e == hipSuccess) e = create_lane(second);
 		if (e != hipSuccess)
 		{
-			(void)hipFree(lane.d_totals);
-			if (lane.ev_begin) (void)hipEventDestroy(lane.ev_begin);
-			if (lane.ev_end) (void)hipEventDestroy(lane.ev_end);
-			for (hipStream_t &s : r->lane_streams)
-			{
-				if (s) (void)hipStreamDestroy(s);
-				s = nullptr;
-			}
+			if (stream) (void)hipStreamDestroy(stream);
+			if (second.stream) (void)hipStreamDestroy(second.stream);
+			release_lane(second);
 			return hip_fail(r, e, "sdfr_set_frames_in_flight");
 		}
-		lane.stream = r->lane_streams[1];
-		r->other = lane;
-		r->stream = r->lane_streams[0]; // the current lane keeps its workspace and the row order it has learned
-		r->out_lo = r->out_hi = nullptr;
-		r->pst_lo = r->pst_hi = nullptr;
+		r->lane.stream = stream;
+		r->lane.out_lo = r->lane.out_hi = nullptr;
+		r->lane.pst_lo = r->lane.pst_hi = nullptr;
+		r->other = second;
 		r->frames_in_flight = 2;
 		return SDFR_OK;
 	});
@@ -188,9 +174,9 @@ int sdfr_wait_frame(sdfr_renderer *r, void *hip_stream)
 {
 	return guarded(r, [&]() -> int {
 		if (!r) return SDFR_ERR_INVALID_ARGUMENT;
-		if (!r->have_render) return SDFR_OK;
+		if (!r->lane.have_render) return SDFR_OK;
 		SDFR_HIP(hipSetDevice(r->device));
-		SDFR_HIP(hipStreamWaitEvent((hipStream_t)hip_stream, r->ev_end, 0));
+		SDFR_HIP(hipStreamWaitEvent((hipStream_t)hip_stream, r->lane.ev_end, 0));
 		return SDFR_OK;
 	});
 }
@@ -226,9 +212,9 @@ int sdfr_create(int device_ordinal, sdfr_renderer **out)
 		r->U.front = V3(f.x, f.y, f.z);
 		r->U.right = V3(rt.x, rt.y, rt.z);
 		r->U.top = V3(tp.x, tp.y, tp.z);
-		if (hipMalloc((void **)&r->d_totals, 2 * sizeof(RenderTotals)) != hipSuccess || hipEventCreate(&r->ev_begin) != hipSuccess ||
-			hipEventCreate(&r->ev_end) != hipSuccess)
+		if (create_lane(r->lane) != hipSuccess)
 		{
+			release_lane(r->lane);
 			delete r;
 			return SDFR_ERR_HIP;
 		}
@@ -247,13 +233,12 @@ void sdfr_destroy(sdfr_renderer *r)
 {
 	if (!r) return;
 	(void)hipSetDevice(r->device);
-	(void)hipStreamSynchronize(r->stream);
+	(void)hipStreamSynchronize(r->lane.stream);
 	if (r->comm_stream) (void)hipStreamSynchronize(r->comm_stream);
 	comm_forget_renderer(r);
 	release_second_lane(r); // waits for it, frees its workspace, counters, events and the two internal streams
-	free_workspace(r);
+	release_lane(r->lane);
 	jit_unload(r->jit);
-	(void)hipFree(r->d_totals);
 	(void)hipFree(r->d_stage);
 	(void)hipFree(r->d_pstat);
 	(void)hipFree(r->d_wire);
@@ -264,8 +249,6 @@ void sdfr_destroy(sdfr_renderer *r)
 	if (r->ev_gathered) (void)hipEventDestroy(r->ev_gathered);
 	for (hipEvent_t e : r->ev_xfer)
 		if (e) (void)hipEventDestroy(e);
-	(void)hipEventDestroy(r->ev_begin);
-	(void)hipEventDestroy(r->ev_end);
 	for (hipEvent_t e : r->ev_post) (void)hipEventDestroy(e);
 	for (int i = 0; i < 32; ++i)
 	{
@@ -282,7 +265,7 @@ int sdfr_set_stream(sdfr_renderer *r, void *hip_stream)
 	return guarded(r, [&]() -> int {
 		if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 		r->user_stream = (hipStream_t)hip_stream;
-		if (r->frames_in_flight == 1) r->stream = r->user_stream; // (two frames in flight run on the handle's own two streams)
+		if (r->frames_in_flight == 1) r->lane.stream = r->user_stream; // (two frames in flight run on the handle's own two streams)
 		return SDFR_OK;
 	});
 }
@@ -398,7 +381,7 @@ int sdfr_load_scene_hlsl(sdfr_renderer *r, const char *name, const char *hlsl_so
 		JitScene js;
 		std::string err;
 		if (!jit_compile(r->device, name, hlsl_scene_source(hlsl_source), slots, js, err)) return fail(r, SDFR_ERR_COMPILE, err);
-		SDFR_HIP(hipStreamSynchronize(r->stream));
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 		if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream)); // the frame before may still run the old module
 		jit_unload(r->jit);
 		r->jit = js;
@@ -423,7 +406,7 @@ int sdfr_load_scene_source(sdfr_renderer *r, const char *name, const char *sourc
 		// like the reference, a scene that fails to compile leaves the previous one in place
 		// (SceneManager.cpp:118-127 keeps the old shader and shows the compiler's message)
 		if (!jit_compile(r->device, name, source, slots, js, err)) return fail(r, SDFR_ERR_COMPILE, err);
-		SDFR_HIP(hipStreamSynchronize(r->stream));
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 		if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream));
 		jit_unload(r->jit);
 		r->jit = js;
@@ -684,9 +667,15 @@ int sdfr_set_strip_split(sdfr_renderer *r, int priv_count, int priv_period)
 	});
 }
 
-// a scene to render and a frame size it can have
-static int check_frame(sdfr_renderer *r, int width, int height)
+// the arguments of render_impl, in the order their errors win; a private render without private strips renders nothing
+// and needs no scene
+static int check_render(sdfr_renderer *r, int width, int height, int rank, int world, const void *out, int format, RenderMode mode)
 {
+	if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
+	if (format != SDFR_RGBA32F && format != SDFR_RGBA16F && !(mode == RENDER_STRIPS && is_wire_format(format)))
+		return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
+	if (mode == RENDER_PRIVATE && r->priv_count == 0) return SDFR_OK;
+	if (world < 1 || rank < 0 || rank >= world) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad rank/world");
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
 	if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 	return SDFR_OK;
@@ -696,8 +685,6 @@ static int check_frame(sdfr_renderer *r, int width, int height)
 // SDFRenderer.cpp:75-78) and derive the per-frame constants
 static int latch_frame(sdfr_renderer *r, int width, int height)
 {
-	const int rc = check_frame(r, width, height);
-	if (rc != SDFR_OK) return rc;
 	FrameU &U = r->U;
 	U.width = width;
 	U.height = height;
@@ -715,25 +702,22 @@ static int latch_frame(sdfr_renderer *r, int width, int height)
 	for (size_t k = 0; k < r->scene_var_slots.size(); ++k) U.scene_var[k] = val(r->scene_var_slots[k].c_str());
 	U.step_shortcuts = r->step_shortcuts ? 1 : 0;
 	frame_derive(U, r->scene);
-	if (r->scene == SDFR_SCENE_COUNT) SDFR_HIP(jit_prepare(r->jit, U, r->stream));
+	if (r->scene == SDFR_SCENE_COUNT) SDFR_HIP(jit_prepare(r->jit, U, r->lane.stream));
 	return SDFR_OK;
 }
 
 } // extern "C"
 
 int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int world, void *out, int format, int out_on_host, uint32_t *pixel_stats,
-	RenderMode mode, RenderTotals *totals)
+	RenderMode mode, RenderTotals *totals, bool caller_times)
 {
-	if (r && !totals) totals = r->d_totals;
-	if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
+	int rc = check_render(r, width, height, rank, world, out, format, mode);
+	if (rc != SDFR_OK || (mode == RENDER_PRIVATE && r->priv_count == 0)) return rc; // (no private strips: nothing to render)
+	if (!totals) totals = r->lane.d_totals;
 	const bool strips = mode == RENDER_STRIPS;
-	if (format != SDFR_RGBA32F && format != SDFR_RGBA16F && !(strips && is_wire_format(format)))
-		return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
-	if (mode == RENDER_PRIVATE && r->priv_count == 0) return SDFR_OK; // no private strips: nothing to render
-	if (world < 1 || rank < 0 || rank >= world) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad rank/world");
 	SDFR_HIP(hipSetDevice(r->device));
 	const auto t_setup = std::chrono::steady_clock::now();
-	int rc = latch_frame(r, width, height);
+	rc = latch_frame(r, width, height);
 	if (rc != SDFR_OK) return rc;
 	r->ms_setup = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_setup).count();
 
@@ -791,51 +775,51 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 		// whose last strip is missing or cut short have any)
 		const int last_local_strip = rm.local_rows / SDFR_STRIP_ROWS - 1;
 		const long long last_row_end = last_local_strip < 0 ? 0 : ((long long)strip_local_to_global(rm, (uint32_t)last_local_strip) + 1) * SDFR_STRIP_ROWS;
-		if (last_row_end > height && out_bytes) SDFR_HIP(hipMemsetAsync(d_out, 0, out_bytes, r->stream));
+		if (last_row_end > height && out_bytes) SDFR_HIP(hipMemsetAsync(d_out, 0, out_bytes, r->lane.stream));
 	}
 
 	const bool pixel_schedule = r->scene == SDFR_SCENE_COUNT || r->schedule == SDFR_SCHEDULE_PIXEL;
-	if (!pixel_schedule) SDFR_HIP(hipMemsetAsync(totals, 0, sizeof(RenderTotals), r->stream)); // the wavefront kernels add to it
+	if (!pixel_schedule) SDFR_HIP(hipMemsetAsync(totals, 0, sizeof(RenderTotals), r->lane.stream)); // the wavefront kernels add to it
 	hipError_t e;
 	if (rm.local_rows == 0) return SDFR_OK; // e.g. every strip of a small frame is private
 	{
 		size_t need = (size_t)launch_capacity_items(width, rm);
 		if (need < local_pixels) need = local_pixels; // private strips index the workspace by image position
-		rc = ensure_workspace(r, need, !pixel_schedule);
+		rc = ensure_workspace(r, r->lane, need, !pixel_schedule);
 	}
 	if (rc != SDFR_OK) return rc;
-	if (!r->caller_times) SDFR_HIP(hipEventRecord(r->ev_begin, r->stream));
+	if (!caller_times) SDFR_HIP(hipEventRecord(r->lane.ev_begin, r->lane.stream));
 	if (r->scene == SDFR_SCENE_COUNT) // scenes compiled at run time exist for the PIXEL schedule only
 	{
-		e = jit_launch_pixel(r->jit, r->U, rm, d_out, format, d_pstat, totals, r->ws, r->stream, r->launch_mode);
+		e = jit_launch_pixel(r->jit, r->U, rm, d_out, format, d_pstat, totals, r->lane.ws, r->lane.stream, r->launch_mode);
 		r->last_wavefront = false;
 	}
 	else if (r->schedule == SDFR_SCHEDULE_PIXEL)
 	{
-		e = launch_pixel_schedule(r->scene, r->U, rm, d_out, format, d_pstat, totals, r->ws, r->stream, r->launch_mode);
+		e = launch_pixel_schedule(r->scene, r->U, rm, d_out, format, d_pstat, totals, r->lane.ws, r->lane.stream, r->launch_mode);
 		r->last_wavefront = false;
 	}
 	else
 	{
-		e = launch_wavefront_schedule(r->scene, r->U, rm, d_out, format, d_pstat, totals, r->ws, r->stream, r->profiling ? r->ev_march : nullptr,
+		e = launch_wavefront_schedule(r->scene, r->U, rm, d_out, format, d_pstat, totals, r->lane.ws, r->lane.stream, r->profiling ? r->ev_march : nullptr,
 			r->profiling ? r->ev_shade : nullptr, &r->last_rounds);
 		r->last_wavefront = true;
 		r->last_profiled = r->profiling;
 	}
 	if (e != hipSuccess) return hip_fail(r, e, "kernel launch");
 	++r->launches;
-	if (!r->caller_times)
+	if (!caller_times)
 	{
-		SDFR_HIP(hipEventRecord(r->ev_end, r->stream));
-		r->totals_parts = 1;
+		SDFR_HIP(hipEventRecord(r->lane.ev_end, r->lane.stream));
+		r->lane.totals_parts = 1;
 	}
-	r->have_render = true;
+	r->lane.have_render = true;
 
 	if (out_on_host)
 	{
-		SDFR_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, r->stream));
-		if (pixel_stats) SDFR_HIP(hipMemcpyAsync(pixel_stats, d_pstat, local_pixels * 12, hipMemcpyDeviceToHost, r->stream));
-		SDFR_HIP(hipStreamSynchronize(r->stream));
+		SDFR_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, r->lane.stream));
+		if (pixel_stats) SDFR_HIP(hipMemcpyAsync(pixel_stats, d_pstat, local_pixels * 12, hipMemcpyDeviceToHost, r->lane.stream));
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 	}
 	return SDFR_OK;
 }
@@ -847,41 +831,35 @@ int sdfr_render(sdfr_renderer *r, int width, int height, void *out, int format, 
 	return guarded(r, [&]() -> int {
 		if (r && r->frames_in_flight == 2)
 		{
-			// render_impl's own checks, before the lanes change: a call that fails leaves "the frame submitted last" (sdfr_get_stats,
+			// checked before the lanes change: a call that fails leaves "the frame submitted last" (sdfr_get_stats,
 			// sdfr_wait_frame) and the ranges the two lanes write as they were
-			if (!out) return SDFR_ERR_INVALID_ARGUMENT;
-			if (format != SDFR_RGBA32F && format != SDFR_RGBA16F) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
-			int rc = check_frame(r, width, height);
+			int rc = check_render(r, width, height, 0, 1, out, format, RENDER_FULL);
 			if (rc != SDFR_OK) return rc;
-			// the lane of the frame before last takes this one; its stream orders it behind that frame (same workspace)
 			SDFR_HIP(hipSetDevice(r->device));
-			swap_lanes(r);
-			const char *const kept[4] = {r->out_lo, r->out_hi, r->pst_lo, r->pst_hi};
 			const size_t pixels = (size_t)width * height;
 			const char *lo = out_on_host ? nullptr : (const char *)out;
 			const char *hi = lo ? lo + image_bytes(pixels, format) : nullptr;
 			const char *plo = out_on_host ? nullptr : (const char *)pixel_stats;
 			const char *phi = plo ? plo + pixels * 12 : nullptr;
-			// the frame still in flight on the other lane writes [other.out_lo, other.out_hi) and [other.pst_lo, other.pst_hi): the same
-			// memory twice in a row is a hazard between the two streams
+			// the lane of the frame before last takes this one; its stream orders it behind that frame (same workspace).  The
+			// frame still in flight writes [out_lo, out_hi) and [pst_lo, pst_hi): the same memory twice in a row is a hazard
+			// between the two streams
 			auto overlaps = [](const char *a, const char *b, const char *c, const char *d) { return a && c && a < d && c < b; };
-			const sdfr_renderer::Lane &o = r->other;
+			const sdfr_renderer::Lane &o = r->lane;
 			if (o.have_render && (overlaps(lo, hi, o.out_lo, o.out_hi) || overlaps(lo, hi, o.pst_lo, o.pst_hi) || overlaps(plo, phi, o.out_lo, o.out_hi) ||
 					overlaps(plo, phi, o.pst_lo, o.pst_hi)))
-				SDFR_HIP(hipStreamWaitEvent(r->stream, o.ev_end, 0));
-			r->out_lo = lo;
-			r->out_hi = hi;
-			r->pst_lo = plo;
-			r->pst_hi = phi;
+				SDFR_HIP(hipStreamWaitEvent(r->other.stream, o.ev_end, 0));
+			std::swap(r->lane, r->other);
 			const unsigned launches = r->launches;
 			rc = render_impl(r, width, height, 0, 1, out, format, out_on_host, pixel_stats, RENDER_FULL);
-			if (rc != SDFR_OK && r->launches == launches) // nothing launched: the lanes go back to where they were
+			if (r->launches == launches) // nothing launched: the lanes go back to where they were
+				std::swap(r->lane, r->other);
+			else
 			{
-				r->out_lo = kept[0];
-				r->out_hi = kept[1];
-				r->pst_lo = kept[2];
-				r->pst_hi = kept[3];
-				swap_lanes(r);
+				r->lane.out_lo = lo;
+				r->lane.out_hi = hi;
+				r->lane.pst_lo = plo;
+				r->lane.pst_hi = phi;
 			}
 			return rc;
 		}
@@ -909,7 +887,7 @@ int sdfr_assemble_strips(sdfr_renderer *r, int width, int height, int world, con
 		if (!r || !gathered || !out_image || width < 1 || height < 1 || world < 1) return SDFR_ERR_INVALID_ARGUMENT;
 		if (!is_wire_format(format)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
 		SDFR_HIP(hipSetDevice(r->device));
-		hipError_t e = launch_assemble_strips(width, height, world, gathered, out_image, format, r->priv_count, r->priv_period, r->stream);
+		hipError_t e = launch_assemble_strips(width, height, world, gathered, out_image, format, r->priv_count, r->priv_period, r->lane.stream);
 		if (e != hipSuccess) return hip_fail(r, e, "assemble launch");
 		return SDFR_OK;
 	});
@@ -924,17 +902,17 @@ int sdfr_postprocess(sdfr_renderer *r, int width, int height, const void *scene_
 		const size_t flag_bytes = postprocess_flag_bytes(width, height);
 		if (r->post_flag_bytes < flag_bytes)
 		{
-			SDFR_HIP(hipStreamSynchronize(r->stream)); // a postprocess still in flight reads the old one
+			SDFR_HIP(hipStreamSynchronize(r->lane.stream)); // a postprocess still in flight reads the old one
 			(void)hipFree(r->d_post_flags);
 			r->d_post_flags = nullptr;
 			r->post_flag_bytes = 0;
 			SDFR_HIP(hipMalloc((void **)&r->d_post_flags, flag_bytes));
 			r->post_flag_bytes = flag_bytes;
 		}
-		SDFR_HIP(hipEventRecord(r->ev_post[0], r->stream));
-		hipError_t e = launch_postprocess(width, height, scene_rgba16f, bloom_scratch_rgba16f, out_rgba8, r->d_post_flags, r->stream, r->ev_post[1]);
+		SDFR_HIP(hipEventRecord(r->ev_post[0], r->lane.stream));
+		hipError_t e = launch_postprocess(width, height, scene_rgba16f, bloom_scratch_rgba16f, out_rgba8, r->d_post_flags, r->lane.stream, r->ev_post[1]);
 		if (e != hipSuccess) return hip_fail(r, e, "postprocess launch");
-		SDFR_HIP(hipEventRecord(r->ev_post[2], r->stream));
+		SDFR_HIP(hipEventRecord(r->ev_post[2], r->lane.stream));
 		r->have_post = true;
 		return SDFR_OK;
 	});
@@ -958,11 +936,11 @@ int sdfr_selftest_math(sdfr_renderer *r, int what, float constant, uint64_t *mis
 		SDFR_HIP(hipSetDevice(r->device));
 		unsigned long long *d = nullptr;
 		SDFR_HIP(hipMalloc((void **)&d, sizeof(unsigned long long)));
-		hipError_t e = hipMemsetAsync(d, 0, sizeof(unsigned long long), r->stream);
-		if (e == hipSuccess) e = launch_selftest_math(what, constant, d, r->stream);
+		hipError_t e = hipMemsetAsync(d, 0, sizeof(unsigned long long), r->lane.stream);
+		if (e == hipSuccess) e = launch_selftest_math(what, constant, d, r->lane.stream);
 		unsigned long long h = 0;
-		if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, r->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+		if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, r->lane.stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(r->lane.stream);
 		(void)hipFree(d);
 		if (e != hipSuccess) return hip_fail(r, e, "selftest");
 		*mismatches = h;
@@ -976,10 +954,10 @@ int sdfr_debug_read_partials(sdfr_renderer *r, void *host, size_t records)
 {
 	return guarded(r, [&]() -> int {
 		if (!r || !host) return SDFR_ERR_INVALID_ARGUMENT;
-		SDFR_HIP(hipStreamSynchronize(r->stream));
-		if (records > r->ws.capacity / 64 + 1) records = r->ws.capacity / 64 + 1;
-		SDFR_HIP(hipMemcpy(host, r->ws.partials, records * sizeof(RenderTotals), hipMemcpyDeviceToHost));
-		SDFR_HIP(hipMemset(r->ws.partials, 0, records * sizeof(RenderTotals))); // records the next launch does not write read as empty
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
+		if (records > r->lane.ws.capacity / 64 + 1) records = r->lane.ws.capacity / 64 + 1;
+		SDFR_HIP(hipMemcpy(host, r->lane.ws.partials, records * sizeof(RenderTotals), hipMemcpyDeviceToHost));
+		SDFR_HIP(hipMemset(r->lane.ws.partials, 0, records * sizeof(RenderTotals))); // records the next launch does not write read as empty
 		return SDFR_OK;
 	});
 }
@@ -990,7 +968,7 @@ int sdfr_register_host_target(sdfr_renderer *r, void *host_image, size_t bytes)
 	return guarded(r, [&]() -> int {
 		if (!r || (host_image && bytes == 0)) return SDFR_ERR_INVALID_ARGUMENT;
 		SDFR_HIP(hipSetDevice(r->device));
-		SDFR_HIP(hipStreamSynchronize(r->stream));
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 		if (r->pinned_host) (void)hipHostUnregister(r->pinned_host);
 		r->pinned_host = nullptr;
 		r->pinned_bytes = 0;
@@ -1006,7 +984,7 @@ int sdfr_sync(sdfr_renderer *r)
 {
 	return guarded(r, [&]() -> int {
 		if (!r) return SDFR_ERR_INVALID_ARGUMENT;
-		SDFR_HIP(hipStreamSynchronize(r->stream));
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 		if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream));
 		return SDFR_OK;
 	});
@@ -1017,14 +995,14 @@ int sdfr_get_stats(sdfr_renderer *r, sdfr_stats *out)
 	return guarded(r, [&]() -> int {
 		if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
 		memset(out, 0, sizeof *out);
-		if (!r->have_render) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "nothing rendered yet");
-		SDFR_HIP(hipEventSynchronize(r->ev_end));
+		if (!r->lane.have_render) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "nothing rendered yet");
+		SDFR_HIP(hipEventSynchronize(r->lane.ev_end));
 		float ms = 0.f;
-		SDFR_HIP(hipEventElapsedTime(&ms, r->ev_begin, r->ev_end));
+		SDFR_HIP(hipEventElapsedTime(&ms, r->lane.ev_begin, r->lane.ev_end));
 		out->ms_gpu = ms;
 		RenderTotals t[2];
-		SDFR_HIP(hipMemcpy(t, r->d_totals, sizeof t, hipMemcpyDeviceToHost));
-		for (int k = 0; k < r->totals_parts; ++k)
+		SDFR_HIP(hipMemcpy(t, r->lane.d_totals, sizeof t, hipMemcpyDeviceToHost));
+		for (int k = 0; k < r->lane.totals_parts; ++k)
 		{
 			out->pixels += t[k].pixels;
 			out->rays += t[k].rays;
@@ -1064,11 +1042,11 @@ int sdfr_get_timings(sdfr_renderer *r, sdfr_timing *out, int capacity)
 			}
 			++n;
 		};
-		if (r->have_render)
+		if (r->lane.have_render)
 		{
-			SDFR_HIP(hipEventSynchronize(r->ev_end));
+			SDFR_HIP(hipEventSynchronize(r->lane.ev_end));
 			float ms = 0.f;
-			SDFR_HIP(hipEventElapsedTime(&ms, r->ev_begin, r->ev_end));
+			SDFR_HIP(hipEventElapsedTime(&ms, r->lane.ev_begin, r->lane.ev_end));
 			put("setup", r->ms_setup);
 			put("draw", ms);
 			for (int i = 0; r->last_wavefront && r->last_profiled && i < r->last_rounds && i < 16; ++i)
@@ -1083,7 +1061,7 @@ int sdfr_get_timings(sdfr_renderer *r, sdfr_timing *out, int capacity)
 				put(nm, b);
 			}
 		}
-		if (r->have_render && r->have_xfer)
+		if (r->lane.have_render && r->have_xfer)
 		{
 			// the last sdfr_render_gather's transfer on the comm stream: rank 0 receives world - 1 messages at once (one per link),
 			// a peer sends one; the bytes ride in the name so that a caller can turn the time into a rate

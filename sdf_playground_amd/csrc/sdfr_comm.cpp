@@ -227,7 +227,7 @@ int gather_render(sdfr_renderer *r, const sdfr_comm *c, const GatherShape &g)
 	if (r->wire_bytes < need)
 	{
 		// frames still in flight on either stream read or write the old buffer
-		SDFR_HIP(hipStreamSynchronize(r->stream));
+		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 		SDFR_HIP(hipStreamSynchronize(r->comm_stream));
 		(void)hipFree(r->d_wire);
 		r->d_wire = nullptr;
@@ -235,14 +235,12 @@ int gather_render(sdfr_renderer *r, const sdfr_comm *c, const GatherShape &g)
 		SDFR_HIP(hipMalloc(&r->d_wire, need));
 		r->wire_bytes = need;
 	}
-	SDFR_HIP(hipEventRecord(r->ev_begin, r->stream));
-	SDFR_HIP(hipMemsetAsync(r->d_totals, 0, 2 * sizeof(RenderTotals), r->stream));
-	r->caller_times = true;
+	SDFR_HIP(hipEventRecord(r->lane.ev_begin, r->lane.stream));
+	SDFR_HIP(hipMemsetAsync(r->lane.d_totals, 0, 2 * sizeof(RenderTotals), r->lane.stream));
 	int rc = SDFR_OK;
-	if (g.rank_bytes) rc = render_impl(r, g.width, g.height, c->rank, g.world, r->d_wire, g.wire_format, 0, nullptr, RENDER_STRIPS, r->d_totals);
-	r->caller_times = false;
+	if (g.rank_bytes) rc = render_impl(r, g.width, g.height, c->rank, g.world, r->d_wire, g.wire_format, 0, nullptr, RENDER_STRIPS, r->lane.d_totals, true);
 	if (rc != SDFR_OK) return rc;
-	SDFR_HIP(hipEventRecord(r->ev_strips, r->stream));
+	SDFR_HIP(hipEventRecord(r->ev_strips, r->lane.stream));
 	SDFR_HIP(hipStreamWaitEvent(r->comm_stream, r->ev_strips, 0));
 	return SDFR_OK;
 }
@@ -284,18 +282,16 @@ int gather_finish(sdfr_renderer *r, const sdfr_comm *c, const GatherShape &g, vo
 		}
 		if (r->priv_count > 0)
 		{
-			r->caller_times = true;
-			const int rc = render_impl(r, g.width, g.height, 0, 1, root_image, g.image_format, 0, nullptr, RENDER_PRIVATE, r->d_totals + 1);
-			r->caller_times = false;
+			const int rc = render_impl(r, g.width, g.height, 0, 1, root_image, g.image_format, 0, nullptr, RENDER_PRIVATE, r->lane.d_totals + 1, true);
 			if (rc != SDFR_OK) return rc;
 			parts = 2;
 		}
 	}
 	SDFR_HIP(hipEventRecord(r->ev_gathered, r->comm_stream));
-	SDFR_HIP(hipStreamWaitEvent(r->stream, r->ev_gathered, 0));
-	SDFR_HIP(hipEventRecord(r->ev_end, r->stream));
-	r->totals_parts = parts;
-	r->have_render = true;
+	SDFR_HIP(hipStreamWaitEvent(r->lane.stream, r->ev_gathered, 0));
+	SDFR_HIP(hipEventRecord(r->lane.ev_end, r->lane.stream));
+	r->lane.totals_parts = parts;
+	r->lane.have_render = true;
 	r->last_wavefront = false;
 	return SDFR_OK;
 }

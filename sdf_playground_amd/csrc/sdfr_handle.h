@@ -16,8 +16,27 @@
 
 struct sdfr_renderer
 {
+	// What one frame in flight owns: its stream, its workspace (ray queue, counter records, tile cursors with the row order
+	// learned from ITS last frame), its counters and its two events.  `lane` is the lane of the frame submitted last; every
+	// entry point but sdfr_render works on it.  With two frames in flight (sdfr_set_frames_in_flight) `other` is the lane of
+	// the frame before, and sdfr_render swaps the two before it launches.
+	struct Lane
+	{
+		hipStream_t stream = nullptr; // user_stream with one frame in flight; the library's own with two
+		sdfr::WavefrontWorkspace ws = {};
+		size_t wavefront_capacity = 0; // pixels the wavefront-only part of `ws` is allocated for
+		sdfr::RenderTotals *d_totals = nullptr; // [2]: counters of the last launch; [1] = the private strips of a gather (sdfr_comm.cpp)
+		int totals_parts = 1;                   // how many of them the last render filled
+		hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+		bool have_render = false;
+		const char *out_lo = nullptr, *out_hi = nullptr; // device range its last frame was rendered into (two frames in flight only)
+		const char *pst_lo = nullptr, *pst_hi = nullptr; // ... and the device range of that frame's pixel_stats
+	};
+	Lane lane, other;
+	int frames_in_flight = 1;
+	hipStream_t user_stream = nullptr; // what sdfr_set_stream gave (in use while frames_in_flight == 1)
+
 	int device = 0;
-	hipStream_t stream = nullptr;
 	int scene = -1; // index of an ahead-of-time scene, or SDFR_SCENE_COUNT: `jit` holds a scene compiled at run time
 	sdfr::JitScene jit;
 	int schedule = SDFR_SCHEDULE_PIXEL; // the faster one on every measured scene
@@ -30,10 +49,6 @@ struct sdfr_renderer
 	std::vector<std::string> scene_var_slots; // slot k of FrameU::scene_var <- this variable
 	mutable std::string error;
 
-	sdfr::RenderTotals *d_totals = nullptr; // [2]: counters of the last launch; [1] = the private strips of a gather (sdfr_comm.cpp)
-	int totals_parts = 1;             // how many of them the last render filled
-	sdfr::WavefrontWorkspace ws = {};
-	size_t wavefront_capacity = 0; // pixels the wavefront-only part of `ws` is allocated for
 	void *d_stage = nullptr; // staging image for host-destination renders
 	size_t stage_bytes = 0;
 	uint32_t *d_pstat = nullptr;
@@ -42,7 +57,6 @@ struct sdfr_renderer
 	void *pinned_host = nullptr;
 	size_t pinned_bytes = 0;
 
-	hipEvent_t ev_begin = nullptr, ev_end = nullptr;
 	hipEvent_t ev_post[3] = {}; // before / between / after the two post-processing kernels
 	bool have_post = false;
 	bool step_shortcuts = true; // sdfr_set_step_shortcuts
@@ -51,7 +65,6 @@ struct sdfr_renderer
 	double ms_setup = 0.0;      // host time of the last latch_frame (+ Scene::prepare of a run-time scene)
 	hipEvent_t ev_march[32] = {}, ev_shade[32] = {};
 	int last_rounds = 0;
-	bool have_render = false;
 	bool last_wavefront = false;
 	bool last_profiled = false;
 
@@ -64,32 +77,8 @@ struct sdfr_renderer
 	size_t xfer_bytes = 0;                      // bytes this rank sent (peers) or received (rank 0) in that transfer
 	void *d_wire = nullptr;    // this rank's compact strips; on the root: world x that, slot 0 = its own
 	size_t wire_bytes = 0;
-	bool caller_times = false; // render_impl leaves ev_begin / ev_end to its caller
 	std::vector<void *> comms_used; // sdfr_comm* whose transfers ran on comm_stream (sdfr_comm.cpp keeps both sides of the list)
 
-	// Two frames in flight inside one handle (sdfr_set_frames_in_flight).  What a frame in flight owns -- its stream, its
-	// workspace (ray queue, counter records, tile cursors with the row order learned from ITS last frame), its counters
-	// and its two events -- is a Lane; the members above (`stream`, `ws`, `wavefront_capacity`, `d_totals`, `totals_parts`,
-	// `ev_begin`, `ev_end`, `have_render`) are the CURRENT lane's, `other` is the lane of the frame before.  sdfr_render swaps the two
-	// before it launches, so everything else in the library keeps working on "the handle's stream and workspace".
-	struct Lane
-	{
-		hipStream_t stream = nullptr;
-		sdfr::WavefrontWorkspace ws = {};
-		size_t wavefront_capacity = 0;
-		sdfr::RenderTotals *d_totals = nullptr;
-		int totals_parts = 1;
-		hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-		bool have_render = false;
-		const char *out_lo = nullptr, *out_hi = nullptr; // device range its last frame was rendered into
-		const char *pst_lo = nullptr, *pst_hi = nullptr; // ... and the device range of that frame's pixel_stats
-	};
-	int frames_in_flight = 1;
-	Lane other;
-	hipStream_t lane_streams[2] = {nullptr, nullptr}; // the library's own streams while frames_in_flight == 2
-	hipStream_t user_stream = nullptr;                // what sdfr_set_stream gave (in use while frames_in_flight == 1)
-	const char *out_lo = nullptr, *out_hi = nullptr;  // the current lane's
-	const char *pst_lo = nullptr, *pst_hi = nullptr;
 	unsigned launches = 0; // render launches so far: did a call that failed launch anything before it failed
 };
 
@@ -140,10 +129,11 @@ enum RenderMode { RENDER_FULL, RENDER_STRIPS, RENDER_PRIVATE };
 size_t image_bytes(size_t pixels, int format);
 bool is_wire_format(int format);
 
-// one launch of the handle's scene over the rows `mode` selects (sdfr_api.cpp).  `totals` receives
-// the launch's counters (nullptr: the handle's d_totals).
+// one launch of the handle's scene over the rows `mode` selects, on the current lane (sdfr_api.cpp).  `totals` receives
+// the launch's counters (nullptr: the lane's d_totals).  caller_times: the caller records the lane's ev_begin / ev_end
+// and sets its totals_parts (a gather times strips, transfer and assembly as one frame).
 int render_impl(sdfr_renderer *r, int width, int height, int rank, int world, void *out, int format, int out_on_host, uint32_t *pixel_stats,
-	RenderMode mode, RenderTotals *totals = nullptr);
+	RenderMode mode, RenderTotals *totals = nullptr, bool caller_times = false);
 
 // the stream and events of a gathered frame (sdfr_comm.cpp)
 int gather_prepare_streams(sdfr_renderer *r);
