@@ -26,10 +26,11 @@ static uint32_t work_items(const FrameU &U, const RowMap &rm) { return launch_wo
 // =================================================================================================
 // PIXEL schedule (body: sdfr_pixel_kernel.h)
 // =================================================================================================
+// the shading's noise reads its gradients from LDS where the scene asks for it (PixelNoiseGrads); the debug variants keep the formula
 template <class Scene, bool DBG>
 __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_pixel(PixelKernelArgs args)
 {
-	pixel_kernel<Scene, DBG>(args);
+	pixel_kernel<Scene, DBG, typename PickNoiseGrads<!DBG && PixelNoiseGrads<Scene>::table>::type>(args);
 }
 
 // =================================================================================================

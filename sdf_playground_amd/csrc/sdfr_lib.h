@@ -342,24 +342,26 @@ SDF_HD vec3 checker_color(vec3 p, vec3 dir, vec3 off_right, vec3 off_bottom)
 }
 
 // sky (sdf_common.hlsl:85-94) with the frame-uniform rotation sin/cos(-stime*0.025) passed in
+template <class NG = NoiseGradFormula>
 SDF_HD vec3 sky_color(vec3 dir, float rot_s, float rot_c)
 {
 	vec2 r = rot2(V2(dir.x, dir.z), rot_s, rot_c);
 	dir.x = r.x;
 	dir.z = r.y;
-	float n = turbulence3(dir * V3(1.f, 6.f, 1.f) * 2.5f);
+	float n = turbulence3<NG>(dir * V3(1.f, 6.f, 1.f) * 2.5f);
 	vec3 blue = V3(43.f, 164.f, 247.f) / 255.f;
 	vec3 white = V3(212.f, 224.f, 238.f) / 255.f;
 	vec3 sky = lerp(blue, white, n) * 1.2f;
 	return lerp(V3s(0.25f), sky, sat1(dir.y * 8.f + 0.125f));
 }
 // the same sky with the cloud mix remapped to n * scale + bias (scenes with their own sky)
+template <class NG = NoiseGradFormula>
 SDF_HD vec3 sky_color_mix(vec3 dir, float rot_s, float rot_c, float scale, float bias)
 {
 	vec2 r = rot2(V2(dir.x, dir.z), rot_s, rot_c);
 	dir.x = r.x;
 	dir.z = r.y;
-	float n = turbulence3(dir * V3(1.f, 6.f, 1.f) * 2.5f);
+	float n = turbulence3<NG>(dir * V3(1.f, 6.f, 1.f) * 2.5f);
 	vec3 blue = V3(43.f, 164.f, 247.f) / 255.f;
 	vec3 white = V3(212.f, 224.f, 238.f) / 255.f;
 	vec3 sky = lerp(blue, white, n * scale + bias) * 1.2f;
@@ -439,22 +441,25 @@ SDF_HD vec4 braid(vec2 uv, float width, float run_length, float run_flip, vec2 m
 }
 
 // ---- procedural materials (sdf_materials.hlsl:6-31) --------------------------------------
+template <class NG = NoiseGradFormula>
 SDF_HD vec3 mat_marble(vec3 p, vec3 tint)
 {
-	float wave = dot(V3(3.f, 2.f, 1.f), p) * 2.f + turbulence3(p) * 5.f;
+	float wave = dot(V3(3.f, 2.f, 1.f), p) * 2.f + turbulence3<NG>(p) * 5.f;
 	float s = (1.f + sin1(wave)) * 0.5f;
 	s = pow1(s, 0.5f);
 	return tint * s;
 }
+template <class NG = NoiseGradFormula>
 SDF_HD vec3 mat_wood(vec3 p)
 {
-	float dist = sqrt1(p.x * p.x + p.y * p.y) + 0.125f * turbulence3(p);
+	float dist = sqrt1(p.x * p.x + p.y * p.y) + 0.125f * turbulence3<NG>(p);
 	float s = 0.5f * abs1(sin1(2.f * 12.f * dist * 3.14159f));
 	return V3(0.3125f + s, 0.117f + s, 0.117f);
 }
+template <class NG = NoiseGradFormula>
 SDF_HD vec4 mat_fire(vec3 p, float threshold)
 {
-	float turb = turbulence3(p) + 0.35f;
+	float turb = turbulence3<NG>(p) + 0.35f;
 	turb = turb > threshold ? turb : 0.f;
 	return V4(5.f * turb, 2.f * turb, 1.f * turb, 0.5f * turb);
 }

@@ -20,13 +20,12 @@ SDF_HD float pcg_hashf(uint32_t v) { return (float)pcg_hash(v) / (float)0xFFFFFF
 SDF_HD float noise_mod289(float x) { return x - floor1(x * 0.00346020761245674740484429065744f) * 289.0f; }
 SDF_HD float noise_permute(float x) { return noise_mod289(x * x * 34.0f + x); }
 
-// gradient of one simplex corner dotted with the corner offset `xc`, times the corner's
-// falloff weight: returns (m^4, dot(grad, xc)) as (x, y)
-SDF_HD vec2 simplex_corner(float p, vec3 xc)
+// normalised gradient number j of snoise3 (the 7 x 7 points of a square folded onto an octahedron); j = p mod 49, computed
+// by the corner.  The only definition of these gradients: the table below is filled by this same function.
+SDF_HD vec3 simplex_grad(float j)
 {
 	const float n_ = 0.142857142857f;
 	const float ns_x = n_ * 2.0f - 0.0f, ns_y = n_ * 0.5f - 1.0f, ns_z = n_ * 1.0f - 0.0f;
-	float j = p - 49.0f * floor1(p * ns_z * ns_z);
 	float xq = floor1(j * ns_z);
 	float yq = floor1(j - 7.0f * xq);
 	float gx = xq * ns_x + ns_y;
@@ -36,13 +35,62 @@ SDF_HD vec2 simplex_corner(float p, vec3 xc)
 	float sy = floor1(gy) * 2.0f + 1.0f;
 	float sh = -step1(h, 0.0f);
 	vec3 g = V3(gx + sx * sh, gy + sy * sh, h);
-	g = g * rsqrt1(dot(g, g));
+	return g * rsqrt1(dot(g, g));
+}
+
+// Where a corner gets its gradient from: the gradient source NG of snoise3 / turbulence3 and of the shading that calls them.
+// NoiseGradFormula evaluates simplex_grad.  NoiseGradTable<Tab> reads simplex_grad(k), k = 0..63, from a table that Tab holds
+// (Tab::at(c, k): component c of gradient k; the pixel kernel keeps it in LDS, sdfr_pixel_kernel.h) and clears `ok` unless j
+// is that k -- every j the permute chain produces is an integer in 0..48 (tests/test_noise_table_cpu.py), and -0 reads entry 0,
+// simplex_grad(-0) being simplex_grad(+0) bit for bit.  A lane that ends with `ok` cleared evaluates the noise once more with
+// the formula (snoise3, turbulence3), so the bits are the formula's whatever the input.  The check is per lane and the
+// recomputation sits after the straight-line table code, not in each corner: a branch per corner costs the register
+// allocator more than the formula it skips.
+struct NoiseGradFormula
+{
+	static SDF_HD vec3 grad(float j, bool &) { return simplex_grad(j); }
+};
+#define SDFR_NOISE_GRADS 64
+template <class Tab>
+struct NoiseGradTable
+{
+	static SDF_HD vec3 grad(float j, bool &ok)
+	{
+		// the clamp keeps the conversion defined (NaN -> the last entry) and the index inside the table whatever j is; clamped
+		// from above first, which left the headline's march loops with the better register draw (tools/kernel_resources.py)
+		const uint32_t k = (uint32_t)max1(min1(j, (float)(SDFR_NOISE_GRADS - 1)), 0.0f);
+		ok = ok & ((float)k == j);
+		return V3(Tab::at(0, k), Tab::at(1, k), Tab::at(2, k));
+	}
+};
+
+// The input of that second evaluation, opaque to the compiler: shared with the table path, the corner offsets and weights
+// would stay live to the end of the noise and spill.
+SDF_HD vec3 noise_recompute_input(vec3 v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z));
+#endif
+	return v;
+}
+
+// gradient of one simplex corner dotted with the corner offset `xc`, times the corner's
+// falloff weight: returns (m^4, dot(grad, xc)) as (x, y)
+template <class NG>
+SDF_HD vec2 simplex_corner(float p, vec3 xc, bool &ok)
+{
+	const float n_ = 0.142857142857f;
+	const float ns_z = n_ * 1.0f - 0.0f;
+	float j = p - 49.0f * floor1(p * ns_z * ns_z);
+	vec3 g = NG::grad(j, ok);
 	float m = max1(0.6f - dot(xc, xc), 0.0f);
 	m = m * m;
 	return V2(m * m, dot(g, xc));
 }
 
-SDF_HD float snoise3(vec3 v)
+// the noise; `ok` as NG::grad leaves it
+template <class NG>
+SDF_HD float snoise3_grads(vec3 v, bool &ok)
 {
 	const float Cx = 0.166666666666666667f, Cy = 0.333333333333333333f;
 	// skew to the simplex grid
@@ -66,11 +114,20 @@ SDF_HD float snoise3(vec3 v)
 	float p2 = noise_permute(noise_permute(noise_permute(i.z + i2.z) + i.y + i2.y) + i.x + i2.x);
 	float p3 = noise_permute(noise_permute(noise_permute(i.z + 1.0f) + i.y + 1.0f) + i.x + 1.0f);
 
-	vec2 c0 = simplex_corner(p0, x0);
-	vec2 c1 = simplex_corner(p1, x1);
-	vec2 c2 = simplex_corner(p2, x2);
-	vec2 c3 = simplex_corner(p3, x3);
+	vec2 c0 = simplex_corner<NG>(p0, x0, ok);
+	vec2 c1 = simplex_corner<NG>(p1, x1, ok);
+	vec2 c2 = simplex_corner<NG>(p2, x2, ok);
+	vec2 c3 = simplex_corner<NG>(p3, x3, ok);
 	return 42.0f * dot(V4(c0.x, c1.x, c2.x, c3.x), V4(c0.y, c1.y, c2.y, c3.y));
+}
+
+template <class NG = NoiseGradFormula>
+SDF_HD float snoise3(vec3 v)
+{
+	bool ok = true;
+	const float n = snoise3_grads<NG>(v, ok);
+	if (ok) return n;
+	return snoise3_grads<NoiseGradFormula>(noise_recompute_input(v), ok);
 }
 
 // ---- 2-D (noise.hlsl:142-203) ------------------------------------------------------------------------------
@@ -167,9 +224,19 @@ SDF_HD float snoise4(vec4 v)
 	return 49.0f * (dot(V3(c0.x, c1.x, c2.x), V3(c0.y, c1.y, c2.y)) + dot(V2(c3.x, c4.x), V2(c3.y, c4.y)));
 }
 
+template <class NG>
+SDF_HD float turbulence3_grads(vec3 p, bool &ok)
+{
+	return div_c((snoise3_grads<NG>(p, ok) + snoise3_grads<NG>(p * 2.f, ok) / 2.f + snoise3_grads<NG>(p * 4.f, ok) / 4.f + snoise3_grads<NG>(p * 8.f, ok) / 8.f) * 8.f,
+		15.f, 1.0f / 15.f);
+}
+template <class NG = NoiseGradFormula>
 SDF_HD float turbulence3(vec3 p)
 {
-	return div_c((snoise3(p) + snoise3(p * 2.f) / 2.f + snoise3(p * 4.f) / 4.f + snoise3(p * 8.f) / 8.f) * 8.f, 15.f, 1.0f / 15.f);
+	bool ok = true;
+	const float t = turbulence3_grads<NG>(p, ok);
+	if (ok) return t;
+	return turbulence3_grads<NoiseGradFormula>(noise_recompute_input(p), ok);
 }
 
 } // namespace sdfr

@@ -466,7 +466,8 @@ SDF_HD vec3 light_colour(const Light &L)
 // Shade a ray that hit the scene (pshader_sdf.hlsl:317-620).  Returns the colour this ray
 // adds to the pixel (already multiplied by the ray's contribution); updates `hdr`; pushes
 // secondary rays.
-template <class Scene, bool DBG, class Store, bool INL = false>
+// NG: where the noise of the procedural materials gets its gradients (sdfr_noise.h)
+template <class Scene, bool DBG, class Store, bool INL = false, class NG = NoiseGradFormula>
 SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, const PixelRay &px, const HitInfo &hit, float max_range,
 	float &hdr, Spawner<Store> &q, InlineShadows *inl = nullptr)
 {
@@ -567,18 +568,18 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 			hdr = 0.f;
 			break;
 		case MAT_WOOD:
-			diffuse = diffuse + mat_wood(m.mpos);
+			diffuse = diffuse + mat_wood<NG>(m.mpos);
 			break;
 		case MAT_MARBLE_DARK:
-			diffuse = diffuse + mat_marble(m.mpos, V3(0.556f, 0.478f, 0.541f));
+			diffuse = diffuse + mat_marble<NG>(m.mpos, V3(0.556f, 0.478f, 0.541f));
 			break;
 		case MAT_MARBLE_LIGHT:
-			diffuse = diffuse + mat_marble(m.mpos, V3(0.7f, 0.7f, 0.7f));
+			diffuse = diffuse + mat_marble<NG>(m.mpos, V3(0.7f, 0.7f, 0.7f));
 			break;
 		case MAT_FIRE:
 		{
 			float fadeout = sat1(dot(-view_dir, n));
-			vec4 fc = mat_fire(m.mpos, 1.f - fadeout);
+			vec4 fc = mat_fire<NG>(m.mpos, 1.f - fadeout);
 			color = color + V3(fc.x, fc.y, fc.z);
 			m.diffuse = V4(1.f, 1.f, 1.f, sat1(fc.w));
 			break;
@@ -777,12 +778,23 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 
 // A ray that left the scene (pshader_sdf.hlsl:621-632): an escaped shadow ray delivers the
 // light it carries, any other ray sees the background.
-template <class Scene>
+// The background through the gradient source NG where the scene's takes one (the shared sky: background<NG>), else as it is.
+template <class Scene, class NG, class = void>
+struct SceneBackground
+{
+	static SDF_HD vec3 get(const FrameU &U, vec3 dir, uint32_t iter) { return Scene::background(U, dir, iter); }
+};
+template <class Scene, class NG>
+struct SceneBackground<Scene, NG, typename VoidOfN<decltype(Scene::template background<NG>(*(const FrameU *)0, V3s(0.f), 0u))>::type>
+{
+	static SDF_HD vec3 get(const FrameU &U, vec3 dir, uint32_t iter) { return Scene::template background<NG>(U, dir, iter); }
+};
+template <class Scene, class NG = NoiseGradFormula>
 SDF_HD vec3 shade_miss(const FrameU &U, const RayRec &ray, uint32_t iter)
 {
 	if (ray_is_shadow(ray))
 		return V3s(0.f) + ray.contrib;
-	return V3s(0.f) + Scene::background(U, ray.dir, iter) * ray.contrib;
+	return V3s(0.f) + SceneBackground<Scene, NG>::get(U, ray.dir, iter) * ray.contrib;
 }
 
 } // namespace sdfr

@@ -433,9 +433,45 @@ struct TileQueue
 	}
 };
 
+// ---- the gradients of snoise3 in LDS (NoiseGradTable, sdfr_noise.h) ---------------------------------------------------------
+// 64 gradients x 3 components, 768 B per block: 4 352 + 768 = 5 120 B, which still fits 8 blocks of one wave per SIMD in a CU's
+// 160 KiB.  Component planes, so that a lookup is three ds_read_b32 off one address (k * 4 + 0 / 256 / 512).  The kernel fills
+// the table with the device's own simplex_grad before its first tile; a wave-sized block needs no more than the barrier.
+__shared__ float noise_grad_lds[3][SDFR_NOISE_GRADS];
+struct NoiseGradLdsTab
+{
+	static __device__ __forceinline__ float at(int c, uint32_t k) { return noise_grad_lds[c][k]; }
+};
+typedef NoiseGradTable<NoiseGradLdsTab> NoiseGradLds;
+static_assert(SDFR_NOISE_GRADS == SDFR_PIXEL_BLOCK, "one lane fills one gradient");
+// The gradient source of a scene's pixel kernel: the table where the scene declares `noise_grad_table = true`, the formula
+// elsewhere.  The table pays where the shading's turbulence3 runs in most waves; elsewhere it only draws LDS and a different
+// register assignment (the march loops of the other configuration scenes came out with more spills or more one-bank fma).
+template <class Scene, class = void>
+struct PixelNoiseGrads { static constexpr bool table = false; };
+template <class Scene>
+struct PixelNoiseGrads<Scene, typename VoidOf<decltype(Scene::noise_grad_table)>::type> { static constexpr bool table = Scene::noise_grad_table; };
+template <bool TABLE>
+struct PickNoiseGrads { typedef NoiseGradFormula type; };
+template <>
+struct PickNoiseGrads<true> { typedef NoiseGradLds type; };
+template <class NG>
+__device__ __forceinline__ void noise_grads_fill() {}
+template <>
+__device__ __forceinline__ void noise_grads_fill<NoiseGradLds>()
+{
+	const uint32_t k = lane_now();
+	const vec3 g = simplex_grad((float)k);
+	noise_grad_lds[0][k] = g.x;
+	noise_grad_lds[1][k] = g.y;
+	noise_grad_lds[2][k] = g.z;
+	__syncthreads();
+}
+
 // body of the pixel kernel; the __global__ wrappers are k_pixel (scenes compiled ahead of time,
 // sdfr_kernels_group.hip) and the extern "C" kernels sdfr_jit.cpp generates around a run-time scene
-template <class Scene, bool DBG>
+// NG: the gradient source of the shading's noise -- the formula unless the wrapper passes the LDS table (NoiseGradLds)
+template <class Scene, bool DBG, class NG = NoiseGradFormula>
 __device__ __forceinline__ void pixel_kernel(const PixelKernelArgs &args_by_value)
 {
 	// The argument block is the kernarg segment.  Read through the by-value parameter, the compiler loads every field it
@@ -462,6 +498,7 @@ __device__ __forceinline__ void pixel_kernel(const PixelKernelArgs &args_by_valu
 	// the fold kernel that follows adds into the totals: clear them here (kernel boundary = ordering)
 	if (blockIdx.x == 0 && threadIdx.x < 4) reinterpret_cast<unsigned long long *>(totals)[threadIdx.x] = 0ull;
 	__shared__ float lds_rays[SDFR_LDS_RAY_FIELDS + SDFR_LDS_PIXEL_RAY_FIELDS][SDFR_PIXEL_BLOCK];
+	noise_grads_fill<NG>();
 #ifdef SDFR_WAVE_TRACE
 	const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime(); // 100 MHz
 	uint32_t trace_tiles = 0, trace_ticks = 0; // tiles rendered; 10-ns ticks from taking a tile to having rendered it, summed
@@ -508,7 +545,7 @@ __device__ __forceinline__ void pixel_kernel(const PixelKernelArgs &args_by_valu
 		{
 			GlobalRayStore backing = {ray_queue, cap, pc.pid};
 			LdsCachedRayStore store(backing, &lds_rays[0][lane]);
-			vec4 v = render_pixel<Scene, DBG, LdsCachedRayStore>(U, pc.px, pc.py, pcnt, store);
+			vec4 v = render_pixel<Scene, DBG, LdsCachedRayStore, NG>(U, pc.px, pc.py, pcnt, store);
 			store_pixel(out, format, pc.pid, v, (uint32_t)rm.local_rows * (uint32_t)U.width);
 			if (pixel_stats)
 			{

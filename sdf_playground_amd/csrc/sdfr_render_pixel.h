@@ -128,8 +128,9 @@ struct PixelCounters
 
 // `store` holds the pixel's pending rays (put/get by slot).  The primary ray never enters
 // it: the reference pops it from slot 0 before anything is pushed (pshader_sdf.hlsl:289-294),
-// so the queue is empty -- and slot 0 free again -- when the first hit is shaded.
-template <class Scene, bool DBG, class Store>
+// so the queue is empty -- and slot 0 free again -- when the first hit is shaded.  NG: the gradient source of the shading's
+// noise (sdfr_noise.h).
+template <class Scene, bool DBG, class Store, class NG = NoiseGradFormula>
 SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, Store &store)
 {
 	SDFR_CLK(c_begin);
@@ -272,13 +273,13 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 				inl.acc = acc;
 				inl.budget = U.bounce_count - 1 - bounce;
 				inl.taken = 0;
-				out = shade_hit<Scene, DBG, Store, true>(U, F, ray, store.pixel_ray_kept(), hit, max_range, hdr, q, &inl);
+				out = shade_hit<Scene, DBG, Store, true, NG>(U, F, ray, store.pixel_ray_kept(), hit, max_range, hdr, q, &inl);
 				acc = inl.acc;
 				bounce += inl.taken;
 				cnt.rays += (uint32_t)inl.taken;
 			}
 			else
-				out = shade_hit<Scene, DBG, Store>(U, F, ray, store.pixel_ray_kept(), hit, max_range, hdr, q);
+				out = shade_hit<Scene, DBG, Store, false, NG>(U, F, ray, store.pixel_ray_kept(), hit, max_range, hdr, q);
 			store.keep_hdr(hdr);
 			depths = q.depths;
 			count = q.count;
@@ -291,7 +292,7 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		}
 		else
 		{
-			out = shade_miss<Scene>(U, ray, m.iter);
+			out = shade_miss<Scene, NG>(U, ray, m.iter);
 #ifdef SDFR_PHASE_CLOCKS
 			asm volatile("" : "+v"(out.x), "+v"(out.y), "+v"(out.z));
 #endif

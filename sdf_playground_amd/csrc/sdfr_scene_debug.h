@@ -62,7 +62,8 @@ struct SceneDebugMaterials
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // normal_test: a diagnostic scene for the one callback of the scene ABI that no reference scene fills in, map_normal
@@ -135,7 +136,8 @@ struct SceneNormalTest
 	}
 	static SDF_HD bool light(const FrameU &, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 } // namespace sdfr

@@ -54,7 +54,8 @@ struct SceneFastSphere
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -169,7 +170,8 @@ struct SceneCubeSea
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -180,6 +182,7 @@ struct SceneLabyrinth
 	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_render_pixel.h)
 	static constexpr int retire_after = 4; // configuration 3, two sessions: 1.252 (1) / 1.236 (2) / 1.224 (3) / 1.224 (4) / 1.233 (5) / 1.237 (8) / 1.243 (16) ms
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
+	static constexpr bool noise_grad_table = true; // marble walls, vase and sky: turbulence3 in ~80 % of tiles (sdfr_pixel_kernel.h)
 	static const char *variables() { return ""; }
 	enum { SU_FIRE_SCROLL = 0 };
 	static SDF_HD void prepare(FrameU &U) { U.su[SU_FIRE_SCROLL] = U.stime * 3.f; }
@@ -346,7 +349,8 @@ struct SceneLabyrinth
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -449,7 +453,8 @@ struct SceneFractal
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -676,7 +681,8 @@ struct SceneLense
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	// the scene carries its own copy of the sky (sdf_scene_lense.hlsl:108-117), same arithmetic
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -764,7 +770,8 @@ struct SceneGems
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -860,7 +867,8 @@ struct SceneLightShadows
 		return true;
 	}
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 } // namespace sdfr

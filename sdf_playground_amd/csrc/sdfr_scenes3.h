@@ -92,7 +92,8 @@ struct SceneFractal2
 		return true;
 	}
 	static SDF_HD float ambient() { return 0.1f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -144,7 +145,8 @@ struct SceneShell
 		return true;
 	}
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color_mix(dir, U.sky_s, U.sky_c, 1.f, 0.f); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color_mix<NG>(dir, U.sky_s, U.sky_c, 1.f, 0.f); }
 };
 
 // =========================================================================================
@@ -251,7 +253,8 @@ struct SceneSpiral
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -370,7 +373,8 @@ struct SceneTerrain
 	}
 	static SDF_HD bool light(const FrameU &U, int i, Light &L) { return sun_light(i, L); }
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 // =========================================================================================
@@ -465,7 +469,8 @@ struct SceneTiling
 		return true;
 	}
 	static SDF_HD float ambient() { return 0.075f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color_mix(dir, U.sky_s, U.sky_c, 0.8f, 0.2f); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color_mix<NG>(dir, U.sky_s, U.sky_c, 0.8f, 0.2f); }
 };
 
 } // namespace sdfr

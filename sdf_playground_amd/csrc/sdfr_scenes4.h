@@ -286,7 +286,8 @@ struct SceneTree
 		return true;
 	}
 	static SDF_HD float ambient() { return 0.2f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+	template <class NG = NoiseGradFormula>
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color<NG>(dir, U.sky_s, U.sky_c); }
 };
 
 } // namespace sdfr

@@ -1,0 +1,226 @@
+"""The gradient table of snoise3 (sdf_playground_amd/csrc/sdfr_noise.h: simplex_grad, NoiseGradTable; the pixel kernel keeps the
+table in LDS, sdfr_pixel_kernel.h).
+
+A corner of snoise3 hashes its lattice point to p and takes gradient j = p - 49 floor(p / 49) of simplex_grad.  The pixel kernel of
+a scene that declares `noise_grad_table` reads simplex_grad(k), k = 0..63, from a table its own lanes fill with that function, and
+evaluates the noise once more with the formula for a lane whose j was not one of those integers.  Checked here, on the CPU with
+the product's headers: simplex_grad is the corner's former inline formula bit for bit; every j the permute chain produces from
+the lattice coordinates of |x| < 2^24 is an integer in 0..48 (so the table is all real inputs need); and snoise3 / turbulence3
+through a table filled by simplex_grad equal the formula bit for bit, on random, huge, negative, lattice and non-finite points.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
+
+SOURCE = r"""
+#include "sdfr_noise.h"
+#include <cstring>
+#include <set>
+using namespace sdfr;
+
+// the gradient of a corner as simplex_corner computed it inline before simplex_grad existed
+static vec3 old_inline_grad(float p_j)
+{
+	const float n_ = 0.142857142857f;
+	const float ns_x = n_ * 2.0f - 0.0f, ns_y = n_ * 0.5f - 1.0f, ns_z = n_ * 1.0f - 0.0f;
+	float j = p_j;
+	float xq = floor1(j * ns_z);
+	float yq = floor1(j - 7.0f * xq);
+	float gx = xq * ns_x + ns_y;
+	float gy = yq * ns_x + ns_y;
+	float h = 1.0f - abs1(gx) - abs1(gy);
+	float sx = floor1(gx) * 2.0f + 1.0f;
+	float sy = floor1(gy) * 2.0f + 1.0f;
+	float sh = -step1(h, 0.0f);
+	vec3 g = V3(gx + sx * sh, gy + sy * sh, h);
+	g = g * rsqrt1(dot(g, g));
+	return g;
+}
+
+struct HostTab
+{
+	static float t[3][SDFR_NOISE_GRADS];
+	static float at(int c, uint32_t k) { return t[c][k]; }
+};
+float HostTab::t[3][SDFR_NOISE_GRADS];
+typedef NoiseGradTable<HostTab> HostGrads;
+
+extern "C" void nt_fill()
+{
+	for (int k = 0; k < SDFR_NOISE_GRADS; ++k)
+	{
+		const vec3 g = simplex_grad((float)k);
+		HostTab::t[0][k] = g.x; HostTab::t[1][k] = g.y; HostTab::t[2][k] = g.z;
+	}
+}
+
+// out: n x 6 floats, simplex_grad(j) then the old inline formula
+extern "C" void nt_grads(const float *j, float *out, long long n)
+{
+	for (long long k = 0; k < n; ++k)
+	{
+		const vec3 a = simplex_grad(j[k]), b = old_inline_grad(j[k]);
+		float *o = out + 6 * k;
+		o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = b.x; o[4] = b.y; o[5] = b.z;
+	}
+}
+
+// The hashed gradient index of every corner snoise3 can form from lattice coordinates i = floor(.) with |i| <= lim: returns the
+// number of distinct j, writes them (at most 4096) to js, and counts in *bad the ones that are not an integer in 0..48.
+extern "C" int nt_domain(int lim, float *js, int *n_level0, int *n_level1, int *n_level2, long long *bad)
+{
+	std::set<uint32_t> s0; // mod289 of every integer in [-lim, lim]
+	for (int x = -lim; x <= lim; ++x)
+	{
+		const float m = noise_mod289((float)x);
+		uint32_t u; memcpy(&u, &m, 4);
+		s0.insert(u);
+	}
+	auto f = [](uint32_t u) { float x; memcpy(&x, &u, 4); return x; };
+	auto b = [](float x) { uint32_t u; memcpy(&u, &x, 4); return u; };
+	// innermost level: permute(i.z + o), o = 0 (corner 0: "i.z" alone, bit-identical since mod289 never returns -0) or 1
+	std::set<uint32_t> l1, l2, l3;
+	for (uint32_t z : s0)
+		for (float o : {0.0f, 1.0f}) l1.insert(b(noise_permute(o == 0.0f ? f(z) : f(z) + o)));
+	// middle: permute(l1 + i.y + o), the two additions in this order as snoise3 writes them
+	for (uint32_t a : l1)
+		for (uint32_t y : s0)
+		{
+			l2.insert(b(noise_permute(f(a) + f(y))));
+			l2.insert(b(noise_permute(f(a) + f(y) + 1.0f)));
+		}
+	for (uint32_t a : l2)
+		for (uint32_t x : s0)
+		{
+			l3.insert(b(noise_permute(f(a) + f(x))));
+			l3.insert(b(noise_permute(f(a) + f(x) + 1.0f)));
+		}
+	std::set<uint32_t> jset;
+	long long nbad = 0;
+	const float ns_z = 0.142857142857f * 1.0f - 0.0f;
+	for (uint32_t u : l3)
+	{
+		const float p = f(u);
+		const float j = p - 49.0f * floor1(p * ns_z * ns_z);
+		if (!(j >= 0.0f && j <= 48.0f && floor1(j) == j)) ++nbad;
+		jset.insert(b(j));
+	}
+	int n = 0;
+	for (uint32_t u : jset)
+		if (n < 4096) js[n++] = f(u);
+	*n_level0 = (int)s0.size(); *n_level1 = (int)l1.size(); *n_level2 = (int)l2.size();
+	*bad = nbad;
+	return (int)jset.size();
+}
+
+// what = 0: snoise3, 1: turbulence3; out: n x 2 (formula, table); returns how many points the table path sent back to the formula
+extern "C" long long nt_noise(int what, const float *in, float *out, long long n)
+{
+	long long fell_back = 0;
+	for (long long k = 0; k < n; ++k)
+	{
+		const vec3 v = V3(in[3 * k], in[3 * k + 1], in[3 * k + 2]);
+		bool ok = true;
+		if (what == 0)
+		{
+			out[2 * k] = snoise3<NoiseGradFormula>(v);
+			out[2 * k + 1] = snoise3<HostGrads>(v);
+			snoise3_grads<HostGrads>(v, ok);
+		}
+		else
+		{
+			out[2 * k] = turbulence3<NoiseGradFormula>(v);
+			out[2 * k + 1] = turbulence3<HostGrads>(v);
+			turbulence3_grads<HostGrads>(v, ok);
+		}
+		fell_back += ok ? 0 : 1;
+	}
+	return fell_back;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    d = tmp_path_factory.mktemp("noise_table")
+    src, so = os.path.join(d, "noise_table.cpp"), os.path.join(d, "libnoise_table.so")
+    with open(src, "w") as f:
+        f.write(SOURCE)
+    # the options of tests/hostsim: no contraction, as the kernels are built (-ffp-contract=off)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
+                    "-I" + CSRC, "-shared", "-o", so, src], check=True)
+    L = ctypes.CDLL(so)
+    L.nt_noise.restype = ctypes.c_longlong
+    L.nt_fill()
+    return L
+
+
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def test_simplex_grad_is_the_former_inline_formula(lib):
+    j = np.concatenate([np.arange(64, dtype=np.float32), np.float32([-0.0])])
+    out = np.zeros((len(j), 6), np.float32)
+    lib.nt_grads(_ptr(j), _ptr(out), ctypes.c_longlong(len(j)))
+    assert np.array_equal(out[:, :3].view(np.uint32), out[:, 3:].view(np.uint32))
+    # -0 reads entry 0 of the table: its gradient must be +0's, bit for bit
+    assert np.array_equal(out[-1, :3].view(np.uint32), out[0, :3].view(np.uint32))
+    # unit length, and 49 different gradients for j = 0..48
+    assert np.allclose(np.linalg.norm(out[:49, :3].astype(np.float64), axis=1), 1.0, atol=1e-6)
+    assert len({tuple(r) for r in out[:49, :3].view(np.uint32)}) == 49
+
+
+def test_every_reachable_gradient_index_is_an_integer_in_0_to_48(lib):
+    js = np.zeros(4096, np.float32)
+    n0, n1, n2 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    bad = ctypes.c_longlong()
+    n = lib.nt_domain(1 << 24, _ptr(js), ctypes.byref(n0), ctypes.byref(n1), ctypes.byref(n2), ctypes.byref(bad))
+    # every integer of |x| <= 2^24 (every float in that range that floor() can return) through mod289, then the three permute
+    # levels: a few hundred values each (mod289 rounds a few inputs to -1 or 289, beside 0..288)
+    assert 0 < n0.value <= 300 and 0 < n1.value <= 300 and 0 < n2.value <= 300, (n0.value, n1.value, n2.value)
+    assert bad.value == 0
+    assert sorted(js[:n].tolist()) == [float(k) for k in range(49)]
+    assert not np.signbit(js[:n]).any()
+
+
+def _points(rng, n):
+    parts = [
+        rng.uniform(-8.0, 8.0, (n, 3)),
+        rng.uniform(-1e4, 1e4, (n // 4, 3)),
+        rng.uniform(-1e7, 1e7, (n // 8, 3)),
+        # far beyond 2^24: mod289 and the permutes no longer see integers, the table path falls back
+        np.sign(rng.standard_normal((n // 16, 3))) * 10.0 ** rng.uniform(7.0, 30.0, (n // 16, 3)),
+        # on and next to the lattice of the skewed grid
+        np.round(rng.uniform(-300.0, 300.0, (n // 8, 3))),
+        np.round(rng.uniform(-300.0, 300.0, (n // 8, 3)) * 6.0) / 6.0,
+        np.round(rng.uniform(-300.0, 300.0, (n // 8, 3)) * 3.0) / 3.0,
+    ]
+    pts = np.concatenate(parts).astype(np.float32)
+    edge = pts[: n // 8].copy()
+    edge = np.nextafter(np.round(edge), np.float32(np.inf) * np.sign(rng.standard_normal(edge.shape)).astype(np.float32))
+    special = np.float32([[0, 0, 0], [-0.0, -0.0, -0.0], [np.inf, 1, 2], [-np.inf, 0, 0], [np.nan, 0.5, 0.5],
+                          [3.4e38, -3.4e38, 1e-45], [2 ** 24, 2 ** 24 + 2, -(2 ** 24)], [289, -289, 578]])
+    return np.ascontiguousarray(np.concatenate([pts, edge.astype(np.float32), special]).astype(np.float32))
+
+
+@pytest.mark.parametrize("what,name,n", [(0, "snoise3", 2_000_000), (1, "turbulence3", 1_000_000)])
+def test_table_path_equals_the_formula(lib, what, name, n):
+    rng = np.random.default_rng(20261016 + what)
+    pts = _points(rng, n)
+    out = np.zeros((len(pts), 2), np.float32)
+    fell_back = lib.nt_noise(what, _ptr(pts), _ptr(out), ctypes.c_longlong(len(pts)))
+    same = out[:, 0].view(np.uint32) == out[:, 1].view(np.uint32)
+    assert same.all(), (name, pts[~same][:5], out[~same][:5])
+    # the fallback is exercised (huge and non-finite points), and only there: within |x| < 2^20 (the skew and the octaves stay
+    # below 2^24) every lane uses the table
+    assert fell_back > 0
+    small = np.abs(pts).max(axis=1) < 2 ** 20
+    sub = np.ascontiguousarray(pts[small])
+    assert lib.nt_noise(what, _ptr(sub), _ptr(np.zeros((len(sub), 2), np.float32)), ctypes.c_longlong(len(sub))) == 0
