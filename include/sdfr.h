@@ -284,6 +284,52 @@ int sdfr_postprocess(sdfr_renderer *r, int width, int height, const void *scene_
 
 int sdfr_sync(sdfr_renderer *r);
 
+/* ---- questions put to the loaded scene (no counterpart: the reference's scene answers only its pixel shader).  Each answer is a
+ *      value the reference's driver computes (Engine/shader/pshader_sdf.hlsl), with the handle's current camera, time, variables and
+ *      limits latched as sdfr_render latches them; DESIGN.md "Queries".
+ *        - on_host = 1: every pointer is host memory and the call returns when the answers are there.  on_host = 0: every pointer is
+ *          device memory of the handle's GPU; the work is enqueued on the handle's stream -- with two frames in flight the lane of the
+ *          frame submitted last, as sdfr_postprocess -- and the call returns.  With one frame in flight the answers are ready for
+ *          work enqueued after the call on the same stream.  With two, that lane's stream is internal and sdfr_wait_frame does not
+ *          cover a query (it waits for the frame, which a query never is): call sdfr_sync before reading device answers, or use
+ *          on_host = 1.
+ *        - n = 0 does nothing; n < 0 or n > INT32_MAX, a NULL required pointer, a bad on_host: SDFR_ERR_INVALID_ARGUMENT; no scene:
+ *          SDFR_ERR_NO_SCENE.
+ *        - a query changes nothing a render uses or reports: sdfr_get_stats / sdfr_get_timings, the frame sdfr_wait_frame waits for
+ *          and the persistent launch's row order stay as they were.
+ *      Points, rays and pixels are [n][3] float and [n][2] int32 arrays. ----------------------------------------------------------- */
+
+/* distance[i] = map_geometry (:111-135, debug plane and show_objects included) at GeometryInput{pos = points[i], dir = (0,0,0,0),
+ * camera_distance = 0, ray offsets 0} with the default MarchingInput -- dir.w = 0: the scenes' direction-free ("slow") methods.
+ * normals (NULL: not wanted) [n][3]: the driver's normal there (:164-177, :320-330): map_normal with the NormalOutput preloaded
+ * {grad_eps, 0, false}, its normal if it sets use_normal, else normalize of the three forward differences at normal_sample_dist
+ * against baseline = distance[i]. */
+int sdfr_query_distance(sdfr_renderer *r, int64_t n, const float *points, float *distance, float *normals, int on_host);
+
+/* The first hit along a ray: what the driver does with a primary ray up to its material (:299-353). */
+typedef struct sdfr_hit
+{
+	float t;              /* camera_distance where the march stopped (in units of |dir|) */
+	float distance;       /* scene_distance of its last evaluation */
+	float pos[3];         /* mad(dir, t, origin) */
+	float normal[3];      /* the driver's normal at the hit (:164-177, :320-330), camera_distance = t, baseline = distance; 0 on a miss */
+	uint32_t iterations;  /* iter as march_ray leaves it (:179-220) */
+	uint32_t material_id; /* map_material's id at the hit (:333-353), MaterialInput{normal, iterations, distance}; 0 on a miss */
+	int32_t hit;          /* 1 hit, 0 miss, -1 invalid item (a pick outside the frame) */
+	uint32_t reserved;    /* 0 */
+} sdfr_hit;               /* 48 bytes: three 16-byte stores per item (device arrays aligned to 16 bytes) */
+
+/* march_ray (:179-220) from origins[i] along dirs[i] -- used as given, not normalised, dir.w = 1 --, inside_sign +1, the default
+ * MarchingInput, dist_max = max_distance (0: limits.range; negative or not finite: SDFR_ERR_INVALID_ARGUMENT), at most
+ * limits.iter_count iterations, camera_distance from 0, ray offsets 0.  A ray that starts inside a solid hits at iteration 0.
+ * With step shortcuts on (sdfr_set_step_shortcuts) a miss may end early -- hit = 0 with a smaller t, distance and iterations, as
+ * march_evals in sdfr_get_stats --; every field of a hit is the same either way. */
+int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, int on_host);
+
+/* What is under a pixel: pixel (x, y)'s primary ray of a width x height frame of the current camera (:263-267, its ray offsets the
+ * pixel's), marched to limits.range, otherwise as sdfr_query_rays.  A pixel outside the frame gives hit = -1. */
+int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host);
+
 /* ---- two frames in flight inside one handle (no counterpart: D3D11's immediate context pipelines the reference's draws by itself)
  *      The end of a frame runs on a nearly empty chip -- the last waves finishing their tiles -- and only the NEXT frame can fill it
  *      (DESIGN.md 4.1).  With n = 2 sdfr_render alternates between two internal streams, each with a workspace of its own (the

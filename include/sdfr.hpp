@@ -101,15 +101,24 @@ public:
 	// true if it did render something, false otherwise (no valid scene)
 	bool render(const Camera &camera, int width, int height, void *target, int format = SDFR_RGBA32F, bool target_on_host = false)
 	{
-		if (!handle) return false;
-		for (const auto &kv : variables) sdfr_var_set(handle, kv.first.c_str(), kv.second.value);
-		const float eye[3] = {camera.eye.x, camera.eye.y, camera.eye.z};
-		const float tgt[3] = {camera.target.x, camera.target.y, camera.target.z};
-		const int rc = camera.target_is_direction ? sdfr_set_camera_direction(handle, eye, tgt, camera.fovy, camera.aspect, camera.roll)
-												  : sdfr_set_camera_lookat(handle, eye, tgt, camera.fovy, camera.aspect, camera.roll);
-		if (rc != SDFR_OK) return false;
-		sdfr_set_time(handle, stime);
+		if (!handle || !pushState(&camera)) return false;
 		return sdfr_render(handle, width, height, target, format, target_on_host ? 1 : 0, nullptr) == SDFR_OK;
+	}
+
+	// Questions put to the loaded scene with this renderer's variables and time (sdfr_query_distance, sdfr_query_rays, sdfr_pick in
+	// sdfr.h); pick also takes the camera the pixels belong to.  on_host: every pointer is host memory and the answers are there
+	// when the call returns; else device memory, enqueued.  Points and rays [n][3], pixels [n][2].
+	bool queryDistance(int64_t n, const float *points, float *distance, float *normals = nullptr, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_query_distance(handle, n, points, distance, normals, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool queryRays(int64_t n, const float *origins, const float *dirs, sdfr_hit *hits, float max_distance = 0.f, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_query_rays(handle, n, origins, dirs, max_distance, hits, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool pick(const Camera &camera, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, bool on_host = true)
+	{
+		return handle && pushState(&camera) && sdfr_pick(handle, width, height, n, pixels_xy, hits, on_host ? 1 : 0) == SDFR_OK;
 	}
 
 	// two frames in flight inside this renderer (sdfr_set_frames_in_flight): render into two targets in turn, sync() waits for both
@@ -119,6 +128,22 @@ public:
 	sdfr_renderer *native() { return handle; }
 
 private:
+	// what render() hands the library before it renders, and the queries too: the variables, the time and (if given) the camera
+	bool pushState(const Camera *camera = nullptr)
+	{
+		for (const auto &kv : variables) sdfr_var_set(handle, kv.first.c_str(), kv.second.value);
+		if (camera)
+		{
+			const float eye[3] = {camera->eye.x, camera->eye.y, camera->eye.z};
+			const float tgt[3] = {camera->target.x, camera->target.y, camera->target.z};
+			const int rc = camera->target_is_direction ? sdfr_set_camera_direction(handle, eye, tgt, camera->fovy, camera->aspect, camera->roll)
+													   : sdfr_set_camera_lookat(handle, eye, tgt, camera->fovy, camera->aspect, camera->roll);
+			if (rc != SDFR_OK) return false;
+		}
+		sdfr_set_time(handle, stime); // (as render() always did: a time the library refuses leaves the last one)
+		return true;
+	}
+
 	bool refreshVariables()
 	{
 		variables.clear();

@@ -71,6 +71,12 @@ class Stats(ctypes.Structure):
                 ("shade_launches", ctypes.c_uint32)]
 
 
+# sdfr_hit (include/sdfr.h): the answer of a ray query or a pick, 48 bytes
+HIT_DTYPE = np.dtype([("t", np.float32), ("distance", np.float32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,)),
+                      ("iterations", np.uint32), ("material_id", np.uint32), ("hit", np.int32), ("reserved", np.uint32)])
+assert HIT_DTYPE.itemsize == 48
+
+
 # every symbol include/sdfr.h declares (tests check that the library exports all of them)
 EXPORTED_SYMBOLS = [
     "sdfr_create", "sdfr_destroy", "sdfr_last_error", "sdfr_set_stream", "sdfr_scene_count", "sdfr_scene_name", "sdfr_load_scene",
@@ -81,7 +87,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_set_strip_split", "sdfr_strip_buffer_pixels_split", "sdfr_strip_buffer_bytes_split", "sdfr_render_private_strips",
     "sdfr_comm_unique_id", "sdfr_comm_create", "sdfr_comm_create_all", "sdfr_comm_destroy", "sdfr_comm_close", "sdfr_comm_library_info", "sdfr_comm_rank", "sdfr_comm_world",
     "sdfr_comm_last_error", "sdfr_comm_selftest", "sdfr_render_gather", "sdfr_render_gather_all", "sdfr_set_launch_mode", "sdfr_set_step_shortcuts",
-    "sdfr_register_host_target",
+    "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick",
 ]
 
 _lib = None
@@ -176,6 +182,10 @@ def load_library():
     L.sdfr_comm_last_error.argtypes = [vp]
     L.sdfr_comm_last_error.restype = ctypes.c_char_p
     L.sdfr_comm_selftest.argtypes = [vp, ctypes.c_size_t, vp]
+    i64 = ctypes.c_int64
+    L.sdfr_query_distance.argtypes = [vp, i64, vp, vp, vp, ci]
+    L.sdfr_query_rays.argtypes = [vp, i64, vp, vp, cf, vp, ci]
+    L.sdfr_pick.argtypes = [vp, ci, ci, i64, vp, vp, ci]
     L.sdfr_render_gather.argtypes = [vp, vp, ci, ci, vp, ci, ci]
     L.sdfr_render_gather_all.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, vp, ci, ci]
     _lib = L
@@ -454,6 +464,87 @@ class SDFRenderer:
         self._check(self._L.sdfr_render(self._h, width, height, img.ctypes.data_as(ctypes.c_void_p), fmt, 1,
                                         st.ctypes.data_as(ctypes.c_void_p) if pixel_stats else None))
         return (img, st) if pixel_stats else img
+
+    # ---- questions put to the loaded scene (sdfr_query_distance / sdfr_query_rays / sdfr_pick; DESIGN.md "Queries") -------------
+    # numpy arrays: the host path, answers returned as new arrays.  Contiguous device torch tensors: the device path, enqueued on the
+    # handle's stream, answers written into the caller's tensors (`out`, like render(out=...)); a hit record is a row of an [n, 12]
+    # float32 tensor whose integer fields (iterations, material_id, hit, reserved: columns 8-11) are read with .view(torch.int32).
+
+    def _dev(self, t, numel, what, ints=False, hits=False):
+        """the device pointer of a query tensor, after checking what the kernels will read or write through it: a contiguous tensor
+        on the handle's GPU of `numel` float32 elements (int32 for pixels; hit records float32 or int32).  Raises, also under -O."""
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
+            raise TypeError("%s: a contiguous device tensor is needed" % what)
+        if t.device.index is not None and t.device.index != self.device:
+            raise ValueError("%s: on %s, the renderer is on device %d" % (what, t.device, self.device))
+        allowed = (torch.float32, torch.int32) if hits else ((torch.int32,) if ints else (torch.float32,))
+        if t.dtype not in allowed:
+            raise TypeError("%s: dtype %s, expected %s" % (what, t.dtype, " or ".join(str(d) for d in allowed)))
+        if t.numel() != numel:
+            raise ValueError("%s: %d elements, expected %d" % (what, t.numel(), numel))
+        return ctypes.c_void_p(t.data_ptr())
+
+    def queryDistance(self, points, normals=False, out=None, out_normals=None):
+        """Scene distance at points [n, 3] (and the normal there if `normals`): distance [n] or (distance [n], normals [n, 3])."""
+        if hasattr(points, "data_ptr"):
+            n = points.numel() // 3
+            import torch
+
+            if out is None:
+                out = torch.empty(n, dtype=torch.float32, device=points.device)
+            if normals and out_normals is None:
+                out_normals = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            pn = self._dev(out_normals, 3 * n, "out_normals") if normals else None
+            self._check(self._L.sdfr_query_distance(self._h, n, self._dev(points, 3 * n, "points"), self._dev(out, n, "out"), pn, 0))
+            return (out, out_normals) if normals else out
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        d = np.empty(n, np.float32)
+        nr = np.empty((n, 3), np.float32) if normals else None
+        self._check(self._L.sdfr_query_distance(self._h, n, p.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p),
+                                                nr.ctypes.data_as(ctypes.c_void_p) if normals else None, 1))
+        return (d, nr) if normals else d
+
+    def queryRays(self, origins, dirs, max_distance=0.0, out=None):
+        """First hit along rays origins [n, 3] + t * dirs [n, 3] (dirs as given, not normalised; max_distance 0 = limits.range):
+        a HIT_DTYPE array [n], or the [n, 12] device tensor `out`."""
+        if hasattr(origins, "data_ptr"):
+            n = origins.numel() // 3
+            import torch
+
+            if out is None:
+                out = torch.empty((n, 12), dtype=torch.float32, device=origins.device)
+            self._check(self._L.sdfr_query_rays(self._h, n, self._dev(origins, 3 * n, "origins"), self._dev(dirs, 3 * n, "dirs"), float(max_distance),
+                                                self._dev(out, 12 * n, "out", hits=True), 0))
+            return out
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        assert o.shape == d.shape
+        hits = np.empty(o.shape[0], HIT_DTYPE)
+        self._check(self._L.sdfr_query_rays(self._h, o.shape[0], o.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p),
+                                            float(max_distance), hits.ctypes.data_as(ctypes.c_void_p), 1))
+        return hits
+
+    def pick(self, pixels_xy, width, height, camera=None, out=None):
+        """What lies under pixels [n, 2] (x, y; row 0 = top) of a width x height frame of the current camera: a HIT_DTYPE array [n]
+        (hit = -1 for a pixel outside the frame), or the [n, 12] device tensor `out`."""
+        if camera is not None:
+            self.setCamera(camera)
+        if hasattr(pixels_xy, "data_ptr"):
+            n = pixels_xy.numel() // 2
+            import torch
+
+            if out is None:
+                out = torch.empty((n, 12), dtype=torch.float32, device=pixels_xy.device)
+            self._check(self._L.sdfr_pick(self._h, int(width), int(height), n, self._dev(pixels_xy, 2 * n, "pixels_xy", ints=True), self._dev(out, 12 * n, "out", hits=True), 0))
+            return out
+        px = np.ascontiguousarray(pixels_xy, np.int32).reshape(-1, 2)
+        hits = np.empty(px.shape[0], HIT_DTYPE)
+        self._check(self._L.sdfr_pick(self._h, int(width), int(height), px.shape[0], px.ctypes.data_as(ctypes.c_void_p),
+                                      hits.ctypes.data_as(ctypes.c_void_p), 1))
+        return hits
 
     def registerHostTarget(self, array):
         """Page-lock a numpy image that render(out=array) will fill every frame (sdfr_register_host_target); None

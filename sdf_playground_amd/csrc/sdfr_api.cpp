@@ -5,8 +5,10 @@
 // sdfr_kernels.hip; there is no CPU rendering path.
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
+#include "sdfr_query.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -241,6 +243,7 @@ void sdfr_destroy(sdfr_renderer *r)
 	jit_unload(r->jit);
 	(void)hipFree(r->d_stage);
 	(void)hipFree(r->d_pstat);
+	(void)hipFree(r->d_query);
 	(void)hipFree(r->d_wire);
 	(void)hipFree(r->d_post_flags);
 	if (r->pinned_host) (void)hipHostUnregister(r->pinned_host);
@@ -681,11 +684,10 @@ static int check_render(sdfr_renderer *r, int width, int height, int rank, int w
 	return SDFR_OK;
 }
 
-// latch the variable values into the frame uniforms (the reference uploads them every frame,
-// SDFRenderer.cpp:75-78) and derive the per-frame constants
-static int latch_frame(sdfr_renderer *r, int width, int height)
+// latch the variable values into the frame uniforms U (the reference uploads them every frame,
+// SDFRenderer.cpp:75-78) and derive the per-frame constants; a run-time scene's prepare kernel runs on `stream`
+static int latch_into(sdfr_renderer *r, FrameU &U, int width, int height, hipStream_t stream)
 {
-	FrameU &U = r->U;
 	U.width = width;
 	U.height = height;
 	const auto &m = r->vars.getVariables();
@@ -702,8 +704,115 @@ static int latch_frame(sdfr_renderer *r, int width, int height)
 	for (size_t k = 0; k < r->scene_var_slots.size(); ++k) U.scene_var[k] = val(r->scene_var_slots[k].c_str());
 	U.step_shortcuts = r->step_shortcuts ? 1 : 0;
 	frame_derive(U, r->scene);
-	if (r->scene == SDFR_SCENE_COUNT) SDFR_HIP(jit_prepare(r->jit, U, r->lane.stream));
+	if (r->scene == SDFR_SCENE_COUNT) SDFR_HIP(jit_prepare(r->jit, U, stream));
 	return SDFR_OK;
+}
+// ... the handle's own, for a render
+static int latch_frame(sdfr_renderer *r, int width, int height) { return latch_into(r, r->U, width, height, r->lane.stream); }
+
+// The three queries (sdfr_query.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not the
+// handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
+// out: distance + normals, or hits.
+static const size_t k_query_stage_keep = (size_t)64 << 20; // staging bytes a handle keeps between host queries
+static_assert(sizeof(sdfr_hit) == 4 * QUERY_HIT_WORDS, "sdfr_hit is the query kernels' 12-word record");
+static int query_impl(sdfr_renderer *r, int kind, int64_t n, const float *pos, const float *dir, const int32_t *pixels, int width, int height,
+	float max_distance, float *distance, float *normals, sdfr_hit *hits, int on_host)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	if (n < 0 || n > (int64_t)INT32_MAX) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad item count");
+	if (on_host != 0 && on_host != 1) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
+	if (!std::isfinite(max_distance) || max_distance < 0.f) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "max_distance must be finite and >= 0");
+	if (kind == QUERY_PICK && (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30))
+		return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	if (n == 0) return SDFR_OK;
+	const bool inputs_ok = kind == QUERY_POINTS ? pos != nullptr : kind == QUERY_RAYS ? pos && dir : pixels != nullptr;
+	const bool outputs_ok = kind == QUERY_POINTS ? distance != nullptr : hits != nullptr;
+	if (!inputs_ok || !outputs_ok) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
+	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
+	SDFR_HIP(hipSetDevice(r->device));
+	hipStream_t stream = r->lane.stream; // the handle's stream, or the lane of the frame submitted last (as sdfr_postprocess)
+	FrameU U = r->U;
+	int rc = kind == QUERY_PICK ? latch_into(r, U, width, height, stream) : latch_into(r, U, 1, 1, stream);
+	if (rc != SDFR_OK) return rc;
+
+	QueryArgs q;
+	q.kind = kind;
+	q.n = (int)n;
+	q.pos = pos;
+	q.dir = dir;
+	q.pixels = pixels;
+	q.dist_max = max_distance == 0.f ? U.range : max_distance;
+	q.distance = distance;
+	q.normals = normals;
+	q.hits = reinterpret_cast<uint32_t *>(hits);
+	// the sizes of the arrays, in the order they are staged: inputs, then answers
+	const size_t N = (size_t)n;
+	const size_t in0 = kind == QUERY_PICK ? N * 8 : N * 12, in1 = kind == QUERY_RAYS ? N * 12 : 0;
+	const size_t out0 = kind == QUERY_POINTS ? N * 4 : N * sizeof(sdfr_hit), out1 = kind == QUERY_POINTS && normals ? N * 12 : 0;
+	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+	if (on_host)
+	{
+		const size_t need = up(in0) + up(in1) + up(out0) + up(out1);
+		if (r->query_bytes < need)
+		{
+			(void)hipFree(r->d_query); // (host queries are synchronous: none is using it)
+			r->d_query = nullptr;
+			r->query_bytes = 0;
+			SDFR_HIP(hipMalloc(&r->d_query, need));
+			r->query_bytes = need;
+		}
+		char *base = static_cast<char *>(r->d_query);
+		char *d_in0 = base, *d_in1 = d_in0 + up(in0), *d_out0 = d_in1 + up(in1), *d_out1 = d_out0 + up(out0);
+		SDFR_HIP(hipMemcpyAsync(d_in0, kind == QUERY_PICK ? (const void *)pixels : (const void *)pos, in0, hipMemcpyHostToDevice, stream));
+		if (in1) SDFR_HIP(hipMemcpyAsync(d_in1, dir, in1, hipMemcpyHostToDevice, stream));
+		q.pos = kind == QUERY_PICK ? nullptr : reinterpret_cast<const float *>(d_in0);
+		q.pixels = kind == QUERY_PICK ? reinterpret_cast<const int32_t *>(d_in0) : nullptr;
+		q.dir = in1 ? reinterpret_cast<const float *>(d_in1) : nullptr;
+		q.distance = kind == QUERY_POINTS ? reinterpret_cast<float *>(d_out0) : nullptr;
+		q.normals = out1 ? reinterpret_cast<float *>(d_out1) : nullptr;
+		q.hits = kind == QUERY_POINTS ? nullptr : reinterpret_cast<uint32_t *>(d_out0);
+	}
+	if (r->scene == SDFR_SCENE_COUNT)
+	{
+		std::string err;
+		const JitQueryStatus js = jit_launch_query(r->jit, r->device, U, q, stream, err);
+		if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
+	}
+	else
+	{
+		const hipError_t e = launch_query(r->scene, U, q, stream);
+		if (e != hipSuccess) return hip_fail(r, e, "query launch");
+	}
+	if (on_host)
+	{
+		SDFR_HIP(hipMemcpyAsync(kind == QUERY_POINTS ? (void *)distance : (void *)hits, kind == QUERY_POINTS ? (const void *)q.distance : (const void *)q.hits,
+			out0, hipMemcpyDeviceToHost, stream));
+		if (out1) SDFR_HIP(hipMemcpyAsync(normals, q.normals, out1, hipMemcpyDeviceToHost, stream));
+		SDFR_HIP(hipStreamSynchronize(stream));
+		if (r->query_bytes > k_query_stage_keep)
+		{
+			// a large host query does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
+			(void)hipFree(r->d_query);
+			r->d_query = nullptr;
+			r->query_bytes = 0;
+		}
+	}
+	return SDFR_OK;
+}
+
+int sdfr_query_distance(sdfr_renderer *r, int64_t n, const float *points, float *distance, float *normals, int on_host)
+{
+	return guarded(r, [&]() -> int { return query_impl(r, QUERY_POINTS, n, points, nullptr, nullptr, 0, 0, 0.f, distance, normals, nullptr, on_host); });
+}
+
+int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, int on_host)
+{
+	return guarded(r, [&]() -> int { return query_impl(r, QUERY_RAYS, n, origins, dirs, nullptr, 0, 0, max_distance, nullptr, nullptr, hits, on_host); });
+}
+
+int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host)
+{
+	return guarded(r, [&]() -> int { return query_impl(r, QUERY_PICK, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, on_host); });
 }
 
 } // extern "C"

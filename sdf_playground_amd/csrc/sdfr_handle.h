@@ -53,6 +53,8 @@ struct sdfr_renderer
 	size_t stage_bytes = 0;
 	uint32_t *d_pstat = nullptr;
 	size_t pstat_bytes = 0;
+	void *d_query = nullptr; // staging of host-memory queries (sdfr_query_*, sdfr_pick): inputs and answers; kept up to 64 MiB
+	size_t query_bytes = 0;
 	// sdfr_register_host_target: the caller's persistent host image, page-locked with the runtime
 	void *pinned_host = nullptr;
 	size_t pinned_bytes = 0;

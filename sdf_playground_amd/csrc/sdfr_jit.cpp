@@ -16,6 +16,7 @@
 // libhiprtc.so is opened on first use: the library has no load-time dependency on it.
 #include "sdfr_jit.h"
 #include "sdfr_pixel.h"
+#include "sdfr_query.h"
 
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
@@ -78,10 +79,10 @@ std::string header_dir()
 
 } // namespace
 
-std::string jit_translation_unit(const std::string &scene_source, const std::vector<std::string> &var_slots)
+std::string jit_translation_unit(const std::string &scene_source, const std::vector<std::string> &var_slots, bool query)
 {
 	std::string tu;
-	tu += "#include \"sdfr_pixel_kernel.h\"\n";
+	tu += query ? "#include \"sdfr_query_kernel.h\"\n" : "#include \"sdfr_pixel_kernel.h\"\n";
 	// a scene that came in the reference's dialect (sdfr_hlsl.cpp) needs the HLSL vocabulary
 	if (scene_source.find("hlsl::SceneAdapter") != std::string::npos) tu += "#include \"sdfr_hlsl.h\"\n";
 	tu += "namespace sdfr {\n";
@@ -90,9 +91,19 @@ std::string jit_translation_unit(const std::string &scene_source, const std::vec
 	tu += "#line 1 \"scene\"\n";
 	tu += scene_source;
 	tu += "\n#line 1 \"sdfr_jit_kernels\"\n";
-	tu += "extern \"C\" __global__ void sdfr_jit_prepare(FrameU *U) { if (blockIdx.x == 0 && threadIdx.x == 0) Scene::prepare(*U); }\n";
-	tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_pixel(PixelKernelArgs args) { pixel_kernel<Scene, false>(args); }\n";
-	tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_pixel_debug(PixelKernelArgs args) { pixel_kernel<Scene, true>(args); }\n";
+	if (query)
+	{
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_points(QueryKernelArgs a) { query_points_kernel<Scene, false>(a); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_points_debug(QueryKernelArgs a) { query_points_kernel<Scene, true>(a); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_rays(QueryKernelArgs a) { query_rays_kernel<Scene, false>(a); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_rays_debug(QueryKernelArgs a) { query_rays_kernel<Scene, true>(a); }\n";
+	}
+	else
+	{
+		tu += "extern \"C\" __global__ void sdfr_jit_prepare(FrameU *U) { if (blockIdx.x == 0 && threadIdx.x == 0) Scene::prepare(*U); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_pixel(PixelKernelArgs args) { pixel_kernel<Scene, false>(args); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_pixel_debug(PixelKernelArgs args) { pixel_kernel<Scene, true>(args); }\n";
+	}
 	tu += "} // namespace sdfr\n";
 	return tu;
 }
@@ -100,12 +111,13 @@ std::string jit_translation_unit(const std::string &scene_source, const std::vec
 void jit_unload(JitScene &js)
 {
 	if (js.module) (void)hipModuleUnload(js.module);
+	if (js.query_module) (void)hipModuleUnload(js.query_module);
 	if (js.d_frame) (void)hipFree(js.d_frame);
 	js = JitScene();
 }
 
 bool jit_compile_code(const std::string &arch_name, const std::string &name, const std::string &scene_source, const std::vector<std::string> &var_slots,
-	std::vector<char> &code, std::string &error)
+	std::vector<char> &code, std::string &error, bool query)
 {
 	Hiprtc &rtc = hiprtc();
 	if (!rtc.ok)
@@ -113,7 +125,7 @@ bool jit_compile_code(const std::string &arch_name, const std::string &name, con
 		error = "run-time scene compilation needs libhiprtc.so, which could not be loaded";
 		return false;
 	}
-	const std::string tu = jit_translation_unit(scene_source, var_slots);
+	const std::string tu = jit_translation_unit(scene_source, var_slots, query);
 	hiprtcProgram prog = nullptr;
 	hiprtcResult rc = rtc.create(&prog, tu.c_str(), (name + ".scene.hip").c_str(), 0, nullptr, nullptr);
 	if (rc != HIPRTC_SUCCESS)
@@ -163,6 +175,8 @@ bool jit_compile(int device, const std::string &name, const std::string &scene_s
 
 	JitScene js;
 	js.name = name;
+	js.source = scene_source;
+	js.var_slots = var_slots;
 	hipError_t e = hipModuleLoadData(&js.module, code.data());
 	if (e == hipSuccess) e = hipModuleGetFunction(&js.prepare, js.module, "sdfr_jit_prepare");
 	if (e == hipSuccess) e = hipModuleGetFunction(&js.pixel, js.module, "sdfr_jit_pixel");
@@ -189,6 +203,50 @@ hipError_t jit_prepare(const JitScene &js, FrameU &U, hipStream_t stream)
 	e = hipMemcpyAsync(&U, js.d_frame, sizeof U, hipMemcpyDeviceToHost, stream);
 	if (e != hipSuccess) return e;
 	return hipStreamSynchronize(stream);
+}
+
+JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const QueryArgs &q, hipStream_t stream, std::string &error)
+{
+	if (!js.query_module)
+	{
+		hipDeviceProp_t prop;
+		if (hipGetDeviceProperties(&prop, device) != hipSuccess)
+		{
+			error = "hipGetDeviceProperties failed";
+			return JIT_QUERY_HIP;
+		}
+		std::vector<char> code;
+		if (!jit_compile_code(prop.gcnArchName, js.name, js.source, js.var_slots, code, error, true)) return JIT_QUERY_COMPILE;
+		hipModule_t m = nullptr;
+		hipError_t e = hipModuleLoadData(&m, code.data());
+		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_points, m, "sdfr_jit_query_points");
+		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_points_debug, m, "sdfr_jit_query_points_debug");
+		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_rays, m, "sdfr_jit_query_rays");
+		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_rays_debug, m, "sdfr_jit_query_rays_debug");
+		if (e != hipSuccess)
+		{
+			error = std::string("loading the scene's query kernels failed: ") + hipGetErrorString(e);
+			if (m) (void)hipModuleUnload(m);
+			js.query_points = js.query_points_debug = js.query_rays = js.query_rays_debug = nullptr;
+			return JIT_QUERY_HIP;
+		}
+		js.query_module = m;
+	}
+	const bool dbg = frame_needs_debug(U);
+	hipFunction_t fn = q.kind == QUERY_POINTS ? (dbg ? js.query_points_debug : js.query_points) : (dbg ? js.query_rays_debug : js.query_rays);
+	const uint32_t bt = (uint32_t)pixel_block_threads();
+	const uint32_t blocks = ((uint32_t)q.n + bt - 1u) / bt;
+	QueryKernelArgs a;
+	a.U = U;
+	a.q = q;
+	void *args[] = {&a};
+	const hipError_t e = hipModuleLaunchKernel(fn, blocks, 1, 1, bt, 1, 1, 0, stream, args, nullptr);
+	if (e != hipSuccess)
+	{
+		error = std::string("query launch: ") + hipGetErrorString(e);
+		return JIT_QUERY_HIP;
+	}
+	return JIT_QUERY_OK;
 }
 
 hipError_t jit_launch_pixel(const JitScene &js, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,

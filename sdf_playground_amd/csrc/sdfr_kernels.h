@@ -32,6 +32,10 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events,
 	int *n_rounds_out);
 
+// one query (sdfr_query.h) of a built-in scene: q.n > 0 items, every pointer device memory
+struct QueryArgs;
+hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream);
+
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,
 	int priv_period, hipStream_t stream);
 

@@ -384,6 +384,10 @@ int device_cu_count(int device)
 		hipEvent_t *, hipEvent_t *, int *);
 SDFR_FOR_EACH_GROUP(SDFR_DECLARE_GROUP)
 #undef SDFR_DECLARE_GROUP
+// ... and their query kernels in as many more (sdfr_query_group.hip)
+#define SDFR_DECLARE_QUERY_GROUP(G) hipError_t launch_query_group##G(int, const FrameU &, const QueryArgs &, hipStream_t);
+SDFR_FOR_EACH_GROUP(SDFR_DECLARE_QUERY_GROUP)
+#undef SDFR_DECLARE_QUERY_GROUP
 
 int scene_tile_w_log2(int scene)
 {
@@ -417,6 +421,18 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 	switch (scene % SDFR_GROUPS)
 	{
 #define SDFR_CALL_GROUP(G) case G: return launch_wavefront_group##G(scene, U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
+		SDFR_FOR_EACH_GROUP(SDFR_CALL_GROUP)
+#undef SDFR_CALL_GROUP
+	default: return hipErrorInvalidValue;
+	}
+}
+
+hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream)
+{
+	if (scene < 0 || scene >= SDFR_SCENE_COUNT) return hipErrorInvalidValue;
+	switch (scene % SDFR_GROUPS)
+	{
+#define SDFR_CALL_GROUP(G) case G: return launch_query_group##G(scene, U, q, stream);
 		SDFR_FOR_EACH_GROUP(SDFR_CALL_GROUP)
 #undef SDFR_CALL_GROUP
 	default: return hipErrorInvalidValue;

@@ -1,0 +1,322 @@
+"""GPU tier of the scene queries (sdfr_query_distance, sdfr_query_rays, sdfr_pick) through libsdfr.so: bit for bit against the
+oracle's definitions (tests/cpp/query_oracle.cpp) for every scene compiled ahead of time and the run-time scenes with an oracle
+twin, host and device memory; the run-time scenes' lazily compiled query module; step shortcuts; agreement with the renderer's own
+primary rays; no side effects on rendering; sizes and argument checks."""
+import os
+import zlib
+
+import numpy as np
+import pytest
+
+import query_util as qu
+
+pytestmark = pytest.mark.gpu
+
+N_POINTS = 20000
+N_RAYS = 2000
+W, H = 64, 48
+SCENES_DIR = qu.SCENES_DIR
+DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
+                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    yield r
+    r.close()
+
+
+def _load(r, scene):
+    if scene in qu.HLSL:
+        r.initShaderHlsl(scene, os.path.join(SCENES_DIR, scene + ".hlsl"))
+    else:
+        r.initShader(scene)
+
+
+def _setup(r, scene, of, variables=None, load=True):
+    """the handle's state = the oracle frame `of`"""
+    if load:
+        _load(r, scene)
+    r.setParameters(of.stime)
+    r.setCameraBasis(of.eye, of.front, of.right, of.top)
+    r.setLimits(**DEFAULT_LIMITS)
+    r.setStepShortcuts(False)
+    for name, v in (variables or {}).items():
+        assert r.setValue(name, v)
+
+
+def _torch_dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _check_all(r, scene, of, seed, device=True):
+    import torch
+
+    pts = qu.point_samples(scene, of, seed, N_POINTS)
+    d_ref, n_ref = qu.oracle_points(scene, of, pts)
+    d, n = r.queryDistance(pts, normals=True)
+    qu.assert_same("%s distance (host)" % scene, d, d_ref)
+    qu.assert_same("%s normal (host)" % scene, n, n_ref)
+    o, dirs = qu.ray_samples(of, seed + 7, N_RAYS)
+    h_ref = qu.oracle_rays(scene, of, o, dirs)
+    qu.assert_same("%s rays (host)" % scene, qu.hits_array(r.queryRays(o, dirs)), h_ref)
+    px = qu.pick_grid(W, H)
+    p_ref = qu.oracle_pick(scene, of, px)
+    qu.assert_same("%s pick (host)" % scene, qu.hits_array(r.pick(px, W, H)), p_ref)
+    if device:
+        dd = r.queryDistance(_torch_dev(pts))  # without normals
+        hd = r.queryRays(_torch_dev(o), _torch_dev(dirs))
+        pd = r.pick(_torch_dev(px), W, H)
+        torch.cuda.synchronize()
+        qu.assert_same("%s distance (device)" % scene, dd.cpu().numpy(), d_ref)
+        qu.assert_same("%s rays (device)" % scene, qu.hits_array(hd.cpu().numpy()), h_ref)
+        qu.assert_same("%s pick (device)" % scene, qu.hits_array(pd.cpu().numpy()), p_ref)
+        dn, nn = r.queryDistance(_torch_dev(pts), normals=True)
+        torch.cuda.synchronize()
+        qu.assert_same("%s normal (device)" % scene, nn.cpu().numpy(), n_ref)
+    return h_ref, p_ref
+
+
+@pytest.mark.parametrize("scene", qu.BUILTIN)
+def test_builtin_queries_equal_oracle(renderer, scene):
+    of = qu.frame(scene, 1.25, W, H)
+    _setup(renderer, scene, of)
+    _check_all(renderer, scene, of, seed=zlib.crc32(scene.encode()) & 0xffff)
+
+
+@pytest.mark.parametrize("scene", sorted(qu.MOVED_VARS))
+def test_queries_with_moved_variables(renderer, scene):
+    of = qu.frame(scene, 0.5, W, H, qu.MOVED_VARS[scene])
+    _setup(renderer, scene, of, qu.MOVED_VARS[scene])
+    _check_all(renderer, scene, of, seed=11, device=False)
+
+
+def test_debug_plane_and_hidden_objects(renderer):
+    v = {"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}
+    of = qu.frame("labyrinth", 0.75, W, H, v)
+    _setup(renderer, "labyrinth", of, v)
+    _check_all(renderer, "labyrinth", of, seed=21, device=False)
+    renderer.resetVariables()
+
+
+@pytest.mark.parametrize("scene", qu.HLSL)
+def test_runtime_scenes_equal_oracle(renderer, scene):
+    of = qu.frame(scene, 0.5, W, H)
+    _setup(renderer, scene, of)
+    _check_all(renderer, scene, of, seed=31)
+
+
+def test_pendulum_hlsl_equals_its_cpp_twin():
+    import sdf_playground_amd as sp
+
+    of = qu.frame("fast_sphere", 0.8, W, H)  # (only the camera and limits: the pendulum has no oracle twin)
+    px = qu.pick_grid(W, H)
+    o, dirs = qu.ray_samples(of, 41, N_RAYS)
+    pts = np.concatenate([o + dirs * t for t in (0.5, 1.5, 3.0)])
+    out = []
+    for how in ("hlsl", "cpp"):
+        r = sp.SDFRenderer(0)
+        try:
+            if how == "hlsl":
+                r.initShaderHlsl("pendulum_hlsl", os.path.join(SCENES_DIR, "pendulum.hlsl"))
+            else:
+                r.initShaderSource("pendulum_cpp", os.path.join(SCENES_DIR, "pendulum.scene.h"))
+            _setup(r, None, of, load=False)
+            d, n = r.queryDistance(pts, normals=True)
+            out.append((d, n, qu.hits_array(r.queryRays(o, dirs)), qu.hits_array(r.pick(px, W, H))))
+        finally:
+            r.close()
+    (a, b) = out
+    for k, what in enumerate(("distance", "normal", "rays", "pick")):
+        qu.assert_same("pendulum " + what, a[k], b[k])
+    assert (a[2][:, 10] == 1).any()
+
+
+def test_runtime_query_module_follows_the_scene(renderer):
+    # a built-in scene after a run-time one uses the built-in kernels; a second run-time scene gets its own query module
+    of = qu.frame("labyrinth", 0.3, W, H)
+    _setup(renderer, "noise_lod", qu.frame("noise_lod", 0.3, W, H))
+    renderer.queryDistance(np.zeros((4, 3), np.float32))
+    _setup(renderer, "labyrinth", of)
+    _check_all(renderer, "labyrinth", of, seed=51, device=False)
+    for scene in ("noise_lod", "dialect_tour"):
+        of = qu.frame(scene, 0.3, W, H)
+        _setup(renderer, scene, of)
+        _check_all(renderer, scene, of, seed=52, device=False)
+
+
+@pytest.mark.parametrize("scene", ["labyrinth", "lense", "cube_sea"])
+def test_step_shortcuts_keep_hits(renderer, scene):
+    of = qu.frame(scene, 0.25, W, H)
+    _setup(renderer, scene, of)
+    o, dirs = qu.ray_samples(of, 61, N_RAYS)
+    px = qu.pick_grid(W, H)
+    exact = qu.hits_array(renderer.queryRays(o, dirs))
+    pexact = qu.hits_array(renderer.pick(px, W, H))
+    renderer.setStepShortcuts(True)
+    short = qu.hits_array(renderer.queryRays(o, dirs))
+    pshort = qu.hits_array(renderer.pick(px, W, H))
+    renderer.setStepShortcuts(False)
+    for e, s in ((exact, short), (pexact, pshort)):
+        hit = e[:, 10] == 1
+        assert np.array_equal(s[:, 10], e[:, 10])
+        assert np.array_equal(s[hit], e[hit])
+        assert (s[~hit, 8] <= e[~hit, 8]).all()
+
+
+@pytest.mark.parametrize("scene", ["labyrinth", "lense", "noise_lod"])
+def test_pick_misses_where_the_render_does(renderer, scene):
+    w, h = 160, 96
+    of = qu.frame(scene, 0.6, w, h)
+    _setup(renderer, scene, of)
+    _, st = renderer.render(None, w, h, pixel_stats=True)
+    hits = renderer.pick(qu.pick_grid(w, h)[: w * h], w, h)
+    assert np.array_equal((hits["hit"] == 0).reshape(h, w), st[..., 2] == 0)
+
+
+def _stats(r):
+    s = r.getStats()
+    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
+
+
+def test_queries_leave_rendering_alone(renderer):
+    scene = "labyrinth"
+    of = qu.frame(scene, 0.4, 96, 64)
+    _setup(renderer, scene, of)
+    o, dirs = qu.ray_samples(of, 71, 500)
+    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
+    s0, t0 = _stats(renderer), renderer.getTimings()
+    renderer.queryRays(o, dirs)
+    renderer.pick(qu.pick_grid(32, 16), 32, 16)
+    renderer.queryDistance(o, normals=True)
+    assert _stats(renderer) == s0 and renderer.getTimings() == t0
+    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
+    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+
+
+def test_two_frames_in_flight(renderer):
+    import torch
+
+    scene = "lense"
+    of = qu.frame(scene, 0.9, W, H)
+    _setup(renderer, scene, of)
+    o, dirs = qu.ray_samples(of, 81, 1000)
+    ref = qu.hits_array(renderer.queryRays(o, dirs))
+    img_ref = renderer.render(None, 128, 72)
+    renderer.setFramesInFlight(2)
+    try:
+        imgs = [torch.empty((72, 128, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        got = []
+        for k in range(4):
+            renderer.render(None, 128, 72, out=imgs[k % 2])
+            got.append(qu.hits_array(renderer.queryRays(o, dirs)))
+            dev = renderer.queryRays(_torch_dev(o), _torch_dev(dirs))
+            renderer.waitFrame(torch.cuda.current_stream().cuda_stream)
+            renderer.sync()
+            got.append(qu.hits_array(dev.cpu().numpy()))
+            assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img_ref.view(np.uint32))
+        for g in got:
+            assert np.array_equal(g, ref)
+    finally:
+        renderer.setFramesInFlight(1)
+
+
+def test_sizes_and_arguments(renderer):
+    import ctypes
+
+    import sdf_playground_amd as sp
+    import torch
+
+    L = sp.load_library()
+    scene = "fast_sphere"
+    of = qu.frame(scene, 0.0, W, H)
+    _setup(renderer, scene, of)
+    h = renderer._h
+    buf = np.zeros(64, np.float32)
+    p = buf.ctypes.data_as(ctypes.c_void_p)
+    assert L.sdfr_query_distance(h, 0, None, None, None, 1) == 0
+    assert L.sdfr_query_rays(h, 0, None, None, 0.0, None, 0) == 0
+    assert L.sdfr_pick(h, W, H, 0, None, None, 1) == 0
+    assert L.sdfr_query_distance(h, -1, p, p, None, 1) == -1
+    assert L.sdfr_query_distance(h, 2 ** 31, p, p, None, 1) == -1
+    assert L.sdfr_query_distance(h, 1, None, p, None, 1) == -1
+    assert L.sdfr_query_distance(h, 1, p, None, None, 1) == -1
+    assert L.sdfr_query_distance(h, 1, p, p, None, 2) == -1
+    assert L.sdfr_query_rays(h, 1, p, None, 0.0, p, 1) == -1
+    for bad in (-1.0, float("inf"), float("nan")):
+        assert L.sdfr_query_rays(h, 1, p, p, bad, p, 1) == -1
+    assert L.sdfr_pick(h, 0, H, 1, p, p, 1) == -1
+    assert L.sdfr_pick(h, W, H, 1, None, p, 1) == -1
+    assert L.sdfr_query_distance(None, 1, p, p, None, 1) == -1
+    fresh = sp.SDFRenderer(0)
+    try:
+        assert L.sdfr_query_distance(fresh._h, 1, p, p, None, 1) == -4
+        assert L.sdfr_pick(fresh._h, W, H, 1, p, p, 1) == -4
+    finally:
+        fresh.close()
+    # picks outside the frame
+    hits = renderer.pick(np.array([[-1, 0], [W, 0], [0, H], [3, 4]], np.int32), W, H)
+    assert list(hits["hit"][:3]) == [-1, -1, -1] and hits["hit"][3] in (0, 1)
+    # a count that is no multiple of any block, on the device
+    n = 2 ** 22 + 17
+    rng = np.random.default_rng(5)
+    pts = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
+    d = renderer.queryDistance(_torch_dev(pts))
+    torch.cuda.synchronize()
+    d = d.cpu().numpy()
+    k = np.r_[0:300, n - 300:n]
+    d_ref, _ = qu.oracle_points(scene, of, pts[k], normals=False)
+    qu.assert_same("large n", d[k], d_ref)
+    dirs = np.repeat(np.array([[0.0, -1.0, 0.3]], np.float32), n, 0)
+    hd = renderer.queryRays(_torch_dev(pts), _torch_dev(dirs))
+    torch.cuda.synchronize()
+    hd = qu.hits_array(hd.cpu().numpy())
+    qu.assert_same("large n rays", hd[k], qu.oracle_rays(scene, of, pts[k], dirs[k]))
+
+
+def test_item_offsets_past_32_bits(renderer):
+    # past item 2^32 / 3 the offset of a float3 record (3 * i) no longer fits 32 bits: the last items must still read their own
+    # point and write their own normal
+    import torch
+
+    scene = "fast_sphere"
+    of = qu.frame(scene, 0.0, W, H)
+    _setup(renderer, scene, of)
+    n = (1 << 32) // 3 + 1000
+    tail = np.random.default_rng(9).uniform(-3, 3, (1000, 3)).astype(np.float32)
+    pts = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    pts[n - 1000:] = torch.from_numpy(tail).cuda()
+    d, nr = renderer.queryDistance(pts, normals=True)
+    torch.cuda.synchronize()
+    d_ref, n_ref = qu.oracle_points(scene, of, tail)
+    qu.assert_same("distance past 2^32 / 3 items", d[n - 1000:].cpu().numpy(), d_ref)
+    qu.assert_same("normal past 2^32 / 3 items", nr[n - 1000:].cpu().numpy(), n_ref)
+    zero_d, zero_n = qu.oracle_points(scene, of, np.zeros((1, 3), np.float32))
+    qu.assert_same("distance of the first items", d[:1000].cpu().numpy(), np.repeat(zero_d, 1000))
+    qu.assert_same("normal of the first items", nr[:1000].cpu().numpy(), np.repeat(zero_n, 1000, 0))
+    del pts, d, nr
+    torch.cuda.empty_cache()
+
+
+def test_device_tensors_are_checked(renderer):
+    import torch
+
+    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    pts = torch.zeros((8, 3), dtype=torch.float32, device="cuda")
+    with pytest.raises(TypeError):
+        renderer.queryDistance(pts.to(torch.int32))
+    with pytest.raises(TypeError):
+        renderer.pick(torch.zeros((8, 2), dtype=torch.float32, device="cuda"), W, H)
+    with pytest.raises(TypeError):
+        renderer.queryRays(pts, pts.t().contiguous().t())  # not contiguous
+    with pytest.raises(ValueError):
+        renderer.queryDistance(pts, out=torch.empty(7, dtype=torch.float32, device="cuda"))
+    out = torch.empty((8, 12), dtype=torch.int32, device="cuda")  # hit records may be int32 as well
+    renderer.queryRays(pts, pts + 1.0, out=out)
+    torch.cuda.synchronize()
+    assert set(out[:, 10].cpu().tolist()) <= {0, 1}
