@@ -1,9 +1,8 @@
 """Builds libsdfr.so (C ABI + gfx950 kernels) in-tree with hipcc.
 
-Every source is compiled to an object of its own, in parallel; the per-scene kernels
-(csrc/sdfr_kernels_group.hip) are compiled once per scene (-DSDFR_GROUP=<scene index>, SDFR_GROUPS units), so that
-the build takes ~20 s on 8 cores instead of a minute and a scene can have code-generation options of its own
-(SCENE_FLAGS below).
+Every source is compiled to an object of its own, in parallel; the per-scene kernels (SCENE_SOURCES) are compiled
+once per scene of the registry (-DSDFR_SCENE=<scene index>, scene_command), so that the build takes ~20 s on 8 cores
+instead of a minute and a scene can have code-generation options of its own (SCENE_FLAGS below).
 
 Flags that matter for correctness:
   -ffp-contract=off   only the explicit fma() calls fuse (arithmetic contract)
@@ -25,8 +24,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsdfr.so")
 OBJDIR = os.path.join(HERE, "build")
 SOURCES = ["sdfr_api.cpp", "sdfr_comm.cpp", "sdfr_hlsl.cpp", "sdfr_jit.cpp", "sdfr_kernels.hip", "sdfr_post.hip"]
-GROUP_SOURCE = "sdfr_kernels_group.hip"
-QUERY_SOURCE = "sdfr_query_group.hip"  # the query kernels, per group as well, with the group's options (a unit of their own)
+# the render kernels, and the query kernels in a unit of their own: both per scene, with the scene's options
+SCENE_SOURCES = ["sdfr_kernels_scene.hip", "sdfr_query_scene.hip"]
 ARCH = "gfx950"
 # Per scene: options that change the register ASSIGNMENT or the instruction ORDER of its kernels, never the arithmetic.  A three-source
 # instruction (v_fma_f32, v_fmac_f32) whose sources all lie in one VGPR bank (register number mod 4) issues at half rate on gfx950
@@ -53,26 +52,21 @@ def scene_registry():
     return [(int(i), n) for i, n in re.findall(r"X\((\d+), (Scene\w+)\)", text)]
 
 
-def group_flags(g, override=None):
-    """Options of compile unit g: those of the scenes in it (one scene per unit: SDFR_GROUPS >= scene count).
-    override: {scene struct name: [flags]} replaces SCENE_FLAGS for those scenes (developer A/B of another register draw)."""
-    groups = scene_groups()
-    flags = []
-    table = dict(SCENE_FLAGS)
-    table.update(override or {})
-    for i, name in scene_registry():
-        if i % groups == g:
-            flags += [f for f in table.get(name, []) if f not in flags or f == "-mllvm"]
-    return flags
-
-
 FLAGS = ["--offload-arch=" + ARCH, "-std=c++17", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-x", "hip", "-Wno-unused-result",
          "-Wno-unknown-pragmas", "-I" + CSRC]
 
 
-def scene_groups():
-    text = open(os.path.join(CSRC, "sdfr_perpixel.h")).read()
-    return int(re.search(r"#define SDFR_GROUPS (\d+)", text).group(1))
+def _hipcc():
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def scene_command(scene, source, out, extra=(), own=None):
+    """The hipcc command of one scene unit: `source` (one of SCENE_SOURCES) for `scene` (struct name) with the shipped options,
+    then `extra`, then the scene's own options -- SCENE_FLAGS, or `own` instead where given -- writing `out`."""
+    index = {name: i for i, name in scene_registry()}[scene]
+    own = SCENE_FLAGS.get(scene, []) if own is None else own
+    return ([_hipcc()] + FLAGS + list(extra) + ["-DSDFR_SCENE=%d" % index] + list(own)
+            + [os.path.join(CSRC, source), "-o", out])
 
 
 def _deps():
@@ -92,31 +86,35 @@ def build(force=False, verbose=False, extra=(), out=None, jobs=None, scene_flags
     scene_flags: {scene struct name: [flags]} instead of SCENE_FLAGS for those scenes (only their units differ from the default build)."""
     if out is None and not force and not _stale():
         return LIB
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    hipcc = _hipcc()
     extra = list(extra)
     objdir = os.path.join(OBJDIR, hashlib.sha1(" ".join(extra).encode()).hexdigest()[:10] if extra else "default")
     os.makedirs(objdir, exist_ok=True)
-    units = [(s, [], os.path.join(objdir, s + ".o")) for s in SOURCES]
-    for g in range(scene_groups()):
-        flags = group_flags(g, scene_flags)
-        tag = "" if flags == group_flags(g) else "." + hashlib.sha1(" ".join(flags).encode()).hexdigest()[:8]
-        for src in (GROUP_SOURCE, QUERY_SOURCE):
-            units.append((src, ["-DSDFR_GROUP=%d" % g] + flags, os.path.join(objdir, "%s.%d%s.o" % (src, g, tag))))
+    source_units, scene_units = [], []  # (object, command)
+    for s in SOURCES:
+        obj = os.path.join(objdir, s + ".o")
+        source_units.append((obj, [hipcc] + FLAGS + extra + ["-c", os.path.join(CSRC, s), "-o", obj]))
+    for i, name in scene_registry():
+        own = (scene_flags or {}).get(name, SCENE_FLAGS.get(name, []))
+        # other options than the scene's own: objects of their own, which a default build never reuses
+        tag = "" if own == SCENE_FLAGS.get(name, []) else "." + hashlib.sha1(" ".join(own).encode()).hexdigest()[:8]
+        for src in SCENE_SOURCES:
+            obj = os.path.join(objdir, "%s.%d%s.o" % (src, i, tag))
+            scene_units.append((obj, scene_command(name, src, obj, extra + ["-c"], own)))
     newest_dep = max(os.path.getmtime(d) for d in _deps())
 
     def compile_unit(u):
-        src, defs, obj = u
+        obj, cmd = u
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > newest_dep:
             return
-        cmd = [hipcc] + FLAGS + extra + defs + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)
 
-    # the group units first: they are the long ones
+    # the scene units first: they are the long ones
     with ThreadPoolExecutor(max_workers=jobs or min(8, os.cpu_count() or 1)) as pool:
-        list(pool.map(compile_unit, sorted(units, key=lambda u: u[0] not in (GROUP_SOURCE, QUERY_SOURCE))))
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-fPIC", "-shared"] + [u[2] for u in units] + ["-o", out or LIB]
+        list(pool.map(compile_unit, scene_units + source_units))
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-fPIC", "-shared"] + [obj for obj, _cmd in source_units + scene_units] + ["-o", out or LIB]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

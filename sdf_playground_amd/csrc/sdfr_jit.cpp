@@ -255,7 +255,7 @@ hipError_t jit_launch_pixel(const JitScene &js, const FrameU &U, const RowMap &r
 	uint32_t n_work = launch_work_items(U.width, rm);
 	if ((size_t)n_work > ws.capacity) return hipErrorInvalidValue;
 	const uint32_t bt = (uint32_t)pixel_block_threads();
-	// a persistent launch, as for the scenes compiled ahead of time (run_pixel, sdfr_kernels_group.hip)
+	// a persistent launch, as for the scenes compiled ahead of time (run_pixel, sdfr_kernels_scene.hip)
 	hipFunction_t fn = frame_needs_debug(U) ? js.pixel_debug : js.pixel;
 	int per_cu = 0, device = 0;
 	if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)bt, 0) != hipSuccess || per_cu < 1) per_cu = 1;

@@ -52,7 +52,7 @@ uint32_t launch_capacity_items(int width, const RowMap &rm)
 }
 
 // =================================================================================================
-// kernels that do not depend on the scene (the per-scene ones: sdfr_kernels_group.hip)
+// kernels that do not depend on the scene (the per-scene ones: sdfr_kernels_scene.hip)
 // =================================================================================================
 // Folds the per-block partial sums of a pixel-schedule launch (one 32-byte record per wave: 4 MB
 // at 4K) into the render totals, which the pixel kernel has cleared: a few blocks, each keeping
@@ -222,7 +222,7 @@ hipError_t launch_reduce_totals(const RenderTotals *partials, uint32_t n_blocks,
 	return hipGetLastError();
 }
 
-// march result fields, list counters: see sdfr_kernels_group.hip
+// march result fields, list counters: see sdfr_kernels_scene.hip
 enum { CNT_ROUND0 = 0 };
 
 // ---- k_init: primary rays, empty queues, cleared accumulators, round-0 list ---------------------
@@ -377,17 +377,14 @@ int device_cu_count(int device)
 	return prop.multiProcessorCount;
 }
 
-// the per-scene launchers live in SDFR_GROUPS translation units (sdfr_kernels_group.hip); scene i is in group i % SDFR_GROUPS
-#define SDFR_DECLARE_GROUP(G) \
-	hipError_t launch_pixel_group##G(int, const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, int); \
-	hipError_t launch_wavefront_group##G(int, const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, \
-		hipEvent_t *, hipEvent_t *, int *);
-SDFR_FOR_EACH_GROUP(SDFR_DECLARE_GROUP)
-#undef SDFR_DECLARE_GROUP
-// ... and their query kernels in as many more (sdfr_query_group.hip)
-#define SDFR_DECLARE_QUERY_GROUP(G) hipError_t launch_query_group##G(int, const FrameU &, const QueryArgs &, hipStream_t);
-SDFR_FOR_EACH_GROUP(SDFR_DECLARE_QUERY_GROUP)
-#undef SDFR_DECLARE_QUERY_GROUP
+// the per-scene launchers: one compile unit per scene of the registry (sdfr_kernels_scene.hip, sdfr_query_scene.hip)
+#define SDFR_DECLARE_SCENE(I, S) \
+	hipError_t launch_pixel_scene##I(const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, int); \
+	hipError_t launch_wavefront_scene##I(const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, \
+		hipEvent_t *, hipEvent_t *, int *); \
+	hipError_t launch_query_scene##I(const FrameU &, const QueryArgs &, hipStream_t);
+SDFR_FOR_EACH_SCENE(SDFR_DECLARE_SCENE)
+#undef SDFR_DECLARE_SCENE
 
 int scene_tile_w_log2(int scene)
 {
@@ -403,13 +400,12 @@ int scene_tile_w_log2(int scene)
 hipError_t launch_pixel_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
 {
-	if (scene < 0 || scene >= SDFR_SCENE_COUNT) return hipErrorInvalidValue;
-	switch (scene % SDFR_GROUPS)
+	switch (scene)
 	{
-#define SDFR_CALL_GROUP(G) case G: return launch_pixel_group##G(scene, U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode);
-		SDFR_FOR_EACH_GROUP(SDFR_CALL_GROUP)
-#undef SDFR_CALL_GROUP
-	default: return hipErrorInvalidValue;
+#define SDFR_CALL_SCENE(I, S) case I: return launch_pixel_scene##I(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode);
+		SDFR_FOR_EACH_SCENE(SDFR_CALL_SCENE)
+#undef SDFR_CALL_SCENE
+	default: return hipErrorInvalidValue; // not a scene of the registry
 	}
 }
 
@@ -417,25 +413,23 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events,
 	int *n_rounds_out)
 {
-	if (scene < 0 || scene >= SDFR_SCENE_COUNT) return hipErrorInvalidValue;
-	switch (scene % SDFR_GROUPS)
+	switch (scene)
 	{
-#define SDFR_CALL_GROUP(G) case G: return launch_wavefront_group##G(scene, U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
-		SDFR_FOR_EACH_GROUP(SDFR_CALL_GROUP)
-#undef SDFR_CALL_GROUP
-	default: return hipErrorInvalidValue;
+#define SDFR_CALL_SCENE(I, S) case I: return launch_wavefront_scene##I(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
+		SDFR_FOR_EACH_SCENE(SDFR_CALL_SCENE)
+#undef SDFR_CALL_SCENE
+	default: return hipErrorInvalidValue; // not a scene of the registry
 	}
 }
 
 hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
-	if (scene < 0 || scene >= SDFR_SCENE_COUNT) return hipErrorInvalidValue;
-	switch (scene % SDFR_GROUPS)
+	switch (scene)
 	{
-#define SDFR_CALL_GROUP(G) case G: return launch_query_group##G(scene, U, q, stream);
-		SDFR_FOR_EACH_GROUP(SDFR_CALL_GROUP)
-#undef SDFR_CALL_GROUP
-	default: return hipErrorInvalidValue;
+#define SDFR_CALL_SCENE(I, S) case I: return launch_query_scene##I(U, q, stream);
+		SDFR_FOR_EACH_SCENE(SDFR_CALL_SCENE)
+#undef SDFR_CALL_SCENE
+	default: return hipErrorInvalidValue; // not a scene of the registry
 	}
 }
 

@@ -1,17 +1,17 @@
-// sdfr_kernels_group.hip -- the per-scene kernels of the renderer (k_pixel, k_march, k_shade; see
-// sdfr_kernels.hip for the two schedules), instantiated for ONE group of scenes.  The build compiles
-// this file SDFR_GROUPS times with -DSDFR_GROUP=0.. (sdf_playground_amd/buildlib.py), in parallel:
-// 23 scenes x 2 debug variants x 3 kernels in one translation unit took a minute to compile, and
-// nothing in one scene's kernels depends on another's.  Scene i belongs to group i % SDFR_GROUPS; with SDFR_GROUPS >= the number
-// of scenes (sdfr_perpixel.h) every scene is a unit of its own and can be built with its own options (buildlib.SCENE_FLAGS).
+// sdfr_kernels_scene.hip -- the per-scene kernels of the renderer (k_pixel, k_march, k_shade; see
+// sdfr_kernels.hip for the two schedules), instantiated for ONE scene.  The build compiles this file
+// once per scene of the registry (sdfr_perpixel.h) with -DSDFR_SCENE=<index> (sdf_playground_amd/buildlib.py),
+// in parallel: 23 scenes x 2 debug variants x 3 kernels in one translation unit took a minute to compile,
+// nothing in one scene's kernels depends on another's, and a scene can be built with options of its own
+// (buildlib.SCENE_FLAGS).
 #include <cstdlib>
 
 #include "sdfr_kernels.h"
 #include "sdfr_perpixel.h"
 #include "sdfr_pixel_kernel.h"
 
-#ifndef SDFR_GROUP
-#error "compile with -DSDFR_GROUP=<0 .. SDFR_GROUPS-1>"
+#ifndef SDFR_SCENE
+#error "compile with -DSDFR_SCENE=<scene index, sdfr_perpixel.h>"
 #endif
 
 namespace sdfr {
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(SDFR_BLOCK) void k_shade(FrameU U, RowMap rm, Wavef
 }
 
 // =================================================================================================
-// launchers of this group's scenes
+// launchers of this unit's scene
 // =================================================================================================
 template <class Scene, bool DBG>
 static hipError_t run_pixel(const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
@@ -402,59 +402,23 @@ static hipError_t run_wavefront(const FrameU &U, const RowMap &rm, void *out, in
 	return hipGetLastError();
 }
 
-// a scene outside this group is not instantiated here
-template <class Scene, bool InGroup>
-struct GroupRunner
-{
-	static hipError_t pixel(const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, int, int) { return hipErrorInvalidValue; }
-	static hipError_t wavefront(const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, hipEvent_t *,
-		hipEvent_t *, int *)
-	{
-		return hipErrorInvalidValue;
-	}
-};
-template <class Scene>
-struct GroupRunner<Scene, true>
-{
-	static hipError_t pixel(const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
-		const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode, int scene_index)
-	{
-		return frame_needs_debug(U) ? run_pixel<Scene, true>(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, scene_index)
-									: run_pixel<Scene, false>(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, scene_index);
-	}
-	static hipError_t wavefront(const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
-		const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events, int *n_rounds_out)
-	{
-		return frame_needs_debug(U) ? run_wavefront<Scene, true>(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out)
-									: run_wavefront<Scene, false>(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
-	}
-};
-
+// the entry points sdfr_kernels.hip dispatches to, named by the scene's index
 #define SDFR_CAT2(a, b) a##b
 #define SDFR_CAT(a, b) SDFR_CAT2(a, b)
+using UnitScene = SceneAt<SDFR_SCENE>::type;
 
-hipError_t SDFR_CAT(launch_pixel_group, SDFR_GROUP)(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
-	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
+hipError_t SDFR_CAT(launch_pixel_scene, SDFR_SCENE)(const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
+	const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
 {
-	switch (scene)
-	{
-#define SDFR_RUN(I, S) case I: return GroupRunner<S, (I) % SDFR_GROUPS == SDFR_GROUP>::pixel(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, I);
-		SDFR_FOR_EACH_SCENE(SDFR_RUN)
-#undef SDFR_RUN
-	default: return hipErrorInvalidValue;
-	}
+	return frame_needs_debug(U) ? run_pixel<UnitScene, true>(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, SDFR_SCENE)
+								: run_pixel<UnitScene, false>(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, SDFR_SCENE);
 }
 
-hipError_t SDFR_CAT(launch_wavefront_group, SDFR_GROUP)(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
+hipError_t SDFR_CAT(launch_wavefront_scene, SDFR_SCENE)(const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events, int *n_rounds_out)
 {
-	switch (scene)
-	{
-#define SDFR_RUN(I, S) case I: return GroupRunner<S, (I) % SDFR_GROUPS == SDFR_GROUP>::wavefront(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
-		SDFR_FOR_EACH_SCENE(SDFR_RUN)
-#undef SDFR_RUN
-	default: return hipErrorInvalidValue;
-	}
+	return frame_needs_debug(U) ? run_wavefront<UnitScene, true>(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out)
+								: run_wavefront<UnitScene, false>(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
 }
 
 } // namespace sdfr

@@ -469,7 +469,7 @@ __device__ __forceinline__ void noise_grads_fill<NoiseGradLds>()
 }
 
 // body of the pixel kernel; the __global__ wrappers are k_pixel (scenes compiled ahead of time,
-// sdfr_kernels_group.hip) and the extern "C" kernels sdfr_jit.cpp generates around a run-time scene
+// sdfr_kernels_scene.hip) and the extern "C" kernels sdfr_jit.cpp generates around a run-time scene
 // NG: the gradient source of the shading's noise -- the formula unless the wrapper passes the LDS table (NoiseGradLds)
 template <class Scene, bool DBG, class NG = NoiseGradFormula>
 __device__ __forceinline__ void pixel_kernel(const PixelKernelArgs &args_by_value)

@@ -1,5 +1,5 @@
 // sdfr_query_kernel.h -- the query kernels (sdfr_query.h), one lane per item.  Shared by the kernels compiled ahead of time
-// (sdfr_query_group.hip, a translation unit of its own so that the pixel kernels' code does not change) and by the query
+// (sdfr_query_scene.hip, a translation unit of its own so that the pixel kernels' code does not change) and by the query
 // module sdfr_jit.cpp builds for a scene compiled at run time.  Device compilation only.
 //
 // Items are read as float3 / int2 records of consecutive lanes (coalesced), results leave as 16-byte stores; launched with

@@ -1,6 +1,6 @@
-// sdfr_query_group.hip -- the query kernels (k_query_points, k_query_rays: sdfr_query_kernel.h) of ONE scene group, compiled
-// once per group with -DSDFR_GROUP=<g> and the group's code-generation options (sdf_playground_amd/buildlib.py), like
-// sdfr_kernels_group.hip.  They live in a unit of their own: a second caller of the shared inline stages in the pixel kernels'
+// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays: sdfr_query_kernel.h) of ONE scene, compiled
+// once per scene with -DSDFR_SCENE=<index> and the scene's code-generation options (sdf_playground_amd/buildlib.py), like
+// sdfr_kernels_scene.hip.  They live in a unit of their own: a second caller of the shared inline stages in the pixel kernels'
 // unit could change the inliner's decisions there, and with them k_pixel's code.
 //
 // Plain IEEE sqrt / reciprocal / constant division (SDFR_SAFE_MATH, sdfr_math.h), as scenes compiled at run time get them: the
@@ -12,8 +12,8 @@
 #include "sdfr_perpixel.h"
 #include "sdfr_query_kernel.h"
 
-#ifndef SDFR_GROUP
-#error "compile with -DSDFR_GROUP=<0 .. SDFR_GROUPS-1>"
+#ifndef SDFR_SCENE
+#error "compile with -DSDFR_SCENE=<scene index, sdfr_perpixel.h>"
 #endif
 
 namespace sdfr {
@@ -45,33 +45,13 @@ static hipError_t run_query(const FrameU &U, const QueryArgs &q, hipStream_t str
 	return hipGetLastError();
 }
 
-// a scene outside this group is not instantiated here
-template <class Scene, bool InGroup>
-struct QueryRunner
-{
-	static hipError_t run(const FrameU &, const QueryArgs &, hipStream_t) { return hipErrorInvalidValue; }
-};
-template <class Scene>
-struct QueryRunner<Scene, true>
-{
-	static hipError_t run(const FrameU &U, const QueryArgs &q, hipStream_t stream)
-	{
-		return frame_needs_debug(U) ? run_query<Scene, true>(U, q, stream) : run_query<Scene, false>(U, q, stream);
-	}
-};
-
 #define SDFR_CAT2(a, b) a##b
 #define SDFR_CAT(a, b) SDFR_CAT2(a, b)
+using UnitScene = SceneAt<SDFR_SCENE>::type;
 
-hipError_t SDFR_CAT(launch_query_group, SDFR_GROUP)(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream)
+hipError_t SDFR_CAT(launch_query_scene, SDFR_SCENE)(const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
-	switch (scene)
-	{
-#define SDFR_RUN(I, S) case I: return QueryRunner<S, (I) % SDFR_GROUPS == SDFR_GROUP>::run(U, q, stream);
-		SDFR_FOR_EACH_SCENE(SDFR_RUN)
-#undef SDFR_RUN
-	default: return hipErrorInvalidValue;
-	}
+	return frame_needs_debug(U) ? run_query<UnitScene, true>(U, q, stream) : run_query<UnitScene, false>(U, q, stream);
 }
 
 } // namespace sdfr

@@ -2,7 +2,7 @@
 
     python tools/isa_loops.py <scene struct name, e.g. SceneCubeSea> [extra hipcc flags]
 
-Compiles the scene's group of csrc/sdfr_kernels_group.hip to assembly and lists every loop of
+Compiles the scene's unit of csrc/sdfr_kernels_scene.hip to assembly and lists every loop of
 k_pixel<Scene, false> with its instruction counts by issue class (tools/ubench: full rate /
 half rate / transcendental), spills and memory operations."""
 import os
@@ -18,17 +18,14 @@ TRANS = ("v_rsq", "v_rcp", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")
 
 
 def compile_scene(scene, extra_flags=None, out_dir="/tmp"):
-    """hipcc -S of the scene's compile unit with the shipped options (buildlib.FLAGS + the scene's own, buildlib.SCENE_FLAGS);
-    returns (assembly text, the compiler's kernel-resource-usage remarks)."""
-    text = open(os.path.join(CSRC, "sdfr_perpixel.h")).read()
-    idx = int(re.search(r"X\((\d+), %s\)" % scene, text).group(1))
-    groups = int(re.search(r"#define SDFR_GROUPS (\d+)", text).group(1))
-    out = os.path.join(out_dir, "isa_%s.s" % scene)
+    """hipcc -S of the scene's compile unit with the shipped options (buildlib.scene_command: buildlib.FLAGS + the scene's own,
+    buildlib.SCENE_FLAGS, which `extra_flags` replace where given); returns (assembly text, the compiler's kernel-resource-usage remarks)."""
     sys.path.insert(0, ROOT)
-    from sdf_playground_amd.buildlib import group_flags  # the scene's own code-generation options, unless the caller passes some
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-x", "hip", "-Wno-unused-result",
-           "-Wno-unknown-pragmas", "-I" + CSRC, "-DSDFR_GROUP=%d" % (idx % groups), "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-           os.path.join(CSRC, "sdfr_kernels_group.hip"), "-o", out] + (list(extra_flags) if extra_flags else group_flags(idx % groups))
+    from sdf_playground_amd import buildlib
+
+    out = os.path.join(out_dir, "isa_%s.s" % scene)
+    cmd = buildlib.scene_command(scene, "sdfr_kernels_scene.hip", out, ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"],
+                                 extra_flags or None)
     r = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, text=True)
     return open(out).read(), r.stderr
 
