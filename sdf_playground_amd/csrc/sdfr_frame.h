@@ -153,6 +153,11 @@ SDF_HD void row_map_tiles(RowMap &rm, int width)
 	rm.tiles_x = ((uint32_t)width + (1u << rm.tile_w_log2) - 1u) >> rm.tile_w_log2;
 	rm.tiles_x_magic = rm.tiles_x > 1u ? (uint32_t)(0x100000000ull / rm.tiles_x) : 0xffffffffu;
 }
+// most hand-out units (tile rows, or squares of tiles) a launch keeps row feedback for (sdfr_pixel_kernel.h); the launch plan
+// (sdfr_launch_plan.h) cuts a frame into at most this many squares
+#ifndef SDFR_ROW_FEEDBACK_MAX
+#define SDFR_ROW_FEEDBACK_MAX 512u
+#endif
 // squares of tiles such that the frame has at most `max_units` of them; not for strip launches (their rows are not the frame's)
 SDF_HD void row_map_units(RowMap &rm, uint32_t max_units)
 {
@@ -187,18 +192,10 @@ SDF_HD void split_by_magic(uint32_t n, uint32_t d, uint32_t magic, uint32_t &quo
 	quotient = q;
 	rest = r;
 }
-// tile / tiles_x and tile % tiles_x: with m = floor(2^32 / d) the estimate mulhi(n, m) is the quotient or one below it
+// tile / tiles_x and tile % tiles_x
 SDF_HD void tile_row_and_column(const RowMap &rm, uint32_t tile, uint32_t &row, uint32_t &column)
 {
-	uint32_t q = (uint32_t)(((unsigned long long)tile * rm.tiles_x_magic) >> 32);
-	uint32_t r = tile - q * rm.tiles_x;
-	if (r >= rm.tiles_x)
-	{
-		q += 1u;
-		r -= rm.tiles_x;
-	}
-	row = q;
-	column = r;
+	split_by_magic(tile, rm.tiles_x, rm.tiles_x_magic, row, column);
 }
 
 // local strip index of this launch -> strip index in the frame

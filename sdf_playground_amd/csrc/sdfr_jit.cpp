@@ -252,42 +252,14 @@ JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const
 hipError_t jit_launch_pixel(const JitScene &js, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
 {
-	uint32_t n_work = launch_work_items(U.width, rm);
-	if ((size_t)n_work > ws.capacity) return hipErrorInvalidValue;
-	const uint32_t bt = (uint32_t)pixel_block_threads();
-	// a persistent launch, as for the scenes compiled ahead of time (run_pixel, sdfr_kernels_scene.hip)
-	hipFunction_t fn = frame_needs_debug(U) ? js.pixel_debug : js.pixel;
-	int per_cu = 0, device = 0;
-	if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)bt, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-	(void)hipGetDevice(&device);
-	const PixelLaunchMode mode = pixel_launch_mode(launch_mode, false); // a run-time scene: one wave per tile unless asked otherwise
-	if (mode.blocks_per_cu > 0 && mode.blocks_per_cu < per_cu) per_cu = mode.blocks_per_cu;
-	PixelKernelArgs pk;
-	pk.U = U;
-	pk.rm = rm;
-	const uint32_t hand_out_items = n_work; // (tile rows: squares of tiles -- RowMap::unit_log2 -- are a built-in scene's own choice)
-	if ((size_t)hand_out_items > ws.capacity) return hipErrorInvalidValue;
-	const uint32_t blocks = pixel_launch_blocks(mode, (hand_out_items + bt - 1u) / bt, (uint32_t)(device_cu_count(device) * per_cu));
-	pk.rm.retire_after = mode.persistent ? (uint32_t)mode.retire_after : 0u;
+	// the launch of the scenes compiled ahead of time (launch_pixel, sdfr_kernels.hip), with the traits of a run-time scene: one wave
+	// per tile unless asked otherwise, tile rows only (squares of tiles -- RowMap::unit_log2 -- are a built-in scene's own choice)
+	const bool dbg = frame_needs_debug(U);
 	uint32_t name_hash = 2166136261u; // a run-time scene is known by its name
 	for (char ch : js.name) name_hash = (name_hash ^ (unsigned char)ch) * 16777619u;
-	const uint32_t tiles_x = ((uint32_t)U.width + (1u << rm.tile_w_log2) - 1u) >> rm.tile_w_log2;
-	const uint32_t feedback_rows = !mode.persistent ? 0u : pk.rm.unit_log2 ? pk.rm.units : ((n_work + bt - 1u) / bt) / tiles_x;
-	pk.rm.feedback_key = mode.persistent ? pixel_feedback_key(0x80000000u | name_hash | (frame_needs_debug(U) ? 1u : 0u), U.width, pk.rm, feedback_rows) : 0u;
-	pk.n_work = hand_out_items;
-	pk.format = format;
-	pk.out = out;
-	pk.pixel_stats = pixel_stats;
-	pk.partials = ws.partials;
-	pk.totals = totals;
-	pk.ray_queue = ws.ray_queue;
-	pk.cap = ws.capacity;
-	pk.tile_cursors = mode.persistent ? ws.tile_cursors : nullptr;
-	RenderTotals *partials = ws.partials;
-	void *args[] = {&pk};
-	const hipError_t e = hipModuleLaunchKernel(fn, blocks, 1, 1, bt, 1, 1, 0, stream, args, nullptr);
-	if (e != hipSuccess) return e;
-	return launch_reduce_totals(partials, blocks, totals, stream, ws.tile_cursors, feedback_rows, (unsigned long long)n_work, pk.rm.feedback_key);
+	const PixelSceneTraits traits = {false, 8, false, 0x80000000u | name_hash | (dbg ? 1u : 0u)};
+	const PixelKernelRef k = {nullptr, dbg ? js.pixel_debug : js.pixel, nullptr}; // (a module's occupancy is asked on every launch)
+	return launch_pixel(k, traits, U, rm, out, format, pixel_stats, totals, ws, stream, launch_mode);
 }
 
 } // namespace sdfr

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "sdfr_frame.h"
+#include "sdfr_launch_plan.h"
 
 namespace sdfr {
 
@@ -24,6 +25,28 @@ struct WavefrontWorkspace
 	RenderTotals *partials; // [capacity / 64 + 1] per-block counter sums of the pixel schedule
 	uint32_t *tile_cursors; // [8 x 32] tile hand-out counters of the pixel kernel (TileQueue), zero between launches
 };
+
+// list entries a march wave (k_march) claims per atomic; the wavefront launcher sizes its grid by it
+#define SDFR_GRAB 128
+
+// What a scene unit (sdfr_kernels_scene.hip, one per scene of the registry) exports: its kernels by host pointer, [DBG], and
+// how the scene wants them launched.  Everything that plans and launches lives in sdfr_kernels.hip, once.
+struct SceneKernels
+{
+	const void *pixel[2], *march[2], *shade[2];
+	bool persistent_tiles, square_units; // PersistentTiles, SquareUnits (sdfr_render_pixel.h)
+	int retire_after, tile_w_log2;       // RetireAfter, SceneTileShape
+};
+// ... and a scene's query unit (sdfr_query_scene.hip)
+struct SceneQueryKernels
+{
+	const void *points[2], *rays[2];
+};
+// a unit names its getter by its scene's index: scene_kernels_<index>(), scene_query_kernels_<index>()
+#define SDFR_CAT2(a, b) a##b
+#define SDFR_CAT(a, b) SDFR_CAT2(a, b)
+const SceneKernels *scene_kernels(int scene); // null: not a scene of the registry
+const SceneQueryKernels *scene_query_kernels(int scene);
 
 hipError_t launch_pixel_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode = 0);
@@ -55,33 +78,23 @@ hipError_t launch_wavefront_init(const FrameU &U, const RowMap &rm, uint32_t n_w
 // feedback_rows: tile rows of the launch if it was a persistent one whose rows should be re-ordered for the next frame (else 0)
 hipError_t launch_reduce_totals(const RenderTotals *partials, uint32_t n_blocks, RenderTotals *totals, hipStream_t stream, uint32_t *tile_cursors,
 	uint32_t feedback_rows, unsigned long long frame_pixels, uint32_t feedback_key);
-// RowMap::feedback_key of a launch: scene (index, or a hash of a run-time scene's name), frame width and what the row map selects,
-// hashed into the upper 22 bits; the low 10 bits ARE the number of units (tile rows or squares, <= SDFR_ROW_FEEDBACK_MAX = 512) the
-// order was made for: two launches with equal keys have equally long orders whatever the hash does
-uint32_t pixel_feedback_key(uint32_t scene_key, int width, const RowMap &rm, uint32_t feedback_rows);
 int pixel_tile_cursor_words();
 int scene_tile_w_log2(int scene); // the tile shape a built-in scene asks for (SceneTileShape); 3 = 8 x 8, also for run-time scenes
-// how the pixel kernels are launched: persistent (resident waves pull tiles from the cursors) or one wave per
-// tile.  launch_mode: 0 = the scene's own default (PersistentTiles), 1 = one wave per tile, 2 = persistent;
-// the developer knobs SDFR_PIXEL_PERSISTENT=0|1 and SDFR_PIXEL_BLOCKS_PER_CU=n (cap of a persistent grid) override.
-// retire_after (persistent launches; SDFR_PIXEL_RETIRE_AFTER=n overrides, 0 = never): see pixel_launch_blocks.
-struct PixelLaunchMode { bool persistent; int blocks_per_cu; int retire_after; };
-PixelLaunchMode pixel_launch_mode(int launch_mode, bool scene_default_persistent, int scene_retire_after = 8);
-// Blocks of a pixel launch.  One wave per tile: as many as tiles.  Persistent: what stays resident -- and, when waves
-// retire after `retire_after` tiles, the replacements as well: tiles / retire_after, plus half a chip of waves that
-// end for want of tiles before they have had their share.  Why waves retire: a SIMD serves its oldest waves first, so
-// of the waves that start together the ones in its upper slots crawl for the whole frame (tools/wave_trace.py: two
-// tiles against sixty), and what they hold when the queue runs dry is finished by one or two waves per SIMD while the
-// rest of the chip idles -- the last 7 % of a labyrinth frame, a fifth of a fractal frame.  A wave that leaves after 8
-// tiles is replaced by a younger one, the crawlers become the oldest and catch up.  Measured (ms per frame, one frame
-// in flight; never / 4 / 8 / 16): labyrinth 4K 1.375 / 1.370 / 1.359 / 1.366, cube_sea 1080p 0.883 / 0.844 / 0.840 /
-// 0.877, fractal 4K 1.607 / 1.470 / 1.485 / 1.549 (one wave per tile: 1.397, -, 1.482).
-uint32_t pixel_launch_blocks(const PixelLaunchMode &mode, uint32_t tiles, uint32_t resident_blocks);
+// How launch_pixel reaches a pixel kernel: a kernel of this library by its host pointer (`kernel`), or a function of a module
+// loaded at run time (`function`, sdfr_jit.cpp).  blocks_per_cu: where the occupancy query's answer is kept between launches
+// (0 = not asked yet), or null to ask on every launch.
+struct PixelKernelRef
+{
+	const void *kernel;
+	hipFunction_t function;
+	int *blocks_per_cu;
+};
+// One launch of the pixel schedule, for built-in and run-time scenes alike: reads the developer knobs, asks how many blocks of the
+// kernel stay resident, plans (plan_pixel_launch, sdfr_launch_plan.h), launches the kernel and then the fold (launch_reduce_totals).
+hipError_t launch_pixel(const PixelKernelRef &k, const PixelSceneTraits &scene, const FrameU &U, const RowMap &rm, void *out, int format,
+	uint32_t *pixel_stats, RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode);
 
 int pixel_block_threads(); // block size of the pixel kernels (partials are sized by it)
 int device_cu_count(int device);
-// work items (padded to whole tiles) of a launch: lists and per-pixel state are sized by this
-uint32_t launch_work_items(int width, const RowMap &rm);
-uint32_t launch_capacity_items(int width, const RowMap &rm); // >= launch_work_items: what the workspace of a launch is sized for
 
 } // namespace sdfr

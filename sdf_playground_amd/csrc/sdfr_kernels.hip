@@ -29,27 +29,9 @@
 #include <cstdlib>
 #include "sdfr_perpixel.h"
 #include "sdfr_pixel_kernel.h"
+#include "sdfr_query.h"
 
 namespace sdfr {
-
-uint32_t launch_work_items(int width, const RowMap &rm)
-{
-	const uint32_t tw_log2 = (uint32_t)rm.tile_w_log2, th_log2 = 6u - tw_log2;
-	const uint32_t tiles_x = ((uint32_t)width + (1u << tw_log2) - 1u) >> tw_log2;
-	const uint32_t tiles_y = ((uint32_t)rm.local_rows + (1u << th_log2) - 1u) >> th_log2;
-	return tiles_x * tiles_y * 64u;
-}
-// what a handle's per-launch scratch is sized for: the work items, or -- a persistent launch hands a full frame out in squares of tiles that
-// cover it with a margin (row_map_units), and launches at most one block per tile handed out -- the items of those squares
-uint32_t launch_capacity_items(int width, const RowMap &rm)
-{
-	const uint32_t items = launch_work_items(width, rm);
-	RowMap units = rm;
-	row_map_tiles(units, width);
-	row_map_units(units, SDFR_ROW_FEEDBACK_MAX);
-	const uint32_t padded = units.unit_log2 ? (units.units << (2u * units.unit_log2)) * 64u : 0u;
-	return padded > items ? padded : items;
-}
 
 // =================================================================================================
 // kernels that do not depend on the scene (the per-scene ones: sdfr_kernels_scene.hip)
@@ -170,42 +152,6 @@ __global__ __launch_bounds__(SDFR_REDUCE_THREADS) void k_reduce_totals(const Ren
 }
 int pixel_tile_cursor_words() { return (int)SDFR_CURSOR_WORDS; }
 
-PixelLaunchMode pixel_launch_mode(int launch_mode, bool scene_default_persistent, int scene_retire_after)
-{
-	static const int env_persistent = [] { const char *e = getenv("SDFR_PIXEL_PERSISTENT"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-	static const int env_blocks = [] { const char *e = getenv("SDFR_PIXEL_BLOCKS_PER_CU"); return e ? atoi(e) : 0; }();
-	PixelLaunchMode m;
-	m.persistent = launch_mode == 2 || (launch_mode == 0 && scene_default_persistent);
-	if (env_persistent >= 0) m.persistent = env_persistent != 0;
-	m.blocks_per_cu = env_blocks;
-	static const int env_retire = [] { const char *e = getenv("SDFR_PIXEL_RETIRE_AFTER"); return e ? atoi(e) : -1; }();
-	m.retire_after = env_retire >= 0 ? env_retire : scene_retire_after;
-	return m;
-}
-
-uint32_t pixel_launch_blocks(const PixelLaunchMode &mode, uint32_t tiles, uint32_t resident_blocks)
-{
-	if (!mode.persistent) return tiles;
-	uint32_t blocks = resident_blocks;
-	if (mode.retire_after > 0) blocks = resident_blocks / 2u + tiles / (uint32_t)mode.retire_after;
-	if (blocks < resident_blocks) blocks = resident_blocks;
-	return blocks < tiles ? blocks : tiles;
-}
-
-uint32_t pixel_feedback_key(uint32_t scene_key, int width, const RowMap &rm, uint32_t feedback_rows)
-{
-	static_assert(SDFR_ROW_FEEDBACK_MAX < 1024u, "the unit count rides in the key's low 10 bits");
-	if (feedback_rows > SDFR_ROW_FEEDBACK_MAX) return 0u; // no feedback for such a launch (the kernel and the fold agree: fb_rows <= MAX)
-	// FNV-1a over what a row order depends on; never 0
-	uint32_t h = 2166136261u;
-	const uint32_t words[] = {scene_key, (uint32_t)width, (uint32_t)rm.local_rows, (uint32_t)rm.rank, (uint32_t)rm.world, (uint32_t)rm.tile_w_log2,
-		(uint32_t)rm.priv_count, (uint32_t)rm.priv_period, (uint32_t)rm.direct, rm.unit_log2};
-	for (uint32_t w : words)
-		for (int b = 0; b < 4; ++b) h = (h ^ ((w >> (8 * b)) & 0xffu)) * 16777619u;
-	h = (h & ~1023u) | feedback_rows;
-	return h ? h : 1024u;
-}
-
 hipError_t launch_reduce_totals(const RenderTotals *partials, uint32_t n_blocks, RenderTotals *totals, hipStream_t stream, uint32_t *tile_cursors,
 	uint32_t feedback_rows, unsigned long long frame_pixels, uint32_t feedback_key)
 {
@@ -222,7 +168,7 @@ hipError_t launch_reduce_totals(const RenderTotals *partials, uint32_t n_blocks,
 	return hipGetLastError();
 }
 
-// march result fields, list counters: see sdfr_kernels_scene.hip
+// counters[]: [r] = size of round r's list (r = 0..16); [32 + r] = march cursor of round r
 enum { CNT_ROUND0 = 0 };
 
 // ---- k_init: primary rays, empty queues, cleared accumulators, round-0 list ---------------------
@@ -377,60 +323,161 @@ int device_cu_count(int device)
 	return prop.multiProcessorCount;
 }
 
-// the per-scene launchers: one compile unit per scene of the registry (sdfr_kernels_scene.hip, sdfr_query_scene.hip)
+// the scenes' kernels and launch traits: one compile unit per scene of the registry exports them (sdfr_kernels_scene.hip, sdfr_query_scene.hip)
 #define SDFR_DECLARE_SCENE(I, S) \
-	hipError_t launch_pixel_scene##I(const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, int); \
-	hipError_t launch_wavefront_scene##I(const FrameU &, const RowMap &, void *, int, uint32_t *, RenderTotals *, const WavefrontWorkspace &, hipStream_t, \
-		hipEvent_t *, hipEvent_t *, int *); \
-	hipError_t launch_query_scene##I(const FrameU &, const QueryArgs &, hipStream_t);
+	const SceneKernels *SDFR_CAT(scene_kernels_, I)(); \
+	const SceneQueryKernels *SDFR_CAT(scene_query_kernels_, I)();
 SDFR_FOR_EACH_SCENE(SDFR_DECLARE_SCENE)
 #undef SDFR_DECLARE_SCENE
+const SceneKernels *scene_kernels(int scene)
+{
+#define SDFR_SCENE_CASE(I, S) case I: return SDFR_CAT(scene_kernels_, I)();
+	switch (scene) { SDFR_FOR_EACH_SCENE(SDFR_SCENE_CASE) default: return nullptr; } // not a scene of the registry
+#undef SDFR_SCENE_CASE
+}
+const SceneQueryKernels *scene_query_kernels(int scene)
+{
+#define SDFR_SCENE_CASE(I, S) case I: return SDFR_CAT(scene_query_kernels_, I)();
+	switch (scene) { SDFR_FOR_EACH_SCENE(SDFR_SCENE_CASE) default: return nullptr; }
+#undef SDFR_SCENE_CASE
+}
 
 int scene_tile_w_log2(int scene)
 {
-	switch (scene)
+	const SceneKernels *k = scene_kernels(scene);
+	return k ? k->tile_w_log2 : 3;
+}
+
+// ---- PIXEL schedule (kernel body: sdfr_pixel_kernel.h; the plan: sdfr_launch_plan.h) ----
+static int env_int(const char *name, int unset)
+{
+	const char *e = getenv(name);
+	return e ? atoi(e) : unset;
+}
+
+hipError_t launch_pixel(const PixelKernelRef &k, const PixelSceneTraits &scene, const FrameU &U, const RowMap &rm, void *out, int format,
+	uint32_t *pixel_stats, RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
+{
+	static_assert(SDFR_PIXEL_BLOCK == SDFR_TILE_ITEMS, "the plan counts one block per tile");
+	static const PixelLaunchKnobs knobs = [] { // developer knobs, read once
+		PixelLaunchKnobs k;
+		const char *e = getenv("SDFR_PIXEL_PERSISTENT");
+		k.persistent = e ? (atoi(e) != 0 ? 1 : 0) : -1;
+		k.blocks_per_cu = env_int("SDFR_PIXEL_BLOCKS_PER_CU", 0);
+		k.retire_after = env_int("SDFR_PIXEL_RETIRE_AFTER", -1);
+		k.square_units = env_int("SDFR_PIXEL_SQUARE_UNITS", -1); // 0: tile rows for every scene
+		return k;
+	}();
+	// a persistent launch: as many blocks as stay resident, each pulling tiles until none is left
+	// (TileQueue, sdfr_pixel_kernel.h).  The occupancy query may over-state by a block per CU for
+	// SGPR-heavy kernels (MI355X_MICROARCH.md); a surplus block simply starts when another has ended.
+	int blocks_per_cu = k.blocks_per_cu ? *k.blocks_per_cu : 0;
+	if (blocks_per_cu == 0)
 	{
-#define SDFR_SHAPE(I, S) case I: return SceneTileShape<S>::value;
-		SDFR_FOR_EACH_SCENE(SDFR_SHAPE)
-#undef SDFR_SHAPE
-	default: return 3;
+		const hipError_t e = k.function ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k.function, SDFR_PIXEL_BLOCK, 0)
+										: hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k.kernel, SDFR_PIXEL_BLOCK, 0);
+		if (e != hipSuccess || blocks_per_cu < 1) blocks_per_cu = 1;
+		if (k.blocks_per_cu) *k.blocks_per_cu = blocks_per_cu;
 	}
+	int device = 0;
+	(void)hipGetDevice(&device);
+	const PixelLaunchPlan plan = plan_pixel_launch(scene, knobs, launch_mode, U.width, rm, ws.capacity, blocks_per_cu, device_cu_count(device));
+	if (!plan.fits) return hipErrorInvalidValue;
+	PixelKernelArgs args = {U, plan.rows, plan.n_work, format, out, pixel_stats, ws.partials, totals, ws.ray_queue, ws.capacity,
+		plan.tile_cursors ? ws.tile_cursors : nullptr};
+	void *kernel_args[] = {&args};
+	if (k.function)
+	{
+		const hipError_t e = hipModuleLaunchKernel(k.function, plan.blocks, 1, 1, SDFR_PIXEL_BLOCK, 1, 1, 0, stream, kernel_args, nullptr);
+		if (e != hipSuccess) return e;
+	}
+	else
+		(void)hipLaunchKernel(k.kernel, dim3(plan.blocks), dim3(SDFR_PIXEL_BLOCK), kernel_args, 0, stream); // (a failure is the last error the fold's launcher returns)
+	return launch_reduce_totals(ws.partials, plan.blocks, totals, stream, ws.tile_cursors, plan.feedback_rows, plan.frame_pixels, plan.rows.feedback_key);
 }
 
 hipError_t launch_pixel_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
 {
-	switch (scene)
-	{
-#define SDFR_CALL_SCENE(I, S) case I: return launch_pixel_scene##I(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode);
-		SDFR_FOR_EACH_SCENE(SDFR_CALL_SCENE)
-#undef SDFR_CALL_SCENE
-	default: return hipErrorInvalidValue; // not a scene of the registry
-	}
+	const SceneKernels *sk = scene_kernels(scene);
+	if (!sk) return hipErrorInvalidValue;
+	const int dbg = frame_needs_debug(U) ? 1 : 0;
+	static int blocks_per_cu[SDFR_SCENE_COUNT][2]; // asked once per kernel and process (not per device: every device of a process is taken to be alike)
+	const PixelKernelRef k = {sk->pixel[dbg], nullptr, &blocks_per_cu[scene][dbg]};
+	const PixelSceneTraits traits = {sk->persistent_tiles, sk->retire_after, sk->square_units, (uint32_t)scene * 2u + (uint32_t)dbg};
+	return launch_pixel(k, traits, U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode);
 }
 
-hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
+// ---- WAVEFRONT schedule ----
+hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events,
 	int *n_rounds_out)
 {
-	switch (scene)
+	const SceneKernels *sk = scene_kernels(scene);
+	if (!sk) return hipErrorInvalidValue;
+	const int dbg = frame_needs_debug(U) ? 1 : 0;
+	const uint32_t n_work = launch_work_items(U.width, rm);
+	if ((size_t)n_work > ws.capacity) return hipErrorInvalidValue; // lists are indexed by work item, state by pixel id < n_work
+	const uint32_t init_blocks = (n_work + SDFR_BLOCK - 1) / SDFR_BLOCK;
+	(void)launch_wavefront_init(U, rm, n_work, ws, pixel_stats, stream);
+
+	int device = 0;
+	(void)hipGetDevice(&device);
+	const int cus = device_cu_count(device);
+	int march_blocks_per_cu = 0, shade_blocks_per_cu = 0;
+	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&march_blocks_per_cu, sk->march[dbg], SDFR_BLOCK, 0);
+	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&shade_blocks_per_cu, sk->shade[dbg], SDFR_BLOCK, 0);
+	if (march_blocks_per_cu < 1) march_blocks_per_cu = 1;
+	if (shade_blocks_per_cu < 1) shade_blocks_per_cu = 1;
+	// persistent grids: what the occupancy query calls resident (it may over-state by a block
+	// per CU for SGPR-heavy kernels; harmless here because work is claimed dynamically), but
+	// never more waves than there are ranges to claim
+	const uint32_t grabs = (n_work + SDFR_GRAB - 1u) / SDFR_GRAB;
+	uint32_t march_blocks = (uint32_t)(cus * march_blocks_per_cu);
+	if (march_blocks > (grabs + 3u) / 4u) march_blocks = (grabs + 3u) / 4u;
+	if (march_blocks < 1) march_blocks = 1;
+	uint32_t shade_blocks = (uint32_t)(cus * shade_blocks_per_cu);
+	if (shade_blocks > init_blocks) shade_blocks = init_blocks;
+	if (shade_blocks < 1) shade_blocks = 1;
+
+	// the kernels' parameters (k_march, k_shade: sdfr_kernels_scene.hip) by address
+	FrameU frame = U;
+	RowMap rows = rm;
+	WavefrontWorkspace work = ws;
+	uint32_t *list_cur = ws.list_a, *list_next = ws.list_b;
+	const int rounds = U.bounce_count;
+	for (int r = 0; r < rounds; ++r)
 	{
-#define SDFR_CALL_SCENE(I, S) case I: return launch_wavefront_scene##I(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
-		SDFR_FOR_EACH_SCENE(SDFR_CALL_SCENE)
-#undef SDFR_CALL_SCENE
-	default: return hipErrorInvalidValue; // not a scene of the registry
+		uint32_t *n_cur = ws.counters + r, *n_next = ws.counters + r + 1, *cursor = ws.counters + 32 + r;
+		void *march_args[] = {&frame, &rows, &work, &list_cur, &n_cur, &cursor, &pixel_stats, &totals};
+		void *shade_args[] = {&frame, &rows, &work, &list_cur, &n_cur, &list_next, &n_next, &r, &out, &format, &pixel_stats, &totals};
+		if (march_events) (void)hipEventRecord(march_events[2 * r], stream);
+		(void)hipLaunchKernel(sk->march[dbg], dim3(march_blocks), dim3(SDFR_BLOCK), march_args, 0, stream);
+		if (march_events) (void)hipEventRecord(march_events[2 * r + 1], stream);
+		if (shade_events) (void)hipEventRecord(shade_events[2 * r], stream);
+		(void)hipLaunchKernel(sk->shade[dbg], dim3(shade_blocks), dim3(SDFR_BLOCK), shade_args, 0, stream);
+		if (shade_events) (void)hipEventRecord(shade_events[2 * r + 1], stream);
+		uint32_t *t = list_cur;
+		list_cur = list_next;
+		list_next = t;
 	}
+	if (n_rounds_out) *n_rounds_out = rounds;
+	return hipGetLastError();
 }
 
+// ---- queries (kernel bodies: sdfr_query_kernel.h) ----
 hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
-	switch (scene)
-	{
-#define SDFR_CALL_SCENE(I, S) case I: return launch_query_scene##I(U, q, stream);
-		SDFR_FOR_EACH_SCENE(SDFR_CALL_SCENE)
-#undef SDFR_CALL_SCENE
-	default: return hipErrorInvalidValue; // not a scene of the registry
-	}
+	const SceneQueryKernels *qk = scene_query_kernels(scene);
+	if (!qk) return hipErrorInvalidValue;
+	const int dbg = frame_needs_debug(U) ? 1 : 0;
+	const uint32_t blocks = ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK;
+	QueryKernelArgs a;
+	a.U = U;
+	a.q = q;
+	void *args[] = {&a};
+	(void)hipLaunchKernel(q.kind == QUERY_POINTS ? qk->points[dbg] : qk->rays[dbg], dim3(blocks), dim3(SDFR_PIXEL_BLOCK), args, 0, stream);
+	return hipGetLastError();
 }
 
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,

@@ -1,11 +1,9 @@
 // sdfr_kernels_scene.hip -- the per-scene kernels of the renderer (k_pixel, k_march, k_shade; see
-// sdfr_kernels.hip for the two schedules), instantiated for ONE scene.  The build compiles this file
+// sdfr_kernels.hip for the two schedules and everything that launches them), instantiated for ONE scene.  The build compiles this file
 // once per scene of the registry (sdfr_perpixel.h) with -DSDFR_SCENE=<index> (sdf_playground_amd/buildlib.py),
 // in parallel: 23 scenes x 2 debug variants x 3 kernels in one translation unit took a minute to compile,
 // nothing in one scene's kernels depends on another's, and a scene can be built with options of its own
 // (buildlib.SCENE_FLAGS).
-#include <cstdlib>
-
 #include "sdfr_kernels.h"
 #include "sdfr_perpixel.h"
 #include "sdfr_pixel_kernel.h"
@@ -16,12 +14,8 @@
 
 namespace sdfr {
 
-// refill a march wave once this many lanes are idle (or when all are)
+// refill a march wave once this many lanes are idle (or when all are); a wave claims SDFR_GRAB list entries per atomic (sdfr_kernels.h)
 #define SDFR_REFILL_THRESHOLD 16
-// list entries a march wave claims per atomic
-#define SDFR_GRAB 128
-
-static uint32_t work_items(const FrameU &U, const RowMap &rm) { return launch_work_items(U.width, rm); }
 
 // =================================================================================================
 // PIXEL schedule (body: sdfr_pixel_kernel.h)
@@ -38,9 +32,6 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_pixel(PixelKernelArgs args)
 // =================================================================================================
 // march result fields
 enum { RS_STATUS = 0, RS_T, RS_D, RS_NX, RS_NY, RS_NZ, RS_SAMPLE_DIST, RS_COUNT };
-// counters[]: [r] = size of round r's list (r = 0..16); [32 + r] = march cursor of round r
-enum { CNT_ROUND0 = 0 };
-
 
 // ---- k_march ----------------------------------------------------------------------------------------
 enum { LANE_IDLE = 0, LANE_MARCH = 1, LANE_GRAD0 = 2, LANE_GRAD1 = 3, LANE_GRAD2 = 4 };
@@ -296,129 +287,29 @@ __global__ __launch_bounds__(SDFR_BLOCK) void k_shade(FrameU U, RowMap rm, Wavef
 }
 
 // =================================================================================================
-// launchers of this unit's scene
+// what this unit exports: the scene's kernels and launch traits, under a name made of the scene's index (scene_kernels, sdfr_kernels.hip)
 // =================================================================================================
-template <class Scene, bool DBG>
-static hipError_t run_pixel(const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
-	const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode, int scene_index)
-{
-	const uint32_t n_work = work_items(U, rm);
-	if ((size_t)n_work > ws.capacity) return hipErrorInvalidValue;
-	// a persistent launch: as many blocks as stay resident, each pulling tiles until none is left
-	// (TileQueue, sdfr_pixel_kernel.h).  The occupancy query may over-state by a block per CU for
-	// SGPR-heavy kernels (MI355X_MICROARCH.md); a surplus block simply starts when another has ended.
-	static int blocks_per_cu = 0; // per instantiation
-	if (blocks_per_cu == 0)
-	{
-		int n = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_pixel<Scene, DBG>, SDFR_PIXEL_BLOCK, 0) != hipSuccess || n < 1) n = 1;
-		blocks_per_cu = n;
-	}
-	int device = 0;
-	(void)hipGetDevice(&device);
-	const uint32_t tiles_blocks = (n_work + SDFR_PIXEL_BLOCK - 1) / SDFR_PIXEL_BLOCK;
-	const PixelLaunchMode mode = pixel_launch_mode(launch_mode, PersistentTiles<Scene>::value, RetireAfter<Scene>::value);
-	uint32_t per_cu = (uint32_t)blocks_per_cu;
-	if (mode.blocks_per_cu > 0 && (uint32_t)mode.blocks_per_cu < per_cu) per_cu = (uint32_t)mode.blocks_per_cu;
-	RowMap rows = rm;
-	uint32_t hand_out_items = n_work;
-	static const bool squares_off = [] { const char *e = getenv("SDFR_PIXEL_SQUARE_UNITS"); return e && atoi(e) == 0; }(); // developer knob: tile rows for every scene
-	if (mode.persistent && SquareUnits<Scene>::value && !squares_off)
-	{
-		// full frames are handed out in squares of tiles, dearest square first (RowMap::unit_log2); the squares cover the frame with a margin
-		row_map_units(rows, SDFR_ROW_FEEDBACK_MAX);
-		if (rows.unit_log2) hand_out_items = (rows.units << (2u * rows.unit_log2)) * 64u;
-	}
-	if ((size_t)hand_out_items > ws.capacity) return hipErrorInvalidValue; // one counter record per block, at most one block per tile handed out
-	const uint32_t blocks = pixel_launch_blocks(mode, (hand_out_items + SDFR_PIXEL_BLOCK - 1) / SDFR_PIXEL_BLOCK, (uint32_t)device_cu_count(device) * per_cu);
-	rows.retire_after = mode.persistent ? (uint32_t)mode.retire_after : 0u;
-	const uint32_t tiles_x = ((uint32_t)U.width + (1u << rm.tile_w_log2) - 1u) >> rm.tile_w_log2;
-	const uint32_t feedback_rows = !mode.persistent ? 0u : rows.unit_log2 ? rows.units : tiles_blocks / tiles_x;
-	rows.feedback_key = mode.persistent ? pixel_feedback_key((uint32_t)scene_index * 2u + (DBG ? 1u : 0u), U.width, rows, feedback_rows) : 0u;
-	PixelKernelArgs args;
-	args.U = U;
-	args.rm = rows;
-	args.n_work = hand_out_items;
-	args.format = format;
-	args.out = out;
-	args.pixel_stats = pixel_stats;
-	args.partials = ws.partials;
-	args.totals = totals;
-	args.ray_queue = ws.ray_queue;
-	args.cap = ws.capacity;
-	args.tile_cursors = mode.persistent ? ws.tile_cursors : (uint32_t *)nullptr;
-	hipLaunchKernelGGL((k_pixel<Scene, DBG>), dim3(blocks), dim3(SDFR_PIXEL_BLOCK), 0, stream, args);
-	// (the fold leaves frames with many rays per pixel in image order, SDFR_ROW_FEEDBACK_MAX_RAYS: a rule about tile ROWS -- their queue records
-	// are contiguous in image order --, not about squares, which scatter them either way)
-	return launch_reduce_totals(ws.partials, blocks, totals, stream, ws.tile_cursors, feedback_rows,
-		rows.unit_log2 ? ~0ull >> 8 : (unsigned long long)n_work, rows.feedback_key);
-}
-
-template <class Scene, bool DBG>
-static hipError_t run_wavefront(const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
-	const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events, int *n_rounds_out)
-{
-	const uint32_t n_work = work_items(U, rm);
-	if ((size_t)n_work > ws.capacity) return hipErrorInvalidValue; // lists are indexed by work item, state by pixel id < n_work
-	const uint32_t init_blocks = (n_work + SDFR_BLOCK - 1) / SDFR_BLOCK;
-	(void)launch_wavefront_init(U, rm, n_work, ws, pixel_stats, stream);
-
-	int device = 0;
-	(void)hipGetDevice(&device);
-	const int cus = device_cu_count(device);
-	int march_blocks_per_cu = 0, shade_blocks_per_cu = 0;
-	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&march_blocks_per_cu, k_march<Scene, DBG>, SDFR_BLOCK, 0);
-	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&shade_blocks_per_cu, k_shade<Scene, DBG>, SDFR_BLOCK, 0);
-	if (march_blocks_per_cu < 1) march_blocks_per_cu = 1;
-	if (shade_blocks_per_cu < 1) shade_blocks_per_cu = 1;
-	// persistent grids: what the occupancy query calls resident (it may over-state by a block
-	// per CU for SGPR-heavy kernels; harmless here because work is claimed dynamically), but
-	// never more waves than there are ranges to claim
-	const uint32_t grabs = (n_work + SDFR_GRAB - 1u) / SDFR_GRAB;
-	uint32_t march_blocks = (uint32_t)(cus * march_blocks_per_cu);
-	if (march_blocks > (grabs + 3u) / 4u) march_blocks = (grabs + 3u) / 4u;
-	if (march_blocks < 1) march_blocks = 1;
-	uint32_t shade_blocks = (uint32_t)(cus * shade_blocks_per_cu);
-	if (shade_blocks > init_blocks) shade_blocks = init_blocks;
-	if (shade_blocks < 1) shade_blocks = 1;
-
-	uint32_t *list_cur = ws.list_a, *list_next = ws.list_b;
-	const int rounds = U.bounce_count;
-	for (int r = 0; r < rounds; ++r)
-	{
-		if (march_events) (void)hipEventRecord(march_events[2 * r], stream);
-		hipLaunchKernelGGL((k_march<Scene, DBG>), dim3(march_blocks), dim3(SDFR_BLOCK), 0, stream, U, rm, ws, list_cur, ws.counters + r,
-			ws.counters + 32 + r, pixel_stats, totals);
-		if (march_events) (void)hipEventRecord(march_events[2 * r + 1], stream);
-		if (shade_events) (void)hipEventRecord(shade_events[2 * r], stream);
-		hipLaunchKernelGGL((k_shade<Scene, DBG>), dim3(shade_blocks), dim3(SDFR_BLOCK), 0, stream, U, rm, ws, list_cur, ws.counters + r, list_next,
-			ws.counters + r + 1, r, out, format, pixel_stats, totals);
-		if (shade_events) (void)hipEventRecord(shade_events[2 * r + 1], stream);
-		uint32_t *t = list_cur;
-		list_cur = list_next;
-		list_next = t;
-	}
-	if (n_rounds_out) *n_rounds_out = rounds;
-	return hipGetLastError();
-}
-
-// the entry points sdfr_kernels.hip dispatches to, named by the scene's index
-#define SDFR_CAT2(a, b) a##b
-#define SDFR_CAT(a, b) SDFR_CAT2(a, b)
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
-hipError_t SDFR_CAT(launch_pixel_scene, SDFR_SCENE)(const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats, RenderTotals *totals,
-	const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
+const SceneKernels *SDFR_CAT(scene_kernels_, SDFR_SCENE)()
 {
-	return frame_needs_debug(U) ? run_pixel<UnitScene, true>(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, SDFR_SCENE)
-								: run_pixel<UnitScene, false>(U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode, SDFR_SCENE);
-}
-
-hipError_t SDFR_CAT(launch_wavefront_scene, SDFR_SCENE)(const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
-	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events, int *n_rounds_out)
-{
-	return frame_needs_debug(U) ? run_wavefront<UnitScene, true>(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out)
-								: run_wavefront<UnitScene, false>(U, rows, out, format, pixel_stats, totals, ws, stream, march_events, shade_events, n_rounds_out);
+	// (named in the order pixel, march, shade with the debug variant first: a unit's code object holds its kernels in the order they are
+	// first named in, and this keeps the order, and with it every byte of the object's code, that the launchers which lived here gave it)
+	static const SceneKernels k = [] {
+		SceneKernels k;
+		k.pixel[1] = (const void *)k_pixel<UnitScene, true>;
+		k.pixel[0] = (const void *)k_pixel<UnitScene, false>;
+		k.march[1] = (const void *)k_march<UnitScene, true>;
+		k.shade[1] = (const void *)k_shade<UnitScene, true>;
+		k.march[0] = (const void *)k_march<UnitScene, false>;
+		k.shade[0] = (const void *)k_shade<UnitScene, false>;
+		k.persistent_tiles = PersistentTiles<UnitScene>::value;
+		k.square_units = SquareUnits<UnitScene>::value;
+		k.retire_after = RetireAfter<UnitScene>::value;
+		k.tile_w_log2 = SceneTileShape<UnitScene>::value;
+		return k;
+	}();
+	return &k;
 }
 
 } // namespace sdfr

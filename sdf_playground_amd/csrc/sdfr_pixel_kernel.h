@@ -2,7 +2,7 @@
 // reference's bounce loop start to finish (sdfr_render_pixel.h), waves cover 8x8 pixel tiles,
 // pending rays wait in an HBM queue behind a one-entry register cache.
 //
-// Shared by the kernels compiled ahead of time (sdfr_kernels.hip) and by the translation unit
+// Shared by the kernels compiled ahead of time (sdfr_kernels_scene.hip) and by the translation unit
 // sdfr_jit.cpp builds around a scene compiled at run time (hiprtc), so both run the very same
 // code.  Device compilation only.
 #pragma once
@@ -365,10 +365,8 @@ struct LdsCachedRayStore
 // resemble each other row by row (sky, horizon, floor) even when the camera turns.  State lives behind the tile cursors:
 // [META] key of the launch the order was made by (RowMap::feedback_key: scene, frame size, row selection, tile shape; anything
 // else, e.g. 0 before the first frame or after a frame with many rays per pixel: hand out top to bottom),
-// [COST ...] this frame's cost per row, [ORDER ...] the permutation.  Persistent launches of up to 512 tile rows.
-#ifndef SDFR_ROW_FEEDBACK_MAX
-#define SDFR_ROW_FEEDBACK_MAX 512u
-#endif
+// [COST ...] this frame's cost per row, [ORDER ...] the permutation.  Persistent launches of up to 512 tile rows
+// (SDFR_ROW_FEEDBACK_MAX, sdfr_frame.h).
 #define SDFR_ROW_META (SDFR_TILE_CURSORS * SDFR_TILE_CURSOR_STRIDE)
 #define SDFR_ROW_COST (SDFR_ROW_META + 32u)
 #define SDFR_ROW_ORDER (SDFR_ROW_COST + SDFR_ROW_FEEDBACK_MAX)
@@ -595,7 +593,7 @@ __device__ __forceinline__ void pixel_kernel(const PixelKernelArgs &args_by_valu
 		trace_mark = __builtin_amdgcn_s_memrealtime();
 #endif
 		tiles.tile_took(age.ticks_since_start());
-		// make room for a younger wave (pixel_launch_blocks, sdfr_kernels.h) -- but never with claimed tiles in hand
+		// make room for a younger wave (pixel_launch_blocks, sdfr_launch_plan.h) -- but never with claimed tiles in hand
 		if (rm.retire_after && ++tiles_done >= rm.retire_after && !tiles.holds_claimed_tiles()) break;
 #ifdef SDFR_WAVE_TRACE
 		trace_tiles++;

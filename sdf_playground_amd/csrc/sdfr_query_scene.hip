@@ -31,27 +31,21 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_rays(QueryKernelArgs a)
 	query_rays_kernel<Scene, DBG>(a);
 }
 
-template <class Scene, bool DBG>
-static hipError_t run_query(const FrameU &U, const QueryArgs &q, hipStream_t stream)
-{
-	const uint32_t blocks = ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK;
-	QueryKernelArgs a;
-	a.U = U;
-	a.q = q;
-	if (q.kind == QUERY_POINTS)
-		hipLaunchKernelGGL((k_query_points<Scene, DBG>), dim3(blocks), dim3(SDFR_PIXEL_BLOCK), 0, stream, a);
-	else
-		hipLaunchKernelGGL((k_query_rays<Scene, DBG>), dim3(blocks), dim3(SDFR_PIXEL_BLOCK), 0, stream, a);
-	return hipGetLastError();
-}
-
-#define SDFR_CAT2(a, b) a##b
-#define SDFR_CAT(a, b) SDFR_CAT2(a, b)
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
-hipError_t SDFR_CAT(launch_query_scene, SDFR_SCENE)(const FrameU &U, const QueryArgs &q, hipStream_t stream)
+// what this unit exports (scene_query_kernels, launch_query: sdfr_kernels.hip)
+const SceneQueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
 {
-	return frame_needs_debug(U) ? run_query<UnitScene, true>(U, q, stream) : run_query<UnitScene, false>(U, q, stream);
+	// (the debug variants first: the order the kernels are first named in is their order in the unit's code object, kept as it was)
+	static const SceneQueryKernels k = [] {
+		SceneQueryKernels k;
+		k.points[1] = (const void *)k_query_points<UnitScene, true>;
+		k.rays[1] = (const void *)k_query_rays<UnitScene, true>;
+		k.points[0] = (const void *)k_query_points<UnitScene, false>;
+		k.rays[0] = (const void *)k_query_rays<UnitScene, false>;
+		return k;
+	}();
+	return &k;
 }
 
 } // namespace sdfr

@@ -104,7 +104,7 @@ template <class Scene>
 struct SceneTileShape<Scene, typename VoidOf<decltype(Scene::tile_w_log2)>::type> { static constexpr int value = Scene::tile_w_log2; };
 
 // tiles a wave of the scene's persistent launch renders before it makes room for a younger one (pixel_launch_blocks,
-// sdfr_kernels.h); a scene may say `static constexpr int retire_after = n;` (0 = never)
+// sdfr_launch_plan.h); a scene may say `static constexpr int retire_after = n;` (0 = never)
 template <class Scene, class = void>
 struct RetireAfter { static constexpr int value = 8; };
 template <class Scene>
