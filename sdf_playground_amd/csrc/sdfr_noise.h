@@ -20,6 +20,83 @@ SDF_HD float pcg_hashf(uint32_t v) { return (float)pcg_hash(v) / (float)0xFFFFFF
 SDF_HD float noise_mod289(float x) { return x - floor1(x * 0.00346020761245674740484429065744f) * 289.0f; }
 SDF_HD float noise_permute(float x) { return noise_mod289(x * x * 34.0f + x); }
 
+// How snoise3 hashes a lattice point: the hash H of its gradient source (NG::Hash).  NoiseHashPlain is the definition, the text of
+// noise.hlsl operation by operation; NoiseHashExact computes the same bits with fewer instructions where its precondition holds.
+struct NoiseHashPlain
+{
+	// hashed gradient index of each of the four corners of the cell i (i1, i2: the offsets of the middle corners, components
+	// 0 or 1); the "+ 0" of corner 0 is the identity because mod289 never returns -0.  Nothing to check.
+	static SDF_HD vec4 corners(vec3 i, vec3 i1, vec3 i2, bool &)
+	{
+		i = V3(noise_mod289(i.x), noise_mod289(i.y), noise_mod289(i.z));
+		float p0 = noise_permute(noise_permute(noise_permute(i.z) + i.y) + i.x);
+		float p1 = noise_permute(noise_permute(noise_permute(i.z + i1.z) + i.y + i1.y) + i.x + i1.x);
+		float p2 = noise_permute(noise_permute(noise_permute(i.z + i2.z) + i.y + i2.y) + i.x + i2.x);
+		float p3 = noise_permute(noise_permute(noise_permute(i.z + 1.0f) + i.y + 1.0f) + i.x + 1.0f);
+		return V4(p0, p1, p2, p3);
+	}
+	// the gradient index j = p mod 49 of a corner
+	static SDF_HD float mod49(float p)
+	{
+		const float n_ = 0.142857142857f;
+		const float ns_z = n_ * 1.0f - 0.0f;
+		return p - 49.0f * floor1(p * ns_z * ns_z);
+	}
+};
+
+// The same hash with a*b + c written fma(a, b, c) wherever the product a*b is exact: the fma then rounds the same real number the
+// two plain operations round (the product adds no rounding of its own), once, and a correctly rounded result is unique -- zeros
+// included: an exactly zero sum of nonzero terms is +0 either way, and where the product is a zero the fma adds the same signed
+// zero the plain form adds (x - P is x + (-P); the fma's product is written -c * f, so it is -P).  One v_fmamk / v_fmac instead
+// of a multiplication and an addition, twice per permute and once per corner.
+//
+// Precondition: the reduced lattice coordinates r = mod289(i) are integers in [-1, 289]; `corners` clears `ok` unless they are,
+// once per snoise3, and a lane whose `ok` is cleared evaluates the noise again with NoiseHashPlain (snoise3, turbulence3), so the
+// bits are the definition's whatever the input.
+//   * What leaves mod289 is integer-valued or not finite: i = floor(.) is integer-valued or not finite, so is f = floor1(i * c),
+//     so is the rounded product f * 289 (a product of integers is an integer; below 2^24 it is exact, and every float from 2^23
+//     on is an integer), and so is the rounded difference of two integer-valued floats for the same reason.  The range test is
+//     therefore all the test there is; NaN (from i = +-inf: inf - inf) fails both comparisons.  -0 cannot arrive: i = -0 gives
+//     f = -0, f * 289 = -0 and -0 - -0 = +0, and any other zero difference is +0; it would pass the test and be harmless.
+//   * mod289(i) is one of -1 .. 289 for every integer |i| <= 2^24 (float rounding of i * c puts a few multiples of 289 on the
+//     wrong side of floor1: -1 and 289 beside 0 .. 288), hence for every input with |x| < 2^20 even in turbulence3's last octave:
+//     `ok` stays set there.  The reduction of the lattice coordinates itself stays plain: fused, it differs from the definition
+//     for |i| >= 2^24 (f * 289 no longer exact) with both results inside the range, so no test of r would catch it.
+//   * By induction every value of the chain is then an integer of [-1, 289] and every argument x of a permute, a sum of at most two
+//     of them and 0 or 1, an integer of [-2, 579].  x * x <= 335 241 is exact, 34 x^2 <= 11 398 194 < 2^24 is exact, so
+//     fma(x * x, 34, x) = 34 x^2 + x =: y exactly, as the two plain operations give it, 0 <= y <= 11 398 773 < 2^24.
+//     In mod289(y), f = floor1(y * c) is an integer 0 <= f <= 39 443, 289 f < 2^24 is exact, so fma(-289, f, y) is the plain
+//     y - f * 289.  That result lies in [-1, 289] again for each of the 582 arguments x: tests/test_noise_fused_cpu.py goes through
+//     them all (and through every x up to 702), which closes the induction.
+//   * j: f = floor1(p * ns_z * ns_z) is one of -1 .. 5 for p in [-1, 289], 49 f is exact.
+struct NoiseHashExact
+{
+	static SDF_HD bool reduced(float r) { return (r >= -1.0f) & (r <= 289.0f); }
+	static SDF_HD float mod289(float y) { return fma1(-289.0f, floor1(y * 0.00346020761245674740484429065744f), y); }
+	static SDF_HD float permute(float x) { return mod289(fma1(x * x, 34.0f, x)); }
+	// The innermost permute of the four corners is permute(i.z + {0, i1.z, i2.z, 1}) with i1.z, i2.z 0 or 1: two permutes and
+	// two selects instead of four permutes.  i.z + 0 is i.z (never -0, above) and i.z + 1 is what corner 3 adds -- the very
+	// arguments of the plain text, so this part needs no precondition.
+	static SDF_HD vec4 corners(vec3 i, vec3 i1, vec3 i2, bool &ok)
+	{
+		i = V3(noise_mod289(i.x), noise_mod289(i.y), noise_mod289(i.z));
+		ok = ok & reduced(i.x) & reduced(i.y) & reduced(i.z);
+		const float q0 = permute(i.z), q3 = permute(i.z + 1.0f);
+		const float q1 = i1.z != 0.0f ? q3 : q0, q2 = i2.z != 0.0f ? q3 : q0;
+		float p0 = permute(permute(q0 + i.y) + i.x);
+		float p1 = permute(permute(q1 + i.y + i1.y) + i.x + i1.x);
+		float p2 = permute(permute(q2 + i.y + i2.y) + i.x + i2.x);
+		float p3 = permute(permute(q3 + i.y + 1.0f) + i.x + 1.0f);
+		return V4(p0, p1, p2, p3);
+	}
+	static SDF_HD float mod49(float p)
+	{
+		const float n_ = 0.142857142857f;
+		const float ns_z = n_ * 1.0f - 0.0f;
+		return fma1(-49.0f, floor1(p * ns_z * ns_z), p);
+	}
+};
+
 // normalised gradient number j of snoise3 (the 7 x 7 points of a square folded onto an octahedron); j = p mod 49, computed
 // by the corner.  The only definition of these gradients: the table below is filled by this same function.
 SDF_HD vec3 simplex_grad(float j)
@@ -48,12 +125,14 @@ SDF_HD vec3 simplex_grad(float j)
 // allocator more than the formula it skips.
 struct NoiseGradFormula
 {
+	typedef NoiseHashPlain Hash;
 	static SDF_HD vec3 grad(float j, bool &) { return simplex_grad(j); }
 };
 #define SDFR_NOISE_GRADS 64
 template <class Tab>
 struct NoiseGradTable
 {
+	typedef NoiseHashExact Hash; // the fallback of the table is the fallback of the hash: one `ok`, one recomputation
 	static SDF_HD vec3 grad(float j, bool &ok)
 	{
 		// the clamp keeps the conversion defined (NaN -> the last entry) and the index inside the table whatever j is; clamped
@@ -79,9 +158,7 @@ SDF_HD vec3 noise_recompute_input(vec3 v)
 template <class NG>
 SDF_HD vec2 simplex_corner(float p, vec3 xc, bool &ok)
 {
-	const float n_ = 0.142857142857f;
-	const float ns_z = n_ * 1.0f - 0.0f;
-	float j = p - 49.0f * floor1(p * ns_z * ns_z);
+	float j = NG::Hash::mod49(p);
 	vec3 g = NG::grad(j, ok);
 	float m = max1(0.6f - dot(xc, xc), 0.0f);
 	m = m * m;
@@ -106,18 +183,12 @@ SDF_HD float snoise3_grads(vec3 v, bool &ok)
 	vec3 x2 = x0 - i2 + Cy;
 	vec3 x3 = x0 - 0.5f;
 
-	i = V3(noise_mod289(i.x), noise_mod289(i.y), noise_mod289(i.z));
-	// hashed gradient index of each corner; the "+ 0" of corner 0 is the identity because
-	// mod289 never returns -0
-	float p0 = noise_permute(noise_permute(noise_permute(i.z) + i.y) + i.x);
-	float p1 = noise_permute(noise_permute(noise_permute(i.z + i1.z) + i.y + i1.y) + i.x + i1.x);
-	float p2 = noise_permute(noise_permute(noise_permute(i.z + i2.z) + i.y + i2.y) + i.x + i2.x);
-	float p3 = noise_permute(noise_permute(noise_permute(i.z + 1.0f) + i.y + 1.0f) + i.x + 1.0f);
+	const vec4 p = NG::Hash::corners(i, i1, i2, ok);
 
-	vec2 c0 = simplex_corner<NG>(p0, x0, ok);
-	vec2 c1 = simplex_corner<NG>(p1, x1, ok);
-	vec2 c2 = simplex_corner<NG>(p2, x2, ok);
-	vec2 c3 = simplex_corner<NG>(p3, x3, ok);
+	vec2 c0 = simplex_corner<NG>(p.x, x0, ok);
+	vec2 c1 = simplex_corner<NG>(p.y, x1, ok);
+	vec2 c2 = simplex_corner<NG>(p.z, x2, ok);
+	vec2 c3 = simplex_corner<NG>(p.w, x3, ok);
 	return 42.0f * dot(V4(c0.x, c1.x, c2.x, c3.x), V4(c0.y, c1.y, c2.y, c3.y));
 }
 

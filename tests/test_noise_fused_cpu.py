@@ -1,0 +1,210 @@
+"""CPU tier: the fused hash of the table path of snoise3 / turbulence3 (NoiseHashExact, sdf_playground_amd/csrc/sdfr_noise.h).
+
+The pixel kernel of a scene that reads its simplex gradients from the LDS table (the labyrinth) also hashes its lattice points
+with fma(x * x, 34, x), fma(-289, floor(.), y) and fma(-49, floor(.), p) where the plain text multiplies and then adds, and shares
+the innermost permute of the four corners.  The proof beside the code says the bits are the plain text's whenever the reduced
+lattice coordinates are integers of [-1, 289], that a lane where they are not evaluates the noise once more with the plain text,
+and that this never happens for |x| < 2^20.  Checked here with a host build of the product's headers
+(tests/cpp/noise_fused_host.cpp, compiled the way tests/hostsim builds them), against the oracle's literal restatement of the
+shader (oracle/noise.h), which stays plain IEEE.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
+SRC = os.path.join(ROOT, "tests", "cpp", "noise_fused_host.cpp")
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("noise_fused") / "libnoise_fused.so")
+    # the options of tests/hostsim: no contraction, as the kernels are built (-ffp-contract=off)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
+                    "-I" + CSRC, "-shared", "-o", so, SRC], check=True)
+    L = ctypes.CDLL(so)
+    L.nf_noise.restype = ctypes.c_longlong
+    L.nf_lattice_range.restype = ctypes.c_longlong
+    L.nf_fused_lattice_would_differ.restype = ctypes.c_longlong
+    L.nf_corners.restype = ctypes.c_longlong
+    L.nf_fill()
+    return L
+
+
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def product(lib, what, pts):
+    """(formula with the plain hash, table with the fused hash, per point: the table path fell back) of snoise3 (0) / turbulence3 (1)"""
+    pts = np.ascontiguousarray(pts, np.float32)
+    out = np.zeros((len(pts), 2), np.float32)
+    fell = np.zeros(len(pts), np.uint8)
+    n = lib.nf_noise(what, _ptr(pts), _ptr(out), _ptr(fell), ctypes.c_longlong(len(pts)))
+    assert n == int(fell.sum())
+    return out[:, 0], out[:, 1], fell.astype(bool)
+
+
+def oracle_snoise3(pts):
+    pts = np.ascontiguousarray(pts, np.float32)
+    out = np.zeros(len(pts), np.float32)
+    po.lib().orc_noise(3, _ptr(pts), _ptr(out), ctypes.c_longlong(len(pts)))
+    return out
+
+
+def oracle_turbulence3(pts):
+    """oracle/noise.h turbulence(): (n(p) + n(2p) / 2 + n(4p) / 4 + n(8p) / 8) * 8 / 15, every operation a plain IEEE float32 one"""
+    f = np.float32
+    pts = np.ascontiguousarray(pts, np.float32)
+    with np.errstate(all="ignore"):
+        n1, n2, n4, n8 = (oracle_snoise3(pts * f(s)) for s in (1.0, 2.0, 4.0, 8.0))
+        return (((n1 + n2 / f(2.0)) + n4 / f(4.0)) + n8 / f(8.0)) * f(8.0) / f(15.0)
+
+
+def _same(a, b):
+    """bit for bit; a NaN is a NaN (the payload of a NaN is not part of the contract: nothing reads it)"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return (_bits(a) == _bits(b)) | (np.isnan(a) & np.isnan(b))
+
+
+def _existing_points():
+    """the 240 000 points of tests/test_noise_cpu.py in three dimensions, and its lattice-aligned grid (ties in the ranking)"""
+    parts = []
+    for seed, scale in ((1, 3.0), (2, 40.0), (3, 700.0), (4, 0.05)):
+        rng = np.random.default_rng(seed)
+        parts.append(((rng.random((60000, 3)) * 2 - 1) * scale).astype(np.float32))
+    grid = np.stack(np.meshgrid(*[np.arange(-3, 4) * 0.5] * 3, indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+    return np.concatenate(parts), grid
+
+
+@pytest.mark.parametrize("what,oracle", [(0, oracle_snoise3), (1, oracle_turbulence3)])
+def test_fused_table_path_equals_the_oracle_on_the_points_of_the_noise_test(lib, what, oracle):
+    pts, grid = _existing_points()
+    assert len(pts) == 240000
+    for p in (pts, grid):
+        formula, fused, fell = product(lib, what, p)
+        ref = oracle(p)
+        assert np.array_equal(_bits(fused), _bits(ref)), (what, int((_bits(fused) != _bits(ref)).sum()))
+        assert np.array_equal(_bits(formula), _bits(ref))
+        assert not fell.any()
+
+
+def test_fused_permute_equals_the_plain_one_for_every_integer_argument(lib):
+    lo, hi = -2, 702
+    out = np.zeros((hi - lo + 1, 6), np.float32)
+    lib.nf_permutes(lo, hi, _ptr(out))
+    x = np.arange(lo, hi + 1)
+    # permute, and the corner's j of it
+    assert np.array_equal(_bits(out[:, 0]), _bits(out[:, 1]))
+    assert np.array_equal(_bits(out[:, 2]), _bits(out[:, 3]))
+    # mod289 alone, on the same small integers
+    assert np.array_equal(_bits(out[:, 4]), _bits(out[:, 5]))
+    # the induction of the proof: the arguments a chain can form are the integers of [-2, 579], and a permute of one of them is an
+    # integer of [-1, 289] again, never -0 (in fact of 0 .. 288: float rounding misplaces none of these 582)
+    chain = (x >= -2) & (x <= 579)
+    p = out[chain, 0]
+    assert (p == np.floor(p)).all() and p.min() >= -1.0 and p.max() <= 289.0 and not np.signbit(p).any()
+    assert np.array_equal(p.astype(np.int64), (34 * x[chain] ** 2 + x[chain]) % 289)
+    j = out[chain, 2]
+    assert (j == np.floor(j)).all() and j.min() >= 0.0 and j.max() <= 48.0 and not np.signbit(j).any()
+    # 34 x^2 + x stays below 2^24 on that range: the bound the exactness of every product rests on
+    assert int((34 * x[chain] ** 2 + x[chain]).max()) == 11398773 < 2 ** 24
+
+
+def test_reduced_lattice_coordinates_of_everything_below_2_to_24_pass_the_range_test(lib):
+    lo, hi = ctypes.c_float(), ctypes.c_float()
+    refused = lib.nf_lattice_range(1 << 24, ctypes.byref(lo), ctypes.byref(hi))
+    assert refused == 0
+    assert -1.0 <= lo.value and hi.value <= 289.0, (lo.value, hi.value)
+
+
+def test_whole_hash_fused_equals_plain_wherever_the_range_test_passes(lib):
+    rng = np.random.default_rng(8)
+    cells = np.concatenate([
+        rng.integers(-600, 600, (100000, 3)).astype(np.float32),
+        rng.integers(-(1 << 24), 1 << 24, (100000, 3)).astype(np.float32),
+        # beyond 2^24: the plain reduction is no longer x mod 289, but whatever integer of the range it gives, the chain is exact
+        np.floor(np.sign(rng.standard_normal((100000, 3))) * 2.0 ** rng.uniform(24.0, 40.0, (100000, 3))).astype(np.float32),
+        np.float32([[0, 0, 0], [-0.0, -0.0, -0.0], [288, 288, 288], [289, 289, 289], [-1, -1, -1], [2 ** 24, -(2 ** 24), 2 ** 24 - 1]]),
+    ])
+    cells = np.ascontiguousarray(cells, np.float32)
+    kept = ctypes.c_longlong()
+    bad = lib.nf_corners(_ptr(cells), ctypes.c_longlong(len(cells)), ctypes.byref(kept))
+    assert bad == 0
+    # the first two blocks and the special cells pass the test whole; most of the third does too
+    assert kept.value >= 6 * 200006
+
+
+def test_the_lattice_reduction_has_to_stay_plain(lib):
+    """mod289 of the lattice coordinates is NOT fused, and this is why: from 2^24 on f * 289 is no longer exact, the fused and the
+    plain reduction differ, and both results look like reduced coordinates -- no test of the result would send the lane back."""
+    rng = np.random.default_rng(9)
+    big = np.floor(2.0 ** rng.uniform(25.0, 30.0, 200000)).astype(np.float32)
+    first = ctypes.c_float()
+    assert lib.nf_fused_lattice_would_differ(_ptr(big), ctypes.c_longlong(len(big)), ctypes.byref(first)) > 0
+    # while below 2^23 the two agree everywhere (f * 289 < 2^24)
+    small = np.arange(-(1 << 23), (1 << 23) + 1, 97, dtype=np.float32)
+    assert lib.nf_fused_lattice_would_differ(_ptr(small), ctypes.c_longlong(len(small)), ctypes.byref(first)) == 0
+
+
+def _fallback_points():
+    """inputs whose bits rest on the recomputation: |x| of 2^20, 2^24, 2^31, 1e30, infinity and NaN, in one, two and three components,
+    both signs, beside ordinary components"""
+    mags = [2.0 ** 20, 2.0 ** 24, 2.0 ** 31, 1e30, np.inf, np.nan]
+    rng = np.random.default_rng(10)
+    pts = []
+    for m in mags:
+        for s in (1.0, -1.0):
+            for mask in range(1, 8):
+                for _rep in range(8):
+                    v = rng.uniform(-50.0, 50.0, 3)
+                    for c in range(3):
+                        if mask >> c & 1:
+                            v[c] = s * m
+                    pts.append(v)
+                    pts.append(np.where([mask >> c & 1 for c in range(3)], s * m, 0.0))
+    return np.ascontiguousarray(np.float32(pts))
+
+
+@pytest.mark.parametrize("what,oracle", [(0, oracle_snoise3), (1, oracle_turbulence3)])
+def test_huge_and_non_finite_inputs_give_the_formula_s_bits(lib, what, oracle):
+    pts = _fallback_points()
+    formula, fused, fell = product(lib, what, pts)
+    assert _same(fused, formula).all(), pts[~_same(fused, formula)][:5]
+    assert np.array_equal(_bits(fused), _bits(formula))
+    assert _same(fused, oracle(pts)).all()
+    # non-finite inputs cannot pass the range test (NaN fails both comparisons): the recomputation is what gives these their bits.
+    # A huge finite input may well pass it -- the plain reduction of 1e30 is a small integer like any other, and from there on
+    # the chain is exact -- and then has the formula's bits without the recomputation.
+    assert fell[~np.isfinite(pts).all(axis=1)].all()
+    assert not fell[np.abs(pts).max(axis=1) < 2.0 ** 20].any()
+
+
+@pytest.mark.parametrize("what", [0, 1])
+def test_the_fallback_is_never_taken_below_2_to_20(lib, what):
+    rng = np.random.default_rng(11 + what)
+    top = np.nextafter(np.float32(2.0 ** 20), np.float32(0))
+    n = 300000
+    pts = np.concatenate([
+        rng.uniform(-700.0, 700.0, (n, 3)),
+        rng.uniform(-(2.0 ** 20), 2.0 ** 20, (n, 3)),
+        # all three components next to 2^20, equal signs: the skew and the last octave take the lattice coordinates to just
+        # under 2^24, the largest the claim covers
+        np.sign(rng.standard_normal((n // 4, 1))) * rng.uniform(2.0 ** 20 - 64.0, 2.0 ** 20, (n // 4, 3)),
+        np.float32([[top, top, top], [-top, -top, -top], [top, -top, top], [top, 0, 0]]),
+    ]).astype(np.float32)
+    pts = np.clip(pts, -top, top)
+    assert np.abs(pts).max() < 2.0 ** 20
+    formula, fused, fell = product(lib, what, pts)
+    assert not fell.any(), pts[fell][:5]
+    assert np.array_equal(_bits(fused), _bits(formula))
