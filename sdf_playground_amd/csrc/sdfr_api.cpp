@@ -124,17 +124,63 @@ static void release_lane(sdfr_renderer::Lane &l)
 	if (l.ev_end) (void)hipEventDestroy(l.ev_end);
 	l = sdfr_renderer::Lane();
 }
+// waits for every frame in flight: the current lane and, with two frames in flight, the other one
+static int sync_lanes(sdfr_renderer *r)
+{
+	SDFR_HIP(hipStreamSynchronize(r->lane.stream));
+	if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream));
+	return SDFR_OK;
+}
 // back to one frame in flight: the current lane keeps its workspace and runs on the caller's stream again
 static void release_second_lane(sdfr_renderer *r)
 {
 	if (r->frames_in_flight != 2) return;
-	(void)hipStreamSynchronize(r->lane.stream);
-	(void)hipStreamSynchronize(r->other.stream);
+	(void)sync_lanes(r);
 	(void)hipStreamDestroy(r->lane.stream);
 	(void)hipStreamDestroy(r->other.stream);
 	release_lane(r->other);
 	r->lane.stream = r->user_stream;
 	r->frames_in_flight = 1;
+}
+
+// the reference's camera (Camera.h) as the camera entries configure it; the caller aims it (SetLookat / SetDirection)
+static host::Camera make_camera(float fovy, float aspect, float roll, const host::Vec3 &eye)
+{
+	host::Camera cam;
+	cam.SetAspect(aspect);
+	cam.SetFOVY(fovy);
+	cam.SetRoll(roll);
+	cam.SetEye(eye);
+	return cam;
+}
+static int set_camera_from(sdfr_renderer *r, const host::Camera &cam)
+{
+	host::Vec3 e, f, rt, tp;
+	cam.GetBasis(e, f, rt, tp);
+	r->U.eye = V3(e.x, e.y, e.z);
+	r->U.front = V3(f.x, f.y, f.z);
+	r->U.right = V3(rt.x, rt.y, rt.z);
+	r->U.top = V3(tp.x, tp.y, tp.z);
+	return SDFR_OK;
+}
+
+// the limits of sdfr_limits and where the frame keeps them: copy(limit, frame's) for each, in either direction
+template <class Limits, class Frame, class Copy>
+static void for_each_limit(Limits &l, Frame &U, Copy copy)
+{
+	copy(l.iter_count, U.iter_count);
+	copy(l.bounce_count, U.bounce_count);
+	copy(l.ray_count, U.ray_count);
+	copy(l.light_count, U.light_count);
+	copy(l.range, U.range);
+	copy(l.max_cost_default, U.max_cost_default); // (unsigned in the frame)
+	copy(l.extension_lights, U.extension_lights);
+	copy(l.extension_marble_reflection, U.extension_marble_reflection);
+	copy(l.dist_eps, U.dist_eps);
+	copy(l.grad_eps, U.grad_eps);
+	copy(l.reflect_eps, U.reflect_eps);
+	copy(l.refract_eps, U.refract_eps);
+	copy(l.shadow_eps, U.shadow_eps);
 }
 
 extern "C" {
@@ -202,18 +248,9 @@ int sdfr_create(int device_ordinal, sdfr_renderer **out)
 		if (const char *t = getenv("SDFR_STEP_SHORTCUTS")) r->step_shortcuts = atoi(t) != 0; // default of sdfr_set_step_shortcuts
 		frame_defaults(r->U);
 		// start-up camera of the reference (Application.cpp:214-224), aspect of its 1200x800 window
-		host::Camera cam;
-		cam.SetAspect(1200.f / 800.f);
-		cam.SetFOVY(60.f * 3.14159265358979f / 180.f);
-		cam.SetRoll(0.f);
-		cam.SetEye(host::Vec3(0.f, 2.f, -3.f));
+		host::Camera cam = make_camera(60.f * 3.14159265358979f / 180.f, 1200.f / 800.f, 0.f, host::Vec3(0.f, 2.f, -3.f));
 		cam.SetLookat(host::Vec3(0.f, 1.f, 0.f));
-		host::Vec3 e, f, rt, tp;
-		cam.GetBasis(e, f, rt, tp);
-		r->U.eye = V3(e.x, e.y, e.z);
-		r->U.front = V3(f.x, f.y, f.z);
-		r->U.right = V3(rt.x, rt.y, rt.z);
-		r->U.top = V3(tp.x, tp.y, tp.z);
+		set_camera_from(r, cam);
 		if (create_lane(r->lane) != hipSuccess)
 		{
 			release_lane(r->lane);
@@ -241,11 +278,7 @@ void sdfr_destroy(sdfr_renderer *r)
 	release_second_lane(r); // waits for it, frees its workspace, counters, events and the two internal streams
 	release_lane(r->lane);
 	jit_unload(r->jit);
-	(void)hipFree(r->d_stage);
-	(void)hipFree(r->d_pstat);
-	(void)hipFree(r->d_query);
-	(void)hipFree(r->d_wire);
-	(void)hipFree(r->d_post_flags);
+	for (sdfr_device_buffer *b : {&r->stage, &r->pstat, &r->query, &r->wire, &r->post_flags}) b->release();
 	if (r->pinned_host) (void)hipHostUnregister(r->pinned_host);
 	if (r->comm_stream) (void)hipStreamDestroy(r->comm_stream);
 	if (r->ev_strips) (void)hipEventDestroy(r->ev_strips);
@@ -306,6 +339,53 @@ static int build_variable_table(sdfr_renderer *r, const std::string &scene_text,
 	return SDFR_OK;
 }
 
+// the last step of every load: the handle takes the scene (an index, or SDFR_SCENE_COUNT: r->jit) with its variable table and slots
+static int install_scene(sdfr_renderer *r, int scene, const host::ShaderVariableManager &vm, const std::vector<std::string> &slots)
+{
+	r->vars = vm;
+	r->scene_var_slots = slots;
+	r->scene = scene;
+	return SDFR_OK;
+}
+
+// Scenes compiled at run time, in the library's own form or (hlsl) in the reference's dialect (sdfr_hlsl.h / sdfr_hlsl.cpp).  The
+// variable table of a dialect scene comes from the tags of the ORIGINAL text (ShaderUtil.cpp:122-191); the class generated from it
+// (hlsl_scene_source) reads them through the same VAR_<name>(...) macros as any run-time scene.  Tags first: a text whose tags
+// are malformed is neither translated nor compiled.
+static int load_runtime_scene(sdfr_renderer *r, const char *name, const char *text, bool hlsl)
+{
+	SDFR_HIP(hipSetDevice(r->device));
+	host::ShaderVariableManager vm;
+	std::vector<std::string> slots;
+	int rc = build_variable_table(r, text, vm, slots);
+	if (rc != SDFR_OK) return rc;
+	JitScene js;
+	std::string err;
+	// like the reference, a scene that fails to compile leaves the previous one in place
+	// (SceneManager.cpp:118-127 keeps the old shader and shows the compiler's message)
+	if (!jit_compile(r->device, name, hlsl ? hlsl_scene_source(text) : std::string(text), slots, js, err)) return fail(r, SDFR_ERR_COMPILE, err);
+	rc = sync_lanes(r); // the frame before may still run the old module
+	if (rc != SDFR_OK) return rc;
+	jit_unload(r->jit);
+	r->jit = js;
+	return install_scene(r, SDFR_SCENE_COUNT, vm, slots);
+}
+static int check_runtime_scene(const char *text, bool hlsl, const char *arch, char *log, size_t log_bytes)
+{
+	if (log && log_bytes) log[0] = 0;
+	sdfr_renderer scratch; // only its error string is used
+	host::ShaderVariableManager vm;
+	std::vector<std::string> slots;
+	std::string err;
+	int rc = build_variable_table(&scratch, text, vm, slots);
+	if (rc != SDFR_OK) err = scratch.error;
+	std::vector<char> code;
+	if (rc == SDFR_OK && !jit_compile_code(arch && arch[0] ? arch : "gfx950", "scene", hlsl ? hlsl_scene_source(text) : std::string(text), slots, code, err))
+		rc = SDFR_ERR_COMPILE;
+	if (rc != SDFR_OK && log && log_bytes) snprintf(log, log_bytes, "%s", err.c_str());
+	return rc;
+}
+
 int sdfr_load_scene(sdfr_renderer *r, const char *name)
 {
 	return guarded(r, [&]() -> int {
@@ -316,32 +396,15 @@ int sdfr_load_scene(sdfr_renderer *r, const char *name)
 		std::vector<std::string> slots;
 		const int rc = build_variable_table(r, scene_variables(idx), vm, slots);
 		if (rc != SDFR_OK) return rc;
-		r->vars = vm;
-		r->scene_var_slots = slots;
-		r->scene = idx;
-		return SDFR_OK;
+		return install_scene(r, idx, vm, slots);
 	});
 }
 
 int sdfr_check_scene_source(const char *source, const char *arch, char *log, size_t log_bytes)
 {
-	return guarded(nullptr, [&]() -> int {
-		if (!source) return SDFR_ERR_INVALID_ARGUMENT;
-		if (log && log_bytes) log[0] = 0;
-		sdfr_renderer scratch; // only its error string is used
-		host::ShaderVariableManager vm;
-		std::vector<std::string> slots;
-		std::string err;
-		int rc = build_variable_table(&scratch, source, vm, slots);
-		if (rc != SDFR_OK) err = scratch.error;
-		std::vector<char> code;
-		if (rc == SDFR_OK && !jit_compile_code(arch && arch[0] ? arch : "gfx950", "scene", source, slots, code, err)) rc = SDFR_ERR_COMPILE;
-		if (rc != SDFR_OK && log && log_bytes) snprintf(log, log_bytes, "%s", err.c_str());
-		return rc;
-	});
+	return guarded(nullptr, [&]() -> int { return source ? check_runtime_scene(source, false, arch, log, log_bytes) : SDFR_ERR_INVALID_ARGUMENT; });
 }
 
-// ---- scenes in the reference's own dialect (sdfr_hlsl.h / sdfr_hlsl.cpp) ------------------------------------
 int sdfr_translate_scene_hlsl(const char *hlsl_source, char *out, size_t out_bytes)
 {
 	return guarded(nullptr, [&]() -> int {
@@ -354,70 +417,17 @@ int sdfr_translate_scene_hlsl(const char *hlsl_source, char *out, size_t out_byt
 
 int sdfr_check_scene_hlsl(const char *hlsl_source, const char *arch, char *log, size_t log_bytes)
 {
-	return guarded(nullptr, [&]() -> int {
-		if (!hlsl_source) return SDFR_ERR_INVALID_ARGUMENT;
-		// the variable table comes from the tags of the ORIGINAL text (ShaderUtil.cpp:122-191); the generated class reads them
-		// through the same VAR_<name>(...) macros as any run-time scene
-		if (log && log_bytes) log[0] = 0;
-		sdfr_renderer scratch;
-		host::ShaderVariableManager vm;
-		std::vector<std::string> slots;
-		std::string err;
-		int rc = build_variable_table(&scratch, hlsl_source, vm, slots);
-		if (rc != SDFR_OK) err = scratch.error;
-		std::vector<char> code;
-		if (rc == SDFR_OK && !jit_compile_code(arch && arch[0] ? arch : "gfx950", "scene", hlsl_scene_source(hlsl_source), slots, code, err)) rc = SDFR_ERR_COMPILE;
-		if (rc != SDFR_OK && log && log_bytes) snprintf(log, log_bytes, "%s", err.c_str());
-		return rc;
-	});
+	return guarded(nullptr, [&]() -> int { return hlsl_source ? check_runtime_scene(hlsl_source, true, arch, log, log_bytes) : SDFR_ERR_INVALID_ARGUMENT; });
 }
 
 int sdfr_load_scene_hlsl(sdfr_renderer *r, const char *name, const char *hlsl_source)
 {
-	return guarded(r, [&]() -> int {
-		if (!r || !name || !hlsl_source) return SDFR_ERR_INVALID_ARGUMENT;
-		SDFR_HIP(hipSetDevice(r->device));
-		host::ShaderVariableManager vm;
-		std::vector<std::string> slots;
-		const int rc = build_variable_table(r, hlsl_source, vm, slots);
-		if (rc != SDFR_OK) return rc;
-		JitScene js;
-		std::string err;
-		if (!jit_compile(r->device, name, hlsl_scene_source(hlsl_source), slots, js, err)) return fail(r, SDFR_ERR_COMPILE, err);
-		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
-		if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream)); // the frame before may still run the old module
-		jit_unload(r->jit);
-		r->jit = js;
-		r->vars = vm;
-		r->scene_var_slots = slots;
-		r->scene = SDFR_SCENE_COUNT;
-		return SDFR_OK;
-	});
+	return guarded(r, [&]() -> int { return r && name && hlsl_source ? load_runtime_scene(r, name, hlsl_source, true) : SDFR_ERR_INVALID_ARGUMENT; });
 }
 
 int sdfr_load_scene_source(sdfr_renderer *r, const char *name, const char *source)
 {
-	return guarded(r, [&]() -> int {
-		if (!r || !name || !source) return SDFR_ERR_INVALID_ARGUMENT;
-		SDFR_HIP(hipSetDevice(r->device));
-		host::ShaderVariableManager vm;
-		std::vector<std::string> slots;
-		const int rc = build_variable_table(r, source, vm, slots);
-		if (rc != SDFR_OK) return rc;
-		JitScene js;
-		std::string err;
-		// like the reference, a scene that fails to compile leaves the previous one in place
-		// (SceneManager.cpp:118-127 keeps the old shader and shows the compiler's message)
-		if (!jit_compile(r->device, name, source, slots, js, err)) return fail(r, SDFR_ERR_COMPILE, err);
-		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
-		if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream));
-		jit_unload(r->jit);
-		r->jit = js;
-		r->vars = vm;
-		r->scene_var_slots = slots;
-		r->scene = SDFR_SCENE_COUNT;
-		return SDFR_OK;
-	});
+	return guarded(r, [&]() -> int { return r && name && source ? load_runtime_scene(r, name, source, false) : SDFR_ERR_INVALID_ARGUMENT; });
 }
 
 const char *sdfr_current_scene(const sdfr_renderer *r)
@@ -489,26 +499,11 @@ int sdfr_set_camera(sdfr_renderer *r, const float eye[3], const float front[3], 
 	});
 }
 
-static int set_camera_from(sdfr_renderer *r, const host::Camera &cam)
-{
-	host::Vec3 e, f, rt, tp;
-	cam.GetBasis(e, f, rt, tp);
-	r->U.eye = V3(e.x, e.y, e.z);
-	r->U.front = V3(f.x, f.y, f.z);
-	r->U.right = V3(rt.x, rt.y, rt.z);
-	r->U.top = V3(tp.x, tp.y, tp.z);
-	return SDFR_OK;
-}
-
 int sdfr_set_camera_lookat(sdfr_renderer *r, const float eye[3], const float lookat[3], float fovy, float aspect, float roll)
 {
 	return guarded(r, [&]() -> int {
 		if (!r || !eye || !lookat) return SDFR_ERR_INVALID_ARGUMENT;
-		host::Camera cam;
-		cam.SetAspect(aspect);
-		cam.SetFOVY(fovy);
-		cam.SetRoll(roll);
-		cam.SetEye(host::Vec3(eye[0], eye[1], eye[2]));
+		host::Camera cam = make_camera(fovy, aspect, roll, host::Vec3(eye[0], eye[1], eye[2]));
 		cam.SetLookat(host::Vec3(lookat[0], lookat[1], lookat[2]));
 		return set_camera_from(r, cam);
 	});
@@ -518,11 +513,7 @@ int sdfr_set_camera_direction(sdfr_renderer *r, const float eye[3], const float 
 {
 	return guarded(r, [&]() -> int {
 		if (!r || !eye || !direction) return SDFR_ERR_INVALID_ARGUMENT;
-		host::Camera cam;
-		cam.SetAspect(aspect);
-		cam.SetFOVY(fovy);
-		cam.SetRoll(roll);
-		cam.SetEye(host::Vec3(eye[0], eye[1], eye[2]));
+		host::Camera cam = make_camera(fovy, aspect, roll, host::Vec3(eye[0], eye[1], eye[2]));
 		cam.SetDirection(host::Vec3(direction[0], direction[1], direction[2]));
 		return set_camera_from(r, cam);
 	});
@@ -556,19 +547,7 @@ int sdfr_get_limits(const sdfr_renderer *r, sdfr_limits *out)
 {
 	return guarded(r, [&]() -> int {
 		if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
-		out->iter_count = r->U.iter_count;
-		out->bounce_count = r->U.bounce_count;
-		out->ray_count = r->U.ray_count;
-		out->light_count = r->U.light_count;
-		out->range = r->U.range;
-		out->max_cost_default = (int)r->U.max_cost_default;
-		out->extension_lights = r->U.extension_lights;
-		out->extension_marble_reflection = r->U.extension_marble_reflection;
-		out->dist_eps = r->U.dist_eps;
-		out->grad_eps = r->U.grad_eps;
-		out->reflect_eps = r->U.reflect_eps;
-		out->refract_eps = r->U.refract_eps;
-		out->shadow_eps = r->U.shadow_eps;
+		for_each_limit(*out, r->U, [](auto &limit, const auto &frame) { limit = frame; });
 		return SDFR_OK;
 	});
 }
@@ -585,19 +564,7 @@ int sdfr_set_limits(sdfr_renderer *r, const sdfr_limits *l)
 		if (!(l->dist_eps > 0.f && l->dist_eps <= SDFR_MAX_DIST_EPS) || !(l->grad_eps > 0.f && l->grad_eps <= 1.f) || !(l->reflect_eps >= 0.f && l->reflect_eps <= 1.f) ||
 			!(l->refract_eps >= 0.f && l->refract_eps <= 1.f) || !(l->shadow_eps >= 0.f && l->shadow_eps <= 1.f))
 			return fail(r, SDFR_ERR_INVALID_ARGUMENT, "epsilons out of range (0 < dist_eps <= 1e-3, 0 < grad_eps <= 1, 0 <= reflect_eps, refract_eps, shadow_eps <= 1)");
-		r->U.iter_count = l->iter_count;
-		r->U.bounce_count = l->bounce_count;
-		r->U.ray_count = l->ray_count;
-		r->U.light_count = l->light_count;
-		r->U.range = l->range;
-		r->U.max_cost_default = (uint32_t)l->max_cost_default;
-		r->U.extension_lights = l->extension_lights;
-		r->U.extension_marble_reflection = l->extension_marble_reflection;
-		r->U.dist_eps = l->dist_eps;
-		r->U.grad_eps = l->grad_eps;
-		r->U.reflect_eps = l->reflect_eps;
-		r->U.refract_eps = l->refract_eps;
-		r->U.shadow_eps = l->shadow_eps;
+		for_each_limit(*l, r->U, [](const auto &limit, auto &frame) { frame = limit; });
 		return SDFR_OK;
 	});
 }
@@ -655,9 +622,7 @@ int64_t sdfr_strip_buffer_pixels(int width, int height, int world)
 int64_t sdfr_strip_buffer_pixels_split(int width, int height, int world, int priv_count, int priv_period)
 {
 	if (width < 1 || height < 1 || world < 1 || priv_count < 0 || priv_period < 1 || priv_count >= priv_period) return 0;
-	const int64_t strips = ((int64_t)height + SDFR_STRIP_ROWS - 1) / SDFR_STRIP_ROWS;
-	const int64_t shared = strips - (int64_t)private_strip_count((uint32_t)strips, priv_count, priv_period);
-	return ((shared + world - 1) / world) * SDFR_STRIP_ROWS * (int64_t)width;
+	return strip_buffer_pixels(width, height, world, priv_count, priv_period);
 }
 
 int sdfr_set_strip_split(sdfr_renderer *r, int priv_count, int priv_period)
@@ -675,8 +640,8 @@ int sdfr_set_strip_split(sdfr_renderer *r, int priv_count, int priv_period)
 static int check_render(sdfr_renderer *r, int width, int height, int rank, int world, const void *out, int format, RenderMode mode)
 {
 	if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
-	if (format != SDFR_RGBA32F && format != SDFR_RGBA16F && !(mode == RENDER_STRIPS && is_wire_format(format)))
-		return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
+	// an image is RGBA32F or RGBA16F; a strip buffer may also be in one of the packed wire formats
+	if (mode == RENDER_STRIPS ? !is_wire_format(format) : format != SDFR_RGBA32F && format != SDFR_RGBA16F) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
 	if (mode == RENDER_PRIVATE && r->priv_count == 0) return SDFR_OK;
 	if (world < 1 || rank < 0 || rank >= world) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad rank/world");
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
@@ -753,15 +718,8 @@ static int query_impl(sdfr_renderer *r, int kind, int64_t n, const float *pos, c
 	if (on_host)
 	{
 		const size_t need = up(in0) + up(in1) + up(out0) + up(out1);
-		if (r->query_bytes < need)
-		{
-			(void)hipFree(r->d_query); // (host queries are synchronous: none is using it)
-			r->d_query = nullptr;
-			r->query_bytes = 0;
-			SDFR_HIP(hipMalloc(&r->d_query, need));
-			r->query_bytes = need;
-		}
-		char *base = static_cast<char *>(r->d_query);
+		SDFR_HIP(r->query.reserve(need)); // (host queries are synchronous: none is using the old one)
+		char *base = static_cast<char *>(r->query.ptr);
 		char *d_in0 = base, *d_in1 = d_in0 + up(in0), *d_out0 = d_in1 + up(in1), *d_out1 = d_out0 + up(out0);
 		SDFR_HIP(hipMemcpyAsync(d_in0, kind == QUERY_PICK ? (const void *)pixels : (const void *)pos, in0, hipMemcpyHostToDevice, stream));
 		if (in1) SDFR_HIP(hipMemcpyAsync(d_in1, dir, in1, hipMemcpyHostToDevice, stream));
@@ -789,13 +747,8 @@ static int query_impl(sdfr_renderer *r, int kind, int64_t n, const float *pos, c
 			out0, hipMemcpyDeviceToHost, stream));
 		if (out1) SDFR_HIP(hipMemcpyAsync(normals, q.normals, out1, hipMemcpyDeviceToHost, stream));
 		SDFR_HIP(hipStreamSynchronize(stream));
-		if (r->query_bytes > k_query_stage_keep)
-		{
-			// a large host query does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
-			(void)hipFree(r->d_query);
-			r->d_query = nullptr;
-			r->query_bytes = 0;
-		}
+		// a large host query does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
+		if (r->query.bytes > k_query_stage_keep) r->query.release();
 	}
 	return SDFR_OK;
 }
@@ -823,69 +776,32 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 	int rc = check_render(r, width, height, rank, world, out, format, mode);
 	if (rc != SDFR_OK || (mode == RENDER_PRIVATE && r->priv_count == 0)) return rc; // (no private strips: nothing to render)
 	if (!totals) totals = r->lane.d_totals;
-	const bool strips = mode == RENDER_STRIPS;
 	SDFR_HIP(hipSetDevice(r->device));
 	const auto t_setup = std::chrono::steady_clock::now();
 	rc = latch_frame(r, width, height);
 	if (rc != SDFR_OK) return rc;
 	r->ms_setup = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_setup).count();
 
-	RowMap rm;
-	rm.rank = rank;
-	rm.world = world;
-	rm.tile_w_log2 = r->tile_w_log2 ? r->tile_w_log2 : scene_tile_w_log2(r->scene);
-	rm.priv_count = mode == RENDER_FULL ? 0 : r->priv_count;
-	rm.priv_period = mode == RENDER_FULL ? 1 : r->priv_period;
-	rm.direct = mode == RENDER_PRIVATE ? 1 : 0;
-	row_map_tiles(rm, width);
-	rm.unit_log2 = rm.units_x = rm.units_x_magic = rm.units = 0u; // the launcher of a persistent launch decides (row_map_units)
-	rm.retire_after = 0u;
-	rm.feedback_key = 0u;
-	const uint32_t frame_strips = (uint32_t)((height + SDFR_STRIP_ROWS - 1) / SDFR_STRIP_ROWS);
-	if (mode == RENDER_FULL)
-		rm.local_rows = height;
-	else if (mode == RENDER_STRIPS) // a strip buffer keeps whole strips (rows past the frame stay zero)
-		rm.local_rows = (int)(sdfr_strip_buffer_pixels_split(width, height, world, rm.priv_count, rm.priv_period) / width);
-	else
-		rm.local_rows = (int)(private_strip_count(frame_strips, rm.priv_count, rm.priv_period) * SDFR_STRIP_ROWS);
-	// pixels the output (and the per-pixel workspace, which is indexed like the output) spans
-	const size_t local_pixels = mode == RENDER_PRIVATE ? (size_t)width * height : (size_t)rm.local_rows * width;
+	const FrameRows rows = frame_rows(mode, width, height, rank, world, r->tile_w_log2 ? r->tile_w_log2 : scene_tile_w_log2(r->scene), r->priv_count, r->priv_period);
+	const RowMap &rm = rows.rm;
+	const size_t local_pixels = rows.local_pixels;
 	const size_t out_bytes = image_bytes(local_pixels, format);
 
 	void *d_out = out;
 	uint32_t *d_pstat = pixel_stats;
 	if (out_on_host)
 	{
-		if (r->stage_bytes < out_bytes)
-		{
-			(void)hipFree(r->d_stage);
-			r->d_stage = nullptr;
-			r->stage_bytes = 0;
-			SDFR_HIP(hipMalloc(&r->d_stage, out_bytes));
-			r->stage_bytes = out_bytes;
-		}
-		d_out = r->d_stage;
+		SDFR_HIP(r->stage.reserve(out_bytes));
+		d_out = r->stage.ptr;
 		if (pixel_stats)
 		{
-			if (r->pstat_bytes < local_pixels * 12)
-			{
-				(void)hipFree(r->d_pstat);
-				r->d_pstat = nullptr;
-				r->pstat_bytes = 0;
-				SDFR_HIP(hipMalloc((void **)&r->d_pstat, local_pixels * 12));
-				r->pstat_bytes = local_pixels * 12;
-			}
-			d_pstat = r->d_pstat;
+			SDFR_HIP(r->pstat.reserve(local_pixels * 12));
+			d_pstat = static_cast<uint32_t *>(r->pstat.ptr);
 		}
 	}
-	if (strips)
-	{
-		// rows of the buffer past the end of the frame are never written: define them (only the ranks
-		// whose last strip is missing or cut short have any)
-		const int last_local_strip = rm.local_rows / SDFR_STRIP_ROWS - 1;
-		const long long last_row_end = last_local_strip < 0 ? 0 : ((long long)strip_local_to_global(rm, (uint32_t)last_local_strip) + 1) * SDFR_STRIP_ROWS;
-		if (last_row_end > height && out_bytes) SDFR_HIP(hipMemsetAsync(d_out, 0, out_bytes, r->lane.stream));
-	}
+	// rows of a strip buffer past the end of the frame are never written: define them (only the ranks whose last strip is
+	// missing or cut short have any)
+	if (mode == RENDER_STRIPS && strips_end_past_frame(rm, height) && out_bytes) SDFR_HIP(hipMemsetAsync(d_out, 0, out_bytes, r->lane.stream));
 
 	const bool pixel_schedule = r->scene == SDFR_SCENE_COUNT || r->schedule == SDFR_SCHEDULE_PIXEL;
 	if (!pixel_schedule) SDFR_HIP(hipMemsetAsync(totals, 0, sizeof(RenderTotals), r->lane.stream)); // the wavefront kernels add to it
@@ -1009,17 +925,10 @@ int sdfr_postprocess(sdfr_renderer *r, int width, int height, const void *scene_
 		if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 		SDFR_HIP(hipSetDevice(r->device));
 		const size_t flag_bytes = postprocess_flag_bytes(width, height);
-		if (r->post_flag_bytes < flag_bytes)
-		{
-			SDFR_HIP(hipStreamSynchronize(r->lane.stream)); // a postprocess still in flight reads the old one
-			(void)hipFree(r->d_post_flags);
-			r->d_post_flags = nullptr;
-			r->post_flag_bytes = 0;
-			SDFR_HIP(hipMalloc((void **)&r->d_post_flags, flag_bytes));
-			r->post_flag_bytes = flag_bytes;
-		}
+		if (r->post_flags.bytes < flag_bytes) SDFR_HIP(hipStreamSynchronize(r->lane.stream)); // a postprocess still in flight reads the old one
+		SDFR_HIP(r->post_flags.reserve(flag_bytes));
 		SDFR_HIP(hipEventRecord(r->ev_post[0], r->lane.stream));
-		hipError_t e = launch_postprocess(width, height, scene_rgba16f, bloom_scratch_rgba16f, out_rgba8, r->d_post_flags, r->lane.stream, r->ev_post[1]);
+		hipError_t e = launch_postprocess(width, height, scene_rgba16f, bloom_scratch_rgba16f, out_rgba8, static_cast<unsigned char *>(r->post_flags.ptr), r->lane.stream, r->ev_post[1]);
 		if (e != hipSuccess) return hip_fail(r, e, "postprocess launch");
 		SDFR_HIP(hipEventRecord(r->ev_post[2], r->lane.stream));
 		r->have_post = true;
@@ -1092,11 +1001,22 @@ int sdfr_register_host_target(sdfr_renderer *r, void *host_image, size_t bytes)
 int sdfr_sync(sdfr_renderer *r)
 {
 	return guarded(r, [&]() -> int {
-		if (!r) return SDFR_ERR_INVALID_ARGUMENT;
-		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
-		if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream));
-		return SDFR_OK;
+		return r ? sync_lanes(r) : SDFR_ERR_INVALID_ARGUMENT;
 	});
+}
+
+// the profiled rounds of the last frame, if the wavefront schedule rendered it: their number, and the milliseconds of each
+// round's march and shade launches (-1: that time cannot be read)
+struct RoundTime { float march, shade; };
+static int round_times(const sdfr_renderer *r, RoundTime t[16])
+{
+	int n = 0;
+	for (; r->last_wavefront && r->last_profiled && n < r->last_rounds && n < 16; ++n)
+	{
+		if (hipEventElapsedTime(&t[n].march, r->ev_march[2 * n], r->ev_march[2 * n + 1]) != hipSuccess) t[n].march = -1.f;
+		if (hipEventElapsedTime(&t[n].shade, r->ev_shade[2 * n], r->ev_shade[2 * n + 1]) != hipSuccess) t[n].shade = -1.f;
+	}
+	return n;
 }
 
 int sdfr_get_stats(sdfr_renderer *r, sdfr_stats *out)
@@ -1120,11 +1040,11 @@ int sdfr_get_stats(sdfr_renderer *r, sdfr_stats *out)
 		}
 		if (r->last_wavefront)
 		{
-			for (int i = 0; r->last_profiled && i < r->last_rounds && i < 16; ++i)
+			RoundTime t[16];
+			for (int i = 0, n = round_times(r, t); i < n; ++i) // whichever of the two times can be read
 			{
-				float a = 0.f, b = 0.f;
-				if (hipEventElapsedTime(&a, r->ev_march[2 * i], r->ev_march[2 * i + 1]) == hipSuccess) out->ms_march += a;
-				if (hipEventElapsedTime(&b, r->ev_shade[2 * i], r->ev_shade[2 * i + 1]) == hipSuccess) out->ms_shade += b;
+				if (t[i].march >= 0.f) out->ms_march += t[i].march;
+				if (t[i].shade >= 0.f) out->ms_shade += t[i].shade;
 			}
 			out->march_launches = (uint32_t)r->last_rounds;
 			out->shade_launches = (uint32_t)r->last_rounds;
@@ -1158,16 +1078,15 @@ int sdfr_get_timings(sdfr_renderer *r, sdfr_timing *out, int capacity)
 			SDFR_HIP(hipEventElapsedTime(&ms, r->lane.ev_begin, r->lane.ev_end));
 			put("setup", r->ms_setup);
 			put("draw", ms);
-			for (int i = 0; r->last_wavefront && r->last_profiled && i < r->last_rounds && i < 16; ++i)
+			RoundTime t[16];
+			for (int i = 0, rounds = round_times(r, t); i < rounds; ++i)
 			{
-				float a = 0.f, b = 0.f;
+				if (t[i].march < 0.f || t[i].shade < 0.f) continue; // a round is listed with both of its times or not at all
 				char nm[32];
-				if (hipEventElapsedTime(&a, r->ev_march[2 * i], r->ev_march[2 * i + 1]) != hipSuccess) continue;
-				if (hipEventElapsedTime(&b, r->ev_shade[2 * i], r->ev_shade[2 * i + 1]) != hipSuccess) continue;
 				snprintf(nm, sizeof nm, "draw: march %d", i);
-				put(nm, a);
+				put(nm, t[i].march);
 				snprintf(nm, sizeof nm, "draw: shade %d", i);
-				put(nm, b);
+				put(nm, t[i].shade);
 			}
 		}
 		if (r->lane.have_render && r->have_xfer)

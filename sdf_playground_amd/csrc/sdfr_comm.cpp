@@ -224,21 +224,17 @@ int gather_render(sdfr_renderer *r, const sdfr_comm *c, const GatherShape &g)
 	int prc = gather_prepare_streams(r);
 	if (prc != SDFR_OK) return prc;
 	const size_t need = (c->rank == 0 ? (size_t)g.world : (size_t)1) * g.rank_bytes;
-	if (r->wire_bytes < need)
+	if (r->wire.bytes < need)
 	{
 		// frames still in flight on either stream read or write the old buffer
 		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
 		SDFR_HIP(hipStreamSynchronize(r->comm_stream));
-		(void)hipFree(r->d_wire);
-		r->d_wire = nullptr;
-		r->wire_bytes = 0;
-		SDFR_HIP(hipMalloc(&r->d_wire, need));
-		r->wire_bytes = need;
+		SDFR_HIP(r->wire.reserve(need));
 	}
 	SDFR_HIP(hipEventRecord(r->lane.ev_begin, r->lane.stream));
 	SDFR_HIP(hipMemsetAsync(r->lane.d_totals, 0, 2 * sizeof(RenderTotals), r->lane.stream));
 	int rc = SDFR_OK;
-	if (g.rank_bytes) rc = render_impl(r, g.width, g.height, c->rank, g.world, r->d_wire, g.wire_format, 0, nullptr, RENDER_STRIPS, r->lane.d_totals, true);
+	if (g.rank_bytes) rc = render_impl(r, g.width, g.height, c->rank, g.world, r->wire.ptr, g.wire_format, 0, nullptr, RENDER_STRIPS, r->lane.d_totals, true);
 	if (rc != SDFR_OK) return rc;
 	SDFR_HIP(hipEventRecord(r->ev_strips, r->lane.stream));
 	SDFR_HIP(hipStreamWaitEvent(r->comm_stream, r->ev_strips, 0));
@@ -254,13 +250,13 @@ int gather_transfer(sdfr_renderer *r, sdfr_comm *c, const GatherShape &g)
 	{
 		for (int p = 1; p < g.world; ++p)
 		{
-			ncclResult_t rc = n.recv((char *)r->d_wire + (size_t)p * g.rank_bytes, g.rank_bytes, ncclInt8, p, c->comm, r->comm_stream);
+			ncclResult_t rc = n.recv((char *)r->wire.ptr + (size_t)p * g.rank_bytes, g.rank_bytes, ncclInt8, p, c->comm, r->comm_stream);
 			if (rc != ncclSuccess) return fail(r, nccl_fail(c, rc, "ncclRecv"), c->error);
 		}
 	}
 	else
 	{
-		ncclResult_t rc = n.send(r->d_wire, g.rank_bytes, ncclInt8, 0, c->comm, r->comm_stream);
+		ncclResult_t rc = n.send(r->wire.ptr, g.rank_bytes, ncclInt8, 0, c->comm, r->comm_stream);
 		if (rc != ncclSuccess) return fail(r, nccl_fail(c, rc, "ncclSend"), c->error);
 	}
 	return SDFR_OK;
@@ -276,7 +272,7 @@ int gather_finish(sdfr_renderer *r, const sdfr_comm *c, const GatherShape &g, vo
 	{
 		if (g.rank_bytes)
 		{
-			hipError_t e = launch_assemble_strips(g.width, g.height, g.world, r->d_wire, root_image, g.wire_format, r->priv_count, r->priv_period,
+			hipError_t e = launch_assemble_strips(g.width, g.height, g.world, r->wire.ptr, root_image, g.wire_format, r->priv_count, r->priv_period,
 				r->comm_stream);
 			if (e != hipSuccess) return hip_fail(r, e, "assemble launch");
 		}

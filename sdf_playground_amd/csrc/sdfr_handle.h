@@ -14,6 +14,28 @@
 #include <string>
 #include <vector>
 
+// A device buffer that only grows, kept from call to call.  reserve() replaces a buffer that is too small (the old contents are
+// gone); the caller first waits for whatever may still use the old one.  Empty after a failed reserve().
+struct sdfr_device_buffer
+{
+	void *ptr = nullptr;
+	size_t bytes = 0;
+	hipError_t reserve(size_t need)
+	{
+		if (bytes >= need) return hipSuccess;
+		release();
+		const hipError_t e = hipMalloc(&ptr, need);
+		if (e == hipSuccess) bytes = need;
+		return e;
+	}
+	void release()
+	{
+		(void)hipFree(ptr);
+		ptr = nullptr;
+		bytes = 0;
+	}
+};
+
 struct sdfr_renderer
 {
 	// What one frame in flight owns: its stream, its workspace (ray queue, counter records, tile cursors with the row order
@@ -49,12 +71,8 @@ struct sdfr_renderer
 	std::vector<std::string> scene_var_slots; // slot k of FrameU::scene_var <- this variable
 	mutable std::string error;
 
-	void *d_stage = nullptr; // staging image for host-destination renders
-	size_t stage_bytes = 0;
-	uint32_t *d_pstat = nullptr;
-	size_t pstat_bytes = 0;
-	void *d_query = nullptr; // staging of host-memory queries (sdfr_query_*, sdfr_pick): inputs and answers; kept up to 64 MiB
-	size_t query_bytes = 0;
+	sdfr_device_buffer stage, pstat; // staging image and pixel_stats of host-destination renders
+	sdfr_device_buffer query;        // staging of host-memory queries (sdfr_query_*, sdfr_pick): inputs and answers; kept up to 64 MiB
 	// sdfr_register_host_target: the caller's persistent host image, page-locked with the runtime
 	void *pinned_host = nullptr;
 	size_t pinned_bytes = 0;
@@ -62,8 +80,7 @@ struct sdfr_renderer
 	hipEvent_t ev_post[3] = {}; // before / between / after the two post-processing kernels
 	bool have_post = false;
 	bool step_shortcuts = true; // sdfr_set_step_shortcuts
-	unsigned char *d_post_flags = nullptr; // per row segment: did the horizontal bloom pass store any light (sdfr_post.hip)
-	size_t post_flag_bytes = 0;
+	sdfr_device_buffer post_flags; // per row segment: did the horizontal bloom pass store any light (sdfr_post.hip)
 	double ms_setup = 0.0;      // host time of the last latch_frame (+ Scene::prepare of a run-time scene)
 	hipEvent_t ev_march[32] = {}, ev_shade[32] = {};
 	int last_rounds = 0;
@@ -77,8 +94,7 @@ struct sdfr_renderer
 	hipEvent_t ev_xfer[2] = {nullptr, nullptr}; // around the last gather's transfer on the comm stream ("gather transfer", sdfr_get_timings)
 	bool have_xfer = false;
 	size_t xfer_bytes = 0;                      // bytes this rank sent (peers) or received (rank 0) in that transfer
-	void *d_wire = nullptr;    // this rank's compact strips; on the root: world x that, slot 0 = its own
-	size_t wire_bytes = 0;
+	sdfr_device_buffer wire;   // this rank's compact strips; on the root: world x that, slot 0 = its own
 	std::vector<void *> comms_used; // sdfr_comm* whose transfers ran on comm_stream (sdfr_comm.cpp keeps both sides of the list)
 
 	unsigned launches = 0; // render launches so far: did a call that failed launch anything before it failed
@@ -124,8 +140,6 @@ static inline int hip_fail(const sdfr_renderer *r, hipError_t e, const char *wha
 	do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(r, e_, #call); } while (0)
 
 namespace sdfr {
-
-enum RenderMode { RENDER_FULL, RENDER_STRIPS, RENDER_PRIVATE };
 
 // bytes of a compact image of `pixels` pixels (the packed strip formats are padded to 4)
 size_t image_bytes(size_t pixels, int format);

@@ -11,6 +11,65 @@
 namespace sdfr {
 
 enum { SDFR_TILE_ITEMS = 64 }; // work items of a tile: one wave, one block of the pixel kernel
+#ifndef SDFR_STRIP_ROWS
+#define SDFR_STRIP_ROWS 8 // include/sdfr.h; the 8-row strips of RowMap (sdfr_frame.h)
+#endif
+
+// which rows of a frame a render covers: all of them, this rank's shared strips (compact buffer), or the private strips (in place)
+enum RenderMode { RENDER_FULL, RENDER_STRIPS, RENDER_PRIVATE };
+
+// pixels of one rank's compact strip buffer (sdfr_strip_buffer_pixels_split, arguments checked): whole strips, the same on every rank
+inline int64_t strip_buffer_pixels(int width, int height, int world, int priv_count, int priv_period)
+{
+	const int64_t strips = ((int64_t)height + SDFR_STRIP_ROWS - 1) / SDFR_STRIP_ROWS;
+	const int64_t shared = strips - (int64_t)private_strip_count((uint32_t)strips, priv_count, priv_period);
+	return ((shared + world - 1) / world) * SDFR_STRIP_ROWS * (int64_t)width;
+}
+// a row map as the API hands it to the launchers: tiles set, no hand-out units, retire_after or feedback_key -- the launcher of
+// a persistent launch decides those (plan_pixel_launch)
+inline RowMap api_row_map(int width, int local_rows, int rank, int world, int tile_w_log2, int priv_count, int priv_period, int direct)
+{
+	RowMap rm;
+	rm.local_rows = local_rows;
+	rm.rank = rank;
+	rm.world = world;
+	rm.tile_w_log2 = tile_w_log2;
+	rm.priv_count = priv_count;
+	rm.priv_period = priv_period;
+	rm.direct = direct;
+	row_map_tiles(rm, width);
+	rm.unit_log2 = rm.units_x = rm.units_x_magic = rm.units = 0u;
+	rm.retire_after = 0u;
+	rm.feedback_key = 0u;
+	return rm;
+}
+// The rows of one render of the API (render_impl, sdfr_api.cpp) and the pixels its output -- and the per-pixel workspace, which is
+// indexed like the output -- spans.  priv_count / priv_period: the handle's strip split, which a full frame ignores.
+struct FrameRows
+{
+	RowMap rm;
+	size_t local_pixels;
+};
+inline FrameRows frame_rows(RenderMode mode, int width, int height, int rank, int world, int tile_w_log2, int priv_count, int priv_period)
+{
+	if (mode == RENDER_FULL) { priv_count = 0; priv_period = 1; }
+	int local_rows = height;
+	if (mode == RENDER_STRIPS) // a strip buffer keeps whole strips (rows past the frame stay zero)
+		local_rows = (int)(strip_buffer_pixels(width, height, world, priv_count, priv_period) / width);
+	else if (mode == RENDER_PRIVATE)
+		local_rows = (int)(private_strip_count((uint32_t)((height + SDFR_STRIP_ROWS - 1) / SDFR_STRIP_ROWS), priv_count, priv_period) * SDFR_STRIP_ROWS);
+	FrameRows f;
+	f.rm = api_row_map(width, local_rows, rank, world, tile_w_log2, priv_count, priv_period, mode == RENDER_PRIVATE ? 1 : 0);
+	f.local_pixels = mode == RENDER_PRIVATE ? (size_t)width * height : (size_t)local_rows * width;
+	return f;
+}
+// does a strip buffer of `rm` end past the frame: its last strip is missing or cut short, and those rows are never written
+inline bool strips_end_past_frame(const RowMap &rm, int height)
+{
+	const int last_local_strip = rm.local_rows / SDFR_STRIP_ROWS - 1;
+	const long long last_row_end = last_local_strip < 0 ? 0 : ((long long)strip_local_to_global(rm, (uint32_t)last_local_strip) + 1) * SDFR_STRIP_ROWS;
+	return last_row_end > height;
+}
 
 // work items (padded to whole tiles) of a launch: lists and per-pixel state are sized by this
 inline uint32_t launch_work_items(int width, const RowMap &rm)
@@ -116,7 +175,7 @@ struct PixelLaunchPlan
 	uint32_t feedback_rows;   // units the fold sorts for the next frame (0: not a persistent launch)
 	unsigned long long frame_pixels; // the fold's measure of "many rays per pixel"
 };
-// rm: as the API makes it (row_map_tiles done, no hand-out units, sdfr_api.cpp); capacity: items the workspace holds (one counter record
+// rm: as the API makes it (api_row_map); capacity: items the workspace holds (one counter record
 // per block, at most one block per tile handed out); resident_blocks_per_cu: the occupancy query's answer for the kernel, >= 1
 inline PixelLaunchPlan plan_pixel_launch(const PixelSceneTraits &scene, const PixelLaunchKnobs &knobs, int launch_mode, int width, const RowMap &rm,
 	size_t capacity, int resident_blocks_per_cu, int cus)

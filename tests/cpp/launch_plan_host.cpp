@@ -25,24 +25,13 @@ struct LpOut
 	uint64_t frame_pixels;
 };
 
-// the row map as the API makes it (render_impl, sdfr_api.cpp), then the plan
+// the row map as the API makes it (api_row_map), then the plan
 void lp_plan(int n, const LpIn *in, LpOut *out)
 {
 	for (int i = 0; i < n; ++i)
 	{
 		const LpIn &a = in[i];
-		RowMap rm;
-		rm.local_rows = a.local_rows;
-		rm.rank = a.rank;
-		rm.world = a.world;
-		rm.tile_w_log2 = a.tile_w_log2;
-		rm.priv_count = a.priv_count;
-		rm.priv_period = a.priv_period;
-		rm.direct = a.direct;
-		row_map_tiles(rm, a.width);
-		rm.unit_log2 = rm.units_x = rm.units_x_magic = rm.units = 0u;
-		rm.retire_after = 0u;
-		rm.feedback_key = 0u;
+		const RowMap rm = api_row_map(a.width, a.local_rows, a.rank, a.world, a.tile_w_log2, a.priv_count, a.priv_period, a.direct);
 		const PixelSceneTraits scene = {a.persistent_tiles != 0, a.retire_after, a.square_units != 0, a.scene_key};
 		const PixelLaunchKnobs knobs = {a.knob_persistent, a.knob_blocks_per_cu, a.knob_retire_after, a.knob_square_units};
 		const PixelLaunchPlan p = plan_pixel_launch(scene, knobs, a.launch_mode, a.width, rm, (size_t)a.capacity, a.resident_blocks_per_cu, a.cus);
@@ -64,6 +53,18 @@ void lp_plan(int n, const LpIn *in, LpOut *out)
 		o.capacity_items = launch_capacity_items(a.width, rm);
 		o.frame_pixels = p.frame_pixels;
 	}
+}
+
+// the rows of a render of the API: render mode, frame, rank / world, tile shape and the handle's strip split -> FrameRows
+struct FrIn
+{
+	int32_t mode, width, height, rank, world, tile_w_log2, priv_count, priv_period;
+};
+static_assert(sizeof(FrameRows) == 72, "FrameRows as tests/test_launch_plan_cpu.py spells it: the 15 words of RowMap, then the pixels");
+void lp_frame_rows(int n, const FrIn *in, FrameRows *out)
+{
+	for (int i = 0; i < n; ++i)
+		out[i] = frame_rows((RenderMode)in[i].mode, in[i].width, in[i].height, in[i].rank, in[i].world, in[i].tile_w_log2, in[i].priv_count, in[i].priv_period);
 }
 
 int lp_row_feedback_max() { return (int)SDFR_ROW_FEEDBACK_MAX; }

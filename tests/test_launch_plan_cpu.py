@@ -7,7 +7,9 @@ renders the right pixels, only slower -- so it is checked here, as arithmetic.
 Three kinds of check over one grid of inputs: equality with a second spelling of the arithmetic (`parent_run_pixel`,
 `parent_jit_launch_pixel` below: written from the two launchers of commit 880a4f7, run_pixel of sdfr_kernels_scene.hip and
 jit_launch_pixel of sdfr_jit.cpp, each as it stood there) -- a characterisation that pins those numbers without arguing that they
-are right --, the invariants the kernels rely on, and a few literal rows for the benchmark's configurations."""
+are right --, the invariants the kernels rely on, and a few literal rows for the benchmark's configurations.  The row maps of that
+grid are a second spelling too (`row_maps`, written from render_impl of commit ce3740b): frame_rows, which render_impl calls, is checked
+against it."""
 import ctypes
 import itertools
 import os
@@ -35,6 +37,21 @@ class LpOut(ctypes.Structure):
     _fields_ = [(n, U64 if n == "frame_pixels" else I32 if n in ("fits", "tile_cursors") else U32) for n in OUT_FIELDS]
 
 
+# lp_frame_rows: FrIn, and FrameRows (sdfr_launch_plan.h) = RowMap (sdfr_frame.h) word by word, then the pixels the output spans
+FRAME_FIELDS = ["mode", "width", "height", "rank", "world", "tile_w_log2", "priv_count", "priv_period"]
+ROW_MAP_INTS = ["local_rows", "rank", "world", "tile_w_log2", "priv_count", "priv_period", "direct"]
+ROW_MAP_WORDS = ["tiles_x", "tiles_x_magic", "unit_log2", "units_x", "units_x_magic", "units", "retire_after", "feedback_key"]
+RENDER_FULL, RENDER_STRIPS, RENDER_PRIVATE = 0, 1, 2
+
+
+class FrIn(ctypes.Structure):
+    _fields_ = [(n, I32) for n in FRAME_FIELDS]
+
+
+class FrameRows(ctypes.Structure):
+    _fields_ = [(n, I32) for n in ROW_MAP_INTS] + [(n, U32) for n in ROW_MAP_WORDS] + [("local_pixels", U64)]
+
+
 _lib = None
 
 
@@ -52,6 +69,8 @@ def lib():
         _lib = ctypes.CDLL(so)
         _lib.lp_plan.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         _lib.lp_plan.restype = None
+        _lib.lp_frame_rows.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.lp_frame_rows.restype = None
     return _lib
 
 
@@ -186,7 +205,7 @@ def private_strip_count(strips, priv_count, priv_period):
     return (strips // priv_period) * priv_count + min(strips % priv_period, priv_count)
 
 
-def row_maps(height):
+def row_maps(height, empty=False):
     """the row maps render_impl (sdfr_api.cpp) makes: the full frame, strips of world 1..8, a strip split, its private strips"""
     strips = cdiv(height, 8)
     maps = [dict(local_rows=height, rank=0, world=1, priv_count=0, priv_period=1, direct=0)]
@@ -196,7 +215,7 @@ def row_maps(height):
         shared = strips - private_strip_count(strips, pc, pp)
         maps.append(dict(local_rows=cdiv(shared, world) * 8, rank=world - 1, world=world, priv_count=pc, priv_period=pp, direct=0))
         maps.append(dict(local_rows=private_strip_count(strips, pc, pp) * 8, rank=0, world=world, priv_count=pc, priv_period=pp, direct=1))
-    return [m for m in maps if m["local_rows"] > 0]  # (no rows: the API launches nothing)
+    return [m for m in maps if empty or m["local_rows"] > 0]  # (no rows: the API launches nothing)
 
 
 def grid():
@@ -282,6 +301,34 @@ def test_plan_keeps_what_the_kernels_rely_on(planned):
             assert o["feedback_key"] == 0 and o["feedback_rows"] == 0 and o["retire_after"] == 0 and o["unit_log2"] == 0, (c, o)
             assert o["blocks"] == o["n_work"] // 64, (c, o)
     assert squares > 10000
+
+
+def test_frame_rows_are_the_row_maps_of_the_grid():
+    """frame_rows, which render_impl calls, against `row_maps`: every row map of the grid, the empty ones included.  A full frame is
+    asked for on a handle that carries a strip split, which it ignores."""
+    cases, want = [], []
+    for width, height, tw in itertools.product(WIDTHS, HEIGHTS, (3, 4, 5, 6)):
+        for k, m in enumerate(row_maps(height, empty=True)):
+            mode = RENDER_FULL if k == 0 else RENDER_PRIVATE if m["direct"] else RENDER_STRIPS
+            split = (3, 5) if mode == RENDER_FULL else (m["priv_count"], m["priv_period"])
+            cases.append(dict(mode=mode, width=width, height=height, rank=m["rank"], world=m["world"], tile_w_log2=tw, priv_count=split[0],
+                              priv_period=split[1]))
+            want.append(m)
+    n = len(cases)
+    assert n == len(WIDTHS) * len(HEIGHTS) * 4 * 13 and any(m["local_rows"] == 0 for m in want)
+    assert {c["mode"] for c in cases} == {RENDER_FULL, RENDER_STRIPS, RENDER_PRIVATE}
+    assert ctypes.sizeof(FrameRows) == 72
+    a, o = (FrIn * n)(), (FrameRows * n)()
+    for k, c in enumerate(cases):
+        for f in FRAME_FIELDS:
+            setattr(a[k], f, c[f])
+    lib().lp_frame_rows(n, a, o)
+    for c, m, got in zip(cases, want, o):
+        assert {f: getattr(got, f) for f in m} == m, (c, m)
+        tiles_x = cdiv(c["width"], 1 << c["tile_w_log2"])
+        assert (got.tile_w_log2, got.tiles_x, got.tiles_x_magic) == (c["tile_w_log2"], tiles_x, (1 << 32) // tiles_x if tiles_x > 1 else M32), c
+        assert (got.unit_log2, got.units_x, got.units_x_magic, got.units, got.retire_after, got.feedback_key) == (0, 0, 0, 0, 0, 0), c
+        assert got.local_pixels == c["width"] * (c["height"] if c["mode"] == RENDER_PRIVATE else m["local_rows"]), (c, m)
 
 
 def test_keys_tell_launches_apart():
