@@ -330,6 +330,61 @@ int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const flo
  * pixel's), marched to limits.range, otherwise as sdfr_query_rays.  A pixel outside the frame gives hit = -1. */
 int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host);
 
+/* ---- the loaded scene as a triangle mesh: naive surface nets over a lattice of scene distances (no counterpart in the reference;
+ *      DESIGN.md "Mesh extraction").  One vertex per grid cell the surface passes through, one quad (two triangles) per lattice edge
+ *      that changes sign: an indexed mesh with shared vertices, closed wherever the surface stays inside the grid.  All arithmetic
+ *      is fp32 and unfused, in the order written here, so every number of the mesh is defined exactly.
+ *
+ *      Lattice point (i, j, k), 0 <= i <= nx ..., is at origin + (float)i * cell per axis: one multiply, then one add.
+ *      Distance and inside: D(i, j, k) is what sdfr_query_distance returns at that point; s = D - iso; a point is INSIDE iff s < 0
+ *      (NaN is therefore outside).
+ *      Active cells: cell (i, j, k), 0 <= i < nx ..., has the corners (i + di, j + dj, k + dk); it is ACTIVE iff at least one corner
+ *      is inside and at least one is not.  Active cells get consecutive vertex indices in the order of their linear index
+ *      i + nx * (j + ny * k).
+ *      Vertex position: visit the cell's 12 edges in this order: the 4 along x with (dj, dk) = (0,0), (1,0), (0,1), (1,1); the 4
+ *      along y with (di, dk) in that order; the 4 along z with (di, dj) in that order.  An edge runs from its lower endpoint a to
+ *      its upper endpoint b; if exactly one of them is inside, t = s_a / (s_a - s_b) and the crossing is a's position with the edge
+ *      axis' coordinate replaced by p_a + t * (p_b - p_a).  Each crossing is added component by component to a running sum, in
+ *      that order; the vertex is sum / (float)crossings, three divisions.
+ *      Quads: every lattice edge from a point P along axis a to its neighbour that has exactly one endpoint inside, where -- with
+ *      (a, b, c) the cyclic axis order (x,y,z), (y,z,x) or (z,x,y) -- P's coordinates on axes b and c are >= 1 and <= n_b - 1,
+ *      n_c - 1, so that the four cells around the edge exist.  With C(ob, oc) the cell at P offset by ob, oc on axes b and c, the
+ *      quad is the vertices of C(-1,-1), C(0,-1), C(0,0), C(-1,0) in that order when P is inside -- counter-clockwise seen from
+ *      outside, its normal towards +a -- and in the reverse order, C(-1,0), C(0,0), C(0,-1), C(-1,-1), when P is outside.  Quad
+ *      (q0, q1, q2, q3) becomes the triangles (q0, q1, q2) and (q0, q2, q3).  Quads are ordered by P's linear index
+ *      i + (nx + 1) * (j + (ny + 1) * k), then by axis x, y, z.  Edges on the grid's boundary emit nothing: the mesh is open where
+ *      the surface leaves the box.
+ *      Normals: normals[v] is the normal sdfr_query_distance returns at positions[v] (the driver's map_normal, or forward
+ *      differences against the distance at the vertex).
+ *
+ *        - counts is host memory, required, and filled when the call returns: the call reads the two totals back, so it is
+ *          synchronous up to that point.  The arrays are host (on_host = 1) or device (on_host = 0) memory as for the queries; with
+ *          device arrays the emit work is enqueued on the stream the queries use (two frames in flight: sdfr_sync before reading).
+ *        - if either capacity is smaller than the corresponding count, only counts is written, the arrays are untouched and the
+ *          call returns SDFR_OK: compare counts with the capacities.  Capacities 0 with NULL arrays: the counting call.
+ *        - SDFR_ERR_INVALID_ARGUMENT: a bad grid (below; origin and iso finite), a NULL grid or counts, a negative capacity, a NULL
+ *          array with a non-zero capacity (normals excepted: NULL = not wanted), a bad on_host.  SDFR_ERR_NO_SCENE: no scene.
+ *        - like a query, the call latches camera, time, variables and limits into a copy and changes nothing a render uses or
+ *          reports.  Its workspace (12 bytes per lattice point) is the handle's own and is given back after a call that needed
+ *          more than 64 MiB; such a call with device arrays waits for its emit work before it returns. ------------------------- */
+typedef struct sdfr_mesh_grid
+{
+	float origin[3];    /* lattice point (0,0,0) */
+	float cell;         /* edge length of a cell, > 0, finite */
+	int32_t nx, ny, nz; /* cells per axis, each 1..1024; (nx+1)(ny+1)(nz+1) <= 2^30 */
+	float iso;          /* the surface is distance == iso (0: the scene's surface) */
+} sdfr_mesh_grid;
+typedef struct sdfr_mesh_counts
+{
+	int64_t vertices, triangles;
+} sdfr_mesh_counts;
+int sdfr_mesh_extract(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions /*[v][3]*/,
+	float *normals /*[v][3] or NULL*/, uint32_t *indices /*[t][3]*/, sdfr_mesh_counts *counts /*host, required*/, int on_host);
+/* GPU time of the last sdfr_mesh_extract's stages in ms -- sample the lattice, classify + prefix sums, emit, normals -- if
+ * sdfr_set_profiling was on during it (else SDFR_ERR_INVALID_ARGUMENT); a stage that did not run (a counting call, no normals) is 0.
+ * Waits for that work. */
+int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4]);
+
 /* ---- two frames in flight inside one handle (no counterpart: D3D11's immediate context pipelines the reference's draws by itself)
  *      The end of a frame runs on a nearly empty chip -- the last waves finishing their tiles -- and only the NEXT frame can fill it
  *      (DESIGN.md 4.1).  With n = 2 sdfr_render alternates between two internal streams, each with a workspace of its own (the

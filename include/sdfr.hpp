@@ -121,6 +121,15 @@ public:
 		return handle && pushState(&camera) && sdfr_pick(handle, width, height, n, pixels_xy, hits, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// The loaded scene as a triangle mesh (sdfr_mesh_extract in sdfr.h: surface nets over `grid`), with this renderer's variables and
+	// time.  counts is always filled; the arrays only if both capacities suffice (capacities 0, arrays null: the counting call).
+	bool extractMesh(const sdfr_mesh_grid &grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals, uint32_t *indices,
+		sdfr_mesh_counts &counts, bool on_host = true)
+	{
+		return handle && pushState() &&
+			sdfr_mesh_extract(handle, &grid, vertex_capacity, triangle_capacity, positions, normals, indices, &counts, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// two frames in flight inside this renderer (sdfr_set_frames_in_flight): render into two targets in turn, sync() waits for both
 	bool setFramesInFlight(int n) { return sdfr_set_frames_in_flight(handle, n) == SDFR_OK; }
 	bool sync() { return sdfr_sync(handle) == SDFR_OK; }

@@ -71,6 +71,15 @@ class Stats(ctypes.Structure):
                 ("shade_launches", ctypes.c_uint32)]
 
 
+class MeshGrid(ctypes.Structure):  # sdfr_mesh_grid
+    _fields_ = [("origin", ctypes.c_float * 3), ("cell", ctypes.c_float), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32),
+                ("iso", ctypes.c_float)]
+
+
+class MeshCounts(ctypes.Structure):  # sdfr_mesh_counts
+    _fields_ = [("vertices", ctypes.c_int64), ("triangles", ctypes.c_int64)]
+
+
 # sdfr_hit (include/sdfr.h): the answer of a ray query or a pick, 48 bytes
 HIT_DTYPE = np.dtype([("t", np.float32), ("distance", np.float32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,)),
                       ("iterations", np.uint32), ("material_id", np.uint32), ("hit", np.int32), ("reserved", np.uint32)])
@@ -87,7 +96,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_set_strip_split", "sdfr_strip_buffer_pixels_split", "sdfr_strip_buffer_bytes_split", "sdfr_render_private_strips",
     "sdfr_comm_unique_id", "sdfr_comm_create", "sdfr_comm_create_all", "sdfr_comm_destroy", "sdfr_comm_close", "sdfr_comm_library_info", "sdfr_comm_rank", "sdfr_comm_world",
     "sdfr_comm_last_error", "sdfr_comm_selftest", "sdfr_render_gather", "sdfr_render_gather_all", "sdfr_set_launch_mode", "sdfr_set_step_shortcuts",
-    "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick",
+    "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick", "sdfr_mesh_extract", "sdfr_mesh_get_timings",
 ]
 
 _lib = None
@@ -186,6 +195,8 @@ def load_library():
     L.sdfr_query_distance.argtypes = [vp, i64, vp, vp, vp, ci]
     L.sdfr_query_rays.argtypes = [vp, i64, vp, vp, cf, vp, ci]
     L.sdfr_pick.argtypes = [vp, ci, ci, i64, vp, vp, ci]
+    L.sdfr_mesh_extract.argtypes = [vp, ctypes.POINTER(MeshGrid), i64, i64, vp, vp, vp, ctypes.POINTER(MeshCounts), ci]
+    L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
     L.sdfr_render_gather.argtypes = [vp, vp, ci, ci, vp, ci, ci]
     L.sdfr_render_gather_all.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, vp, ci, ci]
     _lib = L
@@ -545,6 +556,41 @@ class SDFRenderer:
         self._check(self._L.sdfr_pick(self._h, int(width), int(height), px.shape[0], px.ctypes.data_as(ctypes.c_void_p),
                                       hits.ctypes.data_as(ctypes.c_void_p), 1))
         return hits
+
+    # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
+    def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False):
+        """Surface nets over the lattice origin + (i, j, k) * cell, dims = (nx, ny, nz) cells: (positions [v, 3] float32, normals [v, 3]
+        float32 or None, indices [t, 3]) -- numpy arrays (indices uint32), or with device=True torch tensors on the renderer's GPU
+        (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call."""
+        grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
+        counts = MeshCounts()
+        self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), 0 if device else 1))
+        v, t = int(counts.vertices), int(counts.triangles)
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            pos = torch.empty((v, 3), dtype=torch.float32, device=dev)
+            nrm = torch.empty((v, 3), dtype=torch.float32, device=dev) if normals else None
+            idx = torch.empty((t, 3), dtype=torch.int32, device=dev)
+            ptr = lambda a: ctypes.c_void_p(a.data_ptr()) if a is not None and a.numel() else None  # noqa: E731
+        else:
+            pos = np.empty((v, 3), np.float32)
+            nrm = np.empty((v, 3), np.float32) if normals else None
+            idx = np.empty((t, 3), np.uint32)
+            ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+        if v:
+            again = MeshCounts()
+            self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), v, t, ptr(pos), ptr(nrm), ptr(idx), ctypes.byref(again), 0 if device else 1))
+            if (again.vertices, again.triangles) != (v, t):
+                raise SdfrError(-9, "the mesh changed between the counting and the filling call")
+        return pos, nrm, idx
+
+    def getMeshTimings(self):
+        """GPU ms of the last extractMesh's filling call, if setProfiling(True) was on: {sample, classify_scan, emit, normals}."""
+        ms = (ctypes.c_double * 4)()
+        self._check(self._L.sdfr_mesh_get_timings(self._h, ctypes.byref(ms)))
+        return dict(zip(("sample", "classify_scan", "emit", "normals"), [float(x) for x in ms]))
 
     def registerHostTarget(self, array):
         """Page-lock a numpy image that render(out=array) will fill every frame (sdfr_register_host_target); None

@@ -10,11 +10,15 @@
     python -m sdf_playground_amd.cli --scene-source my.scene.h --check              # compile only, no GPU
     python -m sdf_playground_amd.cli --scene-hlsl sdf_playground_amd/scenes/pendulum.hlsl --out p.png   # a scene in the reference's dialect
     python -m sdf_playground_amd.cli --scene-hlsl Engine/shader/scenes/sdf_scene_tree.hlsl --translate   # the generated C++
+    python -m sdf_playground_amd.cli --scene tree --mesh tree.obj --mesh-box -2 0 -2 2 4 2 --mesh-cell 0.02   # the scene as a triangle mesh
 
 --out writes the tone-mapped + bloomed LDR image (HDR::process, like the reference's window);
---out-hdr writes the raw float32 RGBA frame as .npy.  Needs a GPU.
+--out-hdr writes the raw float32 RGBA frame as .npy.  --mesh writes the scene's surface (distance == --mesh-iso) inside --mesh-box
+as a Wavefront OBJ with normals: surface nets on cells of edge --mesh-cell (SDFRenderer.extractMesh), at --time with the --set
+variables.  Needs a GPU.
 """
 import argparse
+import math
 import struct
 import sys
 import zlib
@@ -64,6 +68,18 @@ def parse_var_tags(text):
     return dict(sorted(out.items()))
 
 
+def mesh_grid_from_box(box, cell):
+    """--mesh-box x0 y0 z0 x1 y1 z1 and --mesh-cell -> (origin, dims): the lattice starts at the box's low corner and has as many
+    whole cells per axis as cover the box (at least one, at most 1024)."""
+    lo, hi = box[:3], box[3:]
+    if not cell > 0 or any(not h > l for l, h in zip(lo, hi)):
+        raise ValueError("--mesh-box needs x0 < x1, y0 < y1, z0 < z1 and --mesh-cell > 0")
+    dims = tuple(max(1, int(math.ceil((h - l) / cell - 1e-6))) for l, h in zip(lo, hi))
+    if max(dims) > 1024:
+        raise ValueError("--mesh-box / --mesh-cell give %dx%dx%d cells: at most 1024 per axis" % dims)
+    return tuple(lo), dims
+
+
 def _vec(s):
     v = tuple(float(x) for x in s.split(","))
     if len(v) != 3:
@@ -95,6 +111,10 @@ def main(argv=None):
     ap.add_argument("--out")
     ap.add_argument("--out-hdr")
     ap.add_argument("--parse-hlsl", metavar="FILE")
+    ap.add_argument("--mesh", metavar="OUT.obj", help="write the scene's surface inside --mesh-box as a Wavefront OBJ (needs --mesh-box and --mesh-cell)")
+    ap.add_argument("--mesh-box", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--mesh-cell", type=float, metavar="C", help="edge length of a cell")
+    ap.add_argument("--mesh-iso", type=float, default=0.0, metavar="V", help="the surface is distance == V (default 0)")
     a = ap.parse_args(argv)
 
     if a.parse_hlsl:
@@ -120,6 +140,14 @@ def main(argv=None):
         return 0 if ok else 1
     if not a.scene and not a.scene_source and not a.scene_hlsl:
         ap.error("--scene, --scene-source or --scene-hlsl is required")
+    mesh_grid = None
+    if a.mesh:
+        if a.mesh_box is None or a.mesh_cell is None:
+            ap.error("--mesh needs --mesh-box and --mesh-cell")
+        try:
+            mesh_grid = mesh_grid_from_box(a.mesh_box, a.mesh_cell)
+        except ValueError as e:
+            ap.error(str(e))
     r = sp.SDFRenderer(a.device)
     if a.scene_source or a.scene_hlsl:
         import os
@@ -153,6 +181,15 @@ def main(argv=None):
     cam.SetRoll(a.roll)
     r.setLimits(iter_count=a.iter_count, max_cost_default=a.max_cost)
     r.setParameters(a.time)
+    if mesh_grid:
+        from .obj import write_obj
+
+        pos, nrm, idx = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso)
+        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso))
+        print("%s: %d vertices, %d triangles (%dx%dx%d cells) -> %s" % ((a.scene, len(pos), len(idx)) + mesh_grid[1] + (a.mesh,)))
+        if not a.out and not a.out_hdr:
+            r.close()
+            return 0
     if a.out_hdr:
         np.save(a.out_hdr, r.render(cam, w, h))
     if a.out:

@@ -5,6 +5,7 @@
 // sdfr_kernels.hip; there is no CPU rendering path.
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
+#include "sdfr_mesh.h"
 #include "sdfr_query.h"
 
 #include <chrono>
@@ -278,7 +279,9 @@ void sdfr_destroy(sdfr_renderer *r)
 	release_second_lane(r); // waits for it, frees its workspace, counters, events and the two internal streams
 	release_lane(r->lane);
 	jit_unload(r->jit);
-	for (sdfr_device_buffer *b : {&r->stage, &r->pstat, &r->query, &r->wire, &r->post_flags}) b->release();
+	for (sdfr_device_buffer *b : {&r->stage, &r->pstat, &r->query, &r->mesh, &r->wire, &r->post_flags}) b->release();
+	for (hipEvent_t e : r->ev_mesh)
+		if (e) (void)hipEventDestroy(e);
 	if (r->pinned_host) (void)hipHostUnregister(r->pinned_host);
 	if (r->comm_stream) (void)hipStreamDestroy(r->comm_stream);
 	if (r->ev_strips) (void)hipEventDestroy(r->ev_strips);
@@ -766,6 +769,171 @@ int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const flo
 int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host)
 {
 	return guarded(r, [&]() -> int { return query_impl(r, QUERY_PICK, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, on_host); });
+}
+
+// sdfr_mesh_extract (the definition: include/sdfr.h; stages: sdfr_mesh.h, sdfr_mesh.hip).  Like a query it latches the frame into a
+// copy and writes nothing a render uses or reports.  Sample the lattice, classify and scan, read the two totals back; then, if the
+// capacities allow, emit vertices and indices and ask the point query for the normals at the vertices.
+static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals,
+	uint32_t *indices, sdfr_mesh_counts *counts, int on_host)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	if (!grid || !counts) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
+	if (on_host != 0 && on_host != 1) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
+	bool grid_ok = std::isfinite(grid->cell) && grid->cell > 0.f && std::isfinite(grid->iso);
+	for (int a = 0; a < 3; ++a) grid_ok = grid_ok && std::isfinite(grid->origin[a]);
+	for (int32_t n : {grid->nx, grid->ny, grid->nz}) grid_ok = grid_ok && n >= 1 && n <= 1024;
+	if (!grid_ok || (int64_t)(grid->nx + 1) * (grid->ny + 1) * (grid->nz + 1) > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad mesh grid");
+	if (vertex_capacity < 0 || triangle_capacity < 0) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "negative capacity");
+	if ((vertex_capacity > 0 && !positions) || (triangle_capacity > 0 && !indices)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null array with a capacity");
+	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
+	SDFR_HIP(hipSetDevice(r->device));
+	hipStream_t stream = r->lane.stream; // as the queries
+	FrameU U = r->U;
+	const int rc = latch_into(r, U, 1, 1, stream);
+	if (rc != SDFR_OK) return rc;
+
+	MeshGrid g;
+	for (int a = 0; a < 3; ++a) g.origin[a] = grid->origin[a];
+	g.cell = grid->cell;
+	g.n[0] = grid->nx;
+	g.n[1] = grid->ny;
+	g.n[2] = grid->nz;
+	g.iso = grid->iso;
+	const size_t points = mesh_point_count(g), cells = mesh_cell_count(g);
+	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+	const size_t b_lattice = up(points * 4), b_cells = up((cells + 1) * 4), b_points = up((points + 1) * 4);
+	const size_t b_sums = up((mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)) * 4);
+
+	for (hipEvent_t &e : r->ev_mesh)
+		if (!e) SDFR_HIP(hipEventCreate(&e));
+	hipEvent_t *ev = r->profiling ? r->ev_mesh : nullptr;
+	r->mesh_timed = 0;
+	// the last extraction's emit work (device arrays: enqueued, perhaps on the other lane's stream) still reads the workspace
+	SDFR_HIP(hipStreamWaitEvent(stream, r->ev_mesh[6], 0));
+	if (r->mesh.bytes < b_lattice + b_cells + b_points + b_sums) SDFR_HIP(hipEventSynchronize(r->ev_mesh[6]));
+	SDFR_HIP(r->mesh.reserve(b_lattice + b_cells + b_points + b_sums));
+	char *base = static_cast<char *>(r->mesh.ptr);
+	float *d_lattice = reinterpret_cast<float *>(base);
+	uint32_t *d_cells = reinterpret_cast<uint32_t *>(base + b_lattice), *d_points = reinterpret_cast<uint32_t *>(base + b_lattice + b_cells);
+	uint32_t *d_sums = reinterpret_cast<uint32_t *>(base + b_lattice + b_cells + b_points);
+	// a workspace past what a handle keeps is given back once the work that uses it is done
+	auto release_large = [&]() -> int {
+		if (r->mesh.bytes <= k_query_stage_keep) return SDFR_OK;
+		SDFR_HIP(hipStreamSynchronize(stream));
+		r->mesh.release();
+		return SDFR_OK;
+	};
+
+	LatticeArgs la;
+	for (int a = 0; a < 3; ++a) la.origin[a] = g.origin[a];
+	la.cell = g.cell;
+	la.px = g.n[0] + 1;
+	la.py = g.n[1] + 1;
+	la.pz = g.n[2] + 1;
+	static const int rows = [] { const char *e = getenv("SDFR_MESH_LATTICE_ROWS"); return e && atoi(e) != 0 ? 1 : 0; }(); // developer knob: the A/B
+	la.rows = rows;
+	la.out = d_lattice;
+	if (ev) SDFR_HIP(hipEventRecord(ev[0], stream));
+	if (r->scene == SDFR_SCENE_COUNT)
+	{
+		std::string err;
+		const JitQueryStatus js = jit_launch_query_lattice(r->jit, r->device, U, la, stream, err);
+		if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
+	}
+	else
+	{
+		const hipError_t e = launch_query_lattice(r->scene, U, la, stream);
+		if (e != hipSuccess) return hip_fail(r, e, "lattice launch");
+	}
+	if (ev) SDFR_HIP(hipEventRecord(ev[1], stream));
+	SDFR_HIP(launch_mesh_count(g, d_lattice, d_cells, d_points, d_sums, stream));
+	if (ev) SDFR_HIP(hipEventRecord(ev[2], stream));
+	uint32_t n_vertices = 0, n_quads = 0;
+	SDFR_HIP(hipMemcpyAsync(&n_vertices, d_cells + cells, 4, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipMemcpyAsync(&n_quads, d_points + points, 4, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+	if (ev) r->mesh_timed = 1;
+	counts->vertices = (int64_t)n_vertices;
+	counts->triangles = 2 * (int64_t)n_quads;
+	if (counts->vertices > vertex_capacity || counts->triangles > triangle_capacity || n_vertices == 0) return release_large();
+
+	const size_t V = n_vertices, T = (size_t)counts->triangles;
+	float *d_pos = positions, *d_nrm = normals;
+	uint32_t *d_idx = T ? indices : nullptr;
+	if (on_host)
+	{
+		const size_t b_pos = up(V * 12), b_nrm = normals ? up(V * 12) : 0;
+		SDFR_HIP(r->query.reserve(b_pos + b_nrm + up(T * 12))); // (host calls are synchronous: none is using the old one)
+		char *stage = static_cast<char *>(r->query.ptr);
+		d_pos = reinterpret_cast<float *>(stage);
+		d_nrm = normals ? reinterpret_cast<float *>(stage + b_pos) : nullptr;
+		d_idx = T ? reinterpret_cast<uint32_t *>(stage + b_pos + b_nrm) : nullptr;
+	}
+	if (ev) SDFR_HIP(hipEventRecord(ev[3], stream));
+	SDFR_HIP(launch_mesh_emit(g, d_lattice, d_cells, d_points, d_pos, d_idx, stream));
+	if (ev) SDFR_HIP(hipEventRecord(ev[4], stream));
+	if (d_nrm)
+	{
+		QueryArgs q = {};
+		q.kind = QUERY_POINTS;
+		q.n = (int)V; // <= 2^30
+		q.pos = d_pos;
+		q.distance = d_lattice; // the point query also writes its distances: into the lattice, which nothing reads any more
+		q.normals = d_nrm;
+		if (r->scene == SDFR_SCENE_COUNT)
+		{
+			std::string err;
+			const JitQueryStatus js = jit_launch_query(r->jit, r->device, U, q, stream, err);
+			if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
+		}
+		else
+		{
+			const hipError_t e = launch_query(r->scene, U, q, stream);
+			if (e != hipSuccess) return hip_fail(r, e, "query launch");
+		}
+		if (ev) SDFR_HIP(hipEventRecord(ev[5], stream));
+	}
+	if (ev) r->mesh_timed = d_nrm ? 2 : 3;
+	if (on_host)
+	{
+		SDFR_HIP(hipMemcpyAsync(positions, d_pos, V * 12, hipMemcpyDeviceToHost, stream));
+		if (normals) SDFR_HIP(hipMemcpyAsync(normals, d_nrm, V * 12, hipMemcpyDeviceToHost, stream));
+		if (T) SDFR_HIP(hipMemcpyAsync(indices, d_idx, T * 12, hipMemcpyDeviceToHost, stream));
+		SDFR_HIP(hipStreamSynchronize(stream));
+		if (r->query.bytes > k_query_stage_keep) r->query.release();
+	}
+	else
+		SDFR_HIP(hipEventRecord(r->ev_mesh[6], stream));
+	return release_large();
+}
+
+int sdfr_mesh_extract(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals,
+	uint32_t *indices, sdfr_mesh_counts *counts, int on_host)
+{
+	return guarded(r, [&]() -> int { return mesh_impl(r, grid, vertex_capacity, triangle_capacity, positions, normals, indices, counts, on_host); });
+}
+
+int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
+{
+	return guarded(r, [&]() -> int {
+		if (!r || !ms) return SDFR_ERR_INVALID_ARGUMENT;
+		if (!r->mesh_timed) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "the last sdfr_mesh_extract was not timed (sdfr_set_profiling)");
+		SDFR_HIP(hipSetDevice(r->device));
+		const int pairs[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+		const int have = r->mesh_timed == 1 ? 2 : r->mesh_timed == 2 ? 4 : 3;
+		for (int k = 0; k < 4; ++k)
+		{
+			float t = 0.f;
+			if (k < have)
+			{
+				SDFR_HIP(hipEventSynchronize(r->ev_mesh[pairs[k][1]]));
+				SDFR_HIP(hipEventElapsedTime(&t, r->ev_mesh[pairs[k][0]], r->ev_mesh[pairs[k][1]]));
+			}
+			ms[k] = t;
+		}
+		return SDFR_OK;
+	});
 }
 
 } // extern "C"

@@ -73,6 +73,12 @@ struct sdfr_renderer
 
 	sdfr_device_buffer stage, pstat; // staging image and pixel_stats of host-destination renders
 	sdfr_device_buffer query;        // staging of host-memory queries (sdfr_query_*, sdfr_pick): inputs and answers; kept up to 64 MiB
+	// sdfr_mesh_extract: the lattice's distances, the vertex index per cell, the quad offset per lattice point and the scans' block
+	// sums (the handle's own: never a lane's workspace); kept up to 64 MiB like `query`, which stages the arrays of a host extraction
+	sdfr_device_buffer mesh;
+	hipEvent_t ev_mesh[7] = {}; // made by the first extraction.  [6]: the end of the last one's device work, which the next one waits
+	                            // for before it reuses `mesh`; [0..5]: around its stages when profiling is on (sdfr_mesh_get_timings)
+	int mesh_timed = 0;         // 0: the last extraction was not timed; 1: up to its counts; 2: all four stages; 3: no normals asked
 	// sdfr_register_host_target: the caller's persistent host image, page-locked with the runtime
 	void *pinned_host = nullptr;
 	size_t pinned_bytes = 0;

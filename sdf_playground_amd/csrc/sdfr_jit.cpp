@@ -97,6 +97,8 @@ std::string jit_translation_unit(const std::string &scene_source, const std::vec
 		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_points_debug(QueryKernelArgs a) { query_points_kernel<Scene, true>(a); }\n";
 		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_rays(QueryKernelArgs a) { query_rays_kernel<Scene, false>(a); }\n";
 		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_rays_debug(QueryKernelArgs a) { query_rays_kernel<Scene, true>(a); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_lattice(LatticeKernelArgs a) { query_lattice_kernel<Scene, false>(a); }\n";
+		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_lattice_debug(LatticeKernelArgs a) { query_lattice_kernel<Scene, true>(a); }\n";
 	}
 	else
 	{
@@ -205,7 +207,8 @@ hipError_t jit_prepare(const JitScene &js, FrameU &U, hipStream_t stream)
 	return hipStreamSynchronize(stream);
 }
 
-JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const QueryArgs &q, hipStream_t stream, std::string &error)
+// compiles and loads the scene's query module if this is its first query
+static JitQueryStatus jit_query_module(JitScene &js, int device, std::string &error)
 {
 	if (!js.query_module)
 	{
@@ -223,15 +226,24 @@ JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const
 		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_points_debug, m, "sdfr_jit_query_points_debug");
 		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_rays, m, "sdfr_jit_query_rays");
 		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_rays_debug, m, "sdfr_jit_query_rays_debug");
+		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_lattice, m, "sdfr_jit_query_lattice");
+		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_lattice_debug, m, "sdfr_jit_query_lattice_debug");
 		if (e != hipSuccess)
 		{
 			error = std::string("loading the scene's query kernels failed: ") + hipGetErrorString(e);
 			if (m) (void)hipModuleUnload(m);
-			js.query_points = js.query_points_debug = js.query_rays = js.query_rays_debug = nullptr;
+			js.query_points = js.query_points_debug = js.query_rays = js.query_rays_debug = js.query_lattice = js.query_lattice_debug = nullptr;
 			return JIT_QUERY_HIP;
 		}
 		js.query_module = m;
 	}
+	return JIT_QUERY_OK;
+}
+
+JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const QueryArgs &q, hipStream_t stream, std::string &error)
+{
+	const JitQueryStatus ready = jit_query_module(js, device, error);
+	if (ready != JIT_QUERY_OK) return ready;
 	const bool dbg = frame_needs_debug(U);
 	hipFunction_t fn = q.kind == QUERY_POINTS ? (dbg ? js.query_points_debug : js.query_points) : (dbg ? js.query_rays_debug : js.query_rays);
 	const uint32_t bt = (uint32_t)pixel_block_threads();
@@ -244,6 +256,24 @@ JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const
 	if (e != hipSuccess)
 	{
 		error = std::string("query launch: ") + hipGetErrorString(e);
+		return JIT_QUERY_HIP;
+	}
+	return JIT_QUERY_OK;
+}
+
+JitQueryStatus jit_launch_query_lattice(JitScene &js, int device, const FrameU &U, const LatticeArgs &g, hipStream_t stream, std::string &error)
+{
+	const JitQueryStatus ready = jit_query_module(js, device, error);
+	if (ready != JIT_QUERY_OK) return ready;
+	LatticeKernelArgs a;
+	a.U = U;
+	a.g = g;
+	void *args[] = {&a};
+	const hipError_t e = hipModuleLaunchKernel(frame_needs_debug(U) ? js.query_lattice_debug : js.query_lattice, query_lattice_blocks(g), 1, 1,
+		(uint32_t)pixel_block_threads(), 1, 1, 0, stream, args, nullptr);
+	if (e != hipSuccess)
+	{
+		error = std::string("lattice launch: ") + hipGetErrorString(e);
 		return JIT_QUERY_HIP;
 	}
 	return JIT_QUERY_OK;

@@ -18,6 +18,7 @@ struct JitScene
 	std::vector<std::string> var_slots;
 	hipModule_t query_module = nullptr;
 	hipFunction_t query_points = nullptr, query_points_debug = nullptr, query_rays = nullptr, query_rays_debug = nullptr;
+	hipFunction_t query_lattice = nullptr, query_lattice_debug = nullptr;
 };
 
 // the translation unit compiled for a scene: variable macros, the scene text, the kernels (the pixel kernels, or with
@@ -40,6 +41,8 @@ hipError_t jit_prepare(const JitScene &js, FrameU &U, hipStream_t stream);
 // JIT_QUERY_COMPILE: the query module did not compile (the compiler's log in `error`); JIT_QUERY_HIP: it did not load or launch
 enum JitQueryStatus { JIT_QUERY_OK = 0, JIT_QUERY_COMPILE = 1, JIT_QUERY_HIP = 2 };
 JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const QueryArgs &q, hipStream_t stream, std::string &error);
+// the same for the distance query over a lattice (sdfr_query.h: LatticeArgs; sdfr_mesh_extract)
+JitQueryStatus jit_launch_query_lattice(JitScene &js, int device, const FrameU &U, const LatticeArgs &g, hipStream_t stream, std::string &error);
 
 hipError_t jit_launch_pixel(const JitScene &js, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode = 0);

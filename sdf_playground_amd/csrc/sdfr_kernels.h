@@ -40,7 +40,7 @@ struct SceneKernels
 // ... and a scene's query unit (sdfr_query_scene.hip)
 struct SceneQueryKernels
 {
-	const void *points[2], *rays[2];
+	const void *points[2], *rays[2], *lattice[2];
 };
 // a unit names its getter by its scene's index: scene_kernels_<index>(), scene_query_kernels_<index>()
 #define SDFR_CAT2(a, b) a##b
@@ -58,6 +58,20 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 // one query (sdfr_query.h) of a built-in scene: q.n > 0 items, every pointer device memory
 struct QueryArgs;
 hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream);
+// the distance query over a lattice (sdfr_query.h: LatticeArgs) of a built-in scene
+struct LatticeArgs;
+hipError_t launch_query_lattice(int scene, const FrameU &U, const LatticeArgs &g, hipStream_t stream);
+uint32_t query_lattice_blocks(const LatticeArgs &g); // blocks of one wave that cover the lattice in the mapping g.rows selects
+
+// Surface nets over a lattice of distances (sdfr_mesh.h, sdfr_mesh.hip), every pointer device memory.  launch_mesh_count: the vertex
+// flag per cell and the quad count per lattice point, then their exclusive prefix sums in place -- cell_vertex [cells + 1] and
+// point_quad [points + 1], whose last elements are the totals; sums: mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)
+// words of scratch.  launch_mesh_emit: positions [vertices][3] and, unless null (no quads), indices [2 * quads][3].
+struct MeshGrid;
+size_t mesh_scan_sum_words(size_t n);
+hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *cell_vertex, uint32_t *point_quad, uint32_t *sums, hipStream_t stream);
+hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
+	uint32_t *indices, hipStream_t stream);
 
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,
 	int priv_period, hipStream_t stream);

@@ -480,6 +480,24 @@ hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStrea
 	return hipGetLastError();
 }
 
+uint32_t query_lattice_blocks(const LatticeArgs &g)
+{
+	const uint32_t px = (uint32_t)g.px, py = (uint32_t)g.py, pz = (uint32_t)g.pz;
+	return g.rows ? (px * py * pz + 63u) / 64u : ((px + 3u) / 4u) * ((py + 3u) / 4u) * ((pz + 3u) / 4u);
+}
+
+hipError_t launch_query_lattice(int scene, const FrameU &U, const LatticeArgs &g, hipStream_t stream)
+{
+	const SceneQueryKernels *qk = scene_query_kernels(scene);
+	if (!qk) return hipErrorInvalidValue;
+	LatticeKernelArgs a;
+	a.U = U;
+	a.g = g;
+	void *args[] = {&a};
+	(void)hipLaunchKernel(qk->lattice[frame_needs_debug(U) ? 1 : 0], dim3(query_lattice_blocks(g)), dim3(SDFR_PIXEL_BLOCK), args, 0, stream);
+	return hipGetLastError();
+}
+
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,
 	int priv_period, hipStream_t stream)
 {

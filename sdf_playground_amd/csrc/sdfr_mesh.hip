@@ -1,0 +1,165 @@
+// sdfr_mesh.hip -- the scene-independent kernels of sdfr_mesh_extract (stage functions: sdfr_mesh.h): classify cells and lattice
+// points, exclusive prefix sums of the two flag arrays, emit vertices, emit indices.  The distances they read come from the
+// scene's lattice kernel (sdfr_query_kernel.h: query_lattice_kernel).
+//
+// The prefix sum is the plain three-phase one -- per-block totals, their scan (the same three phases again while they are more
+// than one block), then every block scans its own elements on top of its offset -- so no kernel ever waits for another workgroup:
+// the phases are separate launches of one stream.  The output order (cells and lattice points by linear index) is the scan's.
+#include "sdfr_kernels.h"
+#include "sdfr_mesh.h"
+
+namespace sdfr {
+
+#define SDFR_MESH_BLOCK 256 // threads of every kernel here = elements a scan block owns
+static_assert(SDFR_MESH_BLOCK % 64 == 0 && SDFR_MESH_BLOCK <= 1024, "whole waves");
+
+// exclusive prefix sum of `v` over the block's threads and the block's total: wave64 shuffles inside a wave, LDS across the waves
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t &total)
+{
+	__shared__ uint32_t wave_sum[SDFR_MESH_BLOCK / 64];
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint32_t incl = v;
+	for (int d = 1; d < 64; d <<= 1)
+	{
+		const uint32_t up = __shfl_up(incl, d, 64);
+		if (lane >= (uint32_t)d) incl += up;
+	}
+	if (lane == 63u) wave_sum[wave] = incl;
+	__syncthreads();
+	uint32_t before = 0u, all = 0u;
+	for (uint32_t w = 0; w < SDFR_MESH_BLOCK / 64; ++w)
+	{
+		const uint32_t s = wave_sum[w];
+		if (w < wave) before += s;
+		all += s;
+	}
+	total = all;
+	return before + incl - v;
+}
+
+// phase 1: sums[b] = total of block b's elements
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_scan_reduce(const uint32_t *__restrict__ data, uint32_t n, uint32_t *__restrict__ sums)
+{
+	const uint32_t i = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	uint32_t total;
+	(void)block_exclusive_scan(i < n ? data[i] : 0u, total);
+	if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// phase 3 (offsets: the scanned block totals), and the whole scan of n <= SDFR_MESH_BLOCK elements (offsets null)
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_scan_down(uint32_t *__restrict__ data, uint32_t n, const uint32_t *__restrict__ offsets)
+{
+	const uint32_t i = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	uint32_t total;
+	const uint32_t ex = block_exclusive_scan(i < n ? data[i] : 0u, total);
+	if (i < n) data[i] = ex + (offsets ? offsets[blockIdx.x] : 0u);
+}
+
+size_t mesh_scan_sum_words(size_t n)
+{
+	size_t words = 0;
+	while (n > SDFR_MESH_BLOCK)
+	{
+		n = (n + SDFR_MESH_BLOCK - 1) / SDFR_MESH_BLOCK;
+		words += n;
+	}
+	return words;
+}
+
+// data [n] -> its exclusive prefix sum, in place; sums: mesh_scan_sum_words(n) words
+static void scan_exclusive(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream)
+{
+	if (n <= SDFR_MESH_BLOCK)
+	{
+		hipLaunchKernelGGL(k_mesh_scan_down, dim3(1), dim3(SDFR_MESH_BLOCK), 0, stream, data, n, (const uint32_t *)nullptr);
+		return;
+	}
+	const uint32_t blocks = (n + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK;
+	hipLaunchKernelGGL(k_mesh_scan_reduce, dim3(blocks), dim3(SDFR_MESH_BLOCK), 0, stream, (const uint32_t *)data, n, sums);
+	scan_exclusive(sums, blocks, sums + blocks, stream);
+	hipLaunchKernelGGL(k_mesh_scan_down, dim3(blocks), dim3(SDFR_MESH_BLOCK), 0, stream, data, n, (const uint32_t *)sums);
+}
+
+// lattice point p -> (i, j, k); p < 2^30
+__device__ __forceinline__ void point_coords(const MeshGrid &g, uint32_t p, int &i, int &j, int &k)
+{
+	const uint32_t px = (uint32_t)(g.n[0] + 1), py = (uint32_t)(g.n[1] + 1);
+	const uint32_t row = p / px;
+	i = (int)(p - row * px);
+	k = (int)(row / py);
+	j = (int)(row - (uint32_t)k * py);
+}
+
+// one lane per lattice point: its quad count, and the vertex flag of the cell whose lowest corner it is; the element after the
+// last of each array is the 0 whose prefix sum is the total
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_classify(MeshGrid g, const float *__restrict__ lattice, uint32_t *__restrict__ cell_vertex,
+	uint32_t *__restrict__ point_quad)
+{
+	const uint32_t p = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	const uint32_t points = mesh_point_count(g);
+	if (p > points) return;
+	if (p == points)
+	{
+		point_quad[points] = 0u;
+		cell_vertex[mesh_cell_count(g)] = 0u;
+		return;
+	}
+	int i, j, k;
+	point_coords(g, p, i, j, k);
+	point_quad[p] = mesh_point_quads(g, lattice, i, j, k);
+	if (i < g.n[0] && j < g.n[1] && k < g.n[2]) cell_vertex[mesh_cell_index(g, i, j, k)] = mesh_cell_active(g, lattice, i, j, k);
+}
+
+// one lane per cell: an active cell (its scanned index differs from the next cell's) writes its vertex
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_emit_vertices(MeshGrid g, const float *__restrict__ lattice, const uint32_t *__restrict__ cell_vertex,
+	float *__restrict__ positions)
+{
+	const uint32_t c = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	if (c >= mesh_cell_count(g)) return;
+	const uint32_t v = cell_vertex[c];
+	if (cell_vertex[c + 1u] == v) return;
+	const uint32_t nx = (uint32_t)g.n[0], ny = (uint32_t)g.n[1];
+	const uint32_t row = c / nx, k = row / ny;
+	float pos[3];
+	mesh_cell_vertex(g, lattice, (int)(c - row * nx), (int)(row - k * ny), (int)k, pos);
+	float *o = positions + (size_t)3 * v;
+	o[0] = pos[0];
+	o[1] = pos[1];
+	o[2] = pos[2];
+}
+
+// one lane per lattice point: a point with quads writes their triangles
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_emit_indices(MeshGrid g, const float *__restrict__ lattice, const uint32_t *__restrict__ cell_vertex,
+	const uint32_t *__restrict__ point_quad, uint32_t *__restrict__ indices)
+{
+	const uint32_t p = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	if (p >= mesh_point_count(g)) return;
+	const uint32_t q = point_quad[p];
+	if (point_quad[p + 1u] == q) return;
+	int i, j, k;
+	point_coords(g, p, i, j, k);
+	mesh_point_emit(g, lattice, cell_vertex, i, j, k, q, indices);
+}
+
+hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *cell_vertex, uint32_t *point_quad, uint32_t *sums, hipStream_t stream)
+{
+	const uint32_t points = mesh_point_count(g), cells = mesh_cell_count(g);
+	hipLaunchKernelGGL(k_mesh_classify, dim3(points / SDFR_MESH_BLOCK + 1u), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice, cell_vertex, point_quad);
+	scan_exclusive(cell_vertex, cells + 1u, sums, stream);
+	scan_exclusive(point_quad, points + 1u, sums + mesh_scan_sum_words((size_t)cells + 1), stream);
+	return hipGetLastError();
+}
+
+hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
+	uint32_t *indices, hipStream_t stream)
+{
+	const uint32_t points = mesh_point_count(g), cells = mesh_cell_count(g);
+	hipLaunchKernelGGL(k_mesh_emit_vertices, dim3((cells + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice, cell_vertex,
+		positions);
+	if (indices)
+		hipLaunchKernelGGL(k_mesh_emit_indices, dim3((points + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice,
+			cell_vertex, point_quad, indices);
+	return hipGetLastError();
+}
+
+} // namespace sdfr

@@ -29,6 +29,23 @@ struct QueryKernelArgs
 	QueryArgs q;
 };
 
+// One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
+// computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
+// out[i + px * (j + py * k)].  px * py * pz <= 2^30.
+struct LatticeArgs
+{
+	float origin[3];
+	float cell;
+	int32_t px, py, pz; // lattice points per axis
+	int32_t rows;       // 0: a wave owns a 4 x 4 x 4 brick of points; 1: 64 consecutive points of a row (the A/B of DESIGN.md 4.6)
+	float *out;
+};
+struct LatticeKernelArgs
+{
+	FrameU U;
+	LatticeArgs g;
+};
+
 // map_geometry at the sample of a query: a scene that reads the march state (GeoStep) gets the running camera_distance and
 // the ray's offsets, every other scene (p, dir) as in the pixel pipeline
 template <class Scene, bool DBG>

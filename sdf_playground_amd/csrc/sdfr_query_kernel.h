@@ -64,4 +64,37 @@ __device__ __forceinline__ void query_rays_kernel(const QueryKernelArgs &a)
 		for (int k = 0; k < QUERY_HIT_WORDS; ++k) out[k] = rec[k];
 }
 
+// The distance query over a lattice (LatticeArgs): one wave per block, one point per lane.  A wave owns a 4 x 4 x 4 brick of points,
+// so that its lanes stay within 3 cells of each other and the scenes' wave-level branches (bounding volumes, cell lookups) stay
+// coherent; its stores are runs of 4 floats.  rows = 1 maps 64 consecutive points of the linear index instead (coalesced stores,
+// a wave 64 cells long).  Lanes past the lattice's ragged edges leave.
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_lattice_kernel(const LatticeKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a brick is 64 points");
+	const LatticeArgs &g = a.g;
+	const uint32_t px = (uint32_t)g.px, py = (uint32_t)g.py, pz = (uint32_t)g.pz, lane = threadIdx.x;
+	uint32_t i, j, k;
+	if (g.rows)
+	{
+		const uint32_t p = blockIdx.x * 64u + lane; // < 2^30 + 64
+		const uint32_t row = p / px;
+		i = p - row * px;
+		k = row / py;
+		j = row - k * py;
+	}
+	else
+	{
+		const uint32_t bx = (px + 3u) >> 2, by = (py + 3u) >> 2;
+		const uint32_t brow = blockIdx.x / bx;
+		const uint32_t bk = brow / by;
+		i = (blockIdx.x - brow * bx) * 4u + (lane & 3u);
+		j = (brow - bk * by) * 4u + ((lane >> 2) & 3u);
+		k = bk * 4u + (lane >> 4);
+	}
+	if (i >= px || j >= py || k >= pz) return;
+	const vec3 p = V3(g.origin[0] + (float)i * g.cell, g.origin[1] + (float)j * g.cell, g.origin[2] + (float)k * g.cell);
+	g.out[i + px * (j + py * k)] = query_point<Scene, DBG>(a.U, p, nullptr); // (the index is < 2^30)
+}
+
 } // namespace sdfr

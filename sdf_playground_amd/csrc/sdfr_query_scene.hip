@@ -1,4 +1,4 @@
-// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays: sdfr_query_kernel.h) of ONE scene, compiled
+// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice: sdfr_query_kernel.h) of ONE scene, compiled
 // once per scene with -DSDFR_SCENE=<index> and the scene's code-generation options (sdf_playground_amd/buildlib.py), like
 // sdfr_kernels_scene.hip.  They live in a unit of their own: a second caller of the shared inline stages in the pixel kernels'
 // unit could change the inliner's decisions there, and with them k_pixel's code.
@@ -31,6 +31,13 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_rays(QueryKernelArgs a)
 	query_rays_kernel<Scene, DBG>(a);
 }
 
+// the distance query over a lattice of points made from their indices (sdfr_mesh_extract)
+template <class Scene, bool DBG>
+__global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_lattice(LatticeKernelArgs a)
+{
+	query_lattice_kernel<Scene, DBG>(a);
+}
+
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
 // what this unit exports (scene_query_kernels, launch_query: sdfr_kernels.hip)
@@ -43,6 +50,8 @@ const SceneQueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
 		k.rays[1] = (const void *)k_query_rays<UnitScene, true>;
 		k.points[0] = (const void *)k_query_points<UnitScene, false>;
 		k.rays[0] = (const void *)k_query_rays<UnitScene, false>;
+		k.lattice[1] = (const void *)k_query_lattice<UnitScene, true>;
+		k.lattice[0] = (const void *)k_query_lattice<UnitScene, false>;
 		return k;
 	}();
 	return &k;
