@@ -201,6 +201,35 @@ typedef enum sdfr_format
  * evaluations, hits}.  Replaces SDFRenderer::render (SDFRenderer.cpp:65-107). */
 int sdfr_render(sdfr_renderer *r, int width, int height, void *out, int format, int out_on_host, uint32_t *pixel_stats);
 
+/* ---- anti-aliasing: supersample and resolve on the device (no counterpart: the reference shoots one ray through each pixel's
+ *      centre, pshader_sdf.hlsl:263-267).  K = factor, one of 1, 2, 4, 8.
+ *
+ *      Let S[Y][X][c], 0 <= Y < K * height, 0 <= X < K * width, be the RGBA32F frame sdfr_render produces at width K * width, height
+ *      K * height with the handle's current state: the sub-samples' ray offsets (ddx = 2 / (K * width), ddy = -2 / (K * height)) are
+ *      those of that larger frame, which is what supersampling means for the scenes' footprint-filtered materials.  With
+ *        box2(A)[y][x][c] = ((A[2y][2x][c] + A[2y][2x+1][c]) + (A[2y+1][2x][c] + A[2y+1][2x+1][c])) * 0.25f
+ *      in fp32 and in exactly that order, the image is box2 applied log2 K times to S; K = 1 is S itself.  (A pyramid on purpose:
+ *      factor 4 is factor 2 of factor 2.)  S is never held whole: it is rendered and resolved in passes over the strip machinery
+ *      below, each pass in a buffer of the handle's own that is kept between calls and freed by sdfr_destroy.
+ *        - alpha is averaged like the colours.  It becomes the share of a pixel's sub-samples that carry the tone-map flag, which is
+ *          the weight sdfr_postprocess blends the tone-mapped colour with already: an anti-aliased RGBA16F frame goes through it as is.
+ *        - format: SDFR_RGBA32F or SDFR_RGBA16F.  The 16F image is the fp32 result converted once, round to nearest even, as a direct
+ *          16F render converts its fp32 result -- not an average of halves.  The strip formats: SDFR_ERR_INVALID_ARGUMENT.
+ *        - pixel_stats (optional, same memory space as `out`): [height][width][3] uint32, the sums over a pixel's K^2 sub-samples of
+ *          {rays, march evaluations, hits}.
+ *        - SDFR_ERR_INVALID_ARGUMENT: a factor outside {1, 2, 4, 8}, width or height below 1, K^2 * width * height above 2^30 (the
+ *          frame cap of sdfr_render applied to S), a NULL `out`, a bad out_on_host.  SDFR_ERR_NO_SCENE: no scene.  Nothing is written
+ *          on error.
+ *        - out_on_host = 1 returns with the image there; out_on_host = 0 enqueues every pass on the handle's stream and returns: no
+ *          host synchronisation between passes.  With two frames in flight the call runs on the lane of the frame submitted last, as
+ *          sdfr_render_strips and sdfr_postprocess do.
+ *        - sdfr_get_stats / sdfr_get_timings afterwards report the whole anti-aliased frame: pixels = K^2 * width * height; rays,
+ *          evaluations and hits summed over all passes; ms_gpu from the first pass's start to the last resolve's end.  With
+ *          sdfr_set_profiling the timings add "draw: resolve", the time inside the resolve launches.
+ *        - the handle's strip split (sdfr_set_strip_split) is ignored, as a full frame ignores it.  Built-in and run-time scenes,
+ *          both schedules. */
+int sdfr_render_aa(sdfr_renderer *r, int width, int height, int factor, void *out, int format, int out_on_host, uint32_t *pixel_stats);
+
 /* A host that renders into host memory (out_on_host = 1) every frame: register the image buffer once.  It is
  * page-locked with the HIP runtime, so the copy of a frame runs at PCIe speed (3840x2160 RGBA32F: ~3 ms) instead
  * of through pageable staging (~12 ms).  The caller keeps the buffer alive and at this address until it registers

@@ -105,6 +105,15 @@ public:
 		return sdfr_render(handle, width, height, target, format, target_on_host ? 1 : 0, nullptr) == SDFR_OK;
 	}
 
+	// the same anti-aliased (sdfr_render_aa in sdfr.h): factor x factor sub-samples per pixel, factor one of 1, 2, 4, 8, rendered and
+	// resolved on the device in passes; pixel_stats (optional, where the target is): [height][width][3] summed counters
+	bool renderAA(const Camera &camera, int width, int height, int factor, void *target, int format = SDFR_RGBA32F, bool target_on_host = false,
+		uint32_t *pixel_stats = nullptr)
+	{
+		if (!handle || !pushState(&camera)) return false;
+		return sdfr_render_aa(handle, width, height, factor, target, format, target_on_host ? 1 : 0, pixel_stats) == SDFR_OK;
+	}
+
 	// Questions put to the loaded scene with this renderer's variables and time (sdfr_query_distance, sdfr_query_rays, sdfr_pick in
 	// sdfr.h); pick also takes the camera the pixels belong to.  on_host: every pointer is host memory and the answers are there
 	// when the call returns; else device memory, enqueued.  Points and rays [n][3], pixels [n][2].

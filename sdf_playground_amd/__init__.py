@@ -97,6 +97,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_comm_unique_id", "sdfr_comm_create", "sdfr_comm_create_all", "sdfr_comm_destroy", "sdfr_comm_close", "sdfr_comm_library_info", "sdfr_comm_rank", "sdfr_comm_world",
     "sdfr_comm_last_error", "sdfr_comm_selftest", "sdfr_render_gather", "sdfr_render_gather_all", "sdfr_set_launch_mode", "sdfr_set_step_shortcuts",
     "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick", "sdfr_mesh_extract", "sdfr_mesh_get_timings",
+    "sdfr_render_aa",
 ]
 
 _lib = None
@@ -169,6 +170,7 @@ def load_library():
     L.sdfr_strip_buffer_bytes_split.restype = ctypes.c_int64
     L.sdfr_render_private_strips.argtypes = [vp, ci, ci, vp, ci]
     L.sdfr_render.argtypes = [vp, ci, ci, vp, ci, ci, vp]
+    L.sdfr_render_aa.argtypes = [vp, ci, ci, ci, vp, ci, ci, vp]
     L.sdfr_render_strips.argtypes = [vp, ci, ci, ci, ci, vp, ci]
     L.sdfr_assemble_strips.argtypes = [vp, ci, ci, ci, vp, vp, ci]
     L.sdfr_sync.argtypes = [vp]
@@ -474,6 +476,28 @@ class SDFRenderer:
         st = np.zeros((height, width, 3), np.uint32) if pixel_stats else None
         self._check(self._L.sdfr_render(self._h, width, height, img.ctypes.data_as(ctypes.c_void_p), fmt, 1,
                                         st.ctypes.data_as(ctypes.c_void_p) if pixel_stats else None))
+        return (img, st) if pixel_stats else img
+
+    def renderAA(self, camera=None, width=1200, height=800, factor=2, out=None, fmt=RGBA32F, pixel_stats=False):
+        """Renders one anti-aliased frame (sdfr_render_aa): factor x factor sub-samples per pixel (factor 1, 2, 4 or 8), rendered and
+        box-filtered on the GPU in passes of bounded memory.  Arguments and results as render(); alpha comes back as the share of a
+        pixel's sub-samples that carry the tone-map flag, pixel_stats as the sums over them."""
+        if camera is not None:
+            self.setCamera(camera)
+        if out is not None and hasattr(out, "data_ptr"):
+            assert out.is_cuda and out.is_contiguous() and out.numel() == width * height * 4
+            pst = None
+            if pixel_stats is not False and pixel_stats is not None:
+                assert hasattr(pixel_stats, "data_ptr") and pixel_stats.is_cuda and pixel_stats.is_contiguous()
+                assert pixel_stats.numel() == width * height * 3 and pixel_stats.element_size() == 4
+                pst = ctypes.c_void_p(pixel_stats.data_ptr())
+            self._check(self._L.sdfr_render_aa(self._h, width, height, factor, ctypes.c_void_p(out.data_ptr()), fmt, 0, pst))
+            return out
+        dt = np.float32 if fmt == RGBA32F else np.float16
+        img = np.zeros((height, width, 4), dt) if out is None else out
+        st = np.zeros((height, width, 3), np.uint32) if pixel_stats else None
+        self._check(self._L.sdfr_render_aa(self._h, width, height, factor, img.ctypes.data_as(ctypes.c_void_p), fmt, 1,
+                                           st.ctypes.data_as(ctypes.c_void_p) if pixel_stats else None))
         return (img, st) if pixel_stats else img
 
     # ---- questions put to the loaded scene (sdfr_query_distance / sdfr_query_rays / sdfr_pick; DESIGN.md "Queries") -------------

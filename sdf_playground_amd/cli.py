@@ -10,6 +10,7 @@
     python -m sdf_playground_amd.cli --scene-source my.scene.h --check              # compile only, no GPU
     python -m sdf_playground_amd.cli --scene-hlsl sdf_playground_amd/scenes/pendulum.hlsl --out p.png   # a scene in the reference's dialect
     python -m sdf_playground_amd.cli --scene-hlsl Engine/shader/scenes/sdf_scene_tree.hlsl --translate   # the generated C++
+    python -m sdf_playground_amd.cli --scene labyrinth --aa 4 --out clean.png        # 4 x 4 sub-samples per pixel, resolved on the GPU
     python -m sdf_playground_amd.cli --scene tree --mesh tree.obj --mesh-box -2 0 -2 2 4 2 --mesh-cell 0.02   # the scene as a triangle mesh
 
 --out writes the tone-mapped + bloomed LDR image (HDR::process, like the reference's window);
@@ -87,7 +88,7 @@ def _vec(s):
     return v
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser(prog="sdf_playground_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--list-scenes", action="store_true")
     ap.add_argument("--scene")
@@ -110,11 +111,25 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out")
     ap.add_argument("--out-hdr")
+    ap.add_argument("--aa", type=int, choices=(1, 2, 4, 8), default=1, metavar="K", help="anti-aliasing for --out / --out-hdr: K x K sub-samples per pixel, "
+                    "box-filtered on the GPU (SDFRenderer.renderAA); 1, 2, 4 or 8; default 1: one ray per pixel")
     ap.add_argument("--parse-hlsl", metavar="FILE")
     ap.add_argument("--mesh", metavar="OUT.obj", help="write the scene's surface inside --mesh-box as a Wavefront OBJ (needs --mesh-box and --mesh-cell)")
     ap.add_argument("--mesh-box", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     ap.add_argument("--mesh-cell", type=float, metavar="C", help="edge length of a cell")
     ap.add_argument("--mesh-iso", type=float, default=0.0, metavar="V", help="the surface is distance == V (default 0)")
+    return ap
+
+
+def render_call(renderer, aa):
+    """what --out / --out-hdr call for --aa K: render itself for K = 1 (today's path), else renderAA with that factor"""
+    if aa == 1:
+        return renderer.render
+    return lambda *args, **kw: renderer.renderAA(*args, factor=aa, **kw)
+
+
+def main(argv=None):
+    ap = make_parser()
     a = ap.parse_args(argv)
 
     if a.parse_hlsl:
@@ -191,11 +206,11 @@ def main(argv=None):
             r.close()
             return 0
     if a.out_hdr:
-        np.save(a.out_hdr, r.render(cam, w, h))
+        np.save(a.out_hdr, render_call(r, a.aa)(cam, w, h))
     if a.out:
         hdr = sp.HDR(r)
         hdr.init(w, h)
-        r.render(cam, w, h, out=hdr.getRenderTarget(), fmt=sp.RGBA16F)
+        render_call(r, a.aa)(cam, w, h, out=hdr.getRenderTarget(), fmt=sp.RGBA16F)
         write_png(a.out, hdr.process().cpu().numpy())
     s = r.getStats()
     print("%s %dx%d: %.3f ms, %d rays (%.1f Mrays/s)" % (a.scene, w, h, s.ms_gpu, s.rays, s.rays / max(s.ms_gpu, 1e-9) / 1e3))

@@ -3,10 +3,12 @@
 // Host logic only: handle state (scene, variable table, camera, limits), per-frame uniform
 // preparation, device buffers and launches.  All pixels are produced by the HIP kernels in
 // sdfr_kernels.hip; there is no CPU rendering path.
+#include "sdfr_aa_plan.h"
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
 #include "sdfr_mesh.h"
 #include "sdfr_query.h"
+#include "sdfr_resolve.h"
 
 #include <chrono>
 #include <cmath>
@@ -279,7 +281,9 @@ void sdfr_destroy(sdfr_renderer *r)
 	release_second_lane(r); // waits for it, frees its workspace, counters, events and the two internal streams
 	release_lane(r->lane);
 	jit_unload(r->jit);
-	for (sdfr_device_buffer *b : {&r->stage, &r->pstat, &r->query, &r->mesh, &r->wire, &r->post_flags}) b->release();
+	for (sdfr_device_buffer *b : {&r->stage, &r->pstat, &r->query, &r->mesh, &r->wire, &r->post_flags, &r->aa_color, &r->aa_stats, &r->aa_totals}) b->release();
+	if (r->ev_aa_done) (void)hipEventDestroy(r->ev_aa_done);
+	for (hipEvent_t e : r->ev_aa) (void)hipEventDestroy(e);
 	for (hipEvent_t e : r->ev_mesh)
 		if (e) (void)hipEventDestroy(e);
 	if (r->pinned_host) (void)hipHostUnregister(r->pinned_host);
@@ -944,6 +948,7 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 	int rc = check_render(r, width, height, rank, world, out, format, mode);
 	if (rc != SDFR_OK || (mode == RENDER_PRIVATE && r->priv_count == 0)) return rc; // (no private strips: nothing to render)
 	if (!totals) totals = r->lane.d_totals;
+	r->aa_timed_passes = 0; // (sdfr_render_aa sets it once its passes are through)
 	SDFR_HIP(hipSetDevice(r->device));
 	const auto t_setup = std::chrono::steady_clock::now();
 	rc = latch_frame(r, width, height);
@@ -1017,7 +1022,127 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 	return SDFR_OK;
 }
 
+// sdfr_render_aa (the definition: include/sdfr.h; the plan: sdfr_aa_plan.h; the kernel: sdfr_resolve.hip).  The supersampled frame
+// S is rendered pass by pass as strip launches into the handle's compact buffer, and every pass is resolved into its rows of the
+// image before the next one reuses the buffer: one stream, no host synchronisation between passes.
+static int render_aa_impl(sdfr_renderer *r, int width, int height, int factor, void *out, int format, int out_on_host, uint32_t *pixel_stats)
+{
+	if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
+	if (format != SDFR_RGBA32F && format != SDFR_RGBA16F) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
+	if (aa_factor_log2(factor) < 0) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "factor must be 1, 2, 4 or 8");
+	if (out_on_host != 0 && out_on_host != 1) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "out_on_host must be 0 or 1");
+	if (width < 1 || height < 1 || (int64_t)width * factor * factor > ((int64_t)1 << 30) / height) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
+	SDFR_HIP(hipSetDevice(r->device));
+
+	unsigned long long budget = SDFR_AA_DEFAULT_BUDGET;
+	if (const char *e = getenv("SDFR_AA_BUDGET_BYTES")) // developer knob, read on every call: bytes of one pass's compact colour buffer
+	{
+		const unsigned long long v = strtoull(e, nullptr, 10);
+		if (v > 0) budget = v;
+	}
+	const AaPlan plan = plan_aa(width, height, factor, budget);
+	const size_t pixels = (size_t)width * height;
+	hipStream_t stream = r->lane.stream; // the handle's stream, or the lane of the frame submitted last
+
+	if (!r->ev_aa_done) SDFR_HIP(hipEventCreate(&r->ev_aa_done));
+	// the last call's passes (device destination: enqueued, perhaps on the other lane's stream) still use the buffers
+	SDFR_HIP(hipStreamWaitEvent(stream, r->ev_aa_done, 0));
+	const size_t color_bytes = plan.pass_pixels * 16, stats_bytes = pixel_stats ? plan.pass_pixels * 12 : 0;
+	if (r->aa_color.bytes < color_bytes || r->aa_stats.bytes < stats_bytes || !r->aa_totals.ptr)
+	{
+		const int rc = sync_lanes(r); // before a buffer in use is replaced
+		if (rc != SDFR_OK) return rc;
+		SDFR_HIP(r->aa_color.reserve(color_bytes));
+		SDFR_HIP(r->aa_stats.reserve(stats_bytes));
+		SDFR_HIP(r->aa_totals.reserve(sizeof(RenderTotals)));
+	}
+	void *d_out = out;
+	uint32_t *d_pstat = pixel_stats;
+	if (out_on_host)
+	{
+		SDFR_HIP(r->stage.reserve(image_bytes(pixels, format)));
+		d_out = r->stage.ptr;
+		if (pixel_stats)
+		{
+			SDFR_HIP(r->pstat.reserve(pixels * 12));
+			d_pstat = static_cast<uint32_t *>(r->pstat.ptr);
+		}
+	}
+	const bool timed = r->profiling;
+	while (timed && r->ev_aa.size() < 2 * (size_t)plan.passes)
+	{
+		hipEvent_t e = nullptr;
+		SDFR_HIP(hipEventCreate(&e));
+		r->ev_aa.push_back(e);
+	}
+
+	const int tile_w_log2 = r->tile_w_log2 ? r->tile_w_log2 : scene_tile_w_log2(r->scene);
+	const int split_count = r->priv_count, split_period = r->priv_period; // ignored, as a full frame ignores it
+	r->priv_count = 0;
+	r->priv_period = 1;
+	int rc = SDFR_OK;
+	SDFR_HIP(hipEventRecord(r->lane.ev_begin, stream));
+	for (uint32_t p = 0; p < plan.passes && rc == SDFR_OK; ++p)
+	{
+		rc = render_impl(r, plan.s_width, plan.s_height, (int)p, (int)plan.passes, r->aa_color.ptr, SDFR_RGBA32F, 0,
+			pixel_stats ? static_cast<uint32_t *>(r->aa_stats.ptr) : nullptr, RENDER_STRIPS, static_cast<RenderTotals *>(r->aa_totals.ptr), true);
+		if (rc != SDFR_OK) break;
+		ResolveArgs a = {};
+		a.color = static_cast<const float *>(r->aa_color.ptr);
+		a.stats = pixel_stats ? static_cast<const uint32_t *>(r->aa_stats.ptr) : nullptr;
+		a.out = d_out;
+		a.out_stats = d_pstat;
+		a.rm = aa_pass_row_map(plan, p, tile_w_log2);
+		a.s_width = plan.s_width;
+		a.width = width;
+		a.height = height;
+		a.factor_log2 = plan.factor_log2;
+		a.format = format;
+		a.local_strips = aa_pass_strips(plan, p);
+		a.pass_totals = static_cast<const RenderTotals *>(r->aa_totals.ptr);
+		a.frame_totals = r->lane.d_totals;
+		a.first_pass = p == 0;
+		hipError_t e = timed ? hipEventRecord(r->ev_aa[2 * p], stream) : hipSuccess;
+		if (e == hipSuccess) e = launch_resolve(a, stream);
+		if (e == hipSuccess && timed) e = hipEventRecord(r->ev_aa[2 * p + 1], stream);
+		if (e != hipSuccess) rc = hip_fail(r, e, "resolve launch");
+	}
+	r->priv_count = split_count;
+	r->priv_period = split_period;
+	// (also after a pass that failed: what was enqueued is ordered before the next call's use of the buffers)
+	(void)hipEventRecord(r->lane.ev_end, stream);
+	(void)hipEventRecord(r->ev_aa_done, stream);
+	r->lane.totals_parts = 1;
+	if (rc != SDFR_OK) return rc;
+	r->aa_timed_passes = timed ? (int)plan.passes : 0;
+	if (out_on_host)
+	{
+		SDFR_HIP(hipMemcpyAsync(out, d_out, image_bytes(pixels, format), hipMemcpyDeviceToHost, stream));
+		if (pixel_stats) SDFR_HIP(hipMemcpyAsync(pixel_stats, d_pstat, pixels * 12, hipMemcpyDeviceToHost, stream));
+		SDFR_HIP(hipStreamSynchronize(stream));
+	}
+	else if (r->frames_in_flight == 2)
+	{
+		// the lane now also writes this image: the next frame, on the other lane, must see it in the range it checks for overlap
+		auto widen = [](const char *&lo, const char *&hi, const char *a, const char *b) {
+			if (!a) return;
+			lo = lo && lo < a ? lo : a;
+			hi = hi && hi > b ? hi : b;
+		};
+		const char *o = static_cast<const char *>(out), *s = reinterpret_cast<const char *>(pixel_stats);
+		widen(r->lane.out_lo, r->lane.out_hi, o, o + image_bytes(pixels, format));
+		widen(r->lane.pst_lo, r->lane.pst_hi, s, s ? s + pixels * 12 : nullptr);
+	}
+	return SDFR_OK;
+}
+
 extern "C" {
+
+int sdfr_render_aa(sdfr_renderer *r, int width, int height, int factor, void *out, int format, int out_on_host, uint32_t *pixel_stats)
+{
+	return guarded(r, [&]() -> int { return render_aa_impl(r, width, height, factor, out, format, out_on_host, pixel_stats); });
+}
 
 int sdfr_render(sdfr_renderer *r, int width, int height, void *out, int format, int out_on_host, uint32_t *pixel_stats)
 {
@@ -1255,6 +1380,17 @@ int sdfr_get_timings(sdfr_renderer *r, sdfr_timing *out, int capacity)
 				put(nm, t[i].march);
 				snprintf(nm, sizeof nm, "draw: shade %d", i);
 				put(nm, t[i].shade);
+			}
+			if (r->aa_timed_passes > 0) // a profiled sdfr_render_aa: the time inside its resolve launches, summed over the passes
+			{
+				double sum = 0.0;
+				for (int p = 0; p < r->aa_timed_passes; ++p)
+				{
+					float t = 0.f;
+					SDFR_HIP(hipEventElapsedTime(&t, r->ev_aa[2 * p], r->ev_aa[2 * p + 1]));
+					sum += t;
+				}
+				put("draw: resolve", sum);
 			}
 		}
 		if (r->lane.have_render && r->have_xfer)

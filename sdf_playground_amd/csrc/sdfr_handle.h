@@ -79,6 +79,14 @@ struct sdfr_renderer
 	hipEvent_t ev_mesh[7] = {}; // made by the first extraction.  [6]: the end of the last one's device work, which the next one waits
 	                            // for before it reuses `mesh`; [0..5]: around its stages when profiling is on (sdfr_mesh_get_timings)
 	int mesh_timed = 0;         // 0: the last extraction was not timed; 1: up to its counts; 2: all four stages; 3: no normals asked
+	// sdfr_render_aa: one pass's compact strips of the supersampled frame (RGBA32F), their per-sub-sample counters when pixel_stats is
+	// wanted, and the counters of one pass's launch.  The handle's own and kept between calls (an animation calls every frame): never
+	// a lane's workspace.  ev_aa_done: the end of the last call's device work, which the next call -- perhaps on the other lane's
+	// stream -- waits for before it reuses them.  ev_aa: around each pass's resolve when profiling is on ("draw: resolve").
+	sdfr_device_buffer aa_color, aa_stats, aa_totals;
+	hipEvent_t ev_aa_done = nullptr;
+	std::vector<hipEvent_t> ev_aa;
+	int aa_timed_passes = 0; // passes of the last render if it was a profiled sdfr_render_aa, else 0
 	// sdfr_register_host_target: the caller's persistent host image, page-locked with the runtime
 	void *pinned_host = nullptr;
 	size_t pinned_bytes = 0;

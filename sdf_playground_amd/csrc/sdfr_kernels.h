@@ -83,6 +83,10 @@ size_t postprocess_flag_bytes(int width, int height);
 hipError_t launch_postprocess(int width, int height, const void *scene16, void *bloom1, void *ldr8, unsigned char *flags, hipStream_t stream,
 	hipEvent_t mid_event = nullptr);
 
+// the resolve of one pass of sdfr_render_aa (sdfr_resolve.h, sdfr_resolve.hip): every strip of the pass, all pyramid levels
+struct ResolveArgs;
+hipError_t launch_resolve(ResolveArgs a, hipStream_t stream);
+
 hipError_t launch_selftest_math(int what, float c, unsigned long long *d_mismatches, hipStream_t stream);
 
 // wavefront schedule, scene-independent start of a frame: primary rays, empty queues, round-0 list

@@ -1,0 +1,329 @@
+"""GPU tier of sdfr_render_aa: the anti-aliased frame through the C ABI against the definition of include/sdfr.h (aa_util.pyramid, numpy)
+applied to the same handle's sdfr_render of the supersampled frame -- bit for bit -- and to the oracle's -- the parity bar --, the
+summed counters against the oracle's; passes, formats, destinations, edges, other schedules and scene kinds, the handle's state, the
+post-processing of an anti-aliased frame, the argument errors.  Frames are 37 x 21 unless a case says otherwise; SDFR_AA_BUDGET_BYTES
+forces several passes on them."""
+import os
+
+import numpy as np
+import pytest
+
+import aa_util as au
+from test_gpu_parity import TOL
+
+pytestmark = pytest.mark.gpu
+
+W, H = au.W, au.H
+SCENES = {"fast_sphere": 0.0, "labyrinth": 1.25, "lense": 1.25}  # scene: time
+RGBA32F, RGBA16F = 0, 1
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    yield r
+    r.close()
+
+
+@pytest.fixture(autouse=True)
+def _default_budget(monkeypatch):
+    monkeypatch.delenv("SDFR_AA_BUDGET_BYTES", raising=False)
+
+
+def _budget(monkeypatch, width, factor, strips):
+    """a byte budget that holds `strips` strips of S per pass; None: the library's default (one pass at these sizes)"""
+    if strips is None:
+        monkeypatch.delenv("SDFR_AA_BUDGET_BYTES", raising=False)
+    else:
+        monkeypatch.setenv("SDFR_AA_BUDGET_BYTES", str(au.budget_for(width, factor, strips)))
+
+
+def _setup(r, oracle, scene, stime):
+    """the scene with the camera tests/test_gpu_parity.py gives it and the reference's limits"""
+    import sdf_playground_amd as sp
+
+    kind, eye, tgt, fovy, asp, basis = au.camera_of(oracle, scene)
+    r.initShader(scene)
+    r.setParameters(stime)
+    cam = sp.Camera()
+    cam.SetEye(eye)
+    (cam.SetLookat if kind == "lookat" else cam.SetDirection)(tgt)
+    cam.SetFOVY(float(fovy))
+    cam.SetAspect(float(asp))
+    r.setCamera(cam)
+    assert np.array_equal(r.getCameraBasis().view(np.uint32), basis.view(np.uint32))
+    r.setSchedule(sp.SCHEDULE_PIXEL)
+    r.setLimits(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
+                extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
+
+
+def _own_pyramid(r, width, height, factor):
+    """the definition applied to the same handle's sdfr_render of S: (image, summed stats)"""
+    s, st = r.render(None, width * factor, height * factor, pixel_stats=True)
+    return au.pyramid(s, factor), au.sum_stats(st, factor)
+
+
+# ---- 1. parity ------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("factor", au.FACTORS)
+@pytest.mark.parametrize("scene", sorted(SCENES))
+def test_parity_with_the_definition_and_the_oracle(renderer, oracle, monkeypatch, scene, factor):
+    _setup(renderer, oracle, scene, SCENES[scene])
+    strips, passes, _ = au.plan(W, H, factor, au.budget_for(W, factor, 2))
+    assert passes >= 3 and (factor == 2 or strips % passes != 0), "several passes; at factors 4 and 8 they do not divide the 11 and 21 strips"
+    _budget(monkeypatch, W, factor, 2)
+    img, st = renderer.renderAA(None, W, H, factor, pixel_stats=True)
+    stats = renderer.getStats()
+    want, want_st = _own_pyramid(renderer, W, H, factor)
+    assert au.same_bits(img, want), "%s x%d: not the pyramid of the handle's own render of S" % (scene, factor)
+    assert np.array_equal(st, want_st)
+    s, ost, tot = au.oracle_s(oracle, scene, SCENES[scene], W, H, factor)
+    diff = np.abs(img.astype(np.float64) - au.pyramid(s, factor).astype(np.float64)).max()
+    print("%s x%d: L-inf against the oracle's pyramid %g" % (scene, factor, diff))
+    assert not np.isnan(img).any() and diff <= TOL
+    assert np.array_equal(st, au.sum_stats(ost, factor)), "the summed counters are the oracle's"
+    assert (stats.pixels, stats.rays, stats.march_evals, stats.hits) == tuple(int(x) for x in tot)
+
+
+# ---- 2. pass independence ----------------------------------------------------------------------------------------------------------------
+
+def test_the_passes_do_not_show(renderer, oracle, monkeypatch):
+    _setup(renderer, oracle, "labyrinth", 1.25)
+    results = []
+    for strips in (None, 4, 3, 1):  # the default budget: one pass; then 3, 4 and 11 passes over the 11 strips of S
+        _budget(monkeypatch, W, 4, strips)
+        results.append(renderer.renderAA(None, W, H, 4, pixel_stats=True))
+    assert au.plan(W, H, 4, 1 << 30)[1] == 1 and [au.plan(W, H, 4, au.budget_for(W, 4, n))[1] for n in (4, 3, 1)] == [3, 4, 11]
+    for img, st in results[1:]:
+        assert au.same_bits(img, results[0][0]) and np.array_equal(st, results[0][1])
+
+
+# ---- 3. formats and destinations ---------------------------------------------------------------------------------------------------------
+
+def test_formats_and_destinations(renderer, oracle, monkeypatch):
+    import torch
+
+    _setup(renderer, oracle, "lense", 1.25)
+    _budget(monkeypatch, W, 4, 2)
+    img, st = renderer.renderAA(None, W, H, 4, pixel_stats=True)
+    img16 = renderer.renderAA(None, W, H, 4, fmt=RGBA16F)
+    assert np.array_equal(img16.view(np.uint16), oracle.float_to_half(img)), "the 16F image is the fp32 image converted once, to nearest even"
+    d32 = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
+    d16 = torch.zeros((H, W, 4), dtype=torch.float16, device="cuda")
+    dst = torch.zeros((H, W, 3), dtype=torch.int32, device="cuda")
+    renderer.renderAA(None, W, H, 4, out=d32, pixel_stats=dst)
+    renderer.renderAA(None, W, H, 4, out=d16, fmt=RGBA16F)
+    renderer.sync()
+    assert au.same_bits(d32.cpu().numpy(), img) and np.array_equal(dst.cpu().numpy().view(np.uint32), st)
+    assert au.same_bits(d16.cpu().numpy(), img16)
+    # factor 1 is sdfr_render, image and counters, in one pass and in several
+    ref, rst = renderer.render(None, W, H, pixel_stats=True)
+    for strips in (None, 1):
+        _budget(monkeypatch, W, 1, strips)
+        one, ost = renderer.renderAA(None, W, H, 1, pixel_stats=True)
+        assert au.same_bits(one, ref) and np.array_equal(ost, rst)
+    assert au.same_bits(renderer.renderAA(None, W, H, 1, fmt=RGBA16F), renderer.render(None, W, H, fmt=RGBA16F))
+
+
+# ---- 4. the pyramid property -------------------------------------------------------------------------------------------------------------
+
+def test_factor_4_is_factor_2_of_factor_2(renderer, oracle, monkeypatch):
+    _setup(renderer, oracle, "labyrinth", 1.25)
+    _budget(monkeypatch, W, 4, 2)
+    four = renderer.renderAA(None, W, H, 4)
+    two = renderer.renderAA(None, 2 * W, 2 * H, 2)
+    assert au.same_bits(four, au.box2(two))
+    assert not au.same_bits(four, renderer.render(None, W, H)), "the scene has edges: anti-aliasing changes the picture"
+
+
+# ---- 5. edges ----------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("width,height,factor,strips", [(W, 1, 8, 1), (1, H, 8, 2), (W, 3, 4, 1), (W, 3, 4, None), (300, 5, 2, 1)],
+                         ids=["H1xK8", "W1xK8", "H3xK4", "H3xK4-one-pass", "W300-two-blocks"])
+def test_edges_and_guard_rows(renderer, oracle, monkeypatch, width, height, factor, strips):
+    """one row, one column, a cut-short last strip of S (K * H = 12: one strip and a half), a row wider than one block of the resolve
+    kernel -- rendered into the middle of a canary-filled device buffer with guard rows before and after"""
+    import torch
+
+    _setup(renderer, oracle, "fast_sphere", 0.0)
+    _budget(monkeypatch, width, factor, strips)
+    want, want_st = _own_pyramid(renderer, width, height, factor)
+    guard = 3
+    for fmt, dtype, canary in ((RGBA32F, torch.float32, -7.5), (RGBA16F, torch.float16, -7.5)):
+        buf = torch.full((height + 2 * guard, width, 4), canary, dtype=dtype, device="cuda")
+        sbuf = torch.full((height + 2 * guard, width, 3), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+        renderer.renderAA(None, width, height, factor, out=buf[guard:guard + height], fmt=fmt, pixel_stats=sbuf[guard:guard + height])
+        renderer.sync()
+        got, got_st = buf.cpu().numpy(), sbuf.cpu().numpy().view(np.uint32)
+        for g in (got[:guard], got[guard + height:]):
+            assert (g == canary).all(), "written outside [H][W]"
+        for g in (got_st[:guard], got_st[guard + height:]):
+            assert (g == 0x5A5A5A5A).all(), "counters written outside [H][W]"
+        if fmt == RGBA32F:
+            assert au.same_bits(got[guard:guard + height], want)
+        else:
+            assert np.array_equal(got[guard:guard + height].view(np.uint16), oracle.float_to_half(want))
+        assert np.array_equal(got_st[guard:guard + height], want_st)
+
+
+# ---- 6. other paths ----------------------------------------------------------------------------------------------------------------------
+
+def test_a_scene_compiled_at_run_time(renderer, monkeypatch):
+    import sdf_playground_amd as sp
+
+    path = os.path.join(os.path.dirname(os.path.abspath(sp.__file__)), "scenes", "pendulum.hlsl")
+    r = sp.SDFRenderer(0)
+    r.initShaderHlsl("pendulum", path)
+    r.setParameters(0.8)
+    cam = sp.Camera()
+    cam.SetAspect(W / H)
+    r.setCamera(cam)
+    _budget(monkeypatch, W, 4, 2)
+    img, st = r.renderAA(None, W, H, 4, pixel_stats=True)
+    want, want_st = _own_pyramid(r, W, H, 4)
+    assert au.same_bits(img, want) and np.array_equal(st, want_st)
+    assert len(np.unique(st[..., 2])) > 2, "the picture has content"
+    r.close()
+
+
+def test_the_wavefront_schedule(renderer, oracle, monkeypatch):
+    import sdf_playground_amd as sp
+
+    _setup(renderer, oracle, "lense", 1.25)
+    _budget(monkeypatch, W, 2, 2)
+    pix = renderer.renderAA(None, W, H, 2, pixel_stats=True)
+    renderer.setSchedule(sp.SCHEDULE_WAVEFRONT)
+    img, st = renderer.renderAA(None, W, H, 2, pixel_stats=True)
+    stats = renderer.getStats()
+    want, want_st = _own_pyramid(renderer, W, H, 2)
+    renderer.setSchedule(sp.SCHEDULE_PIXEL)
+    assert au.same_bits(img, want) and np.array_equal(st, want_st)
+    assert au.same_bits(img, pix[0]) and np.array_equal(st, pix[1])
+    tot = au.oracle_s(oracle, "lense", 1.25, W, H, 2)[2]
+    assert (stats.pixels, stats.rays, stats.march_evals, stats.hits) == tuple(int(x) for x in tot)
+
+
+# ---- 7. the handle's state ---------------------------------------------------------------------------------------------------------------
+
+def test_a_render_is_the_same_before_and_after(renderer, oracle, monkeypatch):
+    _setup(renderer, oracle, "labyrinth", 1.25)
+    before = renderer.render(None, 120, 72, pixel_stats=True)
+    sb = renderer.getStats()
+    renderer.setStripSplit(1, 3)  # ignored by an anti-aliased frame, as by a full one; kept for the strip calls
+    _budget(monkeypatch, W, 4, 2)
+    img, st = renderer.renderAA(None, W, H, 4, pixel_stats=True)
+    s = renderer.getStats()
+    assert s.pixels == 16 * W * H
+    assert (s.rays, s.march_evals, s.hits) == tuple(int(x) for x in st.reshape(-1, 3).astype(np.uint64).sum(axis=0))
+    assert s.ms_gpu > 0.0 and abs(renderer.getTimings()["draw"] - s.ms_gpu) < 1e-6
+    renderer.setStripSplit(0, 1)
+    assert au.same_bits(img, renderer.renderAA(None, W, H, 4))
+    after = renderer.render(None, 120, 72, pixel_stats=True)
+    sa = renderer.getStats()
+    assert au.same_bits(after[0], before[0]) and np.array_equal(after[1], before[1])
+    assert (sa.pixels, sa.rays, sa.march_evals, sa.hits) == (sb.pixels, sb.rays, sb.march_evals, sb.hits)
+    # profiling adds the resolve's time to the named timings of an anti-aliased frame, and only of that
+    renderer.setProfiling(True)
+    renderer.renderAA(None, W, H, 4)
+    t = renderer.getTimings()
+    assert "draw: resolve" in t and 0.0 < t["draw: resolve"] < t["draw"]
+    renderer.render(None, W, H)
+    assert "draw: resolve" not in renderer.getTimings()
+    renderer.setProfiling(False)
+
+
+def test_two_frames_in_flight(oracle, monkeypatch):
+    import sdf_playground_amd as sp
+    import torch
+
+    r = sp.SDFRenderer(0)
+    _setup(r, oracle, "lense", 1.25)
+    want, want_st = _own_pyramid(r, W, H, 4)
+    plain_want = r.render(None, 4 * W, 4 * H)
+    r.setFramesInFlight(2)
+    _budget(monkeypatch, W, 4, 2)
+    plain = torch.zeros((4 * H, 4 * W, 4), dtype=torch.float32, device="cuda")
+    aa = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+    st = torch.zeros((H, W, 3), dtype=torch.int32, device="cuda")
+    r.render(None, 4 * W, 4 * H, out=plain)
+    r.renderAA(None, W, H, 4, out=aa[0], pixel_stats=st)
+    r.render(None, 4 * W, 4 * H, out=plain)  # the other lane
+    r.renderAA(None, W, H, 4, out=aa[1])     # ... whose anti-aliased frame reuses the handle's pass buffer
+    r.sync()
+    assert au.same_bits(plain.cpu().numpy(), plain_want)
+    assert au.same_bits(aa[0].cpu().numpy(), want) and au.same_bits(aa[1].cpu().numpy(), want)
+    assert np.array_equal(st.cpu().numpy().view(np.uint32), want_st)
+    assert r.getStats().pixels == 16 * W * H
+    r.setFramesInFlight(1)
+    r.close()
+
+
+# ---- 8. post-processing ------------------------------------------------------------------------------------------------------------------
+
+def test_postprocess_of_an_anti_aliased_frame(renderer, oracle, monkeypatch):
+    """an RGBA16F anti-aliased frame whose alpha takes fractional values -- the share of a pixel's sub-samples that are tone-mapped --
+    through sdfr_postprocess, at the bar of tests/test_gpu_post.py: the LDR image byte for byte, the bloom buffer bit for bit"""
+    import sdf_playground_amd as sp
+    from test_debug_materials_cpu import CAMS
+
+    w, h = 64, 40
+    renderer.initShader("debug_materials")  # tone-mapped and untone-mapped views side by side
+    renderer.setParameters(0.4)
+    renderer.setLimits(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7)
+    cam = sp.Camera()
+    cam.SetEye(CAMS[0][0])
+    cam.SetLookat(CAMS[0][1])
+    cam.SetAspect(w / h)
+    renderer.setCamera(cam)
+    _budget(monkeypatch, w, 2, 3)
+    hdr = sp.HDR(renderer)
+    hdr.init(w, h)
+    renderer.renderAA(None, w, h, 2, out=hdr.getRenderTarget(), fmt=RGBA16F)
+    ldr = hdr.process().cpu().numpy()
+    renderer.sync()
+    scene16 = hdr.getRenderTarget().cpu().numpy()
+    alpha = scene16[..., 3].astype(np.float32)
+    print("alpha values:", np.unique(alpha))
+    assert ((alpha > 0) & (alpha < 1)).any(), "no fractional alpha: the case would show nothing"
+    assert (alpha == 0).any() and (alpha == 1).any()
+    b1, _b2, ref = oracle.postprocess(scene16)
+    assert np.array_equal(hdr._bloom.cpu().numpy().view(np.uint16), b1.view(np.uint16))
+    assert np.array_equal(ldr, ref)
+
+
+# ---- 9. arguments ------------------------------------------------------------------------------------------------------------------------
+
+def test_argument_errors_write_nothing(renderer, oracle):
+    import ctypes
+
+    import sdf_playground_amd as sp
+    import torch
+
+    L = sp.load_library()
+    _setup(renderer, oracle, "fast_sphere", 0.0)
+    host = np.full((H, W, 4), -3.25, np.float32)
+    host_st = np.full((H, W, 3), 0xABCDEF01, np.uint32)
+    dev = torch.full((H, W, 4), -3.25, dtype=torch.float32, device="cuda")
+    hp, sp_, dp = host.ctypes.data_as(ctypes.c_void_p), host_st.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dev.data_ptr())
+    INVALID, NO_SCENE = -1, -4
+    h = renderer._h
+    cases = [(W, H, f, hp, RGBA32F, 1) for f in (0, 3, 5, 6, 7, 16, -2)]                       # a factor outside {1, 2, 4, 8}
+    cases += [(0, H, 2, hp, RGBA32F, 1), (W, 0, 2, hp, RGBA32F, 1), (-1, H, 2, hp, RGBA32F, 1)]  # width or height below 1
+    cases += [(1 << 14, (1 << 10) + 1, 8, hp, RGBA32F, 1), (1 << 15, 1 << 15, 2, hp, RGBA32F, 1)]  # K^2 * W * H above 2^30
+    cases += [(W, H, 2, None, RGBA32F, 1), (W, H, 2, None, RGBA32F, 0)]                          # no image
+    cases += [(W, H, 2, hp, RGBA32F, 2), (W, H, 2, hp, RGBA32F, -1)]                             # a bad out_on_host
+    cases += [(W, H, 2, hp, fmt, 1) for fmt in (2, 3, 4, -1)]                                    # the strip formats are not images
+    for width, height, factor, out, fmt, on_host in cases:
+        assert L.sdfr_render_aa(h, width, height, factor, out, fmt, on_host, sp_) == INVALID, (width, height, factor, fmt, on_host)
+    assert L.sdfr_render_aa(h, W, H, 3, dp, RGBA32F, 0, None) == INVALID
+    assert L.sdfr_render_aa(None, W, H, 2, hp, RGBA32F, 1, None) == INVALID
+    fresh = sp.SDFRenderer(0)
+    assert L.sdfr_render_aa(fresh._h, W, H, 2, hp, RGBA32F, 1, sp_) == NO_SCENE
+    assert L.sdfr_render_aa(fresh._h, W, H, 2, dp, RGBA32F, 0, None) == NO_SCENE
+    fresh.close()
+    renderer.sync()
+    assert (host == -3.25).all() and (host_st == 0xABCDEF01).all() and (dev.cpu().numpy() == -3.25).all()
+    # ... and the same buffers with good arguments are written
+    assert L.sdfr_render_aa(h, W, H, 2, hp, RGBA32F, 1, sp_) == 0 and not (host == -3.25).any()
