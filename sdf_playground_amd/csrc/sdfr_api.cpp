@@ -642,6 +642,10 @@ int sdfr_set_strip_split(sdfr_renderer *r, int priv_count, int priv_period)
 	});
 }
 
+// what every entry point that takes a frame size or an "is host memory" flag accepts
+static bool frame_size_ok(int width, int height) { return width >= 1 && height >= 1 && (int64_t)width * height <= (int64_t)1 << 30; }
+static bool is_flag(int v) { return v == 0 || v == 1; }
+
 // the arguments of render_impl, in the order their errors win; a private render without private strips renders nothing
 // and needs no scene
 static int check_render(sdfr_renderer *r, int width, int height, int rank, int world, const void *out, int format, RenderMode mode)
@@ -652,7 +656,7 @@ static int check_render(sdfr_renderer *r, int width, int height, int rank, int w
 	if (mode == RENDER_PRIVATE && r->priv_count == 0) return SDFR_OK;
 	if (world < 1 || rank < 0 || rank >= world) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad rank/world");
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
-	if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	if (!frame_size_ok(width, height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 	return SDFR_OK;
 }
 
@@ -682,20 +686,62 @@ static int latch_into(sdfr_renderer *r, FrameU &U, int width, int height, hipStr
 // ... the handle's own, for a render
 static int latch_frame(sdfr_renderer *r, int width, int height) { return latch_into(r, r->U, width, height, r->lane.stream); }
 
+// The kernels of the loaded scene, built in or compiled at run time: the two places that ask which it is for a launch.
+// The pixel kernel for the handle's frame, and how the scene wants it launched ...
+static int loaded_pixel_kernel(sdfr_renderer *r, PixelKernel &pk)
+{
+	const bool dbg = frame_needs_debug(r->U);
+	if (r->scene == SDFR_SCENE_COUNT) pk = jit_pixel_kernel(r->jit, dbg);
+	else if (!scene_pixel_kernel(r->scene, dbg, pk)) return hip_fail(r, hipErrorInvalidValue, "kernel launch");
+	return SDFR_OK;
+}
+// ... and the query kernel of `kind` (QUERY_KERNEL_*) for frame U; a run-time scene compiles its query module on its first query
+static int loaded_query_kernel(sdfr_renderer *r, int kind, const FrameU &U, KernelRef &k)
+{
+	const QueryKernels *qk = nullptr;
+	if (r->scene == SDFR_SCENE_COUNT)
+	{
+		std::string err;
+		const JitQueryStatus js = jit_query_kernels(r->jit, r->device, qk, err);
+		if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
+	}
+	else if (!(qk = scene_query_kernels(r->scene)))
+		return hip_fail(r, hipErrorInvalidValue, kind == QUERY_KERNEL_LATTICE ? "lattice launch" : "query launch");
+	k = qk->k[kind][frame_needs_debug(U) ? 1 : 0];
+	return SDFR_OK;
+}
+// one query of the loaded scene, every pointer of `q` device memory
+static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipStream_t stream)
+{
+	KernelRef k;
+	const int rc = loaded_query_kernel(r, q.kind == QUERY_POINTS ? QUERY_KERNEL_POINTS : QUERY_KERNEL_RAYS, U, k);
+	if (rc != SDFR_OK) return rc;
+	const hipError_t e = launch_query(k, U, q, stream);
+	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "query launch");
+}
+
 // The three queries (sdfr_query.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not the
 // handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
 // out: distance + normals, or hits.
 static const size_t k_query_stage_keep = (size_t)64 << 20; // staging bytes a handle keeps between host queries
 static_assert(sizeof(sdfr_hit) == 4 * QUERY_HIT_WORDS, "sdfr_hit is the query kernels' 12-word record");
+// the end of a host call: the answers back to the caller in the order they were named, and `stream` synchronised.  A large call
+// does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
+static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
+{
+	for (int k = 0; k < st.n_answers; ++k) SDFR_HIP(hipMemcpyAsync(st.answers[k].host, st.answers[k].device, st.answers[k].bytes, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+	if (st.buffer->bytes > k_query_stage_keep) st.buffer->release();
+	return SDFR_OK;
+}
 static int query_impl(sdfr_renderer *r, int kind, int64_t n, const float *pos, const float *dir, const int32_t *pixels, int width, int height,
 	float max_distance, float *distance, float *normals, sdfr_hit *hits, int on_host)
 {
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 	if (n < 0 || n > (int64_t)INT32_MAX) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad item count");
-	if (on_host != 0 && on_host != 1) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
+	if (!is_flag(on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
 	if (!std::isfinite(max_distance) || max_distance < 0.f) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "max_distance must be finite and >= 0");
-	if (kind == QUERY_PICK && (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30))
-		return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	if (kind == QUERY_PICK && !frame_size_ok(width, height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 	if (n == 0) return SDFR_OK;
 	const bool inputs_ok = kind == QUERY_POINTS ? pos != nullptr : kind == QUERY_RAYS ? pos && dir : pixels != nullptr;
 	const bool outputs_ok = kind == QUERY_POINTS ? distance != nullptr : hits != nullptr;
@@ -721,43 +767,22 @@ static int query_impl(sdfr_renderer *r, int kind, int64_t n, const float *pos, c
 	const size_t N = (size_t)n;
 	const size_t in0 = kind == QUERY_PICK ? N * 8 : N * 12, in1 = kind == QUERY_RAYS ? N * 12 : 0;
 	const size_t out0 = kind == QUERY_POINTS ? N * 4 : N * sizeof(sdfr_hit), out1 = kind == QUERY_POINTS && normals ? N * 12 : 0;
-	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+	Carving st({in0, in1, out0, out1});
 	if (on_host)
 	{
-		const size_t need = up(in0) + up(in1) + up(out0) + up(out1);
-		SDFR_HIP(r->query.reserve(need)); // (host queries are synchronous: none is using the old one)
-		char *base = static_cast<char *>(r->query.ptr);
-		char *d_in0 = base, *d_in1 = d_in0 + up(in0), *d_out0 = d_in1 + up(in1), *d_out1 = d_out0 + up(out0);
-		SDFR_HIP(hipMemcpyAsync(d_in0, kind == QUERY_PICK ? (const void *)pixels : (const void *)pos, in0, hipMemcpyHostToDevice, stream));
-		if (in1) SDFR_HIP(hipMemcpyAsync(d_in1, dir, in1, hipMemcpyHostToDevice, stream));
-		q.pos = kind == QUERY_PICK ? nullptr : reinterpret_cast<const float *>(d_in0);
-		q.pixels = kind == QUERY_PICK ? reinterpret_cast<const int32_t *>(d_in0) : nullptr;
-		q.dir = in1 ? reinterpret_cast<const float *>(d_in1) : nullptr;
-		q.distance = kind == QUERY_POINTS ? reinterpret_cast<float *>(d_out0) : nullptr;
-		q.normals = out1 ? reinterpret_cast<float *>(d_out1) : nullptr;
-		q.hits = kind == QUERY_POINTS ? nullptr : reinterpret_cast<uint32_t *>(d_out0);
+		SDFR_HIP(st.reserve(r->query)); // (host queries are synchronous: none is using the old one)
+		SDFR_HIP(hipMemcpyAsync(st.piece<void>(0), kind == QUERY_PICK ? (const void *)pixels : (const void *)pos, in0, hipMemcpyHostToDevice, stream));
+		if (in1) SDFR_HIP(hipMemcpyAsync(st.piece<void>(1), dir, in1, hipMemcpyHostToDevice, stream));
+		q.pos = kind == QUERY_PICK ? nullptr : st.piece<const float>(0);
+		q.pixels = kind == QUERY_PICK ? st.piece<const int32_t>(0) : nullptr;
+		q.dir = in1 ? st.piece<const float>(1) : nullptr;
+		q.distance = kind == QUERY_POINTS ? st.answer(2, distance, out0) : nullptr;
+		q.normals = out1 ? st.answer(3, normals, out1) : nullptr;
+		q.hits = kind == QUERY_POINTS ? nullptr : st.answer(2, reinterpret_cast<uint32_t *>(hits), out0);
 	}
-	if (r->scene == SDFR_SCENE_COUNT)
-	{
-		std::string err;
-		const JitQueryStatus js = jit_launch_query(r->jit, r->device, U, q, stream, err);
-		if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
-	}
-	else
-	{
-		const hipError_t e = launch_query(r->scene, U, q, stream);
-		if (e != hipSuccess) return hip_fail(r, e, "query launch");
-	}
-	if (on_host)
-	{
-		SDFR_HIP(hipMemcpyAsync(kind == QUERY_POINTS ? (void *)distance : (void *)hits, kind == QUERY_POINTS ? (const void *)q.distance : (const void *)q.hits,
-			out0, hipMemcpyDeviceToHost, stream));
-		if (out1) SDFR_HIP(hipMemcpyAsync(normals, q.normals, out1, hipMemcpyDeviceToHost, stream));
-		SDFR_HIP(hipStreamSynchronize(stream));
-		// a large host query does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
-		if (r->query.bytes > k_query_stage_keep) r->query.release();
-	}
-	return SDFR_OK;
+	rc = run_query(r, U, q, stream);
+	if (rc != SDFR_OK) return rc;
+	return on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
 }
 
 int sdfr_query_distance(sdfr_renderer *r, int64_t n, const float *points, float *distance, float *normals, int on_host)
@@ -783,7 +808,7 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 {
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 	if (!grid || !counts) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
-	if (on_host != 0 && on_host != 1) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
+	if (!is_flag(on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
 	bool grid_ok = std::isfinite(grid->cell) && grid->cell > 0.f && std::isfinite(grid->iso);
 	for (int a = 0; a < 3; ++a) grid_ok = grid_ok && std::isfinite(grid->origin[a]);
 	for (int32_t n : {grid->nx, grid->ny, grid->nz}) grid_ok = grid_ok && n >= 1 && n <= 1024;
@@ -794,7 +819,7 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	SDFR_HIP(hipSetDevice(r->device));
 	hipStream_t stream = r->lane.stream; // as the queries
 	FrameU U = r->U;
-	const int rc = latch_into(r, U, 1, 1, stream);
+	int rc = latch_into(r, U, 1, 1, stream);
 	if (rc != SDFR_OK) return rc;
 
 	MeshGrid g;
@@ -805,9 +830,7 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	g.n[2] = grid->nz;
 	g.iso = grid->iso;
 	const size_t points = mesh_point_count(g), cells = mesh_cell_count(g);
-	auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-	const size_t b_lattice = up(points * 4), b_cells = up((cells + 1) * 4), b_points = up((points + 1) * 4);
-	const size_t b_sums = up((mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)) * 4);
+	Carving work({points * 4, (cells + 1) * 4, (points + 1) * 4, (mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)) * 4});
 
 	for (hipEvent_t &e : r->ev_mesh)
 		if (!e) SDFR_HIP(hipEventCreate(&e));
@@ -815,12 +838,10 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	r->mesh_timed = 0;
 	// the last extraction's emit work (device arrays: enqueued, perhaps on the other lane's stream) still reads the workspace
 	SDFR_HIP(hipStreamWaitEvent(stream, r->ev_mesh[6], 0));
-	if (r->mesh.bytes < b_lattice + b_cells + b_points + b_sums) SDFR_HIP(hipEventSynchronize(r->ev_mesh[6]));
-	SDFR_HIP(r->mesh.reserve(b_lattice + b_cells + b_points + b_sums));
-	char *base = static_cast<char *>(r->mesh.ptr);
-	float *d_lattice = reinterpret_cast<float *>(base);
-	uint32_t *d_cells = reinterpret_cast<uint32_t *>(base + b_lattice), *d_points = reinterpret_cast<uint32_t *>(base + b_lattice + b_cells);
-	uint32_t *d_sums = reinterpret_cast<uint32_t *>(base + b_lattice + b_cells + b_points);
+	if (r->mesh.bytes < work.total) SDFR_HIP(hipEventSynchronize(r->ev_mesh[6]));
+	SDFR_HIP(work.reserve(r->mesh));
+	float *d_lattice = work.piece<float>(0);
+	uint32_t *d_cells = work.piece<uint32_t>(1), *d_points = work.piece<uint32_t>(2), *d_sums = work.piece<uint32_t>(3);
 	// a workspace past what a handle keeps is given back once the work that uses it is done
 	auto release_large = [&]() -> int {
 		if (r->mesh.bytes <= k_query_stage_keep) return SDFR_OK;
@@ -839,17 +860,11 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	la.rows = rows;
 	la.out = d_lattice;
 	if (ev) SDFR_HIP(hipEventRecord(ev[0], stream));
-	if (r->scene == SDFR_SCENE_COUNT)
-	{
-		std::string err;
-		const JitQueryStatus js = jit_launch_query_lattice(r->jit, r->device, U, la, stream, err);
-		if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
-	}
-	else
-	{
-		const hipError_t e = launch_query_lattice(r->scene, U, la, stream);
-		if (e != hipSuccess) return hip_fail(r, e, "lattice launch");
-	}
+	KernelRef lattice_kernel;
+	rc = loaded_query_kernel(r, QUERY_KERNEL_LATTICE, U, lattice_kernel);
+	if (rc != SDFR_OK) return rc;
+	const hipError_t e = launch_query_lattice(lattice_kernel, U, la, stream);
+	if (e != hipSuccess) return hip_fail(r, e, "lattice launch");
 	if (ev) SDFR_HIP(hipEventRecord(ev[1], stream));
 	SDFR_HIP(launch_mesh_count(g, d_lattice, d_cells, d_points, d_sums, stream));
 	if (ev) SDFR_HIP(hipEventRecord(ev[2], stream));
@@ -865,14 +880,13 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	const size_t V = n_vertices, T = (size_t)counts->triangles;
 	float *d_pos = positions, *d_nrm = normals;
 	uint32_t *d_idx = T ? indices : nullptr;
+	Carving st({V * 12, normals ? V * 12 : 0, T * 12});
 	if (on_host)
 	{
-		const size_t b_pos = up(V * 12), b_nrm = normals ? up(V * 12) : 0;
-		SDFR_HIP(r->query.reserve(b_pos + b_nrm + up(T * 12))); // (host calls are synchronous: none is using the old one)
-		char *stage = static_cast<char *>(r->query.ptr);
-		d_pos = reinterpret_cast<float *>(stage);
-		d_nrm = normals ? reinterpret_cast<float *>(stage + b_pos) : nullptr;
-		d_idx = T ? reinterpret_cast<uint32_t *>(stage + b_pos + b_nrm) : nullptr;
+		SDFR_HIP(st.reserve(r->query)); // (host calls are synchronous: none is using the old one)
+		d_pos = st.answer(0, positions, V * 12);
+		d_nrm = normals ? st.answer(1, normals, V * 12) : nullptr;
+		d_idx = T ? st.answer(2, indices, T * 12) : nullptr;
 	}
 	if (ev) SDFR_HIP(hipEventRecord(ev[3], stream));
 	SDFR_HIP(launch_mesh_emit(g, d_lattice, d_cells, d_points, d_pos, d_idx, stream));
@@ -885,30 +899,14 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 		q.pos = d_pos;
 		q.distance = d_lattice; // the point query also writes its distances: into the lattice, which nothing reads any more
 		q.normals = d_nrm;
-		if (r->scene == SDFR_SCENE_COUNT)
-		{
-			std::string err;
-			const JitQueryStatus js = jit_launch_query(r->jit, r->device, U, q, stream, err);
-			if (js != JIT_QUERY_OK) return fail(r, js == JIT_QUERY_COMPILE ? SDFR_ERR_COMPILE : SDFR_ERR_HIP, err);
-		}
-		else
-		{
-			const hipError_t e = launch_query(r->scene, U, q, stream);
-			if (e != hipSuccess) return hip_fail(r, e, "query launch");
-		}
+		rc = run_query(r, U, q, stream);
+		if (rc != SDFR_OK) return rc;
 		if (ev) SDFR_HIP(hipEventRecord(ev[5], stream));
 	}
 	if (ev) r->mesh_timed = d_nrm ? 2 : 3;
-	if (on_host)
-	{
-		SDFR_HIP(hipMemcpyAsync(positions, d_pos, V * 12, hipMemcpyDeviceToHost, stream));
-		if (normals) SDFR_HIP(hipMemcpyAsync(normals, d_nrm, V * 12, hipMemcpyDeviceToHost, stream));
-		if (T) SDFR_HIP(hipMemcpyAsync(indices, d_idx, T * 12, hipMemcpyDeviceToHost, stream));
-		SDFR_HIP(hipStreamSynchronize(stream));
-		if (r->query.bytes > k_query_stage_keep) r->query.release();
-	}
-	else
-		SDFR_HIP(hipEventRecord(r->ev_mesh[6], stream));
+	rc = on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
+	if (rc != SDFR_OK) return rc;
+	if (!on_host) SDFR_HIP(hipEventRecord(r->ev_mesh[6], stream));
 	return release_large();
 }
 
@@ -942,6 +940,26 @@ int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
 
 } // extern "C"
 
+// Where a render writes when the caller's image and pixel_stats (or null) are host memory: the handle's staging buffers ...
+static int stage_frame(sdfr_renderer *r, int on_host, size_t out_bytes, size_t pixels, void *&d_out, uint32_t *&d_pstat)
+{
+	if (!on_host) return SDFR_OK;
+	SDFR_HIP(r->stage.reserve(out_bytes));
+	d_out = r->stage.ptr;
+	if (!d_pstat) return SDFR_OK;
+	SDFR_HIP(r->pstat.reserve(pixels * 12));
+	d_pstat = static_cast<uint32_t *>(r->pstat.ptr);
+	return SDFR_OK;
+}
+// ... and from there to the caller once `stream` has rendered them
+static int unstage_frame(sdfr_renderer *r, void *out, const void *d_out, size_t out_bytes, uint32_t *pixel_stats, const uint32_t *d_pstat, size_t pixels, hipStream_t stream)
+{
+	SDFR_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+	if (pixel_stats) SDFR_HIP(hipMemcpyAsync(pixel_stats, d_pstat, pixels * 12, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+	return SDFR_OK;
+}
+
 int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int world, void *out, int format, int out_on_host, uint32_t *pixel_stats,
 	RenderMode mode, RenderTotals *totals, bool caller_times)
 {
@@ -962,21 +980,13 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 
 	void *d_out = out;
 	uint32_t *d_pstat = pixel_stats;
-	if (out_on_host)
-	{
-		SDFR_HIP(r->stage.reserve(out_bytes));
-		d_out = r->stage.ptr;
-		if (pixel_stats)
-		{
-			SDFR_HIP(r->pstat.reserve(local_pixels * 12));
-			d_pstat = static_cast<uint32_t *>(r->pstat.ptr);
-		}
-	}
+	rc = stage_frame(r, out_on_host, out_bytes, local_pixels, d_out, d_pstat);
+	if (rc != SDFR_OK) return rc;
 	// rows of a strip buffer past the end of the frame are never written: define them (only the ranks whose last strip is
 	// missing or cut short have any)
 	if (mode == RENDER_STRIPS && strips_end_past_frame(rm, height) && out_bytes) SDFR_HIP(hipMemsetAsync(d_out, 0, out_bytes, r->lane.stream));
 
-	const bool pixel_schedule = r->scene == SDFR_SCENE_COUNT || r->schedule == SDFR_SCHEDULE_PIXEL;
+	const bool pixel_schedule = r->scene == SDFR_SCENE_COUNT || r->schedule == SDFR_SCHEDULE_PIXEL; // (scenes compiled at run time exist for the PIXEL schedule only)
 	if (!pixel_schedule) SDFR_HIP(hipMemsetAsync(totals, 0, sizeof(RenderTotals), r->lane.stream)); // the wavefront kernels add to it
 	hipError_t e;
 	if (rm.local_rows == 0) return SDFR_OK; // e.g. every strip of a small frame is private
@@ -987,15 +997,13 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 	}
 	if (rc != SDFR_OK) return rc;
 	if (!caller_times) SDFR_HIP(hipEventRecord(r->lane.ev_begin, r->lane.stream));
-	if (r->scene == SDFR_SCENE_COUNT) // scenes compiled at run time exist for the PIXEL schedule only
+	if (pixel_schedule)
 	{
-		e = jit_launch_pixel(r->jit, r->U, rm, d_out, format, d_pstat, totals, r->lane.ws, r->lane.stream, r->launch_mode);
+		PixelKernel pk;
 		r->last_wavefront = false;
-	}
-	else if (r->schedule == SDFR_SCHEDULE_PIXEL)
-	{
-		e = launch_pixel_schedule(r->scene, r->U, rm, d_out, format, d_pstat, totals, r->lane.ws, r->lane.stream, r->launch_mode);
-		r->last_wavefront = false;
+		rc = loaded_pixel_kernel(r, pk);
+		if (rc != SDFR_OK) return rc;
+		e = launch_pixel(pk, r->U, rm, d_out, format, d_pstat, totals, r->lane.ws, r->lane.stream, r->launch_mode);
 	}
 	else
 	{
@@ -1013,13 +1021,7 @@ int sdfr::render_impl(sdfr_renderer *r, int width, int height, int rank, int wor
 	}
 	r->lane.have_render = true;
 
-	if (out_on_host)
-	{
-		SDFR_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, r->lane.stream));
-		if (pixel_stats) SDFR_HIP(hipMemcpyAsync(pixel_stats, d_pstat, local_pixels * 12, hipMemcpyDeviceToHost, r->lane.stream));
-		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
-	}
-	return SDFR_OK;
+	return out_on_host ? unstage_frame(r, out, d_out, out_bytes, pixel_stats, d_pstat, local_pixels, r->lane.stream) : SDFR_OK;
 }
 
 // sdfr_render_aa (the definition: include/sdfr.h; the plan: sdfr_aa_plan.h; the kernel: sdfr_resolve.hip).  The supersampled frame
@@ -1030,7 +1032,7 @@ static int render_aa_impl(sdfr_renderer *r, int width, int height, int factor, v
 	if (!r || !out) return SDFR_ERR_INVALID_ARGUMENT;
 	if (format != SDFR_RGBA32F && format != SDFR_RGBA16F) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad format");
 	if (aa_factor_log2(factor) < 0) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "factor must be 1, 2, 4 or 8");
-	if (out_on_host != 0 && out_on_host != 1) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "out_on_host must be 0 or 1");
+	if (!is_flag(out_on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "out_on_host must be 0 or 1");
 	if (width < 1 || height < 1 || (int64_t)width * factor * factor > ((int64_t)1 << 30) / height) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
 	SDFR_HIP(hipSetDevice(r->device));
@@ -1051,24 +1053,16 @@ static int render_aa_impl(sdfr_renderer *r, int width, int height, int factor, v
 	const size_t color_bytes = plan.pass_pixels * 16, stats_bytes = pixel_stats ? plan.pass_pixels * 12 : 0;
 	if (r->aa_color.bytes < color_bytes || r->aa_stats.bytes < stats_bytes || !r->aa_totals.ptr)
 	{
-		const int rc = sync_lanes(r); // before a buffer in use is replaced
-		if (rc != SDFR_OK) return rc;
+		const int synced = sync_lanes(r); // before a buffer in use is replaced
+		if (synced != SDFR_OK) return synced;
 		SDFR_HIP(r->aa_color.reserve(color_bytes));
 		SDFR_HIP(r->aa_stats.reserve(stats_bytes));
 		SDFR_HIP(r->aa_totals.reserve(sizeof(RenderTotals)));
 	}
 	void *d_out = out;
 	uint32_t *d_pstat = pixel_stats;
-	if (out_on_host)
-	{
-		SDFR_HIP(r->stage.reserve(image_bytes(pixels, format)));
-		d_out = r->stage.ptr;
-		if (pixel_stats)
-		{
-			SDFR_HIP(r->pstat.reserve(pixels * 12));
-			d_pstat = static_cast<uint32_t *>(r->pstat.ptr);
-		}
-	}
+	int rc = stage_frame(r, out_on_host, image_bytes(pixels, format), pixels, d_out, d_pstat);
+	if (rc != SDFR_OK) return rc;
 	const bool timed = r->profiling;
 	while (timed && r->ev_aa.size() < 2 * (size_t)plan.passes)
 	{
@@ -1081,7 +1075,6 @@ static int render_aa_impl(sdfr_renderer *r, int width, int height, int factor, v
 	const int split_count = r->priv_count, split_period = r->priv_period; // ignored, as a full frame ignores it
 	r->priv_count = 0;
 	r->priv_period = 1;
-	int rc = SDFR_OK;
 	SDFR_HIP(hipEventRecord(r->lane.ev_begin, stream));
 	for (uint32_t p = 0; p < plan.passes && rc == SDFR_OK; ++p)
 	{
@@ -1116,13 +1109,8 @@ static int render_aa_impl(sdfr_renderer *r, int width, int height, int factor, v
 	r->lane.totals_parts = 1;
 	if (rc != SDFR_OK) return rc;
 	r->aa_timed_passes = timed ? (int)plan.passes : 0;
-	if (out_on_host)
-	{
-		SDFR_HIP(hipMemcpyAsync(out, d_out, image_bytes(pixels, format), hipMemcpyDeviceToHost, stream));
-		if (pixel_stats) SDFR_HIP(hipMemcpyAsync(pixel_stats, d_pstat, pixels * 12, hipMemcpyDeviceToHost, stream));
-		SDFR_HIP(hipStreamSynchronize(stream));
-	}
-	else if (r->frames_in_flight == 2)
+	if (out_on_host) return unstage_frame(r, out, d_out, image_bytes(pixels, format), pixel_stats, d_pstat, pixels, stream);
+	if (r->frames_in_flight == 2)
 	{
 		// the lane now also writes this image: the next frame, on the other lane, must see it in the range it checks for overlap
 		auto widen = [](const char *&lo, const char *&hi, const char *a, const char *b) {
@@ -1215,7 +1203,7 @@ int sdfr_postprocess(sdfr_renderer *r, int width, int height, const void *scene_
 {
 	return guarded(r, [&]() -> int {
 		if (!r || !scene_rgba16f || !bloom_scratch_rgba16f || !out_rgba8) return SDFR_ERR_INVALID_ARGUMENT;
-		if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+		if (!frame_size_ok(width, height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 		SDFR_HIP(hipSetDevice(r->device));
 		const size_t flag_bytes = postprocess_flag_bytes(width, height);
 		if (r->post_flags.bytes < flag_bytes) SDFR_HIP(hipStreamSynchronize(r->lane.stream)); // a postprocess still in flight reads the old one

@@ -8,9 +8,12 @@
 #include "sdfr_hostlib.h"
 #include "sdfr_jit.h"
 #include "sdfr_kernels.h"
+#include "sdfr_stage.h"
 
+#include <cassert>
 #include <cstdio>
 #include <exception>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -33,6 +36,38 @@ struct sdfr_device_buffer
 		(void)hipFree(ptr);
 		ptr = nullptr;
 		bytes = 0;
+	}
+};
+
+// One device buffer cut into pieces (sdfr_stage.h): the parts of a workspace, or the device stand-ins of a caller's host arrays, of
+// which the answers are copied back at the end of the call.
+struct Carving
+{
+	size_t offset[sdfr::SDFR_STAGE_MAX_PIECES], total = 0;
+	sdfr_device_buffer *buffer = nullptr;
+	struct { void *host; const void *device; size_t bytes; } answers[sdfr::SDFR_STAGE_MAX_PIECES];
+	int n_answers = 0;
+	Carving(std::initializer_list<size_t> bytes)
+	{
+		assert(bytes.size() <= (size_t)sdfr::SDFR_STAGE_MAX_PIECES);
+		total = sdfr::stage_offsets(bytes.begin(), (int)bytes.size(), offset);
+	}
+	hipError_t reserve(sdfr_device_buffer &b) // (the caller first waits for whatever may still use the old one)
+	{
+		buffer = &b;
+		return b.reserve(total);
+	}
+	template <class T>
+	T *piece(int k) const
+	{
+		return reinterpret_cast<T *>(static_cast<char *>(buffer->ptr) + offset[k]);
+	}
+	// piece k, whose first `bytes` bytes go back to `host` at the end of the call (copy_answers_back, sdfr_api.cpp)
+	template <class T>
+	T *answer(int k, T *host, size_t bytes)
+	{
+		answers[n_answers++] = {host, piece<T>(k), bytes};
+		return piece<T>(k);
 	}
 };
 

@@ -16,7 +16,6 @@
 // libhiprtc.so is opened on first use: the library has no load-time dependency on it.
 #include "sdfr_jit.h"
 #include "sdfr_pixel.h"
-#include "sdfr_query.h"
 
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
@@ -77,6 +76,14 @@ std::string header_dir()
 	return "csrc";
 }
 
+// the query kernels of a run-time scene by kind (QUERY_KERNEL_*): the symbol (its DBG variant: + "_debug"), the kernel template
+// (sdfr_query_kernel.h) and its argument type
+const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_KINDS] = {
+	{"sdfr_jit_query_points", "query_points_kernel", "QueryKernelArgs"},
+	{"sdfr_jit_query_rays", "query_rays_kernel", "QueryKernelArgs"},
+	{"sdfr_jit_query_lattice", "query_lattice_kernel", "LatticeKernelArgs"},
+};
+
 } // namespace
 
 std::string jit_translation_unit(const std::string &scene_source, const std::vector<std::string> &var_slots, bool query)
@@ -93,12 +100,10 @@ std::string jit_translation_unit(const std::string &scene_source, const std::vec
 	tu += "\n#line 1 \"sdfr_jit_kernels\"\n";
 	if (query)
 	{
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_points(QueryKernelArgs a) { query_points_kernel<Scene, false>(a); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_points_debug(QueryKernelArgs a) { query_points_kernel<Scene, true>(a); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_rays(QueryKernelArgs a) { query_rays_kernel<Scene, false>(a); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_rays_debug(QueryKernelArgs a) { query_rays_kernel<Scene, true>(a); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_lattice(LatticeKernelArgs a) { query_lattice_kernel<Scene, false>(a); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_query_lattice_debug(LatticeKernelArgs a) { query_lattice_kernel<Scene, true>(a); }\n";
+		for (const auto &k : k_query_kernels)
+			for (int dbg = 0; dbg < 2; ++dbg)
+				tu += std::string("extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void ") + k.symbol + (dbg ? "_debug(" : "(") + k.args + " a) { " + k.body +
+					"<Scene, " + (dbg ? "true" : "false") + ">(a); }\n";
 	}
 	else
 	{
@@ -207,8 +212,7 @@ hipError_t jit_prepare(const JitScene &js, FrameU &U, hipStream_t stream)
 	return hipStreamSynchronize(stream);
 }
 
-// compiles and loads the scene's query module if this is its first query
-static JitQueryStatus jit_query_module(JitScene &js, int device, std::string &error)
+JitQueryStatus jit_query_kernels(JitScene &js, int device, const QueryKernels *&out, std::string &error)
 {
 	if (!js.query_module)
 	{
@@ -221,75 +225,32 @@ static JitQueryStatus jit_query_module(JitScene &js, int device, std::string &er
 		std::vector<char> code;
 		if (!jit_compile_code(prop.gcnArchName, js.name, js.source, js.var_slots, code, error, true)) return JIT_QUERY_COMPILE;
 		hipModule_t m = nullptr;
+		QueryKernels found = {};
 		hipError_t e = hipModuleLoadData(&m, code.data());
-		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_points, m, "sdfr_jit_query_points");
-		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_points_debug, m, "sdfr_jit_query_points_debug");
-		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_rays, m, "sdfr_jit_query_rays");
-		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_rays_debug, m, "sdfr_jit_query_rays_debug");
-		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_lattice, m, "sdfr_jit_query_lattice");
-		if (e == hipSuccess) e = hipModuleGetFunction(&js.query_lattice_debug, m, "sdfr_jit_query_lattice_debug");
+		for (int kind = 0; kind < QUERY_KERNEL_KINDS; ++kind)
+			for (int dbg = 0; dbg < 2 && e == hipSuccess; ++dbg)
+				e = hipModuleGetFunction(&found.k[kind][dbg].function, m, (std::string(k_query_kernels[kind].symbol) + (dbg ? "_debug" : "")).c_str());
 		if (e != hipSuccess)
 		{
 			error = std::string("loading the scene's query kernels failed: ") + hipGetErrorString(e);
 			if (m) (void)hipModuleUnload(m);
-			js.query_points = js.query_points_debug = js.query_rays = js.query_rays_debug = js.query_lattice = js.query_lattice_debug = nullptr;
 			return JIT_QUERY_HIP;
 		}
 		js.query_module = m;
+		js.query = found;
 	}
+	out = &js.query;
 	return JIT_QUERY_OK;
 }
 
-JitQueryStatus jit_launch_query(JitScene &js, int device, const FrameU &U, const QueryArgs &q, hipStream_t stream, std::string &error)
+PixelKernel jit_pixel_kernel(const JitScene &js, bool dbg)
 {
-	const JitQueryStatus ready = jit_query_module(js, device, error);
-	if (ready != JIT_QUERY_OK) return ready;
-	const bool dbg = frame_needs_debug(U);
-	hipFunction_t fn = q.kind == QUERY_POINTS ? (dbg ? js.query_points_debug : js.query_points) : (dbg ? js.query_rays_debug : js.query_rays);
-	const uint32_t bt = (uint32_t)pixel_block_threads();
-	const uint32_t blocks = ((uint32_t)q.n + bt - 1u) / bt;
-	QueryKernelArgs a;
-	a.U = U;
-	a.q = q;
-	void *args[] = {&a};
-	const hipError_t e = hipModuleLaunchKernel(fn, blocks, 1, 1, bt, 1, 1, 0, stream, args, nullptr);
-	if (e != hipSuccess)
-	{
-		error = std::string("query launch: ") + hipGetErrorString(e);
-		return JIT_QUERY_HIP;
-	}
-	return JIT_QUERY_OK;
-}
-
-JitQueryStatus jit_launch_query_lattice(JitScene &js, int device, const FrameU &U, const LatticeArgs &g, hipStream_t stream, std::string &error)
-{
-	const JitQueryStatus ready = jit_query_module(js, device, error);
-	if (ready != JIT_QUERY_OK) return ready;
-	LatticeKernelArgs a;
-	a.U = U;
-	a.g = g;
-	void *args[] = {&a};
-	const hipError_t e = hipModuleLaunchKernel(frame_needs_debug(U) ? js.query_lattice_debug : js.query_lattice, query_lattice_blocks(g), 1, 1,
-		(uint32_t)pixel_block_threads(), 1, 1, 0, stream, args, nullptr);
-	if (e != hipSuccess)
-	{
-		error = std::string("lattice launch: ") + hipGetErrorString(e);
-		return JIT_QUERY_HIP;
-	}
-	return JIT_QUERY_OK;
-}
-
-hipError_t jit_launch_pixel(const JitScene &js, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,
-	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
-{
-	// the launch of the scenes compiled ahead of time (launch_pixel, sdfr_kernels.hip), with the traits of a run-time scene: one wave
+	// launched like the scenes compiled ahead of time (launch_pixel, sdfr_kernels.hip), with the traits of a run-time scene: one wave
 	// per tile unless asked otherwise, tile rows only (squares of tiles -- RowMap::unit_log2 -- are a built-in scene's own choice)
-	const bool dbg = frame_needs_debug(U);
 	uint32_t name_hash = 2166136261u; // a run-time scene is known by its name
 	for (char ch : js.name) name_hash = (name_hash ^ (unsigned char)ch) * 16777619u;
 	const PixelSceneTraits traits = {false, 8, false, 0x80000000u | name_hash | (dbg ? 1u : 0u)};
-	const PixelKernelRef k = {nullptr, dbg ? js.pixel_debug : js.pixel, nullptr}; // (a module's occupancy is asked on every launch)
-	return launch_pixel(k, traits, U, rm, out, format, pixel_stats, totals, ws, stream, launch_mode);
+	return {{nullptr, dbg ? js.pixel_debug : js.pixel}, nullptr, traits}; // (a module's occupancy is asked on every launch)
 }
 
 } // namespace sdfr

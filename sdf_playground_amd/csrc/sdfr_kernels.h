@@ -37,30 +37,38 @@ struct SceneKernels
 	bool persistent_tiles, square_units; // PersistentTiles, SquareUnits (sdfr_render_pixel.h)
 	int retire_after, tile_w_log2;       // RetireAfter, SceneTileShape
 };
-// ... and a scene's query unit (sdfr_query_scene.hip)
-struct SceneQueryKernels
+// How the host names a kernel: a kernel of this library by its host pointer (`kernel`), or a function of a module loaded at run
+// time (`function`, sdfr_jit.cpp).  At a launch, this field is all that differs between a built-in scene and a run-time one.
+struct KernelRef
 {
-	const void *points[2], *rays[2], *lattice[2];
+	const void *kernel;
+	hipFunction_t function;
+};
+// one launch of `blocks` blocks of `threads` threads on `stream`, the kernel's parameters by address
+hipError_t launch_kernel(const KernelRef &k, uint32_t blocks, uint32_t threads, void **args, hipStream_t stream);
+// A scene's query kernels [kind][DBG]: a built-in scene's query unit exports them (sdfr_query_scene.hip), a run-time scene's
+// query module is looked up into the same table (jit_query_kernels, sdfr_jit.h)
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_KINDS = 3 }; // (rays: picks too)
+struct QueryKernels
+{
+	KernelRef k[QUERY_KERNEL_KINDS][2];
 };
 // a unit names its getter by its scene's index: scene_kernels_<index>(), scene_query_kernels_<index>()
 #define SDFR_CAT2(a, b) a##b
 #define SDFR_CAT(a, b) SDFR_CAT2(a, b)
 const SceneKernels *scene_kernels(int scene); // null: not a scene of the registry
-const SceneQueryKernels *scene_query_kernels(int scene);
-
-hipError_t launch_pixel_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
-	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode = 0);
+const QueryKernels *scene_query_kernels(int scene);
 
 hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events,
 	int *n_rounds_out);
 
-// one query (sdfr_query.h) of a built-in scene: q.n > 0 items, every pointer device memory
+// one query (sdfr_query.h) by a scene's kernel of q's kind (points; rays or picks) for U: q.n > 0 items, every pointer device memory
 struct QueryArgs;
-hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream);
-// the distance query over a lattice (sdfr_query.h: LatticeArgs) of a built-in scene
+hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream);
+// the distance query over a lattice (sdfr_query.h: LatticeArgs) by a scene's lattice kernel for U
 struct LatticeArgs;
-hipError_t launch_query_lattice(int scene, const FrameU &U, const LatticeArgs &g, hipStream_t stream);
+hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const LatticeArgs &g, hipStream_t stream);
 uint32_t query_lattice_blocks(const LatticeArgs &g); // blocks of one wave that cover the lattice in the mapping g.rows selects
 
 // Surface nets over a lattice of distances (sdfr_mesh.h, sdfr_mesh.hip), every pointer device memory.  launch_mesh_count: the vertex
@@ -98,19 +106,19 @@ hipError_t launch_reduce_totals(const RenderTotals *partials, uint32_t n_blocks,
 	uint32_t feedback_rows, unsigned long long frame_pixels, uint32_t feedback_key);
 int pixel_tile_cursor_words();
 int scene_tile_w_log2(int scene); // the tile shape a built-in scene asks for (SceneTileShape); 3 = 8 x 8, also for run-time scenes
-// How launch_pixel reaches a pixel kernel: a kernel of this library by its host pointer (`kernel`), or a function of a module
-// loaded at run time (`function`, sdfr_jit.cpp).  blocks_per_cu: where the occupancy query's answer is kept between launches
-// (0 = not asked yet), or null to ask on every launch.
-struct PixelKernelRef
+// A scene's pixel kernel and how the scene wants it launched.  blocks_per_cu: where the occupancy query's answer is kept between
+// launches (0 = not asked yet), or null to ask on every launch.
+struct PixelKernel
 {
-	const void *kernel;
-	hipFunction_t function;
+	KernelRef k;
 	int *blocks_per_cu;
+	PixelSceneTraits traits;
 };
+bool scene_pixel_kernel(int scene, bool dbg, PixelKernel &out); // of a built-in scene (a run-time scene's: jit_pixel_kernel); false: not a scene of the registry
 // One launch of the pixel schedule, for built-in and run-time scenes alike: reads the developer knobs, asks how many blocks of the
 // kernel stay resident, plans (plan_pixel_launch, sdfr_launch_plan.h), launches the kernel and then the fold (launch_reduce_totals).
-hipError_t launch_pixel(const PixelKernelRef &k, const PixelSceneTraits &scene, const FrameU &U, const RowMap &rm, void *out, int format,
-	uint32_t *pixel_stats, RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode);
+hipError_t launch_pixel(const PixelKernel &pk, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,
+	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode);
 
 int pixel_block_threads(); // block size of the pixel kernels (partials are sized by it)
 int device_cu_count(int device);

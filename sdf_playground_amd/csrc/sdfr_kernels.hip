@@ -326,7 +326,7 @@ int device_cu_count(int device)
 // the scenes' kernels and launch traits: one compile unit per scene of the registry exports them (sdfr_kernels_scene.hip, sdfr_query_scene.hip)
 #define SDFR_DECLARE_SCENE(I, S) \
 	const SceneKernels *SDFR_CAT(scene_kernels_, I)(); \
-	const SceneQueryKernels *SDFR_CAT(scene_query_kernels_, I)();
+	const QueryKernels *SDFR_CAT(scene_query_kernels_, I)();
 SDFR_FOR_EACH_SCENE(SDFR_DECLARE_SCENE)
 #undef SDFR_DECLARE_SCENE
 const SceneKernels *scene_kernels(int scene)
@@ -335,7 +335,7 @@ const SceneKernels *scene_kernels(int scene)
 	switch (scene) { SDFR_FOR_EACH_SCENE(SDFR_SCENE_CASE) default: return nullptr; } // not a scene of the registry
 #undef SDFR_SCENE_CASE
 }
-const SceneQueryKernels *scene_query_kernels(int scene)
+const QueryKernels *scene_query_kernels(int scene)
 {
 #define SDFR_SCENE_CASE(I, S) case I: return SDFR_CAT(scene_query_kernels_, I)();
 	switch (scene) { SDFR_FOR_EACH_SCENE(SDFR_SCENE_CASE) default: return nullptr; }
@@ -355,8 +355,15 @@ static int env_int(const char *name, int unset)
 	return e ? atoi(e) : unset;
 }
 
-hipError_t launch_pixel(const PixelKernelRef &k, const PixelSceneTraits &scene, const FrameU &U, const RowMap &rm, void *out, int format,
-	uint32_t *pixel_stats, RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
+hipError_t launch_kernel(const KernelRef &k, uint32_t blocks, uint32_t threads, void **args, hipStream_t stream)
+{
+	if (k.function) return hipModuleLaunchKernel(k.function, blocks, 1, 1, threads, 1, 1, 0, stream, args, nullptr);
+	(void)hipLaunchKernel(k.kernel, dim3(blocks), dim3(threads), args, 0, stream);
+	return hipGetLastError();
+}
+
+hipError_t launch_pixel(const PixelKernel &pk, const FrameU &U, const RowMap &rm, void *out, int format, uint32_t *pixel_stats,
+	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
 {
 	static_assert(SDFR_PIXEL_BLOCK == SDFR_TILE_ITEMS, "the plan counts one block per tile");
 	static const PixelLaunchKnobs knobs = [] { // developer knobs, read once
@@ -371,41 +378,33 @@ hipError_t launch_pixel(const PixelKernelRef &k, const PixelSceneTraits &scene, 
 	// a persistent launch: as many blocks as stay resident, each pulling tiles until none is left
 	// (TileQueue, sdfr_pixel_kernel.h).  The occupancy query may over-state by a block per CU for
 	// SGPR-heavy kernels (MI355X_MICROARCH.md); a surplus block simply starts when another has ended.
-	int blocks_per_cu = k.blocks_per_cu ? *k.blocks_per_cu : 0;
+	int blocks_per_cu = pk.blocks_per_cu ? *pk.blocks_per_cu : 0;
 	if (blocks_per_cu == 0)
 	{
-		const hipError_t e = k.function ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k.function, SDFR_PIXEL_BLOCK, 0)
-										: hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k.kernel, SDFR_PIXEL_BLOCK, 0);
+		const hipError_t e = pk.k.function ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, pk.k.function, SDFR_PIXEL_BLOCK, 0)
+										   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, pk.k.kernel, SDFR_PIXEL_BLOCK, 0);
 		if (e != hipSuccess || blocks_per_cu < 1) blocks_per_cu = 1;
-		if (k.blocks_per_cu) *k.blocks_per_cu = blocks_per_cu;
+		if (pk.blocks_per_cu) *pk.blocks_per_cu = blocks_per_cu;
 	}
 	int device = 0;
 	(void)hipGetDevice(&device);
-	const PixelLaunchPlan plan = plan_pixel_launch(scene, knobs, launch_mode, U.width, rm, ws.capacity, blocks_per_cu, device_cu_count(device));
+	const PixelLaunchPlan plan = plan_pixel_launch(pk.traits, knobs, launch_mode, U.width, rm, ws.capacity, blocks_per_cu, device_cu_count(device));
 	if (!plan.fits) return hipErrorInvalidValue;
 	PixelKernelArgs args = {U, plan.rows, plan.n_work, format, out, pixel_stats, ws.partials, totals, ws.ray_queue, ws.capacity,
 		plan.tile_cursors ? ws.tile_cursors : nullptr};
 	void *kernel_args[] = {&args};
-	if (k.function)
-	{
-		const hipError_t e = hipModuleLaunchKernel(k.function, plan.blocks, 1, 1, SDFR_PIXEL_BLOCK, 1, 1, 0, stream, kernel_args, nullptr);
-		if (e != hipSuccess) return e;
-	}
-	else
-		(void)hipLaunchKernel(k.kernel, dim3(plan.blocks), dim3(SDFR_PIXEL_BLOCK), kernel_args, 0, stream); // (a failure is the last error the fold's launcher returns)
+	const hipError_t e = launch_kernel(pk.k, plan.blocks, SDFR_PIXEL_BLOCK, kernel_args, stream);
+	if (e != hipSuccess) return e;
 	return launch_reduce_totals(ws.partials, plan.blocks, totals, stream, ws.tile_cursors, plan.feedback_rows, plan.frame_pixels, plan.rows.feedback_key);
 }
 
-hipError_t launch_pixel_schedule(int scene, const FrameU &U, const RowMap &rows, void *out, int format, uint32_t *pixel_stats,
-	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, int launch_mode)
+bool scene_pixel_kernel(int scene, bool dbg, PixelKernel &out)
 {
 	const SceneKernels *sk = scene_kernels(scene);
-	if (!sk) return hipErrorInvalidValue;
-	const int dbg = frame_needs_debug(U) ? 1 : 0;
+	if (!sk) return false;
 	static int blocks_per_cu[SDFR_SCENE_COUNT][2]; // asked once per kernel and process (not per device: every device of a process is taken to be alike)
-	const PixelKernelRef k = {sk->pixel[dbg], nullptr, &blocks_per_cu[scene][dbg]};
-	const PixelSceneTraits traits = {sk->persistent_tiles, sk->retire_after, sk->square_units, (uint32_t)scene * 2u + (uint32_t)dbg};
-	return launch_pixel(k, traits, U, rows, out, format, pixel_stats, totals, ws, stream, launch_mode);
+	out = {{sk->pixel[dbg], nullptr}, &blocks_per_cu[scene][dbg], {sk->persistent_tiles, sk->retire_after, sk->square_units, (uint32_t)scene * 2u + (uint32_t)dbg}};
+	return true;
 }
 
 // ---- WAVEFRONT schedule ----
@@ -466,18 +465,13 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 }
 
 // ---- queries (kernel bodies: sdfr_query_kernel.h) ----
-hipError_t launch_query(int scene, const FrameU &U, const QueryArgs &q, hipStream_t stream)
+hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
-	const SceneQueryKernels *qk = scene_query_kernels(scene);
-	if (!qk) return hipErrorInvalidValue;
-	const int dbg = frame_needs_debug(U) ? 1 : 0;
-	const uint32_t blocks = ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK;
 	QueryKernelArgs a;
 	a.U = U;
 	a.q = q;
 	void *args[] = {&a};
-	(void)hipLaunchKernel(q.kind == QUERY_POINTS ? qk->points[dbg] : qk->rays[dbg], dim3(blocks), dim3(SDFR_PIXEL_BLOCK), args, 0, stream);
-	return hipGetLastError();
+	return launch_kernel(k, ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK, SDFR_PIXEL_BLOCK, args, stream);
 }
 
 uint32_t query_lattice_blocks(const LatticeArgs &g)
@@ -486,16 +480,13 @@ uint32_t query_lattice_blocks(const LatticeArgs &g)
 	return g.rows ? (px * py * pz + 63u) / 64u : ((px + 3u) / 4u) * ((py + 3u) / 4u) * ((pz + 3u) / 4u);
 }
 
-hipError_t launch_query_lattice(int scene, const FrameU &U, const LatticeArgs &g, hipStream_t stream)
+hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const LatticeArgs &g, hipStream_t stream)
 {
-	const SceneQueryKernels *qk = scene_query_kernels(scene);
-	if (!qk) return hipErrorInvalidValue;
 	LatticeKernelArgs a;
 	a.U = U;
 	a.g = g;
 	void *args[] = {&a};
-	(void)hipLaunchKernel(qk->lattice[frame_needs_debug(U) ? 1 : 0], dim3(query_lattice_blocks(g)), dim3(SDFR_PIXEL_BLOCK), args, 0, stream);
-	return hipGetLastError();
+	return launch_kernel(k, query_lattice_blocks(g), SDFR_PIXEL_BLOCK, args, stream);
 }
 
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,

@@ -41,18 +41,18 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_lattice(LatticeKernelArgs
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
 // what this unit exports (scene_query_kernels, launch_query: sdfr_kernels.hip)
-const SceneQueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
+const QueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
 {
 	// (the debug variants first: the order the kernels are first named in is their order in the unit's code object, kept as it was)
-	static const SceneQueryKernels k = [] {
-		SceneQueryKernels k;
-		k.points[1] = (const void *)k_query_points<UnitScene, true>;
-		k.rays[1] = (const void *)k_query_rays<UnitScene, true>;
-		k.points[0] = (const void *)k_query_points<UnitScene, false>;
-		k.rays[0] = (const void *)k_query_rays<UnitScene, false>;
-		k.lattice[1] = (const void *)k_query_lattice<UnitScene, true>;
-		k.lattice[0] = (const void *)k_query_lattice<UnitScene, false>;
-		return k;
+	static const QueryKernels k = [] {
+		QueryKernels q = {};
+		q.k[QUERY_KERNEL_POINTS][1].kernel = (const void *)k_query_points<UnitScene, true>;
+		q.k[QUERY_KERNEL_RAYS][1].kernel = (const void *)k_query_rays<UnitScene, true>;
+		q.k[QUERY_KERNEL_POINTS][0].kernel = (const void *)k_query_points<UnitScene, false>;
+		q.k[QUERY_KERNEL_RAYS][0].kernel = (const void *)k_query_rays<UnitScene, false>;
+		q.k[QUERY_KERNEL_LATTICE][1].kernel = (const void *)k_query_lattice<UnitScene, true>;
+		q.k[QUERY_KERNEL_LATTICE][0].kernel = (const void *)k_query_lattice<UnitScene, false>;
+		return q;
 	}();
 	return &k;
 }

@@ -1,6 +1,7 @@
 """GPU tier of the scene queries (sdfr_query_distance, sdfr_query_rays, sdfr_pick) through libsdfr.so: bit for bit against the
 oracle's definitions (tests/cpp/query_oracle.cpp) for every scene compiled ahead of time and the run-time scenes with an oracle
-twin, host and device memory; the run-time scenes' lazily compiled query module; step shortcuts; agreement with the renderer's own
+twin, host and device memory; the run-time scenes' lazily compiled query module; one handle going from a built-in scene to a
+run-time one and back through every entry point that launches the loaded scene; step shortcuts; agreement with the renderer's own
 primary rays; no side effects on rendering; sizes and argument checks."""
 import os
 import zlib
@@ -148,6 +149,80 @@ def test_runtime_query_module_follows_the_scene(renderer):
         of = qu.frame(scene, 0.3, W, H)
         _setup(renderer, scene, of)
         _check_all(renderer, scene, of, seed=52, device=False)
+
+
+# ---- one handle, built-in scene -> run-time scene -> the same built-in scene: every launch of the loaded scene -------------------------
+# 130 items: two full waves and a partial one; a pick list with one pixel outside the frame; 5 x 4 x 3 cells: a 6 x 5 x 4 lattice, no
+# axis a multiple of the lattice kernel's 4-point brick; a 24 x 17 frame: ragged against the 8 x 8 tile
+SW_N, SW_W, SW_H = 130, 24, 17
+SW_GRID = ((-5.35, -0.3, -2.55), 0.25, (5, 4, 3))  # over the floor, and in the labyrinth over a wall's corner
+_switch_refs = {}
+
+
+def _switch_reference(scene):
+    """the inputs of a round and the oracle's answers to them, in the order _switch_answers gives the library's (computed once)"""
+    if scene not in _switch_refs:
+        import mesh_util as mu
+
+        of = qu.frame(scene, 0.5, SW_W, SW_H)
+        pts = qu.point_samples(scene, of, 91, SW_N)
+        o, dirs = qu.ray_samples(of, 92, SW_N)
+        px = np.concatenate([qu.pick_grid(SW_W, SW_H)[:3 * (SW_N - 1):3], [[SW_W, 3]]]).astype(np.int32)
+        assert len(pts) == len(o) == len(px) == SW_N
+        D, _ = qu.oracle_points(scene, of, mu.lattice_points(*SW_GRID), normals=False)
+        pos, idx = mu.surface_nets(D, *SW_GRID, 0.0)
+        assert len(pos) > 0 and len(idx) > 0
+        img, st, _ = qu.po.render(scene, of, stats=True)
+        want = list(qu.oracle_points(scene, of, pts)) + [qu.oracle_rays(scene, of, o, dirs), qu.oracle_pick(scene, of, px), pos,
+                                                          qu.oracle_points(scene, of, pos)[1], idx, img, st]
+        _switch_refs[scene] = (of, (pts, o, dirs, px), want)
+    return _switch_refs[scene]
+
+
+SWITCH_ANSWERS = ("distance", "normal", "rays", "pick", "mesh positions", "mesh normals", "mesh indices", "image", "pixel_stats")
+
+
+def _switch_answers(r, inputs, device):
+    """a point query with normals, a ray query, a pick, a mesh extraction with normals and a render with pixel_stats"""
+    import torch
+
+    pts, o, dirs, px = (_torch_dev(a) for a in inputs) if device else inputs
+    d, n = r.queryDistance(pts, normals=True)
+    rays, picks = r.queryRays(o, dirs), r.pick(px, SW_W, SW_H)
+    pos, nrm, idx = r.extractMesh(*SW_GRID, device=device)
+    if device:
+        img = torch.empty((SW_H, SW_W, 4), dtype=torch.float32, device="cuda")
+        st = torch.empty((SW_H, SW_W, 3), dtype=torch.int32, device="cuda")
+        r.render(None, SW_W, SW_H, out=img, pixel_stats=st)
+        r.sync()
+        torch.cuda.synchronize()
+        d, n, rays, picks, pos, nrm, idx, img, st = (t.cpu().numpy() for t in (d, n, rays, picks, pos, nrm, idx, img, st))
+    else:
+        img, st = r.render(None, SW_W, SW_H, pixel_stats=True)
+    return [d, n, qu.hits_array(rays), qu.hits_array(picks), pos, nrm, idx.view(np.uint32), img, st.view(np.uint32)]
+
+
+def test_one_handle_from_a_builtin_scene_to_a_runtime_scene_and_back():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    try:
+        rounds = []
+        for scene in ("labyrinth", qu.HLSL[0], "labyrinth"):
+            of, inputs, want = _switch_reference(scene)
+            _setup(r, scene, of)
+            rounds.append([])
+            for device in (False, True):
+                got = _switch_answers(r, inputs, device)
+                rounds[-1] += got
+                for what, g, w in zip(SWITCH_ANSWERS, got, want):
+                    assert g.shape == w.shape, (scene, what, device, g.shape, w.shape)
+                    qu.assert_same("%s %s (%s)" % (scene, what, "device" if device else "host"), g, w)
+        assert (rounds[0][3][-1, 10], rounds[1][3][-1, 10]) == (0xffffffff, 0xffffffff)  # the pixel outside the frame: hit = -1
+        for a, b in zip(rounds[0], rounds[2]):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    finally:
+        r.close()
 
 
 @pytest.mark.parametrize("scene", ["labyrinth", "lense", "cube_sea"])

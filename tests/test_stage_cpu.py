@@ -1,0 +1,73 @@
+"""CPU tier: how one device buffer is cut into the stand-ins of a caller's host arrays (sdf_playground_amd/csrc/sdfr_stage.h, built as
+the stand-alone program tests/cpp/stage_host.cpp).  The offsets and totals of the header against the formulas the entry points
+carried before they shared it (query_impl and mesh_impl), spelled out here a second time."""
+import os
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
+BUILD = os.path.join(HERE, "cpp", "_build")
+POINTS, RAYS, PICK = 0, 1, 2
+HIT_BYTES = 48
+
+
+@pytest.fixture(scope="module")
+def exe():
+    os.makedirs(BUILD, exist_ok=True)
+    out = os.path.join(BUILD, "stage_host")
+    src = os.path.join(HERE, "cpp", "stage_host.cpp")
+    deps = [src, os.path.join(CSRC, "sdfr_stage.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        # plain g++: host arithmetic, no HIP header on the include path
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I" + CSRC, "-o", out + ".tmp", src], check=True)
+        os.replace(out + ".tmp", out)
+    return out
+
+
+def carve(exe, lists):
+    """[[bytes of each piece]] -> [(offsets, total)]"""
+    text = "".join(" ".join(str(b) for b in pieces) + "\n" for pieces in lists)
+    lines = subprocess.run([exe], input=text, check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(lines) == len(lists)
+    return [([int(x) for x in l.split()[:-1]], int(l.split()[-1])) for l in lines]
+
+
+def up(b):
+    return (b + 255) & ~255
+
+
+def test_query_staging(exe):
+    """query_impl: inputs, then answers -- in0, in1, out0, out1"""
+    cases, want = [], []
+    for kind in (POINTS, RAYS, PICK):
+        for normals in (False, True):
+            for n in (1, 21, 64, 65, 1000):
+                in0 = n * 8 if kind == PICK else n * 12
+                in1 = n * 12 if kind == RAYS else 0
+                out0 = n * 4 if kind == POINTS else n * HIT_BYTES
+                out1 = n * 12 if kind == POINTS and normals else 0
+                cases.append([in0, in1, out0, out1])
+                d_in1 = up(in0)
+                d_out0 = d_in1 + up(in1)
+                d_out1 = d_out0 + up(out0)
+                want.append(([0, d_in1, d_out0, d_out1], up(in0) + up(in1) + up(out0) + up(out1)))
+    assert len(cases) == 30
+    assert carve(exe, cases) == want
+
+
+def test_mesh_staging(exe):
+    """mesh_impl's host arrays: positions, normals (or none), indices"""
+    cases, want = [], []
+    for V, T in ((1, 0), (5, 6), (1000, 1996)):
+        for normals in (False, True):
+            b_pos = up(V * 12)
+            b_nrm = up(V * 12) if normals else 0
+            cases.append([V * 12, V * 12 if normals else 0, T * 12])
+            want.append(([0, b_pos, b_pos + b_nrm], b_pos + b_nrm + up(T * 12)))
+    assert carve(exe, cases) == want
+
+
+def test_an_empty_piece_takes_no_room(exe):
+    assert carve(exe, [[100, 0, 300], [256, 0, 0, 1], [0, 0, 7], []]) == [([0, 256, 256], 768), ([0, 256, 256, 256], 512), ([0, 0, 0], 256), ([], 0)]
