@@ -359,6 +359,60 @@ int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const flo
  * pixel's), marched to limits.range, otherwise as sdfr_query_rays.  A pixel outside the frame gives hit = -1. */
 int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host);
 
+/* ---- what the surface looks like at a ray's first hit (DESIGN.md "Surface queries"): the driver's lines between the hit and the
+ *      light loop (:333-481), restated as a record.  The surface point is the ray query's: pos, dir, camera_distance = t, the ray's
+ *      offsets, the driver's normal, iterations, scene_distance.  After map_material (:333-353): the marble extension
+ *      (sdfr_limits.extension_marble_reflection), new_normal (:362), and the material switch (:430-481) with the procedural wood,
+ *      marble and fire -- whose view direction is the ray's -- and the debug views.  Nothing is spawned and no light is looked at.
+ *      The entries are queries in every respect listed above: on_host, what is latched, the stream, no effect on stats, timings or
+ *      the row order, n = 0, the argument errors.  `surfaces` is required; `hits` (NULL: not wanted) gets what sdfr_query_rays /
+ *      sdfr_pick give for the same items, bit for bit. ---------------------------------------------------------------------------- */
+typedef struct sdfr_surface
+{
+	uint32_t material_id;    /* material_output.material_id after map_material (:333-353) */
+	uint32_t flags;          /* SDFR_SURFACE_USE_HDR: material_output.use_hdr; SDFR_SURFACE_LIT: the driver's use_light after the switch */
+	uint32_t max_cost;       /* material_output.max_cost */
+	int32_t valid;           /* 1 hit, 0 miss, -1 invalid item (a pixel outside the frame); unless 1, every other word is 0 */
+	float albedo[3];         /* the driver's local diffuse_color after the switch: diffuse_color.xyz plus the wood / marble term */
+	float alpha;             /* material_output.diffuse_color.w after the switch (fire replaces it) */
+	float specular[3];       /* material_output.specular_color.xyz */
+	float specular_power;    /* ... .w */
+	float emissive[3];       /* material_output.emissive_color */
+	float optical_index;     /* material_output.optical_index */
+	float unlit[3];          /* the driver's `color` right after the switch, before any light: the heat colour of MATERIAL_ITER (from the
+	                            hit's iterations and limits.iter_count - 1), the diffuse of MATERIAL_PLAIN, the two normal views, the debug
+	                            plane's colour, the fire's colour; 0 for a lit material */
+	float reserved0;         /* 0 */
+	float reflection[3];     /* material_output.reflection_color, after the marble extension's line */
+	float reserved1;         /* 0 */
+	float refraction[3];     /* material_output.refraction_color */
+	float reserved2;         /* 0 */
+	float shading_normal[3]; /* new_normal = lerp(obj_normal, material_output.normal.xyz, material_output.normal.w) (:362) */
+	float reserved3;         /* 0 */
+} sdfr_surface;              /* 128 bytes: eight 16-byte stores per item (device arrays aligned to 16 bytes; any other alignment: word stores) */
+#define SDFR_SURFACE_USE_HDR 1u
+#define SDFR_SURFACE_LIT 2u
+
+/* sdfr_query_rays, and the surface at each hit. */
+int sdfr_query_ray_surfaces(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits /* or NULL */,
+	sdfr_surface *surfaces, int on_host);
+
+/* sdfr_pick, and the surface under each pixel.  pixels_xy = NULL: the G-buffer of the frame -- every pixel, item y * width + x is pixel
+ * (x, y), n must be width * height (else SDFR_ERR_INVALID_ARGUMENT); nothing is uploaded, and a wave takes an 8 x 8 tile of pixels as
+ * in a render. */
+int sdfr_pick_surfaces(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy /* or NULL */, sdfr_hit *hits /* or NULL */,
+	sdfr_surface *surfaces, int on_host);
+
+/* The surface at the vertices of a mesh (sdfr_mesh_extract's positions and normals, or any [n][3] arrays like them).  A scene selects
+ * its material where |distance| < limits.dist_eps, and a surface-nets vertex lies a fraction of a cell off the surface: asking the
+ * scene AT the vertex finds no material.  So vertex i is looked at from outside, by a ray whose march ends on the surface as the
+ * driver's does: origin = positions[i] + reach * normals[i] per component (one multiply, then one add, unfused), dir = -normals[i]
+ * as given, max_distance = 2 * reach; otherwise sdfr_query_ray_surfaces.  reach must be finite and > 0 (else
+ * SDFR_ERR_INVALID_ARGUMENT); a cell or two is a good value.  A vertex whose ray misses (a degenerate normal, a feature thinner than
+ * the lattice resolves) gets valid = 0. */
+int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits /* or NULL */,
+	sdfr_surface *surfaces, int on_host);
+
 /* ---- the loaded scene as a triangle mesh: naive surface nets over a lattice of scene distances (no counterpart in the reference;
  *      DESIGN.md "Mesh extraction").  One vertex per grid cell the surface passes through, one quad (two triangles) per lattice edge
  *      that changes sign: an indexed mesh with shared vertices, closed wherever the surface stays inside the grid.  All arithmetic

@@ -130,6 +130,23 @@ public:
 		return handle && pushState(&camera) && sdfr_pick(handle, width, height, n, pixels_xy, hits, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// What the surface looks like at the first hit (sdfr_query_ray_surfaces, sdfr_pick_surfaces, sdfr_mesh_surfaces in sdfr.h): hits may
+	// be null; pickSurfaces with pixels_xy null is the G-buffer of the frame, n = width * height.
+	bool queryRaySurfaces(int64_t n, const float *origins, const float *dirs, sdfr_hit *hits, sdfr_surface *surfaces, float max_distance = 0.f,
+		bool on_host = true)
+	{
+		return handle && pushState() && sdfr_query_ray_surfaces(handle, n, origins, dirs, max_distance, hits, surfaces, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool pickSurfaces(const Camera &camera, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, sdfr_surface *surfaces,
+		bool on_host = true)
+	{
+		return handle && pushState(&camera) && sdfr_pick_surfaces(handle, width, height, n, pixels_xy, hits, surfaces, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool meshSurfaces(int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits, sdfr_surface *surfaces, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_mesh_surfaces(handle, n, positions, normals, reach, hits, surfaces, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// The loaded scene as a triangle mesh (sdfr_mesh_extract in sdfr.h: surface nets over `grid`), with this renderer's variables and
 	// time.  counts is always filled; the arrays only if both capacities suffice (capacities 0, arrays null: the counting call).
 	bool extractMesh(const sdfr_mesh_grid &grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals, uint32_t *indices,

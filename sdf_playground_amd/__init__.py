@@ -84,6 +84,15 @@ class MeshCounts(ctypes.Structure):  # sdfr_mesh_counts
 HIT_DTYPE = np.dtype([("t", np.float32), ("distance", np.float32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,)),
                       ("iterations", np.uint32), ("material_id", np.uint32), ("hit", np.int32), ("reserved", np.uint32)])
 assert HIT_DTYPE.itemsize == 48
+# sdfr_surface (include/sdfr.h): what the surface looks like at a hit, 128 bytes
+SURFACE_DTYPE = np.dtype([("material_id", np.uint32), ("flags", np.uint32), ("max_cost", np.uint32), ("valid", np.int32),
+                          ("albedo", np.float32, (3,)), ("alpha", np.float32), ("specular", np.float32, (3,)), ("specular_power", np.float32),
+                          ("emissive", np.float32, (3,)), ("optical_index", np.float32), ("unlit", np.float32, (3,)), ("reserved0", np.float32),
+                          ("reflection", np.float32, (3,)), ("reserved1", np.float32), ("refraction", np.float32, (3,)), ("reserved2", np.float32),
+                          ("shading_normal", np.float32, (3,)), ("reserved3", np.float32)])
+assert SURFACE_DTYPE.itemsize == 128
+SURFACE_USE_HDR = 1
+SURFACE_LIT = 2
 
 
 # every symbol include/sdfr.h declares (tests check that the library exports all of them)
@@ -97,7 +106,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_comm_unique_id", "sdfr_comm_create", "sdfr_comm_create_all", "sdfr_comm_destroy", "sdfr_comm_close", "sdfr_comm_library_info", "sdfr_comm_rank", "sdfr_comm_world",
     "sdfr_comm_last_error", "sdfr_comm_selftest", "sdfr_render_gather", "sdfr_render_gather_all", "sdfr_set_launch_mode", "sdfr_set_step_shortcuts",
     "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick", "sdfr_mesh_extract", "sdfr_mesh_get_timings",
-    "sdfr_render_aa",
+    "sdfr_render_aa", "sdfr_query_ray_surfaces", "sdfr_pick_surfaces", "sdfr_mesh_surfaces",
 ]
 
 _lib = None
@@ -197,6 +206,9 @@ def load_library():
     L.sdfr_query_distance.argtypes = [vp, i64, vp, vp, vp, ci]
     L.sdfr_query_rays.argtypes = [vp, i64, vp, vp, cf, vp, ci]
     L.sdfr_pick.argtypes = [vp, ci, ci, i64, vp, vp, ci]
+    L.sdfr_query_ray_surfaces.argtypes = [vp, i64, vp, vp, cf, vp, vp, ci]
+    L.sdfr_pick_surfaces.argtypes = [vp, ci, ci, i64, vp, vp, vp, ci]
+    L.sdfr_mesh_surfaces.argtypes = [vp, i64, vp, vp, cf, vp, vp, ci]
     L.sdfr_mesh_extract.argtypes = [vp, ctypes.POINTER(MeshGrid), i64, i64, vp, vp, vp, ctypes.POINTER(MeshCounts), ci]
     L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
     L.sdfr_render_gather.argtypes = [vp, vp, ci, ci, vp, ci, ci]
@@ -581,11 +593,85 @@ class SDFRenderer:
                                       hits.ctypes.data_as(ctypes.c_void_p), 1))
         return hits
 
+    # ---- what the surface looks like at a hit (sdfr_query_ray_surfaces / sdfr_pick_surfaces / sdfr_mesh_surfaces; DESIGN.md "Surface
+    # queries").  numpy arrays in: SURFACE_DTYPE records out (and HIT_DTYPE records with hits=True).  Device tensors in: [n, 32] (and
+    # [n, 12]) float32 device tensors out, whose integer fields (columns 0-3 of a surface) are read with .view(torch.int32).
+    def _surfaces(self, call, n, inputs, like, hits):
+        """one surface query: call(hits pointer, surfaces pointer, on_host) -> status; `like`: the device tensor that decides the
+        device path, or None for numpy"""
+        if like is not None:
+            import torch
+
+            h = torch.empty((n, 12), dtype=torch.float32, device=like.device) if hits else None
+            s = torch.empty((n, 32), dtype=torch.float32, device=like.device)
+            self._check(call(*inputs, self._dev(h, 12 * n, "hits", hits=True) if hits and n else None, self._dev(s, 32 * n, "surfaces") if n else None, 0))
+        else:
+            h = np.zeros(n, HIT_DTYPE) if hits else None
+            s = np.zeros(n, SURFACE_DTYPE)
+            self._check(call(*inputs, h.ctypes.data_as(ctypes.c_void_p) if hits else None, s.ctypes.data_as(ctypes.c_void_p), 1))
+        return (h, s) if hits else s
+
+    def queryRaySurfaces(self, origins, dirs, max_distance=0.0, hits=False):
+        """The surface at the first hit along rays (as queryRays): SURFACE_DTYPE records [n], or (hits, surfaces) with hits=True."""
+        if hasattr(origins, "data_ptr"):
+            n = origins.numel() // 3
+            inputs = (self._h, n, self._dev(origins, 3 * n, "origins"), self._dev(dirs, 3 * n, "dirs"), float(max_distance))
+            return self._surfaces(self._L.sdfr_query_ray_surfaces, n, inputs, origins, hits)
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        assert o.shape == d.shape
+        inputs = (self._h, o.shape[0], o.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p), float(max_distance))
+        return self._surfaces(self._L.sdfr_query_ray_surfaces, o.shape[0], inputs, None, hits)
+
+    def pickSurfaces(self, pixels_xy, width, height, hits=False, device=False):
+        """The surface under pixels [n, 2] of a width x height frame of the current camera (as pick).  pixels_xy=None: the G-buffer,
+        every pixel of the frame in row-major order (height * width records; device=True: as device tensors)."""
+        width, height = int(width), int(height)
+        if pixels_xy is None:
+            like = None
+            if device:
+                import torch
+
+                like = torch.empty(0, device=torch.device("cuda", self.device))
+            return self._surfaces(self._L.sdfr_pick_surfaces, width * height, (self._h, width, height, width * height, None), like, hits)
+        if hasattr(pixels_xy, "data_ptr"):
+            n = pixels_xy.numel() // 2
+            inputs = (self._h, width, height, n, self._dev(pixels_xy, 2 * n, "pixels_xy", ints=True))
+            return self._surfaces(self._L.sdfr_pick_surfaces, n, inputs, pixels_xy, hits)
+        px = np.ascontiguousarray(pixels_xy, np.int32).reshape(-1, 2)
+        inputs = (self._h, width, height, px.shape[0], px.ctypes.data_as(ctypes.c_void_p))
+        return self._surfaces(self._L.sdfr_pick_surfaces, px.shape[0], inputs, None, hits)
+
+    def meshSurfaces(self, positions, normals, reach, hits=False):
+        """The surface at mesh vertices positions [n, 3] with normals [n, 3], each looked at from `reach` outside it along its normal
+        (sdfr_mesh_surfaces); valid = 0 where that ray misses."""
+        if hasattr(positions, "data_ptr"):
+            n = positions.numel() // 3
+            inputs = (self._h, n, self._dev(positions, 3 * n, "positions"), self._dev(normals, 3 * n, "normals"), float(reach))
+            return self._surfaces(self._L.sdfr_mesh_surfaces, n, inputs, positions, hits)
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert p.shape == nr.shape
+        inputs = (self._h, p.shape[0], p.ctypes.data_as(ctypes.c_void_p), nr.ctypes.data_as(ctypes.c_void_p), float(reach))
+        return self._surfaces(self._L.sdfr_mesh_surfaces, p.shape[0], inputs, None, hits)
+
     # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
-    def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False):
+    def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None):
         """Surface nets over the lattice origin + (i, j, k) * cell, dims = (nx, ny, nz) cells: (positions [v, 3] float32, normals [v, 3]
         float32 or None, indices [t, 3]) -- numpy arrays (indices uint32), or with device=True torch tensors on the renderer's GPU
-        (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call."""
+        (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call.
+        surfaces=True: a fourth element, the surface at every vertex (meshSurfaces with `reach`, default 2 * cell; needs the normals) --
+        the mesh is made on the GPU and looked at there, whatever `device` says about where the results go."""
+        if surfaces:
+            if not normals:
+                raise ValueError("surfaces=True needs the normals")
+            pos, nrm, idx = self.extractMesh(origin, cell, dims, iso, True, device=True)
+            srf = self.meshSurfaces(pos, nrm, 2.0 * float(cell) if reach is None else reach)
+            if device:
+                return pos, nrm, idx, srf
+            self.sync()
+            return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32),
+                    srf.cpu().numpy().view(np.uint32).reshape(-1).view(SURFACE_DTYPE))
         grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
         counts = MeshCounts()
         self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), 0 if device else 1))

@@ -12,11 +12,16 @@
     python -m sdf_playground_amd.cli --scene-hlsl Engine/shader/scenes/sdf_scene_tree.hlsl --translate   # the generated C++
     python -m sdf_playground_amd.cli --scene labyrinth --aa 4 --out clean.png        # 4 x 4 sub-samples per pixel, resolved on the GPU
     python -m sdf_playground_amd.cli --scene tree --mesh tree.obj --mesh-box -2 0 -2 2 4 2 --mesh-cell 0.02   # the scene as a triangle mesh
+    python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-colors --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... with its materials
+    python -m sdf_playground_amd.cli --scene lense --size 640x360 --gbuffer lense.npz   # depth, normal, albedo, material id per pixel
 
 --out writes the tone-mapped + bloomed LDR image (HDR::process, like the reference's window);
 --out-hdr writes the raw float32 RGBA frame as .npy.  --mesh writes the scene's surface (distance == --mesh-iso) inside --mesh-box
 as a Wavefront OBJ with normals: surface nets on cells of edge --mesh-cell (SDFRenderer.extractMesh), at --time with the --set
-variables.  Needs a GPU.
+variables; --mesh-colors adds a colour per vertex (`v x y z r g b`): the albedo of the material under the vertex, or its unlit colour
+(SDFRenderer.extractMesh(surfaces=True)).  --gbuffer writes what lies under every pixel of the frame --out would render, as an .npz:
+depth [h, w] (the hit's t; inf on a miss), normal [h, w, 3] (the shading normal), albedo [h, w, 3] (as --mesh-colors, unclipped),
+material_id and valid [h, w] (SDFRenderer.pickSurfaces).  Needs a GPU.
 """
 import argparse
 import math
@@ -118,7 +123,19 @@ def make_parser():
     ap.add_argument("--mesh-box", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     ap.add_argument("--mesh-cell", type=float, metavar="C", help="edge length of a cell")
     ap.add_argument("--mesh-iso", type=float, default=0.0, metavar="V", help="the surface is distance == V (default 0)")
+    ap.add_argument("--mesh-colors", action="store_true", help="with --mesh: a colour per vertex, from the material under it")
+    ap.add_argument("--gbuffer", metavar="OUT.npz", help="write depth, normal, albedo, material_id and valid of every pixel of the frame")
     return ap
+
+
+def gbuffer_arrays(hits, surfaces, w, h):
+    """what --gbuffer writes, from the records of pickSurfaces(None, w, h, hits=True)"""
+    lit = (surfaces["flags"] & 2) != 0  # SDFR_SURFACE_LIT
+    hit = surfaces["valid"] == 1
+    return {"depth": np.where(hit, hits["t"], np.float32(np.inf)).astype(np.float32).reshape(h, w),
+            "normal": surfaces["shading_normal"].reshape(h, w, 3),
+            "albedo": np.where(lit[:, None], surfaces["albedo"], surfaces["unlit"]).astype(np.float32).reshape(h, w, 3),
+            "material_id": surfaces["material_id"].reshape(h, w), "valid": surfaces["valid"].reshape(h, w)}
 
 
 def render_call(renderer, aa):
@@ -199,9 +216,25 @@ def main(argv=None):
     if mesh_grid:
         from .obj import write_obj
 
-        pos, nrm, idx = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso)
-        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso))
+        colors = None
+        if a.mesh_colors:
+            from .obj import surface_colors
+
+            pos, nrm, idx, srf = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, surfaces=True)
+            colors, missing = surface_colors(srf)
+        else:
+            pos, nrm, idx = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso)
+        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso), colors=colors)
         print("%s: %d vertices, %d triangles (%dx%dx%d cells) -> %s" % ((a.scene, len(pos), len(idx)) + mesh_grid[1] + (a.mesh,)))
+        if colors is not None:
+            print("%d of %d vertices found no surface within 2 cells and are grey" % (missing, len(pos)))
+        if not a.out and not a.out_hdr and not a.gbuffer:
+            r.close()
+            return 0
+    if a.gbuffer:
+        r.setCamera(cam)
+        np.savez(a.gbuffer, **gbuffer_arrays(*r.pickSurfaces(None, w, h, hits=True), w, h))
+        print("%s %dx%d: G-buffer -> %s" % (a.scene, w, h, a.gbuffer))
         if not a.out and not a.out_hdr:
             r.close()
             return 0

@@ -714,17 +714,18 @@ static int loaded_query_kernel(sdfr_renderer *r, int kind, const FrameU &U, Kern
 static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
 	KernelRef k;
-	const int rc = loaded_query_kernel(r, q.kind == QUERY_POINTS ? QUERY_KERNEL_POINTS : QUERY_KERNEL_RAYS, U, k);
+	const int rc = loaded_query_kernel(r, query_kernel_kind(q), U, k);
 	if (rc != SDFR_OK) return rc;
 	const hipError_t e = launch_query(k, U, q, stream);
 	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "query launch");
 }
 
-// The three queries (sdfr_query.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not the
-// handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
-// out: distance + normals, or hits.
+// The queries (sdfr_query.h, sdfr_surface.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not
+// the handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
+// out: distance + normals, or hits and / or surfaces.
 static const size_t k_query_stage_keep = (size_t)64 << 20; // staging bytes a handle keeps between host queries
 static_assert(sizeof(sdfr_hit) == 4 * QUERY_HIT_WORDS, "sdfr_hit is the query kernels' 12-word record");
+static_assert(sizeof(sdfr_surface) == 4 * QUERY_SURFACE_WORDS, "sdfr_surface is the surface kernel's 32-word record");
 // the end of a host call: the answers back to the caller in the order they were named, and `stream` synchronised.  A large call
 // does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
 static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
@@ -734,70 +735,111 @@ static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
 	if (st.buffer->bytes > k_query_stage_keep) st.buffer->release();
 	return SDFR_OK;
 }
-static int query_impl(sdfr_renderer *r, int kind, int64_t n, const float *pos, const float *dir, const int32_t *pixels, int width, int height,
-	float max_distance, float *distance, float *normals, sdfr_hit *hits, int on_host)
+// What the entry points ask for.  kind = QUERY_*; a QUERY_MESH's positions and normals come as pos and dir.  reach: max_distance of
+// rays (0: the range), the reach of a mesh.  want_surfaces: one of the surface entries, which needs `surfaces` and takes hits or not.
+struct QueryCall
 {
+	int kind;
+	int64_t n;
+	const float *pos, *dir;
+	const int32_t *pixels;
+	int width, height;
+	float reach;
+	float *distance, *normals;
+	sdfr_hit *hits;
+	sdfr_surface *surfaces;
+	bool want_surfaces;
+	int on_host;
+};
+static int query_impl(sdfr_renderer *r, const QueryCall &c)
+{
+	const int kind = c.kind;
+	const bool of_pixels = kind == QUERY_PICK || kind == QUERY_FRAME, of_rays = kind == QUERY_RAYS || kind == QUERY_MESH;
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
-	if (n < 0 || n > (int64_t)INT32_MAX) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad item count");
-	if (!is_flag(on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
-	if (!std::isfinite(max_distance) || max_distance < 0.f) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "max_distance must be finite and >= 0");
-	if (kind == QUERY_PICK && !frame_size_ok(width, height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
-	if (n == 0) return SDFR_OK;
-	const bool inputs_ok = kind == QUERY_POINTS ? pos != nullptr : kind == QUERY_RAYS ? pos && dir : pixels != nullptr;
-	const bool outputs_ok = kind == QUERY_POINTS ? distance != nullptr : hits != nullptr;
+	if (c.n < 0 || c.n > (int64_t)INT32_MAX) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad item count");
+	if (!is_flag(c.on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
+	if (kind == QUERY_MESH ? !(std::isfinite(c.reach) && c.reach > 0.f) : !std::isfinite(c.reach) || c.reach < 0.f)
+		return fail(r, SDFR_ERR_INVALID_ARGUMENT, kind == QUERY_MESH ? "reach must be finite and > 0" : "max_distance must be finite and >= 0");
+	if (of_pixels && !frame_size_ok(c.width, c.height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
+	if (c.n == 0) return SDFR_OK;
+	if (kind == QUERY_FRAME && c.n != (int64_t)c.width * c.height) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "without a pixel list n must be width * height");
+	const bool inputs_ok = kind == QUERY_POINTS ? c.pos != nullptr : of_rays ? c.pos && c.dir : kind == QUERY_FRAME || c.pixels != nullptr;
+	const bool outputs_ok = kind == QUERY_POINTS ? c.distance != nullptr : c.want_surfaces ? c.surfaces != nullptr : c.hits != nullptr;
 	if (!inputs_ok || !outputs_ok) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
 	SDFR_HIP(hipSetDevice(r->device));
 	hipStream_t stream = r->lane.stream; // the handle's stream, or the lane of the frame submitted last (as sdfr_postprocess)
 	FrameU U = r->U;
-	int rc = kind == QUERY_PICK ? latch_into(r, U, width, height, stream) : latch_into(r, U, 1, 1, stream);
+	int rc = of_pixels ? latch_into(r, U, c.width, c.height, stream) : latch_into(r, U, 1, 1, stream);
 	if (rc != SDFR_OK) return rc;
 
 	QueryArgs q;
 	q.kind = kind;
-	q.n = (int)n;
-	q.pos = pos;
-	q.dir = dir;
-	q.pixels = pixels;
-	q.dist_max = max_distance == 0.f ? U.range : max_distance;
-	q.distance = distance;
-	q.normals = normals;
-	q.hits = reinterpret_cast<uint32_t *>(hits);
+	q.n = (int)c.n;
+	q.pos = c.pos;
+	q.dir = c.dir;
+	q.pixels = c.pixels;
+	q.dist_max = c.reach == 0.f ? U.range : c.reach; // (a mesh's rays are marched to 2 * reach: query_mesh_ray)
+	q.reach = c.reach;
+	q.distance = c.distance;
+	q.normals = c.normals;
+	q.hits = reinterpret_cast<uint32_t *>(c.hits);
+	q.surfaces = reinterpret_cast<uint32_t *>(c.surfaces);
 	// the sizes of the arrays, in the order they are staged: inputs, then answers
-	const size_t N = (size_t)n;
-	const size_t in0 = kind == QUERY_PICK ? N * 8 : N * 12, in1 = kind == QUERY_RAYS ? N * 12 : 0;
-	const size_t out0 = kind == QUERY_POINTS ? N * 4 : N * sizeof(sdfr_hit), out1 = kind == QUERY_POINTS && normals ? N * 12 : 0;
+	const size_t N = (size_t)c.n;
+	const size_t in0 = kind == QUERY_FRAME ? 0 : kind == QUERY_PICK ? N * 8 : N * 12, in1 = of_rays ? N * 12 : 0;
+	const size_t out0 = kind == QUERY_POINTS ? N * 4 : c.hits ? N * sizeof(sdfr_hit) : 0;
+	const size_t out1 = kind == QUERY_POINTS ? (c.normals ? N * 12 : 0) : c.surfaces ? N * sizeof(sdfr_surface) : 0;
 	Carving st({in0, in1, out0, out1});
-	if (on_host)
+	if (c.on_host)
 	{
 		SDFR_HIP(st.reserve(r->query)); // (host queries are synchronous: none is using the old one)
-		SDFR_HIP(hipMemcpyAsync(st.piece<void>(0), kind == QUERY_PICK ? (const void *)pixels : (const void *)pos, in0, hipMemcpyHostToDevice, stream));
-		if (in1) SDFR_HIP(hipMemcpyAsync(st.piece<void>(1), dir, in1, hipMemcpyHostToDevice, stream));
-		q.pos = kind == QUERY_PICK ? nullptr : st.piece<const float>(0);
+		if (in0) SDFR_HIP(hipMemcpyAsync(st.piece<void>(0), kind == QUERY_PICK ? (const void *)c.pixels : (const void *)c.pos, in0, hipMemcpyHostToDevice, stream));
+		if (in1) SDFR_HIP(hipMemcpyAsync(st.piece<void>(1), c.dir, in1, hipMemcpyHostToDevice, stream));
+		q.pos = of_pixels ? nullptr : st.piece<const float>(0);
 		q.pixels = kind == QUERY_PICK ? st.piece<const int32_t>(0) : nullptr;
 		q.dir = in1 ? st.piece<const float>(1) : nullptr;
-		q.distance = kind == QUERY_POINTS ? st.answer(2, distance, out0) : nullptr;
-		q.normals = out1 ? st.answer(3, normals, out1) : nullptr;
-		q.hits = kind == QUERY_POINTS ? nullptr : st.answer(2, reinterpret_cast<uint32_t *>(hits), out0);
+		q.distance = kind == QUERY_POINTS ? st.answer(2, c.distance, out0) : nullptr;
+		q.normals = kind == QUERY_POINTS && out1 ? st.answer(3, c.normals, out1) : nullptr;
+		q.hits = kind != QUERY_POINTS && out0 ? st.answer(2, reinterpret_cast<uint32_t *>(c.hits), out0) : nullptr;
+		q.surfaces = kind != QUERY_POINTS && out1 ? st.answer(3, reinterpret_cast<uint32_t *>(c.surfaces), out1) : nullptr;
 	}
 	rc = run_query(r, U, q, stream);
 	if (rc != SDFR_OK) return rc;
-	return on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
+	return c.on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
 }
 
 int sdfr_query_distance(sdfr_renderer *r, int64_t n, const float *points, float *distance, float *normals, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, QUERY_POINTS, n, points, nullptr, nullptr, 0, 0, 0.f, distance, normals, nullptr, on_host); });
+	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_POINTS, n, points, nullptr, nullptr, 0, 0, 0.f, distance, normals, nullptr, nullptr, false, on_host}); });
 }
 
 int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, QUERY_RAYS, n, origins, dirs, nullptr, 0, 0, max_distance, nullptr, nullptr, hits, on_host); });
+	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_RAYS, n, origins, dirs, nullptr, 0, 0, max_distance, nullptr, nullptr, hits, nullptr, false, on_host}); });
 }
 
 int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, QUERY_PICK, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, on_host); });
+	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_PICK, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, nullptr, false, on_host}); });
+}
+
+int sdfr_query_ray_surfaces(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, sdfr_surface *surfaces,
+	int on_host)
+{
+	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_RAYS, n, origins, dirs, nullptr, 0, 0, max_distance, nullptr, nullptr, hits, surfaces, true, on_host}); });
+}
+
+int sdfr_pick_surfaces(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, sdfr_surface *surfaces, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		return query_impl(r, {pixels_xy ? QUERY_PICK : QUERY_FRAME, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, surfaces, true, on_host});
+	});
+}
+
+int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits, sdfr_surface *surfaces, int on_host)
+{
+	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_MESH, n, positions, normals, nullptr, 0, 0, reach, nullptr, nullptr, hits, surfaces, true, on_host}); });
 }
 
 // sdfr_mesh_extract (the definition: include/sdfr.h; stages: sdfr_mesh.h, sdfr_mesh.hip).  Like a query it latches the frame into a

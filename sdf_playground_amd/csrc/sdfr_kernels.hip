@@ -465,13 +465,21 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 }
 
 // ---- queries (kernel bodies: sdfr_query_kernel.h) ----
+int query_kernel_kind(const QueryArgs &q)
+{
+	return q.kind == QUERY_POINTS ? QUERY_KERNEL_POINTS : q.surfaces ? QUERY_KERNEL_SURFACES : QUERY_KERNEL_RAYS;
+}
+
 hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
 	QueryKernelArgs a;
 	a.U = U;
 	a.q = q;
 	void *args[] = {&a};
-	return launch_kernel(k, ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK, SDFR_PIXEL_BLOCK, args, stream);
+	// a block per SDFR_PIXEL_BLOCK items; of a whole frame, a block per 8 x 8 tile of pixels (query_surfaces_kernel)
+	uint32_t blocks = ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK;
+	if (q.kind == QUERY_FRAME) blocks = (((uint32_t)U.width + 7u) >> 3) * (((uint32_t)U.height + 7u) >> 3);
+	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
 }
 
 uint32_t query_lattice_blocks(const LatticeArgs &g)

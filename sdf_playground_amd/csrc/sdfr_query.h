@@ -10,18 +10,23 @@ namespace sdfr {
 
 // One query launch (sdfr_kernels.h: launch_query).  Points: `pos` [n][3] -> `distance` [n], `normals` [n][3] or null.  Rays:
 // `pos` = origins [n][3], `dir` [n][3] -> `hits` [n][12].  Picks: `pixels` [n][2] of a width x height frame -> `hits` [n][12].
-enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2 };
+// With `surfaces` [n][32] (sdfr_surface.h) the surface kernel answers, `hits` may be null, and two more kinds of items exist.
+// Frame: every pixel of the width x height frame, item y * width + x, n = width * height, nothing read.  Mesh: `pos` = vertex
+// positions, `dir` = vertex normals, the ray towards each vertex from `reach` outside it (query_mesh_ray).
+enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2, QUERY_FRAME = 3, QUERY_MESH = 4 };
 struct QueryArgs
 {
 	int kind;  // QUERY_*
 	int n;
 	const float *pos, *dir;
 	const int32_t *pixels;
-	float dist_max; // rays and picks: march_ray's dist_max
+	float dist_max; // rays: march_ray's dist_max (picks and frames: the range; meshes: 2 * reach)
+	float reach;    // meshes
 	float *distance, *normals;
-	uint32_t *hits; // 12 words per item: the layout of sdfr_hit
+	uint32_t *hits;     // 12 words per item: the layout of sdfr_hit
+	uint32_t *surfaces; // 32 words per item: the layout of sdfr_surface
 };
-enum { QUERY_HIT_WORDS = 12 };
+enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32 };
 // what a query kernel takes: one argument, as the pixel kernels (PixelKernelArgs)
 struct QueryKernelArgs
 {
@@ -104,9 +109,16 @@ SDF_HD float query_point(const FrameU &U, vec3 p, vec3 *normal)
 // Ray query: what the driver does with a primary ray up to its material (pshader_sdf.hlsl:299-353): march_ray with dir.w = 1,
 // inside_sign +1, the default MarchingInput, camera_distance from 0 and the given offsets; on a hit the normal and map_material.
 // With FrameU::step_shortcuts a miss may end early, as in the pixel pipeline (render_pixel): hits are unchanged.
-// rec: the 12 words of sdfr_hit.
+// rec: the 12 words of sdfr_hit.  Returns whether the ray hit; of a hit, `at` is the surface point and the material map_material
+// made of it, for whoever goes on where the driver does (sdfr_surface.h).
+struct QueryHit
+{
+	SurfacePoint sp;
+	Material mat;
+};
 template <class Scene, bool DBG>
-SDF_HD void query_ray(const FrameU &U, vec3 origin, vec3 dir, float dist_max, vec3 right_off, vec3 bottom_off, uint32_t rec[QUERY_HIT_WORDS])
+SDF_HD bool query_ray_at(const FrameU &U, vec3 origin, vec3 dir, float dist_max, vec3 right_off, vec3 bottom_off, uint32_t rec[QUERY_HIT_WORDS],
+	QueryHit &at)
 {
 	const DebugFlags F = debug_flags(U);
 	const typename Scene::RayInv R = Scene::ray_setup(U, dir, query_ray_flags());
@@ -142,7 +154,7 @@ SDF_HD void query_ray(const FrameU &U, vec3 origin, vec3 dir, float dist_max, ve
 	if (status == MARCH_HIT)
 	{
 		n = query_normal<Scene, DBG>(U, F, R, pos, dir, m.t, right_off, bottom_off, m.d);
-		SurfacePoint sp;
+		SurfacePoint &sp = at.sp;
 		sp.pos = pos;
 		sp.dir = dir;
 		sp.camera_distance = m.t;
@@ -151,9 +163,9 @@ SDF_HD void query_ray(const FrameU &U, vec3 origin, vec3 dir, float dist_max, ve
 		sp.normal = n;
 		sp.iteration_count = m.iter;
 		sp.scene_distance = m.d;
-		Material mat = default_material(U, pos);
-		map_material<Scene, DBG>(U, F, sp, mat);
-		material = mat.id;
+		at.mat = default_material(U, pos);
+		map_material<Scene, DBG>(U, F, sp, at.mat);
+		material = at.mat.id;
 	}
 	rec[0] = f32_bits(m.t);
 	rec[1] = f32_bits(m.d);
@@ -167,6 +179,13 @@ SDF_HD void query_ray(const FrameU &U, vec3 origin, vec3 dir, float dist_max, ve
 	rec[9] = material;
 	rec[10] = status == MARCH_HIT ? 1u : 0u;
 	rec[11] = 0u;
+	return status == MARCH_HIT;
+}
+template <class Scene, bool DBG>
+SDF_HD void query_ray(const FrameU &U, vec3 origin, vec3 dir, float dist_max, vec3 right_off, vec3 bottom_off, uint32_t rec[QUERY_HIT_WORDS])
+{
+	QueryHit at;
+	query_ray_at<Scene, DBG>(U, origin, dir, dist_max, right_off, bottom_off, rec, at);
 }
 
 // Pick: pixel (px, py)'s primary ray of the frame U describes (pshader_sdf.hlsl:263-267), marched to limits.range; a pixel

@@ -7,6 +7,7 @@
 #pragma once
 #include "sdfr_pixel_kernel.h"
 #include "sdfr_query.h"
+#include "sdfr_surface.h"
 
 namespace sdfr {
 
@@ -15,6 +16,26 @@ SDF_HD vec3 query_load3(const float *__restrict__ p, uint32_t i)
 {
 	const float *r = p + (size_t)3 * i;
 	return V3(r[0], r[1], r[2]);
+}
+
+// item i's record of WORDS words (a multiple of 4) leaves from registers: 16-byte stores into an array aligned to 16 bytes, word
+// stores into any other (sdfr_hit and sdfr_surface themselves only ask for 4-byte alignment)
+template <int WORDS>
+__device__ __forceinline__ void query_store(uint32_t *__restrict__ base, uint32_t i, const uint32_t (&rec)[WORDS])
+{
+	static_assert(WORDS % 4 == 0, "whole 16-byte stores");
+	uint32_t *out = base + (size_t)WORDS * i;
+	if ((reinterpret_cast<size_t>(base) & 15u) == 0u)
+	{
+		uint4 *dst = reinterpret_cast<uint4 *>(out);
+#pragma unroll
+		for (int k = 0; k < WORDS / 4; ++k) dst[k] = make_uint4(rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3]);
+	}
+	else
+	{
+#pragma unroll
+		for (int k = 0; k < WORDS; ++k) out[k] = rec[k];
+	}
 }
 
 template <class Scene, bool DBG>
@@ -52,16 +73,47 @@ __device__ __forceinline__ void query_rays_kernel(const QueryKernelArgs &a)
 	}
 	else
 		query_ray<Scene, DBG>(U, query_load3(q.pos, i), query_load3(q.dir, i), q.dist_max, V3s(0.f), V3s(0.f), rec);
-	uint32_t *out = q.hits + (size_t)QUERY_HIT_WORDS * i;
-	if ((reinterpret_cast<size_t>(q.hits) & 15u) == 0u) // 48-byte records of an aligned array: three 16-byte stores
+	query_store(q.hits, i, rec); // 48-byte records: three 16-byte stores
+}
+
+// The surface queries (sdfr_surface.h): rays, picks, a whole frame or the rays towards a mesh's vertices -> `surfaces`, and `hits`
+// unless null.  One wave per block.  A frame's wave takes an 8 x 8 tile of pixels, as the pixel kernel's does, so that the scenes'
+// wave-level branches stay as coherent as in a render; lanes past the frame's ragged right and bottom edges leave.  Every other
+// kind maps 64 consecutive items.  A record is one whole 128-byte line per lane, built in registers and written by eight 16-byte stores.
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_surfaces_kernel(const QueryKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 pixels");
+	const FrameU &U = a.U;
+	const QueryArgs &q = a.q;
+	const uint32_t lane = threadIdx.x;
+	uint32_t i;
+	QueryRay ray;
+	bool in_frame = true;
+	if (q.kind == QUERY_FRAME)
 	{
-		uint4 *dst = reinterpret_cast<uint4 *>(out);
-		dst[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
-		dst[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
-		dst[2] = make_uint4(rec[8], rec[9], rec[10], rec[11]);
+		const uint32_t tiles_x = ((uint32_t)U.width + 7u) >> 3;
+		const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+		const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+		if (px >= (uint32_t)U.width || py >= (uint32_t)U.height) return;
+		i = py * (uint32_t)U.width + px; // < width * height <= 2^30
+		in_frame = query_pixel_ray(U, (int)px, (int)py, ray);
 	}
-	else // (sdfr_hit itself only asks for 4-byte alignment)
-		for (int k = 0; k < QUERY_HIT_WORDS; ++k) out[k] = rec[k];
+	else
+	{
+		i = blockIdx.x * 64u + lane;
+		if (i >= (uint32_t)q.n) return;
+		if (q.kind == QUERY_PICK)
+			in_frame = query_pixel_ray(U, q.pixels[(size_t)2 * i], q.pixels[(size_t)2 * i + 1], ray);
+		else if (q.kind == QUERY_MESH)
+			ray = query_mesh_ray(query_load3(q.pos, i), query_load3(q.dir, i), q.reach);
+		else
+			ray = query_plain_ray(query_load3(q.pos, i), query_load3(q.dir, i), q.dist_max);
+	}
+	uint32_t hit[QUERY_HIT_WORDS], rec[QUERY_SURFACE_WORDS];
+	query_surface<Scene, DBG>(U, ray, in_frame, hit, rec);
+	if (q.hits) query_store(q.hits, i, hit);
+	query_store(q.surfaces, i, rec);
 }
 
 // The distance query over a lattice (LatticeArgs): one wave per block, one point per lane.  A wave owns a 4 x 4 x 4 brick of points,

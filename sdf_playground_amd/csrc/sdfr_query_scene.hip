@@ -1,4 +1,4 @@
-// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice: sdfr_query_kernel.h) of ONE scene, compiled
+// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice, k_query_surfaces: sdfr_query_kernel.h) of ONE scene, compiled
 // once per scene with -DSDFR_SCENE=<index> and the scene's code-generation options (sdf_playground_amd/buildlib.py), like
 // sdfr_kernels_scene.hip.  They live in a unit of their own: a second caller of the shared inline stages in the pixel kernels'
 // unit could change the inliner's decisions there, and with them k_pixel's code.
@@ -38,6 +38,13 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_lattice(LatticeKernelArgs
 	query_lattice_kernel<Scene, DBG>(a);
 }
 
+// the surface under rays, pixels, a whole frame or towards a mesh's vertices (sdfr_surface.h)
+template <class Scene, bool DBG>
+__global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_surfaces(QueryKernelArgs a)
+{
+	query_surfaces_kernel<Scene, DBG>(a);
+}
+
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
 // what this unit exports (scene_query_kernels, launch_query: sdfr_kernels.hip)
@@ -52,6 +59,8 @@ const QueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
 		q.k[QUERY_KERNEL_RAYS][0].kernel = (const void *)k_query_rays<UnitScene, false>;
 		q.k[QUERY_KERNEL_LATTICE][1].kernel = (const void *)k_query_lattice<UnitScene, true>;
 		q.k[QUERY_KERNEL_LATTICE][0].kernel = (const void *)k_query_lattice<UnitScene, false>;
+		q.k[QUERY_KERNEL_SURFACES][1].kernel = (const void *)k_query_surfaces<UnitScene, true>;
+		q.k[QUERY_KERNEL_SURFACES][0].kernel = (const void *)k_query_surfaces<UnitScene, false>;
 		return q;
 	}();
 	return &k;

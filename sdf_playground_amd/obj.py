@@ -1,20 +1,42 @@
 """A small Wavefront OBJ writer for the meshes of SDFRenderer.extractMesh: `v`, `vn` and `f` lines with 1-based indices."""
 
+MISSING_COLOR = (0.5, 0.5, 0.5)  # a vertex under which no surface was found (surface_colors)
 
-def write_obj(out, positions, normals, indices, comment=None):
-    """Writes the mesh to `out` (a path or a text file object): one `v x y z` per vertex, one `vn x y z` per vertex if `normals` is
-    given, one `f a//a b//b c//c` (`f a b c` without normals) per triangle.  Floats are written with %.9g, which reads back to the
-    same fp32 value.  positions / normals [v, 3], indices [t, 3] (0-based, as extractMesh returns them)."""
+
+def surface_colors(surfaces):
+    """Per-vertex colours [v, 3] float32 of SURFACE_DTYPE records (extractMesh(surfaces=True)): the albedo of a lit material, the
+    unlit colour of any other, clipped to [0, 1] (a NaN becomes 0); MISSING_COLOR where valid != 1.  Also returns how many are missing."""
+    import numpy as np
+
+    lit = (surfaces["flags"] & 2) != 0  # SDFR_SURFACE_LIT
+    rgb = np.where(lit[:, None], surfaces["albedo"], surfaces["unlit"]).astype(np.float32)
+    rgb = np.clip(np.nan_to_num(rgb, nan=0.0), 0.0, 1.0)
+    missing = surfaces["valid"] != 1
+    rgb[missing] = MISSING_COLOR
+    return rgb, int(missing.sum())
+
+
+def write_obj(out, positions, normals, indices, comment=None, colors=None):
+    """Writes the mesh to `out` (a path or a text file object): one `v x y z` per vertex -- `v x y z r g b` with `colors` [v, 3], the
+    per-vertex colour extension most tools read --, one `vn x y z` per vertex if `normals` is given, one `f a//a b//b c//c`
+    (`f a b c` without normals) per triangle.  Floats are written with %.9g, which reads back to the same fp32 value.
+    positions / normals [v, 3], indices [t, 3] (0-based, as extractMesh returns them)."""
     if isinstance(out, (str, bytes)) or hasattr(out, "__fspath__"):
         with open(out, "w") as f:
-            return write_obj(f, positions, normals, indices, comment)
+            return write_obj(f, positions, normals, indices, comment, colors)
     if normals is not None and len(normals) != len(positions):
         raise ValueError("%d normals for %d vertices" % (len(normals), len(positions)))
+    if colors is not None and len(colors) != len(positions):
+        raise ValueError("%d colours for %d vertices" % (len(colors), len(positions)))
     if comment:
         for line in str(comment).splitlines():
             out.write("# %s\n" % line)
-    for p in positions:
-        out.write("v %.9g %.9g %.9g\n" % (float(p[0]), float(p[1]), float(p[2])))
+    if colors is not None:
+        for p, c in zip(positions, colors):
+            out.write("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (float(p[0]), float(p[1]), float(p[2]), float(c[0]), float(c[1]), float(c[2])))
+    else:
+        for p in positions:
+            out.write("v %.9g %.9g %.9g\n" % (float(p[0]), float(p[1]), float(p[2])))
     if normals is not None:
         for n in normals:
             out.write("vn %.9g %.9g %.9g\n" % (float(n[0]), float(n[1]), float(n[2])))

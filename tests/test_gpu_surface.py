@@ -1,0 +1,373 @@
+"""GPU tier of the surface queries (sdfr_query_ray_surfaces, sdfr_pick_surfaces, sdfr_mesh_surfaces) through libsdfr.so: bit for
+bit against the oracle's definition of the record (tests/cpp/surface_oracle.cpp) for every scene compiled ahead of time and the
+run-time scenes with an oracle twin, host and device memory; their hit records against the ray query's and the pick's; the whole
+frame (no pixel list, 8 x 8 tiles) against the pixel list; the mesh with surfaces against the rays made on the host; small and
+awkward sizes, the word-store path, argument checks; no side effects on rendering; one handle across scene changes; and the
+renderer's own pixels where a pixel is its unlit colour."""
+import ctypes
+import os
+import zlib
+
+import numpy as np
+import pytest
+
+import query_util as qu
+import surface_util as su
+
+pytestmark = pytest.mark.gpu
+
+N_RAYS = 2000
+W, H = 64, 48
+FW, FH = 61, 45  # the whole frame: ragged 8 x 8 tiles on both edges
+SCENES_DIR = qu.SCENES_DIR
+DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
+                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
+# the meshes: about 24^3 cells, no axis a multiple of the lattice kernel's brick.  On the fast_sphere grid the oracle finds a surface
+# under every vertex (checked on the CPU before the grid was fixed; the test asserts >= 99 %)
+MESHES = {"fast_sphere": (0.0, (-1.55, -0.3, -1.55), 0.13, (24, 23, 25)), "debug_materials": (0.4, (-2.05, -0.3, -1.55), 0.17, (24, 23, 25))}
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    yield r
+    r.close()
+
+
+def _load(r, scene):
+    if scene in qu.HLSL:
+        r.initShaderHlsl(scene, os.path.join(SCENES_DIR, scene + ".hlsl"))
+    else:
+        r.initShader(scene)
+
+
+def _setup(r, scene, of, variables=None, limits=None):
+    """the handle's state = the oracle frame `of`"""
+    _load(r, scene)
+    r.setParameters(of.stime)
+    r.setCameraBasis(of.eye, of.front, of.right, of.top)
+    r.setLimits(**dict(DEFAULT_LIMITS, **(limits or {})))
+    r.setStepShortcuts(False)
+    for name, v in (variables or {}).items():
+        assert r.setValue(name, v)
+
+
+def _torch_dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _host(pair):
+    """(hits, surfaces) of a device call -> numpy"""
+    import torch
+
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in pair)
+
+
+def _frame_oracle(scene, of, w, h):
+    of.width, of.height = w, h
+    try:
+        return su.oracle_pick(scene, of, su.frame_pixels(w, h))
+    finally:
+        of.width, of.height = W, H
+
+
+def _check_all(r, scene, of, seed, device=True):
+    o, dirs = qu.ray_samples(of, seed + 7, N_RAYS)
+    px = qu.pick_grid(W, H)
+    ray_ref, pick_ref, frame_ref = su.oracle_rays(scene, of, o, dirs), su.oracle_pick(scene, of, px), _frame_oracle(scene, of, FW, FH)
+    rays = r.queryRaySurfaces(o, dirs, hits=True)
+    picks = r.pickSurfaces(px, W, H, hits=True)
+    frame = r.pickSurfaces(None, FW, FH, hits=True)
+    su.assert_same("%s rays (host)" % scene, rays, ray_ref)
+    su.assert_same("%s pick (host)" % scene, picks, pick_ref)
+    su.assert_same("%s frame (host)" % scene, frame, frame_ref)
+    # the hit records are the ray query's and the pick's; the surface carries the hit's material and validity
+    qu.assert_same("%s hits against sdfr_query_rays" % scene, qu.hits_array(rays[0]), qu.hits_array(r.queryRays(o, dirs)))
+    qu.assert_same("%s hits against sdfr_pick" % scene, qu.hits_array(picks[0]), qu.hits_array(r.pick(px, W, H)))
+    qu.assert_same("%s frame hits against sdfr_pick" % scene, qu.hits_array(frame[0]), qu.hits_array(r.pick(su.frame_pixels(FW, FH), FW, FH)))
+    for h, s in (rays, picks, frame):
+        assert np.array_equal(s["material_id"], h["material_id"]) and np.array_equal(s["valid"], h["hit"])
+    # without hits: the same surfaces
+    qu.assert_same("%s rays, hits = NULL" % scene, su.surfaces_array(r.queryRaySurfaces(o, dirs)), ray_ref[1])
+    if device:
+        su.assert_same("%s rays (device)" % scene, _host(r.queryRaySurfaces(_torch_dev(o), _torch_dev(dirs), hits=True)), ray_ref)
+        su.assert_same("%s pick (device)" % scene, _host(r.pickSurfaces(_torch_dev(px), W, H, hits=True)), pick_ref)
+        su.assert_same("%s frame (device)" % scene, _host(r.pickSurfaces(None, FW, FH, hits=True, device=True)), frame_ref)
+    return ray_ref, pick_ref
+
+
+@pytest.mark.parametrize("scene", qu.BUILTIN + qu.HLSL)
+def test_surfaces_equal_oracle(renderer, scene):
+    of = qu.frame(scene, 1.25 if scene in qu.BUILTIN else 0.5, W, H)
+    _setup(renderer, scene, of)
+    _check_all(renderer, scene, of, seed=zlib.crc32(scene.encode()) & 0xffff)
+
+
+@pytest.mark.parametrize("scene", sorted(qu.MOVED_VARS))
+def test_surfaces_with_moved_variables(renderer, scene):
+    of = qu.frame(scene, 0.5, W, H, qu.MOVED_VARS[scene])
+    _setup(renderer, scene, of, qu.MOVED_VARS[scene])
+    _check_all(renderer, scene, of, seed=11, device=False)
+    renderer.resetVariables()
+
+
+def test_debug_plane_and_marble_reflection(renderer):
+    v = {"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}
+    of = qu.frame("labyrinth", 0.75, W, H, v)
+    _setup(renderer, "labyrinth", of, v)
+    _rays, (ph, ps) = _check_all(renderer, "labyrinth", of, seed=21, device=False)
+    assert (ps[:, 0] == 5).any()  # MATERIAL_DISTANCE_PLANE
+    renderer.resetVariables()
+    of = qu.frame("labyrinth", 0.25, W, H)
+    of.extension_marble_reflection = 0.25
+    _setup(renderer, "labyrinth", of, limits=dict(extension_marble_reflection=0.25))
+    _rays, (ph, ps) = _check_all(renderer, "labyrinth", of, seed=31, device=False)
+    assert (ps[:, 20:23] == np.float32(0.25).view(np.uint32)).any()
+    renderer.setLimits(**DEFAULT_LIMITS)
+
+
+def test_whole_frame_equals_the_pixel_list(renderer):
+    scene = "lense"
+    _setup(renderer, scene, qu.frame(scene, 0.6, W, H))
+    for w, h in ((FW, FH), (1, 1), (9, 1), (8, 8), (3, 17)):
+        whole = renderer.pickSurfaces(None, w, h, hits=True)
+        listed = renderer.pickSurfaces(su.frame_pixels(w, h), w, h, hits=True)
+        assert len(whole[1]) == w * h
+        su.assert_same("%d x %d" % (w, h), whole, (qu.hits_array(listed[0]), su.surfaces_array(listed[1])))
+        dev = _host(renderer.pickSurfaces(None, w, h, hits=True, device=True))
+        su.assert_same("%d x %d (device)" % (w, h), dev, (qu.hits_array(listed[0]), su.surfaces_array(listed[1])))
+
+
+@pytest.mark.parametrize("scene", sorted(MESHES))
+def test_mesh_with_surfaces(renderer, scene):
+    stime, origin, cell, dims = MESHES[scene]
+    of = qu.frame(scene, stime, W, H)
+    _setup(renderer, scene, of)
+    pos, nrm, idx, srf = renderer.extractMesh(origin, cell, dims, surfaces=True)
+    plain = renderer.extractMesh(origin, cell, dims)
+    for a, b in zip((pos, nrm, idx), plain):  # the mesh itself is sdfr_mesh_extract's
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert len(pos) > 500 and srf.dtype == __import__("sdf_playground_amd").SURFACE_DTYPE
+    reach = 2.0 * cell
+    o, d, reach2 = su.mesh_rays(pos, nrm, reach)
+    ref = su.oracle_rays(scene, of, o, d, reach2)
+    qu.assert_same("%s mesh surfaces against the oracle" % scene, su.surfaces_array(srf), ref[1])
+    su.assert_same("%s mesh surfaces against the host-made rays" % scene, renderer.queryRaySurfaces(o, d, reach2, hits=True), ref)
+    mesh = renderer.meshSurfaces(pos, nrm, reach, hits=True)
+    su.assert_same("%s meshSurfaces (host)" % scene, mesh, ref)
+    qu.assert_same("%s mesh hits against sdfr_query_rays" % scene, qu.hits_array(mesh[0]), qu.hits_array(renderer.queryRays(o, d, reach2)))
+    assert np.array_equal(mesh[1]["material_id"], mesh[0]["material_id"]) and np.array_equal(mesh[1]["valid"], mesh[0]["hit"])
+    # another reach, on the device, with the mesh left there
+    dpos, dnrm, _didx, dsrf = renderer.extractMesh(origin, cell, dims, surfaces=True, reach=0.2, device=True)
+    (dsrf,) = _host((dsrf,))
+    qu.assert_same("%s mesh surfaces, reach 0.2 (device)" % scene, su.surfaces_array(dsrf), su.oracle_mesh(scene, of, pos, nrm, 0.2)[1])
+    # the usefulness condition on the inputs: a surface under (nearly) every vertex
+    valid = (ref[1][:, 3] == 1).mean()
+    print("%s: %d vertices, %.4f valid" % (scene, len(pos), valid))
+    if scene == "fast_sphere":
+        assert valid >= 0.99
+    else:
+        assert len(np.unique(srf["material_id"][srf["valid"] == 1])) >= 4  # the debug views are on the mesh
+
+
+def _raw(r):
+    import sdf_playground_amd as sp
+
+    return sp.load_library(), r._h
+
+
+def test_small_and_awkward_sizes(renderer):
+    import torch
+
+    scene = "labyrinth"
+    of = qu.frame(scene, 0.3, W, H)
+    _setup(renderer, scene, of)
+    L, h = _raw(renderer)
+    o, dirs = qu.ray_samples(of, 5, 65)
+    ref = su.oracle_rays(scene, of, o, dirs)
+    assert (ref[1][:, 3] == 1).any()
+    for n in (0, 1, 63, 64, 65):
+        got = renderer.queryRaySurfaces(o[:n], dirs[:n], hits=True)
+        su.assert_same("n = %d" % n, got, (ref[0][:n], ref[1][:n]))
+        dev = _host(renderer.queryRaySurfaces(_torch_dev(o[:n].reshape(-1, 3)), _torch_dev(dirs[:n].reshape(-1, 3)), hits=True))
+        su.assert_same("n = %d (device)" % n, dev, (ref[0][:n], ref[1][:n]))
+    # records that start 4 bytes past a 16-byte boundary: the word stores; the words around them stay
+    n = 65
+    sentinel = 0x7fc12345
+    sbuf = torch.full((32 * n + 8,), sentinel, dtype=torch.int32, device="cuda")
+    hbuf = torch.full((12 * n + 8,), sentinel, dtype=torch.int32, device="cuda")
+    assert sbuf.data_ptr() % 16 == 0 and hbuf.data_ptr() % 16 == 0
+    do, dd = _torch_dev(o), _torch_dev(dirs)
+    vp = ctypes.c_void_p
+    assert L.sdfr_query_ray_surfaces(h, n, vp(do.data_ptr()), vp(dd.data_ptr()), 0.0, vp(hbuf.data_ptr() + 4), vp(sbuf.data_ptr() + 4), 0) == 0
+    renderer.sync()
+    s, hh = sbuf.cpu().numpy().view(np.uint32), hbuf.cpu().numpy().view(np.uint32)
+    qu.assert_same("offset surfaces", s[1:1 + 32 * n].reshape(n, 32), ref[1])
+    qu.assert_same("offset hits", hh[1:1 + 12 * n].reshape(n, 12), ref[0])
+    assert s[0] == sentinel and (s[1 + 32 * n:] == sentinel).all() and hh[0] == sentinel and (hh[1 + 12 * n:] == sentinel).all()
+    # picks outside the frame: valid = -1 and zeros
+    hits, srf = renderer.pickSurfaces(np.array([[-1, 0], [W, 0], [0, H], [3, 4]], np.int32), W, H, hits=True)
+    assert list(srf["valid"][:3]) == [-1, -1, -1] and list(hits["hit"][:3]) == [-1, -1, -1] and srf["valid"][3] in (0, 1)
+    words = su.surfaces_array(srf)[:3]
+    assert not words[:, [k for k in range(32) if k != 3]].any()
+
+
+def test_arguments(renderer):
+    import sdf_playground_amd as sp
+
+    scene = "fast_sphere"
+    _setup(renderer, scene, qu.frame(scene, 0.0, W, H))
+    L, h = _raw(renderer)
+    buf = np.zeros(64, np.float32)
+    out = np.full(W * H * 32, 7, np.uint32)  # what no call below may touch
+    hit = np.full(W * H * 12, 7, np.uint32)
+    p, s, hp = (a.ctypes.data_as(ctypes.c_void_p) for a in (buf, out, hit))
+    INVALID, NO_SCENE = -1, -4
+    assert L.sdfr_query_ray_surfaces(h, 0, None, None, 0.0, None, None, 1) == 0
+    assert L.sdfr_pick_surfaces(h, W, H, 0, None, None, None, 0) == 0
+    assert L.sdfr_mesh_surfaces(h, 0, None, None, 0.5, None, None, 1) == 0
+    # NULL surfaces, NULL inputs
+    assert L.sdfr_query_ray_surfaces(h, 1, p, p, 0.0, hp, None, 1) == INVALID
+    assert L.sdfr_pick_surfaces(h, W, H, 1, p, hp, None, 1) == INVALID
+    assert L.sdfr_pick_surfaces(h, W, H, W * H, None, hp, None, 1) == INVALID
+    assert L.sdfr_mesh_surfaces(h, 1, p, p, 0.5, hp, None, 1) == INVALID
+    assert L.sdfr_query_ray_surfaces(h, 1, p, None, 0.0, hp, s, 1) == INVALID
+    assert L.sdfr_mesh_surfaces(h, 1, None, p, 0.5, hp, s, 1) == INVALID
+    # the whole frame: n must be width * height
+    for n in (1, W * H - 1, W * H + 1):
+        assert L.sdfr_pick_surfaces(h, W, H, n, None, hp, s, 1) == INVALID
+    assert L.sdfr_pick_surfaces(h, 0, H, 1, p, hp, s, 1) == INVALID
+    # reach, max_distance
+    for bad in (0.0, -1.0, float("inf"), float("nan")):
+        assert L.sdfr_mesh_surfaces(h, 1, p, p, bad, hp, s, 1) == INVALID
+    for bad in (-1.0, float("inf"), float("nan")):
+        assert L.sdfr_query_ray_surfaces(h, 1, p, p, bad, hp, s, 1) == INVALID
+    # n, on_host, the handle
+    for n in (-1, 2 ** 31):
+        assert L.sdfr_query_ray_surfaces(h, n, p, p, 0.0, hp, s, 1) == INVALID
+        assert L.sdfr_pick_surfaces(h, W, H, n, p, hp, s, 1) == INVALID
+        assert L.sdfr_mesh_surfaces(h, n, p, p, 0.5, hp, s, 1) == INVALID
+    for bad in (2, -1):
+        assert L.sdfr_query_ray_surfaces(h, 1, p, p, 0.0, hp, s, bad) == INVALID
+        assert L.sdfr_pick_surfaces(h, W, H, W * H, None, hp, s, bad) == INVALID
+        assert L.sdfr_mesh_surfaces(h, 1, p, p, 0.5, hp, s, bad) == INVALID
+    assert L.sdfr_query_ray_surfaces(None, 1, p, p, 0.0, hp, s, 1) == INVALID
+    fresh = sp.SDFRenderer(0)
+    try:
+        assert L.sdfr_query_ray_surfaces(fresh._h, 1, p, p, 0.0, hp, s, 1) == NO_SCENE
+        assert L.sdfr_pick_surfaces(fresh._h, W, H, W * H, None, hp, s, 1) == NO_SCENE
+        assert L.sdfr_mesh_surfaces(fresh._h, 1, p, p, 0.5, hp, s, 1) == NO_SCENE
+    finally:
+        fresh.close()
+    assert (out == 7).all() and (hit == 7).all()
+    # and the same buffers are written by a good call
+    assert L.sdfr_pick_surfaces(h, W, H, W * H, None, hp, s, 1) == 0
+    assert set(out.reshape(-1, 32)[:, 3]) <= {0, 1} and set(hit.reshape(-1, 12)[:, 10]) <= {0, 1}
+
+
+def _stats(r):
+    s = r.getStats()
+    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
+
+
+def test_surface_queries_leave_rendering_alone(renderer):
+    scene = "labyrinth"
+    of = qu.frame(scene, 0.4, 96, 64)
+    _setup(renderer, scene, of)
+    o, dirs = qu.ray_samples(of, 71, 500)
+    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
+    s0, t0 = _stats(renderer), renderer.getTimings()
+    renderer.queryRaySurfaces(o, dirs, hits=True)
+    renderer.pickSurfaces(qu.pick_grid(32, 16), 32, 16)
+    renderer.pickSurfaces(None, 33, 17, hits=True)
+    renderer.meshSurfaces(o, dirs, 0.25)
+    renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), surfaces=True)
+    assert _stats(renderer) == s0 and renderer.getTimings() == t0
+    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
+    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+
+
+def test_one_handle_across_scene_changes():
+    # built-in scene -> run-time scene (its lazily compiled query module has the surface kernel) -> the same built-in scene
+    import sdf_playground_amd as sp
+
+    n, w, h = 130, 24, 17
+    r = sp.SDFRenderer(0)
+    try:
+        rounds = []
+        for scene in ("labyrinth", qu.HLSL[0], "labyrinth"):
+            of = qu.frame(scene, 0.5, W, H)
+            _setup(r, scene, of)
+            o, dirs = qu.ray_samples(of, 92, n)
+            ray_ref, frame_ref = su.oracle_rays(scene, of, o, dirs), _frame_oracle(scene, of, w, h)
+            mesh_ref = su.oracle_mesh(scene, of, o, dirs, 0.3)
+            got = [r.queryRaySurfaces(o, dirs, hits=True), r.pickSurfaces(None, w, h, hits=True), r.meshSurfaces(o, dirs, 0.3, hits=True)]
+            for what, g, want in zip(("rays", "frame", "mesh"), got, (ray_ref, frame_ref, mesh_ref)):
+                su.assert_same("%s %s" % (scene, what), g, want)
+            su.assert_same("%s frame (device)" % scene, _host(r.pickSurfaces(None, w, h, hits=True, device=True)), frame_ref)
+            rounds.append(got)
+        for a, b in zip(rounds[0], rounds[2]):
+            assert np.array_equal(su.surfaces_array(a[1]), su.surfaces_array(b[1])) and np.array_equal(qu.hits_array(a[0]), qu.hits_array(b[0]))
+    finally:
+        r.close()
+
+
+def test_unlit_pixels_are_the_renderer_s(renderer):
+    # shade_hit (sdfr_pixel.h) returns color * contribution for a hit; the primary ray's contribution is (1, 1, 1) and the pixel's sum
+    # starts at 0, so a pixel that traced ONE ray (nothing spawned: no reflection, refraction or see-through surface, and an unlit
+    # material sends no shadow rays) whose material is one of the unlit views (use_light false: MATERIAL_ITER, PLAIN, NORMAL1, NORMAL2)
+    # is 0 + (0 + colour) * 1: the bits of `unlit` (a zero of either sign becomes +0 in both).  Its alpha is the tone-map flag: 0
+    # where the view switches it off (all but PLAIN), else use_hdr.
+    from test_debug_materials_cpu import CAMS
+
+    import sdf_playground_amd as sp
+
+    scene, w, h = "debug_materials", 96, 64
+    r = renderer
+    r.initShader(scene)
+    r.setParameters(0.4)
+    r.setLimits(**dict(DEFAULT_LIMITS, iter_count=37))
+    r.setStepShortcuts(False)
+    c = sp.Camera()
+    c.SetEye(CAMS[0][0])
+    c.SetLookat(CAMS[0][1])
+    c.SetAspect(float(np.float32(w) / np.float32(h)))
+    r.setCamera(c)
+    img, st = r.render(None, w, h, pixel_stats=True)
+    hits, srf = r.pickSurfaces(None, w, h, hits=True)
+    r.setLimits(**DEFAULT_LIMITS)
+    srf, hits = srf.reshape(h, w), hits.reshape(h, w)
+    assert np.array_equal(hits["hit"] == 1, st[..., 2] >= 1)  # (only a hit spawns rays: a pixel with a hit has its first surface)
+    unlit = (srf["valid"] == 1) & (srf["flags"] & sp.SURFACE_LIT == 0) & np.isin(srf["material_id"], (1, 2, 3, 4))
+    one_ray = unlit & (st[..., 0] == 1)
+    assert one_ray.sum() > 300 and len(np.unique(srf["material_id"][one_ray])) >= 3
+    qu.assert_same("rendered rgb against unlit", np.ascontiguousarray(img[one_ray][:, :3]), np.ascontiguousarray(srf["unlit"][one_ray]))
+    views = one_ray & (srf["material_id"] != 1)
+    assert (img[views][:, 3] == 0).all()
+    # the heat view's colour came from the hit's iterations and iter_count - 1 = 36
+    heat = one_ray & (srf["material_id"] == 2)
+    assert heat.any() and len(np.unique(srf["unlit"][heat], axis=0)) >= 3
+
+
+def test_cli_writes_colours_and_a_gbuffer(tmp_path, capsys):
+    from sdf_playground_amd import cli
+
+    out, gb = tmp_path / "views.obj", tmp_path / "g.npz"
+    assert cli.main(["--scene", "debug_materials", "--time", "0.4", "--mesh", str(out), "--mesh-colors", "--mesh-box", "-2", "-0.3", "-1.5", "2", "3.5", "2.5",
+                     "--mesh-cell", "0.17", "--gbuffer", str(gb), "--size", "61x45", "--eye", "0,1.6,-4.2", "--lookat", "0,0.6,0"]) == 0
+    said = capsys.readouterr().out
+    assert "vertices found no surface" in said and "G-buffer" in said
+    vs = [s.split() for s in out.read_text().splitlines() if s.startswith("v ")]
+    assert len(vs) > 500 and all(len(v) == 7 for v in vs)
+    rgb = np.array([[float(x) for x in v[4:]] for v in vs])
+    assert rgb.min() >= 0.0 and rgb.max() <= 1.0 and len(np.unique(rgb.round(3), axis=0)) > 10
+    g = np.load(gb)
+    assert g["depth"].shape == (45, 61) and g["normal"].shape == g["albedo"].shape == (45, 61, 3) and g["material_id"].shape == g["valid"].shape == (45, 61)
+    hit = g["valid"] == 1
+    assert hit.sum() > 500 and np.isfinite(g["depth"][hit]).all() and np.isinf(g["depth"][~hit]).all()
+    assert len(np.unique(g["material_id"][hit])) >= 4
