@@ -413,6 +413,47 @@ int sdfr_pick_surfaces(sdfr_renderer *r, int width, int height, int64_t n, const
 int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits /* or NULL */,
 	sdfr_surface *surfaces, int on_host);
 
+/* ---- ambient occlusion at points, hits and mesh vertices (DESIGN.md "Occlusion queries"; no counterpart in the reference): how much
+ *      of the hemisphere above a surface point is blocked within a radius, as an integer mask of which of 64 fixed directions hit
+ *      something.  Every bit is fixed: there is no floating-point reduction and no dependence on order.
+ *      Directions: a table D[64][3] of fp32 unit vectors, cosine-distributed over the hemisphere z > 0.  For k = 0..63, in double
+ *      precision, u = (k + 0.5) / 64, phi = 2 pi frac(k (sqrt 5 - 1) / 2), d = (sqrt u cos phi, sqrt u sin phi, sqrt(1 - u)),
+ *      normalised, then rounded to fp32.  The committed table (sdfr_occlusion_dirs.h, hexadecimal literals; sdfr_occlusion_directions
+ *      returns it) is the definition, not this formula evaluated by some libm.
+ *      Frame: from a normal n, used as given and not normalised: s = copysignf(1, n.z), a = -1 / (s + n.z), b = n.x * n.y * a,
+ *      t = (1 + s * n.x * n.x * a, s * b, -s * n.x), u = (b, s + n.y * n.y * a, -n.y); every product and sum a separate fp32
+ *      operation, left to right as written, unfused.  World direction k, per component c:
+ *      w_k[c] = (t[c] * D[k][0] + u[c] * D[k][1]) + n[c] * D[k][2].
+ *      Ray k: origin = p + bias * n per component (one multiply, then one add), dir = w_k, and otherwise exactly sdfr_query_rays with
+ *      max_distance = radius: march_ray with dir.w = 1, the default MarchingInput, ray offsets 0, at most limits.iter_count
+ *      iterations, the debug plane and show_objects included.  Bit k of the mask is set iff that ray's hit == 1.  Step shortcuts do
+ *      not change hits, so the mask is the same with them on or off.
+ *      An item whose point or normal has a component that is not finite, or whose normal is (0, 0, 0), gets valid = 0 and no march.
+ *      Both entries are queries in every respect listed above: on_host, what is latched, the stream, no effect on stats, timings or
+ *      the row order, n = 0, the argument errors.  bias must be finite and >= 0, radius finite and > 0 (else
+ *      SDFR_ERR_INVALID_ARGUMENT). -------------------------------------------------------------------------------------------------- */
+typedef struct sdfr_occlusion
+{
+	uint32_t mask_lo, mask_hi; /* bit k of the 64-bit mask: direction k hit within radius */
+	uint32_t occluded;         /* popcount of the mask, 0..64; openness = 1 - occluded / 64 */
+	int32_t valid;             /* 1 answered; 0 nothing to answer (above; a miss of sdfr_hit_occlusion); -1 an invalid item; unless 1 the other words are 0 */
+} sdfr_occlusion;              /* 16 bytes: one 16-byte store per item (word stores into an array not aligned to 16 bytes) */
+
+/* The table D, [64][3].  Needs no handle. */
+int sdfr_occlusion_directions(float out[64 * 3]);
+
+/* Item i is (points[i], normals[i]), both [n][3]: sdfr_mesh_extract's two arrays as they are, or any arrays like them.  A surface-nets
+ * vertex lies a fraction of a cell off the surface, on either side of it: with a bias of about a cell the rays start outside, where a
+ * bias of 0 would start some of them inside the solid and count the surface they came from as an occluder.  For points ON the
+ * surface (ray hits) a few dist_eps suffice. */
+int sdfr_query_occlusion(sdfr_renderer *r, int64_t n, const float *points, const float *normals, float bias, float radius, sdfr_occlusion *out,
+	int on_host);
+
+/* Item i is (hits[i].pos, hits[i].normal) where hits[i].hit == 1; otherwise valid = hits[i].hit (0, or -1 for any other value) with
+ * zeros elsewhere.  Takes the hits of sdfr_query_rays, sdfr_pick and the surface queries (the whole-frame G-buffer included) as they
+ * are: no primary ray is marched a second time and no workspace is needed.  hits needs only 4-byte alignment. */
+int sdfr_hit_occlusion(sdfr_renderer *r, int64_t n, const sdfr_hit *hits, float bias, float radius, sdfr_occlusion *out, int on_host);
+
 /* ---- the loaded scene as a triangle mesh: naive surface nets over a lattice of scene distances (no counterpart in the reference;
  *      DESIGN.md "Mesh extraction").  One vertex per grid cell the surface passes through, one quad (two triangles) per lattice edge
  *      that changes sign: an indexed mesh with shared vertices, closed wherever the surface stays inside the grid.  All arithmetic

@@ -147,6 +147,17 @@ public:
 		return handle && pushState() && sdfr_mesh_surfaces(handle, n, positions, normals, reach, hits, surfaces, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// Ambient occlusion (sdfr_query_occlusion, sdfr_hit_occlusion in sdfr.h): which of 64 fixed directions above each point, or each hit
+	// of a query, meet the scene within `radius`.
+	bool queryOcclusion(int64_t n, const float *points, const float *normals, float bias, float radius, sdfr_occlusion *out, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_query_occlusion(handle, n, points, normals, bias, radius, out, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool hitOcclusion(int64_t n, const sdfr_hit *hits, float bias, float radius, sdfr_occlusion *out, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_hit_occlusion(handle, n, hits, bias, radius, out, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// The loaded scene as a triangle mesh (sdfr_mesh_extract in sdfr.h: surface nets over `grid`), with this renderer's variables and
 	// time.  counts is always filled; the arrays only if both capacities suffice (capacities 0, arrays null: the counting call).
 	bool extractMesh(const sdfr_mesh_grid &grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals, uint32_t *indices,

@@ -93,6 +93,9 @@ SURFACE_DTYPE = np.dtype([("material_id", np.uint32), ("flags", np.uint32), ("ma
 assert SURFACE_DTYPE.itemsize == 128
 SURFACE_USE_HDR = 1
 SURFACE_LIT = 2
+# sdfr_occlusion (include/sdfr.h): which of 64 fixed directions above a point are blocked within a radius, 16 bytes
+OCCLUSION_DTYPE = np.dtype([("mask_lo", np.uint32), ("mask_hi", np.uint32), ("occluded", np.uint32), ("valid", np.int32)])
+assert OCCLUSION_DTYPE.itemsize == 16
 
 
 # every symbol include/sdfr.h declares (tests check that the library exports all of them)
@@ -107,6 +110,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_comm_last_error", "sdfr_comm_selftest", "sdfr_render_gather", "sdfr_render_gather_all", "sdfr_set_launch_mode", "sdfr_set_step_shortcuts",
     "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick", "sdfr_mesh_extract", "sdfr_mesh_get_timings",
     "sdfr_render_aa", "sdfr_query_ray_surfaces", "sdfr_pick_surfaces", "sdfr_mesh_surfaces",
+    "sdfr_occlusion_directions", "sdfr_query_occlusion", "sdfr_hit_occlusion",
 ]
 
 _lib = None
@@ -209,6 +213,9 @@ def load_library():
     L.sdfr_query_ray_surfaces.argtypes = [vp, i64, vp, vp, cf, vp, vp, ci]
     L.sdfr_pick_surfaces.argtypes = [vp, ci, ci, i64, vp, vp, vp, ci]
     L.sdfr_mesh_surfaces.argtypes = [vp, i64, vp, vp, cf, vp, vp, ci]
+    L.sdfr_occlusion_directions.argtypes = [vp]
+    L.sdfr_query_occlusion.argtypes = [vp, i64, vp, vp, cf, cf, vp, ci]
+    L.sdfr_hit_occlusion.argtypes = [vp, i64, vp, cf, cf, vp, ci]
     L.sdfr_mesh_extract.argtypes = [vp, ctypes.POINTER(MeshGrid), i64, i64, vp, vp, vp, ctypes.POINTER(MeshCounts), ci]
     L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
     L.sdfr_render_gather.argtypes = [vp, vp, ci, ci, vp, ci, ci]
@@ -220,6 +227,16 @@ def load_library():
 def scene_names():
     L = load_library()
     return [L.sdfr_scene_name(i).decode() for i in range(L.sdfr_scene_count())]
+
+
+def occlusionDirections():
+    """The 64 directions of the occlusion queries (sdfr_occlusion_directions): [64, 3] float32 unit vectors, cosine-distributed over the
+    hemisphere z > 0.  Bit k of a record's mask belongs to row k turned into the frame of the item's normal (include/sdfr.h)."""
+    d = np.empty((64, 3), np.float32)
+    rc = load_library().sdfr_occlusion_directions(d.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise SdfrError(rc, "sdfr_occlusion_directions")
+    return d
 
 
 def check_scene_source(source, arch="gfx950"):
@@ -655,23 +672,71 @@ class SDFRenderer:
         inputs = (self._h, p.shape[0], p.ctypes.data_as(ctypes.c_void_p), nr.ctypes.data_as(ctypes.c_void_p), float(reach))
         return self._surfaces(self._L.sdfr_mesh_surfaces, p.shape[0], inputs, None, hits)
 
+    # ---- ambient occlusion (sdfr_query_occlusion / sdfr_hit_occlusion; DESIGN.md "Occlusion queries").  numpy arrays in:
+    # OCCLUSION_DTYPE records out.  Device tensors in: an [n, 4] int32 device tensor out (mask_lo, mask_hi, occluded, valid), enqueued
+    # on the handle's stream.
+    def _occlusion(self, call, n, inputs, like, bias, radius):
+        if like is not None:
+            import torch
+
+            out = torch.empty((n, 4), dtype=torch.int32, device=like.device)
+            self._check(call(*inputs, float(bias), float(radius), self._dev(out, 4 * n, "occlusion", ints=True) if n else None, 0))
+        else:
+            out = np.zeros(n, OCCLUSION_DTYPE)
+            self._check(call(*inputs, float(bias), float(radius), out.ctypes.data_as(ctypes.c_void_p), 1))
+        return out
+
+    def queryOcclusion(self, points, normals, bias, radius):
+        """Which of the 64 directions (occlusionDirections) above points [n, 3] with normals [n, 3] meet the scene within `radius`,
+        the rays starting `bias` off each point along its normal: OCCLUSION_DTYPE records [n]; openness is 1 - occluded / 64."""
+        if hasattr(points, "data_ptr"):
+            n = points.numel() // 3
+            inputs = (self._h, n, self._dev(points, 3 * n, "points"), self._dev(normals, 3 * n, "normals"))
+            return self._occlusion(self._L.sdfr_query_occlusion, n, inputs, points, bias, radius)
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert p.shape == nr.shape
+        inputs = (self._h, p.shape[0], p.ctypes.data_as(ctypes.c_void_p), nr.ctypes.data_as(ctypes.c_void_p))
+        return self._occlusion(self._L.sdfr_query_occlusion, p.shape[0], inputs, None, bias, radius)
+
+    def hitOcclusion(self, hits, bias, radius):
+        """queryOcclusion at the hits of queryRays, pick or the surface queries -- HIT_DTYPE records [n], or an [n, 12] device tensor --:
+        valid = 0 where the ray missed, -1 where the item was invalid."""
+        if hasattr(hits, "data_ptr"):
+            n = hits.numel() // 12
+            return self._occlusion(self._L.sdfr_hit_occlusion, n, (self._h, n, self._dev(hits, 12 * n, "hits", hits=True)), hits, bias, radius)
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE:
+            h = np.ascontiguousarray(h.view(np.uint32).reshape(-1, 12)).view(HIT_DTYPE).reshape(-1)
+        return self._occlusion(self._L.sdfr_hit_occlusion, h.shape[0], (self._h, h.shape[0], h.ctypes.data_as(ctypes.c_void_p)), None, bias, radius)
+
     # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
-    def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None):
+    def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None, occlusion=False, ao_radius=None,
+                    ao_bias=None):
         """Surface nets over the lattice origin + (i, j, k) * cell, dims = (nx, ny, nz) cells: (positions [v, 3] float32, normals [v, 3]
         float32 or None, indices [t, 3]) -- numpy arrays (indices uint32), or with device=True torch tensors on the renderer's GPU
         (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call.
         surfaces=True: a fourth element, the surface at every vertex (meshSurfaces with `reach`, default 2 * cell; needs the normals) --
-        the mesh is made on the GPU and looked at there, whatever `device` says about where the results go."""
-        if surfaces:
+        the mesh is made on the GPU and looked at there, whatever `device` says about where the results go.
+        occlusion=True: one more element, after the surfaces if both are asked for: the ambient occlusion at every vertex
+        (queryOcclusion with ao_bias, default 1 cell, and ao_radius, default 8 cells; needs the normals), looked at on the GPU likewise."""
+        if surfaces or occlusion:
             if not normals:
-                raise ValueError("surfaces=True needs the normals")
+                raise ValueError("surfaces=True and occlusion=True need the normals")
             pos, nrm, idx = self.extractMesh(origin, cell, dims, iso, True, device=True)
-            srf = self.meshSurfaces(pos, nrm, 2.0 * float(cell) if reach is None else reach)
+            extra = []
+            if surfaces:
+                extra.append(self.meshSurfaces(pos, nrm, 2.0 * float(cell) if reach is None else reach))
+            if occlusion:
+                extra.append(self.queryOcclusion(pos, nrm, float(cell) if ao_bias is None else ao_bias, 8.0 * float(cell) if ao_radius is None else ao_radius))
             if device:
-                return pos, nrm, idx, srf
+                return (pos, nrm, idx) + tuple(extra)
             self.sync()
-            return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32),
-                    srf.cpu().numpy().view(np.uint32).reshape(-1).view(SURFACE_DTYPE))
+            if surfaces:
+                extra[0] = extra[0].cpu().numpy().view(np.uint32).reshape(-1).view(SURFACE_DTYPE)
+            if occlusion:
+                extra[-1] = extra[-1].cpu().numpy().view(np.uint32).reshape(-1).view(OCCLUSION_DTYPE)
+            return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32)) + tuple(extra)
         grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
         counts = MeshCounts()
         self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), 0 if device else 1))

@@ -14,6 +14,7 @@
     python -m sdf_playground_amd.cli --scene tree --mesh tree.obj --mesh-box -2 0 -2 2 4 2 --mesh-cell 0.02   # the scene as a triangle mesh
     python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-colors --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... with its materials
     python -m sdf_playground_amd.cli --scene lense --size 640x360 --gbuffer lense.npz   # depth, normal, albedo, material id per pixel
+    python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-colors --mesh-ao 0.4 --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... shaded by ambient occlusion
 
 --out writes the tone-mapped + bloomed LDR image (HDR::process, like the reference's window);
 --out-hdr writes the raw float32 RGBA frame as .npy.  --mesh writes the scene's surface (distance == --mesh-iso) inside --mesh-box
@@ -21,7 +22,9 @@ as a Wavefront OBJ with normals: surface nets on cells of edge --mesh-cell (SDFR
 variables; --mesh-colors adds a colour per vertex (`v x y z r g b`): the albedo of the material under the vertex, or its unlit colour
 (SDFRenderer.extractMesh(surfaces=True)).  --gbuffer writes what lies under every pixel of the frame --out would render, as an .npz:
 depth [h, w] (the hit's t; inf on a miss), normal [h, w, 3] (the shading normal), albedo [h, w, 3] (as --mesh-colors, unclipped),
-material_id and valid [h, w] (SDFRenderer.pickSurfaces).  Needs a GPU.
+material_id and valid [h, w] (SDFRenderer.pickSurfaces).  --mesh-ao RADIUS multiplies the vertex colours (grey without --mesh-colors)
+by the ambient openness within RADIUS (SDFRenderer.extractMesh(occlusion=True), bias one cell); --gbuffer-ao RADIUS adds `ao` [h, w] to
+the G-buffer: the openness at each pixel's hit as float32, NaN where there is none (SDFRenderer.hitOcclusion).  Needs a GPU.
 """
 import argparse
 import math
@@ -125,11 +128,21 @@ def make_parser():
     ap.add_argument("--mesh-iso", type=float, default=0.0, metavar="V", help="the surface is distance == V (default 0)")
     ap.add_argument("--mesh-colors", action="store_true", help="with --mesh: a colour per vertex, from the material under it")
     ap.add_argument("--gbuffer", metavar="OUT.npz", help="write depth, normal, albedo, material_id and valid of every pixel of the frame")
+    ap.add_argument("--mesh-ao", type=float, metavar="RADIUS", help="with --mesh: vertex colours times the ambient openness within RADIUS")
+    ap.add_argument("--gbuffer-ao", type=float, metavar="RADIUS", help="with --gbuffer: add `ao`, the ambient openness within RADIUS at every pixel's hit")
     return ap
 
 
-def gbuffer_arrays(hits, surfaces, w, h):
-    """what --gbuffer writes, from the records of pickSurfaces(None, w, h, hits=True)"""
+GBUFFER_AO_BIAS = 0.01  # how far off a pixel's hit --gbuffer-ao starts its rays: a hundred dist_eps at the default limits
+
+
+def gbuffer_arrays(hits, surfaces, w, h, occlusion=None):
+    """what --gbuffer writes, from the records of pickSurfaces(None, w, h, hits=True); with `occlusion` (hitOcclusion of those hits) also
+    `ao`: the openness, NaN where valid != 1"""
+    if occlusion is not None:
+        from .obj import openness
+
+        return dict(gbuffer_arrays(hits, surfaces, w, h), ao=openness(occlusion).reshape(h, w))
     lit = (surfaces["flags"] & 2) != 0  # SDFR_SURFACE_LIT
     hit = surfaces["valid"] == 1
     return {"depth": np.where(hit, hits["t"], np.float32(np.inf)).astype(np.float32).reshape(h, w),
@@ -217,23 +230,34 @@ def main(argv=None):
         from .obj import write_obj
 
         colors = None
+        ao = dict(occlusion=True, ao_radius=a.mesh_ao) if a.mesh_ao is not None else {}
         if a.mesh_colors:
             from .obj import surface_colors
 
-            pos, nrm, idx, srf = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, surfaces=True)
+            pos, nrm, idx, srf, *occ = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, surfaces=True, **ao)
             colors, missing = surface_colors(srf)
         else:
-            pos, nrm, idx = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso)
-        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso), colors=colors)
+            pos, nrm, idx, *occ = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, **ao)
+        if occ:
+            from .obj import occlusion_colors
+
+            colors_written = occlusion_colors(occ[0], colors)
+        else:
+            colors_written = colors
+        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso), colors=colors_written)
         print("%s: %d vertices, %d triangles (%dx%dx%d cells) -> %s" % ((a.scene, len(pos), len(idx)) + mesh_grid[1] + (a.mesh,)))
         if colors is not None:
             print("%d of %d vertices found no surface within 2 cells and are grey" % (missing, len(pos)))
+        if occ:
+            print("ambient occlusion within %g: mean openness %.3f" % (a.mesh_ao, float(1.0 - occ[0]["occluded"][occ[0]["valid"] == 1].mean() / 64.0) if (occ[0]["valid"] == 1).any() else 1.0))
         if not a.out and not a.out_hdr and not a.gbuffer:
             r.close()
             return 0
     if a.gbuffer:
         r.setCamera(cam)
-        np.savez(a.gbuffer, **gbuffer_arrays(*r.pickSurfaces(None, w, h, hits=True), w, h))
+        hits, srf = r.pickSurfaces(None, w, h, hits=True)
+        occ = r.hitOcclusion(hits, GBUFFER_AO_BIAS, a.gbuffer_ao) if a.gbuffer_ao is not None else None
+        np.savez(a.gbuffer, **gbuffer_arrays(hits, srf, w, h, occ))
         print("%s %dx%d: G-buffer -> %s" % (a.scene, w, h, a.gbuffer))
         if not a.out and not a.out_hdr:
             r.close()

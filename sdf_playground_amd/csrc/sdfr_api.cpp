@@ -7,6 +7,7 @@
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
 #include "sdfr_mesh.h"
+#include "sdfr_occlusion.h"
 #include "sdfr_query.h"
 #include "sdfr_resolve.h"
 
@@ -720,12 +721,13 @@ static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipS
 	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "query launch");
 }
 
-// The queries (sdfr_query.h, sdfr_surface.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not
+// The queries (sdfr_query.h, sdfr_surface.h, sdfr_occlusion.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not
 // the handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
-// out: distance + normals, or hits and / or surfaces.
+// out: distance + normals, or hits and / or surfaces, or occlusion records.
 static const size_t k_query_stage_keep = (size_t)64 << 20; // staging bytes a handle keeps between host queries
 static_assert(sizeof(sdfr_hit) == 4 * QUERY_HIT_WORDS, "sdfr_hit is the query kernels' 12-word record");
 static_assert(sizeof(sdfr_surface) == 4 * QUERY_SURFACE_WORDS, "sdfr_surface is the surface kernel's 32-word record");
+static_assert(sizeof(sdfr_occlusion) == 4 * QUERY_OCCLUSION_WORDS, "sdfr_occlusion is the occlusion kernel's 4-word record");
 // the end of a host call: the answers back to the caller in the order they were named, and `stream` synchronised.  A large call
 // does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
 static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
@@ -736,7 +738,8 @@ static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
 	return SDFR_OK;
 }
 // What the entry points ask for.  kind = QUERY_*; a QUERY_MESH's positions and normals come as pos and dir.  reach: max_distance of
-// rays (0: the range), the reach of a mesh.  want_surfaces: one of the surface entries, which needs `surfaces` and takes hits or not.
+// rays (0: the range), the reach of a mesh, the radius of an occlusion query.  want_surfaces: one of the surface entries, which needs
+// `surfaces` and takes hits or not.  The occlusion kinds: items pos + dir (points and normals) or hit_items, bias -> occlusion.
 struct QueryCall
 {
 	int kind;
@@ -750,21 +753,30 @@ struct QueryCall
 	sdfr_surface *surfaces;
 	bool want_surfaces;
 	int on_host;
+	const sdfr_hit *hit_items;
+	float bias;
+	sdfr_occlusion *occlusion;
 };
 static int query_impl(sdfr_renderer *r, const QueryCall &c)
 {
 	const int kind = c.kind;
-	const bool of_pixels = kind == QUERY_PICK || kind == QUERY_FRAME, of_rays = kind == QUERY_RAYS || kind == QUERY_MESH;
+	const bool of_occlusion = kind == QUERY_OCCLUSION || kind == QUERY_HIT_OCCLUSION;
+	const bool of_pixels = kind == QUERY_PICK || kind == QUERY_FRAME, of_rays = kind == QUERY_RAYS || kind == QUERY_MESH || kind == QUERY_OCCLUSION;
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 	if (c.n < 0 || c.n > (int64_t)INT32_MAX) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad item count");
 	if (!is_flag(c.on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
-	if (kind == QUERY_MESH ? !(std::isfinite(c.reach) && c.reach > 0.f) : !std::isfinite(c.reach) || c.reach < 0.f)
-		return fail(r, SDFR_ERR_INVALID_ARGUMENT, kind == QUERY_MESH ? "reach must be finite and > 0" : "max_distance must be finite and >= 0");
+	if (kind == QUERY_MESH || of_occlusion ? !(std::isfinite(c.reach) && c.reach > 0.f) : !std::isfinite(c.reach) || c.reach < 0.f)
+		return fail(r, SDFR_ERR_INVALID_ARGUMENT,
+			of_occlusion ? "radius must be finite and > 0" : kind == QUERY_MESH ? "reach must be finite and > 0" : "max_distance must be finite and >= 0");
+	if (of_occlusion && !(std::isfinite(c.bias) && c.bias >= 0.f)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bias must be finite and >= 0");
 	if (of_pixels && !frame_size_ok(c.width, c.height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
 	if (c.n == 0) return SDFR_OK;
 	if (kind == QUERY_FRAME && c.n != (int64_t)c.width * c.height) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "without a pixel list n must be width * height");
-	const bool inputs_ok = kind == QUERY_POINTS ? c.pos != nullptr : of_rays ? c.pos && c.dir : kind == QUERY_FRAME || c.pixels != nullptr;
-	const bool outputs_ok = kind == QUERY_POINTS ? c.distance != nullptr : c.want_surfaces ? c.surfaces != nullptr : c.hits != nullptr;
+	const bool inputs_ok = kind == QUERY_POINTS ? c.pos != nullptr
+		: of_rays                             ? c.pos && c.dir
+		: kind == QUERY_HIT_OCCLUSION         ? c.hit_items != nullptr
+		                                      : kind == QUERY_FRAME || c.pixels != nullptr;
+	const bool outputs_ok = kind == QUERY_POINTS ? c.distance != nullptr : of_occlusion ? c.occlusion != nullptr : c.want_surfaces ? c.surfaces != nullptr : c.hits != nullptr;
 	if (!inputs_ok || !outputs_ok) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
 	SDFR_HIP(hipSetDevice(r->device));
@@ -785,23 +797,29 @@ static int query_impl(sdfr_renderer *r, const QueryCall &c)
 	q.normals = c.normals;
 	q.hits = reinterpret_cast<uint32_t *>(c.hits);
 	q.surfaces = reinterpret_cast<uint32_t *>(c.surfaces);
+	q.hit_items = reinterpret_cast<const uint32_t *>(c.hit_items);
+	q.occlusion = reinterpret_cast<uint32_t *>(c.occlusion);
+	q.bias = c.bias;
 	// the sizes of the arrays, in the order they are staged: inputs, then answers
 	const size_t N = (size_t)c.n;
-	const size_t in0 = kind == QUERY_FRAME ? 0 : kind == QUERY_PICK ? N * 8 : N * 12, in1 = of_rays ? N * 12 : 0;
-	const size_t out0 = kind == QUERY_POINTS ? N * 4 : c.hits ? N * sizeof(sdfr_hit) : 0;
+	const size_t in0 = kind == QUERY_FRAME ? 0 : kind == QUERY_PICK ? N * 8 : kind == QUERY_HIT_OCCLUSION ? N * sizeof(sdfr_hit) : N * 12, in1 = of_rays ? N * 12 : 0;
+	const size_t out0 = kind == QUERY_POINTS ? N * 4 : of_occlusion ? N * sizeof(sdfr_occlusion) : c.hits ? N * sizeof(sdfr_hit) : 0;
 	const size_t out1 = kind == QUERY_POINTS ? (c.normals ? N * 12 : 0) : c.surfaces ? N * sizeof(sdfr_surface) : 0;
 	Carving st({in0, in1, out0, out1});
 	if (c.on_host)
 	{
 		SDFR_HIP(st.reserve(r->query)); // (host queries are synchronous: none is using the old one)
-		if (in0) SDFR_HIP(hipMemcpyAsync(st.piece<void>(0), kind == QUERY_PICK ? (const void *)c.pixels : (const void *)c.pos, in0, hipMemcpyHostToDevice, stream));
+		const void *first = kind == QUERY_PICK ? (const void *)c.pixels : kind == QUERY_HIT_OCCLUSION ? (const void *)c.hit_items : (const void *)c.pos;
+		if (in0) SDFR_HIP(hipMemcpyAsync(st.piece<void>(0), first, in0, hipMemcpyHostToDevice, stream));
 		if (in1) SDFR_HIP(hipMemcpyAsync(st.piece<void>(1), c.dir, in1, hipMemcpyHostToDevice, stream));
-		q.pos = of_pixels ? nullptr : st.piece<const float>(0);
+		q.pos = of_pixels || kind == QUERY_HIT_OCCLUSION ? nullptr : st.piece<const float>(0);
+		q.hit_items = kind == QUERY_HIT_OCCLUSION ? st.piece<const uint32_t>(0) : nullptr;
 		q.pixels = kind == QUERY_PICK ? st.piece<const int32_t>(0) : nullptr;
 		q.dir = in1 ? st.piece<const float>(1) : nullptr;
 		q.distance = kind == QUERY_POINTS ? st.answer(2, c.distance, out0) : nullptr;
 		q.normals = kind == QUERY_POINTS && out1 ? st.answer(3, c.normals, out1) : nullptr;
-		q.hits = kind != QUERY_POINTS && out0 ? st.answer(2, reinterpret_cast<uint32_t *>(c.hits), out0) : nullptr;
+		q.hits = kind != QUERY_POINTS && !of_occlusion && out0 ? st.answer(2, reinterpret_cast<uint32_t *>(c.hits), out0) : nullptr;
+		q.occlusion = of_occlusion ? st.answer(2, reinterpret_cast<uint32_t *>(c.occlusion), out0) : nullptr;
 		q.surfaces = kind != QUERY_POINTS && out1 ? st.answer(3, reinterpret_cast<uint32_t *>(c.surfaces), out1) : nullptr;
 	}
 	rc = run_query(r, U, q, stream);
@@ -840,6 +858,27 @@ int sdfr_pick_surfaces(sdfr_renderer *r, int width, int height, int64_t n, const
 int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits, sdfr_surface *surfaces, int on_host)
 {
 	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_MESH, n, positions, normals, nullptr, 0, 0, reach, nullptr, nullptr, hits, surfaces, true, on_host}); });
+}
+
+int sdfr_occlusion_directions(float *out)
+{
+	if (!out) return SDFR_ERR_INVALID_ARGUMENT;
+	memcpy(out, k_occlusion_dirs, sizeof k_occlusion_dirs);
+	return SDFR_OK;
+}
+
+int sdfr_query_occlusion(sdfr_renderer *r, int64_t n, const float *points, const float *normals, float bias, float radius, sdfr_occlusion *out, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		return query_impl(r, {QUERY_OCCLUSION, n, points, normals, nullptr, 0, 0, radius, nullptr, nullptr, nullptr, nullptr, false, on_host, nullptr, bias, out});
+	});
+}
+
+int sdfr_hit_occlusion(sdfr_renderer *r, int64_t n, const sdfr_hit *hits, float bias, float radius, sdfr_occlusion *out, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		return query_impl(r, {QUERY_HIT_OCCLUSION, n, nullptr, nullptr, nullptr, 0, 0, radius, nullptr, nullptr, nullptr, nullptr, false, on_host, hits, bias, out});
+	});
 }
 
 // sdfr_mesh_extract (the definition: include/sdfr.h; stages: sdfr_mesh.h, sdfr_mesh.hip).  Like a query it latches the frame into a

@@ -48,7 +48,7 @@ struct KernelRef
 hipError_t launch_kernel(const KernelRef &k, uint32_t blocks, uint32_t threads, void **args, hipStream_t stream);
 // A scene's query kernels [kind][DBG]: a built-in scene's query unit exports them (sdfr_query_scene.hip), a run-time scene's
 // query module is looked up into the same table (jit_query_kernels, sdfr_jit.h)
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_KINDS = 4 }; // (rays: picks too)
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_KINDS = 5 }; // (rays: picks too)
 struct QueryKernels
 {
 	KernelRef k[QUERY_KERNEL_KINDS][2];
@@ -65,7 +65,7 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 
 // one query (sdfr_query.h) by a scene's kernel of q's kind (query_kernel_kind) for U: q.n > 0 items, every pointer device memory
 struct QueryArgs;
-int query_kernel_kind(const QueryArgs &q); // QUERY_KERNEL_*: points; surfaces where q.surfaces is given; else rays or picks
+int query_kernel_kind(const QueryArgs &q); // QUERY_KERNEL_*: points; occlusion; surfaces where q.surfaces is given; else rays or picks
 hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream);
 // the distance query over a lattice (sdfr_query.h: LatticeArgs) by a scene's lattice kernel for U
 struct LatticeArgs;

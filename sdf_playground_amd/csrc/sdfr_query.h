@@ -13,7 +13,9 @@ namespace sdfr {
 // With `surfaces` [n][32] (sdfr_surface.h) the surface kernel answers, `hits` may be null, and two more kinds of items exist.
 // Frame: every pixel of the width x height frame, item y * width + x, n = width * height, nothing read.  Mesh: `pos` = vertex
 // positions, `dir` = vertex normals, the ray towards each vertex from `reach` outside it (query_mesh_ray).
-enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2, QUERY_FRAME = 3, QUERY_MESH = 4 };
+// The occlusion kernel (sdfr_occlusion.h) answers the last two kinds into `occlusion` [n][4]: items that are `pos` = points and
+// `dir` = normals, or the pos and normal of the hit records `hit_items` [n][12]; `dist_max` is the radius.
+enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2, QUERY_FRAME = 3, QUERY_MESH = 4, QUERY_OCCLUSION = 5, QUERY_HIT_OCCLUSION = 6 };
 struct QueryArgs
 {
 	int kind;  // QUERY_*
@@ -25,8 +27,12 @@ struct QueryArgs
 	float *distance, *normals;
 	uint32_t *hits;     // 12 words per item: the layout of sdfr_hit
 	uint32_t *surfaces; // 32 words per item: the layout of sdfr_surface
+	// the occlusion kinds (appended: the other kernels' argument offsets stay)
+	const uint32_t *hit_items; // 12 words per item, read
+	uint32_t *occlusion;       // 4 words per item: the layout of sdfr_occlusion
+	float bias;
 };
-enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32 };
+enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32, QUERY_OCCLUSION_WORDS = 4 };
 // what a query kernel takes: one argument, as the pixel kernels (PixelKernelArgs)
 struct QueryKernelArgs
 {
@@ -111,12 +117,16 @@ SDF_HD float query_point(const FrameU &U, vec3 p, vec3 *normal)
 // With FrameU::step_shortcuts a miss may end early, as in the pixel pipeline (render_pixel): hits are unchanged.
 // rec: the 12 words of sdfr_hit.  Returns whether the ray hit; of a hit, `at` is the surface point and the material map_material
 // made of it, for whoever goes on where the driver does (sdfr_surface.h).
+// MARCH_ONLY: the march alone -- whether the ray hit is all that is returned, the normal and map_material of a hit are not computed,
+// `rec` and `at` are not touched (query_ray_hits; the occlusion query, sdfr_occlusion.h).  One copy of the march for both; a
+// template parameter and not a function of its own, because the existing kernels' code stays the same, instruction for instruction,
+// only if the body they instantiate does.
 struct QueryHit
 {
 	SurfacePoint sp;
 	Material mat;
 };
-template <class Scene, bool DBG>
+template <class Scene, bool DBG, bool MARCH_ONLY = false>
 SDF_HD bool query_ray_at(const FrameU &U, vec3 origin, vec3 dir, float dist_max, vec3 right_off, vec3 bottom_off, uint32_t rec[QUERY_HIT_WORDS],
 	QueryHit &at)
 {
@@ -147,6 +157,7 @@ SDF_HD bool query_ray_at(const FrameU &U, vec3 origin, vec3 dir, float dist_max,
 		}
 		status = march_advance(m, d, dist_max, (uint32_t)U.iter_count, U.dist_eps);
 	} while (status == MARCH_CONTINUE);
+	if constexpr (MARCH_ONLY) return status == MARCH_HIT;
 
 	const vec3 pos = march_pos(m);
 	vec3 n = V3s(0.f);
@@ -186,6 +197,15 @@ SDF_HD void query_ray(const FrameU &U, vec3 origin, vec3 dir, float dist_max, ve
 {
 	QueryHit at;
 	query_ray_at<Scene, DBG>(U, origin, dir, dist_max, right_off, bottom_off, rec, at);
+}
+
+// whether the ray hits: query_ray's march and its `hit`, nothing else
+template <class Scene, bool DBG>
+SDF_HD bool query_ray_hits(const FrameU &U, vec3 origin, vec3 dir, float dist_max, vec3 right_off, vec3 bottom_off)
+{
+	uint32_t rec[QUERY_HIT_WORDS];
+	QueryHit at;
+	return query_ray_at<Scene, DBG, true>(U, origin, dir, dist_max, right_off, bottom_off, rec, at);
 }
 
 // Pick: pixel (px, py)'s primary ray of the frame U describes (pshader_sdf.hlsl:263-267), marched to limits.range; a pixel

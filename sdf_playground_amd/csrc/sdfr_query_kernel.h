@@ -1,4 +1,4 @@
-// sdfr_query_kernel.h -- the query kernels (sdfr_query.h), one lane per item.  Shared by the kernels compiled ahead of time
+// sdfr_query_kernel.h -- the query kernels (sdfr_query.h), one lane per item (the occlusion kernel: one wave per item).  Shared by the kernels compiled ahead of time
 // (sdfr_query_scene.hip, a translation unit of its own so that the pixel kernels' code does not change) and by the query
 // module sdfr_jit.cpp builds for a scene compiled at run time.  Device compilation only.
 //
@@ -8,6 +8,7 @@
 #include "sdfr_pixel_kernel.h"
 #include "sdfr_query.h"
 #include "sdfr_surface.h"
+#include "sdfr_occlusion.h"
 
 namespace sdfr {
 
@@ -114,6 +115,46 @@ __device__ __forceinline__ void query_surfaces_kernel(const QueryKernelArgs &a)
 	query_surface<Scene, DBG>(U, ray, in_frame, hit, rec);
 	if (q.hits) query_store(q.hits, i, hit);
 	query_store(q.surfaces, i, rec);
+}
+
+// The occlusion queries (sdfr_occlusion.h): one wave per block, one block per item, lane k marches direction k.  The item -- a point
+// and a normal, or a hit record -- is addressed by the block index alone, so it is read once for the wave (scalar loads); an item
+// without an answer is written by one lane and the whole wave leaves.  All 64 rays start at one origin, so the scenes' wave-level
+// branches start coherent; a lane whose ray has ended waits for the slowest and does nothing else: neither the normal nor the
+// material of a hit is computed.  The mask is one ballot of the hit flags, and one lane writes the 16-byte record.
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_occlusion_kernel(const QueryKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64 && OCCLUSION_DIRS == 64, "one wave per block, one lane per direction");
+	const FrameU &U = a.U;
+	const QueryArgs &q = a.q;
+	const uint32_t i = blockIdx.x, lane = threadIdx.x; // (launch_query: q.n blocks)
+	vec3 p, n;
+	uint32_t valid = 1u;
+	if (q.kind == QUERY_HIT_OCCLUSION)
+	{
+		const uint32_t *h = q.hit_items + (size_t)QUERY_HIT_WORDS * i;
+		valid = occlusion_hit_valid(h[10]);
+		p = V3(bits_f32(h[2]), bits_f32(h[3]), bits_f32(h[4]));
+		n = V3(bits_f32(h[5]), bits_f32(h[6]), bits_f32(h[7]));
+	}
+	else
+	{
+		p = query_load3(q.pos, i);
+		n = query_load3(q.dir, i);
+	}
+	if (valid == 1u && !occlusion_item_ok(p, n)) valid = 0u;
+	uint32_t rec[QUERY_OCCLUSION_WORDS];
+	if (valid != 1u)
+	{
+		occlusion_none(valid, rec);
+		if (lane == 0u) query_store(q.occlusion, i, rec);
+		return;
+	}
+	const bool hit = occlusion_ray_hits<Scene, DBG>(U, p, n, q.bias, q.dist_max, lane);
+	const uint64_t mask = __ballot(hit);
+	occlusion_record(mask, (uint32_t)__popcll(mask), rec);
+	if (lane == 0u) query_store(q.occlusion, i, rec);
 }
 
 // The distance query over a lattice (LatticeArgs): one wave per block, one point per lane.  A wave owns a 4 x 4 x 4 brick of points,

@@ -16,6 +16,27 @@ def surface_colors(surfaces):
     return rgb, int(missing.sum())
 
 
+def openness(occlusion):
+    """1 - occluded / 64 of OCCLUSION_DTYPE records as float32 (every value is exact); NaN where valid != 1."""
+    import numpy as np
+
+    o = (np.float32(1.0) - occlusion["occluded"].astype(np.float32) / np.float32(64.0)).astype(np.float32)
+    o[occlusion["valid"] != 1] = np.nan
+    return o
+
+
+def occlusion_colors(occlusion, colors=None):
+    """Per-vertex colours [v, 3] float32 shaded by ambient occlusion: `colors` (surface_colors; without them MISSING_COLOR's grey) times
+    the openness of the OCCLUSION_DTYPE records (extractMesh(occlusion=True)); a vertex without an answer keeps its colour."""
+    import numpy as np
+
+    o = np.nan_to_num(openness(occlusion), nan=1.0)
+    base = np.tile(np.array(MISSING_COLOR, np.float32), (len(o), 1)) if colors is None else np.asarray(colors, np.float32)
+    if len(base) != len(o):
+        raise ValueError("%d colours for %d occlusion records" % (len(base), len(o)))
+    return (base * o[:, None]).astype(np.float32)
+
+
 def write_obj(out, positions, normals, indices, comment=None, colors=None):
     """Writes the mesh to `out` (a path or a text file object): one `v x y z` per vertex -- `v x y z r g b` with `colors` [v, 3], the
     per-vertex colour extension most tools read --, one `vn x y z` per vertex if `normals` is given, one `f a//a b//b c//c`

@@ -1,0 +1,126 @@
+// tests/cpp/occlusion_host.cpp -- TEST-ONLY: the library's occlusion queries (sdf_playground_amd/csrc/sdfr_occlusion.h) compiled for
+// the CPU, as surface_host.cpp compiles the surface queries, so that the CPU test tier can compare them with the oracle's definition
+// (occlusion_oracle.cpp) bit for bit without a GPU.  An item is done as the kernel's wave does it: the validity test, then lane k's
+// ray for k = 0..63, the hit flags gathered into the mask (the kernel's ballot).  Built once for the scenes compiled ahead of time,
+// and once per run-time scene with -DSDFR_HLSL_SCENE_FILE="<generated file>".  The product never loads this.
+#include "sdfr_hostframe.h"
+#include "sdfr_occlusion.h"
+#ifdef SDFR_HLSL_SCENE_FILE
+#include "sdfr_hlsl.h"
+namespace sdfr {
+#include SDFR_HLSL_SCENE_FILE
+} // namespace sdfr
+#endif
+
+#include <cstring>
+#include <thread>
+#include <vector>
+
+using namespace sdfr;
+
+namespace {
+
+// items [0, n) over up to 16 threads, in contiguous chunks
+template <class F>
+void parallel_items(int n, F fn)
+{
+	int t = (int)std::thread::hardware_concurrency();
+	t = t < 1 ? 1 : (t > 16 ? 16 : t);
+	if (n < 8) t = 1;
+	std::vector<std::thread> pool;
+	const int chunk = (n + t - 1) / t;
+	for (int k = 0; k < t; ++k)
+	{
+		const int a = k * chunk, b = a + chunk < n ? a + chunk : n;
+		if (a >= b) break;
+		pool.emplace_back([=]() { fn(a, b); });
+	}
+	for (auto &th : pool) th.join();
+}
+
+typedef void (*ItemFn)(const FrameU &, vec3, vec3, uint32_t, float, float, uint32_t *);
+
+// `valid`: 1 for a point with a normal, occlusion_hit_valid of a hit record's word
+template <class Scene, bool DBG>
+void item_of(const FrameU &U, vec3 p, vec3 n, uint32_t valid, float bias, float radius, uint32_t *rec)
+{
+	if (valid == 1u && !occlusion_item_ok(p, n)) valid = 0u;
+	if (valid != 1u)
+	{
+		occlusion_none(valid, rec);
+		return;
+	}
+	uint64_t mask = 0;
+	uint32_t count = 0;
+	for (uint32_t lane = 0; lane < OCCLUSION_DIRS; ++lane)
+		if (occlusion_ray_hits<Scene, DBG>(U, p, n, bias, radius, lane))
+		{
+			mask |= (uint64_t)1 << lane;
+			++count;
+		}
+	occlusion_record(mask, count, rec);
+}
+template <class Scene>
+ItemFn fn_of(const FrameU &U)
+{
+	return frame_needs_debug(U) ? &item_of<Scene, true> : &item_of<Scene, false>;
+}
+
+// the frame as the library latches it for a query (latch_into, sdfr_api.cpp); false: no such scene
+bool latch(const char *scene, FrameU &U, ItemFn &f)
+{
+#ifdef SDFR_HLSL_SCENE_FILE
+	(void)scene;
+	frame_derive(U, -1);
+#ifdef SDFR_SCENE_HAS_PREPARE
+	Scene::prepare(U);
+#endif
+	f = fn_of<Scene>(U);
+	return true;
+#else
+	const int si = scene_index(scene);
+	if (si < 0) return false;
+	frame_derive(U, si);
+	switch (si)
+	{
+#define SDFR_FN(I, S) case I: f = fn_of<S>(U); return true;
+		SDFR_FOR_EACH_SCENE(SDFR_FN)
+#undef SDFR_FN
+	}
+	return false;
+#endif
+}
+
+} // namespace
+
+extern "C" {
+
+// `frame`: the inputs of a FrameU (tests/hostsim frame_from_oracle); width and height are set here as the library sets them.
+// hits = null: items points[i], normals[i]; else the hit records [n][12]
+int oh_occlusion(const char *scene, const FrameU *frame, int n, const float *points, const float *normals, const uint32_t *hits, float bias, float radius,
+	uint32_t *out)
+{
+	FrameU U = *frame;
+	U.width = U.height = 1;
+	ItemFn f;
+	if (!latch(scene, U, f)) return -1;
+	parallel_items(n, [&](int lo, int hi) {
+		for (int i = lo; i < hi; ++i)
+		{
+			if (hits)
+			{
+				const uint32_t *h = hits + QUERY_HIT_WORDS * i;
+				f(U, V3(bits_f32(h[2]), bits_f32(h[3]), bits_f32(h[4])), V3(bits_f32(h[5]), bits_f32(h[6]), bits_f32(h[7])), occlusion_hit_valid(h[10]), bias, radius,
+					out + QUERY_OCCLUSION_WORDS * i);
+			}
+			else
+				f(U, V3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), V3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]), 1u, bias, radius,
+					out + QUERY_OCCLUSION_WORDS * i);
+		}
+	});
+	return 0;
+}
+void oh_directions(float *out) { memcpy(out, k_occlusion_dirs, sizeof k_occlusion_dirs); }
+int oh_frame_size() { return (int)sizeof(FrameU); }
+
+} // extern "C"
