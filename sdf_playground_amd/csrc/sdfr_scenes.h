@@ -221,13 +221,28 @@ struct SceneLabyrinth
 		return d;
 	}
 
-	// 20 x 20 cells, mirrored into one octant
+	// op_rep_inf_c(p, 20, 1 / 20) = (x - 20 * floor1(x / 20)) - 10 with x = p + 10, the product and the difference in one fma: the
+	// same bits whenever 20 * f, f = floor1(x / 20), is a float, and the fma then rounds the same exact difference once.  20 f = 4 * (5 f)
+	// is a float when the integer 5 |f| is one: for 5 |f| <= 2^24, that is |f| <= 3355443 -- every |x| < 67108860 (= 20 * 3355443;
+	// |p| <= 67108848 to be sure of x).  Beyond that 20 f may need a 25th bit and the two forms part (tests/test_labyrinth_step_cpu.py
+	// asserts the inside of this edge and shows the first difference beyond it).  What a march reaches: t is at most the range before
+	// an advance, a step is at most 1.5 d, and d <= the walls' distance <= |p.y| + 15, so a sample lies within 2.5 range + 1.5 |origin.y| + 23
+	// of the ray's origin (|dir| <= 1): far inside for every range and every origin up to 1e7 (the default range is 100).
+	// A distance query at a caller's point beyond the edge gets the fused form's bits: the domain, as for div_c.
+	// Non-finite p (a range or an origin of the order of 1e38, nothing else overflows t): inf - inf, NaN in both forms.
+	static SDF_HD float rep20(float p)
+	{
+		const float x = p + 10.f;
+		return fma1(-20.f, floor1(div_c(x, 20.f, 1.0f / 20.f)), x) - 10.f;
+	}
+	// 20 x 20 cells, mirrored into one octant: the larger of the two absolute values first.  max1 / min1 instead of "if (wz > wx) swap":
+	// both operands are abs1 results, so never -0, and for every pair without a NaN the larger and the smaller are the same two bit
+	// patterns either way (equal values are equal bits).  A NaN -- only from a non-finite p.x or p.z, see rep20 -- stayed in its
+	// place in the swap form and is dropped by max1 / min1 (both components become the other value): outside the domain, like rep20.
 	static SDF_HD vec3 fold(vec3 p)
 	{
-		vec2 rep = op_rep_inf_c(V2(p.x, p.z), 20.f, 1.0f / 20.f);
-		float wx = abs1(rep.x), wz = abs1(rep.y);
-		if (wz > wx) { float t = wx; wx = wz; wz = t; }
-		return V3(wx, p.y, wz);
+		const float ax = abs1(rep20(p.x)), az = abs1(rep20(p.z));
+		return V3(max1(ax, az), p.y, min1(ax, az));
 	}
 	// min1(sd_box(p1, b1), sd_box(p2, b2)) with one square root instead of two, bit for bit.  Per box
 	// sd_box = s + m with a = dot(o, o), o = max(q, 0), s = sqrt1(a), m = min1(max1(q.x, q.y, q.z), 0):
@@ -292,9 +307,23 @@ struct SceneLabyrinth
 		const float k = reach + radius;
 		return dot(v, v) >= k * k;
 	}
+	// ground_dist (sdfr_lib.h) with the height dot(p, (0, 1, 0)) = (0 * p.x + 1 * p.y) + 0 * p.z as two fused multiply-adds: 0 * p.x and
+	// 0 * p.z are exact (a zero with the coordinate's sign; NaN for a non-finite one), so each fma rounds the very sum the multiplication
+	// and the addition rounded: the same bits for EVERY input, one instruction fewer (v_mul, v_add, v_fmac -> v_fma, v_fmac).
+	// Not p.y alone (three fewer) and not p.y + 0 (two fewer): for finite p.x, p.z the dot is p.y when p.y != 0, but a zero whose sign
+	// the other two decide when it is not -- -0 only for p.y = -0 with p.x and p.z both negative or -0.  A rendered pixel cannot
+	// tell (a ray that starts at y = +-0 ends at its first sample, and the shading reads hit.d only through a difference and a max1 that
+	// drop the sign), but the distance and ray queries hand that zero to the caller bit for bit (sdfr_query.h: query_point's result,
+	// rec[1] of a ray query from y = -0; tests/test_query_cpu.py has such points), and both forms lose the NaN of a non-finite p.x
+	// or p.z.  tests/test_labyrinth_step_cpu.py holds all three forms against the dot.  The other scenes keep ground_dist.
+	static SDF_HD float floor_dist(vec3 p, bool fast, const GroundInv &g)
+	{
+		const float h = fma1(0.f, p.z, fma1(0.f, p.x, p.y));
+		return fast ? div_c(h, g.denom, g.rdenom) : h;
+	}
 	static SDF_HD float dist(const FrameU &U, const RayInv &R, vec3 p, vec3, bool fast)
 	{
-		float d = min1(3e38f, ground_dist(p, fast, R.ground));
+		float d = min1(3e38f, floor_dist(p, fast, R.ground));
 		const vec3 wp = fold(p);
 		d = min1(d, walls(wp));
 		// One test before the two: both bounding balls (vase: centres (7 | 9, 1.2, 3), r 1.51; torch: (5.2, 2.9, 3), r 0.91) lie in
