@@ -550,45 +550,57 @@ class SDFRenderer:
             raise ValueError("%s: %d elements, expected %d" % (what, t.numel(), numel))
         return ctypes.c_void_p(t.data_ptr())
 
-    def queryDistance(self, points, normals=False, out=None, out_normals=None):
-        """Scene distance at points [n, 3] (and the normal there if `normals`): distance [n] or (distance [n], normals [n, 3])."""
-        if hasattr(points, "data_ptr"):
-            n = points.numel() // 3
+    def _inputs(self, *specs):
+        """The input arrays of a query, specs (array, dtype, columns, name): numpy arrays (made contiguous, of equal length) or, if the
+        first is a device tensor, device tensors (checked: _dev).  -> (n, pointers, the first tensor or None for numpy)"""
+        first, _dtype, columns, _name = specs[0]
+        if hasattr(first, "data_ptr"):
+            n, dev = first.numel() // columns, self._dev
+            return n, [dev(a, c * n, name, dt is np.int32, dt is HIT_DTYPE) for a, dt, c, name in specs], first
+        arrays = []
+        for a, dt, c, _name in specs:
+            a = np.ascontiguousarray(a) if dt is HIT_DTYPE else np.ascontiguousarray(a, dt).reshape(-1, c)
+            if dt is HIT_DTYPE and a.dtype != HIT_DTYPE:  # [n, 12] words
+                a = np.ascontiguousarray(a.view(np.uint32).reshape(-1, c)).view(HIT_DTYPE).reshape(-1)
+            assert not arrays or a.shape == arrays[0].shape
+            arrays.append(a)
+        return arrays[0].shape[0], [a.ctypes.data_as(ctypes.c_void_p) for a in arrays], None
+
+    # the answers of the queries: (numpy dtype, numpy columns, device tensor columns, device tensor is int32, hit records)
+    _DISTANCE = (np.float32, 0, 0, False, False)
+    _NORMALS = (np.float32, 3, 3, False, False)
+    _HITS = (HIT_DTYPE, 0, 12, False, True)
+    _SURFACES = (SURFACE_DTYPE, 0, 32, False, False)
+    _OCCLUSION = (OCCLUSION_DTYPE, 0, 4, True, False)
+
+    def _answer(self, n, like, kind, name, given=None):
+        """One answer array of a query on the side of its inputs (like: their first device tensor, or None for numpy): a new numpy array
+        ([n] records, [n, columns] or [n] float32), or a device tensor -- the caller's `given`, checked, or a new one: [n, columns]
+        or [n], float32 or int32.  -> (array, pointer)"""
+        dtype, columns, words, ints, hits = kind
+        if like is None:
+            a = np.zeros((n, columns) if columns else n, dtype)
+            return a, a.ctypes.data_as(ctypes.c_void_p)
+        if given is None:
             import torch
 
-            if out is None:
-                out = torch.empty(n, dtype=torch.float32, device=points.device)
-            if normals and out_normals is None:
-                out_normals = torch.empty((n, 3), dtype=torch.float32, device=points.device)
-            pn = self._dev(out_normals, 3 * n, "out_normals") if normals else None
-            self._check(self._L.sdfr_query_distance(self._h, n, self._dev(points, 3 * n, "points"), self._dev(out, n, "out"), pn, 0))
-            return (out, out_normals) if normals else out
-        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        n = p.shape[0]
-        d = np.empty(n, np.float32)
-        nr = np.empty((n, 3), np.float32) if normals else None
-        self._check(self._L.sdfr_query_distance(self._h, n, p.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p),
-                                                nr.ctypes.data_as(ctypes.c_void_p) if normals else None, 1))
+            given = torch.empty((n, words) if words else n, dtype=torch.int32 if ints else torch.float32, device=like.device)
+        return given, self._dev(given, n * (words or 1), name, ints, hits)
+
+    def queryDistance(self, points, normals=False, out=None, out_normals=None):
+        """Scene distance at points [n, 3] (and the normal there if `normals`): distance [n] or (distance [n], normals [n, 3])."""
+        n, (p,), like = self._inputs((points, np.float32, 3, "points"))
+        d, pd = self._answer(n, like, self._DISTANCE, "out", out)
+        nr, pn = self._answer(n, like, self._NORMALS, "out_normals", out_normals) if normals else (None, None)
+        self._check(self._L.sdfr_query_distance(self._h, n, p, pd, pn, like is None))
         return (d, nr) if normals else d
 
     def queryRays(self, origins, dirs, max_distance=0.0, out=None):
         """First hit along rays origins [n, 3] + t * dirs [n, 3] (dirs as given, not normalised; max_distance 0 = limits.range):
         a HIT_DTYPE array [n], or the [n, 12] device tensor `out`."""
-        if hasattr(origins, "data_ptr"):
-            n = origins.numel() // 3
-            import torch
-
-            if out is None:
-                out = torch.empty((n, 12), dtype=torch.float32, device=origins.device)
-            self._check(self._L.sdfr_query_rays(self._h, n, self._dev(origins, 3 * n, "origins"), self._dev(dirs, 3 * n, "dirs"), float(max_distance),
-                                                self._dev(out, 12 * n, "out", hits=True), 0))
-            return out
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        assert o.shape == d.shape
-        hits = np.empty(o.shape[0], HIT_DTYPE)
-        self._check(self._L.sdfr_query_rays(self._h, o.shape[0], o.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p),
-                                            float(max_distance), hits.ctypes.data_as(ctypes.c_void_p), 1))
+        n, (o, d), like = self._inputs((origins, np.float32, 3, "origins"), (dirs, np.float32, 3, "dirs"))
+        hits, ph = self._answer(n, like, self._HITS, "out", out)
+        self._check(self._L.sdfr_query_rays(self._h, n, o, d, float(max_distance), ph, like is None))
         return hits
 
     def pick(self, pixels_xy, width, height, camera=None, out=None):
@@ -596,119 +608,63 @@ class SDFRenderer:
         (hit = -1 for a pixel outside the frame), or the [n, 12] device tensor `out`."""
         if camera is not None:
             self.setCamera(camera)
-        if hasattr(pixels_xy, "data_ptr"):
-            n = pixels_xy.numel() // 2
-            import torch
-
-            if out is None:
-                out = torch.empty((n, 12), dtype=torch.float32, device=pixels_xy.device)
-            self._check(self._L.sdfr_pick(self._h, int(width), int(height), n, self._dev(pixels_xy, 2 * n, "pixels_xy", ints=True), self._dev(out, 12 * n, "out", hits=True), 0))
-            return out
-        px = np.ascontiguousarray(pixels_xy, np.int32).reshape(-1, 2)
-        hits = np.empty(px.shape[0], HIT_DTYPE)
-        self._check(self._L.sdfr_pick(self._h, int(width), int(height), px.shape[0], px.ctypes.data_as(ctypes.c_void_p),
-                                      hits.ctypes.data_as(ctypes.c_void_p), 1))
+        n, (px,), like = self._inputs((pixels_xy, np.int32, 2, "pixels_xy"))
+        hits, ph = self._answer(n, like, self._HITS, "out", out)
+        self._check(self._L.sdfr_pick(self._h, int(width), int(height), n, px, ph, like is None))
         return hits
 
     # ---- what the surface looks like at a hit (sdfr_query_ray_surfaces / sdfr_pick_surfaces / sdfr_mesh_surfaces; DESIGN.md "Surface
     # queries").  numpy arrays in: SURFACE_DTYPE records out (and HIT_DTYPE records with hits=True).  Device tensors in: [n, 32] (and
     # [n, 12]) float32 device tensors out, whose integer fields (columns 0-3 of a surface) are read with .view(torch.int32).
-    def _surfaces(self, call, n, inputs, like, hits):
-        """one surface query: call(hits pointer, surfaces pointer, on_host) -> status; `like`: the device tensor that decides the
-        device path, or None for numpy"""
-        if like is not None:
-            import torch
-
-            h = torch.empty((n, 12), dtype=torch.float32, device=like.device) if hits else None
-            s = torch.empty((n, 32), dtype=torch.float32, device=like.device)
-            self._check(call(*inputs, self._dev(h, 12 * n, "hits", hits=True) if hits and n else None, self._dev(s, 32 * n, "surfaces") if n else None, 0))
-        else:
-            h = np.zeros(n, HIT_DTYPE) if hits else None
-            s = np.zeros(n, SURFACE_DTYPE)
-            self._check(call(*inputs, h.ctypes.data_as(ctypes.c_void_p) if hits else None, s.ctypes.data_as(ctypes.c_void_p), 1))
+    def _surfaces(self, call, n, like, hits, *scalars_and_inputs):
+        h, ph = self._answer(n, like, self._HITS, "hits") if hits else (None, None)
+        s, ps = self._answer(n, like, self._SURFACES, "surfaces")
+        self._check(call(self._h, *scalars_and_inputs, ph, ps, like is None))
         return (h, s) if hits else s
 
     def queryRaySurfaces(self, origins, dirs, max_distance=0.0, hits=False):
         """The surface at the first hit along rays (as queryRays): SURFACE_DTYPE records [n], or (hits, surfaces) with hits=True."""
-        if hasattr(origins, "data_ptr"):
-            n = origins.numel() // 3
-            inputs = (self._h, n, self._dev(origins, 3 * n, "origins"), self._dev(dirs, 3 * n, "dirs"), float(max_distance))
-            return self._surfaces(self._L.sdfr_query_ray_surfaces, n, inputs, origins, hits)
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        assert o.shape == d.shape
-        inputs = (self._h, o.shape[0], o.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p), float(max_distance))
-        return self._surfaces(self._L.sdfr_query_ray_surfaces, o.shape[0], inputs, None, hits)
+        n, (o, d), like = self._inputs((origins, np.float32, 3, "origins"), (dirs, np.float32, 3, "dirs"))
+        return self._surfaces(self._L.sdfr_query_ray_surfaces, n, like, hits, n, o, d, float(max_distance))
 
     def pickSurfaces(self, pixels_xy, width, height, hits=False, device=False):
         """The surface under pixels [n, 2] of a width x height frame of the current camera (as pick).  pixels_xy=None: the G-buffer,
         every pixel of the frame in row-major order (height * width records; device=True: as device tensors)."""
         width, height = int(width), int(height)
         if pixels_xy is None:
-            like = None
+            n, px, like = width * height, None, None
             if device:
                 import torch
 
                 like = torch.empty(0, device=torch.device("cuda", self.device))
-            return self._surfaces(self._L.sdfr_pick_surfaces, width * height, (self._h, width, height, width * height, None), like, hits)
-        if hasattr(pixels_xy, "data_ptr"):
-            n = pixels_xy.numel() // 2
-            inputs = (self._h, width, height, n, self._dev(pixels_xy, 2 * n, "pixels_xy", ints=True))
-            return self._surfaces(self._L.sdfr_pick_surfaces, n, inputs, pixels_xy, hits)
-        px = np.ascontiguousarray(pixels_xy, np.int32).reshape(-1, 2)
-        inputs = (self._h, width, height, px.shape[0], px.ctypes.data_as(ctypes.c_void_p))
-        return self._surfaces(self._L.sdfr_pick_surfaces, px.shape[0], inputs, None, hits)
+        else:
+            n, (px,), like = self._inputs((pixels_xy, np.int32, 2, "pixels_xy"))
+        return self._surfaces(self._L.sdfr_pick_surfaces, n, like, hits, width, height, n, px)
 
     def meshSurfaces(self, positions, normals, reach, hits=False):
         """The surface at mesh vertices positions [n, 3] with normals [n, 3], each looked at from `reach` outside it along its normal
         (sdfr_mesh_surfaces); valid = 0 where that ray misses."""
-        if hasattr(positions, "data_ptr"):
-            n = positions.numel() // 3
-            inputs = (self._h, n, self._dev(positions, 3 * n, "positions"), self._dev(normals, 3 * n, "normals"), float(reach))
-            return self._surfaces(self._L.sdfr_mesh_surfaces, n, inputs, positions, hits)
-        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
-        nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-        assert p.shape == nr.shape
-        inputs = (self._h, p.shape[0], p.ctypes.data_as(ctypes.c_void_p), nr.ctypes.data_as(ctypes.c_void_p), float(reach))
-        return self._surfaces(self._L.sdfr_mesh_surfaces, p.shape[0], inputs, None, hits)
+        n, (p, nr), like = self._inputs((positions, np.float32, 3, "positions"), (normals, np.float32, 3, "normals"))
+        return self._surfaces(self._L.sdfr_mesh_surfaces, n, like, hits, n, p, nr, float(reach))
 
     # ---- ambient occlusion (sdfr_query_occlusion / sdfr_hit_occlusion; DESIGN.md "Occlusion queries").  numpy arrays in:
     # OCCLUSION_DTYPE records out.  Device tensors in: an [n, 4] int32 device tensor out (mask_lo, mask_hi, occluded, valid), enqueued
     # on the handle's stream.
-    def _occlusion(self, call, n, inputs, like, bias, radius):
-        if like is not None:
-            import torch
-
-            out = torch.empty((n, 4), dtype=torch.int32, device=like.device)
-            self._check(call(*inputs, float(bias), float(radius), self._dev(out, 4 * n, "occlusion", ints=True) if n else None, 0))
-        else:
-            out = np.zeros(n, OCCLUSION_DTYPE)
-            self._check(call(*inputs, float(bias), float(radius), out.ctypes.data_as(ctypes.c_void_p), 1))
-        return out
-
     def queryOcclusion(self, points, normals, bias, radius):
         """Which of the 64 directions (occlusionDirections) above points [n, 3] with normals [n, 3] meet the scene within `radius`,
         the rays starting `bias` off each point along its normal: OCCLUSION_DTYPE records [n]; openness is 1 - occluded / 64."""
-        if hasattr(points, "data_ptr"):
-            n = points.numel() // 3
-            inputs = (self._h, n, self._dev(points, 3 * n, "points"), self._dev(normals, 3 * n, "normals"))
-            return self._occlusion(self._L.sdfr_query_occlusion, n, inputs, points, bias, radius)
-        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-        assert p.shape == nr.shape
-        inputs = (self._h, p.shape[0], p.ctypes.data_as(ctypes.c_void_p), nr.ctypes.data_as(ctypes.c_void_p))
-        return self._occlusion(self._L.sdfr_query_occlusion, p.shape[0], inputs, None, bias, radius)
+        n, (p, nr), like = self._inputs((points, np.float32, 3, "points"), (normals, np.float32, 3, "normals"))
+        out, po = self._answer(n, like, self._OCCLUSION, "occlusion")
+        self._check(self._L.sdfr_query_occlusion(self._h, n, p, nr, float(bias), float(radius), po, like is None))
+        return out
 
     def hitOcclusion(self, hits, bias, radius):
         """queryOcclusion at the hits of queryRays, pick or the surface queries -- HIT_DTYPE records [n], or an [n, 12] device tensor --:
         valid = 0 where the ray missed, -1 where the item was invalid."""
-        if hasattr(hits, "data_ptr"):
-            n = hits.numel() // 12
-            return self._occlusion(self._L.sdfr_hit_occlusion, n, (self._h, n, self._dev(hits, 12 * n, "hits", hits=True)), hits, bias, radius)
-        h = np.ascontiguousarray(hits)
-        if h.dtype != HIT_DTYPE:
-            h = np.ascontiguousarray(h.view(np.uint32).reshape(-1, 12)).view(HIT_DTYPE).reshape(-1)
-        return self._occlusion(self._L.sdfr_hit_occlusion, h.shape[0], (self._h, h.shape[0], h.ctypes.data_as(ctypes.c_void_p)), None, bias, radius)
+        n, (h,), like = self._inputs((hits, HIT_DTYPE, 12, "hits"))
+        out, po = self._answer(n, like, self._OCCLUSION, "occlusion")
+        self._check(self._L.sdfr_hit_occlusion(self._h, n, h, float(bias), float(radius), po, like is None))
+        return out
 
     # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
     def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None, occlusion=False, ao_radius=None,

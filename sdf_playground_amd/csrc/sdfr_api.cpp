@@ -9,6 +9,7 @@
 #include "sdfr_mesh.h"
 #include "sdfr_occlusion.h"
 #include "sdfr_query.h"
+#include "sdfr_query_plan.h"
 #include "sdfr_resolve.h"
 
 #include <chrono>
@@ -643,10 +644,6 @@ int sdfr_set_strip_split(sdfr_renderer *r, int priv_count, int priv_period)
 	});
 }
 
-// what every entry point that takes a frame size or an "is host memory" flag accepts
-static bool frame_size_ok(int width, int height) { return width >= 1 && height >= 1 && (int64_t)width * height <= (int64_t)1 << 30; }
-static bool is_flag(int v) { return v == 0 || v == 1; }
-
 // the arguments of render_impl, in the order their errors win; a private render without private strips renders nothing
 // and needs no scene
 static int check_render(sdfr_renderer *r, int width, int height, int rank, int world, const void *out, int format, RenderMode mode)
@@ -715,7 +712,7 @@ static int loaded_query_kernel(sdfr_renderer *r, int kind, const FrameU &U, Kern
 static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
 	KernelRef k;
-	const int rc = loaded_query_kernel(r, query_kernel_kind(q), U, k);
+	const int rc = loaded_query_kernel(r, query_kernel_of(q), U, k);
 	if (rc != SDFR_OK) return rc;
 	const hipError_t e = launch_query(k, U, q, stream);
 	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "query launch");
@@ -737,127 +734,109 @@ static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
 	if (st.buffer->bytes > k_query_stage_keep) st.buffer->release();
 	return SDFR_OK;
 }
-// What the entry points ask for.  kind = QUERY_*; a QUERY_MESH's positions and normals come as pos and dir.  reach: max_distance of
-// rays (0: the range), the reach of a mesh, the radius of an occlusion query.  want_surfaces: one of the surface entries, which needs
-// `surfaces` and takes hits or not.  The occlusion kinds: items pos + dir (points and normals) or hit_items, bias -> occlusion.
-struct QueryCall
+static_assert(QUERY_PLAN_OK == SDFR_OK && QUERY_PLAN_INVALID_ARGUMENT == SDFR_ERR_INVALID_ARGUMENT, "plan_query speaks in the library's statuses");
+// One query: what the entry point asks for (QueryRequest), planned by sdfr_query_plan.h and carried out here
+static int query_impl(sdfr_renderer *r, const QueryRequest &c)
 {
-	int kind;
-	int64_t n;
-	const float *pos, *dir;
-	const int32_t *pixels;
-	int width, height;
-	float reach;
-	float *distance, *normals;
-	sdfr_hit *hits;
-	sdfr_surface *surfaces;
-	bool want_surfaces;
-	int on_host;
-	const sdfr_hit *hit_items;
-	float bias;
-	sdfr_occlusion *occlusion;
-};
-static int query_impl(sdfr_renderer *r, const QueryCall &c)
-{
-	const int kind = c.kind;
-	const bool of_occlusion = kind == QUERY_OCCLUSION || kind == QUERY_HIT_OCCLUSION;
-	const bool of_pixels = kind == QUERY_PICK || kind == QUERY_FRAME, of_rays = kind == QUERY_RAYS || kind == QUERY_MESH || kind == QUERY_OCCLUSION;
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
-	if (c.n < 0 || c.n > (int64_t)INT32_MAX) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad item count");
-	if (!is_flag(c.on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
-	if (kind == QUERY_MESH || of_occlusion ? !(std::isfinite(c.reach) && c.reach > 0.f) : !std::isfinite(c.reach) || c.reach < 0.f)
-		return fail(r, SDFR_ERR_INVALID_ARGUMENT,
-			of_occlusion ? "radius must be finite and > 0" : kind == QUERY_MESH ? "reach must be finite and > 0" : "max_distance must be finite and >= 0");
-	if (of_occlusion && !(std::isfinite(c.bias) && c.bias >= 0.f)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bias must be finite and >= 0");
-	if (of_pixels && !frame_size_ok(c.width, c.height)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad frame size");
-	if (c.n == 0) return SDFR_OK;
-	if (kind == QUERY_FRAME && c.n != (int64_t)c.width * c.height) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "without a pixel list n must be width * height");
-	const bool inputs_ok = kind == QUERY_POINTS ? c.pos != nullptr
-		: of_rays                             ? c.pos && c.dir
-		: kind == QUERY_HIT_OCCLUSION         ? c.hit_items != nullptr
-		                                      : kind == QUERY_FRAME || c.pixels != nullptr;
-	const bool outputs_ok = kind == QUERY_POINTS ? c.distance != nullptr : of_occlusion ? c.occlusion != nullptr : c.want_surfaces ? c.surfaces != nullptr : c.hits != nullptr;
-	if (!inputs_ok || !outputs_ok) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
+	const QueryPlan p = plan_query(c, r->U.range);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	if (p.nothing_to_do) return SDFR_OK;
 	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
 	SDFR_HIP(hipSetDevice(r->device));
 	hipStream_t stream = r->lane.stream; // the handle's stream, or the lane of the frame submitted last (as sdfr_postprocess)
 	FrameU U = r->U;
-	int rc = of_pixels ? latch_into(r, U, c.width, c.height, stream) : latch_into(r, U, 1, 1, stream);
+	int rc = latch_into(r, U, p.width, p.height, stream);
 	if (rc != SDFR_OK) return rc;
 
-	QueryArgs q;
-	q.kind = kind;
-	q.n = (int)c.n;
-	q.pos = c.pos;
-	q.dir = c.dir;
-	q.pixels = c.pixels;
-	q.dist_max = c.reach == 0.f ? U.range : c.reach; // (a mesh's rays are marched to 2 * reach: query_mesh_ray)
-	q.reach = c.reach;
-	q.distance = c.distance;
-	q.normals = c.normals;
-	q.hits = reinterpret_cast<uint32_t *>(c.hits);
-	q.surfaces = reinterpret_cast<uint32_t *>(c.surfaces);
-	q.hit_items = reinterpret_cast<const uint32_t *>(c.hit_items);
-	q.occlusion = reinterpret_cast<uint32_t *>(c.occlusion);
-	q.bias = c.bias;
-	// the sizes of the arrays, in the order they are staged: inputs, then answers
-	const size_t N = (size_t)c.n;
-	const size_t in0 = kind == QUERY_FRAME ? 0 : kind == QUERY_PICK ? N * 8 : kind == QUERY_HIT_OCCLUSION ? N * sizeof(sdfr_hit) : N * 12, in1 = of_rays ? N * 12 : 0;
-	const size_t out0 = kind == QUERY_POINTS ? N * 4 : of_occlusion ? N * sizeof(sdfr_occlusion) : c.hits ? N * sizeof(sdfr_hit) : 0;
-	const size_t out1 = kind == QUERY_POINTS ? (c.normals ? N * 12 : 0) : c.surfaces ? N * sizeof(sdfr_surface) : 0;
-	Carving st({in0, in1, out0, out1});
+	QueryArgs q = p.q;
+	Carving st({p.bytes[0], p.bytes[1], p.bytes[2], p.bytes[3]});
 	if (c.on_host)
 	{
+		// the caller's arrays are host memory: each array of the kind that is there gets its piece of the staging buffer
+		const QueryKind &kind = k_query_kinds[q.kind];
 		SDFR_HIP(st.reserve(r->query)); // (host queries are synchronous: none is using the old one)
-		const void *first = kind == QUERY_PICK ? (const void *)c.pixels : kind == QUERY_HIT_OCCLUSION ? (const void *)c.hit_items : (const void *)c.pos;
-		if (in0) SDFR_HIP(hipMemcpyAsync(st.piece<void>(0), first, in0, hipMemcpyHostToDevice, stream));
-		if (in1) SDFR_HIP(hipMemcpyAsync(st.piece<void>(1), c.dir, in1, hipMemcpyHostToDevice, stream));
-		q.pos = of_pixels || kind == QUERY_HIT_OCCLUSION ? nullptr : st.piece<const float>(0);
-		q.hit_items = kind == QUERY_HIT_OCCLUSION ? st.piece<const uint32_t>(0) : nullptr;
-		q.pixels = kind == QUERY_PICK ? st.piece<const int32_t>(0) : nullptr;
-		q.dir = in1 ? st.piece<const float>(1) : nullptr;
-		q.distance = kind == QUERY_POINTS ? st.answer(2, c.distance, out0) : nullptr;
-		q.normals = kind == QUERY_POINTS && out1 ? st.answer(3, c.normals, out1) : nullptr;
-		q.hits = kind != QUERY_POINTS && !of_occlusion && out0 ? st.answer(2, reinterpret_cast<uint32_t *>(c.hits), out0) : nullptr;
-		q.occlusion = of_occlusion ? st.answer(2, reinterpret_cast<uint32_t *>(c.occlusion), out0) : nullptr;
-		q.surfaces = kind != QUERY_POINTS && out1 ? st.answer(3, reinterpret_cast<uint32_t *>(c.surfaces), out1) : nullptr;
+		for (int k = 0; k < 2; ++k)
+		{
+			if (!p.bytes[k]) continue;
+			SDFR_HIP(hipMemcpyAsync(st.piece<void>(k), query_slot_get(p.q, kind.in[k]), p.bytes[k], hipMemcpyHostToDevice, stream));
+			query_slot_set(q, kind.in[k], st.piece<void>(k));
+		}
+		for (int k = 2; k < 4; ++k)
+			if (p.bytes[k]) query_slot_set(q, kind.out[k - 2], st.answer(k, const_cast<void *>(query_slot_get(p.q, kind.out[k - 2])), p.bytes[k]));
 	}
 	rc = run_query(r, U, q, stream);
 	if (rc != SDFR_OK) return rc;
 	return c.on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
 }
+// a caller's records as the kernels' words
+static uint32_t *words(void *records) { return static_cast<uint32_t *>(records); }
+static const uint32_t *words(const void *records) { return static_cast<const uint32_t *>(records); }
 
 int sdfr_query_distance(sdfr_renderer *r, int64_t n, const float *points, float *distance, float *normals, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_POINTS, n, points, nullptr, nullptr, 0, 0, 0.f, distance, normals, nullptr, nullptr, false, on_host}); });
+	return guarded(r, [&]() -> int {
+		QueryRequest c = query_request(QUERY_POINTS, n, on_host);
+		c.q.pos = points;
+		c.q.distance = distance;
+		c.q.normals = normals;
+		return query_impl(r, c);
+	});
+}
+
+// rays -> hits, or with want_surfaces surfaces and perhaps hits
+static QueryRequest ray_request(int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, sdfr_surface *surfaces, bool want_surfaces, int on_host)
+{
+	QueryRequest c = query_request(QUERY_RAYS, n, on_host);
+	c.q.pos = origins;
+	c.q.dir = dirs;
+	c.q.reach = max_distance;
+	c.q.hits = words(hits);
+	c.q.surfaces = words(surfaces);
+	c.want_surfaces = want_surfaces;
+	return c;
+}
+// pixels of a width x height frame, or without a list every pixel of it, likewise
+static QueryRequest pick_request(int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, sdfr_surface *surfaces, bool want_surfaces, int on_host)
+{
+	QueryRequest c = query_request(pixels_xy || !want_surfaces ? QUERY_PICK : QUERY_FRAME, n, on_host);
+	c.width = width;
+	c.height = height;
+	c.q.pixels = pixels_xy;
+	c.q.hits = words(hits);
+	c.q.surfaces = words(surfaces);
+	c.want_surfaces = want_surfaces;
+	return c;
 }
 
 int sdfr_query_rays(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_RAYS, n, origins, dirs, nullptr, 0, 0, max_distance, nullptr, nullptr, hits, nullptr, false, on_host}); });
+	return guarded(r, [&]() -> int { return query_impl(r, ray_request(n, origins, dirs, max_distance, hits, nullptr, false, on_host)); });
 }
 
 int sdfr_pick(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_PICK, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, nullptr, false, on_host}); });
+	return guarded(r, [&]() -> int { return query_impl(r, pick_request(width, height, n, pixels_xy, hits, nullptr, false, on_host)); });
 }
 
 int sdfr_query_ray_surfaces(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, sdfr_surface *surfaces,
 	int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_RAYS, n, origins, dirs, nullptr, 0, 0, max_distance, nullptr, nullptr, hits, surfaces, true, on_host}); });
+	return guarded(r, [&]() -> int { return query_impl(r, ray_request(n, origins, dirs, max_distance, hits, surfaces, true, on_host)); });
 }
 
 int sdfr_pick_surfaces(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, sdfr_surface *surfaces, int on_host)
 {
-	return guarded(r, [&]() -> int {
-		return query_impl(r, {pixels_xy ? QUERY_PICK : QUERY_FRAME, n, nullptr, nullptr, pixels_xy, width, height, 0.f, nullptr, nullptr, hits, surfaces, true, on_host});
-	});
+	return guarded(r, [&]() -> int { return query_impl(r, pick_request(width, height, n, pixels_xy, hits, surfaces, true, on_host)); });
 }
 
 int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits, sdfr_surface *surfaces, int on_host)
 {
-	return guarded(r, [&]() -> int { return query_impl(r, {QUERY_MESH, n, positions, normals, nullptr, 0, 0, reach, nullptr, nullptr, hits, surfaces, true, on_host}); });
+	return guarded(r, [&]() -> int {
+		QueryRequest c = ray_request(n, positions, normals, reach, hits, surfaces, true, on_host);
+		c.q.kind = QUERY_MESH;
+		return query_impl(r, c);
+	});
 }
 
 int sdfr_occlusion_directions(float *out)
@@ -870,14 +849,25 @@ int sdfr_occlusion_directions(float *out)
 int sdfr_query_occlusion(sdfr_renderer *r, int64_t n, const float *points, const float *normals, float bias, float radius, sdfr_occlusion *out, int on_host)
 {
 	return guarded(r, [&]() -> int {
-		return query_impl(r, {QUERY_OCCLUSION, n, points, normals, nullptr, 0, 0, radius, nullptr, nullptr, nullptr, nullptr, false, on_host, nullptr, bias, out});
+		QueryRequest c = query_request(QUERY_OCCLUSION, n, on_host);
+		c.q.pos = points;
+		c.q.dir = normals;
+		c.q.reach = radius;
+		c.q.bias = bias;
+		c.q.occlusion = words(out);
+		return query_impl(r, c);
 	});
 }
 
 int sdfr_hit_occlusion(sdfr_renderer *r, int64_t n, const sdfr_hit *hits, float bias, float radius, sdfr_occlusion *out, int on_host)
 {
 	return guarded(r, [&]() -> int {
-		return query_impl(r, {QUERY_HIT_OCCLUSION, n, nullptr, nullptr, nullptr, 0, 0, radius, nullptr, nullptr, nullptr, nullptr, false, on_host, hits, bias, out});
+		QueryRequest c = query_request(QUERY_HIT_OCCLUSION, n, on_host);
+		c.q.hit_items = words(hits);
+		c.q.reach = radius;
+		c.q.bias = bias;
+		c.q.occlusion = words(out);
+		return query_impl(r, c);
 	});
 }
 

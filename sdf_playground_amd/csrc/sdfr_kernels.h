@@ -5,6 +5,7 @@
 
 #include "sdfr_frame.h"
 #include "sdfr_launch_plan.h"
+#include "sdfr_query_args.h"
 
 namespace sdfr {
 
@@ -47,8 +48,7 @@ struct KernelRef
 // one launch of `blocks` blocks of `threads` threads on `stream`, the kernel's parameters by address
 hipError_t launch_kernel(const KernelRef &k, uint32_t blocks, uint32_t threads, void **args, hipStream_t stream);
 // A scene's query kernels [kind][DBG]: a built-in scene's query unit exports them (sdfr_query_scene.hip), a run-time scene's
-// query module is looked up into the same table (jit_query_kernels, sdfr_jit.h)
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_KINDS = 5 }; // (rays: picks too)
+// query module is looked up into the same table (jit_query_kernels, sdfr_jit.h).  kind: QUERY_KERNEL_* (sdfr_query_args.h)
 struct QueryKernels
 {
 	KernelRef k[QUERY_KERNEL_KINDS][2];
@@ -63,12 +63,10 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 	RenderTotals *totals, const WavefrontWorkspace &ws, hipStream_t stream, hipEvent_t *march_events, hipEvent_t *shade_events,
 	int *n_rounds_out);
 
-// one query (sdfr_query.h) by a scene's kernel of q's kind (query_kernel_kind) for U: q.n > 0 items, every pointer device memory
-struct QueryArgs;
-int query_kernel_kind(const QueryArgs &q); // QUERY_KERNEL_*: points; occlusion; surfaces where q.surfaces is given; else rays or picks
+// one query by a scene's kernel of q's kind (sdfr_query_plan.h: query_kernel_of) for U, in the launches that header plans: q.n > 0
+// items, every pointer device memory
 hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream);
-// the distance query over a lattice (sdfr_query.h: LatticeArgs) by a scene's lattice kernel for U
-struct LatticeArgs;
+// the distance query over a lattice (LatticeArgs) by a scene's lattice kernel for U
 hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const LatticeArgs &g, hipStream_t stream);
 uint32_t query_lattice_blocks(const LatticeArgs &g); // blocks of one wave that cover the lattice in the mapping g.rows selects
 

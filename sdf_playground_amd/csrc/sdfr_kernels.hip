@@ -30,6 +30,7 @@
 #include "sdfr_perpixel.h"
 #include "sdfr_pixel_kernel.h"
 #include "sdfr_query.h"
+#include "sdfr_query_plan.h"
 
 namespace sdfr {
 
@@ -465,40 +466,20 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 }
 
 // ---- queries (kernel bodies: sdfr_query_kernel.h) ----
-int query_kernel_kind(const QueryArgs &q)
-{
-	if (q.kind == QUERY_OCCLUSION || q.kind == QUERY_HIT_OCCLUSION) return QUERY_KERNEL_OCCLUSION;
-	return q.kind == QUERY_POINTS ? QUERY_KERNEL_POINTS : q.surfaces ? QUERY_KERNEL_SURFACES : QUERY_KERNEL_RAYS;
-}
-
+static_assert(QUERY_BLOCK_ITEMS == SDFR_PIXEL_BLOCK, "the query kernels are one wave per block");
 hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
 	QueryKernelArgs a;
 	a.U = U;
-	a.q = q;
 	void *args[] = {&a};
-	if (q.kind == QUERY_OCCLUSION || q.kind == QUERY_HIT_OCCLUSION)
+	for (uint32_t i = 0, n = query_launch_count(q); i < n; ++i)
 	{
-		// a block per item (query_occlusion_kernel).  A launch's threads must number below 2^32, so more than 2^25 items go in several
-		// launches, each with its arrays advanced to its first item (records of 16 bytes: the output's alignment class stays)
-		const uint32_t per_launch = 1u << 25;
-		for (uint32_t first = 0; first < (uint32_t)q.n; first += per_launch)
-		{
-			const uint32_t count = (uint32_t)q.n - first < per_launch ? (uint32_t)q.n - first : per_launch;
-			a.q.n = (int)count;
-			a.q.pos = q.pos ? q.pos + (size_t)3 * first : nullptr;
-			a.q.dir = q.dir ? q.dir + (size_t)3 * first : nullptr;
-			a.q.hit_items = q.hit_items ? q.hit_items + (size_t)QUERY_HIT_WORDS * first : nullptr;
-			a.q.occlusion = q.occlusion + (size_t)QUERY_OCCLUSION_WORDS * first;
-			const hipError_t e = launch_kernel(k, count, SDFR_PIXEL_BLOCK, args, stream);
-			if (e != hipSuccess) return e;
-		}
-		return hipSuccess;
+		const QueryLaunch l = query_launch(q, U.width, U.height, i);
+		a.q = query_launch_args(q, l);
+		const hipError_t e = launch_kernel(k, l.blocks, QUERY_BLOCK_ITEMS, args, stream);
+		if (e != hipSuccess) return e;
 	}
-	// a block per SDFR_PIXEL_BLOCK items; of a whole frame, a block per 8 x 8 tile of pixels (query_surfaces_kernel)
-	uint32_t blocks = ((uint32_t)q.n + SDFR_PIXEL_BLOCK - 1u) / SDFR_PIXEL_BLOCK;
-	if (q.kind == QUERY_FRAME) blocks = (((uint32_t)U.width + 7u) >> 3) * (((uint32_t)U.height + 7u) >> 3);
-	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
+	return hipSuccess;
 }
 
 uint32_t query_lattice_blocks(const LatticeArgs &g)

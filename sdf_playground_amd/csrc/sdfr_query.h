@@ -5,34 +5,12 @@
 // are in sdfr_query_kernel.h, and tests/cpp/query_host.cpp compiles these functions for the CPU to compare them with the oracle.
 #pragma once
 #include "sdfr_pixel.h"
+#include "sdfr_query_args.h"
 
 namespace sdfr {
 
-// One query launch (sdfr_kernels.h: launch_query).  Points: `pos` [n][3] -> `distance` [n], `normals` [n][3] or null.  Rays:
-// `pos` = origins [n][3], `dir` [n][3] -> `hits` [n][12].  Picks: `pixels` [n][2] of a width x height frame -> `hits` [n][12].
-// With `surfaces` [n][32] (sdfr_surface.h) the surface kernel answers, `hits` may be null, and two more kinds of items exist.
-// Frame: every pixel of the width x height frame, item y * width + x, n = width * height, nothing read.  Mesh: `pos` = vertex
-// positions, `dir` = vertex normals, the ray towards each vertex from `reach` outside it (query_mesh_ray).
-// The occlusion kernel (sdfr_occlusion.h) answers the last two kinds into `occlusion` [n][4]: items that are `pos` = points and
-// `dir` = normals, or the pos and normal of the hit records `hit_items` [n][12]; `dist_max` is the radius.
-enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2, QUERY_FRAME = 3, QUERY_MESH = 4, QUERY_OCCLUSION = 5, QUERY_HIT_OCCLUSION = 6 };
-struct QueryArgs
-{
-	int kind;  // QUERY_*
-	int n;
-	const float *pos, *dir;
-	const int32_t *pixels;
-	float dist_max; // rays: march_ray's dist_max (picks and frames: the range; meshes: 2 * reach)
-	float reach;    // meshes
-	float *distance, *normals;
-	uint32_t *hits;     // 12 words per item: the layout of sdfr_hit
-	uint32_t *surfaces; // 32 words per item: the layout of sdfr_surface
-	// the occlusion kinds (appended: the other kernels' argument offsets stay)
-	const uint32_t *hit_items; // 12 words per item, read
-	uint32_t *occlusion;       // 4 words per item: the layout of sdfr_occlusion
-	float bias;
-};
-enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32, QUERY_OCCLUSION_WORDS = 4 };
+// QueryArgs, what one query launch reads and writes: sdfr_query_args.h; which of its arrays each kind of item takes, and how the
+// kinds are launched: the table of sdfr_query_plan.h
 // what a query kernel takes: one argument, as the pixel kernels (PixelKernelArgs)
 struct QueryKernelArgs
 {
@@ -40,17 +18,7 @@ struct QueryKernelArgs
 	QueryArgs q;
 };
 
-// One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
-// computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
-// out[i + px * (j + py * k)].  px * py * pz <= 2^30.
-struct LatticeArgs
-{
-	float origin[3];
-	float cell;
-	int32_t px, py, pz; // lattice points per axis
-	int32_t rows;       // 0: a wave owns a 4 x 4 x 4 brick of points; 1: 64 consecutive points of a row (the A/B of DESIGN.md 4.6)
-	float *out;
-};
+// ... and a lattice kernel (LatticeArgs: sdfr_query_args.h)
 struct LatticeKernelArgs
 {
 	FrameU U;

@@ -1,0 +1,53 @@
+// sdfr_query_args.h -- what the host hands a query kernel, as plain structs: included by the device code (sdfr_query.h) and by the host
+// code that plans a query (sdfr_query_plan.h), which includes no HIP header.  The kernels read these as kernel arguments: the layout
+// below is pinned.
+#pragma once
+#if !defined(__HIPCC_RTC__) // hiprtc has no system headers: a run-time scene's query module gets the integer types from sdfr_math.h
+#include <stdint.h>
+#endif
+
+namespace sdfr {
+
+// One query launch.  Which members a kind reads and writes, at how many bytes per item, is the table of sdfr_query_plan.h
+// (k_query_kinds); every other pointer is null, and the kernels branch on `normals`, `hits` and `surfaces`.
+enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2, QUERY_FRAME = 3, QUERY_MESH = 4, QUERY_OCCLUSION = 5, QUERY_HIT_OCCLUSION = 6, QUERY_KINDS = 7 };
+struct QueryArgs
+{
+	int kind;  // QUERY_*
+	int n;
+	const float *pos, *dir;
+	const int32_t *pixels;
+	float dist_max; // rays: march_ray's dist_max (picks and frames: the range; meshes: 2 * reach; occlusion: the radius)
+	float reach;    // meshes
+	float *distance, *normals;
+	uint32_t *hits;     // 12 words per item: the layout of sdfr_hit
+	uint32_t *surfaces; // 32 words per item: the layout of sdfr_surface
+	// the occlusion kinds (appended: the other kernels' argument offsets stay)
+	const uint32_t *hit_items; // 12 words per item, read
+	uint32_t *occlusion;       // 4 words per item: the layout of sdfr_occlusion
+	float bias;
+};
+enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32, QUERY_OCCLUSION_WORDS = 4 };
+static_assert(sizeof(QueryArgs) == 96, "QueryArgs is a kernel argument");
+static_assert(__builtin_offsetof(QueryArgs, kind) == 0 && __builtin_offsetof(QueryArgs, n) == 4 && __builtin_offsetof(QueryArgs, pos) == 8 && __builtin_offsetof(QueryArgs, dir) == 16, "");
+static_assert(__builtin_offsetof(QueryArgs, pixels) == 24 && __builtin_offsetof(QueryArgs, dist_max) == 32 && __builtin_offsetof(QueryArgs, reach) == 36, "");
+static_assert(__builtin_offsetof(QueryArgs, distance) == 40 && __builtin_offsetof(QueryArgs, normals) == 48 && __builtin_offsetof(QueryArgs, hits) == 56, "");
+static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offsetof(QueryArgs, hit_items) == 72 && __builtin_offsetof(QueryArgs, occlusion) == 80, "");
+static_assert(__builtin_offsetof(QueryArgs, bias) == 88, "");
+
+// A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_KINDS = 5 };
+
+// One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
+// computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
+// out[i + px * (j + py * k)].  px * py * pz <= 2^30.
+struct LatticeArgs
+{
+	float origin[3];
+	float cell;
+	int32_t px, py, pz; // lattice points per axis
+	int32_t rows;       // 0: a wave owns a 4 x 4 x 4 brick of points; 1: 64 consecutive points of a row (the A/B of DESIGN.md 4.6)
+	float *out;
+};
+
+} // namespace sdfr

@@ -4,7 +4,6 @@ tests ask about and a scene whose answer is known without either.  Frames, ray s
 Test infrastructure: the product never imports this."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -48,64 +47,22 @@ float3 map_background(float3 dir, uint iter_count)
 }
 """
 
-_oracle = None
-
-
 def oracle_lib():
-    global _oracle
-    if _oracle is None:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        so = os.path.join(qu.BUILD, "libocclusion_oracle.so")
-        cpp = os.path.join(qu.HERE, "cpp")
-        deps = [os.path.join(cpp, "occlusion_oracle.cpp"), os.path.join(cpp, "query_oracle.cpp"), os.path.join(qu.CSRC, "sdfr_occlusion_dirs.h")]
-        deps += [os.path.join(qu.ORACLE, f) for f in os.listdir(qu.ORACLE) if f.endswith(".h")]
-        if qu._stale(so, deps):
-            subprocess.run(["g++"] + qu.FLAGS + ["-I" + qu.ORACLE, "-I" + qu.CSRC, "-shared", "-o", so + ".tmp", deps[0]], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
-        assert L.qo_frame_size() == ctypes.sizeof(qu.po.OrcFrame)
-        vp, cf = ctypes.c_void_p, ctypes.c_float
-        L.oo_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, cf, cf, vp]
-        L.oo_hits.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, cf, cf, vp]
-        L.oo_directions.argtypes = [vp]
-        _oracle = L
-    return _oracle
-
-
-_hosts = {}
+    L = qu.build_oracle_lib("occlusion_oracle", ["occlusion_oracle.cpp", "query_oracle.cpp"], (qu.ORACLE, qu.CSRC), [os.path.join(qu.CSRC, "sdfr_occlusion_dirs.h")])
+    vp, cf = ctypes.c_void_p, ctypes.c_float
+    L.oo_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, cf, cf, vp]
+    L.oo_hits.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, cf, cf, vp]
+    L.oo_directions.argtypes = [vp]
+    return L
 
 
 def host_lib(scene, text=None):
-    """The library's occlusion functions for the CPU: one build for the built-in scenes, one per run-time scene (as query_util.host_lib);
-    `text`: the dialect text of a run-time scene that is no file"""
-    key = scene if scene in qu.HLSL or text is not None else "builtin"
-    if key not in _hosts:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        src = os.path.join(qu.HERE, "cpp", "occlusion_host.cpp")
-        deps = [src] + [os.path.join(qu.CSRC, f) for f in os.listdir(qu.CSRC) if f.endswith((".h", ".inl"))]
-        defs = []
-        if key != "builtin":
-            import sdf_playground_amd as sp
-
-            if text is None:
-                text = open(os.path.join(qu.SCENES_DIR, scene + ".hlsl")).read()
-            gen = os.path.join(qu.BUILD, scene + ".scene.inc")
-            body = "".join("#define VAR_%s(...) (U.scene_var[%d])\n" % (n, k) for k, n in enumerate(qu._var_slots(text))) + sp.translate_scene_hlsl(text)
-            if not os.path.exists(gen) or open(gen).read() != body:
-                with open(gen, "w") as f:
-                    f.write(body)
-            deps.append(gen)
-            defs = ['-DSDFR_HLSL_SCENE_FILE="%s"' % gen]
-        so = os.path.join(qu.BUILD, "libocclusion_host_%s.so" % key)
-        if qu._stale(so, deps):
-            subprocess.run(["g++"] + qu.FLAGS + ["-I" + qu.CSRC] + defs + ["-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
-        vp, cf = ctypes.c_void_p, ctypes.c_float
-        L.oh_occlusion.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp, cf, cf, vp]
-        L.oh_directions.argtypes = [vp]
-        _hosts[key] = L
-    return _hosts[key]
+    """The library's occlusion functions for the CPU; `text`: the dialect text of a run-time scene that is no file"""
+    L = qu.build_host_lib("occlusion_host", "occlusion_host.cpp", scene, text)
+    vp, cf = ctypes.c_void_p, ctypes.c_float
+    L.oh_occlusion.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp, cf, cf, vp]
+    L.oh_directions.argtypes = [vp]
+    return L
 
 
 def _f3(a):

@@ -40,30 +40,22 @@ def _stale(out, deps):
     return not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
-_oracle = None
+_libs = {}
 
 
-def oracle_lib():
-    global _oracle
-    if _oracle is None:
+def build_oracle_lib(name, sources, includes=(ORACLE,), more_deps=()):
+    """lib<name>.so of the oracle's definitions: sources[0] (tests/cpp) compiled with `includes`; stale when a source, an oracle header or
+    one of more_deps is newer"""
+    if name not in _libs:
         os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libquery_oracle.so")
-        src = os.path.join(HERE, "cpp", "query_oracle.cpp")
-        deps = [src] + [os.path.join(ORACLE, f) for f in os.listdir(ORACLE) if f.endswith(".h")]
+        so = os.path.join(BUILD, "lib%s.so" % name)
+        deps = [os.path.join(HERE, "cpp", f) for f in sources] + list(more_deps) + [os.path.join(ORACLE, f) for f in os.listdir(ORACLE) if f.endswith(".h")]
         if _stale(so, deps):
-            subprocess.run(["g++"] + FLAGS + ["-I" + ORACLE, "-shared", "-o", so + ".tmp", src], check=True)
+            subprocess.run(["g++"] + FLAGS + ["-I" + d for d in includes] + ["-shared", "-o", so + ".tmp", deps[0]], check=True)
             os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
-        assert L.qo_frame_size() == ctypes.sizeof(po.OrcFrame)
-        vp = ctypes.c_void_p
-        L.qo_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
-        L.qo_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp]
-        L.qo_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp]
-        _oracle = L
-    return _oracle
-
-
-_hosts = {}
+        _libs[name] = ctypes.CDLL(so)
+        assert _libs[name].qo_frame_size() == ctypes.sizeof(po.OrcFrame)
+    return _libs[name]
 
 
 def _var_slots(text):
@@ -74,19 +66,21 @@ def _var_slots(text):
     return slots
 
 
-def host_lib(scene):
-    """The library's query functions for the CPU: one build for the built-in scenes, one per run-time scene (HLSL, translated by
-    the library as sdfr_load_scene_hlsl translates it)."""
-    key = scene if scene in HLSL else "builtin"
-    if key not in _hosts:
+def build_host_lib(name, source, scene, text=None):
+    """lib<name>_<key>.so of the library's own functions for the CPU, from tests/cpp/<source> over csrc: one build ("builtin") for the
+    built-in scenes, one per run-time scene -- a scene of HLSL, or any name with its dialect `text` -- translated by the library as
+    sdfr_load_scene_hlsl translates it"""
+    key = scene if scene in HLSL or text is not None else "builtin"
+    if (name, key) not in _libs:
         os.makedirs(BUILD, exist_ok=True)
-        src = os.path.join(HERE, "cpp", "query_host.cpp")
+        src = os.path.join(HERE, "cpp", source)
         deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inl"))]
         defs = []
         if key != "builtin":
             import sdf_playground_amd as sp
 
-            text = open(os.path.join(SCENES_DIR, scene + ".hlsl")).read()
+            if text is None:
+                text = open(os.path.join(SCENES_DIR, scene + ".hlsl")).read()
             gen = os.path.join(BUILD, scene + ".scene.inc")
             body = "".join("#define VAR_%s(...) (U.scene_var[%d])\n" % (n, k) for k, n in enumerate(_var_slots(text))) + sp.translate_scene_hlsl(text)
             if not os.path.exists(gen) or open(gen).read() != body:
@@ -94,17 +88,31 @@ def host_lib(scene):
                     f.write(body)
             deps.append(gen)
             defs = ['-DSDFR_HLSL_SCENE_FILE="%s"' % gen]
-        so = os.path.join(BUILD, "libquery_host_%s.so" % key)
+        so = os.path.join(BUILD, "lib%s_%s.so" % (name, key))
         if _stale(so, deps):
             subprocess.run(["g++"] + FLAGS + ["-I" + CSRC] + defs + ["-shared", "-o", so + ".tmp", src], check=True)
             os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
-        vp = ctypes.c_void_p
-        L.qh_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
-        L.qh_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp]
-        L.qh_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
-        _hosts[key] = L
-    return _hosts[key]
+        _libs[name, key] = ctypes.CDLL(so)
+    return _libs[name, key]
+
+
+def oracle_lib():
+    L = build_oracle_lib("query_oracle", ["query_oracle.cpp"])
+    vp = ctypes.c_void_p
+    L.qo_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
+    L.qo_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp]
+    L.qo_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp]
+    return L
+
+
+def host_lib(scene):
+    """The library's query functions for the CPU"""
+    L = build_host_lib("query_host", "query_host.cpp", scene)
+    vp = ctypes.c_void_p
+    L.qh_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
+    L.qh_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp]
+    L.qh_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    return L
 
 
 # ---- frames ---------------------------------------------------------------------------------------------------------------------

@@ -3,8 +3,6 @@
 rays towards mesh vertices.  Frames, samples and the bit comparison are query_util's.  Test infrastructure: the product never
 imports this."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -13,61 +11,21 @@ import query_util as qu
 HIT_WORDS = qu.HIT_WORDS
 SURFACE_WORDS = 32
 
-_oracle = None
-
-
 def oracle_lib():
-    global _oracle
-    if _oracle is None:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        so = os.path.join(qu.BUILD, "libsurface_oracle.so")
-        cpp = os.path.join(qu.HERE, "cpp")
-        deps = [os.path.join(cpp, "surface_oracle.cpp"), os.path.join(cpp, "query_oracle.cpp")]
-        deps += [os.path.join(qu.ORACLE, f) for f in os.listdir(qu.ORACLE) if f.endswith(".h")]
-        if qu._stale(so, deps):
-            subprocess.run(["g++"] + qu.FLAGS + ["-I" + qu.ORACLE, "-shared", "-o", so + ".tmp", deps[0]], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
-        assert L.qo_frame_size() == ctypes.sizeof(qu.po.OrcFrame)
-        vp = ctypes.c_void_p
-        L.so_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp, vp]
-        L.so_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
-        _oracle = L
-    return _oracle
-
-
-_hosts = {}
+    L = qu.build_oracle_lib("surface_oracle", ["surface_oracle.cpp", "query_oracle.cpp"])
+    vp = ctypes.c_void_p
+    L.so_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp, vp]
+    L.so_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
+    return L
 
 
 def host_lib(scene):
-    """The library's surface functions for the CPU: one build for the built-in scenes, one per run-time scene (as query_util.host_lib)."""
-    key = scene if scene in qu.HLSL else "builtin"
-    if key not in _hosts:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        src = os.path.join(qu.HERE, "cpp", "surface_host.cpp")
-        deps = [src] + [os.path.join(qu.CSRC, f) for f in os.listdir(qu.CSRC) if f.endswith((".h", ".inl"))]
-        defs = []
-        if key != "builtin":
-            import sdf_playground_amd as sp
-
-            text = open(os.path.join(qu.SCENES_DIR, scene + ".hlsl")).read()
-            gen = os.path.join(qu.BUILD, scene + ".scene.inc")
-            body = "".join("#define VAR_%s(...) (U.scene_var[%d])\n" % (n, k) for k, n in enumerate(qu._var_slots(text))) + sp.translate_scene_hlsl(text)
-            if not os.path.exists(gen) or open(gen).read() != body:
-                with open(gen, "w") as f:
-                    f.write(body)
-            deps.append(gen)
-            defs = ['-DSDFR_HLSL_SCENE_FILE="%s"' % gen]
-        so = os.path.join(qu.BUILD, "libsurface_host_%s.so" % key)
-        if qu._stale(so, deps):
-            subprocess.run(["g++"] + qu.FLAGS + ["-I" + qu.CSRC] + defs + ["-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
-        vp = ctypes.c_void_p
-        L.sh_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float, vp, vp]
-        L.sh_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
-        _hosts[key] = L
-    return _hosts[key]
+    """The library's surface functions for the CPU"""
+    L = qu.build_host_lib("surface_host", "surface_host.cpp", scene)
+    vp = ctypes.c_void_p
+    L.sh_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_float, vp, vp]
+    L.sh_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+    return L
 
 
 def _out(n):
