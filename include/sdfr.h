@@ -413,6 +413,93 @@ int sdfr_pick_surfaces(sdfr_renderer *r, int width, int height, int64_t n, const
 int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits /* or NULL */,
 	sdfr_surface *surfaces, int on_host);
 
+/* ---- how the scene's lights fall on a ray's first hit (DESIGN.md "Lighting queries"): the driver's light loop (:505-593) and the life of
+ *      the shadow rays it starts (:598-632), restated as records.  An item is a ray as in the surface queries -- a caller's ray, a
+ *      pixel's primary ray with its ray offsets, a mesh vertex's ray --, marched as sdfr_query_rays / sdfr_pick march it and continued
+ *      on a hit exactly as sdfr_surface is: normal, map_material, the marble extension, new_normal, the material switch.  It is treated
+ *      as a PRIMARY ray: depth 0, contribution (1, 1, 1), inside_sign +1.  Nothing but shadow rays is spawned: no reflection, no
+ *      refraction, no continuation through a see-through hit, no background.
+ *      If the driver's use_light is false (sdfr_surface.flags without SDFR_SURFACE_LIT), `own` is the driver's colour after the switch
+ *      (sdfr_surface.unlit) and no light is looked at.  Otherwise, in the driver's order of operations, all fp32:
+ *      the light table preloaded unused and zero, ambient_lighting_factor 0.075, the scene's map_light, the extension lights;
+ *      view_dir = the ray's direction; shadow_move_distance = max(shadow_eps, normal_sample_dist) + max(0, -scene_distance);
+ *      scene_pos = mad(new_normal, shadow_move_distance, pos).  For each slot i < limits.light_count that is used, in slot order:
+ *      lighting_dir, distance_to_trace and falloff_factor (directional: pos.xyz / (length + dist_eps), limits.range, 1; point:
+ *      scene_pos - pos.xyz normalised by its length, that length - extend, pow(0.1, falloff)); light_color = color * falloff_factor;
+ *      color += diffuse_color * light_color * ambient_lighting_factor; light_dot = saturate(dot(-new_normal, lighting_dir));
+ *      light_influenced_color = 0 + diffuse_color * light_color * light_dot, then + specular_color.xyz * light_color * specular_factor
+ *      with half_vec = -normalize(view_dir + lighting_dir), specular_factor = pow(saturate(dot(new_normal, half_vec)), specular_color.w).
+ *      A shadow chain is started iff 0 + 2 < max_cost && light_dot > 0.  The driver's ray queue (limits.ray_count) and bounce budget
+ *      (limits.bounce_count) are NOT looked at: the query answers as a pixel whose queue never fills and whose bounces never run out.
+ *      Chain: pos = scene_pos, dir = -lighting_dir, range = distance_to_trace, C = light_influenced_color * (1, 1, 1) *
+ *      saturate(alpha), depth = 2, has_transparent = false, last_transparent_pos = 0.  Each segment is the driver's turn for a shadow
+ *      ray (:299-353): march_ray with is_shadow_pass = true, the chain's has_transparent / last_transparent_pos, dist_max = range, the
+ *      item's ray offsets, camera_distance from 0.  A miss: the chain ESCAPES and delivers C.  A hit: the normal (map_normal with
+ *      dir.w = 0, else the forward differences against scene_distance) and map_material (+ the marble extension's line); the material
+ *      switch is not applied.  If diffuse.w < 1 && depth + 2 < max_cost (the hit's own max_cost): C = ((1 - diffuse.w) * diffuse.xyz)
+ *      * C, pos = the hit position, range = range - camera_distance, has_transparent = true, last_transparent_pos = pos, depth += 2,
+ *      next segment.  Otherwise the chain is BLOCKED and delivers 0.  A chain is also blocked after its 64th segment hits (the driver
+ *      has no such bound; its 8-slot queue and bounce_count end a chain far earlier).
+ *      After the loop: color = (color + emissive) * saturate(alpha): that is `own`.
+ *      `lit` is the renderer's pixel (sdfr_render, RGBA32F, no supersampling; rgb, bit for bit) when all of these hold: the primary
+ *      hit spawns nothing else -- no reflection (reflection 0, or max_cost <= 3), no refraction (refraction 0, or max_cost <= 4) and no
+ *      continuation through a see-through hit (alpha >= 1, or max_cost <= 2; lit or unlit material alike) --; every started chain has
+ *      exactly one segment, so that the driver pops the shadow rays in slot order; and 1 + popcount(traced_mask) <= limits.bounce_count
+ *      and <= limits.ray_count.  Otherwise `lit` is the stated sum and not a pixel.
+ *      With step shortcuts on only misses end early, so every record is the same with them on or off.
+ *      The entries are queries in every respect listed above: on_host, what is latched, the stream, no effect on stats, timings or
+ *      the row order, n = 0, the argument errors.  `lighting` is required; `hits` (NULL: not wanted) gets what sdfr_query_rays /
+ *      sdfr_pick give for the same items, bit for bit; `lights` (NULL: not wanted) gets eight samples per item, [n][8]. ------------- */
+typedef struct sdfr_lighting
+{
+	int32_t valid;          /* 1 hit, 0 miss, -1 invalid item (a pixel outside the frame); unless 1, every other word is 0 */
+	uint32_t used_mask;     /* bit i: slot i < limits.light_count is used */
+	uint32_t traced_mask;   /* bit i: a shadow chain was started for it */
+	uint32_t visible_mask;  /* bit i: that chain escaped */
+	float own[3];           /* the driver's `color` as defined above: the ambient lines and emissive times saturate(alpha), or the unlit colour */
+	float ambient_factor;   /* ambient_lighting_factor after map_light; 0 for an unlit material */
+	float direct[3];        /* 0, then + delivered of each escaped chain in slot order, fp32 */
+	uint32_t segments;      /* shadow segments marched, all chains */
+	float lit[3];           /* (0 + own), then + delivered of each escaped chain in slot order, fp32 */
+	float reserved;         /* 0 */
+} sdfr_lighting;            /* 64 bytes: four 16-byte stores per item (device arrays aligned to 16 bytes; any other alignment: word stores) */
+
+typedef struct sdfr_light_sample
+{
+	int32_t state;          /* SDFR_LIGHT_UNUSED (also: slot >= limits.light_count, an unlit material, a miss -- then every word is 0),
+	                           SDFR_LIGHT_NO_CHAIN used but no chain started, SDFR_LIGHT_BLOCKED, SDFR_LIGHT_ESCAPED */
+	uint32_t flags;         /* SDFR_LIGHT_DIRECTIONAL */
+	uint32_t segments;      /* of this slot's chain */
+	uint32_t reserved0;     /* 0 */
+	float dir[3];           /* lighting_dir */
+	float distance;         /* distance_to_trace */
+	float color[3];         /* light_color, after the falloff */
+	float light_dot;
+	float influenced[3];    /* light_influenced_color, unshadowed */
+	float specular_factor;
+	float delivered[3];     /* what the chain delivered: C of an escaped chain, else 0 */
+	float reserved1;        /* 0 */
+} sdfr_light_sample;        /* 80 bytes, eight per item: five 16-byte stores each (word stores into an array not aligned to 16 bytes) */
+#define SDFR_LIGHT_DIRECTIONAL 1u
+#define SDFR_LIGHT_UNUSED 0
+#define SDFR_LIGHT_NO_CHAIN 1
+#define SDFR_LIGHT_BLOCKED 2
+#define SDFR_LIGHT_ESCAPED 3
+
+/* sdfr_query_rays, and the lighting at each hit. */
+int sdfr_query_ray_lighting(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits /* or NULL */,
+	sdfr_lighting *lighting, sdfr_light_sample *lights /* or NULL */, int on_host);
+
+/* sdfr_pick, and the lighting under each pixel.  pixels_xy = NULL: the whole frame as in sdfr_pick_surfaces -- item y * width + x is
+ * pixel (x, y), n must be width * height, a wave takes an 8 x 8 tile of pixels. */
+int sdfr_pick_lighting(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy /* or NULL */, sdfr_hit *hits /* or NULL */,
+	sdfr_lighting *lighting, sdfr_light_sample *lights /* or NULL */, int on_host);
+
+/* The lighting at the vertices of a mesh: each vertex is looked at along the ray sdfr_mesh_surfaces defines (reach finite and > 0),
+ * whose direction -normals[i] is also the view direction of the specular term. */
+int sdfr_mesh_lighting(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits /* or NULL */,
+	sdfr_lighting *lighting, sdfr_light_sample *lights /* or NULL */, int on_host);
+
 /* ---- ambient occlusion at points, hits and mesh vertices (DESIGN.md "Occlusion queries"; no counterpart in the reference): how much
  *      of the hemisphere above a surface point is blocked within a radius, as an integer mask of which of 64 fixed directions hit
  *      something.  Every bit is fixed: there is no floating-point reduction and no dependence on order.

@@ -147,6 +147,24 @@ public:
 		return handle && pushState() && sdfr_mesh_surfaces(handle, n, positions, normals, reach, hits, surfaces, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// How the scene's lights fall on the first hit (sdfr_query_ray_lighting, sdfr_pick_lighting, sdfr_mesh_lighting in sdfr.h): hits and
+	// lights ([n][8] samples) may be null; pickLighting with pixels_xy null is the whole frame, n = width * height.
+	bool queryRayLighting(int64_t n, const float *origins, const float *dirs, sdfr_hit *hits, sdfr_lighting *lighting, sdfr_light_sample *lights,
+		float max_distance = 0.f, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_query_ray_lighting(handle, n, origins, dirs, max_distance, hits, lighting, lights, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool pickLighting(const Camera &camera, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, sdfr_lighting *lighting,
+		sdfr_light_sample *lights, bool on_host = true)
+	{
+		return handle && pushState(&camera) && sdfr_pick_lighting(handle, width, height, n, pixels_xy, hits, lighting, lights, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool meshLighting(int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits, sdfr_lighting *lighting,
+		sdfr_light_sample *lights, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_mesh_lighting(handle, n, positions, normals, reach, hits, lighting, lights, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// Ambient occlusion (sdfr_query_occlusion, sdfr_hit_occlusion in sdfr.h): which of 64 fixed directions above each point, or each hit
 	// of a query, meet the scene within `radius`.
 	bool queryOcclusion(int64_t n, const float *points, const float *normals, float bias, float radius, sdfr_occlusion *out, bool on_host = true)

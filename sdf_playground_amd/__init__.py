@@ -96,6 +96,18 @@ SURFACE_LIT = 2
 # sdfr_occlusion (include/sdfr.h): which of 64 fixed directions above a point are blocked within a radius, 16 bytes
 OCCLUSION_DTYPE = np.dtype([("mask_lo", np.uint32), ("mask_hi", np.uint32), ("occluded", np.uint32), ("valid", np.int32)])
 assert OCCLUSION_DTYPE.itemsize == 16
+# sdfr_lighting (include/sdfr.h): how the scene's lights fall on a hit, 64 bytes; sdfr_light_sample: one light slot of it, 80 bytes, [n, 8]
+LIGHTING_DTYPE = np.dtype([("valid", np.int32), ("used_mask", np.uint32), ("traced_mask", np.uint32), ("visible_mask", np.uint32),
+                           ("own", np.float32, (3,)), ("ambient_factor", np.float32), ("direct", np.float32, (3,)), ("segments", np.uint32),
+                           ("lit", np.float32, (3,)), ("reserved", np.float32)])
+assert LIGHTING_DTYPE.itemsize == 64
+LIGHT_SAMPLE_DTYPE = np.dtype([("state", np.int32), ("flags", np.uint32), ("segments", np.uint32), ("reserved0", np.uint32),
+                               ("dir", np.float32, (3,)), ("distance", np.float32), ("color", np.float32, (3,)), ("light_dot", np.float32),
+                               ("influenced", np.float32, (3,)), ("specular_factor", np.float32), ("delivered", np.float32, (3,)),
+                               ("reserved1", np.float32)])
+assert LIGHT_SAMPLE_DTYPE.itemsize == 80
+LIGHT_DIRECTIONAL = 1
+LIGHT_UNUSED, LIGHT_NO_CHAIN, LIGHT_BLOCKED, LIGHT_ESCAPED = 0, 1, 2, 3
 
 
 # every symbol include/sdfr.h declares (tests check that the library exports all of them)
@@ -111,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_register_host_target", "sdfr_query_distance", "sdfr_query_rays", "sdfr_pick", "sdfr_mesh_extract", "sdfr_mesh_get_timings",
     "sdfr_render_aa", "sdfr_query_ray_surfaces", "sdfr_pick_surfaces", "sdfr_mesh_surfaces",
     "sdfr_occlusion_directions", "sdfr_query_occlusion", "sdfr_hit_occlusion",
+    "sdfr_query_ray_lighting", "sdfr_pick_lighting", "sdfr_mesh_lighting",
 ]
 
 _lib = None
@@ -213,6 +226,9 @@ def load_library():
     L.sdfr_query_ray_surfaces.argtypes = [vp, i64, vp, vp, cf, vp, vp, ci]
     L.sdfr_pick_surfaces.argtypes = [vp, ci, ci, i64, vp, vp, vp, ci]
     L.sdfr_mesh_surfaces.argtypes = [vp, i64, vp, vp, cf, vp, vp, ci]
+    L.sdfr_query_ray_lighting.argtypes = [vp, i64, vp, vp, cf, vp, vp, vp, ci]
+    L.sdfr_pick_lighting.argtypes = [vp, ci, ci, i64, vp, vp, vp, vp, ci]
+    L.sdfr_mesh_lighting.argtypes = [vp, i64, vp, vp, cf, vp, vp, vp, ci]
     L.sdfr_occlusion_directions.argtypes = [vp]
     L.sdfr_query_occlusion.argtypes = [vp, i64, vp, vp, cf, cf, vp, ci]
     L.sdfr_hit_occlusion.argtypes = [vp, i64, vp, cf, cf, vp, ci]
@@ -572,6 +588,8 @@ class SDFRenderer:
     _HITS = (HIT_DTYPE, 0, 12, False, True)
     _SURFACES = (SURFACE_DTYPE, 0, 32, False, False)
     _OCCLUSION = (OCCLUSION_DTYPE, 0, 4, True, False)
+    _LIGHTING = (LIGHTING_DTYPE, 0, 16, False, False)
+    _LIGHT_SAMPLES = (LIGHT_SAMPLE_DTYPE, 8, 160, False, False)
 
     def _answer(self, n, like, kind, name, given=None):
         """One answer array of a query on the side of its inputs (like: their first device tensor, or None for numpy): a new numpy array
@@ -647,6 +665,44 @@ class SDFRenderer:
         n, (p, nr), like = self._inputs((positions, np.float32, 3, "positions"), (normals, np.float32, 3, "normals"))
         return self._surfaces(self._L.sdfr_mesh_surfaces, n, like, hits, n, p, nr, float(reach))
 
+    # ---- how the scene's lights fall on a hit (sdfr_query_ray_lighting / sdfr_pick_lighting / sdfr_mesh_lighting; DESIGN.md "Lighting
+    # queries").  numpy arrays in: LIGHTING_DTYPE records out; hits=True adds HIT_DTYPE records in front, lights=True LIGHT_SAMPLE_DTYPE
+    # records [n, 8] behind.  Device tensors in: [n, 16] (and [n, 12], [n, 160]) float32 device tensors out, whose integer fields are
+    # read with .view(torch.int32).
+    def _lighting(self, call, n, like, hits, lights, *scalars_and_inputs):
+        h, ph = self._answer(n, like, self._HITS, "hits") if hits else (None, None)
+        g, pg = self._answer(n, like, self._LIGHTING, "lighting")
+        s, ps = self._answer(n, like, self._LIGHT_SAMPLES, "lights") if lights else (None, None)
+        self._check(call(self._h, *scalars_and_inputs, ph, pg, ps, like is None))
+        out = ((h,) if hits else ()) + (g,) + ((s,) if lights else ())
+        return out if len(out) > 1 else g
+
+    def queryRayLighting(self, origins, dirs, max_distance=0.0, hits=False, lights=False):
+        """The direct lighting at the first hit along rays (as queryRays): LIGHTING_DTYPE records [n]; with hits and / or lights a tuple
+        (hits, lighting, light samples [n, 8]) of those asked for."""
+        n, (o, d), like = self._inputs((origins, np.float32, 3, "origins"), (dirs, np.float32, 3, "dirs"))
+        return self._lighting(self._L.sdfr_query_ray_lighting, n, like, hits, lights, n, o, d, float(max_distance))
+
+    def pickLighting(self, pixels_xy, width, height, hits=False, lights=False, device=False):
+        """The direct lighting under pixels [n, 2] of a width x height frame of the current camera (as pick).  pixels_xy=None: every pixel
+        of the frame in row-major order (height * width records; device=True: as device tensors)."""
+        width, height = int(width), int(height)
+        if pixels_xy is None:
+            n, px, like = width * height, None, None
+            if device:
+                import torch
+
+                like = torch.empty(0, device=torch.device("cuda", self.device))
+        else:
+            n, (px,), like = self._inputs((pixels_xy, np.int32, 2, "pixels_xy"))
+        return self._lighting(self._L.sdfr_pick_lighting, n, like, hits, lights, width, height, n, px)
+
+    def meshLighting(self, positions, normals, reach, hits=False, lights=False):
+        """The direct lighting at mesh vertices positions [n, 3] with normals [n, 3], each looked at from `reach` outside it along its
+        normal (sdfr_mesh_lighting); valid = 0 where that ray misses."""
+        n, (p, nr), like = self._inputs((positions, np.float32, 3, "positions"), (normals, np.float32, 3, "normals"))
+        return self._lighting(self._L.sdfr_mesh_lighting, n, like, hits, lights, n, p, nr, float(reach))
+
     # ---- ambient occlusion (sdfr_query_occlusion / sdfr_hit_occlusion; DESIGN.md "Occlusion queries").  numpy arrays in:
     # OCCLUSION_DTYPE records out.  Device tensors in: an [n, 4] int32 device tensor out (mask_lo, mask_hi, occluded, valid), enqueued
     # on the handle's stream.
@@ -668,30 +724,36 @@ class SDFRenderer:
 
     # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
     def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None, occlusion=False, ao_radius=None,
-                    ao_bias=None):
+                    ao_bias=None, lighting=False):
         """Surface nets over the lattice origin + (i, j, k) * cell, dims = (nx, ny, nz) cells: (positions [v, 3] float32, normals [v, 3]
         float32 or None, indices [t, 3]) -- numpy arrays (indices uint32), or with device=True torch tensors on the renderer's GPU
         (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call.
         surfaces=True: a fourth element, the surface at every vertex (meshSurfaces with `reach`, default 2 * cell; needs the normals) --
         the mesh is made on the GPU and looked at there, whatever `device` says about where the results go.
         occlusion=True: one more element, after the surfaces if both are asked for: the ambient occlusion at every vertex
-        (queryOcclusion with ao_bias, default 1 cell, and ao_radius, default 8 cells; needs the normals), looked at on the GPU likewise."""
-        if surfaces or occlusion:
+        (queryOcclusion with ao_bias, default 1 cell, and ao_radius, default 8 cells; needs the normals), looked at on the GPU likewise.
+        lighting=True: one more element, the last: the direct lighting at every vertex (meshLighting with `reach`; needs the normals)."""
+        if surfaces or occlusion or lighting:
             if not normals:
-                raise ValueError("surfaces=True and occlusion=True need the normals")
+                raise ValueError("surfaces=True, occlusion=True and lighting=True need the normals")
             pos, nrm, idx = self.extractMesh(origin, cell, dims, iso, True, device=True)
             extra = []
             if surfaces:
                 extra.append(self.meshSurfaces(pos, nrm, 2.0 * float(cell) if reach is None else reach))
             if occlusion:
                 extra.append(self.queryOcclusion(pos, nrm, float(cell) if ao_bias is None else ao_bias, 8.0 * float(cell) if ao_radius is None else ao_radius))
+            if lighting:
+                extra.append(self.meshLighting(pos, nrm, 2.0 * float(cell) if reach is None else reach))
             if device:
                 return (pos, nrm, idx) + tuple(extra)
             self.sync()
             if surfaces:
                 extra[0] = extra[0].cpu().numpy().view(np.uint32).reshape(-1).view(SURFACE_DTYPE)
             if occlusion:
-                extra[-1] = extra[-1].cpu().numpy().view(np.uint32).reshape(-1).view(OCCLUSION_DTYPE)
+                k = 1 if surfaces else 0
+                extra[k] = extra[k].cpu().numpy().view(np.uint32).reshape(-1).view(OCCLUSION_DTYPE)
+            if lighting:
+                extra[-1] = extra[-1].cpu().numpy().view(np.uint32).reshape(-1).view(LIGHTING_DTYPE)
             return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32)) + tuple(extra)
         grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
         counts = MeshCounts()

@@ -130,6 +130,9 @@ def make_parser():
     ap.add_argument("--gbuffer", metavar="OUT.npz", help="write depth, normal, albedo, material_id and valid of every pixel of the frame")
     ap.add_argument("--mesh-ao", type=float, metavar="RADIUS", help="with --mesh: vertex colours times the ambient openness within RADIUS")
     ap.add_argument("--gbuffer-ao", type=float, metavar="RADIUS", help="with --gbuffer: add `ao`, the ambient openness within RADIUS at every pixel's hit")
+    ap.add_argument("--mesh-lit", action="store_true", help="with --mesh: a colour per vertex, from the scene's lights as the renderer shades a hit "
+                    "(instead of --mesh-colors / --mesh-ao)")
+    ap.add_argument("--gbuffer-lighting", action="store_true", help="with --gbuffer: add `lit`, `own`, `direct` and the used, traced and visible light masks")
     return ap
 
 
@@ -149,6 +152,13 @@ def gbuffer_arrays(hits, surfaces, w, h, occlusion=None):
             "normal": surfaces["shading_normal"].reshape(h, w, 3),
             "albedo": np.where(lit[:, None], surfaces["albedo"], surfaces["unlit"]).astype(np.float32).reshape(h, w, 3),
             "material_id": surfaces["material_id"].reshape(h, w), "valid": surfaces["valid"].reshape(h, w)}
+
+
+def gbuffer_lighting_arrays(lighting, w, h):
+    """what --gbuffer-lighting adds, from the lighting records of pickLighting(None, w, h)"""
+    out = {k: lighting[k].reshape(h, w, 3) for k in ("lit", "own", "direct")}
+    out.update({k: lighting[k].reshape(h, w) for k in ("used_mask", "traced_mask", "visible_mask")})
+    return out
 
 
 def render_call(renderer, aa):
@@ -231,7 +241,13 @@ def main(argv=None):
 
         colors = None
         ao = dict(occlusion=True, ao_radius=a.mesh_ao) if a.mesh_ao is not None else {}
-        if a.mesh_colors:
+        if a.mesh_lit:
+            from .obj import lighting_colors
+
+            pos, nrm, idx, lighting = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, lighting=True)
+            colors, missing = lighting_colors(lighting)
+            occ = []
+        elif a.mesh_colors:
             from .obj import surface_colors
 
             pos, nrm, idx, srf, *occ = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, surfaces=True, **ao)
@@ -257,7 +273,8 @@ def main(argv=None):
         r.setCamera(cam)
         hits, srf = r.pickSurfaces(None, w, h, hits=True)
         occ = r.hitOcclusion(hits, GBUFFER_AO_BIAS, a.gbuffer_ao) if a.gbuffer_ao is not None else None
-        np.savez(a.gbuffer, **gbuffer_arrays(hits, srf, w, h, occ))
+        more = gbuffer_lighting_arrays(r.pickLighting(None, w, h), w, h) if a.gbuffer_lighting else {}
+        np.savez(a.gbuffer, **gbuffer_arrays(hits, srf, w, h, occ), **more)
         print("%s %dx%d: G-buffer -> %s" % (a.scene, w, h, a.gbuffer))
         if not a.out and not a.out_hdr:
             r.close()

@@ -718,13 +718,15 @@ static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipS
 	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "query launch");
 }
 
-// The queries (sdfr_query.h, sdfr_surface.h, sdfr_occlusion.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not
+// The queries (sdfr_query.h, sdfr_surface.h, sdfr_occlusion.h, sdfr_lighting.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not
 // the handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
-// out: distance + normals, or hits and / or surfaces, or occlusion records.
+// out: distance + normals, or hits and / or surfaces, or occlusion records, or lighting records with hits and light samples on request.
 static const size_t k_query_stage_keep = (size_t)64 << 20; // staging bytes a handle keeps between host queries
 static_assert(sizeof(sdfr_hit) == 4 * QUERY_HIT_WORDS, "sdfr_hit is the query kernels' 12-word record");
 static_assert(sizeof(sdfr_surface) == 4 * QUERY_SURFACE_WORDS, "sdfr_surface is the surface kernel's 32-word record");
 static_assert(sizeof(sdfr_occlusion) == 4 * QUERY_OCCLUSION_WORDS, "sdfr_occlusion is the occlusion kernel's 4-word record");
+static_assert(sizeof(sdfr_lighting) == 4 * QUERY_LIGHTING_WORDS, "sdfr_lighting is the lighting kernel's 16-word record");
+static_assert(sizeof(sdfr_light_sample) == 4 * QUERY_LIGHT_SAMPLE_WORDS && SDFR_MAX_LIGHTS == QUERY_LIGHT_SLOTS, "sdfr_light_sample[8] is the lighting kernel's 8 x 20 words");
 // the end of a host call: the answers back to the caller in the order they were named, and `stream` synchronised.  A large call
 // does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
 static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
@@ -750,7 +752,7 @@ static int query_impl(sdfr_renderer *r, const QueryRequest &c)
 	if (rc != SDFR_OK) return rc;
 
 	QueryArgs q = p.q;
-	Carving st({p.bytes[0], p.bytes[1], p.bytes[2], p.bytes[3]});
+	Carving st({p.bytes[0], p.bytes[1], p.bytes[2], p.bytes[3], p.bytes[4], p.bytes[5]});
 	if (c.on_host)
 	{
 		// the caller's arrays are host memory: each array of the kind that is there gets its piece of the staging buffer
@@ -764,6 +766,8 @@ static int query_impl(sdfr_renderer *r, const QueryRequest &c)
 		}
 		for (int k = 2; k < 4; ++k)
 			if (p.bytes[k]) query_slot_set(q, kind.out[k - 2], st.answer(k, const_cast<void *>(query_slot_get(p.q, kind.out[k - 2])), p.bytes[k]));
+		for (int k = 4; k < 6; ++k)
+			if (p.bytes[k]) query_slot_set(q, k_query_lighting_slots[k - 4], st.answer(k, const_cast<void *>(query_slot_get(p.q, k_query_lighting_slots[k - 4])), p.bytes[k]));
 	}
 	rc = run_query(r, U, q, stream);
 	if (rc != SDFR_OK) return rc;
@@ -834,6 +838,39 @@ int sdfr_mesh_surfaces(sdfr_renderer *r, int64_t n, const float *positions, cons
 {
 	return guarded(r, [&]() -> int {
 		QueryRequest c = ray_request(n, positions, normals, reach, hits, surfaces, true, on_host);
+		c.q.kind = QUERY_MESH;
+		return query_impl(r, c);
+	});
+}
+
+// the lighting entries: the ray kinds' requests with `lighting` and perhaps `lights` instead of surfaces
+static QueryRequest with_lighting(QueryRequest c, sdfr_lighting *lighting, sdfr_light_sample *lights)
+{
+	c.q.lighting = words(lighting);
+	c.q.lights = words(lights);
+	c.want_surfaces = false;
+	c.want_lighting = true;
+	return c;
+}
+
+int sdfr_query_ray_lighting(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, float max_distance, sdfr_hit *hits, sdfr_lighting *lighting,
+	sdfr_light_sample *lights, int on_host)
+{
+	return guarded(r, [&]() -> int { return query_impl(r, with_lighting(ray_request(n, origins, dirs, max_distance, hits, nullptr, false, on_host), lighting, lights)); });
+}
+
+int sdfr_pick_lighting(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, sdfr_hit *hits, sdfr_lighting *lighting, sdfr_light_sample *lights,
+	int on_host)
+{
+	// (pick_request: without a pixel list the whole frame, as the surface entry)
+	return guarded(r, [&]() -> int { return query_impl(r, with_lighting(pick_request(width, height, n, pixels_xy, hits, nullptr, true, on_host), lighting, lights)); });
+}
+
+int sdfr_mesh_lighting(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, sdfr_hit *hits, sdfr_lighting *lighting,
+	sdfr_light_sample *lights, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		QueryRequest c = with_lighting(ray_request(n, positions, normals, reach, hits, nullptr, false, on_host), lighting, lights);
 		c.q.kind = QUERY_MESH;
 		return query_impl(r, c);
 	});

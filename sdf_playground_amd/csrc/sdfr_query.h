@@ -4,7 +4,7 @@
 // stages of sdfr_pixel.h as the pixel pipeline calls them (sdfr_render_pixel.h); the kernels that run them one lane per item
 // are in sdfr_query_kernel.h, and tests/cpp/query_host.cpp compiles these functions for the CPU to compare them with the oracle.
 #pragma once
-#include "sdfr_pixel.h"
+#include "sdfr_render_pixel.h"
 #include "sdfr_query_args.h"
 
 namespace sdfr {
@@ -89,17 +89,23 @@ SDF_HD float query_point(const FrameU &U, vec3 p, vec3 *normal)
 // `rec` and `at` are not touched (query_ray_hits; the occlusion query, sdfr_occlusion.h).  One copy of the march for both; a
 // template parameter and not a function of its own, because the existing kernels' code stays the same, instruction for instruction,
 // only if the body they instantiate does.
+// SHADOW: one segment of a shadow ray (sdfr_lighting.h), the driver's turn for a ray with is_shadow_ray set (pshader_sdf.hlsl:299-353 again):
+// the march is made with *shadow_flags as the MarchingInput -- is_shadow_pass, and the has_transparent / last_transparent_pos of the
+// chain so far -- and a scene whose materials do not read the normal of a shadow hit (ShadowHitsNeedNormal) is not asked for it, as in
+// the pixel pipeline; everything else is the same body, for the same reason as above.
 struct QueryHit
 {
 	SurfacePoint sp;
 	Material mat;
 };
-template <class Scene, bool DBG, bool MARCH_ONLY = false>
+template <class Scene, bool DBG, bool MARCH_ONLY = false, bool SHADOW = false>
 SDF_HD bool query_ray_at(const FrameU &U, vec3 origin, vec3 dir, float dist_max, vec3 right_off, vec3 bottom_off, uint32_t rec[QUERY_HIT_WORDS],
-	QueryHit &at)
+	QueryHit &at, const RayFlags *shadow_flags = nullptr)
 {
 	const DebugFlags F = debug_flags(U);
-	const typename Scene::RayInv R = Scene::ray_setup(U, dir, query_ray_flags());
+	RayFlags flags = query_ray_flags();
+	if constexpr (SHADOW) flags = *shadow_flags;
+	const typename Scene::RayInv R = Scene::ray_setup(U, dir, flags);
 	March m = march_begin(origin, dir);
 	int status;
 	const bool shortcuts = !DBG && (RayEscapes<Scene>::available || EscapesFrom<Scene>::available) && U.step_shortcuts != 0;
@@ -132,7 +138,7 @@ SDF_HD bool query_ray_at(const FrameU &U, vec3 origin, vec3 dir, float dist_max,
 	uint32_t material = 0u;
 	if (status == MARCH_HIT)
 	{
-		n = query_normal<Scene, DBG>(U, F, R, pos, dir, m.t, right_off, bottom_off, m.d);
+		if constexpr (!SHADOW || ShadowHitsNeedNormal<Scene>::value) n = query_normal<Scene, DBG>(U, F, R, pos, dir, m.t, right_off, bottom_off, m.d);
 		SurfacePoint &sp = at.sp;
 		sp.pos = pos;
 		sp.dir = dir;

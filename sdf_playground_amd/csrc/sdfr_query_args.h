@@ -9,7 +9,7 @@
 namespace sdfr {
 
 // One query launch.  Which members a kind reads and writes, at how many bytes per item, is the table of sdfr_query_plan.h
-// (k_query_kinds); every other pointer is null, and the kernels branch on `normals`, `hits` and `surfaces`.
+// (k_query_kinds); every other pointer is null, and the kernels branch on `normals`, `hits`, `surfaces` and `lights`.
 enum { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_PICK = 2, QUERY_FRAME = 3, QUERY_MESH = 4, QUERY_OCCLUSION = 5, QUERY_HIT_OCCLUSION = 6, QUERY_KINDS = 7 };
 struct QueryArgs
 {
@@ -26,17 +26,20 @@ struct QueryArgs
 	const uint32_t *hit_items; // 12 words per item, read
 	uint32_t *occlusion;       // 4 words per item: the layout of sdfr_occlusion
 	float bias;
+	// the lighting kernel (appended likewise)
+	uint32_t *lighting; // 16 words per item: the layout of sdfr_lighting
+	uint32_t *lights;   // or null: 8 x 20 words per item, the layout of sdfr_light_sample[8]
 };
-enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32, QUERY_OCCLUSION_WORDS = 4 };
-static_assert(sizeof(QueryArgs) == 96, "QueryArgs is a kernel argument");
+enum { QUERY_HIT_WORDS = 12, QUERY_SURFACE_WORDS = 32, QUERY_OCCLUSION_WORDS = 4, QUERY_LIGHTING_WORDS = 16, QUERY_LIGHT_SAMPLE_WORDS = 20, QUERY_LIGHT_SLOTS = 8 };
+static_assert(sizeof(QueryArgs) == 112, "QueryArgs is a kernel argument");
 static_assert(__builtin_offsetof(QueryArgs, kind) == 0 && __builtin_offsetof(QueryArgs, n) == 4 && __builtin_offsetof(QueryArgs, pos) == 8 && __builtin_offsetof(QueryArgs, dir) == 16, "");
 static_assert(__builtin_offsetof(QueryArgs, pixels) == 24 && __builtin_offsetof(QueryArgs, dist_max) == 32 && __builtin_offsetof(QueryArgs, reach) == 36, "");
 static_assert(__builtin_offsetof(QueryArgs, distance) == 40 && __builtin_offsetof(QueryArgs, normals) == 48 && __builtin_offsetof(QueryArgs, hits) == 56, "");
 static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offsetof(QueryArgs, hit_items) == 72 && __builtin_offsetof(QueryArgs, occlusion) == 80, "");
-static_assert(__builtin_offsetof(QueryArgs, bias) == 88, "");
+static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
-// A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_KINDS = 5 };
+// A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_KINDS = 6 };
 
 // One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into

@@ -9,6 +9,7 @@
 #include "sdfr_query.h"
 #include "sdfr_surface.h"
 #include "sdfr_occlusion.h"
+#include "sdfr_lighting.h"
 
 namespace sdfr {
 
@@ -115,6 +116,72 @@ __device__ __forceinline__ void query_surfaces_kernel(const QueryKernelArgs &a)
 	query_surface<Scene, DBG>(U, ray, in_frame, hit, rec);
 	if (q.hits) query_store(q.hits, i, hit);
 	query_store(q.surfaces, i, rec);
+}
+
+// The lighting queries (sdfr_lighting.h): the surface kernel's items, mapped to lanes the same way (the lines are repeated, not shared:
+// a helper of both changed the surface kernel's code) -> `lighting`, `hits` unless null, and unless `lights` is null the eight
+// light samples of the item.  One lane per item: the primary ray is marched once, and the lane loops over the light slots and follows
+// each shadow chain itself -- a lane per (item, light) would march the primary ray eight times, (P + S) / 8 per item against
+// (P + 8 S) / 64.  A sample leaves as soon as its slot is done (five 16-byte stores, or 20 words), so that no lane holds eight of them.
+struct LightSampleStore
+{
+	uint32_t *item; // the item's eight samples, or null
+	bool aligned;
+	__device__ __forceinline__ bool wanted() const { return item != nullptr; }
+	__device__ __forceinline__ void operator()(int slot, const uint32_t (&s)[QUERY_LIGHT_SAMPLE_WORDS]) const
+	{
+		uint32_t *out = item + QUERY_LIGHT_SAMPLE_WORDS * slot;
+		if (aligned)
+		{
+			uint4 *dst = reinterpret_cast<uint4 *>(out);
+#pragma unroll
+			for (int k = 0; k < QUERY_LIGHT_SAMPLE_WORDS / 4; ++k) dst[k] = make_uint4(s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
+		}
+		else
+		{
+#pragma unroll
+			for (int k = 0; k < QUERY_LIGHT_SAMPLE_WORDS; ++k) out[k] = s[k];
+		}
+	}
+};
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_lighting_kernel(const QueryKernelArgs &a)
+{
+	static_assert(QUERY_LIGHT_SLOTS == SDFR_MAX_LIGHTS && QUERY_LIGHT_SAMPLE_WORDS % 4 == 0, "eight samples of whole 16-byte pieces per item");
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 pixels");
+	const FrameU &U = a.U;
+	const QueryArgs &q = a.q;
+	const uint32_t lane = threadIdx.x;
+	uint32_t i;
+	QueryRay ray;
+	bool in_frame = true;
+	if (q.kind == QUERY_FRAME)
+	{
+		const uint32_t tiles_x = ((uint32_t)U.width + 7u) >> 3;
+		const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+		const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+		if (px >= (uint32_t)U.width || py >= (uint32_t)U.height) return;
+		i = py * (uint32_t)U.width + px; // < width * height <= 2^30
+		in_frame = query_pixel_ray(U, (int)px, (int)py, ray);
+	}
+	else
+	{
+		i = blockIdx.x * 64u + lane;
+		if (i >= (uint32_t)q.n) return;
+		if (q.kind == QUERY_PICK)
+			in_frame = query_pixel_ray(U, q.pixels[(size_t)2 * i], q.pixels[(size_t)2 * i + 1], ray);
+		else if (q.kind == QUERY_MESH)
+			ray = query_mesh_ray(query_load3(q.pos, i), query_load3(q.dir, i), q.reach);
+		else
+			ray = query_plain_ray(query_load3(q.pos, i), query_load3(q.dir, i), q.dist_max);
+	}
+	LightSampleStore samples;
+	samples.item = q.lights ? q.lights + (size_t)(QUERY_LIGHT_SLOTS * QUERY_LIGHT_SAMPLE_WORDS) * i : nullptr; // (n * 640 bytes: 64-bit)
+	samples.aligned = (reinterpret_cast<size_t>(q.lights) & 15u) == 0u;
+	uint32_t hit[QUERY_HIT_WORDS], rec[QUERY_LIGHTING_WORDS];
+	query_lighting<Scene, DBG>(U, ray, in_frame, hit, rec, samples);
+	if (q.hits) query_store(q.hits, i, hit);
+	query_store(q.lighting, i, rec);
 }
 
 // The occlusion queries (sdfr_occlusion.h): one wave per block, one block per item, lane k marches direction k.  The item -- a point

@@ -36,7 +36,7 @@ struct QueryKind
 	int reach_rule;   // QUERY_REACH_* of `reach`
 	const char *reach_text;
 	bool bias;  // takes a bias: finite and >= 0
-	int kernel; // QUERY_KERNEL_*; the ray kernel's kinds go to the surface kernel exactly when surfaces are asked for (query_kernel_of)
+	int kernel; // QUERY_KERNEL_*; the ray kernel's kinds go to the surface kernel exactly when surfaces are asked for, to the lighting kernel when lighting is (query_kernel_of)
 	int grid;   // QUERY_GRID_*
 };
 #define SDFR_Q(member, bytes) {offsetof(QueryArgs, member), bytes}
@@ -52,6 +52,8 @@ static const QueryKind k_query_kinds[QUERY_KINDS] = {
 	/* OCCLUSION: points, normals */ {{SDFR_Q(pos, 12), SDFR_Q(dir, 12)}, {SDFR_Q(occlusion, 4 * QUERY_OCCLUSION_WORDS), SDFR_Q_NONE}, false, false, QUERY_REACH_POSITIVE, k_query_radius_text, true, QUERY_KERNEL_OCCLUSION, QUERY_GRID_BLOCK_PER_ITEM},
 	/* HIT_OCCLUSION */ {{SDFR_Q(hit_items, 4 * QUERY_HIT_WORDS), SDFR_Q_NONE}, {SDFR_Q(occlusion, 4 * QUERY_OCCLUSION_WORDS), SDFR_Q_NONE}, false, false, QUERY_REACH_POSITIVE, k_query_radius_text, true, QUERY_KERNEL_OCCLUSION, QUERY_GRID_BLOCK_PER_ITEM},
 };
+// what the lighting entries add to a ray kind's arrays: `lighting` required, `lights` optional; `hits` is then optional and `surfaces` is not taken
+static const QuerySlot k_query_lighting_slots[2] = {SDFR_Q(lighting, 4 * QUERY_LIGHTING_WORDS), SDFR_Q(lights, 4 * QUERY_LIGHT_SLOTS * QUERY_LIGHT_SAMPLE_WORDS)};
 #undef SDFR_Q_HITS
 #undef SDFR_Q_NONE
 #undef SDFR_Q
@@ -68,7 +70,8 @@ inline void query_slot_set(QueryArgs &q, const QuerySlot &s, const void *p) { me
 inline int query_kernel_of(const QueryArgs &q)
 {
 	const int kernel = k_query_kinds[q.kind].kernel;
-	return kernel == QUERY_KERNEL_RAYS && q.surfaces ? QUERY_KERNEL_SURFACES : kernel;
+	if (kernel != QUERY_KERNEL_RAYS) return kernel;
+	return q.lighting ? QUERY_KERNEL_LIGHTING : q.surfaces ? QUERY_KERNEL_SURFACES : kernel;
 }
 
 // The launches of q (q.n > 0 items of a width x height frame): launch k covers the items [first, first + count) with `blocks` blocks of
@@ -104,14 +107,15 @@ inline QueryArgs query_launch_args(const QueryArgs &q, const QueryLaunch &l)
 	const QueryKind &kind = k_query_kinds[q.kind];
 	QueryArgs a = q;
 	a.n = (int)l.count;
-	for (const QuerySlot *s : {&kind.in[0], &kind.in[1], &kind.out[0], &kind.out[1]})
+	for (const QuerySlot *s : {&kind.in[0], &kind.in[1], &kind.out[0], &kind.out[1], &k_query_lighting_slots[0], &k_query_lighting_slots[1]})
 		if (const void *p = s->bytes ? query_slot_get(q, *s) : nullptr) query_slot_set(a, *s, static_cast<const char *>(p) + s->bytes * (size_t)l.first);
 	return a;
 }
 
 // What an entry point asks for: the kernel's arguments as the caller gave them -- q.kind, the arrays of that kind, q.reach (the
 // max_distance of rays, the reach of a mesh, the radius of an occlusion query) and q.bias; everything else stays null or 0 -- and what
-// only the host needs.  want_surfaces: one of the surface entries, which needs q.surfaces and takes q.hits or not.
+// only the host needs.  want_surfaces: one of the surface entries, which needs q.surfaces and takes q.hits or not.  want_lighting: one of
+// the lighting entries (the kinds of the ray kernel only), which needs q.lighting and takes q.hits and q.lights or not.
 struct QueryRequest
 {
 	QueryArgs q;
@@ -119,6 +123,7 @@ struct QueryRequest
 	int width, height;
 	bool want_surfaces;
 	int on_host;
+	bool want_lighting;
 };
 inline QueryRequest query_request(int kind, int64_t n, int on_host)
 {
@@ -136,7 +141,7 @@ struct QueryPlan
 	const char *error;
 	bool nothing_to_do; // n = 0
 	QueryArgs q;        // for the caller's arrays as device memory; a host call points the slots at its staging pieces
-	size_t bytes[4];    // of the arrays in the order they are staged: in[0], in[1], out[0], out[1]
+	size_t bytes[6];    // of the arrays in the order they are staged: in[0], in[1], out[0], out[1], lighting, lights
 	int width, height;  // of the frame to latch
 	int kernel;         // QUERY_KERNEL_*
 	uint32_t launches;  // query_launch(q, width, height, 0 .. launches - 1)
@@ -161,17 +166,21 @@ inline QueryPlan plan_query(const QueryRequest &c, float range)
 	p.nothing_to_do = c.n == 0;
 	if (p.nothing_to_do) return p;
 	if (kind.frame_items && c.n != (int64_t)c.width * c.height) return fail("without a pixel list n must be width * height");
-	const QuerySlot &required = kind.out[c.want_surfaces ? 1 : 0];
+	const bool lighting = c.want_lighting && kind.kernel == QUERY_KERNEL_RAYS;
+	const QuerySlot &required = lighting ? k_query_lighting_slots[0] : kind.out[c.want_surfaces ? 1 : 0];
 	for (const QuerySlot *s : {&kind.in[0], &kind.in[1], &required})
 		if (s->bytes && !query_slot_get(c.q, *s)) return fail("null pointer");
 
 	p.q = c.q;
+	if (lighting) p.q.surfaces = nullptr;
+	else p.q.lighting = p.q.lights = nullptr;
 	p.q.n = (int)c.n;
 	p.q.dist_max = reach == 0.f ? range : reach; // (a mesh's rays are marched to 2 * reach: query_mesh_ray)
 	for (int k = 0; k < 2; ++k)
 	{
 		p.bytes[k] = (size_t)c.n * kind.in[k].bytes;
-		p.bytes[2 + k] = kind.out[k].bytes && query_slot_get(c.q, kind.out[k]) ? (size_t)c.n * kind.out[k].bytes : 0;
+		p.bytes[2 + k] = kind.out[k].bytes && query_slot_get(p.q, kind.out[k]) ? (size_t)c.n * kind.out[k].bytes : 0;
+		p.bytes[4 + k] = query_slot_get(p.q, k_query_lighting_slots[k]) ? (size_t)c.n * k_query_lighting_slots[k].bytes : 0;
 	}
 	p.width = kind.frame ? c.width : 1;
 	p.height = kind.frame ? c.height : 1;

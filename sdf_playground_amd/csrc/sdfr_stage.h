@@ -6,7 +6,7 @@
 
 namespace sdfr {
 
-enum { SDFR_STAGE_ALIGN = 256, SDFR_STAGE_MAX_PIECES = 4 };
+enum { SDFR_STAGE_ALIGN = 256, SDFR_STAGE_MAX_PIECES = 6 };
 
 // pieces of bytes[0 .. n) one after the other, each starting on a multiple of SDFR_STAGE_ALIGN (a piece of no bytes takes no room):
 // offsets[k] = where piece k starts; returns the bytes of the whole

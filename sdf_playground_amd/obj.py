@@ -37,6 +37,18 @@ def occlusion_colors(occlusion, colors=None):
     return (base * o[:, None]).astype(np.float32)
 
 
+def lighting_colors(lighting):
+    """Per-vertex colours [v, 3] float32 of LIGHTING_DTYPE records (extractMesh(lighting=True)): `lit`, the hit's own colour plus the
+    light every unshadowed light delivers, clipped to [0, 1] (a NaN becomes 0); MISSING_COLOR where valid != 1.  Also returns how many
+    are missing."""
+    import numpy as np
+
+    rgb = np.clip(np.nan_to_num(lighting["lit"].astype(np.float32), nan=0.0), 0.0, 1.0)
+    missing = lighting["valid"] != 1
+    rgb[missing] = MISSING_COLOR
+    return rgb, int(missing.sum())
+
+
 def write_obj(out, positions, normals, indices, comment=None, colors=None):
     """Writes the mesh to `out` (a path or a text file object): one `v x y z` per vertex -- `v x y z r g b` with `colors` [v, 3], the
     per-vertex colour extension most tools read --, one `vn x y z` per vertex if `normals` is given, one `f a//a b//b c//c`
