@@ -596,6 +596,83 @@ int sdfr_mesh_extract(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vert
  * Waits for that work. */
 int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4]);
 
+/* ---- a texture atlas of an extracted mesh (no counterpart in the reference; DESIGN.md "Texture atlas"): one square tile of texels per
+ *      quad of the mesh, baked on the GPU.  Surface nets emits quads: triangles 2q and 2q + 1 are (q0, q1, q2) and (q0, q2, q3) of one
+ *      quad, so a tile per quad needs no chart cutting and no packing search, and bilinear filtering inside a quad never leaves its tile.
+ *      All arithmetic is fp32.  Every operation is separate and unfused unless an fma is written.
+ *
+ *      Layout.  sdfr_atlas_layout(triangles, tile, width, out) is host only and needs no handle.
+ *        - tile T is one of 4, 8, 16, 32.
+ *        - width W is a multiple of 8 and of T, and W <= 16384.
+ *        - triangles is >= 0 and even, and quads = triangles / 2.
+ *        - tiles_per_row = W / T.
+ *        - rows = ceil(quads / tiles_per_row).
+ *        - height H = rows * T rounded up to a multiple of 8, at least 8.
+ *        - W * H must be a frame size the renderer accepts (W * H <= 2^30).
+ *        - Anything else is SDFR_ERR_INVALID_ARGUMENT.
+ *      Quad q owns the tile at column q % tiles_per_row, row q / tiles_per_row.  Its texels are (x0 + a, y0 + b) with x0 = col * T,
+ *      y0 = row * T and 0 <= a, b < T.  Texel (x, y) is item y * W + x, and row 0 is the top row of the image.
+ *
+ *      Quad of a tile.  The quad is (i0, i1, i2, i3) = (idx[2q][0], idx[2q][1], idx[2q][2], idx[2q+1][2]).  The tile is well formed
+ *      iff all of these hold:
+ *        - idx[2q+1][0] == i0;
+ *        - idx[2q+1][1] == i2;
+ *        - all four indices are < vertex_count, and the kernel checks this before it loads a vertex.
+ *      Otherwise every texel of the tile is invalid (-1).  Texels of no quad are invalid too.  These are the tiles past quads and the
+ *      rows past rows * T.
+ *
+ *      Texel -> surface point.  u = (float)a / (float)(T - 1) and v = (float)b / (float)(T - 1), one division each.  Corners map to
+ *      texel centres: q0 <-> (0, 0), q1 <-> (T-1, 0), q2 <-> (T-1, T-1), q3 <-> (0, T-1).  With A any of the two vertex arrays, per
+ *      component:
+ *        - if u >= v (triangle 2q):  X = (A0 + u * (A1 - A0)) + v * (A2 - A1);
+ *        - else (triangle 2q + 1):   X = (A0 + v * (A3 - A0)) + u * (A2 - A3).
+ *      P is X of the positions and M is X of the normals.  The unit normal is N = M * r with
+ *      r = 1.0f / sqrtf(fmaf(M.z, M.z, fmaf(M.y, M.y, M.x * M.x))).  This is `normalize` of sdfr_math.h as the query unit compiles it,
+ *      with IEEE square root and reciprocal.
+ *      A texel whose P or M has a non-finite component, or whose M is (0, 0, 0), or whose N is not finite, is DEGENERATE.
+ *
+ *      UVs.  sdfr_atlas_uvs(atlas, uvs [triangles][3][2], host) is pure host code.  The corner at texel (x, y) gets
+ *      (((float)x + 0.5f) / (float)W, ((float)y + 0.5f) / (float)H), with the origin top-left.  The corners are in the order of the
+ *      triangle's indices.  Bilinear filtering inside a quad never reads another tile.
+ *
+ *      sdfr_atlas_texels writes, for every texel of the image: valid = 1 with P and N; valid = 0 (degenerate) or -1 (invalid), with
+ *      zeros.  This is the escape hatch: a caller runs any existing query over the texels, for example sdfr_query_occlusion for a baked
+ *      AO map.  It looks at the mesh alone: it needs NO scene to be loaded and latches nothing; the handle gives the device, the
+ *      stream and the staging of a host call.
+ *
+ *      sdfr_atlas_bake.  A texel with sdfr_atlas_texels valid = 1 is looked at exactly as sdfr_mesh_surfaces / sdfr_mesh_lighting look
+ *      at the item (P, N, reach): the ray is theirs, and everything latched is as for a query.  Layers:
+ *        SDFR_ATLAS_ALBEDO  (sdfr_surface.albedo where the SDFR_SURFACE_LIT flag is set, else .unlit; .alpha)
+ *        SDFR_ATLAS_NORMAL  (sdfr_surface.shading_normal, 0)
+ *        SDFR_ATLAS_LIT     (sdfr_lighting.lit, 1)
+ *        - Every value is bit for bit that of those records.
+ *        - valid = the record's valid, 1 or 0, for a non-degenerate texel of a well-formed tile.  It is 0 for a degenerate texel, which
+ *          is not marched, and -1 for an invalid one.
+ *        - Every requested plane is written at every texel, with zeros unless valid = 1, so no caller clears anything.
+ *        - The lighting part, the light loop and the shadow chains, runs only when SDFR_ATLAS_LIT is asked for.
+ *        - reach is finite and > 0, layers is non-zero, and a requested plane's pointer is non-NULL.  Otherwise
+ *          SDFR_ERR_INVALID_ARGUMENT.  So is an atlas that sdfr_atlas_layout did not make, and a negative vertex_count.
+ *        - on_host, streams, two frames in flight, no effect on stats, timings or the row order, and n = 0 (no triangles: the 8-row
+ *          image is filled with -1 and zeros, and no scene is needed) all follow the queries section.  A plane is written by 16-byte
+ *          stores into device memory aligned to 16 bytes, by word stores into any other. -------------------------------------------- */
+typedef struct sdfr_atlas
+{
+	int64_t triangles, quads;
+	int32_t tile, width, height; /* T, W, H */
+	int32_t tiles_per_row, rows;
+	int32_t reserved;            /* 0 */
+} sdfr_atlas;
+#define SDFR_ATLAS_ALBEDO 1u
+#define SDFR_ATLAS_NORMAL 2u
+#define SDFR_ATLAS_LIT 4u
+int sdfr_atlas_layout(int64_t triangles, int tile, int width, sdfr_atlas *out);
+int sdfr_atlas_uvs(const sdfr_atlas *atlas, float *uvs /* [triangles][3][2], host */);
+int sdfr_atlas_texels(sdfr_renderer *r, const sdfr_atlas *atlas, int64_t vertex_count, const float *positions, const float *normals,
+	const uint32_t *indices, float *texel_positions /*[H*W][3]*/, float *texel_normals /*[H*W][3]*/, int32_t *valid /*[H*W]*/, int on_host);
+int sdfr_atlas_bake(sdfr_renderer *r, const sdfr_atlas *atlas, int64_t vertex_count, const float *positions, const float *normals,
+	const uint32_t *indices, float reach, uint32_t layers, float *albedo, float *normal, float *lit /* each [H*W][4] or NULL */,
+	int32_t *valid /* [H*W], required */, int on_host);
+
 /* ---- two frames in flight inside one handle (no counterpart: D3D11's immediate context pipelines the reference's draws by itself)
  *      The end of a frame runs on a nearly empty chip -- the last waves finishing their tiles -- and only the NEXT frame can fill it
  *      (DESIGN.md 4.1).  With n = 2 sdfr_render alternates between two internal streams, each with a workspace of its own (the

@@ -185,6 +185,23 @@ public:
 			sdfr_mesh_extract(handle, &grid, vertex_capacity, triangle_capacity, positions, normals, indices, &counts, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// The texture atlas of an extracted mesh (sdfr_atlas_layout, sdfr_atlas_uvs, sdfr_atlas_texels, sdfr_atlas_bake in sdfr.h): one square
+	// tile of texels per quad.  atlasTexels looks at the mesh alone; bakeAtlas looks at every texel as meshSurfaces / meshLighting look at
+	// a vertex, with this renderer's variables and time.  layers: SDFR_ATLAS_*; a plane that is not asked for may be null.
+	static bool atlasLayout(int64_t triangles, int tile, int width, sdfr_atlas &out) { return sdfr_atlas_layout(triangles, tile, width, &out) == SDFR_OK; }
+	static bool atlasUVs(const sdfr_atlas &atlas, float *uvs) { return sdfr_atlas_uvs(&atlas, uvs) == SDFR_OK; }
+	bool atlasTexels(const sdfr_atlas &atlas, int64_t vertex_count, const float *positions, const float *normals, const uint32_t *indices, float *texel_positions,
+		float *texel_normals, int32_t *valid, bool on_host = true)
+	{
+		return handle && sdfr_atlas_texels(handle, &atlas, vertex_count, positions, normals, indices, texel_positions, texel_normals, valid, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool bakeAtlas(const sdfr_atlas &atlas, int64_t vertex_count, const float *positions, const float *normals, const uint32_t *indices, float reach, uint32_t layers,
+		float *albedo, float *normal, float *lit, int32_t *valid, bool on_host = true)
+	{
+		return handle && pushState() &&
+			sdfr_atlas_bake(handle, &atlas, vertex_count, positions, normals, indices, reach, layers, albedo, normal, lit, valid, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// two frames in flight inside this renderer (sdfr_set_frames_in_flight): render into two targets in turn, sync() waits for both
 	bool setFramesInFlight(int n) { return sdfr_set_frames_in_flight(handle, n) == SDFR_OK; }
 	bool sync() { return sdfr_sync(handle) == SDFR_OK; }

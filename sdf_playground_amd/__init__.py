@@ -81,6 +81,13 @@ class MeshCounts(ctypes.Structure):  # sdfr_mesh_counts
 
 
 # sdfr_hit (include/sdfr.h): the answer of a ray query or a pick, 48 bytes
+class Atlas(ctypes.Structure):  # sdfr_atlas
+    _fields_ = [("triangles", ctypes.c_int64), ("quads", ctypes.c_int64), ("tile", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("tiles_per_row", ctypes.c_int32), ("rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+ATLAS_LAYERS = {"albedo": 1, "normal": 2, "lit": 4}  # SDFR_ATLAS_*
+
 HIT_DTYPE = np.dtype([("t", np.float32), ("distance", np.float32), ("pos", np.float32, (3,)), ("normal", np.float32, (3,)),
                       ("iterations", np.uint32), ("material_id", np.uint32), ("hit", np.int32), ("reserved", np.uint32)])
 assert HIT_DTYPE.itemsize == 48
@@ -124,6 +131,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_render_aa", "sdfr_query_ray_surfaces", "sdfr_pick_surfaces", "sdfr_mesh_surfaces",
     "sdfr_occlusion_directions", "sdfr_query_occlusion", "sdfr_hit_occlusion",
     "sdfr_query_ray_lighting", "sdfr_pick_lighting", "sdfr_mesh_lighting",
+    "sdfr_atlas_layout", "sdfr_atlas_uvs", "sdfr_atlas_texels", "sdfr_atlas_bake",
 ]
 
 _lib = None
@@ -234,6 +242,10 @@ def load_library():
     L.sdfr_hit_occlusion.argtypes = [vp, i64, vp, cf, cf, vp, ci]
     L.sdfr_mesh_extract.argtypes = [vp, ctypes.POINTER(MeshGrid), i64, i64, vp, vp, vp, ctypes.POINTER(MeshCounts), ci]
     L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
+    L.sdfr_atlas_layout.argtypes = [i64, ci, ci, ctypes.POINTER(Atlas)]
+    L.sdfr_atlas_uvs.argtypes = [ctypes.POINTER(Atlas), vp]
+    L.sdfr_atlas_texels.argtypes = [vp, ctypes.POINTER(Atlas), i64, vp, vp, vp, vp, vp, vp, ci]
+    L.sdfr_atlas_bake.argtypes = [vp, ctypes.POINTER(Atlas), i64, vp, vp, vp, cf, ctypes.c_uint32, vp, vp, vp, vp, ci]
     L.sdfr_render_gather.argtypes = [vp, vp, ci, ci, vp, ci, ci]
     L.sdfr_render_gather_all.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ci, ci, ci, vp, ci, ci]
     _lib = L
@@ -253,6 +265,38 @@ def occlusionDirections():
     if rc != 0:
         raise SdfrError(rc, "sdfr_occlusion_directions")
     return d
+
+
+def atlasLayout(triangles, tile=8, width=None):
+    """The texture atlas of a mesh of `triangles` triangles (sdfr_atlas_layout): one tile x tile square of texels per quad, `width`
+    texels wide (default: atlasDefaultWidth).  -> Atlas (triangles, quads, tile, width, height, tiles_per_row, rows)."""
+    a = Atlas()
+    if width is None:
+        width = atlasDefaultWidth(int(triangles) // 2, tile)
+    rc = load_library().sdfr_atlas_layout(int(triangles), int(tile), int(width), ctypes.byref(a))
+    if rc != 0:
+        raise SdfrError(rc, "sdfr_atlas_layout: tile must be 4, 8, 16 or 32, width a multiple of 8 and of the tile up to 16384, triangles even")
+    return a
+
+
+def atlasDefaultWidth(quads, tile=8):
+    """The smallest allowed atlas width >= tile * ceil(sqrt(quads)): a square-ish image."""
+    tile, quads = int(tile), max(int(quads), 0)
+    side = int(np.ceil(np.sqrt(quads)))
+    while side * side < quads:
+        side += 1
+    step = max(8, tile)
+    return min(max(step, (tile * side + step - 1) // step * step), 16384)
+
+
+def atlasUVs(atlas):
+    """The texture coordinates of the atlas (sdfr_atlas_uvs): [triangles, 3, 2] float32, one (u, v) per triangle corner in the order
+    of the triangle's indices, origin top-left, every corner on the centre of its quad's corner texel."""
+    uvs = np.empty((int(atlas.triangles), 3, 2), np.float32)
+    rc = load_library().sdfr_atlas_uvs(ctypes.byref(atlas), uvs.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise SdfrError(rc, "sdfr_atlas_uvs")
+    return uvs
 
 
 def check_scene_source(source, arch="gfx950"):
@@ -724,7 +768,7 @@ class SDFRenderer:
 
     # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
     def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None, occlusion=False, ao_radius=None,
-                    ao_bias=None, lighting=False):
+                    ao_bias=None, lighting=False, atlas=None):
         """Surface nets over the lattice origin + (i, j, k) * cell, dims = (nx, ny, nz) cells: (positions [v, 3] float32, normals [v, 3]
         float32 or None, indices [t, 3]) -- numpy arrays (indices uint32), or with device=True torch tensors on the renderer's GPU
         (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call.
@@ -732,11 +776,30 @@ class SDFRenderer:
         the mesh is made on the GPU and looked at there, whatever `device` says about where the results go.
         occlusion=True: one more element, after the surfaces if both are asked for: the ambient occlusion at every vertex
         (queryOcclusion with ao_bias, default 1 cell, and ao_radius, default 8 cells; needs the normals), looked at on the GPU likewise.
-        lighting=True: one more element, the last: the direct lighting at every vertex (meshLighting with `reach`; needs the normals)."""
-        if surfaces or occlusion or lighting:
+        lighting=True: one more element, the last: the direct lighting at every vertex (meshLighting with `reach`; needs the normals).
+        atlas=dict(tile=8, width=None, layers=("albedo",), occlusion=False): one more element after all of those: the mesh's texture atlas
+        baked with `reach` -- bakeAtlas's dict with "uvs" [t, 3, 2] added (atlasUVs), and with occlusion=True an "openness" plane [H, W]
+        (atlasTexels + queryOcclusion with ao_bias and ao_radius: 1 - occluded / 64 where that is answered, else 0)."""
+        if surfaces or occlusion or lighting or atlas is not None:
             if not normals:
-                raise ValueError("surfaces=True, occlusion=True and lighting=True need the normals")
+                raise ValueError("surfaces=True, occlusion=True, lighting=True and atlas need the normals")
             pos, nrm, idx = self.extractMesh(origin, cell, dims, iso, True, device=True)
+            baked = None
+            if atlas is not None:
+                unknown = set(atlas) - {"tile", "width", "layers", "occlusion"}
+                if unknown:
+                    raise ValueError("atlas: unknown keys %s" % sorted(unknown))
+                tile, width = atlas.get("tile", 8), atlas.get("width")
+                baked = self.bakeAtlas(pos, nrm, idx, tile, width, 2.0 * float(cell) if reach is None else reach, atlas.get("layers", ("albedo",)))
+                baked["uvs"] = atlasUVs(baked["atlas"])
+                if atlas.get("occlusion"):
+                    import torch
+
+                    _a, tp, tn, tv = self.atlasTexels(pos, nrm, idx, tile, baked["atlas"].width)
+                    ao = self.queryOcclusion(tp.reshape(-1, 3), tn.reshape(-1, 3), float(cell) if ao_bias is None else ao_bias,
+                                             8.0 * float(cell) if ao_radius is None else ao_radius)
+                    answered = (ao[:, 3] == 1) & (tv.reshape(-1) == 1)
+                    baked["openness"] = torch.where(answered, 1.0 - ao[:, 2].to(torch.float32) / 64.0, torch.zeros((), device=ao.device)).reshape(tv.shape)
             extra = []
             if surfaces:
                 extra.append(self.meshSurfaces(pos, nrm, 2.0 * float(cell) if reach is None else reach))
@@ -745,8 +808,10 @@ class SDFRenderer:
             if lighting:
                 extra.append(self.meshLighting(pos, nrm, 2.0 * float(cell) if reach is None else reach))
             if device:
-                return (pos, nrm, idx) + tuple(extra)
+                return (pos, nrm, idx) + tuple(extra) + ((baked,) if baked is not None else ())
             self.sync()
+            if baked is not None:
+                baked = {k: (a.cpu().numpy() if hasattr(a, "data_ptr") else a) for k, a in baked.items()}
             if surfaces:
                 extra[0] = extra[0].cpu().numpy().view(np.uint32).reshape(-1).view(SURFACE_DTYPE)
             if occlusion:
@@ -754,7 +819,7 @@ class SDFRenderer:
                 extra[k] = extra[k].cpu().numpy().view(np.uint32).reshape(-1).view(OCCLUSION_DTYPE)
             if lighting:
                 extra[-1] = extra[-1].cpu().numpy().view(np.uint32).reshape(-1).view(LIGHTING_DTYPE)
-            return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32)) + tuple(extra)
+            return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32)) + tuple(extra) + ((baked,) if baked is not None else ())
         grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
         counts = MeshCounts()
         self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), 0 if device else 1))
@@ -778,6 +843,83 @@ class SDFRenderer:
             if (again.vertices, again.triangles) != (v, t):
                 raise SdfrError(-9, "the mesh changed between the counting and the filling call")
         return pos, nrm, idx
+
+    # ---- the texture atlas of a mesh (sdfr_atlas_texels / sdfr_atlas_bake; DESIGN.md "Texture atlas") -------------------------------
+    def _atlas_inputs(self, positions, normals, indices, device):
+        """-> (vertex count, triangle count, pointers, on_host, the torch device or None)"""
+        if hasattr(positions, "data_ptr") or device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            as_dev = lambda a, dt: a if hasattr(a, "data_ptr") else torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)  # noqa: E731
+            pos, nrm = as_dev(positions, np.float32).reshape(-1, 3), as_dev(normals, np.float32).reshape(-1, 3)
+            idx = indices if hasattr(indices, "data_ptr") else torch.from_numpy(np.ascontiguousarray(indices, np.uint32).view(np.int32)).to(dev)
+            idx = idx.reshape(-1, 3)
+            v, t = pos.shape[0], idx.shape[0]
+            ptrs = [self._dev(pos, 3 * v, "positions") if v else None, self._dev(nrm, 3 * v, "normals") if v else None,
+                    self._dev(idx, 3 * t, "indices", ints=True) if t else None]
+            return v, t, ptrs, 0, dev, (pos, nrm, idx)
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+        if nrm.shape != pos.shape:
+            raise ValueError("positions and normals differ in shape")
+        return pos.shape[0], idx.shape[0], [a.ctypes.data_as(ctypes.c_void_p) for a in (pos, nrm, idx)], 1, None, (pos, nrm, idx)
+
+    @staticmethod
+    def _atlas_plane(shape, dev, ints=False):
+        if dev is None:
+            a = np.empty(shape, np.int32 if ints else np.float32)
+            return a, a.ctypes.data_as(ctypes.c_void_p)
+        import torch
+
+        a = torch.empty(shape, dtype=torch.int32 if ints else torch.float32, device=dev)
+        return a, ctypes.c_void_p(a.data_ptr())
+
+    def atlasTexels(self, positions, normals, indices, tile=8, width=None, device=False):
+        """The surface point and unit normal of every texel of the mesh's atlas (sdfr_atlas_texels): (atlas, positions [H, W, 3],
+        normals [H, W, 3], valid [H, W] int32 -- 1, 0 for a degenerate texel, -1 for a texel of no well-formed quad, zeros there).
+        numpy arrays, or torch tensors on the renderer's GPU with device tensors in or device=True.  Needs no scene."""
+        v, t, ptrs, on_host, dev, keep = self._atlas_inputs(positions, normals, indices, device)
+        atlas = atlasLayout(t, tile, width)
+        h, w = atlas.height, atlas.width
+        P, pp = self._atlas_plane((h, w, 3), dev)
+        N, pn = self._atlas_plane((h, w, 3), dev)
+        valid, pv = self._atlas_plane((h, w), dev, True)
+        self._check(self._L.sdfr_atlas_texels(self._h, ctypes.byref(atlas), v, ptrs[0], ptrs[1], ptrs[2], pp, pn, pv, on_host))
+        if dev is not None and not device and not hasattr(positions, "data_ptr"):
+            self.sync()
+            P, N, valid = P.cpu().numpy(), N.cpu().numpy(), valid.cpu().numpy()
+        return atlas, P, N, valid
+
+    def bakeAtlas(self, positions, normals, indices, tile=8, width=None, reach=None, layers=("albedo",), device=False):
+        """Bake the loaded scene's surface into the mesh's atlas (sdfr_atlas_bake): every texel is looked at as meshSurfaces /
+        meshLighting look at a vertex, from `reach` outside it along its normal.  layers: any of "albedo" (rgb + alpha), "normal"
+        (the shading normal, 0) and "lit" (the direct lighting, 1).  -> {"atlas": Atlas, "valid": [H, W] int32 (1 hit, 0 miss or
+        degenerate, -1 no quad), and one [H, W, 4] float32 plane per layer}: numpy arrays, or torch tensors on the renderer's GPU
+        with device tensors in or device=True (enqueued on the handle's stream)."""
+        if reach is None:
+            raise ValueError("bakeAtlas needs a reach (a cell or two of the mesh's lattice)")
+        layers = (layers,) if isinstance(layers, str) else tuple(layers)
+        mask = 0
+        for name in layers:
+            if name not in ATLAS_LAYERS:
+                raise ValueError("unknown atlas layer %r: one of %s" % (name, ", ".join(sorted(ATLAS_LAYERS))))
+            mask |= ATLAS_LAYERS[name]
+        v, t, ptrs, on_host, dev, keep = self._atlas_inputs(positions, normals, indices, device)
+        atlas = atlasLayout(t, tile, width)
+        h, w = atlas.height, atlas.width
+        out, pl = {"atlas": atlas}, {}
+        for name in ("albedo", "normal", "lit"):
+            out[name], pl[name] = self._atlas_plane((h, w, 4), dev) if name in layers else (None, None)
+        out["valid"], pv = self._atlas_plane((h, w), dev, True)
+        self._check(self._L.sdfr_atlas_bake(self._h, ctypes.byref(atlas), v, ptrs[0], ptrs[1], ptrs[2], float(reach), mask, pl["albedo"], pl["normal"],
+                                            pl["lit"], pv, on_host))
+        out = {k: a for k, a in out.items() if a is not None}
+        if dev is not None and not device and not hasattr(positions, "data_ptr"):
+            self.sync()
+            out = {k: (a if k == "atlas" else a.cpu().numpy()) for k, a in out.items()}
+        return out
 
     def getMeshTimings(self):
         """GPU ms of the last extractMesh's filling call, if setProfiling(True) was on: {sample, classify_scan, emit, normals}."""

@@ -132,6 +132,11 @@ def make_parser():
     ap.add_argument("--gbuffer-ao", type=float, metavar="RADIUS", help="with --gbuffer: add `ao`, the ambient openness within RADIUS at every pixel's hit")
     ap.add_argument("--mesh-lit", action="store_true", help="with --mesh: a colour per vertex, from the scene's lights as the renderer shades a hit "
                     "(instead of --mesh-colors / --mesh-ao)")
+    ap.add_argument("--mesh-atlas", metavar="OUT.png", help="with --mesh: bake the surface into a texture atlas, one square tile of texels per quad: "
+                    "writes the image, a material library beside the OBJ, and the OBJ with texture coordinates")
+    ap.add_argument("--atlas-tile", type=int, choices=(4, 8, 16, 32), default=8, metavar="T", help="texels per tile edge: 4, 8, 16 or 32 (default 8)")
+    ap.add_argument("--atlas-width", type=int, metavar="W", help="width of the atlas, a multiple of 8 and of the tile (default: a square-ish image)")
+    ap.add_argument("--atlas-layer", choices=("albedo", "lit", "normal"), default="albedo", help="what the atlas holds (default albedo)")
     ap.add_argument("--gbuffer-lighting", action="store_true", help="with --gbuffer: add `lit`, `own`, `direct` and the used, traced and visible light masks")
     return ap
 
@@ -199,6 +204,11 @@ def main(argv=None):
     if a.mesh:
         if a.mesh_box is None or a.mesh_cell is None:
             ap.error("--mesh needs --mesh-box and --mesh-cell")
+        if a.mesh_atlas and a.atlas_width is not None and (a.atlas_width < 8 or a.atlas_width > 16384 or a.atlas_width % 8 or a.atlas_width % a.atlas_tile):
+            ap.error("--atlas-width must be a multiple of 8 and of --atlas-tile, at most 16384")
+    elif a.mesh_atlas:
+        ap.error("--mesh-atlas needs --mesh")
+    if a.mesh:
         try:
             mesh_grid = mesh_grid_from_box(a.mesh_box, a.mesh_cell)
         except ValueError as e:
@@ -241,12 +251,15 @@ def main(argv=None):
 
         colors = None
         ao = dict(occlusion=True, ao_radius=a.mesh_ao) if a.mesh_ao is not None else {}
+        baked = None
+        if a.mesh_atlas:
+            ao["atlas"] = dict(tile=a.atlas_tile, width=a.atlas_width, layers=(a.atlas_layer,))
         if a.mesh_lit:
             from .obj import lighting_colors
 
-            pos, nrm, idx, lighting = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, lighting=True)
+            ao.pop("occlusion", None), ao.pop("ao_radius", None)
+            pos, nrm, idx, lighting, *occ = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, lighting=True, **ao)
             colors, missing = lighting_colors(lighting)
-            occ = []
         elif a.mesh_colors:
             from .obj import surface_colors
 
@@ -254,13 +267,34 @@ def main(argv=None):
             colors, missing = surface_colors(srf)
         else:
             pos, nrm, idx, *occ = r.extractMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, **ao)
+        if a.mesh_atlas:
+            baked = occ.pop()
         if occ:
             from .obj import occlusion_colors
 
             colors_written = occlusion_colors(occ[0], colors)
         else:
             colors_written = colors
-        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso), colors=colors_written)
+        uvs = mtl = None
+        if baked is not None:
+            import os
+
+            from .obj import atlas_rgba8, write_mtl
+
+            plane = baked[a.atlas_layer]
+            if a.atlas_layer == "normal":
+                plane = plane * np.float32(0.5) + np.float32(0.5)
+            image = atlas_rgba8(plane, baked["valid"])
+            write_png(a.mesh_atlas, image)
+            mtl = os.path.splitext(a.mesh)[0] + ".mtl"
+            write_mtl(mtl, os.path.relpath(os.path.abspath(a.mesh_atlas), os.path.dirname(os.path.abspath(mtl))))
+            uvs = baked["uvs"]
+        write_obj(a.mesh, pos, nrm, idx, comment="%s, time %g, cell %g, iso %g" % (a.scene, a.time, a.mesh_cell, a.mesh_iso), colors=colors_written,
+                  uvs=uvs, material="atlas" if mtl else None, mtllib=os.path.basename(mtl) if mtl else None)
+        if baked is not None:
+            at, tiles = baked["atlas"], baked["valid"] != -1
+            print("atlas %s: %dx%d, %d tiles of %dx%d texels, %d of %d tile texels found no surface -> %s, %s" % (
+                a.atlas_layer, at.width, at.height, at.quads, at.tile, at.tile, int((baked["valid"] == 0).sum()), int(tiles.sum()), a.mesh_atlas, mtl))
         print("%s: %d vertices, %d triangles (%dx%dx%d cells) -> %s" % ((a.scene, len(pos), len(idx)) + mesh_grid[1] + (a.mesh,)))
         if colors is not None:
             print("%d of %d vertices found no surface within 2 cells and are grey" % (missing, len(pos)))

@@ -4,6 +4,7 @@
 // preparation, device buffers and launches.  All pixels are produced by the HIP kernels in
 // sdfr_kernels.hip; there is no CPU rendering path.
 #include "sdfr_aa_plan.h"
+#include "sdfr_atlas_plan.h"
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
 #include "sdfr_mesh.h"
@@ -1043,6 +1044,132 @@ int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
 			ms[k] = t;
 		}
 		return SDFR_OK;
+	});
+}
+
+// ---- the texture atlas of a mesh (the definition: include/sdfr.h; the plan: sdfr_atlas_plan.h; the texel map and the bake: sdfr_atlas.h).
+// sdfr_atlas_texels looks at the mesh alone and needs no scene; sdfr_atlas_bake is a query: the frame is latched into a copy and nothing
+// a render uses or reports is written.  A host call stages three inputs and up to four answers in the handle's query buffer, cut here
+// (stage_offsets) because a Carving holds six pieces.
+static_assert(sizeof(sdfr_atlas) == sizeof(AtlasLayout) && offsetof(sdfr_atlas, tile) == offsetof(AtlasLayout, tile) && offsetof(sdfr_atlas, rows) == offsetof(AtlasLayout, rows),
+	"sdfr_atlas is the plan's AtlasLayout");
+static_assert(SDFR_ATLAS_ALBEDO == ATLAS_ALBEDO && SDFR_ATLAS_NORMAL == ATLAS_NORMAL && SDFR_ATLAS_LIT == ATLAS_LIT, "the layer bits are the kernel's");
+static const AtlasLayout *layout_of(const sdfr_atlas *a) { return reinterpret_cast<const AtlasLayout *>(a); }
+
+int sdfr_atlas_layout(int64_t triangles, int tile, int width, sdfr_atlas *out)
+{
+	AtlasLayout l;
+	if (!out || !atlas_layout(triangles, tile, width, l)) return SDFR_ERR_INVALID_ARGUMENT;
+	memcpy(out, &l, sizeof l);
+	return SDFR_OK;
+}
+
+int sdfr_atlas_uvs(const sdfr_atlas *atlas, float *uvs)
+{
+	if (!atlas || !atlas_layout_ok(*layout_of(atlas)) || (atlas->triangles > 0 && !uvs)) return SDFR_ERR_INVALID_ARGUMENT;
+	atlas_uvs(*layout_of(atlas), uvs);
+	return SDFR_OK;
+}
+
+static int atlas_impl(sdfr_renderer *r, const AtlasRequest &c)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	const AtlasPlan p = plan_atlas(c);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	if (p.needs_scene && r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
+	SDFR_HIP(hipSetDevice(r->device));
+	hipStream_t stream = r->lane.stream; // as the queries
+
+	AtlasArgs g = p.a;
+	struct { void *host; const void *device; size_t bytes; } answers[4];
+	int n_answers = 0;
+	if (c.on_host)
+	{
+		size_t offset[ATLAS_STAGE_PIECES];
+		SDFR_HIP(r->query.reserve(stage_offsets(p.bytes, ATLAS_STAGE_PIECES, offset))); // (host calls are synchronous: none is using the old one)
+		char *base = static_cast<char *>(r->query.ptr);
+		auto piece = [&](int k) -> void * { return p.bytes[k] ? base + offset[k] : nullptr; };
+		const void *in[3] = {p.a.positions, p.a.normals, p.a.indices};
+		for (int k = 0; k < 3; ++k)
+			if (p.bytes[k]) SDFR_HIP(hipMemcpyAsync(piece(k), in[k], p.bytes[k], hipMemcpyHostToDevice, stream));
+		g.positions = static_cast<const float *>(piece(0));
+		g.normals = static_cast<const float *>(piece(1));
+		g.indices = static_cast<const uint32_t *>(piece(2));
+		void *out[4] = {c.bake ? (void *)p.a.albedo : (void *)p.a.texel_positions, c.bake ? (void *)p.a.normal : (void *)p.a.texel_normals,
+			c.bake ? (void *)p.a.lit : (void *)p.a.valid, c.bake ? (void *)p.a.valid : nullptr};
+		for (int k = 0; k < 4; ++k)
+			if (p.bytes[3 + k]) answers[n_answers++] = {out[k], piece(3 + k), p.bytes[3 + k]};
+		if (c.bake)
+		{
+			g.albedo = static_cast<float *>(piece(3));
+			g.normal = static_cast<float *>(piece(4));
+			g.lit = static_cast<float *>(piece(5));
+			g.valid = static_cast<int32_t *>(piece(6));
+		}
+		else
+		{
+			g.texel_positions = static_cast<float *>(piece(3));
+			g.texel_normals = static_cast<float *>(piece(4));
+			g.valid = static_cast<int32_t *>(piece(5));
+		}
+	}
+	if (p.needs_scene)
+	{
+		FrameU U = r->U;
+		int rc = latch_into(r, U, 1, 1, stream);
+		if (rc != SDFR_OK) return rc;
+		KernelRef k;
+		rc = loaded_query_kernel(r, QUERY_KERNEL_ATLAS, U, k);
+		if (rc != SDFR_OK) return rc;
+		const hipError_t e = launch_atlas_bake(k, U, g, p.blocks, stream);
+		if (e != hipSuccess) return hip_fail(r, e, "atlas launch");
+	}
+	else
+		SDFR_HIP(launch_atlas_texels(g, p.blocks, stream));
+	if (!c.on_host) return SDFR_OK;
+	for (int k = 0; k < n_answers; ++k) SDFR_HIP(hipMemcpyAsync(answers[k].host, answers[k].device, answers[k].bytes, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+	if (r->query.bytes > k_query_stage_keep) r->query.release();
+	return SDFR_OK;
+}
+
+int sdfr_atlas_texels(sdfr_renderer *r, const sdfr_atlas *atlas, int64_t vertex_count, const float *positions, const float *normals, const uint32_t *indices,
+	float *texel_positions, float *texel_normals, int32_t *valid, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		AtlasRequest c = {};
+		c.atlas = layout_of(atlas);
+		c.vertex_count = vertex_count;
+		c.a.positions = positions;
+		c.a.normals = normals;
+		c.a.indices = indices;
+		c.a.texel_positions = texel_positions;
+		c.a.texel_normals = texel_normals;
+		c.a.valid = valid;
+		c.on_host = on_host;
+		return atlas_impl(r, c);
+	});
+}
+
+int sdfr_atlas_bake(sdfr_renderer *r, const sdfr_atlas *atlas, int64_t vertex_count, const float *positions, const float *normals, const uint32_t *indices,
+	float reach, uint32_t layers, float *albedo, float *normal, float *lit, int32_t *valid, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		AtlasRequest c = {};
+		c.atlas = layout_of(atlas);
+		c.vertex_count = vertex_count;
+		c.a.positions = positions;
+		c.a.normals = normals;
+		c.a.indices = indices;
+		c.a.reach = reach;
+		c.a.layers = layers;
+		c.a.albedo = albedo;
+		c.a.normal = normal;
+		c.a.lit = lit;
+		c.a.valid = valid;
+		c.bake = true;
+		c.on_host = on_host;
+		return atlas_impl(r, c);
 	});
 }
 

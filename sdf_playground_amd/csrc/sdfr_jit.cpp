@@ -85,6 +85,7 @@ const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_
 	{"sdfr_jit_query_surfaces", "query_surfaces_kernel", "QueryKernelArgs"},
 	{"sdfr_jit_query_occlusion", "query_occlusion_kernel", "QueryKernelArgs"},
 	{"sdfr_jit_query_lighting", "query_lighting_kernel", "QueryKernelArgs"},
+	{"sdfr_jit_bake_atlas", "atlas_bake_kernel", "AtlasKernelArgs"},
 };
 
 } // namespace

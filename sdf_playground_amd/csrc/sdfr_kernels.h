@@ -80,6 +80,12 @@ hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *
 hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
 	uint32_t *indices, hipStream_t stream);
 
+// The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
+// per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes
+// instead the image of a bake without quads.  launch_atlas_bake: a scene's bake kernel (QUERY_KERNEL_ATLAS) for U.
+hipError_t launch_atlas_texels(const AtlasArgs &g, uint32_t blocks, hipStream_t stream);
+hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream);
+
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,
 	int priv_period, hipStream_t stream);
 

@@ -497,6 +497,15 @@ hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const Latti
 	return launch_kernel(k, query_lattice_blocks(g), SDFR_PIXEL_BLOCK, args, stream);
 }
 
+hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
+{
+	AtlasKernelArgs a;
+	a.U = U;
+	a.g = g;
+	void *args[] = {&a};
+	return launch_kernel(k, blocks, QUERY_BLOCK_ITEMS, args, stream);
+}
+
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,
 	int priv_period, hipStream_t stream)
 {

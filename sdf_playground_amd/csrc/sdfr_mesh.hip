@@ -1,4 +1,5 @@
-// sdfr_mesh.hip -- the scene-independent kernels of sdfr_mesh_extract (stage functions: sdfr_mesh.h): classify cells and lattice
+// sdfr_mesh.hip -- the scene-independent kernels of sdfr_mesh_extract (stage functions: sdfr_mesh.h) and of the mesh's texture atlas
+// (k_atlas_texels, at the end; sdfr_atlas.h): classify cells and lattice
 // points, exclusive prefix sums of the two flag arrays, emit vertices, emit indices.  The distances they read come from the
 // scene's lattice kernel (sdfr_query_kernel.h: query_lattice_kernel).
 //
@@ -7,6 +8,8 @@
 // the phases are separate launches of one stream.  The output order (cells and lattice points by linear index) is the scan's.
 #include "sdfr_kernels.h"
 #include "sdfr_mesh.h"
+#define SDFR_ATLAS_GEOMETRY_ONLY // the texel map alone: no scene is looked at here
+#include "sdfr_atlas.h"
 
 namespace sdfr {
 
@@ -159,6 +162,50 @@ hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint3
 	if (indices)
 		hipLaunchKernelGGL(k_mesh_emit_indices, dim3((points + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice,
 			cell_vertex, point_quad, indices);
+	return hipGetLastError();
+}
+
+// ---- the texels of a mesh's texture atlas (sdfr_atlas_texels; the map: sdfr_atlas.h) ----
+// One wave per block and one texel per lane, an 8 x 8 square of the image per wave as in the bake kernel (sdfr_query_kernel.h): the
+// quad of a tile of 8 texels and more is addressed by the block index alone and read once for the wave.  Every texel of the image is
+// written: state 1 with its point and unit normal, 0 (degenerate) or -1 (no well-formed quad) with zeros.  With the planes of a bake
+// instead of the two texel arrays (a bake of a mesh without quads, which needs no scene): -1 and zeros.
+__global__ __launch_bounds__(64) void k_atlas_texels(AtlasArgs g)
+{
+	const uint32_t lane = threadIdx.x;
+	const uint32_t blocks_x = (uint32_t)g.width >> 3;
+	const uint32_t by = blockIdx.x / blocks_x, bx = blockIdx.x - by * blocks_x;
+	const uint32_t x = bx * 8u + (lane & 7u), y = by * 8u + (lane >> 3);
+	if (x >= (uint32_t)g.width || y >= (uint32_t)g.height) return; // (never: both are multiples of 8 and the grid covers them exactly)
+	const uint32_t T = 1u << g.tile_log2;
+	AtlasQuad Q;
+	if (g.tile_log2 >= 3) Q = atlas_load_quad(g, atlas_tile_of(g, bx * 8u, by * 8u)); // wave-uniform
+	else Q = atlas_load_quad(g, atlas_tile_of(g, x, y));
+	vec3 P, N;
+	const int state = atlas_texel(Q, x & (T - 1u), y & (T - 1u), T, P, N);
+	const size_t i = (size_t)y * (uint32_t)g.width + x;
+	g.valid[i] = state;
+	if (g.texel_positions)
+	{
+		float *p = g.texel_positions + 3 * i, *n = g.texel_normals + 3 * i;
+		p[0] = P.x;
+		p[1] = P.y;
+		p[2] = P.z;
+		n[0] = N.x;
+		n[1] = N.y;
+		n[2] = N.z;
+	}
+	for (float *plane : {g.albedo, g.normal, g.lit})
+		if (plane)
+		{
+			float *o = plane + 4 * i;
+			o[0] = o[1] = o[2] = o[3] = 0.f;
+		}
+}
+
+hipError_t launch_atlas_texels(const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
+{
+	hipLaunchKernelGGL(k_atlas_texels, dim3(blocks), dim3(64), 0, stream, g);
 	return hipGetLastError();
 }
 

@@ -25,6 +25,13 @@ struct LatticeKernelArgs
 	LatticeArgs g;
 };
 
+// ... and the atlas bake kernel (AtlasArgs: sdfr_query_args.h)
+struct AtlasKernelArgs
+{
+	FrameU U;
+	AtlasArgs g;
+};
+
 // map_geometry at the sample of a query: a scene that reads the march state (GeoStep) gets the running camera_distance and
 // the ray's offsets, every other scene (p, dir) as in the pixel pipeline
 template <class Scene, bool DBG>

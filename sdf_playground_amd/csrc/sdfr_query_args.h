@@ -39,7 +39,7 @@ static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offseto
 static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
 // A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_KINDS = 6 };
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_KINDS = 7 };
 
 // One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
@@ -51,6 +51,25 @@ struct LatticeArgs
 	int32_t px, py, pz; // lattice points per axis
 	int32_t rows;       // 0: a wave owns a 4 x 4 x 4 brick of points; 1: 64 consecutive points of a row (the A/B of DESIGN.md 4.6)
 	float *out;
+};
+
+// One atlas launch (sdfr_atlas.h, sdfr_atlas_plan.h; sdfr_atlas_texels and sdfr_atlas_bake): the texels of a width x height image cut into
+// square tiles of 1 << tile_log2 texels, tile q = row * tiles_per_row + col the quad of triangles 2q and 2q + 1 of `indices`.  A wave
+// takes an 8 x 8 square of the image.  The scene-free kernel (k_atlas_texels) writes texel_positions, texel_normals and valid; the bake
+// kernel writes the planes of `layers` that are there, and valid.
+enum { ATLAS_ALBEDO = 1u, ATLAS_NORMAL = 2u, ATLAS_LIT = 4u, ATLAS_LAYERS = 7u }; // SDFR_ATLAS_*
+struct AtlasArgs
+{
+	const float *positions, *normals; // [vertex_count][3]
+	const uint32_t *indices;          // [2 * quads][3]
+	uint32_t vertex_count, quads;
+	int32_t tile_log2, tiles_per_row;
+	int32_t width, height; // multiples of 8; width * height <= 2^30
+	float reach;
+	uint32_t layers;
+	float *albedo, *normal, *lit; // [height * width][4] each, or null
+	int32_t *valid;               // [height * width]
+	float *texel_positions, *texel_normals; // [height * width][3] each
 };
 
 } // namespace sdfr

@@ -10,6 +10,7 @@
 #include "sdfr_surface.h"
 #include "sdfr_occlusion.h"
 #include "sdfr_lighting.h"
+#include "sdfr_atlas.h"
 
 namespace sdfr {
 
@@ -255,6 +256,39 @@ __device__ __forceinline__ void query_lattice_kernel(const LatticeKernelArgs &a)
 	if (i >= px || j >= py || k >= pz) return;
 	const vec3 p = V3(g.origin[0] + (float)i * g.cell, g.origin[1] + (float)j * g.cell, g.origin[2] + (float)k * g.cell);
 	g.out[i + px * (j + py * k)] = query_point<Scene, DBG>(a.U, p, nullptr); // (the index is < 2^30)
+}
+
+// The atlas bake (sdfr_atlas.h): one wave per block, one texel per lane; a wave takes an 8 x 8 square of the IMAGE -- one quad's tile at
+// T = 8, four at T = 4, part of one at T = 16 and 32.  Each lane makes its texel's ray from the mesh arrays: from a tile of 8 texels
+// and more the quad is addressed by the block index alone, so its six indices and four vertices are read once for the wave (scalar
+// loads); at T = 4 a lane addresses its own.  A texel that is invalid or degenerate is not marched.  Every plane that is asked for
+// leaves as one 16-byte store per lane -- a wave's row of 8 texels is 128 contiguous bytes -- and `valid` as one word, at every texel
+// of the image.  Nothing here is shared with the kernels above: their code stays as it was.
+template <class Scene, bool DBG>
+__device__ __forceinline__ void atlas_bake_kernel(const AtlasKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: 8 x 8 texels");
+	const FrameU &U = a.U;
+	const AtlasArgs &g = a.g;
+	const uint32_t lane = threadIdx.x;
+	const uint32_t blocks_x = (uint32_t)g.width >> 3;
+	const uint32_t by = blockIdx.x / blocks_x, bx = blockIdx.x - by * blocks_x;
+	const uint32_t x = bx * 8u + (lane & 7u), y = by * 8u + (lane >> 3);
+	if (x >= (uint32_t)g.width || y >= (uint32_t)g.height) return; // (never: both are multiples of 8 and the grid covers them exactly)
+	const uint32_t T = 1u << g.tile_log2;
+	AtlasQuad Q;
+	if (g.tile_log2 >= 3) Q = atlas_load_quad(g, atlas_tile_of(g, bx * 8u, by * 8u)); // wave-uniform
+	else Q = atlas_load_quad(g, atlas_tile_of(g, x, y));
+	vec3 P, N;
+	const int state = atlas_texel(Q, x & (T - 1u), y & (T - 1u), T, P, N);
+	uint32_t albedo[4] = {0u, 0u, 0u, 0u}, normal[4] = {0u, 0u, 0u, 0u}, lit[4] = {0u, 0u, 0u, 0u};
+	uint32_t valid = (uint32_t)state;
+	if (state == ATLAS_TEXEL_VALID) valid = atlas_bake_texel<Scene, DBG>(U, P, N, g.reach, g.layers, albedo, normal, lit);
+	const uint32_t i = y * (uint32_t)g.width + x; // < width * height <= 2^30
+	if (g.albedo) query_store(reinterpret_cast<uint32_t *>(g.albedo), i, albedo);
+	if (g.normal) query_store(reinterpret_cast<uint32_t *>(g.normal), i, normal);
+	if (g.lit) query_store(reinterpret_cast<uint32_t *>(g.lit), i, lit);
+	g.valid[i] = (int32_t)valid;
 }
 
 } // namespace sdfr

@@ -1,4 +1,4 @@
-// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice, k_query_surfaces, k_query_occlusion, k_query_lighting: sdfr_query_kernel.h) of ONE scene, compiled
+// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice, k_query_surfaces, k_query_occlusion, k_query_lighting, k_bake_atlas: sdfr_query_kernel.h) of ONE scene, compiled
 // once per scene with -DSDFR_SCENE=<index> and the scene's code-generation options (sdf_playground_amd/buildlib.py), like
 // sdfr_kernels_scene.hip.  They live in a unit of their own: a second caller of the shared inline stages in the pixel kernels'
 // unit could change the inliner's decisions there, and with them k_pixel's code.
@@ -59,6 +59,13 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_lighting(QueryKernelArgs 
 	query_lighting_kernel<Scene, DBG>(a);
 }
 
+// the atlas bake: a texel of a mesh's texture atlas per lane (sdfr_atlas.h)
+template <class Scene, bool DBG>
+__global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_bake_atlas(AtlasKernelArgs a)
+{
+	atlas_bake_kernel<Scene, DBG>(a);
+}
+
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
 // what this unit exports (scene_query_kernels, launch_query: sdfr_kernels.hip)
@@ -79,6 +86,8 @@ const QueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
 		q.k[QUERY_KERNEL_OCCLUSION][0].kernel = (const void *)k_query_occlusion<UnitScene, false>;
 		q.k[QUERY_KERNEL_LIGHTING][1].kernel = (const void *)k_query_lighting<UnitScene, true>;
 		q.k[QUERY_KERNEL_LIGHTING][0].kernel = (const void *)k_query_lighting<UnitScene, false>;
+		q.k[QUERY_KERNEL_ATLAS][1].kernel = (const void *)k_bake_atlas<UnitScene, true>;
+		q.k[QUERY_KERNEL_ATLAS][0].kernel = (const void *)k_bake_atlas<UnitScene, false>;
 		return q;
 	}();
 	return &k;

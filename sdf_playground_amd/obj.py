@@ -1,4 +1,5 @@
-"""A small Wavefront OBJ writer for the meshes of SDFRenderer.extractMesh: `v`, `vn` and `f` lines with 1-based indices."""
+"""A small Wavefront OBJ writer for the meshes of SDFRenderer.extractMesh: `v`, `vn` and `f` lines with 1-based indices; with the UVs
+of a texture atlas (extractMesh(atlas=...)) also `vt` lines, a material library and the atlas as an RGBA8 image."""
 
 MISSING_COLOR = (0.5, 0.5, 0.5)  # a vertex under which no surface was found (surface_colors)
 
@@ -49,14 +50,42 @@ def lighting_colors(lighting):
     return rgb, int(missing.sum())
 
 
-def write_obj(out, positions, normals, indices, comment=None, colors=None):
+def atlas_rgba8(plane, valid):
+    """An atlas plane [H, W, 3 or 4] float32 (bakeAtlas) as an RGBA8 image [H, W, 4] uint8: rgb clipped to [0, 1] (a NaN becomes 0) as
+    surface_colors does, times 255 and rounded; alpha 255.  MISSING_COLOR where valid == 0 (a texel of a quad under which no surface
+    was found); alpha 0, and black, where valid == -1 (a texel of no quad)."""
+    import numpy as np
+
+    plane, valid = np.asarray(plane, np.float32), np.asarray(valid)
+    rgb = np.clip(np.nan_to_num(plane[..., :3], nan=0.0), 0.0, 1.0)
+    rgb = np.where((valid == 0)[..., None], np.array(MISSING_COLOR, np.float32), rgb)
+    out = np.empty(valid.shape + (4,), np.uint8)
+    out[..., :3] = np.floor(rgb * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)
+    out[..., 3] = 255
+    out[valid == -1] = 0
+    return out
+
+
+def write_mtl(path, texture, name="atlas"):
+    """Writes a material library with one material `name` whose diffuse map is the image file `texture` (a name relative to the
+    library's directory)."""
+    with open(path, "w") as f:
+        f.write("newmtl %s\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s\n" % (name, texture))
+
+
+def write_obj(out, positions, normals, indices, comment=None, colors=None, uvs=None, material=None, mtllib=None):
     """Writes the mesh to `out` (a path or a text file object): one `v x y z` per vertex -- `v x y z r g b` with `colors` [v, 3], the
     per-vertex colour extension most tools read --, one `vn x y z` per vertex if `normals` is given, one `f a//a b//b c//c`
     (`f a b c` without normals) per triangle.  Floats are written with %.9g, which reads back to the same fp32 value.
-    positions / normals [v, 3], indices [t, 3] (0-based, as extractMesh returns them)."""
+    positions / normals [v, 3], indices [t, 3] (0-based, as extractMesh returns them).
+    uvs [t, 3, 2] (atlasUVs: origin top-left): one `vt u (1 - v)` per triangle corner -- OBJ's origin is bottom-left; 1 - v is written in full, so that 1 - it reads back to v --, and faces
+    `f a/ta/a b/tb/b c/tc/c` (`f a/ta b/tb c/tc` without normals).  material: a `usemtl` line before the faces, and with mtllib (the
+    library's file name, write_mtl) a `mtllib` line at the top.  With uvs=None and no material the file is what it always was."""
     if isinstance(out, (str, bytes)) or hasattr(out, "__fspath__"):
         with open(out, "w") as f:
-            return write_obj(f, positions, normals, indices, comment, colors)
+            return write_obj(f, positions, normals, indices, comment, colors, uvs, material, mtllib)
+    if uvs is not None and len(uvs) != len(indices):
+        raise ValueError("%d triangles of UVs for %d triangles" % (len(uvs), len(indices)))
     if normals is not None and len(normals) != len(positions):
         raise ValueError("%d normals for %d vertices" % (len(normals), len(positions)))
     if colors is not None and len(colors) != len(positions):
@@ -64,6 +93,8 @@ def write_obj(out, positions, normals, indices, comment=None, colors=None):
     if comment:
         for line in str(comment).splitlines():
             out.write("# %s\n" % line)
+    if material and mtllib:
+        out.write("mtllib %s\n" % mtllib)
     if colors is not None:
         for p, c in zip(positions, colors):
             out.write("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (float(p[0]), float(p[1]), float(p[2]), float(c[0]), float(c[1]), float(c[2])))
@@ -73,8 +104,17 @@ def write_obj(out, positions, normals, indices, comment=None, colors=None):
     if normals is not None:
         for n in normals:
             out.write("vn %.9g %.9g %.9g\n" % (float(n[0]), float(n[1]), float(n[2])))
+    if uvs is not None:
+        out.write("".join("vt %.9g %r\n" % (float(c[0]), 1.0 - float(c[1])) for tri in uvs for c in tri))
+    if material:
+        out.write("usemtl %s\n" % material)
     lines = []
-    for t in indices:
+    for k, t in enumerate(indices):
         a, b, c = int(t[0]) + 1, int(t[1]) + 1, int(t[2]) + 1
+        if uvs is not None:
+            ta = 3 * k + 1
+            lines.append("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (a, ta, a, b, ta + 1, b, c, ta + 2, c) if normals is not None
+                         else "f %d/%d %d/%d %d/%d\n" % (a, ta, b, ta + 1, c, ta + 2))
+            continue
         lines.append("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) if normals is not None else "f %d %d %d\n" % (a, b, c))
     out.write("".join(lines))
