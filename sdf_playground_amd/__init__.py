@@ -426,6 +426,7 @@ class SDFRenderer:
         if rc != SDFR_OK:
             raise SdfrError(rc, "sdfr_create(device=%d) failed" % device)
         self.device = int(device)
+        self._frames_in_flight = 1
         return True
 
     def close(self):
@@ -798,6 +799,8 @@ class SDFRenderer:
                     _a, tp, tn, tv = self.atlasTexels(pos, nrm, idx, tile, baked["atlas"].width)
                     ao = self.queryOcclusion(tp.reshape(-1, 3), tn.reshape(-1, 3), float(cell) if ao_bias is None else ao_bias,
                                              8.0 * float(cell) if ao_radius is None else ao_radius)
+                    if self._frames_in_flight == 2:
+                        self.sync()  # the handle's stream is then its own: torch's does not wait for the records and states it reads next
                     answered = (ao[:, 3] == 1) & (tv.reshape(-1) == 1)
                     baked["openness"] = torch.where(answered, 1.0 - ao[:, 2].to(torch.float32) / 64.0, torch.zeros((), device=ao.device)).reshape(tv.shape)
             extra = []
@@ -1006,6 +1009,7 @@ class SDFRenderer:
         """sdfr_set_frames_in_flight: 2 = render() alternates between two internal streams and workspaces, so that a frame starts
         while the one before drains (render into two images in turn; sync() waits for both); 1 = the default."""
         self._check(self._L.sdfr_set_frames_in_flight(self._h, int(n)))
+        self._frames_in_flight = int(n)
 
     def waitFrame(self, stream=None):
         """sdfr_wait_frame: `stream` (a raw hipStream_t / torch stream's .cuda_stream; None = the default stream) waits on the

@@ -1,0 +1,553 @@
+"""Seeded sequences of MIXED calls on ONE renderer handle: renders, anti-aliased frames, post-processing, every query family, mesh
+extraction and atlas calls, interleaved.  tests/handle_sequences.py drives what a handle carries from frame to frame; this module
+drives the state the handle has gained since: the staging of host queries (`query`, cut three ways and released past 64 MiB), the
+extraction workspace (`mesh`, reused across lanes behind an event, released past 64 MiB), the supersampling buffers, and the
+per-handle query kernels in their DBG and non-DBG variants, on built-in scenes and on one compiled at run time.
+
+No torch, no GPU: the CPU tier (tests/test_handle_mixed_cpu.py) proves what the committed seeds cover, the GPU tier
+(tests/test_gpu_handle_mixed.py) runs them.  A step is one call on the handle, with the settings changed just before it (`set`) and
+the whole state a fresh handle needs to answer it (`state`).  The inputs of a call are drawn from the step's own seeded generator
+(rays(), points(), normals(), pixel_list(), lattice in the step)."""
+import math
+import random
+
+import handle_sequences as hs
+
+FAMILIES = ("render", "aa", "post", "points", "rays", "pick", "surfaces", "occlusion", "lighting", "mesh", "atlas", "failed")
+HOST_AND_DEVICE = tuple(f for f in FAMILIES if f not in ("post", "failed"))  # sdfr_postprocess takes device tensors only
+# (failed, failed) cannot be: a failed call always sits between two valid calls
+PAIRS = tuple((a, b) for a in FAMILIES for b in FAMILIES if (a, b) != ("failed", "failed"))
+
+ITEMS = (1, 63, 64, 65, 255, 1000, 4096)
+FRAME_SIZES = tuple(s for s in hs.SMALL_SIZES if s[0] <= 320 and s[1] <= 180)
+AA_SIZES = tuple(s for s in FRAME_SIZES if s[0] <= 160 and s[1] <= 90)
+AA_FACTORS = (2, 4)
+MAX_LATTICE = 24
+CELLS = (0.09, 0.13, 0.17)
+TILES = (4, 8, 16)
+MAX_ATLAS_WIDTH = 256
+LAYER_SETS = (("albedo",), ("normal",), ("lit",), ("albedo", "normal"), ("albedo", "lit"), ("normal", "lit"), ("albedo", "normal", "lit"))
+MESH_FORMS = (None, None, "surfaces", "occlusion", "lighting", "atlas_occlusion")
+SPLITS = hs.SPLITS
+DEBUG_VARS = {"debug_nx": 0.3, "debug_ny": 1.0}  # + the point debug_vars() puts the plane through: the driver's debug plane
+KEEP = 64 << 20                                   # k_query_stage_keep (sdfr_api.cpp): what a handle keeps of `query` and of `mesh`
+STAGE_ALIGN = 256                                 # SDFR_STAGE_ALIGN (sdfr_stage.h)
+MESH_BLOCK = 256                                  # SDFR_MESH_BLOCK (sdfr_mesh.hip)
+HIT_BYTES, SURFACE_BYTES, OCCLUSION_BYTES, LIGHTING_BYTES, LIGHTS_BYTES = 48, 128, 16, 64, 8 * 80
+
+# argument errors refused on the host before anything is launched: (kind, sdfr_last_error); all SDFR_ERR_INVALID_ARGUMENT but the capacities
+# smaller than the counts, which is SDFR_OK with the counts and nothing written
+FAILURES = (("negative_n", "bad item count"), ("null_pointer", "null pointer"), ("bad_on_host", "on_host must be 0 or 1"),
+            ("mesh_negative_capacity", "negative capacity"), ("mesh_small_capacity", None), ("aa_factor_3", "factor must be 1, 2, 4 or 8"),
+            ("aa_bad_format", "bad format"), ("atlas_bad_layout", "bad atlas"))
+FAILURE_KINDS = tuple(k for k, _ in FAILURES)
+FAILURE_ENTRIES = ("points", "rays", "pick", "surfaces", "occlusion", "lighting")  # whose entry a query's argument error goes through
+
+BLOCKS = ("staging", "lanes", "large_mesh", "aa_in_flight", "scene_change")
+STRETCH = 10  # free steps on the run-time scene, inside the scene_change block: one entry per seed (every entry compiles the scene again)
+BLOCK_STEPS = {"staging": 4, "lanes": 4, "large_mesh": 2, "aa_in_flight": 6, "scene_change": 4 + STRETCH}
+BIG_FRAME = (384, 240)  # pickLighting(None, hits, lights) of it on the host: past the keep (staging_bytes)
+
+SEEDS = (24, 92, 16, 62)  # the committed seeds (what they cover: tests/test_handle_mixed_cpu.py)
+STEPS = 64
+
+# the scene variables the sequences move (hs.SCENE_VARS, but the lense stays off the camera orbit's centre: at zpos 0 nothing of the scene
+# is left around it, and the lattices there would be empty)
+SCENE_VARS = dict(hs.SCENE_VARS, lense=dict(hs.SCENE_VARS["lense"], zpos=(5.0, 25.0)))
+
+# where a scene's surface is: the centre of its point boxes and lattices
+CENTRES = {"labyrinth": (-2.0, 3.9, 4.37), "cube_sea": (0.0, 0.1, 0.0), "fractal": (0.5, 1.2, 0.0), "lense": (0.0, 0.0, 0.0), "gems": (1.0, 0.1, -2.2),
+           "light_shadows": (0.0, 1.2, -0.5), hs.RUNTIME_SCENE: (0.0, 1.2, -1.0)}
+
+
+def _aligned(b):
+    return (b + STAGE_ALIGN - 1) // STAGE_ALIGN * STAGE_ALIGN
+
+
+def stage_total(pieces):
+    """stage_offsets (sdfr_stage.h): the pieces one after the other, each on a multiple of 256 bytes"""
+    return sum(_aligned(b) for b in pieces)
+
+
+def staging_bytes(step):
+    """bytes of `query` a HOST call stages, by the formulas of the plans (sdfr_query_plan.h, sdfr_atlas_plan.h, mesh_impl); a mesh
+    extraction's are known only with its counts: None"""
+    p = step
+    n = p.get("n", 0)
+    hits = HIT_BYTES if p.get("hits") else 0
+    call = p["call"]
+    if call == "queryDistance":
+        return stage_total([n * 12, 0, n * 4, n * 12 if p["normals"] else 0, 0, 0])
+    if call in ("queryRays", "pick"):
+        return stage_total([n * (8 if call == "pick" else 12), 0 if call == "pick" else n * 12, n * HIT_BYTES, 0, 0, 0])
+    if call in ("queryRaySurfaces", "meshSurfaces", "pickSurfaces"):
+        ins = [0, 0] if p.get("frame") else ([n * 8, 0] if call == "pickSurfaces" else [n * 12, n * 12])
+        return stage_total(ins + [n * hits, n * SURFACE_BYTES, 0, 0])
+    if call in ("queryRayLighting", "meshLighting", "pickLighting"):
+        ins = [0, 0] if p.get("frame") else ([n * 8, 0] if call == "pickLighting" else [n * 12, n * 12])
+        return stage_total(ins + [n * hits, 0, n * LIGHTING_BYTES, n * LIGHTS_BYTES if p["lights"] else 0])
+    if call == "queryOcclusion":
+        return stage_total([n * 12, n * 12, n * OCCLUSION_BYTES, 0, 0, 0])
+    if call == "hitOcclusion":
+        return stage_total([n * HIT_BYTES, 0, n * OCCLUSION_BYTES, 0, 0, 0])
+    return None
+
+
+def workspace_bytes(dims):
+    """bytes of `mesh` an extraction over `dims` cells needs: the Carving of mesh_impl (sdfr_api.cpp)"""
+    def scan_sum_words(n):  # mesh_scan_sum_words (sdfr_mesh.hip)
+        words = 0
+        while n > MESH_BLOCK:
+            n = (n + MESH_BLOCK - 1) // MESH_BLOCK
+            words += n
+        return words
+
+    points = (dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1)
+    cells = dims[0] * dims[1] * dims[2]
+    return stage_total([points * 4, (cells + 1) * 4, (points + 1) * 4, (scan_sum_words(cells + 1) + scan_sum_words(points + 1)) * 4])
+
+
+def _big_lattice():
+    n = 1
+    while workspace_bytes((n, n, n)) <= KEEP:
+        n += 1
+    return (n, n, n)
+
+
+BIG_LATTICE = _big_lattice()  # the smallest cube of cells whose workspace is past the keep
+
+
+def eye_and_front(scene, t):
+    kind, eye, target = hs.camera(scene, t)
+    d = target if kind == "dir" else tuple(a - b for a, b in zip(target, eye))
+    n = math.sqrt(sum(x * x for x in d))
+    return eye, tuple(x / n for x in d)
+
+
+def rays(step):
+    """(origins, dirs), n rows each: from the step's camera eye into a cone around its view direction, lengths 0.25 .. 4 as given"""
+    rng = random.Random(step["seed"])
+    eye, front = eye_and_front(step["state"]["scene"], step["state"]["t"])
+    dirs = []
+    for _ in range(step["n"]):
+        length = math.exp(rng.uniform(math.log(0.25), math.log(4.0)))
+        dirs.append(tuple((f + rng.uniform(-0.6, 0.6)) * length for f in front))
+    return [eye] * step["n"], dirs
+
+
+def points(step):
+    """n points of a box around the scene's centre"""
+    rng = random.Random(step["seed"] + 1)
+    c = CENTRES[step["state"]["scene"]]
+    return [tuple(c[a] + rng.uniform(-2.5, 2.5) for a in range(3)) for _ in range(step["n"])]
+
+
+def normals(step):
+    """n unit vectors"""
+    rng = random.Random(step["seed"] + 2)
+    out = []
+    while len(out) < step["n"]:
+        v = [rng.gauss(0, 1) for _ in range(3)]
+        n = math.sqrt(sum(x * x for x in v))
+        if n > 1e-3:
+            out.append(tuple(x / n for x in v))
+    return out
+
+
+def pixel_list(step):
+    """n pixels (x, y) of the step's w x h frame and of a rim around it: the first is always outside"""
+    rng = random.Random(step["seed"] + 3)
+    w, h = step["w"], step["h"]
+    out = [(-1, 0), (w, h - 1), (0, h), (w - 1, h - 1), (0, 0)][:step["n"]]
+    while len(out) < step["n"]:
+        out.append((rng.randrange(-2, w + 2), rng.randrange(-2, h + 2)))
+    return out
+
+
+def lattice(scene, rng, most=MAX_LATTICE, least=5, dims=None, cell=None):
+    """(origin, cell, dims) of a lattice around the scene's centre, a little off it so that no lattice plane is a plane of the scene"""
+    cell = cell or rng.choice(CELLS)
+    dims = dims or tuple(rng.randrange(least, most + 1) for _ in range(3))
+    c = CENTRES[scene]
+    origin = tuple(round(c[a] - 0.5 * dims[a] * cell + rng.uniform(0.01, 0.05), 4) for a in range(3))
+    return dict(origin=origin, cell=cell, dims=dims)
+
+
+def debug_vars(scene):
+    """the driver's debug plane through a point a little under the scene's centre, tilted"""
+    c = CENTRES[scene]
+    return dict(DEBUG_VARS, debug_x=c[0], debug_y=round(c[1] - 0.1, 3), debug_z=c[2])
+
+
+def share_of(pair):
+    """which of the committed seeds works towards a pair of families first: a diagonal, so that no seed has all the pairs of one family"""
+    return (FAMILIES.index(pair[0]) + FAMILIES.index(pair[1])) % len(SEEDS)
+
+
+def slot_of(seed):
+    return SEEDS.index(seed) if seed in SEEDS else seed % len(SEEDS)
+
+
+class _Gen:
+    def __init__(self, seed, n, slot=None):
+        self.rng = rng = random.Random(seed)
+        self.n = n
+        self.slot = slot_of(seed) if slot is None else slot
+        self.state = dict(scene=None, limits="default", vars={}, t=0.0, stime=0.0, schedule="pixel", launch="auto", shortcuts=False, fif=1,
+                          debug=False, split=(0, 1))
+        self.steps = []
+        self.runtime_entries = 0
+        self.failed = 0
+        # this seed's share of the coverage the committed seeds have together
+        self.want_pairs = {p for p in PAIRS if share_of(p) == self.slot}
+        self.want_runtime = {f for k, f in enumerate(FAMILIES) if k % len(SEEDS) == self.slot}
+        self.want_forms = {(f, host, fif) for f in HOST_AND_DEVICE for host in (False, True) for fif in (1, 2)}
+        self.want_debug = set(FAMILIES)
+        self.used = {}
+        self.last_frame = None   # index of the last render / aa step: what post processes
+        self.last_hits = None    # index of the last step that answered hit records
+        self.last_mesh = None    # index of the last extraction
+        # the scripted blocks in a seeded order, with seeded gaps of free steps between them
+        order = list(BLOCKS)
+        rng.shuffle(order)
+        free = n - sum(BLOCK_STEPS.values())
+        cuts = sorted(rng.sample(range(3, free - 3), len(order)))
+        self.block_at, at = {}, 0
+        for k, name in enumerate(order):
+            at = cuts[k] + sum(BLOCK_STEPS[b] for b in order[:k])
+            self.block_at[at] = name
+        self.scripted = set()  # the steps that are scripted: all of a block's but the free steps of the stretch
+        for at, name in self.block_at.items():
+            self.scripted.update(k for k in range(at, at + BLOCK_STEPS[name]) if name != "scene_change" or not 2 <= k - at < 2 + STRETCH)
+
+    # ---- state -----------------------------------------------------------------------------------------------------------------
+    def change(self, key, value, changes):
+        if self.state[key] != value:
+            self.state[key] = value
+            changes[key] = value
+
+    def load(self, scene, changes):
+        st = self.state
+        if scene == st["scene"]:
+            return
+        if scene == hs.RUNTIME_SCENE:
+            self.runtime_entries += 1
+        st["vars"] = {}  # loading a scene resets its variables, the debug plane's too
+        st["debug"] = False
+        st["scene"] = changes["scene"] = scene
+        st["t"] = changes["t"] = round(self.rng.uniform(0, 2 * math.pi), 4)
+
+    def builtin(self, changes):
+        self.load(self.rng.choice([s for s in hs.BUILTIN_SCENES if s != self.state["scene"]]), changes)
+
+    def place(self, changes):
+        """the scene of a free step: now and then another built-in one, once a stretch on the run-time scene"""
+        rng, st = self.rng, self.state
+        if st["scene"] is None:
+            self.builtin(changes)
+        elif rng.random() < 0.12:
+            self.builtin(changes)
+
+    def settings(self, family, changes):
+        rng, st = self.rng, self.state
+        if st["scene"] is None:
+            self.builtin(changes)
+        scene = st["scene"]
+        if rng.random() < 0.15:
+            self.change("schedule", rng.choice(hs.SCHEDULES), changes)
+        if rng.random() < 0.2:
+            self.change("launch", rng.choice(hs.LAUNCH_MODES), changes)
+        if rng.random() < 0.15:
+            self.change("shortcuts", not st["shortcuts"], changes)
+        if rng.random() < 0.12:
+            self.change("limits", rng.choice(sorted(hs.LIMITS)), changes)
+        if scene in SCENE_VARS and rng.random() < 0.25:
+            name = rng.choice(sorted(SCENE_VARS[scene]))
+            lo, hi = SCENE_VARS[scene][name]
+            v = round(rng.uniform(lo, hi), 3)
+            st["vars"] = dict(st["vars"], **{name: v})
+            changes["var"] = (name, v)
+        debug = st["debug"]
+        if family in self.want_debug:
+            debug = debug or rng.random() < 0.5
+        elif rng.random() < 0.25:
+            debug = not debug
+        self.change("debug", debug, changes)
+        if rng.random() < 0.5:
+            self.change("t", round(rng.uniform(0, 2 * math.pi), 4), changes)
+        if rng.random() < 0.25:
+            self.change("stime", round(rng.uniform(0, 3), 3), changes)
+
+    # ---- what comes next -------------------------------------------------------------------------------------------------------
+    def allowed(self, i):
+        prev = self.steps[-1]["family"] if self.steps else None
+        out = [f for f in FAMILIES if f != "failed"]
+        if self.last_frame is None:
+            out.remove("post")
+        edge = i == 0 or i == self.n - 1 or i + 1 in self.scripted or i - 1 in self.scripted
+        if prev not in (None, "failed") and not edge:
+            out.append("failed")
+        return out
+
+    def pick_family(self, i):
+        rng = self.rng
+        if i == 0:
+            return "render"
+        prev = self.steps[-1]["family"]
+        allowed = self.allowed(i)
+        if self.state["scene"] == hs.RUNTIME_SCENE:
+            duty = [f for f in allowed if f in self.want_runtime]
+            if duty:
+                return rng.choice(duty)
+        fresh = [f for f in allowed if (prev, f) in self.want_pairs]
+        if fresh:
+            return rng.choice(fresh)
+        # nothing new from here: go where the most is left to start from (a failed call cannot be followed by one)
+        left = {f: sum(1 for (a, b) in self.want_pairs if a == f and (f != "failed" or b != "failed")) for f in allowed}
+        best = max(left.values())
+        if best == 0:
+            return rng.choice([f for f in allowed if f != "failed"])
+        return rng.choice([f for f in allowed if left[f] == best])
+
+    def pick_form(self, family, changes):
+        """host or device, and one or two frames in flight: what is left to cover first"""
+        rng, st = self.rng, self.state
+        left = sorted((h, fif) for (f, h, fif) in self.want_forms if f == family)  # (sorted: a set's order is not the seed's)
+        if family == "post":
+            host = False
+            if rng.random() < 0.15:
+                self.change("fif", 3 - st["fif"], changes)
+        elif left:
+            here = [h for h, fif in left if fif == st["fif"]]
+            if here:
+                host = rng.choice(here)
+            else:
+                host, fif = rng.choice(left)
+                self.change("fif", fif, changes)
+        else:
+            host = rng.random() < 0.5
+            if rng.random() < 0.1:
+                self.change("fif", 3 - st["fif"], changes)
+        return host
+
+    def vary(self, key, options):
+        """one of `options`, those not yet taken for `key` first: a seed goes through the variants of a call instead of drawing some twice"""
+        used = self.used.setdefault(key, [])
+        left = [o for o in options if o not in used]
+        if not left:
+            del used[:]
+            left = list(options)
+        o = self.rng.choice(left)
+        used.append(o)
+        return o
+
+    # ---- the calls -------------------------------------------------------------------------------------------------------------
+    def new(self, i, family, call, changes, host, block=None, **params):
+        s = dict(i=i, family=family, call=call, host=host, set=changes, block=block, seed=self.rng.randrange(1 << 30), **params)
+        s["state"] = dict(self.state, vars=dict(self.state["vars"]))
+        self.steps.append(s)
+        st = self.state
+        if len(self.steps) > 1:
+            self.want_pairs.discard((self.steps[-2]["family"], family))
+        self.want_forms.discard((family, host, st["fif"]))
+        if st["debug"]:
+            self.want_debug.discard(family)
+        if st["scene"] == hs.RUNTIME_SCENE:
+            self.want_runtime.discard(family)
+        if family in ("render", "aa") and call != "renderPrivateStrips":
+            self.last_frame = i
+        if (call in ("queryRays", "pick") or params.get("hits")) and block is None:
+            self.last_hits = i
+        if family == "mesh" and call == "extractMesh" and block != "large_mesh":
+            self.last_mesh = i
+        return s
+
+    def free_step(self, i, family, changes):
+        rng, st, vary = self.rng, self.state, self.vary
+        host = self.pick_form(family, changes)
+        scene = st["scene"]
+        yes_no = (False, True)
+        n = vary("n " + family, ITEMS)
+        w, h = vary("size", FRAME_SIZES)
+        if family == "render":
+            return self.new(i, family, "render", changes, host, w=w, h=h, fmt=vary("render fmt", (hs.RGBA32F, hs.RGBA16F)), stats=vary("render stats", yes_no))
+        if family == "aa":
+            w, h = vary("aa size", AA_SIZES)
+            return self.new(i, family, "renderAA", changes, host, w=w, h=h, factor=vary("factor", AA_FACTORS), fmt=vary("aa fmt", (hs.RGBA32F, hs.RGBA16F)),
+                            stats=vary("aa stats", yes_no))
+        if family == "post":
+            return self.new(i, family, "postprocess", changes, False, src=self.last_frame)
+        if family == "points":
+            return self.new(i, family, "queryDistance", changes, host, n=n, normals=vary("points normals", yes_no))
+        if family == "rays":
+            return self.new(i, family, "queryRays", changes, host, n=n)
+        if family == "pick":
+            return self.new(i, family, "pick", changes, host, n=n, w=w, h=h)
+        if family == "surfaces":
+            call = vary("surfaces", ("queryRaySurfaces", "pickSurfaces", "pickSurfacesFrame", "meshSurfaces"))
+            hits = vary(call + " hits", yes_no)
+            if call == "pickSurfacesFrame":
+                return self.new(i, family, "pickSurfaces", changes, host, n=w * h, w=w, h=h, frame=True, hits=hits)
+            if call == "meshSurfaces":
+                return self.new(i, family, call, changes, host, n=n, hits=hits, lattice=lattice(scene, rng), reach=0.2)
+            return self.new(i, family, call, changes, host, n=n, w=w, h=h, frame=False, hits=hits)
+        if family == "occlusion":
+            call = vary("occlusion", ("hitOcclusion of a step", "hitOcclusion", "queryOcclusion"))
+            if call == "hitOcclusion of a step" and self.last_hits is not None:
+                return self.new(i, family, "hitOcclusion", changes, host, n=self.steps[self.last_hits]["n"], src=self.last_hits, bias=0.01, radius=1.0)
+            if call == "hitOcclusion":
+                return self.new(i, family, "hitOcclusion", changes, host, n=n, src=None, bias=0.01, radius=1.0)
+            return self.new(i, family, "queryOcclusion", changes, host, n=n, bias=0.05, radius=1.0)
+        if family == "lighting":
+            call = vary("lighting", ("queryRayLighting", "pickLighting", "pickLightingFrame", "meshLighting"))
+            hits, lights = vary(call + " hits", yes_no), vary(call + " lights", yes_no)
+            if call == "pickLightingFrame":
+                return self.new(i, family, "pickLighting", changes, host, n=w * h, w=w, h=h, frame=True, hits=hits, lights=lights)
+            if call == "meshLighting":
+                return self.new(i, family, call, changes, host, n=n, hits=hits, lights=lights, lattice=lattice(scene, rng), reach=0.2)
+            return self.new(i, family, call, changes, host, n=n, w=w, h=h, frame=False, hits=hits, lights=lights)
+        if family == "mesh":
+            form = vary("mesh form", MESH_FORMS)
+            lat = lattice(scene, rng, 14 if form == "atlas_occlusion" else MAX_LATTICE)
+            more = dict(tile=vary("tile", TILES), width=vary("width", (64, 128, MAX_ATLAS_WIDTH)), layers=vary("layers", LAYER_SETS)) if form == "atlas_occlusion" else {}
+            return self.new(i, family, "extractMesh", changes, host, lattice=lat, normals=form is not None or vary("mesh normals", yes_no), form=form, **more)
+        if family == "atlas":
+            src = self.last_mesh if self.last_mesh is not None and vary("atlas src", yes_no) else None
+            lat = self.steps[src]["lattice"] if src is not None else lattice(scene, rng, 12)
+            call = vary("atlas", ("atlasTexels", "bakeAtlas", "bakeAtlas"))
+            return self.new(i, family, call, changes, host, src=src, lattice=lat, tile=vary("tile", TILES), width=vary("width", (64, 128, MAX_ATLAS_WIDTH)),
+                            layers=vary("layers", LAYER_SETS) if call == "bakeAtlas" else (), reach=0.2)
+        assert family == "failed"
+        kind = FAILURE_KINDS[(self.slot + self.failed * len(SEEDS)) % len(FAILURE_KINDS)]
+        self.failed += 1
+        return self.new(i, family, "failed", changes, rng.random() < 0.5, fail=kind, entry=vary("entry", FAILURE_ENTRIES), n=rng.choice(ITEMS[:5]),
+                        w=w, h=h, lattice=lattice(scene, rng, 8))
+
+    # ---- the scripted blocks ---------------------------------------------------------------------------------------------------
+    def block(self, i, name):
+        rng, st = self.rng, self.state
+        k = i - [at for at, b in self.block_at.items() if b == name][0]
+        changes = {}
+        if k == 0 and name != "scene_change":
+            self.settings("render", changes)
+            if st["scene"] == hs.RUNTIME_SCENE:
+                self.builtin(changes)
+        scene = st["scene"]
+        if name == "staging":
+            # a host query past the keep (`query` is released at its end), then the three ways `query` is cut, small
+            if k == 0:
+                w, h = BIG_FRAME
+                return self.new(i, "lighting", "pickLighting", changes, True, name, n=w * h, w=w, h=h, frame=True, hits=True, lights=True)
+            if k == 1:
+                return self.new(i, "atlas", "bakeAtlas", changes, True, name, src=None, lattice=lattice(scene, rng, 8), tile=4, width=64,
+                                layers=("albedo", "normal", "lit"), reach=0.2)
+            if k == 2:
+                return self.new(i, "mesh", "extractMesh", changes, True, name, lattice=lattice(scene, rng, 9), normals=True, form=None)
+            return self.new(i, "rays", "queryRays", changes, True, name, n=65)
+        if name == "lanes":
+            # two frames in flight: an extraction on one lane, a frame (the lanes swap), a larger extraction on the other lane (waits
+            # for the first one's emit work, grows `mesh`), a smaller one (reuses it); read after one sync
+            self.change("fif", 2, changes)
+            if k == 1:
+                w, h = rng.choice(FRAME_SIZES[3:])
+                return self.new(i, "render", "render", changes, False, name, w=w, h=h, fmt=hs.RGBA32F, stats=True, defer=True)
+            lat = lattice(scene, rng, dims={0: (11, 9, 10), 2: (24, 23, 22), 3: (7, 8, 6)}[k])
+            return self.new(i, "mesh", "extractMesh", changes, False, name, lattice=lat, normals=True, form=None, defer=k != 3)
+        if name == "large_mesh":
+            lat = lattice(scene, rng, 10)
+            if k == 0:
+                lat = lattice(scene, rng, dims=BIG_LATTICE, cell=0.02)
+                return self.new(i, "mesh", "countMesh", changes, rng.random() < 0.5, name, lattice=lat, normals=False, form=None)
+            return self.new(i, "mesh", "extractMesh", changes, rng.random() < 0.5, name, lattice=lat, normals=True, form=None)
+        if name == "aa_in_flight":
+            # a strip split left set across an anti-aliased frame between two plain frames in flight; A, B: two images of one size
+            self.change("fif", 2, changes)
+            if k == 0:
+                self.size = rng.choice(AA_SIZES[3:])
+                self.change("schedule", "pixel", changes)
+                split = rng.choice(SPLITS)
+                if st["split"] != split:
+                    st["split"] = changes["split"] = split
+            w, h = self.size
+            if k in (0, 5):
+                return self.new(i, "render", "renderPrivateStrips", changes, False, name, w=w, h=h, fmt=hs.RGBA32F, stats=False)
+            self.change("t", round(rng.uniform(0, 2 * math.pi), 4), changes)
+            if k == 2:
+                return self.new(i, "aa", "renderAA", changes, False, name, w=w, h=h, factor=2, fmt=hs.RGBA32F, stats=True, image="B", defer=True)
+            return self.new(i, "render", "render", changes, False, name, w=w, h=h, fmt=hs.RGBA32F, stats=True, image="AB"[k == 3], defer=k != 4)
+        assert name == "scene_change"
+        # device work enqueued, then a scene change with no sync of the test's own: the answers are those of the scene of the call.  To
+        # the run-time scene, STRETCH free steps on it, and from it again
+        if k == 0:
+            self.settings("rays", changes)
+            if st["scene"] == hs.RUNTIME_SCENE:
+                self.builtin(changes)
+            return self.new(i, "rays", "queryRays", changes, False, name, n=1000, defer=True)
+        if k == 1:
+            self.load(hs.RUNTIME_SCENE, changes)
+            return self.new(i, "mesh", "extractMesh", changes, False, name, lattice=lattice(hs.RUNTIME_SCENE, rng), normals=True, form=None, defer=True)
+        if k < 2 + STRETCH:
+            family = self.pick_family(i)
+            self.settings(family, changes)
+            return self.free_step(i, family, changes)
+        if k == 2 + STRETCH:
+            return self.new(i, "surfaces", "queryRaySurfaces", changes, False, name, n=255, w=1, h=1, frame=False, hits=True, defer=True)
+        self.builtin(changes)
+        return self.new(i, "points", "queryDistance", changes, True, name, n=64, normals=True)
+
+    def step(self, i):
+        for at, name in self.block_at.items():
+            if at <= i < at + BLOCK_STEPS[name]:
+                return self.block(i, name)
+        changes = {}
+        self.place(changes)
+        family = self.pick_family(i)
+        self.settings(family, changes)
+        if family == "post" and self.last_frame is None:
+            family = "render"
+        return self.free_step(i, family, changes)
+
+
+def sequence(seed, n=None, slot=None):
+    """The steps of `seed`: a list of dicts (see the module's doc string).  Deterministic per seed.  slot: which share of the coverage
+    the seed works towards first (default: its place among the committed seeds)."""
+    n = STEPS if n is None else n
+    g = _Gen(seed, n, slot)
+    for i in range(n):
+        g.step(i)
+    return g.steps
+
+
+# ---- what a sequence covers (tests/test_handle_mixed_cpu.py) ----------------------------------------------------------------------
+def transitions(steps):
+    return {(a["family"], b["family"]) for a, b in zip(steps, steps[1:])}
+
+
+def forms(steps):
+    """{(family, host, frames in flight)}"""
+    return {(s["family"], s["host"], s["state"]["fif"]) for s in steps if s["family"] != "failed"}
+
+
+def on_runtime_scene(steps):
+    return {s["family"] for s in steps if s["state"]["scene"] == hs.RUNTIME_SCENE}
+
+
+def with_debug(steps):
+    return {s["family"] for s in steps if s["state"]["debug"]}
+
+
+def blocks(steps):
+    """{name: [steps]} of the scripted blocks"""
+    out = {}
+    for s in steps:
+        if s["block"]:
+            out.setdefault(s["block"], []).append(s)
+    return out
+
+
+def failure_kinds(steps):
+    return {s["fail"] for s in steps if s["family"] == "failed"}
+
+
+def runtime_entries(steps):
+    return sum(1 for s in steps if s["set"].get("scene") == hs.RUNTIME_SCENE)

@@ -1,0 +1,778 @@
+"""GPU tier: one renderer handle through seeded sequences of MIXED calls (tests/handle_mixed_sequences.py): renders, anti-aliased
+frames, post-processing, every query family, mesh extraction and atlas calls, host and device form, one and two frames in flight,
+built-in scenes and one compiled at run time, the debug plane on and off, failed calls in between.
+
+Every step runs on ONE handle, through the C entry points, into buffers of the test's own: pre-filled with a sentinel no call
+produces and a guard tail of 256 bytes behind them.  After every step every output array equals, bit for bit, what a reference
+handle answers for the same state and inputs (one handle per scene, configured in full for every answer: one frame in flight, the
+default launch mode, host form); no sentinel is left in what the call owns, the guard tail and what the call does not own are
+untouched; and after a query, an extraction, an atlas call or a failed call sdfr_get_stats still reports the last frame.  With two
+frames in flight device answers are read after sdfr_sync, as include/sdfr.h tells a caller to, and nowhere else does the test
+synchronise the handle.  About one step in eight has its reference answer checked against the CPU oracle on a stride sample, every
+family at least once per seed."""
+import ctypes
+import math
+import time
+
+import numpy as np
+import pytest
+
+import handle_mixed_sequences as hm
+import handle_sequences as hs
+from test_gpu_handle_state import FOVY, LAUNCH, NAN16, NAN32, SCHEDULE, _apply, _limits, _load_scene, _set_camera, _totals
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64                 # words behind every buffer: 256 bytes
+ONES = 0xFFFFFFFF          # the -1 of the pixel statistics and the indices
+HALVES = (NAN16 << 16) | NAN16
+OK, ERR_INVALID_ARGUMENT, ERR_NO_SCENE = 0, -1, -4
+LAYER_BITS = {"albedo": 1, "normal": 2, "lit": 4}
+ENTRY_CALLS = {"points": dict(call="queryDistance", normals=True), "rays": dict(call="queryRays"), "pick": dict(call="pick"),
+               "surfaces": dict(call="queryRaySurfaces", hits=True, frame=False), "occlusion": dict(call="queryOcclusion", bias=0.05, radius=1.0),
+               "lighting": dict(call="queryRayLighting", hits=True, lights=True, frame=False)}
+ORACLE_FAMILIES = tuple(f for f in hm.FAMILIES if f != "failed")
+
+
+class Buf:
+    """`words` 32-bit words of host or device memory filled with `fill`, and a guard tail.  owned: the words the call must write,
+    from the start (None: all); the others, and the tail, must stay as they are."""
+
+    def __init__(self, words, host, fill=NAN32, owned=None):
+        import torch
+
+        self.words, self.host, self.fill, self.owned = int(words), host, fill, owned
+        if host:
+            self.a = np.full(self.words + GUARD, fill, np.uint32)
+        else:
+            self.a = torch.full((self.words + GUARD,), fill - (1 << 32) if fill >= 1 << 31 else fill, dtype=torch.int32, device="cuda")
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.a.ctypes.data if self.host else self.a.data_ptr())
+
+    def raw(self):
+        return self.a if self.host else self.a.cpu().numpy().view(np.uint32)
+
+    def read(self, what):
+        """the owned words, after checking the rest"""
+        a = self.raw()
+        owned = self.words if self.owned is None else self.owned
+        assert (a[owned:] == self.fill).all(), (what, "written past what the call owns", int((a[owned:] != self.fill).sum()))
+        assert not (a[:owned] == self.fill).any(), (what, "sentinel left in what the call owns", int((a[:owned] == self.fill).sum()))
+        return a[:owned].copy()
+
+    def untouched(self):
+        return bool((self.raw() == self.fill).all())
+
+
+def _upload(a, host):
+    """an input array where the call reads it: numpy, or a finished device copy"""
+    a = np.ascontiguousarray(a)
+    if host:
+        return a, ctypes.c_void_p(a.ctypes.data)
+    import torch
+
+    t = torch.from_numpy(a.view(np.int32).reshape(-1).copy()).cuda()
+    return t, ctypes.c_void_p(t.data_ptr())
+
+
+def _grid(lat):
+    import sdf_playground_amd as sp
+
+    return sp.MeshGrid((ctypes.c_float * 3)(*lat["origin"]), lat["cell"], lat["dims"][0], lat["dims"][1], lat["dims"][2], 0.0)
+
+
+def _image_words(w, h, fmt):
+    return (w * h * 2, HALVES) if fmt == hs.RGBA16F else (w * h * 4, NAN32)
+
+
+class Call:
+    """One call of a step on a handle: its buffers, its status, what it keeps alive."""
+
+    def __init__(self, r, s, inp, host, shared=None, override=None):
+        import sdf_playground_amd as sp
+
+        self.s, self.host, self.bufs, self.alive, self.extra = s, host, {}, [], {}
+        self.rc = self.run(r, sp, s, inp, host, shared, override or {})
+
+    def out(self, name, words, fill=NAN32, owned=None):
+        self.bufs[name] = Buf(words, self.host, fill, owned)
+        return self.bufs[name].ptr
+
+    def inp(self, a, null=False):
+        if null:
+            return None
+        t, p = _upload(a, self.host)
+        self.alive.append(t)
+        return p
+
+    def go(self, fn, *args):
+        """the C call, once the buffers and inputs torch made for it are finished: with two frames in flight the handle's streams do
+        not wait for torch's.  Only torch's stream is waited for, never the device: the handle's own work stays in flight."""
+        if not self.host:
+            import torch
+
+            torch.cuda.current_stream().synchronize()
+        return fn(*args)
+
+    def run(self, r, sp, s, inp, host, shared, ov):
+        L, h, oh = r._L, r._h, ov.get("on_host", 1 if host else 0)
+        call, n = s["call"], ov.get("n", s.get("n", 0))
+        null = ov.get("null", False)
+        w, hh = s.get("w", 0), s.get("h", 0)
+        if call in ("render", "renderAA", "renderPrivateStrips"):
+            fmt = s["fmt"]
+            words, fill = _image_words(w, hh, fmt)
+            if shared is not None and s.get("image"):
+                for name, wd, fl in (("image", words, fill), ("stats", w * hh * 3, ONES)):
+                    if (s["image"], name) not in shared:
+                        shared[s["image"], name] = Buf(wd, False, fl)
+                    self.bufs[name] = shared[s["image"], name]
+            else:
+                self.out("image", words, fill)
+                if s["stats"]:
+                    self.out("stats", w * hh * 3, ONES)
+            pst = self.bufs["stats"].ptr if s["stats"] else None
+            if call == "render":
+                return self.go(L.sdfr_render, h, w, hh, self.bufs["image"].ptr, ov.get("fmt", fmt), oh, pst)
+            if call == "renderAA":
+                return self.go(L.sdfr_render_aa, h, w, hh, ov.get("factor", s["factor"]), self.bufs["image"].ptr, ov.get("fmt", fmt), oh, pst)
+            return self.go(L.sdfr_render_private_strips, h, w, hh, self.bufs["image"].ptr, fmt)
+        if call == "postprocess":
+            hh, w = inp["scene16"].shape[:2]
+            return self.go(L.sdfr_postprocess, h, w, hh, self.inp(inp["scene16"]), self.out("bloom", w * hh * 2, HALVES), self.out("ldr", w * hh))
+        hits = lambda: self.out("hits", 12 * abs(n)) if s.get("hits") else None  # noqa: E731
+        if call == "queryDistance":
+            return self.go(L.sdfr_query_distance, h, n, self.inp(inp["points"], null), self.out("distance", abs(n)), self.out("normals", 3 * abs(n)) if s["normals"] else None, oh)
+        if call == "queryRays":
+            return self.go(L.sdfr_query_rays, h, n, self.inp(inp["origins"], null), self.inp(inp["dirs"]), 0.0, self.out("hits", 12 * abs(n)), oh)
+        if call == "pick":
+            return self.go(L.sdfr_pick, h, w, hh, n, self.inp(inp["pixels"], null), self.out("hits", 12 * abs(n)), oh)
+        if call == "queryRaySurfaces":
+            return self.go(L.sdfr_query_ray_surfaces, h, n, self.inp(inp["origins"], null), self.inp(inp["dirs"]), 0.0, hits(), self.out("surfaces", 32 * abs(n)), oh)
+        if call == "pickSurfaces":
+            return self.go(L.sdfr_pick_surfaces, h, w, hh, n, None if s["frame"] else self.inp(inp["pixels"]), hits(), self.out("surfaces", 32 * n), oh)
+        if call == "meshSurfaces":
+            return self.go(L.sdfr_mesh_surfaces, h, n, self.inp(inp["points"]), self.inp(inp["normals"]), s["reach"], hits(), self.out("surfaces", 32 * n), oh)
+        lights = lambda: self.out("lights", 160 * abs(n)) if s.get("lights") else None  # noqa: E731
+        if call == "queryRayLighting":
+            return self.go(L.sdfr_query_ray_lighting, h, n, self.inp(inp["origins"], null), self.inp(inp["dirs"]), 0.0, hits(), self.out("lighting", 16 * abs(n)), lights(), oh)
+        if call == "pickLighting":
+            return self.go(L.sdfr_pick_lighting, h, w, hh, n, None if s["frame"] else self.inp(inp["pixels"]), hits(), self.out("lighting", 16 * n), lights(), oh)
+        if call == "meshLighting":
+            return self.go(L.sdfr_mesh_lighting, h, n, self.inp(inp["points"]), self.inp(inp["normals"]), s["reach"], hits(), self.out("lighting", 16 * n), lights(), oh)
+        if call == "queryOcclusion":
+            return self.go(L.sdfr_query_occlusion, h, n, self.inp(inp["points"], null), self.inp(inp["normals"]), s["bias"], s["radius"], self.out("occlusion", 4 * abs(n)), oh)
+        if call == "hitOcclusion":
+            return self.go(L.sdfr_hit_occlusion, h, n, self.inp(inp["hits"]), s["bias"], s["radius"], self.out("occlusion", 4 * n), oh)
+        if call in ("countMesh", "extractMesh") and not s.get("form"):
+            return self.extract(r, sp, s, oh, ov)
+        if call == "extractMesh":
+            return self.composed(r, s, host)
+        if call in ("atlasTexels", "bakeAtlas"):
+            pos, nrm, idx = inp["mesh"]
+            atlas = sp.atlasLayout(len(idx), s["tile"], s["width"])
+            if ov.get("bad_atlas"):
+                atlas.height += 1
+            texels = atlas.width * atlas.height
+            self.extra["shape"] = (atlas.height, atlas.width)
+            ins = [self.inp(pos), self.inp(nrm), self.inp(idx)]
+            if call == "atlasTexels":
+                return self.go(L.sdfr_atlas_texels, h, ctypes.byref(atlas), len(pos), ins[0], ins[1], ins[2], self.out("texel_positions", 3 * texels),
+                                           self.out("texel_normals", 3 * texels), self.out("valid", texels), oh)
+            mask = sum(LAYER_BITS[k] for k in s["layers"])
+            # every plane is handed in: one that is not asked for must stay as it is
+            planes = [self.out(k, 4 * texels, owned=None if k in s["layers"] else 0) for k in ("albedo", "normal", "lit")]
+            return self.go(L.sdfr_atlas_bake, h, ctypes.byref(atlas), len(pos), ins[0], ins[1], ins[2], s["reach"], mask, planes[0], planes[1], planes[2],
+                                     self.out("valid", texels), oh)
+        raise KeyError(call)
+
+    def extract(self, r, sp, s, oh, ov):
+        """sdfr_mesh_extract: the counting call, then (extractMesh) the filling call into arrays two rows larger than the counts"""
+        L, h = r._L, r._h
+        grid, counts = _grid(s["lattice"]), sp.MeshCounts()
+        if "capacity" in ov:  # a failed call: arrays for ov["rows"] rows, capacities as given
+            cv, ct = ov["capacity"]
+            rows = ov["rows"]
+            rc = self.go(L.sdfr_mesh_extract, h, ctypes.byref(grid), cv, ct, self.out("positions", 3 * rows[0]), self.out("normals", 3 * rows[0]),
+                                     self.out("indices", 3 * rows[1], ONES), ctypes.byref(counts), oh)
+            self.extra["counts"] = (int(counts.vertices), int(counts.triangles))
+            return rc
+        rc = self.go(L.sdfr_mesh_extract, h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), oh)
+        v, t = int(counts.vertices), int(counts.triangles)
+        self.extra["counts"] = (v, t)
+        if rc != OK or s["call"] == "countMesh" or v == 0:
+            return rc
+        again = sp.MeshCounts()
+        rc = self.go(L.sdfr_mesh_extract, h, ctypes.byref(grid), v + 2, t + 2, self.out("positions", 3 * (v + 2), owned=3 * v),
+                                 self.out("normals", 3 * (v + 2), owned=3 * v) if s["normals"] else None,
+                                 self.out("indices", 3 * (t + 2), ONES, owned=3 * t), ctypes.byref(again), oh)
+        assert (again.vertices, again.triangles) == (v, t)
+        return rc
+
+    def composed(self, r, s, host):
+        """extractMesh(surfaces= / occlusion= / lighting= / atlas=): the wrapper's own composition, arrays of its own making"""
+        lat, form = s["lattice"], s["form"]
+        kw = dict(surfaces=form == "surfaces", occlusion=form == "occlusion", lighting=form == "lighting")
+        if form == "atlas_occlusion":
+            kw["atlas"] = dict(tile=s["tile"], width=s["width"], layers=s["layers"], occlusion=True)
+        got = r.extractMesh(lat["origin"], lat["cell"], lat["dims"], normals=True, device=not host, **kw)
+        self.extra["composed"] = got
+        return OK
+
+    def answers(self, r, what, synced=False):
+        """{name: words} of everything the call answered, read as the contract allows; every buffer checked"""
+        out = {k: b.read((what, k)) for k, b in self.bufs.items()}
+        if "counts" in self.extra:
+            out["counts"] = np.array(self.extra["counts"], np.int64)
+        if "composed" in self.extra:
+            got = self.extra["composed"]
+            names = ["positions", "normals", "indices"] + ([self.s["form"]] if self.s["form"] != "atlas_occlusion" else [])
+            for name, a in zip(names, got):
+                out[name] = _words(a)
+            if self.s["form"] == "atlas_occlusion":
+                baked = got[-1]
+                for k, a in baked.items():
+                    if k != "atlas":
+                        out["atlas " + k] = _words(a)
+                out["atlas layout"] = np.array([getattr(baked["atlas"], f) for f in ("triangles", "quads", "tile", "width", "height", "tiles_per_row", "rows")])
+        return out
+
+
+def _words(a):
+    """the bytes of an array the wrapper made, numpy (records included) or torch"""
+    if hasattr(a, "data_ptr"):
+        a = a.cpu().numpy()
+    return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+
+
+def _same(what, got, want):
+    assert sorted(got) == sorted(want), (what, sorted(got), sorted(want))
+    for k in want:
+        assert got[k].shape == want[k].shape, (what, k, got[k].shape, want[k].shape)
+        bad = got[k] != want[k]
+        assert not bad.any(), (what, k, "%d of %d words differ, the first at %d" % (int(bad.sum()), bad.size, int(np.argmax(bad))))
+
+
+def _state_key(st):
+    return (st["scene"], st["limits"], tuple(sorted(st["vars"].items())), st["t"], st["stime"], st["shortcuts"], st["schedule"], st["debug"])
+
+
+def _call_key(s):
+    skip = ("i", "set", "state", "block", "host", "defer", "image", "family")
+    return tuple(sorted((k, repr(v)) for k, v in s.items() if k not in skip))
+
+
+def _debug(r, scene, on):
+    for name, v in hm.debug_vars(scene).items():
+        assert r.setValue(name, v if on else 0.0)
+
+
+def _camera_size(s):
+    return s.get("w") or 16, s.get("h") or 9
+
+
+class References:
+    """What a handle in the state of a step answers for the step's call: one handle per scene, configured in full for every answer
+    (one frame in flight, the default launch mode, no strip split, host form), cached by state, call and inputs."""
+
+    def __init__(self, oracle):
+        self.oracle = oracle
+        self.handles = {}
+        self.cache = {}
+
+    def close(self):
+        for r in self.handles.values():
+            r.close()
+
+    def handle(self, st):
+        import sdf_playground_amd as sp
+
+        r = self.handles.get(st["scene"])
+        if r is None:
+            r = self.handles[st["scene"]] = sp.SDFRenderer(0)
+            _load_scene(r, st["scene"])
+        r.resetVariables()
+        r.setLaunchMode(LAUNCH["auto"])
+        r.setLimits(**_limits(st["limits"]))
+        for name, v in sorted(st["vars"].items()):
+            assert r.setValue(name, v)
+        if st["debug"]:
+            _debug(r, st["scene"], True)
+        r.setParameters(st["stime"])
+        r.setStepShortcuts(st["shortcuts"])
+        r.setSchedule(SCHEDULE[st["schedule"]])
+        return r
+
+    def pseudo(self, s, **changes):
+        """the answer of another call in the state of `s` (or in `state`)"""
+        return self.answer(dict(s, family=None, form=None, block=None, **changes))
+
+    def mesh(self, s, state=None, lat=None):
+        """(positions [v, 3], normals [v, 3], indices [t, 3]) of the lattice of `s` in its state"""
+        got = self.pseudo(s, call="extractMesh", normals=True, state=state or s["state"], lattice=lat or s["lattice"])
+        assert got["counts"][0] > 0, "the lattice misses the surface"
+        return got["positions"].view(np.float32).reshape(-1, 3), got["normals"].view(np.float32).reshape(-1, 3), got["indices"].reshape(-1, 3)
+
+    def inputs(self, s, steps):
+        """the input arrays of a step's call, from its own seeded generator, from an earlier step's answers or from a fresh extraction"""
+        call, inp = s["call"], {}
+        if call in ("queryRays", "queryRaySurfaces", "queryRayLighting"):
+            o, d = hm.rays(s)
+            inp["origins"], inp["dirs"] = np.array(o, np.float32).reshape(-1, 3), np.array(d, np.float32).reshape(-1, 3)
+        if call in ("pick", "pickSurfaces", "pickLighting") and not s.get("frame"):
+            inp["pixels"] = np.array(hm.pixel_list(s), np.int32).reshape(-1, 2)
+        if call in ("queryDistance", "queryOcclusion"):
+            inp["points"] = np.array(hm.points(s), np.float32).reshape(-1, 3)
+        if call == "queryOcclusion":
+            inp["normals"] = np.array(hm.normals(s), np.float32).reshape(-1, 3)
+        if call in ("meshSurfaces", "meshLighting"):
+            pos, nrm, _idx = self.mesh(s)
+            k = np.arange(s["n"]) % len(pos)  # the step's n items: the vertices, again from the first if there are fewer
+            inp["points"], inp["normals"] = pos[k].copy(), nrm[k].copy()
+        if call == "hitOcclusion":
+            src = steps[s["src"]] if s.get("src") is not None else dict(s, call="queryRays", family="rays")
+            inp["hits"] = self.answer(src, steps)["hits"].reshape(-1, 12)
+        if call in ("atlasTexels", "bakeAtlas"):
+            src = steps[s["src"]] if s.get("src") is not None else s
+            inp["mesh"] = self.mesh(s, src["state"], src["lattice"])
+        if call == "postprocess":
+            src = steps[s["src"]]
+            img = self.pseudo(src, call="render", fmt=hs.RGBA16F, stats=False)["image"]
+            inp["scene16"] = img.view(np.float16).reshape(src["h"], src["w"], 4)
+        return inp
+
+    def answer(self, s, steps=None, inp=None):
+        key = (_state_key(s["state"]), _call_key(s))
+        if key in self.cache:
+            return self.cache[key]
+        inp = self.inputs(s, steps) if inp is None else inp
+        r = self.handle(s["state"])
+        _set_camera(r, s["state"]["scene"], s["state"]["t"], *_camera_size(s))
+        if s["call"] == "renderPrivateStrips":
+            got = self.pseudo(s, call="render", stats=True)
+        else:
+            host = s["call"] != "postprocess"
+            c = Call(r, s, inp, host)
+            assert c.rc == OK, (s["call"], c.rc, r._L.sdfr_last_error(r._h))
+            r.sync()
+            got = c.answers(r, ("reference", s["call"]))
+            if s["call"] in ("render", "renderAA"):
+                got["totals"] = np.array(_totals(r.getStats()), np.int64)
+        for a in got.values():
+            a.setflags(write=False)
+        self.cache[key] = got
+        return got
+
+    # ---- the reference against the CPU oracle: a stride sample -----------------------------------------------------------------
+    def frame(self, s, w, h):
+        oracle, st = self.oracle, s["state"]
+        kind, eye, target = hs.camera(st["scene"], st["t"])
+        basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, target, FOVY, np.float32(w) / np.float32(h))
+        f = oracle.default_frame(st["scene"], w, h, basis=basis, stime=st["stime"])
+        for name, v in _limits(st["limits"]).items():
+            setattr(f, name, v)
+        slots = {row[0]: row[6] for row in oracle.var_table(st["scene"])}
+        for name, v in list(st["vars"].items()) + (list(hm.debug_vars(st["scene"]).items()) if st["debug"] else []):
+            if slots[name] >= 0:
+                f.scene_var[slots[name]] = v
+            else:
+                setattr(f, name, v)
+        return f
+
+    def check_oracle(self, s, steps):
+        import aa_util
+        import atlas_util as au
+        import lighting_util as lu
+        import mesh_util as mu
+        import occlusion_util as ou
+        import query_util as qu
+        import surface_util as su
+
+        oracle, st, scene, call = self.oracle, s["state"], s["state"]["scene"], s["call"]
+        want = self.answer(s, steps)
+        inp = self.inputs(s, steps)
+        w, h = _camera_size(s)
+        of = self.frame(s, w, h)
+        what = ("oracle", s["i"], call, scene)
+        n = s.get("n", 0)
+        pick = np.arange(0, n, max(1, -(-n // 256)))  # at most 256 items
+
+        def hits_equal(got, ref):
+            got, ref = got.reshape(-1, 12)[pick], qu.hits_array(ref)
+            if st["shortcuts"]:  # a miss may end early: its t, distance and iterations are then smaller
+                assert np.array_equal(got[:, 10], ref[:, 10]), what
+                got, ref = got[ref[:, 10] == 1], ref[ref[:, 10] == 1]
+            qu.assert_same(str(what) + " hits", got, ref)
+
+        def pixels():
+            return (su.frame_pixels(w, h) if s["frame"] else inp["pixels"])[pick]
+
+        if call in ("render", "renderPrivateStrips"):
+            fmt = s["fmt"]
+            want = self.pseudo(s, call="render", stats=True)
+            img = want["image"].view(np.uint16 if fmt == hs.RGBA16F else np.uint32).reshape(h, w, 4)
+            stride = max(1, int(math.ceil(math.sqrt(w * h / 1500.0))))
+            ref, rst, _ = oracle.render(scene, of, region=(0, 0, w, h), step=(stride, stride), stats=True)
+            ref, rst = ref[::stride, ::stride], rst[::stride, ::stride]
+            assert np.array_equal(img[::stride, ::stride], oracle.float_to_half(ref) if fmt == hs.RGBA16F else ref.view(np.uint32)), what
+            got = want["stats"].reshape(h, w, 3)[::stride, ::stride]
+            assert np.array_equal(got[..., 0], rst[..., 0]) and np.array_equal(got[..., 2], rst[..., 2]), what
+            assert np.array_equal(got[..., 1], rst[..., 1]) if not st["shortcuts"] else (got[..., 1] <= rst[..., 1]).all(), what
+        elif call == "renderAA":
+            # a window of the image: its sub-samples from the oracle's frame S, resolved by the definition's pyramid
+            k, fmt = s["factor"], s["fmt"]
+            bw, bh = min(w, 16), min(h, 8)
+            x0, y0 = (s["i"] * 5) % (w - bw + 1), (s["i"] * 3) % (h - bh + 1)
+            big = self.frame(s, k * w, k * h)
+            S, _st, _ = oracle.render(scene, big, region=(k * x0, k * y0, k * (x0 + bw), k * (y0 + bh)), stats=True)
+            ref = aa_util.pyramid(S[k * y0:k * (y0 + bh), k * x0:k * (x0 + bw)], k)
+            img = want["image"].view(np.uint16 if fmt == hs.RGBA16F else np.uint32).reshape(h, w, 4)[y0:y0 + bh, x0:x0 + bw]
+            ref = oracle.float_to_half(ref) if fmt == hs.RGBA16F else ref
+            assert aa_util.same_bits_or_nan(img.view(np.float16 if fmt == hs.RGBA16F else np.float32), ref.view(np.float16 if fmt == hs.RGBA16F else np.float32)), what
+            if s["stats"]:
+                got = want["stats"].reshape(h, w, 3)[y0:y0 + bh, x0:x0 + bw]
+                rst = aa_util.sum_stats(_st[k * y0:k * (y0 + bh), k * x0:k * (x0 + bw)], k)
+                assert np.array_equal(got[..., 0], rst[..., 0]) and np.array_equal(got[..., 2], rst[..., 2]), what
+                assert np.array_equal(got[..., 1], rst[..., 1]) if not st["shortcuts"] else (got[..., 1] <= rst[..., 1]).all(), what
+        elif call == "postprocess":
+            b1, _b2, ldr = oracle.postprocess(inp["scene16"])
+            assert np.array_equal(want["ldr"].view(np.uint8), ldr.reshape(-1)) and np.array_equal(want["bloom"].view(np.uint16), b1.view(np.uint16).reshape(-1)), what
+        elif call == "queryDistance":
+            d, nr = qu.oracle_points(scene, of, inp["points"][pick])
+            qu.assert_same(str(what), want["distance"][pick], d.view(np.uint32))
+            if s["normals"]:
+                qu.assert_same(str(what) + " normals", want["normals"].reshape(-1, 3)[pick], nr.view(np.uint32))
+        elif call == "queryRays":
+            hits_equal(want["hits"], qu.oracle_rays(scene, of, inp["origins"][pick], inp["dirs"][pick]))
+        elif call == "pick":
+            hits_equal(want["hits"], qu.oracle_pick(scene, of, inp["pixels"][pick]))
+        elif call in ("queryRaySurfaces", "pickSurfaces", "meshSurfaces"):
+            if call == "queryRaySurfaces":
+                rh, rs = su.oracle_rays(scene, of, inp["origins"][pick], inp["dirs"][pick])
+            elif call == "pickSurfaces":
+                rh, rs = su.oracle_pick(scene, of, pixels())
+            else:
+                rh, rs = su.oracle_mesh(scene, of, inp["points"][pick], inp["normals"][pick], s["reach"])
+            qu.assert_same(str(what), want["surfaces"].reshape(-1, 32)[pick], rs)
+            if s["hits"]:
+                hits_equal(want["hits"], rh)
+        elif call in ("queryRayLighting", "pickLighting", "meshLighting"):
+            if call == "queryRayLighting":
+                rh, rg, rl = lu.oracle_rays(scene, of, inp["origins"][pick], inp["dirs"][pick])
+            elif call == "pickLighting":
+                rh, rg, rl = lu.oracle_pick(scene, of, pixels())
+            else:
+                rh, rg, rl = lu.oracle_mesh(scene, of, inp["points"][pick], inp["normals"][pick], s["reach"])
+            qu.assert_same(str(what), want["lighting"].reshape(-1, 16)[pick], rg)
+            if s["lights"]:
+                qu.assert_same(str(what) + " lights", want["lights"].reshape(-1, 160)[pick], rl.reshape(-1, 160))
+            if s["hits"]:
+                hits_equal(want["hits"], rh)
+        elif call == "queryOcclusion":
+            qu.assert_same(str(what), want["occlusion"].reshape(-1, 4)[pick], ou.oracle_points(scene, of, inp["points"][pick], inp["normals"][pick], s["bias"], s["radius"]))
+        elif call == "hitOcclusion":
+            qu.assert_same(str(what), want["occlusion"].reshape(-1, 4)[pick], ou.oracle_hits(scene, of, inp["hits"][pick], s["bias"], s["radius"]))
+        elif call == "extractMesh":
+            lat = s["lattice"]
+            plain = self.pseudo(s, call="extractMesh", normals=True)
+            if s.get("form"):  # a composed call: its mesh is the plain extraction's
+                for k in ("positions", "normals", "indices"):
+                    assert np.array_equal(want[k], plain[k].view(np.uint8)), (what, k)
+            want = plain
+            D = qu.oracle_points(scene, of, mu.lattice_points(lat["origin"], lat["cell"], lat["dims"]), normals=False)[0]
+            pos, idx = mu.surface_nets(D, lat["origin"], lat["cell"], lat["dims"], 0.0)
+            assert tuple(want["counts"]) == (len(pos), len(idx)), what
+            qu.assert_same(str(what) + " positions", want["positions"].reshape(-1, 3), pos.view(np.uint32))
+            assert np.array_equal(want["indices"].reshape(-1, 3), idx), what
+            if "normals" in want:
+                k = np.arange(0, len(pos), max(1, -(-len(pos) // 256)))
+                qu.assert_same(str(what) + " normals", want["normals"].reshape(-1, 3)[k], qu.oracle_points(scene, of, pos[k])[1].view(np.uint32))
+        elif call in ("atlasTexels", "bakeAtlas"):
+            pos, nrm, idx = inp["mesh"]
+            P, N, state = au.oracle_texels(pos, nrm, idx, s["tile"], s["width"])
+            if call == "atlasTexels":
+                assert np.array_equal(want["valid"].view(np.int32), state.reshape(-1)), what
+                qu.assert_same(str(what) + " positions", want["texel_positions"].reshape(-1, 3), P.reshape(-1, 3).view(np.uint32))
+                qu.assert_same(str(what) + " normals", want["texel_normals"].reshape(-1, 3), N.reshape(-1, 3).view(np.uint32))
+            else:
+                live = np.flatnonzero(state.reshape(-1) == 1)
+                live = live[::max(1, -(-len(live) // 256))]
+                assert len(live) > 0 and np.array_equal(want["valid"].view(np.int32)[state.reshape(-1) != 1], state.reshape(-1)[state.reshape(-1) != 1]), what
+                p, nr = P.reshape(-1, 3)[live], N.reshape(-1, 3)[live]
+                _h, srf = su.oracle_mesh(scene, of, p, nr, s["reach"])
+                hit = srf[:, 3] == 1
+                assert np.array_equal(want["valid"][live], srf[:, 3]), what
+                if "albedo" in s["layers"]:
+                    ref = np.zeros((len(live), 4), np.uint32)
+                    ref[:, :3] = np.where(((srf[:, 1] & 2) != 0)[:, None], srf[:, 4:7], srf[:, 16:19])
+                    ref[:, 3] = srf[:, 7]
+                    ref[~hit] = 0
+                    qu.assert_same(str(what) + " albedo", want["albedo"].reshape(-1, 4)[live], ref)
+                if "normal" in s["layers"]:
+                    ref = np.zeros((len(live), 4), np.uint32)
+                    ref[:, :3] = srf[:, 28:31]
+                    ref[~hit] = 0
+                    qu.assert_same(str(what) + " normal", want["normal"].reshape(-1, 4)[live], ref)
+                if "lit" in s["layers"]:
+                    _h, g, _s = lu.oracle_mesh(scene, of, p, nr, s["reach"], lights=False)
+                    ref = np.zeros((len(live), 4), np.uint32)
+                    ref[:, :3] = g[:, 12:15]
+                    ref[:, 3] = au.ONE
+                    ref[~hit] = 0
+                    qu.assert_same(str(what) + " lit", want["lit"].reshape(-1, 4)[live], ref)
+        else:
+            raise KeyError(call)
+
+
+@pytest.fixture(scope="module")
+def refs(oracle):
+    r = References(oracle)
+    # the reference handle of the run-time scene compiles the scene and its query kernels once, here: seconds that are no seed's
+    st = dict(scene=hs.RUNTIME_SCENE, limits="default", vars={}, t=0.0, stime=0.0, shortcuts=False, schedule="pixel", debug=False)
+    r.answer(dict(call="queryDistance", n=1, normals=False, seed=0, state=st))
+    yield r
+    r.close()
+
+
+def _apply_all(r, s):
+    _apply(r, s["set"])
+    if "debug" in s["set"]:
+        _debug(r, s["state"]["scene"], s["set"]["debug"])
+    _set_camera(r, s["state"]["scene"], s["state"]["t"], *_camera_size(s))
+
+
+def _private_rows(s):
+    import sdf_playground_amd as sp
+
+    rows = np.zeros(s["h"], bool)
+    rows[sp.private_rows_host(s["h"], s["state"]["split"])] = True
+    return rows
+
+
+def _check(r, refs, steps, c, where, last):
+    """the answers of a finished call against the reference's"""
+    s = c.s
+    want = dict(refs.answer(s, steps))
+    tot = want.pop("totals", None)
+    if s["call"] == "renderPrivateStrips":
+        rows = _private_rows(s)
+        b = c.bufs["image"]
+        got = b.raw()
+        assert (got[b.words:] == b.fill).all(), (where, "written past the image")
+        got, ref = got[:b.words].reshape(s["h"], -1), want["image"].reshape(s["h"], -1)
+        assert np.array_equal(got[rows], ref[rows]), (where, "private rows")
+        assert (got[~rows] == b.fill).all(), (where, "a private launch wrote a shared row")
+        st = want["stats"].reshape(s["h"], s["w"], 3)[rows].astype(np.int64)
+        return (st.shape[0] * st.shape[1],) + tuple(int(st[..., k].sum()) for k in range(3))
+    got = c.answers(r, where)
+    if not s.get("stats", True):
+        want.pop("stats", None)
+    _same(where, got, want)
+    return tuple(int(x) for x in tot) if tot is not None else last
+
+
+def _fail(r, refs, steps, s, keep, where):
+    """one argument error through the raw entry: the status, the words of sdfr_last_error, nothing written"""
+    kind = s["fail"]
+    message = dict(hm.FAILURES)[kind]
+    status = ERR_INVALID_ARGUMENT
+    host = s["host"]
+    if kind in ("negative_n", "null_pointer", "bad_on_host"):
+        q = dict(s, **ENTRY_CALLS[s["entry"]])
+        ov = {"negative_n": dict(n=-1), "null_pointer": dict(null=True), "bad_on_host": dict(on_host=2)}[kind]
+        c = Call(r, q, refs.inputs(q, steps), host, override=ov)
+    elif kind in ("mesh_negative_capacity", "mesh_small_capacity"):
+        v, t = (int(x) for x in refs.pseudo(s, call="extractMesh", normals=True)["counts"])
+        assert v >= 2 and t >= 2
+        q = dict(s, call="extractMesh", form=None, normals=True)
+        cap = (-1, t) if kind == "mesh_negative_capacity" else ((v - 1, t) if s["seed"] % 2 else (v, t - 1))
+        c = Call(r, q, {}, host, override=dict(capacity=cap, rows=(v, t)))
+        if kind == "mesh_small_capacity":
+            status = OK
+            assert c.extra["counts"] == (v, t), (where, c.extra["counts"], (v, t))
+    elif kind in ("aa_factor_3", "aa_bad_format"):
+        q = dict(s, call="renderAA", factor=2, fmt=hs.RGBA32F, stats=True)
+        c = Call(r, q, {}, host, override=dict(factor=3) if kind == "aa_factor_3" else dict(fmt=7))
+    else:
+        q = dict(s, call="bakeAtlas", tile=4, width=64, layers=("albedo", "normal", "lit"), reach=0.2)
+        pos = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], np.float32)
+        nrm = np.array([[0, 0, 1]] * 4, np.float32)
+        c = Call(r, q, dict(mesh=(pos, nrm, np.array([[0, 1, 2], [0, 2, 3]], np.uint32))), host, override=dict(bad_atlas=True))
+    assert c.rc == status, (where, c.rc, status)
+    if message is not None:
+        assert r._L.sdfr_last_error(r._h).decode() == message, (where, r._L.sdfr_last_error(r._h))
+    keep.append(c)
+    return c
+
+
+def _run_sequence(refs, seed):
+    import torch
+    import sdf_playground_amd as sp
+
+    steps = hm.sequence(seed)
+    r = sp.SDFRenderer(0)
+    side = torch.cuda.Stream()
+    last = None        # what sdfr_get_stats reports: the totals of the last render or aa step
+    last_image = None  # the call of the last device frame, if that is the frame submitted last: what sdfr_wait_frame waits for
+    pending = []       # calls whose answers are read later (defer): (call, where)
+    shared = {}        # the two images of the aa_in_flight block
+    keep = []          # calls that failed: their buffers are checked untouched at the end
+    copies = []        # (a side stream's copy of the last frame's image after sdfr_wait_frame, that frame's call, where)
+    waited = 0
+    refs.cache.clear()
+    checked = {}       # family: steps whose reference answer was checked against the oracle
+    try:
+        # every reference answer first: nothing but the handle under test then works on the GPU between a call and the next
+        t0 = time.perf_counter()
+        for s in steps:
+            if s["family"] != "failed":
+                refs.answer(s, steps)
+        spent = {"references": time.perf_counter() - t0, "oracle": 0.0, "slowest step": (0.0, None)}
+        for s in steps:
+            t1 = time.perf_counter()
+            i, st, call, host = s["i"], s["state"], s["call"], s["host"]
+            where = (seed, i, s["family"], call, "host" if host else "device", st["scene"], st["fif"], s["block"])
+            _apply_all(r, s)
+            if s["family"] == "failed":
+                c = _fail(r, refs, steps, s, keep, where)
+                assert all(b.untouched() for b in c.bufs.values()), (where, "a failed call wrote")
+                if last is not None:
+                    assert _totals(r.getStats()) == last, (where, "a failed call changed what sdfr_get_stats reports")
+                continue
+            inp = refs.inputs(s, steps)
+            refs.answer(s, steps, inp)  # (before the call: nothing of the test's runs between a deferred call and the next)
+            frame_query = s["family"] not in ("render", "aa", "post")
+            if frame_query and last_image is not None and st["fif"] == 2:
+                # the frame sdfr_wait_frame waits for is still the last frame: a side stream that waits (on the device) reads it whole
+                r.waitFrame(side.cuda_stream)
+                with torch.cuda.stream(side):
+                    copies.append((last_image.bufs["image"].a.clone(), last_image, where))
+            c = Call(r, s, inp, host, shared)
+            assert c.rc == OK, (where, c.rc, r._L.sdfr_last_error(r._h))
+            if s["family"] in ("render", "aa"):
+                last_image = c if not host and call != "renderPrivateStrips" else None
+            if s.get("defer"):
+                pending.append((c, where))
+                continue
+            if st["fif"] == 2 and (not host or pending):
+                r.sync()  # two frames in flight: "call sdfr_sync before reading device answers"
+            for pc, pwhere in pending:
+                if pc.s.get("image") and any(c2.s.get("image") == pc.s["image"] for c2, _ in pending[pending.index((pc, pwhere)) + 1:] + [(c, where)]):
+                    continue  # a later frame of the block went into the same image: the last writer's is what must be there
+                got = _check(r, refs, steps, pc, pwhere, last)
+                if pc.s["family"] in ("render", "aa"):
+                    last = got
+            pending = []
+            got = _check(r, refs, steps, c, where, last)
+            if s["family"] in ("render", "aa"):
+                last = got
+            if last is not None:
+                assert _totals(r.getStats()) == last, (where, "sdfr_get_stats does not report the last frame", _totals(r.getStats()), last)
+            for copy, frame, cwhere in copies:
+                side.synchronize()
+                want = refs.answer(frame.s, steps)["image"]
+                assert np.array_equal(copy.cpu().numpy().view(np.uint32)[:frame.bufs["image"].words], want), (cwhere, "sdfr_wait_frame did not wait for the last frame")
+                waited += 1
+            copies = []
+            if st["scene"] != hs.RUNTIME_SCENE and call != "countMesh" and (i % 8 == seed % 8 or s["family"] not in checked):
+                t2 = time.perf_counter()
+                refs.check_oracle(s, steps)
+                spent["oracle"] += time.perf_counter() - t2
+                checked[s["family"]] = checked.get(s["family"], 0) + 1
+            spent["slowest step"] = max(spent["slowest step"], (time.perf_counter() - t1, where[1:6]))
+        assert not pending
+        r.sync()
+        # where a seed's seconds go (the first step on the run-time scene compiles it and its query kernels: most of them)
+        print("seed %d: %.2f s, of which references %.2f, oracle %.2f, the slowest step %.2f %r; oracle checks %r"
+              % (seed, time.perf_counter() - t0, spent["references"], spent["oracle"], spent["slowest step"][0], spent["slowest step"][1], checked))
+        for c in keep:
+            assert all(b.untouched() for b in c.bufs.values()), (seed, c.s["i"], "the buffers of a failed call were written later")
+        assert waited >= 1, "no step checked sdfr_wait_frame"
+        assert sorted(checked) == sorted(ORACLE_FAMILIES), (seed, "families never checked against the oracle", sorted(set(ORACLE_FAMILIES) - set(checked)))
+        assert sum(checked.values()) >= len(steps) // 8, checked
+    finally:
+        r.close()
+    return steps
+
+
+@pytest.mark.parametrize("seed", hm.SEEDS)
+def test_one_handle_through_a_mixed_sequence(refs, seed):
+    steps = _run_sequence(refs, seed)
+    assert len(steps) == hm.STEPS
+
+
+def _every_entry(r, host):
+    """(name, call) of one small call of every scene-dependent entry point"""
+    s0 = dict(i=0, seed=5, n=65, w=16, h=9, host=host, block=None, family=None, form=None,
+              state=dict(scene="gems", t=0.3), lattice=dict(origin=(0.5, -0.3, -2.7), cell=0.13, dims=(7, 6, 5)), reach=0.2, bias=0.05, radius=1.0,
+              tile=4, width=64, layers=("albedo", "normal", "lit"))
+    o, d = hm.rays(s0)
+    quad = (np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], np.float32), np.array([[0, 0, 1]] * 4, np.float32), np.array([[0, 1, 2], [0, 2, 3]], np.uint32))
+    inp = dict(origins=np.array(o, np.float32), dirs=np.array(d, np.float32), points=np.array(hm.points(s0), np.float32), normals=np.array(hm.normals(s0), np.float32),
+               pixels=np.array(hm.pixel_list(s0), np.int32), hits=np.zeros((65, 12), np.uint32), mesh=quad)
+    calls = [dict(call="render", fmt=hs.RGBA32F, stats=True), dict(call="renderAA", factor=2, fmt=hs.RGBA32F, stats=True), dict(call="queryDistance", normals=True),
+             dict(call="queryRays"), dict(call="pick"), dict(call="queryRaySurfaces", hits=True, frame=False), dict(call="pickSurfaces", hits=True, frame=False),
+             dict(call="pickSurfaces", hits=True, frame=True, n=16 * 9), dict(call="meshSurfaces", hits=True), dict(call="queryOcclusion"), dict(call="hitOcclusion"),
+             dict(call="queryRayLighting", hits=True, lights=True, frame=False), dict(call="pickLighting", hits=True, lights=True, frame=False),
+             dict(call="pickLighting", hits=True, lights=True, frame=True, n=16 * 9), dict(call="meshLighting", hits=True, lights=True), dict(call="countMesh"),
+             dict(call="bakeAtlas")]
+    for q in calls:
+        yield dict(s0, **q), inp
+
+
+def test_before_any_scene_every_entry_fails_and_writes_nothing():
+    """a new handle has no scene: every scene-dependent entry point of every family returns SDFR_ERR_NO_SCENE and writes nothing, in
+    host and in device form; sdfr_atlas_texels, which looks at the mesh alone, works"""
+    import sdf_playground_amd as sp
+    import atlas_util as au
+
+    r = sp.SDFRenderer(0)
+    try:
+        for host in (True, False):
+            for q, inp in _every_entry(r, host):
+                c = Call(r, q, inp, host)
+                what = (q["call"], "host" if host else "device")
+                assert c.rc == ERR_NO_SCENE and r._L.sdfr_last_error(r._h).decode() == "no scene loaded", (what, c.rc, r._L.sdfr_last_error(r._h))
+                r.sync()
+                assert all(b.untouched() for b in c.bufs.values()), (what, "written without a scene")
+            q, inp = next(iter(_every_entry(r, host)))
+            q = dict(q, call="atlasTexels")
+            c = Call(r, q, inp, host)
+            assert c.rc == OK
+            r.sync()
+            got = c.answers(r, "atlasTexels without a scene")
+            P, N, valid = au.oracle_texels(*inp["mesh"], 4, 64)
+            assert np.array_equal(got["valid"].view(np.int32), valid.reshape(-1))
+            assert np.array_equal(got["texel_positions"], P.reshape(-1).view(np.uint32)) and np.array_equal(got["texel_normals"], N.reshape(-1).view(np.uint32))
+        with pytest.raises(sp.SdfrError) as e:
+            r.getStats()
+        assert e.value.code == ERR_INVALID_ARGUMENT
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("device", (False, True))
+def test_atlas_openness_with_two_frames_in_flight(device):
+    """extractMesh(atlas=dict(occlusion=True)) reads the occlusion records and the texel states with torch right after the handle
+    has enqueued them: with two frames in flight that is an internal stream, which torch's does not wait for.  The same call with
+    one and with two frames in flight, host and device form: every array is the same."""
+    import sdf_playground_amd as sp
+
+    got = []
+    for fif in (1, 2):
+        r = sp.SDFRenderer(0)
+        try:
+            r.initShader("light_shadows")
+            r.setParameters(0.5)
+            r.setFramesInFlight(fif)
+            out = r.extractMesh((-1.45, -0.2, -1.95), 0.13, (22, 23, 21), device=device, atlas=dict(tile=8, width=256, layers=("albedo", "lit"), occlusion=True))
+            r.sync()
+            baked = out[-1]
+            got.append({k: _words(a) for k, a in list(zip(("positions", "normals", "indices"), out)) + [(k, a) for k, a in baked.items() if k != "atlas"]})
+        finally:
+            r.close()
+    assert got[0]["positions"].size > 3 * 200 and (got[0]["openness"].view(np.float32) > 0).mean() > 0.05
+    assert not np.isin(got[0]["openness"].view(np.float32), (0.0, 1.0)).all()
+    _same("two frames in flight against one", got[1], got[0])
