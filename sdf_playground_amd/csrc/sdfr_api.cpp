@@ -7,7 +7,7 @@
 #include "sdfr_atlas_plan.h"
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
-#include "sdfr_mesh.h"
+#include "sdfr_mesh_plan.h"
 #include "sdfr_occlusion.h"
 #include "sdfr_query.h"
 #include "sdfr_query_plan.h"
@@ -719,56 +719,91 @@ static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipS
 	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "query launch");
 }
 
-// The queries (sdfr_query.h, sdfr_surface.h, sdfr_occlusion.h, sdfr_lighting.h).  The frame is latched into a copy, and nothing a render uses or reports is written: not
-// the handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order.  In: kind's inputs (pos / dir / pixels);
-// out: distance + normals, or hits and / or surfaces, or occlusion records, or lighting records with hits and light samples on request.
-static const size_t k_query_stage_keep = (size_t)64 << 20; // staging bytes a handle keeps between host queries
+// The calls that put a question to the loaded scene without rendering a frame -- the queries (sdfr_query.h, sdfr_surface.h, sdfr_occlusion.h,
+// sdfr_lighting.h), the mesh extraction and the texture atlas -- share one protocol: the plan's argument checks, begin_query, for a
+// host call stage_host_arrays, the launches, and for a host call copy_answers_back.  The frame is latched into a copy, and nothing a render uses
+// or reports is written: not the handle's FrameU or ms_setup, not a lane's workspace, counters, events or row order, not `launches`.
+static const size_t k_query_stage_keep = (size_t)64 << 20; // bytes a handle keeps of `query` and of `mesh` between calls
 static_assert(sizeof(sdfr_hit) == 4 * QUERY_HIT_WORDS, "sdfr_hit is the query kernels' 12-word record");
 static_assert(sizeof(sdfr_surface) == 4 * QUERY_SURFACE_WORDS, "sdfr_surface is the surface kernel's 32-word record");
 static_assert(sizeof(sdfr_occlusion) == 4 * QUERY_OCCLUSION_WORDS, "sdfr_occlusion is the occlusion kernel's 4-word record");
 static_assert(sizeof(sdfr_lighting) == 4 * QUERY_LIGHTING_WORDS, "sdfr_lighting is the lighting kernel's 16-word record");
 static_assert(sizeof(sdfr_light_sample) == 4 * QUERY_LIGHT_SAMPLE_WORDS && SDFR_MAX_LIGHTS == QUERY_LIGHT_SLOTS, "sdfr_light_sample[8] is the lighting kernel's 8 x 20 words");
-// the end of a host call: the answers back to the caller in the order they were named, and `stream` synchronised.  A large call
-// does not hold its staging for the rest of the handle's life; small ones keep reusing theirs
+// What such a call starts with once its arguments stand: the scene, if it needs one; the device; the handle's stream, or the lane of the
+// frame submitted last (as sdfr_postprocess); and with a scene its frame of width x height latched into the copy U
+static int begin_query(sdfr_renderer *r, bool needs_scene, int width, int height, FrameU &U, hipStream_t &stream)
+{
+	if (needs_scene && r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
+	SDFR_HIP(hipSetDevice(r->device));
+	stream = r->lane.stream;
+	if (!needs_scene) return SDFR_OK;
+	U = r->U;
+	return latch_into(r, U, width, height, stream);
+}
+// The caller's arrays are host memory: each of `arrays` that is there (bytes > 0) gets its piece of the handle's query buffer, in their
+// order.  An input's copy to the device is enqueued, an answer is noted for copy_answers_back, and the field is pointed at the piece; an
+// array of no bytes keeps its pointer (null stays null, and an absent array's alignment class does not matter)
+static int stage_host_arrays(sdfr_renderer *r, Carving &st, const StagedArray *arrays, int n, hipStream_t stream)
+{
+	assert(n <= (int)SDFR_STAGE_MAX_PIECES);
+	size_t bytes[SDFR_STAGE_MAX_PIECES];
+	for (int k = 0; k < n; ++k) bytes[k] = arrays[k].bytes;
+	st.cut(bytes, n);
+	SDFR_HIP(st.reserve(r->query)); // (host calls are synchronous: none is using the old one)
+	for (int k = 0; k < n; ++k)
+	{
+		const StagedArray &a = arrays[k];
+		if (!a.bytes) continue;
+		void *host, *piece = st.piece<void>(k);
+		memcpy(&host, a.field, sizeof host);
+		if (a.input) SDFR_HIP(hipMemcpyAsync(piece, host, a.bytes, hipMemcpyHostToDevice, stream));
+		else st.answers[st.n_answers++] = {host, piece, a.bytes};
+		memcpy(a.field, &piece, sizeof piece);
+	}
+	return SDFR_OK;
+}
+// A buffer past what a handle keeps is given back once the work on `stream` that uses it is done: a large call does not hold its
+// staging or workspace for the rest of the handle's life; small ones keep reusing theirs
+static int release_large(sdfr_renderer *r, sdfr_device_buffer &b, hipStream_t stream)
+{
+	if (b.bytes <= k_query_stage_keep) return SDFR_OK;
+	SDFR_HIP(hipStreamSynchronize(stream));
+	b.release();
+	return SDFR_OK;
+}
+// the end of a host call: the answers back to the caller in the order they were named, and `stream` synchronised (for a large call's
+// release once more, drained as it is: what a host extraction has always done for its workspace)
 static int copy_answers_back(sdfr_renderer *r, Carving &st, hipStream_t stream)
 {
 	for (int k = 0; k < st.n_answers; ++k) SDFR_HIP(hipMemcpyAsync(st.answers[k].host, st.answers[k].device, st.answers[k].bytes, hipMemcpyDeviceToHost, stream));
 	SDFR_HIP(hipStreamSynchronize(stream));
-	if (st.buffer->bytes > k_query_stage_keep) st.buffer->release();
-	return SDFR_OK;
+	return release_large(r, *st.buffer, stream);
 }
-static_assert(QUERY_PLAN_OK == SDFR_OK && QUERY_PLAN_INVALID_ARGUMENT == SDFR_ERR_INVALID_ARGUMENT, "plan_query speaks in the library's statuses");
-// One query: what the entry point asks for (QueryRequest), planned by sdfr_query_plan.h and carried out here
+static_assert(QUERY_PLAN_OK == SDFR_OK && QUERY_PLAN_INVALID_ARGUMENT == SDFR_ERR_INVALID_ARGUMENT, "the plans speak in the library's statuses");
+// One query: what the entry point asks for (QueryRequest), planned by sdfr_query_plan.h and carried out here.  In: kind's inputs (pos / dir /
+// pixels); out: distance + normals, or hits and / or surfaces, or occlusion records, or lighting records with hits and light samples on request.
 static int query_impl(sdfr_renderer *r, const QueryRequest &c)
 {
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 	const QueryPlan p = plan_query(c, r->U.range);
 	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
 	if (p.nothing_to_do) return SDFR_OK;
-	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
-	SDFR_HIP(hipSetDevice(r->device));
-	hipStream_t stream = r->lane.stream; // the handle's stream, or the lane of the frame submitted last (as sdfr_postprocess)
-	FrameU U = r->U;
-	int rc = latch_into(r, U, p.width, p.height, stream);
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, true, p.width, p.height, U, stream);
 	if (rc != SDFR_OK) return rc;
 
 	QueryArgs q = p.q;
-	Carving st({p.bytes[0], p.bytes[1], p.bytes[2], p.bytes[3], p.bytes[4], p.bytes[5]});
+	Carving st;
 	if (c.on_host)
 	{
-		// the caller's arrays are host memory: each array of the kind that is there gets its piece of the staging buffer
+		// the arrays of the kind in the order of p.bytes, each through its member of q
 		const QueryKind &kind = k_query_kinds[q.kind];
-		SDFR_HIP(st.reserve(r->query)); // (host queries are synchronous: none is using the old one)
-		for (int k = 0; k < 2; ++k)
-		{
-			if (!p.bytes[k]) continue;
-			SDFR_HIP(hipMemcpyAsync(st.piece<void>(k), query_slot_get(p.q, kind.in[k]), p.bytes[k], hipMemcpyHostToDevice, stream));
-			query_slot_set(q, kind.in[k], st.piece<void>(k));
-		}
-		for (int k = 2; k < 4; ++k)
-			if (p.bytes[k]) query_slot_set(q, kind.out[k - 2], st.answer(k, const_cast<void *>(query_slot_get(p.q, kind.out[k - 2])), p.bytes[k]));
-		for (int k = 4; k < 6; ++k)
-			if (p.bytes[k]) query_slot_set(q, k_query_lighting_slots[k - 4], st.answer(k, const_cast<void *>(query_slot_get(p.q, k_query_lighting_slots[k - 4])), p.bytes[k]));
+		const QuerySlot *slots[6] = {&kind.in[0], &kind.in[1], &kind.out[0], &kind.out[1], &k_query_lighting_slots[0], &k_query_lighting_slots[1]};
+		StagedArray arrays[6];
+		for (int k = 0; k < 6; ++k) arrays[k] = {reinterpret_cast<char *>(&q) + slots[k]->member, p.bytes[k], k < 2};
+		rc = stage_host_arrays(r, st, arrays, 6, stream);
+		if (rc != SDFR_OK) return rc;
 	}
 	rc = run_query(r, U, q, stream);
 	if (rc != SDFR_OK) return rc;
@@ -909,38 +944,22 @@ int sdfr_hit_occlusion(sdfr_renderer *r, int64_t n, const sdfr_hit *hits, float 
 	});
 }
 
-// sdfr_mesh_extract (the definition: include/sdfr.h; stages: sdfr_mesh.h, sdfr_mesh.hip).  Like a query it latches the frame into a
-// copy and writes nothing a render uses or reports.  Sample the lattice, classify and scan, read the two totals back; then, if the
-// capacities allow, emit vertices and indices and ask the point query for the normals at the vertices.
-static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals,
-	uint32_t *indices, sdfr_mesh_counts *counts, int on_host)
+// sdfr_mesh_extract (the definition: include/sdfr.h; the plan: sdfr_mesh_plan.h; stages: sdfr_mesh.h, sdfr_mesh.hip), a call of the queries'
+// protocol.  Sample the lattice, classify and scan, read the two totals back; then, if the capacities allow, emit vertices and indices
+// and ask the point query for the normals at the vertices.
+static_assert(sizeof(sdfr_mesh_grid) == sizeof(MeshGrid) && offsetof(sdfr_mesh_grid, cell) == offsetof(MeshGrid, cell) && offsetof(sdfr_mesh_grid, nx) == offsetof(MeshGrid, n) &&
+		offsetof(sdfr_mesh_grid, iso) == offsetof(MeshGrid, iso), "sdfr_mesh_grid is the plan's MeshGrid");
+static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *counts)
 {
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
-	if (!grid || !counts) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null pointer");
-	if (!is_flag(on_host)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "on_host must be 0 or 1");
-	bool grid_ok = std::isfinite(grid->cell) && grid->cell > 0.f && std::isfinite(grid->iso);
-	for (int a = 0; a < 3; ++a) grid_ok = grid_ok && std::isfinite(grid->origin[a]);
-	for (int32_t n : {grid->nx, grid->ny, grid->nz}) grid_ok = grid_ok && n >= 1 && n <= 1024;
-	if (!grid_ok || (int64_t)(grid->nx + 1) * (grid->ny + 1) * (grid->nz + 1) > (int64_t)1 << 30) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "bad mesh grid");
-	if (vertex_capacity < 0 || triangle_capacity < 0) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "negative capacity");
-	if ((vertex_capacity > 0 && !positions) || (triangle_capacity > 0 && !indices)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, "null array with a capacity");
-	if (r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
-	SDFR_HIP(hipSetDevice(r->device));
-	hipStream_t stream = r->lane.stream; // as the queries
-	FrameU U = r->U;
-	int rc = latch_into(r, U, 1, 1, stream);
+	const MeshPlan p = plan_mesh(c);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, true, 1, 1, U, stream);
 	if (rc != SDFR_OK) return rc;
 
-	MeshGrid g;
-	for (int a = 0; a < 3; ++a) g.origin[a] = grid->origin[a];
-	g.cell = grid->cell;
-	g.n[0] = grid->nx;
-	g.n[1] = grid->ny;
-	g.n[2] = grid->nz;
-	g.iso = grid->iso;
-	const size_t points = mesh_point_count(g), cells = mesh_cell_count(g);
-	Carving work({points * 4, (cells + 1) * 4, (points + 1) * 4, (mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)) * 4});
-
+	Carving work({p.work[0], p.work[1], p.work[2], p.work[3]});
 	for (hipEvent_t &e : r->ev_mesh)
 		if (!e) SDFR_HIP(hipEventCreate(&e));
 	hipEvent_t *ev = r->profiling ? r->ev_mesh : nullptr;
@@ -951,20 +970,8 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	SDFR_HIP(work.reserve(r->mesh));
 	float *d_lattice = work.piece<float>(0);
 	uint32_t *d_cells = work.piece<uint32_t>(1), *d_points = work.piece<uint32_t>(2), *d_sums = work.piece<uint32_t>(3);
-	// a workspace past what a handle keeps is given back once the work that uses it is done
-	auto release_large = [&]() -> int {
-		if (r->mesh.bytes <= k_query_stage_keep) return SDFR_OK;
-		SDFR_HIP(hipStreamSynchronize(stream));
-		r->mesh.release();
-		return SDFR_OK;
-	};
 
-	LatticeArgs la;
-	for (int a = 0; a < 3; ++a) la.origin[a] = g.origin[a];
-	la.cell = g.cell;
-	la.px = g.n[0] + 1;
-	la.py = g.n[1] + 1;
-	la.pz = g.n[2] + 1;
+	LatticeArgs la = p.lattice;
 	static const int rows = [] { const char *e = getenv("SDFR_MESH_LATTICE_ROWS"); return e && atoi(e) != 0 ? 1 : 0; }(); // developer knob: the A/B
 	la.rows = rows;
 	la.out = d_lattice;
@@ -975,36 +982,35 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 	const hipError_t e = launch_query_lattice(lattice_kernel, U, la, stream);
 	if (e != hipSuccess) return hip_fail(r, e, "lattice launch");
 	if (ev) SDFR_HIP(hipEventRecord(ev[1], stream));
-	SDFR_HIP(launch_mesh_count(g, d_lattice, d_cells, d_points, d_sums, stream));
+	SDFR_HIP(launch_mesh_count(p.g, d_lattice, d_cells, d_points, d_sums, stream));
 	if (ev) SDFR_HIP(hipEventRecord(ev[2], stream));
 	uint32_t n_vertices = 0, n_quads = 0;
-	SDFR_HIP(hipMemcpyAsync(&n_vertices, d_cells + cells, 4, hipMemcpyDeviceToHost, stream));
-	SDFR_HIP(hipMemcpyAsync(&n_quads, d_points + points, 4, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipMemcpyAsync(&n_vertices, d_cells + p.cells, 4, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipMemcpyAsync(&n_quads, d_points + p.points, 4, hipMemcpyDeviceToHost, stream));
 	SDFR_HIP(hipStreamSynchronize(stream));
 	if (ev) r->mesh_timed = 1;
-	counts->vertices = (int64_t)n_vertices;
-	counts->triangles = 2 * (int64_t)n_quads;
-	if (counts->vertices > vertex_capacity || counts->triangles > triangle_capacity || n_vertices == 0) return release_large();
+	const MeshFill f = plan_mesh_fill(c, n_vertices, n_quads);
+	counts->vertices = f.vertices;
+	counts->triangles = f.triangles;
+	if (!f.fill) return release_large(r, r->mesh, stream);
 
-	const size_t V = n_vertices, T = (size_t)counts->triangles;
-	float *d_pos = positions, *d_nrm = normals;
-	uint32_t *d_idx = T ? indices : nullptr;
-	Carving st({V * 12, normals ? V * 12 : 0, T * 12});
-	if (on_host)
+	float *d_pos = c.positions, *d_nrm = c.normals;
+	uint32_t *d_idx = f.bytes[2] ? c.indices : nullptr;
+	Carving st;
+	if (c.on_host)
 	{
-		SDFR_HIP(st.reserve(r->query)); // (host calls are synchronous: none is using the old one)
-		d_pos = st.answer(0, positions, V * 12);
-		d_nrm = normals ? st.answer(1, normals, V * 12) : nullptr;
-		d_idx = T ? st.answer(2, indices, T * 12) : nullptr;
+		const StagedArray arrays[3] = {{&d_pos, f.bytes[0], false}, {&d_nrm, f.bytes[1], false}, {&d_idx, f.bytes[2], false}};
+		rc = stage_host_arrays(r, st, arrays, 3, stream); // (in `query`, never in `mesh`)
+		if (rc != SDFR_OK) return rc;
 	}
 	if (ev) SDFR_HIP(hipEventRecord(ev[3], stream));
-	SDFR_HIP(launch_mesh_emit(g, d_lattice, d_cells, d_points, d_pos, d_idx, stream));
+	SDFR_HIP(launch_mesh_emit(p.g, d_lattice, d_cells, d_points, d_pos, d_idx, stream));
 	if (ev) SDFR_HIP(hipEventRecord(ev[4], stream));
 	if (d_nrm)
 	{
 		QueryArgs q = {};
 		q.kind = QUERY_POINTS;
-		q.n = (int)V; // <= 2^30
+		q.n = (int)n_vertices; // <= 2^30
 		q.pos = d_pos;
 		q.distance = d_lattice; // the point query also writes its distances: into the lattice, which nothing reads any more
 		q.normals = d_nrm;
@@ -1013,16 +1019,19 @@ static int mesh_impl(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t verte
 		if (ev) SDFR_HIP(hipEventRecord(ev[5], stream));
 	}
 	if (ev) r->mesh_timed = d_nrm ? 2 : 3;
-	rc = on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
+	if (c.on_host) rc = copy_answers_back(r, st, stream);
+	else SDFR_HIP(hipEventRecord(r->ev_mesh[6], stream)); // the end of the device work the next extraction waits for
 	if (rc != SDFR_OK) return rc;
-	if (!on_host) SDFR_HIP(hipEventRecord(r->ev_mesh[6], stream));
-	return release_large();
+	return release_large(r, r->mesh, stream);
 }
 
 int sdfr_mesh_extract(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals,
 	uint32_t *indices, sdfr_mesh_counts *counts, int on_host)
 {
-	return guarded(r, [&]() -> int { return mesh_impl(r, grid, vertex_capacity, triangle_capacity, positions, normals, indices, counts, on_host); });
+	return guarded(r, [&]() -> int {
+		const MeshRequest c = {reinterpret_cast<const MeshGrid *>(grid), vertex_capacity, triangle_capacity, positions, normals, indices, counts, on_host};
+		return mesh_impl(r, c, counts);
+	});
 }
 
 int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
@@ -1048,9 +1057,8 @@ int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
 }
 
 // ---- the texture atlas of a mesh (the definition: include/sdfr.h; the plan: sdfr_atlas_plan.h; the texel map and the bake: sdfr_atlas.h).
-// sdfr_atlas_texels looks at the mesh alone and needs no scene; sdfr_atlas_bake is a query: the frame is latched into a copy and nothing
-// a render uses or reports is written.  A host call stages three inputs and up to four answers in the handle's query buffer, cut here
-// (stage_offsets) because a Carving holds six pieces.
+// sdfr_atlas_texels looks at the mesh alone and needs no scene, as a bake of no quads; any other sdfr_atlas_bake is a call of the queries'
+// protocol.  A host call stages three inputs and up to four answers.
 static_assert(sizeof(sdfr_atlas) == sizeof(AtlasLayout) && offsetof(sdfr_atlas, tile) == offsetof(AtlasLayout, tile) && offsetof(sdfr_atlas, rows) == offsetof(AtlasLayout, rows),
 	"sdfr_atlas is the plan's AtlasLayout");
 static_assert(SDFR_ATLAS_ALBEDO == ATLAS_ALBEDO && SDFR_ATLAS_NORMAL == ATLAS_NORMAL && SDFR_ATLAS_LIT == ATLAS_LIT, "the layer bits are the kernel's");
@@ -1076,48 +1084,22 @@ static int atlas_impl(sdfr_renderer *r, const AtlasRequest &c)
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 	const AtlasPlan p = plan_atlas(c);
 	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
-	if (p.needs_scene && r->scene < 0) return fail(r, SDFR_ERR_NO_SCENE, "no scene loaded");
-	SDFR_HIP(hipSetDevice(r->device));
-	hipStream_t stream = r->lane.stream; // as the queries
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, p.needs_scene, 1, 1, U, stream);
+	if (rc != SDFR_OK) return rc;
 
 	AtlasArgs g = p.a;
-	struct { void *host; const void *device; size_t bytes; } answers[4];
-	int n_answers = 0;
+	Carving st;
 	if (c.on_host)
 	{
-		size_t offset[ATLAS_STAGE_PIECES];
-		SDFR_HIP(r->query.reserve(stage_offsets(p.bytes, ATLAS_STAGE_PIECES, offset))); // (host calls are synchronous: none is using the old one)
-		char *base = static_cast<char *>(r->query.ptr);
-		auto piece = [&](int k) -> void * { return p.bytes[k] ? base + offset[k] : nullptr; };
-		const void *in[3] = {p.a.positions, p.a.normals, p.a.indices};
-		for (int k = 0; k < 3; ++k)
-			if (p.bytes[k]) SDFR_HIP(hipMemcpyAsync(piece(k), in[k], p.bytes[k], hipMemcpyHostToDevice, stream));
-		g.positions = static_cast<const float *>(piece(0));
-		g.normals = static_cast<const float *>(piece(1));
-		g.indices = static_cast<const uint32_t *>(piece(2));
-		void *out[4] = {c.bake ? (void *)p.a.albedo : (void *)p.a.texel_positions, c.bake ? (void *)p.a.normal : (void *)p.a.texel_normals,
-			c.bake ? (void *)p.a.lit : (void *)p.a.valid, c.bake ? (void *)p.a.valid : nullptr};
-		for (int k = 0; k < 4; ++k)
-			if (p.bytes[3 + k]) answers[n_answers++] = {out[k], piece(3 + k), p.bytes[3 + k]};
-		if (c.bake)
-		{
-			g.albedo = static_cast<float *>(piece(3));
-			g.normal = static_cast<float *>(piece(4));
-			g.lit = static_cast<float *>(piece(5));
-			g.valid = static_cast<int32_t *>(piece(6));
-		}
-		else
-		{
-			g.texel_positions = static_cast<float *>(piece(3));
-			g.texel_normals = static_cast<float *>(piece(4));
-			g.valid = static_cast<int32_t *>(piece(5));
-		}
+		StagedArray arrays[ATLAS_STAGE_PIECES];
+		for (int k = 0; k < ATLAS_STAGE_PIECES; ++k) arrays[k] = {reinterpret_cast<char *>(&g) + k_atlas_stage_slots[c.bake ? 1 : 0][k], p.bytes[k], k < ATLAS_STAGE_INPUTS};
+		rc = stage_host_arrays(r, st, arrays, ATLAS_STAGE_PIECES, stream);
+		if (rc != SDFR_OK) return rc;
 	}
 	if (p.needs_scene)
 	{
-		FrameU U = r->U;
-		int rc = latch_into(r, U, 1, 1, stream);
-		if (rc != SDFR_OK) return rc;
 		KernelRef k;
 		rc = loaded_query_kernel(r, QUERY_KERNEL_ATLAS, U, k);
 		if (rc != SDFR_OK) return rc;
@@ -1126,27 +1108,32 @@ static int atlas_impl(sdfr_renderer *r, const AtlasRequest &c)
 	}
 	else
 		SDFR_HIP(launch_atlas_texels(g, p.blocks, stream));
-	if (!c.on_host) return SDFR_OK;
-	for (int k = 0; k < n_answers; ++k) SDFR_HIP(hipMemcpyAsync(answers[k].host, answers[k].device, answers[k].bytes, hipMemcpyDeviceToHost, stream));
-	SDFR_HIP(hipStreamSynchronize(stream));
-	if (r->query.bytes > k_query_stage_keep) r->query.release();
-	return SDFR_OK;
+	return c.on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
+}
+
+// what both entries ask for: the atlas, the mesh, the validity map
+static AtlasRequest atlas_request(const sdfr_atlas *atlas, int64_t vertex_count, const float *positions, const float *normals, const uint32_t *indices, int32_t *valid,
+	bool bake, int on_host)
+{
+	AtlasRequest c = {};
+	c.atlas = layout_of(atlas);
+	c.vertex_count = vertex_count;
+	c.a.positions = positions;
+	c.a.normals = normals;
+	c.a.indices = indices;
+	c.a.valid = valid;
+	c.bake = bake;
+	c.on_host = on_host;
+	return c;
 }
 
 int sdfr_atlas_texels(sdfr_renderer *r, const sdfr_atlas *atlas, int64_t vertex_count, const float *positions, const float *normals, const uint32_t *indices,
 	float *texel_positions, float *texel_normals, int32_t *valid, int on_host)
 {
 	return guarded(r, [&]() -> int {
-		AtlasRequest c = {};
-		c.atlas = layout_of(atlas);
-		c.vertex_count = vertex_count;
-		c.a.positions = positions;
-		c.a.normals = normals;
-		c.a.indices = indices;
+		AtlasRequest c = atlas_request(atlas, vertex_count, positions, normals, indices, valid, false, on_host);
 		c.a.texel_positions = texel_positions;
 		c.a.texel_normals = texel_normals;
-		c.a.valid = valid;
-		c.on_host = on_host;
 		return atlas_impl(r, c);
 	});
 }
@@ -1155,20 +1142,12 @@ int sdfr_atlas_bake(sdfr_renderer *r, const sdfr_atlas *atlas, int64_t vertex_co
 	float reach, uint32_t layers, float *albedo, float *normal, float *lit, int32_t *valid, int on_host)
 {
 	return guarded(r, [&]() -> int {
-		AtlasRequest c = {};
-		c.atlas = layout_of(atlas);
-		c.vertex_count = vertex_count;
-		c.a.positions = positions;
-		c.a.normals = normals;
-		c.a.indices = indices;
+		AtlasRequest c = atlas_request(atlas, vertex_count, positions, normals, indices, valid, true, on_host);
 		c.a.reach = reach;
 		c.a.layers = layers;
 		c.a.albedo = albedo;
 		c.a.normal = normal;
 		c.a.lit = lit;
-		c.a.valid = valid;
-		c.bake = true;
-		c.on_host = on_host;
 		return atlas_impl(r, c);
 	});
 }

@@ -78,16 +78,21 @@ struct AtlasRequest
 	bool bake; // sdfr_atlas_bake; else sdfr_atlas_texels
 	int on_host;
 };
-enum { ATLAS_STAGE_PIECES = 7 }; // more than a Carving holds (sdfr_stage.h: 6): the API cuts its staging buffer with stage_offsets itself
+// the arrays of a call in the order a host call stages them, as the pointer of AtlasArgs each goes through: three inputs, then the
+// answers of the texels [0] or of a bake [1]
+enum { ATLAS_STAGE_INPUTS = 3, ATLAS_STAGE_PIECES = 7 };
+#define SDFR_A(member) offsetof(AtlasArgs, member)
+static const size_t k_atlas_stage_slots[2][ATLAS_STAGE_PIECES] = {
+	{SDFR_A(positions), SDFR_A(normals), SDFR_A(indices), SDFR_A(texel_positions), SDFR_A(texel_normals), SDFR_A(valid), SDFR_A(valid) /* no bytes */},
+	{SDFR_A(positions), SDFR_A(normals), SDFR_A(indices), SDFR_A(albedo), SDFR_A(normal), SDFR_A(lit), SDFR_A(valid)}};
+#undef SDFR_A
 struct AtlasPlan
 {
 	int status; // QUERY_PLAN_*
 	const char *error;
 	AtlasArgs a;     // for the caller's arrays as device memory; a host call points them at its staging pieces
 	bool needs_scene; // a bake of at least one quad; everything else runs without one
-	// the arrays in the order they are staged: positions, normals, indices, then the answers -- a bake: albedo, normal, lit, valid;
-	// the texels: texel_positions, texel_normals, valid, nothing
-	size_t bytes[ATLAS_STAGE_PIECES];
+	size_t bytes[ATLAS_STAGE_PIECES]; // of the arrays of k_atlas_stage_slots[bake]; an array that is not there, and the texels' seventh: 0
 	uint32_t blocks; // of QUERY_BLOCK_ITEMS threads: one per 8 x 8 square of the image (QUERY_GRID_BLOCK_PER_TILE)
 };
 

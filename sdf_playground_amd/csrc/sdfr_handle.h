@@ -40,17 +40,19 @@ struct sdfr_device_buffer
 };
 
 // One device buffer cut into pieces (sdfr_stage.h): the parts of a workspace, or the device stand-ins of a caller's host arrays, of
-// which the answers are copied back at the end of the call.
+// which the answers are copied back at the end of the call (stage_host_arrays and copy_answers_back, sdfr_api.cpp).
 struct Carving
 {
 	size_t offset[sdfr::SDFR_STAGE_MAX_PIECES], total = 0;
 	sdfr_device_buffer *buffer = nullptr;
 	struct { void *host; const void *device; size_t bytes; } answers[sdfr::SDFR_STAGE_MAX_PIECES];
 	int n_answers = 0;
-	Carving(std::initializer_list<size_t> bytes)
+	Carving() {}
+	Carving(std::initializer_list<size_t> bytes) { cut(bytes.begin(), (int)bytes.size()); }
+	void cut(const size_t *bytes, int n)
 	{
-		assert(bytes.size() <= (size_t)sdfr::SDFR_STAGE_MAX_PIECES);
-		total = sdfr::stage_offsets(bytes.begin(), (int)bytes.size(), offset);
+		assert(n <= (int)sdfr::SDFR_STAGE_MAX_PIECES);
+		total = sdfr::stage_offsets(bytes, n, offset);
 	}
 	hipError_t reserve(sdfr_device_buffer &b) // (the caller first waits for whatever may still use the old one)
 	{
@@ -62,13 +64,14 @@ struct Carving
 	{
 		return reinterpret_cast<T *>(static_cast<char *>(buffer->ptr) + offset[k]);
 	}
-	// piece k, whose first `bytes` bytes go back to `host` at the end of the call (copy_answers_back, sdfr_api.cpp)
-	template <class T>
-	T *answer(int k, T *host, size_t bytes)
-	{
-		answers[n_answers++] = {host, piece<T>(k), bytes};
-		return piece<T>(k);
-	}
+};
+// An array of a call whose arrays are host or device memory: the pointer the kernel is handed it through (any T *: read and written
+// as a void *), its bytes, and whether the kernel reads it (an input) or writes it (an answer)
+struct StagedArray
+{
+	void *field;
+	size_t bytes;
+	bool input;
 };
 
 struct sdfr_renderer

@@ -30,6 +30,20 @@ SDF_HD uint32_t mesh_cell_index(const MeshGrid &g, int i, int j, int k)
 SDF_HD uint32_t mesh_point_count(const MeshGrid &g) { return (uint32_t)(g.n[0] + 1) * (uint32_t)(g.n[1] + 1) * (uint32_t)(g.n[2] + 1); }
 SDF_HD uint32_t mesh_cell_count(const MeshGrid &g) { return (uint32_t)g.n[0] * (uint32_t)g.n[1] * (uint32_t)g.n[2]; }
 
+#define SDFR_MESH_BLOCK 256 // threads of every kernel of sdfr_mesh.hip = elements a block of its prefix sums owns
+// words of scratch the exclusive prefix sum of n elements needs: the totals of its blocks, of their blocks ... while they are more than
+// one block (host only; the declaration: sdfr_kernels.h)
+inline size_t mesh_scan_sum_words(size_t n)
+{
+	size_t words = 0;
+	while (n > SDFR_MESH_BLOCK)
+	{
+		n = (n + SDFR_MESH_BLOCK - 1) / SDFR_MESH_BLOCK;
+		words += n;
+	}
+	return words;
+}
+
 // coordinate `axis` of the lattice points with index `i` on that axis: one multiply, then one add
 SDF_HD float mesh_coord(const MeshGrid &g, int axis, int i) { return g.origin[axis] + (float)i * g.cell; }
 

@@ -13,7 +13,6 @@
 
 namespace sdfr {
 
-#define SDFR_MESH_BLOCK 256 // threads of every kernel here = elements a scan block owns
 static_assert(SDFR_MESH_BLOCK % 64 == 0 && SDFR_MESH_BLOCK <= 1024, "whole waves");
 
 // exclusive prefix sum of `v` over the block's threads and the block's total: wave64 shuffles inside a wave, LDS across the waves
@@ -58,18 +57,7 @@ __global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_scan_down(uint32_t *__
 	if (i < n) data[i] = ex + (offsets ? offsets[blockIdx.x] : 0u);
 }
 
-size_t mesh_scan_sum_words(size_t n)
-{
-	size_t words = 0;
-	while (n > SDFR_MESH_BLOCK)
-	{
-		n = (n + SDFR_MESH_BLOCK - 1) / SDFR_MESH_BLOCK;
-		words += n;
-	}
-	return words;
-}
-
-// data [n] -> its exclusive prefix sum, in place; sums: mesh_scan_sum_words(n) words
+// data [n] -> its exclusive prefix sum, in place; sums: mesh_scan_sum_words(n) words (sdfr_mesh.h)
 static void scan_exclusive(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream)
 {
 	if (n <= SDFR_MESH_BLOCK)

@@ -1,0 +1,84 @@
+// sdfr_mesh_plan.h -- sdfr_mesh_extract (include/sdfr.h) as far as the host decides it: the argument checks in the order their errors
+// win, the grid, the lattice launch's arguments, the sizes of the workspace's four pieces, and once the two totals are read back whether
+// the call fills the caller's arrays and how many bytes of each.  Plain host arithmetic, no HIP call, like sdfr_query_plan.h and
+// sdfr_atlas_plan.h: mesh_impl (sdfr_api.cpp) carries the plan out, tests/test_mesh_plan_cpu.py checks it on a machine without a GPU.
+#pragma once
+#include "sdfr_mesh.h"
+#include "sdfr_query_plan.h"
+
+namespace sdfr {
+
+// What sdfr_mesh_extract was given; but for the grid's, the pointers are only compared with null here
+struct MeshRequest
+{
+	const MeshGrid *grid; // sdfr_mesh_grid, field for field
+	int64_t vertex_capacity, triangle_capacity;
+	float *positions, *normals;
+	uint32_t *indices;
+	const void *counts;
+	int on_host;
+};
+struct MeshPlan
+{
+	int status; // QUERY_PLAN_*
+	const char *error;
+	MeshGrid g;
+	LatticeArgs lattice; // but `rows` and `out`, which are the entry point's
+	size_t points, cells;
+	size_t work[4]; // bytes of the workspace's pieces: the lattice, the cells' scan, the points' scan, both scans' block sums
+};
+
+// The checks after the handle's and before the scene's, in the order their errors win.
+inline MeshPlan plan_mesh(const MeshRequest &c)
+{
+	MeshPlan p = {};
+	auto fail = [&p](const char *text) {
+		p.status = QUERY_PLAN_INVALID_ARGUMENT;
+		p.error = text;
+		return p;
+	};
+	if (!c.grid || !c.counts) return fail("null pointer");
+	if (!is_flag(c.on_host)) return fail("on_host must be 0 or 1");
+	const MeshGrid &g = *c.grid;
+	bool grid_ok = std::isfinite(g.cell) && g.cell > 0.f && std::isfinite(g.iso);
+	for (int a = 0; a < 3; ++a) grid_ok = grid_ok && std::isfinite(g.origin[a]) && g.n[a] >= 1 && g.n[a] <= 1024;
+	if (!grid_ok || (int64_t)(g.n[0] + 1) * (g.n[1] + 1) * (g.n[2] + 1) > (int64_t)1 << 30) return fail("bad mesh grid");
+	if (c.vertex_capacity < 0 || c.triangle_capacity < 0) return fail("negative capacity");
+	if ((c.vertex_capacity > 0 && !c.positions) || (c.triangle_capacity > 0 && !c.indices)) return fail("null array with a capacity");
+
+	p.g = g;
+	for (int a = 0; a < 3; ++a) p.lattice.origin[a] = g.origin[a];
+	p.lattice.cell = g.cell;
+	p.lattice.px = g.n[0] + 1;
+	p.lattice.py = g.n[1] + 1;
+	p.lattice.pz = g.n[2] + 1;
+	p.points = mesh_point_count(g);
+	p.cells = mesh_cell_count(g);
+	p.work[0] = p.points * 4;
+	p.work[1] = (p.cells + 1) * 4;
+	p.work[2] = (p.points + 1) * 4;
+	p.work[3] = (mesh_scan_sum_words(p.cells + 1) + mesh_scan_sum_words(p.points + 1)) * 4;
+	return p;
+}
+
+// The second phase, with the totals the device counted: the counts the caller is told, whether the capacities allow the call to fill the
+// arrays (a mesh without a vertex fills nothing), and the bytes of positions, normals (not wanted: 0) and indices it then writes
+struct MeshFill
+{
+	int64_t vertices, triangles;
+	bool fill;
+	size_t bytes[3];
+};
+inline MeshFill plan_mesh_fill(const MeshRequest &c, uint32_t vertices, uint32_t quads)
+{
+	MeshFill f = {};
+	f.vertices = (int64_t)vertices;
+	f.triangles = 2 * (int64_t)quads;
+	f.fill = f.vertices <= c.vertex_capacity && f.triangles <= c.triangle_capacity && vertices != 0;
+	f.bytes[0] = (size_t)vertices * 12;
+	f.bytes[1] = c.normals ? (size_t)vertices * 12 : 0;
+	f.bytes[2] = (size_t)f.triangles * 12;
+	return f;
+}
+
+} // namespace sdfr

@@ -32,7 +32,7 @@ SPLITS = hs.SPLITS
 DEBUG_VARS = {"debug_nx": 0.3, "debug_ny": 1.0}  # + the point debug_vars() puts the plane through: the driver's debug plane
 KEEP = 64 << 20                                   # k_query_stage_keep (sdfr_api.cpp): what a handle keeps of `query` and of `mesh`
 STAGE_ALIGN = 256                                 # SDFR_STAGE_ALIGN (sdfr_stage.h)
-MESH_BLOCK = 256                                  # SDFR_MESH_BLOCK (sdfr_mesh.hip)
+MESH_BLOCK = 256                                  # SDFR_MESH_BLOCK (sdfr_mesh.h)
 HIT_BYTES, SURFACE_BYTES, OCCLUSION_BYTES, LIGHTING_BYTES, LIGHTS_BYTES = 48, 128, 16, 64, 8 * 80
 
 # argument errors refused on the host before anything is launched: (kind, sdfr_last_error); all SDFR_ERR_INVALID_ARGUMENT but the capacities
@@ -70,7 +70,7 @@ def stage_total(pieces):
 
 
 def staging_bytes(step):
-    """bytes of `query` a HOST call stages, by the formulas of the plans (sdfr_query_plan.h, sdfr_atlas_plan.h, mesh_impl); a mesh
+    """bytes of `query` a HOST call stages, by the formulas of the plans (sdfr_query_plan.h, sdfr_atlas_plan.h, sdfr_mesh_plan.h); a mesh
     extraction's are known only with its counts: None"""
     p = step
     n = p.get("n", 0)
@@ -94,8 +94,8 @@ def staging_bytes(step):
 
 
 def workspace_bytes(dims):
-    """bytes of `mesh` an extraction over `dims` cells needs: the Carving of mesh_impl (sdfr_api.cpp)"""
-    def scan_sum_words(n):  # mesh_scan_sum_words (sdfr_mesh.hip)
+    """bytes of `mesh` an extraction over `dims` cells needs: the four pieces of plan_mesh (sdfr_mesh_plan.h)"""
+    def scan_sum_words(n):  # mesh_scan_sum_words (sdfr_mesh.h)
         words = 0
         while n > MESH_BLOCK:
             n = (n + MESH_BLOCK - 1) // MESH_BLOCK

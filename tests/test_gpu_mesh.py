@@ -114,7 +114,7 @@ def test_iso_and_a_dyadic_cell(renderer):
 
 
 def test_scan_at_depth(renderer):
-    # The prefix sums work on blocks of 256 elements (SDFR_MESH_BLOCK, sdfr_mesh.hip) and recurse on the block totals.  48^3 cells =
+    # The prefix sums work on blocks of 256 elements (SDFR_MESH_BLOCK, sdfr_mesh.h) and recurse on the block totals.  48^3 cells =
     # 110592 (+1) flags: 433 blocks, whose totals take 2 blocks, whose totals take the final single block -- so both levels that
     # can have more than one block do, for the cells and for the 49^3 = 117649 (+1) lattice points alike (460 -> 2 -> 1).
     scene, origin, cell, dims = "labyrinth", (-5.5, -0.25, -3.5), 0.125, (48, 48, 48)
@@ -266,23 +266,34 @@ def test_arguments(renderer):
     o, dims = (-0.5, -0.3, -0.5), (8, 8, 8)
     buf, ibuf = np.zeros((4096, 3), np.float32), np.zeros((8192, 3), np.uint32)
     INVALID, NO_SCENE = -1, -4
+
+    def refused(text, *args, **kwargs):
+        """SDFR_ERR_INVALID_ARGUMENT, with the text tests/test_mesh_plan_cpu.py names for the fault"""
+        return _raw(L, h, *args, **kwargs)[0] == INVALID and L.sdfr_last_error(h).decode() == text
+
     assert _raw(L, h, _grid(o, 0.1, dims), 4096, 8192, buf, None, ibuf)[0] == 0  # (normals may be NULL)
     bad_grids = [_grid(o, 0.0, dims), _grid(o, -0.1, dims), _grid(o, float("inf"), dims), _grid(o, float("nan"), dims),
                  _grid((float("nan"), 0.0, 0.0), 0.1, dims), _grid((0.0, float("inf"), 0.0), 0.1, dims), _grid(o, 0.1, dims, float("nan")),
                  _grid(o, 0.1, (0, 8, 8)), _grid(o, 0.1, (8, -1, 8)), _grid(o, 0.1, (8, 8, 1025)), _grid(o, 0.1, (1024, 1024, 1024))]
     for g in bad_grids:
-        assert _raw(L, h, g, 0, 0, None, None, None)[0] == INVALID
-    assert _raw(L, h, _grid(o, 0.1, (1023, 1023, 1023)), 0, 0, None, None, None, on_host=2)[0] == INVALID  # (the largest grid is a good one)
+        assert refused("bad mesh grid", g, 0, 0, None, None, None)
+    assert refused("on_host must be 0 or 1", _grid(o, 0.1, (1023, 1023, 1023)), 0, 0, None, None, None, on_host=2)  # (the largest grid is a good one)
     g = _grid(o, 0.1, dims)
-    assert _raw(L, h, None, 0, 0, None, None, None)[0] == INVALID
+    assert refused("null pointer", None, 0, 0, None, None, None)
     assert L.sdfr_mesh_extract(h, ctypes.byref(g), 0, 0, None, None, None, None, 1) == INVALID  # counts is required
-    assert _raw(L, h, g, 1, 0, None, None, None)[0] == INVALID
-    assert _raw(L, h, g, 0, 1, None, None, None)[0] == INVALID
-    assert _raw(L, h, g, 4096, 1, buf, None, None)[0] == INVALID
-    assert _raw(L, h, g, -1, 0, None, None, None)[0] == INVALID
-    assert _raw(L, h, g, 0, -1, None, None, None)[0] == INVALID
+    assert L.sdfr_last_error(h).decode() == "null pointer"
+    assert refused("null array with a capacity", g, 1, 0, None, None, None)
+    assert refused("null array with a capacity", g, 0, 1, None, None, None)
+    assert refused("null array with a capacity", g, 4096, 1, buf, None, None)
+    assert refused("negative capacity", g, -1, 0, None, None, None)
+    assert refused("negative capacity", g, 0, -1, None, None, None)
     for bad in (-1, 2):
-        assert _raw(L, h, g, 0, 0, None, None, None, on_host=bad)[0] == INVALID
+        assert refused("on_host must be 0 or 1", g, 0, 0, None, None, None, on_host=bad)
+    # two faults at once: the text of the one checked first
+    assert refused("null pointer", None, 0, 0, None, None, None, on_host=2)
+    assert refused("on_host must be 0 or 1", bad_grids[0], 0, 0, None, None, None, on_host=2)
+    assert refused("bad mesh grid", bad_grids[7], -1, 0, None, None, None)
+    assert refused("negative capacity", g, -1, 1, None, None, None)
     assert _raw(L, None, g, 0, 0, None, None, None)[0] == INVALID
     fresh = sp.SDFRenderer(0)
     try:

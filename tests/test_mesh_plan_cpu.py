@@ -1,0 +1,217 @@
+"""CPU tier: the plan of sdfr_mesh_extract (sdf_playground_amd/csrc/sdfr_mesh_plan.h, built as the stand-alone program
+tests/cpp/mesh_plan_host.cpp).  The rules mesh_impl carried inline before it had a plan are spelled out here a second time (parent_rules:
+the statuses, the error texts and their precedence, the grid, the lattice, the workspace's four pieces, the fill decision and the answer
+sizes), and the plan has to agree with them for every argument fault, every grid and every pair of counts below."""
+import math
+import os
+import struct
+import subprocess
+
+import pytest
+
+import handle_mixed_sequences as hm
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
+BUILD = os.path.join(HERE, "cpp", "_build")
+
+INVALID = -1  # SDFR_ERR_INVALID_ARGUMENT
+NULL_POINTER, BAD_ON_HOST, BAD_GRID = "null pointer", "on_host must be 0 or 1", "bad mesh grid"
+NEGATIVE_CAPACITY, NULL_ARRAY = "negative capacity", "null array with a capacity"
+ORIGIN, DIMS = (-0.5, -0.3, -0.5), (8, 8, 8)
+NAN, INF = float("nan"), float("inf")
+
+
+def _exe(name, flags):
+    os.makedirs(BUILD, exist_ok=True)
+    out = os.path.join(BUILD, name)
+    src = os.path.join(HERE, "cpp", "mesh_plan_host.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("sdfr_mesh_plan.h", "sdfr_mesh.h", "sdfr_math.h", "sdfr_query_plan.h", "sdfr_query_args.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        # plain g++: host arithmetic, no HIP header on the include path
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror"] + flags + ["-I" + CSRC, "-o", out + ".tmp", src], check=True)
+        os.replace(out + ".tmp", out)
+    return out
+
+
+@pytest.fixture(scope="module")
+def exe():
+    return _exe("mesh_plan_host", [])
+
+
+# ---- requests, as sdfr_mesh_extract makes them -----------------------------------------------------------------------------------------
+def request(origin=ORIGIN, cell=0.1, dims=DIMS, iso=0.0, grid=True, vcap=0, tcap=0, positions=False, normals=False, indices=False, counts=True,
+            on_host=0, V=0, Q=0):
+    """the arrays: given or null; V, Q: the totals the device counts, for the second phase"""
+    return dict(origin=origin, cell=cell, dims=dims, iso=iso, grid=grid, vcap=vcap, tcap=tcap, positions=positions, normals=normals, indices=indices,
+                counts=counts, on_host=on_host, V=V, Q=Q)
+
+
+def line_of(r):
+    f = lambda v: repr(float(v))  # noqa: E731 ("nan", "inf" and the shortest decimal of a double: strtof reads them all)
+    return " ".join([str(int(r["grid"]))] + [f(v) for v in r["origin"]] + [f(r["cell"])] + [str(n) for n in r["dims"]] + [f(r["iso"])]
+                    + [str(r["vcap"]), str(r["tcap"])] + [str(int(r[a])) for a in ("positions", "normals", "indices", "counts")]
+                    + [str(r["on_host"]), str(r["V"]), str(r["Q"])])
+
+
+def f32_bits(v):
+    return struct.unpack("I", struct.pack("f", v))[0]
+
+
+# ---- the rules of mesh_impl (sdfr_api.cpp) before the plan --------------------------------------------------------------------------------
+def scan_sum_words(n):
+    words = 0
+    while n > 256:
+        n = (n + 255) // 256
+        words += n
+    return words
+
+
+def parent_rules(r):
+    """-> (status, text, plan or None)"""
+    if not r["grid"] or not r["counts"]:
+        return INVALID, NULL_POINTER, None
+    if r["on_host"] not in (0, 1):
+        return INVALID, BAD_ON_HOST, None
+    nx, ny, nz = r["dims"]
+    cell = struct.unpack("f", struct.pack("f", r["cell"]))[0]
+    ok = math.isfinite(cell) and cell > 0 and math.isfinite(r["iso"]) and all(math.isfinite(v) for v in r["origin"])
+    ok = ok and all(1 <= n <= 1024 for n in r["dims"])
+    if not ok or (nx + 1) * (ny + 1) * (nz + 1) > 1 << 30:
+        return INVALID, BAD_GRID, None
+    if r["vcap"] < 0 or r["tcap"] < 0:
+        return INVALID, NEGATIVE_CAPACITY, None
+    if (r["vcap"] > 0 and not r["positions"]) or (r["tcap"] > 0 and not r["indices"]):
+        return INVALID, NULL_ARRAY, None
+    points, cells = (nx + 1) * (ny + 1) * (nz + 1), nx * ny * nz
+    work = [points * 4, (cells + 1) * 4, (points + 1) * 4, (scan_sum_words(cells + 1) + scan_sum_words(points + 1)) * 4]
+    V, T = r["V"], 2 * r["Q"]
+    fill = V <= r["vcap"] and T <= r["tcap"] and V != 0
+    return 0, "", dict(points=points, cells=cells, work=work, fill=fill, V=V, T=T, bytes=[V * 12, V * 12 if r["normals"] else 0, T * 12])
+
+
+def expected_line(r):
+    status, text, plan = parent_rules(r)
+    out = "%d;%s" % (status, text)
+    if plan:
+        nx, ny, nz = r["dims"]
+        o = " ".join("%08x" % f32_bits(v) for v in r["origin"])
+        out += ";%s %08x %08x %d %d %d" % (o, f32_bits(r["cell"]), f32_bits(r["iso"]), nx, ny, nz)
+        out += ";%s %08x %d %d %d" % (o, f32_bits(r["cell"]), nx + 1, ny + 1, nz + 1)
+        out += ";%d %d;%d %d %d %d" % ((plan["points"], plan["cells"]) + tuple(plan["work"]))
+        out += ";%d %d %d;%d %d %d" % ((int(plan["fill"]), plan["V"], plan["T"]) + tuple(plan["bytes"]))
+    return out
+
+
+def run(exe, reqs):
+    text = "".join(line_of(r) + "\n" for r in reqs)
+    lines = subprocess.run([exe], input=text, check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(lines) == len(reqs)
+    return lines
+
+
+# ---- the cases ------------------------------------------------------------------------------------------------------------------------
+# the eleven bad grids of tests/test_gpu_mesh.py::test_arguments
+BAD_GRIDS = [dict(cell=0.0), dict(cell=-0.1), dict(cell=INF), dict(cell=NAN), dict(origin=(NAN, 0.0, 0.0)), dict(origin=(0.0, INF, 0.0)), dict(iso=NAN),
+             dict(dims=(0, 8, 8)), dict(dims=(8, -1, 8)), dict(dims=(8, 8, 1025)), dict(dims=(1024, 1024, 1024))]
+
+
+def fault_cases():
+    """(what, request, the text that wins)"""
+    cases = [("bad grid %r" % g, request(**g), BAD_GRID) for g in BAD_GRIDS]
+    cases += [("null grid", request(grid=False), NULL_POINTER), ("null counts", request(counts=False), NULL_POINTER),
+              ("on_host -1", request(on_host=-1), BAD_ON_HOST), ("on_host 2", request(on_host=2), BAD_ON_HOST),
+              ("vertex capacity -1", request(vcap=-1), NEGATIVE_CAPACITY), ("triangle capacity -1", request(tcap=-1), NEGATIVE_CAPACITY),
+              ("positions null", request(vcap=1), NULL_ARRAY), ("indices null", request(tcap=1), NULL_ARRAY),
+              ("indices null, positions there", request(vcap=4096, tcap=1, positions=True), NULL_ARRAY)]
+    # two faults at once, one request per adjacent pair of checks: the earlier text wins
+    cases += [("null grid + on_host 2", request(grid=False, on_host=2), NULL_POINTER),
+              ("on_host 2 + bad grid", request(on_host=2, cell=0.0), BAD_ON_HOST),
+              ("bad grid + negative capacity", request(dims=(0, 8, 8), vcap=-1), BAD_GRID),
+              ("negative capacity + null array", request(vcap=-1, tcap=1), NEGATIVE_CAPACITY),
+              ("null array + negative capacity", request(vcap=1, tcap=-1), NEGATIVE_CAPACITY)]
+    return cases
+
+
+def good_cases():
+    return [("the largest grid", request(dims=(1023, 1023, 1023))),
+            ("normals null with a capacity", request(vcap=4096, tcap=8192, positions=True, indices=True)),
+            ("the counting call", request()), ("a host call", request(on_host=1, vcap=1, tcap=1, positions=True, normals=True, indices=True)),
+            ("arrays without a capacity", request(positions=True, normals=True, indices=True)),
+            ("iso and a negative origin", request(origin=(-1.5, 0.0, 2.25), cell=0.0625, dims=(48, 40, 44), iso=0.05))]
+
+
+WORKSPACE_DIMS = ((1, 1, 1), (6, 6, 6), (7, 7, 7), (40, 40, 40), (15, 16, 17), hm.BIG_LATTICE)
+
+
+def fill_cases():
+    """capacities 100 vertices and 50 triangles: the counts within, at and one past each; no vertex; no quad; normals wanted or not"""
+    cases = []
+    for normals in (False, True):
+        for V, Q in ((99, 10), (100, 10), (101, 10), (10, 24), (10, 25), (10, 26), (100, 25), (101, 26), (0, 0), (7, 0), (1, 1)):
+            cases.append(request(vcap=100, tcap=50, positions=True, normals=normals, indices=True, on_host=1, V=V, Q=Q))
+    # the counting call never fills; the largest counts a lattice of 2^30 points can have
+    cases += [request(V=5, Q=3), request(dims=(1023, 1023, 1023), vcap=1 << 30, tcap=1 << 33, positions=True, normals=True, indices=True, V=1 << 30, Q=3 << 30)]
+    return cases
+
+
+# ---- the tests ------------------------------------------------------------------------------------------------------------------------
+def test_argument_faults(exe):
+    """every argument fault of sdfr_mesh_extract: its status and its text, and of two faults the one checked first"""
+    cases = fault_cases()
+    got = run(exe, [r for _what, r, _text in cases])
+    for (what, r, text), line in zip(cases, got):
+        assert line == "%d;%s" % (INVALID, text), what
+        assert line == expected_line(r), what
+    assert {text for _w, _r, text in cases} == {NULL_POINTER, BAD_ON_HOST, BAD_GRID, NEGATIVE_CAPACITY, NULL_ARRAY}
+
+
+def test_good_requests(exe):
+    """the grid as it was given, the lattice's points per axis; 2^30 lattice points exactly are allowed, normals are optional"""
+    cases = good_cases()
+    got = run(exe, [r for _what, r in cases])
+    for (what, r), line in zip(cases, got):
+        assert line.startswith("0;;"), what
+        assert line == expected_line(r), what
+    assert got[0].split(";")[4] == "%d %d" % (1 << 30, 1023 ** 3)
+    assert got[5].split(";")[3].split()[4:] == ["49", "41", "45"]
+
+
+def test_workspace_sizes(exe):
+    """the four pieces, through every branch of the scan's recursion on its block totals"""
+    got = run(exe, [request(dims=d) for d in WORKSPACE_DIMS])
+    for dims, line in zip(WORKSPACE_DIMS, got):
+        assert line == expected_line(request(dims=dims)), dims
+        work = [int(x) for x in line.split(";")[5].split()]
+        points, cells = (dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1), dims[0] * dims[1] * dims[2]
+        assert work[:3] == [points * 4, cells * 4 + 4, points * 4 + 4]
+        assert hm.stage_total(work) == hm.workspace_bytes(dims), dims
+    sums = {dims: int(line.split(";")[5].split()[3]) // 4 for dims, line in zip(WORKSPACE_DIMS, got)}
+    assert sums[(1, 1, 1)] == 0                       # 2 and 9 elements: one block each
+    assert sums[(6, 6, 6)] == 2                       # 217 cells + 1: one block; 344 points + 1: two blocks
+    assert sums[(7, 7, 7)] == 2 + 3                   # 344 and 513 elements
+    assert sums[(40, 40, 40)] == 251 + (270 + 2)      # 64001 elements: 251 blocks; 68922: 270 blocks, whose totals take 2 more
+    assert sums[(15, 16, 17)] == 16 + 20              # 4081 and 4897 elements
+    assert hm.workspace_bytes(hm.BIG_LATTICE) > hm.KEEP
+
+
+def test_second_phase(exe):
+    """with the counts read back: fill only when both fit and there is a vertex; the bytes of positions, normals and indices"""
+    cases = fill_cases()
+    got = run(exe, cases)
+    for r, line in zip(cases, got):
+        assert line == expected_line(r), r
+    decided = {(r["V"], r["Q"], r["normals"]): line.split(";")[6:] for r, line in zip(cases[:22], got)}
+    assert decided[(100, 25, True)] == ["1 100 50", "1200 1200 600"]
+    assert decided[(100, 25, False)] == ["1 100 50", "1200 0 600"]
+    assert decided[(101, 10, True)][0] == "0 101 20" and decided[(10, 26, True)][0] == "0 10 52" and decided[(0, 0, True)][0] == "0 0 0"
+    assert decided[(7, 0, True)] == ["1 7 0", "84 84 0"]  # vertices without a quad: filled, and no index is written
+    assert got[-2].split(";")[6] == "0 5 6"
+    assert got[-1].split(";")[6:] == ["1 %d %d" % (1 << 30, 6 << 30), "%d %d %d" % (12 << 30, 12 << 30, 72 << 30)]
+
+
+def test_under_sanitizers(exe):
+    """the same program built with the address and undefined-behaviour sanitizers, over every request above: the same answers"""
+    reqs = [r for _w, r, _t in fault_cases()] + [r for _w, r in good_cases()] + [request(dims=d) for d in WORKSPACE_DIMS] + fill_cases()
+    checked = _exe("mesh_plan_host_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    assert run(checked, reqs) == run(exe, reqs)

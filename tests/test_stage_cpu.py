@@ -1,6 +1,6 @@
 """CPU tier: how one device buffer is cut into the stand-ins of a caller's host arrays (sdf_playground_amd/csrc/sdfr_stage.h, built as
 the stand-alone program tests/cpp/stage_host.cpp).  The offsets and totals of the header against the formulas the entry points
-carried before they shared it (query_impl and mesh_impl), spelled out here a second time."""
+carried before they shared it (query_impl, mesh_impl and atlas_impl), spelled out here a second time."""
 import os
 import subprocess
 
@@ -71,3 +71,30 @@ def test_mesh_staging(exe):
 
 def test_an_empty_piece_takes_no_room(exe):
     assert carve(exe, [[100, 0, 300], [256, 0, 0, 1], [0, 0, 7], []]) == [([0, 256, 256], 768), ([0, 256, 256, 256], 512), ([0, 0, 0], 256), ([], 0)]
+
+
+def test_atlas_staging(exe):
+    """atlas_impl's host arrays: positions, normals, indices, then the answers -- of a bake the planes of its layers and valid, of the
+    texel call the texels' positions, normals and valid, and no seventh"""
+    cases, want = [], []
+    for V, T in ((5, 6), (1000, 1996)):
+        for width, height in ((8, 8), (64, 16)):
+            texels = width * height
+            answers = [[texels * 12, texels * 12, texels * 4, 0]]  # sdfr_atlas_texels
+            for layers in range(1, 8):  # sdfr_atlas_bake: albedo 1, normal 2, lit 4
+                answers.append([texels * 16 if layers & bit else 0 for bit in (1, 2, 4)] + [texels * 4])
+            for out in answers:
+                pieces = [V * 12, V * 12, T * 12] + out
+                cases.append(pieces)
+                d_normals = up(V * 12)
+                d_indices = d_normals + up(V * 12)
+                d_out0 = d_indices + up(T * 12)
+                d_out1 = d_out0 + up(out[0])
+                d_out2 = d_out1 + up(out[1])
+                d_out3 = d_out2 + up(out[2])
+                want.append(([0, d_normals, d_indices, d_out0, d_out1, d_out2, d_out3], d_out3 + up(out[3])))
+    assert len(cases) == 2 * 2 * 8 and all(len(c) == 7 for c in cases)
+    assert carve(exe, cases) == want
+    # written out: V = 5, T = 6 at 8 x 8 texels, the texel call and a bake of albedo and lit
+    assert carve(exe, [[60, 60, 72, 768, 768, 256, 0], [60, 60, 72, 1024, 0, 1024, 256]]) == [([0, 256, 512, 768, 1536, 2304, 2560], 2560),
+                                                                                            ([0, 256, 512, 768, 1792, 1792, 2816], 3072)]
