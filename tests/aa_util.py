@@ -4,11 +4,10 @@ and planner built for the CPU (tests/cpp/resolve_host.cpp); compact strip buffer
 never imports this."""
 import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 
+import cppbuild
 import query_util as qu
 
 F = np.float32
@@ -93,14 +92,7 @@ _host = None
 def host_lib():
     global _host
     if _host is None:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        so = os.path.join(qu.BUILD, "libresolve_host.so")
-        src = os.path.join(qu.HERE, "cpp", "resolve_host.cpp")
-        deps = [src] + [os.path.join(qu.CSRC, f) for f in ("sdfr_resolve.h", "sdfr_aa_plan.h", "sdfr_launch_plan.h", "sdfr_frame.h", "sdfr_math.h")]
-        if qu._stale(so, deps):
-            subprocess.run(["g++"] + qu.FLAGS + ["-I" + qu.CSRC, "-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
+        L = ctypes.CDLL(qu.build_lib("resolve_host", "resolve_host.cpp", ["-I" + qu.CSRC], cppbuild.csrc_headers()))
         vp, ci, cu, ull = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_ulonglong
         L.rh_plan.argtypes = [ci, ci, ci, ull, vp]
         L.rh_plan.restype = None

@@ -4,8 +4,6 @@ library's atlas code built for the CPU (tests/cpp/atlas_host.cpp), the two test 
 comparison are query_util's.  Test infrastructure: the product never imports this."""
 import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 
@@ -26,12 +24,7 @@ _oracle = []
 
 def oracle_lib():
     if not _oracle:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        src, so = os.path.join(qu.HERE, "cpp", "atlas_oracle.cpp"), os.path.join(qu.BUILD, "libatlas_oracle.so")
-        if qu._stale(so, [src]):
-            subprocess.run(["g++"] + qu.FLAGS + ["-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
+        L = ctypes.CDLL(qu.build_lib("atlas_oracle", "atlas_oracle.cpp"))  # no header but the standard library's
         vp, i64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
         L.ao_layout.argtypes = [i64, ci, ci, vp]
         L.ao_uvs.argtypes = [i64, ci, ci, vp]

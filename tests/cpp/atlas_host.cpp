@@ -7,38 +7,9 @@
 #include "sdfr_hostframe.h"
 #include "sdfr_atlas.h"
 #include "sdfr_atlas_plan.h"
-#ifdef SDFR_HLSL_SCENE_FILE
-#include "sdfr_hlsl.h"
-namespace sdfr {
-#include SDFR_HLSL_SCENE_FILE
-} // namespace sdfr
-#endif
-
-#include <cstring>
-#include <thread>
-#include <vector>
-
-using namespace sdfr;
+#include "host_common.h"
 
 namespace {
-
-// blocks [0, n) over up to 16 threads, in contiguous chunks
-template <class F>
-void parallel_blocks(int n, F fn)
-{
-	int t = (int)std::thread::hardware_concurrency();
-	t = t < 1 ? 1 : (t > 16 ? 16 : t);
-	if (n < 16) t = 1;
-	std::vector<std::thread> pool;
-	const int chunk = (n + t - 1) / t;
-	for (int k = 0; k < t; ++k)
-	{
-		const int a = k * chunk, b = a + chunk < n ? a + chunk : n;
-		if (a >= b) break;
-		pool.emplace_back([=]() { fn(a, b); });
-	}
-	for (auto &th : pool) th.join();
-}
 
 // one texel of a bake as the kernel's lane does it after the texel map
 typedef uint32_t (*TexelFn)(const FrameU &, vec3, vec3, float, uint32_t, uint32_t *, uint32_t *, uint32_t *);
@@ -47,36 +18,15 @@ uint32_t texel_of(const FrameU &U, vec3 P, vec3 N, float reach, uint32_t layers,
 {
 	return atlas_bake_texel<Scene, DBG>(U, P, N, reach, layers, albedo, normal, lit);
 }
-template <class Scene>
-TexelFn fn_of(const FrameU &U)
+// the family's function for a scene and a frame, the debug or the plain instantiation: what latch hands out
+struct Pick
 {
-	return frame_needs_debug(U) ? &texel_of<Scene, true> : &texel_of<Scene, false>;
-}
-
-// the frame as the library latches it for a query (latch_into, sdfr_api.cpp); false: no such scene
-bool latch(const char *scene, FrameU &U, TexelFn &f)
-{
-#ifdef SDFR_HLSL_SCENE_FILE
-	(void)scene;
-	frame_derive(U, -1);
-#ifdef SDFR_SCENE_HAS_PREPARE
-	Scene::prepare(U);
-#endif
-	f = fn_of<Scene>(U);
-	return true;
-#else
-	const int si = scene_index(scene);
-	if (si < 0) return false;
-	frame_derive(U, si);
-	switch (si)
+	template <class Scene>
+	static TexelFn of(const FrameU &U)
 	{
-#define SDFR_FN(I, S) case I: f = fn_of<S>(U); return true;
-		SDFR_FOR_EACH_SCENE(SDFR_FN)
-#undef SDFR_FN
+		return frame_needs_debug(U) ? &texel_of<Scene, true> : &texel_of<Scene, false>;
 	}
-	return false;
-#endif
-}
+};
 
 // the lanes of block `block` as the kernels map them; fn(x, y, state, P, N)
 template <class F>
@@ -192,7 +142,7 @@ int ah_texels(int64_t triangles, int tile, int width, int64_t vertex_count, cons
 	AtlasArgs g;
 	if (!args_of(triangles, tile, width, vertex_count, positions, normals, indices, g)) return -1;
 	const int blocks = (g.width / 8) * (g.height / 8);
-	parallel_blocks(blocks, [&](int lo, int hi) {
+	parallel_items(blocks, 16, [&](int lo, int hi) {
 		for (int b = lo; b < hi; ++b)
 			block_texels(g, (uint32_t)b, [&](uint32_t x, uint32_t y, int state, vec3 p, vec3 n) {
 				const size_t i = (size_t)y * (size_t)g.width + x;
@@ -208,14 +158,13 @@ int ah_texels(int64_t triangles, int tile, int width, int64_t vertex_count, cons
 int ah_bake(const char *scene, const FrameU *frame, int64_t triangles, int tile, int width, int64_t vertex_count, const float *positions, const float *normals,
 	const uint32_t *indices, float reach, uint32_t layers, uint32_t *albedo, uint32_t *normal, uint32_t *lit, int32_t *valid)
 {
-	FrameU U = *frame;
-	U.width = U.height = 1;
+	FrameU U;
 	TexelFn f;
-	if (!latch(scene, U, f)) return -1;
+	if (!latch<Pick>(scene, frame, U, f)) return -1;
 	AtlasArgs g;
 	if (!args_of(triangles, tile, width, vertex_count, positions, normals, indices, g)) return -1;
 	const int blocks = (g.width / 8) * (g.height / 8);
-	parallel_blocks(blocks, [&](int lo, int hi) {
+	parallel_items(blocks, 16, [&](int lo, int hi) {
 		for (int b = lo; b < hi; ++b)
 			block_texels(g, (uint32_t)b, [&](uint32_t x, uint32_t y, int state, vec3 p, vec3 n) {
 				const size_t i = (size_t)y * (size_t)g.width + x;

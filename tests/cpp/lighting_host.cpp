@@ -4,47 +4,10 @@
 // with -DSDFR_HLSL_SCENE_FILE="<generated file>".  The product never loads this.
 #include "sdfr_hostframe.h"
 #include "sdfr_lighting.h"
-#ifdef SDFR_HLSL_SCENE_FILE
-#include "sdfr_hlsl.h"
-namespace sdfr {
-#include SDFR_HLSL_SCENE_FILE
-} // namespace sdfr
-#endif
-
-#include <cstring>
-#include <thread>
-#include <vector>
-
-using namespace sdfr;
+#include "host_common.h"
 
 namespace {
 
-// items [0, n) over up to 16 threads, in contiguous chunks
-template <class F>
-void parallel_items(int n, F fn)
-{
-	int t = (int)std::thread::hardware_concurrency();
-	t = t < 1 ? 1 : (t > 16 ? 16 : t);
-	if (n < 256) t = 1;
-	std::vector<std::thread> pool;
-	const int chunk = (n + t - 1) / t;
-	for (int k = 0; k < t; ++k)
-	{
-		const int a = k * chunk, b = a + chunk < n ? a + chunk : n;
-		if (a >= b) break;
-		pool.emplace_back([=]() { fn(a, b); });
-	}
-	for (auto &th : pool) th.join();
-}
-
-// one item of a kind (QUERY_RAYS, QUERY_MESH: a = origin / position, b = dir / normal; QUERY_PICK: px, py), as the kernel's lane does it
-struct Item
-{
-	int kind;
-	const float *a, *b;
-	int px, py;
-	float dist_max, reach;
-};
 typedef void (*ItemFn)(const FrameU &, const Item &, uint32_t *, uint32_t *, uint32_t *);
 
 // where an item's eight light samples go, as the kernel's LightSampleStore: nowhere if they are not wanted
@@ -59,90 +22,43 @@ template <class Scene, bool DBG>
 void item_of(const FrameU &U, const Item &it, uint32_t *hit, uint32_t *rec, uint32_t *samples)
 {
 	QueryRay ray;
-	bool in_frame = true;
-	if (it.kind == QUERY_PICK)
-		in_frame = query_pixel_ray(U, it.px, it.py, ray);
-	else if (it.kind == QUERY_MESH)
-		ray = query_mesh_ray(V3(it.a[0], it.a[1], it.a[2]), V3(it.b[0], it.b[1], it.b[2]), it.reach);
-	else
-		ray = query_plain_ray(V3(it.a[0], it.a[1], it.a[2]), V3(it.b[0], it.b[1], it.b[2]), it.dist_max);
+	const bool in_frame = item_ray(U, it, ray);
 	query_lighting<Scene, DBG>(U, ray, in_frame, hit, rec, HostSamples{samples});
 }
-template <class Scene>
-ItemFn fn_of(const FrameU &U)
+// the family's function for a scene and a frame, the debug or the plain instantiation: what latch hands out
+struct Pick
 {
-	return frame_needs_debug(U) ? &item_of<Scene, true> : &item_of<Scene, false>;
-}
-
-// the frame as the library latches it for a query (latch_into, sdfr_api.cpp); false: no such scene
-bool latch(const char *scene, FrameU &U, ItemFn &f)
-{
-#ifdef SDFR_HLSL_SCENE_FILE
-	(void)scene;
-	frame_derive(U, -1);
-#ifdef SDFR_SCENE_HAS_PREPARE
-	Scene::prepare(U);
-#endif
-	f = fn_of<Scene>(U);
-	return true;
-#else
-	const int si = scene_index(scene);
-	if (si < 0) return false;
-	frame_derive(U, si);
-	switch (si)
+	template <class Scene>
+	static ItemFn of(const FrameU &U)
 	{
-#define SDFR_FN(I, S) case I: f = fn_of<S>(U); return true;
-		SDFR_FOR_EACH_SCENE(SDFR_FN)
-#undef SDFR_FN
+		return frame_needs_debug(U) ? &item_of<Scene, true> : &item_of<Scene, false>;
 	}
-	return false;
-#endif
-}
+};
+
+// item i's eight samples in `lights`, which may be null
+uint32_t *samples_of(uint32_t *lights, int i) { return lights ? lights + (size_t)QUERY_LIGHT_SLOTS * QUERY_LIGHT_SAMPLE_WORDS * i : nullptr; }
 
 } // namespace
 
 extern "C" {
 
-// `frame`: the inputs of a FrameU (tests/hostsim frame_from_oracle); width and height are set here as the library sets them.
+// `frame`: the inputs of a FrameU (tests/hostsim frame_from_oracle); width and height are set as the library sets them (latch).
 // lights may be null.  mesh = 0: rays a -> b, max_distance `reach` (0: the range); mesh = 1: the rays towards vertices a with normals b from `reach` outside
 int lh_rays(const char *scene, const FrameU *frame, int mesh, int n, const float *a, const float *b, float reach, uint32_t *hits, uint32_t *lighting, uint32_t *lights)
 {
-	FrameU U = *frame;
-	U.width = U.height = 1;
+	FrameU U;
 	ItemFn f;
-	if (!latch(scene, U, f)) return -1;
-	Item it = {};
-	it.kind = mesh ? QUERY_MESH : QUERY_RAYS;
-	it.dist_max = reach == 0.f ? U.range : reach; // (a mesh's rays: 2 * reach, query_mesh_ray)
-	it.reach = reach;
-	parallel_items(n, [&](int lo, int hi) {
-		Item mine = it;
-		for (int i = lo; i < hi; ++i)
-		{
-			mine.a = a + 3 * i;
-			mine.b = b + 3 * i;
-			f(U, mine, hits + QUERY_HIT_WORDS * i, lighting + QUERY_LIGHTING_WORDS * i, lights ? lights + (size_t)QUERY_LIGHT_SLOTS * QUERY_LIGHT_SAMPLE_WORDS * i : nullptr);
-		}
-	});
+	if (!latch<Pick>(scene, frame, U, f)) return -1;
+	ray_items(U, mesh, n, a, b, reach,
+		[&](const Item &it, int i) { f(U, it, hits + QUERY_HIT_WORDS * i, lighting + QUERY_LIGHTING_WORDS * i, samples_of(lights, i)); });
 	return 0;
 }
 int lh_pick(const char *scene, const FrameU *frame, int width, int height, int n, const int32_t *pixels, uint32_t *hits, uint32_t *lighting, uint32_t *lights)
 {
-	FrameU U = *frame;
-	U.width = width;
-	U.height = height;
+	FrameU U;
 	ItemFn f;
-	if (!latch(scene, U, f)) return -1;
-	parallel_items(n, [&](int lo, int hi) {
-		Item mine = {};
-		mine.kind = QUERY_PICK;
-		for (int i = lo; i < hi; ++i)
-		{
-			mine.px = pixels[2 * i];
-			mine.py = pixels[2 * i + 1];
-			f(U, mine, hits + QUERY_HIT_WORDS * i, lighting + QUERY_LIGHTING_WORDS * i, lights ? lights + (size_t)QUERY_LIGHT_SLOTS * QUERY_LIGHT_SAMPLE_WORDS * i : nullptr);
-		}
-	});
+	if (!latch<Pick>(scene, frame, U, f, width, height)) return -1;
+	pick_items(n, pixels, [&](const Item &it, int i) { f(U, it, hits + QUERY_HIT_WORDS * i, lighting + QUERY_LIGHTING_WORDS * i, samples_of(lights, i)); });
 	return 0;
 }
 int lh_frame_size() { return (int)sizeof(FrameU); }

@@ -5,38 +5,9 @@
 // and once per run-time scene with -DSDFR_HLSL_SCENE_FILE="<generated file>".  The product never loads this.
 #include "sdfr_hostframe.h"
 #include "sdfr_occlusion.h"
-#ifdef SDFR_HLSL_SCENE_FILE
-#include "sdfr_hlsl.h"
-namespace sdfr {
-#include SDFR_HLSL_SCENE_FILE
-} // namespace sdfr
-#endif
-
-#include <cstring>
-#include <thread>
-#include <vector>
-
-using namespace sdfr;
+#include "host_common.h"
 
 namespace {
-
-// items [0, n) over up to 16 threads, in contiguous chunks
-template <class F>
-void parallel_items(int n, F fn)
-{
-	int t = (int)std::thread::hardware_concurrency();
-	t = t < 1 ? 1 : (t > 16 ? 16 : t);
-	if (n < 8) t = 1;
-	std::vector<std::thread> pool;
-	const int chunk = (n + t - 1) / t;
-	for (int k = 0; k < t; ++k)
-	{
-		const int a = k * chunk, b = a + chunk < n ? a + chunk : n;
-		if (a >= b) break;
-		pool.emplace_back([=]() { fn(a, b); });
-	}
-	for (auto &th : pool) th.join();
-}
 
 typedef void (*ItemFn)(const FrameU &, vec3, vec3, uint32_t, float, float, uint32_t *);
 
@@ -60,51 +31,29 @@ void item_of(const FrameU &U, vec3 p, vec3 n, uint32_t valid, float bias, float 
 		}
 	occlusion_record(mask, count, rec);
 }
-template <class Scene>
-ItemFn fn_of(const FrameU &U)
+// the family's function for a scene and a frame, the debug or the plain instantiation: what latch hands out
+struct Pick
 {
-	return frame_needs_debug(U) ? &item_of<Scene, true> : &item_of<Scene, false>;
-}
-
-// the frame as the library latches it for a query (latch_into, sdfr_api.cpp); false: no such scene
-bool latch(const char *scene, FrameU &U, ItemFn &f)
-{
-#ifdef SDFR_HLSL_SCENE_FILE
-	(void)scene;
-	frame_derive(U, -1);
-#ifdef SDFR_SCENE_HAS_PREPARE
-	Scene::prepare(U);
-#endif
-	f = fn_of<Scene>(U);
-	return true;
-#else
-	const int si = scene_index(scene);
-	if (si < 0) return false;
-	frame_derive(U, si);
-	switch (si)
+	template <class Scene>
+	static ItemFn of(const FrameU &U)
 	{
-#define SDFR_FN(I, S) case I: f = fn_of<S>(U); return true;
-		SDFR_FOR_EACH_SCENE(SDFR_FN)
-#undef SDFR_FN
+		return frame_needs_debug(U) ? &item_of<Scene, true> : &item_of<Scene, false>;
 	}
-	return false;
-#endif
-}
+};
 
 } // namespace
 
 extern "C" {
 
-// `frame`: the inputs of a FrameU (tests/hostsim frame_from_oracle); width and height are set here as the library sets them.
+// `frame`: the inputs of a FrameU (tests/hostsim frame_from_oracle); width and height are set as the library sets them (latch).
 // hits = null: items points[i], normals[i]; else the hit records [n][12]
 int oh_occlusion(const char *scene, const FrameU *frame, int n, const float *points, const float *normals, const uint32_t *hits, float bias, float radius,
 	uint32_t *out)
 {
-	FrameU U = *frame;
-	U.width = U.height = 1;
+	FrameU U;
 	ItemFn f;
-	if (!latch(scene, U, f)) return -1;
-	parallel_items(n, [&](int lo, int hi) {
+	if (!latch<Pick>(scene, frame, U, f)) return -1;
+	parallel_items(n, 8, [&](int lo, int hi) {
 		for (int i = lo; i < hi; ++i)
 		{
 			if (hits)

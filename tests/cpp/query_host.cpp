@@ -1,41 +1,12 @@
 // tests/cpp/query_host.cpp -- TEST-ONLY: the library's scene queries (sdf_playground_amd/csrc/sdfr_query.h) compiled for the CPU,
 // as tests/hostsim compiles the per-pixel pipeline, so that the CPU test tier can compare them with the oracle's definitions
 // (query_oracle.cpp) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene with
-// -DSDFR_HLSL_SCENE_FILE="<generated file>" (tests/hostsim: build_hlsl).  The product never loads this.
+// -DSDFR_HLSL_SCENE_FILE="<generated file>" (host_common.h).  The product never loads this.
 #include "sdfr_hostframe.h"
 #include "sdfr_query.h"
-#ifdef SDFR_HLSL_SCENE_FILE
-#include "sdfr_hlsl.h"
-namespace sdfr {
-#include SDFR_HLSL_SCENE_FILE
-} // namespace sdfr
-#endif
-
-#include <cstring>
-#include <thread>
-#include <vector>
-
-using namespace sdfr;
+#include "host_common.h"
 
 namespace {
-
-// items [0, n) over up to 16 threads, in contiguous chunks
-template <class F>
-void parallel_items(int n, F fn)
-{
-	int t = (int)std::thread::hardware_concurrency();
-	t = t < 1 ? 1 : (t > 16 ? 16 : t);
-	if (n < 256) t = 1;
-	std::vector<std::thread> pool;
-	const int chunk = (n + t - 1) / t;
-	for (int k = 0; k < t; ++k)
-	{
-		const int a = k * chunk, b = a + chunk < n ? a + chunk : n;
-		if (a >= b) break;
-		pool.emplace_back([=]() { fn(a, b); });
-	}
-	for (auto &th : pool) th.join();
-}
 
 struct Fns
 {
@@ -71,37 +42,16 @@ void pick_of(const FrameU &U, int n, const int32_t *px, uint32_t *hits)
 {
 	for (int i = 0; i < n; ++i) query_pick<Scene, DBG>(U, px[2 * i], px[2 * i + 1], hits + QUERY_HIT_WORDS * i);
 }
-template <class Scene>
-Fns fns_of(const FrameU &U)
+// the family's function for a scene and a frame, the debug or the plain instantiation: what latch hands out
+struct Pick
 {
-	if (frame_needs_debug(U)) return Fns{&points_of<Scene, true>, &rays_of<Scene, true>, &pick_of<Scene, true>};
-	return Fns{&points_of<Scene, false>, &rays_of<Scene, false>, &pick_of<Scene, false>};
-}
-
-// the frame as the library latches it for a query (latch_into, sdfr_api.cpp); false: no such scene
-bool latch(const char *scene, FrameU &U, Fns &f)
-{
-#ifdef SDFR_HLSL_SCENE_FILE
-	(void)scene;
-	frame_derive(U, -1);
-#ifdef SDFR_SCENE_HAS_PREPARE
-	Scene::prepare(U);
-#endif
-	f = fns_of<Scene>(U);
-	return true;
-#else
-	const int si = scene_index(scene);
-	if (si < 0) return false;
-	frame_derive(U, si);
-	switch (si)
+	template <class Scene>
+	static Fns of(const FrameU &U)
 	{
-#define SDFR_FN(I, S) case I: f = fns_of<S>(U); return true;
-		SDFR_FOR_EACH_SCENE(SDFR_FN)
-#undef SDFR_FN
+		if (frame_needs_debug(U)) return Fns{&points_of<Scene, true>, &rays_of<Scene, true>, &pick_of<Scene, true>};
+		return Fns{&points_of<Scene, false>, &rays_of<Scene, false>, &pick_of<Scene, false>};
 	}
-	return false;
-#endif
-}
+};
 
 } // namespace
 
@@ -110,31 +60,27 @@ extern "C" {
 // `frame`: the inputs of a FrameU (tests/hostsim frame_from_oracle); width and height are set here as the library sets them
 int qh_points(const char *scene, const FrameU *frame, int n, const float *points, float *distance, float *normals)
 {
-	FrameU U = *frame;
-	U.width = U.height = 1;
+	FrameU U;
 	Fns f;
-	if (!latch(scene, U, f)) return -1;
-	parallel_items(n, [&](int a, int b) { f.points(U, b - a, points + 3 * a, distance + a, normals ? normals + 3 * a : nullptr); });
+	if (!latch<Pick>(scene, frame, U, f)) return -1;
+	parallel_items(n, 256, [&](int a, int b) { f.points(U, b - a, points + 3 * a, distance + a, normals ? normals + 3 * a : nullptr); });
 	return 0;
 }
 int qh_rays(const char *scene, const FrameU *frame, int n, const float *origins, const float *dirs, float max_distance, uint32_t *hits)
 {
-	FrameU U = *frame;
-	U.width = U.height = 1;
+	FrameU U;
 	Fns f;
-	if (!latch(scene, U, f)) return -1;
+	if (!latch<Pick>(scene, frame, U, f)) return -1;
 	const float dist_max = max_distance == 0.f ? U.range : max_distance;
-	parallel_items(n, [&](int a, int b) { f.rays(U, b - a, origins + 3 * a, dirs + 3 * a, dist_max, hits + QUERY_HIT_WORDS * a); });
+	parallel_items(n, 256, [&](int a, int b) { f.rays(U, b - a, origins + 3 * a, dirs + 3 * a, dist_max, hits + QUERY_HIT_WORDS * a); });
 	return 0;
 }
 int qh_pick(const char *scene, const FrameU *frame, int width, int height, int n, const int32_t *pixels, uint32_t *hits)
 {
-	FrameU U = *frame;
-	U.width = width;
-	U.height = height;
+	FrameU U;
 	Fns f;
-	if (!latch(scene, U, f)) return -1;
-	parallel_items(n, [&](int a, int b) { f.pick(U, b - a, pixels + 2 * a, hits + QUERY_HIT_WORDS * a); });
+	if (!latch<Pick>(scene, frame, U, f, width, height)) return -1;
+	parallel_items(n, 256, [&](int a, int b) { f.pick(U, b - a, pixels + 2 * a, hits + QUERY_HIT_WORDS * a); });
 	return 0;
 }
 int qh_frame_size() { return (int)sizeof(FrameU); }

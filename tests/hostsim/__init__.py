@@ -3,12 +3,17 @@
 of the HIP kernels with the oracle without a GPU.  The product never loads this library."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "sdf_playground_amd", "csrc")
+if os.path.dirname(_HERE) not in sys.path:
+    sys.path.insert(0, os.path.dirname(_HERE))
+
+import cppbuild  # noqa: E402
+
+_FLAGS = cppbuild.EXACT_FLAGS + ["-pthread", "-I" + cppbuild.CSRC]
 
 
 class FrameU(ctypes.Structure):
@@ -40,12 +45,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(_HERE, "libhostsim.so")
-        srcs = [os.path.join(_HERE, "hostsim.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.run(
-                ["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
-                 "-pthread", "-I" + _CSRC, "-shared", "-o", so, os.path.join(_HERE, "hostsim.cpp")], check=True)
+        so = cppbuild.compile(os.path.join(_HERE, "libhostsim.so"), [os.path.join(_HERE, "hostsim.cpp")],
+                              [os.path.join(_HERE, "render_rows.h")] + cppbuild.csrc_headers(), _FLAGS)
         _lib = ctypes.CDLL(so)
         _lib.hostsim_math.restype = ctypes.c_float
         _lib.hostsim_math.argtypes = [ctypes.c_int, ctypes.c_float, ctypes.c_float]
@@ -73,7 +74,7 @@ def render(scene, frame, stats=True, nthreads=None):
     out = np.zeros((H, W, 4), np.float32)
     st = np.zeros((H, W, 3), np.uint32) if stats else None
     rc = lib().hostsim_render(scene.encode(), ctypes.byref(frame), out.ctypes.data_as(ctypes.c_void_p),
-                              st.ctypes.data_as(ctypes.c_void_p) if stats else None, nthreads or os.cpu_count() or 1)
+                              st.ctypes.data_as(ctypes.c_void_p) if stats else None, nthreads or cppbuild.default_threads())
     if rc != 0:
         raise ValueError("hostsim_render failed: %d" % rc)
     return out, st
@@ -83,33 +84,22 @@ def render(scene, frame, stats=True, nthreads=None):
 _HLSL_DIR = os.path.join(_HERE, "_hlsl")
 
 
-def build_hlsl(name, hlsl_text):
-    """Translates `hlsl_text` with the library (sdfr_translate_scene_hlsl), compiles it with g++ around the product's per-pixel
-    pipeline (hlsl_host.cpp) and returns the loaded library.  The VAR_ macros are the ones the run-time compiler would
-    generate: slot k = order of first appearance."""
-    import re
-    import sys
+def build_hlsl(name, text, cpp=False):
+    """Compiles a run-time scene with g++ around the product's per-pixel pipeline (hlsl_host.cpp) and returns the loaded library and
+    the scene's variable slots.  `text` is in the reference's dialect and translated by the library (sdfr_translate_scene_hlsl), or,
+    cpp=True, in the library's C++ form (`struct Scene`, sdf_playground_amd/scenes/README.md), which may have a prepare()."""
+    translate = None
+    if not cpp:
+        if cppbuild.ROOT not in sys.path:
+            sys.path.insert(0, cppbuild.ROOT)
+        import sdf_playground_amd as sp
 
-    root = os.path.dirname(os.path.dirname(_HERE))
-    if root not in sys.path:
-        sys.path.insert(0, root)
-    import sdf_playground_amd as sp
-
-    os.makedirs(_HLSL_DIR, exist_ok=True)
+        translate = sp.translate_scene_hlsl
     gen = os.path.join(_HLSL_DIR, name + ".scene.inc")
-    slots = []
-    for m in re.finditer(r"VAR_(\w+)\s*\(", hlsl_text):
-        if m.group(1) not in slots:
-            slots.append(m.group(1))
-    text = "".join("#define VAR_%s(...) (U.scene_var[%d])\n" % (n, k) for k, n in enumerate(slots)) + sp.translate_scene_hlsl(hlsl_text)
-    if not os.path.exists(gen) or open(gen).read() != text:
-        with open(gen, "w") as f:
-            f.write(text)
-    so = os.path.join(_HLSL_DIR, "lib%s.so" % name)
-    deps = [gen, os.path.join(_HERE, "hlsl_host.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inl"))]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas", "-w",
-                        "-pthread", "-I" + _CSRC, '-DSDFR_HLSL_SCENE_FILE="%s"' % gen, "-shared", "-o", so, os.path.join(_HERE, "hlsl_host.cpp")], check=True)
+    slots = cppbuild.scene_include(gen, text, translate)
+    flags = _FLAGS + ["-w", '-DSDFR_HLSL_SCENE_FILE="%s"' % gen] + (["-DSDFR_SCENE_HAS_PREPARE=1"] if cpp else [])
+    so = cppbuild.compile(os.path.join(_HLSL_DIR, "lib%s.so" % name), [os.path.join(_HERE, "hlsl_host.cpp")],
+                          [gen, os.path.join(_HERE, "render_rows.h")] + cppbuild.csrc_headers(), flags)
     L = ctypes.CDLL(so)
     assert L.hlslsim_frame_size() == ctypes.sizeof(FrameU)
     return L, slots
@@ -120,34 +110,9 @@ def render_hlsl(L, frame, stats=True, nthreads=None):
     out = np.zeros((H, W, 4), np.float32)
     st = np.zeros((H, W, 3), np.uint32) if stats else None
     rc = L.hlslsim_render(ctypes.byref(frame), out.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p) if stats else None,
-                          nthreads or os.cpu_count() or 1)
+                          nthreads or cppbuild.default_threads())
     assert rc == 0
     return out, st
-
-
-def build_scene_source(name, cpp_text):
-    """The same harness for a run-time scene in the library's C++ form (`struct Scene`, sdf_playground_amd/scenes/README.md)."""
-    import re
-
-    os.makedirs(_HLSL_DIR, exist_ok=True)
-    gen = os.path.join(_HLSL_DIR, name + ".scene.inc")
-    slots = []
-    for m in re.finditer(r"VAR_(\w+)\s*\(", cpp_text):
-        if m.group(1) not in slots:
-            slots.append(m.group(1))
-    text = "".join("#define VAR_%s(...) (U.scene_var[%d])\n" % (n, k) for k, n in enumerate(slots)) + cpp_text
-    if not os.path.exists(gen) or open(gen).read() != text:
-        with open(gen, "w") as f:
-            f.write(text)
-    so = os.path.join(_HLSL_DIR, "lib%s.so" % name)
-    deps = [gen, os.path.join(_HERE, "hlsl_host.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inl"))]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas", "-w",
-                        "-pthread", "-I" + _CSRC, '-DSDFR_HLSL_SCENE_FILE="%s"' % gen, "-DSDFR_SCENE_HAS_PREPARE=1", "-shared", "-o", so,
-                        os.path.join(_HERE, "hlsl_host.cpp")], check=True)
-    L = ctypes.CDLL(so)
-    assert L.hlslsim_frame_size() == ctypes.sizeof(FrameU)
-    return L, slots
 
 
 render_scene_source = render_hlsl

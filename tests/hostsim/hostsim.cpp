@@ -2,15 +2,10 @@
 // (sdf_playground_amd/csrc/sdfr_perpixel.h) for the CPU, so that the stage arithmetic can be
 // bit-compared with the oracle in the CPU test tier, where there is no GPU.  This library is
 // never loaded by the product; the product renders on the GPU only.
-#include "sdfr_hostframe.h"
-
-#include <atomic>
-#include <thread>
-#include <vector>
+#include "render_rows.h"
 
 using namespace sdfr;
 
-typedef CachedRayStore<LocalRayStore> HostStore; // same store stack as the pixel kernel
 typedef vec4 (*pixel_fn)(const FrameU &, int, int, PixelCounters &, HostStore &);
 
 extern "C" int hostsim_render(const char *scene, FrameU *frame, float *out_rgba, unsigned *out_stats, int nthreads)
@@ -25,37 +20,7 @@ extern "C" int hostsim_render(const char *scene, FrameU *frame, float *out_rgba,
 		SDFR_FOR_EACH_SCENE(SDFR_FN)
 #undef SDFR_FN
 	}
-	const FrameU U = *frame;
-	std::atomic<int> next_row(0);
-	auto worker = [&]() {
-		for (;;)
-		{
-			int y = next_row.fetch_add(1);
-			if (y >= U.height) break;
-			for (int x = 0; x < U.width; ++x)
-			{
-				PixelCounters c = {0, 0, 0};
-				LocalRayStore backing;
-				HostStore store(backing);
-				vec4 v = fn(U, x, y, c, store);
-				size_t idx = (size_t)y * U.width + x;
-				out_rgba[4 * idx + 0] = v.x;
-				out_rgba[4 * idx + 1] = v.y;
-				out_rgba[4 * idx + 2] = v.z;
-				out_rgba[4 * idx + 3] = v.w;
-				if (out_stats)
-				{
-					out_stats[3 * idx + 0] = c.rays;
-					out_stats[3 * idx + 1] = c.march_evals;
-					out_stats[3 * idx + 2] = c.hits;
-				}
-			}
-		}
-	};
-	std::vector<std::thread> pool;
-	for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-	worker();
-	for (auto &th : pool) th.join();
+	render_rows(*frame, fn, out_rgba, out_stats, nthreads);
 	return 0;
 }
 

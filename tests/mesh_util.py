@@ -2,11 +2,10 @@
 numpy from the header's words, np.float32 operations only; the library's stage functions built for the CPU (tests/cpp/mesh_host.cpp);
 the lattice points; and the topology checks.  Test infrastructure: the product never imports this."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import cppbuild
 import query_util as qu
 
 F = np.float32
@@ -106,15 +105,7 @@ _host = None
 def host_lib():
     global _host
     if _host is None:
-        os.makedirs(qu.BUILD, exist_ok=True)
-        so = os.path.join(qu.BUILD, "libmesh_host.so")
-        src = os.path.join(qu.HERE, "cpp", "mesh_host.cpp")
-        deps = [src, os.path.join(qu.CSRC, "sdfr_mesh.h"), os.path.join(qu.CSRC, "sdfr_math.h")]
-        if qu._stale(so, deps):
-            assert "-ffp-contract=off" in qu.FLAGS
-            subprocess.run(["g++"] + qu.FLAGS + ["-I" + qu.CSRC, "-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
-        L = ctypes.CDLL(so)
+        L = ctypes.CDLL(qu.build_lib("mesh_host", "mesh_host.cpp", ["-I" + qu.CSRC], cppbuild.csrc_headers()))
         assert L.mh_grid_size() == ctypes.sizeof(HostGrid)
         vp = ctypes.c_void_p
         L.mh_extract.argtypes = [ctypes.POINTER(HostGrid), vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp]

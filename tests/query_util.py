@@ -3,17 +3,13 @@
 seeded sample sets, and the bit comparison.  Test infrastructure: the product never imports this."""
 import ctypes
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
-ORACLE = os.path.join(ROOT, "oracle")
-BUILD = os.path.join(HERE, "cpp", "_build")
+import cppbuild
+from cppbuild import BUILD, CSRC, HERE, ORACLE, ROOT
+
 SCENES_DIR = os.path.join(ROOT, "sdf_playground_amd", "scenes")
 for _d in (ROOT, HERE):
     if _d not in sys.path:
@@ -32,38 +28,26 @@ TIMES = [0.0, 1.25]
 MOVED_VARS = {"lense": {"xpos": 0.7, "zpos": 6.5, "mixing": 0.35}, "cube": {"size": 1.4, "ypos": 0.3, "red": 0.2},
               "neon": {"r1": 1.3, "spacing": 0.05}, "tiling": {"m1": 2.0, "width": 0.25, "truchet_width": 0.1},
               "fractal2": {"slider": 1.7}, "terrain": {"levels": 5.0}}
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas", "-w", "-pthread"]
+FLAGS = cppbuild.EXACT_FLAGS + ["-w", "-pthread"]
 HIT_WORDS = 12
 
 
-def _stale(out, deps):
-    return not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
-
-
 _libs = {}
+
+
+def build_lib(name, source, flags=(), deps=()):
+    """tests/cpp/_build/lib<name>.so from tests/cpp/<source> with FLAGS and `flags`, stale when the source or one of `deps` is newer -> its path"""
+    return cppbuild.compile(os.path.join(BUILD, "lib%s.so" % name), [os.path.join(HERE, "cpp", source)], deps, FLAGS + list(flags))
 
 
 def build_oracle_lib(name, sources, includes=(ORACLE,), more_deps=()):
     """lib<name>.so of the oracle's definitions: sources[0] (tests/cpp) compiled with `includes`; stale when a source, an oracle header or
     one of more_deps is newer"""
     if name not in _libs:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "lib%s.so" % name)
-        deps = [os.path.join(HERE, "cpp", f) for f in sources] + list(more_deps) + [os.path.join(ORACLE, f) for f in os.listdir(ORACLE) if f.endswith(".h")]
-        if _stale(so, deps):
-            subprocess.run(["g++"] + FLAGS + ["-I" + d for d in includes] + ["-shared", "-o", so + ".tmp", deps[0]], check=True)
-            os.replace(so + ".tmp", so)
-        _libs[name] = ctypes.CDLL(so)
+        deps = [os.path.join(HERE, "cpp", f) for f in sources[1:]] + list(more_deps) + cppbuild.oracle_headers()
+        _libs[name] = ctypes.CDLL(build_lib(name, sources[0], ["-I" + d for d in includes], deps))
         assert _libs[name].qo_frame_size() == ctypes.sizeof(po.OrcFrame)
     return _libs[name]
-
-
-def _var_slots(text):
-    slots = []
-    for m in re.finditer(r"VAR_(\w+)\s*\(", text):
-        if m.group(1) not in slots:
-            slots.append(m.group(1))
-    return slots
 
 
 def build_host_lib(name, source, scene, text=None):
@@ -72,27 +56,18 @@ def build_host_lib(name, source, scene, text=None):
     sdfr_load_scene_hlsl translates it"""
     key = scene if scene in HLSL or text is not None else "builtin"
     if (name, key) not in _libs:
-        os.makedirs(BUILD, exist_ok=True)
-        src = os.path.join(HERE, "cpp", source)
-        deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inl"))]
-        defs = []
+        deps = [os.path.join(HERE, "cpp", "host_common.h")] + cppbuild.csrc_headers()
+        flags = ["-I" + CSRC]
         if key != "builtin":
             import sdf_playground_amd as sp
 
             if text is None:
                 text = open(os.path.join(SCENES_DIR, scene + ".hlsl")).read()
             gen = os.path.join(BUILD, scene + ".scene.inc")
-            body = "".join("#define VAR_%s(...) (U.scene_var[%d])\n" % (n, k) for k, n in enumerate(_var_slots(text))) + sp.translate_scene_hlsl(text)
-            if not os.path.exists(gen) or open(gen).read() != body:
-                with open(gen, "w") as f:
-                    f.write(body)
+            cppbuild.scene_include(gen, text, sp.translate_scene_hlsl)
             deps.append(gen)
-            defs = ['-DSDFR_HLSL_SCENE_FILE="%s"' % gen]
-        so = os.path.join(BUILD, "lib%s_%s.so" % (name, key))
-        if _stale(so, deps):
-            subprocess.run(["g++"] + FLAGS + ["-I" + CSRC] + defs + ["-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
-        _libs[name, key] = ctypes.CDLL(so)
+            flags.append('-DSDFR_HLSL_SCENE_FILE="%s"' % gen)
+        _libs[name, key] = ctypes.CDLL(build_lib("%s_%s" % (name, key), source, flags, deps))
     return _libs[name, key]
 
 

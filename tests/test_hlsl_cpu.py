@@ -86,7 +86,7 @@ def test_pendulum_hlsl_equals_its_cpp_twin():
     import hostsim
 
     LH, slots = hostsim.build_hlsl("pendulum_hlsl", open(os.path.join(SCENES_DIR, "pendulum.hlsl")).read())
-    LC, slots_c = hostsim.build_scene_source("pendulum_cpp", open(os.path.join(SCENES_DIR, "pendulum.scene.h")).read())
+    LC, slots_c = hostsim.build_hlsl("pendulum_cpp", open(os.path.join(SCENES_DIR, "pendulum.scene.h")).read(), cpp=True)
     assert slots == slots_c == ["swing", "rod", "radius"]
     for stime, values in ((0.3, (0.7, 1.8, 0.45)), (2.1, (1.1, 2.2, 0.7))):
         f = hostsim.FrameU()

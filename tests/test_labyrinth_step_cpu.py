@@ -6,26 +6,21 @@ pipeline, the host build of the product's headers (tests/hostsim), against the o
 tests/labyrinth_step_cameras.py, those at y = -0, on and under the floor among them."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cppbuild
 import labyrinth_step_cameras as lsc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "labyrinth_step_host.cpp")
+SRC = os.path.join(cppbuild.HERE, "cpp", "labyrinth_step_host.cpp")
 F32 = np.float32
 EDGE = F32(67108848.0)  # the largest |p| rep20's comment claims: |p + 10| < 20 * 3355443
 
 
 @pytest.fixture(scope="module")
-def step_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("step") / "libstep.so")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
-                    "-I" + CSRC, "-shared", "-o", so, SRC], check=True)
-    return ctypes.CDLL(so)
+def step_lib():
+    return ctypes.CDLL(cppbuild.csrc_lib("step", SRC))
 
 
 def _ptr(a):

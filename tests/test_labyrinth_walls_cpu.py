@@ -7,22 +7,18 @@ square root on the domain both forms rely on (sdfr_math.h), which is all the pro
 renders the labyrinth against the oracle."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "labyrinth_walls_host.cpp")
+import cppbuild
+
+SRC = os.path.join(cppbuild.HERE, "cpp", "labyrinth_walls_host.cpp")
 
 
 @pytest.fixture(scope="module")
-def walls_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("walls") / "libwalls.so")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
-                    "-I" + CSRC, "-shared", "-o", so, SRC], check=True)
-    lib = ctypes.CDLL(so)
+def walls_lib():
+    lib = ctypes.CDLL(cppbuild.csrc_lib("walls", SRC))
     lib.walls_check.restype = ctypes.c_int64
     lib.walls_check.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p]
     lib.walls_grid.restype = ctypes.c_int64

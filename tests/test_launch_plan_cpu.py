@@ -13,13 +13,10 @@ against it."""
 import ctypes
 import itertools
 import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
-BUILD = os.path.join(HERE, "cpp", "_build")
+import cppbuild
 
 I32, U32, U64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
 IN_FIELDS = ["persistent_tiles", "retire_after", "square_units", "scene_key", "knob_persistent", "knob_blocks_per_cu", "knob_retire_after",
@@ -58,14 +55,9 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "liblaunch_plan_host.so")
-        src = os.path.join(HERE, "cpp", "launch_plan_host.cpp")
-        deps = [src] + [os.path.join(CSRC, f) for f in ("sdfr_launch_plan.h", "sdfr_frame.h", "sdfr_math.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            # plain g++: the plan is host arithmetic, no HIP header on the include path
-            subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-I" + CSRC, "-shared", "-o", so + ".tmp", src], check=True)
-            os.replace(so + ".tmp", so)
+        # the plan is host arithmetic: no HIP header on the include path
+        so = cppbuild.compile(os.path.join(cppbuild.BUILD, "liblaunch_plan_host.so"), [os.path.join(cppbuild.HERE, "cpp", "launch_plan_host.cpp")],
+                              cppbuild.csrc_headers(), cppbuild.PLAIN_FLAGS + ["-fPIC", "-Wno-unknown-pragmas", "-I" + cppbuild.CSRC])
         _lib = ctypes.CDLL(so)
         _lib.lp_plan.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         _lib.lp_plan.restype = None

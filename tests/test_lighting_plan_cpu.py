@@ -2,15 +2,12 @@
 stand-alone program tests/cpp/lighting_plan_host.cpp): `lighting` required, `hits` and `lights` optional, `surfaces` never taken, the
 six staging sizes, the lighting kernel, one launch of a block per 64 items or per 8 x 8 tile of the frame, and the argument errors in the
 order of the other queries.  tests/test_query_plan_cpu.py keeps checking the requests that existed before, through its own program."""
-import os
 import struct
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
-BUILD = os.path.join(HERE, "cpp", "_build")
+import cppbuild
 
 RAYS, PICK, FRAME, MESH = 1, 2, 3, 4
 KERNEL_LIGHTING = 5
@@ -22,14 +19,7 @@ RANGE = "37.5"
 
 @pytest.fixture(scope="module")
 def exe():
-    os.makedirs(BUILD, exist_ok=True)
-    out = os.path.join(BUILD, "lighting_plan_host")
-    src = os.path.join(HERE, "cpp", "lighting_plan_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("sdfr_query_plan.h", "sdfr_query_args.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I" + CSRC, "-o", out + ".tmp", src], check=True)
-        os.replace(out + ".tmp", out)
-    return out
+    return cppbuild.plan_program("lighting_plan_host")
 
 
 def plans(exe, requests):

@@ -3,17 +3,14 @@ tests/cpp/mesh_plan_host.cpp).  The rules mesh_impl carried inline before it had
 the statuses, the error texts and their precedence, the grid, the lattice, the workspace's four pieces, the fill decision and the answer
 sizes), and the plan has to agree with them for every argument fault, every grid and every pair of counts below."""
 import math
-import os
 import struct
 import subprocess
 
 import pytest
 
+import cppbuild
 import handle_mixed_sequences as hm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
-BUILD = os.path.join(HERE, "cpp", "_build")
 
 INVALID = -1  # SDFR_ERR_INVALID_ARGUMENT
 NULL_POINTER, BAD_ON_HOST, BAD_GRID = "null pointer", "on_host must be 0 or 1", "bad mesh grid"
@@ -23,15 +20,7 @@ NAN, INF = float("nan"), float("inf")
 
 
 def _exe(name, flags):
-    os.makedirs(BUILD, exist_ok=True)
-    out = os.path.join(BUILD, name)
-    src = os.path.join(HERE, "cpp", "mesh_plan_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("sdfr_mesh_plan.h", "sdfr_mesh.h", "sdfr_math.h", "sdfr_query_plan.h", "sdfr_query_args.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        # plain g++: host arithmetic, no HIP header on the include path
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror"] + flags + ["-I" + CSRC, "-o", out + ".tmp", src], check=True)
-        os.replace(out + ".tmp", out)
-    return out
+    return cppbuild.plan_program("mesh_plan_host", name, flags)
 
 
 @pytest.fixture(scope="module")

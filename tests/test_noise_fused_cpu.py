@@ -10,25 +10,20 @@ shader (oracle/noise.h), which stays plain IEEE.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cppbuild
 from oracle import pyoracle as po
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "noise_fused_host.cpp")
+SRC = os.path.join(cppbuild.HERE, "cpp", "noise_fused_host.cpp")
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("noise_fused") / "libnoise_fused.so")
-    # the options of tests/hostsim: no contraction, as the kernels are built (-ffp-contract=off)
-    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
-                    "-I" + CSRC, "-shared", "-o", so, SRC], check=True)
-    L = ctypes.CDLL(so)
+def lib():
+    # the options of tests/hostsim: no contraction, as the kernels are built
+    L = ctypes.CDLL(cppbuild.csrc_lib("noise_fused", SRC))
     L.nf_noise.restype = ctypes.c_longlong
     L.nf_lattice_range.restype = ctypes.c_longlong
     L.nf_fused_lattice_would_differ.restype = ctypes.c_longlong

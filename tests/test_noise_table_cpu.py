@@ -10,13 +10,11 @@ through a table filled by simplex_grad equal the formula bit for bit, on random,
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sdf_playground_amd", "csrc")
+import cppbuild
 
 SOURCE = r"""
 #include "sdfr_noise.h"
@@ -147,15 +145,10 @@ extern "C" long long nt_noise(int what, const float *in, float *out, long long n
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("noise_table")
-    src, so = os.path.join(d, "noise_table.cpp"), os.path.join(d, "libnoise_table.so")
-    with open(src, "w") as f:
-        f.write(SOURCE)
-    # the options of tests/hostsim: no contraction, as the kernels are built (-ffp-contract=off)
-    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-mfma", "-mavx2", "-fno-math-errno", "-Wno-unknown-pragmas",
-                    "-I" + CSRC, "-shared", "-o", so, src], check=True)
-    L = ctypes.CDLL(so)
+def lib():
+    src = cppbuild.write_if_changed(os.path.join(cppbuild.BUILD, "noise_table.cpp"), SOURCE)
+    # the options of tests/hostsim: no contraction, as the kernels are built
+    L = ctypes.CDLL(cppbuild.csrc_lib("noise_table", src))
     L.nt_noise.restype = ctypes.c_longlong
     L.nt_fill()
     return L

@@ -4,15 +4,13 @@ table are spelled out here a second time (parent_rules: the statuses, the error 
 an occlusion query into launches), and the plan has to agree with them for every kind, every argument fault and every size below.
 The split of more than 2^25 occlusion items into several launches is checked here as arithmetic only: no device has run it."""
 import math
-import os
 import struct
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
-BUILD = os.path.join(HERE, "cpp", "_build")
+import cppbuild
+
 
 POINTS, RAYS, PICK, FRAME, MESH, OCCLUSION, HIT_OCCLUSION = range(7)
 KERNEL_POINTS, KERNEL_RAYS, KERNEL_LATTICE, KERNEL_SURFACES, KERNEL_OCCLUSION = range(5)
@@ -24,15 +22,7 @@ INT32_MAX = 2 ** 31 - 1
 
 
 def _exe(name, flags):
-    os.makedirs(BUILD, exist_ok=True)
-    out = os.path.join(BUILD, name)
-    src = os.path.join(HERE, "cpp", "query_plan_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("sdfr_query_plan.h", "sdfr_query_args.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        # plain g++: host arithmetic, no HIP header on the include path
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror"] + flags + ["-I" + CSRC, "-o", out + ".tmp", src], check=True)
-        os.replace(out + ".tmp", out)
-    return out
+    return cppbuild.plan_program("query_plan_host", name, flags)
 
 
 @pytest.fixture(scope="module")

@@ -1,29 +1,18 @@
 """CPU tier: how one device buffer is cut into the stand-ins of a caller's host arrays (sdf_playground_amd/csrc/sdfr_stage.h, built as
 the stand-alone program tests/cpp/stage_host.cpp).  The offsets and totals of the header against the formulas the entry points
 carried before they shared it (query_impl, mesh_impl and atlas_impl), spelled out here a second time."""
-import os
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "csrc")
-BUILD = os.path.join(HERE, "cpp", "_build")
+import cppbuild
 POINTS, RAYS, PICK = 0, 1, 2
 HIT_BYTES = 48
 
 
 @pytest.fixture(scope="module")
 def exe():
-    os.makedirs(BUILD, exist_ok=True)
-    out = os.path.join(BUILD, "stage_host")
-    src = os.path.join(HERE, "cpp", "stage_host.cpp")
-    deps = [src, os.path.join(CSRC, "sdfr_stage.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        # plain g++: host arithmetic, no HIP header on the include path
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I" + CSRC, "-o", out + ".tmp", src], check=True)
-        os.replace(out + ".tmp", out)
-    return out
+    return cppbuild.plan_program("stage_host")
 
 
 def carve(exe, lists):
