@@ -414,6 +414,41 @@ struct EscapesFrom<Scene, typename VoidOfN<decltype(&Scene::escapes_from)>::type
 	static constexpr bool available = true;
 	static SDF_HD float get(const FrameU &U, vec3 start, vec3 dir, float range) { return Scene::escapes_from(U, start, dir, range); }
 };
+// The reference shades every hit, also a shadow ray's: the material callback runs, and unless the surface is see-through
+// (alpha below 1: the ray goes on, tinted) the hit adds 0, pushes nothing and leaves the tone-map flag alone.  A scene whose
+// material() is a pure function that never lowers the alpha may declare `shadow_hits_need_material = false`: the pixel kernel then
+// counts such a hit and adds the 0 without calling shade_hit (never in the debug-plane build, which keeps the reference's path).
+template <class Scene, class = void>
+struct ShadowHitsNeedMaterial { static constexpr bool value = true; };
+template <class Scene>
+struct ShadowHitsNeedMaterial<Scene, typename VoidOfN<decltype(Scene::shadow_hits_need_material)>::type>
+{
+	static constexpr bool value = Scene::shadow_hits_need_material;
+};
+
+// A scene whose light() puts a directional light into slot 0 in every frame may declare `static SDF_HD vec3 frame_sun_dir(const FrameU &U)`:
+// that light's L.pos / (length(L.pos) + U.dist_eps), made once by its prepare() -- the operands are a constant and a frame uniform, and the
+// light loop would form the same three quotients and the root at every hit.  Slot 0 is the scene's own in every frame: extension lights
+// overwrite slots 1 and above (light_in_slot).
+template <class Scene, class = void>
+struct FrameSunDir
+{
+	static constexpr bool available = false;
+	static SDF_HD vec3 get(const FrameU &) { return V3s(0.f); }
+};
+template <class Scene>
+struct FrameSunDir<Scene, typename VoidOfN<decltype(&Scene::frame_sun_dir)>::type>
+{
+	static constexpr bool available = true;
+	static SDF_HD vec3 get(const FrameU &U) { return Scene::frame_sun_dir(U); }
+};
+// the direction in which directional light i shines
+template <class Scene>
+SDF_HD vec3 directional_light_dir(const FrameU &U, int i, const Light &L)
+{
+	if (FrameSunDir<Scene>::available && i == 0) return FrameSunDir<Scene>::get(U);
+	return L.pos / (length(L.pos) + U.dist_eps);
+}
 // A scene with ray_escapes may also declare `static constexpr bool inline_escaped_shadows = true`: a shadow ray that escapes where it
 // starts (no evaluation at all: two thirds of the rays of gems with eight lights, whose floor pixels send eight of them past the
 // ring) is then not queued -- a 48-byte record out and back, a turn of the bounce loop -- but delivers its light from the light
@@ -646,7 +681,7 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 					float trace_dist;
 					if (L.directional)
 					{
-						ldir = L.pos / (length(L.pos) + U.dist_eps);
+						ldir = directional_light_dir<Scene>(U, i, L);
 						trace_dist = U.range;
 					}
 					else
@@ -716,7 +751,7 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 				float falloff = 1.f;
 				if (L.directional)
 				{
-					ldir = L.pos / (length(L.pos) + U.dist_eps);
+					ldir = directional_light_dir<Scene>(U, i, L);
 					trace_dist = U.range;
 				}
 				else

@@ -209,6 +209,16 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		SDFR_CLK_ADD(clk_march, c0, c1);
 		store.ray_marched(ray, cnt.march_evals - evals_before, status); // a hook for analysis builds (tests/hostsim); empty in the kernels
 
+		// A shadow ray stopped by a surface whose material nobody needs (ShadowHitsNeedMaterial, sdfr_pixel.h): the hit is counted, and what
+		// shade_hit would come to -- add 0, push nothing, leave the tone-map flag alone -- is what a miss does with a ray that carries no
+		// light: shade_miss of a shadow ray is 0 + contrib, +0 in every component, as V3s(0) is.  Written as a change of the ray and not as a
+		// third branch beside hit and miss: the branch cost the march loop a one-bank fma or the kernel 4 bytes of scratch, wherever it stood.
+		if (!DBG && !ShadowHitsNeedMaterial<Scene>::value && ray_is_shadow(ray) && status == MARCH_HIT)
+		{
+			cnt.hits++;
+			ray.contrib = V3s(0.f);
+			status = MARCH_MISS;
+		}
 		vec3 out;
 		if (status == MARCH_HIT)
 		{

@@ -183,9 +183,22 @@ struct SceneLabyrinth
 	static constexpr int retire_after = 4; // configuration 3, two sessions: 1.252 (1) / 1.236 (2) / 1.224 (3) / 1.224 (4) / 1.233 (5) / 1.237 (8) / 1.243 (16) ms
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
 	static constexpr bool noise_grad_table = true; // marble walls, vase and sky: turbulence3 in ~80 % of tiles (sdfr_pixel_kernel.h)
+	static constexpr bool shadow_hits_need_material = false; // material() is a pure function and sets no alpha: a shadow ray's hit adds 0 whatever it is made of (sdfr_render_pixel.h)
 	static const char *variables() { return ""; }
-	enum { SU_FIRE_SCROLL = 0 };
-	static SDF_HD void prepare(FrameU &U) { U.su[SU_FIRE_SCROLL] = U.stime * 3.f; }
+	enum { SU_FIRE_SCROLL = 0, SU_SUN_DIR = 1 /* .. 3 */ };
+	static SDF_HD void prepare(FrameU &U)
+	{
+		U.su[SU_FIRE_SCROLL] = U.stime * 3.f;
+		// the sun's direction as the light loop forms it at every hit (shade_hit, sdfr_pixel.h): a constant and a frame uniform
+		Light sun;
+		sun_light(0, sun);
+		const vec3 ldir = sun.pos / (length(sun.pos) + U.dist_eps);
+		U.su[SU_SUN_DIR + 0] = ldir.x;
+		U.su[SU_SUN_DIR + 1] = ldir.y;
+		U.su[SU_SUN_DIR + 2] = ldir.z;
+	}
+	// the direction in which the directional light of slot 0 shines (FrameSunDir, sdfr_pixel.h): light() puts the sun there in every frame
+	static SDF_HD vec3 frame_sun_dir(const FrameU &U) { return V3(U.su[SU_SUN_DIR + 0], U.su[SU_SUN_DIR + 1], U.su[SU_SUN_DIR + 2]); }
 
 	static SDF_HD float fire_cone(vec3 p) { return sd_round_cone(p, V3(0.f, 1.1f, 0.f), V3(0.f, 1.6f, 0.f), 0.15f, 0.1f); }
 
@@ -270,9 +283,33 @@ struct SceneLabyrinth
 	// For the walls every a lies in sqrt1's domain: a component q = |w - c| - h (h >= 1) that is not 0 and below h / 2 is
 	// an exact difference of two floats >= 1/2, so |q| >= 2^-24 and a nonzero a is >= 2^-48 (w.x and w.z are folded to
 	// about [0, 10]: only a |w.y| >= 2^64 overflows, to +inf, above).
+	// sd_box_pair_min with the six clamps o = max(q, 0) -- v_max_f32, half rate on gfx950 -- written as sums, o' = q + |q| -- v_add_f32 with
+	// the absolute value as a source modifier, full rate (tools/ubench/valu_ubench.hip: add_self_abs against max_zero) --, bit for bit
+	// on its domain: finite p, as for rep20, with every q either zero or between 2^-48 and 2^62 in magnitude.  For finite q
+	//   o' = 2 q exactly for q > 0 (a doubling is exact short of overflow), and +0 for q < 0 (x + (-x) is +0 when rounding to nearest)
+	//   and for both zeros (-0 + +0 = +0): o' = 2 o, but for the sign of a zero, which the squares drop.
+	// o feeds nothing but dot(o, o), and a power of two goes through every rounding of what follows while nothing overflows or
+	// becomes subnormal (a product that is not zero lies in [2^-96, 2^124], a sum of three below 2^126):
+	//   * dot(o', o') = 4 a: the products are 4 times the products, each sum 4 times the sum, rounded alike; a = 0 stays +0;
+	//   * min1(4 a2, 4 a1) = 4 min1(a2, a1);
+	//   * sqrt1(4 a) = 2 sqrt1(a): sqrt1 is correctly rounded on [2^-96, FLT_MAX] and at +0, and 4 a stays in there (a < 2^126); on the
+	//     device its 2^-126 bias stays below half an ulp of 4 a just as of a;
+	//   * the closing sqrt1(..) + in becomes fma1(0.5, 2 sqrt1(a), in): the product is sqrt1(a) exactly, so the fma rounds the same sum.
+	// The six v_max become six v_add, and no instruction is added: the v_add that closed becomes the v_fma.  Outside the domain: a NaN
+	// component is dropped by max1 and kept by the sum (only a non-finite coordinate makes one), and q of 2^62 and more can overflow 4 a
+	// where a was finite -- sd_box_pair_min above stays as the form for any pair of boxes.  For the walls a q that is not zero is at
+	// least 2^-24 (above), and below 2^62 while |w.y| is; tests/test_labyrinth_clamp_cpu.py holds this form against sd_box_pair_min and
+	// against the two sd_box calls, |w.y| up to 1e6, and shows the NaN.
+	static SDF_HD float sd_box_pair_min_adds(vec3 p1, vec3 b1, vec3 p2, vec3 b2)
+	{
+		const vec3 q1 = abs(p1) - b1, q2 = abs(p2) - b2;
+		const vec3 o1 = q1 + abs(q1), o2 = q2 + abs(q2);
+		const float in = min1(min1(max1(q1.x, max1(q1.y, q1.z)), max1(q2.x, max1(q2.y, q2.z))), 0.f);
+		return fma1(0.5f, sqrt1(min1(dot(o2, o2), dot(o1, o1))), in);
+	}
 	static SDF_HD float walls(vec3 wp)
 	{
-		return sd_box_pair_min(wp - V3(3.5f, 2.f, 3.f), V3(1.5f, 2.f, 1.f), wp - V3(7.f, 2.f, 5.f), V3(3.f, 2.f, 1.f));
+		return sd_box_pair_min_adds(wp - V3(3.5f, 2.f, 3.f), V3(1.5f, 2.f, 1.f), wp - V3(7.f, 2.f, 5.f), V3(3.f, 2.f, 1.f));
 	}
 	// position in the vase's frame (the vase is mirrored about x = 8)
 	static SDF_HD vec3 vase_local(vec3 wp) { return V3(abs1(wp.x - 8.f), wp.y, wp.z) - V3(1.f, 0.f, 3.f); }

@@ -56,6 +56,9 @@
 #define A_ADD_LIT(i) asm volatile("v_add_f32 %0, 0x3f8ccccd, %0" : "+v"(a##i));
 #define A_MUL_SGPR(i) asm volatile("v_mul_f32 %0, s4, %0" : "+v"(a##i));
 #define A_ADD_ABS(i) asm volatile("v_add_f32_e64 %0, |%0|, %1" : "+v"(a##i) : "v"(c));
+// the clamp max(x, 0) and the sum x + |x| that gives 2 max(x, 0) (SceneLabyrinth::sd_box_pair_min_adds): VOP3 add with a source modifier
+#define A_MAX_ZERO(i) asm volatile("v_max_f32 %0, 0, %0" : "+v"(a##i));
+#define A_ADD_SELF_ABS(i) asm volatile("v_add_f32_e64 %0, %0, |%0|" : "+v"(a##i));
 #define A_MIN3(i) asm volatile("v_min3_f32 %0, %0, %1, %2" : "+v"(a##i) : "v"(b), "v"(c));
 #define A_MED3(i) asm volatile("v_med3_f32 %0, %0, %1, %2" : "+v"(a##i) : "v"(b), "v"(c));
 #define A_TRUNC(i) asm volatile("v_trunc_f32 %0, %0" : "+v"(a##i));
@@ -100,6 +103,8 @@ KERNEL(fmamk, REP8(A_FMAMK))
 KERNEL(add_lit, REP8(A_ADD_LIT))
 KERNEL(mul_sgpr, REP8(A_MUL_SGPR))
 KERNEL(add_abs, REP8(A_ADD_ABS))
+KERNEL(max_zero, REP8(A_MAX_ZERO))
+KERNEL(add_self_abs, REP8(A_ADD_SELF_ABS))
 KERNEL(min3, REP8(A_MIN3))
 KERNEL(med3, REP8(A_MED3))
 KERNEL(trunc, REP8(A_TRUNC))
@@ -135,7 +140,8 @@ __global__ __launch_bounds__(256) void k_mul_dep(float *out, int iters, float b,
 typedef void (*kfn)(float *, int, float, float);
 struct Entry { const char *name; kfn fn; };
 
-int main()
+// valu_ubench [name ...]: only the named cases
+int main(int argc, char **argv)
 {
 	hipDeviceProp_t prop;
 	hipGetDeviceProperties(&prop, 0);
@@ -147,7 +153,7 @@ int main()
 	std::vector<Entry> entries = {
 #define E(n) {#n, k_##n},
 		E(fma) E(fmac) E(mul) E(add) E(min) E(max3) E(floor) E(rndne) E(fract) E(mov) E(cndmask) E(cmp_vcc) E(cmp_sgpr) E(cvt_f32_u32) E(lshl) E(add_u32)
-		E(subrev_sgpr) E(cndmask_sgpr) E(max) E(sub) E(and) E(fmamk) E(add_lit) E(mul_sgpr) E(add_abs) E(min3) E(med3) E(trunc) E(cvt_i32) E(mul_lo_u32) E(pk_fma) E(pk_mul) E(pk_add) E(div_scale) E(div_fmas) E(div_fixup) E(sqrt) E(rcp) E(rsq) E(exp) E(fma_dep) E(mul_dep) E(fma_min_pair) E(fma3_sqrt)
+		E(subrev_sgpr) E(cndmask_sgpr) E(max) E(sub) E(and) E(fmamk) E(add_lit) E(mul_sgpr) E(add_abs) E(max_zero) E(add_self_abs) E(min3) E(med3) E(trunc) E(cvt_i32) E(mul_lo_u32) E(pk_fma) E(pk_mul) E(pk_add) E(div_scale) E(div_fmas) E(div_fixup) E(sqrt) E(rcp) E(rsq) E(exp) E(fma_dep) E(mul_dep) E(fma_min_pair) E(fma3_sqrt)
 	};
 	const int iters = 40000;
 	hipEvent_t e0, e1;
@@ -156,6 +162,9 @@ int main()
 	printf("%-14s %10s %10s %10s %10s   (cycles per wave64 instruction per SIMD at 2.4 GHz; waves/SIMD = 1,2,4,8)\n", "op", "w1", "w2", "w4", "w8");
 	for (auto &en : entries)
 	{
+		bool wanted = argc < 2;
+		for (int k = 1; k < argc; ++k) wanted = wanted || std::string(argv[k]) == en.name;
+		if (!wanted) continue;
 		printf("%-14s", en.name);
 		for (int wps : {1, 2, 4, 8})
 		{
