@@ -33,8 +33,11 @@ struct Census
 	// (DESIGN.md 1.3 explains why their values are never used).
 	unsigned long long sqrt_out_of_domain, divc_out_of_domain; // near field
 	unsigned long long far_field;
+	// arguments of a reciprocal the kernels take with rcp1 (sdfr_math.h) outside +-0, +-inf and 2^-100 <= |a| <= 2^100
+	// (NaN propagates through the fast form as through the division and is not counted)
+	unsigned long long rcp_out_of_domain;
 };
-inline Census &census() { static thread_local Census c = {0, 0, 0, 0, 0}; return c; }
+inline Census &census() { static thread_local Census c = {0, 0, 0, 0, 0, 0}; return c; }
 inline void census_check_sqrt(float a)
 {
 	uint32_t u = dm::f2u(a);
@@ -46,6 +49,12 @@ inline void census_check_divc(float a)
 	float m = fabsf(a);
 	if (a != a || m > 0x1p110f) census().far_field++;
 	else if (!(m == 0.f || m >= 0x1p-100f)) census().divc_out_of_domain++;
+}
+inline void census_check_rcp(float a)
+{
+	float m = fabsf(a);
+	if (a != a || m == 0.f || m > 3.402823466e+38f) return;
+	if (!(m >= 0x1p-100f && m <= 0x1p100f)) census().rcp_out_of_domain++;
 }
 inline void census_check_plane(float a, float c)
 {
@@ -74,6 +83,7 @@ inline void census_check_raydiv(float a, float c)
 #define ORC_COUNT_T() (census().flops += 1, census().transc += 1)
 #define ORC_CHECK_SQRT(a) census_check_sqrt(a)
 #define ORC_CHECK_DIVC(a) census_check_divc(a)
+#define ORC_CHECK_RCP(a) census_check_rcp(a)
 #define ORC_CHECK_PLANE(a, c) census_check_plane(a, c)
 #define ORC_CHECK_RAYDIV(a, c) census_check_raydiv(a, c)
 struct real
@@ -107,6 +117,7 @@ inline float val(real a) { return a; }
 #define ORC_COUNT_T() ((void)0)
 #define ORC_CHECK_SQRT(a) ((void)0)
 #define ORC_CHECK_DIVC(a) ((void)0)
+#define ORC_CHECK_RCP(a) ((void)0)
 #define ORC_CHECK_PLANE(a, c) ((void)0)
 #define ORC_CHECK_RAYDIV(a, c) ((void)0)
 #endif
@@ -121,13 +132,25 @@ inline real r_trunc(real a) { ORC_COUNT(1); return real(truncf(val(a))); }
 // HLSL round() is round-half-to-even (a-T.1)
 inline real r_round(real a) { ORC_COUNT(1); return real(rintf(val(a))); }
 inline real r_sqrt(real a) { ORC_COUNT(1); ORC_CHECK_SQRT(val(a)); return real(sqrtf(val(a))); }
-inline real r_rsqrt(real a) { ORC_COUNT(1); ORC_CHECK_SQRT(val(a)); return real(1.0f / sqrtf(val(a))); }
+inline real r_rsqrt(real a) { ORC_COUNT(1); ORC_CHECK_SQRT(val(a)); ORC_CHECK_RCP(sqrtf(val(a))); return real(1.0f / sqrtf(val(a))); }
+// 1 / a where the kernels take the reciprocal with rcp1: plain IEEE division here; the census build records arguments outside
+// the range on which rcp1 is verified
+inline real r_rcp(real a) { ORC_COUNT(1); ORC_CHECK_RCP(val(a)); return real(1.0f / val(a)); }
 // a / c where c is a scene constant: plain IEEE division here; the census build records
 // numerators outside the range on which the kernels' div_c is verified
 inline real r_div_const(real a, real c) { ORC_CHECK_DIVC(val(a)); return a / c; }
 inline real r_sin(real a) { ORC_COUNT_T(); return real(dm::sinf_det(val(a))); }
 inline real r_cos(real a) { ORC_COUNT_T(); return real(dm::cosf_det(val(a))); }
-inline real r_atan2(real y, real x) { ORC_COUNT_T(); return real(dm::atan2f_det(val(y), val(x))); }
+// the census build records the one reciprocal inside (detmath.h atan_pos: -(1 / t) for t = |y| / |x| > tan(3 pi / 8), rcp1 in the kernels)
+inline void census_check_atan2(float y, float x)
+{
+#ifdef ORACLE_CENSUS
+	if (x != x || y != y || fabsf(x) == 0.f) return;
+	const float t = fabsf(y) / fabsf(x);
+	if (t > 2.414213562373095f) ORC_CHECK_RCP(t);
+#endif
+}
+inline real r_atan2(real y, real x) { ORC_COUNT_T(); census_check_atan2(val(y), val(x)); return real(dm::atan2f_det(val(y), val(x))); }
 inline real r_exp2(real a) { ORC_COUNT_T(); return real(dm::exp2f_det(val(a))); }
 inline real r_log2(real a) { ORC_COUNT_T(); return real(dm::log2f_det(val(a))); }
 inline real r_pow(real x, real y) { ORC_COUNT_T(); ORC_COUNT_T(); ORC_COUNT(1); return real(dm::powf_det(val(x), val(y))); }

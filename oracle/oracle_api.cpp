@@ -368,7 +368,7 @@ int orc_render(const char *scene, const orc_frame *frame, float *out_rgba, unsig
 
 #ifdef ORACLE_CENSUS
 // flop census of the calling thread (render with nthreads = 1): {flops, transcendentals}
-void orc_census_reset() { census() = Census{0, 0, 0, 0, 0}; }
+void orc_census_reset() { census() = Census{0, 0, 0, 0, 0, 0}; }
 // {flops, transcendentals, near-field sqrt / division arguments out of domain, far-field (overflowed) arguments}
 void orc_census_get(unsigned long long *out4)
 {
@@ -378,6 +378,9 @@ void orc_census_get(unsigned long long *out4)
 	out4[3] = census().divc_out_of_domain;
 	out4[4] = census().far_field;
 }
+// reciprocals whose argument lies outside rcp1's domain (hlsl.h census_check_rcp: r_rcp, r_rsqrt, atan2's inner 1 / t, sdRoundCone; the
+// ground plane's reciprocal is under census_check_plane), counted apart so that orc_census_get keeps its five words
+unsigned long long orc_census_rcp() { return census().rcp_out_of_domain; }
 #endif
 
 // HDR::process restated (oracle/postprocess.h).  scene: RGBA16F [h][w][4]; bloom1/bloom2:
@@ -417,13 +420,99 @@ void orc_noise(int what, const float *in, float *out, long long n)
 	}
 }
 
-// Known-answer access to individual library functions (tests/test_oracle_*.py).
-// Returns the number of outputs written, or -1 for an unknown function.
-int orc_kat(const char *fn, const float *in, float *out)
+} // extern "C"
+
+namespace {
+
+// (a, b, c) in descending order: three compare-exchanges, a swap only where the later value is greater (so equal values and NaN stay)
+float3 kat_sort3_desc(float3 v)
 {
-	std::string f(fn);
+	real a = v.x, b = v.y, c = v.z, t;
+	if (c > b) { t = b; b = c; c = t; }
+	if (b > a) { t = a; a = b; b = t; }
+	if (c > b) { t = b; b = c; c = t; }
+	return float3(a, b, c);
+}
+// whether the ray p + t dir, t >= 0, stays outside the ball (c, radius): p is outside, and the ball lies behind the ray or the ray's
+// line passes the centre at more than the radius -- |v|^2 |dir|^2 - (v . dir)^2 > radius^2 |dir|^2, dir not taken to be a unit vector
+bool kat_ray_passes_ball(float3 p, float3 dir, float3 c, real radius)
+{
+	const float3 v = p - c;
+	const real b = dot(v, dir), vv = dot(v, v), dd = dot(dir, dir);
+	return vv > radius * radius && (b >= real(0.f) || vv * dd - b * b > radius * radius * dd);
+}
+
+// One evaluation of the library function `f`: up to 16 inputs, up to 8 outputs.  Returns the number of outputs written, or -1 for an
+// unknown function.
+int kat_eval(const std::string &f, const float *in, float *out)
+{
+	auto v2 = [&](int o) { return float2(in[o], in[o + 1]); };
 	auto v3 = [&](int o) { return float3(in[o], in[o + 1], in[o + 2]); };
+	auto v4 = [&](int o) { return float4(in[o], in[o + 1], in[o + 2], in[o + 3]); };
+	auto put2 = [&](float2 v) { out[0] = val(v.x); out[1] = val(v.y); return 2; };
 	auto put3 = [&](float3 v) { out[0] = val(v.x); out[1] = val(v.y); out[2] = val(v.z); return 3; };
+	auto put4 = [&](float4 v) { out[0] = val(v.x); out[1] = val(v.y); out[2] = val(v.z); out[3] = val(v.w); return 4; };
+	// intrinsics (hlsl.h)
+	if (f == "fma") { out[0] = val(r_fma(in[0], in[1], in[2])); return 1; }
+	if (f == "abs") { out[0] = val(r_abs(in[0])); return 1; }
+	if (f == "floor") { out[0] = val(r_floor(in[0])); return 1; }
+	if (f == "trunc") { out[0] = val(r_trunc(in[0])); return 1; }
+	if (f == "sqrt") { out[0] = val(r_sqrt(in[0])); return 1; }
+	if (f == "rsqrt") { out[0] = val(r_rsqrt(in[0])); return 1; }
+	if (f == "rcp") { out[0] = val(r_rcp(in[0])); return 1; }
+	if (f == "div_const") { out[0] = val(r_div_const(in[0], in[1])); return 1; }
+	if (f == "fmod_const") { out[0] = val(r_fmod_const(in[0], in[1])); return 1; }
+	if (f == "saturate") { out[0] = val(r_saturate(in[0])); return 1; }
+	if (f == "clamp") { out[0] = val(r_clamp(in[0], in[1], in[2])); return 1; }
+	if (f == "lerp") { out[0] = val(r_lerp(in[0], in[1], in[2])); return 1; }
+	if (f == "ftoi") { out[0] = (float)r_ftoi(in[0]); return 1; } // the integer as a float: exact below 2^24, rounded alike above
+	if (f == "atan") { out[0] = val(r_atan2(in[0], real(1.f))); return 1; }
+	if (f == "dot2") { out[0] = val(dot(v2(0), v2(2))); return 1; }
+	if (f == "dot3") { out[0] = val(dot(v3(0), v3(3))); return 1; }
+	if (f == "dot4") { out[0] = val(dot(v4(0), v4(4))); return 1; }
+	if (f == "length2") { out[0] = val(length(v2(0))); return 1; }
+	if (f == "length3") { out[0] = val(length(v3(0))); return 1; }
+	if (f == "normalize2") return put2(normalize(v2(0)));
+	if (f == "lerp2") return put2(lerp(v2(0), v2(2), real(in[4])));
+	if (f == "lerp3") return put3(lerp(v3(0), v3(3), real(in[6])));
+	if (f == "mad") return put3(mad(v3(0), in[3], v3(4)));
+	// the 32 bits of the hash as two exactly representable floats
+	if (f == "hash_hi") { uint32_t u; memcpy(&u, &in[0], 4); out[0] = (float)(hash(u) >> 8); return 1; }
+	if (f == "hash_lo") { uint32_t u; memcpy(&u, &in[0], 4); out[0] = (float)(hash(u) & 0xffu); return 1; }
+	// sdf_primitives.hlsl, sdf_ops.hlsl
+	if (f == "sdLimit1") { out[0] = val(sdLimit1(in[0], in[1], in[2])); return 1; }
+	if (f == "sdLimit3") { out[0] = val(sdLimit3(v3(0), v3(3), v3(6))); return 1; }
+	if (f == "opRepInfConst") { out[0] = val(opRepInf(float2(in[0], in[0]), float2(in[1], in[1])).x); return 1; }
+	if (f == "opShell") { out[0] = val(opShell(in[0], in[1], in[2])); return 1; }
+	if (f == "opAB2UV") return put2(opAB2UV(v2(0)));
+	if (f == "opChamfer") { out[0] = val(opChamfer(in[0], in[1], in[2])); return 1; }
+	if (f == "opChamferMerge") { out[0] = val(opChamferMerge(in[0], in[1], in[2])); return 1; }
+	if (f == "opPipeMerge") { out[0] = val(opPipeMerge(in[0], in[1], in[2], in[3])); return 1; }
+	if (f == "staircase") { out[0] = val(staircase(in[0], in[1], in[2])); return 1; }
+	if (f == "smax1") { out[0] = val(smax1(in[0], in[1], in[2])); return 1; }
+	// sdf_common.hlsl, sdf_materials.hlsl
+	if (f == "HUEtoRGB") return put3(HUEtoRGB(in[0]));
+	if (f == "RGBtoBrightness") { out[0] = val(RGBtoBrightness(v3(0))); return 1; }
+	if (f == "tile_color_at") return put4(tile_color_from_pos(get_tile_impact(v3(0), v3(3))));
+	// (dir, pos, offset_right, offset_bottom.xy): the direction first, so that a probe scene varies it per point -- a direction that
+	// does not descend makes every tap NaN --, and the twelfth input is the first again: a probe scene has eleven
+	if (f == "total_tile_color") return put3(total_tile_color(v3(3), v3(0), v3(6), float3(in[9], in[10], in[0])));
+	if (f == "sky_color_mix") return put3(sky_color_mix(v3(0), in[3], in[4], in[5]));
+	if (f == "voronoi") return put4(voronoi(v2(0), in[2]));
+	if (f == "truchet_band") return put4(truchet_band(v2(0), in[2], in[3], v2(4)));
+	if (f == "braid") return put4(braid(v2(0), in[2], in[3], in[4], v2(5)));
+	if (f == "coordinate_material") { out[0] = val(coordinate_material(v3(0), v3(3), in[6])); return 1; }
+	// helpers of the kernels' scenes without a counterpart in the reference's shader text, stated here from their meaning (below)
+	if (f == "any3") { out[0] = any(v3(0)) ? 1.f : 0.f; return 1; }
+	if (f == "set_rgb") { float4 c = v4(0); set_rgb(c, in[4]); return put4(c); }
+	if (f == "sort3_desc") return put3(kat_sort3_desc(v3(0)));
+	if (f == "ray_passes_ball") { out[0] = kat_ray_passes_ball(v3(0), v3(3), v3(6), in[9]) ? 1.f : 0.f; return 1; }
+	if (f == "ray_leaves_floor_and_ball")
+	{
+		const bool leaves = (val(real(in[4])) >= 0.f) && (in[1] > 1e-20f) && (in[1] > in[6] || kat_ray_passes_ball(v3(0), v3(3), v3(7), in[10]));
+		out[0] = leaves ? 1.f : 0.f;
+		return 1;
+	}
 	if (f == "sdSphereFast") { out[0] = val(sdSphereFast(v3(0), float4(v3(3), in[6]), in[7])); return 1; }
 	if (f == "sdSphere") { out[0] = val(sdSphere(v3(0), in[3])); return 1; }
 	if (f == "sdBox") { out[0] = val(sdBox(v3(0), v3(3))); return 1; }
@@ -476,5 +565,58 @@ int orc_kat(const char *fn, const float *in, float *out)
 	if (f == "HSVtoRGB") return put3(HSVtoRGB(v3(0)));
 	return -1;
 }
+
+// n evaluations: input i is in[i * stride .. i * stride + stride) (stride <= 16, the rest of the 16 inputs is zero), its outputs are
+// out[8 * i .. 8 * i + 8).  flags (may be NULL; census build only): bit 0 = a square root, bit 1 = a constant division or ray
+// division, bit 2 = a reciprocal outside the domain of the kernels' fast exact forms during evaluation i, bit 3 = an overflowed
+// ("far field") argument of one of them.
+int kat_batch(const char *fn, long long n, const float *in, int stride, float *out, unsigned char *flags)
+{
+	if (stride < 0 || stride > 16) return -2;
+	const std::string f(fn);
+	int outputs = 0;
+	for (long long i = 0; i < n; ++i)
+	{
+		float a[16] = {0.f}, o[8] = {0.f};
+		memcpy(a, in + i * stride, sizeof(float) * (size_t)stride);
+#ifdef ORACLE_CENSUS
+		const Census before = census();
+#endif
+		outputs = kat_eval(f, a, o);
+		if (outputs < 0) return -1;
+		memcpy(out + 8 * i, o, sizeof o);
+#ifdef ORACLE_CENSUS
+		if (flags)
+		{
+			const Census &c = census();
+			flags[i] = (unsigned char)((c.sqrt_out_of_domain != before.sqrt_out_of_domain ? 1 : 0) | (c.divc_out_of_domain != before.divc_out_of_domain ? 2 : 0) |
+				(c.rcp_out_of_domain != before.rcp_out_of_domain ? 4 : 0) | (c.far_field != before.far_field ? 8 : 0));
+		}
+#else
+		(void)flags;
+#endif
+	}
+	return outputs;
+}
+
+} // namespace
+
+extern "C" {
+
+// Known-answer access to individual library functions (tests/test_oracle_*.py).
+// Returns the number of outputs written, or -1 for an unknown function.
+int orc_kat(const char *fn, const float *in, float *out) { return kat_eval(fn, in, out); }
+
+// The same for n inputs in one call (tests/probe_scenes.py): see kat_batch.  Returns the number of outputs per input, -1 for an
+// unknown function, -2 for a stride beyond 16.
+int orc_kat_batch(const char *fn, long long n, const float *in, int stride, float *out) { return kat_batch(fn, n, in, stride, out, nullptr); }
+
+#ifdef ORACLE_CENSUS
+// ... and, in the census build, one flag byte per input: whether its evaluation left the domain of a fast exact form (kat_batch)
+int orc_kat_batch_census(const char *fn, long long n, const float *in, int stride, float *out, unsigned char *flags)
+{
+	return kat_batch(fn, n, in, stride, out, flags);
+}
+#endif
 
 } // extern "C"

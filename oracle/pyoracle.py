@@ -228,6 +228,26 @@ def kat(fn, *args, nout=4):
     return o[:n].copy()
 
 
+def kat_batch(fn, inputs, census=False):
+    """orc_kat for many inputs: inputs [n, k <= 16] float32 -> outputs [n, m] float32 (m = what the function writes); with
+    census=True (liboracle_census.so) -> (outputs, flags [n] uint8): bit 0 / 1 / 2 = a square root / constant division /
+    reciprocal of that evaluation had an argument outside the domain of the kernels' fast exact form, bit 3 = an overflowed one."""
+    x = np.ascontiguousarray(inputs, np.float32)
+    assert x.ndim == 2 and x.shape[1] <= 16
+    n = x.shape[0]
+    out = np.zeros((n, 8), np.float32)
+    vp = ctypes.c_void_p
+    if census:
+        flags = np.zeros(n, np.uint8)
+        m = lib(census=True).orc_kat_batch_census(fn.encode(), ctypes.c_longlong(n), vp(x.ctypes.data), x.shape[1], vp(out.ctypes.data), vp(flags.ctypes.data))
+    else:
+        m = lib().orc_kat_batch(fn.encode(), ctypes.c_longlong(n), vp(x.ctypes.data), x.shape[1], vp(out.ctypes.data))
+    if m < 0:
+        raise KeyError(fn)
+    out = np.ascontiguousarray(out[:, :m])
+    return (out, flags) if census else out
+
+
 def kat_u32(fn, u):
     a = np.zeros(16, np.float32)
     a.view(np.uint32)[0] = u
@@ -272,8 +292,11 @@ def census(scene, frame, step=(1, 1), region=None):
     L.orc_census_get(c.ctypes.data_as(ctypes.c_void_p))
     census.last_domain_violations = (int(c[2]), int(c[3]))
     census.last_far_field = int(c[4])
+    L.orc_census_rcp.restype = ctypes.c_ulonglong
+    census.last_rcp_violations = int(L.orc_census_rcp())  # reciprocals outside rcp1's domain (r_rcp, r_rsqrt, atan2, sdRoundCone)
     return out, totals, int(c[0]), int(c[1])
 
 
 census.last_domain_violations = (0, 0)
 census.last_far_field = 0
+census.last_rcp_violations = 0

@@ -227,7 +227,7 @@ inline real sdRoundCone(float3 p, float3 a, float3 b, real r1, real r2)
 	real l2 = dot(ba, ba);
 	real rr = r1 - r2;
 	real a2 = l2 - rr * rr;
-	real il2 = real(1.0f) / l2;
+	real il2 = r_rcp(l2); // 1.0f / l2
 
 	float3 pa = p - a;
 	real y = dot(pa, ba);

@@ -42,6 +42,38 @@ def cameras():
     return cams
 
 
+FAR22 = 4194304.0  # 2^22: the marble's last octaves reach lattice coordinates of 2^24 .. 2^26
+LATE = 369098752.0  # 11 * 2^25: the fire's scrolled coordinate, 3 * stime, is beyond 2^30 in every octave
+
+
+def fallback_cameras():
+    """[(name, kind, eye, direction or look-at, stime)]: frames in which some noise evaluations, and not all, leave the gradient table's
+    straight-line path (sdfr_noise.h: a lane whose `ok` is cleared evaluates the noise again with the formula) -- which needs a
+    lattice coordinate i whose noise_mod289 leaves [-1, 289].  For positive i that happens from 2^24 on, at a rate of 2e-3 and more.  For
+    negative i it happens only for the 850 values -17957882 - 1156 k, down to -18939326, where it gives 290 (an exhaustive sweep of
+    the even integers of [-2^25, -2^24]; none in the next three binades).  tests/test_labyrinth_fallback_cpu.py counts, on the host
+    build with the table, what falls back in each of these frames; directions, offsets and LATE were chosen by those counts.
+      * late*: bench sweep cameras that show a torch, at a time so late that the fire's scrolled coordinate falls back in every flame pixel;
+      * far22_pp, _np, _pn: one camera per quadrant at +-2^22; where x or z is positive, walls and vases fall back in a few pixels;
+      * far22_nn: the quadrant where both are negative.  With |x| = |z| = 2^22 the walls' lattice coordinates are about -7.0e6 times
+        the octave (1, 2, 4, 8) and -2.8e6 times it for y, the vases' three times that: none of them meets the band above, and of 6000
+        random cameras within 2000 units of (-2^22, -2^22) none had a pixel fall back.  The camera therefore stands at 1.3 * 2^22, where
+        the walls' second octave (about -1.84e7) lies in the band; it was the second of the first 25 random cameras there with a count."""
+    import bench
+
+    cams = []
+    for k in (3, 15):
+        kind, eye, target, _stime = bench.CONFIGS["3"]["camera"](k)
+        cams.append(("late%d" % k, kind, eye, target, LATE))
+    cams += [
+        ("far22_pp", "dir", (FAR22 + 11.25, 5.0, FAR22 - 6.5), (-0.7, -0.3, 0.7), 0.6),
+        ("far22_np", "dir", (-(FAR22 - 8.5), 6.5, FAR22 + 14.0), (-0.3, -0.3, -0.95), 0.6),
+        ("far22_pn", "dir", (FAR22 + 11.25, 5.0, -(FAR22 - 6.5)), (-0.9, -0.3, -0.4), 0.6),
+        ("far22_nn", "dir", (-5596275.0, 6.5, -5419721.0), (0.39, -0.3, 0.92), 0.6),
+    ]
+    return cams
+
+
 def oracle_frame(oracle, cam, **limits):
     _name, kind, eye, target, stime = cam
     basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, target, FOVY, np.float32(W) / np.float32(H))

@@ -76,3 +76,25 @@ def test_wavefront_schedule_matches_the_oracle(renderer, oracle, name):
 
     cam = next(c for c in CAMERAS if c[0] == name)
     _compare(renderer, oracle, cam, [sp.SCHEDULE_WAVEFRONT])
+
+
+# ---- the gradient table's second pass -----------------------------------------------------------------------------------
+# Frames in which some lanes of the pixel kernel, and not all, find their lattice coordinates outside the table path's domain and
+# evaluate the noise again with the formula, divergently (sdfr_noise.h: snoise3 / turbulence3 with NoiseGradTable); no camera above
+# reaches that.  tests/test_labyrinth_fallback_cpu.py counts the pixels that do, per frame, on the host build with the table.
+FALLBACK_CAMERAS = lsc.fallback_cameras()
+
+
+@pytest.mark.parametrize("name", [c[0] for c in FALLBACK_CAMERAS])
+def test_table_fallback_frames_match_the_oracle(renderer, oracle, name):
+    import sdf_playground_amd as sp
+
+    cam = next(c for c in FALLBACK_CAMERAS if c[0] == name)
+    _compare(renderer, oracle, cam, [sp.SCHEDULE_PIXEL])
+
+
+def test_table_fallback_frame_matches_the_oracle_on_the_wavefront_schedule(renderer, oracle):
+    """the wavefront kernels shade with the formula: the same frame, the other gradient source"""
+    import sdf_playground_amd as sp
+
+    _compare(renderer, oracle, next(c for c in FALLBACK_CAMERAS if c[0] == "far22_pn"), [sp.SCHEDULE_WAVEFRONT])
