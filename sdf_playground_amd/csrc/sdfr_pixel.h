@@ -206,6 +206,22 @@ SDF_HD int march_advance(March &m, float d, float dist_max, uint32_t iter_count,
 }
 // relaxation starts at the fourth sample (pshader_sdf.hlsl:189-192)
 SDF_HD void march_pre(March &m) { if (m.iter == 3) m.factor = 1.5f; }
+// march_advance for one of a ray's first three samples, where m.factor is 1 (requires m.iter < 3 and m.iter < iter_count; no march_pre
+// before it): no over-step, d * 1 is d, so the step forward and the last safe point are the one sum, and m.factor stays.  Every field
+// of the state and the status come out as march_pre + march_advance leave them, bit for bit (tests/test_march_peel_cpu.py).
+SDF_HD int march_advance_unrelaxed(March &m, float d, float dist_max, uint32_t iter_count, float dist_eps)
+{
+	m.d = d;
+	const bool out_of_range = m.t > dist_max;
+	const bool stop = out_of_range | (d < dist_eps);
+	const float fwd = m.t + d;
+	m.last_d = d;
+	m.t = stop ? m.t : fwd;
+	m.last_safe = stop ? m.last_safe : fwd;
+	if (stop) return out_of_range ? MARCH_MISS : MARCH_HIT;
+	m.iter++;
+	return m.iter < iter_count ? MARCH_CONTINUE : MARCH_MISS;
+}
 
 // ---- forward-difference normal (pshader_sdf.hlsl:164-177, Q10) --------------------------------
 SDF_HD vec3 grad_sample_pos(vec3 p, int axis, float eps)
@@ -424,6 +440,19 @@ template <class Scene>
 struct ShadowHitsNeedMaterial<Scene, typename VoidOfN<decltype(Scene::shadow_hits_need_material)>::type>
 {
 	static constexpr bool value = Scene::shadow_hits_need_material;
+};
+
+// The relaxation starts at a ray's fourth sample, so in its first three the march's rewind logic has nothing to decide.  A scene that
+// declares `peel_unrelaxed_samples = true` gets those three samples as straight-line code in front of the march loop of its pixel kernel
+// (render_pixel: march_advance_unrelaxed, then the factor once, then the loop without march_pre) -- the same samples, states and counters;
+// more code, fewer instructions per pass.  Per scene, because it is another register draw for the whole kernel: a scene opts in with a
+// measurement of its own.  Never in the debug-plane build.
+template <class Scene, class = void>
+struct PeelUnrelaxedSamples { static constexpr bool value = false; };
+template <class Scene>
+struct PeelUnrelaxedSamples<Scene, typename VoidOfN<decltype(Scene::peel_unrelaxed_samples)>::type>
+{
+	static constexpr bool value = Scene::peel_unrelaxed_samples;
 };
 
 // A scene whose light() puts a directional light into slot 0 in every frame may declare `static SDF_HD vec3 frame_sun_dir(const FrameU &U)`:

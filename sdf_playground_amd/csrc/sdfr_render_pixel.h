@@ -110,6 +110,10 @@ struct RetireAfter { static constexpr int value = 8; };
 template <class Scene>
 struct RetireAfter<Scene, typename VoidOf<decltype(Scene::retire_after)>::type> { static constexpr int value = Scene::retire_after; };
 
+// which sample of a ray a pass of the peeled march takes (render_pixel): one of the first three, whose m.factor is 1, or a later one
+template <bool FirstThree>
+struct MarchSample { static constexpr bool value = FirstThree; };
+
 struct PixelCounters
 {
 	uint32_t rays, march_evals, hits;
@@ -171,6 +175,51 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		float clear_from = 3e38f;
 		if constexpr (EscapesFrom<Scene>::available)
 			if (shortcuts) clear_from = EscapesFrom<Scene>::get(U, ray.pos, ray.dir, max_range); // (a ray inside a refracting body ends on its surface)
+		if constexpr (!DBG && PeelUnrelaxedSamples<Scene>::value)
+		{
+			// The loop below with the ray's first three samples in front of it as straight-line code (PeelUnrelaxedSamples, sdfr_pixel.h): one
+			// pass, `first_three` a MarchSample: with m.factor 1 for certain an escaped sample ends the ray before its evaluation and nothing
+			// is rewound (march_advance_unrelaxed).  Then the factor once, then the passes that may rewind, without march_pre.
+			auto march_step = [&](auto first_three) -> int
+			{
+				constexpr bool UNRELAXED = decltype(first_three)::value;
+				bool escaped = shortcuts && RayEscapes<Scene>::test(U, R, march_pos(m), ray.dir);
+				if constexpr (EscapesFrom<Scene>::available) escaped = escaped || m.t >= clear_from;
+				if (escaped && (UNRELAXED || m.factor == 1.f)) return MARCH_MISS;
+				float d;
+				if constexpr (SceneReadsMarchState<Scene>::value)
+				{
+					const PixelRay pr = store.pixel_ray_kept();
+					GeoStep gs;
+					gs.camera_distance = m.t;
+					gs.right_off = pr.right_ray;
+					gs.bottom_off = pr.bottom_ray;
+					d = map_geometry_at<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true, gs) * inside_sign;
+				}
+				else
+					d = map_geometry<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true) * inside_sign;
+				cnt.march_evals++;
+				if constexpr (UNRELAXED)
+					return march_advance_unrelaxed(m, d, max_range, (uint32_t)U.iter_count, U.dist_eps);
+				else
+				{
+					if (escaped && !((m.last_d + d) < m.last_d * m.factor)) return MARCH_MISS;
+					return march_advance(m, d, max_range, (uint32_t)U.iter_count, U.dist_eps);
+				}
+			};
+			// (a ray goes on more often than not: said, because a comparison with 0 counts as unlikely and the compiler laid the passes out backwards)
+			status = march_step(MarchSample<true>());
+			if (__builtin_expect(status == MARCH_CONTINUE, 1)) status = march_step(MarchSample<true>());
+			if (__builtin_expect(status == MARCH_CONTINUE, 1)) status = march_step(MarchSample<true>());
+			if (__builtin_expect(status == MARCH_CONTINUE, 1))
+			{
+				m.factor = 1.5f;
+				do
+					status = march_step(MarchSample<false>());
+				while (status == MARCH_CONTINUE);
+			}
+		}
+		else // the march as every other scene's kernel has it (body not re-indented: their code stays what it was)
 		do
 		{
 			march_pre(m);

@@ -184,6 +184,7 @@ struct SceneLabyrinth
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
 	static constexpr bool noise_grad_table = true; // marble walls, vase and sky: turbulence3 in ~80 % of tiles (sdfr_pixel_kernel.h)
 	static constexpr bool shadow_hits_need_material = false; // material() is a pure function and sets no alpha: a shadow ray's hit adds 0 whatever it is made of (sdfr_render_pixel.h)
+	static constexpr bool peel_unrelaxed_samples = true; // a ray's first three samples as straight-line code in front of the march loop (sdfr_pixel.h)
 	static const char *variables() { return ""; }
 	enum { SU_FIRE_SCROLL = 0, SU_SUN_DIR = 1 /* .. 3 */ };
 	static SDF_HD void prepare(FrameU &U)
