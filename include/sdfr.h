@@ -596,6 +596,41 @@ int sdfr_mesh_extract(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vert
  * Waits for that work. */
 int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4]);
 
+/* ---- ... with the scene's sharp edges and corners kept (DESIGN.md "Sharp mesh extraction").  sdfr_mesh_extract in every respect but
+ *      two: the position of each vertex, and normals[v], which follows because it is the point query's normal at positions[v].  The
+ *      lattice and the inside test, the active cells and their order, the quads with their order and winding, the indices and the
+ *      counts, the capacity rule and the counting call, the argument errors and their precedence, what is latched, the stream, two
+ *      frames in flight, on_host and the workspace are sdfr_mesh_extract's, word for word.  The mesh keeps surface nets' connectivity
+ *      (dual contouring's): only the vertices move, onto the planes the scene has where the cell's edges cross its surface.
+ *
+ *      All arithmetic is fp32; every operation is separate and unfused, in the order written.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *      D(q) is what sdfr_query_distance returns at q.  For an active cell, visit its 12 edges in sdfr_mesh_extract's order, from lower
+ *      endpoint a to upper endpoint b; an edge with exactly one endpoint inside yields a crossing:
+ *      Refine: lo = 0, hi = 1, s_lo = D_a - iso, s_hi = D_b - iso.  Four times: mid = 0.5f * (lo + hi); q = a's position with the
+ *      edge axis' coordinate p_a + mid * (p_b - p_a); s = D(q) - iso; if (s < 0) == (s_lo < 0) then lo = mid, s_lo = s, otherwise
+ *      hi = mid, s_hi = s.  Then t = lo + (s_lo / (s_lo - s_hi)) * (hi - lo); if !(t >= lo && t <= hi) (NaN too), t = 0.5f * (lo + hi).
+ *      The crossing p_i is a's position with the edge axis' coordinate p_a + t * (p_b - p_a).
+ *      Plane: d_i and n_i are the distance and the normal sdfr_query_distance returns at p_i; s_i = d_i - iso.  The crossing
+ *      contributes a plane iff all of n_i and s_i are finite and n_i is not (0, 0, 0).
+ *      Mass point: m = the running per-component sum of all crossings in edge order, divided by (float)crossings -- surface nets'
+ *      formula over the refined crossings.
+ *      Normal equations, over the c contributing planes in edge order: b_i = ((n_i.x*(p_i.x - m.x) + n_i.y*(p_i.y - m.y)) +
+ *      n_i.z*(p_i.z - m.z)) - s_i; H_kl = the running sum from 0 of n_i[k]*n_i[l], six distinct entries; then H_kk = H_kk +
+ *      0x1p-8f * (float)c; g_k = the running sum from 0 of n_i[k]*b_i.
+ *      Solve, three steps of conjugate gradients from y = 0: r = g, d = g, rr = dot(r, r).  Up to three times: if !(rr > 0) stop;
+ *      Hd_k = (H_k0*d.x + H_k1*d.y) + H_k2*d.z; dHd = dot(d, Hd); if !(dHd > 0) stop; alpha = rr / dHd; y_k = y_k + alpha*d_k;
+ *      r_k = r_k - alpha*Hd_k; rr2 = dot(r, r); beta = rr2 / rr; d_k = r_k + beta*d_k; rr = rr2.  With c = 0 nothing runs and y = 0.
+ *      Vertex: x = m + y; if any component of x is not finite, x = m.  With h = 0.5f * cell, lo_k the cell's lower lattice coordinate
+ *      minus h and hi_k its upper one plus h: x_k = fminf(fmaxf(x_k, lo_k), hi_k).
+ *
+ *        - a vertex therefore never leaves its own cell by more than half a cell on any axis.  A vertex outside its own cell can in
+ *          principle fold a quad: the connectivity is not changed to prevent that.
+ *        - 8 scene evaluations per crossing (4 bisection samples, the point query and the 3 samples of its normal), about 40 per
+ *          vertex, on top of sdfr_mesh_extract's lattice.
+ *        - sdfr_mesh_get_timings keeps its four slots: the sharp vertices are counted in "emit". ------------------------------------- */
+int sdfr_mesh_extract_sharp(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions /*[v][3]*/,
+	float *normals /*[v][3] or NULL*/, uint32_t *indices /*[t][3]*/, sdfr_mesh_counts *counts /*host, required*/, int on_host);
+
 /* ---- a texture atlas of an extracted mesh (no counterpart in the reference; DESIGN.md "Texture atlas"): one square tile of texels per
  *      quad of the mesh, baked on the GPU.  Surface nets emits quads: triangles 2q and 2q + 1 are (q0, q1, q2) and (q0, q2, q3) of one
  *      quad, so a tile per quad needs no chart cutting and no packing search, and bilinear filtering inside a quad never leaves its tile.

@@ -184,6 +184,13 @@ public:
 		return handle && pushState() &&
 			sdfr_mesh_extract(handle, &grid, vertex_capacity, triangle_capacity, positions, normals, indices, &counts, on_host ? 1 : 0) == SDFR_OK;
 	}
+	// ... with the vertices on the scene's edges and corners (sdfr_mesh_extract_sharp in sdfr.h): the same counts and indices
+	bool extractMeshSharp(const sdfr_mesh_grid &grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals, uint32_t *indices,
+		sdfr_mesh_counts &counts, bool on_host = true)
+	{
+		return handle && pushState() &&
+			sdfr_mesh_extract_sharp(handle, &grid, vertex_capacity, triangle_capacity, positions, normals, indices, &counts, on_host ? 1 : 0) == SDFR_OK;
+	}
 
 	// The texture atlas of an extracted mesh (sdfr_atlas_layout, sdfr_atlas_uvs, sdfr_atlas_texels, sdfr_atlas_bake in sdfr.h): one square
 	// tile of texels per quad.  atlasTexels looks at the mesh alone; bakeAtlas looks at every texel as meshSurfaces / meshLighting look at

@@ -132,6 +132,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_occlusion_directions", "sdfr_query_occlusion", "sdfr_hit_occlusion",
     "sdfr_query_ray_lighting", "sdfr_pick_lighting", "sdfr_mesh_lighting",
     "sdfr_atlas_layout", "sdfr_atlas_uvs", "sdfr_atlas_texels", "sdfr_atlas_bake",
+    "sdfr_mesh_extract_sharp",
 ]
 
 _lib = None
@@ -241,6 +242,7 @@ def load_library():
     L.sdfr_query_occlusion.argtypes = [vp, i64, vp, vp, cf, cf, vp, ci]
     L.sdfr_hit_occlusion.argtypes = [vp, i64, vp, cf, cf, vp, ci]
     L.sdfr_mesh_extract.argtypes = [vp, ctypes.POINTER(MeshGrid), i64, i64, vp, vp, vp, ctypes.POINTER(MeshCounts), ci]
+    L.sdfr_mesh_extract_sharp.argtypes = L.sdfr_mesh_extract.argtypes
     L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
     L.sdfr_atlas_layout.argtypes = [i64, ci, ci, ctypes.POINTER(Atlas)]
     L.sdfr_atlas_uvs.argtypes = [ctypes.POINTER(Atlas), vp]
@@ -769,10 +771,12 @@ class SDFRenderer:
 
     # ---- the loaded scene as a triangle mesh (sdfr_mesh_extract; DESIGN.md "Mesh extraction") ------------------------------------
     def extractMesh(self, origin, cell, dims, iso=0.0, normals=True, device=False, surfaces=False, reach=None, occlusion=False, ao_radius=None,
-                    ao_bias=None, lighting=False, atlas=None):
+                    ao_bias=None, lighting=False, atlas=None, sharp=False):
         """Surface nets over the lattice origin + (i, j, k) * cell, dims = (nx, ny, nz) cells: (positions [v, 3] float32, normals [v, 3]
         float32 or None, indices [t, 3]) -- numpy arrays (indices uint32), or with device=True torch tensors on the renderer's GPU
         (indices int32: the same 32 bits), enqueued on the handle's stream.  The counting call, then the filling call.
+        sharp=True: sdfr_mesh_extract_sharp -- the same indices, every vertex moved onto the scene's planes at its cell's edge crossings, so
+        that the scene's edges and corners stay sharp; everything below composes with it unchanged.
         surfaces=True: a fourth element, the surface at every vertex (meshSurfaces with `reach`, default 2 * cell; needs the normals) --
         the mesh is made on the GPU and looked at there, whatever `device` says about where the results go.
         occlusion=True: one more element, after the surfaces if both are asked for: the ambient occlusion at every vertex
@@ -784,7 +788,7 @@ class SDFRenderer:
         if surfaces or occlusion or lighting or atlas is not None:
             if not normals:
                 raise ValueError("surfaces=True, occlusion=True, lighting=True and atlas need the normals")
-            pos, nrm, idx = self.extractMesh(origin, cell, dims, iso, True, device=True)
+            pos, nrm, idx = self.extractMesh(origin, cell, dims, iso, True, device=True, sharp=sharp)
             baked = None
             if atlas is not None:
                 unknown = set(atlas) - {"tile", "width", "layers", "occlusion"}
@@ -825,7 +829,8 @@ class SDFRenderer:
             return (pos.cpu().numpy(), nrm.cpu().numpy(), idx.cpu().numpy().view(np.uint32)) + tuple(extra) + ((baked,) if baked is not None else ())
         grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
         counts = MeshCounts()
-        self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), 0 if device else 1))
+        extract = self._L.sdfr_mesh_extract_sharp if sharp else self._L.sdfr_mesh_extract
+        self._check(extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), 0 if device else 1))
         v, t = int(counts.vertices), int(counts.triangles)
         if device:
             import torch
@@ -842,7 +847,7 @@ class SDFRenderer:
             ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
         if v:
             again = MeshCounts()
-            self._check(self._L.sdfr_mesh_extract(self._h, ctypes.byref(grid), v, t, ptr(pos), ptr(nrm), ptr(idx), ctypes.byref(again), 0 if device else 1))
+            self._check(extract(self._h, ctypes.byref(grid), v, t, ptr(pos), ptr(nrm), ptr(idx), ctypes.byref(again), 0 if device else 1))
             if (again.vertices, again.triangles) != (v, t):
                 raise SdfrError(-9, "the mesh changed between the counting and the filling call")
         return pos, nrm, idx

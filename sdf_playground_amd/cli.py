@@ -13,13 +13,15 @@
     python -m sdf_playground_amd.cli --scene labyrinth --aa 4 --out clean.png        # 4 x 4 sub-samples per pixel, resolved on the GPU
     python -m sdf_playground_amd.cli --scene tree --mesh tree.obj --mesh-box -2 0 -2 2 4 2 --mesh-cell 0.02   # the scene as a triangle mesh
     python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-colors --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... with its materials
+    python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-sharp --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... with its walls' edges kept sharp
     python -m sdf_playground_amd.cli --scene lense --size 640x360 --gbuffer lense.npz   # depth, normal, albedo, material id per pixel
     python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-colors --mesh-ao 0.4 --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... shaded by ambient occlusion
 
 --out writes the tone-mapped + bloomed LDR image (HDR::process, like the reference's window);
 --out-hdr writes the raw float32 RGBA frame as .npy.  --mesh writes the scene's surface (distance == --mesh-iso) inside --mesh-box
 as a Wavefront OBJ with normals: surface nets on cells of edge --mesh-cell (SDFRenderer.extractMesh), at --time with the --set
-variables; --mesh-colors adds a colour per vertex (`v x y z r g b`): the albedo of the material under the vertex, or its unlit colour
+variables; --mesh-sharp keeps the same triangles and moves every vertex onto the scene's planes at its cell's edge crossings, so that
+edges and corners stay sharp (SDFRenderer.extractMesh(sharp=True)); --mesh-colors adds a colour per vertex (`v x y z r g b`): the albedo of the material under the vertex, or its unlit colour
 (SDFRenderer.extractMesh(surfaces=True)).  --gbuffer writes what lies under every pixel of the frame --out would render, as an .npz:
 depth [h, w] (the hit's t; inf on a miss), normal [h, w, 3] (the shading normal), albedo [h, w, 3] (as --mesh-colors, unclipped),
 material_id and valid [h, w] (SDFRenderer.pickSurfaces).  --mesh-ao RADIUS multiplies the vertex colours (grey without --mesh-colors)
@@ -126,6 +128,8 @@ def make_parser():
     ap.add_argument("--mesh-box", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     ap.add_argument("--mesh-cell", type=float, metavar="C", help="edge length of a cell")
     ap.add_argument("--mesh-iso", type=float, default=0.0, metavar="V", help="the surface is distance == V (default 0)")
+    ap.add_argument("--mesh-sharp", action="store_true", help="with --mesh: keep the scene's sharp edges and corners -- the same triangles, every "
+                    "vertex moved onto the scene's planes at its cell's edge crossings (SDFRenderer.extractMesh(sharp=True))")
     ap.add_argument("--mesh-colors", action="store_true", help="with --mesh: a colour per vertex, from the material under it")
     ap.add_argument("--gbuffer", metavar="OUT.npz", help="write depth, normal, albedo, material_id and valid of every pixel of the frame")
     ap.add_argument("--mesh-ao", type=float, metavar="RADIUS", help="with --mesh: vertex colours times the ambient openness within RADIUS")
@@ -208,6 +212,8 @@ def main(argv=None):
             ap.error("--atlas-width must be a multiple of 8 and of --atlas-tile, at most 16384")
     elif a.mesh_atlas:
         ap.error("--mesh-atlas needs --mesh")
+    elif a.mesh_sharp:
+        ap.error("--mesh-sharp needs --mesh")
     if a.mesh:
         try:
             mesh_grid = mesh_grid_from_box(a.mesh_box, a.mesh_cell)
@@ -252,6 +258,8 @@ def main(argv=None):
         colors = None
         ao = dict(occlusion=True, ao_radius=a.mesh_ao) if a.mesh_ao is not None else {}
         baked = None
+        if a.mesh_sharp:
+            ao["sharp"] = True
         if a.mesh_atlas:
             ao["atlas"] = dict(tile=a.atlas_tile, width=a.atlas_width, layers=(a.atlas_layer,))
         if a.mesh_lit:

@@ -946,10 +946,11 @@ int sdfr_hit_occlusion(sdfr_renderer *r, int64_t n, const sdfr_hit *hits, float 
 
 // sdfr_mesh_extract (the definition: include/sdfr.h; the plan: sdfr_mesh_plan.h; stages: sdfr_mesh.h, sdfr_mesh.hip), a call of the queries'
 // protocol.  Sample the lattice, classify and scan, read the two totals back; then, if the capacities allow, emit vertices and indices
-// and ask the point query for the normals at the vertices.
+// and ask the point query for the normals at the vertices.  sharp: sdfr_mesh_extract_sharp -- the emit stage leaves each vertex's cell
+// index instead of the vertex, and the scene's sharp-vertex kernel (sdfr_mesh_sharp.h) makes the vertices from them; all else is the same.
 static_assert(sizeof(sdfr_mesh_grid) == sizeof(MeshGrid) && offsetof(sdfr_mesh_grid, cell) == offsetof(MeshGrid, cell) && offsetof(sdfr_mesh_grid, nx) == offsetof(MeshGrid, n) &&
 		offsetof(sdfr_mesh_grid, iso) == offsetof(MeshGrid, iso), "sdfr_mesh_grid is the plan's MeshGrid");
-static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *counts)
+static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *counts, bool sharp)
 {
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
 	const MeshPlan p = plan_mesh(c);
@@ -1004,7 +1005,16 @@ static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *c
 		if (rc != SDFR_OK) return rc;
 	}
 	if (ev) SDFR_HIP(hipEventRecord(ev[3], stream));
-	SDFR_HIP(launch_mesh_emit(p.g, d_lattice, d_cells, d_points, d_pos, d_idx, stream));
+	SDFR_HIP(launch_mesh_emit(p.g, d_lattice, d_cells, d_points, d_pos, d_idx, sharp, stream));
+	if (sharp)
+	{
+		KernelRef sharp_kernel;
+		rc = loaded_query_kernel(r, QUERY_KERNEL_MESH_SHARP, U, sharp_kernel);
+		if (rc != SDFR_OK) return rc;
+		const MeshSharpArgs m = {{p.g.origin[0], p.g.origin[1], p.g.origin[2]}, p.g.cell, {p.g.n[0], p.g.n[1], p.g.n[2]}, p.g.iso, d_lattice, d_pos, n_vertices};
+		const hipError_t es = launch_mesh_sharp(sharp_kernel, U, m, stream);
+		if (es != hipSuccess) return hip_fail(r, es, "sharp vertex launch");
+	}
 	if (ev) SDFR_HIP(hipEventRecord(ev[4], stream));
 	if (d_nrm)
 	{
@@ -1030,7 +1040,16 @@ int sdfr_mesh_extract(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vert
 {
 	return guarded(r, [&]() -> int {
 		const MeshRequest c = {reinterpret_cast<const MeshGrid *>(grid), vertex_capacity, triangle_capacity, positions, normals, indices, counts, on_host};
-		return mesh_impl(r, c, counts);
+		return mesh_impl(r, c, counts, false);
+	});
+}
+
+int sdfr_mesh_extract_sharp(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions, float *normals,
+	uint32_t *indices, sdfr_mesh_counts *counts, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		const MeshRequest c = {reinterpret_cast<const MeshGrid *>(grid), vertex_capacity, triangle_capacity, positions, normals, indices, counts, on_host};
+		return mesh_impl(r, c, counts, true);
 	});
 }
 

@@ -86,6 +86,7 @@ const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_
 	{"sdfr_jit_query_occlusion", "query_occlusion_kernel", "QueryKernelArgs"},
 	{"sdfr_jit_query_lighting", "query_lighting_kernel", "QueryKernelArgs"},
 	{"sdfr_jit_bake_atlas", "atlas_bake_kernel", "AtlasKernelArgs"},
+	{"sdfr_jit_mesh_sharp", "mesh_sharp_kernel", "MeshSharpKernelArgs"},
 };
 
 } // namespace
@@ -152,7 +153,8 @@ bool jit_compile_code(const std::string &arch_name, const std::string &name, con
 	// checked against and a user's text is not: run-time scenes get the plain IEEE forms unless the text
 	// opts in by containing the token SDFR_FAST_EXACT_MATH (say, in a comment)
 	const char *math = scene_source.find("SDFR_FAST_EXACT_MATH") != std::string::npos ? "-DSDFR_FAST_EXACT_MATH=1" : "-DSDFR_SAFE_MATH=1";
-	const char *opts[] = {arch.c_str(), "-std=c++17", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", inc.c_str(), block.c_str(), math};
+	const std::string sharp_lanes = "-DSDFR_MESH_SHARP_LANES=" + std::to_string(SDFR_MESH_SHARP_LANES); // must match launch_mesh_sharp
+	const char *opts[] = {arch.c_str(), "-std=c++17", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", inc.c_str(), block.c_str(), math, sharp_lanes.c_str()};
 	rc = rtc.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
 	size_t log_bytes = 0;
 	rtc.log_size(prog, &log_bytes);

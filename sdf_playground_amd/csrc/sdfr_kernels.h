@@ -73,12 +73,15 @@ uint32_t query_lattice_blocks(const LatticeArgs &g); // blocks of one wave that 
 // Surface nets over a lattice of distances (sdfr_mesh.h, sdfr_mesh.hip), every pointer device memory.  launch_mesh_count: the vertex
 // flag per cell and the quad count per lattice point, then their exclusive prefix sums in place -- cell_vertex [cells + 1] and
 // point_quad [points + 1], whose last elements are the totals; sums: mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)
-// words of scratch.  launch_mesh_emit: positions [vertices][3] and, unless null (no quads), indices [2 * quads][3].
+// words of scratch.  launch_mesh_emit: positions [vertices][3] and, unless null (no quads), indices [2 * quads][3]; cells_only: instead of
+// a vertex, its cell's linear index as the bits of its first word, for launch_mesh_sharp -- a scene's sharp-vertex kernel
+// (QUERY_KERNEL_MESH_SHARP) for U, which makes the vertices of sdfr_mesh_extract_sharp from them (sdfr_mesh_sharp.h).
 struct MeshGrid;
 size_t mesh_scan_sum_words(size_t n);
 hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *cell_vertex, uint32_t *point_quad, uint32_t *sums, hipStream_t stream);
 hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
-	uint32_t *indices, hipStream_t stream);
+	uint32_t *indices, bool cells_only, hipStream_t stream);
+hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshSharpArgs &m, hipStream_t stream);
 
 // The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
 // per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes

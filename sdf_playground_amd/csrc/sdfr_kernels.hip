@@ -497,6 +497,16 @@ hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const Latti
 	return launch_kernel(k, query_lattice_blocks(g), SDFR_PIXEL_BLOCK, args, stream);
 }
 
+hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshSharpArgs &m, hipStream_t stream)
+{
+	MeshSharpKernelArgs a;
+	a.U = U;
+	a.m = m;
+	void *args[] = {&a};
+	const uint32_t per_block = (uint32_t)SDFR_PIXEL_BLOCK / SDFR_MESH_SHARP_LANES; // vertices of a block
+	return launch_kernel(k, (m.vertices + per_block - 1u) / per_block, SDFR_PIXEL_BLOCK, args, stream);
+}
+
 hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
 {
 	AtlasKernelArgs a;

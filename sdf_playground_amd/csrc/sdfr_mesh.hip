@@ -1,7 +1,8 @@
 // sdfr_mesh.hip -- the scene-independent kernels of sdfr_mesh_extract (stage functions: sdfr_mesh.h) and of the mesh's texture atlas
 // (k_atlas_texels, at the end; sdfr_atlas.h): classify cells and lattice
 // points, exclusive prefix sums of the two flag arrays, emit vertices, emit indices.  The distances they read come from the
-// scene's lattice kernel (sdfr_query_kernel.h: query_lattice_kernel).
+// scene's lattice kernel (sdfr_query_kernel.h: query_lattice_kernel).  For sdfr_mesh_extract_sharp the vertex pass leaves each
+// vertex's cell index instead (k_mesh_emit_cells), and the scene's sharp-vertex kernel makes the vertices (mesh_sharp_kernel).
 //
 // The prefix sum is the plain three-phase one -- per-block totals, their scan (the same three phases again while they are more
 // than one block), then every block scans its own elements on top of its offset -- so no kernel ever waits for another workgroup:
@@ -119,6 +120,17 @@ __global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_emit_vertices(MeshGrid
 	o[2] = pos[2];
 }
 
+// one lane per cell, for the sharp vertices (sdfr_mesh_sharp.h): an active cell writes its own linear index (< 2^30) as the bits of its
+// vertex's first word, where the scene's sharp-vertex kernel (sdfr_query_kernel.h: mesh_sharp_kernel) finds it and writes the vertex
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_emit_cells(MeshGrid g, const uint32_t *__restrict__ cell_vertex, float *__restrict__ positions)
+{
+	const uint32_t c = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	if (c >= mesh_cell_count(g)) return;
+	const uint32_t v = cell_vertex[c];
+	if (cell_vertex[c + 1u] == v) return;
+	positions[(size_t)3 * v] = bits_f32(c);
+}
+
 // one lane per lattice point: a point with quads writes their triangles
 __global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_emit_indices(MeshGrid g, const float *__restrict__ lattice, const uint32_t *__restrict__ cell_vertex,
 	const uint32_t *__restrict__ point_quad, uint32_t *__restrict__ indices)
@@ -142,11 +154,14 @@ hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *
 }
 
 hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
-	uint32_t *indices, hipStream_t stream)
+	uint32_t *indices, bool cells_only, hipStream_t stream)
 {
 	const uint32_t points = mesh_point_count(g), cells = mesh_cell_count(g);
-	hipLaunchKernelGGL(k_mesh_emit_vertices, dim3((cells + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice, cell_vertex,
-		positions);
+	if (cells_only)
+		hipLaunchKernelGGL(k_mesh_emit_cells, dim3((cells + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, cell_vertex, positions);
+	else
+		hipLaunchKernelGGL(k_mesh_emit_vertices, dim3((cells + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice, cell_vertex,
+			positions);
 	if (indices)
 		hipLaunchKernelGGL(k_mesh_emit_indices, dim3((points + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice,
 			cell_vertex, point_quad, indices);

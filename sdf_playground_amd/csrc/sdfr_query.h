@@ -32,6 +32,13 @@ struct AtlasKernelArgs
 	AtlasArgs g;
 };
 
+// ... and the sharp-vertex kernel (MeshSharpArgs: sdfr_query_args.h)
+struct MeshSharpKernelArgs
+{
+	FrameU U;
+	MeshSharpArgs m;
+};
+
 // map_geometry at the sample of a query: a scene that reads the march state (GeoStep) gets the running camera_distance and
 // the ray's offsets, every other scene (p, dir) as in the pixel pipeline
 template <class Scene, bool DBG>

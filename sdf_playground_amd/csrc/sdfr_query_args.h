@@ -39,7 +39,7 @@ static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offseto
 static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
 // A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_KINDS = 7 };
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_KINDS = 8 };
 
 // One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
@@ -51,6 +51,25 @@ struct LatticeArgs
 	int32_t px, py, pz; // lattice points per axis
 	int32_t rows;       // 0: a wave owns a 4 x 4 x 4 brick of points; 1: 64 consecutive points of a row (the A/B of DESIGN.md 4.6)
 	float *out;
+};
+
+// One launch of the sharp vertices (sdfr_mesh_sharp.h; sdfr_mesh_extract_sharp): the grid, field for field MeshGrid's, the lattice of its
+// distances, and positions [vertices][3], whose word 3 * v holds vertex v's cell index when the kernel starts and which it overwrites.
+// SDFR_MESH_SHARP_LANES lanes per vertex, 64 / SDFR_MESH_SHARP_LANES vertices per block of one wave: 16, a lane per edge of the cell, is
+// what ships; 1, a lane per vertex, exists for the A/B of DESIGN.md 4.12 (a developer build: buildlib.build(extra=["-DSDFR_MESH_SHARP_LANES=1"])).
+#ifndef SDFR_MESH_SHARP_LANES
+#define SDFR_MESH_SHARP_LANES 16
+#endif
+static_assert(SDFR_MESH_SHARP_LANES == 16 || SDFR_MESH_SHARP_LANES == 1, "a lane per edge or a lane per vertex");
+struct MeshSharpArgs
+{
+	float origin[3];
+	float cell;
+	int32_t n[3];
+	float iso;
+	const float *lattice;
+	float *positions;
+	uint32_t vertices;
 };
 
 // One atlas launch (sdfr_atlas.h, sdfr_atlas_plan.h; sdfr_atlas_texels and sdfr_atlas_bake): the texels of a width x height image cut into

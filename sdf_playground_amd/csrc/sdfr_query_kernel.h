@@ -11,6 +11,7 @@
 #include "sdfr_occlusion.h"
 #include "sdfr_lighting.h"
 #include "sdfr_atlas.h"
+#include "sdfr_mesh_sharp.h"
 
 namespace sdfr {
 
@@ -289,6 +290,81 @@ __device__ __forceinline__ void atlas_bake_kernel(const AtlasKernelArgs &a)
 	if (g.normal) query_store(reinterpret_cast<uint32_t *>(g.normal), i, normal);
 	if (g.lit) query_store(reinterpret_cast<uint32_t *>(g.lit), i, lit);
 	g.valid[i] = (int32_t)valid;
+}
+
+// The sharp vertices of a mesh (sdfr_mesh_sharp.h; sdfr_mesh_extract_sharp): one wave per block, 16 lanes per vertex, so 4 vertices per
+// wave.  Most cells of a grid are inactive, so the work is per vertex: sdfr_mesh.hip has left vertex v's cell index in word 3 * v of
+// `positions`.  Lanes 0 .. 11 of a vertex own the cell's 12 edges: a lane whose edge crosses the surface makes its four bisection
+// evaluations and the point query with its normal (a uniform trip count; the lanes without a crossing sit masked), then every lane of
+// the group reads the twelve crossings in edge order through shuffles and sums them sequentially -- the bits of the sequential host
+// code -- and lane 0 writes the vertex over the cell index.  A group reads and writes its own vertex's three words only.
+// LANES = 1 (SDFR_MESH_SHARP_LANES, sdfr_query_args.h: a developer build, the A/B of DESIGN.md 4.12): a lane per vertex visits the 12
+// edges itself, as the host code does.
+template <class Scene, bool DBG>
+struct MeshSharpScene
+{
+	const FrameU &U;
+	__device__ __forceinline__ float distance(vec3 p) const { return query_point<Scene, DBG>(U, p, nullptr); }
+	__device__ __forceinline__ float distance_normal(vec3 p, vec3 &n) const { return query_point<Scene, DBG>(U, p, &n); }
+};
+template <class Scene, bool DBG, int LANES = SDFR_MESH_SHARP_LANES>
+__device__ __forceinline__ void mesh_sharp_kernel(const MeshSharpKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64 && (LANES == 16 || LANES == 1), "one wave per block: 4 vertices of 16 lanes, or 64 of one");
+	const MeshSharpArgs &m = a.m;
+	MeshGrid g;
+	for (int k = 0; k < 3; ++k)
+	{
+		g.origin[k] = m.origin[k];
+		g.n[k] = m.n[k];
+	}
+	g.cell = m.cell;
+	g.iso = m.iso;
+	const uint32_t lane = threadIdx.x, edge = lane & (uint32_t)(LANES - 1), base = lane - edge;
+	const uint32_t v = blockIdx.x * (uint32_t)(64 / LANES) + lane / (uint32_t)LANES; // < 2^30 + 64
+	const bool live = v < m.vertices;
+	float *o = m.positions + (size_t)3 * (live ? v : 0u);
+	uint32_t c = live ? f32_bits(o[0]) : 0u; // the cell's linear index, < 2^30 (read by every lane of the group before lane 0 writes)
+	if (c >= mesh_cell_count(g)) c = 0u;     // (never: k_mesh_emit_cells wrote it)
+	const uint32_t nx = (uint32_t)g.n[0], ny = (uint32_t)g.n[1];
+	const uint32_t row = c / nx, ck = row / ny;
+	const int i = (int)(c - row * nx), j = (int)(row - ck * ny), k = (int)ck;
+	const MeshSharpScene<Scene, DBG> scene = {a.U};
+	float x[3];
+	if constexpr (LANES == 1)
+	{
+		if (!live) return;
+		MeshSharpCrossing all[12];
+		for (int e = 0; e < 12; ++e) mesh_sharp_crossing(g, m.lattice, scene, i, j, k, e, all[e]);
+		mesh_sharp_vertex(g, i, j, k, [&all](int e) { return all[e]; }, x);
+	}
+	else
+	{
+		MeshSharpCrossing mine;
+		mine.flags = 0u;
+		mine.s = 0.f;
+		for (int t = 0; t < 3; ++t) mine.p[t] = mine.n[t] = 0.f;
+		if (live && edge < 12u) mesh_sharp_crossing(g, m.lattice, scene, i, j, k, (int)edge, mine);
+		// (every lane of the wave is here again: the shuffles below read lanes of the reader's own group)
+		mesh_sharp_vertex(g, i, j, k, [&](int e) {
+			MeshSharpCrossing r;
+			const int from = (int)base + e;
+			for (int t = 0; t < 3; ++t)
+			{
+				r.p[t] = __shfl(mine.p[t], from, 64);
+				r.n[t] = __shfl(mine.n[t], from, 64);
+			}
+			r.s = __shfl(mine.s, from, 64);
+			r.flags = (uint32_t)__shfl((int)mine.flags, from, 64);
+			return r;
+		}, x);
+	}
+	if (live && edge == 0u)
+	{
+		o[0] = x[0];
+		o[1] = x[1];
+		o[2] = x[2];
+	}
 }
 
 } // namespace sdfr
