@@ -430,6 +430,24 @@ struct EscapesFrom<Scene, typename VoidOfN<decltype(&Scene::escapes_from)>::type
 	static constexpr bool available = true;
 	static SDF_HD float get(const FrameU &U, vec3 start, vec3 dir, float range) { return Scene::escapes_from(U, start, dir, range); }
 };
+// ... and / or `static SDF_HD void ray_bounds(const FrameU &U, RayInv &R, vec3 start, vec3 dir, float range)`, called once per ray
+// right after ray_setup, with the ray's start and the range it is marched to: the scene may strengthen R with facts that hold for
+// every sample with t <= range, and its ray_escapes may then call such a ray gone although the scene goes on beyond `range`.  The
+// licence is escapes_from's: a hit needs m.t <= dist_max (march_advance), and a miss of such a scene is the same result whatever
+// ended it -- the range, the iteration limit or the rule.  Nothing per step.  Only render_pixel calls it, and only with step
+// shortcuts on: the wavefront march applies no shortcuts, the ray queries and the light loop's shadow probe keep ray_setup alone.
+template <class Scene, class = void>
+struct RayBounds
+{
+	static constexpr bool available = false;
+	template <class R> static SDF_HD void apply(const FrameU &, R &, vec3, vec3, float) {}
+};
+template <class Scene>
+struct RayBounds<Scene, typename VoidOfN<decltype(&Scene::ray_bounds)>::type>
+{
+	static constexpr bool available = true;
+	template <class R> static SDF_HD void apply(const FrameU &U, R &r, vec3 start, vec3 dir, float range) { Scene::ray_bounds(U, r, start, dir, range); }
+};
 // The reference shades every hit, also a shadow ray's: the material callback runs, and unless the surface is see-through
 // (alpha below 1: the ray goes on, tinted) the hit adds 0, pushes nothing and leaves the tone-map flag alone.  A scene whose
 // material() is a pure function that never lowers the alpha may declare `shadow_hits_need_material = false`: the pixel kernel then

@@ -163,7 +163,7 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		}
 		cnt.rays++;
 
-		const typename Scene::RayInv R = Scene::ray_setup(U, ray.dir, ray_flags(ray));
+		typename Scene::RayInv R = Scene::ray_setup(U, ray.dir, ray_flags(ray));
 		const float inside_sign = ray_inside_sign(ray);
 		const float max_range = ray_is_shadow(ray) ? ray.shadow_range : U.range;
 
@@ -172,6 +172,8 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		int status;
 		const uint32_t evals_before = cnt.march_evals;
 		const bool shortcuts = !DBG && (RayEscapes<Scene>::available || EscapesFrom<Scene>::available) && U.step_shortcuts != 0 && inside_sign > 0.f;
+		if constexpr (RayBounds<Scene>::available)
+			if (shortcuts) RayBounds<Scene>::apply(U, R, ray.pos, ray.dir, max_range); // what the start and the range fix for the whole ray
 		float clear_from = 3e38f;
 		if constexpr (EscapesFrom<Scene>::available)
 			if (shortcuts) clear_from = EscapesFrom<Scene>::get(U, ray.pos, ray.dir, max_range); // (a ray inside a refracting body ends on its surface)

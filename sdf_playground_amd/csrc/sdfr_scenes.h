@@ -219,6 +219,17 @@ struct SceneLabyrinth
 	// floor behind it as well: the sky-bound primary rays of the upper part of the picture (they start above the walls:
 	// no step at all) and every shadow ray once it has cleared the walls.
 	static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &R, vec3 p, vec3) { return R.rising && p.y > 4.01f; }
+	// Once per ray (RayBounds, sdfr_pixel.h): a descending ray that is still above 4.01 where its range ends counts as rising.  march_pos
+	// forms p.y as this one fma of dir.y, t and start.y (mad, sdfr_math.h: one fma per component, host and device).  For dir.y < 0 and
+	// t <= range the exact dir.y * t + start.y is no smaller than at `range`, and rounding is monotone: every sample within the range,
+	// the first (t = 0) included, has p.y > 4.01, so ray_escapes ends the ray before its first evaluation.  Nothing is lost: above 4.01
+	// the scene is at least 0.01 away, more than any dist_eps the library accepts, so no sample within the range is a hit, and beyond
+	// the range none is (march_advance).  A NaN fails the comparison; dir.y = -0 is rising already.  Holds for any kind of ray and any
+	// range: a shadow ray towards a point light passes its own, the ones towards the sun rise anyway.
+	static SDF_HD void ray_bounds(const FrameU &, RayInv &R, vec3 start, vec3 dir, float range)
+	{
+		R.rising = R.rising || (dir.y < 0.f && fma1(dir.y, range, start.y) > 4.01f);
+	}
 
 	static SDF_HD float vase(vec3 p)
 	{
