@@ -25,7 +25,7 @@
 //     grad4, mod289 and permute of noise.hlsl are there.
 // SceneAdapter<UserScene> then presents the class to the pixel kernel as any other scene (dist / material / normal / lights /
 // background).  A geometry step sees the GeometryInput the reference hands it: the sample's running camera_distance and the
-// pixel's ray offsets (SceneReadsMarchState, sdfr_pixel.h).
+// pixel's ray offsets (geometry_reads_march_state, sdfr_scene_traits.h).
 #pragma once
 #include "sdfr_pixel.h"
 #include "sdfr_hlsl_swizzles.h"

@@ -35,7 +35,7 @@ struct WavefrontWorkspace
 struct SceneKernels
 {
 	const void *pixel[2], *march[2], *shade[2];
-	bool persistent_tiles, square_units; // PersistentTiles, SquareUnits (sdfr_render_pixel.h)
+	bool persistent_tiles, square_units; // PersistentTiles, SquareUnits (sdfr_scene_traits.h)
 	int retire_after, tile_w_log2;       // RetireAfter, SceneTileShape
 };
 // How the host names a kernel: a kernel of this library by its host pointer (`kernel`), or a function of a module loaded at run

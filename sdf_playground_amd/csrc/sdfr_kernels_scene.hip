@@ -20,11 +20,11 @@ namespace sdfr {
 // =================================================================================================
 // PIXEL schedule (body: sdfr_pixel_kernel.h)
 // =================================================================================================
-// the shading's noise reads its gradients from LDS where the scene asks for it (PixelNoiseGrads); the debug variants keep the formula
+// the shading's noise reads its gradients from LDS where the scene asks for it (PixelNoiseGrads, sdfr_scene_traits.h); the debug variants keep the formula
 template <class Scene, bool DBG>
 __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_pixel(PixelKernelArgs args)
 {
-	pixel_kernel<Scene, DBG, typename PickNoiseGrads<!DBG && PixelNoiseGrads<Scene>::table>::type>(args);
+	pixel_kernel<Scene, DBG, typename PickNoiseGrads<!DBG && PixelNoiseGrads<Scene>::value>::type>(args);
 }
 
 // =================================================================================================
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(SDFR_BLOCK) void k_march(FrameU U, RowMap rm, Wavef
 					baseline = m.d * inside_sign;
 					state = LANE_GRAD0;
 					sample_dist = U.grad_eps;
-					if (SceneNormal<Scene>::available)
+					if (SceneNormal<Scene>::value)
 					{
 						// map_normal (pshader_sdf.hlsl:318-330): the scene's own normal ends the ray here, a changed spacing feeds the samples
 						int px, py;

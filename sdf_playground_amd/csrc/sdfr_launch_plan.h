@@ -98,7 +98,7 @@ inline uint32_t launch_capacity_items(int width, const RowMap &rm)
 	return padded > items ? padded : items;
 }
 
-// What the plan has to know of the scene.  Built-in scenes: PersistentTiles, RetireAfter, SquareUnits (sdfr_render_pixel.h) and
+// What the plan has to know of the scene.  Built-in scenes: PersistentTiles, RetireAfter, SquareUnits (sdfr_scene_traits.h) and
 // 2 * index + DBG; a scene compiled at run time: one wave per tile unless asked otherwise, 8, never, and
 // 0x80000000 | fnv1a(name) | DBG.
 struct PixelSceneTraits

@@ -84,21 +84,9 @@ SDF_HD void lighting_record(const FrameU &U, const SurfacePoint &sp, const Mater
 	{
 		ambient = SceneAmbient<Scene>::get(); // map_light may override the default 0.075
 		// a scene in the reference's own shape fills the whole light table in one call (SceneLights); every other scene answers slot by slot
-		Light table[SceneLights<Scene>::available ? SDFR_MAX_LIGHTS : 1];
-		bool table_used[SceneLights<Scene>::available ? SDFR_MAX_LIGHTS : 1];
-		if (SceneLights<Scene>::available)
-		{
-			for (int i = 0; i < SDFR_MAX_LIGHTS; ++i)
-			{
-				table_used[i] = false;
-				table[i].pos = V3s(0.f);
-				table[i].directional = false;
-				table[i].extend = 0.f;
-				table[i].color = V3s(0.f);
-				table[i].falloff = 0.f;
-			}
-			SceneLights<Scene>::call(U, sp, table, table_used, ambient);
-		}
+			Light table[SceneLights<Scene>::value ? SDFR_MAX_LIGHTS : 1];
+		bool table_used[SceneLights<Scene>::value ? SDFR_MAX_LIGHTS : 1];
+		if constexpr (SceneLights<Scene>::value) scene_light_table<Scene>(U, sp, table, table_used, ambient);
 		const float sample_dist = scene_normal<Scene>(U, sp.pos, sp.dir, sp.camera_distance, sp.right_off, sp.bottom_off).sample_dist;
 		const float move = max1(U.shadow_eps, sample_dist) + max1(0.f, -sp.scene_distance);
 		const vec3 lit_pos = mad(n, move, sp.pos);

@@ -10,6 +10,7 @@
 #pragma once
 #include "sdfr_frame.h"
 #include "sdfr_lib.h"
+#include "sdfr_scene_traits.h"
 
 namespace sdfr {
 
@@ -104,14 +105,16 @@ SDF_HD DebugFlags debug_flags(const FrameU &U)
 SDF_HD bool frame_needs_debug(const FrameU &U) { return U.debug_plane_on != 0 || U.show_on == 0; }
 
 // ---- scene distance with the driver's debug plane (pshader_sdf.hlsl:111-135) ---------------
-template <class Scene, bool DBG>
-SDF_HD float map_geometry(const FrameU &U, const DebugFlags &F, const typename Scene::RayInv &R, vec3 p, vec3 dir, bool fast)
+// Step: nothing, or the GeoStep of a scene that reads the march state (scene_distance, below, makes it).  Called without one by the
+// wavefront march (k_march), where no scene that reads the march state runs.
+template <class Scene, bool DBG, class... Step>
+SDF_HD float map_geometry(const FrameU &U, const DebugFlags &F, const typename Scene::RayInv &R, vec3 p, vec3 dir, bool fast, const Step &...gs)
 {
 	if (!DBG)
-		return Scene::dist(U, R, p, dir, fast);
+		return Scene::dist(U, R, p, dir, fast, gs...);
 	float d = 3e38f;
 	if (F.show_on)
-		d = Scene::dist(U, R, p, dir, fast);
+		d = Scene::dist(U, R, p, dir, fast, gs...);
 	if (F.plane_on)
 	{
 		float plane = sd_plane_fast(p - V3(U.debug_x, U.debug_y, U.debug_z), dir, fast, U.debug_normal);
@@ -120,40 +123,23 @@ SDF_HD float map_geometry(const FrameU &U, const DebugFlags &F, const typename S
 	return d;
 }
 
-// ---- the march state a scene's geometry step may look at (pshader_sdf.hlsl:187-218, 297-302) -----------------------
-// In the reference a geometry step sees the whole GeometryInput: the running camera_distance of the sample and the pixel's
-// ray offsets besides position and direction.  No scene of the reference reads them there, and the scenes compiled ahead of
-// time take (p, dir) only.  A scene that declares `static constexpr bool geometry_reads_march_state = true` (what scenes in
-// the reference's dialect get, sdfr_hlsl.h) has `dist` called with a sixth argument instead; for every other scene none of
-// this exists in the generated code.
-struct GeoStep
-{
-	float camera_distance;       // geometry.camera_distance at this sample (the hit's, for the normal's samples)
-	vec3 right_off, bottom_off;  // geometry.right_ray_offset / bottom_ray_offset: the pixel's, for every ray of the pixel
-};
-template <bool B>
-struct VoidIf {};
-template <>
-struct VoidIf<true> { typedef void type; };
-template <class Scene, class = void>
-struct SceneReadsMarchState { static constexpr bool value = false; };
-template <class Scene>
-struct SceneReadsMarchState<Scene, typename VoidIf<Scene::geometry_reads_march_state>::type> { static constexpr bool value = true; };
-
+// The one call for a scene's distance at a sample: its camera_distance and the pixel's ray offsets go along, and a scene that reads the
+// march state (geometry_reads_march_state, sdfr_scene_traits.h) gets them as a GeoStep -- formed here and nowhere else; every other
+// scene gets (p, dir), and the three arguments leave no trace in its code.
 template <class Scene, bool DBG>
-SDF_HD float map_geometry_at(const FrameU &U, const DebugFlags &F, const typename Scene::RayInv &R, vec3 p, vec3 dir, bool fast, const GeoStep &gs)
+SDF_HD float scene_distance(const FrameU &U, const DebugFlags &F, const typename Scene::RayInv &R, vec3 p, vec3 dir, bool fast, float camera_distance,
+	vec3 right_off, vec3 bottom_off)
 {
-	if (!DBG)
-		return Scene::dist(U, R, p, dir, fast, gs);
-	float d = 3e38f;
-	if (F.show_on)
-		d = Scene::dist(U, R, p, dir, fast, gs);
-	if (F.plane_on)
+	if constexpr (SceneReadsMarchState<Scene>::value)
 	{
-		float plane = sd_plane_fast(p - V3(U.debug_x, U.debug_y, U.debug_z), dir, fast, U.debug_normal);
-		return min1(d, plane);
+		GeoStep gs;
+		gs.camera_distance = camera_distance;
+		gs.right_off = right_off;
+		gs.bottom_off = bottom_off;
+		return map_geometry<Scene, DBG>(U, F, R, p, dir, fast, gs);
 	}
-	return d;
+	else
+		return map_geometry<Scene, DBG>(U, F, R, p, dir, fast);
 }
 
 // ---- sphere tracing with over-relaxation (pshader_sdf.hlsl:179-220) as a resumable state ----
@@ -231,27 +217,6 @@ SDF_HD vec3 grad_sample_pos(vec3 p, int axis, float eps)
 	return p + V3(0.f, 0.f, eps);
 }
 
-// ---- the scene's map_normal (pshader_sdf.hlsl:318-330; sdf_structs.hlsl:39-52) -----------------------
-// A scene may declare `static SDF_HD void normal(const FrameU &U, const SurfacePoint &sp, NormalOut &no)`: called once per
-// hit with the NormalOutput preloaded {grad_eps, 0, false}; sp.normal is 0 (the geometric normal is what is being made).
-// It may hand back the normal itself (no.use_normal = true: the three forward-difference evaluations are not made) and /
-// or change no.sample_dist, the spacing of those samples -- which the driver uses a second time, for the offset of the
-// shadow rays (pshader_sdf.hlsl:520).  Every scene of the reference leaves map_normal empty: a scene without the
-// member costs nothing.
-template <class...>
-struct VoidOfN { typedef void type; };
-template <class Scene, class = void>
-struct SceneNormal
-{
-	static constexpr bool available = false;
-	static SDF_HD void call(const FrameU &, const SurfacePoint &, NormalOut &) {}
-};
-template <class Scene>
-struct SceneNormal<Scene, typename VoidOfN<decltype(&Scene::normal)>::type>
-{
-	static constexpr bool available = true;
-	static SDF_HD void call(const FrameU &U, const SurfacePoint &sp, NormalOut &no) { Scene::normal(U, sp, no); }
-};
 // normal_output as the driver preloads it, then the scene's say
 template <class Scene>
 SDF_HD NormalOut scene_normal(const FrameU &U, vec3 hit_pos, vec3 dir, float camera_distance, vec3 right_ray, vec3 bottom_ray)
@@ -260,7 +225,7 @@ SDF_HD NormalOut scene_normal(const FrameU &U, vec3 hit_pos, vec3 dir, float cam
 	no.sample_dist = U.grad_eps;
 	no.normal = V3s(0.f);
 	no.use_normal = false;
-	if (SceneNormal<Scene>::available)
+	if (SceneNormal<Scene>::value)
 	{
 		SurfacePoint sp;
 		sp.pos = hit_pos;
@@ -275,33 +240,6 @@ SDF_HD NormalOut scene_normal(const FrameU &U, vec3 hit_pos, vec3 dir, float cam
 	}
 	return no;
 }
-
-// ---- the scene's map_light as ONE call per hit (pshader_sdf.hlsl:505-516) -----------------------------
-// The scenes compiled ahead of time answer `light(U, i, L)` slot by slot and `ambient()` without arguments: their lights do
-// not depend on the hit point, and unused slots cost nothing.  A scene may instead declare
-//   static SDF_HD void lights(const FrameU &U, const SurfacePoint &sp, Light L[SDFR_MAX_LIGHTS], bool used[SDFR_MAX_LIGHTS], float &ambient)
-// -- the reference's own shape: map_light(geometry, inout LightOutput[8], inout ambient), called once per lit hit with
-// `used` all false and `ambient` 0.075 (what scenes in the reference's dialect get, sdfr_hlsl.h).
-template <class Scene, class = void>
-struct SceneLights
-{
-	static constexpr bool available = false;
-	static SDF_HD void call(const FrameU &, const SurfacePoint &, Light *, bool *, float &) {}
-};
-template <class Scene>
-struct SceneLights<Scene, typename VoidOfN<decltype(&Scene::lights)>::type>
-{
-	static constexpr bool available = true;
-	static SDF_HD void call(const FrameU &U, const SurfacePoint &sp, Light *L, bool *used, float &ambient) { Scene::lights(U, sp, L, used, ambient); }
-};
-template <class Scene, bool HasLights = SceneLights<Scene>::available>
-struct SceneAmbient { static SDF_HD float get() { return Scene::ambient(); } };
-template <class Scene>
-struct SceneAmbient<Scene, true> { static SDF_HD float get() { return 0.075f; } };
-template <class Scene, bool HasLights = SceneLights<Scene>::available>
-struct SceneLightSlot { static SDF_HD bool get(const FrameU &U, int i, Light &L) { return Scene::light(U, i, L); } };
-template <class Scene>
-struct SceneLightSlot<Scene, true> { static SDF_HD bool get(const FrameU &, int, Light &) { return false; } };
 
 // ---- results handed from marching to shading ---------------------------------------------------
 struct HitInfo
@@ -377,17 +315,7 @@ SDF_HD void map_material(const FrameU &U, const DebugFlags &F, const SurfacePoin
 		nf.is_shadow = false;
 		nf.last_transparent_pos = V3s(0.f);
 		typename Scene::RayInv R0 = Scene::ray_setup(U, sp.dir, nf);
-		float d;
-		if constexpr (SceneReadsMarchState<Scene>::value)
-		{
-			GeoStep gs;
-			gs.camera_distance = sp.camera_distance;
-			gs.right_off = sp.right_off;
-			gs.bottom_off = sp.bottom_off;
-			d = Scene::dist(U, R0, sp.pos, sp.dir, false, gs);
-		}
-		else
-			d = Scene::dist(U, R0, sp.pos, sp.dir, false);
+		const float d = scene_distance<Scene, false>(U, F, R0, sp.pos, sp.dir, false, sp.camera_distance, sp.right_off, sp.bottom_off); // the scene's alone
 		m.id = MAT_DISTANCE_PLANE;
 		m.prop_x = d / U.debug_scale;
 	}
@@ -397,118 +325,13 @@ SDF_HD void map_material(const FrameU &U, const DebugFlags &F, const SurfacePoin
 	}
 }
 
-// A scene may declare `static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &R, vec3 p, vec3 dir)`: true only if
-// NOTHING of the scene lies on the ray from p onwards -- then the ray is a miss already (an escaped shadow ray delivers
-// its light, any other ray sees the background, whose colour does not depend on the step count in such a scene), and the
-// pixel kernel stops marching it (FrameU::step_shortcuts; never in the debug-plane build, whose plane is an extra object).
-template <class Scene, class = void>
-struct RayEscapes
-{
-	static constexpr bool available = false;
-	template <class R> static SDF_HD bool test(const FrameU &, const R &, vec3, vec3) { return false; }
-};
-template <class Scene>
-struct RayEscapes<Scene, typename VoidOfN<decltype(&Scene::ray_escapes)>::type>
-{
-	static constexpr bool available = true;
-	template <class R> static SDF_HD bool test(const FrameU &U, const R &r, vec3 p, vec3 dir) { return Scene::ray_escapes(U, r, p, dir); }
-};
-
-// ... and / or `static SDF_HD float escapes_from(const FrameU &U, vec3 start, vec3 dir, float range)`, worked out once per ray: the
-// distance along the ray from which on nothing of the scene lies between the march and `range`, where it declares the ray out of
-// range (a shadow ray towards a point light ends there; samples beyond are misses whatever they measure) -- 3e38 if there is no such
-// distance.  A sample beyond it is a miss as well; one comparison per step.
-template <class Scene, class = void>
-struct EscapesFrom
-{
-	static constexpr bool available = false;
-	static SDF_HD float get(const FrameU &, vec3, vec3, float) { return 3e38f; }
-};
-template <class Scene>
-struct EscapesFrom<Scene, typename VoidOfN<decltype(&Scene::escapes_from)>::type>
-{
-	static constexpr bool available = true;
-	static SDF_HD float get(const FrameU &U, vec3 start, vec3 dir, float range) { return Scene::escapes_from(U, start, dir, range); }
-};
-// ... and / or `static SDF_HD void ray_bounds(const FrameU &U, RayInv &R, vec3 start, vec3 dir, float range)`, called once per ray
-// right after ray_setup, with the ray's start and the range it is marched to: the scene may strengthen R with facts that hold for
-// every sample with t <= range, and its ray_escapes may then call such a ray gone although the scene goes on beyond `range`.  The
-// licence is escapes_from's: a hit needs m.t <= dist_max (march_advance), and a miss of such a scene is the same result whatever
-// ended it -- the range, the iteration limit or the rule.  Nothing per step.  Only render_pixel calls it, and only with step
-// shortcuts on: the wavefront march applies no shortcuts, the ray queries and the light loop's shadow probe keep ray_setup alone.
-template <class Scene, class = void>
-struct RayBounds
-{
-	static constexpr bool available = false;
-	template <class R> static SDF_HD void apply(const FrameU &, R &, vec3, vec3, float) {}
-};
-template <class Scene>
-struct RayBounds<Scene, typename VoidOfN<decltype(&Scene::ray_bounds)>::type>
-{
-	static constexpr bool available = true;
-	template <class R> static SDF_HD void apply(const FrameU &U, R &r, vec3 start, vec3 dir, float range) { Scene::ray_bounds(U, r, start, dir, range); }
-};
-// The reference shades every hit, also a shadow ray's: the material callback runs, and unless the surface is see-through
-// (alpha below 1: the ray goes on, tinted) the hit adds 0, pushes nothing and leaves the tone-map flag alone.  A scene whose
-// material() is a pure function that never lowers the alpha may declare `shadow_hits_need_material = false`: the pixel kernel then
-// counts such a hit and adds the 0 without calling shade_hit (never in the debug-plane build, which keeps the reference's path).
-template <class Scene, class = void>
-struct ShadowHitsNeedMaterial { static constexpr bool value = true; };
-template <class Scene>
-struct ShadowHitsNeedMaterial<Scene, typename VoidOfN<decltype(Scene::shadow_hits_need_material)>::type>
-{
-	static constexpr bool value = Scene::shadow_hits_need_material;
-};
-
-// The relaxation starts at a ray's fourth sample, so in its first three the march's rewind logic has nothing to decide.  A scene that
-// declares `peel_unrelaxed_samples = true` gets those three samples as straight-line code in front of the march loop of its pixel kernel
-// (render_pixel: march_advance_unrelaxed, then the factor once, then the loop without march_pre) -- the same samples, states and counters;
-// more code, fewer instructions per pass.  Per scene, because it is another register draw for the whole kernel: a scene opts in with a
-// measurement of its own.  Never in the debug-plane build.
-template <class Scene, class = void>
-struct PeelUnrelaxedSamples { static constexpr bool value = false; };
-template <class Scene>
-struct PeelUnrelaxedSamples<Scene, typename VoidOfN<decltype(Scene::peel_unrelaxed_samples)>::type>
-{
-	static constexpr bool value = Scene::peel_unrelaxed_samples;
-};
-
-// A scene whose light() puts a directional light into slot 0 in every frame may declare `static SDF_HD vec3 frame_sun_dir(const FrameU &U)`:
-// that light's L.pos / (length(L.pos) + U.dist_eps), made once by its prepare() -- the operands are a constant and a frame uniform, and the
-// light loop would form the same three quotients and the root at every hit.  Slot 0 is the scene's own in every frame: extension lights
-// overwrite slots 1 and above (light_in_slot).
-template <class Scene, class = void>
-struct FrameSunDir
-{
-	static constexpr bool available = false;
-	static SDF_HD vec3 get(const FrameU &) { return V3s(0.f); }
-};
-template <class Scene>
-struct FrameSunDir<Scene, typename VoidOfN<decltype(&Scene::frame_sun_dir)>::type>
-{
-	static constexpr bool available = true;
-	static SDF_HD vec3 get(const FrameU &U) { return Scene::frame_sun_dir(U); }
-};
 // the direction in which directional light i shines
 template <class Scene>
 SDF_HD vec3 directional_light_dir(const FrameU &U, int i, const Light &L)
 {
-	if (FrameSunDir<Scene>::available && i == 0) return FrameSunDir<Scene>::get(U);
+	if (FrameSunDir<Scene>::value && i == 0) return FrameSunDir<Scene>::get(U);
 	return L.pos / (length(L.pos) + U.dist_eps);
 }
-// A scene with ray_escapes may also declare `static constexpr bool inline_escaped_shadows = true`: a shadow ray that escapes where it
-// starts (no evaluation at all: two thirds of the rays of gems with eight lights, whose floor pixels send eight of them past the
-// ring) is then not queued -- a 48-byte record out and back, a turn of the bounce loop -- but delivers its light from the light
-// loop that made it, when that keeps the order of the pixel's sums: the queue is empty (it would be the next ray taken: smallest
-// depth, lowest slot), the hit's own colour has been added (shade_hit adds it before the lights' rays: InlineShadows::acc), and
-// the ray budget reaches it.  From the first ray that has to be queued on, the rest are queued as well.
-template <class Scene, class = void>
-struct InlineEscapedShadows { static constexpr bool value = false; };
-template <class Scene>
-struct InlineEscapedShadows<Scene, typename VoidOfN<decltype(Scene::inline_escaped_shadows)>::type>
-{
-	static constexpr bool value = Scene::inline_escaped_shadows && RayEscapes<Scene>::available;
-};
 struct InlineShadows
 {
 	vec3 acc;   // the pixel's sum; shade_hit adds the hit's colour and the delivered light to it, in the order the bounce loop would
@@ -516,12 +339,29 @@ struct InlineShadows
 	int taken;  // shadow rays delivered here: each counts as a ray and a turn
 };
 
+// map_light for a scene in the reference's own shape (lights(), sdfr_scene_traits.h): the table as the driver hands it over -- no slot used, every
+// light zero --, then the scene's one call, which may also change `ambient`.  Called under `if constexpr (SceneLights<Scene>::value)`:
+// handing the one-entry tables of a scene that answers slot by slot to a function, even an empty one, changed every scene's query kernels.
+template <class Scene>
+SDF_HD void scene_light_table(const FrameU &U, const SurfacePoint &sp, Light *table, bool *table_used, float &ambient)
+{
+	for (int i = 0; i < SDFR_MAX_LIGHTS; ++i)
+	{
+		table_used[i] = false;
+		table[i].pos = V3s(0.f);
+		table[i].directional = false;
+		table[i].extend = 0.f;
+		table[i].color = V3s(0.f);
+		table[i].falloff = 0.f;
+	}
+	Scene::lights(U, sp, table, table_used, ambient);
+}
 // light i of the frame: the scene's (its own slot function or the table a scene in the reference's shape filled), or an extension light
 template <class Scene, class Table, class Used>
 SDF_HD bool light_in_slot(const FrameU &U, int i, const Table &table, const Used &table_used, Light &L)
 {
 	bool used = SceneLightSlot<Scene>::get(U, i, L);
-	if (SceneLights<Scene>::available)
+	if (SceneLights<Scene>::value)
 	{
 		L = table[i];
 		used = table_used[i];
@@ -686,21 +526,9 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 		{
 			float ambient = SceneAmbient<Scene>::get(); // map_light may override the default 0.075
 			// a scene in the reference's own shape fills the whole light table in one call (SceneLights)
-			Light table[SceneLights<Scene>::available ? SDFR_MAX_LIGHTS : 1];
-			bool table_used[SceneLights<Scene>::available ? SDFR_MAX_LIGHTS : 1];
-			if (SceneLights<Scene>::available)
-			{
-				for (int i = 0; i < SDFR_MAX_LIGHTS; ++i)
-				{
-					table_used[i] = false;
-					table[i].pos = V3s(0.f);
-					table[i].directional = false;
-					table[i].extend = 0.f;
-					table[i].color = V3s(0.f);
-					table[i].falloff = 0.f;
-				}
-				SceneLights<Scene>::call(U, sp, table, table_used, ambient);
-			}
+			Light table[SceneLights<Scene>::value ? SDFR_MAX_LIGHTS : 1];
+			bool table_used[SceneLights<Scene>::value ? SDFR_MAX_LIGHTS : 1];
+			if constexpr (SceneLights<Scene>::value) scene_light_table<Scene>(U, sp, table, table_used, ambient);
 			float move = max1(U.shadow_eps, hit.sample_dist) + max1(0.f, -hit.d);
 			vec3 lit_pos = mad(n, move, hit.pos);
 			const float alpha = sat1(m.diffuse.w);
@@ -772,12 +600,13 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 					}
 				}
 			}
-			else // the reference's one loop: every light's ambient share and its shadow ray (body not re-indented: the headline kernel's code)
+			else // the reference's one loop: every light's ambient share and its shadow ray (body not re-indented: the headline kernel's code;
+			// light_in_slot and light_colour in its place were tried and changed every scene's code)
 			for (int i = 0; i < U.light_count; ++i)
 			{
 				Light L;
 				bool used = SceneLightSlot<Scene>::get(U, i, L);
-				if (SceneLights<Scene>::available)
+				if (SceneLights<Scene>::value)
 				{
 					L = table[i];
 					used = table_used[i];
@@ -860,17 +689,6 @@ SDF_HD vec3 shade_hit(const FrameU &U, const DebugFlags &F, const RayRec &ray, c
 
 // A ray that left the scene (pshader_sdf.hlsl:621-632): an escaped shadow ray delivers the
 // light it carries, any other ray sees the background.
-// The background through the gradient source NG where the scene's takes one (the shared sky: background<NG>), else as it is.
-template <class Scene, class NG, class = void>
-struct SceneBackground
-{
-	static SDF_HD vec3 get(const FrameU &U, vec3 dir, uint32_t iter) { return Scene::background(U, dir, iter); }
-};
-template <class Scene, class NG>
-struct SceneBackground<Scene, NG, typename VoidOfN<decltype(Scene::template background<NG>(*(const FrameU *)0, V3s(0.f), 0u))>::type>
-{
-	static SDF_HD vec3 get(const FrameU &U, vec3 dir, uint32_t iter) { return Scene::template background<NG>(U, dir, iter); }
-};
 template <class Scene, class NG = NoiseGradFormula>
 SDF_HD vec3 shade_miss(const FrameU &U, const RayRec &ray, uint32_t iter)
 {

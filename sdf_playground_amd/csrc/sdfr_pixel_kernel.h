@@ -36,16 +36,8 @@ static_assert(SDFR_BLOCK <= 64 * SDFR_MAX_WAVES_PER_BLOCK && SDFR_PIXEL_BLOCK <=
 // 4: 1.61 / 2.2 / 7.9, 5: 1.55 / 2.16 / 7.8, 6: 1.50 / 2.25 / 8.0, 7: 1.43 / 2.03 / 7.2, 8: 1.5 / 2.1 / 7.2.
 // With the persistent launch (round 2) the headline scene no longer cares (labyrinth at 4K, ms: 3 waves 1.39, 4: 1.42,
 // 5: 1.40, 6: 1.40, 7: 1.40, 8: 1.41); scenes with very long evaluations prefer fewer waves with more registers and
-// say so with `waves_per_simd` (tree: 5), scenes whose march loop fits 64 registers can ask for 8.
-#ifndef SDFR_PIXEL_WAVES_PER_EU
-#define SDFR_PIXEL_WAVES_PER_EU 7
-#endif
-template <class Scene, class = void>
-struct PixelWavesPerSimd { static constexpr int value = SDFR_PIXEL_WAVES_PER_EU; };
-#ifndef SDFR_PIXEL_WAVES_FIXED // developer builds that sweep SDFR_PIXEL_WAVES_PER_EU override the scenes' own choice
-template <class Scene>
-struct PixelWavesPerSimd<Scene, typename VoidOf<decltype(Scene::waves_per_simd)>::type> { static constexpr int value = Scene::waves_per_simd; };
-#endif
+// say so with `waves_per_simd` (tree: 5), scenes whose march loop fits 64 registers can ask for 8 (PixelWavesPerSimd and the
+// default SDFR_PIXEL_WAVES_PER_EU: sdfr_scene_traits.h).
 #define SDFR_PIXEL_KERNEL_ATTRS(Scene) __launch_bounds__(SDFR_PIXEL_BLOCK) __attribute__((amdgpu_waves_per_eu(PixelWavesPerSimd<Scene>::value)))
 
 // This lane's index in its wave, made where it is needed (three instructions).  A block of the pixel kernel is one wave, so
@@ -74,7 +66,7 @@ __device__ __forceinline__ uint32_t handed_out_row(uint32_t ty, const uint32_t *
 // lane `lane` of the wave that renders tile `tile` (wave-uniform: the split into row and column is scalar work)
 // the unit (square of tiles, RowMap::unit_log2) the `slot`-th unit to be handed out is
 __device__ __forceinline__ uint32_t handed_out_unit(uint32_t slot, const uint32_t *order) { return order ? order[slot] : slot; }
-// UNITS: the kernel of a scene that may be handed out in squares (SquareUnits, sdfr_render_pixel.h); the others do not carry the code
+// UNITS: the kernel of a scene that may be handed out in squares (SquareUnits, sdfr_scene_traits.h); the others do not carry the code
 template <bool UNITS = false>
 __device__ __forceinline__ bool tile_to_pixel(const FrameU &U, const RowMap &rm, uint32_t tile, uint32_t lane, PixelCoord &pc, const uint32_t *order = nullptr)
 {
@@ -442,13 +434,10 @@ struct NoiseGradLdsTab
 };
 typedef NoiseGradTable<NoiseGradLdsTab> NoiseGradLds;
 static_assert(SDFR_NOISE_GRADS == SDFR_PIXEL_BLOCK, "one lane fills one gradient");
-// The gradient source of a scene's pixel kernel: the table where the scene declares `noise_grad_table = true`, the formula
+// The gradient source of a scene's pixel kernel: the table where the scene declares `noise_grad_table = true` (PixelNoiseGrads,
+// sdfr_scene_traits.h), the formula
 // elsewhere.  The table pays where the shading's turbulence3 runs in most waves; elsewhere it only draws LDS and a different
 // register assignment (the march loops of the other configuration scenes came out with more spills or more one-bank fma).
-template <class Scene, class = void>
-struct PixelNoiseGrads { static constexpr bool table = false; };
-template <class Scene>
-struct PixelNoiseGrads<Scene, typename VoidOf<decltype(Scene::noise_grad_table)>::type> { static constexpr bool table = Scene::noise_grad_table; };
 template <bool TABLE>
 struct PickNoiseGrads { typedef NoiseGradFormula type; };
 template <>

@@ -39,24 +39,6 @@ struct MeshSharpKernelArgs
 	MeshSharpArgs m;
 };
 
-// map_geometry at the sample of a query: a scene that reads the march state (GeoStep) gets the running camera_distance and
-// the ray's offsets, every other scene (p, dir) as in the pixel pipeline
-template <class Scene, bool DBG>
-SDF_HD float query_geometry(const FrameU &U, const DebugFlags &F, const typename Scene::RayInv &R, vec3 p, vec3 dir, bool fast, float camera_distance,
-	vec3 right_off, vec3 bottom_off)
-{
-	if constexpr (SceneReadsMarchState<Scene>::value)
-	{
-		GeoStep gs;
-		gs.camera_distance = camera_distance;
-		gs.right_off = right_off;
-		gs.bottom_off = bottom_off;
-		return map_geometry_at<Scene, DBG>(U, F, R, p, dir, fast, gs);
-	}
-	else
-		return map_geometry<Scene, DBG>(U, F, R, p, dir, fast);
-}
-
 // the driver's normal at pos (pshader_sdf.hlsl:164-177, 320-330): map_normal with the NormalOutput preloaded {grad_eps, 0, false};
 // its normal if it sets use_normal, else the three forward differences against `baseline`, normalised
 template <class Scene, bool DBG>
@@ -65,9 +47,9 @@ SDF_HD vec3 query_normal(const FrameU &U, const DebugFlags &F, const typename Sc
 {
 	const NormalOut no = scene_normal<Scene>(U, pos, dir, camera_distance, right_off, bottom_off);
 	if (no.use_normal) return no.normal;
-	const float g0 = query_geometry<Scene, DBG>(U, F, R, grad_sample_pos(pos, 0, no.sample_dist), dir, false, camera_distance, right_off, bottom_off) - baseline;
-	const float g1 = query_geometry<Scene, DBG>(U, F, R, grad_sample_pos(pos, 1, no.sample_dist), dir, false, camera_distance, right_off, bottom_off) - baseline;
-	const float g2 = query_geometry<Scene, DBG>(U, F, R, grad_sample_pos(pos, 2, no.sample_dist), dir, false, camera_distance, right_off, bottom_off) - baseline;
+	const float g0 = scene_distance<Scene, DBG>(U, F, R, grad_sample_pos(pos, 0, no.sample_dist), dir, false, camera_distance, right_off, bottom_off) - baseline;
+	const float g1 = scene_distance<Scene, DBG>(U, F, R, grad_sample_pos(pos, 1, no.sample_dist), dir, false, camera_distance, right_off, bottom_off) - baseline;
+	const float g2 = scene_distance<Scene, DBG>(U, F, R, grad_sample_pos(pos, 2, no.sample_dist), dir, false, camera_distance, right_off, bottom_off) - baseline;
 	return normalize(V3(g0, g1, g2));
 }
 
@@ -89,7 +71,7 @@ SDF_HD float query_point(const FrameU &U, vec3 p, vec3 *normal)
 	const DebugFlags F = debug_flags(U);
 	const vec3 zero = V3s(0.f);
 	const typename Scene::RayInv R = Scene::ray_setup(U, zero, query_ray_flags());
-	const float d = query_geometry<Scene, DBG>(U, F, R, p, zero, false, 0.f, zero, zero);
+	const float d = scene_distance<Scene, DBG>(U, F, R, p, zero, false, 0.f, zero, zero);
 	if (normal) *normal = query_normal<Scene, DBG>(U, F, R, p, zero, 0.f, zero, zero, d);
 	return d;
 }
@@ -122,22 +104,22 @@ SDF_HD bool query_ray_at(const FrameU &U, vec3 origin, vec3 dir, float dist_max,
 	const typename Scene::RayInv R = Scene::ray_setup(U, dir, flags);
 	March m = march_begin(origin, dir);
 	int status;
-	const bool shortcuts = !DBG && (RayEscapes<Scene>::available || EscapesFrom<Scene>::available) && U.step_shortcuts != 0;
+	const bool shortcuts = !DBG && (RayEscapes<Scene>::value || EscapesFrom<Scene>::value) && U.step_shortcuts != 0;
 	float clear_from = 3e38f;
-	if constexpr (EscapesFrom<Scene>::available)
+	if constexpr (EscapesFrom<Scene>::value)
 		if (shortcuts) clear_from = EscapesFrom<Scene>::get(U, origin, dir, dist_max);
 	do
 	{
 		march_pre(m);
 		// the step shortcut of render_pixel: only a sample the march will not take back may end the ray
 		bool escaped = shortcuts && RayEscapes<Scene>::test(U, R, march_pos(m), dir);
-		if constexpr (EscapesFrom<Scene>::available) escaped = escaped || m.t >= clear_from;
+		if constexpr (EscapesFrom<Scene>::value) escaped = escaped || m.t >= clear_from;
 		if (escaped && m.factor == 1.f)
 		{
 			status = MARCH_MISS;
 			break;
 		}
-		const float d = query_geometry<Scene, DBG>(U, F, R, march_pos(m), dir, true, m.t, right_off, bottom_off);
+		const float d = scene_distance<Scene, DBG>(U, F, R, march_pos(m), dir, true, m.t, right_off, bottom_off);
 		if (escaped && !((m.last_d + d) < m.last_d * m.factor))
 		{
 			status = MARCH_MISS;

@@ -57,59 +57,6 @@ struct CachedRayStore
 	}
 };
 
-// Q1 of SURVEY.md 8: the reference takes the forward-difference normal of every hit, also of
-// shadow-ray hits, whose shading never looks at it -- unless the scene's material callback reads
-// MaterialInput.obj_normal.  A scene that declares `shadow_hits_need_normal = false` lets the
-// pixel kernel skip those three scene evaluations; outputs and counters are unchanged.  Scenes
-// without the declaration (run-time scenes by default) keep the reference's behaviour.
-template <class...>
-struct VoidOf { typedef void type; };
-template <class Scene, class = void>
-struct ShadowHitsNeedNormal { static constexpr bool value = true; };
-template <class Scene>
-struct ShadowHitsNeedNormal<Scene, typename VoidOf<decltype(Scene::shadow_hits_need_normal)>::type>
-{
-	static constexpr bool value = Scene::shadow_hits_need_normal;
-};
-
-// How a scene's pixel kernel is launched by default (sdfr_set_launch_mode(AUTO)): a scene that declares
-// `persistent_tiles = true` gets the persistent launch (resident waves pull tiles, TileQueue), the others one
-// wave per tile.  Measured per scene on MI355X at 3840x2160 (profiles/r02_launch_modes.txt): the persistent
-// launch wins where tiles are expensive and uneven (labyrinth, cube_sea, fractal, lense, light_shadows: 1.5-3 %)
-// and loses where they are cheap (fast_sphere +14 %, cube +33 %: the tile cursors become the bottleneck).
-template <class Scene, class = void>
-struct PersistentTiles { static constexpr bool value = false; };
-template <class Scene>
-struct PersistentTiles<Scene, typename VoidOf<decltype(Scene::persistent_tiles)>::type>
-{
-	static constexpr bool value = Scene::persistent_tiles;
-};
-
-// A scene may say `static constexpr bool square_units = true;`: its persistent full-frame launches hand the tiles out in squares (RowMap::
-// unit_log2) instead of tile rows, dearest square first by the last frame's cost -- for a scene that is an object in the middle of the picture,
-// whose dear tiles sit in the middle of many rows (fractal: BASELINE configuration 4 1.174 -> 1.062 ms; the labyrinth +1.6 %, cube_sea +2.8 %,
-// lense with 8 lights +13 ... +17 %: their cost runs along rows; gems with 8 lights 1.657 -> 1.563 ms; the tree gains 2 % from the squares and
-// loses 7 % by carrying the code: another register draw).
-template <class Scene, class = void>
-struct SquareUnits { static constexpr bool value = false; };
-template <class Scene>
-struct SquareUnits<Scene, typename VoidOf<decltype(Scene::square_units)>::type> { static constexpr bool value = Scene::square_units; };
-
-// The pixels of a wave: 8 x 8 unless the scene says `static constexpr int tile_w_log2 = n;` (a (1 << n) x (64 >> n) tile, n = 3 .. 6).  Measured
-// for every scene and configuration (profiles/r03_launch_experiments.txt): 8 x 8 is the best or within 1.5 % -- except gems with 8 lights and depth 4,
-// whose waves lose fewer lanes on 16 x 4 (BASELINE configuration 5g 1.579 -> 1.517 ms), and lense and neon at 4K (-3 %).
-template <class Scene, class = void>
-struct SceneTileShape { static constexpr int value = 3; };
-template <class Scene>
-struct SceneTileShape<Scene, typename VoidOf<decltype(Scene::tile_w_log2)>::type> { static constexpr int value = Scene::tile_w_log2; };
-
-// tiles a wave of the scene's persistent launch renders before it makes room for a younger one (pixel_launch_blocks,
-// sdfr_launch_plan.h); a scene may say `static constexpr int retire_after = n;` (0 = never)
-template <class Scene, class = void>
-struct RetireAfter { static constexpr int value = 8; };
-template <class Scene>
-struct RetireAfter<Scene, typename VoidOf<decltype(Scene::retire_after)>::type> { static constexpr int value = Scene::retire_after; };
-
 // which sample of a ray a pass of the peeled march takes (render_pixel): one of the first three, whose m.factor is 1, or a later one
 template <bool FirstThree>
 struct MarchSample { static constexpr bool value = FirstThree; };
@@ -171,35 +118,25 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		March m = march_begin(ray.pos, ray.dir);
 		int status;
 		const uint32_t evals_before = cnt.march_evals;
-		const bool shortcuts = !DBG && (RayEscapes<Scene>::available || EscapesFrom<Scene>::available) && U.step_shortcuts != 0 && inside_sign > 0.f;
-		if constexpr (RayBounds<Scene>::available)
+		const bool shortcuts = !DBG && (RayEscapes<Scene>::value || EscapesFrom<Scene>::value) && U.step_shortcuts != 0 && inside_sign > 0.f;
+		if constexpr (RayBounds<Scene>::value)
 			if (shortcuts) RayBounds<Scene>::apply(U, R, ray.pos, ray.dir, max_range); // what the start and the range fix for the whole ray
 		float clear_from = 3e38f;
-		if constexpr (EscapesFrom<Scene>::available)
+		if constexpr (EscapesFrom<Scene>::value)
 			if (shortcuts) clear_from = EscapesFrom<Scene>::get(U, ray.pos, ray.dir, max_range); // (a ray inside a refracting body ends on its surface)
 		if constexpr (!DBG && PeelUnrelaxedSamples<Scene>::value)
 		{
-			// The loop below with the ray's first three samples in front of it as straight-line code (PeelUnrelaxedSamples, sdfr_pixel.h): one
+			// The loop below with the ray's first three samples in front of it as straight-line code (PeelUnrelaxedSamples, sdfr_scene_traits.h): one
 			// pass, `first_three` a MarchSample: with m.factor 1 for certain an escaped sample ends the ray before its evaluation and nothing
 			// is rewound (march_advance_unrelaxed).  Then the factor once, then the passes that may rewind, without march_pre.
 			auto march_step = [&](auto first_three) -> int
 			{
 				constexpr bool UNRELAXED = decltype(first_three)::value;
 				bool escaped = shortcuts && RayEscapes<Scene>::test(U, R, march_pos(m), ray.dir);
-				if constexpr (EscapesFrom<Scene>::available) escaped = escaped || m.t >= clear_from;
+				if constexpr (EscapesFrom<Scene>::value) escaped = escaped || m.t >= clear_from;
 				if (escaped && (UNRELAXED || m.factor == 1.f)) return MARCH_MISS;
-				float d;
-				if constexpr (SceneReadsMarchState<Scene>::value)
-				{
-					const PixelRay pr = store.pixel_ray_kept();
-					GeoStep gs;
-					gs.camera_distance = m.t;
-					gs.right_off = pr.right_ray;
-					gs.bottom_off = pr.bottom_ray;
-					d = map_geometry_at<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true, gs) * inside_sign;
-				}
-				else
-					d = map_geometry<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true) * inside_sign;
+				const PixelRay pr = store.pixel_ray_kept(); // (read by a scene that reads the march state alone)
+				const float d = scene_distance<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true, m.t, pr.right_ray, pr.bottom_ray) * inside_sign;
 				cnt.march_evals++;
 				if constexpr (UNRELAXED)
 					return march_advance_unrelaxed(m, d, max_range, (uint32_t)U.iter_count, U.dist_eps);
@@ -221,7 +158,8 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 				while (status == MARCH_CONTINUE);
 			}
 		}
-		else // the march as every other scene's kernel has it (body not re-indented: their code stays what it was)
+		else // the march as every other scene's kernel has it (body not re-indented: their code stays what it was; one step body shared with the
+		// passes above was tried and changed every scene's code)
 		do
 		{
 			march_pre(m);
@@ -230,7 +168,7 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 			// shows that it did not over-step (march_advance's test) -- an over-stepped sample can lie beyond an obstacle
 			// that the rewound march then hits.
 			bool escaped = shortcuts && RayEscapes<Scene>::test(U, R, march_pos(m), ray.dir);
-			if constexpr (EscapesFrom<Scene>::available) escaped = escaped || m.t >= clear_from;
+			if constexpr (EscapesFrom<Scene>::value) escaped = escaped || m.t >= clear_from;
 			if (escaped && m.factor == 1.f)
 			{
 				status = MARCH_MISS; // what the remaining steps would come to
@@ -240,13 +178,9 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 			if constexpr (SceneReadsMarchState<Scene>::value)
 			{
 				const PixelRay pr = store.pixel_ray_kept();
-				GeoStep gs;
-				gs.camera_distance = m.t;
-				gs.right_off = pr.right_ray;
-				gs.bottom_off = pr.bottom_ray;
-				d = map_geometry_at<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true, gs) * inside_sign;
+				d = scene_distance<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true, m.t, pr.right_ray, pr.bottom_ray) * inside_sign;
 			}
-			else
+			else // (through scene_distance as well, this call changed the code of the tree's kernel)
 				d = map_geometry<Scene, DBG>(U, F, R, march_pos(m), ray.dir, true) * inside_sign;
 			cnt.march_evals++;
 			if (escaped && !((m.last_d + d) < m.last_d * m.factor))
@@ -260,7 +194,7 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 		SDFR_CLK_ADD(clk_march, c0, c1);
 		store.ray_marched(ray, cnt.march_evals - evals_before, status); // a hook for analysis builds (tests/hostsim); empty in the kernels
 
-		// A shadow ray stopped by a surface whose material nobody needs (ShadowHitsNeedMaterial, sdfr_pixel.h): the hit is counted, and what
+		// A shadow ray stopped by a surface whose material nobody needs (ShadowHitsNeedMaterial, sdfr_scene_traits.h): the hit is counted, and what
 		// shade_hit would come to -- add 0, push nothing, leave the tone-map flag alone -- is what a miss does with a ray that carries no
 		// light: shade_miss of a shadow ray is 0 + contrib, +0 in every component, as V3s(0) is.  Written as a change of the ray and not as a
 		// third branch beside hit and miss: the branch cost the march loop a one-bank fma or the kernel 4 bytes of scratch, wherever it stood.
@@ -285,7 +219,7 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 			{
 				// map_normal, then the sampled normal unless the scene supplied one (pshader_sdf.hlsl:318-330)
 				NormalOut no;
-				if (SceneNormal<Scene>::available)
+				if (SceneNormal<Scene>::value)
 				{
 					const PixelRay pr = store.pixel_ray_kept();
 					no = scene_normal<Scene>(U, hit.pos, ray.dir, hit.t, pr.right_ray, pr.bottom_ray);
@@ -302,15 +236,11 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 					{
 						// grad() works on the hit's GeometryInput: its camera_distance and offsets stay (pshader_sdf.hlsl:164-177)
 						const PixelRay pr = store.pixel_ray_kept();
-						GeoStep gs;
-						gs.camera_distance = hit.t;
-						gs.right_off = pr.right_ray;
-						gs.bottom_off = pr.bottom_ray;
-						g0 = map_geometry_at<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 0, no.sample_dist), ray.dir, false, gs) - baseline;
-						g1 = map_geometry_at<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 1, no.sample_dist), ray.dir, false, gs) - baseline;
-						g2 = map_geometry_at<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 2, no.sample_dist), ray.dir, false, gs) - baseline;
+						g0 = scene_distance<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 0, no.sample_dist), ray.dir, false, hit.t, pr.right_ray, pr.bottom_ray) - baseline;
+						g1 = scene_distance<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 1, no.sample_dist), ray.dir, false, hit.t, pr.right_ray, pr.bottom_ray) - baseline;
+						g2 = scene_distance<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 2, no.sample_dist), ray.dir, false, hit.t, pr.right_ray, pr.bottom_ray) - baseline;
 					}
-					else
+					else // (through scene_distance as well, these calls changed the code of every built-in scene's kernels but normal_test's)
 					{
 						g0 = map_geometry<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 0, no.sample_dist), ray.dir, false) - baseline;
 						g1 = map_geometry<Scene, DBG>(U, F, R, grad_sample_pos(hit.pos, 1, no.sample_dist), ray.dir, false) - baseline;
@@ -329,7 +259,7 @@ SDF_HD vec4 render_pixel(const FrameU &U, int px, int py, PixelCounters &cnt, St
 			float hdr = store.hdr_kept();
 			if constexpr (INL)
 			{
-				// escaped shadow rays deliver their light from the light loop (InlineEscapedShadows, sdfr_pixel.h): each is a ray and a turn of this loop
+				// escaped shadow rays deliver their light from the light loop (InlineEscapedShadows, sdfr_scene_traits.h): each is a ray and a turn of this loop
 				InlineShadows inl;
 				inl.acc = acc;
 				inl.budget = U.bounce_count - 1 - bounce;

@@ -67,7 +67,7 @@ struct SceneDebugMaterials
 };
 
 // normal_test: a diagnostic scene for the one callback of the scene ABI that no reference scene fills in, map_normal
-// (sdf_structs.hlsl:39-52, pshader_sdf.hlsl:318-330, :520) -- here Scene::normal (SceneNormal, sdfr_pixel.h).  A ball
+// (sdf_structs.hlsl:39-52, pshader_sdf.hlsl:318-330, :520) -- here Scene::normal (SceneNormal, sdfr_scene_traits.h).  A ball
 // whose normal is analytic (VAR_analytic), a mirror-coated block and a drum whose normals are sampled VAR_round apart
 // ("larger than usual values lead to rounded corners"), a block left at the default.  Loaded by name, like debug_materials;
 // oracle twin: oracle/test_scenes.h.

@@ -8,10 +8,11 @@
 //   ray_setup()   once per ray: everything in map() that depends on the ray only
 //   dist()        map(..., geometry_step = true): scene distance at a point
 //   material()    map(..., geometry_step = false): material of the surface at a hit point
-//   normal()      map_normal, optional (SceneNormal, sdfr_pixel.h); every scene of the reference leaves it empty, so
+//   normal()      map_normal, optional (SceneNormal, sdfr_scene_traits.h); every scene of the reference leaves it empty, so
 //                 none of the scenes here has one -- the diagnostic scene normal_test does (sdfr_scene_debug.h)
 //   light()       map_light, one light slot at a time
 //   background()  map_background
+// and to what a scene may declare beside them: the table of sdfr_scene_traits.h.
 //
 // Scenes: fast_sphere, cube_sea, labyrinth, fractal, lense, gems, light_shadows
 // (Engine/shader/scenes/sdf_scene_<name>.hlsl).
@@ -37,7 +38,7 @@ struct SceneFastSphere
 	}
 	// floor + one sphere of radius 0.5 about (0, 1, 0)
 	static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &, vec3 p, vec3 dir) { return ray_leaves_floor_and_ball(p, dir, 1.51f, V3(0.f, 1.f, 0.f), 0.52f); }
-	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_pixel.h)
+	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_scene_traits.h)
 	static SDF_HD float dist(const FrameU &U, const RayInv &R, vec3 p, vec3 dir, bool fast)
 	{
 		float d = min1(3e38f, ground_dist(p, fast, R.ground));
@@ -62,7 +63,7 @@ struct SceneFastSphere
 struct SceneCubeSea
 {
 	static const char *name() { return "cube_sea"; }
-	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_render_pixel.h)
+	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_scene_traits.h)
 	static constexpr int retire_after = 4; // at 4K, 256 steps: 2.98 (2) / 2.88 (4) / 2.98 (8) ms; configuration 2 (1080p) is indifferent, 0.75 ms from never to 8
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
 	static const char *variables() { return ""; }
@@ -179,12 +180,12 @@ struct SceneLabyrinth
 {
 	static const char *name() { return "labyrinth"; }
 	static constexpr int waves_per_simd = 7; // configuration 3, round 3 (argument block read on demand: 16 spilled registers instead of 30), one session: 1.247 (5) / 1.234 (6) / 1.226 (7) / 1.254 (8) ms; round 2 had 6 ahead of 7 by 3 % (profiles/r03_launch_experiments.txt)
-	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_render_pixel.h)
+	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_scene_traits.h)
 	static constexpr int retire_after = 4; // configuration 3, two sessions: 1.252 (1) / 1.236 (2) / 1.224 (3) / 1.224 (4) / 1.233 (5) / 1.237 (8) / 1.243 (16) ms
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
-	static constexpr bool noise_grad_table = true; // marble walls, vase and sky: turbulence3 in ~80 % of tiles (sdfr_pixel_kernel.h)
+	static constexpr bool noise_grad_table = true; // marble walls, vase and sky: turbulence3 in ~80 % of tiles (sdfr_scene_traits.h)
 	static constexpr bool shadow_hits_need_material = false; // material() is a pure function and sets no alpha: a shadow ray's hit adds 0 whatever it is made of (sdfr_render_pixel.h)
-	static constexpr bool peel_unrelaxed_samples = true; // a ray's first three samples as straight-line code in front of the march loop (sdfr_pixel.h)
+	static constexpr bool peel_unrelaxed_samples = true; // a ray's first three samples as straight-line code in front of the march loop (sdfr_scene_traits.h)
 	static const char *variables() { return ""; }
 	enum { SU_FIRE_SCROLL = 0, SU_SUN_DIR = 1 /* .. 3 */ };
 	static SDF_HD void prepare(FrameU &U)
@@ -198,7 +199,7 @@ struct SceneLabyrinth
 		U.su[SU_SUN_DIR + 1] = ldir.y;
 		U.su[SU_SUN_DIR + 2] = ldir.z;
 	}
-	// the direction in which the directional light of slot 0 shines (FrameSunDir, sdfr_pixel.h): light() puts the sun there in every frame
+	// the direction in which the directional light of slot 0 shines (FrameSunDir, sdfr_scene_traits.h): light() puts the sun there in every frame
 	static SDF_HD vec3 frame_sun_dir(const FrameU &U) { return V3(U.su[SU_SUN_DIR + 0], U.su[SU_SUN_DIR + 1], U.su[SU_SUN_DIR + 2]); }
 
 	static SDF_HD float fire_cone(vec3 p) { return sd_round_cone(p, V3(0.f, 1.1f, 0.f), V3(0.f, 1.6f, 0.f), 0.15f, 0.1f); }
@@ -219,7 +220,7 @@ struct SceneLabyrinth
 	// floor behind it as well: the sky-bound primary rays of the upper part of the picture (they start above the walls:
 	// no step at all) and every shadow ray once it has cleared the walls.
 	static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &R, vec3 p, vec3) { return R.rising && p.y > 4.01f; }
-	// Once per ray (RayBounds, sdfr_pixel.h): a descending ray that is still above 4.01 where its range ends counts as rising.  march_pos
+	// Once per ray (RayBounds, sdfr_scene_traits.h): a descending ray that is still above 4.01 where its range ends counts as rising.  march_pos
 	// forms p.y as this one fma of dir.y, t and start.y (mad, sdfr_math.h: one fma per component, host and device).  For dir.y < 0 and
 	// t <= range the exact dir.y * t + start.y is no smaller than at `range`, and rounding is monotone: every sample within the range,
 	// the first (t = 0) included, has p.y > 4.01, so ray_escapes ends the ray before its first evaluation.  Nothing is lost: above 4.01
@@ -435,10 +436,10 @@ struct SceneLabyrinth
 struct SceneFractal
 {
 	static const char *name() { return "fractal"; }
-	static constexpr bool square_units = true; // an object in the middle of the picture: its dear tiles are handed out first (sdfr_render_pixel.h)
+	static constexpr bool square_units = true; // an object in the middle of the picture: its dear tiles are handed out first (sdfr_scene_traits.h)
 	static constexpr int retire_after = 1; // its tiles are very uneven: configuration 4 with tile rows 1.203 (1) / 1.178 (2) / 1.199 (4) / 1.38 (8) ms, with the squares 1.044 (1) / 1.058 (2) / 1.070 (3) / 1.072 (4) / 1.19 (8)
 	static constexpr int waves_per_simd = 7; // configuration 4, round 3, one session: 1.26 (5) / 1.22 (6) / 1.196 (7) / 1.193 (8) ms
-	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_render_pixel.h)
+	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_scene_traits.h)
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
 	static const char *variables() { return ""; }
 	static SDF_HD void prepare(FrameU &) {}
@@ -452,7 +453,7 @@ struct SceneFractal
 	}
 	// every box lies in the unit ball about (0, 1, 0) (see dist): nothing above y = 2, and the floor is behind a ray that does not descend
 	static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &, vec3 p, vec3 dir) { return ray_leaves_floor_and_ball(p, dir, 2.01f, V3(0.f, 1.f, 0.f), 1.02f); }
-	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_pixel.h)
+	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_scene_traits.h)
 	// 8-level recursive fold; returns the distance, and the level that first touched
 	static SDF_HD float fold(vec3 p, float *level_hit)
 	{
@@ -539,9 +540,9 @@ struct SceneFractal
 struct SceneLense
 {
 	static const char *name() { return "lense"; }
-	static constexpr int tile_w_log2 = 4; // 16 x 4 pixels per wave: 4.10 -> 3.98 ms at 4K, configuration 5 unchanged (sdfr_render_pixel.h)
-	static constexpr int waves_per_simd = 8; // the march loop fits 64 registers: BASELINE configuration 5 11.5 -> 11.05 ms (sdfr_pixel_kernel.h)
-	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_render_pixel.h)
+	static constexpr int tile_w_log2 = 4; // 16 x 4 pixels per wave: 4.10 -> 3.98 ms at 4K, configuration 5 unchanged (sdfr_scene_traits.h)
+	static constexpr int waves_per_simd = 8; // the march loop fits 64 registers: BASELINE configuration 5 11.5 -> 11.05 ms (sdfr_scene_traits.h)
+	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_scene_traits.h)
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
 	// the scene's variable tags in source order; slot k of FrameU::scene_var is the k-th distinct name
 	static const char *variables()
@@ -767,13 +768,13 @@ struct SceneLense
 struct SceneGems
 {
 	static const char *name() { return "gems"; }
-	static constexpr int tile_w_log2 = 4; // 16 x 4 pixels per wave: configuration 5g 1.579 -> 1.517 ms (sdfr_render_pixel.h)
+	static constexpr int tile_w_log2 = 4; // 16 x 4 pixels per wave: configuration 5g 1.579 -> 1.517 ms (sdfr_scene_traits.h)
 	static constexpr bool square_units = true; // the gems in the middle of the picture: with 8 lights and depth 4 their tiles render for 0.9 ms; first, not last: configuration 5g 1.657 -> 1.563 ms
 	static constexpr bool persistent_tiles = true; // with 8 lights and depth 4 (configuration 5g) 2.88 -> 2.80 ms; the plain scene 1.10 -> 1.09
 	static constexpr int retire_after = 1; // configuration 5g with tile rows 1.74 (8) / 1.68 (2) / 1.71 (1) ms, with the squares 1.480 (1) / 1.505 (2) / 1.510 (3) / 1.562 (4) / 1.81 (8) (profiles/r03_launch_experiments.txt)
-	static constexpr int waves_per_simd = 7; // configuration 5g, with its escaped shadow rays delivered: 1.368 (5) / 1.336 (6) / 1.336 (7) / 1.536 (8) ms; the plain scene 0.799 / 0.818 / 0.779 / 0.873 (sdfr_pixel_kernel.h)
+	static constexpr int waves_per_simd = 7; // configuration 5g, with its escaped shadow rays delivered: 1.368 (5) / 1.336 (6) / 1.336 (7) / 1.536 (8) ms; the plain scene 0.799 / 0.818 / 0.779 / 0.873 (sdfr_scene_traits.h)
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
-	static constexpr bool inline_escaped_shadows = true; // a floor pixel's shadow rays pass the ring at a distance (sdfr_pixel.h)
+	static constexpr bool inline_escaped_shadows = true; // a floor pixel's shadow rays pass the ring at a distance (sdfr_scene_traits.h)
 	static const char *variables() { return ""; }
 	enum { SU_ROT_S = 0, SU_ROT_C = 1 };
 	static SDF_HD void prepare(FrameU &U)
@@ -856,7 +857,7 @@ struct SceneGems
 struct SceneLightShadows
 {
 	static const char *name() { return "light_shadows"; }
-	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_render_pixel.h)
+	static constexpr bool persistent_tiles = true; // expensive, uneven tiles: resident waves pulling tiles win (sdfr_scene_traits.h)
 	static constexpr bool shadow_hits_need_normal = false; // material() does not read sp.normal
 	static const char *variables() { return ""; }
 	// su layout: 5 x {x, y_geometry, z, y_light} then 5 x rgb (colour of sphere i)

@@ -53,7 +53,7 @@ struct SceneFractal2
 	// so it is >= |p - c| - 1.21: skipped where that is not below the floor's distance, and a ray that leaves the ball and the floor is a miss
 	// (0.02 of slack; checked numerically in tests/test_scene_bounds_cpu.py).
 	static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &, vec3 p, vec3 dir) { return ray_leaves_floor_and_ball(p, dir, 2.24f, V3(0.f, 1.f, 0.f), 1.23f); }
-	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_pixel.h)
+	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_scene_traits.h)
 	static SDF_HD float dist(const FrameU &U, const RayInv &R, vec3 p, vec3, bool fast)
 	{
 		float d = min1(3e38f, ground_dist(p, fast, R.ground));
@@ -121,7 +121,7 @@ struct SceneShell
 	// op_shell(d, inner, outer) = |d - middle| - half >= d - outer, so shells() >= cube - 0.35 >= |p - (0, 1, 0)| - 0.866 - 0.35: the shells
 	// lie in the ball of radius 1.2161 about the cube's centre (1.24: slack), below y = 2.24; a ray that leaves it and the floor is a miss
 	static SDF_HD bool ray_escapes(const FrameU &U, const RayInv &, vec3 p, vec3 dir) { return ray_leaves_floor_and_ball(p, dir, 2.25f, V3(0.f, 1.f, 0.f), 1.24f); }
-	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_pixel.h)
+	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_scene_traits.h)
 	static SDF_HD float dist(const FrameU &U, const RayInv &R, vec3 p, vec3, bool fast)
 	{
 		float d = min1(3e38f, shells(p));
@@ -235,7 +235,7 @@ struct SceneSpiral
 	{
 		return ray_leaves_floor_and_ball(p, dir, U.su[SU_CENTER_Y] + U.su[SU_REACH], V3(0.f, U.su[SU_CENTER_Y], 0.f), U.su[SU_REACH]);
 	}
-	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_pixel.h)
+	static constexpr bool inline_escaped_shadows = true; // shadow rays that escape where they start are not queued (sdfr_scene_traits.h)
 	// the floor scrolls under the spring: it is evaluated at x + shift
 	static SDF_HD vec3 scrolled(const FrameU &U, vec3 p) { return V3(p.x + U.su[SU_SHIFT_X], p.y, p.z); }
 	static SDF_HD float dist(const FrameU &U, const RayInv &R, vec3 p, vec3, bool fast)

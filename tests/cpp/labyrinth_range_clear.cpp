@@ -1,5 +1,5 @@
 // tests/cpp/labyrinth_range_clear.cpp -- TEST-ONLY stand-alone host program: SceneLabyrinth::ray_bounds (sdf_playground_amd/csrc/sdfr_scenes.h;
-// RayBounds, sdfr_pixel.h) against a dense walk.  The rule lets a descending ray that is still above the wall tops where its range ends
+// RayBounds, sdfr_scene_traits.h) against a dense walk.  The rule lets a descending ray that is still above the wall tops where its range ends
 // count as rising, so that ray_escapes ends it before its first evaluation; here, wherever the rule sets the flag on a descending ray,
 // every sample from t = 0 to t = range must have march_pos' height above 4.01 (what ray_escapes tests) and the scene at least 0.002 away
 // (twice the largest dist_eps the library accepts), evaluated as the march evaluates it (fast = true).
@@ -14,9 +14,9 @@
 
 using namespace sdfr;
 
-static_assert(RayBounds<SceneLabyrinth>::available, "the labyrinth declares ray_bounds");
-static_assert(!RayBounds<SceneCubeSea>::available && !RayBounds<SceneFastSphere>::available, "a scene without the member gets the no-op");
-static_assert(!EscapesFrom<SceneLabyrinth>::available, "the rule is not an escapes_from: nothing per step");
+static_assert(RayBounds<SceneLabyrinth>::value, "the labyrinth declares ray_bounds");
+static_assert(!RayBounds<SceneCubeSea>::value && !RayBounds<SceneFastSphere>::value, "a scene without the member gets the no-op");
+static_assert(!EscapesFrom<SceneLabyrinth>::value, "the rule is not an escapes_from: nothing per step");
 
 namespace {
 

@@ -596,7 +596,7 @@ extern "C" long long hostsim_check_lense_escape_rule(long long n, unsigned seed,
 template <class Scene>
 static long long check_escape_rule(const FrameU &U, long long n, unsigned seed, long long *fired, float *witness)
 {
-	if constexpr (!RayEscapes<Scene>::available) return -1;
+	if constexpr (!RayEscapes<Scene>::value) return -1;
 	else
 	{
 		unsigned long long state = seed * 2654435761ull + 6262ull;
@@ -649,12 +649,12 @@ extern "C" long long hostsim_check_escape_rule(const char *scene, FrameU *frame,
 	return -2;
 }
 
-// Which step-shortcut traits a built-in scene declares (sdfr_pixel.h): 1 = ray_escapes, 2 = escapes_from, 4 = inline_escaped_shadows in
+// Which step-shortcut traits a built-in scene declares (sdfr_scene_traits.h): 1 = ray_escapes, 2 = escapes_from, 4 = inline_escaped_shadows in
 // effect (declared, and the scene has a ray_escapes for it to act on).  -2: no such scene.
 template <class Scene>
 static int scene_rules()
 {
-	return (RayEscapes<Scene>::available ? 1 : 0) | (EscapesFrom<Scene>::available ? 2 : 0) | (InlineEscapedShadows<Scene>::value ? 4 : 0);
+	return (RayEscapes<Scene>::value ? 1 : 0) | (EscapesFrom<Scene>::value ? 2 : 0) | (InlineEscapedShadows<Scene>::value ? 4 : 0);
 }
 extern "C" int hostsim_scene_rules(const char *scene)
 {
@@ -675,7 +675,7 @@ extern "C" int hostsim_scene_rules(const char *scene)
 template <class Scene>
 static long long check_escapes_from(const FrameU &U, long long n, unsigned seed, long long *fired, float *witness)
 {
-	if constexpr (!EscapesFrom<Scene>::available) return -1;
+	if constexpr (!EscapesFrom<Scene>::value) return -1;
 	else
 	{
 		unsigned long long state = seed * 2654435761ull + 7373ull;

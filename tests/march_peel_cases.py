@@ -1,4 +1,4 @@
-"""The labyrinth frames of the tests of the peeled march (PeelUnrelaxedSamples, sdfr_pixel.h: a ray's first three samples as straight-line code
+"""The labyrinth frames of the tests of the peeled march (PeelUnrelaxedSamples, sdfr_scene_traits.h: a ray's first three samples as straight-line code
 in front of the march loop): tests/test_march_peel_pipeline_cpu.py on the host build, tests/test_gpu_march_peel.py on the kernels.  Each case is
 an eye of tests/labyrinth_shed_cameras.py or one of its own, with limits of its own, and is rendered with every iteration limit of ITER_COUNTS:
 1, 2 and 3 end every ray inside the peeled passes, 4 in the first pass of the loop behind them.

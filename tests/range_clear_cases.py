@@ -1,4 +1,4 @@
-"""The labyrinth frames of the tests of SceneLabyrinth::ray_bounds (RayBounds, sdfr_pixel.h: a descending ray that is still above the wall
+"""The labyrinth frames of the tests of SceneLabyrinth::ray_bounds (RayBounds, sdfr_scene_traits.h: a descending ray that is still above the wall
 tops, y = 4.01, where its range ends is a miss before its first evaluation): tests/test_range_clear_pipeline_cpu.py on the host build,
 tests/test_gpu_range_clear.py on the kernels.  96 x 54 pixels, a field of view of 60 degrees: a row is about 0.02 in dir.y.
 

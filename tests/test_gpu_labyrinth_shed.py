@@ -1,6 +1,6 @@
 """GPU tier: the labyrinth's pixel kernel after it shed work a frame or a result already fixes -- the walls' clamps as sums, no
 material for the hits of shadow rays, the sun's direction per frame (SceneLabyrinth, sdfr_scenes.h; ShadowHitsNeedMaterial,
-FrameSunDir, sdfr_pixel.h) -- against the oracle, bit for bit:
+FrameSunDir, sdfr_scene_traits.h) -- against the oracle, bit for bit:
 pixels, rays and hits per pixel, and the evaluations, exactly where every step is marched and as an upper bound with step shortcuts.
 100 x 60 pixels: 13 x 8 tiles, the right and the bottom ones partial.  The eyes are those of the CPU tier
 (tests/labyrinth_shed_cameras.py)."""

@@ -1,5 +1,5 @@
 """GPU tier: the labyrinth's pixel kernel with its peeled march -- a ray's first three samples as straight-line code, the factor once, the march
-loop without march_pre (PeelUnrelaxedSamples, sdfr_pixel.h; render_pixel) -- against the oracle, bit for bit: pixels, rays and hits per pixel,
+loop without march_pre (PeelUnrelaxedSamples, sdfr_scene_traits.h; render_pixel) -- against the oracle, bit for bit: pixels, rays and hits per pixel,
 and the evaluations, exactly where every step is marched and as an upper bound with step shortcuts.  The frames are those of the CPU tier
 (tests/march_peel_cases.py, which also says what they have to contain; tests/test_march_peel_pipeline_cpu.py asserts it and holds the control:
 tests/test_march_peel_cpu.py shows that the factor one sample early is seen): 96 x 54 pixels, 12 x 7 tiles, the bottom ones partial; every

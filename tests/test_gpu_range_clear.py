@@ -1,4 +1,4 @@
-"""GPU tier: the labyrinth's pixel kernel with its once-per-ray rule (SceneLabyrinth::ray_bounds; RayBounds, sdfr_pixel.h: a descending ray still
+"""GPU tier: the labyrinth's pixel kernel with its once-per-ray rule (SceneLabyrinth::ray_bounds; RayBounds, sdfr_scene_traits.h: a descending ray still
 above the wall tops where its range ends is a miss before its first evaluation) against the oracle, bit for bit: pixels, rays and hits per
 pixel, and the evaluations, exactly where every step is marched and as an upper bound with step shortcuts.  The frames are those of the CPU
 tier (tests/range_clear_cases.py; tests/test_range_clear_pipeline_cpu.py asserts what they contain), one wave per tile and the persistent

@@ -1,4 +1,4 @@
-"""CPU tier: SceneLabyrinth::ray_bounds (sdfr_scenes.h; RayBounds, sdfr_pixel.h) by a dense walk.  The stand-alone host program
+"""CPU tier: SceneLabyrinth::ray_bounds (sdfr_scenes.h; RayBounds, sdfr_scene_traits.h) by a dense walk.  The stand-alone host program
 tests/cpp/labyrinth_range_clear.cpp draws 200 000 rays -- starts 4 to 60 high, |dir.y| from 1e-6 to 1, directions up to 6e-4 short of unit
 length, ranges from 0.5 to 1000 -- and, wherever the rule sets the flag on a descending ray, walks t from 0 to the range: every sample must be
 above 4.01 as ray_escapes sees it, with SceneLabyrinth::dist(..., fast = true) >= 0.002.  It also holds the edge cases: the fma one ulp either

@@ -1,5 +1,5 @@
 """CPU tier: the labyrinth after its pixel kernel shed work that a frame or a result already fixes (SceneLabyrinth, sdfr_scenes.h;
-ShadowHitsNeedMaterial, FrameSunDir, sdfr_pixel.h).  The sun's direction as prepare() stores it against the light loop's own
+ShadowHitsNeedMaterial, FrameSunDir, sdfr_scene_traits.h).  The sun's direction as prepare() stores it against the light loop's own
 expression; then the whole pipeline, the host build of the product's headers (tests/hostsim: render_pixel with the unshaded shadow hits,
 the stored sun and the walls' sums), against the oracle -- pixels and per-pixel counters bit for bit, step shortcuts on and off -- from
 the sweep eyes of bench.py and from eyes near a vase and the torch, in corridors below the wall tops, inside a wall, below the floor,

@@ -1,5 +1,5 @@
 """CPU tier: the whole pipeline with the labyrinth's peeled march -- the host build of the product's headers (tests/hostsim: render_pixel with a
-ray's first three samples as straight-line code, the factor once, the loop without march_pre; PeelUnrelaxedSamples, sdfr_pixel.h) against the
+ray's first three samples as straight-line code, the factor once, the loop without march_pre; PeelUnrelaxedSamples, sdfr_scene_traits.h) against the
 oracle: pixels, rays and hits per pixel bit for bit, the evaluations equal where every step is marched and no more than the oracle's with step
 shortcuts.  The frames and what they have to contain: tests/march_peel_cases.py; every case with the iteration limits 1, 2, 3, 4, 5, 100, 256."""
 import numpy as np

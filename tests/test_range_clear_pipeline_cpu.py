@@ -1,4 +1,4 @@
-"""CPU tier: the whole pipeline with the labyrinth's once-per-ray rule (SceneLabyrinth::ray_bounds; RayBounds, sdfr_pixel.h) -- the host build of
+"""CPU tier: the whole pipeline with the labyrinth's once-per-ray rule (SceneLabyrinth::ray_bounds; RayBounds, sdfr_scene_traits.h) -- the host build of
 the product's headers (tests/hostsim) against the oracle: pixels, rays and hits per pixel bit for bit, the evaluations equal where every step is
 marched and no more than the oracle's with step shortcuts.  The frames: tests/range_clear_cases.py, every case with the iteration limits 1, 3,
 100 and 256.  Then, on the oracle and the host build alone, what the cases are for: the band's pixels march in the oracle and not in the product,

@@ -379,7 +379,7 @@ def _scene_rules():
 
 def test_shared_scene_lists_match_the_rules_the_scenes_declare():
     """tests/shortcut_scenes.py names the scenes whose rules the GPU tier covers one by one: it must be what the functors declare
-    (sdfr_pixel.h: RayEscapes, EscapesFrom, InlineEscapedShadows), so that a rule added or removed without the tests fails here"""
+    (sdfr_scene_traits.h: RayEscapes, EscapesFrom, InlineEscapedShadows), so that a rule added or removed without the tests fails here"""
     rules = _scene_rules()
     assert tuple(rules) == ALL_SCENES and all(v >= 0 for v in rules.values()), rules
     assert {s for s, v in rules.items() if v & 1} == RAY_ESCAPES

@@ -90,7 +90,7 @@ def test_camera_under_the_floor_matches_the_oracle_with_shortcuts(oracle, scene)
 
 @pytest.mark.parametrize("bounces,slots", [(16, 8), (9, 8), (5, 8), (3, 8), (2, 8), (1, 8), (16, 4), (16, 1), (6, 3)])
 def test_shadow_rays_delivered_from_the_light_loop_keep_budget_and_order(oracle, bounces, slots):
-    """gems declares inline_escaped_shadows (sdfr_pixel.h): a floor pixel's escaped shadow rays never enter the queue.  With eight
+    """gems declares inline_escaped_shadows (sdfr_scene_traits.h): a floor pixel's escaped shadow rays never enter the queue.  With eight
     lights, a ray budget that ends among them and a queue shorter than their number, pixels, ray and hit counts stay the oracle's."""
     import hostsim
 
@@ -110,7 +110,7 @@ def test_shadow_rays_delivered_from_the_light_loop_keep_budget_and_order(oracle,
 
 @pytest.mark.parametrize("ball", [None, (3.0, 1.5, 4.0), (-4.0, -3.0, 0.5), (0.0, 0.0, 25.0)])
 def test_lense_shadow_rays_end_between_the_blob_fields(oracle, ball):
-    """lense declares escapes_from (sdfr_pixel.h): a shadow ray towards an extension light (3 high, between the blob fields) is a miss
+    """lense declares escapes_from (sdfr_scene_traits.h): a shadow ray towards an extension light (3 high, between the blob fields) is a miss
     once it is inside the free slab and has lens, light ball and pane behind it or aside.  Pixels, rays and hits stay the oracle's
     wherever the light ball is moved."""
     import hostsim

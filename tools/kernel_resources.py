@@ -24,7 +24,7 @@ BASELINE = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
 
 
 def waves_per_simd(scene):
-    """the scene's `waves_per_simd` declaration (default 7: sdfr_pixel_kernel.h PixelWavesPerSimd)"""
+    """the scene's `waves_per_simd` declaration (default 7: sdfr_scene_traits.h PixelWavesPerSimd)"""
     for f in os.listdir(isa_loops.CSRC):
         if f.startswith("sdfr_scene"):
             text = open(os.path.join(isa_loops.CSRC, f)).read()
