@@ -631,6 +631,80 @@ int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4]);
 int sdfr_mesh_extract_sharp(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t vertex_capacity, int64_t triangle_capacity, float *positions /*[v][3]*/,
 	float *normals /*[v][3] or NULL*/, uint32_t *indices /*[t][3]*/, sdfr_mesh_counts *counts /*host, required*/, int on_host);
 
+/* ---- where the surface is: what a lattice holds, and the grid that fits the surface (no counterpart in the reference; DESIGN.md
+ *      "Mesh survey and fit").  Every result is an integer, counted exactly: no floating-point reduction, no dependence on order.
+ *
+ *      sdfr_mesh_survey.  D, s = D - iso, INSIDE, ACTIVE and the quad rule are sdfr_mesh_extract's, word for word, and so are the
+ *      grid's limits.  A cell is NEAR iff it is active or some corner has fabsf(s) <= band (NaN is never near and never inside).
+ *      active_cells is counts.vertices of sdfr_mesh_extract on the same grid and 2 * quads its counts.triangles; inside_points counts
+ *      the lattice points with s < 0; the bounds are inclusive cell indices per axis -- with no such cell lo[a] = n[a] and hi[a] = -1;
+ *      face_active counts the active cells with i == 0, i == nx - 1, j == 0, j == ny - 1, k == 0, k == nz - 1 (a cell may lie on
+ *      several): the surface leaves the box there, and sdfr_mesh_extract's mesh is open.
+ *
+ *        - out is host memory; the call is synchronous, like the counting call: it reads the result back.
+ *        - like a query, it latches camera, time, variables and limits into a copy and changes nothing a render uses or reports
+ *          (stats, timings, row order; sdfr_mesh_get_timings keeps the last extraction's); it runs on the lane of the frame submitted
+ *          last.  Its workspace is the mesh workspace of the handle, of which it needs the lattice alone (4 bytes per lattice point)
+ *          and 92 KiB for the result words; it is given back after a call that needed more than 64 MiB.
+ *        - errors, in the order they win: SDFR_ERR_INVALID_ARGUMENT for a NULL grid or out ("null pointer"), a grid
+ *          sdfr_mesh_extract refuses ("bad mesh grid"), a band that is not finite or < 0; then SDFR_ERR_NO_SCENE.  Nothing is written
+ *          on error. ------------------------------------------------------------------------------------------------------------ */
+typedef struct sdfr_mesh_survey_result
+{
+	int64_t active_cells;   /* == counts.vertices of sdfr_mesh_extract on the same grid */
+	int64_t quads;          /* 2 * quads == counts.triangles */
+	int64_t near_cells;
+	int64_t inside_points;  /* lattice points with s < 0 */
+	int32_t active_lo[3], active_hi[3]; /* inclusive cell indices; none: lo[a] = n[a], hi[a] = -1 */
+	int32_t near_lo[3], near_hi[3];
+	int64_t face_active[6]; /* active cells with i == 0, i == nx-1, j == 0, j == ny-1, k == 0, k == nz-1 */
+} sdfr_mesh_survey_result;
+int sdfr_mesh_survey(sdfr_renderer *r, const sdfr_mesh_grid *grid, float band, sdfr_mesh_survey_result *out /* host */);
+
+/*      sdfr_mesh_fit: shrink a search grid onto the surface, coarse to fine.  `search` is a grid at the TARGET cell size c; it may be
+ *      far larger than an extractable grid: n[a] in 1 .. 2^20 (origin, cell, iso finite, cell > 0).  levels L in 0 .. 10 with
+ *      cell * 2^L finite, margin m in 0 .. 8.
+ *
+ *      Start with the window lo = 0, hi = n, in cells of the search grid, hi exclusive.  For l = L, L - 1, ..., 0, with step = 1 << l:
+ *      the level grid has origin_l[a] = origin[a] + (float)lo[a] * c (one multiply, then one add, unfused), cell_l = c * (float)step,
+ *      n_l[a] = ceil((hi[a] - lo[a]) / step), and the same iso.  If sdfr_mesh_extract would refuse the level grid (more than 1024
+ *      cells on an axis, more than 2^30 lattice points, an origin that is no longer finite), stop: SDFR_FIT_TOO_LARGE at this level, with
+ *      the window so far.  Otherwise survey it with band_l = 1.75f * cell_l for l >= 1 and band_l = 0 for l = 0, and take the bounds
+ *      b of its near cells (l >= 1) or of its active cells (l = 0).  If there are none, stop: SDFR_FIT_EMPTY at this level.  Otherwise,
+ *      with g = 1 for l >= 1 and g = m for l = 0: lo'[a] = max(lo[a] + (b_lo[a] - g) * step, 0) and hi'[a] = min(lo[a] + (b_hi[a] + 1 + g)
+ *      * step, n[a]).  After level 0 the state is SDFR_FIT_FOUND and the fitted grid is origin[a] + (float)lo[a] * c, cell c,
+ *      n = hi - lo, iso: extractable by construction, and a sub-lattice of the search grid's wherever the search lattice's coordinates
+ *      are exact (dyadic origin and cell).
+ *
+ *      Why coarse levels may be trusted: sphere tracing already needs |D - iso| never to exceed the true distance to the
+ *      iso-surface.  A coarse cell the surface passes through has every corner within its diagonal, sqrt(3) * cell_l < 1.75 * cell_l,
+ *      of the surface, so under that contract every corner has |s| <= band_l and the cell is near: no level drops it.
+ *        1. With levels = 0 nothing rests on that contract: the fit is one dense survey of the search grid (which must then be
+ *           extractable) and its active bounds.
+ *        2. A scene whose distance OVERESTIMATES (a warped or scaled field without a matching divisor) may lose what a coarse level
+ *           missed: the window can only shrink.
+ *        3. With margin >= 1 the fitted grid's mesh is the search grid's mesh: the same vertices in the same order and the same
+ *           quads.  Cropping keeps the order of the linear indices, and every active cell ends up interior, so that no quad is
+ *           dropped; where the fit is clamped to the search window, the search grid would have dropped those boundary quads as well.
+ *
+ *        - out is host memory.  state, level (the level reached), surveys (how many ran), lo and hi (the window) are always filled;
+ *          grid is the fitted grid when FOUND and zeros otherwise; last is the last survey that ran, zeros if none did.
+ *        - protocol, lane and workspace are sdfr_mesh_survey's; the frame is latched once for all levels.
+ *        - errors, in the order they win: SDFR_ERR_INVALID_ARGUMENT for a NULL search or out ("null pointer"), a bad search grid,
+ *          bad levels, a bad margin; then SDFR_ERR_NO_SCENE.  Nothing is written on error. ---------------------------------------- */
+#define SDFR_FIT_EMPTY 0
+#define SDFR_FIT_FOUND 1
+#define SDFR_FIT_TOO_LARGE 2
+typedef struct sdfr_mesh_fit_result
+{
+	int32_t state;          /* SDFR_FIT_EMPTY 0, SDFR_FIT_FOUND 1, SDFR_FIT_TOO_LARGE 2 */
+	int32_t level, surveys; /* the level reached; surveys run */
+	int32_t lo[3], hi[3];   /* the window in cells of the search grid, hi exclusive */
+	sdfr_mesh_grid grid;    /* FOUND: the fitted grid; else zeros */
+	sdfr_mesh_survey_result last; /* the last survey run; zeros if none */
+} sdfr_mesh_fit_result;
+int sdfr_mesh_fit(sdfr_renderer *r, const sdfr_mesh_grid *search, int levels, int margin, sdfr_mesh_fit_result *out /* host */);
+
 /* ---- a texture atlas of an extracted mesh (no counterpart in the reference; DESIGN.md "Texture atlas"): one square tile of texels per
  *      quad of the mesh, baked on the GPU.  Surface nets emits quads: triangles 2q and 2q + 1 are (q0, q1, q2) and (q0, q2, q3) of one
  *      quad, so a tile per quad needs no chart cutting and no packing search, and bilinear filtering inside a quad never leaves its tile.

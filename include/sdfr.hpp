@@ -192,6 +192,18 @@ public:
 			sdfr_mesh_extract_sharp(handle, &grid, vertex_capacity, triangle_capacity, positions, normals, indices, &counts, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// Where the surface is (sdfr_mesh_survey and sdfr_mesh_fit in sdfr.h), with this renderer's variables and time: what the lattice of
+	// `grid` holds, counted in integers; and `search` (up to 2^20 cells per axis) shrunk onto the surface coarse to fine -- out.grid is
+	// then what extractMesh takes, if out.state == SDFR_FIT_FOUND.
+	bool surveyMesh(const sdfr_mesh_grid &grid, float band, sdfr_mesh_survey_result &out)
+	{
+		return handle && pushState() && sdfr_mesh_survey(handle, &grid, band, &out) == SDFR_OK;
+	}
+	bool fitMesh(const sdfr_mesh_grid &search, int levels, int margin, sdfr_mesh_fit_result &out)
+	{
+		return handle && pushState() && sdfr_mesh_fit(handle, &search, levels, margin, &out) == SDFR_OK;
+	}
+
 	// The texture atlas of an extracted mesh (sdfr_atlas_layout, sdfr_atlas_uvs, sdfr_atlas_texels, sdfr_atlas_bake in sdfr.h): one square
 	// tile of texels per quad.  atlasTexels looks at the mesh alone; bakeAtlas looks at every texel as meshSurfaces / meshLighting look at
 	// a vertex, with this renderer's variables and time.  layers: SDFR_ATLAS_*; a plane that is not asked for may be null.

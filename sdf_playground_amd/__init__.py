@@ -80,6 +80,32 @@ class MeshCounts(ctypes.Structure):  # sdfr_mesh_counts
     _fields_ = [("vertices", ctypes.c_int64), ("triangles", ctypes.c_int64)]
 
 
+class MeshSurvey(ctypes.Structure):  # sdfr_mesh_survey_result
+    _fields_ = [("active_cells", ctypes.c_int64), ("quads", ctypes.c_int64), ("near_cells", ctypes.c_int64), ("inside_points", ctypes.c_int64),
+                ("active_lo", ctypes.c_int32 * 3), ("active_hi", ctypes.c_int32 * 3), ("near_lo", ctypes.c_int32 * 3), ("near_hi", ctypes.c_int32 * 3),
+                ("face_active", ctypes.c_int64 * 6)]
+
+    def as_dict(self):
+        return {name: (int(getattr(self, name)) if name.endswith(("cells", "quads", "points")) else tuple(int(v) for v in getattr(self, name)))
+                for name, _type in self._fields_}
+
+
+FIT_EMPTY, FIT_FOUND, FIT_TOO_LARGE = 0, 1, 2  # SDFR_FIT_*
+
+
+class MeshFit(ctypes.Structure):  # sdfr_mesh_fit_result
+    _fields_ = [("state", ctypes.c_int32), ("level", ctypes.c_int32), ("surveys", ctypes.c_int32), ("lo", ctypes.c_int32 * 3), ("hi", ctypes.c_int32 * 3),
+                ("grid", MeshGrid), ("last", MeshSurvey)]
+
+
+def default_fit_levels(dims):
+    """fitMesh's levels=None: the smallest L with ceil(n / 2^L) <= 64 on every axis, 10 at the most"""
+    levels = 0
+    while levels < 10 and max(-(-int(n) // (1 << levels)) for n in dims) > 64:
+        levels += 1
+    return levels
+
+
 # sdfr_hit (include/sdfr.h): the answer of a ray query or a pick, 48 bytes
 class Atlas(ctypes.Structure):  # sdfr_atlas
     _fields_ = [("triangles", ctypes.c_int64), ("quads", ctypes.c_int64), ("tile", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -133,6 +159,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_query_ray_lighting", "sdfr_pick_lighting", "sdfr_mesh_lighting",
     "sdfr_atlas_layout", "sdfr_atlas_uvs", "sdfr_atlas_texels", "sdfr_atlas_bake",
     "sdfr_mesh_extract_sharp",
+    "sdfr_mesh_survey", "sdfr_mesh_fit",
 ]
 
 _lib = None
@@ -244,6 +271,8 @@ def load_library():
     L.sdfr_mesh_extract.argtypes = [vp, ctypes.POINTER(MeshGrid), i64, i64, vp, vp, vp, ctypes.POINTER(MeshCounts), ci]
     L.sdfr_mesh_extract_sharp.argtypes = L.sdfr_mesh_extract.argtypes
     L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
+    L.sdfr_mesh_survey.argtypes = [vp, ctypes.POINTER(MeshGrid), cf, ctypes.POINTER(MeshSurvey)]
+    L.sdfr_mesh_fit.argtypes = [vp, ctypes.POINTER(MeshGrid), ci, ci, ctypes.POINTER(MeshFit)]
     L.sdfr_atlas_layout.argtypes = [i64, ci, ci, ctypes.POINTER(Atlas)]
     L.sdfr_atlas_uvs.argtypes = [ctypes.POINTER(Atlas), vp]
     L.sdfr_atlas_texels.argtypes = [vp, ctypes.POINTER(Atlas), i64, vp, vp, vp, vp, vp, vp, ci]
@@ -928,6 +957,34 @@ class SDFRenderer:
             self.sync()
             out = {k: (a if k == "atlas" else a.cpu().numpy()) for k, a in out.items()}
         return out
+
+    # ---- where the surface is (sdfr_mesh_survey / sdfr_mesh_fit; DESIGN.md "Mesh survey and fit") -----------------------------------
+    def surveyMesh(self, origin, cell, dims, iso=0.0, band=0.0):
+        """What the lattice of extractMesh(origin, cell, dims, iso) holds (sdfr_mesh_survey), counted on the GPU in integers: a dict of
+        active_cells (the mesh's vertices), quads (half its triangles), near_cells (active, or a corner with |distance - iso| <= band),
+        inside_points, the inclusive bounds active_lo / active_hi / near_lo / near_hi (none: lo = dims, hi = -1) and face_active, the
+        active cells on the box's six faces -- non-zero where the surface leaves the box and the mesh is open."""
+        grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
+        out = MeshSurvey()
+        self._check(self._L.sdfr_mesh_survey(self._h, ctypes.byref(grid), float(band), ctypes.byref(out)))
+        return out.as_dict()
+
+    def fitMesh(self, origin, cell, dims, iso=0.0, levels=None, margin=1):
+        """Shrink the search grid (origin, cell, dims) -- up to 2^20 cells per axis -- onto the surface, coarse to fine (sdfr_mesh_fit).
+        levels=None: the smallest number of levels whose coarsest grid has at most 64 cells per axis (10 at the most).  -> a dict:
+        state (FIT_EMPTY, FIT_FOUND, FIT_TOO_LARGE), level, surveys, the window lo / hi in search cells, survey (the last one run, or
+        None), and for FIT_FOUND origin and dims of the fitted grid (else None), to hand to extractMesh with the same cell and iso.
+        Coarse levels rest on the scene's distance never overestimating (what sphere tracing needs too); levels=0 rests on nothing."""
+        if levels is None:
+            levels = default_fit_levels(dims)
+        grid = MeshGrid((ctypes.c_float * 3)(*[float(v) for v in origin]), float(cell), int(dims[0]), int(dims[1]), int(dims[2]), float(iso))
+        out = MeshFit()
+        self._check(self._L.sdfr_mesh_fit(self._h, ctypes.byref(grid), int(levels), int(margin), ctypes.byref(out)))
+        found = out.state == FIT_FOUND
+        return dict(state=int(out.state), level=int(out.level), surveys=int(out.surveys), lo=tuple(out.lo), hi=tuple(out.hi),
+                    origin=tuple(float(v) for v in out.grid.origin) if found else None,
+                    dims=(int(out.grid.nx), int(out.grid.ny), int(out.grid.nz)) if found else None,
+                    survey=out.last.as_dict() if out.surveys else None)
 
     def getMeshTimings(self):
         """GPU ms of the last extractMesh's filling call, if setProfiling(True) was on: {sample, classify_scan, emit, normals}."""

@@ -16,12 +16,14 @@
     python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-sharp --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... with its walls' edges kept sharp
     python -m sdf_playground_amd.cli --scene lense --size 640x360 --gbuffer lense.npz   # depth, normal, albedo, material id per pixel
     python -m sdf_playground_amd.cli --scene labyrinth --mesh lab.obj --mesh-colors --mesh-ao 0.4 --mesh-box -6 0 -3 0 2 3 --mesh-cell 0.02   # ... shaded by ambient occlusion
+    python -m sdf_playground_amd.cli --scene tree --mesh tree.obj --mesh-fit --mesh-box -50 -50 -50 50 50 50 --mesh-cell 0.02   # ... in a box the library finds
 
 --out writes the tone-mapped + bloomed LDR image (HDR::process, like the reference's window);
 --out-hdr writes the raw float32 RGBA frame as .npy.  --mesh writes the scene's surface (distance == --mesh-iso) inside --mesh-box
 as a Wavefront OBJ with normals: surface nets on cells of edge --mesh-cell (SDFRenderer.extractMesh), at --time with the --set
 variables; --mesh-sharp keeps the same triangles and moves every vertex onto the scene's planes at its cell's edge crossings, so that
-edges and corners stay sharp (SDFRenderer.extractMesh(sharp=True)); --mesh-colors adds a colour per vertex (`v x y z r g b`): the albedo of the material under the vertex, or its unlit colour
+edges and corners stay sharp (SDFRenderer.extractMesh(sharp=True)); --mesh-fit takes --mesh-box as a search box of up to 2^20 cells per
+axis, fits the grid onto the surface inside it first (SDFRenderer.fitMesh) and prints the fitted box; --mesh-colors adds a colour per vertex (`v x y z r g b`): the albedo of the material under the vertex, or its unlit colour
 (SDFRenderer.extractMesh(surfaces=True)).  --gbuffer writes what lies under every pixel of the frame --out would render, as an .npz:
 depth [h, w] (the hit's t; inf on a miss), normal [h, w, 3] (the shading normal), albedo [h, w, 3] (as --mesh-colors, unclipped),
 material_id and valid [h, w] (SDFRenderer.pickSurfaces).  --mesh-ao RADIUS multiplies the vertex colours (grey without --mesh-colors)
@@ -79,16 +81,34 @@ def parse_var_tags(text):
     return dict(sorted(out.items()))
 
 
-def mesh_grid_from_box(box, cell):
+def mesh_grid_from_box(box, cell, limit=1024):
     """--mesh-box x0 y0 z0 x1 y1 z1 and --mesh-cell -> (origin, dims): the lattice starts at the box's low corner and has as many
-    whole cells per axis as cover the box (at least one, at most 1024)."""
+    whole cells per axis as cover the box (at least one, at most 1024 -- or `limit`, for the search box of --mesh-fit)."""
     lo, hi = box[:3], box[3:]
     if not cell > 0 or any(not h > l for l, h in zip(lo, hi)):
         raise ValueError("--mesh-box needs x0 < x1, y0 < y1, z0 < z1 and --mesh-cell > 0")
     dims = tuple(max(1, int(math.ceil((h - l) / cell - 1e-6))) for l, h in zip(lo, hi))
-    if max(dims) > 1024:
-        raise ValueError("--mesh-box / --mesh-cell give %dx%dx%d cells: at most 1024 per axis" % dims)
+    if max(dims) > limit:
+        raise ValueError("--mesh-box / --mesh-cell give %dx%dx%d cells: at most %d per axis" % (dims + (limit,)))
     return tuple(lo), dims
+
+
+def fit_message(fit, search_dims, cell):
+    """what --mesh-fit says of SDFRenderer.fitMesh's answer: the fitted box, or why there is none"""
+    from . import FIT_EMPTY, FIT_FOUND
+
+    if fit["state"] == FIT_FOUND:
+        o, n = fit["origin"], fit["dims"]
+        hi = tuple(float(np.float32(o[k]) + np.float32(n[k]) * np.float32(cell)) for k in range(3))
+        open_faces = sum(1 for v in fit["survey"]["face_active"] if v)
+        return ("fitted box %g %g %g %g %g %g: %dx%dx%d of %dx%dx%d cells, %d surveys%s"
+                % (tuple(o) + hi + tuple(n) + tuple(search_dims) + (fit["surveys"],
+                   ", the surface leaves the search box on %d faces (an open mesh)" % open_faces if open_faces else "")))
+    if fit["state"] == FIT_EMPTY:
+        return "--mesh-fit: no surface inside --mesh-box (nothing found at level %d, cells of %g)" % (fit["level"], cell * (1 << fit["level"]))
+    window = tuple(h - l for l, h in zip(fit["lo"], fit["hi"]))
+    return ("--mesh-fit: the surface spans %dx%dx%d cells at level %d, more than one extraction takes (1024 per axis, 2^30 lattice points): "
+            "a larger --mesh-cell or a smaller --mesh-box" % (window + (fit["level"],)))
 
 
 def _vec(s):
@@ -130,6 +150,11 @@ def make_parser():
     ap.add_argument("--mesh-iso", type=float, default=0.0, metavar="V", help="the surface is distance == V (default 0)")
     ap.add_argument("--mesh-sharp", action="store_true", help="with --mesh: keep the scene's sharp edges and corners -- the same triangles, every "
                     "vertex moved onto the scene's planes at its cell's edge crossings (SDFRenderer.extractMesh(sharp=True))")
+    ap.add_argument("--mesh-fit", action="store_true", help="with --mesh: --mesh-box is a search box (up to 2^20 cells per axis); the grid is fitted onto "
+                    "the surface inside it before the extraction (SDFRenderer.fitMesh), and the fitted box is printed")
+    ap.add_argument("--mesh-fit-levels", type=int, metavar="L", help="with --mesh-fit: coarse levels, 0..10 (default: the coarsest grid has at most "
+                    "64 cells per axis); 0: one dense survey, which trusts nothing about the scene's distance")
+    ap.add_argument("--mesh-fit-margin", type=int, default=1, metavar="M", help="with --mesh-fit: cells kept around the surface, 0..8 (default 1)")
     ap.add_argument("--mesh-colors", action="store_true", help="with --mesh: a colour per vertex, from the material under it")
     ap.add_argument("--gbuffer", metavar="OUT.npz", help="write depth, normal, albedo, material_id and valid of every pixel of the frame")
     ap.add_argument("--mesh-ao", type=float, metavar="RADIUS", help="with --mesh: vertex colours times the ambient openness within RADIUS")
@@ -214,9 +239,15 @@ def main(argv=None):
         ap.error("--mesh-atlas needs --mesh")
     elif a.mesh_sharp:
         ap.error("--mesh-sharp needs --mesh")
+    elif a.mesh_fit:
+        ap.error("--mesh-fit needs --mesh")
+    if a.mesh_fit_levels is not None and not a.mesh_fit:
+        ap.error("--mesh-fit-levels needs --mesh-fit")
+    if a.mesh_fit and ((a.mesh_fit_levels is not None and not 0 <= a.mesh_fit_levels <= 10) or not 0 <= a.mesh_fit_margin <= 8):
+        ap.error("--mesh-fit-levels must be 0..10 and --mesh-fit-margin 0..8")
     if a.mesh:
         try:
-            mesh_grid = mesh_grid_from_box(a.mesh_box, a.mesh_cell)
+            mesh_grid = mesh_grid_from_box(a.mesh_box, a.mesh_cell, 1 << 20 if a.mesh_fit else 1024)
         except ValueError as e:
             ap.error(str(e))
     r = sp.SDFRenderer(a.device)
@@ -252,6 +283,14 @@ def main(argv=None):
     cam.SetRoll(a.roll)
     r.setLimits(iter_count=a.iter_count, max_cost_default=a.max_cost)
     r.setParameters(a.time)
+    if mesh_grid and a.mesh_fit:
+        fit = r.fitMesh(mesh_grid[0], a.mesh_cell, mesh_grid[1], iso=a.mesh_iso, levels=a.mesh_fit_levels, margin=a.mesh_fit_margin)
+        message = fit_message(fit, mesh_grid[1], a.mesh_cell)
+        if fit["state"] != sp.FIT_FOUND:
+            print(message, file=sys.stderr)
+            return 1
+        print(message)
+        mesh_grid = (fit["origin"], fit["dims"])
     if mesh_grid:
         from .obj import write_obj
 

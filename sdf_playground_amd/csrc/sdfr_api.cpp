@@ -950,6 +950,29 @@ int sdfr_hit_occlusion(sdfr_renderer *r, int64_t n, const sdfr_hit *hits, float 
 // index instead of the vertex, and the scene's sharp-vertex kernel (sdfr_mesh_sharp.h) makes the vertices from them; all else is the same.
 static_assert(sizeof(sdfr_mesh_grid) == sizeof(MeshGrid) && offsetof(sdfr_mesh_grid, cell) == offsetof(MeshGrid, cell) && offsetof(sdfr_mesh_grid, nx) == offsetof(MeshGrid, n) &&
 		offsetof(sdfr_mesh_grid, iso) == offsetof(MeshGrid, iso), "sdfr_mesh_grid is the plan's MeshGrid");
+// `work` cut out of the handle's mesh workspace, for work on `stream`
+static int reserve_mesh_workspace(sdfr_renderer *r, Carving &work, hipStream_t stream)
+{
+	for (hipEvent_t &e : r->ev_mesh)
+		if (!e) SDFR_HIP(hipEventCreate(&e));
+	// the last extraction's emit work (device arrays: enqueued, perhaps on the other lane's stream) still reads the workspace
+	SDFR_HIP(hipStreamWaitEvent(stream, r->ev_mesh[6], 0));
+	if (r->mesh.bytes < work.total) SDFR_HIP(hipEventSynchronize(r->ev_mesh[6]));
+	SDFR_HIP(work.reserve(r->mesh));
+	return SDFR_OK;
+}
+// the loaded scene's distances at the lattice points of `la`, into d_lattice
+static int sample_lattice(sdfr_renderer *r, const FrameU &U, LatticeArgs la, float *d_lattice, hipStream_t stream)
+{
+	static const int rows = [] { const char *e = getenv("SDFR_MESH_LATTICE_ROWS"); return e && atoi(e) != 0 ? 1 : 0; }(); // developer knob: the A/B
+	la.rows = rows;
+	la.out = d_lattice;
+	KernelRef lattice_kernel;
+	const int rc = loaded_query_kernel(r, QUERY_KERNEL_LATTICE, U, lattice_kernel);
+	if (rc != SDFR_OK) return rc;
+	const hipError_t e = launch_query_lattice(lattice_kernel, U, la, stream);
+	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "lattice launch");
+}
 static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *counts, bool sharp)
 {
 	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
@@ -961,27 +984,16 @@ static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *c
 	if (rc != SDFR_OK) return rc;
 
 	Carving work({p.work[0], p.work[1], p.work[2], p.work[3]});
-	for (hipEvent_t &e : r->ev_mesh)
-		if (!e) SDFR_HIP(hipEventCreate(&e));
+	rc = reserve_mesh_workspace(r, work, stream);
+	if (rc != SDFR_OK) return rc;
 	hipEvent_t *ev = r->profiling ? r->ev_mesh : nullptr;
 	r->mesh_timed = 0;
-	// the last extraction's emit work (device arrays: enqueued, perhaps on the other lane's stream) still reads the workspace
-	SDFR_HIP(hipStreamWaitEvent(stream, r->ev_mesh[6], 0));
-	if (r->mesh.bytes < work.total) SDFR_HIP(hipEventSynchronize(r->ev_mesh[6]));
-	SDFR_HIP(work.reserve(r->mesh));
 	float *d_lattice = work.piece<float>(0);
 	uint32_t *d_cells = work.piece<uint32_t>(1), *d_points = work.piece<uint32_t>(2), *d_sums = work.piece<uint32_t>(3);
 
-	LatticeArgs la = p.lattice;
-	static const int rows = [] { const char *e = getenv("SDFR_MESH_LATTICE_ROWS"); return e && atoi(e) != 0 ? 1 : 0; }(); // developer knob: the A/B
-	la.rows = rows;
-	la.out = d_lattice;
 	if (ev) SDFR_HIP(hipEventRecord(ev[0], stream));
-	KernelRef lattice_kernel;
-	rc = loaded_query_kernel(r, QUERY_KERNEL_LATTICE, U, lattice_kernel);
+	rc = sample_lattice(r, U, p.lattice, d_lattice, stream);
 	if (rc != SDFR_OK) return rc;
-	const hipError_t e = launch_query_lattice(lattice_kernel, U, la, stream);
-	if (e != hipSuccess) return hip_fail(r, e, "lattice launch");
 	if (ev) SDFR_HIP(hipEventRecord(ev[1], stream));
 	SDFR_HIP(launch_mesh_count(p.g, d_lattice, d_cells, d_points, d_sums, stream));
 	if (ev) SDFR_HIP(hipEventRecord(ev[2], stream));
@@ -1071,6 +1083,71 @@ int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
 			}
 			ms[k] = t;
 		}
+		return SDFR_OK;
+	});
+}
+
+// ---- sdfr_mesh_survey and sdfr_mesh_fit (the definitions: include/sdfr.h; the plans: sdfr_mesh_plan.h; the predicates and the fit's loop:
+// sdfr_mesh_survey.h; the kernel: sdfr_mesh.hip), calls of the queries' protocol and synchronous like the counting call.  The workspace is
+// the extraction's, of which a survey takes the lattice and the result words; no profiling event is recorded: sdfr_mesh_get_timings keeps
+// the last extraction's.
+static_assert(sizeof(sdfr_mesh_survey_result) == sizeof(MeshSurvey) && offsetof(sdfr_mesh_survey_result, active_lo) == offsetof(MeshSurvey, active_lo) &&
+		offsetof(sdfr_mesh_survey_result, near_hi) == offsetof(MeshSurvey, near_hi) && offsetof(sdfr_mesh_survey_result, face_active) == offsetof(MeshSurvey, face_active),
+	"sdfr_mesh_survey_result is the kernel's MeshSurvey");
+static_assert(sizeof(sdfr_mesh_fit_result) == sizeof(MeshFit) && offsetof(sdfr_mesh_fit_result, lo) == offsetof(MeshFit, lo) && offsetof(sdfr_mesh_fit_result, grid) == offsetof(MeshFit, grid) &&
+		offsetof(sdfr_mesh_fit_result, last) == offsetof(MeshFit, last) && SDFR_FIT_EMPTY == MESH_FIT_EMPTY && SDFR_FIT_FOUND == MESH_FIT_FOUND && SDFR_FIT_TOO_LARGE == MESH_FIT_TOO_LARGE,
+	"sdfr_mesh_fit_result is the loop's MeshFit");
+// one planned survey with the frame U on `stream`, read back into `out`
+static int survey_lattice(sdfr_renderer *r, const FrameU &U, const MeshSurveyPlan &p, float band, MeshSurvey &out, hipStream_t stream)
+{
+	Carving work({p.work[0], p.work[1]});
+	int rc = reserve_mesh_workspace(r, work, stream);
+	if (rc != SDFR_OK) return rc;
+	float *d_lattice = work.piece<float>(0);
+	MeshSurvey *d_survey = work.piece<MeshSurvey>(1);
+	rc = sample_lattice(r, U, p.lattice, d_lattice, stream);
+	if (rc != SDFR_OK) return rc;
+	SDFR_HIP(launch_mesh_survey(p.g, d_lattice, band, d_survey, stream));
+	SDFR_HIP(hipMemcpyAsync(&out, d_survey, sizeof out, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+	return release_large(r, r->mesh, stream);
+}
+
+int sdfr_mesh_survey(sdfr_renderer *r, const sdfr_mesh_grid *grid, float band, sdfr_mesh_survey_result *out)
+{
+	return guarded(r, [&]() -> int {
+		if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+		const MeshSurveyPlan p = plan_mesh_survey(reinterpret_cast<const MeshGrid *>(grid), band, out);
+		if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+		FrameU U;
+		hipStream_t stream;
+		int rc = begin_query(r, true, 1, 1, U, stream);
+		if (rc != SDFR_OK) return rc;
+		MeshSurvey s;
+		rc = survey_lattice(r, U, p, band, s, stream);
+		if (rc != SDFR_OK) return rc;
+		memcpy(out, &s, sizeof s);
+		return SDFR_OK;
+	});
+}
+
+int sdfr_mesh_fit(sdfr_renderer *r, const sdfr_mesh_grid *search, int levels, int margin, sdfr_mesh_fit_result *out)
+{
+	return guarded(r, [&]() -> int {
+		if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+		const MeshGrid *g = reinterpret_cast<const MeshGrid *>(search);
+		if (const char *error = plan_mesh_fit(g, levels, margin, out)) return fail(r, SDFR_ERR_INVALID_ARGUMENT, error);
+		FrameU U;
+		hipStream_t stream;
+		int rc = begin_query(r, true, 1, 1, U, stream);
+		if (rc != SDFR_OK) return rc;
+		MeshFit f;
+		rc = mesh_fit(*g, levels, margin, [&](const MeshGrid &level, float band, MeshSurvey &s) -> int {
+			const MeshSurveyPlan p = plan_mesh_survey(&level, band, &s); // (stands: the loop surveys no grid mesh_grid_ok refuses)
+			return p.status != QUERY_PLAN_OK ? fail(r, p.status, p.error) : survey_lattice(r, U, p, band, s, stream);
+		}, f);
+		if (rc != SDFR_OK) return rc;
+		memcpy(out, &f, sizeof f);
 		return SDFR_OK;
 	});
 }

@@ -82,6 +82,10 @@ hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *
 hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
 	uint32_t *indices, bool cells_only, hipStream_t stream);
 hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshSharpArgs &m, hipStream_t stream);
+// What the lattice holds (sdfr_mesh_survey.h; sdfr_mesh_survey): out, MESH_SURVEY_WORK_BYTES of device memory, is the survey of g, near
+// cells with `band`, followed by the words k_mesh_survey counted it in with integer atomics, each word in a page of its own.
+struct MeshSurvey;
+hipError_t launch_mesh_survey(const MeshGrid &g, const float *lattice, float band, MeshSurvey *out, hipStream_t stream);
 
 // The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
 // per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes

@@ -9,6 +9,7 @@
 // the phases are separate launches of one stream.  The output order (cells and lattice points by linear index) is the scan's.
 #include "sdfr_kernels.h"
 #include "sdfr_mesh.h"
+#include "sdfr_mesh_survey.h"
 #define SDFR_ATLAS_GEOMETRY_ONLY // the texel map alone: no scene is looked at here
 #include "sdfr_atlas.h"
 
@@ -165,6 +166,132 @@ hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint3
 	if (indices)
 		hipLaunchKernelGGL(k_mesh_emit_indices, dim3((points + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice,
 			cell_vertex, point_quad, indices);
+	return hipGetLastError();
+}
+
+// ---- what a lattice holds (sdfr_mesh_survey; the predicates: sdfr_mesh_survey.h) ----
+// One lane per lattice point, as k_mesh_classify: the point's quads, its inside flag, and the cell whose lowest corner it is.  Every
+// result is an integer.  A wave counts by ballot and popcount and takes the bounds of its cells by shuffles -- only a wave that holds a
+// near cell, an active one: most hold none --; its first lane leaves the wave's 10 counts and 12 bounds in LDS; then lane t of the block
+// adds up word t of the four waves and, if the block saw anything for that word, issues the one atomic: a 64-bit atomicAdd for a count,
+// atomicMin / atomicMax on 32 bits for a bound (agent scope, HIP's default).  Integer atomics: the order of arrival changes nothing.
+// While they are counted the 22 words lie MESH_SURVEY_WORD_STRIDE bytes apart, after the packed result they are gathered into at the
+// end (k_mesh_survey_pack): packed into the result's one 128-byte line, the atomics of all words and all blocks queued up behind each
+// other and the kernel took 2.5 times as long (profiles/mesh_survey_timing.txt).  k_mesh_survey_init sets them: lo = n, hi = -1.
+static_assert(offsetof(MeshSurvey, quads) == 8 && offsetof(MeshSurvey, near_cells) == 16 && offsetof(MeshSurvey, inside_points) == 24 &&
+		offsetof(MeshSurvey, active_lo) == 32 && offsetof(MeshSurvey, active_hi) == 44 && offsetof(MeshSurvey, near_lo) == 56 &&
+		offsetof(MeshSurvey, near_hi) == 68 && offsetof(MeshSurvey, face_active) == 80 && sizeof(MeshSurvey) == 128,
+	"the packed words: counts 0..3, bounds 0..11, counts 4..9");
+
+// word t of the survey while it is counted: 0 .. 9 the counts (64 bits), 10 .. 21 the bounds (32 bits), each in a page of its own
+// after the packed result at `out` (MESH_SURVEY_WORK_BYTES in all)
+__device__ __forceinline__ char *survey_word(MeshSurvey *out, int t) { return reinterpret_cast<char *>(out) + (size_t)MESH_SURVEY_WORD_STRIDE * (size_t)(1 + t); }
+
+__global__ void k_mesh_survey_init(MeshSurvey *__restrict__ out, MeshGrid g)
+{
+	const int t = (int)threadIdx.x;
+	if (blockIdx.x != 0) return;
+	if (t < MESH_SURVEY_COUNTS) *reinterpret_cast<int64_t *>(survey_word(out, t)) = 0;
+	else if (t < MESH_SURVEY_COUNTS + MESH_SURVEY_BOUNDS)
+	{
+		const int b = t - MESH_SURVEY_COUNTS;
+		*reinterpret_cast<int32_t *>(survey_word(out, t)) = (b / 3) % 2 == 0 ? g.n[b % 3] : -1;
+	}
+}
+__global__ void k_mesh_survey_pack(MeshSurvey *__restrict__ out)
+{
+	const int t = (int)threadIdx.x;
+	if (blockIdx.x != 0) return;
+	if (t < MESH_SURVEY_COUNTS) *(t < 4 ? &out->active_cells + t : &out->face_active[t - 4]) = *reinterpret_cast<const int64_t *>(survey_word(out, t));
+	else if (t < MESH_SURVEY_COUNTS + MESH_SURVEY_BOUNDS) out->active_lo[t - MESH_SURVEY_COUNTS] = *reinterpret_cast<const int32_t *>(survey_word(out, t));
+}
+
+__device__ __forceinline__ int wave_min(int v)
+{
+	for (int d = 32; d >= 1; d >>= 1)
+	{
+		const int o = __shfl_xor(v, d, 64);
+		v = o < v ? o : v;
+	}
+	return v;
+}
+__device__ __forceinline__ int wave_max(int v)
+{
+	for (int d = 32; d >= 1; d >>= 1)
+	{
+		const int o = __shfl_xor(v, d, 64);
+		v = o > v ? o : v;
+	}
+	return v;
+}
+
+__global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_survey(MeshGrid g, const float *__restrict__ lattice, float band, MeshSurvey *__restrict__ out)
+{
+	constexpr int WAVES = SDFR_MESH_BLOCK / 64;
+	__shared__ uint32_t wave_count[WAVES][MESH_SURVEY_COUNTS];
+	__shared__ int32_t wave_bound[WAVES][MESH_SURVEY_BOUNDS];
+	const uint32_t p = blockIdx.x * (uint32_t)SDFR_MESH_BLOCK + threadIdx.x;
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	// (no early return: every lane of the block takes part in the ballots, the shuffles and the barrier)
+	MeshSurveyPoint c = {};
+	int cell[3] = {0, 0, 0};
+	if (p < mesh_point_count(g))
+	{
+		point_coords(g, p, cell[0], cell[1], cell[2]);
+		c = mesh_survey_point(g, lattice, band, cell[0], cell[1], cell[2]);
+	}
+	const unsigned long long active = __ballot(c.active != 0u), near = __ballot(c.near != 0u);
+	uint32_t counts[MESH_SURVEY_COUNTS];
+	counts[0] = (uint32_t)__popcll(active);
+	counts[1] = (uint32_t)__popcll(__ballot((c.quads & 1u) != 0u)) + 2u * (uint32_t)__popcll(__ballot((c.quads & 2u) != 0u));
+	counts[2] = (uint32_t)__popcll(near);
+	counts[3] = (uint32_t)__popcll(__ballot(c.inside != 0u));
+	for (int f = 0; f < 6; ++f) counts[4 + f] = active ? (uint32_t)__popcll(__ballot(((c.faces >> f) & 1u) != 0u)) : 0u;
+	int32_t bounds[MESH_SURVEY_BOUNDS];
+	for (int a = 0; a < 3; ++a)
+	{
+		// (wave-uniform branches: `active` and `near` are the whole wave's)
+		bounds[a] = active ? wave_min(c.active ? cell[a] : g.n[a]) : g.n[a];
+		bounds[3 + a] = active ? wave_max(c.active ? cell[a] : -1) : -1;
+		bounds[6 + a] = near ? wave_min(c.near ? cell[a] : g.n[a]) : g.n[a];
+		bounds[9 + a] = near ? wave_max(c.near ? cell[a] : -1) : -1;
+	}
+	if (lane == 0u)
+	{
+		for (int t = 0; t < MESH_SURVEY_COUNTS; ++t) wave_count[wave][t] = counts[t];
+		for (int t = 0; t < MESH_SURVEY_BOUNDS; ++t) wave_bound[wave][t] = bounds[t];
+	}
+	__syncthreads();
+	const int t = (int)threadIdx.x;
+	if (t < MESH_SURVEY_COUNTS)
+	{
+		uint32_t sum = 0u;
+		for (int w = 0; w < WAVES; ++w) sum += wave_count[w][t];
+		if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(survey_word(out, t)), (unsigned long long)sum);
+	}
+	else if (t < MESH_SURVEY_COUNTS + MESH_SURVEY_BOUNDS)
+	{
+		const int b = t - MESH_SURVEY_COUNTS, a = b % 3;
+		const bool is_min = (b / 3) % 2 == 0;
+		int32_t v = wave_bound[0][b];
+		for (int w = 1; w < WAVES; ++w)
+		{
+			const int32_t o = wave_bound[w][b];
+			v = (is_min ? o < v : o > v) ? o : v;
+		}
+		int32_t *word = reinterpret_cast<int32_t *>(survey_word(out, t));
+		// (reading the word first, to send only a bound that would move it, was measured with the packed words and was slower: every
+		// block then reads the result, also those that saw nothing -- profiles/mesh_survey_timing.txt)
+		if (is_min ? v < g.n[a] : v >= 0) is_min ? atomicMin(word, v) : atomicMax(word, v);
+	}
+}
+
+hipError_t launch_mesh_survey(const MeshGrid &g, const float *lattice, float band, MeshSurvey *out, hipStream_t stream)
+{
+	const uint32_t points = mesh_point_count(g);
+	hipLaunchKernelGGL(k_mesh_survey_init, dim3(1), dim3(64), 0, stream, out, g);
+	hipLaunchKernelGGL(k_mesh_survey, dim3((points + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice, band, out);
+	hipLaunchKernelGGL(k_mesh_survey_pack, dim3(1), dim3(64), 0, stream, out);
 	return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 // sdfr_atlas_plan.h: mesh_impl (sdfr_api.cpp) carries the plan out, tests/test_mesh_plan_cpu.py checks it on a machine without a GPU.
 #pragma once
 #include "sdfr_mesh.h"
+#include "sdfr_mesh_survey.h"
 #include "sdfr_query_plan.h"
 
 namespace sdfr {
@@ -28,6 +29,18 @@ struct MeshPlan
 	size_t work[4]; // bytes of the workspace's pieces: the lattice, the cells' scan, the points' scan, both scans' block sums
 };
 
+// the launch that samples the grid's lattice, but `rows` and `out`
+inline LatticeArgs mesh_lattice_args(const MeshGrid &g)
+{
+	LatticeArgs la = {};
+	for (int a = 0; a < 3; ++a) la.origin[a] = g.origin[a];
+	la.cell = g.cell;
+	la.px = g.n[0] + 1;
+	la.py = g.n[1] + 1;
+	la.pz = g.n[2] + 1;
+	return la;
+}
+
 // The checks after the handle's and before the scene's, in the order their errors win.
 inline MeshPlan plan_mesh(const MeshRequest &c)
 {
@@ -40,18 +53,12 @@ inline MeshPlan plan_mesh(const MeshRequest &c)
 	if (!c.grid || !c.counts) return fail("null pointer");
 	if (!is_flag(c.on_host)) return fail("on_host must be 0 or 1");
 	const MeshGrid &g = *c.grid;
-	bool grid_ok = std::isfinite(g.cell) && g.cell > 0.f && std::isfinite(g.iso);
-	for (int a = 0; a < 3; ++a) grid_ok = grid_ok && std::isfinite(g.origin[a]) && g.n[a] >= 1 && g.n[a] <= 1024;
-	if (!grid_ok || (int64_t)(g.n[0] + 1) * (g.n[1] + 1) * (g.n[2] + 1) > (int64_t)1 << 30) return fail("bad mesh grid");
+	if (!mesh_grid_ok(g)) return fail("bad mesh grid");
 	if (c.vertex_capacity < 0 || c.triangle_capacity < 0) return fail("negative capacity");
 	if ((c.vertex_capacity > 0 && !c.positions) || (c.triangle_capacity > 0 && !c.indices)) return fail("null array with a capacity");
 
 	p.g = g;
-	for (int a = 0; a < 3; ++a) p.lattice.origin[a] = g.origin[a];
-	p.lattice.cell = g.cell;
-	p.lattice.px = g.n[0] + 1;
-	p.lattice.py = g.n[1] + 1;
-	p.lattice.pz = g.n[2] + 1;
+	p.lattice = mesh_lattice_args(g);
 	p.points = mesh_point_count(g);
 	p.cells = mesh_cell_count(g);
 	p.work[0] = p.points * 4;
@@ -79,6 +86,51 @@ inline MeshFill plan_mesh_fill(const MeshRequest &c, uint32_t vertices, uint32_t
 	f.bytes[1] = c.normals ? (size_t)vertices * 12 : 0;
 	f.bytes[2] = (size_t)f.triangles * 12;
 	return f;
+}
+
+// ---- sdfr_mesh_survey and sdfr_mesh_fit (include/sdfr.h; the predicates and the fit's loop: sdfr_mesh_survey.h) ---------------------------
+// The survey of one grid: the checks in the order their errors win -- null pointers, the grid (sdfr_mesh_extract's rule), the band --,
+// then the lattice launch and the workspace's two pieces: the lattice, and the result with the words it is counted in.
+struct MeshSurveyPlan
+{
+	int status; // QUERY_PLAN_*
+	const char *error;
+	MeshGrid g;
+	LatticeArgs lattice; // but `rows` and `out`
+	size_t points;
+	size_t work[2];
+};
+inline MeshSurveyPlan plan_mesh_survey(const MeshGrid *grid, float band, const void *out)
+{
+	MeshSurveyPlan p = {};
+	auto fail = [&p](const char *text) {
+		p.status = QUERY_PLAN_INVALID_ARGUMENT;
+		p.error = text;
+		return p;
+	};
+	if (!grid || !out) return fail("null pointer");
+	if (!mesh_grid_ok(*grid)) return fail("bad mesh grid");
+	if (!(std::isfinite(band) && band >= 0.f)) return fail("band must be finite and >= 0");
+	p.g = *grid;
+	p.lattice = mesh_lattice_args(p.g);
+	p.points = mesh_point_count(p.g);
+	p.work[0] = p.points * 4;
+	p.work[1] = MESH_SURVEY_WORK_BYTES;
+	return p;
+}
+
+// The arguments of a fit, in the order their errors win: null pointers; the search grid -- origin, cell and iso finite, cell > 0, 1 .. 2^20
+// cells per axis --; levels, 0 .. 10 with cell * 2^levels finite; margin, 0 .. 8.  -> null, or the text of the fault
+inline const char *plan_mesh_fit(const MeshGrid *search, int levels, int margin, const void *out)
+{
+	if (!search || !out) return "null pointer";
+	const MeshGrid &g = *search;
+	bool ok = std::isfinite(g.cell) && g.cell > 0.f && std::isfinite(g.iso);
+	for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(g.origin[a]) && g.n[a] >= 1 && g.n[a] <= MESH_FIT_MAX_CELLS;
+	if (!ok) return "bad search grid";
+	if (levels < 0 || levels > MESH_FIT_MAX_LEVELS || !std::isfinite(g.cell * (float)(1 << levels))) return "levels must be 0..10 and cell * 2^levels finite";
+	if (margin < 0 || margin > MESH_FIT_MAX_MARGIN) return "margin must be 0..8";
+	return nullptr;
 }
 
 } // namespace sdfr
