@@ -13,13 +13,10 @@
 // Everything else on the path is "parity unpinned" by the reference: the oracle is a
 // line-by-line restatement, self-checked with analytic known-answer tests.
 #include "driver.h"
+#include "frame_abi.h"
 #include "host.h"
 #include "postprocess.h"
-#include "scenes.h"
-#include "scenes2.h"
-#include "scenes3.h"
-#include "scenes4.h"
-#include "test_scenes.h"
+#include "scene_list.h"
 
 #include <atomic>
 #include <cstdio>
@@ -30,37 +27,28 @@
 
 using namespace orc;
 
-extern "C" {
-
-struct orc_frame
-{
-	float eye[3], front[3], right[3], top[3];
-	float stime;
-	int width, height;
-	int iter_count, bounce_count, ray_count, light_count;
-	float range;
-	int max_cost_default;
-	float debug_nx, debug_ny, debug_nz, debug_scale, debug_x, debug_y, debug_z, show_objects;
-	float scene_var[8];
-	int extension_lights; // 0..7, extension (SURVEY.md 8d cfg 5)
-	float extension_marble_reflection; // 0 = reference, extension (SURVEY.md 8d cfg 3 as worded)
-	float dist_eps, grad_eps, reflect_eps, refract_eps, shadow_eps; // pshader_sdf.hlsl:31-35
-};
-
-} // extern "C"
-
 namespace {
 
+// the scenes of scene_list.h, the reference's first
 struct SceneEntry
 {
 	const char *name;
-	// VAR_ tags of the scene file in source order (data restated from the scene's HLSL;
-	// e.g. scenes/sdf_scene_lense.hlsl:29-31,85)
-	const char *var_decls;
-	// scene variable names in the order Frame::scene_var uses
-	std::vector<std::string> var_order;
 	float4 (*pixel)(const Frame &, int, int, PixelStats &);
 };
+#define X(name, S) {name, &ps_main<S>},
+const SceneEntry k_scenes[] = {ORC_REFERENCE_SCENES(X) ORC_TEST_SCENES(X)};
+#undef X
+#define X(name, S) +1
+const int k_reference_scenes = 0 ORC_REFERENCE_SCENES(X);
+#undef X
+
+const SceneEntry *find_scene(const char *name)
+{
+	for (const SceneEntry &s : k_scenes)
+		if (strcmp(s.name, name) == 0)
+			return &s;
+	return nullptr;
+}
 
 // VAR_ tags of the driver shader (pshader_sdf.hlsl:88-90,97-99,108,142)
 const char *driver_var_decls =
@@ -69,117 +57,60 @@ const char *driver_var_decls =
 	"VAR_debug_ny(min = -1, max = +1, step = 0.02) VAR_debug_nz(min = -1, max = +1, step = 0.02) "
 	"VAR_show_objects(min = 0, max = 1, step = 1, start = 1) VAR_debug_scale(min = 0.005, max = 2, step = 0.005, start = 0.2)";
 
-const std::vector<SceneEntry> &scenes()
+// the scenes that declare variables; a scene that is not here declares none
+struct SceneVars
 {
-	static const std::vector<SceneEntry> table = {
-		{"fast_sphere", "", {}, &ps_main<SceneFastSphere>},
-		{"cube_sea", "", {}, &ps_main<SceneCubeSea>},
-		{"labyrinth", "", {}, &ps_main<SceneLabyrinth>},
-		{"fractal", "", {}, &ps_main<SceneFractal>},
+	const char *name;
+	// VAR_ tags of the scene file in source order (data restated from the scene's HLSL;
+	// e.g. scenes/sdf_scene_lense.hlsl:29-31,85)
+	const char *var_decls;
+	// scene variable names in the order Frame::scene_var uses
+	std::vector<std::string> var_order;
+};
+
+const SceneVars &scene_vars(const char *name)
+{
+	static const std::vector<SceneVars> table = {
 		{"lense",
 			"VAR_xpos(min = -4, max = 4, step = 0.1) VAR_ypos(min = -4, max = 4, step = 0.1) "
 			"VAR_zpos(min = 0, max = 25, step = 0.1) VAR_mixing(min = 0, max = 1, step = 0.05)",
-			{"xpos", "ypos", "zpos", "mixing"}, &ps_main<SceneLense>},
-		{"gems", "", {}, &ps_main<SceneGems>},
-		{"light_shadows", "", {}, &ps_main<SceneLightShadows>},
+			{"xpos", "ypos", "zpos", "mixing"}},
 		{"cube",
 			"VAR_size(min = 0.2, max = 2, start = 1, step = 0.2) VAR_xpos(min = -2, max = 2, start = 0, step = 0.1) "
 			"VAR_ypos(min = -2, max = 2, start = 0, step = 0.1) VAR_zpos(min = -2, max = 2, start = 0, step = 0.1) "
 			"VAR_red(min = 0, max = 1, start = 0.9, step = 0.05) VAR_green(min = 0, max = 1, start = 0.7, step = 0.05) "
 			"VAR_blue(min = 0, max = 1, start = 0.2, step = 0.05)",
-			{"size", "xpos", "ypos", "zpos", "red", "green", "blue"}, &ps_main<SceneCube>},
-		{"gyroid", "", {}, &ps_main<SceneGyroid>},
-		{"basic_transparency", "", {}, &ps_main<SceneBasicTransparency>},
-		{"basic_clouds", "VAR_offset(min = -5, max = 5, step = 0.05)", {"offset"}, &ps_main<SceneBasicClouds>},
+			{"size", "xpos", "ypos", "zpos", "red", "green", "blue"}},
+		{"basic_clouds", "VAR_offset(min = -5, max = 5, step = 0.05)", {"offset"}},
 		{"coordinate_material",
 			"VAR_boxoffset(min = 0, max = 2, step = 0.1, start = 2) VAR_spherical(min = 0, max = 1, step = 1, start = 0) "
 			"VAR_thres(min=0,max=1,step=0.05, start=0.4)",
-			{"boxoffset", "spherical", "thres"}, &ps_main<SceneCoordinateMaterial>},
-		{"distortion", "", {}, &ps_main<SceneDistortion>},
-		{"table", "", {}, &ps_main<SceneTable>},
-		{"sierpinski", "", {}, &ps_main<SceneSierpinski>},
+			{"boxoffset", "spherical", "thres"}},
 		{"neon",
 			"VAR_r1(min = 0.2, max = 2, start = 1) VAR_r2(min = 0.005, max = 0.1, start = 0.01) VAR_spacing(min = 0.01, max = 0.2, start = 0.1) "
 			"VAR_red(min = 0, max = 3, start = 0.1, step = 0.05) VAR_green(min = 0, max = 3, start = 1.0, step = 0.05) "
 			"VAR_blue(min = 0, max = 3, start = 0.2, step = 0.05)",
-			{"r1", "r2", "spacing", "red", "green", "blue"}, &ps_main<SceneNeon>},
-		{"fractal2", "VAR_slider(min = -5, max = 5, step = 0.01, start = 0)", {"slider"}, &ps_main<SceneFractal2>},
-		{"shell", "", {}, &ps_main<SceneShell>},
-		{"spiral", "", {}, &ps_main<SceneSpiral>},
-		{"terrain", "VAR_levels(min=1, max=10, step=1, start=2)", {"levels"}, &ps_main<SceneTerrain>},
+			{"r1", "r2", "spacing", "red", "green", "blue"}},
+		{"fractal2", "VAR_slider(min = -5, max = 5, step = 0.01, start = 0)", {"slider"}},
+		{"terrain", "VAR_levels(min=1, max=10, step=1, start=2)", {"levels"}},
 		{"tiling",
 			"VAR_m1(min = -1, max = 3, step = 0.1, start = 1) VAR_m2(min = -1, max = 3, step = 0.1, start = 0) "
 			"VAR_width(min = 0.1, max = 0.5, step = 0.05, start = 0.4) VAR_run_length(min = 1, max = 10, step = 1, start = 4) "
 			"VAR_run_flip(min = 1, max = 10, step = 1, start = 2) VAR_flip_chance(min = 0, max = 1, steps = 0.05) "
 			"VAR_truchet_width(min = 0, max = 0.2, step = 0.01)",
-			{"m1", "m2", "width", "run_length", "run_flip", "flip_chance", "truchet_width"}, &ps_main<SceneTiling>},
-		{"tree", "", {}, &ps_main<SceneTree>},
-	};
-	return table;
-}
-
-// scenes that exist for tests only (test_scenes.h): found by name, not part of the reference's list
-const std::vector<SceneEntry> &test_scenes()
-{
-	static const std::vector<SceneEntry> table = {
-		{"debug_materials", "", {}, &ps_main<SceneDebugMaterials>},
-		{"light_shadows_backwards", "", {}, &ps_main<SceneLightShadowsT<true>>}, // scenes.h: for Images/multi-lights.png only
-		{"normal_test", "VAR_round(min = 0.0001, max = 0.05, start = 0.01) VAR_analytic(min = 0, max = 1, step = 1, start = 1)", {"round", "analytic"},
-			&ps_main<SceneNormalTest>},
+			{"m1", "m2", "width", "run_length", "run_flip", "flip_chance", "truchet_width"}},
+		{"normal_test", "VAR_round(min = 0.0001, max = 0.05, start = 0.01) VAR_analytic(min = 0, max = 1, step = 1, start = 1)", {"round", "analytic"}},
 		// the VAR_ tags of sdf_playground_amd/scenes/noise_lod.hlsl and dialect_tour.hlsl, in the order of the text
 		{"noise_lod", "VAR_lod(min = 0, max = 40, start = 9, step = 0.5) VAR_freq(min = 0.5, max = 8, start = 3) VAR_bump(min = 0, max = 0.05, start = 0.02)",
-			{"lod", "freq", "bump"}, &ps_main<SceneNoiseLod>},
+			{"lod", "freq", "bump"}},
 		{"dialect_tour", "VAR_spin(min = -2, max = 2, step = 0.1, start = 0.4) VAR_reach(min = 1, max = 3) VAR_blend(min = 0.01, max = 0.3, start = 0.08, steps = 7) "
-			"VAR_shine() VAR_shine(min = 0, max = 1, start = 0.3, step = 0.05)", {"spin", "reach", "blend", "shine"}, &ps_main<SceneDialectTour>},
+			"VAR_shine() VAR_shine(min = 0, max = 1, start = 0.3, step = 0.05)", {"spin", "reach", "blend", "shine"}},
 	};
-	return table;
-}
-
-const SceneEntry *find_scene(const char *name)
-{
-	for (const auto &s : scenes())
-		if (strcmp(s.name, name) == 0)
-			return &s;
-	for (const auto &s : test_scenes())
-		if (strcmp(s.name, name) == 0)
-			return &s;
-	return nullptr;
-}
-
-Frame to_frame(const orc_frame &f)
-{
-	Frame F;
-	F.eye = float3(f.eye[0], f.eye[1], f.eye[2]);
-	F.front_vec = float3(f.front[0], f.front[1], f.front[2]);
-	F.right_vec = float3(f.right[0], f.right[1], f.right[2]);
-	F.top_vec = float3(f.top[0], f.top[1], f.top[2]);
-	F.stime = f.stime;
-	F.width = f.width;
-	F.height = f.height;
-	F.iter_count = f.iter_count;
-	F.bounce_count = f.bounce_count;
-	F.ray_count = f.ray_count;
-	F.light_count = f.light_count;
-	F.range = f.range;
-	F.max_cost_default = (uint)f.max_cost_default;
-	F.debug_nx = f.debug_nx;
-	F.debug_ny = f.debug_ny;
-	F.debug_nz = f.debug_nz;
-	F.debug_scale = f.debug_scale;
-	F.debug_x = f.debug_x;
-	F.debug_y = f.debug_y;
-	F.debug_z = f.debug_z;
-	F.show_objects = f.show_objects;
-	for (int i = 0; i < MAX_SCENE_VARS; ++i)
-		F.scene_var[i] = f.scene_var[i];
-	F.extension_lights = f.extension_lights < 0 ? 0 : (f.extension_lights > 7 ? 7 : f.extension_lights);
-	F.extension_marble_reflection = f.extension_marble_reflection;
-	F.dist_eps = f.dist_eps;
-	F.grad_eps = f.grad_eps;
-	F.reflect_eps = f.reflect_eps;
-	F.refract_eps = f.refract_eps;
-	F.shadow_eps = f.shadow_eps;
-	return F;
+	static const SceneVars none = {"", "", {}};
+	for (const SceneVars &v : table)
+		if (strcmp(v.name, name) == 0)
+			return v;
+	return none;
 }
 
 int copy_out(const std::string &s, char *buf, int cap)
@@ -194,8 +125,8 @@ int copy_out(const std::string &s, char *buf, int cap)
 
 extern "C" {
 
-int orc_scene_count() { return (int)scenes().size(); }
-const char *orc_scene_name(int i) { return (i >= 0 && i < (int)scenes().size()) ? scenes()[i].name : nullptr; }
+int orc_scene_count() { return k_reference_scenes; }
+const char *orc_scene_name(int i) { return (i >= 0 && i < k_reference_scenes) ? k_scenes[i].name : nullptr; }
 
 // Variable table of a scene exactly as ShaderVariableManager would build it: driver
 // tags + scene tags parsed, std::map order.  Output: one line per variable
@@ -203,9 +134,9 @@ const char *orc_scene_name(int i) { return (i >= 0 && i < (int)scenes().size()) 
 // orc_frame.scene_var, or -1 for the driver's own variables).
 int orc_var_table(const char *scene, char *buf, int cap)
 {
-	const SceneEntry *s = find_scene(scene);
-	if (!s)
+	if (!find_scene(scene))
 		return -1;
+	const SceneVars *s = &scene_vars(scene);
 	host::VariableMap vars;
 	std::string text = std::string(driver_var_decls) + " " + s->var_decls;
 	if (!host::parseVariables(text, vars))
@@ -304,13 +235,7 @@ int orc_render(const char *scene, const orc_frame *frame, float *out_rgba, unsig
 		return -2;
 	if (!(frame->dist_eps > 0.f) || !(frame->grad_eps > 0.f) || !(frame->reflect_eps >= 0.f) || !(frame->refract_eps >= 0.f) || !(frame->shadow_eps >= 0.f))
 		return -3; // a frame that was not made by default_frame
-	const Frame F = to_frame(*frame);
-	// the driver's epsilons (sdf_lib.h): set before the threads start
-	dist_eps = F.dist_eps;
-	grad_eps = F.grad_eps;
-	reflect_eps = F.reflect_eps;
-	refract_eps = F.refract_eps;
-	shadow_eps = F.shadow_eps;
+	const Frame F = enter_frame(*frame);
 	if (nthreads < 1)
 		nthreads = 1;
 	std::atomic<int> next_row(0);

@@ -1,6 +1,6 @@
 // tests/cpp/lighting_host.cpp -- TEST-ONLY: the library's lighting queries (sdf_playground_amd/csrc/sdfr_lighting.h) compiled for the
 // CPU, as surface_host.cpp compiles the surface queries, so that the CPU test tier can compare them with the oracle's definition
-// (lighting_oracle.cpp) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene
+// (lighting_oracle.h) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene
 // with -DSDFR_HLSL_SCENE_FILE="<generated file>".  The product never loads this.
 #include "sdfr_hostframe.h"
 #include "sdfr_lighting.h"

@@ -1,6 +1,6 @@
 // tests/cpp/occlusion_host.cpp -- TEST-ONLY: the library's occlusion queries (sdf_playground_amd/csrc/sdfr_occlusion.h) compiled for
 // the CPU, as surface_host.cpp compiles the surface queries, so that the CPU test tier can compare them with the oracle's definition
-// (occlusion_oracle.cpp) bit for bit without a GPU.  An item is done as the kernel's wave does it: the validity test, then lane k's
+// (occlusion_oracle.h) bit for bit without a GPU.  An item is done as the kernel's wave does it: the validity test, then lane k's
 // ray for k = 0..63, the hit flags gathered into the mask (the kernel's ballot).  Built once for the scenes compiled ahead of time,
 // and once per run-time scene with -DSDFR_HLSL_SCENE_FILE="<generated file>".  The product never loads this.
 #include "sdfr_hostframe.h"

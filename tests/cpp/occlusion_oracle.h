@@ -1,9 +1,10 @@
-// tests/cpp/occlusion_oracle.cpp -- TEST-ONLY: the occlusion record of include/sdfr.h (sdfr_query_occlusion, sdfr_hit_occlusion)
-// defined with the CPU oracle's ray query (query_oracle.cpp: march_ray of oracle/driver.h).  The frame and the rays are written
+// tests/cpp/occlusion_oracle.h -- TEST-ONLY: the occlusion record of include/sdfr.h (sdfr_query_occlusion, sdfr_hit_occlusion)
+// defined with the CPU oracle's ray query (query_oracle.h: ray_turn of oracle/driver.h).  The frame and the rays are written
 // here from the definition in include/sdfr.h, in plain float arithmetic (built with -ffp-contract=off), not with the library's
-// sdfr_occlusion.h; only the direction table, which IS the definition, is shared.  Built by tests/occlusion_util.py; the product
-// never loads it.
-#include "query_oracle.cpp"
+// sdfr_occlusion.h; only the direction table, which IS the definition, is shared.  Part of record_oracle.cpp; the product never
+// loads it.
+#pragma once
+#include "record_oracle.h"
 
 #include <cmath>
 
@@ -57,8 +58,8 @@ void occlusion_item(const Entry *e, const Frame &F, const float *p, const float 
 			const float s01 = m0 + m1;
 			dir[c] = s01 + m2;
 		}
-		uint32_t rec[12];
-		e->rays(F, float3(origin[0], origin[1], origin[2]), float3(dir[0], dir[1], dir[2]), real(radius), float3(real(0.f)), float3(real(0.f)), rec);
+		uint32_t rec[HIT_WORDS];
+		e->rays(F, float3(origin[0], origin[1], origin[2]), float3(dir[0], dir[1], dir[2]), real(radius), no_offset, no_offset, rec);
 		if (rec[10] == 1u) mask |= (uint64_t)1 << k;
 	}
 	out[0] = (uint32_t)(mask & 0xffffffffu);
@@ -71,11 +72,11 @@ void occlusion_item(const Entry *e, const Frame &F, const float *p, const float 
 
 extern "C" {
 
-int oo_points(const char *scene, const qo_frame *f, int n, const float *points, const float *normals, float bias, float radius, uint32_t *out)
+int oo_points(const char *scene, const orc_frame *f, int n, const float *points, const float *normals, float bias, float radius, uint32_t *out)
 {
 	const Entry *e = find(scene);
 	if (!e) return -1;
-	const Frame F = to_frame(*f);
+	const Frame F = enter_frame(*f);
 	parallel_items(64 * n, [&](int a, int b) { // (over rays: an item is 64 of them)
 		for (int i = (a + 63) / 64; i < (b + 63) / 64; ++i) occlusion_item(e, F, points + 3 * i, normals + 3 * i, bias, radius, out + 4 * i);
 	});
@@ -83,11 +84,11 @@ int oo_points(const char *scene, const qo_frame *f, int n, const float *points, 
 }
 
 // items from hit records [n][12]: pos and normal where hit == 1, else valid = hit (anything but 0: -1)
-int oo_hits(const char *scene, const qo_frame *f, int n, const uint32_t *hits, float bias, float radius, uint32_t *out)
+int oo_hits(const char *scene, const orc_frame *f, int n, const uint32_t *hits, float bias, float radius, uint32_t *out)
 {
 	const Entry *e = find(scene);
 	if (!e) return -1;
-	const Frame F = to_frame(*f);
+	const Frame F = enter_frame(*f);
 	parallel_items(64 * n, [&](int a, int b) {
 		for (int i = (a + 63) / 64; i < (b + 63) / 64; ++i)
 		{

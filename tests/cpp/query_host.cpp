@@ -1,6 +1,6 @@
 // tests/cpp/query_host.cpp -- TEST-ONLY: the library's scene queries (sdf_playground_amd/csrc/sdfr_query.h) compiled for the CPU,
 // as tests/hostsim compiles the per-pixel pipeline, so that the CPU test tier can compare them with the oracle's definitions
-// (query_oracle.cpp) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene with
+// (query_oracle.h) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene with
 // -DSDFR_HLSL_SCENE_FILE="<generated file>" (host_common.h).  The product never loads this.
 #include "sdfr_hostframe.h"
 #include "sdfr_query.h"

@@ -1,6 +1,6 @@
 // tests/cpp/surface_host.cpp -- TEST-ONLY: the library's surface queries (sdf_playground_amd/csrc/sdfr_surface.h) compiled for the
 // CPU, as query_host.cpp compiles the scene queries, so that the CPU test tier can compare them with the oracle's definition
-// (surface_oracle.cpp) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene
+// (surface_oracle.h) bit for bit without a GPU.  Built once for the scenes compiled ahead of time, and once per run-time scene
 // with -DSDFR_HLSL_SCENE_FILE="<generated file>".  The product never loads this.
 #include "sdfr_hostframe.h"
 #include "sdfr_surface.h"

@@ -1,5 +1,5 @@
 """Shared by the lighting tests (test_lighting_cpu.py, test_gpu_lighting.py): the oracle's definition of the lighting records
-(tests/cpp/lighting_oracle.cpp), the library's lighting functions built for the CPU (tests/cpp/lighting_host.cpp), the conditions
+(tests/cpp/lighting_oracle.h), the library's lighting functions built for the CPU (tests/cpp/lighting_host.cpp), the conditions
 under which `lit` is the renderer's pixel, and the sums recomputed from the light samples.  Frames, samples and the bit comparison
 are query_util's, the mesh rays surface_util's.  Test infrastructure: the product never imports this."""
 import ctypes
@@ -17,7 +17,7 @@ UNUSED, NO_CHAIN, BLOCKED, ESCAPED = 0, 1, 2, 3
 
 
 def oracle_lib():
-    L = qu.build_oracle_lib("lighting_oracle", ["lighting_oracle.cpp", "query_oracle.cpp"])
+    L = qu.build_oracle_lib()
     vp = ctypes.c_void_p
     L.lo_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp, vp, vp]
     L.lo_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp, vp]

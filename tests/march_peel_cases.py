@@ -70,7 +70,7 @@ def reference(case, iter_count):
 
 
 def _rewinds_after_the_fourth(case):
-    """pixels whose primary ray rewinds at its fifth to twelfth sample, from the oracle's own march (tests/cpp/query_oracle.cpp: march_ray through
+    """pixels whose primary ray rewinds at its fifth to twelfth sample, from the oracle's own march (tests/cpp/query_oracle.h: march_ray through
     the pixel, which leaves the distance it reached): the three counters do not show a rewind, the distance does -- between the iteration
     limits K - 1 and K it goes back only if the K-th sample was taken back, the ray ended by neither limit's run"""
     import query_util as qu

@@ -1,9 +1,8 @@
 """Shared by the occlusion tests (test_occlusion_cpu.py, test_gpu_occlusion.py): the oracle's definition of the occlusion record
-(tests/cpp/occlusion_oracle.cpp), the library's occlusion functions built for the CPU (tests/cpp/occlusion_host.cpp), the items the
+(tests/cpp/occlusion_oracle.h), the library's occlusion functions built for the CPU (tests/cpp/occlusion_host.cpp), the items the
 tests ask about and a scene whose answer is known without either.  Frames, ray samples and the bit comparison are query_util's.
 Test infrastructure: the product never imports this."""
 import ctypes
-import os
 
 import numpy as np
 
@@ -48,7 +47,7 @@ float3 map_background(float3 dir, uint iter_count)
 """
 
 def oracle_lib():
-    L = qu.build_oracle_lib("occlusion_oracle", ["occlusion_oracle.cpp", "query_oracle.cpp"], (qu.ORACLE, qu.CSRC), [os.path.join(qu.CSRC, "sdfr_occlusion_dirs.h")])
+    L = qu.build_oracle_lib()
     vp, cf = ctypes.c_void_p, ctypes.c_float
     L.oo_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, cf, cf, vp]
     L.oo_hits.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, cf, cf, vp]

@@ -1,7 +1,8 @@
 """Shared by the query tests (test_query_cpu.py, test_gpu_query.py): the oracle's definitions of the three scene queries
-(tests/cpp/query_oracle.cpp), the library's query functions built for the CPU (tests/cpp/query_host.cpp), the frames and the
+(tests/cpp/query_oracle.h), the library's query functions built for the CPU (tests/cpp/query_host.cpp), the frames and the
 seeded sample sets, and the bit comparison.  Test infrastructure: the product never imports this."""
 import ctypes
+import glob
 import os
 import sys
 
@@ -40,12 +41,13 @@ def build_lib(name, source, flags=(), deps=()):
     return cppbuild.compile(os.path.join(BUILD, "lib%s.so" % name), [os.path.join(HERE, "cpp", source)], deps, FLAGS + list(flags))
 
 
-def build_oracle_lib(name, sources, includes=(ORACLE,), more_deps=()):
-    """lib<name>.so of the oracle's definitions: sources[0] (tests/cpp) compiled with `includes`; stale when a source, an oracle header or
-    one of more_deps is newer"""
+def build_oracle_lib():
+    """librecord_oracle.so, the one library of the oracle's definitions (the qo_, so_, lo_ and oo_ entry points): tests/cpp/record_oracle.cpp
+    over its headers, the oracle's and the library's direction table; stale when one of them is newer"""
+    name = "record_oracle"
     if name not in _libs:
-        deps = [os.path.join(HERE, "cpp", f) for f in sources[1:]] + list(more_deps) + cppbuild.oracle_headers()
-        _libs[name] = ctypes.CDLL(build_lib(name, sources[0], ["-I" + d for d in includes], deps))
+        deps = sorted(glob.glob(os.path.join(HERE, "cpp", "*_oracle.h"))) + [os.path.join(CSRC, "sdfr_occlusion_dirs.h")] + cppbuild.oracle_headers()
+        _libs[name] = ctypes.CDLL(build_lib(name, name + ".cpp", ["-I" + ORACLE, "-I" + CSRC], deps))
         assert _libs[name].qo_frame_size() == ctypes.sizeof(po.OrcFrame)
     return _libs[name]
 
@@ -72,7 +74,7 @@ def build_host_lib(name, source, scene, text=None):
 
 
 def oracle_lib():
-    L = build_oracle_lib("query_oracle", ["query_oracle.cpp"])
+    L = build_oracle_lib()
     vp = ctypes.c_void_p
     L.qo_points.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]
     L.qo_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp]

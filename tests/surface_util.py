@@ -1,5 +1,5 @@
 """Shared by the surface tests (test_surface_cpu.py, test_gpu_surface.py): the oracle's definition of the surface record
-(tests/cpp/surface_oracle.cpp), the library's surface functions built for the CPU (tests/cpp/surface_host.cpp), and the host-made
+(tests/cpp/surface_oracle.h), the library's surface functions built for the CPU (tests/cpp/surface_host.cpp), and the host-made
 rays towards mesh vertices.  Frames, samples and the bit comparison are query_util's.  Test infrastructure: the product never
 imports this."""
 import ctypes
@@ -12,7 +12,7 @@ HIT_WORDS = qu.HIT_WORDS
 SURFACE_WORDS = 32
 
 def oracle_lib():
-    L = qu.build_oracle_lib("surface_oracle", ["surface_oracle.cpp", "query_oracle.cpp"])
+    L = qu.build_oracle_lib()
     vp = ctypes.c_void_p
     L.so_rays.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, ctypes.c_float, vp, vp]
     L.so_pick.argtypes = [ctypes.c_char_p, vp, ctypes.c_int, vp, vp, vp]

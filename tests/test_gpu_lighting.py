@@ -1,5 +1,5 @@
 """GPU tier of the lighting queries (sdfr_query_ray_lighting, sdfr_pick_lighting, sdfr_mesh_lighting) through libsdfr.so: bit for
-bit against the oracle's definition of the records (tests/cpp/lighting_oracle.cpp) for every scene compiled ahead of time and the
+bit against the oracle's definition of the records (tests/cpp/lighting_oracle.h) for every scene compiled ahead of time and the
 run-time scenes with an oracle twin, host and device memory; their hit records against the ray query's and the pick's; the whole
 frame (no pixel list, 8 x 8 tiles) against the pixel list; step shortcuts on against off; small and awkward sizes, the word-store
 path, with and without the light samples, argument checks; no side effects on rendering; one handle across scene changes; the mesh

@@ -1,5 +1,5 @@
 """GPU tier of the occlusion queries (sdfr_query_occlusion, sdfr_hit_occlusion) through libsdfr.so: bit for bit against the oracle's
-definition of the record (tests/cpp/occlusion_oracle.cpp) for every scene compiled ahead of time and two run-time scenes, host and
+definition of the record (tests/cpp/occlusion_oracle.h) for every scene compiled ahead of time and two run-time scenes, host and
 device memory, both entries, the hits of sdfr_pick and sdfr_pick_surfaces fed back on the device; small sizes, the word-store path
 and a hit array off 16-byte alignment; the debug kernel variant; step shortcuts; a scene whose answer is known without the oracle;
 the mesh with occlusion; argument checks; no side effects on rendering; one handle across scene changes; two frames in flight."""

@@ -1,5 +1,5 @@
 """GPU tier of the scene queries (sdfr_query_distance, sdfr_query_rays, sdfr_pick) through libsdfr.so: bit for bit against the
-oracle's definitions (tests/cpp/query_oracle.cpp) for every scene compiled ahead of time and the run-time scenes with an oracle
+oracle's definitions (tests/cpp/query_oracle.h) for every scene compiled ahead of time and the run-time scenes with an oracle
 twin, host and device memory; the run-time scenes' lazily compiled query module; one handle going from a built-in scene to a
 run-time one and back through every entry point that launches the loaded scene; step shortcuts; agreement with the renderer's own
 primary rays; no side effects on rendering; sizes and argument checks."""

@@ -1,5 +1,5 @@
 """GPU tier of the surface queries (sdfr_query_ray_surfaces, sdfr_pick_surfaces, sdfr_mesh_surfaces) through libsdfr.so: bit for
-bit against the oracle's definition of the record (tests/cpp/surface_oracle.cpp) for every scene compiled ahead of time and the
+bit against the oracle's definition of the record (tests/cpp/surface_oracle.h) for every scene compiled ahead of time and the
 run-time scenes with an oracle twin, host and device memory; their hit records against the ray query's and the pick's; the whole
 frame (no pixel list, 8 x 8 tiles) against the pixel list; the mesh with surfaces against the rays made on the host; small and
 awkward sizes, the word-store path, argument checks; no side effects on rendering; one handle across scene changes; and the

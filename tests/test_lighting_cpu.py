@@ -1,6 +1,6 @@
 """CPU tier of the lighting queries (sdfr_query_ray_lighting, sdfr_pick_lighting, sdfr_mesh_lighting): the library's lighting
 functions (sdf_playground_amd/csrc/sdfr_lighting.h) built for the CPU (tests/cpp/lighting_host.cpp) against the oracle's definition
-of the records (tests/cpp/lighting_oracle.cpp), bit for bit -- a NaN compares as "is a NaN" --, for every scene compiled ahead of
+of the records (tests/cpp/lighting_oracle.h), bit for bit -- a NaN compares as "is a NaN" --, for every scene compiled ahead of
 time and the run-time scenes with an oracle twin, with step shortcuts off and on; the definition itself against the oracle's driver,
 pixel for pixel, where sdfr_lighting.lit is defined to be the pixel; the records' own promises; and the layouts against the Python
 mirrors."""

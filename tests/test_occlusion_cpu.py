@@ -1,6 +1,6 @@
 """CPU tier of the occlusion queries (sdfr_query_occlusion, sdfr_hit_occlusion): the library's occlusion functions
 (sdf_playground_amd/csrc/sdfr_occlusion.h) built for the CPU (tests/cpp/occlusion_host.cpp) against the oracle's definition of the
-record (tests/cpp/occlusion_oracle.cpp), bit for bit on all four words, for every scene compiled ahead of time and the run-time
+record (tests/cpp/occlusion_oracle.h), bit for bit on all four words, for every scene compiled ahead of time and the run-time
 scenes with an oracle twin; the direction table; an answer known without the oracle; sdfr_occlusion's layout against the Python
 mirror OCCLUSION_DTYPE; and the export helpers."""
 import os

@@ -1,6 +1,6 @@
 """CPU tier of the scene queries (sdfr_query_distance, sdfr_query_rays, sdfr_pick): the library's query functions
 (sdf_playground_amd/csrc/sdfr_query.h) built for the CPU (tests/cpp/query_host.cpp) against the oracle's definitions of the three
-queries (tests/cpp/query_oracle.cpp), bit for bit, for every scene compiled ahead of time and the run-time scenes with an oracle
+queries (tests/cpp/query_oracle.h), bit for bit, for every scene compiled ahead of time and the run-time scenes with an oracle
 twin; and sdfr_hit's layout against the Python mirror HIT_DTYPE."""
 import os
 import subprocess

@@ -1,6 +1,6 @@
 """CPU tier of the surface queries (sdfr_query_ray_surfaces, sdfr_pick_surfaces, sdfr_mesh_surfaces): the library's surface
 functions (sdf_playground_amd/csrc/sdfr_surface.h) built for the CPU (tests/cpp/surface_host.cpp) against the oracle's definition
-of the record (tests/cpp/surface_oracle.cpp), bit for bit -- a NaN compares as "is a NaN" --, for every scene compiled ahead of time
+of the record (tests/cpp/surface_oracle.h), bit for bit -- a NaN compares as "is a NaN" --, for every scene compiled ahead of time
 and the run-time scenes with an oracle twin; and sdfr_surface's layout against the Python mirror SURFACE_DTYPE."""
 import os
 import subprocess
