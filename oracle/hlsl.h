@@ -38,6 +38,34 @@ struct Census
 	unsigned long long rcp_out_of_domain;
 };
 inline Census &census() { static thread_local Census c = {0, 0, 0, 0, 0, 0}; return c; }
+// The arguments the scenes feed to the elementary functions of detmath.h, whose accuracy is stated on a domain
+// (tests/golden/math_accuracy.json): per function the extremes of the finite arguments and the count of the others.
+// sin and cos share one record (|argument|); pow records the product y * log2 x that its exp2 receives.
+struct ArgRange
+{
+	float lo, hi;
+	unsigned long long calls, nonfinite;
+	void reset() { lo = 3.402823466e+38f; hi = -3.402823466e+38f; calls = nonfinite = 0; }
+	void see(float a)
+	{
+		calls++;
+		if (a != a || fabsf(a) > 3.402823466e+38f) { nonfinite++; return; }
+		if (a < lo) lo = a;
+		if (a > hi) hi = a;
+	}
+};
+struct MathCensus
+{
+	ArgRange sincos, exp2, log2, pow;
+	void reset() { sincos.reset(); exp2.reset(); log2.reset(); pow.reset(); }
+};
+inline MathCensus &math_census()
+{
+	static thread_local MathCensus c;
+	static thread_local bool fresh = true;
+	if (fresh) { c.reset(); fresh = false; }
+	return c;
+}
 inline void census_check_sqrt(float a)
 {
 	uint32_t u = dm::f2u(a);
@@ -86,6 +114,10 @@ inline void census_check_raydiv(float a, float c)
 #define ORC_CHECK_RCP(a) census_check_rcp(a)
 #define ORC_CHECK_PLANE(a, c) census_check_plane(a, c)
 #define ORC_CHECK_RAYDIV(a, c) census_check_raydiv(a, c)
+#define ORC_SEE_SINCOS(a) math_census().sincos.see(fabsf(a))
+#define ORC_SEE_EXP2(a) math_census().exp2.see(a)
+#define ORC_SEE_LOG2(a) math_census().log2.see(a)
+#define ORC_SEE_POW(x, y) math_census().pow.see((y) * dm::log2f_det(x))
 struct real
 {
 	float v;
@@ -120,6 +152,10 @@ inline float val(real a) { return a; }
 #define ORC_CHECK_RCP(a) ((void)0)
 #define ORC_CHECK_PLANE(a, c) ((void)0)
 #define ORC_CHECK_RAYDIV(a, c) ((void)0)
+#define ORC_SEE_SINCOS(a) ((void)0)
+#define ORC_SEE_EXP2(a) ((void)0)
+#define ORC_SEE_LOG2(a) ((void)0)
+#define ORC_SEE_POW(x, y) ((void)0)
 #endif
 
 typedef unsigned int uint;
@@ -139,8 +175,8 @@ inline real r_rcp(real a) { ORC_COUNT(1); ORC_CHECK_RCP(val(a)); return real(1.0
 // a / c where c is a scene constant: plain IEEE division here; the census build records
 // numerators outside the range on which the kernels' div_c is verified
 inline real r_div_const(real a, real c) { ORC_CHECK_DIVC(val(a)); return a / c; }
-inline real r_sin(real a) { ORC_COUNT_T(); return real(dm::sinf_det(val(a))); }
-inline real r_cos(real a) { ORC_COUNT_T(); return real(dm::cosf_det(val(a))); }
+inline real r_sin(real a) { ORC_COUNT_T(); ORC_SEE_SINCOS(val(a)); return real(dm::sinf_det(val(a))); }
+inline real r_cos(real a) { ORC_COUNT_T(); ORC_SEE_SINCOS(val(a)); return real(dm::cosf_det(val(a))); }
 // the census build records the one reciprocal inside (detmath.h atan_pos: -(1 / t) for t = |y| / |x| > tan(3 pi / 8), rcp1 in the kernels)
 inline void census_check_atan2(float y, float x)
 {
@@ -151,9 +187,9 @@ inline void census_check_atan2(float y, float x)
 #endif
 }
 inline real r_atan2(real y, real x) { ORC_COUNT_T(); census_check_atan2(val(y), val(x)); return real(dm::atan2f_det(val(y), val(x))); }
-inline real r_exp2(real a) { ORC_COUNT_T(); return real(dm::exp2f_det(val(a))); }
-inline real r_log2(real a) { ORC_COUNT_T(); return real(dm::log2f_det(val(a))); }
-inline real r_pow(real x, real y) { ORC_COUNT_T(); ORC_COUNT_T(); ORC_COUNT(1); return real(dm::powf_det(val(x), val(y))); }
+inline real r_exp2(real a) { ORC_COUNT_T(); ORC_SEE_EXP2(val(a)); return real(dm::exp2f_det(val(a))); }
+inline real r_log2(real a) { ORC_COUNT_T(); ORC_SEE_LOG2(val(a)); return real(dm::log2f_det(val(a))); }
+inline real r_pow(real x, real y) { ORC_COUNT_T(); ORC_COUNT_T(); ORC_COUNT(1); ORC_SEE_POW(val(x), val(y)); return real(dm::powf_det(val(x), val(y))); }
 
 // IEEE minNum/maxNum with -0 < +0 (a-T.5)
 inline real r_min(real a_, real b_)

@@ -293,7 +293,7 @@ int orc_render(const char *scene, const orc_frame *frame, float *out_rgba, unsig
 
 #ifdef ORACLE_CENSUS
 // flop census of the calling thread (render with nthreads = 1): {flops, transcendentals}
-void orc_census_reset() { census() = Census{0, 0, 0, 0, 0, 0}; }
+void orc_census_reset() { census() = Census{0, 0, 0, 0, 0, 0}; math_census().reset(); }
 // {flops, transcendentals, near-field sqrt / division arguments out of domain, far-field (overflowed) arguments}
 void orc_census_get(unsigned long long *out4)
 {
@@ -306,6 +306,19 @@ void orc_census_get(unsigned long long *out4)
 // reciprocals whose argument lies outside rcp1's domain (hlsl.h census_check_rcp: r_rcp, r_rsqrt, atan2's inner 1 / t, sdRoundCone; the
 // ground plane's reciprocal is under census_check_plane), counted apart so that orc_census_get keeps its five words
 unsigned long long orc_census_rcp() { return census().rcp_out_of_domain; }
+// the arguments of the elementary functions (hlsl.h MathCensus), likewise apart: four words per record -- smallest and largest finite
+// argument, calls, non-finite arguments -- for sin and cos (of |argument|), exp2, log2 and pow (of y * log2 x), in this order
+void orc_census_math(double *out16)
+{
+	const ArgRange *r[4] = {&math_census().sincos, &math_census().exp2, &math_census().log2, &math_census().pow};
+	for (int k = 0; k < 4; ++k)
+	{
+		out16[4 * k + 0] = r[k]->lo;
+		out16[4 * k + 1] = r[k]->hi;
+		out16[4 * k + 2] = (double)r[k]->calls;
+		out16[4 * k + 3] = (double)r[k]->nonfinite;
+	}
+}
 #endif
 
 // HDR::process restated (oracle/postprocess.h).  scene: RGBA16F [h][w][4]; bloom1/bloom2:

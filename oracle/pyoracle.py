@@ -294,9 +294,16 @@ def census(scene, frame, step=(1, 1), region=None):
     census.last_far_field = int(c[4])
     L.orc_census_rcp.restype = ctypes.c_ulonglong
     census.last_rcp_violations = int(L.orc_census_rcp())  # reciprocals outside rcp1's domain (r_rcp, r_rsqrt, atan2, sdRoundCone)
+    m = np.zeros(16, np.float64)
+    L.orc_census_math(m.ctypes.data_as(ctypes.c_void_p))
+    # arguments of the elementary functions: {function: (smallest, largest finite argument, calls, non-finite arguments)}; "sincos" is
+    # of |argument|, "pow" of the product y * log2 x; a function never called has (None, None, 0, 0)
+    census.last_math = {name: ((float(m[4 * k]), float(m[4 * k + 1])) if m[4 * k + 2] > m[4 * k + 3] else (None, None)) + (int(m[4 * k + 2]), int(m[4 * k + 3]))
+                        for k, name in enumerate(("sincos", "exp2", "log2", "pow"))}
     return out, totals, int(c[0]), int(c[1])
 
 
 census.last_domain_violations = (0, 0)
 census.last_far_field = 0
 census.last_rcp_violations = 0
+census.last_math = {}

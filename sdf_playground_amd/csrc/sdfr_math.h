@@ -193,7 +193,10 @@ SDF_HD int ftoi1(float a)
 }
 
 // ---- deterministic sin / cos / atan2 / exp2 / log2 / pow -------------------------------
-// Cephes single-precision minimax polynomials, 3-term Cody-Waite reduction with fma.
+// Cephes single-precision minimax polynomials, 3-term Cody-Waite reduction with fma.  Error against the true functions, per binade:
+// tests/golden/math_accuracy.json.  sin1 / cos1 / sincos1 are stated for |x| <= 2^16: there |result| <= 1 and the absolute error is
+// below 3e-7 (the error in ulps is large near the zeros); far beyond (from 2^25) the reduction below no longer reduces, results
+// leave [-1, 1] and are inf or NaN for huge finite x.
 struct SinCosArg { float r, q; };
 SDF_HD SinCosArg sincos_reduce(float x)
 {

@@ -118,6 +118,25 @@ def test_fast_math_domain_is_respected_on_all_scenes(oracle):
             assert oracle.census.last_far_field == 0, path
 
 
+def test_sin_and_cos_arguments_stay_inside_the_stated_domain_on_all_scenes(oracle):
+    """sin1 and cos1 are within 3e-7 of the truth, and within [-1, 1], for |x| <= 2^16 (tests/golden/math_accuracy.json; far beyond, the
+    reduction no longer reduces).  The counting build of the oracle records the arguments the scenes hand to sin and cos: on every
+    golden fixture, at the sixteen cameras and times fitted to the reference's screenshots and on every frame bench.py sweeps -- each
+    at a small size -- all are finite and inside the domain, and the largest per scene is the one the table records."""
+    import math_accuracy_util as mau
+
+    measured = mau.census(oracle)
+    recorded = mau.load()["census"]
+    assert sorted(measured) == ["bench", "golden", "reference_cameras"]
+    assert len(measured["golden"]) == len({gu.scene_of(p) for p in gu.golden_files()}) and sum(1 for c in mau.census_frames(oracle) if c[0] == "reference_cameras") == 16
+    for group, scenes in measured.items():
+        for scene, m in scenes.items():
+            if scene not in mau.NONFINITE_SINCOS_ALLOWED:
+                assert m["sincos_nonfinite"] == 0, (group, scene)
+            assert m["sincos_max"] <= mau.SINCOS_DOMAIN, (group, scene, m["sincos_max"])
+            assert m == recorded[group][scene], (group, scene)
+
+
 @pytest.mark.parametrize("scene", ["lense", "gems", "light_shadows"])
 def test_extension_lights_host_stages_match_oracle(oracle, scene):
     """The "8 lights" extension (SURVEY.md 8d cfg 5): 7 orbiting point lights in slots 1..7."""
