@@ -705,6 +705,64 @@ typedef struct sdfr_mesh_fit_result
 } sdfr_mesh_fit_result;
 int sdfr_mesh_fit(sdfr_renderer *r, const sdfr_mesh_grid *search, int levels, int margin, sdfr_mesh_fit_result *out /* host */);
 
+/* ---- the loaded scene's contours on a stack of planes: marching squares over plane lattices of scene distances, the 2-D sibling of
+ *      sdfr_mesh_extract (no counterpart in the reference; DESIGN.md "Slices").  An indexed set of line segments with shared vertices:
+ *      one vertex per lattice edge that changes sign, one segment per crossing of a cell.  The planes may have any orientation, and the
+ *      lattice is not capped at the mesh's 1024 cells per axis.  All arithmetic is fp32; every operation is separate and unfused, in
+ *      the order written here, so every number of the result is defined exactly.
+ *
+ *      Lattice point (i, j) of layer l, 0 <= i <= nu, 0 <= j <= nv, 0 <= l < layers, is per component c
+ *      ((origin[c] + (float)i * du[c]) + (float)j * dv[c]) + (float)l * dw[c]; its linear index is i + (nu + 1) * (j + (nv + 1) * l).
+ *      Distance and inside: D is what sdfr_query_distance returns at the point; s = D - iso; a point is INSIDE iff s < 0 (NaN is
+ *      therefore outside).
+ *      Vertices: one per lattice edge inside a layer that has exactly one endpoint inside.  The u-edge of point (i, j) needs i < nu and
+ *      runs to (i + 1, j); its v-edge needs j < nv and runs to (i, j + 1).  With a the lower endpoint and b the upper one,
+ *      t = s_a / (s_a - s_b); if !(t >= 0 && t <= 1), t = 0.5f.  positions[v][c] = p_a[c] + t * (p_b[c] - p_a[c]) for all three
+ *      components; coords[v] is ((float)i + t, (float)j) for a u-edge and ((float)i, (float)j + t) for a v-edge.  Vertices are ordered
+ *      by the linear index of the point that owns the edge; at a point the u-edge comes before the v-edge.
+ *      Segments: cell (i, j) of layer l, 0 <= i < nu, 0 <= j < nv, has the corners c0 = (i, j), c1 = (i + 1, j), c2 = (i + 1, j + 1),
+ *      c3 = (i, j + 1): counter-clockwise in (u, v).  Side k runs from c_k to c_((k + 1) % 4): side 0 is the u-edge of (i, j), side 1
+ *      the v-edge of (i + 1, j), side 2 the u-edge of (i, j + 1), side 3 the v-edge of (i, j).  Side k is OUT iff c_k is inside and the
+ *      next corner is not, IN iff c_k is not inside and the next corner is; a cell has zero, one or two OUT sides and as many IN sides.
+ *      A segment runs from the vertex on an OUT side to the vertex on an IN side: the inside is on its left, and an outer contour
+ *      runs counter-clockwise in (u, v).  One OUT side: the one segment.  Two OUT sides (two diagonal corners are inside):
+ *      m = ((s0 + s1) + (s2 + s3)) * 0.25f; if m < 0 (NaN is not), OUT side k pairs with IN side (k + 1) % 4, otherwise with IN side
+ *      (k + 3) % 4.  The segments of a cell are ordered by OUT side, cells by i + nu * (j + nv * l).  segments[s] is (index of the
+ *      start vertex, index of the end vertex).  No segment joins two layers.
+ *      Per-layer offsets: layer_vertices[l] is the number of vertices of the layers < l, layer_segments[l] the same for segments;
+ *      both have layers + 1 entries, the last being the totals.
+ *
+ *        - the protocol is sdfr_mesh_extract's, word for word: counts is host memory, required, and filled when the call returns (the
+ *          call reads the totals back, so it is synchronous up to that point); the arrays are host (on_host = 1) or device
+ *          (on_host = 0) memory, with device arrays the emit work is enqueued on the stream the queries use (two frames in flight:
+ *          sdfr_sync before reading); if either capacity is smaller than the corresponding count, only counts and the layer arrays
+ *          are written, the arrays are untouched and the call returns SDFR_OK.  Capacities 0 with NULL arrays: the counting call.
+ *        - layer_vertices and layer_segments are host memory whatever on_host says, each may be NULL, and they are filled whenever the
+ *          call returns SDFR_OK, the counting call included.
+ *        - errors, in the order they win: SDFR_ERR_INVALID_ARGUMENT "null pointer" (grid or counts); on_host not 0 or 1; "bad slice
+ *          grid" (a non-finite origin, step or iso; du or dv all zero; a count outside its range; more than 2^30 points); a negative
+ *          capacity; a NULL array with a non-zero capacity (coords excepted: NULL = not wanted).  Then SDFR_ERR_NO_SCENE.  Nothing is
+ *          written on error.
+ *        - both totals fit 32 bits (each point and each cell yields at most two); offsets into the arrays are 64-bit.
+ *        - like a query, the call latches camera, time, variables and limits into a copy and changes nothing a render uses or
+ *          reports: no stats, no timings (sdfr_mesh_get_timings keeps the last mesh extraction's), no row order.  Its workspace, about
+ *          12 bytes per lattice point, is sdfr_mesh_extract's under the same keep rule. ---------------------------------------------- */
+typedef struct sdfr_slice_grid
+{
+	float origin[3];        /* lattice point (0,0) of layer 0 */
+	float du[3], dv[3];     /* step to the next lattice point along u, along v; finite, neither all zero */
+	float dw[3];            /* step from one layer to the next; finite */
+	int32_t nu, nv, layers; /* cells per layer 1..16384 each, layers 1..65536; (nu+1)(nv+1)*layers <= 2^30 */
+	float iso;              /* the contour is distance == iso (0: the scene's surface) */
+} sdfr_slice_grid;
+typedef struct sdfr_slice_counts
+{
+	int64_t vertices, segments;
+} sdfr_slice_counts;
+int sdfr_slice_extract(sdfr_renderer *r, const sdfr_slice_grid *grid, int64_t vertex_capacity, int64_t segment_capacity, float *positions /*[v][3]*/,
+	float *coords /*[v][2] or NULL*/, uint32_t *segments /*[s][2]*/, int64_t *layer_vertices /*[layers+1], host, or NULL*/,
+	int64_t *layer_segments /*[layers+1], host, or NULL*/, sdfr_slice_counts *counts /*host, required*/, int on_host);
+
 /* ---- a texture atlas of an extracted mesh (no counterpart in the reference; DESIGN.md "Texture atlas"): one square tile of texels per
  *      quad of the mesh, baked on the GPU.  Surface nets emits quads: triangles 2q and 2q + 1 are (q0, q1, q2) and (q0, q2, q3) of one
  *      quad, so a tile per quad needs no chart cutting and no packing search, and bilinear filtering inside a quad never leaves its tile.

@@ -204,6 +204,17 @@ public:
 		return handle && pushState() && sdfr_mesh_fit(handle, &search, levels, margin, &out) == SDFR_OK;
 	}
 
+	// The loaded scene's contours on a stack of planes (sdfr_slice_extract in sdfr.h: marching squares over `grid`), with this renderer's
+	// variables and time.  counts and the two layer arrays ([layers + 1], host, may be null) are always filled; positions, coords (may be
+	// null) and segments only if both capacities suffice (capacities 0, arrays null: the counting call).
+	bool extractSlices(const sdfr_slice_grid &grid, int64_t vertex_capacity, int64_t segment_capacity, float *positions, float *coords, uint32_t *segments,
+		int64_t *layer_vertices, int64_t *layer_segments, sdfr_slice_counts &counts, bool on_host = true)
+	{
+		return handle && pushState() &&
+			sdfr_slice_extract(handle, &grid, vertex_capacity, segment_capacity, positions, coords, segments, layer_vertices, layer_segments, &counts,
+				on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// The texture atlas of an extracted mesh (sdfr_atlas_layout, sdfr_atlas_uvs, sdfr_atlas_texels, sdfr_atlas_bake in sdfr.h): one square
 	// tile of texels per quad.  atlasTexels looks at the mesh alone; bakeAtlas looks at every texel as meshSurfaces / meshLighting look at
 	// a vertex, with this renderer's variables and time.  layers: SDFR_ATLAS_*; a plane that is not asked for may be null.

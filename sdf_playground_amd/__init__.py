@@ -80,6 +80,15 @@ class MeshCounts(ctypes.Structure):  # sdfr_mesh_counts
     _fields_ = [("vertices", ctypes.c_int64), ("triangles", ctypes.c_int64)]
 
 
+class SliceGrid(ctypes.Structure):  # sdfr_slice_grid
+    _fields_ = [("origin", ctypes.c_float * 3), ("du", ctypes.c_float * 3), ("dv", ctypes.c_float * 3), ("dw", ctypes.c_float * 3),
+                ("nu", ctypes.c_int32), ("nv", ctypes.c_int32), ("layers", ctypes.c_int32), ("iso", ctypes.c_float)]
+
+
+class SliceCounts(ctypes.Structure):  # sdfr_slice_counts
+    _fields_ = [("vertices", ctypes.c_int64), ("segments", ctypes.c_int64)]
+
+
 class MeshSurvey(ctypes.Structure):  # sdfr_mesh_survey_result
     _fields_ = [("active_cells", ctypes.c_int64), ("quads", ctypes.c_int64), ("near_cells", ctypes.c_int64), ("inside_points", ctypes.c_int64),
                 ("active_lo", ctypes.c_int32 * 3), ("active_hi", ctypes.c_int32 * 3), ("near_lo", ctypes.c_int32 * 3), ("near_hi", ctypes.c_int32 * 3),
@@ -160,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_atlas_layout", "sdfr_atlas_uvs", "sdfr_atlas_texels", "sdfr_atlas_bake",
     "sdfr_mesh_extract_sharp",
     "sdfr_mesh_survey", "sdfr_mesh_fit",
+    "sdfr_slice_extract",
 ]
 
 _lib = None
@@ -273,6 +283,7 @@ def load_library():
     L.sdfr_mesh_get_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double * 4)]
     L.sdfr_mesh_survey.argtypes = [vp, ctypes.POINTER(MeshGrid), cf, ctypes.POINTER(MeshSurvey)]
     L.sdfr_mesh_fit.argtypes = [vp, ctypes.POINTER(MeshGrid), ci, ci, ctypes.POINTER(MeshFit)]
+    L.sdfr_slice_extract.argtypes = [vp, ctypes.POINTER(SliceGrid), i64, i64, vp, vp, vp, vp, vp, ctypes.POINTER(SliceCounts), ci]
     L.sdfr_atlas_layout.argtypes = [i64, ci, ci, ctypes.POINTER(Atlas)]
     L.sdfr_atlas_uvs.argtypes = [ctypes.POINTER(Atlas), vp]
     L.sdfr_atlas_texels.argtypes = [vp, ctypes.POINTER(Atlas), i64, vp, vp, vp, vp, vp, vp, ci]
@@ -296,6 +307,38 @@ def occlusionDirections():
     if rc != 0:
         raise SdfrError(rc, "sdfr_occlusion_directions")
     return d
+
+
+def chainContours(segments, layer_segments):
+    """The segments of extractSlices joined into polylines, layer by layer: a list with one entry per layer, each a list of
+    (vertex indices int64 [k], closed) in contour direction (the inside on the left).  Integer matching only: every vertex starts at most
+    one segment and ends at most one.  Open chains come first, ordered by their first segment's index, each beginning at the vertex no
+    segment ends at; closed loops follow, each starting at its lowest segment index (closed: the first vertex is not repeated)."""
+    seg = np.asarray(segments).reshape(-1, 2).astype(np.int64)
+    offsets = [int(v) for v in np.asarray(layer_segments).reshape(-1)]
+    layers = []
+    for lo, hi in zip(offsets[:-1], offsets[1:]):
+        part = seg[lo:hi]
+        starts_at = {int(a): k for k, a in enumerate(part[:, 0])}  # vertex -> the segment that starts there
+        ended = set(int(b) for b in part[:, 1])
+        if len(starts_at) != len(part) or len(ended) != len(part):
+            raise ValueError("chainContours: a vertex starts or ends more than one segment")
+        used = np.zeros(len(part), bool)
+        chains = []
+        for closed in (False, True):
+            for k in range(len(part)):
+                if used[k] or (not closed and int(part[k, 0]) in ended):
+                    continue
+                chain = [int(part[k, 0])]
+                while k is not None and not used[k]:
+                    used[k] = True
+                    chain.append(int(part[k, 1]))
+                    k = starts_at.get(chain[-1])
+                if closed:
+                    chain.pop()  # (the loop came back to its first vertex)
+                chains.append((np.asarray(chain, np.int64), closed))
+        layers.append(chains)
+    return layers
 
 
 def atlasLayout(triangles, tile=8, width=None):
@@ -880,6 +923,43 @@ class SDFRenderer:
             if (again.vertices, again.triangles) != (v, t):
                 raise SdfrError(-9, "the mesh changed between the counting and the filling call")
         return pos, nrm, idx
+
+    # ---- the loaded scene's contours on a stack of planes (sdfr_slice_extract; DESIGN.md "Slices") ---------------------------------------
+    def extractSlices(self, origin, du, dv, dw=(0.0, 0.0, 0.0), dims=(1, 1), layers=1, iso=0.0, coords=True, device=False):
+        """Marching squares over `layers` plane lattices: point (i, j) of layer l at origin + i * du + j * dv + l * dw, dims = (nu, nv)
+        cells.  -> (positions [v, 3] float32, coords [v, 2] float32 lattice coordinates or None, segments [s, 2] (start vertex, end vertex:
+        the inside on the left), layer_vertices [layers + 1] int64, layer_segments [layers + 1] int64: layer l's vertices and segments are
+        the rows layer_*[l] .. layer_*[l + 1]).  numpy arrays (segments uint32), or with device=True torch tensors on the renderer's GPU
+        (segments int32: the same 32 bits), enqueued on the handle's stream; the two layer arrays are numpy either way.  The counting call,
+        then the filling call.  chainContours joins the segments into polylines."""
+        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])  # noqa: E731
+        grid = SliceGrid(f3(origin), f3(du), f3(dv), f3(dw), int(dims[0]), int(dims[1]), int(layers), float(iso))
+        counts = SliceCounts()
+        n_layers = max(int(layers), 0) + 1
+        layer_v, layer_s = np.zeros(n_layers, np.int64), np.zeros(n_layers, np.int64)
+        lv, ls = layer_v.ctypes.data_as(ctypes.c_void_p), layer_s.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._L.sdfr_slice_extract(self._h, ctypes.byref(grid), 0, 0, None, None, None, lv, ls, ctypes.byref(counts), 0 if device else 1))
+        v, s = int(counts.vertices), int(counts.segments)
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            pos = torch.empty((v, 3), dtype=torch.float32, device=dev)
+            uv = torch.empty((v, 2), dtype=torch.float32, device=dev) if coords else None
+            seg = torch.empty((s, 2), dtype=torch.int32, device=dev)
+            ptr = lambda a: ctypes.c_void_p(a.data_ptr()) if a is not None and a.numel() else None  # noqa: E731
+        else:
+            pos = np.empty((v, 3), np.float32)
+            uv = np.empty((v, 2), np.float32) if coords else None
+            seg = np.empty((s, 2), np.uint32)
+            ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+        if v:
+            again = SliceCounts()
+            self._check(self._L.sdfr_slice_extract(self._h, ctypes.byref(grid), v, s, ptr(pos), ptr(uv), ptr(seg), lv, ls, ctypes.byref(again),
+                                                   0 if device else 1))
+            if (again.vertices, again.segments) != (v, s):
+                raise SdfrError(-9, "the slices changed between the counting and the filling call")
+        return pos, uv, seg, layer_v, layer_s
 
     # ---- the texture atlas of a mesh (sdfr_atlas_texels / sdfr_atlas_bake; DESIGN.md "Texture atlas") -------------------------------
     def _atlas_inputs(self, positions, normals, indices, device):

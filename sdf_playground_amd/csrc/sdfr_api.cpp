@@ -8,6 +8,7 @@
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
 #include "sdfr_mesh_plan.h"
+#include "sdfr_slice_plan.h"
 #include "sdfr_occlusion.h"
 #include "sdfr_query.h"
 #include "sdfr_query_plan.h"
@@ -1084,6 +1085,80 @@ int sdfr_mesh_get_timings(sdfr_renderer *r, double ms[4])
 			ms[k] = t;
 		}
 		return SDFR_OK;
+	});
+}
+
+// ---- sdfr_slice_extract (the definition: include/sdfr.h; the plan: sdfr_slice_plan.h; stages: sdfr_slice.h, sdfr_slice.hip), a call of the
+// queries' protocol and in every step sdfr_mesh_extract's sibling.  Sample the stack of lattices, classify and scan, gather the layers'
+// offsets and read them back -- their last entries are the two totals --; then, if the capacities allow, emit vertices and segments.
+// The workspace is the extraction's; no profiling event is recorded: sdfr_mesh_get_timings keeps the last mesh extraction's.
+static_assert(sizeof(sdfr_slice_grid) == sizeof(SliceGrid) && offsetof(sdfr_slice_grid, du) == offsetof(SliceGrid, du) && offsetof(sdfr_slice_grid, dv) == offsetof(SliceGrid, dv) &&
+		offsetof(sdfr_slice_grid, dw) == offsetof(SliceGrid, dw) && offsetof(sdfr_slice_grid, nu) == offsetof(SliceGrid, nu) &&
+		offsetof(sdfr_slice_grid, layers) == offsetof(SliceGrid, layers) && offsetof(sdfr_slice_grid, iso) == offsetof(SliceGrid, iso),
+	"sdfr_slice_grid is the plan's SliceGrid");
+static int slice_impl(sdfr_renderer *r, const SliceRequest &c, int64_t *layer_vertices, int64_t *layer_segments, sdfr_slice_counts *counts)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	const SlicePlan p = plan_slice(c);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, true, 1, 1, U, stream);
+	if (rc != SDFR_OK) return rc;
+
+	Carving work({p.work[0], p.work[1], p.work[2], p.work[3], p.work[4]});
+	rc = reserve_mesh_workspace(r, work, stream);
+	if (rc != SDFR_OK) return rc;
+	float *d_lattice = work.piece<float>(0);
+	uint32_t *d_vertices = work.piece<uint32_t>(1), *d_segments = work.piece<uint32_t>(2), *d_sums = work.piece<uint32_t>(3), *d_layers = work.piece<uint32_t>(4);
+
+	static const int rows = [] { const char *e = getenv("SDFR_SLICE_ROWS"); return e && atoi(e) != 0 ? 1 : 0; }(); // developer knob: the A/B
+	SliceArgs sample = p.sample;
+	sample.rows = rows;
+	sample.out = d_lattice;
+	KernelRef slice_kernel;
+	rc = loaded_query_kernel(r, QUERY_KERNEL_SLICES, U, slice_kernel);
+	if (rc != SDFR_OK) return rc;
+	const hipError_t e = launch_query_slices(slice_kernel, U, sample, slice_sample_blocks(sample), stream);
+	if (e != hipSuccess) return hip_fail(r, e, "slice launch");
+	SDFR_HIP(launch_slice_count(p.g, d_lattice, d_vertices, d_segments, d_sums, d_layers, stream));
+	const size_t per = (size_t)p.g.layers + 1;
+	std::vector<uint32_t> offsets(2 * per);
+	SDFR_HIP(hipMemcpyAsync(offsets.data(), d_layers, p.work[4], hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+	const uint32_t n_vertices = offsets[per - 1], n_segments = offsets[2 * per - 1];
+	const SliceFill f = plan_slice_fill(c, n_vertices, n_segments);
+	counts->vertices = f.vertices;
+	counts->segments = f.segments;
+	for (size_t l = 0; l < per; ++l)
+	{
+		if (layer_vertices) layer_vertices[l] = (int64_t)offsets[l];
+		if (layer_segments) layer_segments[l] = (int64_t)offsets[per + l];
+	}
+	if (!f.fill) return release_large(r, r->mesh, stream);
+
+	float *d_pos = c.positions, *d_uv = c.coords;
+	uint32_t *d_seg = f.bytes[2] ? c.segments : nullptr;
+	Carving st;
+	if (c.on_host)
+	{
+		const StagedArray arrays[3] = {{&d_pos, f.bytes[0], false}, {&d_uv, f.bytes[1], false}, {&d_seg, f.bytes[2], false}};
+		rc = stage_host_arrays(r, st, arrays, 3, stream); // (in `query`, never in `mesh`)
+		if (rc != SDFR_OK) return rc;
+	}
+	SDFR_HIP(launch_slice_emit(p.g, d_lattice, d_vertices, d_segments, d_pos, d_uv, d_seg, stream));
+	if (c.on_host) rc = copy_answers_back(r, st, stream);
+	else SDFR_HIP(hipEventRecord(r->ev_mesh[6], stream)); // the end of the device work the next extraction waits for
+	if (rc != SDFR_OK) return rc;
+	return release_large(r, r->mesh, stream);
+}
+
+int sdfr_slice_extract(sdfr_renderer *r, const sdfr_slice_grid *grid, int64_t vertex_capacity, int64_t segment_capacity, float *positions, float *coords,
+	uint32_t *segments, int64_t *layer_vertices, int64_t *layer_segments, sdfr_slice_counts *counts, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		const SliceRequest c = {reinterpret_cast<const SliceGrid *>(grid), vertex_capacity, segment_capacity, positions, coords, segments, counts, on_host};
+		return slice_impl(r, c, layer_vertices, layer_segments, counts);
 	});
 }
 

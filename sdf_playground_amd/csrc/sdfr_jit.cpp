@@ -87,6 +87,7 @@ const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_
 	{"sdfr_jit_query_lighting", "query_lighting_kernel", "QueryKernelArgs"},
 	{"sdfr_jit_bake_atlas", "atlas_bake_kernel", "AtlasKernelArgs"},
 	{"sdfr_jit_mesh_sharp", "mesh_sharp_kernel", "MeshSharpKernelArgs"},
+	{"sdfr_jit_query_slices", "query_slices_kernel", "SliceKernelArgs"},
 };
 
 } // namespace

@@ -82,10 +82,26 @@ hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *
 hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
 	uint32_t *indices, bool cells_only, hipStream_t stream);
 hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshSharpArgs &m, hipStream_t stream);
+// data [n] -> its exclusive prefix sum, in place, by the launches launch_mesh_count makes (k_mesh_scan_*); sums: mesh_scan_sum_words(n) words
+void launch_mesh_scan(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream);
 // What the lattice holds (sdfr_mesh_survey.h; sdfr_mesh_survey): out, MESH_SURVEY_WORK_BYTES of device memory, is the survey of g, near
 // cells with `band`, followed by the words k_mesh_survey counted it in with integer atomics, each word in a page of its own.
 struct MeshSurvey;
 hipError_t launch_mesh_survey(const MeshGrid &g, const float *lattice, float band, MeshSurvey *out, hipStream_t stream);
+
+// Marching squares over a stack of plane lattices (sdfr_slice.h, sdfr_slice.hip; sdfr_slice_extract), every pointer device memory.
+// launch_query_slices: the distance query over the stack (SliceArgs) by a scene's slice kernel (QUERY_KERNEL_SLICES) for U, in
+// `blocks` blocks of one wave (sdfr_slice_plan.h: slice_sample_blocks).  launch_slice_count: the vertex count and the segment count per
+// lattice point, then their exclusive prefix sums in place -- point_vertex and cell_segment [points + 1], whose last elements are the
+// totals; sums: 2 * mesh_scan_sum_words(points + 1) words of scratch -- and layer_offsets [2][layers + 1], the first vertex and the first
+// segment of every layer with the totals after the last.  launch_slice_emit: positions [vertices][3], coords [vertices][2] unless null,
+// and unless null (no segments) segments [segments][2].
+struct SliceGrid;
+hipError_t launch_query_slices(const KernelRef &k, const FrameU &U, const SliceArgs &g, uint32_t blocks, hipStream_t stream);
+hipError_t launch_slice_count(const SliceGrid &g, const float *lattice, uint32_t *point_vertex, uint32_t *cell_segment, uint32_t *sums, uint32_t *layer_offsets,
+	hipStream_t stream);
+hipError_t launch_slice_emit(const SliceGrid &g, const float *lattice, const uint32_t *point_vertex, const uint32_t *cell_segment, float *positions, float *coords,
+	uint32_t *segments, hipStream_t stream);
 
 // The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
 // per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes

@@ -507,6 +507,15 @@ hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshShar
 	return launch_kernel(k, (m.vertices + per_block - 1u) / per_block, SDFR_PIXEL_BLOCK, args, stream);
 }
 
+hipError_t launch_query_slices(const KernelRef &k, const FrameU &U, const SliceArgs &g, uint32_t blocks, hipStream_t stream)
+{
+	SliceKernelArgs a;
+	a.U = U;
+	a.g = g;
+	void *args[] = {&a};
+	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
+}
+
 hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
 {
 	AtlasKernelArgs a;

@@ -145,6 +145,9 @@ __global__ __launch_bounds__(SDFR_MESH_BLOCK) void k_mesh_emit_indices(MeshGrid 
 	mesh_point_emit(g, lattice, cell_vertex, i, j, k, q, indices);
 }
 
+// the same prefix sum for the other extractions of this family (sdfr_slice.hip)
+void launch_mesh_scan(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream) { scan_exclusive(data, n, sums, stream); }
+
 hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *cell_vertex, uint32_t *point_quad, uint32_t *sums, hipStream_t stream)
 {
 	const uint32_t points = mesh_point_count(g), cells = mesh_cell_count(g);

@@ -39,6 +39,13 @@ struct MeshSharpKernelArgs
 	MeshSharpArgs m;
 };
 
+// ... and the slice kernel (SliceArgs: sdfr_query_args.h)
+struct SliceKernelArgs
+{
+	FrameU U;
+	SliceArgs g;
+};
+
 // the driver's normal at pos (pshader_sdf.hlsl:164-177, 320-330): map_normal with the NormalOutput preloaded {grad_eps, 0, false};
 // its normal if it sets use_normal, else the three forward differences against `baseline`, normalised
 template <class Scene, bool DBG>

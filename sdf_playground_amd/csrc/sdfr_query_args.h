@@ -39,7 +39,7 @@ static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offseto
 static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
 // A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_KINDS = 8 };
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_SLICES = 8, QUERY_KERNEL_KINDS = 9 };
 
 // One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
@@ -90,5 +90,19 @@ struct AtlasArgs
 	int32_t *valid;               // [height * width]
 	float *texel_positions, *texel_normals; // [height * width][3] each
 };
+
+// One slice launch (sdfr_kernels.h: launch_query_slices; sdfr_slice_extract): the distance query at the points of a stack of plane
+// lattices, computed from their indices -- point (i, j) of layer l is ((origin + (float)i * du) + (float)j * dv) + (float)l * dw per
+// component, every operation separate (sdfr_slice.h: slice_coord) -- into out[i + pu * (j + pv * l)].  pu * pv * layers <= 2^30.
+struct SliceArgs
+{
+	float origin[3];
+	float du[3], dv[3], dw[3];
+	int32_t pu, pv, layers; // lattice points along u and v, layers
+	int32_t rows;           // 0: a wave owns an 8 x 8 tile of points of one layer; 1: 64 consecutive points of the linear index (the A/B of DESIGN.md 4.14)
+	float *out;
+};
+static_assert(sizeof(SliceArgs) == 72 && __builtin_offsetof(SliceArgs, du) == 12 && __builtin_offsetof(SliceArgs, dw) == 36 && __builtin_offsetof(SliceArgs, pu) == 48, "");
+static_assert(__builtin_offsetof(SliceArgs, rows) == 60 && __builtin_offsetof(SliceArgs, out) == 64, "SliceArgs is a kernel argument");
 
 } // namespace sdfr

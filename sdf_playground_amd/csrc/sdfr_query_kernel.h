@@ -12,6 +12,7 @@
 #include "sdfr_lighting.h"
 #include "sdfr_atlas.h"
 #include "sdfr_mesh_sharp.h"
+#include "sdfr_slice.h"
 
 namespace sdfr {
 
@@ -365,6 +366,40 @@ __device__ __forceinline__ void mesh_sharp_kernel(const MeshSharpKernelArgs &a)
 		o[1] = x[1];
 		o[2] = x[2];
 	}
+}
+
+// The distance query over a stack of plane lattices (SliceArgs; sdfr_slice_extract): one wave per block, one point per lane.  A wave
+// owns an 8 x 8 tile of points of ONE layer -- the layers may lie far apart, the points of a tile lie within 7 steps of each other --
+// so that the scenes' wave-level branches stay coherent, as the 4 x 4 x 4 bricks do for the mesh; its stores are runs of 8 floats.
+// The tile is addressed by the block index alone (scalar arithmetic).  rows = 1 maps 64 consecutive points of the linear index instead.
+// Nothing is read but the kernel's arguments; every lane writes its own 4 bytes; lanes past a layer's ragged edges leave.
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_slices_kernel(const SliceKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 points");
+	const SliceArgs &g = a.g;
+	const uint32_t pu = (uint32_t)g.pu, pv = (uint32_t)g.pv, layers = (uint32_t)g.layers, lane = threadIdx.x;
+	uint32_t i, j, l;
+	if (g.rows)
+	{
+		const uint32_t p = blockIdx.x * 64u + lane; // < 2^30 + 64
+		const uint32_t row = p / pu;
+		i = p - row * pu;
+		l = row / pv;
+		j = row - l * pv;
+	}
+	else
+	{
+		const uint32_t tu = (pu + 7u) >> 3, tv = (pv + 7u) >> 3;
+		const uint32_t trow = blockIdx.x / tu;
+		l = trow / tv;
+		i = (blockIdx.x - trow * tu) * 8u + (lane & 7u);
+		j = (trow - l * tv) * 8u + (lane >> 3);
+	}
+	if (i >= pu || j >= pv || l >= layers) return;
+	const vec3 p = V3(slice_coord(g.origin, g.du, g.dv, g.dw, 0, (int)i, (int)j, (int)l), slice_coord(g.origin, g.du, g.dv, g.dw, 1, (int)i, (int)j, (int)l),
+		slice_coord(g.origin, g.du, g.dv, g.dw, 2, (int)i, (int)j, (int)l));
+	g.out[i + pu * (j + pv * l)] = query_point<Scene, DBG>(a.U, p, nullptr); // (the index is < 2^30)
 }
 
 } // namespace sdfr

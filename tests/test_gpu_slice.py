@@ -1,0 +1,386 @@
+"""GPU tier of sdfr_slice_extract through libsdfr.so: every word equal to the definition of include/sdfr.h restated in numpy
+(slice_util.marching_squares), fed with the oracle's distances for the built-in scenes and the dialect scene and with the library's own
+queryDistance for the run-time probe scene; geometric bounds on a sphere and a plane; the capacity rule and the counting call; no side
+effects on rendering; the argument errors through the raw C ABI."""
+import ctypes
+import math
+import os
+
+import numpy as np
+import pytest
+
+import query_util as qu
+import slice_util as su
+from test_gpu_mesh_survey import DEFAULT_LIMITS, PROBE
+
+pytestmark = pytest.mark.gpu
+
+W, H = 64, 48
+# horizontal planes (u = x, v = z, layers upwards), 37 x 29 cells in 5 layers: ragged against 8 x 8 tiles, 64-lane waves and 256-thread
+# blocks alike.  Per scene: time, the low corner (x, z), the cell, the height of layer 0 and the step between layers -- a box the
+# scene's solid crosses in every layer
+DIMS, LAYERS = (37, 29), 5
+CASES = {"fast_sphere": (0.0, (-0.92, -0.72), 0.05, 0.62, 0.17), "labyrinth": (1.25, (-5.35, -2.55), 0.05, 0.37, 0.23),
+         "gyroid": (0.5, (-0.92, -0.72), 0.05, -0.2, 0.23), "sierpinski": (0.5, (-0.75, -0.55), 0.04, 1.02, 0.11),
+         "noise_lod": (0.5, (-0.92, -0.72), 0.05, 0.4, 0.4)}
+
+
+def axis_grid(scene):
+    _stime, (x0, z0), cell, y0, dy = CASES[scene]
+    return dict(origin=(x0, y0, z0), du=(cell, 0.0, 0.0), dv=(0.0, 0.0, cell), dw=(0.0, dy, 0.0), dims=DIMS, layers=LAYERS)
+
+
+def oblique_grid(scene):
+    """du and dv rotated about y and tilted out of the horizontal, of different lengths; dw orthogonal to neither"""
+    _stime, (x0, z0), cell, y0, dy = CASES[scene]
+    return dict(origin=(x0 + 8 * cell, y0 - 3 * cell, z0 - 4 * cell), du=(0.9 * cell, 0.12 * cell, 0.34 * cell), dv=(-0.3 * cell, 0.07 * cell, 0.83 * cell),
+                dw=(0.4 * cell, 0.9 * dy, -0.3 * cell), dims=DIMS, layers=LAYERS)
+
+
+def _setup(r, scene, of):
+    """the handle's state = the oracle frame `of`"""
+    if scene in qu.HLSL:
+        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
+    else:
+        r.initShader(scene)
+    r.setParameters(of.stime)
+    r.setCameraBasis(of.eye, of.front, of.right, of.top)
+    r.setLimits(**DEFAULT_LIMITS)
+    r.setStepShortcuts(False)
+
+
+def _probe(r, **values):
+    """the probe scene of tests/test_gpu_mesh_survey.py with its variables set; -> distance(grid) by the library's own point query"""
+    if r.currentScene() != "slice_probe":
+        r.initShaderSource("slice_probe", PROBE)
+        r.setLimits(**DEFAULT_LIMITS)
+    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
+        assert r.setValue(name, v)
+    return lambda g: r.queryDistance(su.lattice_points(g["origin"], g["du"], g["dv"], g["dw"], g["dims"], g["layers"]))
+
+
+def _stats(r):
+    s = r.getStats()
+    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    yield r
+    r.close()
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "data_ptr") else a
+
+
+def _assert_same(what, got, want, coords=True):
+    """got: extractSlices' five; want: the restatement's five"""
+    pos, uv, seg, lv, ls = (_host(a) if a is not None else None for a in got)
+    assert pos.shape == want[0].shape and seg.shape == want[2].shape, (what, pos.shape, want[0].shape, seg.shape, want[2].shape)
+    qu.assert_same("%s positions" % (what,), pos, want[0])
+    if coords:
+        qu.assert_same("%s coords" % (what,), uv, want[1])
+    else:
+        assert uv is None, what
+    assert np.array_equal(seg.view(np.uint32), want[2]), (what, "segments")
+    assert lv.dtype == np.int64 and ls.dtype == np.int64 and np.array_equal(lv, want[3]) and np.array_equal(ls, want[4]), (what, "layers")
+
+
+def _want(scene, of, g, iso=0.0):
+    P = su.lattice_points(g["origin"], g["du"], g["dv"], g["dw"], g["dims"], g["layers"])
+    D, _ = qu.oracle_points(scene, of, P, normals=False)
+    return D, su.marching_squares(D, iso=iso, **g)
+
+
+# ---- parity ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", sorted(CASES))
+def test_slices_equal_the_definition(renderer, scene):
+    of = qu.frame(scene, CASES[scene][0], W, H)
+    _setup(renderer, scene, of)
+    for what, g in (("axis", axis_grid(scene)), ("oblique", oblique_grid(scene))):
+        D, want = _want(scene, of, g)
+        assert len(want[0]) > 100 and (np.diff(want[3]) > 0).sum() >= 3, (what, len(want[0]), want[3])
+        su.check_invariants(D, 0.0, want[1], want[2], want[3], want[4], g["dims"], g["layers"])
+        for device in (False, True):
+            for coords in (True, False):
+                got = renderer.extractSlices(coords=coords, device=device, **g)
+                renderer.sync()
+                _assert_same((scene, what, device, coords), got, want, coords)
+    # another iso: the contour moves
+    g = axis_grid(scene)
+    D, want = _want(scene, of, g, iso=0.05)
+    _assert_same((scene, "iso"), renderer.extractSlices(iso=0.05, **g), want)
+
+
+def test_one_large_layer(renderer):
+    """300 x 250 cells: 75 551 points pass 256^2, so both prefix sums recurse on their block totals"""
+    scene = "gyroid"
+    of = qu.frame(scene, 0.5, W, H)
+    _setup(renderer, scene, of)
+    g = dict(origin=(-1.5, 0.3, -1.25), du=(0.01, 0.0, 0.0), dv=(0.0, 0.0, 0.01), dw=(0.0, 0.0, 0.0), dims=(300, 250), layers=1)
+    assert 301 * 251 + 1 > 256 * 256
+    D, want = _want(scene, of, g)
+    assert len(want[0]) > 2000
+    su.check_invariants(D, 0.0, want[1], want[2], want[3], want[4], g["dims"], 1)
+    _assert_same("host", renderer.extractSlices(**g), want)
+    got = renderer.extractSlices(device=True, **g)
+    renderer.sync()
+    _assert_same("device", got, want)
+
+
+def test_tallest_stack(renderer):
+    """65 536 layers of one cell: a wave per layer with four points, and 65 537 offsets per layer array"""
+    scene = "fast_sphere"
+    of = qu.frame(scene, 0.0, W, H)
+    _setup(renderer, scene, of)
+    g = dict(origin=(-1.5, -0.2, -0.9), du=(0.07, 0.0, 0.01), dv=(0.0, 0.02, 0.06), dw=(3.0 / 65536, 2.2 / 65536, 1.8 / 65536), dims=(1, 1), layers=65536)
+    D, want = _want(scene, of, g)
+    assert len(want[0]) > 1000 and len(want[3]) == 65537
+    su.check_invariants(D, 0.0, want[1], want[2], want[3], want[4], g["dims"], g["layers"])
+    _assert_same("host", renderer.extractSlices(**g), want)
+
+
+# ---- the run-time probe scene ------------------------------------------------------------------------------------------------------
+def test_sphere_sliced_obliquely(renderer):
+    import sdf_playground_amd as sp
+
+    c, radius, e = np.array([0.03, 0.05, 0.07]), 1.0, 0.05
+    # an orthonormal frame, tilted: du and dv have length e, the planes' normal is n; dw adds an in-plane drift to 0.3 n
+    a = np.array([0.6, 0.0, 0.8])
+    b = np.array([-0.8 * 0.6, 0.8, 0.6 * 0.6])
+    n = np.cross(a, b)
+    assert abs(np.linalg.norm(b) - 1) < 1e-12 and abs(a @ b) < 1e-12
+    layers = 8
+    dw = 0.3 * n + 0.011 * a - 0.007 * b
+    origin = c - 30.5 * e * a - 30.2 * e * b - 1.05 * n
+    g = dict(origin=tuple(origin), du=tuple(e * a), dv=tuple(e * b), dw=tuple(dw), dims=(61, 61), layers=layers)
+    distance = _probe(renderer, cx=c[0], cy=c[1], cz=c[2], radius=radius)
+    D = distance(g)
+    want = su.marching_squares(D, iso=0.0, **g)
+    got = renderer.extractSlices(**g)
+    _assert_same("sphere", got, want)
+    pos, uv, seg, lv, ls = got
+    su.check_invariants(D, 0.0, uv, seg, lv, ls, g["dims"], layers)
+    chains = sp.chainContours(seg, ls)
+    f32 = lambda v: np.asarray(v, np.float32).astype(np.float64)  # noqa: E731 (the grid as the library was given it)
+    du, dv, dw32, o32 = f32(g["du"]), f32(g["dv"]), f32(g["dw"]), f32(g["origin"])
+    cell_area = np.linalg.norm(np.cross(du, dv))
+    normal = np.cross(du, dv) / cell_area
+    step = max(np.linalg.norm(du), np.linalg.norm(dv))
+    checked = 0
+    for l in range(layers):
+        h = abs((o32 + l * dw32 - c) @ normal)
+        if h >= radius:
+            assert h < radius + step or chains[l] == []
+            continue
+        rho = math.sqrt(radius * radius - h * h)
+        if rho <= 3 * step:
+            continue
+        assert len(chains[l]) == 1 and chains[l][0][1], (l, h)
+        area = su.shoelace(uv, chains[l][0][0]) * cell_area
+        assert math.pi * (rho - step) ** 2 <= area <= math.pi * (rho + step) ** 2, (l, rho, area)
+        checked += 1
+    assert checked >= 6
+    # linear interpolation of a distance whose second derivative along an edge is at most 1 / (r - e)
+    off = np.abs(np.linalg.norm(pos.astype(np.float64) - c, axis=1) - radius)
+    assert off.max() <= step * step / (8 * (radius - step)) + 1e-5, off.max()
+    # device arrays, no coords: the same positions and segments
+    dev = renderer.extractSlices(coords=False, device=True, **g)
+    renderer.sync()
+    _assert_same("sphere, device", dev, want, coords=False)
+
+
+def test_plane_sliced_vertically(renderer):
+    import sdf_playground_amd as sp
+
+    # the plane y = 0.25, inside below it; u = x, v = y (up): every layer is one open chain from the border u = nu to the border u = 0,
+    # the inside on its left
+    g = dict(origin=(-0.6, -0.2, 0.0), du=(0.1, 0.0, 0.0), dv=(0.0, 0.1, 0.0), dw=(0.0, 0.0, 0.2), dims=(12, 9), layers=3)
+    D = _probe(renderer, kind=1.0, height=0.25)(g)
+    want = su.marching_squares(D, iso=0.0, **g)
+    got = renderer.extractSlices(**g)
+    _assert_same("plane", got, want)
+    pos, uv, seg, lv, ls = got
+    su.check_invariants(D, 0.0, uv, seg, lv, ls, g["dims"], 3)
+    assert list(lv) == [0, 13, 26, 39] and list(ls) == [0, 12, 24, 36]
+    chains = sp.chainContours(seg, ls)
+    for l, layer in enumerate(chains):
+        assert len(layer) == 1 and not layer[0][1]
+        chain = layer[0][0]
+        assert list(uv[chain, 0]) == [float(i) for i in range(12, -1, -1)]  # towards -u: the inside, below, is on the left
+        assert np.allclose(uv[chain, 1], 4.5, atol=1e-5) and np.allclose(pos[chain, 1], 0.25, atol=1e-6) and np.allclose(pos[chain, 2], 0.2 * l, atol=1e-6)
+    # iso moves the contour up by 0.1: one lattice row
+    pos2, uv2, _seg, _lv, _ls = renderer.extractSlices(iso=0.1, **g)
+    assert np.allclose(uv2[:, 1], 5.5, atol=1e-4)
+
+
+def test_nan_half_space(renderer):
+    # NaN where x > 0.3: those points are outside; an edge into them is cut at its middle (t is NaN, so 0.5)
+    g = dict(origin=(-0.6, -0.2, 0.0), du=(0.1, 0.0, 0.0), dv=(0.0, 0.1, 0.0), dw=(0.0, 0.0, 0.2), dims=(12, 9), layers=2)
+    D = _probe(renderer, kind=2.0, height=0.25, split=0.3)(g)
+    assert 2 * 10 * 2 <= np.isnan(D).sum() <= 2 * 10 * 4
+    want = su.marching_squares(D, iso=0.0, **g)
+    got = renderer.extractSlices(**g)
+    _assert_same("NaN", got, want)
+    pos, uv, seg, lv, ls = got
+    su.check_invariants(D, 0.0, uv, seg, lv, ls, g["dims"], 2)
+    last_inside = int(np.floor(uv[:, 0].max()))
+    wall = uv[:, 0] == last_inside + 0.5  # the u-edges from the last finite column into the NaN columns, below the plane
+    assert wall.sum() == 2 * 5 and (uv[wall, 1] == np.floor(uv[wall, 1])).all() and uv[wall, 1].max() == 4
+    assert np.isfinite(pos).all()
+
+
+# ---- the protocol ----------------------------------------------------------------------------------------------------------------
+def _raw(L, h, g, vcap, scap, pos, uv, seg, lv, ls, counts, on_host=1):
+    import sdf_playground_amd as sp
+
+    grid = sp.SliceGrid(*[(ctypes.c_float * 3)(*g[k]) for k in ("origin", "du", "dv", "dw")], g["dims"][0], g["dims"][1], g["layers"], g.get("iso", 0.0)) if g else None
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    return L.sdfr_slice_extract(h, ctypes.byref(grid) if grid is not None else None, vcap, scap, p(pos), p(uv), p(seg), p(lv), p(ls),
+                                ctypes.byref(counts) if counts is not None else None, on_host)
+
+
+def test_capacities_and_the_counting_call(renderer):
+    import sdf_playground_amd as sp
+
+    L = sp.load_library()
+    scene = "fast_sphere"
+    of = qu.frame(scene, CASES[scene][0], W, H)
+    _setup(renderer, scene, of)
+    g = axis_grid(scene)
+    _D, want = _want(scene, of, g)
+    V, S = len(want[0]), len(want[2])
+    h = renderer._h
+
+    def call(vcap, scap, arrays=True, coords=True, layer_arrays=True):
+        pos, uv, seg = np.full((V + 2, 3), -7.0, np.float32), np.full((V + 2, 2), -7.0, np.float32), np.full((S + 2, 2), 77, np.uint32)
+        lv, ls = np.full(LAYERS + 1, -7, np.int64), np.full(LAYERS + 1, -7, np.int64)
+        counts = sp.SliceCounts(-7, -7)
+        rc = _raw(L, h, g, vcap, scap, pos if arrays else None, uv if arrays and coords else None, seg if arrays else None, lv if layer_arrays else None,
+                  ls if layer_arrays else None, counts)
+        assert rc == 0 and (counts.vertices, counts.segments) == (V, S)
+        if layer_arrays:
+            assert np.array_equal(lv, want[3]) and np.array_equal(ls, want[4])
+        return pos, uv, seg
+
+    untouched = lambda pos, uv, seg: (pos == -7).all() and (uv == -7).all() and (seg == 77).all()  # noqa: E731
+    assert untouched(*call(0, 0, arrays=False))  # the counting call
+    assert untouched(*call(0, 0))
+    assert untouched(*call(V - 1, S)) and untouched(*call(V, S - 1)) and untouched(*call(V - 1, S + 5))
+    for vcap, scap in ((V, S), (V + 2, S + 2)):
+        pos, uv, seg = call(vcap, scap)
+        qu.assert_same("positions", pos[:V], want[0])
+        qu.assert_same("coords", uv[:V], want[1])
+        assert np.array_equal(seg[:S], want[2])
+        assert (pos[V:] == -7).all() and (uv[V:] == -7).all() and (seg[S:] == 77).all()  # nothing past the counts
+    pos, uv, seg = call(V, S, coords=False, layer_arrays=False)
+    qu.assert_same("positions", pos[:V], want[0])
+    assert (uv == -7).all() and np.array_equal(seg[:S], want[2])
+    # a stack that holds nothing: counts of zero, offsets of zero, and a fill that writes nothing
+    empty = dict(g, origin=(50.0, 50.0, 50.0))
+    pos, lv, ls, counts = np.full((4, 3), -7.0, np.float32), np.full(LAYERS + 1, -7, np.int64), np.full(LAYERS + 1, -7, np.int64), sp.SliceCounts(-7, -7)
+    seg = np.full((4, 2), 77, np.uint32)
+    assert _raw(L, h, empty, 4, 4, pos, None, seg, lv, ls, counts) == 0
+    assert (counts.vertices, counts.segments) == (0, 0) and not lv.any() and not ls.any() and (pos == -7).all() and (seg == 77).all()
+    got = renderer.extractSlices(**empty)
+    assert got[0].shape == (0, 3) and got[1].shape == (0, 2) and got[2].shape == (0, 2) and not got[3].any()
+
+
+def test_slices_leave_rendering_alone(renderer):
+    import torch
+
+    scene = "labyrinth"
+    of = qu.frame(scene, CASES[scene][0], W, H)
+    _setup(renderer, scene, of)
+    g, corner = axis_grid(scene), (-5.35, -0.3, -2.55)
+    _D, want = _want(scene, of, g)
+    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
+    s0, t0 = _stats(renderer), renderer.getTimings()
+    _assert_same("host", renderer.extractSlices(**g), want)
+    got = renderer.extractSlices(device=True, **g)
+    renderer.sync()
+    _assert_same("device", got, want)
+    assert _stats(renderer) == s0 and renderer.getTimings() == t0
+    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
+    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    # the stage timings stay the last mesh extraction's: a slice records none
+    ms = (ctypes.c_double * 4)()
+    import sdf_playground_amd as sp
+
+    renderer.setProfiling(True)
+    try:
+        renderer.extractMesh(corner, 0.1, (8, 8, 8))
+        assert sp.load_library().sdfr_mesh_get_timings(renderer._h, ctypes.byref(ms)) == 0
+        before = tuple(ms)
+        renderer.extractSlices(**g)
+        assert sp.load_library().sdfr_mesh_get_timings(renderer._h, ctypes.byref(ms)) == 0 and tuple(ms) == before
+    finally:
+        renderer.setProfiling(False)
+    # two frames in flight: the call runs on the lane of the frame submitted last, between extractions that leave device work behind
+    renderer.setFramesInFlight(2)
+    try:
+        imgs = [torch.empty((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        for k in range(4):
+            renderer.render(None, W, H, out=imgs[k % 2])
+            dev = renderer.extractSlices(device=True, **g)
+            dpos, _dn, _di = renderer.extractMesh(corner, 0.1, (16, 16, 16), device=True)
+            host = renderer.extractSlices(coords=False, **g)
+            renderer.sync()
+            _assert_same(("device", k), dev, want)
+            _assert_same(("host", k), host, want, coords=False)
+            assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
+            assert _stats(renderer) == s0
+    finally:
+        renderer.setFramesInFlight(1)
+
+
+def test_arguments(renderer):
+    import sdf_playground_amd as sp
+
+    L = sp.load_library()
+    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    h = renderer._h
+    INVALID, NO_SCENE = -1, -4
+    NULL_POINTER, BAD_ON_HOST, BAD_GRID = "null pointer", "on_host must be 0 or 1", "bad slice grid"
+    NEGATIVE_CAPACITY, NULL_ARRAY = "negative capacity", "null array with a capacity"
+    good = dict(origin=(-0.5, 0.9, -0.5), du=(0.1, 0.0, 0.0), dv=(0.0, 0.0, 0.1), dw=(0.0, 0.1, 0.0), dims=(8, 9), layers=3)
+    nan, inf = float("nan"), float("inf")
+
+    def call(handle=h, g=good, vcap=0, scap=0, positions=False, coords=False, segments=False, counts=True, on_host=1):
+        pos, uv, seg = np.full((64, 3), -7.0, np.float32), np.full((64, 2), -7.0, np.float32), np.full((64, 2), 77, np.uint32)
+        layers = g["layers"] if g and 0 < g["layers"] <= 65536 else 1
+        lv, ls = np.full(layers + 1, -7, np.int64), np.full(layers + 1, -7, np.int64)
+        c = sp.SliceCounts(-7, -7)
+        rc = _raw(L, handle, g, vcap, scap, pos if positions else None, uv if coords else None, seg if segments else None, lv, ls, c if counts else None, on_host)
+        if rc != 0:  # nothing is written on error
+            assert (c.vertices, c.segments) == (-7, -7) and (lv == -7).all() and (ls == -7).all() and (pos == -7).all() and (uv == -7).all() and (seg == 77).all()
+        return rc, L.sdfr_last_error(handle).decode() if handle and rc else ""
+
+    assert call() == (0, "")
+    bad = [dict(good, origin=(nan, 0.0, 0.0)), dict(good, du=(0.0, inf, 0.0)), dict(good, dv=(0.0, 0.0, nan)), dict(good, dw=(-inf, 0.0, 0.0)), dict(good, iso=nan),
+           dict(good, du=(0.0, 0.0, 0.0)), dict(good, dv=(0.0, 0.0, 0.0)), dict(good, dims=(0, 9)), dict(good, dims=(8, 16385)), dict(good, layers=0),
+           dict(good, layers=65537), dict(good, dims=(16384, 16384), layers=4)]
+    for g in bad:
+        assert call(g=g) == (INVALID, BAD_GRID), g
+    assert call(g=None) == (INVALID, NULL_POINTER) and call(counts=False) == (INVALID, NULL_POINTER)
+    assert call(on_host=2) == (INVALID, BAD_ON_HOST) and call(on_host=-1) == (INVALID, BAD_ON_HOST)
+    assert call(vcap=-1) == (INVALID, NEGATIVE_CAPACITY) and call(scap=-1) == (INVALID, NEGATIVE_CAPACITY)
+    assert call(vcap=1) == (INVALID, NULL_ARRAY) and call(scap=1) == (INVALID, NULL_ARRAY)
+    assert call(vcap=64, scap=1, positions=True) == (INVALID, NULL_ARRAY)
+    assert call(vcap=64, scap=64, positions=True, segments=True) == (0, "")  # coords may be null
+    # two faults at once: the text of the one checked first
+    assert call(g=None, on_host=2) == (INVALID, NULL_POINTER)
+    assert call(g=bad[0], on_host=2) == (INVALID, BAD_ON_HOST)
+    assert call(g=bad[7], vcap=-1) == (INVALID, BAD_GRID)
+    assert call(vcap=-1, scap=1) == (INVALID, NEGATIVE_CAPACITY) and call(vcap=1, scap=-1) == (INVALID, NEGATIVE_CAPACITY)
+    assert call(handle=None)[0] == INVALID
+    fresh = sp.SDFRenderer(0)
+    try:
+        assert call(handle=fresh._h)[0] == NO_SCENE
+        assert call(handle=fresh._h, g=bad[0]) == (INVALID, BAD_GRID) and call(handle=fresh._h, vcap=1) == (INVALID, NULL_ARRAY)  # the arguments come first
+    finally:
+        fresh.close()
