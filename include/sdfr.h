@@ -763,6 +763,81 @@ int sdfr_slice_extract(sdfr_renderer *r, const sdfr_slice_grid *grid, int64_t ve
 	float *coords /*[v][2] or NULL*/, uint32_t *segments /*[s][2]*/, int64_t *layer_vertices /*[layers+1], host, or NULL*/,
 	int64_t *layer_segments /*[layers+1], host, or NULL*/, sdfr_slice_counts *counts /*host, required*/, int on_host);
 
+/* ---- what a ray passes through: the intervals of a ray that lie inside the solid (no counterpart in the reference; DESIGN.md "Spans"),
+ *      on the field and with the inside test of sdfr_mesh_extract and sdfr_slice_extract, marched entirely on the GPU.  D is what
+ *      sdfr_query_distance returns at a point (the direction-free methods; the debug plane and show_objects apply as they do there); a
+ *      point is INSIDE iff D - iso < 0 (NaN is therefore outside).  A span's ends lie on the contours and the mesh, not dist_eps in
+ *      front of them.  All arithmetic is fp32; every operation is separate and unfused, in the order written here, so every number of the
+ *      result is defined exactly.
+ *
+ *      Sample: p(t)[c] = origin[c] + t * dir[c], one multiply then one add; s(t) = D(p(t)) - iso; inside iff s < 0.
+ *      Start: t_0 = 0.  If the ray is inside at t_0, a span opens with t_in = 0 and SDFR_SPAN_STARTS_INSIDE is set.
+ *      Step: a = fabsf(s_i); h = (a > min_step) ? a : min_step (NaN steps by min_step); t' = t_i + h;
+ *      t_(i+1) = (t' < t_max) ? t' : t_max; evaluate s_(i+1).
+ *      Crossing: if inside differs between the samples i and i + 1, u = s_i / (s_i - s_(i+1)), or 0.5f if !(u >= 0 && u <= 1), and
+ *      t* = t_i + u * (t_(i+1) - t_i).  A crossing into the solid opens a span (t_in = t*), a crossing out closes it (t_out = t*).
+ *      End: the march ends after the sample at t_max; or, that sample not yet made, after max_steps evaluations, and then
+ *      SDFR_SPAN_OUT_OF_STEPS is set (a ray whose max_steps-th sample is the one at t_max is not out of steps).  A span still open is
+ *      closed at t_end, the t of the last evaluation, and SDFR_SPAN_ENDS_INSIDE is set.
+ *      Storage: span k (0-based, in order) is stored at spans[i * max_spans + k] if k < max_spans; later spans are counted and summed
+ *      but not stored.  The slots from min(spans, max_spans) up to max_spans are written as zeros -- all of them for an item without an
+ *      answer.  With max_spans = 0, `spans` may be NULL.
+ *      Invalid items: if any component of origin or dir is not finite, or dir is (0, 0, 0), the item gets valid = 0 and no evaluation.
+ *
+ *      What the march rests on: |D - iso| never overestimates the distance to the level set D = iso, outside and inside -- the contract
+ *      that sphere tracing, and refraction in the driver, already need.  Under it a sign change can only fall into a step of length
+ *      min_step, up to rounding: no feature thicker than min_step along the ray is missed, and a crossing is located to second order in
+ *      min_step.  Where a scene breaks the contract the result is still exactly defined by the words above.
+ *
+ *        - t, t_in and t_out are in units of |dir|: dir is used as given, not normalised, and the steps are taken in t.  A step of h
+ *          in t is h * |dir| in space, so the guarantee above is for |dir| <= 1 and the bracket of a crossing is min_step * |dir| long;
+ *          pixels' rays have unit length, a mesh's normals should.
+ *        - the entries are queries in every respect listed for them: on_host, what is latched, the stream and two frames in flight, no
+ *          effect on stats, timings or the row order, n = 0.  n * max(max_spans, 1) <= 2^30.
+ *        - errors, in the order they win: SDFR_ERR_INVALID_ARGUMENT "null pointer" (params, summaries, a required input; whatever n
+ *          is); on_host not 0 or 1; "bad span parameters"; an item count that is negative or too large; the frame size, or the reach;
+ *          a NULL `spans` with max_spans > 0; without a pixel list an n that is not width * height.  Then SDFR_ERR_NO_SCENE.  Nothing
+ *          is written on error. -------------------------------------------------------------------------------------------------------- */
+typedef struct sdfr_span_params
+{
+	float t_max;       /* finite, >= 0; 0: limits.range */
+	float min_step;    /* finite, > 0 */
+	float iso;         /* finite */
+	int32_t max_steps; /* 1 .. 1<<20: scene evaluations per item, the one at t = 0 included */
+	int32_t max_spans; /* 0 .. 64: spans stored per item */
+} sdfr_span_params;
+typedef struct sdfr_span
+{
+	float t_in, t_out;
+} sdfr_span; /* 8 bytes; in units of |dir| */
+typedef struct sdfr_span_summary
+{
+	uint32_t crossings;  /* sign changes seen, all of them */
+	uint32_t spans;      /* spans opened, all of them; stored = min(spans, max_spans) */
+	uint32_t steps;      /* scene evaluations made */
+	int32_t valid;       /* 1 answered; 0 nothing to answer; -1 invalid item (a pixel outside the frame); unless 1 all other words 0 */
+	float inside_length; /* sum of (t_out - t_in) over ALL spans, in the order they close */
+	float t_end;         /* t of the last evaluation */
+	uint32_t flags;      /* SDFR_SPAN_* */
+	uint32_t reserved;   /* 0 */
+} sdfr_span_summary;     /* 32 bytes: two 16-byte stores per item (device arrays aligned to 16 bytes; any other alignment: word stores) */
+#define SDFR_SPAN_STARTS_INSIDE 1u
+#define SDFR_SPAN_ENDS_INSIDE 2u
+#define SDFR_SPAN_OUT_OF_STEPS 4u
+
+/* The spans of rays origins[i] + t * dirs[i], 0 <= t <= t_max. */
+int sdfr_query_ray_spans(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, const sdfr_span_params *params,
+	sdfr_span_summary *summaries, sdfr_span *spans /* [n][max_spans], or NULL with max_spans = 0 */, int on_host);
+/* The spans of pixels' primary rays: the origin and direction sdfr_pick builds for pixel (x, y) of a width x height frame of the current
+ * camera.  pixels_xy = NULL: the whole frame in row-major order, n = width * height (a wave takes an 8 x 8 tile).  A pixel outside the
+ * frame gets valid = -1. */
+int sdfr_pick_spans(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy /* or NULL: the whole frame */,
+	const sdfr_span_params *params, sdfr_span_summary *summaries, sdfr_span *spans, int on_host);
+/* The spans of sdfr_mesh_surfaces' rays: origin = positions + reach * normals (one multiply, then one add), dir = -normals as given, reach
+ * finite and > 0.  The first stored span is then the wall under the vertex, and its length is the thickness there. */
+int sdfr_mesh_spans(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, const sdfr_span_params *params,
+	sdfr_span_summary *summaries, sdfr_span *spans, int on_host);
+
 /* ---- a texture atlas of an extracted mesh (no counterpart in the reference; DESIGN.md "Texture atlas"): one square tile of texels per
  *      quad of the mesh, baked on the GPU.  Surface nets emits quads: triangles 2q and 2q + 1 are (q0, q1, q2) and (q0, q2, q3) of one
  *      quad, so a tile per quad needs no chart cutting and no packing search, and bilinear filtering inside a quad never leaves its tile.

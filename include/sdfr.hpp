@@ -215,6 +215,25 @@ public:
 				on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// The intervals of rays that lie inside the solid (sdfr_query_ray_spans, sdfr_pick_spans, sdfr_mesh_spans in sdfr.h), with this
+	// renderer's variables and time: one summary per item, and its first params.max_spans spans (spans may be null if that is 0).
+	// pickSpans with pixels_xy null: every pixel of the frame, n = width * height.
+	bool querySpans(int64_t n, const float *origins, const float *dirs, const sdfr_span_params &params, sdfr_span_summary *summaries, sdfr_span *spans,
+		bool on_host = true)
+	{
+		return handle && pushState() && sdfr_query_ray_spans(handle, n, origins, dirs, &params, summaries, spans, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool pickSpans(int width, int height, int64_t n, const int32_t *pixels_xy, const sdfr_span_params &params, sdfr_span_summary *summaries, sdfr_span *spans,
+		bool on_host = true)
+	{
+		return handle && pushState() && sdfr_pick_spans(handle, width, height, n, pixels_xy, &params, summaries, spans, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool meshSpans(int64_t n, const float *positions, const float *normals, float reach, const sdfr_span_params &params, sdfr_span_summary *summaries,
+		sdfr_span *spans, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_mesh_spans(handle, n, positions, normals, reach, &params, summaries, spans, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// The texture atlas of an extracted mesh (sdfr_atlas_layout, sdfr_atlas_uvs, sdfr_atlas_texels, sdfr_atlas_bake in sdfr.h): one square
 	// tile of texels per quad.  atlasTexels looks at the mesh alone; bakeAtlas looks at every texel as meshSurfaces / meshLighting look at
 	// a vertex, with this renderer's variables and time.  layers: SDFR_ATLAS_*; a plane that is not asked for may be null.

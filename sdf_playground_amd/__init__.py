@@ -148,6 +148,17 @@ LIGHT_SAMPLE_DTYPE = np.dtype([("state", np.int32), ("flags", np.uint32), ("segm
                                ("influenced", np.float32, (3,)), ("specular_factor", np.float32), ("delivered", np.float32, (3,)),
                                ("reserved1", np.float32)])
 assert LIGHT_SAMPLE_DTYPE.itemsize == 80
+# sdfr_span_summary (include/sdfr.h): what a ray passes through, 32 bytes; its spans are [n, max_spans, 2] float32 (t_in, t_out)
+SPAN_SUMMARY_DTYPE = np.dtype([("crossings", np.uint32), ("spans", np.uint32), ("steps", np.uint32), ("valid", np.int32), ("inside_length", np.float32),
+                               ("t_end", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
+assert SPAN_SUMMARY_DTYPE.itemsize == 32
+SPAN_STARTS_INSIDE, SPAN_ENDS_INSIDE, SPAN_OUT_OF_STEPS = 1, 2, 4
+
+
+class SpanParams(ctypes.Structure):  # sdfr_span_params
+    _fields_ = [("t_max", ctypes.c_float), ("min_step", ctypes.c_float), ("iso", ctypes.c_float), ("max_steps", ctypes.c_int32), ("max_spans", ctypes.c_int32)]
+
+
 LIGHT_DIRECTIONAL = 1
 LIGHT_UNUSED, LIGHT_NO_CHAIN, LIGHT_BLOCKED, LIGHT_ESCAPED = 0, 1, 2, 3
 
@@ -170,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_mesh_extract_sharp",
     "sdfr_mesh_survey", "sdfr_mesh_fit",
     "sdfr_slice_extract",
+    "sdfr_query_ray_spans", "sdfr_pick_spans", "sdfr_mesh_spans",
 ]
 
 _lib = None
@@ -284,6 +296,9 @@ def load_library():
     L.sdfr_mesh_survey.argtypes = [vp, ctypes.POINTER(MeshGrid), cf, ctypes.POINTER(MeshSurvey)]
     L.sdfr_mesh_fit.argtypes = [vp, ctypes.POINTER(MeshGrid), ci, ci, ctypes.POINTER(MeshFit)]
     L.sdfr_slice_extract.argtypes = [vp, ctypes.POINTER(SliceGrid), i64, i64, vp, vp, vp, vp, vp, ctypes.POINTER(SliceCounts), ci]
+    L.sdfr_query_ray_spans.argtypes = [vp, i64, vp, vp, ctypes.POINTER(SpanParams), vp, vp, ci]
+    L.sdfr_pick_spans.argtypes = [vp, ci, ci, i64, vp, ctypes.POINTER(SpanParams), vp, vp, ci]
+    L.sdfr_mesh_spans.argtypes = [vp, i64, vp, vp, cf, ctypes.POINTER(SpanParams), vp, vp, ci]
     L.sdfr_atlas_layout.argtypes = [i64, ci, ci, ctypes.POINTER(Atlas)]
     L.sdfr_atlas_uvs.argtypes = [ctypes.POINTER(Atlas), vp]
     L.sdfr_atlas_texels.argtypes = [vp, ctypes.POINTER(Atlas), i64, vp, vp, vp, vp, vp, vp, ci]
@@ -960,6 +975,80 @@ class SDFRenderer:
             if (again.vertices, again.segments) != (v, s):
                 raise SdfrError(-9, "the slices changed between the counting and the filling call")
         return pos, uv, seg, layer_v, layer_s
+
+    # ---- what a ray passes through (sdfr_query_ray_spans / sdfr_pick_spans / sdfr_mesh_spans; DESIGN.md "Spans") ----------------------------
+    # -> (summaries, spans): numpy, SPAN_SUMMARY_DTYPE records [n] and float32 [n, max_spans, 2] (t_in, t_out); with device tensors in, or
+    # device=True, device tensors: int32 [n, 8] (inside_length and t_end, columns 4 and 5, are read with .view(torch.float32)) and float32
+    # [n, max_spans, 2], enqueued on the handle's stream.
+    def _spans(self, call, n, like, device, min_step, t_max, iso, max_steps, max_spans, *scalars_and_inputs):
+        params = SpanParams(float(t_max), float(min_step), float(iso), int(max_steps), int(max_spans))
+        slots = min(max(int(max_spans), 0), 64)  # (a count the library refuses still gets its error from the library)
+        if like is None and not device:
+            s, sp = np.zeros(n, SPAN_SUMMARY_DTYPE), np.zeros((n, slots, 2), np.float32)
+            ps, psp = s.ctypes.data_as(ctypes.c_void_p), sp.ctypes.data_as(ctypes.c_void_p) if slots else None
+        else:
+            import torch
+
+            dev = like.device if like is not None else torch.device("cuda", self.device)
+            if n == 0:  # (an empty tensor has no address)
+                return torch.zeros((0, 8), dtype=torch.int32, device=dev), torch.zeros((0, slots, 2), dtype=torch.float32, device=dev)
+            # (the kernel writes every word of every summary and every span slot)
+            s = torch.empty((n, 8), dtype=torch.int32, device=dev)
+            sp = torch.empty((n, slots, 2), dtype=torch.float32, device=dev)
+            ps, psp = ctypes.c_void_p(s.data_ptr()), ctypes.c_void_p(sp.data_ptr()) if slots else None
+        self._check(call(self._h, *scalars_and_inputs, ctypes.byref(params), ps, psp, 0 if (like is not None or device) else 1))
+        if self._span_uploads is not None:  # uploaded here: they may go only when the launch has read them
+            self.sync()
+            self._span_uploads = None
+        return s, sp
+
+    def _span_inputs(self, device, *specs):
+        """_inputs; with device=True numpy inputs are uploaded first, and such a call synchronises before it returns (_spans): the
+        uploads are this call's own and must outlive the launch, which runs on the handle's stream"""
+        self._span_uploads = None
+        if device and not hasattr(specs[0][0], "data_ptr"):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            specs = [(torch.as_tensor(np.ascontiguousarray(a, dt).reshape(-1, c), device=dev), dt, c, name) for a, dt, c, name in specs]
+            n, pointers, like = self._inputs(*specs)
+            self._span_uploads = [a for a, _dt, _c, _name in specs]
+            return n, pointers, like
+        return self._inputs(*specs)
+
+    def querySpans(self, origins, dirs, min_step, t_max=0.0, iso=0.0, max_steps=4096, max_spans=4, device=False):
+        """The intervals of rays origins [n, 3] + t * dirs [n, 3], 0 <= t <= t_max (0: limits.range; dirs as given, t in units of |dir|),
+        that lie inside the solid (distance < iso), marched on the GPU in steps of max(|distance - iso|, min_step) -> (summaries, spans)."""
+        n, (o, d), like = self._span_inputs(device, (origins, np.float32, 3, "origins"), (dirs, np.float32, 3, "dirs"))
+        return self._spans(self._L.sdfr_query_ray_spans, n, like, device, min_step, t_max, iso, max_steps, max_spans, n, o, d)
+
+    def pickSpans(self, pixels_xy, width, height, min_step, t_max=0.0, iso=0.0, max_steps=4096, max_spans=4, device=False):
+        """querySpans along the primary rays of pixels [n, 2] of a width x height frame of the current camera (as pick; valid = -1 outside the
+        frame).  pixels_xy=None: every pixel of the frame in row-major order (height * width items)."""
+        width, height = int(width), int(height)
+        if pixels_xy is None:
+            n, px, like, self._span_uploads = width * height, None, None, None
+        else:
+            n, (px,), like = self._span_inputs(device, (pixels_xy, np.int32, 2, "pixels_xy"))
+        return self._spans(self._L.sdfr_pick_spans, n, like, device, min_step, t_max, iso, max_steps, max_spans, width, height, n, px)
+
+    def meshSpans(self, positions, normals, reach, min_step, t_max=0.0, iso=0.0, max_steps=4096, max_spans=4, device=False):
+        """querySpans along sdfr_mesh_surfaces' rays: from positions [n, 3] + reach * normals [n, 3] along -normals.  The first span is the
+        wall under the vertex."""
+        n, (p, nr), like = self._span_inputs(device, (positions, np.float32, 3, "positions"), (normals, np.float32, 3, "normals"))
+        return self._spans(self._L.sdfr_mesh_spans, n, like, device, min_step, t_max, iso, max_steps, max_spans, n, p, nr, float(reach))
+
+    def meshThickness(self, positions, normals, reach, min_step, t_max=0.0, iso=0.0, max_steps=4096):
+        """The wall thickness under mesh vertices: the length of meshSpans' first span, float32 [n] in units of |normal|; inf where there is
+        none (the ray meets no solid, or the item is invalid) or where that span is closed only by the end of the march (ENDS_INSIDE)."""
+        s, sp = self.meshSpans(positions, normals, reach, min_step, t_max, iso, max_steps, max_spans=1)
+        if hasattr(s, "data_ptr"):
+            self.sync()
+            s, sp = s.cpu().numpy().view(SPAN_SUMMARY_DTYPE).reshape(-1), sp.cpu().numpy()
+        out = np.full(len(s), np.inf, np.float32)
+        closed = (s["valid"] == 1) & (s["spans"] >= 1) & ~((s["spans"] == 1) & ((s["flags"] & SPAN_ENDS_INSIDE) != 0))
+        out[closed] = sp[closed, 0, 1] - sp[closed, 0, 0]
+        return out
 
     # ---- the texture atlas of a mesh (sdfr_atlas_texels / sdfr_atlas_bake; DESIGN.md "Texture atlas") -------------------------------
     def _atlas_inputs(self, positions, normals, indices, device):

@@ -34,6 +34,9 @@ the G-buffer: the openness at each pixel's hit as float32, NaN where there is no
 --slice writes the scene's contours (distance == --slice-iso) on planes across --slice-axis inside --slice-box as an SVG, one group per
 layer: marching squares on cells of edge --slice-cell (SDFRenderer.extractSlices, chainContours, svg.py).  The box is cut into slabs
 --slice-step thick (or --slice-layers of them; default: one, the whole box) and each is sliced through its middle.
+--xray writes how much solid each pixel's primary ray passes through, as the grey 255 * (1 - exp(-K * length)) with K = --xray-density:
+the inside length of SDFRenderer.pickSpans over the whole frame, marched on the GPU in steps of --xray-step at the least.
+--mesh-thickness T_MAX colours the vertices of --mesh by the thickness of the wall under them over T_MAX (SDFRenderer.meshThickness).
 """
 import argparse
 import math
@@ -220,7 +223,20 @@ def make_parser():
     ap.add_argument("--slice-layers", type=int, metavar="N", help="instead of --slice-step: N layers, H = the extent / N")
     ap.add_argument("--slice-iso", type=float, default=0.0, metavar="V", help="the contour is distance == V (default 0)")
     ap.add_argument("--gbuffer-lighting", action="store_true", help="with --gbuffer: add `lit`, `own`, `direct` and the used, traced and visible light masks")
+    ap.add_argument("--xray", metavar="OUT.png", help="write how much solid every pixel's ray passes through as a grey image (needs --xray-step)")
+    ap.add_argument("--xray-step", type=float, metavar="H", help="the march's smallest step: no wall thicker than H along a ray is missed")
+    ap.add_argument("--xray-density", type=float, metavar="K", help="grey = 255 * (1 - exp(-K * length)) (default 1)")
+    ap.add_argument("--mesh-thickness", type=float, metavar="T_MAX", help="with --mesh: a grey per vertex, the wall thickness under it over T_MAX "
+                    "(white: T_MAX or more) (instead of --mesh-colors / --mesh-ao / --mesh-lit)")
     return ap
+
+
+def xray_image(inside_length, w, h, density):
+    """--xray's picture [h, w, 4] uint8 from pickSpans' inside_length [h * w]: grey = 255 * (1 - exp(-density * length)), rounded; a
+    length that is not finite counts as opaque"""
+    length = np.nan_to_num(np.asarray(inside_length, np.float64), nan=np.inf, posinf=np.inf, neginf=0.0)
+    grey = np.rint(255.0 * (1.0 - np.exp(-density * np.maximum(length, 0.0)))).astype(np.uint8).reshape(h, w)
+    return np.stack([grey, grey, grey, np.full_like(grey, 255)], -1)
 
 
 GBUFFER_AO_BIAS = 0.01  # how far off a pixel's hit --gbuffer-ao starts its rays: a hundred dist_eps at the default limits
@@ -303,6 +319,22 @@ def main(argv=None):
             mesh_grid = mesh_grid_from_box(a.mesh_box, a.mesh_cell, 1 << 20 if a.mesh_fit else 1024)
         except ValueError as e:
             ap.error(str(e))
+    if a.mesh_thickness is not None:
+        if not a.mesh:
+            ap.error("--mesh-thickness needs --mesh")
+        if not (a.mesh_thickness > 0 and math.isfinite(a.mesh_thickness)):
+            ap.error("--mesh-thickness must be finite and > 0")
+        if a.mesh_colors or a.mesh_lit or a.mesh_ao is not None:
+            ap.error("--mesh-thickness excludes --mesh-colors, --mesh-lit and --mesh-ao")
+    if a.xray:
+        if a.xray_step is None:
+            ap.error("--xray needs --xray-step")
+        if not (a.xray_step > 0 and math.isfinite(a.xray_step)):
+            ap.error("--xray-step must be finite and > 0")
+        if a.xray_density is not None and not (a.xray_density > 0 and math.isfinite(a.xray_density)):
+            ap.error("--xray-density must be finite and > 0")
+    elif a.xray_step is not None or a.xray_density is not None:
+        ap.error("--xray-step and --xray-density need --xray")
     slice_grid = None
     if a.slice:
         if a.slice_box is None or a.slice_cell is None:
@@ -383,6 +415,12 @@ def main(argv=None):
             from .obj import occlusion_colors
 
             colors_written = occlusion_colors(occ[0], colors)
+        elif a.mesh_thickness is not None:
+            from .obj import thickness_colors
+
+            # from one cell outside the vertex along -normal, in steps of a quarter cell at the least, T_MAX beyond the vertex
+            thick = r.meshThickness(pos, nrm, a.mesh_cell, 0.25 * a.mesh_cell, t_max=a.mesh_cell + a.mesh_thickness, iso=a.mesh_iso)
+            colors_written = thickness_colors(thick, a.mesh_thickness)
         else:
             colors_written = colors
         uvs = mtl = None
@@ -410,7 +448,11 @@ def main(argv=None):
             print("%d of %d vertices found no surface within 2 cells and are grey" % (missing, len(pos)))
         if occ:
             print("ambient occlusion within %g: mean openness %.3f" % (a.mesh_ao, float(1.0 - occ[0]["occluded"][occ[0]["valid"] == 1].mean() / 64.0) if (occ[0]["valid"] == 1).any() else 1.0))
-        if not a.out and not a.out_hdr and not a.gbuffer:
+        if a.mesh_thickness is not None:
+            walls = thick[np.isfinite(thick)]
+            print("wall thickness up to %g: %d of %d vertices have a wall that ends, median %.4g" % (
+                a.mesh_thickness, len(walls), len(thick), float(np.median(walls)) if len(walls) else float("inf")))
+        if not a.out and not a.out_hdr and not a.gbuffer and not a.xray:
             r.close()
             return 0
     if slice_grid:
@@ -422,6 +464,16 @@ def main(argv=None):
         write_svg(a.slice, uv, chains, dims, a.slice_cell, title="%s, time %g, axis %s, cell %g, iso %g" % (a.scene, a.time, a.slice_axis, a.slice_cell, a.slice_iso))
         print("%s: %d vertices, %d segments, %d chains (%d closed) in %d layers of %dx%d cells -> %s" % (
             a.scene, len(pos), len(seg), sum(len(c) for c in chains), sum(1 for c in chains for _i, closed in c if closed), n_layers, dims[0], dims[1], a.slice))
+        if not a.out and not a.out_hdr and not a.gbuffer and not a.xray:
+            r.close()
+            return 0
+    if a.xray:
+        r.setCamera(cam)
+        density = a.xray_density if a.xray_density is not None else 1.0
+        summaries, _none = r.pickSpans(None, w, h, a.xray_step, max_spans=0)
+        write_png(a.xray, xray_image(summaries["inside_length"], w, h, density))
+        print("%s %dx%d: X-ray, step %g, density %g, %d rays ran out of steps -> %s" % (
+            a.scene, w, h, a.xray_step, density, int(((summaries["flags"] & sp.SPAN_OUT_OF_STEPS) != 0).sum()), a.xray))
         if not a.out and not a.out_hdr and not a.gbuffer:
             r.close()
             return 0

@@ -9,6 +9,7 @@
 #include "sdfr_hlsl_translate.h"
 #include "sdfr_mesh_plan.h"
 #include "sdfr_slice_plan.h"
+#include "sdfr_span_plan.h"
 #include "sdfr_occlusion.h"
 #include "sdfr_query.h"
 #include "sdfr_query_plan.h"
@@ -910,6 +911,85 @@ int sdfr_mesh_lighting(sdfr_renderer *r, int64_t n, const float *positions, cons
 		QueryRequest c = with_lighting(ray_request(n, positions, normals, reach, hits, nullptr, false, on_host), lighting, lights);
 		c.q.kind = QUERY_MESH;
 		return query_impl(r, c);
+	});
+}
+
+// ---- the span queries (the definition: include/sdfr.h; the plan: sdfr_span_plan.h; the stage function: sdfr_span.h; the kernel:
+// sdfr_query_kernel.h), calls of the queries' protocol with arguments of their own (SpanArgs)
+static_assert(sizeof(sdfr_span_params) == sizeof(SpanParams) && offsetof(sdfr_span_params, min_step) == offsetof(SpanParams, min_step) &&
+		offsetof(sdfr_span_params, iso) == offsetof(SpanParams, iso) && offsetof(sdfr_span_params, max_steps) == offsetof(SpanParams, max_steps) &&
+		offsetof(sdfr_span_params, max_spans) == offsetof(SpanParams, max_spans),
+	"sdfr_span_params is the plan's SpanParams");
+static_assert(sizeof(sdfr_span_summary) == 4 * SPAN_SUMMARY_WORDS && offsetof(sdfr_span_summary, valid) == 12 && offsetof(sdfr_span_summary, inside_length) == 16 &&
+		offsetof(sdfr_span_summary, flags) == 24 && sizeof(sdfr_span) == 8,
+	"sdfr_span_summary is the span kernel's 8-word record, sdfr_span its two floats");
+static_assert(SDFR_SPAN_STARTS_INSIDE == SPAN_STARTS_INSIDE && SDFR_SPAN_ENDS_INSIDE == SPAN_ENDS_INSIDE && SDFR_SPAN_OUT_OF_STEPS == SPAN_OUT_OF_STEPS, "the flag bits are the kernel's");
+static int span_impl(sdfr_renderer *r, const SpanRequest &c)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	const SpanPlan p = plan_spans(c, r->U.range);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	if (p.nothing_to_do) return SDFR_OK;
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, true, p.width, p.height, U, stream);
+	if (rc != SDFR_OK) return rc;
+
+	SpanArgs s = p.a;
+	Carving st;
+	if (c.on_host)
+	{
+		StagedArray arrays[SPAN_STAGE_PIECES];
+		for (int k = 0; k < SPAN_STAGE_PIECES; ++k)
+			arrays[k] = {reinterpret_cast<char *>(&s) + k_span_stage_slots[s.kind == QUERY_PICK ? 1 : 0][k], p.bytes[k], k < SPAN_STAGE_INPUTS};
+		rc = stage_host_arrays(r, st, arrays, SPAN_STAGE_PIECES, stream);
+		if (rc != SDFR_OK) return rc;
+	}
+	KernelRef k;
+	rc = loaded_query_kernel(r, QUERY_KERNEL_SPANS, U, k);
+	if (rc != SDFR_OK) return rc;
+	const hipError_t e = launch_query_spans(k, U, s, p.blocks, stream);
+	if (e != hipSuccess) return hip_fail(r, e, "span launch");
+	return c.on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
+}
+static SpanRequest span_request(int kind, int64_t n, const void *in0, const void *in1, const sdfr_span_params *params, sdfr_span_summary *summaries, sdfr_span *spans, int on_host)
+{
+	SpanRequest c = {};
+	c.kind = kind;
+	c.n = n;
+	c.in0 = in0;
+	c.in1 = in1;
+	c.params = reinterpret_cast<const SpanParams *>(params);
+	c.summaries = summaries;
+	c.spans = spans;
+	c.on_host = on_host;
+	return c;
+}
+
+int sdfr_query_ray_spans(sdfr_renderer *r, int64_t n, const float *origins, const float *dirs, const sdfr_span_params *params, sdfr_span_summary *summaries,
+	sdfr_span *spans, int on_host)
+{
+	return guarded(r, [&]() -> int { return span_impl(r, span_request(QUERY_RAYS, n, origins, dirs, params, summaries, spans, on_host)); });
+}
+
+int sdfr_pick_spans(sdfr_renderer *r, int width, int height, int64_t n, const int32_t *pixels_xy, const sdfr_span_params *params, sdfr_span_summary *summaries,
+	sdfr_span *spans, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		SpanRequest c = span_request(QUERY_PICK, n, pixels_xy, nullptr, params, summaries, spans, on_host);
+		c.width = width;
+		c.height = height;
+		return span_impl(r, c);
+	});
+}
+
+int sdfr_mesh_spans(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, const sdfr_span_params *params,
+	sdfr_span_summary *summaries, sdfr_span *spans, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		SpanRequest c = span_request(QUERY_MESH, n, positions, normals, params, summaries, spans, on_host);
+		c.reach = reach;
+		return span_impl(r, c);
 	});
 }
 

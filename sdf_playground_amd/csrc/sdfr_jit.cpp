@@ -88,6 +88,7 @@ const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_
 	{"sdfr_jit_bake_atlas", "atlas_bake_kernel", "AtlasKernelArgs"},
 	{"sdfr_jit_mesh_sharp", "mesh_sharp_kernel", "MeshSharpKernelArgs"},
 	{"sdfr_jit_query_slices", "query_slices_kernel", "SliceKernelArgs"},
+	{"sdfr_jit_query_spans", "query_spans_kernel", "SpanKernelArgs"},
 };
 
 } // namespace

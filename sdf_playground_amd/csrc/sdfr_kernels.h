@@ -103,6 +103,10 @@ hipError_t launch_slice_count(const SliceGrid &g, const float *lattice, uint32_t
 hipError_t launch_slice_emit(const SliceGrid &g, const float *lattice, const uint32_t *point_vertex, const uint32_t *cell_segment, float *positions, float *coords,
 	uint32_t *segments, hipStream_t stream);
 
+// The span queries (sdfr_span.h; the plan: sdfr_span_plan.h): a scene's span kernel (QUERY_KERNEL_SPANS) for U over the items of `s`, every
+// pointer device memory, in `blocks` blocks of one wave (span_blocks).
+hipError_t launch_query_spans(const KernelRef &k, const FrameU &U, const SpanArgs &s, uint32_t blocks, hipStream_t stream);
+
 // The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
 // per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes
 // instead the image of a bake without quads.  launch_atlas_bake: a scene's bake kernel (QUERY_KERNEL_ATLAS) for U.

@@ -516,6 +516,15 @@ hipError_t launch_query_slices(const KernelRef &k, const FrameU &U, const SliceA
 	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
 }
 
+hipError_t launch_query_spans(const KernelRef &k, const FrameU &U, const SpanArgs &s, uint32_t blocks, hipStream_t stream)
+{
+	SpanKernelArgs a;
+	a.U = U;
+	a.s = s;
+	void *args[] = {&a};
+	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
+}
+
 hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
 {
 	AtlasKernelArgs a;

@@ -46,6 +46,13 @@ struct SliceKernelArgs
 	SliceArgs g;
 };
 
+// ... and the span kernel (SpanArgs: sdfr_query_args.h)
+struct SpanKernelArgs
+{
+	FrameU U;
+	SpanArgs s;
+};
+
 // the driver's normal at pos (pshader_sdf.hlsl:164-177, 320-330): map_normal with the NormalOutput preloaded {grad_eps, 0, false};
 // its normal if it sets use_normal, else the three forward differences against `baseline`, normalised
 template <class Scene, bool DBG>

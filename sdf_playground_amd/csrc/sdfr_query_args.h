@@ -39,7 +39,7 @@ static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offseto
 static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
 // A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_SLICES = 8, QUERY_KERNEL_KINDS = 9 };
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_SLICES = 8, QUERY_KERNEL_SPANS = 9, QUERY_KERNEL_KINDS = 10 };
 
 // One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
@@ -104,5 +104,26 @@ struct SliceArgs
 };
 static_assert(sizeof(SliceArgs) == 72 && __builtin_offsetof(SliceArgs, du) == 12 && __builtin_offsetof(SliceArgs, dw) == 36 && __builtin_offsetof(SliceArgs, pu) == 48, "");
 static_assert(__builtin_offsetof(SliceArgs, rows) == 60 && __builtin_offsetof(SliceArgs, out) == 64, "SliceArgs is a kernel argument");
+
+// One span launch (sdfr_kernels.h: launch_query_spans; sdfr_query_ray_spans, sdfr_pick_spans, sdfr_mesh_spans): the intervals of each item's
+// ray that lie inside the solid (sdfr_span.h).  kind: QUERY_RAYS (pos, dir), QUERY_PICK (pixels), QUERY_FRAME (every pixel of the frame,
+// n = width * height, a wave per 8 x 8 tile) or QUERY_MESH (pos, dir = positions, normals; reach); every other input is null.
+// summaries: 8 words per item, the layout of sdfr_span_summary; spans: [n][max_spans][2] floats, null if max_spans = 0.
+// n * max(max_spans, 1) <= 2^30.
+struct SpanArgs
+{
+	int32_t kind, n;
+	const float *pos, *dir;
+	const int32_t *pixels;
+	float reach;                // meshes
+	float t_max, min_step, iso; // t_max: the effective one, never the 0 that stands for limits.range
+	int32_t max_steps, max_spans;
+	uint32_t *summaries;
+	float *spans;
+};
+static_assert(sizeof(SpanArgs) == 72 && __builtin_offsetof(SpanArgs, n) == 4 && __builtin_offsetof(SpanArgs, pos) == 8 && __builtin_offsetof(SpanArgs, dir) == 16, "");
+static_assert(__builtin_offsetof(SpanArgs, pixels) == 24 && __builtin_offsetof(SpanArgs, reach) == 32 && __builtin_offsetof(SpanArgs, t_max) == 36, "");
+static_assert(__builtin_offsetof(SpanArgs, iso) == 44 && __builtin_offsetof(SpanArgs, max_steps) == 48 && __builtin_offsetof(SpanArgs, max_spans) == 52, "");
+static_assert(__builtin_offsetof(SpanArgs, summaries) == 56 && __builtin_offsetof(SpanArgs, spans) == 64, "SpanArgs is a kernel argument");
 
 } // namespace sdfr

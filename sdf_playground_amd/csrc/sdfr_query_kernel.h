@@ -13,6 +13,7 @@
 #include "sdfr_atlas.h"
 #include "sdfr_mesh_sharp.h"
 #include "sdfr_slice.h"
+#include "sdfr_span.h"
 
 namespace sdfr {
 
@@ -400,6 +401,102 @@ __device__ __forceinline__ void query_slices_kernel(const SliceKernelArgs &a)
 	const vec3 p = V3(slice_coord(g.origin, g.du, g.dv, g.dw, 0, (int)i, (int)j, (int)l), slice_coord(g.origin, g.du, g.dv, g.dw, 1, (int)i, (int)j, (int)l),
 		slice_coord(g.origin, g.du, g.dv, g.dw, 2, (int)i, (int)j, (int)l));
 	g.out[i + pu * (j + pv * l)] = query_point<Scene, DBG>(a.U, p, nullptr); // (the index is < 2^30)
+}
+
+// The span queries (sdfr_span.h; sdfr_query_ray_spans, sdfr_pick_spans, sdfr_mesh_spans): the surface kernel's items, mapped to lanes the
+// same way (the lines are repeated, not shared, as in the lighting kernel) -> `summaries` and, unless max_spans is 0, `spans`.  One lane
+// per item marches its ray from t = 0 to t_max with the scene's point query (query_point: the direction-free methods), whose per-ray
+// set-up -- the debug flags and Scene::ray_setup for no direction -- is made once per lane, and whose evaluation stands once in the loop
+// of span_item.  The lanes of a wave step independently, so a wave is as long as its longest ray.  A span leaves as one 8-byte store when
+// it closes, the summary as two 16-byte stores at the end; nothing is shared between lanes: no LDS, no atomics.
+// Both go through vector types of the compiler, one store instruction each from the front end on: written as an assignment of a uint4 or
+// float2 struct, the aligned and the word path hold the same member stores, which the optimiser merges across the branch into word
+// stores (the ISA had 21 global_store_dword and nothing wider).  query_store itself stays as it is: the other kernels' code is built on it.
+typedef uint32_t span_u32x4 __attribute__((ext_vector_type(4)));
+typedef float span_f32x2 __attribute__((ext_vector_type(2)));
+template <class Scene, bool DBG>
+struct SpanSceneDistance
+{
+	const FrameU &U;
+	DebugFlags F;
+	typename Scene::RayInv R;
+	__device__ __forceinline__ float operator()(vec3 p) const
+	{
+		const vec3 zero = V3s(0.f);
+		return scene_distance<Scene, DBG>(U, F, R, p, zero, false, 0.f, zero, zero);
+	}
+};
+struct SpanStore
+{
+	float *item; // the item's max_spans slots of two floats; never used when max_spans is 0
+	bool aligned;
+	__device__ __forceinline__ void operator()(int k, float t_in, float t_out) const
+	{
+		if (aligned)
+		{
+			span_f32x2 v;
+			v.x = t_in;
+			v.y = t_out;
+			reinterpret_cast<span_f32x2 *>(item)[k] = v; // one 8-byte store
+		}
+		else
+		{
+			item[2 * k] = t_in;
+			item[2 * k + 1] = t_out;
+		}
+	}
+};
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_spans_kernel(const SpanKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 pixels");
+	const FrameU &U = a.U;
+	const SpanArgs &s = a.s;
+	const uint32_t lane = threadIdx.x;
+	uint32_t i;
+	QueryRay ray;
+	bool in_frame = true;
+	if (s.kind == QUERY_FRAME)
+	{
+		const uint32_t tiles_x = ((uint32_t)U.width + 7u) >> 3;
+		const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+		const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+		if (px >= (uint32_t)U.width || py >= (uint32_t)U.height) return;
+		i = py * (uint32_t)U.width + px; // < width * height <= 2^30
+		in_frame = query_pixel_ray(U, (int)px, (int)py, ray);
+	}
+	else
+	{
+		i = blockIdx.x * 64u + lane;
+		if (i >= (uint32_t)s.n) return;
+		if (s.kind == QUERY_PICK)
+			in_frame = query_pixel_ray(U, s.pixels[(size_t)2 * i], s.pixels[(size_t)2 * i + 1], ray);
+		else if (s.kind == QUERY_MESH)
+			ray = query_mesh_ray(query_load3(s.pos, i), query_load3(s.dir, i), s.reach);
+		else
+			ray = query_plain_ray(query_load3(s.pos, i), query_load3(s.dir, i), s.t_max);
+	}
+	const SpanSceneDistance<Scene, DBG> distance = {U, debug_flags(U), Scene::ray_setup(U, V3s(0.f), query_ray_flags())};
+	SpanStore store;
+	store.item = s.spans + (size_t)2 * (size_t)s.max_spans * i; // (n * max_spans <= 2^30 spans of 8 bytes: 64-bit)
+	store.aligned = (reinterpret_cast<size_t>(s.spans) & 7u) == 0u;
+	uint32_t rec[SPAN_SUMMARY_WORDS];
+	span_item(distance, store, in_frame, ray.origin, ray.dir, s.t_max, s.min_step, s.iso, s.max_steps, s.max_spans, rec);
+	// 32-byte records: two 16-byte stores into an array aligned to 16 bytes, word stores into any other (query_store's rule)
+	uint32_t *out = s.summaries + (size_t)SPAN_SUMMARY_WORDS * i;
+	if ((reinterpret_cast<size_t>(s.summaries) & 15u) == 0u)
+	{
+		span_u32x4 lo, hi;
+		lo.x = rec[0], lo.y = rec[1], lo.z = rec[2], lo.w = rec[3];
+		hi.x = rec[4], hi.y = rec[5], hi.z = rec[6], hi.w = rec[7];
+		reinterpret_cast<span_u32x4 *>(out)[0] = lo;
+		reinterpret_cast<span_u32x4 *>(out)[1] = hi;
+	}
+	else
+	{
+#pragma unroll
+		for (int k = 0; k < SPAN_SUMMARY_WORDS; ++k) out[k] = rec[k];
+	}
 }
 
 } // namespace sdfr

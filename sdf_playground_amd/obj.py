@@ -38,6 +38,15 @@ def occlusion_colors(occlusion, colors=None):
     return (base * o[:, None]).astype(np.float32)
 
 
+def thickness_colors(thickness, t_max):
+    """Per-vertex greys [v, 3] float32 of wall thicknesses (SDFRenderer.meshThickness): thickness / t_max clipped to [0, 1]; a vertex
+    whose wall does not end within reach (inf) is white, one without a number (NaN) too."""
+    import numpy as np
+
+    g = np.clip(np.nan_to_num(np.asarray(thickness, np.float32) / np.float32(t_max), nan=1.0, posinf=1.0), 0.0, 1.0).astype(np.float32)
+    return np.repeat(g[:, None], 3, 1)
+
+
 def lighting_colors(lighting):
     """Per-vertex colours [v, 3] float32 of LIGHTING_DTYPE records (extractMesh(lighting=True)): `lit`, the hit's own colour plus the
     light every unshadowed light delivers, clipped to [0, 1] (a NaN becomes 0); MISSING_COLOR where valid != 1.  Also returns how many

@@ -1,0 +1,446 @@
+"""GPU tier of the span queries (sdfr_query_ray_spans, sdfr_pick_spans, sdfr_mesh_spans) through libsdfr.so: every word equal to the
+definition of include/sdfr.h restated in numpy (span_util.march_spans), fed with the oracle's distances for the built-in scenes and the
+dialect scene, the debug kernel variant included; analytic chords, a plane and a NaN half-space in the run-time probe scene;
+meshThickness; the capacity rule, also into arrays off their alignment; no side effects on rendering; the argument errors through the
+raw C ABI."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import query_util as qu
+import span_util as su
+from test_gpu_mesh_survey import DEFAULT_LIMITS, PROBE
+from test_gpu_slice import CASES
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+W, H = 64, 48
+FW, FH = 19, 11  # the whole frame: ragged against the 8 x 8 tiles in both directions, 6 blocks
+# most rays finish within 128 steps of at least 0.05, some do not (asserted below, per scene)
+MIN_STEP, MAX_STEPS = 0.05, 128
+RANGE = DEFAULT_LIMITS["range"]
+
+
+def _setup(r, scene, of):
+    """the handle's state = the oracle frame `of`"""
+    if scene in qu.HLSL:
+        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
+    else:
+        r.initShader(scene)
+    r.setParameters(of.stime)
+    r.setCameraBasis(of.eye, of.front, of.right, of.top)
+    r.setLimits(**DEFAULT_LIMITS)
+    r.setStepShortcuts(False)
+
+
+def _probe(r, **values):
+    """the probe scene of tests/test_gpu_mesh_survey.py with its variables set"""
+    if r.currentScene() != "span_probe":
+        r.initShaderSource("span_probe", PROBE)
+        r.setLimits(**DEFAULT_LIMITS)
+    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
+        assert r.setValue(name, v)
+
+
+def _stats(r):
+    s = r.getStats()
+    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    yield r
+    r.close()
+
+
+def _host(got):
+    """(summaries, spans) of either path as numpy: SUMMARY_DTYPE records [n], float32 [n, max_spans, 2]"""
+    s, sp = got
+    if hasattr(s, "data_ptr"):
+        s, sp = s.cpu().numpy().view(su.SUMMARY_DTYPE).reshape(-1), sp.cpu().numpy()
+    return s.view(su.SUMMARY_DTYPE), sp
+
+
+def _assert_same(what, got, want, first=None):
+    """every word of every item; first: `want` holds more items, of which `got` are the first ones"""
+    s, sp = _host(got)
+    ws, wsp = want if first is None else (want[0][:first], want[1][:first])
+    assert s.shape == ws.shape and sp.shape == wsp.shape, (what, s.shape, ws.shape, sp.shape, wsp.shape)
+    qu.assert_same("%s summaries" % (what,), np.ascontiguousarray(s).view(np.uint32).reshape(-1, 8), np.ascontiguousarray(ws).view(np.uint32).reshape(-1, 8))
+    if sp.size:
+        qu.assert_same("%s spans" % (what,), sp.reshape(-1, 2), wsp.reshape(-1, 2))
+
+
+def _distance(scene, of):
+    return lambda pts: qu.oracle_points(scene, of, pts, normals=False)[0]
+
+
+def _mostly_finished(S):
+    ran = S["valid"] == 1
+    out = (S["flags"] & su.OUT_OF_STEPS) != 0
+    return out.sum() >= 1 and (ran & ~out).sum() > 0.75 * ran.sum()
+
+
+# ---- parity ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", sorted(CASES))
+def test_spans_equal_the_definition(renderer, scene):
+    import torch
+
+    stime, (x0, z0), cell, y0, _dy = CASES[scene]
+    of = qu.frame(scene, stime, W, H)
+    _setup(renderer, scene, of)
+    D = _distance(scene, of)
+    kw = dict(min_step=MIN_STEP, max_steps=MAX_STEPS)
+    finished = []
+
+    # rays: n = 1, 63, 65, 130 are the first n of one seeded set (an item's answer does not depend on its neighbours)
+    o, d = qu.ray_samples(of, 7, 130)
+    o[5], d[17], d[40] = (np.nan, 0, 0), (0, 0, 0), (np.inf, 1, 0)  # items without an answer
+    for max_spans, iso in ((3, 0.0), (0, 0.0), (3, 0.05)):
+        want = su.march_spans(D, o, d, su.params(MIN_STEP, RANGE, iso, MAX_STEPS, max_spans))
+        su.check_invariants(want[0], want[1], su.params(MIN_STEP, RANGE, iso, MAX_STEPS, max_spans))
+        assert (want[0]["valid"][[5, 17, 40]] == 0).all() and (want[0]["valid"] == 1).sum() == 127
+        finished.append(want[0])
+        for n in (1, 63, 65, 130):
+            _assert_same((scene, "rays", n, max_spans, iso), renderer.querySpans(o[:n], d[:n], iso=iso, max_spans=max_spans, **kw), want, n)
+            dev = renderer.querySpans(torch.as_tensor(o[:n]).cuda(), torch.as_tensor(d[:n]).cuda(), iso=iso, max_spans=max_spans, **kw)
+            renderer.sync()
+            _assert_same((scene, "rays, device", n, max_spans, iso), dev, want, n)
+    # an explicit t_max, and numpy items answered into device arrays
+    want = su.march_spans(D, o, d, su.params(MIN_STEP, 2.5, 0.0, MAX_STEPS, 3))
+    _assert_same((scene, "rays, t_max"), renderer.querySpans(o, d, t_max=2.5, max_spans=3, **kw), want)
+    dev = renderer.querySpans(o, d, t_max=2.5, max_spans=3, device=True, **kw)
+    renderer.sync()
+    _assert_same((scene, "rays, t_max, device=True"), dev, want)
+
+    # picks: a stride through the frame's pixels, and every pixel outside it
+    grid = qu.pick_grid(W, H)
+    px = np.concatenate([grid[: W * H: 23], grid[W * H:]])
+    po, pd, valid = su.pixel_rays(of, px)
+    assert (valid == -1).sum() == 7
+    for max_spans in (3, 0):
+        p = su.params(MIN_STEP, RANGE, 0.0, MAX_STEPS, max_spans)
+        want = su.march_spans(D, po, pd, p, valid)
+        su.check_invariants(want[0], want[1], p)
+        assert (want[0]["valid"] == -1).sum() == 7
+        finished.append(want[0])
+        _assert_same((scene, "picks", max_spans), renderer.pickSpans(px, W, H, max_spans=max_spans, **kw), want)
+        dev = renderer.pickSpans(torch.as_tensor(px).cuda(), W, H, max_spans=max_spans, **kw)
+        renderer.sync()
+        _assert_same((scene, "picks, device", max_spans), dev, want)
+
+    # the whole frame, 19 x 11: every pixel in row-major order
+    of_small = qu.frame(scene, stime, FW, FH)  # (its camera has the aspect of its size)
+    renderer.setCameraBasis(of_small.eye, of_small.front, of_small.right, of_small.top)
+    ys, xs = np.mgrid[0:FH, 0:FW]
+    fo, fd, fvalid = su.pixel_rays(of_small, np.stack([xs.ravel(), ys.ravel()], 1))
+    assert (fvalid == 1).all()
+    for max_spans in (3, 0):
+        want = su.march_spans(_distance(scene, of_small), fo, fd, su.params(MIN_STEP, RANGE, 0.0, MAX_STEPS, max_spans))
+        finished.append(want[0])
+        _assert_same((scene, "frame", max_spans), renderer.pickSpans(None, FW, FH, max_spans=max_spans, **kw), want)
+        dev = renderer.pickSpans(None, FW, FH, max_spans=max_spans, device=True, **kw)
+        renderer.sync()
+        _assert_same((scene, "frame, device", max_spans), dev, want)
+    renderer.setCameraBasis(of.eye, of.front, of.right, of.top)
+    S = np.concatenate(finished)
+    assert _mostly_finished(S), (scene, ((S["flags"] & su.OUT_OF_STEPS) != 0).sum(), len(S))
+
+    # mesh rays on a small extracted mesh
+    mcell = 2 * cell
+    pos, nrm, _idx = renderer.extractMesh((x0, y0, z0), mcell, (16, 12, 16))
+    assert len(pos) > 50
+    reach = 2 * mcell
+    mo, md = su.mesh_rays(pos, nrm, reach)
+    for max_spans in (3, 0):
+        p = su.params(0.25 * mcell, 1.0, 0.0, MAX_STEPS, max_spans)
+        want = su.march_spans(D, mo, md, p)
+        su.check_invariants(want[0], want[1], p)
+        _assert_same((scene, "mesh", max_spans), renderer.meshSpans(pos, nrm, reach, 0.25 * mcell, t_max=1.0, max_steps=MAX_STEPS, max_spans=max_spans), want)
+        dev = renderer.meshSpans(torch.as_tensor(pos).cuda(), torch.as_tensor(nrm).cuda(), reach, 0.25 * mcell, t_max=1.0, max_steps=MAX_STEPS, max_spans=max_spans)
+        renderer.sync()
+        _assert_same((scene, "mesh, device", max_spans), dev, want)
+    assert (want[0]["spans"] >= 1).sum() > 0.5 * len(pos)  # a wall under most vertices
+    qu.assert_same((scene, "thickness"), renderer.meshThickness(pos, nrm, reach, 0.25 * mcell, t_max=1.0, max_steps=MAX_STEPS),
+                   su.thickness(*su.march_spans(D, mo, md, su.params(0.25 * mcell, 1.0, 0.0, MAX_STEPS, 1))))
+
+
+def test_debug_plane_and_show_objects(renderer):
+    """the DBG kernel variant: the debug plane and show_objects apply as they do in sdfr_query_distance"""
+    for scene in ("labyrinth", "dialect_tour"):
+        _setup(renderer, scene, qu.frame(scene, 0.75, W, H))  # (the scene is loaded once: the two frames differ in their variables alone)
+        for variables in ({"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}, {"show_objects": 0.0, "debug_ny": 1.0}):
+            of = qu.frame(scene, 0.75, W, H, variables)
+            for name, v in variables.items():
+                assert renderer.setValue(name, v)
+            try:
+                D = _distance(scene, of)
+                o, d = qu.ray_samples(of, 21, 130)
+                p = su.params(MIN_STEP, RANGE, 0.0, MAX_STEPS, 3)
+                want = su.march_spans(D, o, d, p)
+                su.check_invariants(want[0], want[1], p)
+                # the plane is there: the answers differ from the plain scene's
+                plain = su.march_spans(_distance(scene, qu.frame(scene, 0.75, W, H)), o, d, p)
+                assert not np.array_equal(plain[0], want[0])
+                _assert_same((scene, variables, "rays"), renderer.querySpans(o, d, MIN_STEP, max_steps=MAX_STEPS, max_spans=3), want)
+                dev = renderer.querySpans(o, d, MIN_STEP, max_steps=MAX_STEPS, max_spans=3, device=True)
+                _assert_same((scene, variables, "rays, device"), dev, want)
+                px = qu.pick_grid(W, H)[:: 29]
+                po, pd, valid = su.pixel_rays(of, px)
+                want = su.march_spans(D, po, pd, p, valid)
+                _assert_same((scene, variables, "picks"), renderer.pickSpans(px, W, H, MIN_STEP, max_steps=MAX_STEPS, max_spans=3), want)
+            finally:
+                renderer.resetVariables()
+
+
+# ---- the run-time probe scene ------------------------------------------------------------------------------------------------------
+def _chord_rays(rng, n, centre, rho):
+    """unit rays with impact parameter b <= rho / 2 from 1.5 .. 3 rho in front of the point of closest approach"""
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    e = np.cross(d, rng.normal(size=(n, 3)))
+    e /= np.linalg.norm(e, axis=1, keepdims=True)
+    o = centre + rng.uniform(0, 0.5 * rho, n)[:, None] * e - rng.uniform(1.5 * rho, 3.0 * rho, n)[:, None] * d
+    return o.astype(F), d.astype(F)
+
+
+def test_sphere_chords(renderer):
+    """One span per ray, both ends within min_step^2 / (16 rho) + 1e-5 of the analytic chord's (tests/test_span_cpu.py checks the bound's
+    constant on the host build; the worst case there is 0.57 of it)."""
+    centre, rho, min_step = np.array([0.03, 0.05, 0.07]), 0.8, 0.1
+    _probe(renderer, cx=centre[0], cy=centre[1], cz=centre[2], radius=rho)
+    o, d = _chord_rays(np.random.default_rng(11), 200, centre, rho)
+    p = su.params(min_step, 5.0, max_steps=256, max_spans=2)
+    S, spans = renderer.querySpans(o, d, min_step, t_max=5.0, max_steps=256, max_spans=2)
+    su.check_invariants(S, spans, p)
+    assert (S["spans"] == 1).all() and (S["crossings"] == 2).all() and (S["flags"] == 0).all()
+    # the library's own distance in the restatement: the same words
+    want = su.march_spans(lambda pts: renderer.queryDistance(pts), o, d, p)
+    _assert_same("sphere", (S, spans), want)
+    c32 = np.array([F(v) for v in centre], np.float64)  # the variables as the scene holds them
+    o64, d64 = o.astype(np.float64), d.astype(np.float64)
+    oc = o64 - c32
+    dd, od = (d64 * d64).sum(1), (oc * d64).sum(1)
+    root = np.sqrt(od * od - dd * ((oc * oc).sum(1) - float(F(rho)) ** 2))
+    bound = min_step * min_step / (16 * rho) + 1e-5
+    err = max(np.abs(spans[:, 0, 0] - (-od - root) / dd).max(), np.abs(spans[:, 0, 1] - (-od + root) / dd).max())
+    print("sphere: worst chord-end error %.3g, bound %.3g" % (err, bound))
+    assert err <= bound, (err, bound)
+    assert np.abs(S["inside_length"] - 2 * root / dd).max() <= 2 * bound
+
+
+def test_plane_and_nan_half_space(renderer):
+    rng = np.random.default_rng(3)
+    n, height, min_step = 100, 0.25, 0.1
+    bound = min_step * min_step / 16 + 1e-5
+    # the plane y = height, inside below it: rays from above going down end inside, and enter where they meet the plane
+    _probe(renderer, kind=1.0, height=height)
+    o = np.stack([rng.uniform(-2, 2, n), rng.uniform(0.5, 2.0, n), rng.uniform(-2, 2, n)], 1).astype(F)
+    d = np.stack([rng.uniform(-0.5, 0.5, n), rng.uniform(-1.0, -0.5, n), rng.uniform(-0.5, 0.5, n)], 1)
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
+    p = su.params(min_step, 6.0, max_steps=256, max_spans=2)
+    S, spans = renderer.querySpans(o, d, min_step, t_max=6.0, max_steps=256, max_spans=2)
+    su.check_invariants(S, spans, p)
+    _assert_same("plane", (S, spans), su.march_spans(lambda pts: renderer.queryDistance(pts), o, d, p))
+    assert (S["flags"] == su.ENDS_INSIDE).all() and (S["spans"] == 1).all() and (S["crossings"] == 1).all()
+    t_plane = (float(F(height)) - o[:, 1].astype(np.float64)) / d[:, 1].astype(np.float64)
+    assert np.abs(spans[:, 0, 0] - t_plane).max() <= bound and (spans[:, 0, 1] == F(6.0)).all()
+    assert np.abs(S["inside_length"] - (6.0 - t_plane)).max() <= bound + 1e-5
+    # NaN where x > split: rays that stay in that half-space see NaN alone: outside, no span, steps of min_step
+    _probe(renderer, kind=2.0, height=height, split=0.3)
+    o[:, 0] = rng.uniform(1.0, 2.0, n)
+    d[:, 0] = np.abs(d[:, 0])
+    assert np.isnan(renderer.queryDistance(o)).all()
+    p = su.params(min_step, 1.0, max_steps=256, max_spans=2)
+    S, spans = renderer.querySpans(o, d, min_step, t_max=1.0, max_steps=256, max_spans=2)
+    su.check_invariants(S, spans, p)
+    _assert_same("NaN", (S, spans), su.march_spans(lambda pts: renderer.queryDistance(pts), o, d, p))
+    assert not S["spans"].any() and not S["crossings"].any() and not S["flags"].any() and not spans.any() and (S["inside_length"] == 0).all()
+    assert ((S["steps"] >= 11) & (S["steps"] <= 12)).all() and (S["t_end"] == F(1.0)).all()
+    # ... and rays that come out of it over the solid half (x < split, y < height): the crossing out of NaN is cut at a bracket's middle
+    o2 = np.stack([rng.uniform(0.5, 1.0, n), rng.uniform(-1.0, 0.0, n), rng.uniform(-1, 1, n)], 1).astype(F)
+    d2 = np.tile(np.array([-1.0, 0.0, 0.0], F), (n, 1))
+    S, spans = renderer.querySpans(o2, d2, min_step, t_max=2.0, max_steps=256, max_spans=2)
+    _assert_same("out of NaN", (S, spans), su.march_spans(lambda pts: renderer.queryDistance(pts), o2, d2, su.params(min_step, 2.0, max_steps=256, max_spans=2)))
+    assert (S["spans"] == 1).all() and (S["flags"] == su.ENDS_INSIDE).all()
+    assert (np.abs(spans[:, 0, 0] - (o2[:, 0] - F(0.3))) <= 0.5 * min_step + 1e-5).all()
+
+
+def test_mesh_thickness(renderer):
+    """the sphere of the probe scene, meshed: under every vertex the wall is the sphere's diameter, within two cells plus the chord bound"""
+    centre, rho, cell = (0.1, -0.05, 0.2), 0.5, 0.05
+    _probe(renderer, cx=centre[0], cy=centre[1], cz=centre[2], radius=rho)
+    pos, nrm, _idx = renderer.extractMesh((centre[0] - 0.6, centre[1] - 0.6, centre[2] - 0.6), cell, (24, 24, 24))
+    assert len(pos) > 1000
+    min_step = 0.5 * cell
+    thick = renderer.meshThickness(pos, nrm, 2 * cell, min_step, t_max=2.0)
+    assert thick.dtype == F and thick.shape == (len(pos),) and np.isfinite(thick).all()
+    bound = min_step * min_step / (16 * rho) + 1e-5
+    assert np.abs(thick - 2 * rho).max() <= 2 * cell + bound, np.abs(thick - 2 * rho).max()
+    # a march that stops inside the sphere closes its span at t_max: no thickness
+    assert np.isinf(renderer.meshThickness(pos, nrm, 2 * cell, min_step, t_max=0.5)).all()
+    # device arrays in: the same numbers
+    import torch
+
+    dev = renderer.meshThickness(torch.as_tensor(pos).cuda(), torch.as_tensor(nrm).cuda(), 2 * cell, min_step, t_max=2.0)
+    qu.assert_same("thickness, device", dev, thick)
+
+
+# ---- the protocol ----------------------------------------------------------------------------------------------------------------
+def test_capacity_rule_on_the_labyrinth(renderer):
+    import torch
+
+    scene = "labyrinth"
+    of = qu.frame(scene, CASES[scene][0], W, H)
+    _setup(renderer, scene, of)
+    # of a seeded pool of rays through the labyrinth, those that pass through more than three of its walls
+    o, d = qu.ray_samples(of, 7, 400)
+    p = su.params(0.02, 30.0, max_steps=1024, max_spans=16)
+    pool = su.march_spans(_distance(scene, of), o, d, p)[0]
+    rows = np.nonzero((pool["spans"] > 3) & (pool["spans"] <= 16) & ((pool["flags"] & su.OUT_OF_STEPS) == 0))[0]
+    assert len(rows) >= 9, len(rows)
+    o, d = o[rows[:9]], d[rows[:9]]
+    full = su.march_spans(_distance(scene, of), o, d, p)
+    su.check_invariants(full[0], full[1], p)
+    assert (full[0]["spans"] > 3).all()
+    for max_spans in (0, 1, 3, 16):
+        S, spans = renderer.querySpans(o, d, 0.02, t_max=30.0, max_steps=1024, max_spans=max_spans)
+        # the summary does not depend on what is stored; the stored spans are the first ones
+        qu.assert_same(("summaries", max_spans), S.view(np.uint32).reshape(-1, 8), full[0].view(np.uint32).reshape(-1, 8))
+        qu.assert_same(("spans", max_spans), spans.reshape(-1, 2), np.ascontiguousarray(full[1][:, :max_spans]).reshape(-1, 2))
+        assert spans.shape == (9, max_spans, 2)
+    # device arrays that are not aligned to 16 and 8 bytes are written by the word path: the same words, nothing in front of them
+    ds, dsp = torch.full((9 * 8 + 1,), 7, dtype=torch.int32, device="cuda"), torch.full((9 * 3 * 2 + 1,), 7.0, device="cuda")
+    do, dd = torch.as_tensor(o).cuda(), torch.as_tensor(d).cuda()
+    import sdf_playground_amd as sp
+
+    par = sp.SpanParams(30.0, 0.02, 0.0, 1024, 3)
+    dev = lambda a: ctypes.c_void_p(a.data_ptr())  # noqa: E731
+    assert sp.load_library().sdfr_query_ray_spans(renderer._h, 9, dev(do), dev(dd), ctypes.byref(par), dev(ds[1:]), dev(dsp[1:]), 0) == 0
+    renderer.sync()
+    assert int(ds[0]) == 7 and float(dsp[0]) == 7.0
+    qu.assert_same("summaries off alignment", ds[1:].cpu().numpy().view(np.uint32).reshape(-1, 8), full[0].view(np.uint32).reshape(-1, 8))
+    qu.assert_same("spans off alignment", dsp[1:].cpu().numpy().reshape(-1, 2), np.ascontiguousarray(full[1][:, :3]).reshape(-1, 2))
+
+
+def test_spans_leave_rendering_alone(renderer):
+    import torch
+
+    scene = "labyrinth"
+    of = qu.frame(scene, CASES[scene][0], W, H)
+    _setup(renderer, scene, of)
+    o, d = qu.ray_samples(of, 9, 130)
+    p = su.params(MIN_STEP, RANGE, 0.0, MAX_STEPS, 3)
+    want = su.march_spans(_distance(scene, of), o, d, p)
+    kw = dict(min_step=MIN_STEP, max_steps=MAX_STEPS, max_spans=3)
+    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
+    s0, t0 = _stats(renderer), renderer.getTimings()
+    _assert_same("host", renderer.querySpans(o, d, **kw), want)
+    dev = renderer.querySpans(o, d, device=True, **kw)
+    renderer.pickSpans(None, FW, FH, **kw)
+    renderer.sync()
+    _assert_same("device", dev, want)
+    assert _stats(renderer) == s0 and renderer.getTimings() == t0
+    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
+    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    # two frames in flight: the call runs on the lane of the frame submitted last
+    renderer.setFramesInFlight(2)
+    try:
+        imgs = [torch.empty((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        for k in range(4):
+            renderer.render(None, W, H, out=imgs[k % 2])
+            dev = renderer.querySpans(o, d, device=True, **kw)
+            host = renderer.querySpans(o, d, **kw)
+            renderer.sync()
+            _assert_same(("device", k), dev, want)
+            _assert_same(("host", k), host, want)
+            assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
+            assert _stats(renderer) == s0
+    finally:
+        renderer.setFramesInFlight(1)
+
+
+def test_arguments(renderer):
+    import sdf_playground_amd as sp
+
+    L = sp.load_library()
+    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    h = renderer._h
+    INVALID, NO_SCENE = -1, -4
+    NULL_POINTER, BAD_ON_HOST, BAD_PARAMS, BAD_COUNT = "null pointer", "on_host must be 0 or 1", "bad span parameters", "bad item count"
+    BAD_FRAME, BAD_REACH, NULL_SPANS, BAD_FRAME_N = "bad frame size", "reach must be finite and > 0", "null spans with max_spans > 0", "without a pixel list n must be width * height"
+    nan, inf = float("nan"), float("inf")
+    n = 5
+    o, d = qu.ray_samples(qu.frame("fast_sphere", 0.0, W, H), 1, n)
+    px = np.array([[0, 0], [3, 2], [18, 10], [-1, 0], [5, 5]], np.int32)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+
+    def call(entry="rays", handle=h, count=n, in0=True, in1=True, params=True, summaries=True, spans=True, on_host=1, width=FW, height=FH, reach=0.5,
+             t_max=1.0, min_step=0.05, iso=0.0, max_steps=64, max_spans=2):
+        S, sp_ = np.full((max(count, 1) if 0 <= count < 1000 else 1, 8), 0x77777777, np.uint32), np.full((max(count, 1) if 0 <= count < 1000 else 1, 4, 2), -7.0, F)
+        par = sp.SpanParams(t_max, min_step, iso, max_steps, max_spans)
+        tail = (ctypes.byref(par) if params else None, ptr(S) if summaries else None, ptr(sp_) if spans else None, on_host)
+        if entry == "rays":
+            rc = L.sdfr_query_ray_spans(handle, count, ptr(o) if in0 else None, ptr(d) if in1 else None, *tail)
+        elif entry == "mesh":
+            rc = L.sdfr_mesh_spans(handle, count, ptr(o) if in0 else None, ptr(d) if in1 else None, reach, *tail)
+        else:
+            rc = L.sdfr_pick_spans(handle, width, height, count, ptr(px) if in0 else None, *tail)
+        if rc != 0:  # nothing is written on error
+            assert (S == 0x77777777).all() and (sp_ == -7).all()
+        return rc, L.sdfr_last_error(handle).decode() if handle and rc else ""
+
+    for entry in ("rays", "mesh", "pick"):
+        assert call(entry) == (0, ""), entry
+        assert call(entry, params=False) == (INVALID, NULL_POINTER) and call(entry, summaries=False) == (INVALID, NULL_POINTER)
+        assert call(entry, on_host=2) == (INVALID, BAD_ON_HOST) and call(entry, on_host=-1) == (INVALID, BAD_ON_HOST)
+        for bad in (dict(t_max=nan), dict(t_max=-1.0), dict(t_max=inf), dict(min_step=0.0), dict(min_step=nan), dict(iso=inf), dict(max_steps=0),
+                    dict(max_steps=(1 << 20) + 1), dict(max_spans=-1), dict(max_spans=65)):
+            assert call(entry, **bad) == (INVALID, BAD_PARAMS), (entry, bad)
+        assert call(entry, count=-1) == (INVALID, BAD_COUNT) and call(entry, count=(1 << 30) + 1) == (INVALID, BAD_COUNT)
+        assert call(entry, spans=False) == (INVALID, NULL_SPANS) and call(entry, spans=False, max_spans=0) == (0, "")
+        assert call(entry, count=0) == (0, "")
+        # two faults at once: the text of the one checked first
+        assert call(entry, params=False, on_host=2) == (INVALID, NULL_POINTER)
+        assert call(entry, on_host=2, min_step=0.0) == (INVALID, BAD_ON_HOST)
+        assert call(entry, min_step=0.0, count=-1) == (INVALID, BAD_PARAMS)
+        assert call(entry, handle=None)[0] == INVALID
+    assert call("rays", in0=False) == (INVALID, NULL_POINTER) and call("rays", in1=False) == (INVALID, NULL_POINTER)
+    assert call("mesh", in0=False) == (INVALID, NULL_POINTER) and call("mesh", in1=False) == (INVALID, NULL_POINTER)
+    for reach in (0.0, -1.0, nan, inf):
+        assert call("mesh", reach=reach) == (INVALID, BAD_REACH)
+    assert call("mesh", reach=0.0, count=-1) == (INVALID, BAD_COUNT) and call("mesh", reach=0.0, spans=False) == (INVALID, BAD_REACH)
+    assert call("pick", width=0) == (INVALID, BAD_FRAME) and call("pick", height=-2) == (INVALID, BAD_FRAME)
+    assert call("pick", width=1 << 16, height=(1 << 14) + 1) == (INVALID, BAD_FRAME)
+    assert call("pick", width=0, spans=False) == (INVALID, BAD_FRAME) and call("pick", width=0, count=-1) == (INVALID, BAD_COUNT)
+    assert call("pick", in0=False) == (INVALID, BAD_FRAME_N) and call("pick", in0=False, spans=False) == (INVALID, NULL_SPANS)
+    assert call("pick", in0=False, width=2, height=2, count=4) == (0, "")
+    fresh = sp.SDFRenderer(0)
+    try:
+        for entry in ("rays", "mesh", "pick"):
+            assert call(entry, handle=fresh._h)[0] == NO_SCENE
+            assert call(entry, handle=fresh._h, min_step=0.0) == (INVALID, BAD_PARAMS)  # the arguments come first
+            assert call(entry, handle=fresh._h, spans=False) == (INVALID, NULL_SPANS)
+            assert call(entry, handle=fresh._h, count=0) == (0, "")
+    finally:
+        fresh.close()
+
+
+def test_cli_xray_and_thickness(renderer, tmp_path):
+    """the two command-line uses, end to end on a small frame and a small mesh"""
+    from sdf_playground_amd import cli
+
+    out = tmp_path / "x.png"
+    assert cli.main(["--scene", "fast_sphere", "--size", "%dx%d" % (FW, FH), "--xray", str(out), "--xray-step", "0.05", "--xray-density", "0.5"]) == 0
+    data = out.read_bytes()
+    assert data[:8] == b"\x89PNG\r\n\x1a\n" and data[16:24] == (FW).to_bytes(4, "big") + (FH).to_bytes(4, "big")
+    obj = tmp_path / "m.obj"
+    assert cli.main(["--scene", "fast_sphere", "--mesh", str(obj), "--mesh-box", "-1", "0", "-1", "1", "2", "1", "--mesh-cell", "0.1", "--mesh-thickness", "1.0"]) == 0
+    vertices = [line.split() for line in obj.read_text().splitlines() if line.startswith("v ")]
+    assert len(vertices) > 50 and all(len(v) == 7 and v[4] == v[5] == v[6] and 0.0 <= float(v[4]) <= 1.0 for v in vertices)
