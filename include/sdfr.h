@@ -838,6 +838,86 @@ int sdfr_pick_spans(sdfr_renderer *r, int width, int height, int64_t n, const in
 int sdfr_mesh_spans(sdfr_renderer *r, int64_t n, const float *positions, const float *normals, float reach, const sdfr_span_params *params,
 	sdfr_span_summary *summaries, sdfr_span *spans, int on_host);
 
+/* ---- how much solid there is: volume, centre of mass and inertia of the loaded scene (no counterpart in the reference; DESIGN.md
+ *      "Measure"), integrated on the GPU along a bundle of parallel columns and reduced there in a defined order, so that every bit of
+ *      the result is defined and only one small record crosses the bus.
+ *
+ *      A measure grid is nu x nv parallel columns.  Column (i, j), 0 <= i < nu, 0 <= j < nv, is a ray: its origin per component c is
+ *      (origin[c] + (float)i * du[c]) + (float)j * dv[c], fp32, one multiply and one add per term (the form of the slices' lattice
+ *      points, layer 0); its direction is dw as given.  It is marched exactly as sdfr_query_ray_spans marches that ray under `params`:
+ *      the same D, iso, inside test, step rule, crossing rule, end rule and flags; t_max = 0 means limits.range; max_spans must be 0.
+ *      The column's spans, steps, crossings, flags and valid below are the words of the sdfr_span_summary of that ray.
+ *
+ *      Per column, in the order its spans close, with a = (double)t_in, b = (double)t_out, every fp64 operation separate and unfused:
+ *        m0 += b - a;   m1 += 0.5 * (b*b - a*a);   m2 += ((b*b)*b - (a*a)*a) / 3.0
+ *      -- the integrals of 1, t and t^2 over the inside part of the column; all three start at +0.0.  A column with valid != 1 has
+ *      m0 = m1 = m2 = +0.0 and every other word 0.  With u = (double)i and v = (double)j the column's ten contributions are
+ *        [m0, u*m0, v*m0, m1, (u*u)*m0, (v*v)*m0, m2, (u*v)*m0, v*m1, u*m1]
+ *      and moments[k] is the sum of contribution k over all columns in THIS order:
+ *        - the columns of an 8 x 8 tile are lanes l = (i & 7) + 8 * (j & 7); a lane outside the grid, or with valid != 1, is +0.0;
+ *        - a tile's value is the pairwise tree over its 64 lanes: level by level x[m] = x[2m] + x[2m + 1];
+ *        - tiles are ordered row-major, ti + ceil(nu / 8) * tj;
+ *        - then, until one value remains: the values are grouped in runs of 64 by index, the last run padded with +0.0, and each run is
+ *          replaced by its pairwise tree sum.  A single tile is its own result.
+ *      Exact integers, whatever the order: columns_hit, the columns with spans >= 1; columns_open, those with SDFR_SPAN_STARTS_INSIDE or
+ *      SDFR_SPAN_ENDS_INSIDE (the solid leaves the box there: the measure is of a truncated solid); columns_out_of_steps; columns_invalid
+ *      (valid != 1); the 64-bit totals of steps, spans and crossings; hit_lo and hit_hi, the inclusive bounds of i ([0]) and j ([1]) over
+ *      the hit columns -- with none lo = (nu, nv) and hi = -1, as in the survey; t_lo, the smallest t_in, and t_hi, the largest t_out
+ *      over all spans, fp32 -- with no span +inf and -inf.
+ *
+ *      columns, unless NULL: one 40-byte record per column, row-major i + nu * j, host or device memory as on_host says (device: aligned
+ *      to 4 bytes; to 8 for 8-byte stores) -- a mass-per-column or height map in its own right.
+ *
+ *        - synchronous up to reading `out` back, like the counting call of the mesh; `out` is always host memory.
+ *        - a query in every respect listed for the spans: what is latched, the stream and two frames in flight, no effect on stats,
+ *          timings or the row order.
+ *        - errors, in the order they win: SDFR_ERR_INVALID_ARGUMENT "null pointer" (grid, params, out); on_host not 0 or 1; "bad measure
+ *          grid"; "bad span parameters" (max_spans != 0 included); then SDFR_ERR_NO_SCENE.  Nothing is written on error.
+ *
+ *      sdfr_measure_properties: the physical properties from a result, on the host in fp64, no GPU, every operation separate, in this
+ *      order.  A point of the solid is x = origin + u * du + v * dv + t * dw; a column stands for the unit square of (u, v) around it.
+ *      With M = moments, A the 3 x 3 matrix whose columns are du, dv, dw (as doubles):
+ *        det = (A00 * cx + A10 * cy) + A20 * cz, (cx, cy, cz) = dv x dw = (A11*A22 - A21*A12, A21*A02 - A01*A22, A01*A12 - A11*A02);
+ *        volume = M0 * fabs(det); mass = density * volume; cu = M1 / M0, cv = M2 / M0, cw = M3 / M0;
+ *        centroid[r] = ((origin[r] + cu * Ar0) + cv * Ar1) + cw * Ar2;
+ *        second moments about the lattice centroid, with M0 / 12 for a column's unit footprint: Cuu = (M4 - cu*M1) + M0/12,
+ *        Cvv = (M5 - cv*M2) + M0/12, Cww = M6 - cw*M3, Cuv = M7 - cu*M2, Cvw = M8 - cv*M3, Cwu = M9 - cw*M1 (C symmetric);
+ *        T = C A^T: Tks = (Ck0*As0 + Ck1*As1) + Ck2*As2;  P = A T: Prs = (Ar0*T0s + Ar1*T1s) + Ar2*T2s;  k = density * fabs(det);
+ *        inertia = [k*(Pyy + Pzz), k*(Pzz + Pxx), k*(Pxx + Pyy), -(k*Pxy), -(k*Pyz), -(k*Pzx)]: the tensor about the centroid, world
+ *        axes, its off-diagonal elements with their sign.
+ *      With !(M0 > 0) it writes zeros and returns SDFR_OK.  NULL pointers or a density that is not finite: SDFR_ERR_INVALID_ARGUMENT. */
+typedef struct sdfr_measure_grid
+{
+	float origin[3];    /* column (0, 0) starts here */
+	float du[3], dv[3]; /* step to the next column along u, along v; finite, neither all zero */
+	float dw[3];        /* the columns' direction; finite, not all zero */
+	int32_t nu, nv;     /* columns per axis, each 1..8192; nu * nv <= 2^24 */
+} sdfr_measure_grid;
+typedef struct sdfr_measure_result
+{
+	double moments[10];
+	int64_t columns_hit, columns_open, columns_out_of_steps, columns_invalid;
+	int64_t steps, spans, crossings;
+	int32_t hit_lo[2], hit_hi[2];
+	float t_lo, t_hi;
+} sdfr_measure_result; /* 160 bytes */
+typedef struct sdfr_measure_column
+{
+	double m0, m1, m2;
+	uint32_t spans, steps, flags;
+	int32_t valid;
+} sdfr_measure_column; /* 40 bytes */
+typedef struct sdfr_solid_properties
+{
+	double volume, mass;
+	double centroid[3]; /* world space */
+	double inertia[6];  /* about the centroid, world axes: xx, yy, zz, xy, yz, zx */
+} sdfr_solid_properties;
+
+int sdfr_measure(sdfr_renderer *r, const sdfr_measure_grid *grid, const sdfr_span_params *params, sdfr_measure_result *out /* host, required */,
+	sdfr_measure_column *columns /* [nu * nv], or NULL */, int on_host);
+int sdfr_measure_properties(const sdfr_measure_grid *grid, const sdfr_measure_result *res, double density, sdfr_solid_properties *out);
+
 /* ---- a texture atlas of an extracted mesh (no counterpart in the reference; DESIGN.md "Texture atlas"): one square tile of texels per
  *      quad of the mesh, baked on the GPU.  Surface nets emits quads: triangles 2q and 2q + 1 are (q0, q1, q2) and (q0, q2, q3) of one
  *      quad, so a tile per quad needs no chart cutting and no packing search, and bilinear filtering inside a quad never leaves its tile.

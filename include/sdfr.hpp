@@ -234,6 +234,19 @@ public:
 		return handle && pushState() && sdfr_mesh_spans(handle, n, positions, normals, reach, &params, summaries, spans, on_host ? 1 : 0) == SDFR_OK;
 	}
 
+	// How much solid there is (sdfr_measure, sdfr_measure_properties in sdfr.h), with this renderer's variables and time: the moments of
+	// the solid over the columns of `grid`, marched under params (max_spans 0), integrated and summed on the GPU in a defined order;
+	// columns: null, or one record per column (host memory, or device memory with on_host false).  measureProperties: volume, mass,
+	// centre of mass and inertia tensor from a result, on the host.
+	bool measure(const sdfr_measure_grid &grid, const sdfr_span_params &params, sdfr_measure_result &out, sdfr_measure_column *columns = nullptr, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_measure(handle, &grid, &params, &out, columns, on_host ? 1 : 0) == SDFR_OK;
+	}
+	static bool measureProperties(const sdfr_measure_grid &grid, const sdfr_measure_result &result, double density, sdfr_solid_properties &out)
+	{
+		return sdfr_measure_properties(&grid, &result, density, &out) == SDFR_OK;
+	}
+
 	// The texture atlas of an extracted mesh (sdfr_atlas_layout, sdfr_atlas_uvs, sdfr_atlas_texels, sdfr_atlas_bake in sdfr.h): one square
 	// tile of texels per quad.  atlasTexels looks at the mesh alone; bakeAtlas looks at every texel as meshSurfaces / meshLighting look at
 	// a vertex, with this renderer's variables and time.  layers: SDFR_ATLAS_*; a plane that is not asked for may be null.

@@ -159,6 +159,65 @@ class SpanParams(ctypes.Structure):  # sdfr_span_params
     _fields_ = [("t_max", ctypes.c_float), ("min_step", ctypes.c_float), ("iso", ctypes.c_float), ("max_steps", ctypes.c_int32), ("max_spans", ctypes.c_int32)]
 
 
+class MeasureGrid(ctypes.Structure):  # sdfr_measure_grid
+    _fields_ = [("origin", ctypes.c_float * 3), ("du", ctypes.c_float * 3), ("dv", ctypes.c_float * 3), ("dw", ctypes.c_float * 3),
+                ("nu", ctypes.c_int32), ("nv", ctypes.c_int32)]
+
+
+class MeasureResult(ctypes.Structure):  # sdfr_measure_result
+    _fields_ = [("moments", ctypes.c_double * 10), ("columns_hit", ctypes.c_int64), ("columns_open", ctypes.c_int64), ("columns_out_of_steps", ctypes.c_int64),
+                ("columns_invalid", ctypes.c_int64), ("steps", ctypes.c_int64), ("spans", ctypes.c_int64), ("crossings", ctypes.c_int64),
+                ("hit_lo", ctypes.c_int32 * 2), ("hit_hi", ctypes.c_int32 * 2), ("t_lo", ctypes.c_float), ("t_hi", ctypes.c_float)]
+
+    def as_dict(self):
+        return {name: (tuple(getattr(self, name)) if name in ("moments", "hit_lo", "hit_hi") else getattr(self, name)) for name, _type in self._fields_}
+
+
+class SolidProperties(ctypes.Structure):  # sdfr_solid_properties
+    _fields_ = [("volume", ctypes.c_double), ("mass", ctypes.c_double), ("centroid", ctypes.c_double * 3), ("inertia", ctypes.c_double * 6)]
+
+    def as_dict(self):
+        return {"volume": self.volume, "mass": self.mass, "centroid": tuple(self.centroid), "inertia": tuple(self.inertia)}
+
+
+assert ctypes.sizeof(MeasureGrid) == 56 and ctypes.sizeof(MeasureResult) == 160 and ctypes.sizeof(SolidProperties) == 88
+# sdfr_measure_column: a column's integrals of 1, t and t^2 over its inside part and the words of its span summary, 40 bytes
+MEASURE_COLUMN_DTYPE = np.dtype([("m0", np.float64), ("m1", np.float64), ("m2", np.float64), ("spans", np.uint32), ("steps", np.uint32), ("flags", np.uint32),
+                                 ("valid", np.int32)])
+assert MEASURE_COLUMN_DTYPE.itemsize == 40
+
+
+def measureGrid(box_lo, box_hi, cell, axis="z"):
+    """The measure grid of a box: columns along `axis` ('x', 'y' or 'z'; dw is its unit vector) through the centres of square cells of
+    edge `cell` on the box's lower face across it, ceil(extent / cell) per axis (u, v, w are a cyclic permutation of x, y, z).
+    -> (MeasureGrid, t_max: the box's depth along the axis)"""
+    if axis not in ("x", "y", "z"):
+        raise ValueError("the measure axis must be x, y or z")
+    w = "xyz".index(axis)
+    u, v = (w + 1) % 3, (w + 2) % 3
+    lo, hi, cell = [float(x) for x in box_lo], [float(x) for x in box_hi], float(cell)
+    if not (cell > 0 and all(h > l for l, h in zip(lo, hi))):
+        raise ValueError("the measure box needs lo < hi on every axis and a cell > 0")
+    n = [max(1, int(np.ceil((hi[a] - lo[a]) / cell - 1e-6))) for a in (u, v)]
+    if max(n) > 8192 or n[0] * n[1] > 1 << 24:
+        raise ValueError("the measure box and cell give %dx%d columns: at most 8192 per axis and 2^24 in all" % tuple(n))
+    origin, du, dv, dw = list(lo), [0.0] * 3, [0.0] * 3, [0.0] * 3
+    origin[u], origin[v] = lo[u] + 0.5 * cell, lo[v] + 0.5 * cell
+    du[u], dv[v], dw[w] = cell, cell, 1.0
+    f3 = lambda a: (ctypes.c_float * 3)(*a)  # noqa: E731
+    return MeasureGrid(f3(origin), f3(du), f3(dv), f3(dw), n[0], n[1]), hi[w] - lo[w]
+
+
+def measureProperties(grid, result, density=1.0):
+    """sdfr_measure_properties: volume, mass, centroid (world space) and the inertia tensor about the centroid (xx, yy, zz, xy, yz, zx) of a
+    measure, as a dict; host arithmetic in fp64, no GPU"""
+    out = SolidProperties()
+    rc = load_library().sdfr_measure_properties(ctypes.byref(grid), ctypes.byref(result), float(density), ctypes.byref(out))
+    if rc != SDFR_OK:
+        raise SdfrError(rc, "bad arguments to sdfr_measure_properties")
+    return out.as_dict()
+
+
 LIGHT_DIRECTIONAL = 1
 LIGHT_UNUSED, LIGHT_NO_CHAIN, LIGHT_BLOCKED, LIGHT_ESCAPED = 0, 1, 2, 3
 
@@ -182,6 +241,7 @@ EXPORTED_SYMBOLS = [
     "sdfr_mesh_survey", "sdfr_mesh_fit",
     "sdfr_slice_extract",
     "sdfr_query_ray_spans", "sdfr_pick_spans", "sdfr_mesh_spans",
+    "sdfr_measure", "sdfr_measure_properties",
 ]
 
 _lib = None
@@ -299,6 +359,8 @@ def load_library():
     L.sdfr_query_ray_spans.argtypes = [vp, i64, vp, vp, ctypes.POINTER(SpanParams), vp, vp, ci]
     L.sdfr_pick_spans.argtypes = [vp, ci, ci, i64, vp, ctypes.POINTER(SpanParams), vp, vp, ci]
     L.sdfr_mesh_spans.argtypes = [vp, i64, vp, vp, cf, ctypes.POINTER(SpanParams), vp, vp, ci]
+    L.sdfr_measure.argtypes = [vp, ctypes.POINTER(MeasureGrid), ctypes.POINTER(SpanParams), ctypes.POINTER(MeasureResult), vp, ci]
+    L.sdfr_measure_properties.argtypes = [ctypes.POINTER(MeasureGrid), ctypes.POINTER(MeasureResult), ctypes.c_double, ctypes.POINTER(SolidProperties)]
     L.sdfr_atlas_layout.argtypes = [i64, ci, ci, ctypes.POINTER(Atlas)]
     L.sdfr_atlas_uvs.argtypes = [ctypes.POINTER(Atlas), vp]
     L.sdfr_atlas_texels.argtypes = [vp, ctypes.POINTER(Atlas), i64, vp, vp, vp, vp, vp, vp, ci]
@@ -1049,6 +1111,37 @@ class SDFRenderer:
         closed = (s["valid"] == 1) & (s["spans"] >= 1) & ~((s["spans"] == 1) & ((s["flags"] & SPAN_ENDS_INSIDE) != 0))
         out[closed] = sp[closed, 0, 1] - sp[closed, 0, 0]
         return out
+
+    # ---- how much solid there is (sdfr_measure; DESIGN.md "Measure") ---------------------------------------------------------------------
+    def measure(self, grid, min_step, t_max=0.0, iso=0.0, max_steps=4096, columns=False, device=False):
+        """The moments of the solid over the columns of `grid` (a MeasureGrid: measureGrid, or made by hand), each marched as querySpans
+        marches a ray from its origin along grid.dw, integrated and summed on the GPU in a defined order -> a MeasureResult; with
+        columns=True (result, columns): MEASURE_COLUMN_DTYPE records [nv, nu], or with device=True an int32 tensor [nv, nu, 10] on the
+        renderer's GPU holding the same words."""
+        params = SpanParams(float(t_max), float(min_step), float(iso), int(max_steps), 0)
+        out, cols, pc = MeasureResult(), None, None
+        n = (max(int(grid.nv), 0), max(int(grid.nu), 0))
+        if columns and device:
+            import torch
+
+            cols = torch.empty(n + (10,), dtype=torch.int32, device=torch.device("cuda", self.device))
+            pc = ctypes.c_void_p(cols.data_ptr()) if cols.numel() else None
+        elif columns:
+            cols = np.zeros(n, MEASURE_COLUMN_DTYPE)
+            pc = cols.ctypes.data_as(ctypes.c_void_p) if cols.size else None
+        self._check(self._L.sdfr_measure(self._h, ctypes.byref(grid), ctypes.byref(params), ctypes.byref(out), pc, 0 if device else 1))
+        return (out, cols) if columns else out
+
+    measureProperties = staticmethod(measureProperties)
+
+    def measureSolid(self, box_lo, box_hi, cell, axis="z", density=1.0, min_step=None, iso=0.0, max_steps=4096):
+        """The one-call form: measureGrid over the box, measure with min_step (default cell / 2) over the box's depth, measureProperties
+        -> a dict of the properties, with the MeasureResult as `result` and the grid as `grid`."""
+        grid, depth = measureGrid(box_lo, box_hi, cell, axis)
+        res = self.measure(grid, 0.5 * float(cell) if min_step is None else min_step, t_max=depth, iso=iso, max_steps=max_steps)
+        props = measureProperties(grid, res, density)
+        props["result"], props["grid"] = res, grid
+        return props
 
     # ---- the texture atlas of a mesh (sdfr_atlas_texels / sdfr_atlas_bake; DESIGN.md "Texture atlas") -------------------------------
     def _atlas_inputs(self, positions, normals, indices, device):

@@ -36,6 +36,9 @@ layer: marching squares on cells of edge --slice-cell (SDFRenderer.extractSlices
 --slice-step thick (or --slice-layers of them; default: one, the whole box) and each is sliced through its middle.
 --xray writes how much solid each pixel's primary ray passes through, as the grey 255 * (1 - exp(-K * length)) with K = --xray-density:
 the inside length of SDFRenderer.pickSpans over the whole frame, marched on the GPU in steps of --xray-step at the least.
+--measure prints the volume, mass, centre of mass and inertia tensor of the solid inside --measure-box as one JSON object: columns along
+--measure-axis through cells of edge --measure-cell, marched in steps of --measure-step at the least (default: half a cell), integrated and
+summed on the GPU (SDFRenderer.measureSolid); `warning` says when the solid leaves the box or columns ran out of steps.
 --mesh-thickness T_MAX colours the vertices of --mesh by the thickness of the wall under them over T_MAX (SDFRenderer.meshThickness).
 """
 import argparse
@@ -228,7 +231,31 @@ def make_parser():
     ap.add_argument("--xray-density", type=float, metavar="K", help="grey = 255 * (1 - exp(-K * length)) (default 1)")
     ap.add_argument("--mesh-thickness", type=float, metavar="T_MAX", help="with --mesh: a grey per vertex, the wall thickness under it over T_MAX "
                     "(white: T_MAX or more) (instead of --mesh-colors / --mesh-ao / --mesh-lit)")
+    ap.add_argument("--measure", action="store_true", help="print volume, mass, centre of mass and inertia of the solid in --measure-box as JSON "
+                    "(needs --measure-box and --measure-cell)")
+    ap.add_argument("--measure-box", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--measure-cell", type=float, metavar="C", help="edge length of a column's square footprint")
+    ap.add_argument("--measure-axis", choices=("x", "y", "z"), default="z", help="the columns' direction (default z)")
+    ap.add_argument("--measure-step", type=float, metavar="H", help="the march's smallest step along a column (default C / 2)")
+    ap.add_argument("--measure-density", type=float, metavar="RHO", help="mass per unit volume (default 1)")
     return ap
+
+
+def measure_report(scene, props, cell, axis, step, density):
+    """--measure's JSON object from measureSolid's dict"""
+    res = props["result"]
+    out = {"scene": scene, "cell": cell, "axis": axis, "step": step, "density": density, "columns": [int(props["grid"].nu), int(props["grid"].nv)]}
+    out.update({k: (list(props[k]) if isinstance(props[k], tuple) else props[k]) for k in ("volume", "mass", "centroid", "inertia")})
+    for name in ("columns_hit", "columns_open", "columns_out_of_steps", "columns_invalid", "steps", "spans", "crossings"):
+        out[name] = int(getattr(res, name))
+    warnings = []
+    if res.columns_open:
+        warnings.append("the solid leaves the box in %d columns: this is the measure of a truncated solid" % res.columns_open)
+    if res.columns_out_of_steps:
+        warnings.append("%d columns ran out of steps" % res.columns_out_of_steps)
+    if warnings:
+        out["warning"] = "; ".join(warnings)
+    return out
 
 
 def xray_image(inside_length, w, h, density):
@@ -345,6 +372,20 @@ def main(argv=None):
             ap.error(str(e))
     elif a.slice_box is not None or a.slice_cell is not None or a.slice_step is not None or a.slice_layers is not None:
         ap.error("--slice-box, --slice-cell, --slice-step and --slice-layers need --slice")
+    measure_grid = None
+    if a.measure:
+        if a.measure_box is None or a.measure_cell is None:
+            ap.error("--measure needs --measure-box and --measure-cell")
+        if a.measure_step is not None and not (a.measure_step > 0 and math.isfinite(a.measure_step)):
+            ap.error("--measure-step must be finite and > 0")
+        if a.measure_density is not None and not (a.measure_density > 0 and math.isfinite(a.measure_density)):
+            ap.error("--measure-density must be finite and > 0")
+        try:
+            measure_grid = sp.measureGrid(a.measure_box[:3], a.measure_box[3:], a.measure_cell, a.measure_axis)
+        except ValueError as e:
+            ap.error("--measure-box / --measure-cell: " + str(e))
+    elif a.measure_box is not None or a.measure_cell is not None or a.measure_step is not None or a.measure_density is not None:
+        ap.error("--measure-box, --measure-cell, --measure-step and --measure-density need --measure")
     r = sp.SDFRenderer(a.device)
     if a.scene_source or a.scene_hlsl:
         import os
@@ -464,6 +505,16 @@ def main(argv=None):
         write_svg(a.slice, uv, chains, dims, a.slice_cell, title="%s, time %g, axis %s, cell %g, iso %g" % (a.scene, a.time, a.slice_axis, a.slice_cell, a.slice_iso))
         print("%s: %d vertices, %d segments, %d chains (%d closed) in %d layers of %dx%d cells -> %s" % (
             a.scene, len(pos), len(seg), sum(len(c) for c in chains), sum(1 for c in chains for _i, closed in c if closed), n_layers, dims[0], dims[1], a.slice))
+        if not a.out and not a.out_hdr and not a.gbuffer and not a.xray:
+            r.close()
+            return 0
+    if measure_grid:
+        import json
+
+        density = a.measure_density if a.measure_density is not None else 1.0
+        step = a.measure_step if a.measure_step is not None else 0.5 * a.measure_cell
+        props = r.measureSolid(a.measure_box[:3], a.measure_box[3:], a.measure_cell, a.measure_axis, density, min_step=step)
+        print(json.dumps(measure_report(a.scene, props, a.measure_cell, a.measure_axis, step, density)))
         if not a.out and not a.out_hdr and not a.gbuffer and not a.xray:
             r.close()
             return 0

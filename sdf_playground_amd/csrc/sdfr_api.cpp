@@ -10,6 +10,7 @@
 #include "sdfr_mesh_plan.h"
 #include "sdfr_slice_plan.h"
 #include "sdfr_span_plan.h"
+#include "sdfr_measure_plan.h"
 #include "sdfr_occlusion.h"
 #include "sdfr_query.h"
 #include "sdfr_query_plan.h"
@@ -1305,6 +1306,78 @@ int sdfr_mesh_fit(sdfr_renderer *r, const sdfr_mesh_grid *search, int levels, in
 		memcpy(out, &f, sizeof f);
 		return SDFR_OK;
 	});
+}
+
+// ---- sdfr_measure (the definition: include/sdfr.h; the plan and the properties: sdfr_measure_plan.h; the column and the reductions:
+// sdfr_measure.h; the kernels: sdfr_query_kernel.h and sdfr_mesh.hip), a call of the queries' protocol and synchronous like the counting
+// call of the mesh.  The partials and the tally lie in the extraction's workspace under its keep rule; a host call's `columns` are staged
+// in `query`; the result comes back as its 160 bytes.  No profiling event is recorded.
+static_assert(sizeof(sdfr_measure_grid) == sizeof(MeasureGrid) && offsetof(sdfr_measure_grid, du) == offsetof(MeasureGrid, du) && offsetof(sdfr_measure_grid, dw) == offsetof(MeasureGrid, dw) &&
+		offsetof(sdfr_measure_grid, nu) == offsetof(MeasureGrid, nu) && offsetof(sdfr_measure_grid, nv) == offsetof(MeasureGrid, nv),
+	"sdfr_measure_grid is the plan's MeasureGrid");
+static_assert(sizeof(sdfr_measure_result) == sizeof(MeasureResult) && offsetof(sdfr_measure_result, columns_hit) == offsetof(MeasureResult, columns_hit) &&
+		offsetof(sdfr_measure_result, crossings) == offsetof(MeasureResult, crossings) && offsetof(sdfr_measure_result, hit_hi) == offsetof(MeasureResult, hit_hi) &&
+		offsetof(sdfr_measure_result, t_hi) == offsetof(MeasureResult, t_hi),
+	"sdfr_measure_result is the kernels' MeasureResult");
+static_assert(sizeof(sdfr_measure_column) == 4 * MEASURE_COLUMN_WORDS && offsetof(sdfr_measure_column, spans) == 24 && offsetof(sdfr_measure_column, valid) == 36 &&
+		sizeof(MeasureColumn) == sizeof(sdfr_measure_column), "sdfr_measure_column is the measure kernel's 10-word record");
+static_assert(sizeof(sdfr_solid_properties) == sizeof(SolidProperties) && offsetof(sdfr_solid_properties, centroid) == offsetof(SolidProperties, centroid) &&
+		offsetof(sdfr_solid_properties, inertia) == offsetof(SolidProperties, inertia), "sdfr_solid_properties is the plan's SolidProperties");
+static int measure_impl(sdfr_renderer *r, const MeasureRequest &c, sdfr_measure_result *out)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	const MeasurePlan p = plan_measure(c, r->U.range);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, true, 1, 1, U, stream);
+	if (rc != SDFR_OK) return rc;
+
+	Carving work({p.work[0], p.work[1], p.work[2]});
+	rc = reserve_mesh_workspace(r, work, stream);
+	if (rc != SDFR_OK) return rc;
+	double *const partials[2] = {work.piece<double>(0), work.piece<double>(1)};
+	MeasureArgs g = p.a;
+	g.partials = partials[0];
+	g.tally = work.piece<void>(2);
+	Carving st;
+	if (c.on_host && p.column_bytes)
+	{
+		const StagedArray arrays[1] = {{&g.columns, p.column_bytes, false}};
+		rc = stage_host_arrays(r, st, arrays, 1, stream); // (in `query`, never in `mesh`)
+		if (rc != SDFR_OK) return rc;
+	}
+	KernelRef k;
+	rc = loaded_query_kernel(r, QUERY_KERNEL_MEASURE, U, k);
+	if (rc != SDFR_OK) return rc;
+	SDFR_HIP(launch_measure_init(g.tally, g.nu, g.nv, stream));
+	const hipError_t e = launch_query_measure(k, U, g, p.blocks, stream);
+	if (e != hipSuccess) return hip_fail(r, e, "measure launch");
+	SDFR_HIP(launch_measure_reduce(partials, p.pass_records, p.passes, g.tally, stream));
+	MeasureResult res;
+	SDFR_HIP(hipMemcpyAsync(&res, g.tally, sizeof res, hipMemcpyDeviceToHost, stream));
+	if (c.on_host && p.column_bytes) rc = copy_answers_back(r, st, stream);
+	else SDFR_HIP(hipStreamSynchronize(stream));
+	if (rc != SDFR_OK) return rc;
+	memcpy(out, &res, sizeof res);
+	return release_large(r, r->mesh, stream);
+}
+
+int sdfr_measure(sdfr_renderer *r, const sdfr_measure_grid *grid, const sdfr_span_params *params, sdfr_measure_result *out, sdfr_measure_column *columns, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		const MeasureRequest c = {reinterpret_cast<const MeasureGrid *>(grid), reinterpret_cast<const SpanParams *>(params), out, columns, on_host};
+		return measure_impl(r, c, out);
+	});
+}
+
+int sdfr_measure_properties(const sdfr_measure_grid *grid, const sdfr_measure_result *res, double density, sdfr_solid_properties *out)
+{
+	if (!grid || !res || !out || !std::isfinite(density)) return SDFR_ERR_INVALID_ARGUMENT;
+	SolidProperties o;
+	measure_properties(*reinterpret_cast<const MeasureGrid *>(grid), *reinterpret_cast<const MeasureResult *>(res), density, o);
+	memcpy(out, &o, sizeof o);
+	return SDFR_OK;
 }
 
 // ---- the texture atlas of a mesh (the definition: include/sdfr.h; the plan: sdfr_atlas_plan.h; the texel map and the bake: sdfr_atlas.h).

@@ -89,6 +89,7 @@ const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_
 	{"sdfr_jit_mesh_sharp", "mesh_sharp_kernel", "MeshSharpKernelArgs"},
 	{"sdfr_jit_query_slices", "query_slices_kernel", "SliceKernelArgs"},
 	{"sdfr_jit_query_spans", "query_spans_kernel", "SpanKernelArgs"},
+	{"sdfr_jit_query_measure", "query_measure_kernel", "MeasureKernelArgs"},
 };
 
 } // namespace

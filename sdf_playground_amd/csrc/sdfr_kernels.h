@@ -107,6 +107,15 @@ hipError_t launch_slice_emit(const SliceGrid &g, const float *lattice, const uin
 // pointer device memory, in `blocks` blocks of one wave (span_blocks).
 hipError_t launch_query_spans(const KernelRef &k, const FrameU &U, const SpanArgs &s, uint32_t blocks, hipStream_t stream);
 
+// The measure (sdfr_measure.h; the plan: sdfr_measure_plan.h), every pointer device memory.  launch_measure_init: the tally's words
+// (MEASURE_TALLY_BYTES) set for a grid of nu x nv columns.  launch_query_measure: a scene's measure kernel (QUERY_KERNEL_MEASURE) for U,
+// `blocks` blocks of one wave, one per 8 x 8 tile of columns -> g.partials, the tally, g.columns unless null.  launch_measure_reduce: the
+// passes of k_measure_reduce -- pass k reads pass_records[k] records of ten doubles from partials[k % 2] and writes a 64th as many, rounded
+// up, into the other -- and then the packed result (sdfr_measure_result) at the start of the tally.
+hipError_t launch_measure_init(void *tally, int32_t nu, int32_t nv, hipStream_t stream);
+hipError_t launch_query_measure(const KernelRef &k, const FrameU &U, const MeasureArgs &g, uint32_t blocks, hipStream_t stream);
+hipError_t launch_measure_reduce(double *const partials[2], const uint32_t *pass_records, int passes, void *tally, hipStream_t stream);
+
 // The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
 // per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes
 // instead the image of a bake without quads.  launch_atlas_bake: a scene's bake kernel (QUERY_KERNEL_ATLAS) for U.

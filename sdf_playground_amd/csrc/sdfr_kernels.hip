@@ -525,6 +525,15 @@ hipError_t launch_query_spans(const KernelRef &k, const FrameU &U, const SpanArg
 	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
 }
 
+hipError_t launch_query_measure(const KernelRef &k, const FrameU &U, const MeasureArgs &g, uint32_t blocks, hipStream_t stream)
+{
+	MeasureKernelArgs a;
+	a.U = U;
+	a.g = g;
+	void *args[] = {&a};
+	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
+}
+
 hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
 {
 	AtlasKernelArgs a;

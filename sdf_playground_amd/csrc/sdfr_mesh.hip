@@ -10,6 +10,7 @@
 #include "sdfr_kernels.h"
 #include "sdfr_mesh.h"
 #include "sdfr_mesh_survey.h"
+#include "sdfr_measure.h"
 #define SDFR_ATLAS_GEOMETRY_ONLY // the texel map alone: no scene is looked at here
 #include "sdfr_atlas.h"
 
@@ -295,6 +296,89 @@ hipError_t launch_mesh_survey(const MeshGrid &g, const float *lattice, float ban
 	hipLaunchKernelGGL(k_mesh_survey_init, dim3(1), dim3(64), 0, stream, out, g);
 	hipLaunchKernelGGL(k_mesh_survey, dim3((points + SDFR_MESH_BLOCK - 1u) / SDFR_MESH_BLOCK), dim3(SDFR_MESH_BLOCK), 0, stream, g, lattice, band, out);
 	hipLaunchKernelGGL(k_mesh_survey_pack, dim3(1), dim3(64), 0, stream, out);
+	return hipGetLastError();
+}
+
+// ---- the tiles of a measure, reduced (sdfr_measure; the definition and its host restatement: sdfr_measure.h) ----
+// k_measure_reduce: one wave per block turns a run of 64 consecutive records of one component (blockIdx.y) into one, by the six
+// xor-butterflies of the scene's measure kernel -- the pairwise tree x[m] = x[2m] + x[2m + 1], whichever lane is asked --, the lanes past
+// the last record carrying +0.0.  Launched in passes that ping-pong between two buffers until one record is left: the order of the sum is
+// the launches', never the arrival's.  k_measure_init sets the tally's words before the scene's kernel counts into them with integer
+// atomics (hit_lo = n, hit_hi = -1, the keys of +inf and -inf), sixteen copies of each; k_measure_pack gathers them and the last record
+// into the result.
+static_assert(sizeof(MeasureResult) == 160 && offsetof(MeasureResult, columns_hit) == 80 && offsetof(MeasureResult, steps) == 112 && offsetof(MeasureResult, hit_lo) == 136 &&
+		offsetof(MeasureResult, t_lo) == 152 && sizeof(MeasureResult) <= MEASURE_TALLY_STRIDE * MEASURE_TALLY_FIRST, "the packed result lies before the tally's words");
+static_assert((MEASURE_TALLY_COPIES & (MEASURE_TALLY_COPIES - 1)) == 0 && MEASURE_TALLY_WORDS * MEASURE_TALLY_COPIES <= 256 &&
+		MEASURE_TALLY_BYTES == MEASURE_TALLY_STRIDE * (MEASURE_TALLY_FIRST + MEASURE_TALLY_WORDS * MEASURE_TALLY_COPIES), "a thread per copy of a word in k_measure_init");
+// copy k of word t
+__device__ __forceinline__ char *measure_word(void *tally, int t, int k)
+{
+	return static_cast<char *>(tally) + (size_t)MEASURE_TALLY_STRIDE * (size_t)(MEASURE_TALLY_FIRST + MEASURE_TALLY_COPIES * t + k);
+}
+
+__global__ __launch_bounds__(256) void k_measure_init(void *tally, int32_t nu, int32_t nv)
+{
+	const int t = (int)threadIdx.x / MEASURE_TALLY_COPIES, k = (int)threadIdx.x % MEASURE_TALLY_COPIES;
+	if (blockIdx.x != 0) return;
+	if (t < MEASURE_TALLY_COUNTS) *reinterpret_cast<int64_t *>(measure_word(tally, t, k)) = 0;
+	else if (t < 11) *reinterpret_cast<int32_t *>(measure_word(tally, t, k)) = t == 7 ? nu : t == 8 ? nv : -1;
+	else if (t < MEASURE_TALLY_WORDS) *reinterpret_cast<uint32_t *>(measure_word(tally, t, k)) = measure_order_key(measure_inf(t == 12));
+}
+__global__ __launch_bounds__(64) void k_measure_pack(void *tally, const double *__restrict__ record)
+{
+	const int t = (int)threadIdx.x;
+	if (blockIdx.x != 0) return;
+	MeasureResult *out = static_cast<MeasureResult *>(tally);
+	if (t < MEASURE_TALLY_COUNTS)
+	{
+		int64_t sum = 0;
+		for (int k = 0; k < MEASURE_TALLY_COPIES; ++k) sum += *reinterpret_cast<const int64_t *>(measure_word(tally, t, k));
+		(&out->columns_hit)[t] = sum;
+	}
+	else if (t < 11)
+	{
+		int32_t v = *reinterpret_cast<const int32_t *>(measure_word(tally, t, 0));
+		for (int k = 1; k < MEASURE_TALLY_COPIES; ++k)
+		{
+			const int32_t o = *reinterpret_cast<const int32_t *>(measure_word(tally, t, k));
+			v = (t < 9 ? o < v : o > v) ? o : v;
+		}
+		out->hit_lo[t - 7] = v; // (hit_hi follows hit_lo)
+	}
+	else if (t < MEASURE_TALLY_WORDS)
+	{
+		uint32_t v = *reinterpret_cast<const uint32_t *>(measure_word(tally, t, 0));
+		for (int k = 1; k < MEASURE_TALLY_COPIES; ++k)
+		{
+			const uint32_t o = *reinterpret_cast<const uint32_t *>(measure_word(tally, t, k));
+			v = (t == 11 ? o < v : o > v) ? o : v;
+		}
+		(&out->t_lo)[t - 11] = measure_order_value(v);
+	}
+	else if (t < MEASURE_TALLY_WORDS + MEASURE_MOMENTS) out->moments[t - MEASURE_TALLY_WORDS] = record[t - MEASURE_TALLY_WORDS];
+}
+__global__ __launch_bounds__(64) void k_measure_reduce(const double *__restrict__ in, uint32_t n, double *__restrict__ out)
+{
+	const uint32_t run = blockIdx.x, c = blockIdx.y, i = run * (uint32_t)MEASURE_RUN + threadIdx.x;
+	// (no early return: every lane takes part in the shuffles)
+	double v = i < n ? in[(size_t)i * MEASURE_MOMENTS + c] : 0.0;
+	for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d, 64);
+	if (threadIdx.x == 0) out[(size_t)run * MEASURE_MOMENTS + c] = v;
+}
+
+hipError_t launch_measure_init(void *tally, int32_t nu, int32_t nv, hipStream_t stream)
+{
+	hipLaunchKernelGGL(k_measure_init, dim3(1), dim3(256), 0, stream, tally, nu, nv);
+	return hipGetLastError();
+}
+hipError_t launch_measure_reduce(double *const partials[2], const uint32_t *pass_records, int passes, void *tally, hipStream_t stream)
+{
+	for (int k = 0; k < passes; ++k)
+	{
+		const uint32_t n = pass_records[k], runs = (n + (uint32_t)MEASURE_RUN - 1u) / (uint32_t)MEASURE_RUN;
+		hipLaunchKernelGGL(k_measure_reduce, dim3(runs, MEASURE_MOMENTS), dim3(64), 0, stream, partials[k % 2], n, partials[(k + 1) % 2]);
+	}
+	hipLaunchKernelGGL(k_measure_pack, dim3(1), dim3(64), 0, stream, tally, partials[passes % 2]);
 	return hipGetLastError();
 }
 

@@ -53,6 +53,13 @@ struct SpanKernelArgs
 	SpanArgs s;
 };
 
+// ... and the measure kernel (MeasureArgs: sdfr_query_args.h)
+struct MeasureKernelArgs
+{
+	FrameU U;
+	MeasureArgs g;
+};
+
 // the driver's normal at pos (pshader_sdf.hlsl:164-177, 320-330): map_normal with the NormalOutput preloaded {grad_eps, 0, false};
 // its normal if it sets use_normal, else the three forward differences against `baseline`, normalised
 template <class Scene, bool DBG>

@@ -39,7 +39,7 @@ static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offseto
 static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
 // A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_SLICES = 8, QUERY_KERNEL_SPANS = 9, QUERY_KERNEL_KINDS = 10 };
+enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_SLICES = 8, QUERY_KERNEL_SPANS = 9, QUERY_KERNEL_MEASURE = 10, QUERY_KERNEL_KINDS = 11 };
 
 // One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
@@ -125,5 +125,32 @@ static_assert(sizeof(SpanArgs) == 72 && __builtin_offsetof(SpanArgs, n) == 4 && 
 static_assert(__builtin_offsetof(SpanArgs, pixels) == 24 && __builtin_offsetof(SpanArgs, reach) == 32 && __builtin_offsetof(SpanArgs, t_max) == 36, "");
 static_assert(__builtin_offsetof(SpanArgs, iso) == 44 && __builtin_offsetof(SpanArgs, max_steps) == 48 && __builtin_offsetof(SpanArgs, max_spans) == 52, "");
 static_assert(__builtin_offsetof(SpanArgs, summaries) == 56 && __builtin_offsetof(SpanArgs, spans) == 64, "SpanArgs is a kernel argument");
+
+// One measure launch (sdfr_kernels.h: launch_query_measure; sdfr_measure): the moments of the solid over nu x nv parallel columns
+// (sdfr_measure.h), a wave per 8 x 8 tile of columns.  Column (i, j) starts at (origin + (float)i * du) + (float)j * dv per component and
+// runs along dw.  partials: 10 doubles per tile, tiles row-major; columns: 10 words per column, the layout of sdfr_measure_column, row-major
+// i + nu * j, or null; tally: the words the integer totals are counted in (MEASURE_TALLY_*).  nu, nv <= 8192, nu * nv <= 2^24.
+struct MeasureArgs
+{
+	float origin[3];
+	float du[3], dv[3], dw[3];
+	int32_t nu, nv;
+	float t_max, min_step, iso; // t_max: the effective one, never the 0 that stands for limits.range
+	int32_t max_steps;
+	double *partials;
+	uint32_t *columns;
+	void *tally;
+};
+static_assert(sizeof(MeasureArgs) == 96 && __builtin_offsetof(MeasureArgs, du) == 12 && __builtin_offsetof(MeasureArgs, dw) == 36 && __builtin_offsetof(MeasureArgs, nu) == 48, "");
+static_assert(__builtin_offsetof(MeasureArgs, t_max) == 56 && __builtin_offsetof(MeasureArgs, iso) == 64 && __builtin_offsetof(MeasureArgs, max_steps) == 68, "");
+static_assert(__builtin_offsetof(MeasureArgs, partials) == 72 && __builtin_offsetof(MeasureArgs, columns) == 80 && __builtin_offsetof(MeasureArgs, tally) == 88, "MeasureArgs is a kernel argument");
+// The tally while it is counted: the packed result (sdfr_measure_result, 160 bytes) in the first two lines, then 16 copies of word t,
+// each in a line of its own: line MEASURE_TALLY_FIRST + 16 * t + k, and tile b counts into copy k = b & 15.  (As the survey's words:
+// packed into one line the atomics of all tiles queue up behind each other; and every tile has steps to add, so even a word with a line
+// to itself takes its atomics one by one -- 16 384 tiles stood 170 us behind one word of `steps`)
+// Words 0 .. 6: 64-bit counts -- columns hit, open, out of steps, invalid; steps, spans, crossings; 7 .. 10: hit_lo[2], hit_hi[2];
+// 11, 12: the order keys of t_lo and t_hi.  k_measure_pack adds up, or takes the bounds of, the copies.
+enum { MEASURE_TALLY_COUNTS = 7, MEASURE_TALLY_WORDS = 13, MEASURE_TALLY_COPIES = 16, MEASURE_TALLY_STRIDE = 128, MEASURE_TALLY_FIRST = 2,
+	MEASURE_TALLY_BYTES = 128 * (2 + 13 * 16) };
 
 } // namespace sdfr

@@ -14,6 +14,7 @@
 #include "sdfr_mesh_sharp.h"
 #include "sdfr_slice.h"
 #include "sdfr_span.h"
+#include "sdfr_measure.h"
 
 namespace sdfr {
 
@@ -497,6 +498,141 @@ __device__ __forceinline__ void query_spans_kernel(const SpanKernelArgs &a)
 #pragma unroll
 		for (int k = 0; k < SPAN_SUMMARY_WORDS; ++k) out[k] = rec[k];
 	}
+}
+
+// The measure query (sdfr_measure.h; sdfr_measure): one wave per 8 x 8 tile of columns, addressed by the block index alone, one lane per
+// column, marched as the span kernel marches a ray (the same functor).  The first kernel of this unit whose lanes talk to each other: a
+// lane past the grid's ragged edges does NOT leave -- it carries +0.0 into the reduction, and every lane of the wave reaches every shuffle
+// and ballot below (the march's loop is the only divergent code, and it has ended).
+//   moments: per component six xor-butterflies over the lane distances 1, 2, 4, 8, 16, 32.  Addition commutes, so both partners of a step
+//   hold the same bits and after the six every lane holds the pairwise tree x[m] = x[2m] + x[2m + 1] over the 64 lanes, the order the
+//   definition fixes.  Lane 0 stores the tile's ten doubles; k_measure_reduce (sdfr_mesh.hip) takes it from there.
+//   integers: ballots and popcounts for the column counts, shuffles for the sums and bounds -- every value the whole wave's --, then lane t
+//   issues the atomic of word t (MEASURE_TALLY_*; into the copy of the word that the tile's index selects) if the tile has anything for it: 64-bit atomicAdd, 32-bit atomicMin / atomicMax (agent
+//   scope, HIP's default), the fp32 bounds as their order keys.  Integer atomics: the order of arrival changes nothing.
+// A column's record leaves as five 8-byte stores into an array aligned to 8 bytes, as word stores into any other.
+typedef uint32_t measure_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ double measure_wave_tree(double v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d, 64);
+	return v;
+}
+__device__ __forceinline__ uint32_t measure_wave_sum(uint32_t v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+	return v;
+}
+__device__ __forceinline__ int measure_wave_min(int v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1)
+	{
+		const int o = __shfl_xor(v, d, 64);
+		v = o < v ? o : v;
+	}
+	return v;
+}
+__device__ __forceinline__ int measure_wave_max(int v)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1)
+	{
+		const int o = __shfl_xor(v, d, 64);
+		v = o > v ? o : v;
+	}
+	return v;
+}
+template <class Scene, bool DBG>
+__device__ __forceinline__ void query_measure_kernel(const MeasureKernelArgs &a)
+{
+	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 columns");
+	const FrameU &U = a.U;
+	const MeasureArgs &g = a.g;
+	const uint32_t lane = threadIdx.x;
+	const uint32_t tu = ((uint32_t)g.nu + 7u) >> 3;
+	const uint32_t tj = blockIdx.x / tu, ti = blockIdx.x - tj * tu;
+	const int i = (int)(ti * 8u + (lane & 7u)), j = (int)(tj * 8u + (lane >> 3));
+	const bool live = i < g.nu && j < g.nv;
+	MeasureLane c = measure_no_column();
+	if (live)
+	{
+		const SpanSceneDistance<Scene, DBG> distance = {U, debug_flags(U), Scene::ray_setup(U, V3s(0.f), query_ray_flags())};
+		const vec3 o = V3(measure_origin(g.origin, g.du, g.dv, 0, i, j), measure_origin(g.origin, g.du, g.dv, 1, i, j), measure_origin(g.origin, g.du, g.dv, 2, i, j));
+		c = measure_column(distance, o, V3(g.dw[0], g.dw[1], g.dw[2]), g.t_max, g.min_step, g.iso, g.max_steps);
+		if (g.columns)
+		{
+			uint32_t *out = g.columns + (size_t)MEASURE_COLUMN_WORDS * ((size_t)i + (size_t)g.nu * (size_t)j); // (< 2^24 records of 40 bytes)
+			const uint64_t m[3] = {(uint64_t)__double_as_longlong(c.c.m0), (uint64_t)__double_as_longlong(c.c.m1), (uint64_t)__double_as_longlong(c.c.m2)};
+			const uint32_t w[MEASURE_COLUMN_WORDS] = {(uint32_t)m[0], (uint32_t)(m[0] >> 32), (uint32_t)m[1], (uint32_t)(m[1] >> 32), (uint32_t)m[2], (uint32_t)(m[2] >> 32),
+				c.c.spans, c.c.steps, c.c.flags, (uint32_t)c.c.valid};
+			if ((reinterpret_cast<size_t>(g.columns) & 7u) == 0u)
+			{
+#pragma unroll
+				for (int k = 0; k < MEASURE_COLUMN_WORDS / 2; ++k)
+				{
+					measure_u32x2 v;
+					v.x = w[2 * k];
+					v.y = w[2 * k + 1];
+					reinterpret_cast<measure_u32x2 *>(out)[k] = v; // one 8-byte store
+				}
+			}
+			else
+			{
+#pragma unroll
+				for (int k = 0; k < MEASURE_COLUMN_WORDS; ++k) out[k] = w[k];
+			}
+		}
+	}
+	// ---- from here on the whole wave, converged
+	double v[MEASURE_MOMENTS];
+	measure_contributions(c.c, live ? i : 0, live ? j : 0, v); // (no column, or none with an answer: m0 = m1 = m2 = +0.0, ten times +0.0)
+#pragma unroll
+	for (int k = 0; k < MEASURE_MOMENTS; ++k) v[k] = measure_wave_tree(v[k]);
+	if (lane == 0u)
+	{
+		double *tile = g.partials + (size_t)MEASURE_MOMENTS * blockIdx.x;
+#pragma unroll
+		for (int k = 0; k < MEASURE_MOMENTS; ++k) tile[k] = v[k];
+	}
+
+	const unsigned long long hit = __ballot(c.c.spans >= 1u);
+	const uint32_t n_open = (uint32_t)__popcll(__ballot((c.c.flags & (uint32_t)(SPAN_STARTS_INSIDE | SPAN_ENDS_INSIDE)) != 0u));
+	const uint32_t n_out = (uint32_t)__popcll(__ballot((c.c.flags & (uint32_t)SPAN_OUT_OF_STEPS) != 0u));
+	const uint32_t n_invalid = (uint32_t)__popcll(__ballot(live && c.c.valid != 1));
+	const uint32_t steps = measure_wave_sum(c.c.steps); // (64 columns of at most 2^20 steps: 32 bits hold it)
+	// (wave-uniform branches: `hit` is the whole wave's)
+	const uint32_t spans = hit ? measure_wave_sum(c.c.spans) : 0u, crossings = steps ? measure_wave_sum(c.crossings) : 0u;
+	int32_t lo[2] = {g.nu, g.nv}, hi[2] = {-1, -1};
+	float t_lo = c.t_lo, t_hi = c.t_hi; // (+inf and -inf in a lane without a span; never NaN)
+	if (hit)
+	{
+		const bool mine = c.c.spans >= 1u;
+		lo[0] = measure_wave_min(mine ? i : g.nu), lo[1] = measure_wave_min(mine ? j : g.nv);
+		hi[0] = measure_wave_max(mine ? i : -1), hi[1] = measure_wave_max(mine ? j : -1);
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1)
+		{
+			const float o_lo = __shfl_xor(t_lo, d, 64), o_hi = __shfl_xor(t_hi, d, 64);
+			t_lo = o_lo < t_lo ? o_lo : t_lo;
+			t_hi = o_hi > t_hi ? o_hi : t_hi;
+		}
+	}
+	char *const tally = static_cast<char *>(g.tally) + (size_t)MEASURE_TALLY_STRIDE * (size_t)((uint32_t)MEASURE_TALLY_FIRST + (uint32_t)MEASURE_TALLY_COPIES * (lane < (uint32_t)MEASURE_TALLY_WORDS ? lane : 0u) +
+		(blockIdx.x & (uint32_t)(MEASURE_TALLY_COPIES - 1)));
+	if (lane < (uint32_t)MEASURE_TALLY_COUNTS)
+	{
+		const uint32_t count = lane == 0u ? (uint32_t)__popcll(hit) : lane == 1u ? n_open : lane == 2u ? n_out : lane == 3u ? n_invalid : lane == 4u ? steps : lane == 5u ? spans : crossings;
+		if (count) atomicAdd(reinterpret_cast<unsigned long long *>(tally), (unsigned long long)count);
+	}
+	else if (lane < 11u && hit)
+	{
+		if (lane < 9u) atomicMin(reinterpret_cast<int32_t *>(tally), lane == 7u ? lo[0] : lo[1]);
+		else atomicMax(reinterpret_cast<int32_t *>(tally), lane == 9u ? hi[0] : hi[1]);
+	}
+	else if (lane == 11u && hit) atomicMin(reinterpret_cast<uint32_t *>(tally), measure_order_key(t_lo));
+	else if (lane == 12u && hit) atomicMax(reinterpret_cast<uint32_t *>(tally), measure_order_key(t_hi));
 }
 
 } // namespace sdfr

@@ -1,4 +1,4 @@
-// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice, k_query_surfaces, k_query_occlusion, k_query_lighting, k_bake_atlas, k_mesh_sharp, k_query_slices, k_query_spans: sdfr_query_kernel.h) of ONE scene, compiled
+// sdfr_query_scene.hip -- the query kernels (k_query_points, k_query_rays, k_query_lattice, k_query_surfaces, k_query_occlusion, k_query_lighting, k_bake_atlas, k_mesh_sharp, k_query_slices, k_query_spans, k_query_measure: sdfr_query_kernel.h) of ONE scene, compiled
 // once per scene with -DSDFR_SCENE=<index> and the scene's code-generation options (sdf_playground_amd/buildlib.py), like
 // sdfr_kernels_scene.hip.  They live in a unit of their own: a second caller of the shared inline stages in the pixel kernels'
 // unit could change the inliner's decisions there, and with them k_pixel's code.
@@ -87,6 +87,13 @@ __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_spans(SpanKernelArgs a)
 	query_spans_kernel<Scene, DBG>(a);
 }
 
+// the moments of the solid over a bundle of parallel columns (sdfr_measure)
+template <class Scene, bool DBG>
+__global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void k_query_measure(MeasureKernelArgs a)
+{
+	query_measure_kernel<Scene, DBG>(a);
+}
+
 using UnitScene = SceneAt<SDFR_SCENE>::type;
 
 // what this unit exports (scene_query_kernels, launch_query: sdfr_kernels.hip)
@@ -115,6 +122,8 @@ const QueryKernels *SDFR_CAT(scene_query_kernels_, SDFR_SCENE)()
 		q.k[QUERY_KERNEL_SLICES][0].kernel = (const void *)k_query_slices<UnitScene, false>;
 		q.k[QUERY_KERNEL_SPANS][1].kernel = (const void *)k_query_spans<UnitScene, true>;
 		q.k[QUERY_KERNEL_SPANS][0].kernel = (const void *)k_query_spans<UnitScene, false>;
+		q.k[QUERY_KERNEL_MEASURE][1].kernel = (const void *)k_query_measure<UnitScene, true>;
+		q.k[QUERY_KERNEL_MEASURE][0].kernel = (const void *)k_query_measure<UnitScene, false>;
 		return q;
 	}();
 	return &k;

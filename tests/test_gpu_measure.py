@@ -1,0 +1,359 @@
+"""GPU tier of sdfr_measure through libsdfr.so: every bit of the result record and of the columns equal to the definition of include/sdfr.h
+restated in numpy (measure_util.measure), fed with the oracle's distances for the built-in scenes and a dialect scene, on grids chosen
+where the kernels can go wrong -- one lane, a ragged tile, one full tile, ragged on both axes, a second pass with a padded run, a third
+pass --; the run-time probe scene with its NaN half-space; a tilted grid; the debug kernel variant; columns into host memory, device
+memory and a device array off its alignment; columns that run out of steps; two calls, the same bits; no side effects on rendering with
+two frames in flight; the argument errors through the raw C ABI; measureSolid against the closed forms of a sphere; the command line."""
+import ctypes
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+
+import measure_util as mu
+import query_util as qu
+import span_util as su
+from test_gpu_mesh_survey import DEFAULT_LIMITS, PROBE
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+W, H = 64, 48
+RANGE = DEFAULT_LIMITS["range"]
+CELL, MIN_STEP, MAX_STEPS = 0.05, 0.05, 96
+# scene: (time, the origin of column (0, 0), the columns' direction, their depth): columns of a 0.05 lattice in x and z that come down on
+# the scene from above -- some meet nothing, some pass through a solid, some end in the ground --, or rise out of the ground
+CASES = {"fast_sphere": (0.0, (-1.85, 2.5, -1.05), (0, -1, 0), 2.45), "cube_sea": (0.5, (-1.85, 2.5, -1.05), (0, -1, 0), 2.45),
+         "labyrinth": (1.25, (-5.35, -0.3, -2.55), (0, 1, 0), 2.5), "noise_lod": (0.5, (-1.85, 2.5, -1.05), (0, -1, 0), 2.45)}
+GRIDS = [(1, 1), (7, 5), (8, 8), (9, 17), (72, 65)]  # one lane live; a single ragged tile; one full tile; ragged on both axes; 81 tiles: a second pass with a padded run
+
+
+def _setup(r, scene, of):
+    """the handle's state = the oracle frame `of`"""
+    if scene in qu.HLSL:
+        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
+    else:
+        r.initShader(scene)
+    r.setParameters(of.stime)
+    r.setCameraBasis(of.eye, of.front, of.right, of.top)
+    r.setLimits(**DEFAULT_LIMITS)
+    r.setStepShortcuts(False)
+
+
+def _probe(r, **values):
+    """the probe scene of tests/test_gpu_mesh_survey.py with its variables set"""
+    if r.currentScene() != "measure_probe":
+        r.initShaderSource("measure_probe", PROBE)
+        r.setLimits(**DEFAULT_LIMITS)
+    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
+        assert r.setValue(name, v)
+
+
+def _stats(r):
+    s = r.getStats()
+    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    import sdf_playground_amd as sp
+
+    r = sp.SDFRenderer(0)
+    yield r
+    r.close()
+
+
+def _grid(g):
+    import sdf_playground_amd as sp
+
+    return mu.host_grid(g, sp.MeasureGrid)
+
+
+def _distance(scene, of):
+    return lambda pts: qu.oracle_points(scene, of, pts, normals=False)[0]
+
+
+def _scene_grid(scene, nu, nv, first=(0, 0)):
+    """nu x nv columns of the scene's lattice; column (0, 0) is the lattice's column `first` (so that a small grid sees something)"""
+    _stime, origin, dw, depth = CASES[scene]
+    return mu.grid((origin[0] + first[0] * CELL, origin[1], origin[2] + first[1] * CELL), (CELL, 0, 0), (0, 0, CELL), dw, nu, nv), depth
+
+
+_expected = {}
+
+
+def expected(scene, nu, nv, max_steps=MAX_STEPS):
+    """the restatement over the oracle's distances, once per grid"""
+    key = (scene, nu, nv, max_steps)
+    if key not in _expected:
+        stime = CASES[scene][0]
+        g, depth = _scene_grid(scene, nu, nv, (0, 0) if nu > 60 else (30, 14))
+        _expected[key] = (g, depth) + mu.measure(_distance(scene, qu.frame(scene, stime, W, H)), g, su.params(MIN_STEP, depth, 0.0, max_steps))
+    return _expected[key]
+
+
+def _columns(cols):
+    if hasattr(cols, "data_ptr"):
+        cols = cols.cpu().numpy()
+    return np.ascontiguousarray(cols).view(mu.COLUMN_DTYPE).reshape(cols.shape[0], cols.shape[1])
+
+
+def _check(renderer, what, g, want, want_col, **kw):
+    """the result alone; the result and columns in host memory; the result and columns in device memory"""
+    mu.assert_same_result((what, "result"), renderer.measure(_grid(g), **kw), want)
+    res, cols = renderer.measure(_grid(g), columns=True, **kw)
+    mu.assert_same_result((what, "host"), res, want)
+    mu.assert_same_columns((what, "host"), _columns(cols), want_col)
+    res, cols = renderer.measure(_grid(g), columns=True, device=True, **kw)
+    mu.assert_same_result((what, "device"), res, want)
+    mu.assert_same_columns((what, "device"), _columns(cols), want_col)
+
+
+# ---- parity ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", sorted(CASES))
+def test_measure_equals_the_definition(renderer, scene):
+    _setup(renderer, scene, qu.frame(scene, CASES[scene][0], W, H))
+    hit = 0
+    for nu, nv in GRIDS:
+        g, depth, want, want_col = expected(scene, nu, nv)
+        _check(renderer, (scene, nu, nv), g, want, want_col, min_step=MIN_STEP, t_max=depth, max_steps=MAX_STEPS)
+        hit += want["columns_hit"]
+        assert want["columns_invalid"] == 0 and want["steps"] >= nu * nv
+    g, depth, want, _c = expected(scene, 72, 65)
+    assert want["passes"] == 2 and 0 < want["columns_hit"] and want["moments"][0] > 0 and hit > want["columns_hit"]
+    # t_max = 0 is limits.range: the columns run on to the range, 100
+    small, _depth = _scene_grid(scene, 9, 17, (30, 14))
+    far, far_col = mu.measure(_distance(scene, qu.frame(scene, CASES[scene][0], W, H)), small, su.params(2.0, RANGE, 0.0, MAX_STEPS))
+    mu.assert_same_result((scene, "t_max 0"), renderer.measure(_grid(small), 2.0, max_steps=MAX_STEPS), far)
+    # an iso off zero
+    off, off_col = mu.measure(_distance(scene, qu.frame(scene, CASES[scene][0], W, H)), small, su.params(MIN_STEP, _depth, 0.04, MAX_STEPS))
+    _check(renderer, (scene, "iso"), small, off, off_col, min_step=MIN_STEP, t_max=_depth, iso=0.04, max_steps=MAX_STEPS)
+
+
+def test_a_third_pass_on_fast_sphere(renderer):
+    """520 x 512 columns are 4160 tiles: 65 runs, then 2, then 1"""
+    scene = "fast_sphere"
+    of = qu.frame(scene, 0.0, W, H)
+    _setup(renderer, scene, of)
+    cell = 0.005
+    g = mu.grid((-1.3, 2.5, -1.3), (cell, 0, 0), (0, 0, cell), (0, -1, 0), 520, 512)
+    p = su.params(0.25, 2.45, 0.0, 32)
+    want, want_col = mu.measure(_distance(scene, of), g, p)
+    assert want["passes"] == 3 and len(want["tiles"]) == 4160 and want["columns_hit"] > 20000 and want["columns_out_of_steps"] == 0
+    res, cols = renderer.measure(_grid(g), 0.25, t_max=2.45, max_steps=32, columns=True, device=True)
+    mu.assert_same_result("520 x 512", res, want)
+    mu.assert_same_columns("520 x 512", _columns(cols), want_col)
+    again = renderer.measure(_grid(g), 0.25, t_max=2.45, max_steps=32)
+    assert bytes(again) == bytes(res)  # two calls, the same bits, whatever order the tiles' atomics arrived in
+
+
+def test_probe_scene_with_its_nan_half_space(renderer):
+    """the library's own point query in the restatement: the sphere, the plane, and NaN where x > split"""
+    D = lambda pts: renderer.queryDistance(pts)  # noqa: E731
+    # the plane y = 0.25, solid below, NaN where x > 0.33: columns down from y = 1 end inside where x <= 0.3 and see nothing beyond
+    _probe(renderer, kind=2.0, height=0.25, split=0.33)
+    g = mu.grid((-0.5, 1.0, -0.4), (0.1, 0, 0), (0, 0, 0.1), (0, -1, 0), 17, 9)
+    p = su.params(0.1, 1.5, 0.0, 64)
+    want, want_col = mu.measure(D, g, p)
+    assert want["columns_hit"] == 9 * 9 == want["columns_open"] and want["hit_hi"] == (8, 8) and want["t_hi"] == F(1.5)
+    assert np.isnan(D(mu.column_rays(g)[0][9:10])).all()
+    _check(renderer, "NaN half-space", g, want, want_col, min_step=0.1, t_max=1.5, max_steps=64)
+    # columns along +x out of the solid half into NaN: the crossing is cut at a bracket's middle
+    g = mu.grid((-0.55, -0.3, -0.4), (0, 0.06, 0), (0, 0, 0.1), (1, 0, 0), 16, 9)  # y = -0.3 .. 0.6: ten rows below the plane
+    want, want_col = mu.measure(D, g, p)
+    assert want["columns_hit"] == 10 * 9 and want["columns_open"] == 10 * 9 and want["crossings"] == 10 * 9
+    _check(renderer, "into NaN", g, want, want_col, min_step=0.1, t_max=1.5, max_steps=64)
+    # the sphere
+    _probe(renderer, cx=0.03, cy=0.05, cz=0.07, radius=0.8)
+    g, depth = mu.box_grid((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), 0.05, "y")
+    want, want_col = mu.measure(D, g, su.params(0.025, depth, 0.0, 4096))
+    assert want["columns_open"] == 0 and want["spans"] == want["columns_hit"] > 700
+    _check(renderer, "sphere", g, want, want_col, min_step=0.025, t_max=depth)
+
+
+def test_measure_solid_on_a_sphere(renderer):
+    """the one-call form against 4/3 pi rho^3, the centre and 2/5 m rho^2, rho / cell = 16, within twice the worst case the CPU tier
+    recorded for the definition at that resolution (tests/test_measure_cpu.py: RECORDED_WORST[16])"""
+    import sdf_playground_amd as sp
+    from test_measure_cpu import RECORDED_WORST
+
+    centre, rho, cell, density = (0.03, 0.05, 0.07), 0.8, 0.05, 2.5
+    _probe(renderer, cx=centre[0], cy=centre[1], cz=centre[2], radius=rho)
+    c32, r32 = np.array([F(v) for v in centre], np.float64), float(F(rho))
+    volume = 4.0 / 3.0 * math.pi * r32 ** 3
+    v_bound, i_bound, c_bound = (2 * x for x in RECORDED_WORST[16])
+    for axis in "xyz":
+        props = renderer.measureSolid((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), cell, axis, density)
+        res = props["result"]
+        assert res.columns_open == 0 and res.columns_out_of_steps == 0 and res.columns_invalid == 0 and res.columns_hit > 700
+        print("axis %s: volume %.6f (%.6f), centroid %s, inertia %s" % (axis, props["volume"], volume, props["centroid"], props["inertia"]))
+        assert abs(props["volume"] - volume) / volume <= v_bound and props["mass"] == density * props["volume"]
+        assert np.linalg.norm(np.array(props["centroid"]) - c32) / cell <= c_bound
+        inertia = 0.4 * density * volume * r32 ** 2
+        w = "xyz".index(axis)
+        assert abs(props["inertia"][w] - inertia) / inertia <= i_bound  # about the columns' axis: the moment the CPU tier recorded
+        # the restatement gives the same properties from the same result, bit for bit
+        grid, _depth = sp.measureGrid((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), cell, axis)
+        g = mu.grid(list(grid.origin), list(grid.du), list(grid.dv), list(grid.dw), grid.nu, grid.nv)
+        want = mu.properties(g, dict(moments=list(res.moments)), density)
+        assert (props["volume"], props["mass"], props["centroid"], props["inertia"]) == (want["volume"], want["mass"], want["centroid"], want["inertia"])
+
+
+def test_a_tilted_grid(renderer):
+    """du, dv and dw near the camera's right, top and front, each skewed by the other two so that no component of any is zero, |dw| about
+    0.7: a sheared bundle through what the camera sees"""
+    for scene in ("labyrinth", "fast_sphere"):
+        of = qu.frame(scene, CASES[scene][0], W, H)
+        _setup(renderer, scene, of)
+        eye, front, right, top = (np.array(list(v), np.float64) for v in (of.eye, of.front, of.right, of.top))
+        right, top, front = right / np.linalg.norm(right), top / np.linalg.norm(top), front / np.linalg.norm(front)
+        du, dv, dw = 0.04 * right + 0.006 * top + 0.004 * front, 0.03 * top - 0.005 * right + 0.003 * front, 0.7 * front + 0.05 * right - 0.02 * top
+        g = mu.grid(eye - 16.5 * du - 12.5 * dv, du, dv, dw, 33, 25)
+        p = su.params(0.05, 12.0, 0.0, 192)
+        want, want_col = mu.measure(_distance(scene, of), g, p)
+        assert want["columns_hit"] > 100 and min(abs(x) for v in (g["du"], g["dv"], g["dw"]) for x in v) > 0, (scene, want["columns_hit"])
+        _check(renderer, (scene, "tilted"), g, want, want_col, min_step=0.05, t_max=12.0, max_steps=192)
+        # the properties of a sheared lattice: |det| is the volume of its cell
+        props = renderer.measureProperties(_grid(g), renderer.measure(_grid(g), 0.05, t_max=12.0, max_steps=192), 1.0)
+        det = abs(np.linalg.det(np.stack([g["du"], g["dv"], g["dw"]]).astype(np.float64)))
+        assert abs(props["volume"] - want["moments"][0] * det) <= 1e-12 * props["volume"]
+
+
+def test_debug_plane_and_show_objects(renderer):
+    """the DBG kernel variant: the debug plane on and show_objects off apply as they do in sdfr_query_distance"""
+    scene = "labyrinth"
+    _setup(renderer, scene, qu.frame(scene, 0.75, W, H))
+    g, depth = _scene_grid(scene, 19, 13, (30, 14))
+    p = su.params(MIN_STEP, depth, 0.0, MAX_STEPS)
+    plain = mu.measure(_distance(scene, qu.frame(scene, 0.75, W, H)), g, p)[0]
+    for variables in ({"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}, {"show_objects": 0.0, "debug_ny": 1.0}):
+        of = qu.frame(scene, 0.75, W, H, variables)
+        for name, v in variables.items():
+            assert renderer.setValue(name, v)
+        try:
+            want, want_col = mu.measure(_distance(scene, of), g, p)
+            assert (mu.bits64(want["moments"]).tolist(), want["steps"]) != (mu.bits64(plain["moments"]).tolist(), plain["steps"])  # the plane is there
+            _check(renderer, (scene, variables), g, want, want_col, min_step=MIN_STEP, t_max=depth, max_steps=MAX_STEPS)
+        finally:
+            renderer.resetVariables()
+
+
+# ---- the protocol ----------------------------------------------------------------------------------------------------------------
+def test_columns_off_alignment_and_out_of_steps(renderer):
+    import torch
+    import sdf_playground_amd as sp
+
+    scene = "cube_sea"
+    _setup(renderer, scene, qu.frame(scene, CASES[scene][0], W, H))
+    # max_steps so small that some columns run out of steps and some do not
+    g, depth, want, want_col = expected(scene, 72, 65, 24)
+    n = 72 * 65
+    assert 100 < want["columns_out_of_steps"] < n - 100 and want["columns_hit"] > 100
+    _check(renderer, "out of steps", g, want, want_col, min_step=MIN_STEP, t_max=depth, max_steps=24)
+    # a device array 4 bytes off 8-byte alignment is written by the word path: the same words, nothing in front of them or after them
+    words = torch.full((n * 10 + 2,), 0x77777777, dtype=torch.int32, device="cuda")
+    assert words.data_ptr() % 8 == 0
+    par, out, grid = sp.SpanParams(depth, MIN_STEP, 0.0, 24, 0), sp.MeasureResult(), _grid(g)
+    rc = sp.load_library().sdfr_measure(renderer._h, ctypes.byref(grid), ctypes.byref(par), ctypes.byref(out), ctypes.c_void_p(words.data_ptr() + 4), 0)
+    assert rc == 0
+    renderer.sync()
+    assert int(words[0]) == 0x77777777 and int(words[-1]) == 0x77777777
+    mu.assert_same_result("off alignment", out, want)
+    mu.assert_same_columns("off alignment", words[1:-1].cpu().numpy().view(mu.COLUMN_DTYPE), want_col)
+    # two calls: the same bits
+    a, b = renderer.measure(grid, MIN_STEP, t_max=depth, max_steps=24), renderer.measure(grid, MIN_STEP, t_max=depth, max_steps=24)
+    assert bytes(a) == bytes(b) == bytes(out)
+
+
+def test_measure_leaves_rendering_alone(renderer):
+    import torch
+
+    scene = "labyrinth"
+    of = qu.frame(scene, CASES[scene][0], W, H)
+    _setup(renderer, scene, of)
+    g, depth, want, want_col = expected(scene, 9, 17)
+    kw = dict(min_step=MIN_STEP, t_max=depth, max_steps=MAX_STEPS)
+    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
+    s0, t0 = _stats(renderer), renderer.getTimings()
+    _check(renderer, "after a render", g, want, want_col, **kw)
+    assert _stats(renderer) == s0 and renderer.getTimings() == t0
+    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
+    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    # two frames in flight: the call runs on the lane of the frame submitted last
+    renderer.setFramesInFlight(2)
+    try:
+        imgs = [torch.empty((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+        for k in range(4):
+            renderer.render(None, W, H, out=imgs[k % 2])
+            res, cols = renderer.measure(_grid(g), columns=True, device=(k % 2 == 0), **kw)
+            renderer.sync()
+            mu.assert_same_result(("in flight", k), res, want)
+            mu.assert_same_columns(("in flight", k), _columns(cols), want_col)
+            assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
+            assert _stats(renderer) == s0
+    finally:
+        renderer.setFramesInFlight(1)
+
+
+def test_arguments(renderer):
+    import sdf_playground_amd as sp
+
+    L = sp.load_library()
+    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    h = renderer._h
+    INVALID, NO_SCENE = -1, -4
+    NULL_POINTER, BAD_ON_HOST, BAD_GRID, BAD_PARAMS = "null pointer", "on_host must be 0 or 1", "bad measure grid", "bad span parameters"
+    nan, inf = float("nan"), float("inf")
+
+    def call(handle=h, grid=True, params=True, out=True, columns=True, on_host=1, nu=9, nv=5, origin=(-1.85, 2.5, -1.05), du=(CELL, 0, 0), dv=(0, 0, CELL), dw=(0, -1, 0),
+             t_max=1.0, min_step=0.05, iso=0.0, max_steps=64, max_spans=0):
+        g = _grid(mu.grid(origin, du, dv, dw, nu, nv))
+        par = sp.SpanParams(t_max, min_step, iso, max_steps, max_spans)
+        res = (ctypes.c_uint32 * 40)(*([0x77777777] * 40))
+        cols = np.full((45, 10), 0x77777777, np.uint32)
+        rc = L.sdfr_measure(handle, ctypes.byref(g) if grid else None, ctypes.byref(par) if params else None, ctypes.cast(res, ctypes.POINTER(sp.MeasureResult)) if out else None,
+                            cols.ctypes.data_as(ctypes.c_void_p) if columns else None, on_host)
+        if rc != 0:  # nothing is written on error
+            assert all(w == 0x77777777 for w in res) and (cols == 0x77777777).all()
+        else:
+            assert not (cols == 0x77777777).all(axis=1).any() if columns else (cols == 0x77777777).all()
+        return rc, L.sdfr_last_error(handle).decode() if handle and rc else ""
+
+    assert call() == (0, "") and call(columns=False) == (0, "")
+    assert call(grid=False) == (INVALID, NULL_POINTER) and call(params=False) == (INVALID, NULL_POINTER) and call(out=False) == (INVALID, NULL_POINTER)
+    assert call(on_host=2) == (INVALID, BAD_ON_HOST) and call(on_host=-1) == (INVALID, BAD_ON_HOST)
+    for bad in (dict(nu=0), dict(nv=-1), dict(nu=8193), dict(nu=8192, nv=2049), dict(origin=(nan, 0, 0)), dict(du=(0, 0, 0)), dict(dv=(0, inf, 0)), dict(dw=(0, 0, 0)),
+                dict(dw=(-0.0, 0.0, 0.0)), dict(dw=(0, nan, 0))):
+        assert call(**bad) == (INVALID, BAD_GRID), bad
+    for bad in (dict(t_max=nan), dict(t_max=-1.0), dict(t_max=inf), dict(min_step=0.0), dict(min_step=nan), dict(iso=inf), dict(max_steps=0), dict(max_steps=(1 << 20) + 1),
+                dict(max_spans=-1), dict(max_spans=1), dict(max_spans=64)):
+        assert call(**bad) == (INVALID, BAD_PARAMS), bad
+    # two faults at once: the text of the one checked first
+    assert call(out=False, on_host=2) == (INVALID, NULL_POINTER)
+    assert call(on_host=2, nu=0) == (INVALID, BAD_ON_HOST)
+    assert call(nu=0, max_spans=2) == (INVALID, BAD_GRID)
+    assert call(handle=None)[0] == INVALID
+    fresh = sp.SDFRenderer(0)
+    try:
+        assert call(handle=fresh._h)[0] == NO_SCENE
+        assert call(handle=fresh._h, max_spans=2) == (INVALID, BAD_PARAMS) and call(handle=fresh._h, nu=0) == (INVALID, BAD_GRID)  # the arguments come first
+    finally:
+        fresh.close()
+
+
+def test_cli_measure(renderer, capsys):
+    """the command line end to end: one JSON object, with a warning where the box cuts the solid"""
+    from sdf_playground_amd import cli
+
+    box = ["--measure-box", "-1.85", "0.1", "-1.05", "1.75", "2.5", "2.2", "--measure-cell", "0.05", "--measure-axis", "y", "--measure-density", "3"]
+    capsys.readouterr()
+    assert cli.main(["--scene", "fast_sphere", "--measure"] + box) == 0
+    report = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert report["columns"] == [65, 72] and report["columns_hit"] > 100 and report["volume"] > 0 and report["mass"] == 3 * report["volume"]
+    assert len(report["centroid"]) == 3 and len(report["inertia"]) == 6 and all(report["inertia"][k] > 0 for k in range(3))
+    assert ("warning" in report) == (report["columns_open"] > 0 or report["columns_out_of_steps"] > 0)
+    assert cli.main(["--scene", "fast_sphere", "--measure", "--measure-box", "-1.85", "-0.3", "-1.05", "1.75", "2.5", "2.2", "--measure-cell", "0.1", "--measure-axis", "y"]) == 0
+    report = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert report["columns_open"] > 0 and "truncated" in report["warning"]  # the ground leaves the box
