@@ -140,13 +140,12 @@ static int sync_lanes(sdfr_renderer *r)
 	if (r->frames_in_flight == 2) SDFR_HIP(hipStreamSynchronize(r->other.stream));
 	return SDFR_OK;
 }
-// back to one frame in flight: the current lane keeps its workspace and runs on the caller's stream again
+// back to one frame in flight: the current lane keeps its workspace and runs on the caller's stream again.  The handle's two own
+// streams stay (own_streams): events that outlive this -- the lane's ev_begin / ev_end, ev_mesh -- were last recorded on them
 static void release_second_lane(sdfr_renderer *r)
 {
 	if (r->frames_in_flight != 2) return;
 	(void)sync_lanes(r);
-	(void)hipStreamDestroy(r->lane.stream);
-	(void)hipStreamDestroy(r->other.stream);
 	release_lane(r->other);
 	r->lane.stream = r->user_stream;
 	r->frames_in_flight = 1;
@@ -206,19 +205,18 @@ int sdfr_set_frames_in_flight(sdfr_renderer *r, int n)
 			return SDFR_OK;
 		}
 		SDFR_HIP(hipStreamSynchronize(r->lane.stream));
-		hipStream_t stream = nullptr; // the current lane's from now on: it keeps its workspace and the row order it has learned
 		sdfr_renderer::Lane second;
-		hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-		if (e == hipSuccess) e = hipStreamCreateWithFlags(&second.stream, hipStreamNonBlocking);
+		hipError_t e = hipSuccess;
+		for (hipStream_t &s : r->own_streams)
+			if (!s && e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
 		if (e == hipSuccess) e = create_lane(second);
 		if (e != hipSuccess)
 		{
-			if (stream) (void)hipStreamDestroy(stream);
-			if (second.stream) (void)hipStreamDestroy(second.stream);
 			release_lane(second);
 			return hip_fail(r, e, "sdfr_set_frames_in_flight");
 		}
-		r->lane.stream = stream;
+		second.stream = r->own_streams[1];
+		r->lane.stream = r->own_streams[0]; // the current lane's from now on: it keeps its workspace and the row order it has learned
 		r->lane.out_lo = r->lane.out_hi = nullptr;
 		r->lane.pst_lo = r->lane.pst_hi = nullptr;
 		r->other = second;
@@ -284,7 +282,7 @@ void sdfr_destroy(sdfr_renderer *r)
 	(void)hipStreamSynchronize(r->lane.stream);
 	if (r->comm_stream) (void)hipStreamSynchronize(r->comm_stream);
 	comm_forget_renderer(r);
-	release_second_lane(r); // waits for it, frees its workspace, counters, events and the two internal streams
+	release_second_lane(r); // waits for it, frees its workspace, counters and events
 	release_lane(r->lane);
 	jit_unload(r->jit);
 	for (sdfr_device_buffer *b : {&r->stage, &r->pstat, &r->query, &r->mesh, &r->wire, &r->post_flags, &r->aa_color, &r->aa_stats, &r->aa_totals}) b->release();
@@ -304,6 +302,8 @@ void sdfr_destroy(sdfr_renderer *r)
 		(void)hipEventDestroy(r->ev_march[i]);
 		(void)hipEventDestroy(r->ev_shade[i]);
 	}
+	for (hipStream_t s : r->own_streams) // after every event that was recorded on them
+		if (s) (void)hipStreamDestroy(s);
 	delete r;
 }
 

@@ -95,6 +95,9 @@ struct sdfr_renderer
 	Lane lane, other;
 	int frames_in_flight = 1;
 	hipStream_t user_stream = nullptr; // what sdfr_set_stream gave (in use while frames_in_flight == 1)
+	// the two streams of two frames in flight, made at the first switch to it and kept until the handle goes: the lanes' and the
+	// extraction's events were last recorded on them, and the runtime looks at an event's last stream whenever the event is waited for
+	hipStream_t own_streams[2] = {nullptr, nullptr};
 
 	int device = 0;
 	int scene = -1; // index of an ahead-of-time scene, or SDFR_SCENE_COUNT: `jit` holds a scene compiled at run time

@@ -1,20 +1,25 @@
 """Seeded sequences of MIXED calls on ONE renderer handle: renders, anti-aliased frames, post-processing, every query family, mesh
-extraction and atlas calls, interleaved.  tests/handle_sequences.py drives what a handle carries from frame to frame; this module
-drives the state the handle has gained since: the staging of host queries (`query`, cut three ways and released past 64 MiB), the
-extraction workspace (`mesh`, reused across lanes behind an event, released past 64 MiB), the supersampling buffers, and the
-per-handle query kernels in their DBG and non-DBG variants, on built-in scenes and on one compiled at run time.
+extraction (plain and sharp), atlas calls, surveys and fits, slices, span queries and measures, interleaved.
+tests/handle_sequences.py drives what a handle carries from frame to frame; this module drives the state the handle has gained
+since: the staging of host queries (`query`, cut per call and released past 64 MiB), the extraction workspace (`mesh`, cut two to
+five ways by the mesh, the survey, the slices and the measure, reused across lanes behind an event, released past 64 MiB), the
+supersampling buffers, and the per-handle query kernels in their DBG and non-DBG variants, on built-in scenes and on one compiled
+at run time.
 
 No torch, no GPU: the CPU tier (tests/test_handle_mixed_cpu.py) proves what the committed seeds cover, the GPU tier
 (tests/test_gpu_handle_mixed.py) runs them.  A step is one call on the handle, with the settings changed just before it (`set`) and
 the whole state a fresh handle needs to answer it (`state`).  The inputs of a call are drawn from the step's own seeded generator
-(rays(), points(), normals(), pixel_list(), lattice in the step)."""
+(rays(), points(), normals(), pixel_list(), the lattice, slice stack or measure grid in the step)."""
 import math
 import random
 
 import handle_sequences as hs
 
-FAMILIES = ("render", "aa", "post", "points", "rays", "pick", "surfaces", "occlusion", "lighting", "mesh", "atlas", "failed")
-HOST_AND_DEVICE = tuple(f for f in FAMILIES if f not in ("post", "failed"))  # sdfr_postprocess takes device tensors only
+FAMILIES = ("render", "aa", "post", "points", "rays", "pick", "surfaces", "occlusion", "lighting", "mesh", "atlas", "survey", "slices", "spans", "measure",
+            "failed")
+# sdfr_postprocess takes device tensors only; sdfr_mesh_survey and sdfr_mesh_fit answer into one host record and have no on_host
+HOST_AND_DEVICE = tuple(f for f in FAMILIES if f not in ("post", "survey", "failed"))
+DEVICE_ONLY = ("post", "survey")
 # (failed, failed) cannot be: a failed call always sits between two valid calls
 PAIRS = tuple((a, b) for a in FAMILIES for b in FAMILIES if (a, b) != ("failed", "failed"))
 
@@ -27,29 +32,53 @@ CELLS = (0.09, 0.13, 0.17)
 TILES = (4, 8, 16)
 MAX_ATLAS_WIDTH = 256
 LAYER_SETS = (("albedo",), ("normal",), ("lit",), ("albedo", "normal"), ("albedo", "lit"), ("normal", "lit"), ("albedo", "normal", "lit"))
-MESH_FORMS = (None, None, "surfaces", "occlusion", "lighting", "atlas_occlusion")
+MESH_FORMS = (None, None, "surfaces", "occlusion", "lighting", "atlas_occlusion", "sharp", "sharp_surfaces")
+SHARP_FORMS = ("sharp", "sharp_surfaces")         # sdfr_mesh_extract_sharp; the second feeds its vertices to meshSurfaces
+AXES = ("x", "y", "z")
+BANDS = (0.0, 0.5, 2.0)                           # surveyMesh: the band in cells
+FIT_LEVELS, FIT_MARGINS, MAX_FIT = (0, 2, 3), (0, 1), 40  # fitMesh: a search grid of at most MAX_FIT (<= 64) cells per axis
+MAX_SLICE_LAYERS = 8
+MAX_SPANS = (0, 1, 3, 64)
+SPAN_CALLS = ("querySpans", "pickSpans", "pickSpansFrame", "meshSpans")
+# (min_step, t_max, max_steps) of the span calls.  "finish": every ray reaches t_max (t_max / min_step + 1 <= max_steps); "short": a small
+# min_step and 32 steps, so that rays near a surface run out of steps.  Rays and pixels march a quarter of limits.range, a mesh's rays
+# (unit normals, from 0.2 outside the vertex) two units
+SPAN_PARAMS = {"finish": dict(rays=(100.0 / 256.0, 25.0, 256), mesh=(0.05, 2.0, 256)), "short": dict(rays=(0.02, 25.0, 32), mesh=(0.01, 2.0, 32))}
+MEASURE_COLUMNS = (1, 7, 8, 9, 24)
+MEASURE_BIG = 72                                  # 72 x 72 columns are 81 tiles: more than a run of 64, so that k_measure_reduce runs a pass
+# (min_step, max_steps) of a measure; dw spans the box, so t_max = 1.  "short": columns near a surface run out of steps.  iso is 0 but for
+# the measure of the workspace_cuts block
+MEASURE_PARAMS = {"finish": (1.0 / 64.0, 128), "short": (1.0 / 512.0, 48)}
 SPLITS = hs.SPLITS
 DEBUG_VARS = {"debug_nx": 0.3, "debug_ny": 1.0}  # + the point debug_vars() puts the plane through: the driver's debug plane
 KEEP = 64 << 20                                   # k_query_stage_keep (sdfr_api.cpp): what a handle keeps of `query` and of `mesh`
 STAGE_ALIGN = 256                                 # SDFR_STAGE_ALIGN (sdfr_stage.h)
 MESH_BLOCK = 256                                  # SDFR_MESH_BLOCK (sdfr_mesh.h)
 HIT_BYTES, SURFACE_BYTES, OCCLUSION_BYTES, LIGHTING_BYTES, LIGHTS_BYTES = 48, 128, 16, 64, 8 * 80
+SPAN_SUMMARY_BYTES, SPAN_BYTES, MEASURE_COLUMN_BYTES = 32, 8, 40
+MESH_SURVEY_WORK_BYTES = 4096 * (1 + 10 + 12)     # sdfr_mesh_survey.h
+MEASURE_TALLY_BYTES = 128 * (2 + 13 * 16)         # sdfr_query_args.h
 
 # argument errors refused on the host before anything is launched: (kind, sdfr_last_error); all SDFR_ERR_INVALID_ARGUMENT but the capacities
 # smaller than the counts, which is SDFR_OK with the counts and nothing written
 FAILURES = (("negative_n", "bad item count"), ("null_pointer", "null pointer"), ("bad_on_host", "on_host must be 0 or 1"),
             ("mesh_negative_capacity", "negative capacity"), ("mesh_small_capacity", None), ("aa_factor_3", "factor must be 1, 2, 4 or 8"),
-            ("aa_bad_format", "bad format"), ("atlas_bad_layout", "bad atlas"))
+            ("aa_bad_format", "bad format"), ("atlas_bad_layout", "bad atlas"), ("slice_negative_capacity", "negative capacity"),
+            ("slice_small_capacity", None), ("span_max_spans_65", "bad span parameters"), ("measure_nu_0", "bad measure grid"),
+            ("survey_bad_band", "band must be finite and >= 0"), ("fit_bad_margin", "margin must be 0..8"))
 FAILURE_KINDS = tuple(k for k, _ in FAILURES)
-FAILURE_ENTRIES = ("points", "rays", "pick", "surfaces", "occlusion", "lighting")  # whose entry a query's argument error goes through
+SHARED_KINDS = FAILURE_KINDS[:3]  # the argument errors every query entry has
+SPAN_ENTRIES = ("ray_spans", "pick_spans", "mesh_spans")
+FAILURE_ENTRIES = ("points", "rays", "pick", "surfaces", "occlusion", "lighting") + SPAN_ENTRIES  # whose entry a shared kind goes through
 
-BLOCKS = ("staging", "lanes", "large_mesh", "aa_in_flight", "scene_change")
+BLOCKS = ("staging", "lanes", "large_mesh", "aa_in_flight", "scene_change", "workspace_cuts", "large_new")
 STRETCH = 10  # free steps on the run-time scene, inside the scene_change block: one entry per seed (every entry compiles the scene again)
-BLOCK_STEPS = {"staging": 4, "lanes": 4, "large_mesh": 2, "aa_in_flight": 6, "scene_change": 4 + STRETCH}
+BLOCK_STEPS = {"staging": 4, "lanes": 4, "large_mesh": 2, "aa_in_flight": 6, "scene_change": 4 + STRETCH, "workspace_cuts": 6, "large_new": 5}
 BIG_FRAME = (384, 240)  # pickLighting(None, hits, lights) of it on the host: past the keep (staging_bytes)
+BIG_SPAN_FRAME = (448, 280)  # pickSpans(None, max_spans=64) of it on the host: past the keep; 440 x 280 is not
 
-SEEDS = (24, 92, 16, 62)  # the committed seeds (what they cover: tests/test_handle_mixed_cpu.py)
-STEPS = 64
+SEEDS = (287, 15, 30, 52, 64, 1, 89, 7)  # the committed seeds (what they cover: tests/test_handle_mixed_cpu.py)
+STEPS = 72
 
 # the scene variables the sequences move (hs.SCENE_VARS, but the lense stays off the camera orbit's centre: at zpos 0 nothing of the scene
 # is left around it, and the lattices there would be empty)
@@ -90,31 +119,97 @@ def staging_bytes(step):
         return stage_total([n * 12, n * 12, n * OCCLUSION_BYTES, 0, 0, 0])
     if call == "hitOcclusion":
         return stage_total([n * HIT_BYTES, 0, n * OCCLUSION_BYTES, 0, 0, 0])
+    if call in ("querySpans", "pickSpans", "meshSpans"):  # plan_spans (sdfr_span_plan.h): the two inputs, the summaries, the spans
+        ins = [0, 0] if p.get("frame") else ([n * 8, 0] if call == "pickSpans" else [n * 12, n * 12])
+        return stage_total(ins + [n * SPAN_SUMMARY_BYTES, n * p["max_spans"] * SPAN_BYTES])
+    if call == "measure":  # plan_measure (sdfr_measure_plan.h): the columns alone
+        g = p["grid"]
+        return stage_total([g["nu"] * g["nv"] * MEASURE_COLUMN_BYTES if p["columns"] else 0])
     return None
 
 
-def workspace_bytes(dims):
-    """bytes of `mesh` an extraction over `dims` cells needs: the four pieces of plan_mesh (sdfr_mesh_plan.h)"""
-    def scan_sum_words(n):  # mesh_scan_sum_words (sdfr_mesh.h)
-        words = 0
-        while n > MESH_BLOCK:
-            n = (n + MESH_BLOCK - 1) // MESH_BLOCK
-            words += n
-        return words
+def _scan_sum_words(n):
+    """mesh_scan_sum_words (sdfr_mesh.h)"""
+    words = 0
+    while n > MESH_BLOCK:
+        n = (n + MESH_BLOCK - 1) // MESH_BLOCK
+        words += n
+    return words
 
+
+def workspace_bytes(dims):
+    """bytes of `mesh` an extraction over `dims` cells needs, plain or sharp: the four pieces of plan_mesh (sdfr_mesh_plan.h)"""
     points = (dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1)
     cells = dims[0] * dims[1] * dims[2]
-    return stage_total([points * 4, (cells + 1) * 4, (points + 1) * 4, (scan_sum_words(cells + 1) + scan_sum_words(points + 1)) * 4])
+    return stage_total([points * 4, (cells + 1) * 4, (points + 1) * 4, (_scan_sum_words(cells + 1) + _scan_sum_words(points + 1)) * 4])
 
 
-def _big_lattice():
+def survey_workspace_bytes(dims):
+    """... a survey of `dims` cells needs: the two pieces of plan_mesh_survey (sdfr_mesh_plan.h)"""
+    return stage_total([(dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1) * 4, MESH_SURVEY_WORK_BYTES])
+
+
+def slice_workspace_bytes(dims, layers):
+    """... a slice extraction of `layers` lattices of `dims` cells needs: the five pieces of plan_slice (sdfr_slice_plan.h)"""
+    points = (dims[0] + 1) * (dims[1] + 1) * layers
+    return stage_total([points * 4, (points + 1) * 4, (points + 1) * 4, 2 * _scan_sum_words(points + 1) * 4, 2 * (layers + 1) * 4])
+
+
+def measure_workspace_bytes(nu, nv):
+    """... a measure of nu x nv columns needs: the three pieces of plan_measure (sdfr_measure_plan.h)"""
+    tiles = ((nu + 7) // 8) * ((nv + 7) // 8)
+    return stage_total([tiles * 80, (tiles + 63) // 64 * 80, MEASURE_TALLY_BYTES])
+
+
+def _smallest(past):
     n = 1
-    while workspace_bytes((n, n, n)) <= KEEP:
+    while not past(n):
         n += 1
-    return (n, n, n)
+    return n
 
 
-BIG_LATTICE = _big_lattice()  # the smallest cube of cells whose workspace is past the keep
+BIG_LATTICE = (_smallest(lambda n: workspace_bytes((n, n, n)) > KEEP),) * 3          # the smallest cube of cells whose workspace is past the keep
+BIG_SURVEY = (_smallest(lambda n: survey_workspace_bytes((n, n, n)) > KEEP),) * 3    # ... whose survey's workspace is
+BIG_SLICE_LAYERS = 8
+BIG_SLICE = (_smallest(lambda n: slice_workspace_bytes((n, n), BIG_SLICE_LAYERS) > KEEP),) * 2  # the smallest square stack of 8 layers likewise
+
+
+def slice_grid(lat, axis, layers, angle=0.0):
+    """the slice stack of a lattice's box: `layers` planes across `axis`, each in the middle of its slab of the box, cells of the
+    lattice's size along the two other axes (u, v, w: the cyclic order that ends in the axis); angle: du and dv turned about dw, the
+    layer's middle staying where it is"""
+    w = AXES.index(axis)
+    u, v = (w + 1) % 3, (w + 2) % 3
+    cell, dims = lat["cell"], lat["dims"]
+    depth = dims[w] * cell / layers
+    c, s = math.cos(angle), math.sin(angle)
+    du, dv, dw = [0.0] * 3, [0.0] * 3, [0.0] * 3
+    du[u], du[v], dv[u], dv[v], dw[w] = cell * c, cell * s, -cell * s, cell * c, depth
+    mid = list(lat["origin"])
+    mid[u], mid[v], mid[w] = mid[u] + 0.5 * dims[u] * cell, mid[v] + 0.5 * dims[v] * cell, mid[w] + 0.5 * depth
+    origin = [mid[a] - 0.5 * dims[u] * du[a] - 0.5 * dims[v] * dv[a] for a in range(3)]
+    r = lambda x: tuple(round(t, 5) for t in x)  # noqa: E731
+    return dict(origin=r(origin), du=r(du), dv=r(dv), dw=r(dw), dims=(dims[u], dims[v]), layers=layers)
+
+
+def measure_grid(lat, axis, nu, nv, tilt=0.0):
+    """nu x nv columns over a lattice's box, through the middles of their cells of its lower face across `axis`; dw spans the box's
+    depth (t_max = 1); tilt: dw leans towards u by that share of the depth"""
+    w = AXES.index(axis)
+    u, v = (w + 1) % 3, (w + 2) % 3
+    cell, dims = lat["cell"], lat["dims"]
+    du, dv, dw = [0.0] * 3, [0.0] * 3, [0.0] * 3
+    du[u], dv[v], dw[w] = dims[u] * cell / nu, dims[v] * cell / nv, dims[w] * cell
+    dw[u] = tilt * dw[w]
+    origin = list(lat["origin"])
+    origin[u], origin[v] = origin[u] + 0.5 * du[u] - 0.5 * dw[u], origin[v] + 0.5 * dv[v]
+    r = lambda x: tuple(round(t, 5) for t in x)  # noqa: E731
+    return dict(origin=r(origin), du=r(du), dv=r(dv), dw=r(dw), nu=nu, nv=nv)
+
+
+def span_params(step):
+    """(min_step, t_max, max_steps) of a span step"""
+    return SPAN_PARAMS[step["march"]]["mesh" if step["call"] == "meshSpans" else "rays"]
 
 
 def eye_and_front(scene, t):
@@ -179,6 +274,26 @@ def debug_vars(scene):
     return dict(DEBUG_VARS, debug_x=c[0], debug_y=round(c[1] - 0.1, 3), debug_z=c[2])
 
 
+def oracle_frame(oracle, st, w, h):
+    """the oracle's frame (oracle: the pyoracle module) of a step's state `st` for a w x h image: the orbit's camera, the limits, the
+    scene variables and the debug plane"""
+    import numpy as np
+
+    fovy = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
+    kind, eye, target = hs.camera(st["scene"], st["t"])
+    basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, target, fovy, np.float32(w) / np.float32(h))
+    f = oracle.default_frame(st["scene"], w, h, basis=basis, stime=st["stime"])
+    for name, v in dict(hs.DEFAULT_LIMITS, **hs.LIMITS[st["limits"]]).items():
+        setattr(f, name, v)
+    slots = {row[0]: row[6] for row in oracle.var_table(st["scene"])}
+    for name, v in list(st["vars"].items()) + (list(debug_vars(st["scene"]).items()) if st["debug"] else []):
+        if slots[name] >= 0:
+            f.scene_var[slots[name]] = v
+        else:
+            setattr(f, name, v)
+    return f
+
+
 def share_of(pair):
     """which of the committed seeds works towards a pair of families first: a diagonal, so that no seed has all the pairs of one family"""
     return (FAMILIES.index(pair[0]) + FAMILIES.index(pair[1])) % len(SEEDS)
@@ -202,6 +317,7 @@ class _Gen:
         self.want_pairs = {p for p in PAIRS if share_of(p) == self.slot}
         self.want_runtime = {f for k, f in enumerate(FAMILIES) if k % len(SEEDS) == self.slot}
         self.want_forms = {(f, host, fif) for f in HOST_AND_DEVICE for host in (False, True) for fif in (1, 2)}
+        self.want_forms |= {(f, False, fif) for f in DEVICE_ONLY for fif in (1, 2)}
         self.want_debug = set(FAMILIES)
         self.used = {}
         self.last_frame = None   # index of the last render / aa step: what post processes
@@ -295,6 +411,8 @@ class _Gen:
             return "render"
         prev = self.steps[-1]["family"]
         allowed = self.allowed(i)
+        if prev == "failed" and self.steps[-1]["fail"].startswith("mesh_") and self.steps[-2]["family"] in FAILURE_ENTRIES[:6] and "render" in allowed:
+            return "render"  # a failed mesh call between a query and a render: one of the interleavings the sequences are there for
         if self.state["scene"] == hs.RUNTIME_SCENE:
             duty = [f for f in allowed if f in self.want_runtime]
             if duty:
@@ -313,9 +431,11 @@ class _Gen:
         """host or device, and one or two frames in flight: what is left to cover first"""
         rng, st = self.rng, self.state
         left = sorted((h, fif) for (f, h, fif) in self.want_forms if f == family)  # (sorted: a set's order is not the seed's)
-        if family == "post":
+        if family in DEVICE_ONLY:
             host = False
-            if rng.random() < 0.15:
+            if left and st["fif"] not in [fif for _h, fif in left]:
+                self.change("fif", left[0][1], changes)
+            elif not left and rng.random() < 0.15:
                 self.change("fif", 3 - st["fif"], changes)
         elif left:
             here = [h for h, fif in left if fif == st["fif"]]
@@ -349,7 +469,8 @@ class _Gen:
         st = self.state
         if len(self.steps) > 1:
             self.want_pairs.discard((self.steps[-2]["family"], family))
-        self.want_forms.discard((family, host, st["fif"]))
+        if family != "measure" or params.get("columns"):  # (without `columns` a measure answers into its host record alone)
+            self.want_forms.discard((family, host, st["fif"]))
         if st["debug"]:
             self.want_debug.discard(family)
         if st["scene"] == hs.RUNTIME_SCENE:
@@ -410,18 +531,53 @@ class _Gen:
             form = vary("mesh form", MESH_FORMS)
             lat = lattice(scene, rng, 14 if form == "atlas_occlusion" else MAX_LATTICE)
             more = dict(tile=vary("tile", TILES), width=vary("width", (64, 128, MAX_ATLAS_WIDTH)), layers=vary("layers", LAYER_SETS)) if form == "atlas_occlusion" else {}
-            return self.new(i, family, "extractMesh", changes, host, lattice=lat, normals=form is not None or vary("mesh normals", yes_no), form=form, **more)
+            return self.new(i, family, "extractMesh", changes, host, lattice=lat, normals=form not in (None, "sharp") or vary("mesh normals", yes_no), form=form, **more)
         if family == "atlas":
             src = self.last_mesh if self.last_mesh is not None and vary("atlas src", yes_no) else None
             lat = self.steps[src]["lattice"] if src is not None else lattice(scene, rng, 12)
             call = vary("atlas", ("atlasTexels", "bakeAtlas", "bakeAtlas"))
             return self.new(i, family, call, changes, host, src=src, lattice=lat, tile=vary("tile", TILES), width=vary("width", (64, 128, MAX_ATLAS_WIDTH)),
                             layers=vary("layers", LAYER_SETS) if call == "bakeAtlas" else (), reach=0.2)
+        if family == "survey":
+            if vary("survey", ("surveyMesh", "surveyMesh", "fitMesh")) == "fitMesh":
+                return self.new(i, family, "fitMesh", changes, False, lattice=lattice(scene, rng, MAX_FIT, 24), levels=vary("levels", FIT_LEVELS),
+                                margin=vary("margin", FIT_MARGINS))
+            lat = lattice(scene, rng)
+            return self.new(i, family, "surveyMesh", changes, False, lattice=lat, band=round(vary("band", BANDS) * lat["cell"], 4))
+        if family == "slices":
+            lat = lattice(scene, rng)
+            axis = vary("slice axis", AXES + ("oblique",))
+            stack = slice_grid(lat, rng.choice(AXES), vary("slice layers", tuple(range(1, MAX_SLICE_LAYERS + 1))), round(rng.uniform(0.2, 1.3), 3)) \
+                if axis == "oblique" else slice_grid(lat, axis, vary("slice layers", tuple(range(1, MAX_SLICE_LAYERS + 1))))
+            call = vary("slices", ("extractSlices", "extractSlices", "extractSlices", "countSlices"))
+            return self.new(i, family, call, changes, host, slices=stack, axis=axis, coords=vary("coords", yes_no), layer_vertices=vary("layer_vertices", yes_no),
+                            layer_segments=vary("layer_segments", yes_no))
+        if family == "spans":
+            call = vary("spans", SPAN_CALLS)
+            more = dict(max_spans=vary("max_spans", MAX_SPANS), march=vary("march", tuple(SPAN_PARAMS)))
+            if call == "pickSpansFrame":
+                w, h = vary("spans size", AA_SIZES)
+                return self.new(i, family, "pickSpans", changes, host, n=w * h, w=w, h=h, frame=True, **more)
+            if call == "meshSpans":
+                return self.new(i, family, call, changes, host, n=n, lattice=lattice(scene, rng), reach=0.2, **more)
+            return self.new(i, family, call, changes, host, n=n, w=w, h=h, frame=False, **more)
+        if family == "measure":
+            big = vary("measure big", (False, False, False, True))
+            nu, nv = (MEASURE_BIG, MEASURE_BIG) if big else (vary("nu", MEASURE_COLUMNS), vary("nv", MEASURE_COLUMNS))
+            axis = vary("measure axis", AXES + ("tilted",))
+            grid = measure_grid(lattice(scene, rng), rng.choice(AXES), nu, nv, 0.3) if axis == "tilted" else measure_grid(lattice(scene, rng), axis, nu, nv)
+            return self.new(i, family, "measure", changes, host, grid=grid, axis=axis, columns=vary("columns", yes_no), march=vary("measure march", tuple(MEASURE_PARAMS)))
         assert family == "failed"
-        kind = FAILURE_KINDS[(self.slot + self.failed * len(SEEDS)) % len(FAILURE_KINDS)]
+        # the failed calls of all seeds are numbered slot, slot + seeds, ...: the kinds in turn, and a shared kind through the entries in turn,
+        # the span entries first
+        g = self.slot + self.failed * len(SEEDS)
+        kind = FAILURE_KINDS[g % len(FAILURE_KINDS)]
+        turn = SPAN_ENTRIES + FAILURE_ENTRIES[:-len(SPAN_ENTRIES)]
+        entry = turn[(g // len(FAILURE_KINDS) * len(SHARED_KINDS) + g % len(FAILURE_KINDS)) % len(turn)]
         self.failed += 1
-        return self.new(i, family, "failed", changes, rng.random() < 0.5, fail=kind, entry=vary("entry", FAILURE_ENTRIES), n=rng.choice(ITEMS[:5]),
-                        w=w, h=h, lattice=lattice(scene, rng, 8))
+        lat = lattice(scene, rng, 8)
+        return self.new(i, family, "failed", changes, rng.random() < 0.5, fail=kind, entry=entry, n=rng.choice(ITEMS[:5]), w=w, h=h, lattice=lat,
+                        slices=slice_grid(lat, "y", 4))
 
     # ---- the scripted blocks ---------------------------------------------------------------------------------------------------
     def block(self, i, name):
@@ -475,6 +631,44 @@ class _Gen:
             if k == 2:
                 return self.new(i, "aa", "renderAA", changes, False, name, w=w, h=h, factor=2, fmt=hs.RGBA32F, stats=True, image="B", defer=True)
             return self.new(i, "render", "render", changes, False, name, w=w, h=h, fmt=hs.RGBA32F, stats=True, image="AB"[k == 3], defer=k != 4)
+        if name == "workspace_cuts":
+            # `mesh` cut 5, 3, 2, 4 and 5 ways in one run, two frames in flight, every output in device form: a slice extraction at the
+            # largest free size (its emit enqueued), a frame (the lanes swap), a measure smaller than that workspace (it lands inside what
+            # the emit still reads) and a survey, both synchronous and read at once, a sharp extraction larger than all before (`mesh`
+            # grows behind the event), a smaller slice extraction (reuses it); the deferred answers are read after that one's sync
+            self.change("fif", 2, changes)
+            if k == 0:
+                stack = slice_grid(lattice(scene, rng, dims=(MAX_LATTICE,) * 3), rng.choice(AXES), MAX_SLICE_LAYERS)
+                return self.new(i, "slices", "extractSlices", changes, False, name, slices=stack, axis=None, coords=True, layer_vertices=True, layer_segments=True, defer=True)
+            if k == 1:
+                w, h = rng.choice(FRAME_SIZES[3:])
+                return self.new(i, "render", "render", changes, False, name, w=w, h=h, fmt=hs.RGBA32F, stats=True, defer=True)
+            if k == 2:
+                grid = measure_grid(lattice(scene, rng, dims=(12, 12, 12), cell=0.13), rng.choice(AXES), MEASURE_COLUMNS[-1], MEASURE_COLUMNS[-1])
+                return self.new(i, "measure", "measure", changes, False, name, grid=grid, axis=None, columns=True, march="finish", iso=0.01, alone=True)
+            if k == 3:
+                lat = lattice(scene, rng, dims=(9, 10, 11))
+                return self.new(i, "survey", "surveyMesh", changes, False, name, lattice=lat, band=round(0.5 * lat["cell"], 4), alone=True)
+            if k == 4:
+                return self.new(i, "mesh", "extractMesh", changes, False, name, lattice=lattice(scene, rng, dims=(24, 23, 22)), normals=True, form="sharp", defer=True)
+            stack = slice_grid(lattice(scene, rng, dims=(9, 7, 8)), "y", 3)
+            return self.new(i, "slices", "extractSlices", changes, False, name, slices=stack, axis=None, coords=True, layer_vertices=True, layer_segments=True)
+        if name == "large_new":
+            # the large calls of the survey, the slices and the spans, each followed by a small call that cuts the buffer again: a survey
+            # past the keep; a counting call of a stack past the keep, then a small measure; a host pickSpans of a whole frame whose staging
+            # is past the keep, then a small host measure with `columns`, which is staged in `query`
+            if k == 0:
+                lat = lattice(scene, rng, dims=BIG_SURVEY, cell=0.02)
+                return self.new(i, "survey", "surveyMesh", changes, False, name, lattice=lat, band=0.0)
+            if k == 1:
+                n = BIG_SLICE[0]
+                stack = slice_grid(dict(origin=tuple(round(c - 0.5 * n * 0.005 + 0.003, 4) for c in CENTRES[scene]), cell=0.005, dims=(n, n, n)), "y", BIG_SLICE_LAYERS)
+                return self.new(i, "slices", "countSlices", changes, rng.random() < 0.5, name, slices=stack, axis=None, coords=False, layer_vertices=True, layer_segments=True)
+            if k in (2, 4):
+                grid = measure_grid(lattice(scene, rng, dims=(12, 12, 12), cell=0.13), rng.choice(AXES), 9, 8)
+                return self.new(i, "measure", "measure", changes, k == 4 or rng.random() < 0.5, name, grid=grid, axis=None, columns=True, march="finish")
+            w, h = BIG_SPAN_FRAME
+            return self.new(i, "spans", "pickSpans", changes, True, name, n=w * h, w=w, h=h, frame=True, max_spans=MAX_SPANS[-1], march="short")
         assert name == "scene_change"
         # device work enqueued, then a scene change with no sync of the test's own: the answers are those of the scene of the call.  To
         # the run-time scene, STRETCH free steps on it, and from it again
@@ -491,6 +685,8 @@ class _Gen:
             self.settings(family, changes)
             return self.free_step(i, family, changes)
         if k == 2 + STRETCH:
+            if self.slot % 2:  # every other seed: a span kernel of the run-time scene's module is in flight when the scene goes
+                return self.new(i, "spans", "querySpans", changes, False, name, n=255, w=1, h=1, frame=False, max_spans=3, march="finish", defer=True)
             return self.new(i, "surfaces", "queryRaySurfaces", changes, False, name, n=255, w=1, h=1, frame=False, hits=True, defer=True)
         self.builtin(changes)
         return self.new(i, "points", "queryDistance", changes, True, name, n=64, normals=True)
@@ -524,8 +720,8 @@ def transitions(steps):
 
 
 def forms(steps):
-    """{(family, host, frames in flight)}"""
-    return {(s["family"], s["host"], s["state"]["fif"]) for s in steps if s["family"] != "failed"}
+    """{(family, host, frames in flight)}; a measure counts only with `columns`, the one array whose place on_host decides"""
+    return {(s["family"], s["host"], s["state"]["fif"]) for s in steps if s["family"] != "failed" and (s["family"] != "measure" or s["columns"])}
 
 
 def on_runtime_scene(steps):
@@ -547,6 +743,13 @@ def blocks(steps):
 
 def failure_kinds(steps):
     return {s["fail"] for s in steps if s["family"] == "failed"}
+
+
+def oracle_checkable(s):
+    """whether the GPU tier can hold a step's reference answer against the CPU oracle: a built-in scene (the oracle has no run-time
+    scene), and no counting call over a lattice of millions of points, which numpy would take too long for"""
+    large = s["call"] == "countMesh" or (s["block"] == "large_new" and s["call"] in ("surveyMesh", "countSlices"))
+    return s["family"] != "failed" and s["state"]["scene"] != hs.RUNTIME_SCENE and not large
 
 
 def runtime_entries(steps):

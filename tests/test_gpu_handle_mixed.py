@@ -1,15 +1,18 @@
 """GPU tier: one renderer handle through seeded sequences of MIXED calls (tests/handle_mixed_sequences.py): renders, anti-aliased
-frames, post-processing, every query family, mesh extraction and atlas calls, host and device form, one and two frames in flight,
-built-in scenes and one compiled at run time, the debug plane on and off, failed calls in between.
+frames, post-processing, every query family, mesh extraction (plain and sharp), atlas calls, surveys and fits, slices, span queries
+and measures, host and device form, one and two frames in flight, built-in scenes and one compiled at run time, the debug plane on
+and off, failed calls in between.
 
 Every step runs on ONE handle, through the C entry points, into buffers of the test's own: pre-filled with a sentinel no call
 produces and a guard tail of 256 bytes behind them.  After every step every output array equals, bit for bit, what a reference
 handle answers for the same state and inputs (one handle per scene, configured in full for every answer: one frame in flight, the
 default launch mode, host form); no sentinel is left in what the call owns, the guard tail and what the call does not own are
-untouched; and after a query, an extraction, an atlas call or a failed call sdfr_get_stats still reports the last frame.  With two
-frames in flight device answers are read after sdfr_sync, as include/sdfr.h tells a caller to, and nowhere else does the test
-synchronise the handle.  About one step in eight has its reference answer checked against the CPU oracle on a stride sample, every
-family at least once per seed."""
+untouched (the rows of a mesh or of a slice extraction past its counts are not the call's; the span slots past an item's spans are,
+and are zeros); and after a query, an extraction, an atlas call, a survey, a slice, span or measure call or a failed call
+sdfr_get_stats still reports the last frame.  With two frames in flight device answers are read after sdfr_sync, as include/sdfr.h
+tells a caller to, and nowhere else does the test synchronise the handle.  About one step in eight has its reference answer checked
+against the CPU oracle -- slices, measures, surveys, fits and sharp vertices whole, the rest on a stride sample --, every family at
+least once per seed."""
 import ctypes
 import math
 import time
@@ -19,7 +22,7 @@ import pytest
 
 import handle_mixed_sequences as hm
 import handle_sequences as hs
-from test_gpu_handle_state import FOVY, LAUNCH, NAN16, NAN32, SCHEDULE, _apply, _limits, _load_scene, _set_camera, _totals
+from test_gpu_handle_state import LAUNCH, NAN16, NAN32, SCHEDULE, _apply, _limits, _load_scene, _set_camera, _totals
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +33,10 @@ OK, ERR_INVALID_ARGUMENT, ERR_NO_SCENE = 0, -1, -4
 LAYER_BITS = {"albedo": 1, "normal": 2, "lit": 4}
 ENTRY_CALLS = {"points": dict(call="queryDistance", normals=True), "rays": dict(call="queryRays"), "pick": dict(call="pick"),
                "surfaces": dict(call="queryRaySurfaces", hits=True, frame=False), "occlusion": dict(call="queryOcclusion", bias=0.05, radius=1.0),
-               "lighting": dict(call="queryRayLighting", hits=True, lights=True, frame=False)}
+               "lighting": dict(call="queryRayLighting", hits=True, lights=True, frame=False),
+               "ray_spans": dict(call="querySpans", frame=False, max_spans=3, march="finish"), "pick_spans": dict(call="pickSpans", frame=False, max_spans=3, march="finish"),
+               "mesh_spans": dict(call="meshSpans", reach=0.2, max_spans=3, march="finish")}
+FIT_PADDING = 17  # the word of sdfr_mesh_fit_result between `grid` and `last`, which no field owns
 ORACLE_FAMILIES = tuple(f for f in hm.FAMILIES if f != "failed")
 
 
@@ -83,6 +89,10 @@ def _grid(lat):
     return sp.MeshGrid((ctypes.c_float * 3)(*lat["origin"]), lat["cell"], lat["dims"][0], lat["dims"][1], lat["dims"][2], 0.0)
 
 
+def _f3(v):
+    return (ctypes.c_float * 3)(*[float(x) for x in v])
+
+
 def _image_words(w, h, fmt):
     return (w * h * 2, HALVES) if fmt == hs.RGBA16F else (w * h * 4, NAN32)
 
@@ -99,6 +109,11 @@ class Call:
     def out(self, name, words, fill=NAN32, owned=None):
         self.bufs[name] = Buf(words, self.host, fill, owned)
         return self.bufs[name].ptr
+
+    def record(self, name, struct):
+        """a record the call answers into host memory, whatever on_host says"""
+        b = self.bufs[name] = Buf(ctypes.sizeof(struct) // 4, True)
+        return ctypes.cast(b.ptr, ctypes.POINTER(struct))
 
     def inp(self, a, null=False):
         if null:
@@ -166,10 +181,37 @@ class Call:
             return self.go(L.sdfr_query_occlusion, h, n, self.inp(inp["points"], null), self.inp(inp["normals"]), s["bias"], s["radius"], self.out("occlusion", 4 * abs(n)), oh)
         if call == "hitOcclusion":
             return self.go(L.sdfr_hit_occlusion, h, n, self.inp(inp["hits"]), s["bias"], s["radius"], self.out("occlusion", 4 * n), oh)
-        if call in ("countMesh", "extractMesh") and not s.get("form"):
+        if call in ("countMesh", "extractMesh") and s.get("form") in (None, "sharp"):
             return self.extract(r, sp, s, oh, ov)
         if call == "extractMesh":
             return self.composed(r, s, host)
+        if call == "surveyMesh":
+            grid = _grid(s["lattice"])
+            return self.go(L.sdfr_mesh_survey, h, ctypes.byref(grid), ov.get("band", s["band"]), self.record("survey", sp.MeshSurvey))
+        if call == "fitMesh":
+            grid = _grid(s["lattice"])
+            return self.go(L.sdfr_mesh_fit, h, ctypes.byref(grid), s["levels"], ov.get("margin", s["margin"]), self.record("fit", sp.MeshFit))
+        if call in ("extractSlices", "countSlices"):
+            return self.slices(r, sp, s, oh, ov)
+        if call in ("querySpans", "pickSpans", "meshSpans"):
+            min_step, t_max, max_steps = hm.span_params(s)
+            slots = ov.get("max_spans", s["max_spans"])
+            params = sp.SpanParams(t_max, min_step, 0.0, max_steps, slots)
+            summaries = None if null and call == "pickSpans" else self.out("summaries", 8 * abs(n))  # (a pick's pixels may be NULL: its summaries may not)
+            spans = self.out("spans", 2 * abs(n) * min(slots, 64)) if slots else None
+            if call == "querySpans":
+                return self.go(L.sdfr_query_ray_spans, h, n, self.inp(inp["origins"], null), self.inp(inp["dirs"]), ctypes.byref(params), summaries, spans, oh)
+            if call == "pickSpans":
+                return self.go(L.sdfr_pick_spans, h, w, hh, n, None if s["frame"] else self.inp(inp["pixels"]), ctypes.byref(params), summaries, spans, oh)
+            return self.go(L.sdfr_mesh_spans, h, n, self.inp(inp["points"], null), self.inp(inp["normals"]), s["reach"], ctypes.byref(params), summaries, spans, oh)
+        if call == "measure":
+            g = s["grid"]
+            grid = sp.MeasureGrid(_f3(g["origin"]), _f3(g["du"]), _f3(g["dv"]), _f3(g["dw"]), ov.get("nu", g["nu"]), g["nv"])
+            min_step, max_steps = hm.MEASURE_PARAMS[s["march"]]
+            params = sp.SpanParams(1.0, min_step, s.get("iso", 0.0), max_steps, 0)
+            result = self.record("result", sp.MeasureResult)
+            columns = self.out("columns", 10 * g["nu"] * g["nv"]) if s["columns"] else None
+            return self.go(L.sdfr_measure, h, ctypes.byref(grid), ctypes.byref(params), result, columns, oh)
         if call in ("atlasTexels", "bakeAtlas"):
             pos, nrm, idx = inp["mesh"]
             atlas = sp.atlasLayout(len(idx), s["tile"], s["width"])
@@ -189,32 +231,64 @@ class Call:
         raise KeyError(call)
 
     def extract(self, r, sp, s, oh, ov):
-        """sdfr_mesh_extract: the counting call, then (extractMesh) the filling call into arrays two rows larger than the counts"""
+        """sdfr_mesh_extract, or for the form "sharp" sdfr_mesh_extract_sharp: the counting call, then (extractMesh) the filling call into
+        arrays two rows larger than the counts"""
         L, h = r._L, r._h
+        mesh_extract = L.sdfr_mesh_extract_sharp if s.get("form") == "sharp" else L.sdfr_mesh_extract
         grid, counts = _grid(s["lattice"]), sp.MeshCounts()
         if "capacity" in ov:  # a failed call: arrays for ov["rows"] rows, capacities as given
             cv, ct = ov["capacity"]
             rows = ov["rows"]
-            rc = self.go(L.sdfr_mesh_extract, h, ctypes.byref(grid), cv, ct, self.out("positions", 3 * rows[0]), self.out("normals", 3 * rows[0]),
+            rc = self.go(mesh_extract, h, ctypes.byref(grid), cv, ct, self.out("positions", 3 * rows[0]), self.out("normals", 3 * rows[0]),
                                      self.out("indices", 3 * rows[1], ONES), ctypes.byref(counts), oh)
             self.extra["counts"] = (int(counts.vertices), int(counts.triangles))
             return rc
-        rc = self.go(L.sdfr_mesh_extract, h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), oh)
+        rc = self.go(mesh_extract, h, ctypes.byref(grid), 0, 0, None, None, None, ctypes.byref(counts), oh)
         v, t = int(counts.vertices), int(counts.triangles)
         self.extra["counts"] = (v, t)
         if rc != OK or s["call"] == "countMesh" or v == 0:
             return rc
         again = sp.MeshCounts()
-        rc = self.go(L.sdfr_mesh_extract, h, ctypes.byref(grid), v + 2, t + 2, self.out("positions", 3 * (v + 2), owned=3 * v),
+        rc = self.go(mesh_extract, h, ctypes.byref(grid), v + 2, t + 2, self.out("positions", 3 * (v + 2), owned=3 * v),
                                  self.out("normals", 3 * (v + 2), owned=3 * v) if s["normals"] else None,
                                  self.out("indices", 3 * (t + 2), ONES, owned=3 * t), ctypes.byref(again), oh)
         assert (again.vertices, again.triangles) == (v, t)
         return rc
 
+    def slices(self, r, sp, s, oh, ov):
+        """sdfr_slice_extract: the counting call, then (extractSlices) the filling call into arrays two rows larger than the counts; the
+        layer arrays, host memory whatever on_host says, are handed to both where the step has them"""
+        L, h, g = r._L, r._h, s["slices"]
+        grid, counts = sp.SliceGrid(_f3(g["origin"]), _f3(g["du"]), _f3(g["dv"]), _f3(g["dw"]), g["dims"][0], g["dims"][1], g["layers"], 0.0), sp.SliceCounts()
+        layers = lambda: [Buf(2 * (g["layers"] + 1), True) if s[k] else None for k in ("layer_vertices", "layer_segments")]  # noqa: E731
+        ptr = lambda b: b.ptr if b is not None else None  # noqa: E731
+        if "capacity" in ov:  # a failed call: arrays for ov["rows"] rows, capacities as given; the layer arrays are looked at by the caller
+            (cv, cs), rows = ov["capacity"], ov["rows"]
+            lv, ls = self.extra["layers"] = layers()
+            rc = self.go(L.sdfr_slice_extract, h, ctypes.byref(grid), cv, cs, self.out("positions", 3 * rows[0]), self.out("coords", 2 * rows[0]),
+                         self.out("segments", 2 * rows[1], ONES), ptr(lv), ptr(ls), ctypes.byref(counts), oh)
+            self.extra["counts"] = (int(counts.vertices), int(counts.segments))
+            return rc
+        lv, ls = layers()
+        self.bufs.update({k: b for k, b in (("layer_vertices", lv), ("layer_segments", ls)) if b is not None})
+        rc = self.go(L.sdfr_slice_extract, h, ctypes.byref(grid), 0, 0, None, None, None, ptr(lv), ptr(ls), ctypes.byref(counts), oh)
+        v, n = int(counts.vertices), int(counts.segments)
+        self.extra["counts"] = (v, n)
+        if rc != OK or s["call"] == "countSlices" or v == 0:
+            return rc
+        lv, ls = layers()  # the filling call writes them again
+        again = sp.SliceCounts()
+        rc = self.go(L.sdfr_slice_extract, h, ctypes.byref(grid), v + 2, n + 2, self.out("positions", 3 * (v + 2), owned=3 * v),
+                     self.out("coords", 2 * (v + 2), owned=2 * v) if s["coords"] else None, self.out("segments", 2 * (n + 2), ONES, owned=2 * n), ptr(lv), ptr(ls),
+                     ctypes.byref(again), oh)
+        assert (again.vertices, again.segments) == (v, n)
+        self.bufs.update({k: b for k, b in (("layer_vertices of the filling call", lv), ("layer_segments of the filling call", ls)) if b is not None})
+        return rc
+
     def composed(self, r, s, host):
-        """extractMesh(surfaces= / occlusion= / lighting= / atlas=): the wrapper's own composition, arrays of its own making"""
+        """extractMesh(surfaces= / occlusion= / lighting= / atlas=, sharp=): the wrapper's own composition, arrays of its own making"""
         lat, form = s["lattice"], s["form"]
-        kw = dict(surfaces=form == "surfaces", occlusion=form == "occlusion", lighting=form == "lighting")
+        kw = dict(surfaces=form in ("surfaces", "sharp_surfaces"), occlusion=form == "occlusion", lighting=form == "lighting", sharp=form == "sharp_surfaces")
         if form == "atlas_occlusion":
             kw["atlas"] = dict(tile=s["tile"], width=s["width"], layers=s["layers"], occlusion=True)
         got = r.extractMesh(lat["origin"], lat["cell"], lat["dims"], normals=True, device=not host, **kw)
@@ -224,11 +298,17 @@ class Call:
     def answers(self, r, what, synced=False):
         """{name: words} of everything the call answered, read as the contract allows; every buffer checked"""
         out = {k: b.read((what, k)) for k, b in self.bufs.items()}
+        if "fit" in out:
+            out["fit"] = np.delete(out["fit"], FIT_PADDING)
+        if "spans" in out:  # "the slots from min(spans, max_spans) up to max_spans are written as zeros -- all of them for an item without an answer"
+            stored = out["summaries"].reshape(-1, 8)[:, 1]
+            slots = out["spans"].reshape(len(stored), -1, 2)
+            assert not slots[np.arange(slots.shape[1])[None, :] >= stored[:, None]].any(), (what, "a span slot past the item's spans is not zero")
         if "counts" in self.extra:
             out["counts"] = np.array(self.extra["counts"], np.int64)
         if "composed" in self.extra:
             got = self.extra["composed"]
-            names = ["positions", "normals", "indices"] + ([self.s["form"]] if self.s["form"] != "atlas_occlusion" else [])
+            names = ["positions", "normals", "indices"] + ([self.s["form"].replace("sharp_", "")] if self.s["form"] != "atlas_occlusion" else [])
             for name, a in zip(names, got):
                 out[name] = _words(a)
             if self.s["form"] == "atlas_occlusion":
@@ -318,16 +398,16 @@ class References:
     def inputs(self, s, steps):
         """the input arrays of a step's call, from its own seeded generator, from an earlier step's answers or from a fresh extraction"""
         call, inp = s["call"], {}
-        if call in ("queryRays", "queryRaySurfaces", "queryRayLighting"):
+        if call in ("queryRays", "queryRaySurfaces", "queryRayLighting", "querySpans"):
             o, d = hm.rays(s)
             inp["origins"], inp["dirs"] = np.array(o, np.float32).reshape(-1, 3), np.array(d, np.float32).reshape(-1, 3)
-        if call in ("pick", "pickSurfaces", "pickLighting") and not s.get("frame"):
+        if call in ("pick", "pickSurfaces", "pickLighting", "pickSpans") and not s.get("frame"):
             inp["pixels"] = np.array(hm.pixel_list(s), np.int32).reshape(-1, 2)
         if call in ("queryDistance", "queryOcclusion"):
             inp["points"] = np.array(hm.points(s), np.float32).reshape(-1, 3)
         if call == "queryOcclusion":
             inp["normals"] = np.array(hm.normals(s), np.float32).reshape(-1, 3)
-        if call in ("meshSurfaces", "meshLighting"):
+        if call in ("meshSurfaces", "meshLighting", "meshSpans"):
             pos, nrm, _idx = self.mesh(s)
             k = np.arange(s["n"]) % len(pos)  # the step's n items: the vertices, again from the first if there are fewer
             inp["points"], inp["normals"] = pos[k].copy(), nrm[k].copy()
@@ -367,24 +447,17 @@ class References:
 
     # ---- the reference against the CPU oracle: a stride sample -----------------------------------------------------------------
     def frame(self, s, w, h):
-        oracle, st = self.oracle, s["state"]
-        kind, eye, target = hs.camera(st["scene"], st["t"])
-        basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, target, FOVY, np.float32(w) / np.float32(h))
-        f = oracle.default_frame(st["scene"], w, h, basis=basis, stime=st["stime"])
-        for name, v in _limits(st["limits"]).items():
-            setattr(f, name, v)
-        slots = {row[0]: row[6] for row in oracle.var_table(st["scene"])}
-        for name, v in list(st["vars"].items()) + (list(hm.debug_vars(st["scene"]).items()) if st["debug"] else []):
-            if slots[name] >= 0:
-                f.scene_var[slots[name]] = v
-            else:
-                setattr(f, name, v)
-        return f
+        return hm.oracle_frame(self.oracle, s["state"], w, h)
 
     def check_oracle(self, s, steps):
+        import sdf_playground_amd as sp
+
         import aa_util
         import atlas_util as au
+        import handle_mixed_oracle as ho
         import lighting_util as lu
+        import measure_util as mu_
+        import mesh_survey_util as msu
         import mesh_util as mu
         import occlusion_util as ou
         import query_util as qu
@@ -477,7 +550,18 @@ class References:
         elif call == "extractMesh":
             lat = s["lattice"]
             plain = self.pseudo(s, call="extractMesh", normals=True)
-            if s.get("form"):  # a composed call: its mesh is the plain extraction's
+            if s.get("form") in hm.SHARP_FORMS:
+                # the vertices by the definition fed with the oracle, the indices and counts of the plain extraction, the point query's normals
+                sharp = self.answer(dict(s, family=None, block=None, form="sharp", normals=True))
+                pos = ho.sharp(s, of)
+                assert tuple(sharp["counts"]) == tuple(plain["counts"]) and np.array_equal(sharp["indices"], plain["indices"]), what
+                qu.assert_same(str(what) + " sharp positions", sharp["positions"].reshape(-1, 3), pos.view(np.uint32))
+                k = np.arange(0, len(pos), max(1, -(-len(pos) // 256)))
+                qu.assert_same(str(what) + " sharp normals", sharp["normals"].reshape(-1, 3)[k], qu.oracle_points(scene, of, pos[k])[1].view(np.uint32))
+                for k in ("positions", "normals", "indices"):  # the step's own answer is that mesh: as words, or as the wrapper's bytes
+                    if k in want:
+                        assert np.array_equal(want[k].view(np.uint8), sharp[k].view(np.uint8)), (what, k)
+            elif s.get("form"):  # a composed call: its mesh is the plain extraction's
                 for k in ("positions", "normals", "indices"):
                     assert np.array_equal(want[k], plain[k].view(np.uint8)), (what, k)
             want = plain
@@ -522,6 +606,33 @@ class References:
                     ref[:, 3] = au.ONE
                     ref[~hit] = 0
                     qu.assert_same(str(what) + " lit", want["lit"].reshape(-1, 4)[live], ref)
+        elif call == "surveyMesh":
+            got = sp.MeshSurvey.from_buffer_copy(want["survey"].tobytes()).as_dict()
+            assert got == ho.survey(s, of), (what, got)
+        elif call == "fitMesh":
+            got = msu.fit_dict(sp.MeshFit.from_buffer_copy(np.insert(want["fit"], FIT_PADDING, 0).tobytes()))
+            assert got == ho.fit(s, of) and got["state"] == msu.FOUND, (what, got)
+        elif call in ("extractSlices", "countSlices"):  # whole
+            pos, uv, seg, lv, ls = ho.slices(s, of)
+            assert tuple(want["counts"]) == (len(pos), len(seg)), what
+            for name, ref in (("layer_vertices", lv), ("layer_segments", ls)):
+                for k in (name, name + " of the filling call"):
+                    assert k not in want or np.array_equal(want[k].view(np.int64), ref), (what, k)
+            if call == "extractSlices":
+                qu.assert_same(str(what) + " positions", want["positions"].reshape(-1, 3), pos.view(np.uint32))
+                assert np.array_equal(want["segments"].reshape(-1, 2), seg), what
+                if s["coords"]:
+                    qu.assert_same(str(what) + " coords", want["coords"].reshape(-1, 2), uv.view(np.uint32))
+        elif call in ("querySpans", "pickSpans", "meshSpans"):  # the stride sample
+            S, spans = ho.spans(s, of, ho.span_rays(s, of, (inp["points"], inp["normals"]) if call == "meshSpans" else None, pick))
+            qu.assert_same(str(what) + " summaries", want["summaries"].reshape(-1, 8)[pick], S.view(np.uint32).reshape(-1, 8))
+            if s["max_spans"]:
+                qu.assert_same(str(what) + " spans", want["spans"].reshape(n, -1)[pick], spans.view(np.uint32).reshape(len(pick), -1))
+        elif call == "measure":  # whole: the record and the columns, every bit
+            res, col = ho.measure(s, of)
+            mu_.assert_same_result(what, sp.MeasureResult.from_buffer_copy(want["result"].tobytes()), res)
+            if s["columns"]:
+                assert np.array_equal(want["columns"].reshape(-1, 10), col.reshape(-1).view(np.uint32).reshape(-1, 10)), (what, "columns")
         else:
             raise KeyError(call)
 
@@ -592,6 +703,30 @@ def _fail(r, refs, steps, s, keep, where):
         if kind == "mesh_small_capacity":
             status = OK
             assert c.extra["counts"] == (v, t), (where, c.extra["counts"], (v, t))
+    elif kind in ("slice_negative_capacity", "slice_small_capacity"):
+        q = dict(s, call="extractSlices", coords=True, layer_vertices=True, layer_segments=True)
+        ref = refs.pseudo(q, call="countSlices")
+        v, n = (int(x) for x in ref["counts"])
+        assert v >= 2 and n >= 2
+        cap = (-1, n) if kind == "slice_negative_capacity" else ((v - 1, n) if s["seed"] % 2 else (v, n - 1))
+        c = Call(r, q, {}, host, override=dict(capacity=cap, rows=(v, n)))
+        if kind == "slice_small_capacity":  # "only counts and the layer arrays are written, the arrays are untouched and the call returns SDFR_OK"
+            status = OK
+            assert c.extra["counts"] == (v, n), (where, c.extra["counts"], (v, n))
+            for b, name in zip(c.extra["layers"], ("layer_vertices", "layer_segments")):
+                assert np.array_equal(b.read((where, name)), ref[name]), (where, name)
+        else:
+            assert all(b.untouched() for b in c.extra["layers"]), (where, "a failed call wrote the layer arrays")
+    elif kind == "span_max_spans_65":
+        q = dict(s, **ENTRY_CALLS["ray_spans"])
+        c = Call(r, q, refs.inputs(q, steps), host, override=dict(max_spans=65))
+    elif kind == "measure_nu_0":
+        q = dict(s, call="measure", grid=hm.measure_grid(s["lattice"], "y", 8, 8), columns=True, march="finish")
+        c = Call(r, q, {}, host, override=dict(nu=0))
+    elif kind == "survey_bad_band":
+        c = Call(r, dict(s, call="surveyMesh", band=0.0), {}, host, override=dict(band=-1.0))
+    elif kind == "fit_bad_margin":
+        c = Call(r, dict(s, call="fitMesh", levels=2, margin=1), {}, host, override=dict(margin=9))
     elif kind in ("aa_factor_3", "aa_bad_format"):
         q = dict(s, call="renderAA", factor=2, fmt=hs.RGBA32F, stats=True)
         c = Call(r, q, {}, host, override=dict(factor=3) if kind == "aa_factor_3" else dict(fmt=7))
@@ -623,6 +758,7 @@ def _run_sequence(refs, seed):
     waited = 0
     refs.cache.clear()
     checked = {}       # family: steps whose reference answer was checked against the oracle
+    checked_forms = set()  # ... "sharp", once a sharp mesh was
     try:
         # every reference answer first: nothing but the handle under test then works on the GPU between a call and the next
         t0 = time.perf_counter()
@@ -656,27 +792,35 @@ def _run_sequence(refs, seed):
             if s.get("defer"):
                 pending.append((c, where))
                 continue
-            if st["fif"] == 2 and (not host or pending):
+            alone = bool(s.get("alone"))  # read at once; what is pending stays so
+            device_answers = not host and s["family"] != "survey"  # (a survey answers into a host record and is synchronous)
+            if st["fif"] == 2 and (device_answers or (pending and not alone)):
                 r.sync()  # two frames in flight: "call sdfr_sync before reading device answers"
-            for pc, pwhere in pending:
+            for pc, pwhere in [] if alone else pending:
                 if pc.s.get("image") and any(c2.s.get("image") == pc.s["image"] for c2, _ in pending[pending.index((pc, pwhere)) + 1:] + [(c, where)]):
                     continue  # a later frame of the block went into the same image: the last writer's is what must be there
                 got = _check(r, refs, steps, pc, pwhere, last)
                 if pc.s["family"] in ("render", "aa"):
                     last = got
-            pending = []
+            pending = pending if alone else []
             got = _check(r, refs, steps, c, where, last)
             if s["family"] in ("render", "aa"):
                 last = got
-            if last is not None:
-                assert _totals(r.getStats()) == last, (where, "sdfr_get_stats does not report the last frame", _totals(r.getStats()), last)
+            reported = last
+            for pc, _pwhere in pending:  # (a call read alone: the last frame may be one whose answers are still to be read)
+                if pc.s["family"] in ("render", "aa"):
+                    reported = tuple(int(x) for x in refs.answer(pc.s, steps)["totals"])
+            if reported is not None:
+                assert _totals(r.getStats()) == reported, (where, "sdfr_get_stats does not report the last frame", _totals(r.getStats()), reported)
             for copy, frame, cwhere in copies:
                 side.synchronize()
                 want = refs.answer(frame.s, steps)["image"]
                 assert np.array_equal(copy.cpu().numpy().view(np.uint32)[:frame.bufs["image"].words], want), (cwhere, "sdfr_wait_frame did not wait for the last frame")
                 waited += 1
             copies = []
-            if st["scene"] != hs.RUNTIME_SCENE and call != "countMesh" and (i % 8 == seed % 8 or s["family"] not in checked):
+            sharp = s.get("form") in hm.SHARP_FORMS and "sharp" not in checked_forms
+            if hm.oracle_checkable(s) and (i % 8 == seed % 8 or s["family"] not in checked or sharp):
+                checked_forms.update(["sharp"] if s.get("form") in hm.SHARP_FORMS else [])
                 t2 = time.perf_counter()
                 refs.check_oracle(s, steps)
                 spent["oracle"] += time.perf_counter() - t2
@@ -707,7 +851,9 @@ def _every_entry(r, host):
     """(name, call) of one small call of every scene-dependent entry point"""
     s0 = dict(i=0, seed=5, n=65, w=16, h=9, host=host, block=None, family=None, form=None,
               state=dict(scene="gems", t=0.3), lattice=dict(origin=(0.5, -0.3, -2.7), cell=0.13, dims=(7, 6, 5)), reach=0.2, bias=0.05, radius=1.0,
-              tile=4, width=64, layers=("albedo", "normal", "lit"))
+              tile=4, width=64, layers=("albedo", "normal", "lit"), max_spans=3, march="finish", band=0.0, levels=2, margin=1, columns=True, coords=True,
+              layer_vertices=True, layer_segments=True)
+    s0["slices"], s0["grid"] = hm.slice_grid(s0["lattice"], "y", 3), hm.measure_grid(s0["lattice"], "y", 9, 7)
     o, d = hm.rays(s0)
     quad = (np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], np.float32), np.array([[0, 0, 1]] * 4, np.float32), np.array([[0, 1, 2], [0, 2, 3]], np.uint32))
     inp = dict(origins=np.array(o, np.float32), dirs=np.array(d, np.float32), points=np.array(hm.points(s0), np.float32), normals=np.array(hm.normals(s0), np.float32),
@@ -717,7 +863,11 @@ def _every_entry(r, host):
              dict(call="pickSurfaces", hits=True, frame=True, n=16 * 9), dict(call="meshSurfaces", hits=True), dict(call="queryOcclusion"), dict(call="hitOcclusion"),
              dict(call="queryRayLighting", hits=True, lights=True, frame=False), dict(call="pickLighting", hits=True, lights=True, frame=False),
              dict(call="pickLighting", hits=True, lights=True, frame=True, n=16 * 9), dict(call="meshLighting", hits=True, lights=True), dict(call="countMesh"),
-             dict(call="bakeAtlas")]
+             dict(call="bakeAtlas"), dict(call="countMesh", form="sharp"), dict(call="surveyMesh"), dict(call="fitMesh"), dict(call="countSlices"),
+             dict(call="querySpans", frame=False), dict(call="pickSpans", frame=False), dict(call="pickSpans", frame=True, n=16 * 9), dict(call="meshSpans"),
+             dict(call="measure")]
+    assert len({(q["call"], q.get("form")) for q in calls if q["call"] in ("countMesh", "surveyMesh", "fitMesh", "countSlices", "querySpans", "pickSpans", "meshSpans",
+                                                                            "measure")} - {("countMesh", None)}) == 8
     for q in calls:
         yield dict(s0, **q), inp
 
@@ -776,3 +926,54 @@ def test_atlas_openness_with_two_frames_in_flight(device):
     assert got[0]["positions"].size > 3 * 200 and (got[0]["openness"].view(np.float32) > 0).mean() > 0.05
     assert not np.isin(got[0]["openness"].view(np.float32), (0.0, 1.0)).all()
     _same("two frames in flight against one", got[1], got[0])
+
+
+@pytest.mark.parametrize("device", (False, True))
+def test_sync_calls_wait_for_the_other_lanes_emit(device):
+    """Two frames in flight: a device sharp extraction (its emit and sharp-vertex work enqueued, reading the lattice in `mesh`), a
+    frame (the lanes swap), then at once a measure and a survey on the other lane, both synchronous and both writing `mesh`, with no
+    sync of the test's own.  After sdfr_sync the mesh is the mesh of a handle that did nothing else, and the measure and the survey
+    are a fresh handle's; the measure's columns in host and in device form."""
+    import torch
+    import sdf_playground_amd as sp
+
+    lat = dict(origin=(-3.55, 2.35, 2.81), cell=0.13, dims=(24, 24, 24))
+    st = dict(scene="labyrinth", t=0.7)
+    steps = [dict(i=0, call="extractMesh", form="sharp", normals=True, lattice=lat, state=st),
+             dict(i=1, call="measure", grid=hm.measure_grid(dict(lat, dims=(9, 9, 9)), "y", 9, 8), columns=True, march="finish", state=st),
+             dict(i=2, call="surveyMesh", lattice=dict(lat, dims=(12, 12, 12), cell=0.26), band=0.13, state=st)]
+
+    def handle(fif):
+        r = sp.SDFRenderer(0)
+        r.initShader("labyrinth")
+        r.setParameters(0.5)
+        r.setFramesInFlight(fif)
+        _set_camera(r, "labyrinth", 0.7, 96, 64)
+        return r
+
+    want = []
+    for s in steps:  # each from a handle that does nothing else
+        r = handle(1)
+        try:
+            c = Call(r, s, {}, True)
+            assert c.rc == OK
+            r.sync()
+            want.append(c.answers(r, ("fresh", s["call"])))
+        finally:
+            r.close()
+    assert want[0]["counts"][0] > 500 and sp.MeshSurvey.from_buffer_copy(want[2]["survey"].tobytes()).active_cells > 0
+    assert sp.MeasureResult.from_buffer_copy(want[1]["result"].tobytes()).columns_hit >= 8
+
+    r = handle(2)
+    try:
+        image = torch.empty((64, 96, 4), dtype=torch.float32, device="cuda")
+        mesh = Call(r, steps[0], {}, False)
+        r.render(width=96, height=64, out=image)  # the lanes swap
+        measure = Call(r, steps[1], {}, not device)
+        survey = Call(r, steps[2], {}, False)
+        assert (mesh.rc, measure.rc, survey.rc) == (OK, OK, OK)
+        r.sync()
+        for c, ref, name in ((mesh, want[0], "mesh"), (measure, want[1], "measure"), (survey, want[2], "survey")):
+            _same((name, "after the other lane's emit"), c.answers(r, name), ref)
+    finally:
+        r.close()

@@ -1,5 +1,7 @@
 """CPU tier of the mixed handle sequences (tests/handle_mixed_sequences.py): the committed seeds cover what they are there to cover.
 The GPU tier (tests/test_gpu_handle_mixed.py) runs them."""
+import numpy as np
+
 import handle_mixed_sequences as hm
 import handle_sequences as hs
 
@@ -25,17 +27,23 @@ def test_deterministic_per_seed_and_seeds_differ():
 
 
 def test_every_ordered_pair_of_families_is_a_pair_of_consecutive_steps():
-    """all 12 x 12 but (failed, failed): a failed call always sits between two valid calls"""
-    assert len(hm.FAMILIES) == 12 and len(hm.PAIRS) == 143
+    """all 16 x 16 but (failed, failed): a failed call always sits between two valid calls"""
+    assert len(hm.FAMILIES) == 16 and len(hm.PAIRS) == 255 and len(set(hm.FAMILIES)) == 16
+    assert set(hm.FAMILIES) >= {"survey", "slices", "spans", "measure"}
     seen = set().union(*(hm.transitions(steps) for steps in SEQUENCES.values()))
     assert not set(hm.PAIRS) - seen, sorted(set(hm.PAIRS) - seen)
 
 
 def test_every_family_in_host_and_device_form_with_one_and_two_frames_in_flight():
-    """(postprocess takes device tensors only: it has no host form)"""
+    """(postprocess takes device tensors only, a survey and a fit answer into a host record: no host form and no device form; a
+    measure counts with `columns` alone)"""
     seen = set().union(*(hm.forms(steps) for steps in SEQUENCES.values()))
-    want = {(f, host, fif) for f in hm.HOST_AND_DEVICE for host in (False, True) for fif in (1, 2)} | {("post", False, 1), ("post", False, 2)}
+    assert set(hm.HOST_AND_DEVICE) == set(hm.FAMILIES) - {"post", "survey", "failed"}
+    want = {(f, host, fif) for f in hm.HOST_AND_DEVICE for host in (False, True) for fif in (1, 2)}
+    want |= {(f, False, fif) for f in ("post", "survey") for fif in (1, 2)}
     assert not want - seen, sorted(want - seen)
+    assert all(s["columns"] for s in ALL if s["family"] == "measure" and (s["family"], s["host"], s["state"]["fif"]) in hm.forms([s]))
+    assert {(s["host"], s["state"]["fif"]) for s in ALL if s["call"] == "measure" and s["columns"]} == {(h, f) for h in (False, True) for f in (1, 2)}
     assert all(s["family"] in hm.FAMILIES for s in ALL)
 
 
@@ -43,8 +51,9 @@ def test_every_call_and_variant_of_the_families_occurs():
     calls = {s["call"] for s in ALL}
     assert calls >= {"render", "renderAA", "postprocess", "queryDistance", "queryRays", "pick", "queryRaySurfaces", "pickSurfaces", "meshSurfaces",
                      "queryOcclusion", "hitOcclusion", "queryRayLighting", "pickLighting", "meshLighting", "extractMesh", "countMesh", "atlasTexels",
-                     "bakeAtlas", "renderPrivateStrips", "failed"}
-    for call in ("pickSurfaces", "pickLighting"):
+                     "bakeAtlas", "renderPrivateStrips", "failed", "surveyMesh", "fitMesh", "extractSlices", "countSlices", "querySpans", "pickSpans",
+                     "meshSpans", "measure"}
+    for call in ("pickSurfaces", "pickLighting", "pickSpans"):
         assert {bool(s.get("frame")) for s in ALL if s["call"] == call} == {False, True}, call  # a pixel list, and None = the whole frame
     for call, key in (("render", "stats"), ("renderAA", "stats"), ("queryDistance", "normals"), ("queryRaySurfaces", "hits"), ("pickLighting", "hits"),
                       ("pickLighting", "lights"), ("extractMesh", "normals")):
@@ -57,6 +66,42 @@ def test_every_call_and_variant_of_the_families_occurs():
     assert len({s["layers"] for s in ALL if s["call"] == "bakeAtlas"}) >= 5
     assert {s["tile"] for s in ALL if s["family"] == "atlas"} == set(hm.TILES)
     assert {s["n"] for s in ALL if s["block"] is None and s["call"] in ("queryDistance", "queryRays", "pick")} == set(hm.ITEMS)
+    # the families that came with the survey, the slices, the spans, the measure and the sharp mesh
+    free = [s for s in ALL if s["block"] is None]
+    assert set(hm.SHARP_FORMS) <= set(hm.MESH_FORMS) and {s["normals"] for s in ALL if s.get("form") == "sharp"} == {False, True}
+    assert {round(s["band"] / s["lattice"]["cell"], 1) for s in free if s["call"] == "surveyMesh"} == set(hm.BANDS) == {0.0, 0.5, 2.0}
+    assert {s["levels"] for s in ALL if s["call"] == "fitMesh"} == {0, 2, 3} and {s["margin"] for s in ALL if s["call"] == "fitMesh"} == {0, 1}
+    assert {s["axis"] for s in free if s["family"] == "slices"} == {"x", "y", "z", "oblique"}
+    for s in free:
+        if s["family"] == "slices":  # an axis-aligned stack has du and dv along two axes and dw along the third; an oblique one has them turned about dw
+            g = s["slices"]
+            zeros = [sum(1 for x in g[k] if x == 0.0) for k in ("du", "dv", "dw")]
+            assert zeros == ([1, 1, 2] if s["axis"] == "oblique" else [2, 2, 2]), s
+            assert abs(sum(a * b for a, b in zip(g["du"], g["dv"]))) < 1e-5 and all(sum(a * b for a, b in zip(g[k], g["dw"])) == 0 for k in ("du", "dv"))
+    assert {s["slices"]["layers"] for s in free if s["family"] == "slices"} >= {1, hm.MAX_SLICE_LAYERS}
+    for key in ("coords", "layer_vertices", "layer_segments"):
+        assert {s[key] for s in ALL if s["call"] == "extractSlices"} == {False, True}, key
+    spans = [s for s in free if s["family"] == "spans"]
+    assert {(s["call"], bool(s.get("frame"))) for s in spans} == {("querySpans", False), ("pickSpans", False), ("pickSpans", True), ("meshSpans", False)}
+    assert {s["max_spans"] for s in spans} == {0, 1, 3, 64} and {s["march"] for s in spans} == {"finish", "short"}
+    for march, sets in hm.SPAN_PARAMS.items():
+        for min_step, t_max, max_steps in sets.values():  # "finish": every ray reaches t_max within its steps, whatever the distances
+            assert (t_max / min_step + 2 <= max_steps) == (march == "finish") and (march == "finish" or max_steps == 32)
+    measures = [s for s in free if s["family"] == "measure"]
+    assert {s["grid"]["nu"] for s in measures} | {s["grid"]["nv"] for s in measures} == set(hm.MEASURE_COLUMNS) | {hm.MEASURE_BIG} == {1, 7, 8, 9, 24, 72}
+    assert any(-(-s["grid"]["nu"] // 8) * -(-s["grid"]["nv"] // 8) > 64 for s in measures)  # more than one run of 64 tiles: the reduction runs a pass
+    assert {s["axis"] for s in measures} == {"x", "y", "z", "tilted"} and {s["columns"] for s in measures} == {False, True}
+    assert {s["march"] for s in measures} == {"finish", "short"} and all(ms <= 128 for _m, ms in hm.MEASURE_PARAMS.values())
+    for s in measures:
+        assert sum(1 for x in s["grid"]["dw"] if x != 0.0) == (2 if s["axis"] == "tilted" else 1), s
+
+
+def test_every_seed_has_every_family_where_the_oracle_can_check_it():
+    """the GPU tier holds every family's reference answer against the CPU oracle at least once per seed: every seed has a step of
+    every family on a built-in scene that is no counting call over millions of points"""
+    for seed, steps in SEQUENCES.items():
+        seen = {s["family"] for s in steps if hm.oracle_checkable(s)}
+        assert seen == set(hm.FAMILIES) - {"failed"}, (seed, sorted(set(hm.FAMILIES) - {"failed"} - seen))
 
 
 def test_every_family_on_the_run_time_scene_and_with_the_debug_plane():
@@ -69,10 +114,10 @@ def test_every_family_on_the_run_time_scene_and_with_the_debug_plane():
         assert flips >= 4
 
 
-def test_each_seed_has_the_five_scripted_blocks():
+def test_each_seed_has_the_seven_scripted_blocks():
     for seed, steps in SEQUENCES.items():
         b = hm.blocks(steps)
-        assert sorted(b) == ["aa_in_flight", "lanes", "large_mesh", "scene_change", "staging"] == sorted(hm.BLOCKS), seed
+        assert sorted(b) == ["aa_in_flight", "lanes", "large_mesh", "large_new", "scene_change", "staging", "workspace_cuts"] == sorted(hm.BLOCKS), seed
         for name, part in b.items():
             if name == "scene_change":  # its scripted steps are the first two and the last two, free steps on the run-time scene between them
                 first, end = part[0]["i"], part[0]["i"] + hm.BLOCK_STEPS[name]
@@ -123,9 +168,43 @@ def test_each_seed_has_the_five_scripted_blocks():
         assert q["state"]["scene"] in hs.BUILTIN_SCENES and m["state"]["scene"] == s2["state"]["scene"] == hs.RUNTIME_SCENE and last["state"]["scene"] in hs.BUILTIN_SCENES
         assert "scene" in m["set"] and "scene" in last["set"] and not steps[m["i"] + 1].get("defer")
         assert m["call"] == "extractMesh" and q["family"] != "mesh" and s2["family"] not in ("mesh", "render")
+        assert s2["call"] in ("queryRaySurfaces", "querySpans")
         assert hm.runtime_entries(steps) == 1  # every entry compiles the scene and its query kernels again: seconds
 
+        # 6: `mesh` cut 5, 3, 2, 4 and 5 ways in one run, behind the other lane's enqueued emit work
+        sl, frame, me, su, sh, sl2 = b["workspace_cuts"]
+        assert [s["call"] for s in (sl, frame, me, su, sh, sl2)] == ["extractSlices", "render", "measure", "surveyMesh", "extractMesh", "extractSlices"]
+        assert all(s["state"]["fif"] == 2 and not s["host"] for s in (sl, frame, me, su, sh, sl2))
+        assert [bool(s.get("defer")) for s in (sl, frame, me, su, sh, sl2)] == [True, True, False, False, True, False]
+        assert me.get("alone") and su.get("alone") and not sl2.get("alone")  # read at once, the deferred answers after the last call's sync
+        assert sh["form"] == "sharp" and me["columns"] and me["iso"] == 0.01  # (an iso-surface of its own: the one measure off the scene's surface)
+        g = sl["slices"]
+        assert g["dims"] == (hm.MAX_LATTICE, hm.MAX_LATTICE) and g["layers"] == hm.MAX_SLICE_LAYERS  # the largest free size
+        cuts = [hm.slice_workspace_bytes(g["dims"], g["layers"]), hm.measure_workspace_bytes(me["grid"]["nu"], me["grid"]["nv"]),
+                hm.survey_workspace_bytes(su["lattice"]["dims"]), hm.workspace_bytes(sh["lattice"]["dims"]),
+                hm.slice_workspace_bytes(sl2["slices"]["dims"], sl2["slices"]["layers"])]
+        assert cuts[1] < cuts[0] and cuts[3] > max(cuts[:3]) and cuts[4] < cuts[3] and max(cuts) <= hm.KEEP, cuts
+        assert cuts[0] == 256 * (3 * 79 + 2) and cuts[1] == 768 + 256 + 128 * 210  # 25 * 25 * 8 points in 5 pieces; 9 tiles, one run, the tally
+
+        # 7: the large calls of the new families, each followed by a small call that cuts the buffer again
+        big, count, m1, px, m2 = b["large_new"]
+        assert [s["call"] for s in (big, count, m1, px, m2)] == ["surveyMesh", "countSlices", "measure", "pickSpans", "measure"]
+        n = big["lattice"]["dims"][0]
+        assert big["lattice"]["dims"] == (n, n, n) and hm.survey_workspace_bytes((n, n, n)) > hm.KEEP >= hm.survey_workspace_bytes((n - 1,) * 3)
+        assert hm.survey_workspace_bytes((n, n, n)) == (n + 1) ** 3 * 4 + 4096 * 23 and n == 255
+        g = count["slices"]
+        n = g["dims"][0]
+        assert g["dims"] == (n, n) and hm.slice_workspace_bytes((n, n), g["layers"]) > hm.KEEP >= hm.slice_workspace_bytes((n - 1, n - 1), g["layers"])
+        assert hm.measure_workspace_bytes(m1["grid"]["nu"], m1["grid"]["nv"]) < 1 << 20
+        w, h = hm.BIG_SPAN_FRAME
+        assert (px["host"], px["frame"], px["max_spans"], px["n"], px["w"], px["h"]) == (True, True, 64, w * h, w, h) and w % 8 == 0 and h % 8 == 0
+        assert hm.staging_bytes(px) == w * h * (32 + 64 * 8) == 68239360 > hm.KEEP  # (every piece a multiple of 256 bytes already)
+        assert hm.staging_bytes(dict(px, n=(w - 8) * h)) <= hm.KEEP or hm.staging_bytes(dict(px, n=w * (h - 8))) <= hm.KEEP  # no smaller frame of whole tiles
+        assert m2["host"] and m2["columns"] and 0 < hm.staging_bytes(m2) < 1 << 20
+
         assert any(part[0]["state"]["fif"] == 2 for part in b.values())
+    kinds = {hm.blocks(steps)["scene_change"][2]["call"] for steps in SEQUENCES.values()}
+    assert kinds == {"queryRaySurfaces", "querySpans"}  # the call in flight on the run-time scene when it goes: both kinds
 
 
 def hs_private_rows(height, split):
@@ -135,7 +214,12 @@ def hs_private_rows(height, split):
 
 def test_every_failure_kind_and_each_between_two_valid_calls():
     assert set().union(*(hm.failure_kinds(steps) for steps in SEQUENCES.values())) == set(hm.FAILURE_KINDS)
-    assert len(hm.FAILURE_KINDS) == 8
+    assert len(hm.FAILURE_KINDS) == 14
+    assert dict(hm.FAILURES)["slice_negative_capacity"] == "negative capacity" and dict(hm.FAILURES)["slice_small_capacity"] is None
+    assert [dict(hm.FAILURES)[k] for k in ("span_max_spans_65", "measure_nu_0", "survey_bad_band", "fit_bad_margin")] == [
+        "bad span parameters", "bad measure grid", "band must be finite and >= 0", "margin must be 0..8"]
+    # the kinds every query entry has go through the three span entries too
+    assert {s["entry"] for s in ALL if s["family"] == "failed" and s["fail"] in hm.SHARED_KINDS} >= set(hm.SPAN_ENTRIES)
     for steps in SEQUENCES.values():
         for s in steps:
             if s["family"] == "failed":
@@ -155,13 +239,19 @@ def test_sizes_outside_the_scripted_blocks_are_the_smallest_that_cross_the_edges
         if s["call"] == "renderAA":
             assert s["w"] <= 160 and s["h"] <= 90
         if "lattice" in s:
-            assert max(s["lattice"]["dims"]) <= hm.MAX_LATTICE
+            assert max(s["lattice"]["dims"]) <= (hm.MAX_FIT if s["call"] == "fitMesh" else hm.MAX_LATTICE) and hm.MAX_FIT <= 64
+        if "slices" in s:
+            assert max(s["slices"]["dims"]) <= 24 and 1 <= s["slices"]["layers"] <= 8
+        if s["family"] == "spans" and s.get("frame"):
+            assert (s["w"], s["h"]) in hm.AA_SIZES and s["n"] == s["w"] * s["h"]
+        if s["family"] == "measure":
+            assert {s["grid"]["nu"], s["grid"]["nv"]} <= set(hm.MEASURE_COLUMNS) | {hm.MEASURE_BIG}
         if "tile" in s:
             assert s["tile"] in (4, 8, 16) and s["width"] <= 256 and s["width"] % max(8, s["tile"]) == 0
     # the edges themselves: a lattice that is no cube, item counts around the 64 items of a block, pixels outside the frame
     assert any(len(set(s["lattice"]["dims"])) == 3 for s in ALL if "lattice" in s)
     for s in ALL:
-        if s["call"] in ("pick", "pickSurfaces", "pickLighting") and not s.get("frame"):
+        if s["call"] in ("pick", "pickSurfaces", "pickLighting", "pickSpans") and not s.get("frame"):
             px = hm.pixel_list(s)
             assert len(px) == s["n"] and not (0 <= px[0][0] < s["w"] and 0 <= px[0][1] < s["h"])
 
@@ -173,7 +263,7 @@ def test_every_lattice_meets_the_surface():
     import query_util as qu
 
     for s in ALL:
-        if "lattice" not in s or s["state"]["scene"] == hs.RUNTIME_SCENE or s["call"] == "countMesh":
+        if "lattice" not in s or s["state"]["scene"] == hs.RUNTIME_SCENE or s["call"] == "countMesh" or s["block"] == "large_new":
             continue
         src = SEQUENCES_OF[id(s)][s["src"]] if s["family"] == "atlas" and s["src"] is not None else s  # an atlas of an earlier step's mesh
         st, lat = src["state"], src["lattice"]
@@ -183,6 +273,54 @@ def test_every_lattice_meets_the_surface():
         D = qu.oracle_points(st["scene"], of, mu.lattice_points(lat["origin"], lat["cell"], lat["dims"]), normals=False)[0]
         pos, idx = mu.surface_nets(D, lat["origin"], lat["cell"], lat["dims"], 0.0)
         assert len(pos) >= 8 and len(idx) >= 4, (s["i"], s["call"], st["scene"], st["vars"], lat, len(pos), len(idx))
+
+
+def surface_condition(s):
+    """What a step of the survey, the slices, the spans or the measure on a built-in scene meets of the surface, by the oracle's
+    distances in the step's state: (None, {}) if the step has nothing to meet, else (the condition it misses or None, what was seen)"""
+    import handle_mixed_oracle as ho
+
+    if s["state"]["scene"] == hs.RUNTIME_SCENE:
+        return None, {}
+    of = ho.frame(s, s.get("w") or 16, s.get("h") or 9)
+    call = s["call"]
+    if call in ("extractSlices", "countSlices") or (call == "failed" and s["fail"].startswith("slice_")):
+        pos, _uv, seg, _lv, _ls = ho.slices(s, of)
+        return (None if len(pos) >= 8 and len(seg) >= 4 else "a slice stack has at least 8 vertices and 4 segments"), dict(vertices=len(pos), segments=len(seg))
+    if call in ("querySpans", "pickSpans", "meshSpans"):
+        S, _spans = ho.spans(s, of, ho.span_rays(s, of, ho.mesh_vertices(s, of) if call == "meshSpans" else None), max_spans=0)
+        seen = dict(crossing=float((S["crossings"] > 0).mean()), over=bool((S["spans"] > s["max_spans"]).any()), out_of_steps=bool((S["flags"] & 4).any()),
+                    invalid=bool((S["valid"] == -1).any()))
+        return (None if s["n"] < 64 or seen["crossing"] >= 0.125 else "of 64 or more items one in eight has a crossing"), seen
+    if call == "measure":
+        res, _col = ho.measure(s, of)
+        seen = dict(columns_hit=res["columns_hit"])
+        return (None if s["grid"]["nu"] * s["grid"]["nv"] < 64 or res["columns_hit"] >= 8 else "of 64 or more columns 8 are hit"), seen
+    if call == "surveyMesh" and s["block"] == "large_new":  # vertices > 0: some lattice point is inside and some is not
+        with np.errstate(invalid="ignore"):
+            inside = ho.lattice_distances(s, of) < 0
+        return (None if inside.any() and not inside.all() else "a survey has vertices"), {}
+    if call == "surveyMesh":
+        got = ho.survey(s, of)
+        return (None if got["active_cells"] > 0 else "a survey has vertices"), dict(vertices=got["active_cells"])
+    if call == "fitMesh":
+        got = ho.fit(s, of)
+        return (None if got["state"] == 1 else "a fit returns SDFR_FIT_FOUND"), dict(state=got["state"], dims=got["dims"])
+    return None, {}
+
+
+def test_every_input_of_the_new_families_meets_the_surface():
+    """conditions, not measurements: slices with contours, rays with crossings, columns that are hit, surveys with vertices, fits that
+    find -- every step of the committed seeds on a built-in scene, in its state (scene variables and the debug plane included); and over
+    all seeds some ray has more spans than are stored, some runs out of steps and some pixel is outside its frame"""
+    seen_all = dict(over=False, out_of_steps=False, invalid=False)
+    for s in ALL:
+        missed, seen = surface_condition(s)
+        assert missed is None, (missed, s["i"], s["call"], s["state"]["scene"], s["state"]["vars"], s["state"]["debug"], seen)
+        for k in seen_all:
+            seen_all[k] = seen_all[k] or bool(seen.get(k))
+    assert all(seen_all.values()), seen_all
+    assert hm.BANDS[0] == 0.0  # (a survey's vertices do not depend on the band)
 
 
 def test_the_interleavings_the_suite_never_ran_before():
