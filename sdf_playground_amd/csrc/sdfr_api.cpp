@@ -712,6 +712,19 @@ static int loaded_query_kernel(sdfr_renderer *r, int kind, const FrameU &U, Kern
 	k = qk->k[kind][frame_needs_debug(U) ? 1 : 0];
 	return SDFR_OK;
 }
+// one launch of the loaded scene's kernel of `kind` for frame U with that kind's arguments, in `blocks` blocks of one wave; what: the
+// error text of a launch that fails
+extern "C++" {
+template <class A>
+static int launch_loaded(sdfr_renderer *r, int kind, const FrameU &U, const A &args, uint32_t blocks, hipStream_t stream, const char *what)
+{
+	KernelRef k;
+	const int rc = loaded_query_kernel(r, kind, U, k);
+	if (rc != SDFR_OK) return rc;
+	const hipError_t e = launch_scene_kernel(k, U, args, blocks, stream);
+	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, what);
+}
+} // (a template, inside this file's extern "C")
 // one query of the loaded scene, every pointer of `q` device memory
 static int run_query(sdfr_renderer *r, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
@@ -765,6 +778,14 @@ static int stage_host_arrays(sdfr_renderer *r, Carving &st, const StagedArray *a
 	}
 	return SDFR_OK;
 }
+// ... for the pointer members of an arguments struct: piece k is the member at slots[k] with bytes[k] bytes, the first `inputs` are read
+static int stage_host_members(sdfr_renderer *r, Carving &st, void *args, const size_t *slots, const size_t *bytes, int n, int inputs, hipStream_t stream)
+{
+	assert(n <= (int)SDFR_STAGE_MAX_PIECES);
+	StagedArray arrays[SDFR_STAGE_MAX_PIECES];
+	for (int k = 0; k < n; ++k) arrays[k] = {static_cast<char *>(args) + slots[k], bytes[k], k < inputs};
+	return stage_host_arrays(r, st, arrays, n, stream);
+}
 // A buffer past what a handle keeps is given back once the work on `stream` that uses it is done: a large call does not hold its
 // staging or workspace for the rest of the handle's life; small ones keep reusing theirs
 static int release_large(sdfr_renderer *r, sdfr_device_buffer &b, hipStream_t stream)
@@ -802,10 +823,8 @@ static int query_impl(sdfr_renderer *r, const QueryRequest &c)
 	{
 		// the arrays of the kind in the order of p.bytes, each through its member of q
 		const QueryKind &kind = k_query_kinds[q.kind];
-		const QuerySlot *slots[6] = {&kind.in[0], &kind.in[1], &kind.out[0], &kind.out[1], &k_query_lighting_slots[0], &k_query_lighting_slots[1]};
-		StagedArray arrays[6];
-		for (int k = 0; k < 6; ++k) arrays[k] = {reinterpret_cast<char *>(&q) + slots[k]->member, p.bytes[k], k < 2};
-		rc = stage_host_arrays(r, st, arrays, 6, stream);
+		const size_t slots[6] = {kind.in[0].member, kind.in[1].member, kind.out[0].member, kind.out[1].member, k_query_lighting_slots[0].member, k_query_lighting_slots[1].member};
+		rc = stage_host_members(r, st, &q, slots, p.bytes, 6, 2, stream);
 		if (rc != SDFR_OK) return rc;
 	}
 	rc = run_query(r, U, q, stream);
@@ -940,17 +959,11 @@ static int span_impl(sdfr_renderer *r, const SpanRequest &c)
 	Carving st;
 	if (c.on_host)
 	{
-		StagedArray arrays[SPAN_STAGE_PIECES];
-		for (int k = 0; k < SPAN_STAGE_PIECES; ++k)
-			arrays[k] = {reinterpret_cast<char *>(&s) + k_span_stage_slots[s.kind == QUERY_PICK ? 1 : 0][k], p.bytes[k], k < SPAN_STAGE_INPUTS};
-		rc = stage_host_arrays(r, st, arrays, SPAN_STAGE_PIECES, stream);
+		rc = stage_host_members(r, st, &s, k_span_stage_slots[s.kind == QUERY_PICK ? 1 : 0], p.bytes, SPAN_STAGE_PIECES, SPAN_STAGE_INPUTS, stream);
 		if (rc != SDFR_OK) return rc;
 	}
-	KernelRef k;
-	rc = loaded_query_kernel(r, QUERY_KERNEL_SPANS, U, k);
+	rc = launch_loaded(r, QUERY_KERNEL_SPANS, U, s, p.blocks, stream, "span launch");
 	if (rc != SDFR_OK) return rc;
-	const hipError_t e = launch_query_spans(k, U, s, p.blocks, stream);
-	if (e != hipSuccess) return hip_fail(r, e, "span launch");
 	return c.on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
 }
 static SpanRequest span_request(int kind, int64_t n, const void *in0, const void *in1, const sdfr_span_params *params, sdfr_span_summary *summaries, sdfr_span *spans, int on_host)
@@ -1049,11 +1062,7 @@ static int sample_lattice(sdfr_renderer *r, const FrameU &U, LatticeArgs la, flo
 	static const int rows = [] { const char *e = getenv("SDFR_MESH_LATTICE_ROWS"); return e && atoi(e) != 0 ? 1 : 0; }(); // developer knob: the A/B
 	la.rows = rows;
 	la.out = d_lattice;
-	KernelRef lattice_kernel;
-	const int rc = loaded_query_kernel(r, QUERY_KERNEL_LATTICE, U, lattice_kernel);
-	if (rc != SDFR_OK) return rc;
-	const hipError_t e = launch_query_lattice(lattice_kernel, U, la, stream);
-	return e == hipSuccess ? SDFR_OK : hip_fail(r, e, "lattice launch");
+	return launch_loaded(r, QUERY_KERNEL_LATTICE, U, la, query_lattice_blocks(la), stream, "lattice launch");
 }
 static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *counts, bool sharp)
 {
@@ -1102,12 +1111,9 @@ static int mesh_impl(sdfr_renderer *r, const MeshRequest &c, sdfr_mesh_counts *c
 	SDFR_HIP(launch_mesh_emit(p.g, d_lattice, d_cells, d_points, d_pos, d_idx, sharp, stream));
 	if (sharp)
 	{
-		KernelRef sharp_kernel;
-		rc = loaded_query_kernel(r, QUERY_KERNEL_MESH_SHARP, U, sharp_kernel);
-		if (rc != SDFR_OK) return rc;
 		const MeshSharpArgs m = {{p.g.origin[0], p.g.origin[1], p.g.origin[2]}, p.g.cell, {p.g.n[0], p.g.n[1], p.g.n[2]}, p.g.iso, d_lattice, d_pos, n_vertices};
-		const hipError_t es = launch_mesh_sharp(sharp_kernel, U, m, stream);
-		if (es != hipSuccess) return hip_fail(r, es, "sharp vertex launch");
+		rc = launch_loaded(r, QUERY_KERNEL_MESH_SHARP, U, m, mesh_sharp_blocks(n_vertices), stream, "sharp vertex launch");
+		if (rc != SDFR_OK) return rc;
 	}
 	if (ev) SDFR_HIP(hipEventRecord(ev[4], stream));
 	if (d_nrm)
@@ -1197,11 +1203,8 @@ static int slice_impl(sdfr_renderer *r, const SliceRequest &c, int64_t *layer_ve
 	SliceArgs sample = p.sample;
 	sample.rows = rows;
 	sample.out = d_lattice;
-	KernelRef slice_kernel;
-	rc = loaded_query_kernel(r, QUERY_KERNEL_SLICES, U, slice_kernel);
+	rc = launch_loaded(r, QUERY_KERNEL_SLICES, U, sample, slice_sample_blocks(sample), stream, "slice launch");
 	if (rc != SDFR_OK) return rc;
-	const hipError_t e = launch_query_slices(slice_kernel, U, sample, slice_sample_blocks(sample), stream);
-	if (e != hipSuccess) return hip_fail(r, e, "slice launch");
 	SDFR_HIP(launch_slice_count(p.g, d_lattice, d_vertices, d_segments, d_sums, d_layers, stream));
 	const size_t per = (size_t)p.g.layers + 1;
 	std::vector<uint32_t> offsets(2 * per);
@@ -1347,12 +1350,9 @@ static int measure_impl(sdfr_renderer *r, const MeasureRequest &c, sdfr_measure_
 		rc = stage_host_arrays(r, st, arrays, 1, stream); // (in `query`, never in `mesh`)
 		if (rc != SDFR_OK) return rc;
 	}
-	KernelRef k;
-	rc = loaded_query_kernel(r, QUERY_KERNEL_MEASURE, U, k);
-	if (rc != SDFR_OK) return rc;
 	SDFR_HIP(launch_measure_init(g.tally, g.nu, g.nv, stream));
-	const hipError_t e = launch_query_measure(k, U, g, p.blocks, stream);
-	if (e != hipSuccess) return hip_fail(r, e, "measure launch");
+	rc = launch_loaded(r, QUERY_KERNEL_MEASURE, U, g, p.blocks, stream, "measure launch");
+	if (rc != SDFR_OK) return rc;
 	SDFR_HIP(launch_measure_reduce(partials, p.pass_records, p.passes, g.tally, stream));
 	MeasureResult res;
 	SDFR_HIP(hipMemcpyAsync(&res, g.tally, sizeof res, hipMemcpyDeviceToHost, stream));
@@ -1417,21 +1417,12 @@ static int atlas_impl(sdfr_renderer *r, const AtlasRequest &c)
 	Carving st;
 	if (c.on_host)
 	{
-		StagedArray arrays[ATLAS_STAGE_PIECES];
-		for (int k = 0; k < ATLAS_STAGE_PIECES; ++k) arrays[k] = {reinterpret_cast<char *>(&g) + k_atlas_stage_slots[c.bake ? 1 : 0][k], p.bytes[k], k < ATLAS_STAGE_INPUTS};
-		rc = stage_host_arrays(r, st, arrays, ATLAS_STAGE_PIECES, stream);
+		rc = stage_host_members(r, st, &g, k_atlas_stage_slots[c.bake ? 1 : 0], p.bytes, ATLAS_STAGE_PIECES, ATLAS_STAGE_INPUTS, stream);
 		if (rc != SDFR_OK) return rc;
 	}
-	if (p.needs_scene)
-	{
-		KernelRef k;
-		rc = loaded_query_kernel(r, QUERY_KERNEL_ATLAS, U, k);
-		if (rc != SDFR_OK) return rc;
-		const hipError_t e = launch_atlas_bake(k, U, g, p.blocks, stream);
-		if (e != hipSuccess) return hip_fail(r, e, "atlas launch");
-	}
-	else
-		SDFR_HIP(launch_atlas_texels(g, p.blocks, stream));
+	if (p.needs_scene) rc = launch_loaded(r, QUERY_KERNEL_ATLAS, U, g, p.blocks, stream, "atlas launch");
+	else SDFR_HIP(launch_atlas_texels(g, p.blocks, stream));
+	if (rc != SDFR_OK) return rc;
 	return c.on_host ? copy_answers_back(r, st, stream) : SDFR_OK;
 }
 

@@ -229,6 +229,13 @@ struct PixelKernelArgs
 	unsigned long cap; // pixels the ray queue is allocated for (size_t)
 	uint32_t *tile_cursors;
 };
+// ... and a launch of a scene's query kernel of any kind (sdfr_query_args.h: SDFR_FOR_EACH_QUERY_KERNEL), likewise, with the kind's arguments A
+template <class A>
+struct SceneKernelArgs
+{
+	FrameU U;
+	A a;
+};
 
 enum { FORMAT_RGBA32F = 0, FORMAT_RGBA16F = 1, FORMAT_STRIP_RGB32F_A8 = 2, FORMAT_STRIP_RGB16F_A8 = 3 };
 

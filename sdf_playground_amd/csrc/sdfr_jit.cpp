@@ -4,9 +4,10 @@
 // whenever its file changes (SceneManager.cpp:102-133, SDFRenderer::initShader
 // SDFRenderer.cpp:27-53 with D3DCompile).  The equivalent here: the text of a scene functor
 // (the same shape as the ahead-of-time scenes of sdfr_scenes*.h, named `Scene`) is wrapped
-// into a translation unit around sdfr_pixel_kernel.h, compiled for the device's architecture
-// with hiprtc and loaded as a module.  The pixel kernel body is the one the ahead-of-time
-// scenes use, so a scene renders the same bits either way.
+// into a translation unit around sdfr_pixel_kernel.h (sdfr_jit_unit.h writes its text, and that
+// of the query kernels' unit), compiled for the device's architecture with hiprtc and loaded as
+// a module: this file.  The pixel kernel body is the one the ahead-of-time scenes use, so a
+// scene renders the same bits either way.
 //
 // VAR_ tags: as in the reference (ShaderUtil.cpp:122-191) the variable table is discovered by
 // scanning the source text for `VAR_<name>(key = value, ...)`.  Inside a method that receives
@@ -76,52 +77,7 @@ std::string header_dir()
 	return "csrc";
 }
 
-// the query kernels of a run-time scene by kind (QUERY_KERNEL_*): the symbol (its DBG variant: + "_debug"), the kernel template
-// (sdfr_query_kernel.h) and its argument type
-const struct { const char *symbol, *body, *args; } k_query_kernels[QUERY_KERNEL_KINDS] = {
-	{"sdfr_jit_query_points", "query_points_kernel", "QueryKernelArgs"},
-	{"sdfr_jit_query_rays", "query_rays_kernel", "QueryKernelArgs"},
-	{"sdfr_jit_query_lattice", "query_lattice_kernel", "LatticeKernelArgs"},
-	{"sdfr_jit_query_surfaces", "query_surfaces_kernel", "QueryKernelArgs"},
-	{"sdfr_jit_query_occlusion", "query_occlusion_kernel", "QueryKernelArgs"},
-	{"sdfr_jit_query_lighting", "query_lighting_kernel", "QueryKernelArgs"},
-	{"sdfr_jit_bake_atlas", "atlas_bake_kernel", "AtlasKernelArgs"},
-	{"sdfr_jit_mesh_sharp", "mesh_sharp_kernel", "MeshSharpKernelArgs"},
-	{"sdfr_jit_query_slices", "query_slices_kernel", "SliceKernelArgs"},
-	{"sdfr_jit_query_spans", "query_spans_kernel", "SpanKernelArgs"},
-	{"sdfr_jit_query_measure", "query_measure_kernel", "MeasureKernelArgs"},
-};
-
 } // namespace
-
-std::string jit_translation_unit(const std::string &scene_source, const std::vector<std::string> &var_slots, bool query)
-{
-	std::string tu;
-	tu += query ? "#include \"sdfr_query_kernel.h\"\n" : "#include \"sdfr_pixel_kernel.h\"\n";
-	// a scene that came in the reference's dialect (sdfr_hlsl.cpp) needs the HLSL vocabulary
-	if (scene_source.find("hlsl::SceneAdapter") != std::string::npos) tu += "#include \"sdfr_hlsl.h\"\n";
-	tu += "namespace sdfr {\n";
-	for (size_t k = 0; k < var_slots.size(); ++k)
-		tu += "#define VAR_" + var_slots[k] + "(...) (U.scene_var[" + std::to_string(k) + "])\n";
-	tu += "#line 1 \"scene\"\n";
-	tu += scene_source;
-	tu += "\n#line 1 \"sdfr_jit_kernels\"\n";
-	if (query)
-	{
-		for (const auto &k : k_query_kernels)
-			for (int dbg = 0; dbg < 2; ++dbg)
-				tu += std::string("extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void ") + k.symbol + (dbg ? "_debug(" : "(") + k.args + " a) { " + k.body +
-					"<Scene, " + (dbg ? "true" : "false") + ">(a); }\n";
-	}
-	else
-	{
-		tu += "extern \"C\" __global__ void sdfr_jit_prepare(FrameU *U) { if (blockIdx.x == 0 && threadIdx.x == 0) Scene::prepare(*U); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_pixel(PixelKernelArgs args) { pixel_kernel<Scene, false>(args); }\n";
-		tu += "extern \"C\" __global__ SDFR_PIXEL_KERNEL_ATTRS(Scene) void sdfr_jit_pixel_debug(PixelKernelArgs args) { pixel_kernel<Scene, true>(args); }\n";
-	}
-	tu += "} // namespace sdfr\n";
-	return tu;
-}
 
 void jit_unload(JitScene &js)
 {
@@ -156,7 +112,7 @@ bool jit_compile_code(const std::string &arch_name, const std::string &name, con
 	// checked against and a user's text is not: run-time scenes get the plain IEEE forms unless the text
 	// opts in by containing the token SDFR_FAST_EXACT_MATH (say, in a comment)
 	const char *math = scene_source.find("SDFR_FAST_EXACT_MATH") != std::string::npos ? "-DSDFR_FAST_EXACT_MATH=1" : "-DSDFR_SAFE_MATH=1";
-	const std::string sharp_lanes = "-DSDFR_MESH_SHARP_LANES=" + std::to_string(SDFR_MESH_SHARP_LANES); // must match launch_mesh_sharp
+	const std::string sharp_lanes = "-DSDFR_MESH_SHARP_LANES=" + std::to_string(SDFR_MESH_SHARP_LANES); // must match the launch (mesh_sharp_blocks)
 	const char *opts[] = {arch.c_str(), "-std=c++17", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", inc.c_str(), block.c_str(), math, sharp_lanes.c_str()};
 	rc = rtc.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
 	size_t log_bytes = 0;
@@ -238,7 +194,7 @@ JitQueryStatus jit_query_kernels(JitScene &js, int device, const QueryKernels *&
 		hipError_t e = hipModuleLoadData(&m, code.data());
 		for (int kind = 0; kind < QUERY_KERNEL_KINDS; ++kind)
 			for (int dbg = 0; dbg < 2 && e == hipSuccess; ++dbg)
-				e = hipModuleGetFunction(&found.k[kind][dbg].function, m, (std::string(k_query_kernels[kind].symbol) + (dbg ? "_debug" : "")).c_str());
+				e = hipModuleGetFunction(&found.k[kind][dbg].function, m, jit_query_symbol(kind, dbg != 0).c_str());
 		if (e != hipSuccess)
 		{
 			error = std::string("loading the scene's query kernels failed: ") + hipGetErrorString(e);

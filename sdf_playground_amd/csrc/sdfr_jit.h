@@ -1,5 +1,6 @@
 // sdfr_jit.h -- scenes compiled at run time with hiprtc (sdfr_jit.cpp).
 #pragma once
+#include "sdfr_jit_unit.h"
 #include "sdfr_kernels.h"
 
 #include <string>
@@ -19,10 +20,6 @@ struct JitScene
 	hipModule_t query_module = nullptr;
 	QueryKernels query = {};
 };
-
-// the translation unit compiled for a scene: variable macros, the scene text, the kernels (the pixel kernels, or with
-// `query` the query kernels)
-std::string jit_translation_unit(const std::string &scene_source, const std::vector<std::string> &var_slots, bool query = false);
 
 // compile only (no device needed): code object for `arch_name` ("gfx950")
 bool jit_compile_code(const std::string &arch_name, const std::string &name, const std::string &scene_source, const std::vector<std::string> &var_slots,

@@ -48,11 +48,22 @@ struct KernelRef
 // one launch of `blocks` blocks of `threads` threads on `stream`, the kernel's parameters by address
 hipError_t launch_kernel(const KernelRef &k, uint32_t blocks, uint32_t threads, void **args, hipStream_t stream);
 // A scene's query kernels [kind][DBG]: a built-in scene's query unit exports them (sdfr_query_scene.hip), a run-time scene's
-// query module is looked up into the same table (jit_query_kernels, sdfr_jit.h).  kind: QUERY_KERNEL_* (sdfr_query_args.h)
+// query module is looked up into the same table (jit_query_kernels, sdfr_jit.h).  kind: QUERY_KERNEL_*, a row of the list of
+// sdfr_query_args.h (SDFR_FOR_EACH_QUERY_KERNEL)
 struct QueryKernels
 {
 	KernelRef k[QUERY_KERNEL_KINDS][2];
 };
+// One launch of a scene's query kernel of any kind for U with the kind's arguments, every pointer device memory: `blocks` blocks of one
+// wave.  How many blocks is the kind's plan's to say (sdfr_mesh_plan.h, sdfr_slice_plan.h, sdfr_span_plan.h, sdfr_measure_plan.h,
+// sdfr_atlas_plan.h).
+template <class A>
+hipError_t launch_scene_kernel(const KernelRef &k, const FrameU &U, const A &args, uint32_t blocks, hipStream_t stream)
+{
+	SceneKernelArgs<A> a = {U, args};
+	void *params[] = {&a};
+	return launch_kernel(k, blocks, SDFR_TILE_ITEMS, params, stream);
+}
 // a unit names its getter by its scene's index: scene_kernels_<index>(), scene_query_kernels_<index>()
 #define SDFR_CAT2(a, b) a##b
 #define SDFR_CAT(a, b) SDFR_CAT2(a, b)
@@ -66,22 +77,18 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 // one query by a scene's kernel of q's kind (sdfr_query_plan.h: query_kernel_of) for U, in the launches that header plans: q.n > 0
 // items, every pointer device memory
 hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream);
-// the distance query over a lattice (LatticeArgs) by a scene's lattice kernel for U
-hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const LatticeArgs &g, hipStream_t stream);
-uint32_t query_lattice_blocks(const LatticeArgs &g); // blocks of one wave that cover the lattice in the mapping g.rows selects
 
 // Surface nets over a lattice of distances (sdfr_mesh.h, sdfr_mesh.hip), every pointer device memory.  launch_mesh_count: the vertex
 // flag per cell and the quad count per lattice point, then their exclusive prefix sums in place -- cell_vertex [cells + 1] and
 // point_quad [points + 1], whose last elements are the totals; sums: mesh_scan_sum_words(cells + 1) + mesh_scan_sum_words(points + 1)
 // words of scratch.  launch_mesh_emit: positions [vertices][3] and, unless null (no quads), indices [2 * quads][3]; cells_only: instead of
-// a vertex, its cell's linear index as the bits of its first word, for launch_mesh_sharp -- a scene's sharp-vertex kernel
-// (QUERY_KERNEL_MESH_SHARP) for U, which makes the vertices of sdfr_mesh_extract_sharp from them (sdfr_mesh_sharp.h).
+// a vertex, its cell's linear index as the bits of its first word, for a scene's sharp-vertex kernel (QUERY_KERNEL_MESH_SHARP), which
+// makes the vertices of sdfr_mesh_extract_sharp from them (sdfr_mesh_sharp.h).
 struct MeshGrid;
 size_t mesh_scan_sum_words(size_t n);
 hipError_t launch_mesh_count(const MeshGrid &g, const float *lattice, uint32_t *cell_vertex, uint32_t *point_quad, uint32_t *sums, hipStream_t stream);
 hipError_t launch_mesh_emit(const MeshGrid &g, const float *lattice, const uint32_t *cell_vertex, const uint32_t *point_quad, float *positions,
 	uint32_t *indices, bool cells_only, hipStream_t stream);
-hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshSharpArgs &m, hipStream_t stream);
 // data [n] -> its exclusive prefix sum, in place, by the launches launch_mesh_count makes (k_mesh_scan_*); sums: mesh_scan_sum_words(n) words
 void launch_mesh_scan(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream);
 // What the lattice holds (sdfr_mesh_survey.h; sdfr_mesh_survey): out, MESH_SURVEY_WORK_BYTES of device memory, is the survey of g, near
@@ -89,38 +96,29 @@ void launch_mesh_scan(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t st
 struct MeshSurvey;
 hipError_t launch_mesh_survey(const MeshGrid &g, const float *lattice, float band, MeshSurvey *out, hipStream_t stream);
 
-// Marching squares over a stack of plane lattices (sdfr_slice.h, sdfr_slice.hip; sdfr_slice_extract), every pointer device memory.
-// launch_query_slices: the distance query over the stack (SliceArgs) by a scene's slice kernel (QUERY_KERNEL_SLICES) for U, in
-// `blocks` blocks of one wave (sdfr_slice_plan.h: slice_sample_blocks).  launch_slice_count: the vertex count and the segment count per
-// lattice point, then their exclusive prefix sums in place -- point_vertex and cell_segment [points + 1], whose last elements are the
-// totals; sums: 2 * mesh_scan_sum_words(points + 1) words of scratch -- and layer_offsets [2][layers + 1], the first vertex and the first
+// Marching squares over a stack of plane lattices (sdfr_slice.h, sdfr_slice.hip; sdfr_slice_extract), every pointer device memory; the
+// lattices are a scene's slice kernel's (QUERY_KERNEL_SLICES).  launch_slice_count: the vertex count and the segment count per lattice
+// point, then their exclusive prefix sums in place -- point_vertex and cell_segment [points + 1], whose last elements are the totals; sums: 2 * mesh_scan_sum_words(points + 1) words of scratch -- and layer_offsets [2][layers + 1], the first vertex and the first
 // segment of every layer with the totals after the last.  launch_slice_emit: positions [vertices][3], coords [vertices][2] unless null,
 // and unless null (no segments) segments [segments][2].
 struct SliceGrid;
-hipError_t launch_query_slices(const KernelRef &k, const FrameU &U, const SliceArgs &g, uint32_t blocks, hipStream_t stream);
 hipError_t launch_slice_count(const SliceGrid &g, const float *lattice, uint32_t *point_vertex, uint32_t *cell_segment, uint32_t *sums, uint32_t *layer_offsets,
 	hipStream_t stream);
 hipError_t launch_slice_emit(const SliceGrid &g, const float *lattice, const uint32_t *point_vertex, const uint32_t *cell_segment, float *positions, float *coords,
 	uint32_t *segments, hipStream_t stream);
 
-// The span queries (sdfr_span.h; the plan: sdfr_span_plan.h): a scene's span kernel (QUERY_KERNEL_SPANS) for U over the items of `s`, every
-// pointer device memory, in `blocks` blocks of one wave (span_blocks).
-hipError_t launch_query_spans(const KernelRef &k, const FrameU &U, const SpanArgs &s, uint32_t blocks, hipStream_t stream);
-
 // The measure (sdfr_measure.h; the plan: sdfr_measure_plan.h), every pointer device memory.  launch_measure_init: the tally's words
-// (MEASURE_TALLY_BYTES) set for a grid of nu x nv columns.  launch_query_measure: a scene's measure kernel (QUERY_KERNEL_MEASURE) for U,
-// `blocks` blocks of one wave, one per 8 x 8 tile of columns -> g.partials, the tally, g.columns unless null.  launch_measure_reduce: the
+// (MEASURE_TALLY_BYTES) set for a grid of nu x nv columns.  Then a scene's measure kernel (QUERY_KERNEL_MEASURE), a block per 8 x 8 tile
+// of columns -> MeasureArgs::partials, the tally, the columns unless null.  launch_measure_reduce: the
 // passes of k_measure_reduce -- pass k reads pass_records[k] records of ten doubles from partials[k % 2] and writes a 64th as many, rounded
 // up, into the other -- and then the packed result (sdfr_measure_result) at the start of the tally.
 hipError_t launch_measure_init(void *tally, int32_t nu, int32_t nv, hipStream_t stream);
-hipError_t launch_query_measure(const KernelRef &k, const FrameU &U, const MeasureArgs &g, uint32_t blocks, hipStream_t stream);
 hipError_t launch_measure_reduce(double *const partials[2], const uint32_t *pass_records, int passes, void *tally, hipStream_t stream);
 
 // The texture atlas of a mesh (sdfr_atlas.h; the plan: sdfr_atlas_plan.h), every pointer device memory, `blocks` blocks of one wave, one
 // per 8 x 8 square of the image.  launch_atlas_texels: the scene-free kernel -- the texels' points and normals, or with g's planes
-// instead the image of a bake without quads.  launch_atlas_bake: a scene's bake kernel (QUERY_KERNEL_ATLAS) for U.
+// instead the image of a bake without quads.  Any other bake is a scene's bake kernel's (QUERY_KERNEL_ATLAS).
 hipError_t launch_atlas_texels(const AtlasArgs &g, uint32_t blocks, hipStream_t stream);
-hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream);
 
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,
 	int priv_period, hipStream_t stream);

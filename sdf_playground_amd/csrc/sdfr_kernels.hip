@@ -469,78 +469,13 @@ hipError_t launch_wavefront_schedule(int scene, const FrameU &U, const RowMap &r
 static_assert(QUERY_BLOCK_ITEMS == SDFR_PIXEL_BLOCK, "the query kernels are one wave per block");
 hipError_t launch_query(const KernelRef &k, const FrameU &U, const QueryArgs &q, hipStream_t stream)
 {
-	QueryKernelArgs a;
-	a.U = U;
-	void *args[] = {&a};
 	for (uint32_t i = 0, n = query_launch_count(q); i < n; ++i)
 	{
 		const QueryLaunch l = query_launch(q, U.width, U.height, i);
-		a.q = query_launch_args(q, l);
-		const hipError_t e = launch_kernel(k, l.blocks, QUERY_BLOCK_ITEMS, args, stream);
+		const hipError_t e = launch_scene_kernel(k, U, query_launch_args(q, l), l.blocks, stream);
 		if (e != hipSuccess) return e;
 	}
 	return hipSuccess;
-}
-
-uint32_t query_lattice_blocks(const LatticeArgs &g)
-{
-	const uint32_t px = (uint32_t)g.px, py = (uint32_t)g.py, pz = (uint32_t)g.pz;
-	return g.rows ? (px * py * pz + 63u) / 64u : ((px + 3u) / 4u) * ((py + 3u) / 4u) * ((pz + 3u) / 4u);
-}
-
-hipError_t launch_query_lattice(const KernelRef &k, const FrameU &U, const LatticeArgs &g, hipStream_t stream)
-{
-	LatticeKernelArgs a;
-	a.U = U;
-	a.g = g;
-	void *args[] = {&a};
-	return launch_kernel(k, query_lattice_blocks(g), SDFR_PIXEL_BLOCK, args, stream);
-}
-
-hipError_t launch_mesh_sharp(const KernelRef &k, const FrameU &U, const MeshSharpArgs &m, hipStream_t stream)
-{
-	MeshSharpKernelArgs a;
-	a.U = U;
-	a.m = m;
-	void *args[] = {&a};
-	const uint32_t per_block = (uint32_t)SDFR_PIXEL_BLOCK / SDFR_MESH_SHARP_LANES; // vertices of a block
-	return launch_kernel(k, (m.vertices + per_block - 1u) / per_block, SDFR_PIXEL_BLOCK, args, stream);
-}
-
-hipError_t launch_query_slices(const KernelRef &k, const FrameU &U, const SliceArgs &g, uint32_t blocks, hipStream_t stream)
-{
-	SliceKernelArgs a;
-	a.U = U;
-	a.g = g;
-	void *args[] = {&a};
-	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
-}
-
-hipError_t launch_query_spans(const KernelRef &k, const FrameU &U, const SpanArgs &s, uint32_t blocks, hipStream_t stream)
-{
-	SpanKernelArgs a;
-	a.U = U;
-	a.s = s;
-	void *args[] = {&a};
-	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
-}
-
-hipError_t launch_query_measure(const KernelRef &k, const FrameU &U, const MeasureArgs &g, uint32_t blocks, hipStream_t stream)
-{
-	MeasureKernelArgs a;
-	a.U = U;
-	a.g = g;
-	void *args[] = {&a};
-	return launch_kernel(k, blocks, SDFR_PIXEL_BLOCK, args, stream);
-}
-
-hipError_t launch_atlas_bake(const KernelRef &k, const FrameU &U, const AtlasArgs &g, uint32_t blocks, hipStream_t stream)
-{
-	AtlasKernelArgs a;
-	a.U = U;
-	a.g = g;
-	void *args[] = {&a};
-	return launch_kernel(k, blocks, QUERY_BLOCK_ITEMS, args, stream);
 }
 
 hipError_t launch_assemble_strips(int width, int height, int world, const void *gathered, void *out_image, int format, int priv_count,

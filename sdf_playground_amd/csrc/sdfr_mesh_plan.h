@@ -40,6 +40,18 @@ inline LatticeArgs mesh_lattice_args(const MeshGrid &g)
 	la.pz = g.n[2] + 1;
 	return la;
 }
+// blocks of one wave that cover the lattice in the mapping g.rows selects: 4 x 4 x 4 bricks of points, or runs of 64
+inline uint32_t query_lattice_blocks(const LatticeArgs &g)
+{
+	const uint32_t px = (uint32_t)g.px, py = (uint32_t)g.py, pz = (uint32_t)g.pz;
+	return g.rows ? (px * py * pz + 63u) / 64u : ((px + 3u) / 4u) * ((py + 3u) / 4u) * ((pz + 3u) / 4u);
+}
+// ... and the sharp-vertex launch's: 64 / SDFR_MESH_SHARP_LANES vertices per block of one wave
+inline uint32_t mesh_sharp_blocks(uint32_t vertices)
+{
+	const uint32_t per_block = (uint32_t)QUERY_BLOCK_ITEMS / SDFR_MESH_SHARP_LANES;
+	return (vertices + per_block - 1u) / per_block;
+}
 
 // The checks after the handle's and before the scene's, in the order their errors win.
 inline MeshPlan plan_mesh(const MeshRequest &c)

@@ -10,55 +10,8 @@
 namespace sdfr {
 
 // QueryArgs, what one query launch reads and writes: sdfr_query_args.h; which of its arrays each kind of item takes, and how the
-// kinds are launched: the table of sdfr_query_plan.h
-// what a query kernel takes: one argument, as the pixel kernels (PixelKernelArgs)
-struct QueryKernelArgs
-{
-	FrameU U;
-	QueryArgs q;
-};
-
-// ... and a lattice kernel (LatticeArgs: sdfr_query_args.h)
-struct LatticeKernelArgs
-{
-	FrameU U;
-	LatticeArgs g;
-};
-
-// ... and the atlas bake kernel (AtlasArgs: sdfr_query_args.h)
-struct AtlasKernelArgs
-{
-	FrameU U;
-	AtlasArgs g;
-};
-
-// ... and the sharp-vertex kernel (MeshSharpArgs: sdfr_query_args.h)
-struct MeshSharpKernelArgs
-{
-	FrameU U;
-	MeshSharpArgs m;
-};
-
-// ... and the slice kernel (SliceArgs: sdfr_query_args.h)
-struct SliceKernelArgs
-{
-	FrameU U;
-	SliceArgs g;
-};
-
-// ... and the span kernel (SpanArgs: sdfr_query_args.h)
-struct SpanKernelArgs
-{
-	FrameU U;
-	SpanArgs s;
-};
-
-// ... and the measure kernel (MeasureArgs: sdfr_query_args.h)
-struct MeasureKernelArgs
-{
-	FrameU U;
-	MeasureArgs g;
-};
+// kinds are launched: the table of sdfr_query_plan.h.  What a query kernel takes is one argument, as the pixel kernels:
+// SceneKernelArgs<the kind's arguments> (sdfr_frame.h)
 
 // the driver's normal at pos (pshader_sdf.hlsl:164-177, 320-330): map_normal with the NormalOutput preloaded {grad_eps, 0, false};
 // its normal if it sets use_normal, else the three forward differences against `baseline`, normalised

@@ -38,10 +38,27 @@ static_assert(__builtin_offsetof(QueryArgs, distance) == 40 && __builtin_offseto
 static_assert(__builtin_offsetof(QueryArgs, surfaces) == 64 && __builtin_offsetof(QueryArgs, hit_items) == 72 && __builtin_offsetof(QueryArgs, occlusion) == 80, "");
 static_assert(__builtin_offsetof(QueryArgs, bias) == 88 && __builtin_offsetof(QueryArgs, lighting) == 96 && __builtin_offsetof(QueryArgs, lights) == 104, "");
 
-// A scene's query kernels by kind (QueryKernels, sdfr_kernels.h); rays: picks too; surfaces and lighting: the ray kinds when those records are asked for
-enum { QUERY_KERNEL_POINTS = 0, QUERY_KERNEL_RAYS = 1, QUERY_KERNEL_LATTICE = 2, QUERY_KERNEL_SURFACES = 3, QUERY_KERNEL_OCCLUSION = 4, QUERY_KERNEL_LIGHTING = 5, QUERY_KERNEL_ATLAS = 6, QUERY_KERNEL_MESH_SHARP = 7, QUERY_KERNEL_SLICES = 8, QUERY_KERNEL_SPANS = 9, QUERY_KERNEL_MEASURE = 10, QUERY_KERNEL_KINDS = 11 };
+// A scene's query kernels by kind, the one list of them: X(kind, stem of the kernel's name, body template of sdfr_query_kernel.h, its
+// arguments).  Kind QUERY_KERNEL_<kind> is the row's place in the list.  A built-in scene's unit names the kernel k_<stem>
+// (sdfr_query_scene.hip), a run-time scene's query module sdfr_jit_<stem> (sdfr_jit_unit.h); both take SceneKernelArgs<arguments>
+// (sdfr_frame.h).  rays: picks too; surfaces and lighting: the ray kinds when those records are asked for.  A new kind goes last.
+#define SDFR_FOR_EACH_QUERY_KERNEL(X) \
+	X(POINTS, query_points, query_points_kernel, QueryArgs) \
+	X(RAYS, query_rays, query_rays_kernel, QueryArgs) \
+	X(LATTICE, query_lattice, query_lattice_kernel, LatticeArgs) \
+	X(SURFACES, query_surfaces, query_surfaces_kernel, QueryArgs) \
+	X(OCCLUSION, query_occlusion, query_occlusion_kernel, QueryArgs) \
+	X(LIGHTING, query_lighting, query_lighting_kernel, QueryArgs) \
+	X(ATLAS, bake_atlas, atlas_bake_kernel, AtlasArgs) \
+	X(MESH_SHARP, mesh_sharp, mesh_sharp_kernel, MeshSharpArgs) \
+	X(SLICES, query_slices, query_slices_kernel, SliceArgs) \
+	X(SPANS, query_spans, query_spans_kernel, SpanArgs) \
+	X(MEASURE, query_measure, query_measure_kernel, MeasureArgs)
+#define SDFR_QUERY_KERNEL_ENUM(kind, stem, body, args) QUERY_KERNEL_##kind,
+enum { SDFR_FOR_EACH_QUERY_KERNEL(SDFR_QUERY_KERNEL_ENUM) QUERY_KERNEL_KINDS };
+#undef SDFR_QUERY_KERNEL_ENUM
 
-// One lattice launch (sdfr_kernels.h: launch_query_lattice; sdfr_mesh_extract): the distance query at the points of a regular lattice,
+// One lattice launch (sample_lattice, sdfr_api.cpp; sdfr_mesh_extract): the distance query at the points of a regular lattice,
 // computed from their indices -- point (i, j, k) is origin + (float)index * cell per axis, one multiply then one add -- into
 // out[i + px * (j + py * k)].  px * py * pz <= 2^30.
 struct LatticeArgs
@@ -52,6 +69,7 @@ struct LatticeArgs
 	int32_t rows;       // 0: a wave owns a 4 x 4 x 4 brick of points; 1: 64 consecutive points of a row (the A/B of DESIGN.md 4.6)
 	float *out;
 };
+static_assert(sizeof(LatticeArgs) == 40 && __builtin_offsetof(LatticeArgs, px) == 16 && __builtin_offsetof(LatticeArgs, out) == 32, "LatticeArgs is a kernel argument");
 
 // One launch of the sharp vertices (sdfr_mesh_sharp.h; sdfr_mesh_extract_sharp): the grid, field for field MeshGrid's, the lattice of its
 // distances, and positions [vertices][3], whose word 3 * v holds vertex v's cell index when the kernel starts and which it overwrites.
@@ -71,6 +89,7 @@ struct MeshSharpArgs
 	float *positions;
 	uint32_t vertices;
 };
+static_assert(sizeof(MeshSharpArgs) == 56 && __builtin_offsetof(MeshSharpArgs, lattice) == 32 && __builtin_offsetof(MeshSharpArgs, vertices) == 48, "MeshSharpArgs is a kernel argument");
 
 // One atlas launch (sdfr_atlas.h, sdfr_atlas_plan.h; sdfr_atlas_texels and sdfr_atlas_bake): the texels of a width x height image cut into
 // square tiles of 1 << tile_log2 texels, tile q = row * tiles_per_row + col the quad of triangles 2q and 2q + 1 of `indices`.  A wave
@@ -90,9 +109,9 @@ struct AtlasArgs
 	int32_t *valid;               // [height * width]
 	float *texel_positions, *texel_normals; // [height * width][3] each
 };
+static_assert(sizeof(AtlasArgs) == 104 && __builtin_offsetof(AtlasArgs, vertex_count) == 24 && __builtin_offsetof(AtlasArgs, albedo) == 56 && __builtin_offsetof(AtlasArgs, valid) == 80, "AtlasArgs is a kernel argument");
 
-// One slice launch (sdfr_kernels.h: launch_query_slices; sdfr_slice_extract): the distance query at the points of a stack of plane
-// lattices, computed from their indices -- point (i, j) of layer l is ((origin + (float)i * du) + (float)j * dv) + (float)l * dw per
+// One slice launch (sdfr_slice_extract): the distance query at the points of a stack of plane lattices, computed from their indices -- point (i, j) of layer l is ((origin + (float)i * du) + (float)j * dv) + (float)l * dw per
 // component, every operation separate (sdfr_slice.h: slice_coord) -- into out[i + pu * (j + pv * l)].  pu * pv * layers <= 2^30.
 struct SliceArgs
 {
@@ -105,7 +124,7 @@ struct SliceArgs
 static_assert(sizeof(SliceArgs) == 72 && __builtin_offsetof(SliceArgs, du) == 12 && __builtin_offsetof(SliceArgs, dw) == 36 && __builtin_offsetof(SliceArgs, pu) == 48, "");
 static_assert(__builtin_offsetof(SliceArgs, rows) == 60 && __builtin_offsetof(SliceArgs, out) == 64, "SliceArgs is a kernel argument");
 
-// One span launch (sdfr_kernels.h: launch_query_spans; sdfr_query_ray_spans, sdfr_pick_spans, sdfr_mesh_spans): the intervals of each item's
+// One span launch (sdfr_query_ray_spans, sdfr_pick_spans, sdfr_mesh_spans): the intervals of each item's
 // ray that lie inside the solid (sdfr_span.h).  kind: QUERY_RAYS (pos, dir), QUERY_PICK (pixels), QUERY_FRAME (every pixel of the frame,
 // n = width * height, a wave per 8 x 8 tile) or QUERY_MESH (pos, dir = positions, normals; reach); every other input is null.
 // summaries: 8 words per item, the layout of sdfr_span_summary; spans: [n][max_spans][2] floats, null if max_spans = 0.
@@ -126,7 +145,7 @@ static_assert(__builtin_offsetof(SpanArgs, pixels) == 24 && __builtin_offsetof(S
 static_assert(__builtin_offsetof(SpanArgs, iso) == 44 && __builtin_offsetof(SpanArgs, max_steps) == 48 && __builtin_offsetof(SpanArgs, max_spans) == 52, "");
 static_assert(__builtin_offsetof(SpanArgs, summaries) == 56 && __builtin_offsetof(SpanArgs, spans) == 64, "SpanArgs is a kernel argument");
 
-// One measure launch (sdfr_kernels.h: launch_query_measure; sdfr_measure): the moments of the solid over nu x nv parallel columns
+// One measure launch (sdfr_measure): the moments of the solid over nu x nv parallel columns
 // (sdfr_measure.h), a wave per 8 x 8 tile of columns.  Column (i, j) starts at (origin + (float)i * du) + (float)j * dv per component and
 // runs along dw.  partials: 10 doubles per tile, tiles row-major; columns: 10 words per column, the layout of sdfr_measure_column, row-major
 // i + nu * j, or null; tally: the words the integer totals are counted in (MEASURE_TALLY_*).  nu, nv <= 8192, nu * nv <= 2^24.

@@ -46,10 +46,10 @@ __device__ __forceinline__ void query_store(uint32_t *__restrict__ base, uint32_
 }
 
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_points_kernel(const QueryKernelArgs &a)
+__device__ __forceinline__ void query_points_kernel(const SceneKernelArgs<QueryArgs> &a)
 {
 	const FrameU &U = a.U;
-	const QueryArgs &q = a.q;
+	const QueryArgs &q = a.a;
 	const uint32_t i = blockIdx.x * (uint32_t)SDFR_PIXEL_BLOCK + threadIdx.x;
 	if (i >= (uint32_t)q.n) return;
 	const vec3 p = query_load3(q.pos, i);
@@ -66,10 +66,10 @@ __device__ __forceinline__ void query_points_kernel(const QueryKernelArgs &a)
 }
 
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_rays_kernel(const QueryKernelArgs &a)
+__device__ __forceinline__ void query_rays_kernel(const SceneKernelArgs<QueryArgs> &a)
 {
 	const FrameU &U = a.U;
-	const QueryArgs &q = a.q;
+	const QueryArgs &q = a.a;
 	const uint32_t i = blockIdx.x * (uint32_t)SDFR_PIXEL_BLOCK + threadIdx.x;
 	if (i >= (uint32_t)q.n) return;
 	uint32_t rec[QUERY_HIT_WORDS];
@@ -88,11 +88,11 @@ __device__ __forceinline__ void query_rays_kernel(const QueryKernelArgs &a)
 // wave-level branches stay as coherent as in a render; lanes past the frame's ragged right and bottom edges leave.  Every other
 // kind maps 64 consecutive items.  A record is one whole 128-byte line per lane, built in registers and written by eight 16-byte stores.
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_surfaces_kernel(const QueryKernelArgs &a)
+__device__ __forceinline__ void query_surfaces_kernel(const SceneKernelArgs<QueryArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 pixels");
 	const FrameU &U = a.U;
-	const QueryArgs &q = a.q;
+	const QueryArgs &q = a.a;
 	const uint32_t lane = threadIdx.x;
 	uint32_t i;
 	QueryRay ray;
@@ -150,12 +150,12 @@ struct LightSampleStore
 	}
 };
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_lighting_kernel(const QueryKernelArgs &a)
+__device__ __forceinline__ void query_lighting_kernel(const SceneKernelArgs<QueryArgs> &a)
 {
 	static_assert(QUERY_LIGHT_SLOTS == SDFR_MAX_LIGHTS && QUERY_LIGHT_SAMPLE_WORDS % 4 == 0, "eight samples of whole 16-byte pieces per item");
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 pixels");
 	const FrameU &U = a.U;
-	const QueryArgs &q = a.q;
+	const QueryArgs &q = a.a;
 	const uint32_t lane = threadIdx.x;
 	uint32_t i;
 	QueryRay ray;
@@ -195,11 +195,11 @@ __device__ __forceinline__ void query_lighting_kernel(const QueryKernelArgs &a)
 // branches start coherent; a lane whose ray has ended waits for the slowest and does nothing else: neither the normal nor the
 // material of a hit is computed.  The mask is one ballot of the hit flags, and one lane writes the 16-byte record.
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_occlusion_kernel(const QueryKernelArgs &a)
+__device__ __forceinline__ void query_occlusion_kernel(const SceneKernelArgs<QueryArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64 && OCCLUSION_DIRS == 64, "one wave per block, one lane per direction");
 	const FrameU &U = a.U;
-	const QueryArgs &q = a.q;
+	const QueryArgs &q = a.a;
 	const uint32_t i = blockIdx.x, lane = threadIdx.x; // (launch_query: q.n blocks)
 	vec3 p, n;
 	uint32_t valid = 1u;
@@ -234,10 +234,10 @@ __device__ __forceinline__ void query_occlusion_kernel(const QueryKernelArgs &a)
 // coherent; its stores are runs of 4 floats.  rows = 1 maps 64 consecutive points of the linear index instead (coalesced stores,
 // a wave 64 cells long).  Lanes past the lattice's ragged edges leave.
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_lattice_kernel(const LatticeKernelArgs &a)
+__device__ __forceinline__ void query_lattice_kernel(const SceneKernelArgs<LatticeArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a brick is 64 points");
-	const LatticeArgs &g = a.g;
+	const LatticeArgs &g = a.a;
 	const uint32_t px = (uint32_t)g.px, py = (uint32_t)g.py, pz = (uint32_t)g.pz, lane = threadIdx.x;
 	uint32_t i, j, k;
 	if (g.rows)
@@ -269,11 +269,11 @@ __device__ __forceinline__ void query_lattice_kernel(const LatticeKernelArgs &a)
 // leaves as one 16-byte store per lane -- a wave's row of 8 texels is 128 contiguous bytes -- and `valid` as one word, at every texel
 // of the image.  Nothing here is shared with the kernels above: their code stays as it was.
 template <class Scene, bool DBG>
-__device__ __forceinline__ void atlas_bake_kernel(const AtlasKernelArgs &a)
+__device__ __forceinline__ void atlas_bake_kernel(const SceneKernelArgs<AtlasArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: 8 x 8 texels");
 	const FrameU &U = a.U;
-	const AtlasArgs &g = a.g;
+	const AtlasArgs &g = a.a;
 	const uint32_t lane = threadIdx.x;
 	const uint32_t blocks_x = (uint32_t)g.width >> 3;
 	const uint32_t by = blockIdx.x / blocks_x, bx = blockIdx.x - by * blocks_x;
@@ -311,10 +311,10 @@ struct MeshSharpScene
 	__device__ __forceinline__ float distance_normal(vec3 p, vec3 &n) const { return query_point<Scene, DBG>(U, p, &n); }
 };
 template <class Scene, bool DBG, int LANES = SDFR_MESH_SHARP_LANES>
-__device__ __forceinline__ void mesh_sharp_kernel(const MeshSharpKernelArgs &a)
+__device__ __forceinline__ void mesh_sharp_kernel(const SceneKernelArgs<MeshSharpArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64 && (LANES == 16 || LANES == 1), "one wave per block: 4 vertices of 16 lanes, or 64 of one");
-	const MeshSharpArgs &m = a.m;
+	const MeshSharpArgs &m = a.a;
 	MeshGrid g;
 	for (int k = 0; k < 3; ++k)
 	{
@@ -376,10 +376,10 @@ __device__ __forceinline__ void mesh_sharp_kernel(const MeshSharpKernelArgs &a)
 // The tile is addressed by the block index alone (scalar arithmetic).  rows = 1 maps 64 consecutive points of the linear index instead.
 // Nothing is read but the kernel's arguments; every lane writes its own 4 bytes; lanes past a layer's ragged edges leave.
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_slices_kernel(const SliceKernelArgs &a)
+__device__ __forceinline__ void query_slices_kernel(const SceneKernelArgs<SliceArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 points");
-	const SliceArgs &g = a.g;
+	const SliceArgs &g = a.a;
 	const uint32_t pu = (uint32_t)g.pu, pv = (uint32_t)g.pv, layers = (uint32_t)g.layers, lane = threadIdx.x;
 	uint32_t i, j, l;
 	if (g.rows)
@@ -448,11 +448,11 @@ struct SpanStore
 	}
 };
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_spans_kernel(const SpanKernelArgs &a)
+__device__ __forceinline__ void query_spans_kernel(const SceneKernelArgs<SpanArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 pixels");
 	const FrameU &U = a.U;
-	const SpanArgs &s = a.s;
+	const SpanArgs &s = a.a;
 	const uint32_t lane = threadIdx.x;
 	uint32_t i;
 	QueryRay ray;
@@ -545,11 +545,11 @@ __device__ __forceinline__ int measure_wave_max(int v)
 	return v;
 }
 template <class Scene, bool DBG>
-__device__ __forceinline__ void query_measure_kernel(const MeasureKernelArgs &a)
+__device__ __forceinline__ void query_measure_kernel(const SceneKernelArgs<MeasureArgs> &a)
 {
 	static_assert(SDFR_PIXEL_BLOCK == 64, "one wave per block: a tile is 64 columns");
 	const FrameU &U = a.U;
-	const MeasureArgs &g = a.g;
+	const MeasureArgs &g = a.a;
 	const uint32_t lane = threadIdx.x;
 	const uint32_t tu = ((uint32_t)g.nu + 7u) >> 3;
 	const uint32_t tj = blockIdx.x / tu, ti = blockIdx.x - tj * tu;

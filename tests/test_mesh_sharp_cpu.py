@@ -12,6 +12,7 @@ import pytest
 
 import mesh_sharp_util as su
 import mesh_util as mu
+import query_kernels_util as ku
 import query_util as qu
 
 ORIGIN, CELL, DIMS = su.GRID
@@ -224,7 +225,12 @@ def test_a_run_time_scene_compiles_with_the_sharp_kernel():
     import sdf_playground_amd as sp
 
     csrc = os.path.join(ROOT, "sdf_playground_amd", "csrc")
-    assert '"sdfr_jit_mesh_sharp", "mesh_sharp_kernel", "MeshSharpKernelArgs"' in open(os.path.join(csrc, "sdfr_jit.cpp")).read()
+    # the kind's row, and its two kernels in the query unit of a run-time scene (tests/cpp/query_kernels_host.cpp)
+    rep = ku.report()
+    row, = [r for r in rep.rows if r.name == "MESH_SHARP"]
+    assert (row.stem, row.body, row.args) == ("mesh_sharp", "mesh_sharp_kernel", "MeshSharpArgs")
+    for symbol, dbg in (("sdfr_jit_mesh_sharp", "false"), ("sdfr_jit_mesh_sharp_debug", "true")):
+        assert 'void %s(SceneKernelArgs<MeshSharpArgs> a) { mesh_sharp_kernel<Scene, %s>(a); }' % (symbol, dbg) in "\n".join(rep.query)
     assert "mesh_sharp_kernel" in open(os.path.join(csrc, "sdfr_query_kernel.h")).read()
     ok, log = sp.check_scene_source(os.path.join(qu.SCENES_DIR, "pendulum.scene.h"))
     assert ok, log
