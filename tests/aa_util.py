@@ -145,10 +145,10 @@ def host_resolve(s, st, width, height, factor, budget, fmt, canary=None):
 # ---- frames -----------------------------------------------------------------------------------------------------------------------
 
 def camera_of(oracle, scene):
-    """the camera tests/test_gpu_parity.py gives the scene: (kind, eye, target, fovy, aspect, basis)"""
-    import test_gpu_parity as par
+    """the camera the parity tests give the scene (gpu_util.parity_cameras): (kind, eye, target, fovy, aspect, basis)"""
+    import gpu_util as gu
 
-    cams, fovy, asp = par._cameras(oracle)
+    cams, fovy, asp = gu.parity_cameras()
     kind, eye, tgt = cams[scene]
     basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, tgt, fovy, asp)
     return kind, eye, tgt, fovy, asp, basis

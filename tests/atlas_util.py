@@ -15,8 +15,8 @@ import surface_util as su
 ALBEDO, NORMAL, LIT = 1, 2, 4
 LAYER_NAMES = {ALBEDO: "albedo", NORMAL: "normal", LIT: "lit"}
 ONE = np.float32(1.0).view(np.uint32)
-# the meshes of tests/test_lighting_cpu.py::MESHES, built as that file builds them: stime, origin, cell, dims
-MESHES = {"fast_sphere": (0.0, (-1.55, -0.3, -1.55), 0.13, (24, 23, 25)), "debug_materials": (0.4, (-2.05, -0.3, -1.55), 0.17, (24, 23, 25))}
+# the meshes of the lighting tests, built as tests/test_lighting_cpu.py builds them: stime, origin, cell, dims
+MESHES = lu.MESHES
 W, H = 64, 48
 
 _oracle = []

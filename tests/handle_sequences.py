@@ -43,6 +43,10 @@ SCENE_VARS = {
 
 SCHEDULES = ("pixel", "wavefront")
 LAUNCH_MODES = ("auto", "per_tile", "persistent")
+SCHEDULE = {"wavefront": 0, "pixel": 1}                  # the library's values of the names above
+LAUNCH = {"auto": 0, "per_tile": 1, "persistent": 2}
+NAN32 = 0x7FC0DEAD  # what a GPU test fills its buffers with: a quiet NaN with a payload no render produces
+NAN16 = 0x7E5A
 WORLDS = (2, 3, 8)
 SPLITS = ((1, 2), (1, 3), (2, 5), (3, 4), (1, 8))
 RGBA32F, RGBA16F, STRIP_RGB32F_A8, STRIP_RGB16F_A8 = 0, 1, 2, 3
@@ -52,6 +56,11 @@ MAX_FAILED = 5
 
 SEEDS = (1, 45, 60)  # the committed seeds (what they cover: tests/test_handle_sequences_cpu.py)
 STEPS = 56
+
+
+def limits(name):
+    """the full limits of the setting `name`"""
+    return dict(DEFAULT_LIMITS, **LIMITS[name])
 
 
 def camera(scene, t):

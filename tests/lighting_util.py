@@ -161,3 +161,50 @@ def pixel_conditions(surfaces, g, bounce_count, ray_count):
     one_segment = g[:, 11].astype(np.int64) == traced
     budget = (1 + traced <= bounce_count) & (1 + traced <= ray_count)
     return spawns_nothing_else(surfaces, g) & one_segment & budget
+
+
+# ---- the cases the CPU and the GPU tier share --------------------------------------------------------------------------------------
+W, H = 64, 48
+# the meshes of tests/test_gpu_surface.py: stime, origin, cell, dims
+MESHES = {"fast_sphere": (0.0, (-1.55, -0.3, -1.55), 0.13, (24, 23, 25)), "debug_materials": (0.4, (-2.05, -0.3, -1.55), 0.17, (24, 23, 25))}
+
+
+def frame_limits(of):
+    """the limits the lighting and atlas tests move, as the oracle frame `of` has them: gpu_util.setup's `limits`"""
+    return dict(light_count=of.light_count, max_cost_default=of.max_cost_default, extension_lights=of.extension_lights,
+                extension_marble_reflection=of.extension_marble_reflection)
+
+
+# the frames on which `lit` is pinned against the driver itself (orc::ps_main's rgb on the CPU, the renderer's pixel on the GPU):
+# scene, stime, frame changes, camera (eye, look-at; None: the start-up camera) -- chosen on the oracle alone.  With all seven extension
+# lights a lit hit starts eight chains, one more than the driver's eight ray slots leave room for beside the primary ray: six here.
+PIXEL_FRAMES = {
+    "basic_transparency": ("basic_transparency", 0.5, {}, ((-5.0, 6.0, 2.0), (0.0, 0.0, 0.0))),
+    "light_shadows": ("light_shadows", 0.5, {}, None),
+    "gems, extension lights": ("gems", 0.5, {"extension_lights": 6}, None),
+    "labyrinth, extension lights": ("labyrinth", 0.5, {"extension_lights": 3}, None),
+}
+
+
+def pixel_frame(key):
+    scene, stime, changes, camera = PIXEL_FRAMES[key]
+    of = qu.frame(scene, stime, W, H)
+    if camera:
+        fovy = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
+        basis = qu.po.camera_lookat(camera[0], camera[1], fovy, np.float32(W) / np.float32(H))
+        for i in range(3):
+            of.eye[i], of.front[i], of.right[i], of.top[i] = basis[0][i], basis[1][i], basis[2][i], basis[3][i]
+    for k, v in changes.items():
+        setattr(of, k, v)
+    return scene, of
+
+
+def pixel_classes(scene, of, g, srf):
+    """(qualifies: the three conditions of include/sdfr.h; single: one chain of any length within the bounce budget, which the driver
+    sums in the same order whatever its length; lit hits)"""
+    ok = pixel_conditions(srf, g, of.bounce_count, of.ray_count)
+    lit_hits = (g[:, 0] == 1) & ((srf[:, 1] & 2) != 0)
+    # the header's wording of the see-through condition and the driver's coincide on these frames: no unlit see-through hit
+    assert not ((srf[:, 3] == 1) & ((srf[:, 1] & 2) == 0) & (f32(srf[:, 7]) < 1)).any()
+    single = spawns_nothing_else(srf, g) & (popcount(g[:, 2]) == 1) & (1 + g[:, 11].astype(np.int64) <= of.bounce_count)
+    return ok, single, lit_hits

@@ -16,6 +16,9 @@ F, D = np.float32, np.float64
 COLUMN_DTYPE = np.dtype([("m0", D), ("m1", D), ("m2", D), ("spans", np.uint32), ("steps", np.uint32), ("flags", np.uint32), ("valid", np.int32)])
 assert COLUMN_DTYPE.itemsize == 40
 INTEGERS = ("columns_hit", "columns_open", "columns_out_of_steps", "columns_invalid", "steps", "spans", "crossings")
+# The restatement against the closed forms of a sphere (tests/test_measure_cpu.py: sphere_errors), per rho / cell: the worst values it gave
+# (recorded in DESIGN.md 4.16), as relative errors of the volume and of I_zz and the centroid's distance in cells
+RECORDED_WORST = {8: (4.8e-3, 1.65e-2, 0.019), 16: (1.14e-3, 4.55e-3, 0.0104), 32: (1.82e-4, 8.83e-4, 0.0045)}
 
 
 def grid(origin, du, dv, dw, nu, nv):

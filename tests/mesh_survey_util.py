@@ -11,6 +11,7 @@ import numpy as np
 import cppbuild
 import mesh_util as mu
 import query_util as qu
+from handle_sequences import DEFAULT_LIMITS
 
 F = np.float32
 EMPTY, FOUND, TOO_LARGE = 0, 1, 2
@@ -236,3 +237,40 @@ FIT_SCENES = {"fast_sphere": (0.0, (-2.0, -0.5, -1.75)), "labyrinth": (1.25, (-5
 def oracle_distance(scene, of):
     """-> distance(origin, cell, dims) by the oracle's definition of the scene"""
     return lambda origin, cell, dims: qu.oracle_points(scene, of, mu.lattice_points(origin, cell, dims), normals=False)[0]
+
+
+# ---- the run-time probe scene of the GPU tier's survey, slice, span and measure tests ----------------------------------------------
+# By `kind` a sphere with its centre and radius in variables, the plane y = height, or that plane with NaN
+# where x > split.  setValue does not clamp, so the ranges below bind nothing.
+PROBE = """struct Scene
+{
+	static SDF_HD void prepare(FrameU &) {}
+	struct RayInv {};
+	static SDF_HD RayInv ray_setup(const FrameU &, vec3, const RayFlags &) { return RayInv(); }
+	static SDF_HD float dist(const FrameU &U, const RayInv &, vec3 p, vec3, bool)
+	{
+		const float kind = VAR_kind(min = 0, max = 2, start = 0);
+		const vec3 c = V3(VAR_cx(min = -100, max = 100, start = 0), VAR_cy(min = -100, max = 100, start = 0), VAR_cz(min = -100, max = 100, start = 0));
+		const float radius = VAR_radius(min = 0, max = 10, start = 1), height = VAR_height(min = -10, max = 10, start = 0.25);
+		const float split = VAR_split(min = -10, max = 10, start = 0.3);
+		if (kind < 0.5f) return sd_sphere(p - c, radius);
+		if (kind > 1.5f && p.x > split) return bits_f32(0x7fc00000u);
+		return p.y - height;
+	}
+	static SDF_HD void material(const FrameU &, const SurfacePoint &, Material &) {}
+	static SDF_HD bool light(const FrameU &, int i, Light &L) { return sun_light(i, L); }
+	static SDF_HD float ambient() { return 0.1f; }
+	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
+};
+"""
+PROBE_DEFAULTS = dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3)
+
+
+def load_probe(r, name, defaults, loaded=None, **values):
+    """the probe scene, compiled as `name` unless it is the handle's scene already (loaded: the caller knows; None: ask the handle),
+    with its variables at `defaults` but for `values`"""
+    if not (r.currentScene() == name if loaded is None else loaded):
+        r.initShaderSource(name, PROBE)
+        r.setLimits(**DEFAULT_LIMITS)
+    for variable, v in dict(defaults, **values).items():
+        assert r.setValue(variable, v)

@@ -10,6 +10,11 @@ import cppbuild
 import query_util as qu
 
 F = np.float32
+# the boxes of the GPU tier's slice and span tests, per scene: time, the low corner (x, z), the cell, the height of layer 0 and the
+# step between layers -- a box the scene's solid crosses in every layer
+CASES = {"fast_sphere": (0.0, (-0.92, -0.72), 0.05, 0.62, 0.17), "labyrinth": (1.25, (-5.35, -2.55), 0.05, 0.37, 0.23),
+         "gyroid": (0.5, (-0.92, -0.72), 0.05, -0.2, 0.23), "sierpinski": (0.5, (-0.75, -0.55), 0.04, 1.02, 0.11),
+         "noise_lod": (0.5, (-0.92, -0.72), 0.05, 0.4, 0.4)}
 
 
 def _f3(v):

@@ -6,17 +6,7 @@ rules at chosen pixels, and the host build of the product's pipeline stages agai
 import numpy as np
 import pytest
 
-W, H = 96, 64
-CAMS = [((0.0, 1.6, -4.2), (0.0, 0.6, 0.0)), ((-3.5, 0.9, -2.0), (-0.6, 0.5, 0.0)), ((0.3, 4.0, -0.8), (0.3, 0.5, 0.0))]
-
-
-def _frame(oracle, cam, iter_count, stime=0.4, **kw):
-    fovy = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
-    f = oracle.default_frame("debug_materials", W, H, basis=oracle.camera_lookat(cam[0], cam[1], fovy, np.float32(W) / np.float32(H)), stime=stime)
-    f.iter_count = iter_count
-    for k, v in kw.items():
-        setattr(f, k, v)
-    return f
+from frame_cases import MATERIALS_CAMS as CAMS, materials_frame as _frame
 
 
 def _heat(it, max_it):

@@ -9,22 +9,14 @@ import numpy as np
 import pytest
 
 import aa_util as au
-from test_gpu_parity import TOL
+from gpu_util import DEFAULT_LIMITS, PARITY_TOL as TOL
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 W, H = au.W, au.H
 SCENES = {"fast_sphere": 0.0, "labyrinth": 1.25, "lense": 1.25}  # scene: time
 RGBA32F, RGBA16F = 0, 1
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 @pytest.fixture(autouse=True)
@@ -41,7 +33,7 @@ def _budget(monkeypatch, width, factor, strips):
 
 
 def _setup(r, oracle, scene, stime):
-    """the scene with the camera tests/test_gpu_parity.py gives it and the reference's limits"""
+    """the scene with the camera the parity tests give it (aa_util.camera_of), the pixel schedule and the reference's limits"""
     import sdf_playground_amd as sp
 
     kind, eye, tgt, fovy, asp, basis = au.camera_of(oracle, scene)
@@ -55,8 +47,7 @@ def _setup(r, oracle, scene, stime):
     r.setCamera(cam)
     assert np.array_equal(r.getCameraBasis().view(np.uint32), basis.view(np.uint32))
     r.setSchedule(sp.SCHEDULE_PIXEL)
-    r.setLimits(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
+    r.setLimits(**DEFAULT_LIMITS)
 
 
 def _own_pyramid(r, width, height, factor):
@@ -266,7 +257,7 @@ def test_postprocess_of_an_anti_aliased_frame(renderer, oracle, monkeypatch):
     """an RGBA16F anti-aliased frame whose alpha takes fractional values -- the share of a pixel's sub-samples that are tone-mapped --
     through sdfr_postprocess, at the bar of tests/test_gpu_post.py: the LDR image byte for byte, the bloom buffer bit for bit"""
     import sdf_playground_amd as sp
-    from test_debug_materials_cpu import CAMS
+    from frame_cases import MATERIALS_CAMS as CAMS
 
     w, h = 64, 40
     renderer.initShader("debug_materials")  # tone-mapped and untone-mapped views side by side

@@ -9,10 +9,12 @@ import numpy as np
 import pytest
 
 import atlas_util as au
+import gpu_util as gu
 import lighting_util as lu
 import query_util as qu
 import surface_util as su
-from test_gpu_lighting import DEFAULT_LIMITS, _setup, _stats
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,27 +22,14 @@ W, H = au.W, au.H
 CASES = [(4, 64), (8, 64), (16, 128)]
 
 
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
+def _setup(r, scene, of):
+    """the handle's state = the oracle frame `of`, with the four limits the tests move taken from it"""
+    gu.setup(r, scene, of, limits=lu.frame_limits(of))
 
 
-def _dev(a, dtype=None):
-    import torch
-
-    a = np.ascontiguousarray(a, dtype)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
-
-
-def _host(baked):
-    import torch
-
-    torch.cuda.synchronize()
-    return {k: (a.cpu().numpy() if hasattr(a, "data_ptr") else a) for k, a in baked.items()}
+def _bake_to_host(baked):
+    """a bake's dictionary with its device tensors as numpy"""
+    return dict(zip(baked, gu.to_host(tuple(baked.values()))))
 
 
 def _assert_texels(what, got, want):
@@ -59,7 +48,7 @@ def test_texels_and_bake_equal_oracle(renderer, scene, tile, width):
     _setup(renderer, scene, of)
     want_texels = au.oracle_texels(pos, nrm, idx, tile, width)
     _assert_texels("%s T=%d texels (host)" % (scene, tile), renderer.atlasTexels(pos, nrm, idx, tile, width), want_texels)
-    dp, dn, di = _dev(pos), _dev(nrm), _dev(idx)
+    dp, dn, di = gu.to_device(pos), gu.to_device(nrm), gu.to_device(idx)
     got = renderer.atlasTexels(dp, dn, di, tile, width)
     torch.cuda.synchronize()
     _assert_texels("%s T=%d texels (device)" % (scene, tile), (got[0],) + tuple(t.cpu().numpy() for t in got[1:]), want_texels)
@@ -68,15 +57,15 @@ def test_texels_and_bake_equal_oracle(renderer, scene, tile, width):
     au.assert_condition(want)
     every = ("albedo", "normal", "lit")
     au.assert_bake("%s T=%d bake (host)" % (scene, tile), renderer.bakeAtlas(pos, nrm, idx, tile, width, reach, every), want)
-    au.assert_bake("%s T=%d bake (device)" % (scene, tile), _host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, every)), want)
+    au.assert_bake("%s T=%d bake (device)" % (scene, tile), _bake_to_host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, every)), want)
     # every layer mask, alone and in pairs: the planes asked for, and only those
     for layers in (("albedo",), ("normal",), ("lit",), ("albedo", "lit"), ("normal", "lit"), ("albedo", "normal")):
-        got = _host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, layers))
+        got = _bake_to_host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, layers))
         assert sorted(got) == sorted(layers + ("atlas", "valid"))
         au.assert_bake("%s T=%d layers %s" % (scene, tile, "+".join(layers)), got, want, sum(b for b, k in au.LAYER_NAMES.items() if k in layers))
     # step shortcuts: only misses end early, and a miss is zeros either way
     renderer.setStepShortcuts(True)
-    au.assert_bake("%s T=%d bake, shortcuts" % (scene, tile), _host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, every)), want)
+    au.assert_bake("%s T=%d bake, shortcuts" % (scene, tile), _bake_to_host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, every)), want)
     renderer.setStepShortcuts(False)
     # another reach
     want2, reach2 = au.reference(scene, tile, width, 0.2)
@@ -101,9 +90,9 @@ def test_bake_is_the_mesh_queries_of_its_texels(renderer, scene):
     of, pos, nrm, idx, cell = au.mesh(scene)
     _setup(renderer, scene, of)
     tile, width, reach = 8, 64, 2 * cell
-    dp, dn, di = _dev(pos), _dev(nrm), _dev(idx)
+    dp, dn, di = gu.to_device(pos), gu.to_device(nrm), gu.to_device(idx)
     _atlas, P, N, state = renderer.atlasTexels(dp, dn, di, tile, width)
-    baked = _host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, ("albedo", "normal", "lit")))
+    baked = _bake_to_host(renderer.bakeAtlas(dp, dn, di, tile, width, reach, ("albedo", "normal", "lit")))
     srf = renderer.meshSurfaces(P.reshape(-1, 3), N.reshape(-1, 3), reach)
     lit = renderer.meshLighting(P.reshape(-1, 3), N.reshape(-1, 3), reach)
     torch.cuda.synchronize()
@@ -136,7 +125,7 @@ def test_handmade_mesh(renderer, tile, width):
     _assert_texels("hand-made texels", renderer.atlasTexels(pos, nrm, idx, tile, width), want_texels)
     want = au.oracle_bake(scene, of, pos, nrm, idx, tile, width, 0.26)
     for device in (False, True):
-        got = _host(renderer.bakeAtlas(pos, nrm, idx, tile, width, 0.26, ("albedo", "normal", "lit"), device=device))
+        got = _bake_to_host(renderer.bakeAtlas(pos, nrm, idx, tile, width, 0.26, ("albedo", "normal", "lit"), device=device))
         au.assert_bake("hand-made bake", got, want)
         for k in ("albedo", "normal", "lit"):
             assert not got[k][got["valid"] != 1].any()
@@ -162,8 +151,8 @@ def test_out_of_range_indices_read_no_vertex(renderer):
     wild = idx.copy()
     wild[0, 1] = 0xffffffff
     wild[2:4] = [[1, 2, 3], [1, 3, 0x7fffffff]]
-    got = renderer.bakeAtlas(_dev(pos[:1]), _dev(nrm[:1]), _dev(wild), 8, 16, 0.26, ("albedo", "lit"))
-    assert (_host(got)["valid"] == -1).all()
+    got = renderer.bakeAtlas(gu.to_device(pos[:1]), gu.to_device(nrm[:1]), gu.to_device(wild), 8, 16, 0.26, ("albedo", "lit"))
+    assert (_bake_to_host(got)["valid"] == -1).all()
     got = renderer.atlasTexels(pos[:1], nrm[:1], wild, 4, 8)
     assert (got[3] == -1).all()
 
@@ -195,15 +184,11 @@ def test_atlas_leaves_rendering_alone(renderer):
     of = qu.frame(scene, 0.4, 96, 64)
     _setup(renderer, scene, of)
     _of, pos, nrm, idx, _cell = au.mesh("fast_sphere")
-    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    renderer.atlasTexels(pos, nrm, idx[:200], 8, 64)
-    renderer.bakeAtlas(pos, nrm, idx[:200], 8, 64, 0.3, ("albedo", "normal", "lit"))
-    _host(renderer.bakeAtlas(_dev(pos), _dev(nrm), _dev(idx[:200]), 4, 64, 0.3, ("lit",)))
-    renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), atlas=dict(tile=4, layers=("albedo", "lit")))
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, 96, 64):
+        renderer.atlasTexels(pos, nrm, idx[:200], 8, 64)
+        renderer.bakeAtlas(pos, nrm, idx[:200], 8, 64, 0.3, ("albedo", "normal", "lit"))
+        _bake_to_host(renderer.bakeAtlas(gu.to_device(pos), gu.to_device(nrm), gu.to_device(idx[:200]), 4, 64, 0.3, ("lit",)))
+        renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), atlas=dict(tile=4, layers=("albedo", "lit")))
 
 
 def test_arguments(renderer):
@@ -277,7 +262,7 @@ def test_arguments(renderer):
 
     base = torch.full((n * 4 + 1,), 7.0, device="cuda")
     dv = torch.full((n,), 7, dtype=torch.int32, device="cuda")
-    dp, dn, di = _dev(pos), _dev(nrm), _dev(idx)
+    dp, dn, di = gu.to_device(pos), gu.to_device(nrm), gu.to_device(idx)
     dev = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     assert L.sdfr_atlas_bake(h, A, len(pos), dev(dp), dev(dn), dev(di), 0.26, 4, None, None, dev(base[1:]), dev(dv), 0) == 0
     torch.cuda.synchronize()

@@ -6,26 +6,18 @@ bench's second pass (two frames in flight) gives the same bits again."""
 import numpy as np
 import pytest
 
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 STRIDE = 12
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
 
 
 def _phase(k):
     # 37 is prime to 144: the sweep's frames sample 16 different phases of the 12 x 12 grid
     j = (37 * k + 5) % (STRIDE * STRIDE)
     return j % STRIDE, j // STRIDE
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 @pytest.mark.parametrize("config", ["2", "3", "3r", "4", "5", "5g"])

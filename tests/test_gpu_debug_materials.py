@@ -7,7 +7,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from test_debug_materials_cpu import CAMS, H, W, _frame
+from frame_cases import MATERIALS_CAMS as CAMS, MATERIALS_H as H, MATERIALS_W as W, materials_frame as _frame  # noqa: E402
 
 
 def _render_and_compare(r, oracle, cam, iter_count, extra, schedules):

@@ -20,9 +20,10 @@ import time
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import handle_mixed_sequences as hm
 import handle_sequences as hs
-from test_gpu_handle_state import LAUNCH, NAN16, NAN32, SCHEDULE, _apply, _limits, _load_scene, _set_camera, _totals
+from handle_sequences import LAUNCH, NAN16, NAN32, SCHEDULE
 
 pytestmark = pytest.mark.gpu
 
@@ -372,10 +373,10 @@ class References:
         r = self.handles.get(st["scene"])
         if r is None:
             r = self.handles[st["scene"]] = sp.SDFRenderer(0)
-            _load_scene(r, st["scene"])
+            gu.load(r, st["scene"])
         r.resetVariables()
         r.setLaunchMode(LAUNCH["auto"])
-        r.setLimits(**_limits(st["limits"]))
+        r.setLimits(**hs.limits(st["limits"]))
         for name, v in sorted(st["vars"].items()):
             assert r.setValue(name, v)
         if st["debug"]:
@@ -429,7 +430,7 @@ class References:
             return self.cache[key]
         inp = self.inputs(s, steps) if inp is None else inp
         r = self.handle(s["state"])
-        _set_camera(r, s["state"]["scene"], s["state"]["t"], *_camera_size(s))
+        gu.orbit_camera(r, s["state"]["scene"], s["state"]["t"], *_camera_size(s))
         if s["call"] == "renderPrivateStrips":
             got = self.pseudo(s, call="render", stats=True)
         else:
@@ -439,7 +440,7 @@ class References:
             r.sync()
             got = c.answers(r, ("reference", s["call"]))
             if s["call"] in ("render", "renderAA"):
-                got["totals"] = np.array(_totals(r.getStats()), np.int64)
+                got["totals"] = np.array(gu.totals(r.getStats()), np.int64)
         for a in got.values():
             a.setflags(write=False)
         self.cache[key] = got
@@ -648,10 +649,10 @@ def refs(oracle):
 
 
 def _apply_all(r, s):
-    _apply(r, s["set"])
+    gu.apply_changes(r, s["set"])
     if "debug" in s["set"]:
         _debug(r, s["state"]["scene"], s["set"]["debug"])
-    _set_camera(r, s["state"]["scene"], s["state"]["t"], *_camera_size(s))
+    gu.orbit_camera(r, s["state"]["scene"], s["state"]["t"], *_camera_size(s))
 
 
 def _private_rows(s):
@@ -775,7 +776,7 @@ def _run_sequence(refs, seed):
                 c = _fail(r, refs, steps, s, keep, where)
                 assert all(b.untouched() for b in c.bufs.values()), (where, "a failed call wrote")
                 if last is not None:
-                    assert _totals(r.getStats()) == last, (where, "a failed call changed what sdfr_get_stats reports")
+                    assert gu.totals(r.getStats()) == last, (where, "a failed call changed what sdfr_get_stats reports")
                 continue
             inp = refs.inputs(s, steps)
             refs.answer(s, steps, inp)  # (before the call: nothing of the test's runs between a deferred call and the next)
@@ -811,7 +812,7 @@ def _run_sequence(refs, seed):
                 if pc.s["family"] in ("render", "aa"):
                     reported = tuple(int(x) for x in refs.answer(pc.s, steps)["totals"])
             if reported is not None:
-                assert _totals(r.getStats()) == reported, (where, "sdfr_get_stats does not report the last frame", _totals(r.getStats()), reported)
+                assert gu.totals(r.getStats()) == reported, (where, "sdfr_get_stats does not report the last frame", gu.totals(r.getStats()), reported)
             for copy, frame, cwhere in copies:
                 side.synchronize()
                 want = refs.answer(frame.s, steps)["image"]
@@ -948,7 +949,7 @@ def test_sync_calls_wait_for_the_other_lanes_emit(device):
         r.initShader("labyrinth")
         r.setParameters(0.5)
         r.setFramesInFlight(fif)
-        _set_camera(r, "labyrinth", 0.7, 96, 64)
+        gu.orbit_camera(r, "labyrinth", 0.7, 96, 64)
         return r
 
     want = []

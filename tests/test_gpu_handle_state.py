@@ -10,23 +10,18 @@ the reference is not only the library compared with itself.  Failed calls sit be
 nothing, with one frame in flight or two."""
 import ctypes
 import math
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import handle_sequences as hs
+from gpu_util import FOVY
+from handle_sequences import LAUNCH, NAN16, NAN32, SCHEDULE
 
 pytestmark = pytest.mark.gpu
 
-FOVY = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
-NAN32 = 0x7FC0DEAD  # a quiet NaN with a payload no render produces
-NAN16 = 0x7E5A
-RUNTIME_SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sdf_playground_amd", "scenes",
-                              hs.RUNTIME_SCENE + ".hlsl")
 ERR_INVALID_ARGUMENT, ERR_NO_SCENE = -1, -4
-LAUNCH = {"auto": 0, "per_tile": 1, "persistent": 2}
-SCHEDULE = {"wavefront": 0, "pixel": 1}
 
 
 def _image_format(fmt):
@@ -67,60 +62,11 @@ def _sentinel_bits(fmt):
     return NAN16 if _image_format(fmt) == hs.RGBA16F else NAN32
 
 
-def _totals(s):
-    return (int(s.pixels), int(s.rays), int(s.march_evals), int(s.hits))
-
-
 def _stat_sums(st, rows=None):
     st = np.asarray(st, np.int64)
     if rows is not None:
         st = st[rows]
     return (st.shape[0] * st.shape[1],) + tuple(int(st[..., k].sum()) for k in range(3))
-
-
-def _set_camera(r, scene, t, w, h):
-    import sdf_playground_amd as sp
-
-    kind, eye, target = hs.camera(scene, t)
-    cam = sp.Camera()
-    cam.SetEye(eye)
-    (cam.SetLookat if kind == "lookat" else cam.SetDirection)(target)
-    cam.SetFOVY(float(FOVY))
-    cam.SetAspect(float(np.float32(w) / np.float32(h)))
-    r.setCamera(cam)
-
-
-def _limits(name):
-    return dict(hs.DEFAULT_LIMITS, **hs.LIMITS[name])
-
-
-def _load_scene(r, scene):
-    if scene == hs.RUNTIME_SCENE:
-        r.initShaderHlsl(scene, RUNTIME_SOURCE)
-    else:
-        r.initShader(scene)
-
-
-def _apply(r, changes):
-    """the settings a step changes, in the order a host would make them (a scene load resets the variables first)"""
-    if "scene" in changes:
-        _load_scene(r, changes["scene"])
-    if "fif" in changes:
-        r.setFramesInFlight(changes["fif"])
-    if "schedule" in changes:
-        r.setSchedule(SCHEDULE[changes["schedule"]])
-    if "launch" in changes:
-        r.setLaunchMode(LAUNCH[changes["launch"]])
-    if "shortcuts" in changes:
-        r.setStepShortcuts(changes["shortcuts"])
-    if "limits" in changes:
-        r.setLimits(**_limits(changes["limits"]))
-    if "var" in changes:
-        assert r.setValue(*changes["var"])
-    if "stime" in changes:
-        r.setParameters(changes["stime"])
-    if "split" in changes:
-        r.setStripSplit(*changes["split"])
 
 
 class References:
@@ -146,11 +92,11 @@ class References:
         else:
             if self.runtime is None:
                 self.runtime = sp.SDFRenderer(0)
-                self.runtime.initShaderHlsl(hs.RUNTIME_SCENE, RUNTIME_SOURCE)
+                gu.load(self.runtime, hs.RUNTIME_SCENE)
             r = self.runtime
             r.resetVariables()
             r.setLaunchMode(LAUNCH["auto"])
-        r.setLimits(**_limits(st["limits"]))
+        r.setLimits(**hs.limits(st["limits"]))
         for name, v in sorted(st["vars"].items()):
             assert r.setValue(name, v)
         r.setParameters(st["stime"])
@@ -168,11 +114,11 @@ class References:
             return self.cache[key]
         r = self._handle(st)
         try:
-            _set_camera(r, st["scene"], st["t"], w, h)
+            gu.orbit_camera(r, st["scene"], st["t"], w, h)
             img = _sentinel_image(h, w, fmt)
             pst = _sentinel_stats(h, w)
             r.render(None, w, h, out=img, fmt=fmt, pixel_stats=pst)
-            tot = _totals(r.getStats())
+            tot = gu.totals(r.getStats())
             r.sync()
             torch.cuda.synchronize()
         finally:
@@ -192,7 +138,7 @@ class References:
         aspect = np.float32(w) / np.float32(h)
         basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, target, FOVY, aspect)
         f = oracle.default_frame(st["scene"], w, h, basis=basis, stime=st["stime"])
-        for name, v in _limits(st["limits"]).items():
+        for name, v in hs.limits(st["limits"]).items():
             setattr(f, name, v)
         slots = {row[0]: row[6] for row in oracle.var_table(st["scene"])}
         for name, v in st["vars"].items():
@@ -255,25 +201,25 @@ def _run_sequence(refs, seed):
         for s in steps:
             i, st, w, h, fmt = s["i"], s["state"], s["w"], s["h"], s["fmt"]
             where = (seed, i, s["call"], st["scene"], w, h, fmt, st["fif"])
-            _apply(r, s["set"])
+            gu.apply_changes(r, s["set"])
             if s["call"] == "failed":
                 target = _fail(r, s, keep)
                 # the frame submitted last is still the last one that succeeded
-                assert _totals(r.getStats()) == last, where
+                assert gu.totals(r.getStats()) == last, where
                 r.waitFrame(side.cuda_stream)
                 r.sync()
                 side.synchronize()
                 assert (_bits(target) == NAN32).all(), where
                 prev_bufs = {}
                 continue
-            _set_camera(r, st["scene"], st["t"], w, h)
+            gu.orbit_camera(r, st["scene"], st["t"], w, h)
             img_ref, pst_ref, tot_ref = refs.get(st, w, h, fmt)
             bufs = {}
             if s["call"] == "device":
                 img = prev_bufs["img"] if s["reuse_image"] else _sentinel_image(h, w, fmt)
                 pst = (prev_bufs["pst"] if s["reuse_stats"] else _sentinel_stats(h, w)) if s["stats"] else None
                 r.render(None, w, h, out=img, fmt=fmt, pixel_stats=pst if pst is not None else False)
-                last = _totals(r.getStats())
+                last = gu.totals(r.getStats())
                 r.sync()
                 assert last == tot_ref, (where, last, tot_ref)
                 got = _bits(img)
@@ -287,7 +233,7 @@ def _run_sequence(refs, seed):
                 out = np.full((h, w, 4), NAN16 if fmt == hs.RGBA16F else NAN32, np.uint16 if fmt == hs.RGBA16F else np.uint32)
                 out = out.view(np.float16 if fmt == hs.RGBA16F else np.float32)
                 res = r.render(None, w, h, out=out, fmt=fmt, pixel_stats=s["stats"])
-                last = _totals(r.getStats())
+                last = gu.totals(r.getStats())
                 assert last == tot_ref, (where, last, tot_ref)
                 img = res[0] if s["stats"] else res
                 assert img is out
@@ -327,7 +273,7 @@ def _run_strips(r, s, where, img_ref, pst_ref):
         for rank in range(world):
             buf = _ready(torch.full((nbytes // 4,), fill, dtype=torch.int32, device="cuda"))
             r.renderStrips(w, h, rank, world, buf, fmt=fmt)
-            last = _totals(r.getStats())
+            last = gu.totals(r.getStats())
             rows = sp.strip_rows_of_rank(h, rank, world, split)
             assert last == _stat_sums(pst_ref, rows), (where, rank, last, _stat_sums(pst_ref, rows))
             bufs.append(buf)
@@ -360,7 +306,7 @@ def _run_private(r, s, where, img_ref, pst_ref):
     split = s["state"]["split"]
     img = _sentinel_image(h, w, fmt)
     r.renderPrivateStrips(w, h, img, fmt=fmt)
-    last = _totals(r.getStats())
+    last = gu.totals(r.getStats())
     r.sync()
     rows = sp.private_rows_host(h, split)
     assert rows and last == _stat_sums(pst_ref, rows), (where, last, _stat_sums(pst_ref, rows))
@@ -397,13 +343,13 @@ def test_a_call_before_any_scene_changes_nothing(refs):
         r.sync()
         assert (_bits(img) == NAN32).all()
         st = dict(scene="gems", limits="5", vars={}, t=0.4, stime=0.25, shortcuts=False, schedule="pixel")
-        _apply(r, dict(scene="gems", limits="5", stime=0.25, shortcuts=False))
+        gu.apply_changes(r, dict(scene="gems", limits="5", stime=0.25, shortcuts=False))
         imgs = []
         for t in (0.4, 1.4):
-            _set_camera(r, "gems", t, 160, 90)
+            gu.orbit_camera(r, "gems", t, 160, 90)
             imgs.append(_sentinel_image(90, 160, hs.RGBA32F))
             r.render(None, 160, 90, out=imgs[-1])
-            assert _totals(r.getStats()) == refs.get(dict(st, t=t), 160, 90, hs.RGBA32F)[2]
+            assert gu.totals(r.getStats()) == refs.get(dict(st, t=t), 160, 90, hs.RGBA32F)[2]
         r.sync()
         for t, im in zip((0.4, 1.4), imgs):
             assert np.array_equal(_bits(im), _bits(refs.get(dict(st, t=t), 160, 90, hs.RGBA32F)[0])), t
@@ -426,12 +372,12 @@ def test_two_frames_in_flight_share_a_pixel_stats_buffer(refs):
     r = sp.SDFRenderer(0)
     side = torch.cuda.Stream()
     try:
-        _apply(r, dict(scene="labyrinth", limits="3", stime=0.5, shortcuts=True, fif=2))
+        gu.apply_changes(r, dict(scene="labyrinth", limits="3", stime=0.5, shortcuts=True, fif=2))
         for wait_between in (True, False):
             img1, img2 = _sentinel_image(h, w, hs.RGBA32F), _sentinel_image(h, w, hs.RGBA32F)
             pst = _sentinel_stats(h, w)
             for t, img in zip(ts[:2], (img1, img2)):
-                _set_camera(r, "labyrinth", t, w, h)
+                gu.orbit_camera(r, "labyrinth", t, w, h)
                 r.render(None, w, h, out=img, pixel_stats=pst)
             if wait_between:
                 r.sync()
@@ -439,13 +385,13 @@ def test_two_frames_in_flight_share_a_pixel_stats_buffer(refs):
                 assert np.array_equal(_bits(img1), _bits(want[0][0])) and np.array_equal(_bits(img2), _bits(want[1][0]))
             _fail(r, dict(i=-1, fail="format", w=w, h=h), [])
             # what getStats and waitFrame describe is still the second frame
-            assert _totals(r.getStats()) == want[1][2], wait_between
+            assert gu.totals(r.getStats()) == want[1][2], wait_between
             r.waitFrame(side.cuda_stream)
             with torch.cuda.stream(side):
                 copy2 = img2.clone()
-            _set_camera(r, "labyrinth", ts[2], w, h)
+            gu.orbit_camera(r, "labyrinth", ts[2], w, h)
             r.render(None, w, h, out=img1, pixel_stats=pst)
-            assert _totals(r.getStats()) == want[2][2], wait_between
+            assert gu.totals(r.getStats()) == want[2][2], wait_between
             r.sync()
             side.synchronize()
             assert np.array_equal(_bits(copy2), _bits(want[1][0])), (wait_between, "waitFrame did not wait for the second frame")

@@ -55,7 +55,7 @@ def test_pendulum_hlsl_equals_its_cpp_twin():
 def test_map_normal_in_the_dialect(oracle):
     """rounded.hlsl (use_normal, normal_sample_dist in HLSL) = the built-in normal_test = the oracle"""
     import sdf_playground_amd as sp
-    from test_normal_cpu import CAMS, _frame
+    from frame_cases import NORMAL_CAMS as CAMS, normal_frame as _frame
 
     r, aot = sp.SDFRenderer(0), sp.SDFRenderer(0)
     try:
@@ -102,7 +102,7 @@ def test_dialect_scene_on_the_gpu_renders_its_oracle_twin_s_bits(oracle, scene):
     dialect_tour: swizzled l-values and swaps, an inout swizzle, float3x3 + mul, static const initialisers, (int) with D3D's
     saturation, a scene-local voronoi overload, opRepLim / opShell / smin, and every VAR_ tag quirk."""
     import sdf_playground_amd as sp
-    from test_hlsl_cpu import TWIN_CAMS, TWIN_CASES, twin_frame
+    from frame_cases import TWIN_CAMS, TWIN_CASES, twin_frame
 
     r = sp.SDFRenderer(0)
     try:

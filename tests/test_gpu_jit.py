@@ -8,18 +8,10 @@ import numpy as np
 import pytest
 
 from jit_util import SCENES_DIR, aot_scene_source
-from test_gpu_parity import H, W, _compare, _setup
+from gpu_util import PARITY_H as H, PARITY_W as W, parity_compare as _compare, parity_setup as _setup
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 # run-time scenes get the plain IEEE sqrt / reciprocal / constant division unless their text opts into the

@@ -5,69 +5,34 @@ frame (no pixel list, 8 x 8 tiles) against the pixel list; step shortcuts on aga
 path, with and without the light samples, argument checks; no side effects on rendering; one handle across scene changes; the mesh
 with lighting; and the renderer's own pixels where `lit` is defined to be the pixel."""
 import ctypes
-import os
 import zlib
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import lighting_util as lu
 import query_util as qu
 import surface_util as su
-from test_lighting_cpu import MESHES, PIXEL_FRAMES, pixel_classes, pixel_frame
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
+from lighting_util import MESHES, PIXEL_FRAMES, pixel_classes, pixel_frame
 
 pytestmark = pytest.mark.gpu
 
 N_RAYS = 2000
 W, H = 64, 48
 FW, FH = 61, 45  # the whole frame: ragged 8 x 8 tiles on both edges
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 def _setup(r, scene, of, variables=None, shortcuts=False):
-    """the handle's state = the oracle frame `of`"""
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**dict(DEFAULT_LIMITS, light_count=of.light_count, max_cost_default=of.max_cost_default, extension_lights=of.extension_lights,
-                       extension_marble_reflection=of.extension_marble_reflection))
-    r.setStepShortcuts(shortcuts)
-    for name, v in (variables or {}).items():
-        assert r.setValue(name, v)
-
-
-def _torch_dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _host(answers):
-    import torch
-
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in answers)
+    """the handle's state = the oracle frame `of`, with the four limits the tests move taken from it"""
+    gu.setup(r, scene, of, variables, lu.frame_limits(of), shortcuts)
 
 
 def _frame_oracle(scene, of, w, h):
-    of.width, of.height = w, h
-    try:
+    with gu.with_size(of, w, h):
         return lu.oracle_pick(scene, of, su.frame_pixels(w, h))
-    finally:
-        of.width, of.height = W, H
 
 
 def _check_all(r, scene, of, seed, device=True, n_rays=N_RAYS):
@@ -92,9 +57,9 @@ def _check_all(r, scene, of, seed, device=True, n_rays=N_RAYS):
     lu.assert_same("%s frame, shortcuts" % scene, (None,) + r.pickLighting(None, FW, FH, lights=True), frame_ref)
     r.setStepShortcuts(False)
     if device:
-        lu.assert_same("%s rays (device)" % scene, _host(r.queryRayLighting(_torch_dev(o), _torch_dev(dirs), hits=True, lights=True)), ray_ref)
-        lu.assert_same("%s pick (device)" % scene, _host(r.pickLighting(_torch_dev(px), W, H, hits=True, lights=True)), pick_ref)
-        lu.assert_same("%s frame (device)" % scene, _host(r.pickLighting(None, FW, FH, hits=True, lights=True, device=True)), frame_ref)
+        lu.assert_same("%s rays (device)" % scene, gu.to_host(r.queryRayLighting(gu.to_device(o), gu.to_device(dirs), hits=True, lights=True)), ray_ref)
+        lu.assert_same("%s pick (device)" % scene, gu.to_host(r.pickLighting(gu.to_device(px), W, H, hits=True, lights=True)), pick_ref)
+        lu.assert_same("%s frame (device)" % scene, gu.to_host(r.pickLighting(None, FW, FH, hits=True, lights=True, device=True)), frame_ref)
     return ray_ref, pick_ref
 
 
@@ -144,7 +109,7 @@ def test_whole_frame_equals_the_pixel_list(renderer):
         listed = renderer.pickLighting(su.frame_pixels(w, h), w, h, hits=True, lights=True)
         assert len(listed[1]) == w * h
         lu.assert_same("%d x %d" % (w, h), renderer.pickLighting(None, w, h, hits=True, lights=True), listed)
-        lu.assert_same("%d x %d (device)" % (w, h), _host(renderer.pickLighting(None, w, h, hits=True, lights=True, device=True)), listed)
+        lu.assert_same("%d x %d (device)" % (w, h), gu.to_host(renderer.pickLighting(None, w, h, hits=True, lights=True, device=True)), listed)
 
 
 @pytest.mark.parametrize("scene", sorted(MESHES))
@@ -169,14 +134,8 @@ def test_mesh_with_lighting(renderer, scene):
     # with the surfaces and the occlusion: the lighting is the last element; another reach, on the device
     out = renderer.extractMesh(origin, cell, dims, surfaces=True, occlusion=True, lighting=True, reach=0.2, device=True)
     assert len(out) == 6
-    (dlit,) = _host((out[-1],))
+    (dlit,) = gu.to_host((out[-1],))
     qu.assert_same("%s mesh lighting, reach 0.2 (device)" % scene, lu.lighting_array(dlit), lu.oracle_mesh(scene, of, pos, nrm, 0.2)[1])
-
-
-def _raw(r):
-    import sdf_playground_amd as sp
-
-    return sp.load_library(), r._h
 
 
 def test_small_and_awkward_sizes(renderer):
@@ -185,21 +144,21 @@ def test_small_and_awkward_sizes(renderer):
     scene = "light_shadows"
     of = qu.frame(scene, 0.3, W, H)
     _setup(renderer, scene, of)
-    L, h = _raw(renderer)
+    L, h = gu.raw(renderer)
     o, dirs = qu.ray_samples(of, 5, 65)
     ref = lu.oracle_rays(scene, of, o, dirs)
     assert (ref[1][:, 2] != 0).any()
     for n in (0, 1, 63, 64, 65):
         want = tuple(a[:n] for a in ref)
         lu.assert_same("n = %d" % n, renderer.queryRayLighting(o[:n], dirs[:n], hits=True, lights=True), want)
-        dev = _host(renderer.queryRayLighting(_torch_dev(o[:n].reshape(-1, 3)), _torch_dev(dirs[:n].reshape(-1, 3)), hits=True, lights=True))
+        dev = gu.to_host(renderer.queryRayLighting(gu.to_device(o[:n].reshape(-1, 3)), gu.to_device(dirs[:n].reshape(-1, 3)), hits=True, lights=True))
         lu.assert_same("n = %d (device)" % n, dev, want)
     # records that start 4 bytes past a 16-byte boundary: the word stores; the words around them stay
     n = 65
     sentinel = 0x7fc12345
     bufs = [torch.full((words * n + 8,), sentinel, dtype=torch.int32, device="cuda") for words in (12, 16, 160)]
     assert all(b.data_ptr() % 16 == 0 for b in bufs)
-    do, dd = _torch_dev(o), _torch_dev(dirs)
+    do, dd = gu.to_device(o), gu.to_device(dirs)
     vp = ctypes.c_void_p
     assert L.sdfr_query_ray_lighting(h, n, vp(do.data_ptr()), vp(dd.data_ptr()), 0.0, *[vp(b.data_ptr() + 4) for b in bufs], 0) == 0
     renderer.sync()
@@ -218,7 +177,7 @@ def test_arguments(renderer):
 
     scene = "fast_sphere"
     _setup(renderer, scene, qu.frame(scene, 0.0, W, H))
-    L, h = _raw(renderer)
+    L, h = gu.raw(renderer)
     buf = np.zeros(64, np.float32)
     out, hit, smp = np.full(W * H * 16, 7, np.uint32), np.full(W * H * 12, 7, np.uint32), np.full(W * H * 160, 7, np.uint32)  # what no call below may touch
     p, g, hp, sp_ = (a.ctypes.data_as(ctypes.c_void_p) for a in (buf, out, hit, smp))
@@ -265,26 +224,17 @@ def test_arguments(renderer):
     assert set(out.reshape(-1, 16)[:, 0]) <= {0, 1} and set(hit.reshape(-1, 12)[:, 10]) <= {0, 1} and set(smp.reshape(-1, 20)[:, 0]) <= {0, 1, 2, 3}
 
 
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
 def test_lighting_queries_leave_rendering_alone(renderer):
     scene = "labyrinth"
     of = qu.frame(scene, 0.4, 96, 64)
     _setup(renderer, scene, of)
     o, dirs = qu.ray_samples(of, 71, 500)
-    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    renderer.queryRayLighting(o, dirs, hits=True, lights=True)
-    renderer.pickLighting(qu.pick_grid(32, 16), 32, 16)
-    renderer.pickLighting(None, 33, 17, hits=True)
-    renderer.meshLighting(o, dirs, 0.25, lights=True)
-    renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), lighting=True)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, 96, 64):
+        renderer.queryRayLighting(o, dirs, hits=True, lights=True)
+        renderer.pickLighting(qu.pick_grid(32, 16), 32, 16)
+        renderer.pickLighting(None, 33, 17, hits=True)
+        renderer.meshLighting(o, dirs, 0.25, lights=True)
+        renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), lighting=True)
 
 
 def test_one_handle_across_scene_changes():

@@ -9,16 +9,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from gpu_util import renderer  # noqa: E402,F401
 from scene_divisors import SCENE_DIVISORS  # every divisor handed to div_c / op_rep_inf_c / op_pipe_c / turbulence3 by the scene code
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 def test_fast_sqrt_is_correctly_rounded_on_its_domain(renderer):

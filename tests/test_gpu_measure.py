@@ -7,15 +7,17 @@ two frames in flight; the argument errors through the raw C ABI; measureSolid ag
 import ctypes
 import json
 import math
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import measure_util as mu
+import mesh_survey_util as msu
 import query_util as qu
 import span_util as su
-from test_gpu_mesh_survey import DEFAULT_LIMITS, PROBE
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,39 +32,9 @@ CASES = {"fast_sphere": (0.0, (-1.85, 2.5, -1.05), (0, -1, 0), 2.45), "cube_sea"
 GRIDS = [(1, 1), (7, 5), (8, 8), (9, 17), (72, 65)]  # one lane live; a single ragged tile; one full tile; ragged on both axes; 81 tiles: a second pass with a padded run
 
 
-def _setup(r, scene, of):
-    """the handle's state = the oracle frame `of`"""
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
-
-
 def _probe(r, **values):
-    """the probe scene of tests/test_gpu_mesh_survey.py with its variables set"""
-    if r.currentScene() != "measure_probe":
-        r.initShaderSource("measure_probe", PROBE)
-        r.setLimits(**DEFAULT_LIMITS)
-    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
-        assert r.setValue(name, v)
-
-
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
+    """the probe scene (mesh_survey_util.PROBE) with its variables set"""
+    msu.load_probe(r, "measure_probe", msu.PROBE_DEFAULTS, **values)
 
 
 def _grid(g):
@@ -114,7 +86,7 @@ def _check(renderer, what, g, want, want_col, **kw):
 # ---- parity ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("scene", sorted(CASES))
 def test_measure_equals_the_definition(renderer, scene):
-    _setup(renderer, scene, qu.frame(scene, CASES[scene][0], W, H))
+    gu.setup(renderer, scene, qu.frame(scene, CASES[scene][0], W, H))
     hit = 0
     for nu, nv in GRIDS:
         g, depth, want, want_col = expected(scene, nu, nv)
@@ -136,7 +108,7 @@ def test_a_third_pass_on_fast_sphere(renderer):
     """520 x 512 columns are 4160 tiles: 65 runs, then 2, then 1"""
     scene = "fast_sphere"
     of = qu.frame(scene, 0.0, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     cell = 0.005
     g = mu.grid((-1.3, 2.5, -1.3), (cell, 0, 0), (0, 0, cell), (0, -1, 0), 520, 512)
     p = su.params(0.25, 2.45, 0.0, 32)
@@ -175,15 +147,14 @@ def test_probe_scene_with_its_nan_half_space(renderer):
 
 def test_measure_solid_on_a_sphere(renderer):
     """the one-call form against 4/3 pi rho^3, the centre and 2/5 m rho^2, rho / cell = 16, within twice the worst case the CPU tier
-    recorded for the definition at that resolution (tests/test_measure_cpu.py: RECORDED_WORST[16])"""
+    recorded for the definition at that resolution (measure_util.RECORDED_WORST[16], checked by tests/test_measure_cpu.py)"""
     import sdf_playground_amd as sp
-    from test_measure_cpu import RECORDED_WORST
 
     centre, rho, cell, density = (0.03, 0.05, 0.07), 0.8, 0.05, 2.5
     _probe(renderer, cx=centre[0], cy=centre[1], cz=centre[2], radius=rho)
     c32, r32 = np.array([F(v) for v in centre], np.float64), float(F(rho))
     volume = 4.0 / 3.0 * math.pi * r32 ** 3
-    v_bound, i_bound, c_bound = (2 * x for x in RECORDED_WORST[16])
+    v_bound, i_bound, c_bound = (2 * x for x in mu.RECORDED_WORST[16])
     for axis in "xyz":
         props = renderer.measureSolid((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), cell, axis, density)
         res = props["result"]
@@ -206,7 +177,7 @@ def test_a_tilted_grid(renderer):
     0.7: a sheared bundle through what the camera sees"""
     for scene in ("labyrinth", "fast_sphere"):
         of = qu.frame(scene, CASES[scene][0], W, H)
-        _setup(renderer, scene, of)
+        gu.setup(renderer, scene, of)
         eye, front, right, top = (np.array(list(v), np.float64) for v in (of.eye, of.front, of.right, of.top))
         right, top, front = right / np.linalg.norm(right), top / np.linalg.norm(top), front / np.linalg.norm(front)
         du, dv, dw = 0.04 * right + 0.006 * top + 0.004 * front, 0.03 * top - 0.005 * right + 0.003 * front, 0.7 * front + 0.05 * right - 0.02 * top
@@ -224,7 +195,7 @@ def test_a_tilted_grid(renderer):
 def test_debug_plane_and_show_objects(renderer):
     """the DBG kernel variant: the debug plane on and show_objects off apply as they do in sdfr_query_distance"""
     scene = "labyrinth"
-    _setup(renderer, scene, qu.frame(scene, 0.75, W, H))
+    gu.setup(renderer, scene, qu.frame(scene, 0.75, W, H))
     g, depth = _scene_grid(scene, 19, 13, (30, 14))
     p = su.params(MIN_STEP, depth, 0.0, MAX_STEPS)
     plain = mu.measure(_distance(scene, qu.frame(scene, 0.75, W, H)), g, p)[0]
@@ -246,7 +217,7 @@ def test_columns_off_alignment_and_out_of_steps(renderer):
     import sdf_playground_amd as sp
 
     scene = "cube_sea"
-    _setup(renderer, scene, qu.frame(scene, CASES[scene][0], W, H))
+    gu.setup(renderer, scene, qu.frame(scene, CASES[scene][0], W, H))
     # max_steps so small that some columns run out of steps and some do not
     g, depth, want, want_col = expected(scene, 72, 65, 24)
     n = 72 * 65
@@ -272,15 +243,11 @@ def test_measure_leaves_rendering_alone(renderer):
 
     scene = "labyrinth"
     of = qu.frame(scene, CASES[scene][0], W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     g, depth, want, want_col = expected(scene, 9, 17)
     kw = dict(min_step=MIN_STEP, t_max=depth, max_steps=MAX_STEPS)
-    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    _check(renderer, "after a render", g, want, want_col, **kw)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, W, H) as (img0, s0):
+        _check(renderer, "after a render", g, want, want_col, **kw)
     # two frames in flight: the call runs on the lane of the frame submitted last
     renderer.setFramesInFlight(2)
     try:
@@ -292,7 +259,7 @@ def test_measure_leaves_rendering_alone(renderer):
             mu.assert_same_result(("in flight", k), res, want)
             mu.assert_same_columns(("in flight", k), _columns(cols), want_col)
             assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
-            assert _stats(renderer) == s0
+            assert gu.stats(renderer) == s0
     finally:
         renderer.setFramesInFlight(1)
 
@@ -301,7 +268,7 @@ def test_arguments(renderer):
     import sdf_playground_amd as sp
 
     L = sp.load_library()
-    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    gu.setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
     h = renderer._h
     INVALID, NO_SCENE = -1, -4
     NULL_POINTER, BAD_ON_HOST, BAD_GRID, BAD_PARAMS = "null pointer", "on_host must be 0 or 1", "bad measure grid", "bad span parameters"

@@ -3,13 +3,15 @@ include/sdfr.h restated in numpy (mesh_util.surface_nets) and fed with the oracl
 the point query's at the vertices; host and device memory; the prefix sums at depth; degenerate grids; the capacity rule; closed,
 outward-oriented surfaces of two analytic scenes; no side effects on rendering; argument checks."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import mesh_util as mu
 import query_util as qu
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,37 +23,6 @@ CELL = 0.1
 CASES = {"fast_sphere": (0.0, (-1.85, -0.3, -1.05)), "labyrinth": (1.25, (-5.35, -0.3, -2.55)), "gyroid": (0.5, (-1.85, -0.3, -1.05)),
          "sierpinski": (0.5, (-1.85, -0.3, -1.05)), "noise_lod": (0.5, (-1.85, -0.3, -1.05))}
 assert "noise_lod" in qu.HLSL  # the run-time scene: its lattice kernel comes from the lazily compiled query module
-
-
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-
-
-def _setup(r, scene, of):
-    """the handle's state = the oracle frame `of`"""
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
-
-
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
 
 _refs = {}
 
@@ -93,7 +64,7 @@ def _check_mesh(r, what, pos_ref, idx_ref, origin, cell, dims, iso=0.0, device=T
 def test_mesh_equals_the_definition(renderer, scene):
     stime, origin = CASES[scene]
     of, pos_ref, idx_ref = _reference(scene, stime, origin, CELL, DIMS)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     assert len(pos_ref) > 500 and len(idx_ref) > 500
     _check_mesh(renderer, scene, pos_ref, idx_ref, origin, CELL, DIMS)
 
@@ -108,7 +79,7 @@ def test_the_gyroid_mesh_is_open(renderer):
 def test_iso_and_a_dyadic_cell(renderer):
     scene, origin, cell, dims, iso = "sierpinski", (-1.5, 0.0, -1.5), 0.0625, (48, 40, 44), 0.05
     of, pos_ref, idx_ref = _reference(scene, 0.5, origin, cell, dims, iso)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     assert len(pos_ref) > 500
     _check_mesh(renderer, scene, pos_ref, idx_ref, origin, cell, dims, iso, device=False)
 
@@ -120,7 +91,7 @@ def test_scan_at_depth(renderer):
     scene, origin, cell, dims = "labyrinth", (-5.5, -0.25, -3.5), 0.125, (48, 48, 48)
     assert (dims[0] * dims[1] * dims[2] + 1 + 255) // 256 > 256
     of, pos_ref, idx_ref = _reference(scene, 1.25, origin, cell, dims)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     assert len(pos_ref) > 5000
     _check_mesh(renderer, scene, pos_ref, idx_ref, origin, cell, dims)
 
@@ -132,7 +103,7 @@ def test_degenerate_grids(renderer):
     dims = (1, 29, 21)
     o = (0.35, -0.3, -1.05)  # a slab through the sphere's flank, where x edges cross its surface
     of, pos_ref, idx_ref = _reference(scene, stime, o, CELL, dims)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     assert len(pos_ref) > 20 and len(idx_ref) > 0
     pos, _nrm, idx = _check_mesh(renderer, scene + " nx=1", pos_ref, idx_ref, o, CELL, dims)
     # a 1 x 1 x 1 grid straddling the floor: one vertex, no triangle
@@ -170,7 +141,7 @@ def test_capacity(renderer):
     scene = "fast_sphere"
     stime, origin = CASES[scene]
     of, pos_ref, idx_ref = _reference(scene, stime, origin, CELL, DIMS)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     V, T = len(pos_ref), len(idx_ref)
     g = _grid(origin, CELL, DIMS)
     assert _raw(L, renderer._h, g, 0, 0, None, None, None) == (0, V, T)  # the counting call
@@ -232,13 +203,9 @@ def test_mesh_leaves_rendering_alone(renderer):
     scene = "labyrinth"
     stime, origin = CASES[scene]
     of, pos_ref, idx_ref = _reference(scene, stime, origin, CELL, DIMS)
-    _setup(renderer, scene, of)
-    img0, st0 = renderer.render(None, 64, 48, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    _check_mesh(renderer, scene, pos_ref, idx_ref, origin, CELL, DIMS)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 64, 48, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    gu.setup(renderer, scene, of)
+    with gu.rendering_untouched(renderer, 64, 48) as (img0, s0):
+        _check_mesh(renderer, scene, pos_ref, idx_ref, origin, CELL, DIMS)
     # two frames in flight: the extraction runs on the lane of the frame submitted last; device arrays are read after sdfr_sync
     renderer.setFramesInFlight(2)
     try:
@@ -252,7 +219,7 @@ def test_mesh_leaves_rendering_alone(renderer):
             qu.assert_same("positions (device)", dpos.cpu().numpy(), pos_ref)
             assert np.array_equal(idx, idx_ref) and np.array_equal(didx.cpu().numpy().view(np.uint32), idx_ref)
             assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
-            assert _stats(renderer) == s0
+            assert gu.stats(renderer) == s0
     finally:
         renderer.setFramesInFlight(1)
 
@@ -261,7 +228,7 @@ def test_arguments(renderer):
     import sdf_playground_amd as sp
 
     L = sp.load_library()
-    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    gu.setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
     h = renderer._h
     o, dims = (-0.5, -0.3, -0.5), (8, 8, 8)
     buf, ibuf = np.zeros((4096, 3), np.float32), np.zeros((8192, 3), np.uint32)

@@ -4,14 +4,15 @@ normals equal to the point query's at the vertices; host and device memory; iso 
 counts around the kernel's groups of four; the capacity rule; a box's corners and faces through the library; the clamp; no side effects on
 rendering; composition with the per-vertex queries and the atlas; the CLI."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import mesh_sharp_util as su
 import mesh_util as mu
 import query_util as qu
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,38 +25,6 @@ CASES = {"fast_sphere": (0.0, (-1.85, -0.3, -1.05), None), "labyrinth": (1.25, (
          # one box of half size 0.8 about (0.03, 1.55, 0.07), off the lattice, in a grid clear of the floor
          "cube": (0.5, (-1.82, 0.31, -0.98), {"size": 0.8, "xpos": 0.03, "ypos": 0.55, "zpos": 0.07})}
 CUBE_CENTRE, CUBE_HALF = np.array([0.03, 1.55, 0.07]), 0.8
-
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-
-
-def _setup(r, scene, of, variables=None):
-    """the handle's state = the oracle frame `of`"""
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
-    for name, v in (variables or {}).items():
-        assert r.setValue(name, v)
-
-
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
 
 _refs = {}
 
@@ -105,7 +74,7 @@ def _check_mesh(r, what, ref, origin, cell, dims, iso=0.0, device=True):
 def test_sharp_mesh_equals_the_definition(renderer, scene):
     stime, origin, variables = CASES[scene]
     ref = _reference(scene, stime, origin, CELL, DIMS, variables=variables)
-    _setup(renderer, scene, ref[0], variables)
+    gu.setup(renderer, scene, ref[0], variables)
     try:
         assert len(ref[1]) > 500 and len(ref[4]) > 500
         pos, _nrm, _idx = _check_mesh(renderer, scene, ref, origin, CELL, DIMS)
@@ -118,7 +87,7 @@ def test_sharp_mesh_equals_the_definition(renderer, scene):
 def test_iso_and_a_dyadic_cell(renderer):
     scene, origin, cell, dims, iso = "sierpinski", (-1.5, 0.0, -1.5), 0.0625, (48, 40, 44), 0.05
     ref = _reference(scene, 0.5, origin, cell, dims, iso)
-    _setup(renderer, scene, ref[0])
+    gu.setup(renderer, scene, ref[0])
     assert len(ref[1]) > 500
     _check_mesh(renderer, scene, ref, origin, cell, dims, iso, device=False)
 
@@ -129,7 +98,7 @@ def test_smallest_grids(renderer):
     # a 1 x 1 x 1 grid straddling the floor: one vertex, no triangle
     one = ((0.31, -0.04, 0.27), 0.1, (1, 1, 1))
     ref = _reference(scene, stime, *one)
-    _setup(renderer, scene, ref[0])
+    gu.setup(renderer, scene, ref[0])
     assert len(ref[1]) == 1 and len(ref[4]) == 0
     _check_mesh(renderer, scene + " 1x1x1", ref, *one)
     # nx = 1: a slab through the sphere's flank, quads only along x edges
@@ -149,7 +118,7 @@ def test_vertex_counts_around_the_groups_of_four(renderer, vertices):
     grid = ((2.31, -0.04, 2.27), 0.1, (vertices, 1, 1))
     ref = _reference(scene, CASES[scene][0], *grid)
     assert len(ref[1]) == vertices
-    _setup(renderer, scene, ref[0])
+    gu.setup(renderer, scene, ref[0])
     _check_mesh(renderer, "%d vertices" % vertices, ref, *grid)
 
 
@@ -161,7 +130,7 @@ def test_capacity(renderer):
     scene = "fast_sphere"
     stime, origin, _v = CASES[scene]
     ref = _reference(scene, stime, origin, CELL, DIMS)
-    _setup(renderer, scene, ref[0])
+    gu.setup(renderer, scene, ref[0])
     pos_ref, idx_ref = ref[1], ref[4]
     V, T = len(pos_ref), len(idx_ref)
     g = sp.MeshGrid((ctypes.c_float * 3)(*origin), CELL, DIMS[0], DIMS[1], DIMS[2], 0.0)
@@ -209,7 +178,7 @@ def test_the_cube_keeps_its_edges_and_corners(renderer):
     scene = "cube"
     stime, origin, variables = CASES[scene]
     ref = _reference(scene, stime, origin, CELL, DIMS, variables=variables)
-    _setup(renderer, scene, ref[0], variables)
+    gu.setup(renderer, scene, ref[0], variables)
     try:
         pos, _nrm, _idx = renderer.extractMesh(origin, CELL, DIMS, sharp=True)
         nets, _nn, _ni = renderer.extractMesh(origin, CELL, DIMS)
@@ -228,14 +197,10 @@ def test_sharp_mesh_leaves_rendering_alone(renderer):
     scene = "labyrinth"
     stime, origin, _v = CASES[scene]
     ref = _reference(scene, stime, origin, CELL, DIMS)
-    _setup(renderer, scene, ref[0])
+    gu.setup(renderer, scene, ref[0])
     pos_ref = ref[1]
-    img0, st0 = renderer.render(None, 64, 48, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    _p, _n, idx_ref = _check_mesh(renderer, scene, ref, origin, CELL, DIMS)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 64, 48, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, 64, 48) as (img0, s0):
+        _p, _n, idx_ref = _check_mesh(renderer, scene, ref, origin, CELL, DIMS)
     # two frames in flight: the extraction runs on the lane of the frame submitted last; device arrays are read after sdfr_sync
     renderer.setFramesInFlight(2)
     try:
@@ -249,7 +214,7 @@ def test_sharp_mesh_leaves_rendering_alone(renderer):
             qu.assert_same("positions (device)", dpos.cpu().numpy(), pos_ref)
             assert np.array_equal(idx, idx_ref) and np.array_equal(didx.cpu().numpy().view(np.uint32), idx_ref)
             assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
-            assert _stats(renderer) == s0
+            assert gu.stats(renderer) == s0
     finally:
         renderer.setFramesInFlight(1)
     # the stage timings keep their four slots, the sharp vertices in "emit"
@@ -266,7 +231,7 @@ def test_composition(renderer):
     scene = "labyrinth"
     stime, origin, _v = CASES[scene]
     ref = _reference(scene, stime, origin, CELL, DIMS)
-    _setup(renderer, scene, ref[0])
+    gu.setup(renderer, scene, ref[0])
     options = dict(surfaces=True, occlusion=True, lighting=True, atlas=dict(tile=4))
     sharp = renderer.extractMesh(origin, CELL, DIMS, sharp=True, **options)
     nets = renderer.extractMesh(origin, CELL, DIMS, **options)

@@ -3,14 +3,15 @@ numpy (mesh_survey_util.survey / fit), fed with the oracle's distances for the b
 queryDistance for the run-time probe scene; the counts against sdfr_mesh_extract's counting call; the fitted grid's mesh against the
 search grid's, bit for bit; no side effects on rendering; the argument errors through the raw C ABI."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import mesh_survey_util as su
 import mesh_util as mu
 import query_util as qu
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,33 +21,6 @@ DIMS, CELL = (37, 29, 21), 0.1
 CASES = {"fast_sphere": (0.0, (-1.85, -0.3, -1.05)), "labyrinth": (1.25, (-5.35, -0.3, -2.55)), "gyroid": (0.5, (-1.85, -0.3, -1.05)),
          "sierpinski": (0.5, (-1.85, -0.3, -1.05)), "noise_lod": (0.5, (-1.85, -0.3, -1.05))}
 BANDS = (0.0, 0.05, 0.175)
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-
-# The run-time probe scene: by `kind` a sphere with its centre and radius in variables, the plane y = height, or that plane with NaN
-# where x > split.  setValue does not clamp, so the ranges below bind nothing.
-PROBE = """struct Scene
-{
-	static SDF_HD void prepare(FrameU &) {}
-	struct RayInv {};
-	static SDF_HD RayInv ray_setup(const FrameU &, vec3, const RayFlags &) { return RayInv(); }
-	static SDF_HD float dist(const FrameU &U, const RayInv &, vec3 p, vec3, bool)
-	{
-		const float kind = VAR_kind(min = 0, max = 2, start = 0);
-		const vec3 c = V3(VAR_cx(min = -100, max = 100, start = 0), VAR_cy(min = -100, max = 100, start = 0), VAR_cz(min = -100, max = 100, start = 0));
-		const float radius = VAR_radius(min = 0, max = 10, start = 1), height = VAR_height(min = -10, max = 10, start = 0.25);
-		const float split = VAR_split(min = -10, max = 10, start = 0.3);
-		if (kind < 0.5f) return sd_sphere(p - c, radius);
-		if (kind > 1.5f && p.x > split) return bits_f32(0x7fc00000u);
-		return p.y - height;
-	}
-	static SDF_HD void material(const FrameU &, const SurfacePoint &, Material &) {}
-	static SDF_HD bool light(const FrameU &, int i, Light &L) { return sun_light(i, L); }
-	static SDF_HD float ambient() { return 0.1f; }
-	static SDF_HD vec3 background(const FrameU &U, vec3 dir, uint32_t) { return sky_color(dir, U.sky_s, U.sky_c); }
-};
-"""
-
 
 _probe_loaded = [False]  # is the probe scene the renderer's scene (it is compiled once per load)
 
@@ -54,39 +28,14 @@ _probe_loaded = [False]  # is the probe scene the renderer's scene (it is compil
 def _setup(r, scene, of):
     """the handle's state = the oracle frame `of`"""
     _probe_loaded[0] = False
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
+    gu.setup(r, scene, of)
 
 
 def _probe(r, **values):
     """the probe scene with its variables set; -> distance(origin, cell, dims) by the library's own point query"""
-    if not _probe_loaded[0]:
-        r.initShaderSource("survey_probe", PROBE)
-        r.setLimits(**DEFAULT_LIMITS)
-        _probe_loaded[0] = True
-    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
-        assert r.setValue(name, v)
+    su.load_probe(r, "survey_probe", su.PROBE_DEFAULTS, loaded=_probe_loaded[0], **values)
+    _probe_loaded[0] = True
     return lambda origin, cell, dims: r.queryDistance(mu.lattice_points(origin, cell, dims))
-
-
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 def _assert_same(what, got, want):
@@ -249,13 +198,9 @@ def test_survey_and_fit_leave_rendering_alone(renderer):
     distance = su.oracle_distance(scene, of)
     survey_ref = su.survey(distance(origin, su.FIT_CELL, su.FIT_DIMS), su.FIT_DIMS, 0.0, 0.1)
     fit_ref = su.fit(distance, origin, su.FIT_CELL, su.FIT_DIMS, 0.0, 2, 1)
-    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    _assert_same("survey", renderer.surveyMesh(origin, su.FIT_CELL, su.FIT_DIMS, band=0.1), survey_ref)
-    _assert_same("fit", renderer.fitMesh(origin, su.FIT_CELL, su.FIT_DIMS, levels=2), fit_ref)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, W, H) as (img0, s0):
+        _assert_same("survey", renderer.surveyMesh(origin, su.FIT_CELL, su.FIT_DIMS, band=0.1), survey_ref)
+        _assert_same("fit", renderer.fitMesh(origin, su.FIT_CELL, su.FIT_DIMS, levels=2), fit_ref)
     # two frames in flight: both calls run on the lane of the frame submitted last, between extractions that leave device work behind
     renderer.setFramesInFlight(2)
     try:
@@ -268,7 +213,7 @@ def test_survey_and_fit_leave_rendering_alone(renderer):
             renderer.sync()
             assert len(dpos) == survey_ref["active_cells"]
             assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
-            assert _stats(renderer) == s0
+            assert gu.stats(renderer) == s0
     finally:
         renderer.setFramesInFlight(1)
 

@@ -8,7 +8,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from test_normal_cpu import CAMS, EPS_DEFAULT, EPS_OTHER, H, W, _frame
+from frame_cases import EPS_DEFAULT, EPS_OTHER, NORMAL_CAMS as CAMS, NORMAL_H as H, NORMAL_W as W, normal_frame as _frame  # noqa: E402
 
 
 def _set_camera(sp, r, cam, w, h):

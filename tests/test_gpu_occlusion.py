@@ -4,14 +4,16 @@ device memory, both entries, the hits of sdfr_pick and sdfr_pick_surfaces fed ba
 and a hit array off 16-byte alignment; the debug kernel variant; step shortcuts; a scene whose answer is known without the oracle;
 the mesh with occlusion; argument checks; no side effects on rendering; one handle across scene changes; two frames in flight."""
 import ctypes
-import os
 import zlib
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import occlusion_util as ou
 import query_util as qu
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -19,56 +21,13 @@ N_ITEMS = 150
 W, H = 64, 48
 PW, PH = 9, 7  # the frame whose picks are fed back
 BIAS, RADIUS = ou.BIAS, ou.RADIUS
-SCENES_DIR = qu.SCENES_DIR
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
 # the meshes: about 24^3 cells, no axis a multiple of the lattice kernel's brick
 MESHES = {"fast_sphere": (0.0, (-1.55, -0.3, -1.55), 0.13, (24, 23, 25)), "labyrinth": (0.5, (-5.35, -0.3, -2.55), 0.11, (25, 23, 24))}
 
 
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
-
-def _load(r, scene):
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-
-
-def _setup(r, scene, of, variables=None, limits=None, shortcuts=False):
-    """the handle's state = the oracle frame `of`"""
-    _load(r, scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**dict(DEFAULT_LIMITS, **(limits or {})))
-    r.setStepShortcuts(shortcuts)
-    for name, v in (variables or {}).items():
-        assert r.setValue(name, v)
-
-
-def _dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def _hits_dev(hits):
+def _hits_to_device(hits):
     """HIT_DTYPE records or [n, 12] words -> an [n, 12] int32 device tensor"""
-    return _dev(qu.hits_array(hits).view(np.int32))
+    return gu.to_device(qu.hits_array(hits).view(np.int32))
 
 
 def _check_all(r, scene, of, seed, device=True, n=N_ITEMS):
@@ -80,8 +39,8 @@ def _check_all(r, scene, of, seed, device=True, n=N_ITEMS):
     qu.assert_same("%s points (host)" % scene, ou.occlusion_array(r.queryOcclusion(p, nr, BIAS, RADIUS)), pref)
     qu.assert_same("%s points against hits" % scene, pref[is_item], ref[is_item])
     if device:
-        qu.assert_same("%s hits (device)" % scene, ou.occlusion_array(_host(r.hitOcclusion(_hits_dev(hits), BIAS, RADIUS))), ref)
-        qu.assert_same("%s points (device)" % scene, ou.occlusion_array(_host(r.queryOcclusion(_dev(p), _dev(nr), BIAS, RADIUS))), pref)
+        qu.assert_same("%s hits (device)" % scene, ou.occlusion_array(gu.to_host(r.hitOcclusion(_hits_to_device(hits), BIAS, RADIUS))), ref)
+        qu.assert_same("%s points (device)" % scene, ou.occlusion_array(gu.to_host(r.queryOcclusion(gu.to_device(p), gu.to_device(nr), BIAS, RADIUS))), pref)
     ou.well_formed(ref)
     return hits, ref
 
@@ -89,22 +48,19 @@ def _check_all(r, scene, of, seed, device=True, n=N_ITEMS):
 def _check_picks(r, scene, of):
     """sdfr_hit_occlusion fed by sdfr_pick's and sdfr_pick_surfaces' device hits of a 9 x 7 frame, nothing leaving the device in between"""
     px = qu.pick_grid(PW, PH)  # every pixel, and a few outside the frame: hit = -1
-    of.width, of.height = PW, PH
-    try:
+    with gu.with_size(of, PW, PH):
         want = ou.oracle_hits(scene, of, qu.oracle_pick(scene, of, px), BIAS, RADIUS)
-    finally:
-        of.width, of.height = W, H
-    picked = r.pick(_dev(px), PW, PH)
-    qu.assert_same("%s occlusion of sdfr_pick's hits" % scene, ou.occlusion_array(_host(r.hitOcclusion(picked, BIAS, RADIUS))), want)
+    picked = r.pick(gu.to_device(px), PW, PH)
+    qu.assert_same("%s occlusion of sdfr_pick's hits" % scene, ou.occlusion_array(gu.to_host(r.hitOcclusion(picked, BIAS, RADIUS))), want)
     frame_hits, _srf = r.pickSurfaces(None, PW, PH, hits=True, device=True)
-    qu.assert_same("%s occlusion of the G-buffer's hits" % scene, ou.occlusion_array(_host(r.hitOcclusion(frame_hits, BIAS, RADIUS))), want[:PW * PH])
+    qu.assert_same("%s occlusion of the G-buffer's hits" % scene, ou.occlusion_array(gu.to_host(r.hitOcclusion(frame_hits, BIAS, RADIUS))), want[:PW * PH])
     assert (want[PW * PH:, 3] == 0xffffffff).all() and not want[PW * PH:, :3].any()
 
 
 @pytest.mark.parametrize("scene", qu.BUILTIN + qu.HLSL)
 def test_occlusion_equals_oracle(renderer, scene):
     of = qu.frame(scene, 1.25 if scene in qu.BUILTIN else 0.5, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     _check_all(renderer, scene, of, seed=zlib.crc32(scene.encode()) & 0xffff)
     _check_picks(renderer, scene, of)
 
@@ -114,8 +70,8 @@ def test_small_sizes_and_alignment(renderer):
 
     scene = "labyrinth"
     of = qu.frame(scene, 0.3, W, H)
-    _setup(renderer, scene, of)
-    L, h = _raw(renderer)
+    gu.setup(renderer, scene, of)
+    L, h = gu.raw(renderer)
     hits = ou.hit_items(scene, of, 5, 65)
     ref = ou.oracle_hits(scene, of, hits, BIAS, RADIUS)
     p, nr, _is = ou.points_of_hits(hits)
@@ -124,15 +80,15 @@ def test_small_sizes_and_alignment(renderer):
     for n in (0, 1, 2, 65):
         qu.assert_same("n = %d" % n, ou.occlusion_array(renderer.hitOcclusion(hits[:n], BIAS, RADIUS)), ref[:n])
         qu.assert_same("n = %d points" % n, ou.occlusion_array(renderer.queryOcclusion(p[:n], nr[:n], BIAS, RADIUS)), pref[:n])
-        qu.assert_same("n = %d (device)" % n, ou.occlusion_array(_host(renderer.hitOcclusion(_hits_dev(hits[:n]), BIAS, RADIUS))), ref[:n])
-        dev = renderer.queryOcclusion(_dev(p[:n].reshape(-1, 3)), _dev(nr[:n].reshape(-1, 3)), BIAS, RADIUS)
-        qu.assert_same("n = %d points (device)" % n, ou.occlusion_array(_host(dev)), pref[:n])
+        qu.assert_same("n = %d (device)" % n, ou.occlusion_array(gu.to_host(renderer.hitOcclusion(_hits_to_device(hits[:n]), BIAS, RADIUS))), ref[:n])
+        dev = renderer.queryOcclusion(gu.to_device(p[:n].reshape(-1, 3)), gu.to_device(nr[:n].reshape(-1, 3)), BIAS, RADIUS)
+        qu.assert_same("n = %d points (device)" % n, ou.occlusion_array(gu.to_host(dev)), pref[:n])
     # records that start 4 bytes past a 16-byte boundary: the word stores; the words around them stay.  The hits likewise off by 4 bytes
     n = 65
     sentinel = 0x7fc12345
     obuf = torch.full((4 * n + 8,), sentinel, dtype=torch.int32, device="cuda")
     hbuf = torch.zeros((12 * n + 4,), dtype=torch.int32, device="cuda")
-    hbuf[1:1 + 12 * n] = _hits_dev(hits).reshape(-1)
+    hbuf[1:1 + 12 * n] = _hits_to_device(hits).reshape(-1)
     assert obuf.data_ptr() % 16 == 0 and hbuf.data_ptr() % 16 == 0
     vp = ctypes.c_void_p
     assert L.sdfr_hit_occlusion(h, n, vp(hbuf.data_ptr() + 4), BIAS, RADIUS, vp(obuf.data_ptr() + 4), 0) == 0
@@ -141,7 +97,7 @@ def test_small_sizes_and_alignment(renderer):
     qu.assert_same("offset records", o[1:1 + 4 * n].reshape(n, 4), ref)
     assert o[0] == sentinel and (o[1 + 4 * n:] == sentinel).all()
     obuf.fill_(sentinel)
-    dp, dn = _dev(p), _dev(nr)
+    dp, dn = gu.to_device(p), gu.to_device(nr)
     assert L.sdfr_query_occlusion(h, n, vp(dp.data_ptr()), vp(dn.data_ptr()), BIAS, RADIUS, vp(obuf.data_ptr() + 4), 0) == 0
     renderer.sync()
     o = obuf.cpu().numpy().view(np.uint32)
@@ -152,7 +108,7 @@ def test_small_sizes_and_alignment(renderer):
 def test_degenerate_items(renderer):
     scene = "labyrinth"
     of = qu.frame(scene, 0.5, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     hits = ou.hit_items(scene, of, 51, 200)
     p, _n, is_item = ou.points_of_hits(hits)
     p = p[is_item][:9].copy()
@@ -175,13 +131,13 @@ def test_debug_plane(renderer):
     v = {"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}
     for scene in ("labyrinth", "dialect_tour"):
         of = qu.frame(scene, 0.75, W, H, v)
-        _setup(renderer, scene, of, v)
+        gu.setup(renderer, scene, of, v)
         hits, ref = _check_all(renderer, scene, of, seed=21, device=False)
         assert (hits[:, 9] == 5).any() and ref[:, 2].any()  # MATERIAL_DISTANCE_PLANE among the items
         v2 = {"show_objects": 0.0, "debug_ny": 1.0}
         renderer.resetVariables()
         of = qu.frame(scene, 0.75, W, H, v2)
-        _setup(renderer, scene, of, v2)
+        gu.setup(renderer, scene, of, v2)
         _check_all(renderer, scene, of, seed=22, device=False)
         renderer.resetVariables()
 
@@ -191,7 +147,7 @@ def test_step_shortcuts_do_not_change_the_mask(renderer, scene):
     of = qu.frame(scene, 0.6, W, H)
     hits = ou.hit_items(scene, of, 33, N_ITEMS)
     ref = ou.oracle_hits(scene, of, hits, BIAS, RADIUS)
-    _setup(renderer, scene, of, shortcuts=True)
+    gu.setup(renderer, scene, of, shortcuts=True)
     on = ou.occlusion_array(renderer.hitOcclusion(hits, BIAS, RADIUS))
     renderer.setStepShortcuts(False)
     off = ou.occlusion_array(renderer.hitOcclusion(hits, BIAS, RADIUS))
@@ -210,7 +166,7 @@ def test_floor_and_wall_is_known_without_the_oracle(renderer):
     renderer.initShaderHlsl("floor_and_wall", ou.FLOOR_AND_WALL)
     renderer.setLimits(**DEFAULT_LIMITS)
     renderer.setStepShortcuts(False)
-    for rec in (renderer.queryOcclusion(*ou.WALL_ITEM, 0.01, 1.0), _host(renderer.queryOcclusion(_dev(ou.WALL_ITEM[0]), _dev(ou.WALL_ITEM[1]), 0.01, 1.0))):
+    for rec in (renderer.queryOcclusion(*ou.WALL_ITEM, 0.01, 1.0), gu.to_host(renderer.queryOcclusion(gu.to_device(ou.WALL_ITEM[0]), gu.to_device(ou.WALL_ITEM[1]), 0.01, 1.0))):
         rec = ou.occlusion_array(rec)
         assert rec[0, 3] == 1
         bits = ou.mask_bits(rec)[0]
@@ -224,7 +180,7 @@ def test_mesh_with_occlusion(renderer, scene):
 
     stime, origin, cell, dims = MESHES[scene]
     of = qu.frame(scene, stime, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     pos, nrm, idx, occ = renderer.extractMesh(origin, cell, dims, occlusion=True)
     plain = renderer.extractMesh(origin, cell, dims)
     for a, b in zip((pos, nrm, idx), plain):  # the mesh itself is sdfr_mesh_extract's
@@ -241,21 +197,15 @@ def test_mesh_with_occlusion(renderer, scene):
     # with the surfaces too, other parameters, everything left on the device
     dpos, dnrm, _didx, dsrf, docc = renderer.extractMesh(origin, cell, dims, surfaces=True, occlusion=True, ao_radius=0.3, ao_bias=0.05, device=True)
     assert tuple(dsrf.shape) == (len(pos), 32)
-    qu.assert_same("%s mesh occlusion, radius 0.3 (device)" % scene, ou.occlusion_array(_host(docc)), ou.oracle_points(scene, of, pos, nrm, 0.05, 0.3))
-
-
-def _raw(r):
-    import sdf_playground_amd as sp
-
-    return sp.load_library(), r._h
+    qu.assert_same("%s mesh occlusion, radius 0.3 (device)" % scene, ou.occlusion_array(gu.to_host(docc)), ou.oracle_points(scene, of, pos, nrm, 0.05, 0.3))
 
 
 def test_arguments(renderer):
     import sdf_playground_amd as sp
 
     scene = "fast_sphere"
-    _setup(renderer, scene, qu.frame(scene, 0.0, W, H))
-    L, h = _raw(renderer)
+    gu.setup(renderer, scene, qu.frame(scene, 0.0, W, H))
+    L, h = gu.raw(renderer)
     buf = np.zeros(64, np.float32)
     hit = np.zeros(4, sp.HIT_DTYPE)
     out = np.full(16, 7, np.uint32)  # what no failing call below may touch
@@ -300,26 +250,17 @@ def test_arguments(renderer):
     assert not out.any()
 
 
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
 def test_occlusion_queries_leave_rendering_alone(renderer):
     scene = "labyrinth"
     of = qu.frame(scene, 0.4, 96, 64)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     hits = ou.hit_items(scene, of, 71, 100)
     p, nr, _is = ou.points_of_hits(hits)
-    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    renderer.hitOcclusion(hits, BIAS, RADIUS)
-    renderer.queryOcclusion(p, nr, BIAS, RADIUS)
-    renderer.hitOcclusion(renderer.pick(_dev(qu.pick_grid(PW, PH)), PW, PH), BIAS, RADIUS)
-    renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), occlusion=True)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, 96, 64):
+        renderer.hitOcclusion(hits, BIAS, RADIUS)
+        renderer.queryOcclusion(p, nr, BIAS, RADIUS)
+        renderer.hitOcclusion(renderer.pick(gu.to_device(qu.pick_grid(PW, PH)), PW, PH), BIAS, RADIUS)
+        renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), occlusion=True)
 
 
 def test_one_handle_across_scene_changes():
@@ -331,12 +272,12 @@ def test_one_handle_across_scene_changes():
         rounds = []
         for scene in ("labyrinth", qu.HLSL[0], "labyrinth"):
             of = qu.frame(scene, 0.5, W, H)
-            _setup(r, scene, of)
+            gu.setup(r, scene, of)
             hits = ou.hit_items(scene, of, 92, 70)
             ref = ou.oracle_hits(scene, of, hits, BIAS, RADIUS)
             got = ou.occlusion_array(r.hitOcclusion(hits, BIAS, RADIUS))
             qu.assert_same("%s hits" % scene, got, ref)
-            qu.assert_same("%s hits (device)" % scene, ou.occlusion_array(_host(r.hitOcclusion(_hits_dev(hits), BIAS, RADIUS))), ref)
+            qu.assert_same("%s hits (device)" % scene, ou.occlusion_array(gu.to_host(r.hitOcclusion(_hits_to_device(hits), BIAS, RADIUS))), ref)
             rounds.append(got)
         assert np.array_equal(rounds[0], rounds[2]) and rounds[0][:, 2].any()
     finally:
@@ -349,14 +290,14 @@ def test_two_frames_in_flight(renderer):
 
     scene, w, h = "labyrinth", 128, 72
     of = qu.frame(scene, 0.4, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     hits = ou.hit_items(scene, of, 13, 70)
     ref = ou.oracle_hits(scene, of, hits, BIAS, RADIUS)
     img_ref = renderer.render(None, w, h)
     renderer.setFramesInFlight(2)
     try:
         imgs = [torch.empty((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-        dh = _hits_dev(hits)
+        dh = _hits_to_device(hits)
         got = []
         for k in range(4):
             renderer.render(None, w, h, out=imgs[k % 2])

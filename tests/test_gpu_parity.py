@@ -5,103 +5,13 @@ Bar (BASELINE.json north_star): <= 1e-4 per-channel L-infinity on the fp32 RGBA 
 Because oracle and kernels share one arithmetic contract the frames are expected to be
 bit-identical; the tests assert the stated tolerance and additionally require bit equality
 of the per-pixel ray / march-evaluation / hit counters."""
-import math
-
 import numpy as np
 import pytest
 
+from gpu_util import DEFAULT_LIMITS, PARITY_H as H, PARITY_TOL as TOL, PARITY_W as W, parity_compare as _compare, parity_setup as _setup
+from gpu_util import renderer  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4
-W, H = 240, 160
-TH = 0.3
-
-
-def _cameras(oracle):
-    fovy = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
-    asp = np.float32(W) / np.float32(H)
-    return {
-        "fast_sphere": ("lookat", (0, 2, -3), (0, 1, 0)),
-        "cube_sea": ("dir", (3 * math.cos(TH), 4.5, 3 * math.sin(TH)), (math.cos(TH + 0.6), -0.45, math.sin(TH + 0.6))),
-        "labyrinth": ("dir", (1.5 * math.cos(TH), 5.0, 1.5 * math.sin(TH)), (math.cos(TH), -0.35, math.sin(TH))),
-        "fractal": ("lookat", (2.2 * math.cos(TH), 1.6, 2.2 * math.sin(TH)), (0, 1, 0)),
-        "lense": ("lookat", (7 * math.sin(-0.3), 0.5, 7 * math.cos(-0.3)), (0, 0, 0)),
-        "gems": ("lookat", (2.5 * math.cos(TH), 2, 2.5 * math.sin(TH)), (0, 1, 0)),
-        "light_shadows": ("lookat", (0, 5, -9), (0, 1, 0)),
-        "cube": ("lookat", (2.5, 2.5, -3), (0, 1, 0)),
-        "gyroid": ("lookat", (1.8, 1.6, -2.2), (0, 0, 0)),
-        "basic_transparency": ("lookat", (2.0, 2.5, -4), (0, 2, 0)),
-        "basic_clouds": ("lookat", (0, 2, -8), (0, 4, 0)),
-        "coordinate_material": ("lookat", (3, 4, -5), (0, 2, 0)),
-        "distortion": ("lookat", (0.8, 1.8, -2.5), (0, 1.5, 0)),
-        "table": ("lookat", (2, 2, -3), (0, 1, 0)),
-        "sierpinski": ("lookat", (1.2, 1.6, -2.2), (0, 1.2, 0)),
-        "neon": ("lookat", (-2, 2.5, -3.5), (0, 2, 1)),
-        "fractal2": ("lookat", (1.8, 1.8, -2.0), (0, 1, 0)),
-        "shell": ("lookat", (-2.2, 1.8, -2.0), (0, 1, 0)),
-        "spiral": ("lookat", (0, 4, -12), (0, 3, 0)),
-        "terrain": ("lookat", (6, 5, -8), (0, 0, 0)),
-        "tiling": ("lookat", (0, 4.5, -9), (0, 4, 0)),
-        "tree": ("lookat", (0, 2.2, -4), (0, 1, 1)),
-    }, fovy, asp
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
-
-def _setup(renderer, oracle, scene, stime, limits=None, variables=None):
-    import sdf_playground_amd as sp
-
-    cams, fovy, asp = _cameras(oracle)
-    kind, eye, tgt = cams[scene]
-    basis = (oracle.camera_lookat if kind == "lookat" else oracle.camera_direction)(eye, tgt, fovy, asp)
-    f = oracle.default_frame(scene, W, H, basis=basis, stime=stime)
-    renderer.initShader(scene)
-    renderer.setParameters(stime)
-    cam = sp.Camera()
-    cam.SetEye(eye)
-    (cam.SetLookat if kind == "lookat" else cam.SetDirection)(tgt)
-    cam.SetFOVY(float(fovy))
-    cam.SetAspect(float(asp))
-    renderer.setCamera(cam)
-    # the C++ host camera must reproduce the oracle's (and the reference's) basis bit for bit
-    assert np.array_equal(renderer.getCameraBasis().view(np.uint32), basis.view(np.uint32))
-    renderer.setLimits(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                       extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-    if limits:
-        renderer.setLimits(**limits)
-        for k, v in limits.items():
-            setattr(f, k, v)
-    if variables:
-        table = {r[0]: r for r in oracle.var_table(scene)}
-        for k, v in variables.items():
-            assert renderer.setValue(k, v)
-            slot = table[k][6]
-            if slot >= 0:
-                f.scene_var[slot] = v
-            else:
-                setattr(f, k, v)
-    return f
-
-
-def _compare(renderer, oracle, scene, f, schedule):
-    renderer.setSchedule(schedule)
-    img, st = renderer.render(None, W, H, pixel_stats=True)
-    ref, rst, tot = oracle.render(scene, f, stats=True)
-    assert not np.isnan(img).any()
-    diff = np.abs(img.astype(np.float64) - ref.astype(np.float64)).max()
-    assert diff <= TOL, "%s: L-inf %g" % (scene, diff)
-    assert np.array_equal(st, rst), "%s: per-pixel ray/eval/hit counters differ" % scene
-    s = renderer.getStats()
-    assert (s.pixels, s.rays, s.march_evals, s.hits) == tuple(int(x) for x in tot)
-    return np.array_equal(img.view(np.uint32), ref.view(np.uint32))
-
 
 SCENES = ["fast_sphere", "cube_sea", "labyrinth", "fractal", "lense", "gems", "light_shadows", "cube", "gyroid", "basic_transparency",
           "basic_clouds", "coordinate_material", "distortion", "table", "sierpinski", "neon", "fractal2", "shell", "spiral", "terrain",
@@ -326,8 +236,7 @@ def test_kernels_reproduce_256x256_digests(renderer, case):
     renderer.setParameters(case["stime"])
     # every limit, also the extensions and the epsilons: the handle is shared by the module's tests, and whatever ran before this one
     # (which depends on the -k selection) must not leak into the digests
-    renderer.setLimits(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                       extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
+    renderer.setLimits(**DEFAULT_LIMITS)
     renderer.resetVariables()
     renderer.setLimits(**case["limits"])
     cam = sp.Camera()          # Application.cpp:214-224

@@ -5,16 +5,9 @@ import math
 import numpy as np
 import pytest
 
+from gpu_util import renderer  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 def _check(renderer, oracle, scene16):

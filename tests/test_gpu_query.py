@@ -9,7 +9,9 @@ import zlib
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import query_util as qu
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -17,42 +19,6 @@ N_POINTS = 20000
 N_RAYS = 2000
 W, H = 64, 48
 SCENES_DIR = qu.SCENES_DIR
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
-
-def _load(r, scene):
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-
-
-def _setup(r, scene, of, variables=None, load=True):
-    """the handle's state = the oracle frame `of`"""
-    if load:
-        _load(r, scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
-    for name, v in (variables or {}).items():
-        assert r.setValue(name, v)
-
-
-def _torch_dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _check_all(r, scene, of, seed, device=True):
@@ -70,14 +36,14 @@ def _check_all(r, scene, of, seed, device=True):
     p_ref = qu.oracle_pick(scene, of, px)
     qu.assert_same("%s pick (host)" % scene, qu.hits_array(r.pick(px, W, H)), p_ref)
     if device:
-        dd = r.queryDistance(_torch_dev(pts))  # without normals
-        hd = r.queryRays(_torch_dev(o), _torch_dev(dirs))
-        pd = r.pick(_torch_dev(px), W, H)
+        dd = r.queryDistance(gu.to_device(pts))  # without normals
+        hd = r.queryRays(gu.to_device(o), gu.to_device(dirs))
+        pd = r.pick(gu.to_device(px), W, H)
         torch.cuda.synchronize()
         qu.assert_same("%s distance (device)" % scene, dd.cpu().numpy(), d_ref)
         qu.assert_same("%s rays (device)" % scene, qu.hits_array(hd.cpu().numpy()), h_ref)
         qu.assert_same("%s pick (device)" % scene, qu.hits_array(pd.cpu().numpy()), p_ref)
-        dn, nn = r.queryDistance(_torch_dev(pts), normals=True)
+        dn, nn = r.queryDistance(gu.to_device(pts), normals=True)
         torch.cuda.synchronize()
         qu.assert_same("%s normal (device)" % scene, nn.cpu().numpy(), n_ref)
     return h_ref, p_ref
@@ -86,21 +52,21 @@ def _check_all(r, scene, of, seed, device=True):
 @pytest.mark.parametrize("scene", qu.BUILTIN)
 def test_builtin_queries_equal_oracle(renderer, scene):
     of = qu.frame(scene, 1.25, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     _check_all(renderer, scene, of, seed=zlib.crc32(scene.encode()) & 0xffff)
 
 
 @pytest.mark.parametrize("scene", sorted(qu.MOVED_VARS))
 def test_queries_with_moved_variables(renderer, scene):
     of = qu.frame(scene, 0.5, W, H, qu.MOVED_VARS[scene])
-    _setup(renderer, scene, of, qu.MOVED_VARS[scene])
+    gu.setup(renderer, scene, of, qu.MOVED_VARS[scene])
     _check_all(renderer, scene, of, seed=11, device=False)
 
 
 def test_debug_plane_and_hidden_objects(renderer):
     v = {"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}
     of = qu.frame("labyrinth", 0.75, W, H, v)
-    _setup(renderer, "labyrinth", of, v)
+    gu.setup(renderer, "labyrinth", of, v)
     _check_all(renderer, "labyrinth", of, seed=21, device=False)
     renderer.resetVariables()
 
@@ -108,7 +74,7 @@ def test_debug_plane_and_hidden_objects(renderer):
 @pytest.mark.parametrize("scene", qu.HLSL)
 def test_runtime_scenes_equal_oracle(renderer, scene):
     of = qu.frame(scene, 0.5, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     _check_all(renderer, scene, of, seed=31)
 
 
@@ -127,7 +93,7 @@ def test_pendulum_hlsl_equals_its_cpp_twin():
                 r.initShaderHlsl("pendulum_hlsl", os.path.join(SCENES_DIR, "pendulum.hlsl"))
             else:
                 r.initShaderSource("pendulum_cpp", os.path.join(SCENES_DIR, "pendulum.scene.h"))
-            _setup(r, None, of, load=False)
+            gu.setup(r, None, of, load=False)
             d, n = r.queryDistance(pts, normals=True)
             out.append((d, n, qu.hits_array(r.queryRays(o, dirs)), qu.hits_array(r.pick(px, W, H))))
         finally:
@@ -141,13 +107,13 @@ def test_pendulum_hlsl_equals_its_cpp_twin():
 def test_runtime_query_module_follows_the_scene(renderer):
     # a built-in scene after a run-time one uses the built-in kernels; a second run-time scene gets its own query module
     of = qu.frame("labyrinth", 0.3, W, H)
-    _setup(renderer, "noise_lod", qu.frame("noise_lod", 0.3, W, H))
+    gu.setup(renderer, "noise_lod", qu.frame("noise_lod", 0.3, W, H))
     renderer.queryDistance(np.zeros((4, 3), np.float32))
-    _setup(renderer, "labyrinth", of)
+    gu.setup(renderer, "labyrinth", of)
     _check_all(renderer, "labyrinth", of, seed=51, device=False)
     for scene in ("noise_lod", "dialect_tour"):
         of = qu.frame(scene, 0.3, W, H)
-        _setup(renderer, scene, of)
+        gu.setup(renderer, scene, of)
         _check_all(renderer, scene, of, seed=52, device=False)
 
 
@@ -186,7 +152,7 @@ def _switch_answers(r, inputs, device):
     """a point query with normals, a ray query, a pick, a mesh extraction with normals and a render with pixel_stats"""
     import torch
 
-    pts, o, dirs, px = (_torch_dev(a) for a in inputs) if device else inputs
+    pts, o, dirs, px = (gu.to_device(a) for a in inputs) if device else inputs
     d, n = r.queryDistance(pts, normals=True)
     rays, picks = r.queryRays(o, dirs), r.pick(px, SW_W, SW_H)
     pos, nrm, idx = r.extractMesh(*SW_GRID, device=device)
@@ -210,7 +176,7 @@ def test_one_handle_from_a_builtin_scene_to_a_runtime_scene_and_back():
         rounds = []
         for scene in ("labyrinth", qu.HLSL[0], "labyrinth"):
             of, inputs, want = _switch_reference(scene)
-            _setup(r, scene, of)
+            gu.setup(r, scene, of)
             rounds.append([])
             for device in (False, True):
                 got = _switch_answers(r, inputs, device)
@@ -228,7 +194,7 @@ def test_one_handle_from_a_builtin_scene_to_a_runtime_scene_and_back():
 @pytest.mark.parametrize("scene", ["labyrinth", "lense", "cube_sea"])
 def test_step_shortcuts_keep_hits(renderer, scene):
     of = qu.frame(scene, 0.25, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     o, dirs = qu.ray_samples(of, 61, N_RAYS)
     px = qu.pick_grid(W, H)
     exact = qu.hits_array(renderer.queryRays(o, dirs))
@@ -248,30 +214,21 @@ def test_step_shortcuts_keep_hits(renderer, scene):
 def test_pick_misses_where_the_render_does(renderer, scene):
     w, h = 160, 96
     of = qu.frame(scene, 0.6, w, h)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     _, st = renderer.render(None, w, h, pixel_stats=True)
     hits = renderer.pick(qu.pick_grid(w, h)[: w * h], w, h)
     assert np.array_equal((hits["hit"] == 0).reshape(h, w), st[..., 2] == 0)
 
 
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
 def test_queries_leave_rendering_alone(renderer):
     scene = "labyrinth"
     of = qu.frame(scene, 0.4, 96, 64)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     o, dirs = qu.ray_samples(of, 71, 500)
-    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    renderer.queryRays(o, dirs)
-    renderer.pick(qu.pick_grid(32, 16), 32, 16)
-    renderer.queryDistance(o, normals=True)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, 96, 64):
+        renderer.queryRays(o, dirs)
+        renderer.pick(qu.pick_grid(32, 16), 32, 16)
+        renderer.queryDistance(o, normals=True)
 
 
 def test_two_frames_in_flight(renderer):
@@ -279,7 +236,7 @@ def test_two_frames_in_flight(renderer):
 
     scene = "lense"
     of = qu.frame(scene, 0.9, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     o, dirs = qu.ray_samples(of, 81, 1000)
     ref = qu.hits_array(renderer.queryRays(o, dirs))
     img_ref = renderer.render(None, 128, 72)
@@ -290,7 +247,7 @@ def test_two_frames_in_flight(renderer):
         for k in range(4):
             renderer.render(None, 128, 72, out=imgs[k % 2])
             got.append(qu.hits_array(renderer.queryRays(o, dirs)))
-            dev = renderer.queryRays(_torch_dev(o), _torch_dev(dirs))
+            dev = renderer.queryRays(gu.to_device(o), gu.to_device(dirs))
             renderer.waitFrame(torch.cuda.current_stream().cuda_stream)
             renderer.sync()
             got.append(qu.hits_array(dev.cpu().numpy()))
@@ -310,7 +267,7 @@ def test_sizes_and_arguments(renderer):
     L = sp.load_library()
     scene = "fast_sphere"
     of = qu.frame(scene, 0.0, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     h = renderer._h
     buf = np.zeros(64, np.float32)
     p = buf.ctypes.data_as(ctypes.c_void_p)
@@ -341,14 +298,14 @@ def test_sizes_and_arguments(renderer):
     n = 2 ** 22 + 17
     rng = np.random.default_rng(5)
     pts = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-    d = renderer.queryDistance(_torch_dev(pts))
+    d = renderer.queryDistance(gu.to_device(pts))
     torch.cuda.synchronize()
     d = d.cpu().numpy()
     k = np.r_[0:300, n - 300:n]
     d_ref, _ = qu.oracle_points(scene, of, pts[k], normals=False)
     qu.assert_same("large n", d[k], d_ref)
     dirs = np.repeat(np.array([[0.0, -1.0, 0.3]], np.float32), n, 0)
-    hd = renderer.queryRays(_torch_dev(pts), _torch_dev(dirs))
+    hd = renderer.queryRays(gu.to_device(pts), gu.to_device(dirs))
     torch.cuda.synchronize()
     hd = qu.hits_array(hd.cpu().numpy())
     qu.assert_same("large n rays", hd[k], qu.oracle_rays(scene, of, pts[k], dirs[k]))
@@ -361,7 +318,7 @@ def test_item_offsets_past_32_bits(renderer):
 
     scene = "fast_sphere"
     of = qu.frame(scene, 0.0, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     n = (1 << 32) // 3 + 1000
     tail = np.random.default_rng(9).uniform(-3, 3, (1000, 3)).astype(np.float32)
     pts = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
@@ -381,7 +338,7 @@ def test_item_offsets_past_32_bits(renderer):
 def test_device_tensors_are_checked(renderer):
     import torch
 
-    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    gu.setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
     pts = torch.zeros((8, 3), dtype=torch.float32, device="cuda")
     with pytest.raises(TypeError):
         renderer.queryDistance(pts.to(torch.int32))

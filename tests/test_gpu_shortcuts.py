@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 from shortcut_scenes import ALL_SCENES, INLINE_ESCAPED_SHADOWS
-from test_gpu_parity import _setup
+from gpu_util import parity_setup as _setup
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -13,15 +14,6 @@ VIEWS = [  # eye, look-at: above the cubes looking over them, from the floor up,
     ((3.0, 4.5, 1.0), (6.0, 3.2, 4.0)), ((0.3, 0.4, 0.2), (2.0, 3.0, 1.5)), ((1.0, 9.0, 1.0), (1.2, 0.0, 1.1)),
     ((0.0, 2.0, 0.0), (8.0, 2.1, 3.0)), ((30.0, 6.0, -25.0), (0.0, 2.0, 0.0)), ((2.0, 3.7, 2.0), (9.0, 3.9, 2.5)),
 ]
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
 
 
 def _render(r, oracle, scene, eye, at, w, h, stime, limits, shortcuts):

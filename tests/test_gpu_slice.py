@@ -4,25 +4,23 @@ queryDistance for the run-time probe scene; geometric bounds on a sphere and a p
 effects on rendering; the argument errors through the raw C ABI."""
 import ctypes
 import math
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
+import mesh_survey_util as msu
 import query_util as qu
 import slice_util as su
-from test_gpu_mesh_survey import DEFAULT_LIMITS, PROBE
+from gpu_util import renderer  # noqa: F401
+from slice_util import CASES
 
 pytestmark = pytest.mark.gpu
 
 W, H = 64, 48
 # horizontal planes (u = x, v = z, layers upwards), 37 x 29 cells in 5 layers: ragged against 8 x 8 tiles, 64-lane waves and 256-thread
-# blocks alike.  Per scene: time, the low corner (x, z), the cell, the height of layer 0 and the step between layers -- a box the
-# scene's solid crosses in every layer
+# blocks alike, over the boxes of slice_util.CASES
 DIMS, LAYERS = (37, 29), 5
-CASES = {"fast_sphere": (0.0, (-0.92, -0.72), 0.05, 0.62, 0.17), "labyrinth": (1.25, (-5.35, -2.55), 0.05, 0.37, 0.23),
-         "gyroid": (0.5, (-0.92, -0.72), 0.05, -0.2, 0.23), "sierpinski": (0.5, (-0.75, -0.55), 0.04, 1.02, 0.11),
-         "noise_lod": (0.5, (-0.92, -0.72), 0.05, 0.4, 0.4)}
 
 
 def axis_grid(scene):
@@ -37,49 +35,15 @@ def oblique_grid(scene):
                 dw=(0.4 * cell, 0.9 * dy, -0.3 * cell), dims=DIMS, layers=LAYERS)
 
 
-def _setup(r, scene, of):
-    """the handle's state = the oracle frame `of`"""
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
-
-
 def _probe(r, **values):
-    """the probe scene of tests/test_gpu_mesh_survey.py with its variables set; -> distance(grid) by the library's own point query"""
-    if r.currentScene() != "slice_probe":
-        r.initShaderSource("slice_probe", PROBE)
-        r.setLimits(**DEFAULT_LIMITS)
-    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
-        assert r.setValue(name, v)
+    """the probe scene (mesh_survey_util.PROBE) with its variables set; -> distance(grid) by the library's own point query"""
+    msu.load_probe(r, "slice_probe", msu.PROBE_DEFAULTS, **values)
     return lambda g: r.queryDistance(su.lattice_points(g["origin"], g["du"], g["dv"], g["dw"], g["dims"], g["layers"]))
-
-
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
-
-def _host(a):
-    return a.cpu().numpy() if hasattr(a, "data_ptr") else a
 
 
 def _assert_same(what, got, want, coords=True):
     """got: extractSlices' five; want: the restatement's five"""
-    pos, uv, seg, lv, ls = (_host(a) if a is not None else None for a in got)
+    pos, uv, seg, lv, ls = (gu.to_host(a, sync=False) if a is not None else None for a in got)
     assert pos.shape == want[0].shape and seg.shape == want[2].shape, (what, pos.shape, want[0].shape, seg.shape, want[2].shape)
     qu.assert_same("%s positions" % (what,), pos, want[0])
     if coords:
@@ -100,7 +64,7 @@ def _want(scene, of, g, iso=0.0):
 @pytest.mark.parametrize("scene", sorted(CASES))
 def test_slices_equal_the_definition(renderer, scene):
     of = qu.frame(scene, CASES[scene][0], W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     for what, g in (("axis", axis_grid(scene)), ("oblique", oblique_grid(scene))):
         D, want = _want(scene, of, g)
         assert len(want[0]) > 100 and (np.diff(want[3]) > 0).sum() >= 3, (what, len(want[0]), want[3])
@@ -120,7 +84,7 @@ def test_one_large_layer(renderer):
     """300 x 250 cells: 75 551 points pass 256^2, so both prefix sums recurse on their block totals"""
     scene = "gyroid"
     of = qu.frame(scene, 0.5, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     g = dict(origin=(-1.5, 0.3, -1.25), du=(0.01, 0.0, 0.0), dv=(0.0, 0.0, 0.01), dw=(0.0, 0.0, 0.0), dims=(300, 250), layers=1)
     assert 301 * 251 + 1 > 256 * 256
     D, want = _want(scene, of, g)
@@ -136,7 +100,7 @@ def test_tallest_stack(renderer):
     """65 536 layers of one cell: a wave per layer with four points, and 65 537 offsets per layer array"""
     scene = "fast_sphere"
     of = qu.frame(scene, 0.0, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     g = dict(origin=(-1.5, -0.2, -0.9), du=(0.07, 0.0, 0.01), dv=(0.0, 0.02, 0.06), dw=(3.0 / 65536, 2.2 / 65536, 1.8 / 65536), dims=(1, 1), layers=65536)
     D, want = _want(scene, of, g)
     assert len(want[0]) > 1000 and len(want[3]) == 65537
@@ -250,7 +214,7 @@ def test_capacities_and_the_counting_call(renderer):
     L = sp.load_library()
     scene = "fast_sphere"
     of = qu.frame(scene, CASES[scene][0], W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     g = axis_grid(scene)
     _D, want = _want(scene, of, g)
     V, S = len(want[0]), len(want[2])
@@ -295,18 +259,14 @@ def test_slices_leave_rendering_alone(renderer):
 
     scene = "labyrinth"
     of = qu.frame(scene, CASES[scene][0], W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     g, corner = axis_grid(scene), (-5.35, -0.3, -2.55)
     _D, want = _want(scene, of, g)
-    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    _assert_same("host", renderer.extractSlices(**g), want)
-    got = renderer.extractSlices(device=True, **g)
-    renderer.sync()
-    _assert_same("device", got, want)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, W, H) as (img0, s0):
+        _assert_same("host", renderer.extractSlices(**g), want)
+        got = renderer.extractSlices(device=True, **g)
+        renderer.sync()
+        _assert_same("device", got, want)
     # the stage timings stay the last mesh extraction's: a slice records none
     ms = (ctypes.c_double * 4)()
     import sdf_playground_amd as sp
@@ -333,7 +293,7 @@ def test_slices_leave_rendering_alone(renderer):
             _assert_same(("device", k), dev, want)
             _assert_same(("host", k), host, want, coords=False)
             assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
-            assert _stats(renderer) == s0
+            assert gu.stats(renderer) == s0
     finally:
         renderer.setFramesInFlight(1)
 
@@ -342,7 +302,7 @@ def test_arguments(renderer):
     import sdf_playground_amd as sp
 
     L = sp.load_library()
-    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    gu.setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
     h = renderer._h
     INVALID, NO_SCENE = -1, -4
     NULL_POINTER, BAD_ON_HOST, BAD_GRID = "null pointer", "on_host must be 0 or 1", "bad slice grid"

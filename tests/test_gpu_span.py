@@ -4,15 +4,17 @@ dialect scene, the debug kernel variant included; analytic chords, a plane and a
 meshThickness; the capacity rule, also into arrays off their alignment; no side effects on rendering; the argument errors through the
 raw C ABI."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
+import mesh_survey_util as msu
 import query_util as qu
 import span_util as su
-from test_gpu_mesh_survey import DEFAULT_LIMITS, PROBE
-from test_gpu_slice import CASES
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
+from slice_util import CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -24,52 +26,20 @@ MIN_STEP, MAX_STEPS = 0.05, 128
 RANGE = DEFAULT_LIMITS["range"]
 
 
-def _setup(r, scene, of):
-    """the handle's state = the oracle frame `of`"""
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(qu.SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**DEFAULT_LIMITS)
-    r.setStepShortcuts(False)
-
-
 def _probe(r, **values):
-    """the probe scene of tests/test_gpu_mesh_survey.py with its variables set"""
-    if r.currentScene() != "span_probe":
-        r.initShaderSource("span_probe", PROBE)
-        r.setLimits(**DEFAULT_LIMITS)
-    for name, v in dict(dict(kind=0.0, cx=0.0, cy=0.0, cz=0.0, radius=1.0, height=0.25, split=0.3), **values).items():
-        assert r.setValue(name, v)
+    """the probe scene (mesh_survey_util.PROBE) with its variables set"""
+    msu.load_probe(r, "span_probe", msu.PROBE_DEFAULTS, **values)
 
 
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
-
-def _host(got):
+def _records(got):
     """(summaries, spans) of either path as numpy: SUMMARY_DTYPE records [n], float32 [n, max_spans, 2]"""
-    s, sp = got
-    if hasattr(s, "data_ptr"):
-        s, sp = s.cpu().numpy().view(su.SUMMARY_DTYPE).reshape(-1), sp.cpu().numpy()
-    return s.view(su.SUMMARY_DTYPE), sp
+    s, sp = gu.to_host(got, sync=False)
+    return s.view(su.SUMMARY_DTYPE).reshape(-1), sp
 
 
 def _assert_same(what, got, want, first=None):
     """every word of every item; first: `want` holds more items, of which `got` are the first ones"""
-    s, sp = _host(got)
+    s, sp = _records(got)
     ws, wsp = want if first is None else (want[0][:first], want[1][:first])
     assert s.shape == ws.shape and sp.shape == wsp.shape, (what, s.shape, ws.shape, sp.shape, wsp.shape)
     qu.assert_same("%s summaries" % (what,), np.ascontiguousarray(s).view(np.uint32).reshape(-1, 8), np.ascontiguousarray(ws).view(np.uint32).reshape(-1, 8))
@@ -94,7 +64,7 @@ def test_spans_equal_the_definition(renderer, scene):
 
     stime, (x0, z0), cell, y0, _dy = CASES[scene]
     of = qu.frame(scene, stime, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     D = _distance(scene, of)
     kw = dict(min_step=MIN_STEP, max_steps=MAX_STEPS)
     finished = []
@@ -174,7 +144,7 @@ def test_spans_equal_the_definition(renderer, scene):
 def test_debug_plane_and_show_objects(renderer):
     """the DBG kernel variant: the debug plane and show_objects apply as they do in sdfr_query_distance"""
     for scene in ("labyrinth", "dialect_tour"):
-        _setup(renderer, scene, qu.frame(scene, 0.75, W, H))  # (the scene is loaded once: the two frames differ in their variables alone)
+        gu.setup(renderer, scene, qu.frame(scene, 0.75, W, H))  # (the scene is loaded once: the two frames differ in their variables alone)
         for variables in ({"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}, {"show_objects": 0.0, "debug_ny": 1.0}):
             of = qu.frame(scene, 0.75, W, H, variables)
             for name, v in variables.items():
@@ -298,7 +268,7 @@ def test_capacity_rule_on_the_labyrinth(renderer):
 
     scene = "labyrinth"
     of = qu.frame(scene, CASES[scene][0], W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     # of a seeded pool of rays through the labyrinth, those that pass through more than three of its walls
     o, d = qu.ray_samples(of, 7, 400)
     p = su.params(0.02, 30.0, max_steps=1024, max_spans=16)
@@ -334,21 +304,17 @@ def test_spans_leave_rendering_alone(renderer):
 
     scene = "labyrinth"
     of = qu.frame(scene, CASES[scene][0], W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     o, d = qu.ray_samples(of, 9, 130)
     p = su.params(MIN_STEP, RANGE, 0.0, MAX_STEPS, 3)
     want = su.march_spans(_distance(scene, of), o, d, p)
     kw = dict(min_step=MIN_STEP, max_steps=MAX_STEPS, max_spans=3)
-    img0, st0 = renderer.render(None, W, H, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    _assert_same("host", renderer.querySpans(o, d, **kw), want)
-    dev = renderer.querySpans(o, d, device=True, **kw)
-    renderer.pickSpans(None, FW, FH, **kw)
-    renderer.sync()
-    _assert_same("device", dev, want)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, W, H, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, W, H) as (img0, s0):
+        _assert_same("host", renderer.querySpans(o, d, **kw), want)
+        dev = renderer.querySpans(o, d, device=True, **kw)
+        renderer.pickSpans(None, FW, FH, **kw)
+        renderer.sync()
+        _assert_same("device", dev, want)
     # two frames in flight: the call runs on the lane of the frame submitted last
     renderer.setFramesInFlight(2)
     try:
@@ -361,7 +327,7 @@ def test_spans_leave_rendering_alone(renderer):
             _assert_same(("device", k), dev, want)
             _assert_same(("host", k), host, want)
             assert np.array_equal(imgs[k % 2].cpu().numpy().view(np.uint32), img0.view(np.uint32))
-            assert _stats(renderer) == s0
+            assert gu.stats(renderer) == s0
     finally:
         renderer.setFramesInFlight(1)
 
@@ -370,7 +336,7 @@ def test_arguments(renderer):
     import sdf_playground_amd as sp
 
     L = sp.load_library()
-    _setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
+    gu.setup(renderer, "fast_sphere", qu.frame("fast_sphere", 0.0, W, H))
     h = renderer._h
     INVALID, NO_SCENE = -1, -4
     NULL_POINTER, BAD_ON_HOST, BAD_PARAMS, BAD_COUNT = "null pointer", "on_host must be 0 or 1", "bad span parameters", "bad item count"

@@ -5,75 +5,30 @@ frame (no pixel list, 8 x 8 tiles) against the pixel list; the mesh with surface
 awkward sizes, the word-store path, argument checks; no side effects on rendering; one handle across scene changes; and the
 renderer's own pixels where a pixel is its unlit colour."""
 import ctypes
-import os
 import zlib
 
 import numpy as np
 import pytest
 
+import gpu_util as gu
 import query_util as qu
 import surface_util as su
+from gpu_util import DEFAULT_LIMITS
+from gpu_util import renderer  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 N_RAYS = 2000
 W, H = 64, 48
 FW, FH = 61, 45  # the whole frame: ragged 8 x 8 tiles on both edges
-SCENES_DIR = qu.SCENES_DIR
-DEFAULT_LIMITS = dict(iter_count=100, bounce_count=16, ray_count=8, light_count=8, range=100.0, max_cost_default=7, extension_lights=0,
-                      extension_marble_reflection=0.0, dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
 # the meshes: about 24^3 cells, no axis a multiple of the lattice kernel's brick.  On the fast_sphere grid the oracle finds a surface
 # under every vertex (checked on the CPU before the grid was fixed; the test asserts >= 99 %)
 MESHES = {"fast_sphere": (0.0, (-1.55, -0.3, -1.55), 0.13, (24, 23, 25)), "debug_materials": (0.4, (-2.05, -0.3, -1.55), 0.17, (24, 23, 25))}
 
 
-@pytest.fixture(scope="module")
-def renderer():
-    import sdf_playground_amd as sp
-
-    r = sp.SDFRenderer(0)
-    yield r
-    r.close()
-
-
-def _load(r, scene):
-    if scene in qu.HLSL:
-        r.initShaderHlsl(scene, os.path.join(SCENES_DIR, scene + ".hlsl"))
-    else:
-        r.initShader(scene)
-
-
-def _setup(r, scene, of, variables=None, limits=None):
-    """the handle's state = the oracle frame `of`"""
-    _load(r, scene)
-    r.setParameters(of.stime)
-    r.setCameraBasis(of.eye, of.front, of.right, of.top)
-    r.setLimits(**dict(DEFAULT_LIMITS, **(limits or {})))
-    r.setStepShortcuts(False)
-    for name, v in (variables or {}).items():
-        assert r.setValue(name, v)
-
-
-def _torch_dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _host(pair):
-    """(hits, surfaces) of a device call -> numpy"""
-    import torch
-
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in pair)
-
-
 def _frame_oracle(scene, of, w, h):
-    of.width, of.height = w, h
-    try:
+    with gu.with_size(of, w, h):
         return su.oracle_pick(scene, of, su.frame_pixels(w, h))
-    finally:
-        of.width, of.height = W, H
 
 
 def _check_all(r, scene, of, seed, device=True):
@@ -95,23 +50,23 @@ def _check_all(r, scene, of, seed, device=True):
     # without hits: the same surfaces
     qu.assert_same("%s rays, hits = NULL" % scene, su.surfaces_array(r.queryRaySurfaces(o, dirs)), ray_ref[1])
     if device:
-        su.assert_same("%s rays (device)" % scene, _host(r.queryRaySurfaces(_torch_dev(o), _torch_dev(dirs), hits=True)), ray_ref)
-        su.assert_same("%s pick (device)" % scene, _host(r.pickSurfaces(_torch_dev(px), W, H, hits=True)), pick_ref)
-        su.assert_same("%s frame (device)" % scene, _host(r.pickSurfaces(None, FW, FH, hits=True, device=True)), frame_ref)
+        su.assert_same("%s rays (device)" % scene, gu.to_host(r.queryRaySurfaces(gu.to_device(o), gu.to_device(dirs), hits=True)), ray_ref)
+        su.assert_same("%s pick (device)" % scene, gu.to_host(r.pickSurfaces(gu.to_device(px), W, H, hits=True)), pick_ref)
+        su.assert_same("%s frame (device)" % scene, gu.to_host(r.pickSurfaces(None, FW, FH, hits=True, device=True)), frame_ref)
     return ray_ref, pick_ref
 
 
 @pytest.mark.parametrize("scene", qu.BUILTIN + qu.HLSL)
 def test_surfaces_equal_oracle(renderer, scene):
     of = qu.frame(scene, 1.25 if scene in qu.BUILTIN else 0.5, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     _check_all(renderer, scene, of, seed=zlib.crc32(scene.encode()) & 0xffff)
 
 
 @pytest.mark.parametrize("scene", sorted(qu.MOVED_VARS))
 def test_surfaces_with_moved_variables(renderer, scene):
     of = qu.frame(scene, 0.5, W, H, qu.MOVED_VARS[scene])
-    _setup(renderer, scene, of, qu.MOVED_VARS[scene])
+    gu.setup(renderer, scene, of, qu.MOVED_VARS[scene])
     _check_all(renderer, scene, of, seed=11, device=False)
     renderer.resetVariables()
 
@@ -119,13 +74,13 @@ def test_surfaces_with_moved_variables(renderer, scene):
 def test_debug_plane_and_marble_reflection(renderer):
     v = {"debug_nx": 0.3, "debug_ny": 1.0, "debug_y": 0.4}
     of = qu.frame("labyrinth", 0.75, W, H, v)
-    _setup(renderer, "labyrinth", of, v)
+    gu.setup(renderer, "labyrinth", of, v)
     _rays, (ph, ps) = _check_all(renderer, "labyrinth", of, seed=21, device=False)
     assert (ps[:, 0] == 5).any()  # MATERIAL_DISTANCE_PLANE
     renderer.resetVariables()
     of = qu.frame("labyrinth", 0.25, W, H)
     of.extension_marble_reflection = 0.25
-    _setup(renderer, "labyrinth", of, limits=dict(extension_marble_reflection=0.25))
+    gu.setup(renderer, "labyrinth", of, limits=dict(extension_marble_reflection=0.25))
     _rays, (ph, ps) = _check_all(renderer, "labyrinth", of, seed=31, device=False)
     assert (ps[:, 20:23] == np.float32(0.25).view(np.uint32)).any()
     renderer.setLimits(**DEFAULT_LIMITS)
@@ -133,13 +88,13 @@ def test_debug_plane_and_marble_reflection(renderer):
 
 def test_whole_frame_equals_the_pixel_list(renderer):
     scene = "lense"
-    _setup(renderer, scene, qu.frame(scene, 0.6, W, H))
+    gu.setup(renderer, scene, qu.frame(scene, 0.6, W, H))
     for w, h in ((FW, FH), (1, 1), (9, 1), (8, 8), (3, 17)):
         whole = renderer.pickSurfaces(None, w, h, hits=True)
         listed = renderer.pickSurfaces(su.frame_pixels(w, h), w, h, hits=True)
         assert len(whole[1]) == w * h
         su.assert_same("%d x %d" % (w, h), whole, (qu.hits_array(listed[0]), su.surfaces_array(listed[1])))
-        dev = _host(renderer.pickSurfaces(None, w, h, hits=True, device=True))
+        dev = gu.to_host(renderer.pickSurfaces(None, w, h, hits=True, device=True))
         su.assert_same("%d x %d (device)" % (w, h), dev, (qu.hits_array(listed[0]), su.surfaces_array(listed[1])))
 
 
@@ -147,7 +102,7 @@ def test_whole_frame_equals_the_pixel_list(renderer):
 def test_mesh_with_surfaces(renderer, scene):
     stime, origin, cell, dims = MESHES[scene]
     of = qu.frame(scene, stime, W, H)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     pos, nrm, idx, srf = renderer.extractMesh(origin, cell, dims, surfaces=True)
     plain = renderer.extractMesh(origin, cell, dims)
     for a, b in zip((pos, nrm, idx), plain):  # the mesh itself is sdfr_mesh_extract's
@@ -164,7 +119,7 @@ def test_mesh_with_surfaces(renderer, scene):
     assert np.array_equal(mesh[1]["material_id"], mesh[0]["material_id"]) and np.array_equal(mesh[1]["valid"], mesh[0]["hit"])
     # another reach, on the device, with the mesh left there
     dpos, dnrm, _didx, dsrf = renderer.extractMesh(origin, cell, dims, surfaces=True, reach=0.2, device=True)
-    (dsrf,) = _host((dsrf,))
+    (dsrf,) = gu.to_host((dsrf,))
     qu.assert_same("%s mesh surfaces, reach 0.2 (device)" % scene, su.surfaces_array(dsrf), su.oracle_mesh(scene, of, pos, nrm, 0.2)[1])
     # the usefulness condition on the inputs: a surface under (nearly) every vertex
     valid = (ref[1][:, 3] == 1).mean()
@@ -175,26 +130,20 @@ def test_mesh_with_surfaces(renderer, scene):
         assert len(np.unique(srf["material_id"][srf["valid"] == 1])) >= 4  # the debug views are on the mesh
 
 
-def _raw(r):
-    import sdf_playground_amd as sp
-
-    return sp.load_library(), r._h
-
-
 def test_small_and_awkward_sizes(renderer):
     import torch
 
     scene = "labyrinth"
     of = qu.frame(scene, 0.3, W, H)
-    _setup(renderer, scene, of)
-    L, h = _raw(renderer)
+    gu.setup(renderer, scene, of)
+    L, h = gu.raw(renderer)
     o, dirs = qu.ray_samples(of, 5, 65)
     ref = su.oracle_rays(scene, of, o, dirs)
     assert (ref[1][:, 3] == 1).any()
     for n in (0, 1, 63, 64, 65):
         got = renderer.queryRaySurfaces(o[:n], dirs[:n], hits=True)
         su.assert_same("n = %d" % n, got, (ref[0][:n], ref[1][:n]))
-        dev = _host(renderer.queryRaySurfaces(_torch_dev(o[:n].reshape(-1, 3)), _torch_dev(dirs[:n].reshape(-1, 3)), hits=True))
+        dev = gu.to_host(renderer.queryRaySurfaces(gu.to_device(o[:n].reshape(-1, 3)), gu.to_device(dirs[:n].reshape(-1, 3)), hits=True))
         su.assert_same("n = %d (device)" % n, dev, (ref[0][:n], ref[1][:n]))
     # records that start 4 bytes past a 16-byte boundary: the word stores; the words around them stay
     n = 65
@@ -202,7 +151,7 @@ def test_small_and_awkward_sizes(renderer):
     sbuf = torch.full((32 * n + 8,), sentinel, dtype=torch.int32, device="cuda")
     hbuf = torch.full((12 * n + 8,), sentinel, dtype=torch.int32, device="cuda")
     assert sbuf.data_ptr() % 16 == 0 and hbuf.data_ptr() % 16 == 0
-    do, dd = _torch_dev(o), _torch_dev(dirs)
+    do, dd = gu.to_device(o), gu.to_device(dirs)
     vp = ctypes.c_void_p
     assert L.sdfr_query_ray_surfaces(h, n, vp(do.data_ptr()), vp(dd.data_ptr()), 0.0, vp(hbuf.data_ptr() + 4), vp(sbuf.data_ptr() + 4), 0) == 0
     renderer.sync()
@@ -221,8 +170,8 @@ def test_arguments(renderer):
     import sdf_playground_amd as sp
 
     scene = "fast_sphere"
-    _setup(renderer, scene, qu.frame(scene, 0.0, W, H))
-    L, h = _raw(renderer)
+    gu.setup(renderer, scene, qu.frame(scene, 0.0, W, H))
+    L, h = gu.raw(renderer)
     buf = np.zeros(64, np.float32)
     out = np.full(W * H * 32, 7, np.uint32)  # what no call below may touch
     hit = np.full(W * H * 12, 7, np.uint32)
@@ -270,26 +219,17 @@ def test_arguments(renderer):
     assert set(out.reshape(-1, 32)[:, 3]) <= {0, 1} and set(hit.reshape(-1, 12)[:, 10]) <= {0, 1}
 
 
-def _stats(r):
-    s = r.getStats()
-    return (s.pixels, s.rays, s.march_evals, s.hits, s.march_launches, s.shade_launches)
-
-
 def test_surface_queries_leave_rendering_alone(renderer):
     scene = "labyrinth"
     of = qu.frame(scene, 0.4, 96, 64)
-    _setup(renderer, scene, of)
+    gu.setup(renderer, scene, of)
     o, dirs = qu.ray_samples(of, 71, 500)
-    img0, st0 = renderer.render(None, 96, 64, pixel_stats=True)
-    s0, t0 = _stats(renderer), renderer.getTimings()
-    renderer.queryRaySurfaces(o, dirs, hits=True)
-    renderer.pickSurfaces(qu.pick_grid(32, 16), 32, 16)
-    renderer.pickSurfaces(None, 33, 17, hits=True)
-    renderer.meshSurfaces(o, dirs, 0.25)
-    renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), surfaces=True)
-    assert _stats(renderer) == s0 and renderer.getTimings() == t0
-    img1, st1 = renderer.render(None, 96, 64, pixel_stats=True)
-    assert np.array_equal(img0.view(np.uint32), img1.view(np.uint32)) and np.array_equal(st0, st1) and _stats(renderer) == s0
+    with gu.rendering_untouched(renderer, 96, 64):
+        renderer.queryRaySurfaces(o, dirs, hits=True)
+        renderer.pickSurfaces(qu.pick_grid(32, 16), 32, 16)
+        renderer.pickSurfaces(None, 33, 17, hits=True)
+        renderer.meshSurfaces(o, dirs, 0.25)
+        renderer.extractMesh((-5.35, -0.3, -2.55), 0.25, (5, 4, 3), surfaces=True)
 
 
 def test_one_handle_across_scene_changes():
@@ -302,14 +242,14 @@ def test_one_handle_across_scene_changes():
         rounds = []
         for scene in ("labyrinth", qu.HLSL[0], "labyrinth"):
             of = qu.frame(scene, 0.5, W, H)
-            _setup(r, scene, of)
+            gu.setup(r, scene, of)
             o, dirs = qu.ray_samples(of, 92, n)
             ray_ref, frame_ref = su.oracle_rays(scene, of, o, dirs), _frame_oracle(scene, of, w, h)
             mesh_ref = su.oracle_mesh(scene, of, o, dirs, 0.3)
             got = [r.queryRaySurfaces(o, dirs, hits=True), r.pickSurfaces(None, w, h, hits=True), r.meshSurfaces(o, dirs, 0.3, hits=True)]
             for what, g, want in zip(("rays", "frame", "mesh"), got, (ray_ref, frame_ref, mesh_ref)):
                 su.assert_same("%s %s" % (scene, what), g, want)
-            su.assert_same("%s frame (device)" % scene, _host(r.pickSurfaces(None, w, h, hits=True, device=True)), frame_ref)
+            su.assert_same("%s frame (device)" % scene, gu.to_host(r.pickSurfaces(None, w, h, hits=True, device=True)), frame_ref)
             rounds.append(got)
         for a, b in zip(rounds[0], rounds[2]):
             assert np.array_equal(su.surfaces_array(a[1]), su.surfaces_array(b[1])) and np.array_equal(qu.hits_array(a[0]), qu.hits_array(b[0]))
@@ -323,7 +263,7 @@ def test_unlit_pixels_are_the_renderer_s(renderer):
     # material sends no shadow rays) whose material is one of the unlit views (use_light false: MATERIAL_ITER, PLAIN, NORMAL1, NORMAL2)
     # is 0 + (0 + colour) * 1: the bits of `unlit` (a zero of either sign becomes +0 in both).  Its alpha is the tone-map flag: 0
     # where the view switches it off (all but PLAIN), else use_hdr.
-    from test_debug_materials_cpu import CAMS
+    from frame_cases import MATERIALS_CAMS as CAMS
 
     import sdf_playground_amd as sp
 

@@ -15,10 +15,11 @@ import sys
 import numpy as np
 import pytest
 
+from frame_cases import NORMAL_CAMS, TWIN_CAMS, TWIN_CASES, normal_frame, twin_frame
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
 SCENES_DIR = os.path.join(os.path.dirname(HERE), "sdf_playground_amd", "scenes")
-FOVY = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
 
 
 # ---- the textual pass -------------------------------------------------------------------------------------------
@@ -70,13 +71,12 @@ def test_reference_scene_files_render_the_oracle_s_bits(oracle):
 def test_rounded_hlsl_is_normal_test(oracle):
     """map_normal in the dialect (use_normal, normal_sample_dist) = the library's normal_test scene = the oracle's"""
     import hostsim
-    from test_normal_cpu import CAMS, _frame
 
     L, slots = hostsim.build_hlsl("rounded", open(os.path.join(SCENES_DIR, "rounded.hlsl")).read())
     assert slots == ["round", "analytic"]
-    for cam in CAMS[:3]:
+    for cam in NORMAL_CAMS[:3]:
         for extra in ({}, dict(round=0.04), dict(analytic=0.0, max_cost_default=9, extension_lights=7)):
-            f = _frame(oracle, "normal_test", cam, **extra)
+            f = normal_frame(oracle, "normal_test", cam, **extra)
             ref, rst, _ = oracle.render("normal_test", f, stats=True)
             img, st = hostsim.render_hlsl(L, hostsim.frame_from_oracle(f))
             assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)) and np.array_equal(st, rst), (cam, extra)
@@ -101,32 +101,6 @@ def test_pendulum_hlsl_equals_its_cpp_twin():
         b, sb = hostsim.render_scene_source(LC, f)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(sa, sb)
         assert (sa[..., 0] >= 2).sum() > 200  # the mirror ball and the shadow rays are in the picture
-
-
-# cameras for the two dialect scenes with oracle twins: (eye, lookat)
-TWIN_CAMS = [((0.0, 2.0, -5.0), (0.0, 1.0, 0.0)), ((4.5, 1.2, -3.5), (0.5, 0.8, 0.5)), ((-3.0, 4.0, 4.5), (0.0, 0.6, 1.0)), ((0.3, 0.4, -14.0), (0.0, 1.0, 0.0))]
-
-
-def twin_frame(oracle, scene, cam, w=96, h=64, stime=0.7, **extra):
-    f = oracle.default_frame(scene, w, h, basis=oracle.camera_lookat(cam[0], cam[1], FOVY, np.float32(w) / np.float32(h)), stime=stime)
-    slots = {r[0]: r[6] for r in oracle.var_table(scene)}
-    for k, v in extra.items():
-        if k in slots:
-            if slots[k] >= 0:
-                f.scene_var[slots[k]] = v
-            else:
-                setattr(f, k, v)
-        else:
-            setattr(f, k, v)
-    return f
-
-
-TWIN_CASES = {
-    # 2-D / 4-D simplex noise, grad4; camera_distance and the ray offsets read in the geometry step (pshader_sdf.hlsl:187-218)
-    "noise_lod": [dict(), dict(lod=3.0, freq=6.5, bump=0.04), dict(lod=40.0, stime=3.9, max_cost_default=9), dict(debug_ny=1.0, debug_y=0.8)],
-    # swizzled l-values, inout swizzles, float3x3 + mul, static const initialisers, saturating (int), a voronoi overload, VAR_ quirks
-    "dialect_tour": [dict(), dict(spin=-1.3, reach=2.7, blend=0.25, shine=0.8), dict(stime=5.2, extension_lights=5, max_cost_default=9), dict(debug_nx=1.0, debug_x=0.3)],
-}
 
 
 @pytest.mark.parametrize("scene", sorted(TWIN_CASES))

@@ -15,12 +15,11 @@ import lighting_util as lu
 import mesh_util as mu
 import query_util as qu
 import surface_util as su
+from lighting_util import MESHES, PIXEL_FRAMES, pixel_classes, pixel_frame
 
 N_RAYS = 2000
 W, H = 64, 48
 FW, FH = 61, 45  # a whole frame with ragged 8 x 8 tiles on both edges
-# the meshes of tests/test_gpu_surface.py: stime, origin, cell, dims
-MESHES = {"fast_sphere": (0.0, (-1.55, -0.3, -1.55), 0.13, (24, 23, 25)), "debug_materials": (0.4, (-2.05, -0.3, -1.55), 0.17, (24, 23, 25))}
 
 
 def _same(what, got, want, shortcuts):
@@ -147,40 +146,7 @@ def test_mesh_vertices(scene):
 
 
 # ---- the pin against the driver itself: where `lit` is defined to be the pixel, it is orc::ps_main's rgb, bit for bit -----------------
-# scene, stime, frame changes, camera (eye, look-at; None: the start-up camera) -- chosen on the oracle alone.  With all seven extension
-# lights a lit hit starts eight chains, one more than the driver's eight ray slots leave room for beside the primary ray: six here.
-PIXEL_FRAMES = {
-    "basic_transparency": ("basic_transparency", 0.5, {}, ((-5.0, 6.0, 2.0), (0.0, 0.0, 0.0))),
-    "light_shadows": ("light_shadows", 0.5, {}, None),
-    "gems, extension lights": ("gems", 0.5, {"extension_lights": 6}, None),
-    "labyrinth, extension lights": ("labyrinth", 0.5, {"extension_lights": 3}, None),
-}
-
-
-def pixel_frame(key):
-    scene, stime, changes, camera = PIXEL_FRAMES[key]
-    of = qu.frame(scene, stime, W, H)
-    if camera:
-        fovy = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
-        basis = qu.po.camera_lookat(camera[0], camera[1], fovy, np.float32(W) / np.float32(H))
-        for i in range(3):
-            of.eye[i], of.front[i], of.right[i], of.top[i] = basis[0][i], basis[1][i], basis[2][i], basis[3][i]
-    for k, v in changes.items():
-        setattr(of, k, v)
-    return scene, of
-
-
-def pixel_classes(scene, of, g, srf):
-    """(qualifies: the three conditions of include/sdfr.h; single: one chain of any length within the bounce budget, which the driver
-    sums in the same order whatever its length; lit hits)"""
-    ok = lu.pixel_conditions(srf, g, of.bounce_count, of.ray_count)
-    lit_hits = (g[:, 0] == 1) & ((srf[:, 1] & 2) != 0)
-    # the header's wording of the see-through condition and the driver's coincide on these frames: no unlit see-through hit
-    assert not ((srf[:, 3] == 1) & ((srf[:, 1] & 2) == 0) & (lu.f32(srf[:, 7]) < 1)).any()
-    single = lu.spawns_nothing_else(srf, g) & (lu.popcount(g[:, 2]) == 1) & (1 + g[:, 11].astype(np.int64) <= of.bounce_count)
-    return ok, single, lit_hits
-
-
+# (the frames and their classes of pixels: lighting_util.PIXEL_FRAMES, shared with the GPU tier)
 @pytest.mark.parametrize("key", sorted(PIXEL_FRAMES))
 def test_lit_is_the_driver_s_pixel(key):
     scene, of = pixel_frame(key)

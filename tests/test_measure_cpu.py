@@ -215,10 +215,10 @@ def test_a_grid_moved_by_whole_columns():
 
 # ---- accuracy of the definition on an analytic sphere -----------------------------------------------------------------------------
 # The restatement against the closed forms 4/3 pi rho^3, the centre and 2/5 m rho^2, the sphere fully inside the box, min_step = cell / 2,
-# sixteen seeded sub-cell offsets of the centre per resolution.  The worst values the restatement gave (recorded in DESIGN.md 4.16), as
+# sixteen seeded sub-cell offsets of the centre per resolution.  The worst values the restatement gave (measure_util.RECORDED_WORST), as
 # relative errors of the volume and of I_zz and the centroid's distance in cells; asserted: twice that, since sixteen offsets sample the
 # worst case thinly.
-RECORDED_WORST = {8: (4.8e-3, 1.65e-2, 0.019), 16: (1.14e-3, 4.55e-3, 0.0104), 32: (1.82e-4, 8.83e-4, 0.0045)}
+RECORDED_WORST = mu.RECORDED_WORST
 
 
 def sphere_errors(ratio, seed=2024, offsets=16):

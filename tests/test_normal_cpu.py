@@ -8,22 +8,7 @@ host build of the product's pipeline stages against the oracle, bit for bit."""
 import numpy as np
 import pytest
 
-W, H = 120, 80
-FOVY = np.float32(60.0) * np.float32(3.14159265358979) / np.float32(180.0)
-CAMS = [((0.2, 2.2, -4.6), (0.0, 0.5, -0.2)), ((3.2, 1.1, -2.4), (1.2, 0.5, -0.3)), ((-3.4, 1.5, -1.6), (-1.2, 0.6, 0.1)), ((0.8, 5.0, -0.9), (0.6, 0.0, -0.5))]
-EPS_DEFAULT = dict(dist_eps=0.0001, grad_eps=0.0001, reflect_eps=0.001, refract_eps=0.001, shadow_eps=0.0003)
-EPS_OTHER = dict(dist_eps=0.0005, grad_eps=0.002, reflect_eps=0.004, refract_eps=0.0025, shadow_eps=0.0011)
-
-
-def _frame(oracle, scene, cam, stime=0.4, w=W, h=H, **kw):
-    f = oracle.default_frame(scene, w, h, basis=oracle.camera_lookat(cam[0], cam[1], FOVY, np.float32(w) / np.float32(h)), stime=stime)
-    slots = {r[0]: r[6] for r in oracle.var_table(scene)}
-    for k, v in kw.items():
-        if k in slots and slots[k] >= 0:
-            f.scene_var[slots[k]] = v
-        else:
-            setattr(f, k, v)
-    return f
+from frame_cases import EPS_DEFAULT, EPS_OTHER, NORMAL_CAMS as CAMS, NORMAL_H as H, NORMAL_W as W, normal_frame as _frame
 
 
 def test_default_frame_carries_the_reference_epsilons(oracle):
