@@ -705,6 +705,72 @@ typedef struct sdfr_mesh_fit_result
 } sdfr_mesh_fit_result;
 int sdfr_mesh_fit(sdfr_renderer *r, const sdfr_mesh_grid *search, int levels, int margin, sdfr_mesh_fit_result *out /* host */);
 
+/* ---- whether the solid is in one piece: its parts and its enclosed voids on a lattice (no counterpart in the reference; DESIGN.md
+ *      "Components").  Connected-component labelling of the lattice sdfr_mesh_extract samples.  Every result is an integer -- labels,
+ *      counts, bounds -- and every bit of it is fixed by the definition: no dependence on order, on the machine or on the run.
+ *
+ *      Grid.  The grid is sdfr_mesh_grid with sdfr_mesh_extract's limits: origin, cell and iso finite, cell > 0, 1 .. 1024 cells per
+ *      axis, at most 2^30 lattice points; anything else is "bad mesh grid".  Lattice point (i, j, k) has the linear index
+ *      x = i + px * (j + py * k), with px = nx + 1, py = ny + 1, pz = nz + 1.  D and s = D - iso are sdfr_mesh_extract's.  A point is
+ *      INSIDE iff s < 0, so NaN is not inside (and -0.0 is not < 0).
+ *
+ *      Components.  Two points are joined iff they are neighbours along a lattice axis (6-connectivity) and are both inside or both
+ *      not inside.  A component is a class of the closure of that relation: every point belongs to exactly one, either a SOLID (its
+ *      points are inside) or a VOID (they are not).
+ *        - a component's root is the smallest linear index among its points;
+ *        - the components are numbered 0 .. C - 1 in ascending order of root;
+ *        - a component is CLOSED iff none of its points lies on a face of the lattice (i = 0, i = px - 1, j = 0, j = py - 1, k = 0,
+ *          k = pz - 1).  A closed solid is a part floating free inside the box; a closed void is an enclosed cavity.
+ *      6-connectivity is used for both phases, the solid and the void alike.  Two bodies that touch only across a lattice diagonal
+ *      are therefore two solids, and a cavity that touches the outside only across a lattice diagonal counts as closed.
+ *
+ *      sdfr_components_label labels the loaded scene.  sdfr_components_label_lattice labels a caller's lattice[px * py * pz] of
+ *      distances, in host or device memory like the other arrays: it needs no scene and uses only n and iso of the grid, which must
+ *      still be a good grid.
+ *        - counts is host memory and is required; both calls are synchronous, like the counting call of the mesh.  inside_points
+ *          equals sdfr_mesh_survey's on the same grid; largest_solid_points and largest_void_points are 0 when there is no component
+ *          of that kind.
+ *        - labels may be NULL (not wanted); otherwise it is [px * py * pz], and labels[x] is the number of x's component.  It is
+ *          written whenever it is given.
+ *        - records [capacity] is filled -- records[c] is component c -- iff counts->components <= capacity.  Otherwise only counts is
+ *          written, and labels if given, and the call returns SDFR_OK: the mesh's capacity rule.  Capacity 0 with NULL records is the
+ *          counting call.
+ *        - like a query, the call latches camera, time, variables and limits into a copy and changes nothing a render uses or
+ *          reports (stats, timings, row order; sdfr_mesh_get_timings keeps the last extraction's); it runs on the lane of the frame
+ *          submitted last.  Its workspace is the mesh workspace of the handle under its keep rule: 12 bytes per lattice point (8
+ *          with the caller's lattice), the prefix sum's block sums, 2 KiB of counts and 40 bytes per component.
+ *        - errors, in the order they win: SDFR_ERR_INVALID_ARGUMENT for a NULL grid or counts, and for the second entry a NULL
+ *          lattice ("null pointer"); an on_host other than 0 or 1; "bad mesh grid"; a negative capacity; NULL records with a capacity;
+ *          then, for the first entry only, SDFR_ERR_NO_SCENE.  Nothing is written on error.
+ *      (Both structs are defined first and named after: the tag and the typedef are the same name.) ---------------------------------- */
+#define SDFR_COMPONENT_INSIDE 1u        /* flags bit 0: a solid */
+#define SDFR_COMPONENT_FACE_SHIFT 8     /* flags bits 8 .. 13: touches the face i = 0, i = px-1, j = 0, j = py-1, k = 0, k = pz-1 */
+#define SDFR_COMPONENT_FACES 0x3f00u    /* none of them set: closed */
+struct sdfr_component /* 40 bytes, 8-byte aligned */
+{
+	uint32_t root;   /* the smallest linear index of the component's points */
+	uint32_t flags;  /* SDFR_COMPONENT_INSIDE | the faces it touches */
+	int64_t points;  /* number of lattice points in the component */
+	int32_t lo[3], hi[3]; /* inclusive point indices per axis */
+};
+typedef struct sdfr_component sdfr_component;
+struct sdfr_component_counts /* 64 bytes */
+{
+	int64_t components;
+	int64_t solids;
+	int64_t voids;
+	int64_t closed_solids;
+	int64_t closed_voids;
+	int64_t inside_points;        /* == sdfr_mesh_survey's on the same grid */
+	int64_t largest_solid_points; /* 0: no solid */
+	int64_t largest_void_points;  /* 0: no void */
+};
+typedef struct sdfr_component_counts sdfr_component_counts;
+int sdfr_components_label(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t capacity, sdfr_component *records /*[capacity] or NULL*/,
+	uint32_t *labels /*[points] or NULL*/, sdfr_component_counts *counts /*host, required*/, int on_host);
+int sdfr_components_label_lattice(sdfr_renderer *r, const sdfr_mesh_grid *grid, const float *lattice /*[points]*/, int64_t capacity,
+	sdfr_component *records /*[capacity] or NULL*/, uint32_t *labels /*[points] or NULL*/, sdfr_component_counts *counts /*host, required*/, int on_host);
+
 /* ---- the loaded scene's contours on a stack of planes: marching squares over plane lattices of scene distances, the 2-D sibling of
  *      sdfr_mesh_extract (no counterpart in the reference; DESIGN.md "Slices").  An indexed set of line segments with shared vertices:
  *      one vertex per lattice edge that changes sign, one segment per crossing of a cell.  The planes may have any orientation, and the

@@ -204,6 +204,20 @@ public:
 		return handle && pushState() && sdfr_mesh_fit(handle, &search, levels, margin, &out) == SDFR_OK;
 	}
 
+	// Whether the solid is in one piece (sdfr_components_label and sdfr_components_label_lattice in sdfr.h): the 6-connected parts and
+	// voids of the lattice of `grid`, with this renderer's variables and time, or of the caller's `lattice` of distances, which needs no
+	// scene.  counts is always filled, labels ([points], may be null) whenever given; records only if the components fit the capacity
+	// (capacity 0, records null: the counting call).
+	bool labelComponents(const sdfr_mesh_grid &grid, int64_t capacity, sdfr_component *records, uint32_t *labels, sdfr_component_counts &counts, bool on_host = true)
+	{
+		return handle && pushState() && sdfr_components_label(handle, &grid, capacity, records, labels, &counts, on_host ? 1 : 0) == SDFR_OK;
+	}
+	bool labelLattice(const sdfr_mesh_grid &grid, const float *lattice, int64_t capacity, sdfr_component *records, uint32_t *labels, sdfr_component_counts &counts,
+		bool on_host = true)
+	{
+		return handle && sdfr_components_label_lattice(handle, &grid, lattice, capacity, records, labels, &counts, on_host ? 1 : 0) == SDFR_OK;
+	}
+
 	// The loaded scene's contours on a stack of planes (sdfr_slice_extract in sdfr.h: marching squares over `grid`), with this renderer's
 	// variables and time.  counts and the two layer arrays ([layers + 1], host, may be null) are always filled; positions, coords (may be
 	// null) and segments only if both capacities suffice (capacities 0, arrays null: the counting call).

@@ -16,7 +16,8 @@ the calls raise -- there is no CPU fallback.
 The package's names live in four modules: _abi (the C ABI: constants, structs, records, the table of functions, the loader), _renderer
 (SDFRenderer, Camera, Variable, HDR and the functions that need no handle), _comm (Comm) and _strips (the strip layout restated in numpy).
 """
-from ._abi import (ATLAS_LAYERS, COMM_ID_BYTES, EXPORTED_SYMBOLS, FIT_EMPTY, FIT_FOUND, FIT_TOO_LARGE, HIT_DTYPE, LAUNCH_AUTO, LAUNCH_PER_TILE,  # noqa: F401
+from ._abi import (ATLAS_LAYERS, COMM_ID_BYTES, COMPONENT_DTYPE, COMPONENT_FACE_SHIFT, COMPONENT_FACES, COMPONENT_INSIDE, EXPORTED_SYMBOLS,  # noqa: F401
+                   ComponentCounts, FIT_EMPTY, FIT_FOUND, FIT_TOO_LARGE, HIT_DTYPE, LAUNCH_AUTO, LAUNCH_PER_TILE,
                    LAUNCH_PERSISTENT, LIB_PATH, LIGHT_BLOCKED, LIGHT_DIRECTIONAL, LIGHT_ESCAPED, LIGHT_NO_CHAIN, LIGHT_SAMPLE_DTYPE, LIGHT_UNUSED,
                    LIGHTING_DTYPE, MEASURE_COLUMN_DTYPE, OCCLUSION_DTYPE, RGBA16F, RGBA32F, SCHEDULE_PIXEL, SCHEDULE_WAVEFRONT, SDFR_OK,
                    SPAN_ENDS_INSIDE, SPAN_OUT_OF_STEPS, SPAN_STARTS_INSIDE, SPAN_SUMMARY_DTYPE, STRIP_RGB16F_A8, STRIP_RGB32F_A8, STRIP_ROWS,

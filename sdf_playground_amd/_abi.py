@@ -94,6 +94,20 @@ class MeshFit(ctypes.Structure):  # sdfr_mesh_fit_result
                 ("grid", MeshGrid), ("last", MeshSurvey)]
 
 
+class ComponentCounts(ctypes.Structure):  # sdfr_component_counts
+    _fields_ = [("components", c_int64), ("solids", c_int64), ("voids", c_int64), ("closed_solids", c_int64), ("closed_voids", c_int64),
+                ("inside_points", c_int64), ("largest_solid_points", c_int64), ("largest_void_points", c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _type in self._fields_}
+
+
+# sdfr_component (include/sdfr.h): one part or void of the lattice, 40 bytes
+COMPONENT_DTYPE = np.dtype([("root", np.uint32), ("flags", np.uint32), ("points", np.int64), ("lo", np.int32, (3,)), ("hi", np.int32, (3,))])
+assert COMPONENT_DTYPE.itemsize == 40 and ctypes.sizeof(ComponentCounts) == 64
+COMPONENT_INSIDE, COMPONENT_FACE_SHIFT, COMPONENT_FACES = 1, 8, 0x3F00  # SDFR_COMPONENT_*
+
+
 class Atlas(ctypes.Structure):  # sdfr_atlas
     _fields_ = [("triangles", c_int64), ("quads", c_int64), ("tile", c_int32), ("width", c_int32), ("height", c_int32),
                 ("tiles_per_row", c_int32), ("rows", c_int32), ("reserved", c_int32)]
@@ -242,7 +256,9 @@ ABI = {
     "sdfr_mesh_extract_sharp": (_ci, [_vp, POINTER(MeshGrid), _i64, _i64, _vp, _vp, _vp, POINTER(MeshCounts), _ci]),
     "sdfr_mesh_survey": (_ci, [_vp, POINTER(MeshGrid), _cf, POINTER(MeshSurvey)]),
     "sdfr_mesh_fit": (_ci, [_vp, POINTER(MeshGrid), _ci, _ci, POINTER(MeshFit)]),
-    "sdfr_slice_extract": (_ci, [_vp, POINTER(SliceGrid), _i64, _i64, _vp, _vp, _vp, _vp, _vp, POINTER(SliceCounts), _ci]),
+    "sdfr_components_label": (_ci, [_vp, POINTER(MeshGrid), _i64, _vp, _vp, POINTER(ComponentCounts), _ci]),
+    "sdfr_components_label_lattice": (_ci, [_vp, POINTER(MeshGrid), _vp, _i64, _vp, _vp, POINTER(ComponentCounts), _ci]),
+    "sdfr_slice_extract": (_ci,[_vp, POINTER(SliceGrid), _i64, _i64, _vp, _vp, _vp, _vp, _vp, POINTER(SliceCounts), _ci]),
     "sdfr_query_ray_spans": (_ci, [_vp, _i64, _vp, _vp, POINTER(SpanParams), _vp, _vp, _ci]),
     "sdfr_pick_spans": (_ci, [_vp, _ci, _ci, _i64, _vp, POINTER(SpanParams), _vp, _vp, _ci]),
     "sdfr_mesh_spans": (_ci, [_vp, _i64, _vp, _vp, _cf, POINTER(SpanParams), _vp, _vp, _ci]),

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._abi import (ATLAS_LAYERS, FIT_FOUND, HIT_DTYPE, LIGHT_SAMPLE_DTYPE, LIGHTING_DTYPE, MEASURE_COLUMN_DTYPE, OCCLUSION_DTYPE, RGBA32F, SDFR_OK,
+from ._abi import (ATLAS_LAYERS, COMPONENT_DTYPE, ComponentCounts, FIT_FOUND, HIT_DTYPE, LIGHT_SAMPLE_DTYPE, LIGHTING_DTYPE, MEASURE_COLUMN_DTYPE, OCCLUSION_DTYPE, RGBA32F, SDFR_OK,
                    SPAN_ENDS_INSIDE, SPAN_SUMMARY_DTYPE, STRIP_RGB16F_A8, STRIP_RGB32F_A8, SURFACE_DTYPE, Atlas, Limits, MeasureGrid, MeasureResult,
                    MeshCounts, MeshFit, MeshGrid, MeshSurvey, SdfrError, SliceCounts, SliceGrid, SolidProperties, SpanParams, Stats, _CTiming,
                    _CVariable, load_library)
@@ -870,6 +870,44 @@ class SDFRenderer:
                     origin=tuple(float(v) for v in out.grid.origin) if found else None,
                     dims=(int(out.grid.nx), int(out.grid.ny), int(out.grid.nz)) if found else None,
                     survey=out.last.as_dict() if out.surveys else None)
+
+    # ---- whether the solid is in one piece (sdfr_components_label / sdfr_components_label_lattice; DESIGN.md "Components") ---------
+    def _components(self, call, grid, lattice, want_labels, side):
+        """The two calls of a labelling: the counting call, then the filling call into records of that size (and the labels), which must
+        count the same.  -> (counts dict, records, labels or None)"""
+        shape = (grid.nz + 1, grid.ny + 1, grid.nx + 1)
+        counts = ComponentCounts()
+        self._check(call(self._h, ctypes.byref(grid), *lattice, 0, None, None, ctypes.byref(counts), side.host))
+        c = int(counts.components)
+        records = side.new(c, COMPONENT_DTYPE, zero=True) if side.host else side.new((c, 10), np.int32)
+        labels = side.new(shape, np.uint32) if want_labels else None
+        again = ComponentCounts()
+        self._check(call(self._h, ctypes.byref(grid), *lattice, c, _ptr(records), _ptr(labels), ctypes.byref(again), side.host))
+        if bytes(again) != bytes(counts):
+            raise SdfrError(-9, "the components changed between the counting and the filling call")
+        return counts.as_dict(), records, labels
+
+    def labelComponents(self, origin, cell, dims, iso=0.0, labels=False, device=False):
+        """The parts and the enclosed voids of the loaded scene on the lattice of extractMesh(origin, cell, dims, iso)
+        (sdfr_components_label): 6-connected components of the inside points (solids) and of the others (voids), numbered by their
+        smallest linear index.  -> (counts, records, labels): counts a dict of components, solids, voids, closed_solids, closed_voids,
+        inside_points, largest_solid_points and largest_void_points; records COMPONENT_DTYPE [components] (root, flags, points, lo,
+        hi); labels uint32 [nz + 1, ny + 1, nx + 1] with labels=True, else None.  With device=True records are an int32 tensor
+        [components, 10] holding the same words and labels an int32 tensor, on the renderer's GPU.  The call is synchronous."""
+        return self._components(self._L.sdfr_components_label, _mesh_grid(origin, cell, dims, iso), (), labels, self._side(device))
+
+    def labelLattice(self, lattice, iso=0.0, labels=False, device=False):
+        """labelComponents of the caller's distances (sdfr_components_label_lattice): lattice [pz, py, px] float32, each at least 2
+        points -- a numpy array, uploaded first if `device`, or a device tensor.  Needs no scene."""
+        side = self._side(device or hasattr(lattice, "data_ptr"))
+        if not hasattr(lattice, "data_ptr"):
+            lattice = np.asarray(lattice, np.float32)
+        if len(lattice.shape) != 3:
+            raise ValueError("lattice: [pz, py, px] distances are needed")
+        pz, py, px = (int(n) for n in lattice.shape)
+        D = side.put(lattice, np.float32)
+        pointer = _ptr(D, empty=True) if side.host else self._dev(D, px * py * pz, "lattice")
+        return self._components(self._L.sdfr_components_label_lattice, _mesh_grid((0.0, 0.0, 0.0), 1.0, (px - 1, py - 1, pz - 1), iso), (pointer,), labels, side)
 
     def getMeshTimings(self):
         """GPU ms of the last extractMesh's filling call, if setProfiling(True) was on: {sample, classify_scan, emit, normals}."""

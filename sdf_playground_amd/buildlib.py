@@ -23,7 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsdfr.so")
 OBJDIR = os.path.join(HERE, "build")
-SOURCES = ["sdfr_api.cpp", "sdfr_comm.cpp", "sdfr_hlsl.cpp", "sdfr_jit.cpp", "sdfr_kernels.hip", "sdfr_mesh.hip", "sdfr_post.hip", "sdfr_resolve.hip", "sdfr_slice.hip"]
+SOURCES = ["sdfr_api.cpp", "sdfr_comm.cpp", "sdfr_components.hip", "sdfr_hlsl.cpp", "sdfr_jit.cpp", "sdfr_kernels.hip", "sdfr_mesh.hip", "sdfr_post.hip", "sdfr_resolve.hip", "sdfr_slice.hip"]
 # the render kernels, and the query kernels in a unit of their own: both per scene, with the scene's options
 SCENE_SOURCES = ["sdfr_kernels_scene.hip", "sdfr_query_scene.hip"]
 ARCH = "gfx950"

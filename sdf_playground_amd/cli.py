@@ -40,6 +40,10 @@ the inside length of SDFRenderer.pickSpans over the whole frame, marched on the 
 --measure-axis through cells of edge --measure-cell, marched in steps of --measure-step at the least (default: half a cell), integrated and
 summed on the GPU (SDFRenderer.measureSolid); `warning` says when the solid leaves the box or columns ran out of steps.
 --mesh-thickness T_MAX colours the vertices of --mesh by the thickness of the wall under them over T_MAX (SDFRenderer.meshThickness).
+--components prints, as one JSON object, how the solid inside --components-box hangs together on a lattice of cells of edge
+--components-cell (SDFRenderer.labelComponents): the counts, and every part and void up to 64 with its points, points x cell^3 as a volume
+estimate, its bounds in world coordinates and its flags; `warning` says when the solid is in several pieces, a piece floats free or a
+cavity is enclosed.  --components-labels OUT.npy writes every lattice point's component number.
 """
 import argparse
 import math
@@ -238,7 +242,42 @@ def make_parser():
     ap.add_argument("--measure-axis", choices=("x", "y", "z"), default="z", help="the columns' direction (default z)")
     ap.add_argument("--measure-step", type=float, metavar="H", help="the march's smallest step along a column (default C / 2)")
     ap.add_argument("--measure-density", type=float, metavar="RHO", help="mass per unit volume (default 1)")
+    ap.add_argument("--components", action="store_true", help="print the separate parts and the enclosed voids of the solid in --components-box as JSON "
+                    "(needs --components-box and --components-cell)")
+    ap.add_argument("--components-box", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--components-cell", type=float, metavar="C", help="edge length of a lattice cell")
+    ap.add_argument("--components-iso", type=float, default=None, metavar="V", help="inside is distance < V (default 0)")
+    ap.add_argument("--components-labels", metavar="OUT.npy", help="with --components: write every lattice point's component number, uint32 [pz, py, px]")
     return ap
+
+
+COMPONENTS_LISTED = 64  # --components prints this many components at the most, in their order
+
+
+def components_report(scene, counts, records, origin, cell, dims, iso):
+    """--components' JSON object from labelComponents' counts and records"""
+    from ._abi import COMPONENT_FACE_SHIFT, COMPONENT_FACES, COMPONENT_INSIDE
+
+    out = {"scene": scene, "origin": [float(v) for v in origin], "cell": cell, "dims": [int(n) for n in dims], "iso": iso, "counts": counts, "components": []}
+    for number, c in enumerate(records[:COMPONENTS_LISTED]):
+        flags = int(c["flags"])
+        out["components"].append({
+            "number": number, "kind": "solid" if flags & COMPONENT_INSIDE else "void", "closed": not flags & COMPONENT_FACES,
+            "points": int(c["points"]), "volume": int(c["points"]) * cell ** 3, "root": int(c["root"]), "flags": flags,
+            "faces": [f for f in range(6) if flags >> (COMPONENT_FACE_SHIFT + f) & 1],
+            "lo": [float(origin[a]) + int(c["lo"][a]) * cell for a in range(3)], "hi": [float(origin[a]) + int(c["hi"][a]) * cell for a in range(3)]})
+    if len(records) > COMPONENTS_LISTED:
+        out["components_not_listed"] = len(records) - COMPONENTS_LISTED
+    warnings = []
+    if counts["solids"] > 1:
+        warnings.append("the solid is in %d pieces" % counts["solids"])
+    if counts["closed_solids"] > 0:
+        warnings.append("%d pieces float free inside the box" % counts["closed_solids"])
+    if counts["closed_voids"] > 0:
+        warnings.append("%d enclosed cavities" % counts["closed_voids"])
+    if warnings:
+        out["warning"] = "; ".join(warnings)
+    return out
 
 
 def measure_report(scene, props, cell, axis, step, density):
@@ -386,6 +425,18 @@ def main(argv=None):
             ap.error("--measure-box / --measure-cell: " + str(e))
     elif a.measure_box is not None or a.measure_cell is not None or a.measure_step is not None or a.measure_density is not None:
         ap.error("--measure-box, --measure-cell, --measure-step and --measure-density need --measure")
+    components_grid = None
+    if a.components:
+        if a.components_box is None or a.components_cell is None:
+            ap.error("--components needs --components-box and --components-cell")
+        if a.components_iso is not None and not math.isfinite(a.components_iso):
+            ap.error("--components-iso must be finite")
+        try:
+            components_grid = mesh_grid_from_box(a.components_box, a.components_cell)
+        except ValueError as e:
+            ap.error(str(e).replace("--mesh-", "--components-"))
+    elif a.components_box is not None or a.components_cell is not None or a.components_iso is not None or a.components_labels is not None:
+        ap.error("--components-box, --components-cell, --components-iso and --components-labels need --components")
     r = sp.SDFRenderer(a.device)
     if a.scene_source or a.scene_hlsl:
         import os
@@ -515,6 +566,17 @@ def main(argv=None):
         step = a.measure_step if a.measure_step is not None else 0.5 * a.measure_cell
         props = r.measureSolid(a.measure_box[:3], a.measure_box[3:], a.measure_cell, a.measure_axis, density, min_step=step)
         print(json.dumps(measure_report(a.scene, props, a.measure_cell, a.measure_axis, step, density)))
+        if not a.out and not a.out_hdr and not a.gbuffer and not a.xray:
+            r.close()
+            return 0
+    if components_grid:
+        import json
+
+        iso = a.components_iso if a.components_iso is not None else 0.0
+        counts, records, labels = r.labelComponents(components_grid[0], a.components_cell, components_grid[1], iso=iso, labels=a.components_labels is not None)
+        if labels is not None:
+            np.save(a.components_labels, labels)
+        print(json.dumps(components_report(a.scene, counts, records, components_grid[0], a.components_cell, components_grid[1], iso)))
         if not a.out and not a.out_hdr and not a.gbuffer and not a.xray:
             r.close()
             return 0

@@ -5,6 +5,7 @@
 // sdfr_kernels.hip; there is no CPU rendering path.
 #include "sdfr_aa_plan.h"
 #include "sdfr_atlas_plan.h"
+#include "sdfr_components_plan.h"
 #include "sdfr_handle.h"
 #include "sdfr_hlsl_translate.h"
 #include "sdfr_mesh_plan.h"
@@ -1308,6 +1309,115 @@ int sdfr_mesh_fit(sdfr_renderer *r, const sdfr_mesh_grid *search, int levels, in
 		if (rc != SDFR_OK) return rc;
 		memcpy(out, &f, sizeof f);
 		return SDFR_OK;
+	});
+}
+
+// ---- sdfr_components_label and sdfr_components_label_lattice (the definition: include/sdfr.h; the plan: sdfr_components_plan.h; the rules:
+// sdfr_components.h; the kernels: sdfr_components.hip), calls of the queries' protocol and synchronous like the counting call.  Sample the
+// lattice (or take the caller's), unite and flatten, flag the roots and scan them, read the number of components back; cut the table behind
+// the workspace's other pieces; then number, tally and pack, and read the 64 bytes of counts back.  The workspace is the extraction's under
+// its keep rule; a host call's lattice and labels are staged in `query`, its records are copied from the table, which holds them in
+// order.  No profiling event is recorded.
+static_assert(sizeof(sdfr_component) == sizeof(Component) && offsetof(sdfr_component, flags) == offsetof(Component, flags) && offsetof(sdfr_component, points) == offsetof(Component, points) &&
+		offsetof(sdfr_component, lo) == offsetof(Component, lo) && offsetof(sdfr_component, hi) == offsetof(Component, hi) && alignof(sdfr_component) == 8,
+	"sdfr_component is the kernels' Component");
+static_assert(sizeof(sdfr_component_counts) == sizeof(ComponentCounts) && offsetof(sdfr_component_counts, inside_points) == offsetof(ComponentCounts, inside_points) &&
+		offsetof(sdfr_component_counts, largest_void_points) == offsetof(ComponentCounts, largest_void_points) && SDFR_COMPONENT_INSIDE == COMPONENT_INSIDE &&
+		SDFR_COMPONENT_FACES == COMPONENT_FACES && (1u << SDFR_COMPONENT_FACE_SHIFT) == COMPONENT_FACE,
+	"sdfr_component_counts is the kernels' ComponentCounts");
+// `work`, cut anew with a last piece added, in the handle's mesh workspace with what the pieces before it hold (the stream is drained)
+static int grow_mesh_workspace(sdfr_renderer *r, Carving &work, const size_t *bytes, int n, hipStream_t stream)
+{
+	work.cut(bytes, n);
+	if (r->mesh.bytes >= work.total) return SDFR_OK;
+	sdfr_device_buffer grown;
+	SDFR_HIP(grown.reserve(work.total));
+	const hipError_t e = hipMemcpyAsync(grown.ptr, r->mesh.ptr, work.offset[n - 1], hipMemcpyDeviceToDevice, stream);
+	const hipError_t s = e == hipSuccess ? hipStreamSynchronize(stream) : e;
+	if (s != hipSuccess)
+	{
+		grown.release();
+		SDFR_HIP(s);
+	}
+	r->mesh.release();
+	r->mesh = grown;
+	return SDFR_OK;
+}
+static int components_impl(sdfr_renderer *r, const ComponentsRequest &c, sdfr_component_counts *counts)
+{
+	if (!r) return SDFR_ERR_INVALID_ARGUMENT;
+	const ComponentsPlan p = plan_components(c);
+	if (p.status != QUERY_PLAN_OK) return fail(r, p.status, p.error);
+	FrameU U;
+	hipStream_t stream;
+	int rc = begin_query(r, !c.own_lattice, 1, 1, U, stream);
+	if (rc != SDFR_OK) return rc;
+
+	Carving work;
+	work.cut(p.work, COMPONENTS_WORK_PIECES);
+	rc = reserve_mesh_workspace(r, work, stream);
+	if (rc != SDFR_OK) return rc;
+	const float *d_lattice = c.own_lattice ? static_cast<const float *>(c.lattice) : work.piece<float>(COMPONENTS_WORK_LATTICE);
+	uint32_t *d_labels = static_cast<uint32_t *>(const_cast<void *>(c.labels));
+	Carving st;
+	if (c.on_host)
+	{
+		const StagedArray arrays[2] = {{(void *)&d_lattice, p.lattice_bytes, true}, {&d_labels, p.label_bytes, false}};
+		rc = stage_host_arrays(r, st, arrays, 2, stream); // (in `query`, never in `mesh`)
+		if (rc != SDFR_OK) return rc;
+	}
+	if (!c.own_lattice)
+	{
+		rc = sample_lattice(r, U, p.lattice, work.piece<float>(COMPONENTS_WORK_LATTICE), stream);
+		if (rc != SDFR_OK) return rc;
+	}
+	uint32_t *d_parent = work.piece<uint32_t>(COMPONENTS_WORK_PARENT), *d_scan = work.piece<uint32_t>(COMPONENTS_WORK_SCAN);
+	SDFR_HIP(launch_components_union(p, d_lattice, d_parent, d_scan, work.piece<uint32_t>(COMPONENTS_WORK_SUMS), stream));
+	uint32_t n_components = 0;
+	SDFR_HIP(hipMemcpyAsync(&n_components, d_scan + p.points, 4, hipMemcpyDeviceToHost, stream));
+	SDFR_HIP(hipStreamSynchronize(stream));
+
+	const ComponentsFill f = plan_components_fill(c, p, n_components);
+	size_t pieces[COMPONENTS_WORK_PIECES];
+	for (int k = 0; k < COMPONENTS_WORK_PIECES; ++k) pieces[k] = p.work[k];
+	pieces[COMPONENTS_WORK_TABLE] = f.table_bytes;
+	rc = grow_mesh_workspace(r, work, pieces, COMPONENTS_WORK_PIECES, stream);
+	if (rc != SDFR_OK) return rc;
+	if (!c.own_lattice) d_lattice = work.piece<float>(COMPONENTS_WORK_LATTICE);
+	d_parent = work.piece<uint32_t>(COMPONENTS_WORK_PARENT);
+	d_scan = work.piece<uint32_t>(COMPONENTS_WORK_SCAN);
+	Component *d_table = work.piece<Component>(COMPONENTS_WORK_TABLE);
+	void *d_result = work.piece<void>(COMPONENTS_WORK_RESULT);
+	Component *d_records = c.on_host ? nullptr : static_cast<Component *>(const_cast<void *>(c.records));
+	SDFR_HIP(launch_components_tally(p, f, d_lattice, d_parent, d_scan, d_labels, d_table, d_records, d_result, stream));
+	ComponentCounts n;
+	SDFR_HIP(hipMemcpyAsync(&n, d_result, sizeof n, hipMemcpyDeviceToHost, stream));
+	if (c.on_host)
+	{
+		if (f.fill) st.answers[st.n_answers++] = {const_cast<void *>(c.records), d_table, f.record_bytes};
+		rc = copy_answers_back(r, st, stream);
+		if (rc != SDFR_OK) return rc;
+	}
+	else SDFR_HIP(hipStreamSynchronize(stream));
+	memcpy(counts, &n, sizeof n);
+	return release_large(r, r->mesh, stream);
+}
+
+int sdfr_components_label(sdfr_renderer *r, const sdfr_mesh_grid *grid, int64_t capacity, sdfr_component *records, uint32_t *labels, sdfr_component_counts *counts,
+	int on_host)
+{
+	return guarded(r, [&]() -> int {
+		const ComponentsRequest c = {reinterpret_cast<const MeshGrid *>(grid), false, nullptr, capacity, records, labels, counts, on_host};
+		return components_impl(r, c, counts);
+	});
+}
+
+int sdfr_components_label_lattice(sdfr_renderer *r, const sdfr_mesh_grid *grid, const float *lattice, int64_t capacity, sdfr_component *records, uint32_t *labels,
+	sdfr_component_counts *counts, int on_host)
+{
+	return guarded(r, [&]() -> int {
+		const ComponentsRequest c = {reinterpret_cast<const MeshGrid *>(grid), true, lattice, capacity, records, labels, counts, on_host};
+		return components_impl(r, c, counts);
 	});
 }
 

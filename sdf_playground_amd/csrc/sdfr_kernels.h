@@ -95,6 +95,17 @@ void launch_mesh_scan(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t st
 // cells with `band`, followed by the words k_mesh_survey counted it in with integer atomics, each word in a page of its own.
 struct MeshSurvey;
 hipError_t launch_mesh_survey(const MeshGrid &g, const float *lattice, float band, MeshSurvey *out, hipStream_t stream);
+// The parts and voids of a lattice (sdfr_components.h, sdfr_components.hip; the plan: sdfr_components_plan.h), every pointer device
+// memory.  launch_components_union: parent [points] = every point's root, and scan [points + 1], the exclusive prefix sum of the root
+// flags, whose last element is the number of components; sums: mesh_scan_sum_words(points + 1) words.  launch_components_tally, with
+// that number in `f`: the points' labels in place of parent and into `labels` unless null, table [components], the records into `records`
+// if f.fill, and the packed counts at the start of result (COMPONENT_RESULT_BYTES).
+struct ComponentsPlan;
+struct ComponentsFill;
+struct Component;
+hipError_t launch_components_union(const ComponentsPlan &p, const float *lattice, uint32_t *parent, uint32_t *scan, uint32_t *sums, hipStream_t stream);
+hipError_t launch_components_tally(const ComponentsPlan &p, const ComponentsFill &f, const float *lattice, uint32_t *parent, const uint32_t *scan, uint32_t *labels,
+	Component *table, Component *records, void *result, hipStream_t stream);
 
 // Marching squares over a stack of plane lattices (sdfr_slice.h, sdfr_slice.hip; sdfr_slice_extract), every pointer device memory; the
 // lattices are a scene's slice kernel's (QUERY_KERNEL_SLICES).  launch_slice_count: the vertex count and the segment count per lattice
