@@ -1,9 +1,10 @@
 """What the CPU oracle answers for the calls of the mixed sequences (tests/handle_mixed_sequences.py) that came with the survey, the
-slices, the spans, the measure and the sharp mesh: each definition of include/sdfr.h as the family's own util module restates it, fed
+slices, the spans, the measure, the sharp mesh and the component labelling: each definition of include/sdfr.h as the family's own util module restates it, fed
 with the oracle's distances in the step's state.  The CPU tier asks them whether a committed step meets the surface, the GPU tier
 compares the reference handle's answers with them.  Test infrastructure: the product never imports this."""
 import numpy as np
 
+import components_util
 import handle_mixed_sequences as hm
 import measure_util
 import mesh_sharp_util
@@ -86,6 +87,20 @@ def sharp(s, of):
     lat, scene = s["lattice"], s["state"]["scene"]
     f = lambda points, normals: qu.oracle_points(scene, of, points, normals=normals)  # noqa: E731
     return mesh_sharp_util.sharp_nets(lattice_distances(s, of), lat["origin"], lat["cell"], lat["dims"], 0.0, f)[0]
+
+
+def synthetic_lattice(s):
+    """(lattice [pz, py, px], iso) of a labelLattice step: components_util.synthetic of the step's kind, dims and seed"""
+    return components_util.synthetic(s["kind"], s["dims"], s["seed"])
+
+
+def components(s, of=None):
+    """-> (counts dict, records, labels [pz, py, px]) by the definition: of the oracle's distances on the step's lattice
+    (labelComponents), or of the caller's lattice itself (labelLattice, which needs no frame)"""
+    if s["call"] == "labelLattice":
+        D, iso = synthetic_lattice(s)
+        return components_util.label(D, s["dims"], iso)
+    return components_util.label(lattice_distances(s, of), s["lattice"]["dims"], 0.0)
 
 
 def mesh_vertices(s, of, lat=None):

@@ -1,22 +1,24 @@
 """Seeded sequences of MIXED calls on ONE renderer handle: renders, anti-aliased frames, post-processing, every query family, mesh
-extraction (plain and sharp), atlas calls, surveys and fits, slices, span queries and measures, interleaved.
+extraction (plain and sharp), atlas calls, surveys and fits, slices, span queries, measures and component labellings, interleaved.
 tests/handle_sequences.py drives what a handle carries from frame to frame; this module drives the state the handle has gained
 since: the staging of host queries (`query`, cut per call and released past 64 MiB), the extraction workspace (`mesh`, cut two to
-five ways by the mesh, the survey, the slices and the measure, reused across lanes behind an event, released past 64 MiB), the
+six ways by the mesh, the survey, the slices, the measure and the labelling, which cuts it again in the middle of its call once the
+components are counted, reused across lanes behind an event, released past 64 MiB), the
 supersampling buffers, and the per-handle query kernels in their DBG and non-DBG variants, on built-in scenes and on one compiled
 at run time.
 
 No torch, no GPU: the CPU tier (tests/test_handle_mixed_cpu.py) proves what the committed seeds cover, the GPU tier
 (tests/test_gpu_handle_mixed.py) runs them.  A step is one call on the handle, with the settings changed just before it (`set`) and
 the whole state a fresh handle needs to answer it (`state`).  The inputs of a call are drawn from the step's own seeded generator
-(rays(), points(), normals(), pixel_list(), the lattice, slice stack or measure grid in the step)."""
+(rays(), points(), normals(), pixel_list(), the lattice, slice stack or measure grid in the step; a labelling's own lattice is
+components_util.synthetic of the step's kind, dims and seed)."""
 import math
 import random
 
 import handle_sequences as hs
 
 FAMILIES = ("render", "aa", "post", "points", "rays", "pick", "surfaces", "occlusion", "lighting", "mesh", "atlas", "survey", "slices", "spans", "measure",
-            "failed")
+            "components", "failed")
 # sdfr_postprocess takes device tensors only; sdfr_mesh_survey and sdfr_mesh_fit answer into one host record and have no on_host
 HOST_AND_DEVICE = tuple(f for f in FAMILIES if f not in ("post", "survey", "failed"))
 DEVICE_ONLY = ("post", "survey")
@@ -49,6 +51,13 @@ MEASURE_BIG = 72                                  # 72 x 72 columns are 81 tiles
 # (min_step, max_steps) of a measure; dw spans the box, so t_max = 1.  "short": columns near a surface run out of steps.  iso is 0 but for
 # the measure of the workspace_cuts block
 MEASURE_PARAMS = {"finish": (1.0 / 64.0, 128), "short": (1.0 / 512.0, 48)}
+COMPONENT_CALLS = ("labelComponents", "labelLattice")  # the scene's own distances on the step's lattice; the caller's lattice
+# labelLattice: components_util.synthetic(kind, dims, seed) -- every point a component, one long path, an enclosed void, -0.0 and tiny values
+SYNTHETIC_KINDS = ("noise", "checkerboard", "serpentine", "hollow_box", "zeros")
+# the capacity of a labelling by name, the count C being known only on the GPU: "none" capacity 0 and no records (the counting call),
+# "exact" C, "roomy" C + 3, "short" C - 1 (SDFR_OK with the counts, the records untouched, the labels written; C = 1: as "exact")
+CAPACITY_RULES = ("none", "exact", "roomy", "short")
+GROW_DIMS = (47, 47, 31)                          # 48 x 48 x 32 points: as a checkerboard more components than COMPONENTS_TABLE_FIRST
 SPLITS = hs.SPLITS
 DEBUG_VARS = {"debug_nx": 0.3, "debug_ny": 1.0}  # + the point debug_vars() puts the plane through: the driver's debug plane
 KEEP = 64 << 20                                   # k_query_stage_keep (sdfr_api.cpp): what a handle keeps of `query` and of `mesh`
@@ -58,6 +67,7 @@ HIT_BYTES, SURFACE_BYTES, OCCLUSION_BYTES, LIGHTING_BYTES, LIGHTS_BYTES = 48, 12
 SPAN_SUMMARY_BYTES, SPAN_BYTES, MEASURE_COLUMN_BYTES = 32, 8, 40
 MESH_SURVEY_WORK_BYTES = 4096 * (1 + 10 + 12)     # sdfr_mesh_survey.h
 MEASURE_TALLY_BYTES = 128 * (2 + 13 * 16)         # sdfr_query_args.h
+COMPONENT_BYTES, COMPONENT_RESULT_BYTES, COMPONENTS_TABLE_FIRST = 40, 256 * 8, 1 << 16  # sdfr_components.h, sdfr_components_plan.h
 
 # argument errors refused on the host before anything is launched: (kind, sdfr_last_error); all SDFR_ERR_INVALID_ARGUMENT but the capacities
 # smaller than the counts, which is SDFR_OK with the counts and nothing written
@@ -65,20 +75,22 @@ FAILURES = (("negative_n", "bad item count"), ("null_pointer", "null pointer"), 
             ("mesh_negative_capacity", "negative capacity"), ("mesh_small_capacity", None), ("aa_factor_3", "factor must be 1, 2, 4 or 8"),
             ("aa_bad_format", "bad format"), ("atlas_bad_layout", "bad atlas"), ("slice_negative_capacity", "negative capacity"),
             ("slice_small_capacity", None), ("span_max_spans_65", "bad span parameters"), ("measure_nu_0", "bad measure grid"),
-            ("survey_bad_band", "band must be finite and >= 0"), ("fit_bad_margin", "margin must be 0..8"))
+            ("survey_bad_band", "band must be finite and >= 0"), ("fit_bad_margin", "margin must be 0..8"),
+            ("components_negative_capacity", "negative capacity"), ("components_small_capacity", None), ("components_null_lattice", "null pointer"))
 FAILURE_KINDS = tuple(k for k, _ in FAILURES)
 SHARED_KINDS = FAILURE_KINDS[:3]  # the argument errors every query entry has
 SPAN_ENTRIES = ("ray_spans", "pick_spans", "mesh_spans")
 FAILURE_ENTRIES = ("points", "rays", "pick", "surfaces", "occlusion", "lighting") + SPAN_ENTRIES  # whose entry a shared kind goes through
 
-BLOCKS = ("staging", "lanes", "large_mesh", "aa_in_flight", "scene_change", "workspace_cuts", "large_new")
+BLOCKS = ("staging", "lanes", "large_mesh", "aa_in_flight", "scene_change", "workspace_cuts", "large_new", "components_grow")
 STRETCH = 10  # free steps on the run-time scene, inside the scene_change block: one entry per seed (every entry compiles the scene again)
-BLOCK_STEPS = {"staging": 4, "lanes": 4, "large_mesh": 2, "aa_in_flight": 6, "scene_change": 4 + STRETCH, "workspace_cuts": 6, "large_new": 5}
+BLOCK_STEPS = {"staging": 4, "lanes": 4, "large_mesh": 2, "aa_in_flight": 6, "scene_change": 4 + STRETCH, "workspace_cuts": 6, "large_new": 5,
+               "components_grow": 6}
 BIG_FRAME = (384, 240)  # pickLighting(None, hits, lights) of it on the host: past the keep (staging_bytes)
 BIG_SPAN_FRAME = (448, 280)  # pickSpans(None, max_spans=64) of it on the host: past the keep; 440 x 280 is not
 
-SEEDS = (287, 15, 30, 52, 64, 1, 89, 7)  # the committed seeds (what they cover: tests/test_handle_mixed_cpu.py)
-STEPS = 72
+SEEDS = (143, 136, 319, 54, 2, 8, 226, 285)  # the committed seeds (what they cover: tests/test_handle_mixed_cpu.py)
+STEPS = 80
 
 # the scene variables the sequences move (hs.SCENE_VARS, but the lense stays off the camera orbit's centre: at zpos 0 nothing of the scene
 # is left around it, and the lattices there would be empty)
@@ -125,7 +137,19 @@ def staging_bytes(step):
     if call == "measure":  # plan_measure (sdfr_measure_plan.h): the columns alone
         g = p["grid"]
         return stage_total([g["nu"] * g["nv"] * MEASURE_COLUMN_BYTES if p["columns"] else 0])
+    if call in COMPONENT_CALLS:  # components_impl (sdfr_api.cpp): the caller's lattice and the labels; the records come straight from the table
+        pts = lattice_points(component_dims(p))
+        return stage_total([pts * 4 if call == "labelLattice" else 0, pts * 4 if p["labels"] else 0])
     return None
+
+
+def lattice_points(dims):
+    return (dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1)
+
+
+def component_dims(step):
+    """the cells of a labelling's lattice: the step's lattice around the scene, or the dims of the caller's"""
+    return step["lattice"]["dims"] if step["call"] == "labelComponents" else step["dims"]
 
 
 def _scan_sum_words(n):
@@ -161,6 +185,15 @@ def measure_workspace_bytes(nu, nv):
     return stage_total([tiles * 80, (tiles + 63) // 64 * 80, MEASURE_TALLY_BYTES])
 
 
+def components_workspace_bytes(dims, own_lattice, components):
+    """... a labelling over `dims` cells needs once `components` are counted: the six pieces of plan_components and of
+    plan_components_fill (sdfr_components_plan.h) -- the table has room for COMPONENTS_TABLE_FIRST components (or every point's, if
+    fewer) and never less.  The cut before they are counted: components = 1"""
+    points = lattice_points(dims)
+    table = max(min(points, COMPONENTS_TABLE_FIRST), components) * COMPONENT_BYTES
+    return stage_total([0 if own_lattice else points * 4, points * 4, (points + 1) * 4, _scan_sum_words(points + 1) * 4, COMPONENT_RESULT_BYTES, table])
+
+
 def _smallest(past):
     n = 1
     while not past(n):
@@ -170,6 +203,7 @@ def _smallest(past):
 
 BIG_LATTICE = (_smallest(lambda n: workspace_bytes((n, n, n)) > KEEP),) * 3          # the smallest cube of cells whose workspace is past the keep
 BIG_SURVEY = (_smallest(lambda n: survey_workspace_bytes((n, n, n)) > KEEP),) * 3    # ... whose survey's workspace is
+BIG_COMPONENTS = (_smallest(lambda n: components_workspace_bytes((n, n, n), False, 1) > KEEP),) * 3  # ... whose labelling's workspace is
 BIG_SLICE_LAYERS = 8
 BIG_SLICE = (_smallest(lambda n: slice_workspace_bytes((n, n), BIG_SLICE_LAYERS) > KEEP),) * 2  # the smallest square stack of 8 layers likewise
 
@@ -469,7 +503,7 @@ class _Gen:
         st = self.state
         if len(self.steps) > 1:
             self.want_pairs.discard((self.steps[-2]["family"], family))
-        if family != "measure" or params.get("columns"):  # (without `columns` a measure answers into its host record alone)
+        if has_form(s):
             self.want_forms.discard((family, host, st["fif"]))
         if st["debug"]:
             self.want_debug.discard(family)
@@ -567,6 +601,12 @@ class _Gen:
             axis = vary("measure axis", AXES + ("tilted",))
             grid = measure_grid(lattice(scene, rng), rng.choice(AXES), nu, nv, 0.3) if axis == "tilted" else measure_grid(lattice(scene, rng), axis, nu, nv)
             return self.new(i, family, "measure", changes, host, grid=grid, axis=axis, columns=vary("columns", yes_no), march=vary("measure march", tuple(MEASURE_PARAMS)))
+        if family == "components":
+            call = vary("components", COMPONENT_CALLS)
+            more = dict(labels=vary(call + " labels", yes_no), capacity=vary(call + " capacity", CAPACITY_RULES))
+            if call == "labelLattice":
+                return self.new(i, family, call, changes, host, dims=lattice(scene, rng)["dims"], kind=vary("synthetic", SYNTHETIC_KINDS), **more)
+            return self.new(i, family, call, changes, host, lattice=lattice(scene, rng), **more)
         assert family == "failed"
         # the failed calls of all seeds are numbered slot, slot + seeds, ...: the kinds in turn, and a shared kind through the entries in turn,
         # the span entries first
@@ -669,6 +709,25 @@ class _Gen:
                 return self.new(i, "measure", "measure", changes, k == 4 or rng.random() < 0.5, name, grid=grid, axis=None, columns=True, march="finish")
             w, h = BIG_SPAN_FRAME
             return self.new(i, "spans", "pickSpans", changes, True, name, n=w * h, w=w, h=h, frame=True, max_spans=MAX_SPANS[-1], march="short")
+        if name == "components_grow":
+            # the labelling's growth of `mesh` in the middle of its call, on a handle that has lived, two frames in flight, every array in
+            # device form: a counting call past the keep (`mesh` is released at its end); a labelling of one component (`mesh` is now
+            # exactly the first cut at GROW_DIMS); a small extraction (its emit enqueued, reading `mesh`); a frame (the lanes swap); a
+            # checkerboard at GROW_DIMS, every point a component: the first cut fits what is there, so the host does not wait for the
+            # emit's event, then the call grows `mesh`, copies and frees the old buffer; a smaller extraction (reuses the grown one)
+            self.change("fif", 2, changes)
+            if k == 0:
+                lat = lattice(scene, rng, dims=BIG_COMPONENTS, cell=0.02)
+                return self.new(i, "components", "labelComponents", changes, False, name, lattice=lat, labels=False, capacity="none")
+            if k == 1:
+                return self.new(i, "components", "labelLattice", changes, False, name, dims=GROW_DIMS, kind="all_outside", labels=True, capacity="exact")
+            if k == 3:
+                w, h = rng.choice(FRAME_SIZES[3:])
+                return self.new(i, "render", "render", changes, False, name, w=w, h=h, fmt=hs.RGBA32F, stats=True, defer=True)
+            if k == 4:
+                return self.new(i, "components", "labelLattice", changes, False, name, dims=GROW_DIMS, kind="checkerboard", labels=True, capacity="exact", alone=True)
+            lat = lattice(scene, rng, dims={2: (11, 9, 10), 5: (7, 8, 6)}[k])
+            return self.new(i, "mesh", "extractMesh", changes, False, name, lattice=lat, normals=True, form=None, defer=k == 2)
         assert name == "scene_change"
         # device work enqueued, then a scene change with no sync of the test's own: the answers are those of the scene of the call.  To
         # the run-time scene, STRETCH free steps on it, and from it again
@@ -719,9 +778,19 @@ def transitions(steps):
     return {(a["family"], b["family"]) for a, b in zip(steps, steps[1:])}
 
 
+def has_form(s):
+    """whether on_host decides where an array of the step lives: a measure's `columns` (without them it answers into its host record
+    alone), a labelling's lattice, records or labels (the counting call of the scene's own distances without labels has none)"""
+    if s["family"] == "measure":
+        return bool(s.get("columns"))
+    if s["family"] == "components":
+        return s["call"] == "labelLattice" or s["labels"] or s["capacity"] != "none"
+    return True
+
+
 def forms(steps):
-    """{(family, host, frames in flight)}; a measure counts only with `columns`, the one array whose place on_host decides"""
-    return {(s["family"], s["host"], s["state"]["fif"]) for s in steps if s["family"] != "failed" and (s["family"] != "measure" or s["columns"])}
+    """{(family, host, frames in flight)} of the steps with an array whose place on_host decides (has_form)"""
+    return {(s["family"], s["host"], s["state"]["fif"]) for s in steps if s["family"] != "failed" and has_form(s)}
 
 
 def on_runtime_scene(steps):
@@ -747,9 +816,12 @@ def failure_kinds(steps):
 
 def oracle_checkable(s):
     """whether the GPU tier can hold a step's reference answer against the CPU oracle: a built-in scene (the oracle has no run-time
-    scene), and no counting call over a lattice of millions of points, which numpy would take too long for"""
-    large = s["call"] == "countMesh" or (s["block"] == "large_new" and s["call"] in ("surveyMesh", "countSlices"))
-    return s["family"] != "failed" and s["state"]["scene"] != hs.RUNTIME_SCENE and not large
+    scene; a labelling of the caller's lattice needs none), and no counting call over a lattice of millions of points, which numpy
+    would take too long for; and a step whose answers are read at once (the GPU tier checks a step when it reads it, and reads the
+    deferred ones of a block together)"""
+    large = s["call"] == "countMesh" or (s["block"] == "large_new" and s["call"] in ("surveyMesh", "countSlices")) or \
+        (s["block"] == "components_grow" and s["call"] == "labelComponents")
+    return s["family"] != "failed" and (s["state"]["scene"] != hs.RUNTIME_SCENE or s["call"] == "labelLattice") and not large and not s.get("defer")
 
 
 def runtime_entries(steps):

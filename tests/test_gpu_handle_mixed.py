@@ -1,18 +1,19 @@
 """GPU tier: one renderer handle through seeded sequences of MIXED calls (tests/handle_mixed_sequences.py): renders, anti-aliased
-frames, post-processing, every query family, mesh extraction (plain and sharp), atlas calls, surveys and fits, slices, span queries
-and measures, host and device form, one and two frames in flight, built-in scenes and one compiled at run time, the debug plane on
+frames, post-processing, every query family, mesh extraction (plain and sharp), atlas calls, surveys and fits, slices, span queries,
+measures and component labellings, host and device form, one and two frames in flight, built-in scenes and one compiled at run time, the debug plane on
 and off, failed calls in between.
 
 Every step runs on ONE handle, through the C entry points, into buffers of the test's own: pre-filled with a sentinel no call
 produces and a guard tail of 256 bytes behind them.  After every step every output array equals, bit for bit, what a reference
 handle answers for the same state and inputs (one handle per scene, configured in full for every answer: one frame in flight, the
 default launch mode, host form); no sentinel is left in what the call owns, the guard tail and what the call does not own are
-untouched (the rows of a mesh or of a slice extraction past its counts are not the call's; the span slots past an item's spans are,
-and are zeros); and after a query, an extraction, an atlas call, a survey, a slice, span or measure call or a failed call
+untouched (the rows of a mesh or of a slice extraction past its counts are not the call's, nor are a labelling's records past its
+components, or any of them where the capacity is short of the components; the span slots past an item's spans are, and are zeros);
+and after a query, an extraction, an atlas call, a survey, a slice, span or measure call, a labelling or a failed call
 sdfr_get_stats still reports the last frame.  With two frames in flight device answers are read after sdfr_sync, as include/sdfr.h
 tells a caller to, and nowhere else does the test synchronise the handle.  About one step in eight has its reference answer checked
-against the CPU oracle -- slices, measures, surveys, fits and sharp vertices whole, the rest on a stride sample --, every family at
-least once per seed."""
+against the CPU oracle -- slices, measures, surveys, fits, sharp vertices and labellings whole, the rest on a stride sample --, every
+family at least once per seed."""
 import ctypes
 import math
 import time
@@ -213,6 +214,8 @@ class Call:
             result = self.record("result", sp.MeasureResult)
             columns = self.out("columns", 10 * g["nu"] * g["nv"]) if s["columns"] else None
             return self.go(L.sdfr_measure, h, ctypes.byref(grid), ctypes.byref(params), result, columns, oh)
+        if call in hm.COMPONENT_CALLS:
+            return self.components(r, sp, s, inp, oh, ov, null)
         if call in ("atlasTexels", "bakeAtlas"):
             pos, nrm, idx = inp["mesh"]
             atlas = sp.atlasLayout(len(idx), s["tile"], s["width"])
@@ -285,6 +288,27 @@ class Call:
         assert (again.vertices, again.segments) == (v, n)
         self.bufs.update({k: b for k, b in (("layer_vertices of the filling call", lv), ("layer_segments of the filling call", ls)) if b is not None})
         return rc
+
+    def components(self, r, sp, s, inp, oh, ov, null):
+        """sdfr_components_label, or for labelLattice sdfr_components_label_lattice of inp["lattice"], with the capacity of the step's rule:
+        C (inp["components"]) is the count the reference handle answered.  The counts record and all labels are the call's, and the first
+        C records where the rule lets it fill them; the records past C, and all of a call whose capacity is short of C, are not"""
+        L, h = r._L, r._h
+        dims = hm.component_dims(s)
+        rule, C = s["capacity"], inp.get("components", 0)
+        if rule == "short" and C == 1:
+            rule = "exact"
+        capacity = {"none": 0, "exact": C, "roomy": C + 3, "short": C - 1}[rule]
+        records = self.out("records", 10 * capacity, owned=10 * C if rule in ("exact", "roomy") else 0) if rule != "none" else None
+        labels = self.out("labels", hm.lattice_points(dims)) if s["labels"] else None
+        counts = self.record("counts", sp.ComponentCounts)
+        capacity = ov.get("capacity", capacity)
+        if s["call"] == "labelLattice":
+            D, iso = inp["lattice"]
+            grid = sp.MeshGrid((ctypes.c_float * 3)(0.0, 0.0, 0.0), 1.0, dims[0], dims[1], dims[2], iso)
+            return self.go(L.sdfr_components_label_lattice, h, ctypes.byref(grid), self.inp(D, null), capacity, records, labels, counts, oh)
+        grid = _grid(s["lattice"])
+        return self.go(L.sdfr_components_label, h, ctypes.byref(grid), capacity, records, labels, counts, oh)
 
     def composed(self, r, s, host):
         """extractMesh(surfaces= / occlusion= / lighting= / atlas=, sharp=): the wrapper's own composition, arrays of its own making"""
@@ -418,6 +442,12 @@ class References:
         if call in ("atlasTexels", "bakeAtlas"):
             src = steps[s["src"]] if s.get("src") is not None else s
             inp["mesh"] = self.mesh(s, src["state"], src["lattice"])
+        if call == "labelLattice":
+            import handle_mixed_oracle as ho
+
+            inp["lattice"] = ho.synthetic_lattice(s)
+        if call in hm.COMPONENT_CALLS and s["capacity"] != "none":  # the capacity rules go by the count of the counting call
+            inp["components"] = int(self.pseudo(s, capacity="none", labels=False)["counts"].view(np.int64)[0])
         if call == "postprocess":
             src = steps[s["src"]]
             img = self.pseudo(src, call="render", fmt=hs.RGBA16F, stats=False)["image"]
@@ -466,6 +496,19 @@ class References:
 
         oracle, st, scene, call = self.oracle, s["state"], s["state"]["scene"], s["call"]
         want = self.answer(s, steps)
+        if call in hm.COMPONENT_CALLS:  # whole, every value an integer: the definition on the oracle's distances, or on the caller's lattice itself (no scene needed)
+            import components_util as cu
+
+            what = ("oracle", s["i"], call, scene)
+            counts, records, labels = ho.components(s, None if call == "labelLattice" else self.frame(s, *_camera_size(s)))
+            assert np.array_equal(want["counts"].view(np.int64), np.array([counts[k] for k in cu.COUNT_KEYS], np.int64)), (what, counts)
+            C, rule = counts["components"], s["capacity"]
+            if rule != "none":
+                filled = rule in ("exact", "roomy") or C == 1
+                assert np.array_equal(want["records"], records.view(np.uint32).reshape(-1) if filled else np.zeros(0, np.uint32)), (what, "records")
+            if s["labels"]:
+                assert np.array_equal(want["labels"], labels.reshape(-1)), (what, "labels")
+            return
         inp = self.inputs(s, steps)
         w, h = _camera_size(s)
         of = self.frame(s, w, h)
@@ -728,6 +771,17 @@ def _fail(r, refs, steps, s, keep, where):
         c = Call(r, dict(s, call="surveyMesh", band=0.0), {}, host, override=dict(band=-1.0))
     elif kind == "fit_bad_margin":
         c = Call(r, dict(s, call="fitMesh", levels=2, margin=1), {}, host, override=dict(margin=9))
+    elif kind in ("components_negative_capacity", "components_small_capacity", "components_null_lattice"):
+        # through either entry (the null lattice through the lattice entry): the scene's distances on the step's lattice, or noise of its dims
+        own = kind == "components_null_lattice" or s["seed"] % 2 == 0
+        small = kind == "components_small_capacity"  # (without labels: a call short of capacity writes them all the same)
+        q = dict(s, call="labelLattice" if own else "labelComponents", dims=s["lattice"]["dims"], kind="noise", labels=not small, capacity="short" if small else "exact")
+        inp = refs.inputs(q, steps)
+        assert inp["components"] >= 2
+        c = Call(r, q, inp, host, override={} if small else dict(capacity=-1) if kind == "components_negative_capacity" else dict(null=True))
+        if small:  # "SDFR_OK with the counts": the counts record is the one thing written
+            status = OK
+            assert np.array_equal(c.bufs.pop("counts").read((where, "counts")), refs.pseudo(q, capacity="none", labels=False)["counts"]), (where, "counts")
     elif kind in ("aa_factor_3", "aa_bad_format"):
         q = dict(s, call="renderAA", factor=2, fmt=hs.RGBA32F, stats=True)
         c = Call(r, q, {}, host, override=dict(factor=3) if kind == "aa_factor_3" else dict(fmt=7))
@@ -858,7 +912,7 @@ def _every_entry(r, host):
     o, d = hm.rays(s0)
     quad = (np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], np.float32), np.array([[0, 0, 1]] * 4, np.float32), np.array([[0, 1, 2], [0, 2, 3]], np.uint32))
     inp = dict(origins=np.array(o, np.float32), dirs=np.array(d, np.float32), points=np.array(hm.points(s0), np.float32), normals=np.array(hm.normals(s0), np.float32),
-               pixels=np.array(hm.pixel_list(s0), np.int32), hits=np.zeros((65, 12), np.uint32), mesh=quad)
+               pixels=np.array(hm.pixel_list(s0), np.int32), hits=np.zeros((65, 12), np.uint32), mesh=quad, components=4)
     calls = [dict(call="render", fmt=hs.RGBA32F, stats=True), dict(call="renderAA", factor=2, fmt=hs.RGBA32F, stats=True), dict(call="queryDistance", normals=True),
              dict(call="queryRays"), dict(call="pick"), dict(call="queryRaySurfaces", hits=True, frame=False), dict(call="pickSurfaces", hits=True, frame=False),
              dict(call="pickSurfaces", hits=True, frame=True, n=16 * 9), dict(call="meshSurfaces", hits=True), dict(call="queryOcclusion"), dict(call="hitOcclusion"),
@@ -866,7 +920,7 @@ def _every_entry(r, host):
              dict(call="pickLighting", hits=True, lights=True, frame=True, n=16 * 9), dict(call="meshLighting", hits=True, lights=True), dict(call="countMesh"),
              dict(call="bakeAtlas"), dict(call="countMesh", form="sharp"), dict(call="surveyMesh"), dict(call="fitMesh"), dict(call="countSlices"),
              dict(call="querySpans", frame=False), dict(call="pickSpans", frame=False), dict(call="pickSpans", frame=True, n=16 * 9), dict(call="meshSpans"),
-             dict(call="measure")]
+             dict(call="measure"), dict(call="labelComponents", labels=True, capacity="roomy")]
     assert len({(q["call"], q.get("form")) for q in calls if q["call"] in ("countMesh", "surveyMesh", "fitMesh", "countSlices", "querySpans", "pickSpans", "meshSpans",
                                                                             "measure")} - {("countMesh", None)}) == 8
     for q in calls:
@@ -875,9 +929,12 @@ def _every_entry(r, host):
 
 def test_before_any_scene_every_entry_fails_and_writes_nothing():
     """a new handle has no scene: every scene-dependent entry point of every family returns SDFR_ERR_NO_SCENE and writes nothing, in
-    host and in device form; sdfr_atlas_texels, which looks at the mesh alone, works"""
+    host and in device form; sdfr_atlas_texels, which looks at the mesh alone, and sdfr_components_label_lattice, which looks at the
+    caller's lattice alone, work and equal their definitions"""
     import sdf_playground_amd as sp
     import atlas_util as au
+    import components_util as cu
+    import handle_mixed_oracle as ho
 
     r = sp.SDFRenderer(0)
     try:
@@ -897,6 +954,15 @@ def test_before_any_scene_every_entry_fails_and_writes_nothing():
             P, N, valid = au.oracle_texels(*inp["mesh"], 4, 64)
             assert np.array_equal(got["valid"].view(np.int32), valid.reshape(-1))
             assert np.array_equal(got["texel_positions"], P.reshape(-1).view(np.uint32)) and np.array_equal(got["texel_normals"], N.reshape(-1).view(np.uint32))
+            q = dict(q, call="labelLattice", dims=(9, 7, 6), kind="hollow_box", labels=True, capacity="roomy")
+            counts, records, labels = ho.components(q)
+            assert counts["components"] == 3 and counts["closed_voids"] == 1  # the void around the box, the box, the void inside it
+            c = Call(r, q, dict(lattice=ho.synthetic_lattice(q), components=counts["components"]), host)
+            assert c.rc == OK, (c.rc, r._L.sdfr_last_error(r._h))
+            r.sync()
+            got = c.answers(r, "labelLattice without a scene")
+            assert np.array_equal(got["counts"].view(np.int64), np.array([counts[k] for k in cu.COUNT_KEYS], np.int64))
+            assert np.array_equal(got["records"], records.view(np.uint32).reshape(-1)) and np.array_equal(got["labels"], labels.reshape(-1))
         with pytest.raises(sp.SdfrError) as e:
             r.getStats()
         assert e.value.code == ERR_INVALID_ARGUMENT
@@ -932,9 +998,10 @@ def test_atlas_openness_with_two_frames_in_flight(device):
 @pytest.mark.parametrize("device", (False, True))
 def test_sync_calls_wait_for_the_other_lanes_emit(device):
     """Two frames in flight: a device sharp extraction (its emit and sharp-vertex work enqueued, reading the lattice in `mesh`), a
-    frame (the lanes swap), then at once a measure and a survey on the other lane, both synchronous and both writing `mesh`, with no
-    sync of the test's own.  After sdfr_sync the mesh is the mesh of a handle that did nothing else, and the measure and the survey
-    are a fresh handle's; the measure's columns in host and in device form."""
+    frame (the lanes swap), then at once a measure, a survey and a labelling on the other lane, all synchronous and all writing
+    `mesh`, with no sync of the test's own.  After sdfr_sync the mesh is the mesh of a handle that did nothing else, and the measure,
+    the survey and the labelling are a fresh handle's; the measure's columns in host and in device form, the labelling's records and
+    labels in the other one."""
     import torch
     import sdf_playground_amd as sp
 
@@ -942,7 +1009,10 @@ def test_sync_calls_wait_for_the_other_lanes_emit(device):
     st = dict(scene="labyrinth", t=0.7)
     steps = [dict(i=0, call="extractMesh", form="sharp", normals=True, lattice=lat, state=st),
              dict(i=1, call="measure", grid=hm.measure_grid(dict(lat, dims=(9, 9, 9)), "y", 9, 8), columns=True, march="finish", state=st),
-             dict(i=2, call="surveyMesh", lattice=dict(lat, dims=(12, 12, 12), cell=0.26), band=0.13, state=st)]
+             dict(i=2, call="surveyMesh", lattice=dict(lat, dims=(12, 12, 12), cell=0.26), band=0.13, state=st),
+             dict(i=3, call="labelComponents", lattice=dict(lat, dims=(12, 12, 12), cell=0.26), labels=True, capacity="exact", state=st)]
+    # (the labelling's workspace fits into the extraction's: it lands inside what the emit still reads)
+    assert hm.components_workspace_bytes((12, 12, 12), False, 1) < hm.workspace_bytes(lat["dims"])
 
     def handle(fif):
         r = sp.SDFRenderer(0)
@@ -952,16 +1022,21 @@ def test_sync_calls_wait_for_the_other_lanes_emit(device):
         gu.orbit_camera(r, "labyrinth", 0.7, 96, 64)
         return r
 
-    want = []
+    want, inp = [], {}
     for s in steps:  # each from a handle that does nothing else
         r = handle(1)
         try:
-            c = Call(r, s, {}, True)
+            if s["call"] == "labelComponents":  # the capacity is the count of the counting call
+                c = Call(r, dict(s, labels=False, capacity="none"), {}, True)
+                assert c.rc == OK
+                inp = dict(components=int(c.answers(r, ("fresh", "count"))["counts"].view(np.int64)[0]))
+            c = Call(r, s, inp, True)
             assert c.rc == OK
             r.sync()
             want.append(c.answers(r, ("fresh", s["call"])))
         finally:
             r.close()
+    assert inp["components"] >= 2 and want[3]["records"].size == 10 * inp["components"]
     assert want[0]["counts"][0] > 500 and sp.MeshSurvey.from_buffer_copy(want[2]["survey"].tobytes()).active_cells > 0
     assert sp.MeasureResult.from_buffer_copy(want[1]["result"].tobytes()).columns_hit >= 8
 
@@ -972,9 +1047,10 @@ def test_sync_calls_wait_for_the_other_lanes_emit(device):
         r.render(width=96, height=64, out=image)  # the lanes swap
         measure = Call(r, steps[1], {}, not device)
         survey = Call(r, steps[2], {}, False)
-        assert (mesh.rc, measure.rc, survey.rc) == (OK, OK, OK)
+        label = Call(r, steps[3], inp, device)
+        assert (mesh.rc, measure.rc, survey.rc, label.rc) == (OK, OK, OK, OK)
         r.sync()
-        for c, ref, name in ((mesh, want[0], "mesh"), (measure, want[1], "measure"), (survey, want[2], "survey")):
+        for c, ref, name in ((mesh, want[0], "mesh"), (measure, want[1], "measure"), (survey, want[2], "survey"), (label, want[3], "labelling")):
             _same((name, "after the other lane's emit"), c.answers(r, name), ref)
     finally:
         r.close()

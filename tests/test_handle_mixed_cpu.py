@@ -1,7 +1,10 @@
-"""CPU tier of the mixed handle sequences (tests/handle_mixed_sequences.py): the committed seeds cover what they are there to cover.
-The GPU tier (tests/test_gpu_handle_mixed.py) runs them."""
+"""CPU tier of the mixed handle sequences (tests/handle_mixed_sequences.py): the committed seeds cover what they are there to cover,
+the component labelling included -- both calls, every capacity rule and synthetic lattice, and the block in which the labelling grows
+the workspace in the middle of its call, whose bytes are followed here by the plan's formulas, themselves held against the library's
+plan.  The GPU tier (tests/test_gpu_handle_mixed.py) runs them."""
 import numpy as np
 
+import handle_mixed_oracle as ho
 import handle_mixed_sequences as hm
 import handle_sequences as hs
 
@@ -27,16 +30,16 @@ def test_deterministic_per_seed_and_seeds_differ():
 
 
 def test_every_ordered_pair_of_families_is_a_pair_of_consecutive_steps():
-    """all 16 x 16 but (failed, failed): a failed call always sits between two valid calls"""
-    assert len(hm.FAMILIES) == 16 and len(hm.PAIRS) == 255 and len(set(hm.FAMILIES)) == 16
-    assert set(hm.FAMILIES) >= {"survey", "slices", "spans", "measure"}
+    """all 17 x 17 but (failed, failed): a failed call always sits between two valid calls"""
+    assert len(hm.FAMILIES) == 17 and len(hm.PAIRS) == 288 and len(set(hm.FAMILIES)) == 17
+    assert set(hm.FAMILIES) >= {"survey", "slices", "spans", "measure", "components"}
     seen = set().union(*(hm.transitions(steps) for steps in SEQUENCES.values()))
     assert not set(hm.PAIRS) - seen, sorted(set(hm.PAIRS) - seen)
 
 
 def test_every_family_in_host_and_device_form_with_one_and_two_frames_in_flight():
     """(postprocess takes device tensors only, a survey and a fit answer into a host record: no host form and no device form; a
-    measure counts with `columns` alone)"""
+    measure counts with `columns` alone, a labelling with a lattice of the caller's, records or labels)"""
     seen = set().union(*(hm.forms(steps) for steps in SEQUENCES.values()))
     assert set(hm.HOST_AND_DEVICE) == set(hm.FAMILIES) - {"post", "survey", "failed"}
     want = {(f, host, fif) for f in hm.HOST_AND_DEVICE for host in (False, True) for fif in (1, 2)}
@@ -45,6 +48,12 @@ def test_every_family_in_host_and_device_form_with_one_and_two_frames_in_flight(
     assert all(s["columns"] for s in ALL if s["family"] == "measure" and (s["family"], s["host"], s["state"]["fif"]) in hm.forms([s]))
     assert {(s["host"], s["state"]["fif"]) for s in ALL if s["call"] == "measure" and s["columns"]} == {(h, f) for h in (False, True) for f in (1, 2)}
     assert all(s["family"] in hm.FAMILIES for s in ALL)
+    assert "components" in hm.HOST_AND_DEVICE
+    for s in ALL:
+        if s["family"] == "components":
+            assert hm.has_form(s) == (s["call"] == "labelLattice" or s["labels"] or s["capacity"] != "none"), s
+    for call in hm.COMPONENT_CALLS:  # each of the two entries by itself, wherever its arrays live
+        assert {(s["host"], s["state"]["fif"]) for s in ALL if s["call"] == call and hm.has_form(s)} == {(h, f) for h in (False, True) for f in (1, 2)}, call
 
 
 def test_every_call_and_variant_of_the_families_occurs():
@@ -52,7 +61,7 @@ def test_every_call_and_variant_of_the_families_occurs():
     assert calls >= {"render", "renderAA", "postprocess", "queryDistance", "queryRays", "pick", "queryRaySurfaces", "pickSurfaces", "meshSurfaces",
                      "queryOcclusion", "hitOcclusion", "queryRayLighting", "pickLighting", "meshLighting", "extractMesh", "countMesh", "atlasTexels",
                      "bakeAtlas", "renderPrivateStrips", "failed", "surveyMesh", "fitMesh", "extractSlices", "countSlices", "querySpans", "pickSpans",
-                     "meshSpans", "measure"}
+                     "meshSpans", "measure", "labelComponents", "labelLattice"}
     for call in ("pickSurfaces", "pickLighting", "pickSpans"):
         assert {bool(s.get("frame")) for s in ALL if s["call"] == call} == {False, True}, call  # a pixel list, and None = the whole frame
     for call, key in (("render", "stats"), ("renderAA", "stats"), ("queryDistance", "normals"), ("queryRaySurfaces", "hits"), ("pickLighting", "hits"),
@@ -94,6 +103,18 @@ def test_every_call_and_variant_of_the_families_occurs():
     assert {s["march"] for s in measures} == {"finish", "short"} and all(ms <= 128 for _m, ms in hm.MEASURE_PARAMS.values())
     for s in measures:
         assert sum(1 for x in s["grid"]["dw"] if x != 0.0) == (2 if s["axis"] == "tilted" else 1), s
+    # the labelling: both calls, each with and without labels and under all four capacity rules; every synthetic kind
+    labellings = [s for s in free if s["family"] == "components"]
+    assert set(hm.CAPACITY_RULES) == {"none", "exact", "roomy", "short"} and set(hm.COMPONENT_CALLS) == {"labelComponents", "labelLattice"}
+    assert {(s["call"], s["labels"]) for s in labellings} == {(c, l) for c in hm.COMPONENT_CALLS for l in (False, True)}
+    assert {(s["call"], s["capacity"]) for s in labellings} == {(c, r) for c in hm.COMPONENT_CALLS for r in hm.CAPACITY_RULES}
+    assert {(s["labels"], s["capacity"]) for s in labellings} == {(l, r) for l in (False, True) for r in hm.CAPACITY_RULES}
+    assert {s["kind"] for s in labellings if s["call"] == "labelLattice"} == set(hm.SYNTHETIC_KINDS) >= {"noise", "checkerboard", "serpentine", "hollow_box", "zeros"}
+    for s in labellings:
+        assert ("lattice" in s) == (s["call"] == "labelComponents") and ("dims" in s) == (s["call"] == "labelLattice"), s
+        if s["call"] == "labelLattice":
+            D, iso = ho.synthetic_lattice(s)
+            assert D.shape == tuple(n + 1 for n in reversed(s["dims"])) and D.dtype == np.float32 and iso == 0.0, s
 
 
 def test_every_seed_has_every_family_where_the_oracle_can_check_it():
@@ -114,10 +135,10 @@ def test_every_family_on_the_run_time_scene_and_with_the_debug_plane():
         assert flips >= 4
 
 
-def test_each_seed_has_the_seven_scripted_blocks():
+def test_each_seed_has_the_eight_scripted_blocks():
     for seed, steps in SEQUENCES.items():
         b = hm.blocks(steps)
-        assert sorted(b) == ["aa_in_flight", "lanes", "large_mesh", "large_new", "scene_change", "staging", "workspace_cuts"] == sorted(hm.BLOCKS), seed
+        assert sorted(b) == ["aa_in_flight", "components_grow", "lanes", "large_mesh", "large_new", "scene_change", "staging", "workspace_cuts"] == sorted(hm.BLOCKS), seed
         for name, part in b.items():
             if name == "scene_change":  # its scripted steps are the first two and the last two, free steps on the run-time scene between them
                 first, end = part[0]["i"], part[0]["i"] + hm.BLOCK_STEPS[name]
@@ -202,9 +223,56 @@ def test_each_seed_has_the_seven_scripted_blocks():
         assert hm.staging_bytes(dict(px, n=(w - 8) * h)) <= hm.KEEP or hm.staging_bytes(dict(px, n=w * (h - 8))) <= hm.KEEP  # no smaller frame of whole tiles
         assert m2["host"] and m2["columns"] and 0 < hm.staging_bytes(m2) < 1 << 20
 
+        # 8: the labelling grows `mesh` in the middle of its call, behind the other lane's enqueued emit work.  `mesh.bytes` through the
+        # block: sdfr_device_buffer::reserve allocates exactly what is asked for and never shrinks, release_large frees past the keep
+        count, one, m1, frame, many, m2 = b["components_grow"]
+        assert [s["call"] for s in (count, one, m1, frame, many, m2)] == ["labelComponents", "labelLattice", "extractMesh", "render", "labelLattice", "extractMesh"]
+        assert all(s["state"]["fif"] == 2 and not s["host"] for s in (count, one, m1, frame, many, m2))
+        assert [bool(s.get("defer")) for s in (count, one, m1, frame, many, m2)] == [False, False, True, True, False, False]
+        assert many.get("alone") and not m2.get("alone")  # the labelling is synchronous and read at once, the deferred answers after the last call's sync
+        assert (count["capacity"], count["labels"]) == ("none", False) and (many["capacity"], many["labels"]) == ("exact", True) and one["labels"]
+        n = count["lattice"]["dims"][0]
+        assert count["lattice"]["dims"] == (n, n, n) == hm.BIG_COMPONENTS and 170 <= n <= 180 and count["lattice"]["cell"] == 0.02
+        assert hm.components_workspace_bytes((n, n, n), False, 1) > hm.KEEP >= hm.components_workspace_bytes((n - 1,) * 3, False, 1)
+        assert one["dims"] == many["dims"] == hm.GROW_DIMS == (47, 47, 31) and (one["kind"], many["kind"]) == ("all_outside", "checkerboard")
+        points = 48 * 48 * 32
+        assert ho.components(one)[0]["components"] == 1 and ho.components(many)[0]["components"] == points == 73728 > hm.COMPONENTS_TABLE_FIRST == 65536
+        mesh_bytes = 0                                                            # after the counting call: past the keep, released
+        first = hm.components_workspace_bytes(one["dims"], True, 1)
+        mesh_bytes = max(mesh_bytes, first)                                       # after the labelling of one component ...
+        assert mesh_bytes == first == hm.components_workspace_bytes(many["dims"], True, 1) == 3214848  # ... exactly the first cut of the checkerboard's
+        assert first == 2 * 294912 + 256 + 1280 + 2048 + 65536 * 40               # parent, scan (one word more: one piece more of 256 bytes), sums, result, table
+        assert hm.workspace_bytes(m1["lattice"]["dims"]) < mesh_bytes             # the extraction whose emit is enqueued: `mesh` stays
+        grown = hm.components_workspace_bytes(many["dims"], True, points)
+        assert mesh_bytes < grown == first + (points - 65536) * 40 == 3542528 <= hm.KEEP  # the second cut: larger, the growth in the middle of the call
+        mesh_bytes = max(mesh_bytes, grown)
+        assert hm.workspace_bytes(m2["lattice"]["dims"]) < mesh_bytes and m1["lattice"]["dims"] != m2["lattice"]["dims"]
+
         assert any(part[0]["state"]["fif"] == 2 for part in b.values())
     kinds = {hm.blocks(steps)["scene_change"][2]["call"] for steps in SEQUENCES.values()}
     assert kinds == {"queryRaySurfaces", "querySpans"}  # the call in flight on the run-time scene when it goes: both kinds
+
+
+def test_the_restated_components_plan_is_the_librarys():
+    """components_workspace_bytes and the labelling's staging_bytes against sdfr_components_plan.h itself, built for the CPU
+    (tests/cpp/components_plan_host.cpp): the free sizes' extremes, a lattice that is no cube, the block's dims before and after the
+    growth and around the 65536 components the table first has room for, and the cube past the keep with its neighbour below"""
+    import components_util as cu
+
+    n = hm.BIG_COMPONENTS[0]
+    cases = [(dims, own, C) for dims in ((5, 5, 5), (24, 24, 24), (7, 23, 14), hm.GROW_DIMS, (n, n, n), (n - 1,) * 3) for own in (0, 1)
+             for C in (1, 2, 65535, 65536, 65537, 73728) if C <= hm.lattice_points(dims)]
+    line = "1 0.0 0.0 0.0 1.0 %d %d %d 0.0 %d %d %d %d %d 1 1 %d"  # (the format: tests/cpp/components_plan_host.cpp)
+    answers = cu.run_plan([line % (dims + (own, own, C, 1, labels, C)) for dims, own, C in cases for labels in (0, 1)])
+    assert len(answers) == 2 * len(cases)
+    for k, (dims, own, C) in enumerate(cases):
+        for labels in (0, 1):
+            fields = answers[2 * k + labels].split(";")
+            assert fields[0] == "0" and int(fields[-1]) == hm.components_workspace_bytes(dims, bool(own), C), (dims, own, C)
+            first = int(fields[-1]) if C <= hm.COMPONENTS_TABLE_FIRST else hm.components_workspace_bytes(dims, bool(own), 1)
+            assert sum(-(-int(w) // 256) * 256 for w in fields[5].split()) == first == hm.components_workspace_bytes(dims, bool(own), 1)  # the cut before they are counted
+            step = dict(call="labelLattice" if own else "labelComponents", lattice=dict(dims=dims), dims=dims, labels=bool(labels))
+            assert hm.staging_bytes(step) == sum(-(-int(b) // 256) * 256 for b in fields[6].split()), (dims, own, labels)
 
 
 def hs_private_rows(height, split):
@@ -214,7 +282,8 @@ def hs_private_rows(height, split):
 
 def test_every_failure_kind_and_each_between_two_valid_calls():
     assert set().union(*(hm.failure_kinds(steps) for steps in SEQUENCES.values())) == set(hm.FAILURE_KINDS)
-    assert len(hm.FAILURE_KINDS) == 14
+    assert len(hm.FAILURE_KINDS) == 17
+    assert [dict(hm.FAILURES)[k] for k in ("components_negative_capacity", "components_small_capacity", "components_null_lattice")] == ["negative capacity", None, "null pointer"]
     assert dict(hm.FAILURES)["slice_negative_capacity"] == "negative capacity" and dict(hm.FAILURES)["slice_small_capacity"] is None
     assert [dict(hm.FAILURES)[k] for k in ("span_max_spans_65", "measure_nu_0", "survey_bad_band", "fit_bad_margin")] == [
         "bad span parameters", "bad measure grid", "band must be finite and >= 0", "margin must be 0..8"]
@@ -240,6 +309,8 @@ def test_sizes_outside_the_scripted_blocks_are_the_smallest_that_cross_the_edges
             assert s["w"] <= 160 and s["h"] <= 90
         if "lattice" in s:
             assert max(s["lattice"]["dims"]) <= (hm.MAX_FIT if s["call"] == "fitMesh" else hm.MAX_LATTICE) and hm.MAX_FIT <= 64
+        if "dims" in s:
+            assert s["call"] == "labelLattice" and 5 <= min(s["dims"]) and max(s["dims"]) <= hm.MAX_LATTICE <= 24  # at most 25^3 points
         if "slices" in s:
             assert max(s["slices"]["dims"]) <= 24 and 1 <= s["slices"]["layers"] <= 8
         if s["family"] == "spans" and s.get("frame"):
@@ -265,6 +336,8 @@ def test_every_lattice_meets_the_surface():
     for s in ALL:
         if "lattice" not in s or s["state"]["scene"] == hs.RUNTIME_SCENE or s["call"] == "countMesh" or s["block"] == "large_new":
             continue
+        if s["block"] == "components_grow" and s["call"] == "labelComponents":  # millions of points: surface_condition() looks at their signs
+            continue
         src = SEQUENCES_OF[id(s)][s["src"]] if s["family"] == "atlas" and s["src"] is not None else s  # an atlas of an earlier step's mesh
         st, lat = src["state"], src["lattice"]
         if st["scene"] == hs.RUNTIME_SCENE:
@@ -276,10 +349,9 @@ def test_every_lattice_meets_the_surface():
 
 
 def surface_condition(s):
-    """What a step of the survey, the slices, the spans or the measure on a built-in scene meets of the surface, by the oracle's
-    distances in the step's state: (None, {}) if the step has nothing to meet, else (the condition it misses or None, what was seen)"""
-    import handle_mixed_oracle as ho
-
+    """What a step of the survey, the slices, the spans, the measure or the labelling on a built-in scene meets of the surface, by the
+    oracle's distances in the step's state: (None, {}) if the step has nothing to meet, else (the condition it misses or None, what
+    was seen)"""
     if s["state"]["scene"] == hs.RUNTIME_SCENE:
         return None, {}
     of = ho.frame(s, s.get("w") or 16, s.get("h") or 9)
@@ -306,17 +378,36 @@ def surface_condition(s):
     if call == "fitMesh":
         got = ho.fit(s, of)
         return (None if got["state"] == 1 else "a fit returns SDFR_FIT_FOUND"), dict(state=got["state"], dims=got["dims"])
+    if call == "labelComponents" and s["block"] == "components_grow":  # millions of points: a solid and a void = some point is inside and some is not
+        with np.errstate(invalid="ignore"):
+            inside = ho.lattice_distances(s, of) < 0
+        return (None if inside.any() and not inside.all() else "a labelling of the scene has a solid and a void"), {}
+    if call == "labelComponents":
+        counts = ho.components(s, of)[0]
+        missed = None if counts["solids"] >= 1 and counts["voids"] >= 1 else "a labelling of the scene has a solid and a void"
+        return missed, dict(components=counts["components"], short=counts["components"] if s["capacity"] == "short" else 0)
     return None, {}
+
+
+def components_seen(s):
+    """what a labelling step of the caller's lattice has, by the definition: needs no scene, so on the run-time scene too"""
+    counts = ho.components(s)[0]
+    return dict(components=counts["components"], short=counts["components"] if s["capacity"] == "short" else 0)
 
 
 def test_every_input_of_the_new_families_meets_the_surface():
     """conditions, not measurements: slices with contours, rays with crossings, columns that are hit, surveys with vertices, fits that
-    find -- every step of the committed seeds on a built-in scene, in its state (scene variables and the debug plane included); and over
-    all seeds some ray has more spans than are stored, some runs out of steps and some pixel is outside its frame"""
-    seen_all = dict(over=False, out_of_steps=False, invalid=False)
+    find, labellings of the scene with a solid and a void -- every step of the committed seeds on a built-in scene, in its state (scene
+    variables and the debug plane included); and over all seeds some ray has more spans than are stored, some runs out of steps, some
+    pixel is outside its frame, some labelling has three or more components and some with the capacity rule "short" has two or more
+    (with one it would fall back to "exact")"""
+    seen_all = dict(over=False, out_of_steps=False, invalid=False, three_components=False, short_of_two=False)
     for s in ALL:
         missed, seen = surface_condition(s)
         assert missed is None, (missed, s["i"], s["call"], s["state"]["scene"], s["state"]["vars"], s["state"]["debug"], seen)
+        if s["call"] == "labelLattice" and s["block"] is None:
+            seen = components_seen(s)
+        seen = dict(seen, three_components=seen.get("components", 0) >= 3, short_of_two=seen.get("short", 0) >= 2)
         for k in seen_all:
             seen_all[k] = seen_all[k] or bool(seen.get(k))
     assert all(seen_all.values()), seen_all
